@@ -8,14 +8,25 @@ HyperGsys/include/hgnnAgg.cuh) over one batch of synthetic input resident in
 HBM.  Workload (BASELINE.json configs[1], in the only form that leaves the
 256 MiB Infinity Cache -- SURVEY.md 8(d) "C2xK"): a batch of K = 1024
 cora-shape hypergraphs (N=2708, M=1579, nnz=4859 each) as one block-diagonal
-incidence matrix, feat_len = 32, fp32.  The single-hypergraph latency (the
-number the reference's result.xlsx reports) is printed in `single_graph`.
+incidence matrix, feat_len = 32, fp32.  With `--full`, the single-hypergraph latency
+(the number the reference's result.xlsx reports) is printed in `single_graph`.
 
-The timed output is checked: after the timed region Y is compared with the CPU
+A plain run (`--gpus N --steps K --warmup W`) does only what the headline needs: it builds the workload, warms up,
+times the K steps, writes the timed output if `--dump-outputs DIR` is given, and prints the final line (`value` in
+edges/s, `ms_per_step` = wall milliseconds of one timed step).  Everything else below -- the oracle and float64
+checks, the CPU baseline, the other configurations, the device-copy floor, the single-hypergraph latencies, the
+rocSPARSE comparator, the sharded section (N > 1) and the detail file -- runs only with `--full`.
+
+`--dump-outputs DIR`: after the timed steps, rank 0 writes what the last timed step returned, Y, as DIR/Y.npy
+(float32).  A Y larger than 48 MB is written as a fixed, seeded sample of its rows instead: DIR/Y_sampled_rows.npy,
+with the row indices in DIR/sampled_row_index.npy (float64).  The inputs are seeded, so two builds run with the same
+arguments can be compared output for output.
+
+With `--full` the timed output is checked: after the timed region Y is compared with the CPU
 oracle on the same input (`parity`), and a mismatch makes the run fail -- the
 reference never times an unchecked variant either (TRY, hgnnAgg.cuh:1159-1169).
 
-`configs` (N = 1): measured the same way in the same run -- the other five cells
+`configs` (N = 1, `--full`): measured the same way in the same run -- the other five cells
 of north_star's target matrix (cora / citeseer / pubmed shape x F = 32 / 128;
 pubmed-shape x64 at F = 128 is BASELINE config 3), config 3's MFMA path (the
 aggregation with the layer's 128 -> 128 linear folded in: hg_aggr_linear_f32,
@@ -27,7 +38,7 @@ the oracle and against a float64 answer (scipy) at 1e-5 * max(1, |ref|).
 N > 1: one process per GPU (torchrun).  Headline: the batch sharded by hyperedge
 group = by hypergraph, K graphs per rank (weak scaling); no vertex is shared
 between shards, so the data path has no collective and ranks meet in the barrier
-that brackets the timed region.  `strong_scaling` (beside it on the line; `sharded` in the detail file): ONE hypergraph (config 4)
+that brackets the timed region.  `strong_scaling` (`--full`; beside it on the line, `sharded` in the detail file): ONE hypergraph (config 4)
 cut into hyperedge groups across the ranks by hypergef_amd.dist.ShardedAggregator
 -- X replicated, each rank aggregates its hyperedges into a dense partial, one
 RCCL all-reduce (or reduce-scatter) of N*F*4 bytes over xGMI sums them: the
@@ -111,7 +122,18 @@ def parse(argv=None):
                    help="control flow only, no GPU and no kernels: launch, rendezvous over gloo, max over ranks, "
                         "the output line (tests/test_bench_line.py)")
     p.add_argument("--inject-exchange-error", action="store_true", help=argparse.SUPPRESS)
-    return p.parse_args(argv)
+    p.add_argument("--full", action="store_true",
+                   help="everything beyond the headline: oracle / float64 parity, CPU baseline, the other configurations, "
+                        "extras, comparator, sharded section (N > 1) and the detail file (the --no-* options still apply)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write the last step's output Y as DIR/*.npy (float32; a seeded row sample "
+                        "when Y exceeds 48 MB)")
+    args = p.parse_args(argv)
+    if args.steps < 1:
+        p.error("--steps must be at least 1")
+    if args.dump_outputs and args.rehearse_cpu:
+        p.error("--dump-outputs needs a GPU run (--rehearse-cpu computes nothing)")
+    return args
 
 
 def make_workload(shape, replicas):
@@ -445,6 +467,32 @@ def run_config(shape, replicas, F, weighted, variant, steps, warmup, dev, sync, 
     return res, cpu, state
 
 
+DUMP_LIMIT_BYTES = 48_000_000  # --dump-outputs: all files of one run together, well inside 64 MB
+DUMP_SEED = 0                    # fixes the row sample, so every build dumps the same rows
+
+
+def dump_outputs(Y, out_dir):
+    """Y (the last timed step's output, [rows, cols] fp32 on the device) to out_dir as .npy: whole if it fits in
+    DUMP_LIMIT_BYTES, else a seeded sample of whole rows (sorted) and their indices.  Returns the paths written."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    rows, cols = Y.shape
+    header = 256  # per .npy file, generous
+    if rows * cols * 4 + header <= DUMP_LIMIT_BYTES:
+        path = os.path.join(out_dir, "Y.npy")
+        np.save(path, Y.detach().float().cpu().numpy())
+        return [path]
+    k = min(rows, (DUMP_LIMIT_BYTES - 2 * header) // (cols * 4 + 8))
+    idx = np.sort(np.random.default_rng(DUMP_SEED).choice(rows, size=k, replace=False))
+    sample = Y.detach().index_select(0, torch.from_numpy(idx).to(Y.device)).float().cpu().numpy()
+    p_rows = os.path.join(out_dir, "Y_sampled_rows.npy")
+    p_idx = os.path.join(out_dir, "sampled_row_index.npy")
+    np.save(p_rows, sample)
+    np.save(p_idx, idx.astype(np.float64))
+    return [p_rows, p_idx]
+
+
 def single_graph_latency(state, F, dev, sync, shape):
     """Latency of ONE hypergraph (what result.xlsx "fig7,fig9" reports, ms per aggregation)."""
     import torch
@@ -730,7 +778,8 @@ def compact_line(out):
                             "max_rel_err_vs_single_gpu": _r(e.get("max_rel_err_vs_single_gpu"), 2)}
         line["strong_scaling"] = ss
         line["scaling_note"] = "value/scaling: independent batches per rank, no collective (weak); strong_scaling: north_star's sharded form"
-    line["detail"] = os.path.basename(out.get("detail_path", "bench_detail.json"))
+    detail = out.get("detail_path", "bench_detail.json")  # None: a plain run writes no detail file
+    line["detail"] = os.path.basename(detail) if detail else None
     for drop in (None, ("scaling_note",), ("hbm_gbs_algorithmic", "device_copy_gbs"), ("single_graph",)):
         for k in drop or ():
             line.pop(k, None)
@@ -888,6 +937,7 @@ def main(argv=None):
                    row_stream=not args.no_row_stream)
     F = args.feat
     one = world == 1
+    full = args.full
     if rehearse:
         barrier()
         res, cpu, st = rehearse_config(args, rank)
@@ -895,8 +945,11 @@ def main(argv=None):
     else:
         res, cpu, st = run_config(args.shape, args.replicas, F, args.weighted, args.variant, args.steps, args.warmup,
                                   dev, sync, barrier, rank, opts_kw,
-                                  want_cpu=one and not args.no_cpu_baseline, want_parity=not args.no_parity,
+                                  want_cpu=full and one and not args.no_cpu_baseline, want_parity=full and not args.no_parity,
                                   linear_out=args.linear_out, linear_math=args.linear_math)  # N > 1: rank 0 still checks its own shard's timed output
+        if args.dump_outputs and rank == 0:  # before any extra reuses Y
+            for p in dump_outputs(st["Y"], args.dump_outputs):
+                print("bench.py: wrote %s" % p, file=sys.stderr)
     wall = st["wall"]
     if world > 1:
         t = torch.tensor([wall], dtype=torch.float64, device=dev)
@@ -917,13 +970,13 @@ def main(argv=None):
         "roofline": res["roofline"],
         "hbm_gbs_algorithmic": res["roofline"]["algorithmic_bytes_per_step"] * world * args.steps / wall / 1e9,
         "plan_build_s": res["plan_build_s"], "fused_schedule_build_s": res["fused_schedule_build_s"],
-        "fused_schedule": res["fused_schedule"], "plan": res["plan"], "detail_path": args.detail,
+        "fused_schedule": res["fused_schedule"], "plan": res["plan"], "detail_path": args.detail if full else None,
     }
     if "parity" in res:
         out["parity"] = res["parity"]
     failed = "parity" in res and not res["parity"]["ok"]
 
-    if not args.no_extras and not args.linear_out and not rehearse:
+    if full and not args.no_extras and not args.linear_out and not rehearse:
         # What a plain device copy X -> Y (the 2NF term of B_alg, no gather, no index traffic)
         # takes on this box: the practical floor of any kernel that reads X and writes Y once.
         X, Y = st["X"], st["Y"]
@@ -943,7 +996,7 @@ def main(argv=None):
     if not rehearse:
         torch.cuda.empty_cache()
 
-    if (world > 1 or args.force_collective) and not args.no_extras:
+    if full and (world > 1 or args.force_collective) and not args.no_extras:
         out["sharded"] = rehearse_sharded(args, rank, world) if rehearse else sharded_section(args, dev, sync, barrier, rank, world)
         errs = torch.tensor([out["sharded"]["errors"]], dtype=torch.int64, device=dev)
         dist.all_reduce(errs, op=dist.ReduceOp.MAX)  # any rank's failure fails every rank
@@ -956,7 +1009,7 @@ def main(argv=None):
     for k in ("plan", "plan_build_s", "fused_schedule"):
         head.pop(k, None)
     configs = [head]
-    if one and not args.no_configs and not args.no_extras and not rehearse:
+    if full and one and not args.no_configs and not args.no_extras and not rehearse:
         # the other BASELINE configurations, same measurement, bounded step counts: north_star's target matrix (the
         # headline is its cora F = 32 cell; replica counts put X + Y beyond the 256 MiB Infinity Cache), config 3 and
         # its MFMA path, config 4, the weighted operator
@@ -985,13 +1038,14 @@ def main(argv=None):
                                 "error": "%s: %s" % (type(exc).__name__, str(exc)[:300])})
                 failed = True
     out["configs_detail"] = configs
-    if one and not args.no_extras and not args.no_comparator and not rehearse and rank == 0:
+    if full and one and not args.no_extras and not args.no_comparator and not rehearse and rank == 0:
         out["comparator"] = rocsparse_comparator(32)
 
     if rank == 0:
         out["cpu_baseline"] = cpu if one and not args.no_cpu_baseline else None
         line = compact_line(out)
-        write_detail(out, args.detail)
+        if full:
+            write_detail(out, args.detail)
         print(line, flush=True)
     if world > 1 or args.force_collective:
         dist.barrier()

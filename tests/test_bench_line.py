@@ -146,7 +146,7 @@ def test_gpus_2_self_launches_torchrun_and_relays_the_line(tmp_path):
     """`python bench.py --gpus 2`, invoked plainly: a child `python -m torch.distributed.run --nproc-per-node 2`, two ranks
     that meet over gloo (--rehearse-cpu: control flow only, no GPU, no kernels), max over ranks, rank 0's line last."""
     detail = str(tmp_path / "detail.json")
-    r, lines = _run_bench("--gpus", "2", "--rehearse-cpu", "--steps", "5", "--warmup", "0", "--detail", detail)
+    r, lines = _run_bench("--gpus", "2", "--rehearse-cpu", "--full", "--steps", "5", "--warmup", "0", "--detail", detail)
     assert r.returncode == 0, r.stderr[-2000:]
     assert "torch.distributed.run" in r.stderr
     d = json.loads(lines[-1])
@@ -162,7 +162,7 @@ def test_gpus_2_self_launches_torchrun_and_relays_the_line(tmp_path):
 
 
 def test_a_failing_exchange_fails_the_run(tmp_path):
-    r, lines = _run_bench("--gpus", "2", "--rehearse-cpu", "--steps", "3", "--warmup", "0", "--inject-exchange-error",
+    r, lines = _run_bench("--gpus", "2", "--rehearse-cpu", "--full", "--steps", "3", "--warmup", "0", "--inject-exchange-error",
                           "--detail", str(tmp_path / "detail.json"))
     assert r.returncode != 0
     d = json.loads(lines[-1])  # the line is still printed, with the error on it
@@ -174,3 +174,66 @@ def test_gpus_mismatch_is_refused():
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--rehearse-cpu"], capture_output=True,
                        text=True, env=env, timeout=120)
     assert r.returncode != 0 and "WORLD_SIZE" in (r.stderr + r.stdout)
+
+
+def test_plain_run_is_the_headline_only(tmp_path):
+    """Without --full the run times the headline and prints the line: no sharded section, no detail file, no parity."""
+    detail = tmp_path / "detail.json"
+    r, lines = _run_bench("--gpus", "2", "--rehearse-cpu", "--steps", "4", "--warmup", "0", "--detail", str(detail))
+    assert r.returncode == 0, r.stderr[-2000:]
+    d = json.loads(lines[-1])
+    for k in REQUIRED:
+        assert k in d, k
+    assert d["steps"] == 4 and d["ms_per_step"] > 0 and d["value"] > 0
+    assert "strong_scaling" not in d and d["parity"] is None and d["cpu_baseline"] is None and len(d["configs"]) == 1
+    assert d["detail"] is None and not detail.exists()
+
+
+def test_options():
+    a = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert (a.steps, a.warmup, a.full, a.dump_outputs) == (7, 2, False, None)
+    assert bench.parse(["--full", "--dump-outputs", "d"]).full
+    with pytest.raises(SystemExit):
+        bench.parse(["--steps", "0"])
+    with pytest.raises(SystemExit):
+        bench.parse(["--rehearse-cpu", "--dump-outputs", "d"])
+
+
+def test_dump_outputs_whole_and_sampled(tmp_path, monkeypatch):
+    """A Y that fits is written whole; a larger one as the same seeded row sample every time, within the limit."""
+    import numpy as np
+    import torch
+    Y = torch.arange(600 * 8, dtype=torch.float32).reshape(600, 8)
+    paths = bench.dump_outputs(Y, str(tmp_path / "whole"))
+    assert [os.path.basename(p) for p in paths] == ["Y.npy"]
+    got = np.load(paths[0])
+    assert got.dtype == np.float32 and np.array_equal(got, Y.numpy())
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 8192)
+    a = bench.dump_outputs(Y, str(tmp_path / "a"))
+    b = bench.dump_outputs(Y, str(tmp_path / "b"))
+    assert [os.path.basename(p) for p in a] == ["Y_sampled_rows.npy", "sampled_row_index.npy"]
+    assert sum(os.path.getsize(p) for p in a) <= 8192
+    rows, idx = np.load(a[0]), np.load(a[1])
+    assert rows.dtype == np.float32 and idx.dtype == np.float64 and 0 < len(idx) < 600
+    assert np.all(np.diff(idx) > 0) and np.array_equal(rows, Y.numpy()[idx.astype(np.int64)])
+    assert np.array_equal(rows, np.load(b[0])) and np.array_equal(idx, np.load(b[1]))
+
+
+@pytest.mark.gpu
+def test_dump_outputs_is_the_timed_output(hg, oracle, tmp_path):
+    """A plain GPU run with --dump-outputs: Y.npy is the aggregation of the run's seeded input (oracle, same bound as
+    the --full parity check), and --steps sets the number of timed steps."""
+    import numpy as np
+    from hypergef_amd import synth
+    out = tmp_path / "dump"
+    r, lines = _run_bench("--gpus", "1", "--replicas", "4", "--steps", "3", "--warmup", "1", "--dump-outputs", str(out))
+    assert r.returncode == 0, r.stderr[-2000:]
+    d = json.loads(lines[-1])
+    assert d["steps"] == 3 and d["ms_per_step"] > 0
+    base, inc = bench.make_workload("cora", 4)
+    X = synth.features_like_reference(inc.N, 32, seed=100)
+    H_ptr, H_ind = oracle.transpose_csr(inc.M, inc.N, inc.csrptr, inc.colind)
+    ref = oracle.hyperaggr_host(inc.N, 32, H_ptr, H_ind, inc.csrptr, inc.colind, X)
+    got = np.load(out / "Y.npy")
+    assert got.dtype == np.float32 and got.shape == ref.shape
+    assert (np.abs(got - ref) <= 1e-5 * np.maximum(1.0, np.abs(ref))).all()

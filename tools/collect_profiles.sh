@@ -7,7 +7,7 @@ tag=${1:-r01}
 root=$GRAFT_REPO_ROOT; [ -z "$root" ] && root=$(cd $(dirname $0)/.. && pwd)
 out=$root/gpurun_out/profiles_new; mkdir -p $out
 cd /tmp && export TMPDIR=/tmp && cd $root
-python3 bench.py > $out/${tag}_bench_default.log 2>&1 || exit 1
+python3 bench.py --full > $out/${tag}_bench_default.log 2>&1 || exit 1
 tail -1 $out/${tag}_bench_default.log > $out/${tag}_bench_default.json
 rocprofv3 --kernel-trace --stats -d $out/stats -o s --output-format csv -- python3 bench.py --steps 50 --warmup 5 --no-extras --no-cpu-baseline > $out/stats.log 2>&1 || exit 1
 cp $out/stats/s_kernel_stats.csv $out/${tag}_bench_default_kernel_stats.csv

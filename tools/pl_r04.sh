@@ -6,7 +6,7 @@
 root=$GRAFT_REPO_ROOT; [ -z "$root" ] && root=$(cd $(dirname $0)/.. && pwd)
 cd $root
 export HG_AGGR_LIB=$root/hypergef_amd/lib/libhgaggr_tuning.so
-run() { timeout -k 10 400 python3 bench.py --shape powerlaw --feat 64 --no-extras --no-cpu-baseline --steps 50 --warmup 5 "$@" 2>&1 | tail -1 | python3 -c "
+run() { timeout -k 10 400 python3 bench.py --full --shape powerlaw --feat 64 --no-extras --no-cpu-baseline --steps 50 --warmup 5 "$@" 2>&1 | tail -1 | python3 -c "
 import sys, json
 d = json.loads(sys.stdin.read())
 print('ms/step %.4f  frac %.4f  parity %s' % (d['ms_per_step'], d['roofline']['frac'], d.get('parity')))"; }

@@ -5,7 +5,7 @@ shape=${1:-cora}; F=${2:-32}
 root=$GRAFT_REPO_ROOT; [ -z "$root" ] && root=$(cd $(dirname $0)/.. && pwd)
 cd /tmp && export TMPDIR=/tmp && cd $root
 out=gpurun_out/single_$shape$F; mkdir -p $out
-timeout -k 10 200 rocprofv3 --kernel-trace -d $out/t -o s --output-format csv -- python3 bench.py --shape $shape --replicas 1 --feat $F --steps 200 --warmup 20 --no-cpu-baseline --no-configs > $out/run.log 2>&1 || { tail -5 $out/run.log; exit 1; }
+timeout -k 10 200 rocprofv3 --kernel-trace -d $out/t -o s --output-format csv -- python3 bench.py --shape $shape --replicas 1 --feat $F --full --steps 200 --warmup 20 --no-cpu-baseline --no-configs > $out/run.log 2>&1 || { tail -5 $out/run.log; exit 1; }
 python3 - $out/t/s_kernel_trace.csv $out/run.log <<'PY'
 import csv, sys, json, collections
 d = collections.defaultdict(list)
