@@ -11,7 +11,9 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("HG_AGGR_LIB") or os.path.join(_HERE, "lib", "libhgaggr.so")
 
 HG_OK = 0
+HG_ERR_INVALID = -1
 HG_ERR_WORKSPACE = -4  # include/hg_aggr.h: caller workspace smaller than hg_plan_workspace_bytes
+HG_ERR_UNSUPPORTED = -5
 HG_VARIANT_AUTO = 0
 HG_VARIANT_PULL = 1
 HG_VARIANT_PUSH_ATOMIC = 2
@@ -31,7 +33,7 @@ SYMBOLS = (
     "hg_plan_create_host", "hg_plan_create_device", "hg_plan_destroy", "hg_plan_get_info",
     "hg_plan_get_vertex_csr", "hg_plan_get_vertex_csr_device", "hg_plan_get_schedule", "hg_plan_prepare", "hg_plan_auto_variant", "hg_plan_bind_scales", "hg_plan_tune_f32",
     "hg_plan_workspace_bytes",
-    "hg_aggr_fused_f32", "hg_linear_pack_f32", "hg_linear_pack_ex_f32", "hg_linear_pack_floats", "hg_linear_rows_f32", "hg_linear_wgrad_workspace_bytes", "hg_linear_wgrad_f32", "hg_aggr_linear_workspace_bytes", "hg_aggr_linear_f32", "hg_aggr_linear_res_f32", "hg_aggr_linear_res_dev_f32",
+    "hg_aggr_fused_f32", "hg_aggr_fused_bf16", "hg_linear_pack_f32", "hg_linear_pack_ex_f32", "hg_linear_pack_floats", "hg_linear_rows_f32", "hg_linear_wgrad_workspace_bytes", "hg_linear_wgrad_f32", "hg_aggr_linear_workspace_bytes", "hg_aggr_linear_f32", "hg_aggr_linear_res_f32", "hg_aggr_linear_res_dev_f32",
     "hg_gather_rows_f32", "hg_aggr_push_groups_f32", "hg_gather_max_f32",
     "hg_scatter_record_f32",
 )
@@ -163,6 +165,8 @@ def lib():
     L.hg_plan_workspace_bytes.argtypes = [vp, i32]
     L.hg_aggr_fused_f32.restype = ctypes.c_int
     L.hg_aggr_fused_f32.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, sz, i32, vp]
+    L.hg_aggr_fused_bf16.restype = ctypes.c_int
+    L.hg_aggr_fused_bf16.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, sz, i32, vp]
     L.hg_gather_rows_f32.restype = ctypes.c_int
     L.hg_gather_rows_f32.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, sz, vp]
     L.hg_gather_max_f32.restype = ctypes.c_int

@@ -27,8 +27,13 @@ int hip_fail(const char *what, hipError_t e) {
 size_t round256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-// rows of an output table are whole, aligned 64-byte units: where the streaming (nt) store hint pays (hg_kernels.hip, HG_Y_NT)
-bool rows_whole_64(const void *base, int32_t F) { return F % 16 == 0 && (reinterpret_cast<uintptr_t>(base) & 63) == 0; }
+// four elements of a row: 16 bytes of fp32, 8 bytes of bf16 -- what a 16-byte (fp32) lane holds
+bool aligned_lane(const void *p, bool bf16) { return (reinterpret_cast<uintptr_t>(p) & (bf16 ? 7 : 15)) == 0; }
+// rows of an output table are whole, aligned 64-byte units: where the streaming (nt) store hint pays (hg_kernels.hip, HG_Y_NT);
+// decided on the row's bytes (bf16: F % 32 == 0)
+bool rows_whole_64(const void *base, int32_t F, bool bf16 = false) {
+  return ((int64_t)F * (bf16 ? 2 : 4)) % 64 == 0 && (reinterpret_cast<uintptr_t>(base) & 63) == 0;
+}
 
 int resolve_opts(const hg_plan_opts *in, hg::Opts &o) {
   if (in) {
@@ -428,10 +433,11 @@ int pick_variant_uncached(const hg_plan *plan, int32_t F, bool vec4, int32_t *va
   return HG_OK;
 }
 
+// src_bf16 / dst_bf16: rows of src / dst are bf16 (at most one of them; they take 16-byte lanes only)
 int run_sched(const hg_plan *p, const hg::Sched &s, int32_t F, const int32_t *ptr,
-              const int32_t *ind, const float *src, const float *scaleA, const float *scaleB,
-              const int32_t *scale_map, const int32_t *dst_map, float *dst, float *partial,
-              hipStream_t stream, bool nt_dst = false) {
+              const int32_t *ind, const void *src, const float *scaleA, const float *scaleB,
+              const int32_t *scale_map, const int32_t *dst_map, void *dst, float *partial,
+              hipStream_t stream, bool nt_dst = false, bool src_bf16 = false, bool dst_bf16 = false) {
   hg::GatherArgs a;
   a.nt_dst = nt_dst ? 1 : 0;
   a.scale_map = scale_map;
@@ -452,8 +458,8 @@ int run_sched(const hg_plan *p, const hg::Sched &s, int32_t F, const int32_t *pt
   a.panel_rows = p->opts.panel_rows;
   a.panel_nnz = p->opts.panel_nnz;
   a.xcd_remap = (p->opts.flags & HG_PLAN_NO_XCD_REMAP) ? 0 : 1;
-  const bool vec4 = (F % 4 == 0) && aligned16(src) && aligned16(dst) && aligned16(partial);
-  hipError_t e = hg::launch_gather(a, (int)s.fixups.size(), s.n_fix_l1, s.d_fixups, vec4, stream);
+  const bool vec4 = (F % 4 == 0) && aligned_lane(src, src_bf16) && aligned_lane(dst, dst_bf16) && aligned16(partial);
+  hipError_t e = hg::launch_gather(a, (int)s.fixups.size(), s.n_fix_l1, s.d_fixups, vec4, stream, src_bf16, dst_bf16);
   if (e != hipSuccess) return hip_fail("gather_rows launch", e);
   return HG_OK;
 }
@@ -489,17 +495,17 @@ int get_row_stream(const hg_plan *cp, int hop, int32_t ng, const hg::RowStream *
 }
 
 int run_hop(const hg_plan *p, int hop, int32_t F, const int32_t *ptr, const int32_t *ind,
-            const float *src, const float *scaleA, const float *scaleB, float *dst,
-            float *partial, hipStream_t stream) {
+            const void *src, const float *scaleA, const float *scaleB, void *dst,
+            float *partial, hipStream_t stream, bool src_bf16 = false, bool dst_bf16 = false) {
   // 16-byte lanes over rows of any width above 8 floats and any 4-byte alignment (wide_rows_ok): the stream
   // kernel loads through a range-checked descriptor and stores only the columns that exist
   const bool lanes16 = F % 4 == 0 || F > 8;
-  const int64_t nsrc = hop == 0 ? p->N : p->M, sb = nsrc * F * 4;
+  const int64_t nsrc = hop == 0 ? p->N : p->M, sb = nsrc * F * (src_bf16 ? 2 : 4);
   // Streaming (nt) stores for the hop's output: always for hop 2 (rows of Y); for hop 1 when Xe [M, F] is larger than
   // about three quarters of the 256 MiB Infinity Cache -- a smaller table is read straight back from it by hop 2 and plain stores keep it
   // there (same-box A/B, profiles/r03_experiments.md: 348-695 MB tables -3..-6 %, 2-143 MB tables +9..+16 % with nt)
   // -- and only for rows of whole 64-byte units (F % 16 == 0): others lose with the hint (hg_kernels.hip, HG_Y_NT)
-  const bool nt_out = rows_whole_64(dst, F) && (hop == 1 || (int64_t)p->M * F * 4 >= ((int64_t)192 << 20));
+  const bool nt_out = rows_whole_64(dst, F, dst_bf16) && (hop == 1 || (int64_t)p->M * F * 4 >= ((int64_t)192 << 20));
   int kind = 0;  // hg_plan_tune_f32's choice for this hop and width: 0 streaming, 1 panels + tasks, 2 latency schedule
   {
     hg_plan *mp = const_cast<hg_plan *>(p);
@@ -531,16 +537,16 @@ int run_hop(const hg_plan *p, int hop, int32_t F, const int32_t *ptr, const int3
     sa.nt_dst = nt_out;
     if (sa.nrec == 0) return HG_OK;
     if (hg::stream_rows_ok(sa, true)) {
-      hipError_t e = hg::launch_stream_rows(sa, stream);
+      hipError_t e = hg::launch_stream_rows(sa, stream, src_bf16, dst_bf16);
       if (e == hipSuccess)
         e = hg::launch_fixups(rs->d_fixups, (int)rs->fixups.size(), rs->n_fix_l1, F, partial, dst, scaleA, scaleB,
-                              nullptr, true, stream, nt_out);
+                              nullptr, true, stream, nt_out, dst_bf16);
       if (e != hipSuccess) return hip_fail("stream_rows launch", e);
       return HG_OK;
     }
   }
   return run_sched(p, (kind == 2 && p->has_lat) ? p->sched_lat[hop] : p->sched[hop], F, ptr, ind, src, scaleA, scaleB,
-                   nullptr, nullptr, dst, partial, stream, nt_out);
+                   nullptr, nullptr, dst, partial, stream, nt_out, src_bf16, dst_bf16);
 }
 
 // pull_only: the call runs the pull layout whatever schedules exist (a forced HG_VARIANT_PULL, a single hop): a
@@ -1018,7 +1024,7 @@ int hg_scatter_record_f32(int32_t N, int32_t M, int32_t F, const float *T, const
   return HG_OK;
 }
 
-// Shared body of hg_aggr_fused_f32 and hg_aggr_linear_f32.  With lin != nullptr the caller
+// Shared body of hg_aggr_fused_f32, hg_aggr_fused_bf16 and hg_aggr_linear_f32.  With lin != nullptr the caller
 // wants (aggregated rows) * Wlin^T in lin->Y: the fused panels do that in their epilogue when
 // they can (lin->done = true); otherwise the aggregated rows go to Y as usual and the caller
 // runs the standalone linear kernel over them.
@@ -1030,34 +1036,46 @@ struct LinReq {
   hg::LinEpilogue epi;
 };
 
+// bf16: rows of X and Y are bf16 (hg_aggr_fused_bf16 has checked F % 4 == 0 and 8-byte alignment, so the lane layout is the one
+// an fp32 call of the same width takes); everything between them is fp32 as in an fp32 call.  No linear epilogue.
 static int aggr_impl(const hg_plan *plan, int32_t F, const int32_t *csrptr_t,
-                     const int32_t *colind_t, const float *X, const float *degE,
-                     const float *degV, const float *W, float *Y, void *workspace,
-                     size_t workspace_bytes, int32_t variant, hg_stream_t stream, LinReq *lin) {
+                     const int32_t *colind_t, const void *X, const float *degE,
+                     const float *degV, const float *W, void *Y, void *workspace,
+                     size_t workspace_bytes, int32_t variant, hg_stream_t stream, LinReq *lin, bool bf16 = false) {
+  const char *fn = bf16 ? "hg_aggr_fused_bf16" : "hg_aggr_fused_f32";
   if (variant == HG_VARIANT_PUSH_ATOMIC) {
     if (!plan) {
       hg::set_error("null plan");
       return HG_ERR_INVALID;
     }
+    if (bf16) {
+      hg::set_error("hg_aggr_fused_bf16: the push kernels are fp32 only");
+      return HG_ERR_UNSUPPORTED;
+    }
     return hg_aggr_push_groups_f32(plan->N, plan->M, F, plan->M, nullptr, nullptr, nullptr, nullptr,
-                                   csrptr_t, colind_t, X, degE, degV, W, Y, stream);
+                                   csrptr_t, colind_t, static_cast<const float *>(X), degE, degV, W,
+                                   static_cast<float *>(Y), stream);
   }
   if (variant != HG_VARIANT_AUTO && variant != HG_VARIANT_PULL && variant != HG_VARIANT_FUSED) {
-    hg::set_error("hg_aggr_fused_f32: unknown variant");
+    hg::set_error(std::string(fn) + ": unknown variant");
     return HG_ERR_UNSUPPORTED;
   }
   // the size is checked against the layout that actually runs, once the variant is resolved
   int rc = check_call(plan, F, workspace, workspace_bytes, kSizeLater);
   if (rc != HG_OK) return rc;
   if (!csrptr_t || (plan->nnz > 0 && !colind_t) || !X || !Y) {
-    hg::set_error("hg_aggr_fused_f32: null array");
+    hg::set_error(std::string(fn) + ": null array");
     return HG_ERR_INVALID;
+  }
+  if (bf16 && (lin || F % 4 != 0 || !aligned_lane(X, true) || !aligned_lane(Y, true))) {
+    hg::set_error("hg_aggr_fused_bf16: F must be a multiple of 4 and X, Y 8-byte aligned");
+    return HG_ERR_UNSUPPORTED;
   }
   hipStream_t s = static_cast<hipStream_t>(stream);
   const Carve c = carve(plan, F);
   char *ws = static_cast<char *>(workspace);
   float *Xe = reinterpret_cast<float *>(ws + c.xe);
-  const bool aligned = (F % 4 == 0) && aligned16(X) && aligned16(Y) && aligned16(Xe);
+  const bool aligned = (F % 4 == 0) && aligned_lane(X, bf16) && aligned_lane(Y, bf16) && aligned16(Xe);
   const bool vec4 = aligned || wide_rows_ok(plan, F);  // the fused chain's lane layout; the pull kernels decide for themselves
   const hg::FusedSched *f = nullptr;
   if (variant == HG_VARIANT_AUTO) {
@@ -1099,7 +1117,7 @@ static int aggr_impl(const hg_plan *plan, int32_t F, const int32_t *csrptr_t,
     // scales pre-gathered into panel order, if the caller bound exactly these arrays
     const bool bound = (degE || degV || W) && f->bound_degE == degE && f->bound_W == W && f->bound_degV == degV;
     if (bound && W && f->bound_W_is_one) W = nullptr;  // multiplying by exactly 1.0f is the identity: same bits, less work
-    const int64_t xb = (int64_t)plan->N * F * 4, mb = (int64_t)f->n_mat * F * 4;
+    const int64_t xb = (int64_t)plan->N * F * (bf16 ? 2 : 4), mb = (int64_t)f->n_mat * F * 4;
     const int32_t x_bytes = xb < ((int64_t)1 << 31) ? (int32_t)xb : 0;
     const int32_t mat_bytes = mb < ((int64_t)1 << 31) ? (int32_t)mb : 0;
     // (a) materialised hyperedges (more than t_big members): Xe_mat rows
@@ -1121,14 +1139,14 @@ static int aggr_impl(const hg_plan *plan, int32_t F, const int32_t *csrptr_t,
       sa.F = F;
       sa.xcd_remap = (plan->opts.flags & HG_PLAN_NO_XCD_REMAP) ? 0 : 1;
       if (hg::stream_rows_ok(sa, vec4)) {  // the streaming row gather; else the general kernel
-        hipError_t e = hg::launch_stream_rows(sa, s);
+        hipError_t e = hg::launch_stream_rows(sa, s, bf16, false);
         if (e == hipSuccess)
           e = hg::launch_fixups(f->mat_stream.d_fixups, (int)f->mat_stream.fixups.size(), f->mat_stream.n_fix_l1, F,
                                 sa.partial, Xe, degE, W, f->d_mat_eid, vec4, s);
         if (e != hipSuccess) return hip_fail("stream_rows launch", e);
       } else {
         rc = run_sched(plan, f->mat_sched, F, f->d_mat_ptr, f->d_mat_ind, X, degE, W, f->d_mat_eid,
-                       nullptr, Xe, reinterpret_cast<float *>(ws + fc.mat_part), s);
+                       nullptr, Xe, reinterpret_cast<float *>(ws + fc.mat_part), s, false, bf16);
         if (rc != HG_OK) return rc;
       }
     }
@@ -1155,7 +1173,7 @@ static int aggr_impl(const hg_plan *plan, int32_t F, const int32_t *csrptr_t,
       h.nrows_mat = f->n_mat;
       h.n_heavy = f->hub.n_heavy;
       for (int q = 0; q < hg::kHubHeavy; q++) h.hslot0[q] = f->hub.hslot0[q];
-      hipError_t e = hg::launch_hub_pass(h, vec4, s);
+      hipError_t e = hg::launch_hub_pass(h, vec4, s, bf16);
       if (e != hipSuccess) return hip_fail("hub_pass launch", e);
     }
     // (c) everything else: vertex panels with the hyperedge sums staged in LDS
@@ -1181,7 +1199,7 @@ static int aggr_impl(const hg_plan *plan, int32_t F, const int32_t *csrptr_t,
     a.mat_bytes = mat_bytes;
     a.nrows_x = plan->N;
     a.nrows_mat = f->n_mat;
-    a.y_nt = rows_whole_64(Y, F);
+    a.y_nt = rows_whole_64(Y, F, bf16);
     // a pre-pass that read at least a quarter of the incidences' member rows: see fused_packed_kernel's run order
     a.reverse_runs = f->n_mat > 0 && !f->mat_ptr.empty() && (int64_t)f->mat_ptr.back() * 4 >= plan->nnz;
     a.bsA = bound ? f->d_bsA : nullptr;
@@ -1199,11 +1217,12 @@ static int aggr_impl(const hg_plan *plan, int32_t F, const int32_t *csrptr_t,
         a.Wlin = nullptr;
       }
     }
-    hipError_t e = hg::launch_fused(a, vec4, s);
+    hipError_t e = hg::launch_fused(a, vec4, s, bf16);
     if (e != hipSuccess) return hip_fail("fused_panel launch", e);
     // (d) hubs and split vertices: Y[v] = degV[v] * (sum of the vertex's partial rows), fixed order
     if (!f->fixups.empty()) {
-      e = hg::launch_fixups(f->d_fixups, (int)f->fixups.size(), f->n_fix_l1, F, partial, Y, degV, nullptr, nullptr, vec4, s, rows_whole_64(Y, F));
+      e = hg::launch_fixups(f->d_fixups, (int)f->fixups.size(), f->n_fix_l1, F, partial, Y, degV, nullptr, nullptr, vec4, s,
+                            rows_whole_64(Y, F, bf16), bf16);
       if (e != hipSuccess) return hip_fail("fixup launch", e);
     }
     return HG_OK;
@@ -1214,11 +1233,11 @@ static int aggr_impl(const hg_plan *plan, int32_t F, const int32_t *csrptr_t,
   }
   // hop 1: Xe[e] = ((sum_{u in e} X[u]) * degE[e]) * W[e]
   rc = run_hop(plan, 0, F, csrptr_t, colind_t, X, degE, W, Xe,
-               reinterpret_cast<float *>(ws + c.part[0]), s);
+               reinterpret_cast<float *>(ws + c.part[0]), s, bf16, false);
   if (rc != HG_OK) return rc;
   // hop 2: Y[v] = (sum_{e contains v} Xe[e]) * degV[v]
   return run_hop(plan, 1, F, plan->d_ptr_v, plan->d_ind_v, Xe, degV, nullptr, Y,
-                 reinterpret_cast<float *>(ws + c.part[1]), s);
+                 reinterpret_cast<float *>(ws + c.part[1]), s, false, bf16);
 }
 
 int hg_aggr_fused_f32(const hg_plan *plan, int32_t F, const int32_t *csrptr_t,
@@ -1227,6 +1246,18 @@ int hg_aggr_fused_f32(const hg_plan *plan, int32_t F, const int32_t *csrptr_t,
                       size_t workspace_bytes, int32_t variant, hg_stream_t stream) {
   return aggr_impl(plan, F, csrptr_t, colind_t, X, degE, degV, W, Y, workspace, workspace_bytes, variant,
                    stream, nullptr);
+}
+
+int hg_aggr_fused_bf16(const hg_plan *plan, int32_t F, const int32_t *csrptr_t,
+                       const int32_t *colind_t, const uint16_t *X, const float *degE,
+                       const float *degV, const float *W, uint16_t *Y, void *workspace,
+                       size_t workspace_bytes, int32_t variant, hg_stream_t stream) {
+  if (variant == HG_VARIANT_PUSH_ATOMIC) {
+    hg::set_error("hg_aggr_fused_bf16: HG_VARIANT_PUSH_ATOMIC is fp32 only");
+    return HG_ERR_UNSUPPORTED;
+  }
+  return aggr_impl(plan, F, csrptr_t, colind_t, X, degE, degV, W, Y, workspace, workspace_bytes, variant,
+                   stream, nullptr, true);
 }
 
 int hg_plan_tune_f32(const hg_plan *plan, int32_t F, const int32_t *csrptr_t, const int32_t *colind_t,

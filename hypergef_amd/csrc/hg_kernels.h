@@ -8,11 +8,17 @@
 
 namespace hg {
 
+// A bf16 element as the kernels see it: the bit pattern (hg_aggr_fused_bf16).  Rows of X and Y may be bf16; the tiles,
+// the materialised table, the partial rows and the scale vectors stay fp32.
+struct bf16 {
+  uint16_t bits;
+};
+
 struct GatherArgs {
   const int32_t *ptr;   // CSR row pointers [nrows + 1]
   const int32_t *ind;   // CSR column indices
-  const float *src;     // gathered table [*, F]
-  float *dst;           // output [nrows, F]
+  const void *src;      // gathered table [*, F], fp32 or bf16 (launch_gather's src_bf16)
+  void *dst;            // output [nrows, F], fp32 or bf16 (launch_gather's dst_bf16)
   const float *scaleA;  // per-row factor applied first, or null
   const float *scaleB;  // per-row factor applied second, or null
   float *partial;       // partial-sum slots [nslots, F]
@@ -51,13 +57,14 @@ struct FusedArgs {
   int32_t ng;             // lane groups the records were packed for
   int32_t cap, rows_cap;  // LDS tile rows (hyperedge slots) and rows per panel
   int32_t dv_regs = 0;    // set by the launcher: bound degV travels in registers, not through LDS (fused_packed_kernel)
-  const float *X, *Xe_mat, *degE, *W, *degV;
+  const void *X;  // fp32, or bf16 (launch_fused's xy_bf16)
+  const float *Xe_mat, *degE, *W, *degV;
   const float *bsA, *bsB, *bsD;  // bound scales in panel order (or null: gather from degE/W/degV)
-  float *Y;
+  void *Y;        // fp32, or bf16 (launch_fused's xy_bf16)
   float *partial = nullptr;  // partial rows (pieces of split vertices): a row id with bit 31 set lands here
   int32_t F;
   int32_t xcd_remap;
-  int32_t x_bytes;        // byte size of X if it fits a buffer descriptor (< 2 GiB), else 0
+  int32_t x_bytes;        // byte size of X (its own element size) if it fits a buffer descriptor (< 2 GiB), else 0
   int32_t mat_bytes;      // same for the materialised table
   int32_t nrows_x;        // rows of X
   int32_t nrows_mat = 0;  // rows of the materialised table
@@ -88,7 +95,8 @@ struct HubArgs {
   const int32_t *wg_first;  // [nwg + 1] rounds of each workgroup
   const int32_t *vslot0;    // [ng * R] first partial row of each virtual row, -1 = unused
   int32_t nwg, ng, cap, max_rec_words;
-  const float *X, *Xe_mat, *degE, *W;
+  const void *X;        // fp32, or bf16 (launch_hub_pass's x_bf16)
+  const float *Xe_mat, *degE, *W;
   float *partial;
   int32_t F;
   int32_t x_bytes, mat_bytes, nrows_x, nrows_mat;
@@ -102,10 +110,11 @@ struct StreamArgs {
   const int32_t *rec;
   const SRec *rec_tab;
   int32_t nrec, ng, cap, max_rec_words;
-  const float *src;             // gathered table [nrows_src, F]
+  const void *src;              // gathered table [nrows_src, F], fp32 or bf16 (launch_stream_rows' src_bf16)
   int32_t src_bytes, nrows_src;
   const float *scaleA, *scaleB; // indexed by the record's sidx lists, or null
-  float *dst, *partial;
+  void *dst;                    // fp32 or bf16 (launch_stream_rows' dst_bf16)
+  float *partial;
   int32_t F, xcd_remap;
   int32_t nt_dst = 0;  // as GatherArgs::nt_dst
 };
@@ -119,17 +128,20 @@ struct PushArgs {
   int32_t F;
 };
 
+// The element type of the rows of X / Y is a launch argument, not a field of the argument blocks: src_bf16 / dst_bf16 /
+// xy_bf16 / x_bf16 pick the kernels' bf16 instances (16-byte lanes, F % 4 == 0; tiles, partial rows and the
+// materialised table stay fp32).  At most one of src_bf16 and dst_bf16.
 hipError_t launch_gather(const GatherArgs &a, int nfix, int nfix_l1, const Fixup *fixups, bool vec4,
-                         hipStream_t stream);
-hipError_t launch_fused(const FusedArgs &a, bool vec4, hipStream_t stream);
-hipError_t launch_hub_pass(const HubArgs &a, bool vec4, hipStream_t stream);
+                         hipStream_t stream, bool src_bf16 = false, bool dst_bf16 = false);
+hipError_t launch_fused(const FusedArgs &a, bool vec4, hipStream_t stream, bool xy_bf16 = false);
+hipError_t launch_hub_pass(const HubArgs &a, bool vec4, hipStream_t stream, bool x_bf16 = false);
 size_t hub_pass_lds_bytes(int32_t cap, int32_t row_floats, int32_t max_rec_words);
-// Y[fx.row] = scale[fx.row] * (sum of the fixup's partial rows); first-level fixups first
-hipError_t launch_fixups(const Fixup *fixups, int nfix, int nfix_l1, int32_t F, float *partial, float *Y,
+// Y[fx.row] = scale[fx.row] * (sum of the fixup's partial rows); first-level fixups first.  Y_bf16: rows of Y are bf16.
+hipError_t launch_fixups(const Fixup *fixups, int nfix, int nfix_l1, int32_t F, float *partial, void *Y,
                          const float *scaleA, const float *scaleB, const int32_t *scale_map, bool vec4,
-                         hipStream_t stream, bool nt_dst = false);
+                         hipStream_t stream, bool nt_dst = false, bool Y_bf16 = false);
 bool stream_rows_ok(const StreamArgs &a, bool vec4);  // buffer-addressable table, 16-byte lanes
-hipError_t launch_stream_rows(const StreamArgs &a, hipStream_t stream);
+hipError_t launch_stream_rows(const StreamArgs &a, hipStream_t stream, bool src_bf16 = false, bool dst_bf16 = false);
 bool fused_linear_ok(const FusedArgs &a);  // can launch_fused run this call's linear epilogue?
 hipError_t launch_linear(const LinearArgs &a, hipStream_t stream);
 int wgrad_parts(int64_t nrows, int32_t Fa, int32_t Fb);

@@ -115,6 +115,41 @@ template <> struct Vec<4> {
   }
 };
 
+// Rows of X and Y in memory, element type T, as the fp32 lanes above.  fp32 rows move through Vec's own accesses.  bf16 rows
+// keep the fp32 lane layout -- a VEC = 4 lane still holds four columns, so it moves 8 bytes (buffer_load_dwordx2, an 8-byte
+// store) -- and every lane group, tile row and reduction step stays where the fp32 instance has it: same sums, same order.
+// Widening is a 16-bit shift (exact); narrowing is the plain cast, v_cvt_pk_bf16_f32 (round to nearest even, NaN stays NaN).
+// Only VEC = 4 exists for bf16: a bf16 call has F % 4 == 0 and 8-byte aligned rows (hg_aggr_fused_bf16).
+template <typename T, int VEC> struct Rows {
+  using V = Vec<VEC>;
+  __device__ __forceinline__ static V load(const float *p) { return V::load(p); }
+  __device__ __forceinline__ static V load_buf(__amdgpu_buffer_rsrc_t r, unsigned off) { return V::load_buf(r, off); }
+  __device__ __forceinline__ static void store(const V &v, float *p) { v.store(p); }
+  __device__ __forceinline__ static void store_n(const V &v, float *p, int n) { v.store_n(p, n); }
+  __device__ __forceinline__ static void store_n_nt(const V &v, float *p, int n) { v.store_n_nt(p, n); }
+};
+template <> struct Rows<bf16, 4> {
+  using V = Vec<4>;
+  typedef unsigned u2 __attribute__((ext_vector_type(2)));
+  __device__ __forceinline__ static V widen(u2 u) {
+    return V{make_float4(__uint_as_float(u.x << 16), __uint_as_float(u.x & 0xffff0000u), __uint_as_float(u.y << 16),
+                         __uint_as_float(u.y & 0xffff0000u))};
+  }
+  __device__ __forceinline__ static unsigned pack(float lo, float hi) {
+    return (unsigned)__builtin_bit_cast(uint16_t, (__bf16)lo) | ((unsigned)__builtin_bit_cast(uint16_t, (__bf16)hi) << 16);
+  }
+  __device__ __forceinline__ static u2 narrow(const V &v) { return u2{pack(v.v.x, v.v.y), pack(v.v.z, v.v.w)}; }
+  __device__ __forceinline__ static V load(const bf16 *p) { return widen(*reinterpret_cast<const u2 *>(p)); }
+  __device__ __forceinline__ static V load_buf(__amdgpu_buffer_rsrc_t r, unsigned off) {
+    return widen(__builtin_amdgcn_raw_buffer_load_b64(r, off, 0, 0));
+  }
+  __device__ __forceinline__ static void store(const V &v, bf16 *p) { *reinterpret_cast<u2 *>(p) = narrow(v); }
+  __device__ __forceinline__ static void store_n(const V &v, bf16 *p, int) { store(v, p); }  // whole lanes: F % 4 == 0
+  __device__ __forceinline__ static void store_n_nt(const V &v, bf16 *p, int) {
+    __builtin_nontemporal_store(narrow(v), reinterpret_cast<u2 *>(p));
+  }
+};
+
 // dst[r,:] = scaleB[r] * (scaleA[r] * sum_{p in row r} src[ind[p],:])
 //
 // Workgroups [0, n_task_blocks) run wave tasks (one long-row slice per wave, its
@@ -123,13 +158,17 @@ template <> struct Vec<4> {
 // row pointers, row scales and index slice are staged into LDS with coalesced
 // loads, then every LPR-lane group walks a contiguous run of the panel's rows as
 // one flat entry stream, U row loads in flight, adding in CSR order (so short
-// rows reproduce the CPU reference's summation order exactly).
-template <int LPR, int VEC, int U, bool PIPE>
+// rows reproduce the CPU reference's summation order exactly).  TS / TD: element types of src / dst rows (Rows).
+template <int LPR, int VEC, int U, bool PIPE, typename TS = float, typename TD = float>
 __global__ __launch_bounds__(256) void gather_rows_kernel(const GatherArgs a) {
   constexpr int G = 64 / LPR;    // row groups per wave
   constexpr int NG = 256 / LPR;  // row groups per workgroup
   using V = Vec<VEC>;
+  using RS = Rows<TS, VEC>;
+  using RD = Rows<TD, VEC>;
   extern __shared__ int32_t smem[];
+  const TS *src = static_cast<const TS *>(a.src);
+  TD *dst = static_cast<TD *>(a.dst);
 
   const int tid = threadIdx.x;
   const int gl = tid & (LPR - 1);
@@ -151,7 +190,7 @@ __global__ __launch_bounds__(256) void gather_rows_kernel(const GatherArgs a) {
         const int q = p + k * G;
         const bool ok = col_ok && q < tk.end;
         const int64_t idx = ok ? a.ind[q] : 0;
-        v[k] = ok ? V::load(a.src + idx * F + col) : V::zero();
+        v[k] = ok ? RS::load(src + idx * F + col) : V::zero();
       }
 #pragma unroll
       for (int k = 0; k < U; k++) acc.add(v[k]);
@@ -164,8 +203,8 @@ __global__ __launch_bounds__(256) void gather_rows_kernel(const GatherArgs a) {
         const int64_t drow = a.dst_map ? a.dst_map[tk.row] : tk.row;
         if (a.scaleA) acc.mul(a.scaleA[srow]);
         if (a.scaleB) acc.mul(a.scaleB[srow]);
-        if (HG_Y_NT && a.nt_dst) acc.store_n_nt(a.dst + drow * F + col, VEC);
-        else acc.store(a.dst + drow * F + col);
+        if (HG_Y_NT && a.nt_dst) RD::store_n_nt(acc, dst + drow * F + col, VEC);
+        else RD::store(acc, dst + drow * F + col);
       } else {
         acc.store(a.partial + (int64_t)tk.slot * F + col);
       }
@@ -211,8 +250,8 @@ __global__ __launch_bounds__(256) void gather_rows_kernel(const GatherArgs a) {
     }
     const int64_t drow = a.dst_map ? sdst[row] : pn.row0 + row;
     if (col_ok) {
-      if (HG_Y_NT && a.nt_dst) acc.store_n_nt(a.dst + drow * F + col, VEC);
-      else acc.store(a.dst + drow * F + col);
+      if (HG_Y_NT && a.nt_dst) RD::store_n_nt(acc, dst + drow * F + col, VEC);
+      else RD::store(acc, dst + drow * F + col);
     }
   };
 
@@ -225,7 +264,7 @@ __global__ __launch_bounds__(256) void gather_rows_kernel(const GatherArgs a) {
 #pragma unroll
     for (int k = 0; k < U; k++) {
       const int64_t idx = sind[p0 + min(k, n - 1)];
-      v[k] = col_ok ? V::load(a.src + idx * F + col) : V::zero();
+      v[k] = col_ok ? RS::load(src + idx * F + col) : V::zero();
     }
   };
   auto consume = [&](int p0, int n, const V(&v)[U]) {
@@ -276,11 +315,12 @@ __global__ __launch_bounds__(256) void gather_rows_kernel(const GatherArgs a) {
 }
 
 // out[row,:] = scaleB * (scaleA * sum_k partial[first+k,:]), slots in order; a first-level
-// fixup (pad > 0) leaves its unscaled sum in partial[pad-1] for the final one.
-template <int LPR, int VEC>
+// fixup (pad > 0) leaves its unscaled sum in partial[pad-1] for the final one.  TD: element type of dst rows.
+template <int LPR, int VEC, typename TD = float>
 __global__ __launch_bounds__(256) void fixup_rows_kernel(const GatherArgs a, const Fixup *fixups,
                                                          int nfix) {
   using V = Vec<VEC>;
+  using RD = Rows<TD, VEC>;
   const int tid = threadIdx.x;
   const int gl = tid & (LPR - 1);
   const int col = (blockIdx.y * LPR + gl) * VEC;
@@ -307,8 +347,9 @@ __global__ __launch_bounds__(256) void fixup_rows_kernel(const GatherArgs a, con
   const int64_t drow = a.dst_map ? a.dst_map[fx.row] : fx.row;
   if (a.scaleA) acc.mul(a.scaleA[srow]);
   if (a.scaleB) acc.mul(a.scaleB[srow]);
-  if (HG_Y_NT && a.nt_dst) acc.store_n_nt(a.dst + drow * F + col, a.F - col);
-  else acc.store_n(a.dst + drow * F + col, a.F - col);
+  TD *dst = static_cast<TD *>(a.dst);
+  if (HG_Y_NT && a.nt_dst) RD::store_n_nt(acc, dst + drow * F + col, a.F - col);
+  else RD::store_n(acc, dst + drow * F + col, a.F - col);
 }
 
 // Diagnostic stamps: lane 0 of every wave adds the ticks since the previous stamp to a
@@ -1272,13 +1313,18 @@ __host__ __device__ inline int lin_tile_floats(int cap, int rows_cap, int tw) {
 // only and fit 8 waves per SIMD without spills; the direct form's registers used to set the budget of every LIN
 // instance (natural demand 85-92 VGPRs, 5-6 waves).
 // SPLIT (LIN, !LINW, K = 128 only): the matrix phase as six bf16 products per fp32 product (mfma_rows_split); a.epi.wsplit.
-template <int LPR, int VEC, int U, bool FAST, bool MAT, bool SCALED, bool DBG, bool LIN = false, int BS = 256, bool LINW = true, bool SPLIT = false>
+// T: element type of the rows of X and Y (Rows; bf16 without LIN only).  Tile, materialised rows and partial rows are fp32.
+template <int LPR, int VEC, int U, bool FAST, bool MAT, bool SCALED, bool DBG, bool LIN = false, int BS = 256, bool LINW = true, bool SPLIT = false,
+          typename T = float>
 __global__ __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(LIN ? (!LINW ? (LPR >= 32 ? HG_LIN_WAVES_STAGED32 : HG_LIN_WAVES_STAGED) : LPR >= 32 ? HG_LIN_WAVES32 : LPR == 16 ? HG_LIN_WAVES16 : HG_LIN_WAVES8) : 1, 8))) void fused_packed_kernel(const FusedArgs a) {
   static_assert(!LIN || BS == 256, "the linear epilogue is written for four waves");
   static_assert(!SPLIT || (LIN && !LINW && LPR == 32 && VEC == 4), "bf16x6 matrix phase: K = 128 staged instances");
+  static_assert(!LIN || std::is_same_v<T, float>, "the linear epilogue takes fp32 rows");
+  constexpr bool XF32 = std::is_same_v<T, float>;
   constexpr int NG = BS / LPR;
   constexpr int TW = LPR * VEC;
   using V = Vec<VEC>;
+  using RX = Rows<T, VEC>;
   extern __shared__ int32_t smem[];
   const int64_t F = a.F;
   const int tid = threadIdx.x;
@@ -1400,11 +1446,15 @@ __global__ __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(LIN ? (!LINW
     // out-of-range buffer load returns zeros without touching memory.
     [[maybe_unused]] const unsigned row_bytes = (unsigned)a.F * 4u;
     [[maybe_unused]] const unsigned col_off = col_ok ? (unsigned)col * 4u : 0x80000000u;
+    // bf16 rows of X: the same offsets at the element size (the materialised table stays fp32)
+    [[maybe_unused]] const unsigned xrow_bytes = (unsigned)a.F * (unsigned)sizeof(T);
+    [[maybe_unused]] const unsigned xcol_off = col_ok ? (unsigned)col * (unsigned)sizeof(T) : 0x80000000u;
+    [[maybe_unused]] const T *X = static_cast<const T *>(a.X);
     [[maybe_unused]] __amdgpu_buffer_rsrc_t rx, rm;
     if constexpr (FAST) {
       const bool no_x = DBG && (a.debug & 1);  // ablation: an empty range turns every load into zeros
-      rx = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(a.X), 0, no_x ? 0 : a.x_bytes, 0x00020000);
-      rm = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(a.Xe_mat ? a.Xe_mat : a.X), 0,
+      rx = __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(a.X), 0, no_x ? 0 : a.x_bytes, 0x00020000);
+      rm = __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(a.Xe_mat ? static_cast<const void *>(a.Xe_mat) : a.X), 0,
                                              (a.Xe_mat && !no_x) ? a.mat_bytes : 0, 0x00020000);
     }
     // The stream has two phases (pack_stream, hg_fused.cpp): steps [0, steps_x) gather member rows of X,
@@ -1424,13 +1474,19 @@ __global__ __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(LIN ? (!LINW
           v[j] = V::zero();
           continue;
         }
-        if constexpr (FAST) {
+        if constexpr (FAST && !XF32 && !MATPH) {
+          v[j] = RX::load_buf(rx, __umul24((unsigned)ent[j], xrow_bytes) + xcol_off);
+        } else if constexpr (FAST) {
           const unsigned off = __umul24((unsigned)ent[j], row_bytes) + col_off;  // flags sit above bit 23
           v[j] = (HG_X_NT && !MATPH) ? V::load_buf_nt(rx, off) : V::load_buf(MATPH ? rm : rx, off);
+        } else if constexpr (!XF32 && !MATPH) {
+          const bool on = col_ok && ent[j] != idle && !(DBG && (a.debug & 1));
+          const int64_t idx = ent[j] & 0x3fffffff;
+          v[j] = on ? RX::load(X + idx * F + col) : V::zero();
         } else {
           const bool on = col_ok && ent[j] != idle && !(DBG && (a.debug & 1));
           const int64_t idx = ent[j] & 0x3fffffff;
-          const float *base = MATPH ? a.Xe_mat : a.X;
+          const float *base = MATPH ? a.Xe_mat : static_cast<const float *>(a.X);
           v[j] = on ? V::load(base + idx * F + col) : V::zero();
         }
       }
@@ -1469,7 +1525,8 @@ __global__ __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(LIN ? (!LINW
           }
           const unsigned off = __umul24((unsigned)ent[j], row_bytes) + col_off;  // flags sit above bit 23
           if (s0 + j >= steps_x) v[j] = V::load_buf(rm, off);  // wave-uniform
-          else v[j] = V::load_buf(rx, off);
+          else if constexpr (XF32) v[j] = V::load_buf(rx, off);
+          else v[j] = RX::load_buf(rx, __umul24((unsigned)ent[j], xrow_bytes) + xcol_off);
         }
 #pragma unroll
         for (int j = 0; j < U; j++) {
@@ -1572,8 +1629,8 @@ __global__ __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(LIN ? (!LINW
       __syncthreads();
       HG_STAMP(6);
       HG_STAMP(7);
-      if (a.F_out > 64) panel_times_wt_split<2>(tile, pstride, nrows, a.F_out, static_cast<const uint4 *>(a.epi.wsplit), prow, a.Y, tid, bsp, a.epi.relu, stp, DBG ? a.debug : 0);
-      else panel_times_wt_split<1>(tile, pstride, nrows, a.F_out, static_cast<const uint4 *>(a.epi.wsplit), prow, a.Y, tid, bsp, a.epi.relu, stp, DBG ? a.debug : 0);
+      if (a.F_out > 64) panel_times_wt_split<2>(tile, pstride, nrows, a.F_out, static_cast<const uint4 *>(a.epi.wsplit), prow, static_cast<float *>(a.Y), tid, bsp, a.epi.relu, stp, DBG ? a.debug : 0);
+      else panel_times_wt_split<1>(tile, pstride, nrows, a.F_out, static_cast<const uint4 *>(a.epi.wsplit), prow, static_cast<float *>(a.Y), tid, bsp, a.epi.relu, stp, DBG ? a.debug : 0);
       HG_STAMP_FLUSH();
       return;
     }
@@ -1589,7 +1646,7 @@ __global__ __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(LIN ? (!LINW
       const int q = min(a.F_out, TW) >> 2;
       for (int i = tid; i < nrows * q; i += 256) {
         const int r = i / q, c = (i - r * q) * 4;
-        *reinterpret_cast<float4 *>(a.Y + (int64_t)prow[r] * a.F_out + c) =
+        *reinterpret_cast<float4 *>(static_cast<float *>(a.Y) + (int64_t)prow[r] * a.F_out + c) =
             *reinterpret_cast<const float4 *>(tile + r * (TW + 4) + c);
       }
       return;
@@ -1603,7 +1660,7 @@ __global__ __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(LIN ? (!LINW
       }
     }
     HG_STAMP(7);
-    panel_times_wt<TW / 4, LINW>(tile, nrows, a.F_out, a.Wlin, prow, 0, a.Y, tid, bv, a.epi.relu, stp);
+    panel_times_wt<TW / 4, LINW>(tile, nrows, a.F_out, a.Wlin, prow, 0, static_cast<float *>(a.Y), tid, bv, a.epi.relu, stp);
     HG_STAMP_FLUSH();
     return;
   } else if (!(DBG && (a.debug & 8))) {  // ---- hop 2
@@ -1616,10 +1673,20 @@ __global__ __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(LIN ? (!LINW
       if (a.degV && pe > pb) acc.mul(dv_regs ? dscale : sdeg[r]);
       if (col_ok && !(DBG && (a.debug & 2))) {
         const int pr = prow[r];  // vertex id, or bit 31 | partial row (a piece of a split vertex)
-        float *dst = (pr < 0 ? a.partial + (int64_t)(pr & 0x7fffffff) * F : a.Y + (int64_t)pr * F) + col;
-        if (DBG && (a.debug & 64)) acc.store_nt(dst);
-        else if (HG_Y_NT && a.y_nt && pr >= 0) acc.store_n_nt(dst, a.F - col);  // partial rows are read back by the fixup pass: plain
-        else acc.store_n(dst, a.F - col);
+        if constexpr (XF32) {
+          float *dst = (pr < 0 ? a.partial + (int64_t)(pr & 0x7fffffff) * F : static_cast<float *>(a.Y) + (int64_t)pr * F) + col;
+          if (DBG && (a.debug & 64)) acc.store_nt(dst);
+          else if (HG_Y_NT && a.y_nt && pr >= 0) acc.store_n_nt(dst, a.F - col);  // partial rows are read back by the fixup pass: plain
+          else acc.store_n(dst, a.F - col);
+        } else {  // partial rows stay fp32
+          if (pr < 0) {
+            acc.store_n(a.partial + (int64_t)(pr & 0x7fffffff) * F + col, a.F - col);
+          } else {
+            T *y = static_cast<T *>(a.Y) + (int64_t)pr * F + col;
+            if (HG_Y_NT && a.y_nt) RX::store_n_nt(acc, y, a.F - col);
+            else RX::store_n(acc, y, a.F - col);
+          }
+        }
       }
     };
     if (SCALED && dv_regs) {  // at most four rows, their factors in dv[0..3] (static indices)
@@ -1659,10 +1726,12 @@ __global__ __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(LIN ? (!LINW
 #else
 #define HG_HUB_ABLATE(bit) false
 #endif
-template <int LPR, int VEC, int U, bool MAT, bool SCALED, bool HEAVY>
+// T: element type of the rows of X (Rows); the partial rows it writes are fp32.
+template <int LPR, int VEC, int U, bool MAT, bool SCALED, bool HEAVY, typename T = float>
 __global__ __launch_bounds__(1024) void hub_pass_kernel(const HubArgs a) {
   constexpr int BS = 1024, NG = BS / LPR, TW = LPR * VEC, R = kHubRows, NH = HEAVY ? kHubHeavy : 1;
   using V = Vec<VEC>;
+  using RX = Rows<T, VEC>;
   extern __shared__ int32_t smem[];
   const int tid = threadIdx.x;
   const int gl = tid & (LPR - 1);
@@ -1686,9 +1755,11 @@ __global__ __launch_bounds__(1024) void hub_pass_kernel(const HubArgs a) {
   if (tid < LPR) V::zero().store(tile + a.cap * TW + lcol);
   const unsigned row_bytes = (unsigned)a.F * 4u;
   const unsigned col_off = col_ok ? (unsigned)col * 4u : 0x80000000u;
-  const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(a.X), 0, HG_HUB_ABLATE(4) ? 0 : a.x_bytes, 0x00020000);
+  [[maybe_unused]] const unsigned xrow_bytes = (unsigned)a.F * (unsigned)sizeof(T);  // rows of X at their element size
+  [[maybe_unused]] const unsigned xcol_off = col_ok ? (unsigned)col * (unsigned)sizeof(T) : 0x80000000u;
+  const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(a.X), 0, HG_HUB_ABLATE(4) ? 0 : a.x_bytes, 0x00020000);
   [[maybe_unused]] const __amdgpu_buffer_rsrc_t rm = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<float *>(a.Xe_mat ? a.Xe_mat : a.X), 0, (a.Xe_mat && !HG_HUB_ABLATE(4)) ? a.mat_bytes : 0, 0x00020000);
+      const_cast<void *>(a.Xe_mat ? static_cast<const void *>(a.Xe_mat) : a.X), 0, (a.Xe_mat && !HG_HUB_ABLATE(4)) ? a.mat_bytes : 0, 0x00020000);
   const int rd0 = a.wg_first[w], rd1 = a.wg_first[w + 1];
   HG_STAMP_INIT(true);
   // A record is at most NPRE * 16 KB: each thread carries NPRE dwordx4 of the NEXT round's record
@@ -1755,8 +1826,12 @@ __global__ __launch_bounds__(1024) void hub_pass_kernel(const HubArgs a) {
             v[j] = V::zero();
             continue;
           }
-          const unsigned off = __umul24((unsigned)ent[j], row_bytes) + col_off;  // flags sit above bit 23
-          v[j] = V::load_buf(MATPH ? rm : rx, off);
+          if constexpr (!MATPH && !std::is_same_v<T, float>) {
+            v[j] = RX::load_buf(rx, __umul24((unsigned)ent[j], xrow_bytes) + xcol_off);
+          } else {
+            const unsigned off = __umul24((unsigned)ent[j], row_bytes) + col_off;  // flags sit above bit 23
+            v[j] = V::load_buf(MATPH ? rm : rx, off);
+          }
         }
 #pragma unroll
         for (int j = 0; j < U; j++) {
@@ -1862,10 +1937,13 @@ __global__ __launch_bounds__(1024) void hub_pass_kernel(const HubArgs a) {
 // eight unpredicated buffer loads in flight per lane -- and finished in registers: the lane group that
 // reaches a row's last entry scales the sum and stores the row (or a chunk's partial row).  No tile, no
 // second hop, one barrier.  The materialisation pre-pass of the fused variant runs on it.
-template <int LPR, int VEC, int U>
+// TS / TD: element types of src / dst rows (Rows); partial rows are fp32.
+template <int LPR, int VEC, int U, typename TS = float, typename TD = float>
 __global__ __launch_bounds__(256) void stream_rows_kernel(const StreamArgs a) {
   constexpr int BS = 256, NG = BS / LPR, TW = LPR * VEC;
   using V = Vec<VEC>;
+  using RS = Rows<TS, VEC>;
+  using RD = Rows<TD, VEC>;
   extern __shared__ int32_t smem[];
   const int tid = threadIdx.x;
   const int gl = tid & (LPR - 1);
@@ -1915,9 +1993,10 @@ __global__ __launch_bounds__(256) void stream_rows_kernel(const StreamArgs a) {
   const int32_t *dstl = rec + rec[6];
   const int g = tid / LPR;
   int slot = rec[rec[4] + g];
-  const unsigned row_bytes = (unsigned)a.F * 4u;
-  const unsigned col_off = col_ok ? (unsigned)col * 4u : 0x80000000u;
-  const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(a.src), 0, a.src_bytes, 0x00020000);
+  const unsigned row_bytes = (unsigned)a.F * (unsigned)sizeof(TS);
+  const unsigned col_off = col_ok ? (unsigned)col * (unsigned)sizeof(TS) : 0x80000000u;
+  const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(a.src), 0, a.src_bytes, 0x00020000);
+  TD *dst = static_cast<TD *>(a.dst);
   const int idle = a.nrows_src;
   V acc = V::zero();
   auto block = [&](const int s0, auto full) {
@@ -1932,7 +2011,7 @@ __global__ __launch_bounds__(256) void stream_rows_kernel(const StreamArgs a) {
         v[j] = V::zero();
         continue;
       }
-      v[j] = V::load_buf(rx, __umul24((unsigned)ent[j], row_bytes) + col_off);  // flags sit above bit 23
+      v[j] = RS::load_buf(rx, __umul24((unsigned)ent[j], row_bytes) + col_off);  // flags sit above bit 23
     }
 #pragma unroll
     for (int j = 0; j < U; j++) {
@@ -1943,8 +2022,16 @@ __global__ __launch_bounds__(256) void stream_rows_kernel(const StreamArgs a) {
         const int d = dstl[slot];
         slot++;
         if (col_ok) {
-          if (HG_Y_NT && a.nt_dst && d >= 0) acc.store_n_nt(a.dst + (int64_t)d * F + col, a.F - col);
-          else acc.store_n((d < 0 ? a.partial + (int64_t)(d & 0x7fffffff) * F : a.dst + (int64_t)d * F) + col, a.F - col);
+          if constexpr (std::is_same_v<TD, float>) {
+            if (HG_Y_NT && a.nt_dst && d >= 0) acc.store_n_nt(dst + (int64_t)d * F + col, a.F - col);
+            else acc.store_n((d < 0 ? a.partial + (int64_t)(d & 0x7fffffff) * F : dst + (int64_t)d * F) + col, a.F - col);
+          } else if (d < 0) {  // partial rows stay fp32
+            acc.store_n(a.partial + (int64_t)(d & 0x7fffffff) * F + col, a.F - col);
+          } else if (HG_Y_NT && a.nt_dst) {
+            RD::store_n_nt(acc, dst + (int64_t)d * F + col, a.F - col);
+          } else {
+            RD::store_n(acc, dst + (int64_t)d * F + col, a.F - col);
+          }
         }
         acc = V::zero();
       }
@@ -2080,21 +2167,21 @@ static hipError_t launch_lds(dim3 grid, size_t lds, hipStream_t stream, const Ar
   return hipGetLastError();
 }
 
-template <int LPR, int VEC>
+template <int LPR, int VEC, typename TD = float>
 static hipError_t launch_fixups_t(const GatherArgs &a, int nfix, int nfix_l1, const Fixup *fixups, hipStream_t stream) {
   const int col_tiles = (a.F + LPR * VEC - 1) / (LPR * VEC);
   const int per_block = 256 / LPR;
   if (nfix_l1 > 0)  // first level of the two-level sums (rows cut into very many tasks)
-    hipLaunchKernelGGL((fixup_rows_kernel<LPR, VEC>), dim3((nfix_l1 + per_block - 1) / per_block, col_tiles),
+    hipLaunchKernelGGL((fixup_rows_kernel<LPR, VEC, TD>), dim3((nfix_l1 + per_block - 1) / per_block, col_tiles),
                        dim3(256), 0, stream, a, fixups, nfix_l1);
   if (nfix > nfix_l1)
-    hipLaunchKernelGGL((fixup_rows_kernel<LPR, VEC>),
+    hipLaunchKernelGGL((fixup_rows_kernel<LPR, VEC, TD>),
                        dim3((nfix - nfix_l1 + per_block - 1) / per_block, col_tiles), dim3(256), 0, stream, a,
                        fixups + nfix_l1, nfix - nfix_l1);
   return hipGetLastError();
 }
 
-template <int LPR, int VEC>
+template <int LPR, int VEC, typename TS = float, typename TD = float>
 static hipError_t launch_gather_t(const GatherArgs &a, int nfix, int nfix_l1, const Fixup *fixups,
                                   hipStream_t stream) {
   const int col_tiles = (a.F + LPR * VEC - 1) / (LPR * VEC);
@@ -2105,24 +2192,27 @@ static hipError_t launch_gather_t(const GatherArgs &a, int nfix, int nfix_l1, co
     const Tuning &t = tuning();
     hipError_t e;
     if (t.unroll == 8) {
-      e = t.pipe ? launch_lds<gather_rows_kernel<LPR, VEC, 8, true>>(grid, lds, stream, a)
-                 : launch_lds<gather_rows_kernel<LPR, VEC, 8, false>>(grid, lds, stream, a);
+      e = t.pipe ? launch_lds<gather_rows_kernel<LPR, VEC, 8, true, TS, TD>>(grid, lds, stream, a)
+                 : launch_lds<gather_rows_kernel<LPR, VEC, 8, false, TS, TD>>(grid, lds, stream, a);
     } else {
-      e = t.pipe ? launch_lds<gather_rows_kernel<LPR, VEC, 4, true>>(grid, lds, stream, a)
-                 : launch_lds<gather_rows_kernel<LPR, VEC, 4, false>>(grid, lds, stream, a);
+      e = t.pipe ? launch_lds<gather_rows_kernel<LPR, VEC, 4, true, TS, TD>>(grid, lds, stream, a)
+                 : launch_lds<gather_rows_kernel<LPR, VEC, 4, false, TS, TD>>(grid, lds, stream, a);
     }
     if (e != hipSuccess) return e;
   }
-  return launch_fixups_t<LPR, VEC>(a, nfix, nfix_l1, fixups, stream);
+  return launch_fixups_t<LPR, VEC, TD>(a, nfix, nfix_l1, fixups, stream);
 }
 
 hipError_t launch_gather(const GatherArgs &a, int nfix, int nfix_l1, const Fixup *fixups, bool vec4,
-                         hipStream_t stream) {
+                         hipStream_t stream, bool src_bf16, bool dst_bf16) {
   const int lanes = vec4 ? a.F / 4 : a.F;
   const int lpr = std::min(64, next_pow2(std::max(lanes, 1)));
-#define HG_CASE(L)                                                        \
-  case L:                                                                 \
-    return vec4 ? launch_gather_t<L, 4>(a, nfix, nfix_l1, fixups, stream) \
+  if ((src_bf16 || dst_bf16) && (!vec4 || (src_bf16 && dst_bf16))) return hipErrorInvalidValue;
+#define HG_CASE(L)                                                                                       \
+  case L:                                                                                                \
+    if (src_bf16) return launch_gather_t<L, 4, bf16, float>(a, nfix, nfix_l1, fixups, stream);            \
+    if (dst_bf16) return launch_gather_t<L, 4, float, bf16>(a, nfix, nfix_l1, fixups, stream);            \
+    return vec4 ? launch_gather_t<L, 4>(a, nfix, nfix_l1, fixups, stream)                                \
                 : launch_gather_t<L, 1>(a, nfix, nfix_l1, fixups, stream);
   switch (lpr) {
     HG_CASE(1)
@@ -2137,10 +2227,11 @@ hipError_t launch_gather(const GatherArgs &a, int nfix, int nfix_l1, const Fixup
   return hipErrorInvalidValue;
 }
 
-hipError_t launch_fixups(const Fixup *fixups, int nfix, int nfix_l1, int32_t F, float *partial, float *Y,
+hipError_t launch_fixups(const Fixup *fixups, int nfix, int nfix_l1, int32_t F, float *partial, void *Y,
                          const float *scaleA, const float *scaleB, const int32_t *scale_map, bool vec4,
-                         hipStream_t stream, bool nt_dst) {
+                         hipStream_t stream, bool nt_dst, bool Y_bf16) {
   if (nfix == 0) return hipSuccess;
+  if (Y_bf16 && (!vec4 || (F & 3))) return hipErrorInvalidValue;
   GatherArgs a{};
   a.nt_dst = nt_dst ? 1 : 0;
   a.F = F;
@@ -2151,8 +2242,9 @@ hipError_t launch_fixups(const Fixup *fixups, int nfix, int nfix_l1, int32_t F, 
   a.scale_map = scale_map;
   const int lanes = vec4 ? (F + 3) / 4 : F;  // vec4 here: 16-byte lanes over rows of any width (loadu / store_n)
   const int lpr = std::min(64, next_pow2(std::max(lanes, 1)));
-#define HG_CASE(L) \
-  case L:          \
+#define HG_CASE(L)                                                                      \
+  case L:                                                                               \
+    if (Y_bf16) return launch_fixups_t<L, 4, bf16>(a, nfix, nfix_l1, fixups, stream);   \
     return vec4 ? launch_fixups_t<L, 4>(a, nfix, nfix_l1, fixups, stream) : launch_fixups_t<L, 1>(a, nfix, nfix_l1, fixups, stream);
   switch (lpr) {
     HG_CASE(1)
@@ -2174,23 +2266,26 @@ bool stream_rows_ok(const StreamArgs &a, bool vec4) {
 }
 
 template <int LPR>
-static hipError_t launch_stream_t(const StreamArgs &a, hipStream_t stream) {
+static hipError_t launch_stream_t(const StreamArgs &a, hipStream_t stream, bool src_bf16, bool dst_bf16) {
   constexpr int TW = LPR * 4;
   const dim3 grid(a.nrec, (a.F + TW - 1) / TW);
   const size_t lds = (size_t)a.max_rec_words * 4 + (size_t)2 * a.cap * 4;
+  if (src_bf16) return launch_lds<stream_rows_kernel<LPR, 4, 8, bf16, float>>(grid, lds, stream, a);
+  if (dst_bf16) return launch_lds<stream_rows_kernel<LPR, 4, 8, float, bf16>>(grid, lds, stream, a);
   return launch_lds<stream_rows_kernel<LPR, 4, 8>>(grid, lds, stream, a);
 }
 
-hipError_t launch_stream_rows(const StreamArgs &a, hipStream_t stream) {
+hipError_t launch_stream_rows(const StreamArgs &a, hipStream_t stream, bool src_bf16, bool dst_bf16) {
   if (a.nrec == 0) return hipSuccess;
+  if ((src_bf16 && dst_bf16) || ((src_bf16 || dst_bf16) && (a.F & 3))) return hipErrorInvalidValue;
   switch (fused_tile_row_floats(a.F, true) / 4) {
-    case 1: return launch_stream_t<1>(a, stream);
-    case 2: return launch_stream_t<2>(a, stream);
-    case 4: return launch_stream_t<4>(a, stream);
-    case 8: return launch_stream_t<8>(a, stream);
-    case 16: return launch_stream_t<16>(a, stream);
-    case 32: return launch_stream_t<32>(a, stream);
-    case 64: return launch_stream_t<64>(a, stream);
+    case 1: return launch_stream_t<1>(a, stream, src_bf16, dst_bf16);
+    case 2: return launch_stream_t<2>(a, stream, src_bf16, dst_bf16);
+    case 4: return launch_stream_t<4>(a, stream, src_bf16, dst_bf16);
+    case 8: return launch_stream_t<8>(a, stream, src_bf16, dst_bf16);
+    case 16: return launch_stream_t<16>(a, stream, src_bf16, dst_bf16);
+    case 32: return launch_stream_t<32>(a, stream, src_bf16, dst_bf16);
+    case 64: return launch_stream_t<64>(a, stream, src_bf16, dst_bf16);
   }
   return hipErrorInvalidValue;
 }
@@ -2199,7 +2294,7 @@ size_t hub_pass_lds_bytes(int32_t cap, int32_t row_floats, int32_t max_rec_words
   return (size_t)(cap + 1) * row_floats * 4 + (size_t)2 * max_rec_words * 4 + (size_t)2 * cap * 4 + 16;
 }
 
-template <int LPR>
+template <int LPR, typename T>
 static hipError_t launch_hub_t(const HubArgs &a, hipStream_t stream) {
   constexpr int TW = LPR * 4;
   if (a.ng != 1024 / LPR) return hipErrorInvalidValue;  // records were packed for another lane layout
@@ -2210,7 +2305,7 @@ static hipError_t launch_hub_t(const HubArgs &a, hipStream_t stream) {
   const size_t lds = hub_pass_lds_bytes(a.cap, TW, a.max_rec_words);
   if (a.cap < 1024 / LPR) return hipErrorInvalidValue;  // the end-of-launch reduction parks one row per lane group in the tile
   const int spec = (a.Xe_mat ? 1 : 0) | ((a.degE || a.W) ? 2 : 0) | (a.n_heavy > 0 ? 4 : 0);
-#define HG_HUB(M, S, H) return launch_lds<hub_pass_kernel<LPR, 4, 4, M, S, H>, 1024>(grid, lds, stream, a)
+#define HG_HUB(M, S, H) return launch_lds<hub_pass_kernel<LPR, 4, 4, M, S, H, T>, 1024>(grid, lds, stream, a)
   switch (spec) {
     case 0: HG_HUB(false, false, false);
     case 1: HG_HUB(true, false, false);
@@ -2224,21 +2319,25 @@ static hipError_t launch_hub_t(const HubArgs &a, hipStream_t stream) {
 #undef HG_HUB
 }
 
-hipError_t launch_hub_pass(const HubArgs &a0, bool vec4, hipStream_t stream) {
+hipError_t launch_hub_pass(const HubArgs &a0, bool vec4, hipStream_t stream, bool x_bf16) {
   HubArgs a = a0;
 #ifdef HG_TUNING
   if (const char *e = getenv("HG_HUB_DEBUG")) a.debug = atoi(e);  // ablation: 1 = no hop 1, 2 = no hop 2
 #endif
   if (a.nwg == 0) return hipSuccess;
   if (!vec4) return hipErrorInvalidValue;
+  if (x_bf16 && (a.F & 3)) return hipErrorInvalidValue;
   const int lpr = fused_tile_row_floats(a.F, true) / 4;
+#define HG_CASE(L) \
+  case L: return x_bf16 ? launch_hub_t<L, bf16>(a, stream) : launch_hub_t<L, float>(a, stream);
   switch (lpr) {
-    case 4: return launch_hub_t<4>(a, stream);
-    case 8: return launch_hub_t<8>(a, stream);
-    case 16: return launch_hub_t<16>(a, stream);
-    case 32: return launch_hub_t<32>(a, stream);
-    case 64: return launch_hub_t<64>(a, stream);
+    HG_CASE(4)
+    HG_CASE(8)
+    HG_CASE(16)
+    HG_CASE(32)
+    HG_CASE(64)
   }
+#undef HG_CASE
   return hipErrorInvalidValue;
 }
 
@@ -2260,10 +2359,12 @@ static int fused_dv_regs(const FusedArgs &a, int ng, size_t lds_without_scales, 
   return fit_without > fit_with ? 1 : 0;
 }
 
-template <int LPR, int VEC>
+// T: element type of the rows of X and Y.  bf16 (VEC = 4 only) takes the fp32 instances' decisions with no diagnostic forms.
+template <int LPR, int VEC, typename T = float>
 static hipError_t launch_fused_t(const FusedArgs &a, hipStream_t stream) {
   if (a.npanels == 0) return hipSuccess;
   constexpr int TW = LPR * VEC;
+  constexpr bool XF32 = std::is_same_v<T, float>;
   if constexpr (VEC == 4 && (LPR == 8 || LPR == 16)) {
     // a tiny dense hypergraph as one or a few 1024-thread panels (hg_api.hip, get_fused): nothing materialised there
     if (a.ng == 1024 / LPR) {
@@ -2271,8 +2372,8 @@ static hipError_t launch_fused_t(const FusedArgs &a, hipStream_t stream) {
       if (!fast || a.Wlin || a.Xe_mat) return hipErrorInvalidValue;
       const dim3 grid(a.npanels, (a.F + TW - 1) / TW);
       const size_t lds = (size_t)a.cap * TW * 4 + (size_t)a.max_rec_words * 4 + fused_scale_floats(a) * 4 + 16;  // dv_regs = 0
-      if (a.degE || a.W) return launch_lds<fused_packed_kernel<LPR, VEC, 8, true, false, true, false, false, 1024>, 1024>(grid, lds, stream, a);
-      return launch_lds<fused_packed_kernel<LPR, VEC, 8, true, false, false, false, false, 1024>, 1024>(grid, lds, stream, a);
+      if (a.degE || a.W) return launch_lds<fused_packed_kernel<LPR, VEC, 8, true, false, true, false, false, 1024, true, false, T>, 1024>(grid, lds, stream, a);
+      return launch_lds<fused_packed_kernel<LPR, VEC, 8, true, false, false, false, false, 1024, true, false, T>, 1024>(grid, lds, stream, a);
     }
   }
   if (a.ng != 256 / LPR) return hipErrorInvalidValue;  // records were packed for another lane layout
@@ -2290,7 +2391,7 @@ static hipError_t launch_fused_t(const FusedArgs &a, hipStream_t stream) {
     const bool fast = t.fused_fast && a.x_bytes > 0 && a.nrows_x < (1 << 24) && a.F < (1 << 22) &&
                       (!a.Xe_mat || (a.mat_bytes > 0 && a.nrows_mat < (1 << 24)));
     if (a.Wlin) {  // linear epilogue: eligibility was checked by fused_linear_ok
-      if constexpr (TW == 32 || TW == 64 || TW == 128) {
+      if constexpr (XF32 && (TW == 32 || TW == 64 || TW == 128)) {
         if (!fast || a.F != TW || a.rows_cap > 4 * (256 / LPR) || (a.F_out & 15)) return hipErrorInvalidValue;
         const size_t lds_l = lds_p - (size_t)a.cap * TW * 4 + (size_t)lin_tile_floats(a.cap, a.rows_cap, TW) * 4;  // slot tile / padded operand rows
         const int spec = (a.Xe_mat ? 1 : 0) | ((a.degE || a.W) ? 2 : 0);
@@ -2334,15 +2435,15 @@ static hipError_t launch_fused_t(const FusedArgs &a, hipStream_t stream) {
       }
     }
     if (fast) {
-      if (t.fused_debug)  // ablation / stamp run (diagnostic build): everything kept at run time
+      if (XF32 && t.fused_debug)  // ablation / stamp run (diagnostic build): everything kept at run time
         return launch_lds<fused_packed_kernel<LPR, VEC, 8, true, true, true, true>>(grid, lds_p, stream, ad);
       // A grid that does not even fill the chip once is latency-bound, not occupancy-bound:
       // put every row gather of a group in flight at once (U = 16) instead of two batches.
       const bool u16 = t.fused_u == 16 || (t.fused_small16 && a.npanels <= 512);
       const int spec = (a.Xe_mat ? 1 : 0) | ((a.degE || a.W) ? 2 : 0);
-#define HG_PK(UU, M, S) return launch_lds<fused_packed_kernel<LPR, VEC, UU, true, M, S, false>>(grid, lds_p, stream, ad)
+#define HG_PK(UU, M, S) return launch_lds<fused_packed_kernel<LPR, VEC, UU, true, M, S, false, false, 256, true, false, T>>(grid, lds_p, stream, ad)
 #ifdef HG_TUNING
-      if (t.fused_u == 12 || t.fused_u == 10) {  // diagnostic build: ten / twelve gathers in flight (unweighted, weighted; no materialised slots)
+      if (XF32 && (t.fused_u == 12 || t.fused_u == 10)) {  // diagnostic build: ten / twelve gathers in flight (unweighted, weighted; no materialised slots)
         if (spec == 0 && t.fused_u == 12) HG_PK(12, false, false);
         if (spec == 2 && t.fused_u == 12) HG_PK(12, false, true);
         if (spec == 0) HG_PK(10, false, false);
@@ -2369,7 +2470,7 @@ static hipError_t launch_fused_t(const FusedArgs &a, hipStream_t stream) {
     if (a.F & 3) return hipErrorInvalidValue;  // other widths ride on the range-checked buffer loads only (hg_api: wide_rows_ok)
   }
   if (a.Wlin) return hipErrorInvalidValue;
-  if constexpr (VEC == 1 && LPR >= 8) {  // F >= 5, not a multiple of 4 (class-count widths): the same buffer-load
+  if constexpr (XF32 && VEC == 1 && LPR >= 8) {  // F >= 5, not a multiple of 4 (class-count widths): the same buffer-load
                                           // loop, one dword per lane (+7-20 % at F = 7, 33; narrower rows: no gain)
     const bool fast = t.fused_fast && !t.fused_debug && a.x_bytes > 0 && a.nrows_x < (1 << 24) && a.F < (1 << 22) &&
                       (!a.Xe_mat || (a.mat_bytes > 0 && a.nrows_mat < (1 << 24)));
@@ -2379,6 +2480,7 @@ static hipError_t launch_fused_t(const FusedArgs &a, hipStream_t stream) {
       return launch_lds<fused_packed_kernel<LPR, VEC, 8, true, true, true, false>>(grid, lds_p, stream, ad);
     }
   }
+  if constexpr (!XF32) return launch_lds<fused_packed_kernel<LPR, VEC, 8, false, true, true, false, false, 256, true, false, T>>(grid, lds_p, stream, ad);
   return launch_lds<fused_packed_kernel<LPR, VEC, 8, false, true, true, kDbgFallback>>(grid, lds_p, stream, ad);
 }
 
@@ -2478,10 +2580,12 @@ hipError_t launch_linear(const LinearArgs &a, hipStream_t stream) {
 
 int fused_tile_row_floats(int F, bool vec4);
 
-hipError_t launch_fused(const FusedArgs &a, bool vec4, hipStream_t stream) {
+hipError_t launch_fused(const FusedArgs &a, bool vec4, hipStream_t stream, bool xy_bf16) {
   const int lpr = fused_tile_row_floats(a.F, vec4) / (vec4 ? 4 : 1);
-#define HG_CASE(L) \
-  case L:          \
+  if (xy_bf16 && (!vec4 || a.Wlin || (a.F & 3))) return hipErrorInvalidValue;
+#define HG_CASE(L)                                              \
+  case L:                                                       \
+    if (xy_bf16) return launch_fused_t<L, 4, bf16>(a, stream);   \
     return vec4 ? launch_fused_t<L, 4>(a, stream) : launch_fused_t<L, 1>(a, stream);
   switch (lpr) {
     HG_CASE(1)

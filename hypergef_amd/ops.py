@@ -132,8 +132,16 @@ def _flat(t):
     return None if t is None else t.reshape(-1)
 
 
+def _times_degV(g, degV):
+    """g * degV per row (the adjoint backward's input).  A bf16 g is multiplied in fp32 and rounded to bf16 once: torch
+    would promote the product to fp32 and send the backward through the fp32 kernels."""
+    if g.dtype == torch.bfloat16:
+        return (g.float() * degV.reshape(-1, 1)).to(torch.bfloat16)
+    return g * degV.reshape(-1, 1)
+
+
 def _forward(sched, csrptr_t, indices_t, node_feat, degE, degV, W, opt):
-    _check_feat(node_feat, "node_feat")
+    _check_feat(node_feat, "node_feat", bf16_ok=True)
     _check_index(csrptr_t, "csrptr_t")
     _check_index(indices_t, "indices_t")
     if node_feat.dim() != 2:
@@ -141,6 +149,8 @@ def _forward(sched, csrptr_t, indices_t, node_feat, degE, degV, W, opt):
     N, F = node_feat.shape
     degE, degV, W = _flat(degE), _flat(degV), _flat(W)
     variant = opt.variant
+    if node_feat.dtype == torch.bfloat16 and variant in ("push_atomic", "push_groups"):
+        raise TypeError("bfloat16 node_feat: the %s kernels are fp32 only (use auto, fused or pull)" % variant)
     if variant == "push_groups":
         key, row, st, ed = sched
         for n, t in (("balan_key", key), ("balan_row", row), ("group_st", st), ("group_ed", ed)):
@@ -185,7 +195,7 @@ class _SumAggr(torch.autograd.Function):
         if ctx.opt.backward == "reference" or degV is None:
             g = _forward(sched, csrptr_t, indices_t, grad_out, degE, degV, W, ctx.opt)
         else:
-            g = _forward(sched, csrptr_t, indices_t, grad_out * degV.reshape(-1, 1), degE, None, W, ctx.opt)
+            g = _forward(sched, csrptr_t, indices_t, _times_degV(grad_out, degV), degE, None, W, ctx.opt)
         return (None,) * 6 + (g, None, None, None, None)
 
 
@@ -193,7 +203,7 @@ def _rows_times(A, B, mode="auto"):
     """A . B for tall-skinny A [N, K], B [K, F]: the library's MFMA rows kernel where it takes the
     widths (1.4-1.5x rocBLAS at K <= 64), torch otherwise.  Backward-pass GEMMs use it."""
     K, F = B.shape
-    if mode != "never" and A.is_cuda and linear_supported(K, F) and A.shape[0] >= 4096:
+    if mode != "never" and A.is_cuda and A.dtype == B.dtype == torch.float32 and linear_supported(K, F) and A.shape[0] >= 4096:
         return linear_rows(A.contiguous(), B.t().contiguous())
     return A @ B
 
@@ -207,7 +217,7 @@ def _wgrad(A, B, mode="auto"):
     """A^T . B over the vertices (the linear's weight gradient): the library's streaming MFMA kernel
     where it takes the widths -- rocBLAS needs 1.2 ms for [64 x 693 k] x [693 k x 64], 17x the time of
     reading the operands -- torch otherwise."""
-    if mode != "never" and A.is_cuda and A.shape[0] >= 4096:
+    if mode != "never" and A.is_cuda and A.dtype == B.dtype == torch.float32 and A.shape[0] >= 4096:
         Fa, Fb = A.shape[1], B.shape[1]
         if wgrad_supported(Fa, Fb):
             return linear_wgrad(A.contiguous(), B.contiguous())
@@ -267,26 +277,29 @@ class _SumAggrLinear(torch.autograd.Function):
     @staticmethod
     def forward(ctx, csrptr_t, indices_t, node_feat, weight, degE, degV, W, opt=None):
         opt = ctx.opt = _opt(opt)
-        _check_feat(node_feat, "node_feat")
-        _check_feat(weight, "weight", device=node_feat.device)
+        _check_feat(node_feat, "node_feat", bf16_ok=True)
+        _check_feat(weight, "weight", device=node_feat.device, bf16_ok=True)
         _check_index(csrptr_t, "csrptr_t")
         _check_index(indices_t, "indices_t")
         if node_feat.dim() != 2 or weight.dim() != 2 or weight.shape[1] != node_feat.shape[1]:
             raise ValueError("node_feat must be [N, F_in] and weight [F_out, F_in]")
+        if weight.dtype != node_feat.dtype:
+            raise TypeError("weight must have node_feat's dtype %s, got %s" % (node_feat.dtype, weight.dtype))
+        f32 = node_feat.dtype == torch.float32  # bf16: torch's GEMM, then the bf16 aggregation (no bf16 MFMA epilogue)
         degE, degV, W = _flat(degE), _flat(degV), _flat(W)
         N, F_in = node_feat.shape
         F_out = weight.shape[0]
         variant = opt.variant
         plan = cached_plan(N, csrptr_t, indices_t)
         mode = opt.fuse_linear
-        fuse = (mode == "always" and linear_supported(F_in, F_out)) or \
-               (mode == "auto" and linear_fusion_pays(F_in, F_out))
+        fuse = f32 and ((mode == "always" and linear_supported(F_in, F_out)) or
+                        (mode == "auto" and linear_fusion_pays(F_in, F_out)))
         if fuse and variant in ("auto", "pull", "fused"):
             out = plan.aggregate_linear(csrptr_t, indices_t, node_feat, weight.detach().contiguous(),
                                         degE, degV, W, variant=variant, math=opt.linear_math)
         else:  # project, then aggregate at F_out (own MFMA rows kernel where it takes the widths)
             wd = weight.detach().contiguous()
-            Z = linear_rows(node_feat, wd) if linear_supported(F_in, F_out) and mode != "never" \
+            Z = linear_rows(node_feat, wd) if f32 and linear_supported(F_in, F_out) and mode != "never" \
                 else torch.nn.functional.linear(node_feat, wd)
             out = _SumAggrLinear._aggr(csrptr_t, indices_t, Z, degE, degV, W, opt)
         ctx.save_for_backward(node_feat, weight, csrptr_t, indices_t, degE, degV, W)
@@ -307,7 +320,7 @@ class _SumAggrLinear(torch.autograd.Function):
         if opt.backward == "reference" or degV is None:
             dZ = _SumAggrLinear._aggr(csrptr_t, indices_t, grad_out, degE, degV, W, opt)
         else:
-            dZ = _SumAggrLinear._aggr(csrptr_t, indices_t, grad_out * degV.reshape(-1, 1), degE, None, W, opt)
+            dZ = _SumAggrLinear._aggr(csrptr_t, indices_t, _times_degV(grad_out, degV), degE, None, W, opt)
         gx = _rows_times(dZ, weight, opt.fuse_linear) if ctx.needs_input_grad[2] else None
         gw = _wgrad(dZ, node_feat, opt.fuse_linear) if ctx.needs_input_grad[3] else None
         return None, None, gx, gw, None, None, None, None
@@ -325,26 +338,27 @@ class _AggrResLinear(torch.autograd.Function):
     @staticmethod
     def forward(ctx, csrptr_t, indices_t, node_feat, M, R, cb, degE, degV, W, ca, relu, need_t, opt=None):
         opt = ctx.opt = _opt(opt)
-        _check_feat(node_feat, "node_feat")
+        _check_feat(node_feat, "node_feat", bf16_ok=True)
         _check_index(csrptr_t, "csrptr_t")
         _check_index(indices_t, "indices_t")
         degE, degV, W = _flat(degE), _flat(degV), _flat(W)
         N, F_in = node_feat.shape
         F_out = M.shape[0]
+        f32 = node_feat.dtype == torch.float32  # bf16: the torch form around the bf16 aggregation (no bf16 MFMA epilogue)
         # cb is a Python float except where it is learned (UniGIN's 1 + eps): then it stays on the device -- the
         # kernel reads it there (hg_aggr_linear_res_dev_f32), nothing is read back, and the step can be captured
         if R is None:
             cbf = 0.0
         elif isinstance(cb, torch.Tensor):
-            cbf = cb.detach().to(torch.float32).reshape(1).contiguous()
+            cbf = cb.detach().to(torch.float32 if f32 else node_feat.dtype).reshape(1).contiguous()
         else:
             cbf = float(cb)
         variant = opt.variant if opt.variant != "push_groups" else "auto"
         Md = M.detach().contiguous()
         Rd = None if R is None else R.detach().contiguous()
         mode = opt.fuse_linear
-        fuse = (mode == "always" and linear_supported(F_in, F_out)) or \
-               (mode == "auto" and linear_fusion_pays(F_in, F_out))
+        fuse = f32 and ((mode == "always" and linear_supported(F_in, F_out)) or
+                        (mode == "auto" and linear_fusion_pays(F_in, F_out)))
         if fuse and variant in ("auto", "pull", "fused"):
             plan = cached_plan(N, csrptr_t, indices_t)
             T = torch.empty_like(node_feat) if need_t else None
@@ -381,7 +395,7 @@ class _AggrResLinear(torch.autograd.Function):
             if opt.backward == "reference" or degV is None:
                 gx = _SumAggrLinear._aggr(csrptr_t, indices_t, g_in, degE, degV, W, opt)
             else:
-                gx = _SumAggrLinear._aggr(csrptr_t, indices_t, g_in * degV.reshape(-1, 1), degE, None, W, opt)
+                gx = _SumAggrLinear._aggr(csrptr_t, indices_t, _times_degV(g_in, degV), degE, None, W, opt)
         gR = None
         if R is not None and ctx.needs_input_grad[4]:
             cbr = cbf / ca if fold else cbf  # dT already carries ca

@@ -187,11 +187,35 @@ class Plan:
                   out=None, workspace=None, bind_scales=True):
         """Y = degV . H (degE . W . (H^T X)) on X's device, current stream.
         bind_scales: see _bind_scales; pass False for scale vectors whose contents change
-        without torch noticing (numpy / DLPack aliases, `.data` writes, other libraries)."""
-        _check_feat(X, "node_feat")
+        without torch noticing (numpy / DLPack aliases, `.data` writes, other libraries).
+        X may be float32 or bfloat16; Y has X's dtype (so must `out`).  The scale vectors are float32 either way.  A bf16
+        call (hg_aggr_fused_bf16) accumulates in fp32 in the fp32 call's order and rounds once: for F % 4 == 0 its result
+        equals aggregate(X.float(), ...).to(torch.bfloat16) bit for bit.  bf16 rows of other widths are padded with zero
+        columns to the next multiple of 4 and the result sliced back -- that path copies X and Y, and runs at the padded
+        width F4: a caller's workspace is used there if it holds workspace_bytes(F4), else the call takes its own.  A
+        bf16 X or out whose data is not 8-byte aligned is copied too."""
+        bf16 = isinstance(X, torch.Tensor) and X.dtype == torch.bfloat16
+        _check_feat(X, "node_feat", bf16_ok=True)
         if X.shape[0] != self.N:
             raise ValueError("node_feat has %d rows, hypergraph has %d vertices" % (X.shape[0], self.N))
         F = X.shape[1]
+        if out is not None and (not isinstance(out, torch.Tensor) or out.dtype != X.dtype):
+            raise TypeError("out must have node_feat's dtype %s, got %s" % (X.dtype, getattr(out, "dtype", type(out))))
+        if bf16 and (F % 4 != 0 or X.data_ptr() % 8 != 0 or (out is not None and out.data_ptr() % 8 != 0)):
+            # hg_aggr_fused_bf16 takes whole four-column lanes at 8-byte alignment: pad / copy, aggregate, slice back
+            F4 = (F + 3) // 4 * 4
+            if F4 == F:
+                Xp = X if X.data_ptr() % 8 == 0 else X.clone()
+            else:
+                Xp = torch.zeros((self.N, F4), dtype=X.dtype, device=X.device)
+                Xp[:, :F] = X
+            if workspace is not None and workspace.numel() * workspace.element_size() < self.workspace_bytes(F4):
+                workspace = None  # sized for F, not for the padded width: this path copies anyway, take an own one
+            Yp = self.aggregate(csrptr_t, colind_t, Xp, degE, degV, W, variant, None, workspace, bind_scales)
+            if out is None:
+                return Yp[:, :F].contiguous() if F4 != F else Yp
+            out.copy_(Yp[:, :F])
+            return out
         for name, t, n in (("degE", degE, self.M), ("degV", degV, self.N), ("W", W, self.M)):
             if t is not None:
                 _check_feat(t, name, device=X.device)
@@ -201,7 +225,7 @@ class Plan:
         stream = torch.cuda.current_stream(X.device)  # looked up once per call: it is a measurable share of a launch-bound call
         if (degE is not None or degV is not None or W is not None) and variant in ("auto", "fused"):
             self._bind_scales(F, degE, degV, W, X.device, bind_scales, stream)
-        Y = out if out is not None else torch.empty((self.N, F), dtype=torch.float32, device=X.device)
+        Y = out if out is not None else torch.empty((self.N, F), dtype=X.dtype, device=X.device)
         if variant == "fused":  # hg_plan_workspace_bytes sizes for what AUTO runs; a forced fused call needs its schedule first
             self._ensure_fused(F)
         own_ws = workspace is None
@@ -211,16 +235,15 @@ class Plan:
             nbytes = workspace.numel() * workspace.element_size()
         with torch.cuda.device(X.device):
             args = (self._h, F, _ptr(csrptr_t), _ptr(colind_t), _ptr(X), _ptr(degE), _ptr(degV), _ptr(W), _ptr(Y))
-            st = _lib.lib().hg_aggr_fused_f32(*args, _ptr(workspace), nbytes, _lib.VARIANTS[variant],
-                                              ctypes.c_void_p(stream.cuda_stream))
+            entry = _lib.lib().hg_aggr_fused_bf16 if bf16 else _lib.lib().hg_aggr_fused_f32
+            st = entry(*args, _ptr(workspace), nbytes, _lib.VARIANTS[variant], ctypes.c_void_p(stream.cuda_stream))
             if st == _lib.HG_ERR_WORKSPACE and own_ws:
                 # The cached size is stale: the call itself built a layout for this width that needs more (e.g. AUTO on an
                 # unaligned view of X with N >= 2^24 takes another schedule than the one the size was asked for).  Nothing
                 # was written; ask again and retry once.
                 self.__dict__.setdefault("_ws_bytes", {}).pop(F, None)
                 workspace, nbytes = self._workspace(F, X.device)
-                st = _lib.lib().hg_aggr_fused_f32(*args, _ptr(workspace), nbytes, _lib.VARIANTS[variant],
-                                                  ctypes.c_void_p(stream.cuda_stream))
+                st = entry(*args, _ptr(workspace), nbytes, _lib.VARIANTS[variant], ctypes.c_void_p(stream.cuda_stream))
             _lib.check(st)
         return Y
 
@@ -519,9 +542,9 @@ def _check_index(t, name):
         raise RuntimeError("%s must be contiguous" % name)
 
 
-def _check_feat(t, name, device=None):
-    if not isinstance(t, torch.Tensor) or t.dtype != torch.float32:
-        raise TypeError("%s must be a float32 tensor" % name)
+def _check_feat(t, name, device=None, bf16_ok=False):
+    if not isinstance(t, torch.Tensor) or not (t.dtype == torch.float32 or (bf16_ok and t.dtype == torch.bfloat16)):
+        raise TypeError("%s must be a float32%s tensor" % (name, " or bfloat16" if bf16_ok else ""))
     if not t.is_cuda:
         raise RuntimeError("%s must be on a GPU (no CPU fallback in this backend)" % name)
     if not t.is_contiguous():

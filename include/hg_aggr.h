@@ -260,6 +260,28 @@ HG_API int hg_aggr_fused_f32(const hg_plan *plan, int32_t F,
                       size_t workspace_bytes, int32_t variant,
                       hg_stream_t stream);
 
+/* The same aggregation with X and Y in bf16 (bit patterns, row-major [N, F]); the arguments are those of
+ * hg_aggr_fused_f32 and the call takes the same plan, scale vectors, workspace and stream.
+ * Numerical contract:
+ *   degE, degV, W stay fp32.  Everything between X and Y is fp32: the LDS hyperedge tile, the materialised
+ *   hyperedge table, the partial rows of split vertices and of the hub pass, the workspace.  Each element is
+ *   accumulated in fp32 in exactly the order the fp32 call uses and rounded to bf16 once, to nearest even
+ *   (NaN stays NaN: the rounding of torch's .to(torch.bfloat16)).  The call runs the schedule and the AUTO
+ *   choice of an fp32 call of the same width and builds none of its own.  bf16 -> fp32 is exact, so for
+ *   X below 2 GiB as fp32:
+ *     hg_aggr_fused_bf16(X)  ==  round_bf16(hg_aggr_fused_f32(fp32(X)))   bit for bit,
+ *   any shape, weighted or not, HG_VARIANT_AUTO / FUSED / PULL.
+ *   The workspace is the fp32 call's: hg_plan_workspace_bytes answers for both forms.
+ * Returns HG_ERR_UNSUPPORTED (message through hg_last_error) for HG_VARIANT_PUSH_ATOMIC, F % 4 != 0, or X / Y
+ * not 8-byte aligned; a caller pads narrower rows with zero columns.  Detect it by the exported symbol
+ * (HG_AGGR_VERSION does not change). */
+HG_API int hg_aggr_fused_bf16(const hg_plan *plan, int32_t F,
+                      const int32_t *csrptr_t, const int32_t *colind_t,
+                      const uint16_t *X, const float *degE, const float *degV,
+                      const float *W, uint16_t *Y, void *workspace,
+                      size_t workspace_bytes, int32_t variant,
+                      hg_stream_t stream);
+
 /* Aggregation with the layer's dense projection folded in: the
  * reference's HyperGsysHGNN / HyperGsysUinGINConv.forward run `X = self.W(X)` (nn.Linear
  * without bias, model/ugsys/hgnn.py:22-23, unigin.py:20-21) and then the aggregation on

@@ -56,6 +56,8 @@ def parse():
                         "such an epoch is ~100 launches of host latency; the eager figures are printed beside the replays")
     p.add_argument("--linear-math", default="f32", choices=["f32", "bf16x6"],
                    help="hgsys backend, layers fused at nhid = 128 on batches: fp32 MFMA, or six bf16 products per fp32 product")
+    p.add_argument("--dtype", default="float32", choices=["float32", "bfloat16"],
+                   help="features and parameters (model.to(dtype)); the hypergraph's scale vectors stay fp32")
     p.add_argument("--output", type=str, default=None)
     return p.parse_args()
 
@@ -82,7 +84,8 @@ def main():
     base = {"cora": synth.cora_shape, "citeseer": synth.citeseer_shape, "pubmed": synth.pubmed_shape}[args.dname]()
     inc = synth.replicate_block_diagonal(base, args.replicas)
     hyperg = hg.HyperGraph.from_incidence(inc, dev, data_name=args.dname)
-    X = torch.randn(inc.N, args.nfeat, device=dev)
+    dtype = getattr(torch, args.dtype)
+    X = torch.randn(inc.N, args.nfeat, device=dev).to(dtype)
     y = torch.randint(0, args.nclass, (inc.N,), device=dev)
     perm = torch.randperm(inc.N, device=dev)
     train_idx = perm[: int(args.train_prop * inc.N)]
@@ -93,6 +96,8 @@ def main():
     else:
         model = models.UniGCNII(args, hyperg, args.nfeat, args.nhid, args.nclass, args.nlayer, args.nhead)
     model.to(dev)
+    if dtype != torch.float32:
+        model.to(dtype)
     if world > 1:
         model = torch.nn.parallel.DistributedDataParallel(
             model, device_ids=[dev.index] if dev.type == "cuda" else None)
