@@ -326,6 +326,11 @@ class _SumAggrLinear(torch.autograd.Function):
         return None, None, gx, gw, None, None, None, None
 
 
+# ca folds into M (backward of _AggrResLinear) only inside [2^-64, 2^64]: there M * ca and cb / ca stay far inside fp32's normal
+# range (2^-126 .. 2^128) for weights and mixing factors of any ordinary size, so nothing flushes to zero or overflows
+_FOLD_MIN, _FOLD_MAX = 2.0 ** -64, 2.0 ** 64
+
+
 class _AggrResLinear(torch.autograd.Function):
     """Y = act((ca * Aggr(X) + cb * R) . M^T): a whole UniGNN layer as one node
     (hg_aggr_linear_res_f32).  UniGCNII (model/ugsys/unigcnii.py:19-21 + the relu of model/gnn.py:199):
@@ -385,20 +390,22 @@ class _AggrResLinear(torch.autograd.Function):
         opt = ctx.opt
         need_gcb = R is not None and ctx.needs_input_grad[5]
         # dX wants ca * (dP . M): the factor rides in the [F_out, F_in] matrix (one tiny kernel) instead of an [N, F] pass over
-        # the product, unless the unscaled product is needed for d cb (UniGIN, where ca = 1 anyway)
-        fold = ca != 1.0 and not need_gcb
+        # the product, unless the unscaled product is needed for d cb (UniGIN, where ca = 1 anyway) or ca cannot be divided
+        # out again for dR (zero, or so small that M * ca or cb / ca leaves fp32's normal range)
+        fold = ctx.needs_input_grad[2] and not need_gcb and ca != 1.0 and _FOLD_MIN <= abs(ca) <= _FOLD_MAX
         dT = _rows_times(dP, M * ca if fold else M, opt.fuse_linear)
         gM = _wgrad(dP, T, opt.fuse_linear) if ctx.needs_input_grad[3] else None
         gx = None
         if ctx.needs_input_grad[2]:
-            g_in = dT if (fold or ca == 1.0) else dT * ca  # UniGIN: ca = 1 -- no [N, F] kernel for a multiplication by one
             if opt.backward == "reference" or degV is None:
-                gx = _SumAggrLinear._aggr(csrptr_t, indices_t, g_in, degE, degV, W, opt)
+                gx = _SumAggrLinear._aggr(csrptr_t, indices_t, dT, degE, degV, W, opt)
             else:
-                gx = _SumAggrLinear._aggr(csrptr_t, indices_t, _times_degV(g_in, degV), degE, None, W, opt)
+                gx = _SumAggrLinear._aggr(csrptr_t, indices_t, _times_degV(dT, degV), degE, None, W, opt)
+            if not fold and ca != 1.0:  # UniGIN: ca = 1 -- no [N, F] kernel for a multiplication by one
+                gx = gx * ca  # after the aggregation: a subnormal ca rounds once, at the end
         gR = None
         if R is not None and ctx.needs_input_grad[4]:
-            cbr = cbf / ca if fold else cbf  # dT already carries ca
+            cbr = cbf / ca if fold else cbf  # a folded dT carries ca
             gR = dT if (not isinstance(cbr, torch.Tensor) and cbr == 1.0) else dT * cbr
         gcb = (dT * R).sum() if need_gcb else None
         return None, None, gx, gM, gR, gcb, None, None, None, None, None, None, None
