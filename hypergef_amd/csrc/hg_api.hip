@@ -29,7 +29,7 @@ size_t round256(size_t x) { return (x + 255) & ~(size_t)255; }
 bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 // four elements of a row: 16 bytes of fp32, 8 bytes of bf16 -- what a 16-byte (fp32) lane holds
 bool aligned_lane(const void *p, bool bf16) { return (reinterpret_cast<uintptr_t>(p) & (bf16 ? 7 : 15)) == 0; }
-// rows of an output table are whole, aligned 64-byte units: where the streaming (nt) store hint pays (hg_kernels.hip, HG_Y_NT);
+// rows of an output table are whole, aligned 64-byte units: where the streaming (nt) store hint pays (hg_kernels.hip);
 // decided on the row's bytes (bf16: F % 32 == 0)
 bool rows_whole_64(const void *base, int32_t F, bool bf16 = false) {
   return ((int64_t)F * (bf16 ? 2 : 4)) % 64 == 0 && (reinterpret_cast<uintptr_t>(base) & 63) == 0;
@@ -190,22 +190,12 @@ bool lin_caps(const hg_plan *p, int32_t F, bool vec4, int32_t &cap, int32_t &mem
   // workgroups instead of seven -- and changed nothing: 32 -> 32 0.209-0.213 ms either way, 32 -> 64 -1 % (9 % more panels
   // eat the eighth workgroup; profiles/r04_experiments.md).
   if (!vec4 || F != 128 || !p->opts.fused_tile_auto || p->opts.fused_steps > 0 || p->nnz <= (1 << 18)) return false;
-  int pct = 150;
-#ifdef HG_TUNING
-  if (const char *e = getenv("HG_LIN_SLOTS_PCT")) pct = atoi(e);  // diagnostic build: 0 = the default schedule
-#endif
-  if (pct <= 0) return false;
+  const int pct = 150;
   fused_caps(p, F, vec4, cap, mem_cap);
   const int32_t ng = 256 / (hg::fused_tile_row_floats(F, vec4) / 4);
   rows_cap = std::min(cap, 4 * ng);
-#ifdef HG_TUNING
-  if (const char *e = getenv("HG_LIN_ROWS_CAP")) rows_cap = std::max(16, std::min(rows_cap, atoi(e) / 8 * 8));
-#endif
   cap = std::max(cap, (rows_cap * pct / 100 + 7) / 8 * 8);
   mem_cap = cap * 4;
-#ifdef HG_TUNING
-  if (const char *e = getenv("HG_LIN_STEPS")) mem_cap = std::max(p->opts.t_big, std::min(mem_cap, atoi(e) * ng));  // whole batches of row loads
-#endif
   return true;
 }
 
@@ -504,7 +494,7 @@ int run_hop(const hg_plan *p, int hop, int32_t F, const int32_t *ptr, const int3
   // Streaming (nt) stores for the hop's output: always for hop 2 (rows of Y); for hop 1 when Xe [M, F] is larger than
   // about three quarters of the 256 MiB Infinity Cache -- a smaller table is read straight back from it by hop 2 and plain stores keep it
   // there (same-box A/B, profiles/r03_experiments.md: 348-695 MB tables -3..-6 %, 2-143 MB tables +9..+16 % with nt)
-  // -- and only for rows of whole 64-byte units (F % 16 == 0): others lose with the hint (hg_kernels.hip, HG_Y_NT)
+  // -- and only for rows of whole 64-byte units (F % 16 == 0): others lose with the hint (hg_kernels.hip)
   const bool nt_out = rows_whole_64(dst, F, dst_bf16) && (hop == 1 || (int64_t)p->M * F * 4 >= ((int64_t)192 << 20));
   int kind = 0;  // hg_plan_tune_f32's choice for this hop and width: 0 streaming, 1 panels + tasks, 2 latency schedule
   {
@@ -880,41 +870,6 @@ int hg_plan_prepare(const hg_plan *p, int32_t F, hg_fused_info *info) {
     info->lds_bytes = (int32_t)((size_t)f->cap * hg::fused_tile_row_floats(F, plan_vec4(p, F)) * 4 + (size_t)f->max_rec_words * 4 + 16);
     info->reserved = 0;
   }
-  return HG_OK;
-}
-
-// Diagnostic only (not declared in hg_aggr.h): per-phase cycle counters of the
-// fused kernel when HG_FUSED_DEBUG has bit 32 set.
-__attribute__((visibility("default"))) int hg_debug_read_stamps(unsigned long long *out16, int reset) {
-  return hg::read_stamps(out16, reset != 0) == hipSuccess ? HG_OK : HG_ERR_HIP;
-}
-
-// Diagnostic only (not declared in hg_aggr.h): sustained rate of v_mfma_f32_16x16x4_f32 from registers.  out3 = {seconds,
-// TFLOP/s, shader-clock ticks (s_memtime) of one wave}; blocks x 4 waves, iters x 16 MFMAs per wave.
-__attribute__((visibility("default"))) int hg_debug_mfma_rate(int32_t blocks, int32_t iters, double *out3) {
-  float *sink = nullptr;
-  unsigned long long *ticks = nullptr, h_ticks = 0;
-  HG_HIP(hipMalloc(reinterpret_cast<void **>(&sink), 16));
-  HG_HIP(hipMalloc(reinterpret_cast<void **>(&ticks), 8));
-  hipEvent_t e0, e1;
-  HG_HIP(hipEventCreate(&e0));
-  HG_HIP(hipEventCreate(&e1));
-  HG_HIP(hg::launch_mfma_rate(blocks, iters, sink, ticks, nullptr));  // warm-up
-  HG_HIP(hipEventRecord(e0, nullptr));
-  HG_HIP(hg::launch_mfma_rate(blocks, iters, sink, ticks, nullptr));
-  HG_HIP(hipEventRecord(e1, nullptr));
-  HG_HIP(hipEventSynchronize(e1));
-  float ms = 0.f;
-  HG_HIP(hipEventElapsedTime(&ms, e0, e1));
-  HG_HIP(hipMemcpy(&h_ticks, ticks, 8, hipMemcpyDeviceToHost));
-  (void)hipFree(sink);
-  (void)hipFree(ticks);
-  (void)hipEventDestroy(e0);
-  (void)hipEventDestroy(e1);
-  const double flop = (double)blocks * 4.0 * iters * 16.0 * 2048.0;
-  out3[0] = ms * 1e-3;
-  out3[1] = flop / (ms * 1e-3) / 1e12;
-  out3[2] = (double)h_ticks;
   return HG_OK;
 }
 

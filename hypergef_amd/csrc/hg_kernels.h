@@ -68,7 +68,6 @@ struct FusedArgs {
   int32_t mat_bytes;      // same for the materialised table
   int32_t nrows_x;        // rows of X
   int32_t nrows_mat = 0;  // rows of the materialised table
-  int32_t debug = 0;      // ablation / stamp bits (experiments only)
   int32_t y_nt = 0;       // rows of Y leave with the streaming (nt) hint: set for rows of whole 64-byte units (F % 16 == 0)
   int32_t reverse_runs = 0;  // each XCD walks its run of panels backwards (set after a substantial materialisation pre-pass)
   // fused linear epilogue (hg_aggr_linear_f32): Y[N, F_out] = (aggregated rows) * Wlin^T
@@ -102,7 +101,6 @@ struct HubArgs {
   int32_t x_bytes, mat_bytes, nrows_x, nrows_mat;
   int32_t n_heavy = 0;  // hubs fed by stream flags (bits 24..27 of a slot's last entry)
   int32_t hslot0[kHubHeavy] = {};  // their first partial rows
-  int32_t debug = 0;    // ablation bits, diagnostic build only
 };
 
 // stream_rows_kernel (RowStream, hg_internal.h)
@@ -151,8 +149,6 @@ hipError_t launch_wgrad(int64_t nrows, int32_t Fa, int32_t Fb, const float *A, c
 hipError_t launch_linear_pack(int32_t F_out, int32_t F_in, const float *Wlin, float *wfrag, hipStream_t stream);
 hipError_t launch_linear_pack_split(int32_t F_out, int32_t F_in, const float *Wlin, void *wsplit, hipStream_t stream);
 int fused_tile_row_floats(int F, bool vec4);
-hipError_t read_stamps(unsigned long long *out, bool reset);
-hipError_t launch_mfma_rate(int blocks, int iters, float *sink, unsigned long long *ticks, hipStream_t stream);
 hipError_t launch_push(const PushArgs &a, hipStream_t stream);
 hipError_t launch_bind_scales(int64_t nslots, const int32_t *eid_all, const float *degE, const float *W,
                               float *bsA, float *bsB, int64_t nrows, const int32_t *prow, const float *degV,

@@ -9,9 +9,6 @@
 #include <hip/hip_runtime.h>
 
 #include <atomic>
-#include <cstdio>
-#include <cstdlib>
-
 #include <type_traits>
 
 #include "hg_kernels.h"
@@ -20,24 +17,11 @@ namespace hg {
 
 // Waves per SIMD linear_rows_kernel is compiled for at K <= 64 (tools/linear_probe.py, 2.77 M rows): 64 x 64: 8 waves
 // 0.550 ms (spills; rocBLAS 0.427), 7 0.315, 6 0.311; 32 x 32: 8 waves 0.147, 7 0.141, 6 0.149.
-#ifndef HG_ROWS_WAVES
-#define HG_ROWS_WAVES 7
-#endif
+constexpr int kRowsWaves = 7;
 // Rows of Y leave the panel kernel with the streaming (nt) hint where a row is whole 64-byte units (F % 16 == 0: the
 // host sets FusedArgs::y_nt / GatherArgs::nt_dst / StreamArgs::nt_dst): +3..8 % there, F = 16 0.45 -> 0.72 of the
 // roofline; rows that end inside a 64-byte unit (F = 4 .. 28, 33) lose 7-50 % with it -- the L2 merges their partial
-// lines only on the plain write-back path (tools/nt_widths.sh, profiles/r03_experiments.md).
-#ifndef HG_Y_NT
-#define HG_Y_NT 1
-#endif
-// Panel records are read once per launch: HG_REC_NT = 1 copies them with the streaming hint as well.
-#ifndef HG_REC_NT
-#define HG_REC_NT 0
-#endif
-// HG_X_NT = 1: the panel kernel's gathers of X rows carry the streaming hint too (experiment).
-#ifndef HG_X_NT
-#define HG_X_NT 0
-#endif
+// lines only on the plain write-back path (profiles/r03_experiments.md; script removed, see git history).
 template <int VEC> struct Vec;
 template <> struct Vec<1> {
   float x;
@@ -46,13 +30,9 @@ template <> struct Vec<1> {
   __device__ __forceinline__ static Vec load_buf(__amdgpu_buffer_rsrc_t r, unsigned off) {
     return Vec{__builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, off, 0, 0))};
   }
-  __device__ __forceinline__ static Vec load_buf_nt(__amdgpu_buffer_rsrc_t r, unsigned off) {
-    return Vec{__builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, off, 0, 2))};
-  }
   __device__ __forceinline__ static Vec loadu(const float *p) { return Vec{*p}; }
   __device__ __forceinline__ void store(float *p) const { *p = x; }
   __device__ __forceinline__ void store_n(float *p, int) const { *p = x; }
-  __device__ __forceinline__ void store_nt(float *p) const { __builtin_nontemporal_store(x, p); }
   __device__ __forceinline__ void store_n_nt(float *p, int) const { __builtin_nontemporal_store(x, p); }
   __device__ __forceinline__ void add(const Vec &o) { x += o.x; }
   __device__ __forceinline__ void mul(float s) { x *= s; }
@@ -67,10 +47,6 @@ template <> struct Vec<4> {
   __device__ __forceinline__ static Vec load_buf(__amdgpu_buffer_rsrc_t r, unsigned off) {
     typedef unsigned u4 __attribute__((ext_vector_type(4)));
     return Vec{__builtin_bit_cast(float4, (u4)__builtin_amdgcn_raw_buffer_load_b128(r, off, 0, 0))};
-  }
-  __device__ __forceinline__ static Vec load_buf_nt(__amdgpu_buffer_rsrc_t r, unsigned off) {  // cache policy bit 1 = nt
-    typedef unsigned u4 __attribute__((ext_vector_type(4)));
-    return Vec{__builtin_bit_cast(float4, (u4)__builtin_amdgcn_raw_buffer_load_b128(r, off, 0, 2))};
   }
   __device__ __forceinline__ void store(float *p) const { *reinterpret_cast<float4 *>(p) = v; }
   // Rows whose width is not a multiple of four floats (or whose base is only 4-byte aligned) still move as
@@ -159,8 +135,9 @@ template <> struct Rows<bf16, 4> {
 // loads, then every LPR-lane group walks a contiguous run of the panel's rows as
 // one flat entry stream, U row loads in flight, adding in CSR order (so short
 // rows reproduce the CPU reference's summation order exactly).  TS / TD: element types of src / dst rows (Rows).
-template <int LPR, int VEC, int U, bool PIPE, typename TS = float, typename TD = float>
+template <int LPR, int VEC, typename TS = float, typename TD = float>
 __global__ __launch_bounds__(256) void gather_rows_kernel(const GatherArgs a) {
+  constexpr int U = 4;           // row loads in flight per lane (8, or two batches in flight: within 3 %, profiles/r01_fused_experiments.md)
   constexpr int G = 64 / LPR;    // row groups per wave
   constexpr int NG = 256 / LPR;  // row groups per workgroup
   using V = Vec<VEC>;
@@ -203,7 +180,7 @@ __global__ __launch_bounds__(256) void gather_rows_kernel(const GatherArgs a) {
         const int64_t drow = a.dst_map ? a.dst_map[tk.row] : tk.row;
         if (a.scaleA) acc.mul(a.scaleA[srow]);
         if (a.scaleB) acc.mul(a.scaleB[srow]);
-        if (HG_Y_NT && a.nt_dst) RD::store_n_nt(acc, dst + drow * F + col, VEC);
+        if (a.nt_dst) RD::store_n_nt(acc, dst + drow * F + col, VEC);
         else RD::store(acc, dst + drow * F + col);
       } else {
         acc.store(a.partial + (int64_t)tk.slot * F + col);
@@ -250,7 +227,7 @@ __global__ __launch_bounds__(256) void gather_rows_kernel(const GatherArgs a) {
     }
     const int64_t drow = a.dst_map ? sdst[row] : pn.row0 + row;
     if (col_ok) {
-      if (HG_Y_NT && a.nt_dst) RD::store_n_nt(acc, dst + drow * F + col, VEC);
+      if (a.nt_dst) RD::store_n_nt(acc, dst + drow * F + col, VEC);
       else RD::store(acc, dst + drow * F + col);
     }
   };
@@ -282,30 +259,12 @@ __global__ __launch_bounds__(256) void gather_rows_kernel(const GatherArgs a) {
     }
   };
 
-  if constexpr (PIPE) {
-    // two batches in flight: the next batch's loads are issued before the
-    // current one is consumed, so the wave always has row loads outstanding
-    V cur[U];
-    int ncur = min(U, stop - pos);
-    if (ncur > 0) issue(pos, ncur, cur);
-    while (ncur > 0) {
-      V nxt[U];
-      const int nn = min(U, stop - pos - ncur);
-      if (nn > 0) issue(pos + ncur, nn, nxt);
-      consume(pos, ncur, cur);
-      pos += ncur;
-      ncur = nn;
-#pragma unroll
-      for (int k = 0; k < U; k++) cur[k] = nxt[k];
-    }
-  } else {
-    while (pos < stop) {
-      const int n = min(U, stop - pos);
-      V v[U];
-      issue(pos, n, v);
-      consume(pos, n, v);
-      pos += n;
-    }
+  while (pos < stop) {
+    const int n = min(U, stop - pos);
+    V v[U];
+    issue(pos, n, v);
+    consume(pos, n, v);
+    pos += n;
   }
   while (r < re) {
     flush(r, acc);
@@ -348,69 +307,9 @@ __global__ __launch_bounds__(256) void fixup_rows_kernel(const GatherArgs a, con
   if (a.scaleA) acc.mul(a.scaleA[srow]);
   if (a.scaleB) acc.mul(a.scaleB[srow]);
   TD *dst = static_cast<TD *>(a.dst);
-  if (HG_Y_NT && a.nt_dst) RD::store_n_nt(acc, dst + drow * F + col, a.F - col);
+  if (a.nt_dst) RD::store_n_nt(acc, dst + drow * F + col, a.F - col);
   else RD::store_n(acc, dst + drow * F + col, a.F - col);
 }
-
-// Diagnostic stamps: lane 0 of every wave adds the ticks since the previous stamp to a
-// global counter per phase.  Compiled only into the diagnostic library (`make stamps`,
-// -DHG_STAMPS, then HG_FUSED_DEBUG bit 32); the production kernels carry no stamp code.
-__device__ unsigned long long hg_stamps[16];
-#ifdef HG_STAMPS
-// ticks are summed per wave (scalar registers) and added to the global counters once, at flush(): one
-// atomic per phase and wave -- an atomic at every stamp serialises thousands of waves on a few addresses and
-// ends up measuring itself
-struct Stamper {
-  bool on = false;
-  unsigned long long st[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-  unsigned long long t0 = 0;
-  unsigned long long c0 = 0, r0 = 0;  // shader-clock and 100 MHz wall-clock readings at init: their deltas (counters 13, 14) give the clock
-  __device__ __forceinline__ void init(bool cond) {
-    on = cond;
-    t0 = on ? __builtin_amdgcn_s_memtime() : 0;
-    c0 = t0;
-    r0 = on ? __builtin_amdgcn_s_memrealtime() : 0;
-  }
-  __device__ __forceinline__ void mark(int i) {
-    if (on) {
-      const unsigned long long t1 = __builtin_amdgcn_s_memtime();
-      st[i] += t1 - t0;
-      t0 = t1;
-    }
-  }
-  __device__ __forceinline__ void flush() {
-    if (on) {
-      st[13] = __builtin_amdgcn_s_memtime() - c0;
-      st[14] = __builtin_amdgcn_s_memrealtime() - r0;
-    }
-    if (on && (threadIdx.x & 63) == 0)
-      for (int i = 0; i < 16; i++)
-        if (st[i]) atomicAdd(&hg_stamps[i], st[i]);
-  }
-};
-#define HG_STAMP_INIT(cond) \
-  Stamper stp;              \
-  stp.init(((a.debug & 32) != 0) && (cond) && (blockIdx.x & 63) == 5)  /* one workgroup in 64: the flush's atomics stay out of the way */
-#else
-struct Stamper {
-  __device__ __forceinline__ void init(bool) {}
-  __device__ __forceinline__ void mark(int) {}
-  __device__ __forceinline__ void flush() {}
-};
-#define HG_STAMP_INIT(cond) [[maybe_unused]] Stamper stp
-#endif
-#define HG_STAMP(i) stp.mark(i)
-#ifdef HG_STAMPS
-// stamp 12: how long the wave's own stores take to be acknowledged after their issue (the wave cannot retire before)
-#define HG_STAMP_FLUSH()                                  \
-  do {                                                    \
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      \
-    stp.mark(12);                                         \
-    stp.flush();                                          \
-  } while (0)
-#else
-#define HG_STAMP_FLUSH() stp.flush()
-#endif
 
 // Workgroup barrier that orders LDS traffic only.  __syncthreads() also drains the
 // vector-memory counter, which on CDNA4 counts stores: in a persistent loop that would
@@ -596,8 +495,7 @@ __device__ __forceinline__ void panel_times_wt_staged(float *t, int nrows, int F
     const int64_t yrow = rowmap ? (int64_t)rowmap[r] : row0 + r;
     float4 o = *reinterpret_cast<const float4 *>(t + r * LD + c);
     if (relu) o = make_float4(fmaxf(o.x, 0.f), fmaxf(o.y, 0.f), fmaxf(o.z, 0.f), fmaxf(o.w, 0.f));
-    if (HG_Y_NT) Vec<4>{o}.store_nt(Y + yrow * F_out + c);
-    else *reinterpret_cast<float4 *>(Y + yrow * F_out + c) = o;
+    Vec<4>{o}.store_nt(Y + yrow * F_out + c);
   }
 }
 
@@ -659,7 +557,7 @@ __device__ __forceinline__ void mfma_rows_chunked(const float *ta, int tstep, co
 template <int KSTEPS, int NPW>
 __device__ __forceinline__ void panel_times_wt_staged_chunked(float *t, int nrows, int F_out, const float *Wlin,
                                                               const int32_t *rowmap, int64_t row0, float *Y, int tid,
-                                                              float (&bpre)[8], int relu, Stamper &stp) {
+                                                              float (&bpre)[8], int relu) {
   constexpr int K = KSTEPS * 4, LD = K + 4, RPN = 4 / NPW;
   const int lane = tid & 63;
   const int NT = F_out >> 4, RT = (nrows + 15) >> 4;
@@ -680,9 +578,7 @@ __device__ __forceinline__ void panel_times_wt_staged_chunked(float *t, int nrow
       default: break;
     }
   }
-  HG_STAMP(8);
   __syncthreads();  // every wave has read its A fragments: the rows can be overwritten
-  HG_STAMP(9);
   if (sp.active) {
 #pragma unroll
     for (int ni = 0; ni < NPW; ni++) {
@@ -699,17 +595,14 @@ __device__ __forceinline__ void panel_times_wt_staged_chunked(float *t, int nrow
     }
   }
   __syncthreads();
-  HG_STAMP(10);
   const int q = F_out >> 2;  // float4 pieces per row
   for (int i = tid; i < nrows * q; i += 256) {
     const int r = i / q, c = (i - r * q) * 4;
     const int64_t yrow = rowmap ? (int64_t)rowmap[r] : row0 + r;
     float4 o = *reinterpret_cast<const float4 *>(t + r * LD + c);
     if (relu) o = make_float4(fmaxf(o.x, 0.f), fmaxf(o.y, 0.f), fmaxf(o.z, 0.f), fmaxf(o.w, 0.f));
-    if (HG_Y_NT) Vec<4>{o}.store_nt(Y + yrow * F_out + c);
-    else *reinterpret_cast<float4 *>(Y + yrow * F_out + c) = o;
+    Vec<4>{o}.store_nt(Y + yrow * F_out + c);
   }
-  HG_STAMP(11);
 }
 
 // ---- fp32 by six bf16 products (K = 128 staged epilogue, HG_LIN_BF16X6) ---------------------------------------------
@@ -789,12 +682,7 @@ __device__ __forceinline__ hg_f4 mfma_bf16(const uint4 &a, const uint4 &b, hg_f4
 
 // Step t of a wave's matrix phase = (k-step t / npw, the wave's column tile t % npw); a column tile past the last one (F_out not
 // a multiple of 64: the last wave has one tile fewer) is clamped -- its products are computed and never written back.
-#ifndef HG_SPLIT_DEPTH
-#define HG_SPLIT_DEPTH 2  // steps of B fragments in registers (12 VGPRs each)
-#endif
-#ifndef HG_SPLIT_APIPE
-#define HG_SPLIT_APIPE 1  // A fragments read one iteration ahead, order pinned
-#endif
+constexpr int kSplitDepth = 2;  // steps of B fragments in registers (12 VGPRs each)
 __device__ __forceinline__ SplitB load_bsplit_step(const uint4 *wsplit, const LinSplit &sp, int NT, int npw, int t, int lane) {
   const int ni = npw == 2 ? (t & 1) : 0, ks = npw == 2 ? (t >> 1) : t;
   return load_bsplit(wsplit, min(sp.nt_first + ni * sp.nt_step, NT - 1), ks, lane);
@@ -809,8 +697,7 @@ __device__ __forceinline__ SplitB load_bsplit_step(const uint4 *wsplit, const Li
 // go in first.
 template <int NPW, int NRT, int D>
 __device__ __forceinline__ void mfma_rows_split(const char *planes, int pstride, const uint4 *wsplit, const LinSplit &sp, int NT, int lane,
-                                                SplitB (&bq)[D], hg_f4 *acc, int dbg = 0) {  // dbg (diagnostic instance, timing only): 1024 = no
-                                                                                            // B loads in the loop, 2048 = no A reads, 4096 = no MFMAs
+                                                SplitB (&bq)[D], hg_f4 *acc) {
   constexpr int RPN = 4 / NPW, NS = 4 * NPW, NI = NS * NRT;
   const int r = lane & 15, kb = lane >> 4;
   const char *prow = planes + (sp.rt_first * 16 + r) * 256;
@@ -836,42 +723,24 @@ __device__ __forceinline__ void mfma_rows_split(const char *planes, int pstride,
     const char *pn = a_ptr(i + 1 < NI ? i + 1 : i);
     const SplitB &b = bq[t % D];
     hg_f4 c = acc[ni * RPN + j];
-    const bool rd = i + 1 < NI && !(dbg & 2048), mm = !(dbg & 4096);
-    if (mm) c = mfma_bf16(al, b.h, c);
-#if HG_SPLIT_APIPE
+    const bool rd = i + 1 < NI;
+    c = mfma_bf16(al, b.h, c);
     __builtin_amdgcn_sched_barrier(0);
     if (rd) al = *reinterpret_cast<const uint4 *>(pn + 2 * pstride);
     __builtin_amdgcn_sched_barrier(0);
-#endif
-    if (mm) {
-      c = mfma_bf16(am, b.m, c);
-      c = mfma_bf16(am, b.h, c);
-    }
-#if HG_SPLIT_APIPE
+    c = mfma_bf16(am, b.m, c);
+    c = mfma_bf16(am, b.h, c);
     __builtin_amdgcn_sched_barrier(0);
     if (rd) am = *reinterpret_cast<const uint4 *>(pn + pstride);
     __builtin_amdgcn_sched_barrier(0);
-#endif
-    if (mm) {
-      c = mfma_bf16(ah, b.l, c);
-      c = mfma_bf16(ah, b.m, c);
-      c = mfma_bf16(ah, b.h, c);
-    }
+    c = mfma_bf16(ah, b.l, c);
+    c = mfma_bf16(ah, b.m, c);
+    c = mfma_bf16(ah, b.h, c);
     acc[ni * RPN + j] = c;
-#if HG_SPLIT_APIPE
     __builtin_amdgcn_sched_barrier(0);
     if (rd) ah = *reinterpret_cast<const uint4 *>(pn);
-#else
-    if (i + 1 < NI) {
-      ah = *reinterpret_cast<const uint4 *>(pn);
-      am = *reinterpret_cast<const uint4 *>(pn + pstride);
-      al = *reinterpret_cast<const uint4 *>(pn + 2 * pstride);
-    }
-#endif
-    if (j == NRT - 1 && t + D < NS && !(dbg & 1024)) bq[t % D] = load_bsplit_step(wsplit, sp, NT, NPW, t + D, lane);
-#if HG_SPLIT_APIPE
+    if (j == NRT - 1 && t + D < NS) bq[t % D] = load_bsplit_step(wsplit, sp, NT, NPW, t + D, lane);
     __builtin_amdgcn_sched_barrier(0);
-#endif
   }
 }
 
@@ -879,7 +748,7 @@ __device__ __forceinline__ void mfma_rows_split(const char *planes, int pstride,
 // fp32 results go back into the same region as [rows][K + 4] floats and leave as whole rows.
 template <int NPW>
 __device__ __forceinline__ void panel_times_wt_split(float *t, int pstride, int nrows, int F_out, const uint4 *wsplit, const int32_t *rowmap,
-                                                     float *Y, int tid, SplitB (&bq)[HG_SPLIT_DEPTH], int relu, Stamper &stp, int dbg = 0) {
+                                                     float *Y, int tid, SplitB (&bq)[kSplitDepth], int relu) {
   constexpr int K = 128, LD = K + 4, RPN = 4 / NPW;
   const int lane = tid & 63;
   const int NT = F_out >> 4, RT = (nrows + 15) >> 4;
@@ -896,16 +765,14 @@ __device__ __forceinline__ void panel_times_wt_split(float *t, int pstride, int 
       // fragments (a panel of the epilogue's schedule has 29 of its 32 rows on average; the second tile of a shorter one
       // multiplies whatever the planes hold there, and those rows are never stored)
       nrt = RT;
-      mfma_rows_split<NPW, 2, HG_SPLIT_DEPTH>(planes, pstride, wsplit, sp, NT, lane, bq, acc, dbg);
+      mfma_rows_split<NPW, 2, kSplitDepth>(planes, pstride, wsplit, sp, NT, lane, bq, acc);
     } else if (nrt == 2) {
-      mfma_rows_split<NPW, 2, HG_SPLIT_DEPTH>(planes, pstride, wsplit, sp, NT, lane, bq, acc, dbg);
+      mfma_rows_split<NPW, 2, kSplitDepth>(planes, pstride, wsplit, sp, NT, lane, bq, acc);
     } else if (nrt == 1) {
-      mfma_rows_split<NPW, 1, HG_SPLIT_DEPTH>(planes, pstride, wsplit, sp, NT, lane, bq, acc, dbg);
+      mfma_rows_split<NPW, 1, kSplitDepth>(planes, pstride, wsplit, sp, NT, lane, bq, acc);
     }
   }
-  HG_STAMP(8);
   __syncthreads();  // every wave has read its A fragments: the planes can be overwritten
-  HG_STAMP(9);
   if (sp.active) {
 #pragma unroll
     for (int ni = 0; ni < NPW; ni++) {
@@ -922,16 +789,13 @@ __device__ __forceinline__ void panel_times_wt_split(float *t, int pstride, int 
     }
   }
   __syncthreads();
-  HG_STAMP(10);
   const int q = F_out >> 2;  // float4 pieces per row
   for (int i = tid; i < nrows * q; i += 256) {
     const int r = i / q, c = (i - r * q) * 4;
     float4 o = *reinterpret_cast<const float4 *>(t + r * LD + c);
     if (relu) o = make_float4(fmaxf(o.x, 0.f), fmaxf(o.y, 0.f), fmaxf(o.z, 0.f), fmaxf(o.w, 0.f));
-    if (HG_Y_NT) Vec<4>{o}.store_nt(Y + (int64_t)rowmap[r] * F_out + c);
-    else *reinterpret_cast<float4 *>(Y + (int64_t)rowmap[r] * F_out + c) = o;
+    Vec<4>{o}.store_nt(Y + (int64_t)rowmap[r] * F_out + c);
   }
-  HG_STAMP(11);
 }
 
 // WIDE = false: the caller guarantees the staged form applies (F_out <= K and few enough row tiles); the direct form
@@ -939,14 +803,14 @@ __device__ __forceinline__ void panel_times_wt_split(float *t, int pstride, int 
 template <int KSTEPS, bool WIDE = true>
 __device__ __forceinline__ void panel_times_wt(float *t, int nrows, int F_out, const float *Wlin,
                                                const int32_t *rowmap, int64_t row0, float *Y, int tid,
-                                               float (&bpre)[BPre<KSTEPS>::N], int relu, Stamper &stp) {
+                                               float (&bpre)[BPre<KSTEPS>::N], int relu) {
   constexpr int K = KSTEPS * 4, LD = K + 4;
   const int nt_all = F_out >> 4, nwr = nt_all >= 3 ? 1 : 4 / nt_all;  // as lin_split
   const int rt_per_wave = (((nrows + 15) >> 4) + nwr - 1) / nwr;
   if (!WIDE || (F_out <= K && rt_per_wave <= (F_out > 64 ? 2 : 4))) {  // workgroup-uniform
     if constexpr (KSTEPS >= 32) {
-      if (F_out > 64) panel_times_wt_staged_chunked<KSTEPS, 2>(t, nrows, F_out, Wlin, rowmap, row0, Y, tid, bpre, relu, stp);
-      else panel_times_wt_staged_chunked<KSTEPS, 1>(t, nrows, F_out, Wlin, rowmap, row0, Y, tid, bpre, relu, stp);
+      if (F_out > 64) panel_times_wt_staged_chunked<KSTEPS, 2>(t, nrows, F_out, Wlin, rowmap, row0, Y, tid, bpre, relu);
+      else panel_times_wt_staged_chunked<KSTEPS, 1>(t, nrows, F_out, Wlin, rowmap, row0, Y, tid, bpre, relu);
     } else {
       if (F_out > 64) panel_times_wt_staged<KSTEPS, 2>(t, nrows, F_out, Wlin, rowmap, row0, Y, tid, bpre, relu);
       else panel_times_wt_staged<KSTEPS, 1>(t, nrows, F_out, Wlin, rowmap, row0, Y, tid, bpre, relu);
@@ -1020,7 +884,7 @@ template <int KSTEPS> struct LinearRows {
   static constexpr int R = KSTEPS >= 32 ? 32 : 64;
 };
 template <int KSTEPS>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(KSTEPS >= 32 ? 6 : KSTEPS >= 16 ? HG_ROWS_WAVES : 8, 8))) void linear_rows_kernel(
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(KSTEPS >= 32 ? 6 : KSTEPS >= 16 ? kRowsWaves : 8, 8))) void linear_rows_kernel(
     const LinearArgs a) {
   constexpr int K = KSTEPS * 4, LD = K + 4, R = LinearRows<KSTEPS>::R;
   __shared__ float t[R * LD];
@@ -1073,9 +937,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(KSTEPS >= 3
     *reinterpret_cast<float4 *>(t + r * LD + c) = v[j];
   }
   __syncthreads();
-  Stamper none;
   panel_times_wt<KSTEPS>(t, nrows, a.F_out, a.Wlin, a.rowmap ? a.rowmap + row0 : nullptr, row0, a.Y,
-                         threadIdx.x, bv, a.epi.relu, none);
+                         threadIdx.x, bv, a.epi.relu);
 }
 
 // ---- weight gradient of the layer's linear: C[Fa, Fb] = A^T B over N rows --------------------
@@ -1250,39 +1113,12 @@ __global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float *partial,
 // budget that follows (512 / waves) decides how much of hop 2's row registers and the B fragments spill.  Measured
 // (tools/linear_probe.py, cora x1024): F = 32 -> 32: 8 waves 0.262 ms, 7 0.258, 6 0.236, 5 0.249; 64 -> 64: 8 waves
 // 0.621, 7 0.539, 6 0.507, 5 0.529, 4 0.532; 128 -> 128 (x256): 6 waves 0.739 (spills), 5 0.370, 4 0.388.
-#ifndef HG_LIN_WAVES8
-#define HG_LIN_WAVES8 8
-#endif
-#ifndef HG_LIN_WAVES16
-#define HG_LIN_WAVES16 6
-#endif
-#ifndef HG_LIN_WAVES32
-#define HG_LIN_WAVES32 5
-#endif
-#ifndef HG_LIN_WAVES_STAGED
-#define HG_LIN_WAVES_STAGED 8
-#endif
+constexpr int kLinWaves8 = 8, kLinWaves16 = 6, kLinWaves32 = 5, kLinWavesStaged = 8;
 // K = 128 staged-only instances: the register budget of six waves per SIMD, which is what the LDS tile of the epilogue's
 // schedule allows anyway (48 slots x 132 floats + record = 26.6 KB: six workgroups per CU); it pays for twelve row
-// gathers in flight per lane (HG_LIN_U32) -- most panels' hop 1 is then one round trip (HG_LIN_MERGE_PHASES)
-#ifndef HG_LIN_WAVES_STAGED32
-#define HG_LIN_WAVES_STAGED32 6
-#endif
-#ifndef HG_MERGE_PHASES_PLAIN
-#define HG_MERGE_PHASES_PLAIN 1  // the plain panels with materialised slots too: both hop-1 phases in one run of batches of eight (same box,
-                                 // three rounds: pubmed x256 F = 32 0.512-0.515 -> 0.526-0.529 of the roofline, x64 F = 128 0.502-0.503 -> 0.507-0.510,
-                                 // weighted pubmed 0.494-0.496 -> 0.505-0.510, power-law step 0.917-0.921 -> 0.907-0.912 ms)
-#endif
-#ifndef HG_LIN_MERGE_PHASES
-#define HG_LIN_MERGE_PHASES 1  // K = 128 staged epilogue instances: hop 1's two phases as one run of batches (with twelve gathers in
-                               // flight at the six-wave budget: -1.2 % on pubmed x64 128 -> 128, -2.2 % on 128 -> 64, same box, three rounds)
-#endif
-#ifndef HG_LIN_R_EARLY
-#define HG_LIN_R_EARLY 1  // a layer's residual rows are requested before hop 2 (0: after it, all four together)
-#endif
-#ifndef HG_LIN_U32
-#define HG_LIN_U32 12  // row gathers in flight per lane, K = 128 staged instances
-#endif
+// gathers in flight per lane (kLinU32) -- most panels' hop 1 is then one round trip (both phases merged, below)
+constexpr int kLinWavesStaged32 = 6;
+constexpr int kLinU32 = 12;  // row gathers in flight per lane, K = 128 staged instances
 typedef unsigned hg_u4 __attribute__((ext_vector_type(4)));
 typedef int hg_i4 __attribute__((ext_vector_type(4)));
 
@@ -1300,8 +1136,7 @@ __host__ __device__ inline int lin_tile_floats(int cap, int rows_cap, int tw) {
 // tables below 2 GiB (the launcher checks; otherwise FAST = false runs the same loop
 // on global loads).
 // MAT / SCALED say whether materialised slots / degE-W scaling can occur at all (the launcher
-// knows); false compiles that path out of the unrolled loop, which is issue-bound.  DBG keeps
-// the ablation switches (a.debug) in the code; production instances have none.
+// knows); false compiles that path out of the unrolled loop, which is issue-bound.
 // LIN: the rows a panel produces go through panel_times_wt (Y = rows * Wlin^T, F_out columns)
 // instead of straight to Y; needs F == LPR * VEC and at most 4 rows per lane group.
 // BS: threads per panel workgroup.  256 everywhere but for a tiny dense hypergraph, whose whole hop-1 stream sits in one
@@ -1314,9 +1149,9 @@ __host__ __device__ inline int lin_tile_floats(int cap, int rows_cap, int tw) {
 // instance (natural demand 85-92 VGPRs, 5-6 waves).
 // SPLIT (LIN, !LINW, K = 128 only): the matrix phase as six bf16 products per fp32 product (mfma_rows_split); a.epi.wsplit.
 // T: element type of the rows of X and Y (Rows; bf16 without LIN only).  Tile, materialised rows and partial rows are fp32.
-template <int LPR, int VEC, int U, bool FAST, bool MAT, bool SCALED, bool DBG, bool LIN = false, int BS = 256, bool LINW = true, bool SPLIT = false,
+template <int LPR, int VEC, int U, bool FAST, bool MAT, bool SCALED, bool LIN = false, int BS = 256, bool LINW = true, bool SPLIT = false,
           typename T = float>
-__global__ __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(LIN ? (!LINW ? (LPR >= 32 ? HG_LIN_WAVES_STAGED32 : HG_LIN_WAVES_STAGED) : LPR >= 32 ? HG_LIN_WAVES32 : LPR == 16 ? HG_LIN_WAVES16 : HG_LIN_WAVES8) : 1, 8))) void fused_packed_kernel(const FusedArgs a) {
+__global__ __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(LIN ? (!LINW ? (LPR >= 32 ? kLinWavesStaged32 : kLinWavesStaged) : LPR >= 32 ? kLinWaves32 : LPR == 16 ? kLinWaves16 : kLinWaves8) : 1, 8))) void fused_packed_kernel(const FusedArgs a) {
   static_assert(!LIN || BS == 256, "the linear epilogue is written for four waves");
   static_assert(!SPLIT || (LIN && !LINW && LPR == 32 && VEC == 4), "bf16x6 matrix phase: K = 128 staged instances");
   static_assert(!LIN || std::is_same_v<T, float>, "the linear epilogue takes fp32 rows");
@@ -1345,7 +1180,6 @@ __global__ __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(LIN ? (!LINW
     if (MAT && a.reverse_runs) i = cpx + (x < rem ? 1 : 0) - 1 - i;
     b = x * cpx + (x < rem ? x : rem) + i;
   }
-  HG_STAMP_INIT(true);
 
   // [cap * TW] slot rows; LIN: the same floats later hold the matrix phase's operand, [rows_cap up to whole 16-row tiles]
   // rows of TW + 4 floats -- the region is the larger of the two (lin_tile_floats: the launcher sizes it the same way)
@@ -1357,7 +1191,6 @@ __global__ __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(LIN ? (!LINW
   float *sdeg = sB + (a.W ? a.cap : 0);                  // [rows_cap], if degV and not kept in registers (below)
 
   const FRec rt = a.rec_tab[b];
-  HG_STAMP(0);
   const int32_t *grec = a.rec + rt.off;
   const int g = tid / LPR;
   // Bound degV, at most four rows per lane group, and the launcher found that the row factors' LDS costs a resident
@@ -1388,7 +1221,7 @@ __global__ __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(LIN ? (!LINW
   const bool bound_e = SCALED && a.bsA && (a.degE || a.W) && rt.nslots > 0, bound_v = a.degV && !dv_regs && a.bsD && rt.nrows > 0;
   const bool pre = bound_e || bound_v;  // workgroup-uniform
   if (pre) {
-    const hg_i4 rv = HG_REC_NT ? __builtin_nontemporal_load(grec4 + min(tid, nrec4 - 1)) : grec4[min(tid, nrec4 - 1)];
+    const hg_i4 rv = grec4[min(tid, nrec4 - 1)];
     float va = 1.f, vb = 1.f, vd = 1.f;
     if (bound_e) {
       const int64_t si = rt.slot_base + min(tid, rt.nslots - 1);
@@ -1404,7 +1237,7 @@ __global__ __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(LIN ? (!LINW
     if (bound_v && tid < rt.nrows) sdeg[tid] = vd;
   }
   for (int i = pre ? tid + BS : tid; i < nrec4; i += BS)
-    reinterpret_cast<hg_i4 *>(rec)[i] = HG_REC_NT ? __builtin_nontemporal_load(grec4 + i) : grec4[i];
+    reinterpret_cast<hg_i4 *>(rec)[i] = grec4[i];
   if (a.degE || a.W)
     for (int i = bound_e ? tid + BS : tid; i < rt.nslots; i += BS) {
       if (a.bsA) {  // bound: one coalesced read instead of a scattered 4-byte gather per slot
@@ -1425,10 +1258,7 @@ __global__ __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(LIN ? (!LINW
         sdeg[i] = pr < 0 ? 1.f : a.degV[pr];
       }
     }
-  HG_STAMP(1);
   __syncthreads();
-  HG_STAMP(2);
-  if (DBG && (a.debug & 16)) return;  // ablation (experiments): record copy only
   const int steps = rec[0], nrows = rec[1];
   const int32_t *gbase = rec + rec[4];
   const int32_t *stream = rec + rec[5];
@@ -1436,7 +1266,7 @@ __global__ __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(LIN ? (!LINW
   const int32_t *prow = rec + rec[7];
   const uint16_t *pvs = reinterpret_cast<const uint16_t *>(rec + rec[9]);
 
-  if (!(DBG && (a.debug & 4))) {  // ---- hop 1
+  {  // ---- hop 1
     [[maybe_unused]] int slot = gbase[g];
     float *tp = tile + gbase[g] * TW + lcol;  // where this group's next finished slot goes
     V acc = V::zero();
@@ -1452,10 +1282,9 @@ __global__ __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(LIN ? (!LINW
     [[maybe_unused]] const T *X = static_cast<const T *>(a.X);
     [[maybe_unused]] __amdgpu_buffer_rsrc_t rx, rm;
     if constexpr (FAST) {
-      const bool no_x = DBG && (a.debug & 1);  // ablation: an empty range turns every load into zeros
-      rx = __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(a.X), 0, no_x ? 0 : a.x_bytes, 0x00020000);
+      rx = __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(a.X), 0, a.x_bytes, 0x00020000);
       rm = __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(a.Xe_mat ? static_cast<const void *>(a.Xe_mat) : a.X), 0,
-                                             (a.Xe_mat && !no_x) ? a.mat_bytes : 0, 0x00020000);
+                                             a.Xe_mat ? a.mat_bytes : 0, 0x00020000);
     }
     // The stream has two phases (pack_stream, hg_fused.cpp): steps [0, steps_x) gather member rows of X,
     // steps [steps_x, steps) rows of the materialised table -- one buffer descriptor per phase, no
@@ -1478,13 +1307,13 @@ __global__ __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(LIN ? (!LINW
           v[j] = RX::load_buf(rx, __umul24((unsigned)ent[j], xrow_bytes) + xcol_off);
         } else if constexpr (FAST) {
           const unsigned off = __umul24((unsigned)ent[j], row_bytes) + col_off;  // flags sit above bit 23
-          v[j] = (HG_X_NT && !MATPH) ? V::load_buf_nt(rx, off) : V::load_buf(MATPH ? rm : rx, off);
+          v[j] = V::load_buf(MATPH ? rm : rx, off);
         } else if constexpr (!XF32 && !MATPH) {
-          const bool on = col_ok && ent[j] != idle && !(DBG && (a.debug & 1));
+          const bool on = col_ok && ent[j] != idle;
           const int64_t idx = ent[j] & 0x3fffffff;
           v[j] = on ? RX::load(X + idx * F + col) : V::zero();
         } else {
-          const bool on = col_ok && ent[j] != idle && !(DBG && (a.debug & 1));
+          const bool on = col_ok && ent[j] != idle;
           const int64_t idx = ent[j] & 0x3fffffff;
           const float *base = MATPH ? a.Xe_mat : static_cast<const float *>(a.X);
           v[j] = on ? V::load(base + idx * F + col) : V::zero();
@@ -1506,11 +1335,14 @@ __global__ __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(LIN ? (!LINW
       }
     };
     const int steps_x = MAT ? rec[8] : steps;
-    if constexpr (MAT && FAST && ((HG_LIN_MERGE_PHASES && LIN && !LINW && LPR >= 32) || (HG_MERGE_PHASES_PLAIN && !LIN && VEC == 4 && BS == 256))) {
-      // Both phases in ONE run of batches, the descriptor picked per step (wave-uniform): a pubmed-shape panel of the
-      // epilogue's schedule has ~7 steps of X rows and ~4 of materialised rows -- two dependent round trips as two
-      // phases, one as a batch of twelve.  The plain panels with materialised slots run it with batches of eight: a
-      // panel's last X batch and its materialised rows share a round trip.
+    // Both phases in ONE run of batches, the descriptor picked per step (wave-uniform): a pubmed-shape panel of the
+    // epilogue's schedule has ~7 steps of X rows and ~4 of materialised rows -- two dependent round trips as two
+    // phases, one as a batch of twelve.  The plain panels with materialised slots run it with batches of eight: a
+    // panel's last X batch and its materialised rows share a round trip.  Measured on one box, three rounds each: K = 128
+    // staged epilogue instances (twelve gathers in flight at the six-wave budget) -1.2 % on pubmed x64 128 -> 128, -2.2 % on
+    // 128 -> 64; plain panels pubmed x256 F = 32 0.512-0.515 -> 0.526-0.529 of the roofline, x64 F = 128 0.502-0.503 ->
+    // 0.507-0.510, weighted pubmed 0.494-0.496 -> 0.505-0.510, power-law step 0.917-0.921 -> 0.907-0.912 ms.
+    if constexpr (MAT && FAST && ((LIN && !LINW && LPR >= 32) || (!LIN && VEC == 4 && BS == 256))) {
       auto mixed = [&](const int s0, auto full) {
         constexpr bool FULL = decltype(full)::value;
         int ent[U];
@@ -1556,19 +1388,17 @@ __global__ __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(LIN ? (!LINW
       }
     }
   }
-  HG_STAMP(3);
   __syncthreads();
-  HG_STAMP(4);
   if constexpr (LIN) {  // ---- hop 2 into registers, then rows * Wlin^T on the matrix cores
     // the B fragments of this wave's first column tile are issued after hop 2 and fly across the two barriers that
     // follow (issued before hop 2 they would hold K/4 more registers through it: 78 instead of 64 VGPRs)
     [[maybe_unused]] float bv[BPre<TW / 4>::N];
-    [[maybe_unused]] SplitB bsp[HG_SPLIT_DEPTH];
+    [[maybe_unused]] SplitB bsp[kSplitDepth];
     const LinSplit sp = lin_split(tid >> 6, a.F_out >> 4);
     if constexpr (SPLIT) {  // the first steps' B fragments (three bf16 planes each): in flight during hop 2
       if (sp.active) {
 #pragma unroll
-        for (int t = 0; t < HG_SPLIT_DEPTH; t++)
+        for (int t = 0; t < kSplitDepth; t++)
           bsp[t] = load_bsplit_step(static_cast<const uint4 *>(a.epi.wsplit), sp, a.F_out >> 4, a.F_out > 64 ? 2 : 1, t, tid & 63);
       }
     }
@@ -1578,12 +1408,10 @@ __global__ __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(LIN ? (!LINW
     // past the group's range reads the panel's last row and is not used), and BEFORE hop 2, which they overlap.  Under
     // `if (r0 + i < r1)` after hop 2 each load was followed by s_waitcnt vmcnt(0) -- four dependent trips to HBM per panel in every
     // UniGCNII / UniGIN layer.
-    [[maybe_unused]] V rr[4];
-    if constexpr (HG_LIN_R_EARLY) {
-      if (a.epi.R) {
+    V rr[4];
+    if (a.epi.R) {
 #pragma unroll
-        for (int i = 0; i < 4; i++) rr[i] = V::load(a.epi.R + (int64_t)prow[min(r0 + i, nrows - 1)] * F + col);
-      }
+      for (int i = 0; i < 4; i++) rr[i] = V::load(a.epi.R + (int64_t)prow[min(r0 + i, nrows - 1)] * F + col);
     }
     V outr[4];
 #pragma unroll
@@ -1598,12 +1426,6 @@ __global__ __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(LIN ? (!LINW
     }
     if (a.epi.R || a.epi.ca != 1.f) {  // t' = ca * t + cb * R[v]  (workgroup-uniform)
       const float cb = a.epi.cb_dev ? *a.epi.cb_dev : a.epi.cb;
-      if constexpr (!HG_LIN_R_EARLY) {
-        if (a.epi.R) {
-#pragma unroll
-          for (int i = 0; i < 4; i++) rr[i] = V::load(a.epi.R + (int64_t)prow[min(r0 + i, nrows - 1)] * F + col);
-        }
-      }
 #pragma unroll
       for (int i = 0; i < 4; i++)
         if (r0 + i < r1) {
@@ -1621,36 +1443,21 @@ __global__ __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(LIN ? (!LINW
         for (int i = 0; i < 4; i++)
           if (r0 + i < r1) outr[i].store(a.epi.T_out + (int64_t)prow[r0 + i] * TW + lcol);
       }
-      HG_STAMP(5);
       __syncthreads();  // every slot row has been read: the tile becomes the operand's three bf16 planes
 #pragma unroll
       for (int i = 0; i < 4; i++)
         if (r0 + i < r1) split_store_row(reinterpret_cast<char *>(tile), pstride, r0 + i, lcol, outr[i].v);
       __syncthreads();
-      HG_STAMP(6);
-      HG_STAMP(7);
-      if (a.F_out > 64) panel_times_wt_split<2>(tile, pstride, nrows, a.F_out, static_cast<const uint4 *>(a.epi.wsplit), prow, static_cast<float *>(a.Y), tid, bsp, a.epi.relu, stp, DBG ? a.debug : 0);
-      else panel_times_wt_split<1>(tile, pstride, nrows, a.F_out, static_cast<const uint4 *>(a.epi.wsplit), prow, static_cast<float *>(a.Y), tid, bsp, a.epi.relu, stp, DBG ? a.debug : 0);
-      HG_STAMP_FLUSH();
+      if (a.F_out > 64) panel_times_wt_split<2>(tile, pstride, nrows, a.F_out, static_cast<const uint4 *>(a.epi.wsplit), prow, static_cast<float *>(a.Y), tid, bsp, a.epi.relu);
+      else panel_times_wt_split<1>(tile, pstride, nrows, a.F_out, static_cast<const uint4 *>(a.epi.wsplit), prow, static_cast<float *>(a.Y), tid, bsp, a.epi.relu);
       return;
     }
-    if (sp.active && !(DBG && (a.debug & 512))) load_bfrag_pre<TW / 4>(a.Wlin, sp.nt_first, tid & 63, bv);
-    HG_STAMP(5);
+    if (sp.active) load_bfrag_pre<TW / 4>(a.Wlin, sp.nt_first, tid & 63, bv);
     __syncthreads();  // every slot row has been read: the tile becomes the [rows][TW + 4] operand
 #pragma unroll
     for (int i = 0; i < 4; i++)
       if (r0 + i < r1) outr[i].store(tile + (r0 + i) * (TW + 4) + lcol);
     __syncthreads();
-    HG_STAMP(6);
-    if (DBG && (a.debug & 256)) {  // ablation (timing only): no matrix work, the rows leave as they are
-      const int q = min(a.F_out, TW) >> 2;
-      for (int i = tid; i < nrows * q; i += 256) {
-        const int r = i / q, c = (i - r * q) * 4;
-        *reinterpret_cast<float4 *>(static_cast<float *>(a.Y) + (int64_t)prow[r] * a.F_out + c) =
-            *reinterpret_cast<const float4 *>(tile + r * (TW + 4) + c);
-      }
-      return;
-    }
     if (a.epi.T_out) {  // the combined rows themselves, for the backward pass (dWlin needs them)
       constexpr int q = TW >> 2;
       for (int i = tid; i < nrows * q; i += 256) {
@@ -1659,11 +1466,9 @@ __global__ __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(LIN ? (!LINW
             *reinterpret_cast<const float4 *>(tile + r * (TW + 4) + c);
       }
     }
-    HG_STAMP(7);
-    panel_times_wt<TW / 4, LINW>(tile, nrows, a.F_out, a.Wlin, prow, 0, static_cast<float *>(a.Y), tid, bv, a.epi.relu, stp);
-    HG_STAMP_FLUSH();
+    panel_times_wt<TW / 4, LINW>(tile, nrows, a.F_out, a.Wlin, prow, 0, static_cast<float *>(a.Y), tid, bv, a.epi.relu);
     return;
-  } else if (!(DBG && (a.debug & 8))) {  // ---- hop 2
+  } else {  // ---- hop 2
     const int rpg = (nrows + NG - 1) / NG;
     const int r0 = min(g * rpg, nrows), r1 = min(r0 + rpg, nrows);
     auto row = [&](const int r, const float dscale) {  // dscale: the row's degV where it came in a register, else read from LDS
@@ -1671,19 +1476,18 @@ __global__ __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(LIN ? (!LINW
       const int pb = r ? pend[r - 1] : 0, pe = pend[r];
       for (int p = pb; p < pe; p++) acc.add(V::load(tile + (int)pvs[p] * TW + lcol));
       if (a.degV && pe > pb) acc.mul(dv_regs ? dscale : sdeg[r]);
-      if (col_ok && !(DBG && (a.debug & 2))) {
+      if (col_ok) {
         const int pr = prow[r];  // vertex id, or bit 31 | partial row (a piece of a split vertex)
         if constexpr (XF32) {
           float *dst = (pr < 0 ? a.partial + (int64_t)(pr & 0x7fffffff) * F : static_cast<float *>(a.Y) + (int64_t)pr * F) + col;
-          if (DBG && (a.debug & 64)) acc.store_nt(dst);
-          else if (HG_Y_NT && a.y_nt && pr >= 0) acc.store_n_nt(dst, a.F - col);  // partial rows are read back by the fixup pass: plain
+          if (a.y_nt && pr >= 0) acc.store_n_nt(dst, a.F - col);  // partial rows are read back by the fixup pass: plain
           else acc.store_n(dst, a.F - col);
         } else {  // partial rows stay fp32
           if (pr < 0) {
             acc.store_n(a.partial + (int64_t)(pr & 0x7fffffff) * F + col, a.F - col);
           } else {
             T *y = static_cast<T *>(a.Y) + (int64_t)pr * F + col;
-            if (HG_Y_NT && a.y_nt) RX::store_n_nt(acc, y, a.F - col);
+            if (a.y_nt) RX::store_n_nt(acc, y, a.F - col);
             else RX::store_n(acc, y, a.F - col);
           }
         }
@@ -1697,8 +1501,6 @@ __global__ __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(LIN ? (!LINW
       for (int r = r0; r < r1; r++) row(r, 1.f);
     }
   }
-  HG_STAMP(5);
-  HG_STAMP_FLUSH();
 }
 
 
@@ -1721,11 +1523,6 @@ __global__ __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(LIN ? (!LINW
 //    registers at a time, all four pairs of a step in flight; a step past a row's end reads the
 //    all-zero row `cap` instead of branching.  Registers are ordered by weight (the plan deals the
 //    heaviest rows first), so the four rows of a chunk have similar lengths.
-#ifdef HG_TUNING
-#define HG_HUB_ABLATE(bit) ((a.debug & (bit)) != 0)  // diagnostic build: HG_HUB_DEBUG, 1 = no hop 1, 2 = no hop 2, 4 = no memory
-#else
-#define HG_HUB_ABLATE(bit) false
-#endif
 // T: element type of the rows of X (Rows); the partial rows it writes are fp32.
 template <int LPR, int VEC, int U, bool MAT, bool SCALED, bool HEAVY, typename T = float>
 __global__ __launch_bounds__(1024) void hub_pass_kernel(const HubArgs a) {
@@ -1757,11 +1554,10 @@ __global__ __launch_bounds__(1024) void hub_pass_kernel(const HubArgs a) {
   const unsigned col_off = col_ok ? (unsigned)col * 4u : 0x80000000u;
   [[maybe_unused]] const unsigned xrow_bytes = (unsigned)a.F * (unsigned)sizeof(T);  // rows of X at their element size
   [[maybe_unused]] const unsigned xcol_off = col_ok ? (unsigned)col * (unsigned)sizeof(T) : 0x80000000u;
-  const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(a.X), 0, HG_HUB_ABLATE(4) ? 0 : a.x_bytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(a.X), 0, a.x_bytes, 0x00020000);
   [[maybe_unused]] const __amdgpu_buffer_rsrc_t rm = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<void *>(a.Xe_mat ? static_cast<const void *>(a.Xe_mat) : a.X), 0, (a.Xe_mat && !HG_HUB_ABLATE(4)) ? a.mat_bytes : 0, 0x00020000);
+      const_cast<void *>(a.Xe_mat ? static_cast<const void *>(a.Xe_mat) : a.X), 0, a.Xe_mat ? a.mat_bytes : 0, 0x00020000);
   const int rd0 = a.wg_first[w], rd1 = a.wg_first[w + 1];
-  HG_STAMP_INIT(true);
   // A record is at most NPRE * 16 KB: each thread carries NPRE dwordx4 of the NEXT round's record
   // through hop 1, so the copy's round trip hides behind the row gathers.
   constexpr int NPRE = 2;
@@ -1786,7 +1582,6 @@ __global__ __launch_bounds__(1024) void hub_pass_kernel(const HubArgs a) {
   int cur = 0;
   if (rd0 < rd1) stash(recbuf, fetch(rd0));
   __syncthreads();
-  HG_STAMP(0);
   for (int rd = rd0; rd < rd1; rd++) {
     const int32_t *rec = recbuf + cur * a.max_rec_words;
     int n4_next = 0;
@@ -1806,8 +1601,7 @@ __global__ __launch_bounds__(1024) void hub_pass_kernel(const HubArgs a) {
     const int32_t *stream = rec + rec[5];
     const uint16_t *pend = reinterpret_cast<const uint16_t *>(rec + rec[6]);
     const uint16_t *pvs = reinterpret_cast<const uint16_t *>(rec + rec[9]);
-    HG_STAMP(1);
-    if (!HG_HUB_ABLATE(1)) {  // ---- hop 1: this round's hyperedge sums -> tile (and heavy hubs' registers)
+    {  // ---- hop 1: this round's hyperedge sums -> tile (and heavy hubs' registers)
       [[maybe_unused]] int slot = gbase[g];
       float *tp = tile + gbase[g] * TW + lcol;
       V sum = V::zero();
@@ -1865,12 +1659,9 @@ __global__ __launch_bounds__(1024) void hub_pass_kernel(const HubArgs a) {
         if (s0 < steps) block(s0, steps, std::false_type{}, std::true_type{});
       }
     }
-    HG_STAMP(2);
     stash(recbuf + (cur ^ 1) * a.max_rec_words, n4_next);  // nobody reads that buffer during this round
     __syncthreads();
-    HG_STAMP(3);
-    // ---- hop 2: every virtual row adds the tile rows of the hyperedges it belongs to
-    if (!HG_HUB_ABLATE(2)) {
+    {  // ---- hop 2: every virtual row adds the tile rows of the hyperedges it belongs to
       // the lane group's R cumulative ends: eight aligned dwords of 16-bit pairs (g * R is a multiple of 16)
       const uint32_t *pw = reinterpret_cast<const uint32_t *>(pend) + g * (R / 2);
       uint32_t ew[R / 2];
@@ -1900,9 +1691,7 @@ __global__ __launch_bounds__(1024) void hub_pass_kernel(const HubArgs a) {
         }
       }
     }
-    HG_STAMP(4);
     __syncthreads();  // the tile is rewritten by the next round, this record by the one after
-    HG_STAMP(5);
     cur ^= 1;
   }
   int vs0[R];  // the lane group's R partial slots: requested together (read one by one next to their stores they were R dependent
@@ -1929,7 +1718,6 @@ __global__ __launch_bounds__(1024) void hub_pass_kernel(const HubArgs a) {
       __syncthreads();
     }
   }
-  HG_STAMP_FLUSH();
 }
 
 // Streaming row gather (RowStream, hg_internal.h): dst[r] = scaleB * (scaleA * sum of the src rows of CSR
@@ -2023,11 +1811,11 @@ __global__ __launch_bounds__(256) void stream_rows_kernel(const StreamArgs a) {
         slot++;
         if (col_ok) {
           if constexpr (std::is_same_v<TD, float>) {
-            if (HG_Y_NT && a.nt_dst && d >= 0) acc.store_n_nt(dst + (int64_t)d * F + col, a.F - col);
+            if (a.nt_dst && d >= 0) acc.store_n_nt(dst + (int64_t)d * F + col, a.F - col);
             else acc.store_n((d < 0 ? a.partial + (int64_t)(d & 0x7fffffff) * F : dst + (int64_t)d * F) + col, a.F - col);
           } else if (d < 0) {  // partial rows stay fp32
             acc.store_n(a.partial + (int64_t)(d & 0x7fffffff) * F + col, a.F - col);
-          } else if (HG_Y_NT && a.nt_dst) {
+          } else if (a.nt_dst) {
             RD::store_n_nt(acc, dst + (int64_t)d * F + col, a.F - col);
           } else {
             RD::store_n(acc, dst + (int64_t)d * F + col, a.F - col);
@@ -2101,43 +1889,8 @@ static inline int next_pow2(int x) {
   return p;
 }
 
-// Experiment knobs.  The shipped library runs the measured best (profiles/r01_fused_experiments.md)
-// and reads nothing from the environment; the diagnostic build (`make tuning`, -DHG_TUNING) reads the
-// HG_* variables once.  Nothing here changes results.
-struct Tuning {
-  int unroll = 4;        // HG_UNROLL = 4|8      : row loads in flight per lane, pull kernel
-  int pipe = 0;          // HG_PIPE = 0|1        : two batches in flight, pull kernel
-  int fused_u = 8;       // HG_FUSED_U = 8|16    : row loads in flight per lane, fused kernel
-  int fused_small16 = 1; // HG_FUSED_SMALL16=0   : no U = 16 for grids of at most 512 panels
-  int fused_fast = 1;    // HG_FUSED_FAST=0      : global loads instead of buffer loads
-  int fused_coltile = 0; // HG_FUSED_COLTILE=1   : 128-byte column tiles for wide rows
-  int fused_debug = 0;   // HG_FUSED_DEBUG=bits  : ablation / stamp switches (timing only)
-};
-static const Tuning &tuning() {
-  static const Tuning t = [] {
-    Tuning x;
-#ifdef HG_TUNING
-    if (const char *e = getenv("HG_UNROLL")) x.unroll = atoi(e) == 8 ? 8 : 4;
-    if (const char *e = getenv("HG_PIPE")) x.pipe = atoi(e) != 0;
-    if (const char *e = getenv("HG_FUSED_U")) x.fused_u = atoi(e) == 16 ? 16 : (atoi(e) == 12 ? 12 : (atoi(e) == 10 ? 10 : 8));
-    if (const char *e = getenv("HG_FUSED_SMALL16")) x.fused_small16 = atoi(e) != 0;
-    if (const char *e = getenv("HG_FUSED_FAST")) x.fused_fast = atoi(e) != 0;
-    if (const char *e = getenv("HG_FUSED_COLTILE")) x.fused_coltile = atoi(e) != 0;
-    if (const char *e = getenv("HG_FUSED_DEBUG")) x.fused_debug = atoi(e);
-#endif
-    return x;
-  }();
-  return t;
-}
-
-
 // Dynamic LDS above the 64 KiB default is an opt-in per kernel; gfx950 has 160 KiB per CU.
 constexpr size_t kLdsMax = 160 * 1024;
-#ifdef HG_TUNING
-constexpr bool kDbgFallback = true;   // diagnostic build: ablation switches stay in the generic instance
-#else
-constexpr bool kDbgFallback = false;
-#endif
 template <auto Kern, int BLOCK = 256, typename Args>
 static hipError_t launch_lds(dim3 grid, size_t lds, hipStream_t stream, const Args &a) {
   static std::atomic<size_t> granted{64 * 1024};
@@ -2148,21 +1901,6 @@ static hipError_t launch_lds(dim3 grid, size_t lds, hipStream_t stream, const Ar
     if (e != hipSuccess) return e;
     granted.store(kLdsMax, std::memory_order_relaxed);
   }
-#ifdef HG_TUNING
-  // diagnostic build, HG_PRINT_OCC=1: what the runtime says about resident workgroups per CU for this launch
-  static const bool print_occ = [] { const char *e = getenv("HG_PRINT_OCC"); return e && atoi(e) != 0; }();
-  if (print_occ) {
-    static std::atomic<size_t> last{(size_t)-1};
-    if (last.exchange(lds) != lds) {
-      int n = -1;
-      hipFuncAttributes fa{};
-      (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, reinterpret_cast<const void *>(Kern), BLOCK, lds);
-      (void)hipFuncGetAttributes(&fa, reinterpret_cast<const void *>(Kern));
-      fprintf(stderr, "[hg occ] %s: block %d, dynamic LDS %zu B, static LDS %zu B, %d VGPRs -> %d workgroups per CU, grid %u x %u\n",
-              __PRETTY_FUNCTION__, BLOCK, lds, (size_t)fa.sharedSizeBytes, fa.numRegs, n, grid.x, grid.y);
-    }
-  }
-#endif
   hipLaunchKernelGGL(Kern, grid, dim3(BLOCK), lds, stream, a);
   return hipGetLastError();
 }
@@ -2189,15 +1927,7 @@ static hipError_t launch_gather_t(const GatherArgs &a, int nfix, int nfix_l1, co
   if (nblocks > 0) {
     const size_t lds = (size_t)(4 * a.panel_rows + 1 + a.panel_nnz) * sizeof(int32_t);
     const dim3 grid(nblocks, col_tiles);
-    const Tuning &t = tuning();
-    hipError_t e;
-    if (t.unroll == 8) {
-      e = t.pipe ? launch_lds<gather_rows_kernel<LPR, VEC, 8, true, TS, TD>>(grid, lds, stream, a)
-                 : launch_lds<gather_rows_kernel<LPR, VEC, 8, false, TS, TD>>(grid, lds, stream, a);
-    } else {
-      e = t.pipe ? launch_lds<gather_rows_kernel<LPR, VEC, 4, true, TS, TD>>(grid, lds, stream, a)
-                 : launch_lds<gather_rows_kernel<LPR, VEC, 4, false, TS, TD>>(grid, lds, stream, a);
-    }
+    const hipError_t e = launch_lds<gather_rows_kernel<LPR, VEC, TS, TD>>(grid, lds, stream, a);
     if (e != hipSuccess) return e;
   }
   return launch_fixups_t<LPR, VEC, TD>(a, nfix, nfix_l1, fixups, stream);
@@ -2319,11 +2049,7 @@ static hipError_t launch_hub_t(const HubArgs &a, hipStream_t stream) {
 #undef HG_HUB
 }
 
-hipError_t launch_hub_pass(const HubArgs &a0, bool vec4, hipStream_t stream, bool x_bf16) {
-  HubArgs a = a0;
-#ifdef HG_TUNING
-  if (const char *e = getenv("HG_HUB_DEBUG")) a.debug = atoi(e);  // ablation: 1 = no hop 1, 2 = no hop 2
-#endif
+hipError_t launch_hub_pass(const HubArgs &a, bool vec4, hipStream_t stream, bool x_bf16) {
   if (a.nwg == 0) return hipSuccess;
   if (!vec4) return hipErrorInvalidValue;
   if (x_bf16 && (a.F & 3)) return hipErrorInvalidValue;
@@ -2359,7 +2085,7 @@ static int fused_dv_regs(const FusedArgs &a, int ng, size_t lds_without_scales, 
   return fit_without > fit_with ? 1 : 0;
 }
 
-// T: element type of the rows of X and Y.  bf16 (VEC = 4 only) takes the fp32 instances' decisions with no diagnostic forms.
+// T: element type of the rows of X and Y.  bf16 (VEC = 4 only) takes the fp32 instances' decisions.
 template <int LPR, int VEC, typename T = float>
 static hipError_t launch_fused_t(const FusedArgs &a, hipStream_t stream) {
   if (a.npanels == 0) return hipSuccess;
@@ -2372,15 +2098,13 @@ static hipError_t launch_fused_t(const FusedArgs &a, hipStream_t stream) {
       if (!fast || a.Wlin || a.Xe_mat) return hipErrorInvalidValue;
       const dim3 grid(a.npanels, (a.F + TW - 1) / TW);
       const size_t lds = (size_t)a.cap * TW * 4 + (size_t)a.max_rec_words * 4 + fused_scale_floats(a) * 4 + 16;  // dv_regs = 0
-      if (a.degE || a.W) return launch_lds<fused_packed_kernel<LPR, VEC, 8, true, false, true, false, false, 1024, true, false, T>, 1024>(grid, lds, stream, a);
-      return launch_lds<fused_packed_kernel<LPR, VEC, 8, true, false, false, false, false, 1024, true, false, T>, 1024>(grid, lds, stream, a);
+      if (a.degE || a.W) return launch_lds<fused_packed_kernel<LPR, VEC, 8, true, false, true, false, 1024, true, false, T>, 1024>(grid, lds, stream, a);
+      return launch_lds<fused_packed_kernel<LPR, VEC, 8, true, false, false, false, 1024, true, false, T>, 1024>(grid, lds, stream, a);
     }
   }
   if (a.ng != 256 / LPR) return hipErrorInvalidValue;  // records were packed for another lane layout
   const int col_tiles = (a.F + TW - 1) / TW;
-  const Tuning &t = tuning();
   FusedArgs ad = a;
-  ad.debug = t.fused_debug;
   const dim3 grid(a.npanels, col_tiles);
   // tile | record | scale staging (only what this call's scales need: without them the F = 32
   // bench shape fits 8 workgroups per CU instead of 7)
@@ -2388,7 +2112,7 @@ static hipError_t launch_fused_t(const FusedArgs &a, hipStream_t stream) {
   ad.dv_regs = a.Wlin ? 0 : fused_dv_regs(a, 256 / LPR, (size_t)a.cap * TW * 4 + (size_t)a.max_rec_words * 4 + 16, 8);
   const size_t lds_p = (size_t)a.cap * TW * 4 + (size_t)a.max_rec_words * 4 + fused_scale_floats(ad) * 4 + 16;
   if constexpr (VEC == 4) {
-    const bool fast = t.fused_fast && a.x_bytes > 0 && a.nrows_x < (1 << 24) && a.F < (1 << 22) &&
+    const bool fast = a.x_bytes > 0 && a.nrows_x < (1 << 24) && a.F < (1 << 22) &&
                       (!a.Xe_mat || (a.mat_bytes > 0 && a.nrows_mat < (1 << 24)));
     if (a.Wlin) {  // linear epilogue: eligibility was checked by fused_linear_ok
       if constexpr (XF32 && (TW == 32 || TW == 64 || TW == 128)) {
@@ -2400,7 +2124,7 @@ static hipError_t launch_fused_t(const FusedArgs &a, hipStream_t stream) {
         const bool staged = a.F_out <= TW && (((a.rows_cap + 15) >> 4) + nwr - 1) / nwr <= (a.F_out > 64 ? 2 : 4);
         // K = 128, staged: the LDS tile already holds occupancy to five workgroups per CU, so the registers for twelve row
         // gathers in flight per lane cost nothing there (a panel's hop 1 is then two dependent batches instead of three)
-        constexpr int UL = LPR >= 32 ? HG_LIN_U32 : 8;
+        constexpr int UL = LPR >= 32 ? kLinU32 : 8;
         // bf16x6 matrix phase (a.epi.wsplit): K = 128, staged, at most 32 rows, and the three operand planes fit the tile region
         bool split = false;
         if constexpr (TW == 128) {
@@ -2410,19 +2134,9 @@ static hipError_t launch_fused_t(const FusedArgs &a, hipStream_t stream) {
         if (!split) ad.epi.wsplit = nullptr;
 #define HG_PKL(M, S)                                                                                                          \
   if constexpr (TW == 128)                                                                                                    \
-    if (split) return launch_lds<fused_packed_kernel<LPR, VEC, UL, true, M, S, false, true, 256, false, true>>(grid, lds_l, stream, ad); \
-  return staged ? launch_lds<fused_packed_kernel<LPR, VEC, UL, true, M, S, false, true, 256, false>>(grid, lds_l, stream, ad) \
-                : launch_lds<fused_packed_kernel<LPR, VEC, 8, true, M, S, false, true, 256, true>>(grid, lds_l, stream, ad)
-#ifdef HG_TUNING
-        if constexpr (TW == 128)
-          if (split && (t.fused_debug & 32))  // phase stamps of the bf16x6 form (tools/lin_stamp_probe.py, STAMP_MATH=bf16x6)
-            return launch_lds<fused_packed_kernel<LPR, VEC, UL, true, true, true, true, true, 256, false, true>>(grid, lds_l, stream, ad);
-        if constexpr (TW == 128)
-          if (staged && t.fused_debug == 32)  // ... and of the fp32 form as shipped (staged only, UL gathers in flight)
-            return launch_lds<fused_packed_kernel<LPR, VEC, UL, true, true, true, true, true, 256, false, false>>(grid, lds_l, stream, ad);
-        if (t.fused_debug & (768 | 1 | 32))  // ablations of the matrix phase / the gathers (tools/linear_probe.py): diagnostic build only
-          return launch_lds<fused_packed_kernel<LPR, VEC, 8, true, true, true, true, true>>(grid, lds_l, stream, ad);
-#endif
+    if (split) return launch_lds<fused_packed_kernel<LPR, VEC, UL, true, M, S, true, 256, false, true>>(grid, lds_l, stream, ad); \
+  return staged ? launch_lds<fused_packed_kernel<LPR, VEC, UL, true, M, S, true, 256, false>>(grid, lds_l, stream, ad) \
+                : launch_lds<fused_packed_kernel<LPR, VEC, 8, true, M, S, true, 256, true>>(grid, lds_l, stream, ad)
         switch (spec) {
           case 0: HG_PKL(false, false);
           case 1: HG_PKL(true, false);
@@ -2435,21 +2149,11 @@ static hipError_t launch_fused_t(const FusedArgs &a, hipStream_t stream) {
       }
     }
     if (fast) {
-      if (XF32 && t.fused_debug)  // ablation / stamp run (diagnostic build): everything kept at run time
-        return launch_lds<fused_packed_kernel<LPR, VEC, 8, true, true, true, true>>(grid, lds_p, stream, ad);
       // A grid that does not even fill the chip once is latency-bound, not occupancy-bound:
       // put every row gather of a group in flight at once (U = 16) instead of two batches.
-      const bool u16 = t.fused_u == 16 || (t.fused_small16 && a.npanels <= 512);
+      const bool u16 = a.npanels <= 512;
       const int spec = (a.Xe_mat ? 1 : 0) | ((a.degE || a.W) ? 2 : 0);
-#define HG_PK(UU, M, S) return launch_lds<fused_packed_kernel<LPR, VEC, UU, true, M, S, false, false, 256, true, false, T>>(grid, lds_p, stream, ad)
-#ifdef HG_TUNING
-      if (XF32 && (t.fused_u == 12 || t.fused_u == 10)) {  // diagnostic build: ten / twelve gathers in flight (unweighted, weighted; no materialised slots)
-        if (spec == 0 && t.fused_u == 12) HG_PK(12, false, false);
-        if (spec == 2 && t.fused_u == 12) HG_PK(12, false, true);
-        if (spec == 0) HG_PK(10, false, false);
-        if (spec == 2) HG_PK(10, false, true);
-      }
-#endif
+#define HG_PK(UU, M, S) return launch_lds<fused_packed_kernel<LPR, VEC, UU, true, M, S, false, 256, true, false, T>>(grid, lds_p, stream, ad)
       if (u16) {
         switch (spec) {
           case 0: HG_PK(16, false, false);
@@ -2472,16 +2176,15 @@ static hipError_t launch_fused_t(const FusedArgs &a, hipStream_t stream) {
   if (a.Wlin) return hipErrorInvalidValue;
   if constexpr (XF32 && VEC == 1 && LPR >= 8) {  // F >= 5, not a multiple of 4 (class-count widths): the same buffer-load
                                           // loop, one dword per lane (+7-20 % at F = 7, 33; narrower rows: no gain)
-    const bool fast = t.fused_fast && !t.fused_debug && a.x_bytes > 0 && a.nrows_x < (1 << 24) && a.F < (1 << 22) &&
+    const bool fast = a.x_bytes > 0 && a.nrows_x < (1 << 24) && a.F < (1 << 22) &&
                       (!a.Xe_mat || (a.mat_bytes > 0 && a.nrows_mat < (1 << 24)));
     if (fast) {
       if (!a.Xe_mat && !a.degE && !a.W)
-        return launch_lds<fused_packed_kernel<LPR, VEC, 8, true, false, false, false>>(grid, lds_p, stream, ad);
-      return launch_lds<fused_packed_kernel<LPR, VEC, 8, true, true, true, false>>(grid, lds_p, stream, ad);
+        return launch_lds<fused_packed_kernel<LPR, VEC, 8, true, false, false>>(grid, lds_p, stream, ad);
+      return launch_lds<fused_packed_kernel<LPR, VEC, 8, true, true, true>>(grid, lds_p, stream, ad);
     }
   }
-  if constexpr (!XF32) return launch_lds<fused_packed_kernel<LPR, VEC, 8, false, true, true, false, false, 256, true, false, T>>(grid, lds_p, stream, ad);
-  return launch_lds<fused_packed_kernel<LPR, VEC, 8, false, true, true, kDbgFallback>>(grid, lds_p, stream, ad);
+  return launch_lds<fused_packed_kernel<LPR, VEC, 8, false, true, true, false, 256, true, false, T>>(grid, lds_p, stream, ad);
 }
 
 hipError_t launch_linear_pack_split(int32_t F_out, int32_t F_in, const float *Wlin, void *wsplit, hipStream_t stream) {
@@ -2553,10 +2256,8 @@ hipError_t launch_wgrad(int64_t nrows, int32_t Fa, int32_t Fb, const float *A, c
 }
 
 bool fused_linear_ok(const FusedArgs &a) {
-  const Tuning &t = tuning();
   const int lpr = a.F / 4;
-  return (a.F == 32 || a.F == 64 || a.F == 128) && a.F_out > 0 && (a.F_out & 15) == 0 && t.fused_fast &&
-         !(t.fused_debug & 222) && a.x_bytes > 0 && a.nrows_x < (1 << 24) &&
+  return (a.F == 32 || a.F == 64 || a.F == 128) && a.F_out > 0 && (a.F_out & 15) == 0 && a.x_bytes > 0 && a.nrows_x < (1 << 24) &&
          (!a.Xe_mat || (a.mat_bytes > 0 && a.nrows_mat < (1 << 24))) &&
          a.ng == 256 / lpr && a.rows_cap <= 4 * (256 / lpr) && a.rows_cap <= a.cap;
 }
@@ -2600,49 +2301,9 @@ hipError_t launch_fused(const FusedArgs &a, bool vec4, hipStream_t stream, bool 
   return hipErrorInvalidValue;
 }
 
-// Diagnostic: what the matrix pipes sustain on v_mfma_f32_16x16x4_f32 with operands in registers -- eight waves per
-// SIMD, four independent accumulators each, `iters` rounds of 16 MFMAs -- and the shader clock meanwhile (s_memtime
-// ticks per wave).  The roofline's 157 TFLOP/s is 64 FLOP / clk / SIMD at 2.4 GHz.
-__global__ __launch_bounds__(256) void mfma_rate_kernel(int iters, float *sink, unsigned long long *ticks) {
-  hg_f4 acc[4];
-#pragma unroll
-  for (int j = 0; j < 4; j++) acc[j] = hg_f4{0.f, 0.f, 0.f, 0.f};
-  float a = (float)threadIdx.x * 1e-3f, b = (float)blockIdx.x * 1e-6f + 1.f;
-  const unsigned long long t0 = __builtin_amdgcn_s_memtime();
-  for (int i = 0; i < iters; i++) {
-#pragma unroll
-    for (int r = 0; r < 4; r++)
-#pragma unroll
-      for (int j = 0; j < 4; j++) acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, acc[j], 0, 0, 0);
-  }
-  const unsigned long long t1 = __builtin_amdgcn_s_memtime();
-  float s = 0.f;
-#pragma unroll
-  for (int j = 0; j < 4; j++) s += acc[j][0] + acc[j][1] + acc[j][2] + acc[j][3];
-  if (s == 12345.678f) sink[0] = s;  // keeps the accumulators alive
-  if (threadIdx.x == 0 && blockIdx.x == 0) ticks[0] = t1 - t0;
-}
-
-hipError_t launch_mfma_rate(int blocks, int iters, float *sink, unsigned long long *ticks, hipStream_t stream) {
-  hipLaunchKernelGGL(mfma_rate_kernel, dim3(blocks), dim3(256), 0, stream, iters, sink, ticks);
-  return hipGetLastError();
-}
-
-hipError_t read_stamps(unsigned long long *out, bool reset) {
-  hipError_t e = hipMemcpyFromSymbol(out, HIP_SYMBOL(hg_stamps), sizeof(hg_stamps));
-  if (e == hipSuccess && reset) {
-    unsigned long long z[16] = {0};
-    e = hipMemcpyToSymbol(HIP_SYMBOL(hg_stamps), z, sizeof(z));
-  }
-  return e;
-}
-
-// floats per LDS tile row for feature width F (what launch_fused will use)
-// Wide rows (F a multiple of 32 floats, above 32) are cut into 128-byte column tiles, one
-// workgroup per (panel, tile): every workgroup then has the F = 32 shape -- 8 lanes per row,
-// 32 row groups, 128 slots in a 16 KB tile -- instead of a few fat row groups and tiny panels.
+// floats per LDS tile row for feature width F (what launch_fused will use): the whole row up to 64 lanes.  Cutting wide
+// rows into 128-byte column tiles (the F = 32 panel shape for every width) lost 7 % at F >= 64.
 int fused_tile_row_floats(int F, bool vec4) {
-  if (vec4 && tuning().fused_coltile && F > 32 && F % 32 == 0) return 32;
   const int lanes = vec4 ? (F + 3) / 4 : F;
   return std::min(64, next_pow2(std::max(lanes, 1))) * (vec4 ? 4 : 1);
 }

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Kernel-level probe: times hop 1, hop 2 and the full aggregation over a sweep
-of batch sizes (working-set residency) for the current HG_* tuning env."""
+of batch sizes (working-set residency) with the library as built."""
 import argparse
 import json
 import os
