@@ -36,6 +36,7 @@ SYMBOLS = (
     "hg_aggr_fused_f32", "hg_aggr_fused_bf16", "hg_linear_pack_f32", "hg_linear_pack_ex_f32", "hg_linear_pack_floats", "hg_linear_rows_f32", "hg_linear_wgrad_workspace_bytes", "hg_linear_wgrad_f32", "hg_aggr_linear_workspace_bytes", "hg_aggr_linear_f32", "hg_aggr_linear_res_f32", "hg_aggr_linear_res_dev_f32",
     "hg_gather_rows_f32", "hg_aggr_push_groups_f32", "hg_gather_max_f32",
     "hg_scatter_record_f32",
+    "hg_aggr_incidence_workspace_bytes", "hg_aggr_incidence_f32", "hg_incidence_dot_f32", "hg_plan_get_incidence_perm",
 )
 
 
@@ -173,6 +174,15 @@ def lib():
     L.hg_gather_max_f32.argtypes = [i32, i32, vp, vp, vp, vp, vp, vp, vp, vp]
     L.hg_scatter_record_f32.restype = ctypes.c_int
     L.hg_scatter_record_f32.argtypes = [i32, i32, i32, vp, vp, vp, vp, vp]
+    if hasattr(L, "hg_aggr_incidence_f32"):  # detected by export (an HG_AGGR_LIB build of an older tree lacks them)
+        L.hg_aggr_incidence_workspace_bytes.restype = sz
+        L.hg_aggr_incidence_workspace_bytes.argtypes = [vp, i32]
+        L.hg_aggr_incidence_f32.restype = ctypes.c_int
+        L.hg_aggr_incidence_f32.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]
+        L.hg_incidence_dot_f32.restype = ctypes.c_int
+        L.hg_incidence_dot_f32.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp]
+        L.hg_plan_get_incidence_perm.restype = ctypes.c_int
+        L.hg_plan_get_incidence_perm.argtypes = [vp, vp]
     L.hg_aggr_push_groups_f32.restype = ctypes.c_int
     L.hg_aggr_push_groups_f32.argtypes = [i32, i32, i32, i64, vp, vp, vp, vp, vp, vp,
                                           vp, vp, vp, vp, vp, vp]

@@ -427,9 +427,12 @@ int pick_variant_uncached(const hg_plan *plan, int32_t F, bool vec4, int32_t *va
 int run_sched(const hg_plan *p, const hg::Sched &s, int32_t F, const int32_t *ptr,
               const int32_t *ind, const void *src, const float *scaleA, const float *scaleB,
               const int32_t *scale_map, const int32_t *dst_map, void *dst, float *partial,
-              hipStream_t stream, bool nt_dst = false, bool src_bf16 = false, bool dst_bf16 = false) {
-  hg::GatherArgs a;
+              hipStream_t stream, bool nt_dst = false, bool src_bf16 = false, bool dst_bf16 = false,
+              const float *w = nullptr, const int32_t *wperm = nullptr) {
+  hg::WeightedGatherArgs a;
   a.nt_dst = nt_dst ? 1 : 0;
+  a.w = w;  // per-entry weights (hg_aggr_incidence_f32): the weighted kernel instances
+  a.wperm = wperm;
   a.scale_map = scale_map;
   a.dst_map = dst_map;
   a.ptr = ptr;
@@ -449,7 +452,12 @@ int run_sched(const hg_plan *p, const hg::Sched &s, int32_t F, const int32_t *pt
   a.panel_nnz = p->opts.panel_nnz;
   a.xcd_remap = (p->opts.flags & HG_PLAN_NO_XCD_REMAP) ? 0 : 1;
   const bool vec4 = (F % 4 == 0) && aligned_lane(src, src_bf16) && aligned_lane(dst, dst_bf16) && aligned16(partial);
-  hipError_t e = hg::launch_gather(a, (int)s.fixups.size(), s.n_fix_l1, s.d_fixups, vec4, stream, src_bf16, dst_bf16);
+  if (w && (src_bf16 || dst_bf16)) {
+    hg::set_error("weighted row gather: fp32 rows only");
+    return HG_ERR_UNSUPPORTED;
+  }
+  hipError_t e = w ? hg::launch_gather_weighted(a, (int)s.fixups.size(), s.n_fix_l1, s.d_fixups, vec4, stream)
+                   : hg::launch_gather(a, (int)s.fixups.size(), s.n_fix_l1, s.d_fixups, vec4, stream, src_bf16, dst_bf16);
   if (e != hipSuccess) return hip_fail("gather_rows launch", e);
   return HG_OK;
 }
@@ -481,6 +489,35 @@ int get_row_stream(const hg_plan *cp, int hop, int32_t ng, const hg::RowStream *
     it = p->row_streams.emplace(key, std::move(rs)).first;
   }
   *out = &it->second;
+  return HG_OK;
+}
+
+// hg_plan::perm on the host (built once, under perm_mu, as get_row_stream builds its schedules) and, with upload, on the
+// device.  The same walk as transpose_csr: H entry q = cursor position of H_T entry p in row-major order.
+int get_incidence_perm(const hg_plan *cp, bool upload_it, const int32_t **d_perm) {
+  hg_plan *p = const_cast<hg_plan *>(cp);
+  std::lock_guard<std::mutex> lock(p->perm_mu);
+  if (!p->perm_built) {
+    try {
+      p->perm.assign((size_t)p->nnz, 0);
+      std::vector<int32_t> cursor(p->ptr_v.begin(), p->ptr_v.end() - 1);
+      for (int32_t e = 0; e < p->M; e++)
+        for (int32_t q = p->ptr_t[e]; q < p->ptr_t[e + 1]; q++) p->perm[cursor[p->ind_t[q]]++] = q;
+    } catch (const std::bad_alloc &) {
+      hg::set_error("incidence permutation: host allocation failed");
+      return HG_ERR_NOMEM;
+    }
+    p->perm_built = true;
+  }
+  if (upload_it && !p->d_perm && p->nnz > 0) {
+    int rc = upload(p->perm, &p->d_perm, p->device_bytes);
+    if (rc != HG_OK) {  // a failed copy leaves nothing behind that a later call would trust
+      if (p->d_perm) (void)hipFree(p->d_perm);
+      p->d_perm = nullptr;
+      return rc;
+    }
+  }
+  if (d_perm) *d_perm = p->d_perm;
   return HG_OK;
 }
 
@@ -694,6 +731,7 @@ void hg_plan_destroy(hg_plan *p) {
     for (void *q : ptrs)
       if (q) (void)hipFree(q);
   }
+  if (p->d_perm) (void)hipFree(p->d_perm);
   delete p;
 }
 
@@ -1466,6 +1504,86 @@ int hg_aggr_linear_f32(const hg_plan *plan, int32_t F_in, int32_t F_out, const i
                        size_t workspace_bytes, int32_t variant, hg_stream_t stream) {
   return hg_aggr_linear_res_f32(plan, F_in, F_out, csrptr_t, colind_t, X, degE, degV, W, wfrag, nullptr, 1.f, 0.f,
                                 0, nullptr, Y, workspace, workspace_bytes, variant, stream);
+}
+
+// ---- incidence-weighted aggregation ---------------------------------------------------------------------------------
+
+size_t hg_aggr_incidence_workspace_bytes(const hg_plan *p, int32_t F) {
+  if (!p || F <= 0) return 0;
+  return carve(p, F).total;  // the pull layout: [Xe][partial rows of hop 1][partial rows of hop 2]
+}
+
+int hg_aggr_incidence_f32(const hg_plan *plan, int32_t F, const int32_t *csrptr_t, const int32_t *colind_t,
+                          const float *X, const float *v2e_val, const float *e2v_val, const float *degE,
+                          const float *degV, const float *W, float *Xe_out, float *Y, void *workspace,
+                          size_t workspace_bytes, hg_stream_t stream) {
+  int rc = check_call(plan, F, workspace, workspace_bytes, kSizePull);
+  if (rc != HG_OK) return rc;
+  if (!csrptr_t || (plan->nnz > 0 && !colind_t) || !X || !Y) {
+    hg::set_error("hg_aggr_incidence_f32: null array");
+    return HG_ERR_INVALID;
+  }
+  if ((v2e_val || e2v_val) && (size_t)(4 * plan->opts.panel_rows + 1 + 2 * plan->opts.panel_nnz) * sizeof(int32_t) >
+                                  (size_t)160 * 1024) {
+    hg::set_error("hg_aggr_incidence_f32: panel_rows / panel_nnz leave no LDS for the staged weights (160 KiB per workgroup)");
+    return HG_ERR_UNSUPPORTED;
+  }
+  const int32_t *perm = nullptr;
+  if (e2v_val && (rc = get_incidence_perm(plan, true, &perm)) != HG_OK) return rc;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const Carve c = carve(plan, F);
+  char *ws = static_cast<char *>(workspace);
+  float *Xe = Xe_out ? Xe_out : reinterpret_cast<float *>(ws + c.xe);
+  // the panels + wave-task kernel on both hops (the streaming row gather has no weighted form): sched[hop], or the
+  // latency schedule where hg_plan_tune_f32 pinned that kernel for this width -- what a forced pull call runs there
+  int kind[2] = {1, 1};
+  {
+    hg_plan *mp = const_cast<hg_plan *>(plan);
+    std::lock_guard<std::mutex> lock(mp->auto_mu);
+    auto it = mp->hop_kernel.find(F);
+    if (it != mp->hop_kernel.end()) {
+      kind[0] = it->second % 3;
+      kind[1] = (it->second / 3) % 3;
+    }
+  }
+  const hg::Sched &s0 = (kind[0] == 2 && plan->has_lat) ? plan->sched_lat[0] : plan->sched[0];
+  const hg::Sched &s1 = (kind[1] == 2 && plan->has_lat) ? plan->sched_lat[1] : plan->sched[1];
+  // streaming stores as run_hop decides them
+  const bool nt0 = rows_whole_64(Xe, F) && (int64_t)plan->M * F * 4 >= ((int64_t)192 << 20);
+  const bool nt1 = rows_whole_64(Y, F);
+  // hop 1: Xe[e] = ((sum_{p=(e,u)} v2e[p] X[u]) * degE[e]) * W[e]
+  rc = run_sched(plan, s0, F, csrptr_t, colind_t, X, degE, W, nullptr, nullptr, Xe,
+                 reinterpret_cast<float *>(ws + c.part[0]), s, nt0, false, false, v2e_val, nullptr);
+  if (rc != HG_OK) return rc;
+  // hop 2: Y[v] = (sum_{q=(v,e)} e2v[perm[q]] Xe[e]) * degV[v]
+  return run_sched(plan, s1, F, plan->d_ptr_v, plan->d_ind_v, Xe, degV, nullptr, nullptr, nullptr, Y,
+                   reinterpret_cast<float *>(ws + c.part[1]), s, nt1, false, false, e2v_val, perm);
+}
+
+int hg_incidence_dot_f32(const hg_plan *plan, int32_t F, const int32_t *csrptr_t, const int32_t *colind_t,
+                         const float *A, const float *B, float *out, hg_stream_t stream) {
+  int rc = check_call(plan, F, nullptr, 0, kSizeLater);
+  if (rc != HG_OK) return rc;
+  if (plan->nnz > 0 && (!csrptr_t || !colind_t || !A || !B || !out)) {
+    hg::set_error("hg_incidence_dot_f32: null array");
+    return HG_ERR_INVALID;
+  }
+  const bool vec4 = F % 4 == 0 && aligned16(A) && aligned16(B);
+  hipError_t e = hg::launch_incidence_dot(plan->M, plan->nnz, F, csrptr_t, colind_t, A, B, out, vec4,
+                                          static_cast<hipStream_t>(stream));
+  if (e != hipSuccess) return hip_fail("incidence_dot launch", e);
+  return HG_OK;
+}
+
+int hg_plan_get_incidence_perm(const hg_plan *plan, int32_t *perm_host) {
+  if (!plan || (plan->nnz > 0 && !perm_host)) {
+    hg::set_error("hg_plan_get_incidence_perm: null argument");
+    return HG_ERR_INVALID;
+  }
+  int rc = get_incidence_perm(plan, false, nullptr);
+  if (rc != HG_OK) return rc;
+  if (plan->nnz > 0) std::memcpy(perm_host, plan->perm.data(), (size_t)plan->nnz * sizeof(int32_t));
+  return HG_OK;
 }
 
 }  // extern "C"

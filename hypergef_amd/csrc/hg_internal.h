@@ -262,6 +262,12 @@ struct hg_plan {
   std::map<int64_t, int32_t> auto_choice;  // what HG_VARIANT_AUTO resolved to, keyed by (F, vec4)
   std::map<int32_t, int32_t> hop_kernel;   // per F, set by hg_plan_tune_f32: k0 + 3 * k1, kernel of each pull hop (hg_tune_info)
   std::mutex auto_mu;
+  // hg_aggr_incidence_f32's hop 2: perm[q] = H_T position of H entry q (the stable transpose behind ptr_v / ind_v).
+  // Built on the host and uploaded on first use, never at plan creation.
+  std::vector<int32_t> perm;
+  bool perm_built = false;
+  int32_t *d_perm = nullptr;
+  std::mutex perm_mu;
   double small_nnz_frac = 0.0;  // share of incidences in hyperedges of <= t_big members
   int64_t device_bytes = 0;
   int device = -1;

@@ -33,6 +33,14 @@ struct GatherArgs {
   int32_t nt_dst = 0;  // rows of dst are final output nothing reads again in this call chain: streaming (nt) stores
 };
 
+// GatherArgs plus per-entry weights (hg_aggr_incidence_f32): entry p of the walked CSR adds w[wperm ? wperm[p] : p] *
+// src[ind[p]].  Only gather_rows_kernel's weighted instances take it (fp32 rows); every other kernel keeps GatherArgs
+// and so reads its arguments where it always did.
+struct WeightedGatherArgs : GatherArgs {
+  const float *w = nullptr;        // null: unit weights, the unweighted kernels
+  const int32_t *wperm = nullptr;  // null: w is in the walked CSR's own order
+};
+
 // What happens to an aggregated row t = Aggr(X)[v] on its way through the linear epilogue:
 //   t' = ca * t + cb * R[v]   (R null: t' = ca * t),   T_out[v] = t' if wanted,
 //   Y[v] = act(t' * Wlin^T),  act = relu or identity.
@@ -131,6 +139,13 @@ struct PushArgs {
 // materialised table stay fp32).  At most one of src_bf16 and dst_bf16.
 hipError_t launch_gather(const GatherArgs &a, int nfix, int nfix_l1, const Fixup *fixups, bool vec4,
                          hipStream_t stream, bool src_bf16 = false, bool dst_bf16 = false);
+// the same with a.w (not null) on the weighted instances; fp32 rows
+hipError_t launch_gather_weighted(const WeightedGatherArgs &a, int nfix, int nfix_l1, const Fixup *fixups, bool vec4,
+                                  hipStream_t stream);
+// out[p] = <A[ind[p], :], B[e, :]> for every entry p of the CSR (ptr, ind) over M rows, e the row holding p (the weight
+// gradient of hg_aggr_incidence_f32).  vec4: F % 4 == 0 and A, B 16-byte aligned.
+hipError_t launch_incidence_dot(int32_t M, int64_t nnz, int32_t F, const int32_t *ptr, const int32_t *ind, const float *A,
+                                const float *B, float *out, bool vec4, hipStream_t stream);
 hipError_t launch_fused(const FusedArgs &a, bool vec4, hipStream_t stream, bool xy_bf16 = false);
 hipError_t launch_hub_pass(const HubArgs &a, bool vec4, hipStream_t stream, bool x_bf16 = false);
 size_t hub_pass_lds_bytes(int32_t cap, int32_t row_floats, int32_t max_rec_words);

@@ -35,6 +35,7 @@ template <> struct Vec<1> {
   __device__ __forceinline__ void store_n(float *p, int) const { *p = x; }
   __device__ __forceinline__ void store_n_nt(float *p, int) const { __builtin_nontemporal_store(x, p); }
   __device__ __forceinline__ void add(const Vec &o) { x += o.x; }
+  __device__ __forceinline__ void fma(const Vec &o, float s) { x = __builtin_fmaf(o.x, s, x); }  // += o * s, one rounding
   __device__ __forceinline__ void mul(float s) { x *= s; }
   __device__ __forceinline__ void xor_reduce(int off) { x += __shfl_xor(x, off, 64); }
 };
@@ -83,6 +84,10 @@ template <> struct Vec<4> {
   }
   __device__ __forceinline__ void add(const Vec &o) {
     v.x += o.v.x; v.y += o.v.y; v.z += o.v.z; v.w += o.v.w;
+  }
+  __device__ __forceinline__ void fma(const Vec &o, float s) {
+    v.x = __builtin_fmaf(o.v.x, s, v.x); v.y = __builtin_fmaf(o.v.y, s, v.y);
+    v.z = __builtin_fmaf(o.v.z, s, v.z); v.w = __builtin_fmaf(o.v.w, s, v.w);
   }
   __device__ __forceinline__ void mul(float s) { v.x *= s; v.y *= s; v.z *= s; v.w *= s; }
   __device__ __forceinline__ void xor_reduce(int off) {
@@ -135,8 +140,11 @@ template <> struct Rows<bf16, 4> {
 // loads, then every LPR-lane group walks a contiguous run of the panel's rows as
 // one flat entry stream, U row loads in flight, adding in CSR order (so short
 // rows reproduce the CPU reference's summation order exactly).  TS / TD: element types of src / dst rows (Rows).
-template <int LPR, int VEC, typename TS = float, typename TD = float>
-__global__ __launch_bounds__(256) void gather_rows_kernel(const GatherArgs a) {
+// WT: per-entry weights (WeightedGatherArgs, hg_aggr_incidence_f32): the same walk, each gathered row added as
+// acc = fma(row, weight, acc).  Wave tasks load the weight beside the index; panels stage the weights in LDS after
+// sind (launch_gather_t sizes those instances' LDS for it).  Partial rows leave already weighted: fixups are unchanged.
+template <int LPR, int VEC, typename TS = float, typename TD = float, bool WT = false>
+__global__ __launch_bounds__(256) void gather_rows_kernel(const std::conditional_t<WT, WeightedGatherArgs, GatherArgs> a) {
   constexpr int U = 4;           // row loads in flight per lane (8, or two batches in flight: within 3 %, profiles/r01_fused_experiments.md)
   constexpr int G = 64 / LPR;    // row groups per wave
   constexpr int NG = 256 / LPR;  // row groups per workgroup
@@ -162,15 +170,20 @@ __global__ __launch_bounds__(256) void gather_rows_kernel(const GatherArgs a) {
     V acc = V::zero();
     for (int p = tk.beg + g; p < tk.end; p += G * U) {
       V v[U];
+      float wv[U];
 #pragma unroll
       for (int k = 0; k < U; k++) {
         const int q = p + k * G;
         const bool ok = col_ok && q < tk.end;
         const int64_t idx = ok ? a.ind[q] : 0;
+        if constexpr (WT) wv[k] = ok ? a.w[a.wperm ? a.wperm[q] : q] : 0.f;
         v[k] = ok ? RS::load(src + idx * F + col) : V::zero();
       }
 #pragma unroll
-      for (int k = 0; k < U; k++) acc.add(v[k]);
+      for (int k = 0; k < U; k++) {
+        if constexpr (WT) acc.fma(v[k], wv[k]);
+        else acc.add(v[k]);
+      }
     }
 #pragma unroll
     for (int off = LPR; off < 64; off <<= 1) acc.xor_reduce(off);
@@ -212,6 +225,13 @@ __global__ __launch_bounds__(256) void gather_rows_kernel(const GatherArgs a) {
     if (a.dst_map) sdst[i] = a.dst_map[pn.row0 + i];
   }
   for (int i = tid; i < pn.nnz_cnt; i += 256) sind[i] = a.ind[pn.nnz0 + i];
+  float *sw = reinterpret_cast<float *>(sind + a.panel_nnz);  // [panel_nnz], WT instances only
+  if constexpr (WT) {
+    for (int i = tid; i < pn.nnz_cnt; i += 256) {
+      const int q = pn.nnz0 + i;
+      sw[i] = a.w[a.wperm ? a.wperm[q] : q];
+    }
+  }
   __syncthreads();
 
   const int g = tid / LPR;
@@ -254,7 +274,8 @@ __global__ __launch_bounds__(256) void gather_rows_kernel(const GatherArgs a) {
           r++;
           row_end = sptr[r + 1];
         }
-        acc.add(v[k]);
+        if constexpr (WT) acc.fma(v[k], sw[p0 + k]);
+        else acc.add(v[k]);
       }
     }
   };
@@ -309,6 +330,73 @@ __global__ __launch_bounds__(256) void fixup_rows_kernel(const GatherArgs a, con
   TD *dst = static_cast<TD *>(a.dst);
   if (a.nt_dst) RD::store_n_nt(acc, dst + drow * F + col, a.F - col);
   else RD::store_n(acc, dst + drow * F + col, a.F - col);
+}
+
+// out[p] = <A[ind[p], :], B[e, :]> for every entry p of the CSR (ptr, ind), e the row that holds p: the gradient of
+// a per-entry weight of hg_aggr_incidence_f32.  Work is cut by entries, not rows (a power-law row reaches 4096
+// entries): a lane group of LPR lanes owns kDotRun consecutive entries.  It finds the row of its first entry by a
+// binary search inside the workgroup's row range (itself two uniform searches over ptr), then steps along.  Each output
+// is one lane group's: the lanes' fma chains over their columns, then a fixed butterfly over the LPR lanes --
+// deterministic.  The kDotRun entries' row loads are issued together.
+constexpr int kDotRun = 4;
+__device__ __forceinline__ int row_of(const int32_t *ptr, int lo, int hi, int64_t p) {  // ptr[lo] <= p < ptr[hi]
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (ptr[mid] <= p) lo = mid;
+    else hi = mid;
+  }
+  return lo;
+}
+template <int LPR, int VEC>
+__global__ __launch_bounds__(256) void incidence_dot_kernel(const int32_t *ptr, const int32_t *ind, int32_t M, int64_t nnz,
+                                                            int32_t F, const float *A, const float *B, float *out) {
+  using V = Vec<VEC>;
+  constexpr int NG = 256 / LPR;
+  const int tid = threadIdx.x, gl = tid & (LPR - 1), g = tid / LPR;
+  const int64_t c0 = (int64_t)blockIdx.x * NG * kDotRun;
+  const int64_t c1 = std::min<int64_t>(c0 + NG * kDotRun, nnz);
+  const int64_t p0 = c0 + (int64_t)g * kDotRun;
+  if (p0 >= c1) return;
+  const int elo = row_of(ptr, 0, M, c0);
+  const int ehi = row_of(ptr, elo, M, c1 - 1);
+  int e = row_of(ptr, elo, ehi + 1, p0);
+  const int n = (int)std::min<int64_t>(kDotRun, nnz - p0);
+  int64_t ua[kDotRun], eb[kDotRun];
+#pragma unroll
+  for (int k = 0; k < kDotRun; k++) {
+    const int64_t p = p0 + std::min(k, n - 1);
+    while (ptr[e + 1] <= p) e++;
+    ua[k] = (int64_t)ind[p] * F;
+    eb[k] = (int64_t)e * F;
+  }
+  float acc[kDotRun];
+#pragma unroll
+  for (int k = 0; k < kDotRun; k++) acc[k] = 0.f;
+  for (int c = gl * VEC; c < F; c += LPR * VEC) {
+    V x[kDotRun], y[kDotRun];
+#pragma unroll
+    for (int k = 0; k < kDotRun; k++) {
+      x[k] = V::load(A + ua[k] + c);
+      y[k] = V::load(B + eb[k] + c);
+    }
+#pragma unroll
+    for (int k = 0; k < kDotRun; k++) {
+      if constexpr (VEC == 4) {
+        acc[k] = __builtin_fmaf(x[k].v.x, y[k].v.x, acc[k]);
+        acc[k] = __builtin_fmaf(x[k].v.y, y[k].v.y, acc[k]);
+        acc[k] = __builtin_fmaf(x[k].v.z, y[k].v.z, acc[k]);
+        acc[k] = __builtin_fmaf(x[k].v.w, y[k].v.w, acc[k]);
+      } else {
+        acc[k] = __builtin_fmaf(x[k].x, y[k].x, acc[k]);
+      }
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < kDotRun; k++) {
+#pragma unroll
+    for (int off = 1; off < LPR; off <<= 1) acc[k] += __shfl_xor(acc[k], off, 64);
+    if (gl == 0 && k < n) out[p0 + k] = acc[k];
+  }
 }
 
 // Workgroup barrier that orders LDS traffic only.  __syncthreads() also drains the
@@ -1919,15 +2007,16 @@ static hipError_t launch_fixups_t(const GatherArgs &a, int nfix, int nfix_l1, co
   return hipGetLastError();
 }
 
-template <int LPR, int VEC, typename TS = float, typename TD = float>
-static hipError_t launch_gather_t(const GatherArgs &a, int nfix, int nfix_l1, const Fixup *fixups,
-                                  hipStream_t stream) {
+template <int LPR, int VEC, typename TS = float, typename TD = float, bool WT = false>
+static hipError_t launch_gather_t(const std::conditional_t<WT, WeightedGatherArgs, GatherArgs> &a, int nfix, int nfix_l1,
+                                  const Fixup *fixups, hipStream_t stream) {
   const int col_tiles = (a.F + LPR * VEC - 1) / (LPR * VEC);
   const int nblocks = a.n_task_blocks + a.npanels;
   if (nblocks > 0) {
-    const size_t lds = (size_t)(4 * a.panel_rows + 1 + a.panel_nnz) * sizeof(int32_t);
+    // the weighted instances stage one float per index entry beside sind
+    const size_t lds = (size_t)(4 * a.panel_rows + 1 + (WT ? 2 : 1) * a.panel_nnz) * sizeof(int32_t);
     const dim3 grid(nblocks, col_tiles);
-    const hipError_t e = launch_lds<gather_rows_kernel<LPR, VEC, TS, TD>>(grid, lds, stream, a);
+    const hipError_t e = launch_lds<gather_rows_kernel<LPR, VEC, TS, TD, WT>>(grid, lds, stream, a);
     if (e != hipSuccess) return e;
   }
   return launch_fixups_t<LPR, VEC, TD>(a, nfix, nfix_l1, fixups, stream);
@@ -1944,6 +2033,57 @@ hipError_t launch_gather(const GatherArgs &a, int nfix, int nfix_l1, const Fixup
     if (dst_bf16) return launch_gather_t<L, 4, float, bf16>(a, nfix, nfix_l1, fixups, stream);            \
     return vec4 ? launch_gather_t<L, 4>(a, nfix, nfix_l1, fixups, stream)                                \
                 : launch_gather_t<L, 1>(a, nfix, nfix_l1, fixups, stream);
+  switch (lpr) {
+    HG_CASE(1)
+    HG_CASE(2)
+    HG_CASE(4)
+    HG_CASE(8)
+    HG_CASE(16)
+    HG_CASE(32)
+    HG_CASE(64)
+  }
+#undef HG_CASE
+  return hipErrorInvalidValue;
+}
+
+hipError_t launch_gather_weighted(const WeightedGatherArgs &a, int nfix, int nfix_l1, const Fixup *fixups, bool vec4,
+                                  hipStream_t stream) {
+  if (!a.w) return hipErrorInvalidValue;
+  const int lanes = vec4 ? a.F / 4 : a.F;
+  const int lpr = std::min(64, next_pow2(std::max(lanes, 1)));
+#define HG_CASE(L)                                                                                     \
+  case L:                                                                                              \
+    return vec4 ? launch_gather_t<L, 4, float, float, true>(a, nfix, nfix_l1, fixups, stream)          \
+                : launch_gather_t<L, 1, float, float, true>(a, nfix, nfix_l1, fixups, stream);
+  switch (lpr) {
+    HG_CASE(1)
+    HG_CASE(2)
+    HG_CASE(4)
+    HG_CASE(8)
+    HG_CASE(16)
+    HG_CASE(32)
+    HG_CASE(64)
+  }
+#undef HG_CASE
+  return hipErrorInvalidValue;
+}
+
+hipError_t launch_incidence_dot(int32_t M, int64_t nnz, int32_t F, const int32_t *ptr, const int32_t *ind, const float *A,
+                                const float *B, float *out, bool vec4, hipStream_t stream) {
+  if (nnz == 0) return hipSuccess;
+  if (M <= 0 || F <= 0 || (vec4 && F % 4)) return hipErrorInvalidValue;
+  const int lanes = vec4 ? F / 4 : F;
+  const int lpr = std::min(64, next_pow2(std::max(lanes, 1)));
+  const int64_t per_block = (int64_t)(256 / lpr) * kDotRun;
+  const int64_t nblocks = (nnz + per_block - 1) / per_block;
+  if (nblocks > 0x7fffffff) return hipErrorInvalidValue;
+#define HG_CASE(L)                                                                                                   \
+  case L:                                                                                                            \
+    if (vec4) hipLaunchKernelGGL((incidence_dot_kernel<L, 4>), dim3((unsigned)nblocks), dim3(256), 0, stream, ptr, ind, M, \
+                                 nnz, F, A, B, out);                                                                 \
+    else hipLaunchKernelGGL((incidence_dot_kernel<L, 1>), dim3((unsigned)nblocks), dim3(256), 0, stream, ptr, ind, M,   \
+                            nnz, F, A, B, out);                                                                      \
+    return hipGetLastError();
   switch (lpr) {
     HG_CASE(1)
     HG_CASE(2)

@@ -432,6 +432,99 @@ def hgnnaggr_linear(csrptr_t, indices_t, node_feat, weight, degE=None, degV=None
     return _SumAggrLinear.apply(csrptr_t, indices_t, node_feat, weight, degE, degV, W, _opt(options))
 
 
+# ---- incidence-weighted aggregation (include/hg_aggr.h, hg_aggr_incidence_f32) ----------------------------------------
+
+def _incidence_args(csrptr_t, indices_t, node_feat, v2e, e2v, opt):
+    """Argument checks of incidence_aggr, in an order that decides every refusal before a device is touched: variant,
+    dtypes, shapes and lengths, then where the tensors live."""
+    if opt.variant not in ("auto", "pull"):
+        raise ValueError("incidence_aggr runs the pull kernels: variant must be 'auto' or 'pull', got %r" % opt.variant)
+    for name, t in (("node_feat", node_feat), ("v2e_weight", v2e), ("e2v_weight", e2v)):
+        if t is not None and (not isinstance(t, torch.Tensor) or t.dtype != torch.float32):
+            raise TypeError("%s must be a float32 tensor (incidence_aggr has no bfloat16 form), got %s"
+                            % (name, getattr(t, "dtype", type(t))))
+    if node_feat.dim() != 2:
+        raise ValueError("node_feat must be [N, F]")
+    if not isinstance(indices_t, torch.Tensor):
+        raise TypeError("indices_t must be an int32 tensor")
+    nnz = indices_t.numel()
+    for name, t in (("v2e_weight", v2e), ("e2v_weight", e2v)):
+        if t is not None and t.numel() != nnz:
+            raise ValueError("%s must have one weight per incidence (nnz = %d), got %d" % (name, nnz, t.numel()))
+    _check_index(csrptr_t, "csrptr_t")
+    _check_index(indices_t, "indices_t")
+    _check_feat(node_feat, "node_feat")
+    for name, t in (("v2e_weight", v2e), ("e2v_weight", e2v)):
+        if t is not None:
+            _check_feat(t, name, device=node_feat.device)
+
+
+class _IncidenceAggr(torch.autograd.Function):
+    """Y = Dv H_e2v De W H_v2e^T X with a weight per incidence, and its exact gradients for X and both weight arrays.
+    With P = degV * dY:  G = the same call on P with the weights swapped and no degV (hop 1's table, De W H_e2v^T P, goes
+    to xe_out); its output is dX.  dv2e[p = (e, u)] = <X[u], G[e]>, de2v[p = (e, v)] = <P[v], Xe[e]> (incidence_dot),
+    Xe the forward's hop-1 table, kept only when e2v needs a gradient.  degE / degV / W get none."""
+
+    @staticmethod
+    def forward(ctx, csrptr_t, indices_t, node_feat, v2e, e2v, degE, degV, W):
+        N, F = node_feat.shape
+        M = csrptr_t.numel() - 1
+        plan = cached_plan(N, csrptr_t, indices_t)
+        keep_xe = e2v is not None and ctx.needs_input_grad[4]
+        Xe = torch.empty((M, F), dtype=torch.float32, device=node_feat.device) if keep_xe else None
+        out = plan.aggregate_incidence(csrptr_t, indices_t, node_feat, v2e, e2v, degE, degV, W, xe_out=Xe)
+        keep_x = v2e is not None and ctx.needs_input_grad[3]
+        ctx.save_for_backward(csrptr_t, indices_t, node_feat if keep_x else None, v2e, e2v, degE, degV, W, Xe)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        csrptr_t, indices_t, X, v2e, e2v, degE, degV, W, Xe = ctx.saved_tensors
+        g = grad_out.contiguous()
+        N, F = g.shape
+        M = csrptr_t.numel() - 1
+        plan = cached_plan(N, csrptr_t, indices_t)
+        P = g if degV is None else g * degV.reshape(-1, 1)
+        need_x = ctx.needs_input_grad[2]
+        need_v2e = v2e is not None and ctx.needs_input_grad[3]
+        need_e2v = e2v is not None and ctx.needs_input_grad[4]
+        gx = gv = ge = None
+        if need_x or need_v2e:
+            G = torch.empty((M, F), dtype=torch.float32, device=g.device) if need_v2e else None
+            gx = plan.aggregate_incidence(csrptr_t, indices_t, P, e2v, v2e, degE, None, W, xe_out=G)
+            if need_v2e:
+                gv = plan.incidence_dot(csrptr_t, indices_t, X, G)
+        if need_e2v:
+            ge = plan.incidence_dot(csrptr_t, indices_t, P, Xe)
+        return None, None, gx if need_x else None, gv, ge, None, None, None
+
+
+def incidence_aggr(csrptr_t, indices_t, node_feat, v2e_weight=None, e2v_weight=None, degE=None, degV=None, W=None,
+                   options=None):
+    """Y[v] = degV[v] * sum_{p=(e,v)} e2v[p] * (degE[e] * W[e] * sum_{p'=(e,u)} v2e[p'] * X[u]): the sum aggregation with a
+    weight per (vertex, hyperedge) incidence, e.g. a probabilistic H or hypergraph attention's coefficients
+    (include/hg_aggr.h, hg_aggr_incidence_f32).  v2e_weight / e2v_weight: float32 [nnz], aligned with indices_t, or None
+    (unit weights); the same tensor twice for a symmetric weighting.  Gradients are exact for node_feat and both weight
+    arrays -- the reference has no rule for this operator, so Options.backward does not apply; degE / degV / W get none.
+    Options.variant 'auto' and 'pull' run (both are the pull kernels); 'fused', 'push_atomic', 'push_groups' raise
+    ValueError.  float32 only (TypeError for bfloat16)."""
+    opt = _opt(options)
+    v2e, e2v = (_flat(t) if isinstance(t, torch.Tensor) else t for t in (v2e_weight, e2v_weight))
+    _incidence_args(csrptr_t, indices_t, node_feat, v2e, e2v, opt)
+    degE, degV, W = _flat(degE), _flat(degV), _flat(W)
+    if not (torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad
+                                            for t in (node_feat, v2e, e2v))):
+        plan = cached_plan(node_feat.shape[0], csrptr_t, indices_t)
+        return plan.aggregate_incidence(csrptr_t, indices_t, node_feat, v2e, e2v, degE, degV, W)
+    return _IncidenceAggr.apply(csrptr_t, indices_t, node_feat, v2e, e2v, degE, degV, W)
+
+
+def HGNNAggrIncidence(hyperg, in_feat, v2e_weight, e2v_weight, degE, degV, Wdiag, options=None):
+    """HGNNAggr with a weight per incidence (incidence_aggr) on a HyperGraph's H_T tensors."""
+    return incidence_aggr(hyperg.H_T_csrptr, hyperg.H_T_colind, in_feat, v2e_weight, e2v_weight, degE, degV, Wdiag,
+                          options=options)
+
+
 # ---- module `hgnnaggr` (hgnnaggr.cc:122-151) ---------------------------------
 
 def hgnnaggr(balan_key, balan_row, group_st, group_ed, csrptr_t, indices_t, node_feat, degE, degV, W, options=None):

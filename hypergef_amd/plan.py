@@ -409,6 +409,66 @@ class Plan:
                 _ptr(dst), _ptr(workspace), nbytes, _stream_handle(src.device)))
         return dst
 
+    def incidence_perm(self):
+        """Host copy (numpy int32 [nnz]) of perm[q] = the H_T position of H entry q: the stable transpose behind
+        vertex_csr(), by which hop 2 of aggregate_incidence reads e2v.  Works on host-only plans too."""
+        perm = np.empty(self.nnz, np.int32)
+        _lib.check(_lib.lib().hg_plan_get_incidence_perm(self._h, perm.ctypes.data_as(ctypes.c_void_p)))
+        return perm
+
+    def incidence_workspace_bytes(self, F):
+        return int(_lib.lib().hg_aggr_incidence_workspace_bytes(self._h, F))
+
+    def aggregate_incidence(self, csrptr_t, colind_t, X, v2e=None, e2v=None, degE=None, degV=None, W=None,
+                            xe_out=None, out=None, workspace=None):
+        """Y = degV . H_e2v (degE . W . (H_v2e^T X)) with a weight per incidence (hg_aggr_incidence_f32): v2e / e2v are
+        float32 [nnz] aligned with colind_t, or None (unit weights).  xe_out ([M, F] float32) receives hop 1's table.
+        The first call with e2v builds and uploads the plan's permutation: not capturable (make one call before a
+        hipGraph capture)."""
+        _check_feat(X, "node_feat")
+        if X.dim() != 2 or X.shape[0] != self.N:
+            raise ValueError("node_feat must be [N = %d, F]" % self.N)
+        F = X.shape[1]
+        for name, t, n in (("v2e", v2e, self.nnz), ("e2v", e2v, self.nnz), ("degE", degE, self.M),
+                           ("degV", degV, self.N), ("W", W, self.M)):
+            if t is not None:
+                _check_feat(t, name, device=X.device)
+                if t.numel() != n:
+                    raise ValueError("%s must have %d elements, got %d" % (name, n, t.numel()))
+        for name, t, rows in (("xe_out", xe_out, self.M), ("out", out, self.N)):
+            if t is not None:
+                _check_feat(t, name, device=X.device)
+                if tuple(t.shape) != (rows, F):
+                    raise ValueError("%s must be [%d, %d]" % (name, rows, F))
+        Y = out if out is not None else torch.empty((self.N, F), dtype=torch.float32, device=X.device)
+        nbytes = self.incidence_workspace_bytes(F)
+        if workspace is None:
+            workspace = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=X.device)
+        else:
+            nbytes = workspace.numel() * workspace.element_size()
+        with torch.cuda.device(X.device):
+            _lib.check(_lib.lib().hg_aggr_incidence_f32(
+                self._h, F, _ptr(csrptr_t), _ptr(colind_t), _ptr(X), _ptr(v2e), _ptr(e2v), _ptr(degE), _ptr(degV),
+                _ptr(W), _ptr(xe_out), _ptr(Y), _ptr(workspace), nbytes, _stream_handle(X.device)))
+        return Y
+
+    def incidence_dot(self, csrptr_t, colind_t, A, B, out=None):
+        """out[p] = <A[u], B[e]> for every H_T entry p = (e, u) (hg_incidence_dot_f32): A [N, F], B [M, F]."""
+        _check_feat(A, "A")
+        _check_feat(B, "B", device=A.device)
+        if A.dim() != 2 or B.dim() != 2 or A.shape[0] != self.N or B.shape[0] != self.M or A.shape[1] != B.shape[1]:
+            raise ValueError("A must be [N = %d, F] and B [M = %d, F]" % (self.N, self.M))
+        if out is None:
+            out = torch.empty(self.nnz, dtype=torch.float32, device=A.device)
+        else:
+            _check_feat(out, "out", device=A.device)
+            if out.numel() != self.nnz:
+                raise ValueError("out must have nnz = %d elements" % self.nnz)
+        with torch.cuda.device(A.device):
+            _lib.check(_lib.lib().hg_incidence_dot_f32(self._h, A.shape[1], _ptr(csrptr_t), _ptr(colind_t), _ptr(A),
+                                                       _ptr(B), _ptr(out), _stream_handle(A.device)))
+        return out
+
 
 def linear_supported(F_in, F_out):
     """Widths hg_aggr_linear_f32 takes (MFMA tiles: K in {32, 64, 128}, 16-column output tiles)."""

@@ -379,6 +379,37 @@ HG_API int hg_gather_rows_f32(const hg_plan *plan, int32_t hop, int32_t F,
                        const float *scaleB, float *dst, void *workspace,
                        size_t workspace_bytes, hg_stream_t stream);
 
+/* ---- incidence-weighted aggregation ---------------------------------------------------------------------
+ * A weight per (vertex, hyperedge) pair: a probabilistic incidence matrix h(v, e) (HGNN), or hypergraph attention's
+ * coefficients a(v, e), learned, in both hops.  For the H_T entries p = (e, u) (the layout of csrptr_t / colind_t):
+ *     Xe[e] = ((sum_{p=(e,u)} v2e[p] * X[u]) * degE[e]) * W[e]          (hop 1, walks H_T)
+ *     Y[v]  =  (sum_{p=(e,v)} e2v[p] * Xe[e]) * degV[v]                 (hop 2, walks H)
+ *   v2e_val, e2v_val: fp32 [nnz] aligned with colind_t, or NULL (unit weights); the same array twice for a symmetric
+ *   weighting.  degE / degV / W as in hg_aggr_fused_f32 (degE = inf on an empty hyperedge is never applied).
+ *   Arithmetic: the unweighted pull variant's order on its panels + wave-task kernel, each gathered row added as
+ *   fma(row, weight, sum).  With both weight pointers NULL the call is that unweighted pull, bit for bit.
+ *   Xe_out: [M, F] or NULL; receives hop 1's table (a backward pass needs it).  X, Xe_out, Y: any F >= 1, 4-byte aligned.
+ *   workspace: hg_aggr_incidence_workspace_bytes(plan, F) (the pull layout), 256-byte aligned.
+ *   Hop 2 reads e2v through the plan's permutation of H entries to H_T positions (hg_plan_get_incidence_perm), built
+ *   and uploaded by the first call that passes e2v_val: that call allocates, so it cannot be captured into a hipGraph.
+ *   Make one such call before capturing (hg_plan_get_incidence_perm alone does not do: it uploads nothing), as
+ *   hg_plan_prepare is called before capturing hg_aggr_fused_f32.  Later calls only enqueue.
+ *   HG_ERR_UNSUPPORTED where panel_rows / panel_nnz leave no LDS for the staged weights.
+ * hg_incidence_dot_f32: out[p] = <A[u, :], B[e, :]> for every H_T entry p = (e, u): the weight gradient (A [N, F],
+ *   B [M, F], out [nnz]).  Work is cut by entries; every output is reduced by one lane group in a fixed order
+ *   (deterministic).
+ * hg_plan_get_incidence_perm: host copy of perm[q] = H_T position of H entry q (the stable transpose behind
+ *   hg_plan_get_vertex_csr, so ind_v[q] is the hyperedge holding position perm[q]); host-only plans too.
+ * Detect these entries by their exported symbols (HG_AGGR_VERSION does not change). */
+HG_API size_t hg_aggr_incidence_workspace_bytes(const hg_plan *plan, int32_t F);
+HG_API int hg_aggr_incidence_f32(const hg_plan *plan, int32_t F, const int32_t *csrptr_t, const int32_t *colind_t,
+                                 const float *X, const float *v2e_val, const float *e2v_val,
+                                 const float *degE, const float *degV, const float *W,
+                                 float *Xe_out, float *Y, void *workspace, size_t workspace_bytes, hg_stream_t stream);
+HG_API int hg_incidence_dot_f32(const hg_plan *plan, int32_t F, const int32_t *csrptr_t, const int32_t *colind_t,
+                                const float *A, const float *B, float *out, hg_stream_t stream);
+HG_API int hg_plan_get_incidence_perm(const hg_plan *plan, int32_t *perm_host);
+
 /* first_aggr = "max" pieces (hgnnaggr_max, source/hgnnaggr/hgnnaggr_cuda.cu:144-208).
  * hg_gather_max_f32: Xe[e,k] = (max_{u in e} X[u,k], start -1e5, strict >) * (degE[e]*W[e]),
  * record[e,k] = winning vertex (0 if none).  The second hop is hg_gather_rows_f32(hop = 1).
