@@ -10,8 +10,10 @@ from . import ops, plan, synth  # noqa: F401
 from .balancer import balance_schedule  # noqa: F401
 from .hypergraph import HyperGraph  # noqa: F401
 from .ops import (HGNNAggr, HGNNAggrIncidence, HGNNAggrLinear, UniGNNConv, UniGNNConvdeg,  # noqa: F401
-                  UniGNNConvLinear, hgnnaggr_linear, incidence_aggr)
+                  UniGNNConvLinear, hgnnaggr_linear, incidence_aggr, incidence_softmax, incidence_sum)
 from .plan import Plan  # noqa: F401
+
+from .models import HypergraphAttnConv  # noqa: F401
 
 # The reference builds two top-level extension modules (setup.py:18,32-33).  They ship as real
 # files next to this package (`hgnnaggr.py`, `unignnaggr.py`: repo root, or site-packages after

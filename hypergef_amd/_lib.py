@@ -37,6 +37,7 @@ SYMBOLS = (
     "hg_gather_rows_f32", "hg_aggr_push_groups_f32", "hg_gather_max_f32",
     "hg_scatter_record_f32",
     "hg_aggr_incidence_workspace_bytes", "hg_aggr_incidence_f32", "hg_incidence_dot_f32", "hg_plan_get_incidence_perm",
+    "hg_incidence_attention_f32", "hg_incidence_attention_bwd_f32", "hg_incidence_sum_f32", "hg_plan_get_segment_info",
 )
 
 
@@ -183,6 +184,15 @@ def lib():
         L.hg_incidence_dot_f32.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp]
         L.hg_plan_get_incidence_perm.restype = ctypes.c_int
         L.hg_plan_get_incidence_perm.argtypes = [vp, vp]
+    if hasattr(L, "hg_incidence_attention_f32"):  # likewise
+        L.hg_incidence_attention_f32.restype = ctypes.c_int
+        L.hg_incidence_attention_f32.argtypes = [vp, i32, vp, vp, vp, vp, ctypes.c_float, vp, vp]
+        L.hg_incidence_attention_bwd_f32.restype = ctypes.c_int
+        L.hg_incidence_attention_bwd_f32.argtypes = [vp, i32, vp, vp, vp, vp, ctypes.c_float, vp, vp, vp, vp, vp, vp]
+        L.hg_incidence_sum_f32.restype = ctypes.c_int
+        L.hg_incidence_sum_f32.argtypes = [vp, i32, vp, vp, vp, vp, vp]
+        L.hg_plan_get_segment_info.restype = ctypes.c_int
+        L.hg_plan_get_segment_info.argtypes = [vp, i32, vp, vp]
     L.hg_aggr_push_groups_f32.restype = ctypes.c_int
     L.hg_aggr_push_groups_f32.argtypes = [i32, i32, i32, i64, vp, vp, vp, vp, vp, vp,
                                           vp, vp, vp, vp, vp, vp]

@@ -9,6 +9,7 @@
 #include <new>
 #include <string>
 
+#include "hg_attention.h"
 #include "hg_kernels.h"
 
 namespace {
@@ -521,6 +522,84 @@ int get_incidence_perm(const hg_plan *cp, bool upload_it, const int32_t **d_perm
   return HG_OK;
 }
 
+// The segment kernels' view of one side of the plan (hg_attention.h): the list of rows longer than kSegLong and the lane-
+// group width for the rest, built once on the host under perm_mu and, with upload, copied to the device -- the laziness
+// rule of get_incidence_perm.
+int get_segments(const hg_plan *cp, int side, bool upload_it, const int32_t **d_long, int32_t *nlong, int32_t *width) {
+  hg_plan *p = const_cast<hg_plan *>(cp);
+  std::lock_guard<std::mutex> lock(p->perm_mu);
+  if (!p->seg_built[side]) {
+    const std::vector<int32_t> &ptr = side == 0 ? p->ptr_t : p->ptr_v;
+    const int32_t nseg = side == 0 ? p->M : p->N;
+    int64_t entries = 0, rows = 0;  // of the non-empty rows a lane group walks
+    try {
+      p->long_seg[side].clear();
+      for (int32_t r = 0; r < nseg; r++) {
+        const int32_t len = ptr[r + 1] - ptr[r];
+        if (len > hg::kSegLong) p->long_seg[side].push_back(r);
+        else if (len > 0) entries += len, rows++;
+      }
+    } catch (const std::bad_alloc &) {
+      hg::set_error("long-segment list: host allocation failed");
+      return HG_ERR_NOMEM;
+    }
+    p->seg_width[side] = hg::seg_width(rows > 0 ? (double)entries / (double)rows : 0.0);
+    p->seg_built[side] = true;
+  }
+  if (upload_it && !p->d_long_seg[side] && !p->long_seg[side].empty()) {
+    int rc = upload(p->long_seg[side], &p->d_long_seg[side], p->device_bytes);
+    if (rc != HG_OK) {
+      if (p->d_long_seg[side]) (void)hipFree(p->d_long_seg[side]);
+      p->d_long_seg[side] = nullptr;
+      return rc;
+    }
+  }
+  if (d_long) *d_long = p->d_long_seg[side];
+  if (nlong) *nlong = (int32_t)p->long_seg[side].size();
+  if (width) *width = p->seg_width[side];
+  return HG_OK;
+}
+
+// Common refusals of the three segment entries; *skip: nothing to do.
+int check_segment_call(const char *who, const hg_plan *plan, int side, const int32_t *csrptr_t, const int32_t *colind_t) {
+  if (!plan) {
+    hg::set_error(std::string(who) + ": null plan");
+    return HG_ERR_INVALID;
+  }
+  if (plan->opts.flags & HG_PLAN_HOST_ONLY) {
+    hg::set_error(std::string(who) + ": plan was built with HG_PLAN_HOST_ONLY and holds no device arrays");
+    return HG_ERR_UNSUPPORTED;
+  }
+  if (side != 0 && side != 1) {
+    hg::set_error(std::string(who) + ": group / side must be 0 (hyperedge) or 1 (vertex)");
+    return HG_ERR_INVALID;
+  }
+  if (!csrptr_t || (plan->nnz > 0 && !colind_t)) {
+    hg::set_error(std::string(who) + ": null array");
+    return HG_ERR_INVALID;
+  }
+  return HG_OK;
+}
+
+// One launch of the segment kernels on `side`: fills the side's arrays of `a` (scores: sv [N], se [M]) and runs `body`.
+int run_segments(const char *who, const hg_plan *plan, int body, int side, const int32_t *csrptr_t, const int32_t *colind_t,
+                 const float *sv, const float *se, hg::SegArgs a, hipStream_t stream) {
+  int rc;
+  const int32_t *perm = nullptr;
+  if (side == 1 && (rc = get_incidence_perm(plan, true, &perm)) != HG_OK) return rc;
+  int32_t width = 4;
+  if ((rc = get_segments(plan, side, true, &a.long_seg, &a.nlong, &width)) != HG_OK) return rc;
+  a.ptr = side == 0 ? csrptr_t : plan->d_ptr_v;
+  a.ind = side == 0 ? colind_t : plan->d_ind_v;
+  a.perm = perm;
+  a.nseg = side == 0 ? plan->M : plan->N;
+  a.own = side == 0 ? se : sv;
+  a.other = side == 0 ? sv : se;
+  hipError_t e = hg::launch_segments(body, side, width, a, stream);
+  if (e != hipSuccess) return hip_fail(who, e);
+  return HG_OK;
+}
+
 int run_hop(const hg_plan *p, int hop, int32_t F, const int32_t *ptr, const int32_t *ind,
             const void *src, const float *scaleA, const float *scaleB, void *dst,
             float *partial, hipStream_t stream, bool src_bf16 = false, bool dst_bf16 = false) {
@@ -732,6 +811,8 @@ void hg_plan_destroy(hg_plan *p) {
       if (q) (void)hipFree(q);
   }
   if (p->d_perm) (void)hipFree(p->d_perm);
+  for (int32_t *q : p->d_long_seg)
+    if (q) (void)hipFree(q);
   delete p;
 }
 
@@ -1583,6 +1664,82 @@ int hg_plan_get_incidence_perm(const hg_plan *plan, int32_t *perm_host) {
   int rc = get_incidence_perm(plan, false, nullptr);
   if (rc != HG_OK) return rc;
   if (plan->nnz > 0) std::memcpy(perm_host, plan->perm.data(), (size_t)plan->nnz * sizeof(int32_t));
+  return HG_OK;
+}
+
+// ---- hypergraph attention coefficients ------------------------------------------------------------------------------
+
+int hg_incidence_attention_f32(const hg_plan *plan, int32_t group, const int32_t *csrptr_t, const int32_t *colind_t,
+                               const float *sv, const float *se, float slope, float *alpha_out, hg_stream_t stream) {
+  int rc = check_segment_call("hg_incidence_attention_f32", plan, group, csrptr_t, colind_t);
+  if (rc != HG_OK) return rc;
+  if ((plan->nnz > 0 && !alpha_out) || !(slope == slope) || slope - slope != 0.f) {
+    hg::set_error("hg_incidence_attention_f32: null alpha_out or non-finite slope");
+    return HG_ERR_INVALID;
+  }
+  if (plan->nnz == 0) return HG_OK;
+  hg::SegArgs a = {};
+  a.slope = slope;
+  a.out_entry = alpha_out;
+  return run_segments("incidence_attention launch", plan, hg::kSegSoftmax, group, csrptr_t, colind_t, sv, se, a,
+                      static_cast<hipStream_t>(stream));
+}
+
+int hg_incidence_attention_bwd_f32(const hg_plan *plan, int32_t group, const int32_t *csrptr_t, const int32_t *colind_t,
+                                   const float *sv, const float *se, float slope, const float *alpha, const float *dalpha,
+                                   float *ds_out, float *dsv_out, float *dse_out, hg_stream_t stream) {
+  int rc = check_segment_call("hg_incidence_attention_bwd_f32", plan, group, csrptr_t, colind_t);
+  if (rc != HG_OK) return rc;
+  if ((plan->nnz > 0 && (!alpha || !dalpha || !ds_out)) || !(slope == slope) || slope - slope != 0.f) {
+    hg::set_error("hg_incidence_attention_bwd_f32: null alpha / dalpha / ds_out or non-finite slope");
+    return HG_ERR_INVALID;
+  }
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  hg::SegArgs a = {};
+  a.slope = slope;
+  a.val = alpha;
+  a.dval = dalpha;
+  a.out_entry = ds_out;
+  a.out_seg = group == 0 ? dse_out : dsv_out;  // the group's own end: summed by the kernel that forms ds
+  rc = run_segments("incidence_attention_bwd launch", plan, hg::kSegSoftmaxBwd, group, csrptr_t, colind_t, sv, se, a, s);
+  if (rc != HG_OK) return rc;
+  float *other_out = group == 0 ? dsv_out : dse_out;  // the other end: a segment sum of ds over that side
+  if (!other_out) return HG_OK;
+  hg::SegArgs b = {};
+  b.val = ds_out;
+  b.out_seg = other_out;
+  return run_segments("incidence_attention_bwd sum launch", plan, hg::kSegSum, 1 - group, csrptr_t, colind_t, nullptr,
+                      nullptr, b, s);
+}
+
+int hg_incidence_sum_f32(const hg_plan *plan, int32_t side, const int32_t *csrptr_t, const int32_t *colind_t,
+                         const float *val, float *out, hg_stream_t stream) {
+  int rc = check_segment_call("hg_incidence_sum_f32", plan, side, csrptr_t, colind_t);
+  if (rc != HG_OK) return rc;
+  if ((plan->nnz > 0 && !val) || !out) {
+    hg::set_error("hg_incidence_sum_f32: null array");
+    return HG_ERR_INVALID;
+  }
+  hg::SegArgs a = {};
+  a.val = val;
+  a.out_seg = out;
+  return run_segments("incidence_sum launch", plan, hg::kSegSum, side, csrptr_t, colind_t, nullptr, nullptr, a,
+                      static_cast<hipStream_t>(stream));
+}
+
+int hg_plan_get_segment_info(const hg_plan *plan, int32_t side, int32_t *info, int32_t *long_seg_host) {
+  if (!plan || !info || (side != 0 && side != 1)) {
+    hg::set_error("hg_plan_get_segment_info: null argument or side not 0 / 1");
+    return HG_ERR_INVALID;
+  }
+  int32_t nlong = 0, width = 0;
+  int rc = get_segments(plan, side, false, nullptr, &nlong, &width);
+  if (rc != HG_OK) return rc;
+  info[0] = width;
+  info[1] = hg::kSegKeep;
+  info[2] = hg::kSegLong;
+  info[3] = nlong;
+  if (long_seg_host && nlong > 0) std::memcpy(long_seg_host, plan->long_seg[side].data(), (size_t)nlong * sizeof(int32_t));
   return HG_OK;
 }
 

@@ -1,0 +1,37 @@
+// Segment kernels of the hypergraph attention coefficients (hg_attention.hip): argument block and launcher, shared with
+// hg_api.hip.  A segment is one group of incidences: a hyperedge's members (side 0, a contiguous H_T row) or a vertex's
+// hyperedges (side 1, an H row whose entries reach their H_T positions through perm).
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+namespace hg {
+
+constexpr int kSegBlock = 256;  // threads per workgroup: 256 / width lane groups, or one long segment
+constexpr int kSegKeep = 4;     // entries per lane whose gathered values stay in registers across the passes
+constexpr int kSegLong = 128;   // segments of more entries leave the lane groups for a whole workgroup
+
+enum { kSegSoftmax = 0, kSegSoftmaxBwd = 1, kSegSum = 2 };
+
+struct SegArgs {
+  const int32_t *ptr;       // the side's CSR row pointers [nseg + 1]: csrptr_t, or the derived ptr_v
+  const int32_t *ind;       // the other end of every entry: colind_t (member vertex), or ind_v (hyperedge)
+  const int32_t *perm;      // side 1: H entry -> H_T position; side 0: null
+  const int32_t *long_seg;  // ids of the segments of more than kSegLong entries, ascending [nlong]
+  int32_t nseg, nlong;
+  const float *own;    // score of the segment's own end ([nseg]: se on side 0, sv on side 1), or null (0)
+  const float *other;  // score gathered through ind ([N] sv on side 0, [M] se on side 1), or null (0)
+  float slope;
+  const float *val;    // kSegSoftmaxBwd: alpha; kSegSum: the summed values; H_T order
+  const float *dval;   // kSegSoftmaxBwd: dalpha, H_T order
+  float *out_entry;    // kSegSoftmax: alpha; kSegSoftmaxBwd: ds; H_T order
+  float *out_seg;      // kSegSoftmaxBwd: the segments' own sums of ds (or null); kSegSum: out [nseg]
+};
+
+// Lane-group width of a side whose segments of at most kSegLong entries hold `mean` entries on average.
+int seg_width(double mean);
+// body: kSeg*; side 0 / 1; width 4 / 8 / 16 (seg_width)
+hipError_t launch_segments(int body, int side, int width, const SegArgs &a, hipStream_t stream);
+
+}  // namespace hg

@@ -1,0 +1,241 @@
+// Hypergraph attention coefficients (include/hg_aggr.h, hg_incidence_attention_f32 and friends): one family of segment
+// kernels with three bodies -- the fused score + softmax, its backward, and the plain segment sum.
+//
+// A segment is a group of incidences: the members of a hyperedge (side 0: a contiguous row of H_T, entry i sits at H_T
+// position i) or the hyperedges of a vertex (side 1: a row of the derived H, entry i sits at H_T position perm[i]).
+// Everything per entry -- alpha, dalpha, ds, val -- lives in H_T order, so side 0 streams it and side 1 reaches it through
+// perm, as hop 2 of hg_aggr_incidence_f32 reaches e2v.
+//
+// Work split.  A lane group of W lanes (4, 8 or 16: the side's mean segment length, seg_width) owns one segment and
+// strides over it; 256 / W segments per workgroup.  A lane gathers its first kSegKeep entries once and keeps them in
+// registers across the passes of a body (softmax: maximum, sum, write); what a longer segment holds beyond W * kSegKeep
+// entries is gathered again in each pass.  Segments of more than kSegLong entries would leave one lane group looping
+// long after the grid has drained (the power-law shape has 4096-entry hyperedges and 25000-entry vertices beside a mean
+// of 3-6): the lane groups skip them, and the first `nlong` workgroups of the same launch take one each from the plan's
+// list, all 256 lanes striding, the same code with W = 256.
+//
+// No atomics.  A lane adds its entries in ascending order, the lanes of a group are combined by an xor butterfly
+// (commutative at every step: all lanes end with the same bits), a workgroup combines its four waves' results in wave
+// order through LDS.  The order depends on the segment's length and the side's width only: two calls give the same bits.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+
+#include "hg_attention.h"
+
+namespace hg {
+namespace {
+
+struct OpMax {
+  static __device__ __forceinline__ float apply(float a, float b) { return fmaxf(a, b); }
+};
+struct OpSum {
+  static __device__ __forceinline__ float apply(float a, float b) { return a + b; }
+};
+
+// Combine one value per lane over the W lanes that share a segment; every lane gets the result.
+template <int W, typename Op>
+__device__ __forceinline__ float combine(float v, float *lds) {
+  if constexpr (W <= 64) {
+#pragma unroll
+    for (int o = W / 2; o > 0; o >>= 1) v = Op::apply(v, __shfl_xor(v, o, W));
+    return v;
+  } else {  // the whole workgroup: four waves
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = Op::apply(v, __shfl_xor(v, o, 64));
+    __syncthreads();  // the previous result has been read by everyone
+    if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return Op::apply(Op::apply(lds[0], lds[1]), Op::apply(lds[2], lds[3]));
+  }
+}
+
+// H_T position of entry i of the walked CSR
+template <int SIDE>
+__device__ __forceinline__ int32_t position(const SegArgs &a, int32_t i) {
+  return SIDE == 0 ? i : a.perm[i];
+}
+
+// raw score of entry i: the segment's own score plus the gathered one of the entry's other end
+__device__ __forceinline__ float raw_score(const SegArgs &a, float own, int32_t i) {
+  return a.other ? own + a.other[a.ind[i]] : own;
+}
+
+__device__ __forceinline__ float leaky(float raw, float slope) { return raw > 0.f ? raw : slope * raw; }
+
+// alpha = softmax over the segment of leaky(raw).  An empty segment runs no entry loop at all: nothing is written and no
+// exponential of (-inf) - (-inf) is formed.  A one-entry segment gives exp(0) / 1 = 1.0f exactly.
+template <int SIDE, int W>
+__device__ __forceinline__ void softmax_segment(const SegArgs &a, int32_t seg, int32_t beg, int32_t end, int lane,
+                                                float *lds) {
+  const float own = (a.own && beg < end) ? a.own[seg] : 0.f;
+  float sc[kSegKeep];
+  int32_t pos[kSegKeep];
+  float m = -INFINITY;
+#pragma unroll
+  for (int k = 0; k < kSegKeep; k++) {
+    const int32_t i = beg + lane + k * W;
+    if (i < end) {
+      pos[k] = position<SIDE>(a, i);
+      sc[k] = leaky(raw_score(a, own, i), a.slope);
+      m = fmaxf(m, sc[k]);
+    }
+  }
+  const int32_t tail = beg + lane + kSegKeep * W;
+#pragma unroll 4
+  for (int32_t i = tail; i < end; i += W) m = fmaxf(m, leaky(raw_score(a, own, i), a.slope));
+  m = combine<W, OpMax>(m, lds);
+  float sum = 0.f;
+#pragma unroll
+  for (int k = 0; k < kSegKeep; k++) {
+    if (beg + lane + k * W < end) {
+      sc[k] = __expf(sc[k] - m);
+      sum += sc[k];
+    }
+  }
+#pragma unroll 4
+  for (int32_t i = tail; i < end; i += W) sum += __expf(leaky(raw_score(a, own, i), a.slope) - m);
+  sum = combine<W, OpSum>(sum, lds);
+  const float inv = 1.f / sum;  // the entry holding the maximum contributes exp(0) = 1: sum >= 1 wherever it is used
+#pragma unroll
+  for (int k = 0; k < kSegKeep; k++)
+    if (beg + lane + k * W < end) a.out_entry[pos[k]] = sc[k] * inv;
+#pragma unroll 4
+  for (int32_t i = tail; i < end; i += W)
+    a.out_entry[position<SIDE>(a, i)] = __expf(leaky(raw_score(a, own, i), a.slope) - m) * inv;
+}
+
+// ds = alpha * (dalpha - t) * leaky'(raw), t = sum over the segment of alpha * dalpha; the segment's own sum of ds goes to
+// out_seg (0 for an empty segment).  slope == 1: the non-linearity is the identity and no score is gathered.
+template <int SIDE, int W>
+__device__ __forceinline__ void softmax_bwd_segment(const SegArgs &a, int32_t seg, int32_t beg, int32_t end, int lane,
+                                                    float *lds, bool valid) {
+  const bool need_raw = a.slope != 1.f;
+  const float own = (need_raw && a.own && beg < end) ? a.own[seg] : 0.f;
+  float al[kSegKeep], da[kSegKeep], fac[kSegKeep];
+  int32_t pos[kSegKeep];
+  float t = 0.f;
+#pragma unroll
+  for (int k = 0; k < kSegKeep; k++) {
+    const int32_t i = beg + lane + k * W;
+    if (i < end) {
+      pos[k] = position<SIDE>(a, i);
+      al[k] = a.val[pos[k]];
+      da[k] = a.dval[pos[k]];
+      fac[k] = (need_raw && !(raw_score(a, own, i) > 0.f)) ? a.slope : 1.f;
+      t += al[k] * da[k];
+    }
+  }
+  const int32_t tail = beg + lane + kSegKeep * W;
+#pragma unroll 4
+  for (int32_t i = tail; i < end; i += W) {
+    const int32_t p = position<SIDE>(a, i);
+    t += a.val[p] * a.dval[p];
+  }
+  t = combine<W, OpSum>(t, lds);
+  float dsum = 0.f;
+#pragma unroll
+  for (int k = 0; k < kSegKeep; k++) {
+    if (beg + lane + k * W < end) {
+      const float d = al[k] * (da[k] - t) * fac[k];
+      a.out_entry[pos[k]] = d;
+      dsum += d;
+    }
+  }
+#pragma unroll 4
+  for (int32_t i = tail; i < end; i += W) {
+    const int32_t p = position<SIDE>(a, i);
+    const float f = (need_raw && !(raw_score(a, own, i) > 0.f)) ? a.slope : 1.f;
+    const float d = a.val[p] * (a.dval[p] - t) * f;
+    a.out_entry[p] = d;
+    dsum += d;
+  }
+  if (a.out_seg) {
+    dsum = combine<W, OpSum>(dsum, lds);
+    if (lane == 0 && valid) a.out_seg[seg] = dsum;
+  }
+}
+
+template <int SIDE, int W>
+__device__ __forceinline__ void sum_segment(const SegArgs &a, int32_t seg, int32_t beg, int32_t end, int lane, float *lds,
+                                            bool valid) {
+  float s = 0.f;
+#pragma unroll 4
+  for (int32_t i = beg + lane; i < end; i += W) s += a.val[position<SIDE>(a, i)];
+  s = combine<W, OpSum>(s, lds);
+  if (lane == 0 && valid) a.out_seg[seg] = s;
+}
+
+template <int BODY, int SIDE, int W>
+__device__ __forceinline__ void run_segment(const SegArgs &a, int32_t seg, int32_t beg, int32_t end, int lane, float *lds,
+                                            bool valid) {
+  if constexpr (BODY == kSegSoftmax) softmax_segment<SIDE, W>(a, seg, beg, end, lane, lds);
+  else if constexpr (BODY == kSegSoftmaxBwd) softmax_bwd_segment<SIDE, W>(a, seg, beg, end, lane, lds, valid);
+  else sum_segment<SIDE, W>(a, seg, beg, end, lane, lds, valid);
+}
+
+// Workgroups [0, nlong): one long segment each (they run longest, so they start first); the others: 256 / W lane groups,
+// one segment each.  Lanes without a segment of their own (past the last one, or a long one's lane group) walk an empty
+// range and take part in the butterflies: no lane leaves before the last cross-lane step.
+template <int BODY, int SIDE, int W>
+__global__ __launch_bounds__(kSegBlock) void segment_kernel(SegArgs a) {
+  __shared__ float lds[kSegBlock / 64];
+  if ((int32_t)blockIdx.x < a.nlong) {
+    const int32_t seg = a.long_seg[blockIdx.x];
+    run_segment<BODY, SIDE, kSegBlock>(a, seg, a.ptr[seg], a.ptr[seg + 1], (int)threadIdx.x, lds, true);
+    return;
+  }
+  constexpr int kGroups = kSegBlock / W;
+  const int64_t s = (int64_t)((int32_t)blockIdx.x - a.nlong) * kGroups + (int)threadIdx.x / W;
+  bool valid = s < a.nseg;
+  const int32_t seg = valid ? (int32_t)s : 0;
+  int32_t beg = 0, end = 0;
+  if (valid) {
+    beg = a.ptr[seg];
+    end = a.ptr[seg + 1];
+    if (end - beg > kSegLong) {  // a workgroup of its own has it
+      beg = end = 0;
+      valid = false;
+    }
+  }
+  run_segment<BODY, SIDE, W>(a, seg, beg, end, (int)threadIdx.x % W, lds, valid);
+}
+
+template <int BODY, int SIDE>
+hipError_t launch_width(int width, unsigned nblocks, const SegArgs &a, hipStream_t stream) {
+  switch (width) {
+    case 4: hipLaunchKernelGGL((segment_kernel<BODY, SIDE, 4>), dim3(nblocks), dim3(kSegBlock), 0, stream, a); break;
+    case 8: hipLaunchKernelGGL((segment_kernel<BODY, SIDE, 8>), dim3(nblocks), dim3(kSegBlock), 0, stream, a); break;
+    case 16: hipLaunchKernelGGL((segment_kernel<BODY, SIDE, 16>), dim3(nblocks), dim3(kSegBlock), 0, stream, a); break;
+    default: return hipErrorInvalidValue;
+  }
+  return hipGetLastError();
+}
+
+template <int BODY>
+hipError_t launch_side(int side, int width, unsigned nblocks, const SegArgs &a, hipStream_t stream) {
+  return side == 0 ? launch_width<BODY, 0>(width, nblocks, a, stream) : launch_width<BODY, 1>(width, nblocks, a, stream);
+}
+
+}  // namespace
+
+// The narrowest lane group that covers an average segment in one step: a wider one idles lanes on the typical segment
+// (mean lengths are 3-6), a narrower one walks it in several dependent steps.
+int seg_width(double mean) { return mean <= 4.0 ? 4 : mean <= 8.0 ? 8 : 16; }
+
+hipError_t launch_segments(int body, int side, int width, const SegArgs &a, hipStream_t stream) {
+  if (a.nseg <= 0) return hipSuccess;
+  if (side < 0 || side > 1 || a.nlong < 0 || !a.ptr || (a.nlong > 0 && !a.long_seg)) return hipErrorInvalidValue;
+  if (width != 4 && width != 8 && width != 16) return hipErrorInvalidValue;
+  const int64_t groups = kSegBlock / width;
+  const int64_t nblocks = a.nlong + (a.nseg + groups - 1) / groups;
+  if (nblocks > 0x7fffffff) return hipErrorInvalidValue;
+  switch (body) {
+    case kSegSoftmax: return launch_side<kSegSoftmax>(side, width, (unsigned)nblocks, a, stream);
+    case kSegSoftmaxBwd: return launch_side<kSegSoftmaxBwd>(side, width, (unsigned)nblocks, a, stream);
+    case kSegSum: return launch_side<kSegSum>(side, width, (unsigned)nblocks, a, stream);
+  }
+  return hipErrorInvalidValue;
+}
+
+}  // namespace hg

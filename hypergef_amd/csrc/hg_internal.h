@@ -268,6 +268,13 @@ struct hg_plan {
   bool perm_built = false;
   int32_t *d_perm = nullptr;
   std::mutex perm_mu;
+  // The segment kernels (hg_incidence_attention_f32, hg_incidence_sum_f32), per side (0: H_T rows, 1: H rows): the rows too
+  // long for a lane group, ascending, and the lane-group width for the others.  Built and uploaded on first use, under
+  // perm_mu, as perm is.
+  std::vector<int32_t> long_seg[2];
+  bool seg_built[2] = {false, false};
+  int32_t seg_width[2] = {4, 4};
+  int32_t *d_long_seg[2] = {nullptr, nullptr};
   double small_nnz_frac = 0.0;  // share of incidences in hyperedges of <= t_big members
   int64_t device_bytes = 0;
   int device = -1;

@@ -525,6 +525,113 @@ def HGNNAggrIncidence(hyperg, in_feat, v2e_weight, e2v_weight, degE, degV, Wdiag
                           options=options)
 
 
+# ---- hypergraph attention coefficients (include/hg_aggr.h, hg_incidence_attention_f32) --------------------------------
+
+_GROUPS = ("hyperedge", "vertex")
+
+
+def _segment_args(what, csrptr_t, indices_t, floats, lengths, group, opt):
+    """Argument checks of incidence_softmax / incidence_sum in _incidence_args' order: every refusal is decided before a
+    device is touched.  floats: (name, tensor or None) pairs; lengths: the element count each must have."""
+    if opt is not None and opt.variant not in ("auto", "pull"):
+        raise ValueError("%s runs the atomic-free segment kernels: variant must be 'auto' or 'pull', got %r"
+                         % (what, opt.variant))
+    if group not in _GROUPS:
+        raise ValueError("group / side must be 'hyperedge' or 'vertex', got %r" % (group,))
+    for name, t in floats:
+        if t is not None and (not isinstance(t, torch.Tensor) or t.dtype != torch.float32):
+            raise TypeError("%s must be a float32 tensor (%s has no bfloat16 form), got %s"
+                            % (name, what, getattr(t, "dtype", type(t))))
+    if not isinstance(csrptr_t, torch.Tensor) or not isinstance(indices_t, torch.Tensor):
+        raise TypeError("csrptr_t and indices_t must be int32 tensors")
+    for (name, t), n in zip(floats, lengths):
+        if t is not None and t.numel() != n:
+            raise ValueError("%s must have %d elements, got %d" % (name, n, t.numel()))
+    _check_index(csrptr_t, "csrptr_t")
+    _check_index(indices_t, "indices_t")
+    for name, t in floats:
+        if t is not None:
+            _check_feat(t, name, device=csrptr_t.device)
+
+
+class _IncidenceSoftmax(torch.autograd.Function):
+    """alpha = softmax over each group of leaky_relu(sv[u] + se[e]) and its exact gradients for both score vectors:
+    ds = alpha (dalpha - sum_g alpha dalpha) leaky', dsv / dse = its sums over each vertex's / hyperedge's incidences."""
+
+    @staticmethod
+    def forward(ctx, csrptr_t, indices_t, sv, se, N, group, slope):
+        plan = cached_plan(N, csrptr_t, indices_t)
+        alpha = plan.incidence_attention(csrptr_t, indices_t, sv, se, group, slope)
+        ctx.save_for_backward(csrptr_t, indices_t, sv, se, alpha)
+        ctx.N, ctx.group, ctx.slope = N, group, slope
+        return alpha
+
+    @staticmethod
+    def backward(ctx, dalpha):
+        csrptr_t, indices_t, sv, se, alpha = ctx.saved_tensors
+        plan = cached_plan(ctx.N, csrptr_t, indices_t)
+        need_sv = sv is not None and ctx.needs_input_grad[2]
+        need_se = se is not None and ctx.needs_input_grad[3]
+        _, dsv, dse = plan.incidence_attention_backward(csrptr_t, indices_t, alpha, dalpha.contiguous(), sv, se, ctx.group,
+                                                        ctx.slope, need_sv=need_sv, need_se=need_se)
+        return None, None, dsv, dse, None, None, None
+
+
+def incidence_softmax(csrptr_t, indices_t, node_score=None, edge_score=None, group="hyperedge", negative_slope=0.2,
+                      options=None, num_nodes=None):
+    """Hypergraph attention's coefficients, alpha [nnz] aligned with indices_t: for every incidence p = (e, u)
+    alpha[p] = softmax over p's group of leaky_relu(node_score[u] + edge_score[e], negative_slope); the group is p's
+    hyperedge (group='hyperedge': the coefficients of a hyperedge's members sum to 1) or p's vertex (group='vertex').
+    node_score [N] / edge_score [M]: float32, either may be None (0).  The result is what incidence_aggr takes as
+    v2e_weight / e2v_weight.  Gradients are exact for both score vectors.  num_nodes: N; required when node_score is
+    None, otherwise optional (node_score's length is taken as N; given, node_score must have that length).  Options.variant 'auto' and 'pull' run; the others raise ValueError.  float32 only (TypeError for bfloat16)."""
+    opt = _opt(options)
+    sv, se = (_flat(t) if isinstance(t, torch.Tensor) else t for t in (node_score, edge_score))
+    if sv is None and num_nodes is None:
+        raise ValueError("incidence_softmax needs node_score or num_nodes (the number of vertices)")
+    N = int(num_nodes) if num_nodes is not None else sv.numel()
+    M = csrptr_t.numel() - 1 if isinstance(csrptr_t, torch.Tensor) else 0
+    _segment_args("incidence_softmax", csrptr_t, indices_t, (("node_score", sv), ("edge_score", se)), (N, M), group, opt)
+    slope = float(negative_slope)
+    if not (torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (sv, se))):
+        return cached_plan(N, csrptr_t, indices_t).incidence_attention(csrptr_t, indices_t, sv, se, group, slope)
+    return _IncidenceSoftmax.apply(csrptr_t, indices_t, sv, se, N, group, slope)
+
+
+class _IncidenceSum(torch.autograd.Function):
+    """out[g] = sum of val over group g; the backward is the gather dout[group(p)] on the plan's cached segment ids."""
+
+    @staticmethod
+    def forward(ctx, csrptr_t, indices_t, val, N, side):
+        plan = cached_plan(N, csrptr_t, indices_t)
+        ctx.save_for_backward(csrptr_t, indices_t)
+        ctx.N, ctx.side = N, side
+        return plan.incidence_sum(csrptr_t, indices_t, val, side)
+
+    @staticmethod
+    def backward(ctx, dout):
+        csrptr_t, indices_t = ctx.saved_tensors
+        plan = cached_plan(ctx.N, csrptr_t, indices_t)
+        return None, None, dout[plan.segment_ids(csrptr_t, indices_t, ctx.side)], None, None
+
+
+def incidence_sum(csrptr_t, indices_t, val, side="hyperedge", num_nodes=None):
+    """Segment sums of a value per incidence (float32 [nnz], aligned with indices_t): out[e] = sum over hyperedge e's
+    members (side='hyperedge', [M]) or out[v] = sum over vertex v's hyperedges (side='vertex', [N]) -- e.g. the weighted
+    degrees of a probabilistic H.  Deterministic, no atomics (hg_incidence_sum_f32); differentiable in val.  num_nodes: N;
+    without it N is taken as the largest member id + 1 (read back from the device on every call, and vertices beyond it,
+    which are in no hyperedge, get no row) -- pass it."""
+    v = _flat(val) if isinstance(val, torch.Tensor) else val
+    nnz = indices_t.numel() if isinstance(indices_t, torch.Tensor) else 0
+    _segment_args("incidence_sum", csrptr_t, indices_t, (("val", v),), (nnz,), side, None)
+    if v is None:
+        raise TypeError("val must be a float32 tensor")
+    N = int(num_nodes) if num_nodes is not None else (int(indices_t.max()) + 1 if nnz else 0)
+    if not (torch.is_grad_enabled() and v.requires_grad):
+        return cached_plan(N, csrptr_t, indices_t).incidence_sum(csrptr_t, indices_t, v, side)
+    return _IncidenceSum.apply(csrptr_t, indices_t, v, N, side)
+
+
 # ---- module `hgnnaggr` (hgnnaggr.cc:122-151) ---------------------------------
 
 def hgnnaggr(balan_key, balan_row, group_st, group_ed, csrptr_t, indices_t, node_feat, degE, degV, W, options=None):

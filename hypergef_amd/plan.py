@@ -469,6 +469,114 @@ class Plan:
                                                        _ptr(B), _ptr(out), _stream_handle(A.device)))
         return out
 
+    def segment_info(self, side):
+        """How the segment kernels cut one side ('hyperedge' / 'vertex', or 0 / 1): {"width": lanes per group, "keep":
+        entries a lane keeps in registers, "long": the longest row a lane group takes, "long_rows": int32 ids of the
+        longer rows, which get a workgroup each} (hg_plan_get_segment_info).  Works on host-only plans."""
+        side = _side(side)
+        info = (ctypes.c_int32 * 4)()
+        _lib.check(_lib.lib().hg_plan_get_segment_info(self._h, side, info, None))
+        rows = np.empty(info[3], np.int32)
+        _lib.check(_lib.lib().hg_plan_get_segment_info(self._h, side, info, rows.ctypes.data_as(ctypes.c_void_p)))
+        return {"width": info[0], "keep": info[1], "long": info[2], "long_rows": rows}
+
+    def _scores(self, sv, se, device=None):
+        for name, t, n in (("node_score", sv, self.N), ("edge_score", se, self.M)):
+            if t is not None:
+                _check_feat(t, name, device=device)
+                device = t.device
+                if t.numel() != n:
+                    raise ValueError("%s must have %d elements, got %d" % (name, n, t.numel()))
+        return device
+
+    def incidence_attention(self, csrptr_t, colind_t, sv=None, se=None, group="hyperedge", slope=0.2, out=None):
+        """alpha [nnz] in H_T order: the softmax over each hyperedge's members (group 'hyperedge') or each vertex's
+        hyperedges ('vertex') of leaky_relu(sv[u] + se[e], slope) (hg_incidence_attention_f32).  sv [N], se [M]: float32,
+        or None (0).  The first call of a form builds and uploads what it needs from the plan: not capturable."""
+        group = _side(group)
+        _check_index(csrptr_t, "csrptr_t")
+        _check_index(colind_t, "indices_t")
+        device = self._scores(sv, se, csrptr_t.device)
+        if out is None:
+            out = torch.empty(self.nnz, dtype=torch.float32, device=device)
+        else:
+            _check_feat(out, "out", device=device)
+            if out.numel() != self.nnz:
+                raise ValueError("out must have nnz = %d elements" % self.nnz)
+        with torch.cuda.device(device):
+            _lib.check(_lib.lib().hg_incidence_attention_f32(self._h, group, _ptr(csrptr_t), _ptr(colind_t), _ptr(sv),
+                                                             _ptr(se), float(slope), _ptr(out), _stream_handle(device)))
+        return out
+
+    def incidence_attention_backward(self, csrptr_t, colind_t, alpha, dalpha, sv=None, se=None, group="hyperedge",
+                                     slope=0.2, need_sv=True, need_se=True):
+        """(ds [nnz], dsv [N] or None, dse [M] or None) for alpha = incidence_attention(...) and its gradient dalpha
+        (hg_incidence_attention_bwd_f32); sv / se as in the forward (they decide the leaky branch)."""
+        group = _side(group)
+        _check_index(csrptr_t, "csrptr_t")
+        _check_index(colind_t, "indices_t")
+        _check_feat(alpha, "alpha")
+        _check_feat(dalpha, "dalpha", device=alpha.device)
+        for name, t in (("alpha", alpha), ("dalpha", dalpha)):
+            if t.numel() != self.nnz:
+                raise ValueError("%s must have nnz = %d elements, got %d" % (name, self.nnz, t.numel()))
+        device = self._scores(sv, se, alpha.device)
+        ds = torch.empty(self.nnz, dtype=torch.float32, device=device)
+        dsv = torch.empty(self.N, dtype=torch.float32, device=device) if need_sv else None
+        dse = torch.empty(self.M, dtype=torch.float32, device=device) if need_se else None
+        with torch.cuda.device(device):
+            _lib.check(_lib.lib().hg_incidence_attention_bwd_f32(
+                self._h, group, _ptr(csrptr_t), _ptr(colind_t), _ptr(sv), _ptr(se), float(slope), _ptr(alpha),
+                _ptr(dalpha), _ptr(ds), _ptr(dsv), _ptr(dse), _stream_handle(device)))
+        return ds, dsv, dse
+
+    def incidence_sum(self, csrptr_t, colind_t, val, side="hyperedge", out=None):
+        """out[e] = sum of val over hyperedge e's incidences (side 'hyperedge', [M]) or out[v] = sum over vertex v's
+        (side 'vertex', [N]); val float32 [nnz] in H_T order (hg_incidence_sum_f32).  Deterministic, no atomics."""
+        side = _side(side)
+        _check_index(csrptr_t, "csrptr_t")
+        _check_index(colind_t, "indices_t")
+        _check_feat(val, "val", device=csrptr_t.device)
+        if val.numel() != self.nnz:
+            raise ValueError("val must have nnz = %d elements, got %d" % (self.nnz, val.numel()))
+        n = self.M if side == 0 else self.N
+        if out is None:
+            out = torch.empty(n, dtype=torch.float32, device=val.device)
+        else:
+            _check_feat(out, "out", device=val.device)
+            if out.numel() != n:
+                raise ValueError("out must have %d elements" % n)
+        with torch.cuda.device(val.device):
+            _lib.check(_lib.lib().hg_incidence_sum_f32(self._h, side, _ptr(csrptr_t), _ptr(colind_t), _ptr(val), _ptr(out),
+                                                       _stream_handle(val.device)))
+        return out
+
+    def segment_ids(self, csrptr_t, colind_t, side):
+        """int64 [nnz] device tensor: the hyperedge (side 'hyperedge') or vertex ('vertex') of every H_T entry -- the gather
+        index of incidence_sum's backward.  Built once per side and kept with the plan."""
+        side = _side(side)
+        cache = self.__dict__.setdefault("_seg_ids", {})
+        ids = cache.get(side)
+        if ids is None:
+            if side == 0:
+                sizes = (csrptr_t[1:] - csrptr_t[:-1]).long()
+                ids = torch.repeat_interleave(torch.arange(self.M, device=csrptr_t.device), sizes, output_size=self.nnz)
+            else:
+                ids = colind_t.long()
+            cache[side] = ids
+        return ids
+
+
+SIDES = {"hyperedge": 0, "vertex": 1}
+
+
+def _side(side):
+    if side in (0, 1):
+        return int(side)
+    if side not in SIDES:
+        raise ValueError("group / side must be 'hyperedge' or 'vertex', got %r" % (side,))
+    return SIDES[side]
+
 
 def linear_supported(F_in, F_out):
     """Widths hg_aggr_linear_f32 takes (MFMA tiles: K in {32, 64, 128}, 16-column output tiles)."""

@@ -410,6 +410,45 @@ HG_API int hg_incidence_dot_f32(const hg_plan *plan, int32_t F, const int32_t *c
                                 const float *A, const float *B, float *out, hg_stream_t stream);
 HG_API int hg_plan_get_incidence_perm(const hg_plan *plan, int32_t *perm_host);
 
+/* ---- hypergraph attention coefficients ------------------------------------------------------------------------------
+ * The weights hg_aggr_incidence_f32 takes, computed where they are used: a score per incidence, normalised by a softmax
+ * over each hyperedge's members or over each vertex's hyperedges.  Single head, fp32.  For every H_T entry p = (e, u):
+ *     raw[p]   = sv[u] + se[e]                              sv: [N] or NULL (0), se: [M] or NULL (0)
+ *     s[p]     = raw[p] > 0 ? raw[p] : slope * raw[p]       (leaky relu; slope = 1: the identity)
+ *     alpha[p] = exp(s[p] - m_g) / sum_{q in g} exp(s[q] - m_g),   m_g = max_{q in g} s[q]
+ *   group = 0: g is the hyperedge of p (a row of H_T); group = 1: g is the vertex of p (a row of H, reached through the
+ *   plan's permutation).  alpha_out: [nnz] in H_T order, ready to be passed as v2e_val / e2v_val.  Positions exist only
+ *   inside non-empty groups, so an empty group writes nothing; a group of one entry gives exactly 1.0f; the maximum is
+ *   subtracted before the exponential, so finite scores of any magnitude give finite coefficients.
+ * hg_incidence_attention_bwd_f32: given alpha (the forward's output) and dalpha, both [nnz] in H_T order,
+ *     t_g = sum_{q in g} alpha[q] * dalpha[q],   ds[p] = alpha[p] * (dalpha[p] - t_g) * (raw[p] > 0 ? 1 : slope)
+ *   ds_out: [nnz], H_T order, required (the sums below are formed from it).  dsv_out: [N] or NULL, dsv[v] = sum of ds
+ *   over v's incidences; dse_out: [M] or NULL, dse[e] = sum of ds over e's members.  Both are fully overwritten (0 for a
+ *   vertex in no hyperedge / an empty hyperedge).  sv / se are read only when slope != 1.
+ * hg_incidence_sum_f32: the segment sum alone, out[e] = sum_{p in H_T row e} val[p] (side = 0, out [M]) or
+ *   out[v] = sum over the H_T positions p of vertex v of val[p] (side = 1, out [N]); val [nnz] in H_T order.  The
+ *   weighted degrees d(v) = sum_e w(e) h(v, e), delta(e) = sum_v h(v, e) of a probabilistic H are such sums.
+ * All three: no atomics; every group is reduced by one lane group (or, above 128 entries, one workgroup) in an order that
+ *   depends on the plan alone, so two calls give the same bits.  csrptr_t / colind_t must be the arrays the plan was built
+ *   from.  The first call that needs the permutation (group / side = 1, or a gradient for the other end of the group) or
+ *   a side's list of long rows builds and uploads it: that call allocates, so it cannot be captured into a hipGraph --
+ *   make one call of the same form before capturing, as for hg_aggr_incidence_f32.  Later calls only enqueue.
+ *   HG_ERR_UNSUPPORTED on a plan built with HG_PLAN_HOST_ONLY; HG_ERR_INVALID (message through hg_last_error, nothing
+ *   launched) for a null plan or array, a group / side other than 0 / 1, a non-finite slope.
+ * hg_plan_get_segment_info: how the segment kernels cut one side (tests, tools; host-only plans too): info[4] = {lanes per
+ *   group, entries a lane keeps in registers, longest row a lane group takes, rows longer than that}; long_seg_host
+ *   (NULL, or room for info[3] ids from a first call) receives those rows, ascending.
+ * Detect these entries by their exported symbols (HG_AGGR_VERSION does not change). */
+HG_API int hg_incidence_attention_f32(const hg_plan *plan, int32_t group, const int32_t *csrptr_t, const int32_t *colind_t,
+                                      const float *sv, const float *se, float slope, float *alpha_out, hg_stream_t stream);
+HG_API int hg_incidence_attention_bwd_f32(const hg_plan *plan, int32_t group, const int32_t *csrptr_t,
+                                          const int32_t *colind_t, const float *sv, const float *se, float slope,
+                                          const float *alpha, const float *dalpha, float *ds_out, float *dsv_out,
+                                          float *dse_out, hg_stream_t stream);
+HG_API int hg_incidence_sum_f32(const hg_plan *plan, int32_t side, const int32_t *csrptr_t, const int32_t *colind_t,
+                                const float *val, float *out, hg_stream_t stream);
+HG_API int hg_plan_get_segment_info(const hg_plan *plan, int32_t side, int32_t *info, int32_t *long_seg_host);
+
 /* first_aggr = "max" pieces (hgnnaggr_max, source/hgnnaggr/hgnnaggr_cuda.cu:144-208).
  * hg_gather_max_f32: Xe[e,k] = (max_{u in e} X[u,k], start -1e5, strict >) * (degE[e]*W[e]),
  * record[e,k] = winning vertex (0 if none).  The second hop is hg_gather_rows_f32(hop = 1).
