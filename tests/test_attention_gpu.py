@@ -41,69 +41,20 @@ from hypergef_amd import synth  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda:0"
-U = 2.0 ** -24
-SENTINEL = -12345.0
-SLOPES = (0.2, 1.0)
-MODES = ("both", "sv", "se")
-
-
-def _thresholds():
-    from hypergef_amd.plan import Plan, make_opts
-    inc = ar.toy()
-    info = Plan.from_host(inc.N, inc.M, inc.csrptr, inc.colind, opts=make_opts(host_only=True)).segment_info(0)
-    return [w * info["keep"] for w in (4, 8, 16)] + [info["long"], 256 * info["keep"]]
-
-
-def _boundaries():
-    sizes = sorted(set(list(range(0, 71)) + [255, 256, 257, 1023, 1024, 1025, 5000]
-                       + [t + d for t in _thresholds() for d in (-1, 0, 1)]))
-    return synth._from_sizes(np.random.default_rng(7), 6000, sizes, name="boundaries")
-
+DEV = ar.DEV
+U = ar.U
+SENTINEL = ar.SENTINEL
+SLOPES = ar.SLOPES
+MODES = ar.MODES
 
 SHAPES = {
     "toy": ar.toy,
     "ragged": lambda: synth.random_incidence(3000, 2000, 6.0, seed=4, empty_frac=0.1),
     "cora": synth.cora_shape,
-    "boundaries": _boundaries,
-    "boundaries_T": lambda: ar.transpose(_boundaries()),
+    "boundaries": ar.boundaries,
+    "boundaries_T": lambda: ar.transpose(ar.boundaries()),
     "powerlaw": lambda: synth.powerlaw(50_000, 200_000),
 }
-
-
-class _Case:
-    def __init__(self, hg, name):
-        from hypergef_amd.plan import Plan
-        self.name = name
-        self.inc = inc = SHAPES[name]()
-        self.h = hg.HyperGraph.from_incidence(inc, DEV, data_name=name, ngs=1 << 30)
-        self.ptr, self.ind = self.h.H_T_csrptr, self.h.H_T_colind
-        self.plan = Plan.from_tensors(inc.N, self.ptr, self.ind)
-        self.graph = gr.Graph(inc)
-        g = torch.Generator().manual_seed(21)
-        sv, se = torch.randn(inc.N, generator=g), torch.randn(inc.M, generator=g)
-        self.sv = (sv * (4.0 / float(sv.abs().max()))).to(DEV)  # max |raw| <= 8
-        self.se = (se * (4.0 / float(se.abs().max()))).to(DEV)
-        self.dalpha = torch.randn(inc.nnz, generator=g).to(DEV)
-        self.val = torch.randn(inc.nnz, generator=g).to(DEV)
-        self.L = {grp: ar.longest(inc, grp) for grp in ar.GROUPS}
-        self._ref = {}
-
-    def scores(self, mode):
-        return (self.sv if mode != "se" else None), (self.se if mode != "sv" else None)
-
-    def ref(self, mode, group, slope):
-        """(alpha, Smax) in float64 from the fp32 scores: computed once, shared by the tests, never modified."""
-        key = (mode, group, slope)
-        if key not in self._ref:
-            sv, se = (gr.f64(t) for t in self.scores(mode))
-            raw = ar.raw_score(self.graph, sv, se)
-            self._ref[key] = (ar.softmax(self.graph, sv, se, group, slope), float(raw.abs().max()) if raw.numel() else 0.0)
-        return self._ref[key]
-
-    def c(self, mode, group, slope):
-        return (self.L[group] + 16 + 16 * self.ref(mode, group, slope)[1]) * U
-
 
 _CASES = {}
 
@@ -114,18 +65,16 @@ def case(hg):
         if name not in _CASES:
             _CASES.clear()  # one shape at a time on the device
             torch.cuda.empty_cache()
-            _CASES[name] = _Case(hg, name)
+            _CASES[name] = ar.Case(hg, SHAPES[name](), name)
         return _CASES[name]
     return get
 
 
-def _bits(t):
-    return t.contiguous().view(torch.int32)
+_bits = ar.bits
 
 
 def _sizes(c, group):
-    idx, n = ar.index_of(c.graph, group)
-    return idx, torch.bincount(idx, minlength=n)
+    return c.sizes(group)
 
 
 CELLS = [(s, g) for s in SHAPES for g in ar.GROUPS]

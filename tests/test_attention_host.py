@@ -108,6 +108,42 @@ def test_segment_info_on_host_only_plans(hg):
             np.testing.assert_array_equal(again["long_rows"], info["long_rows"])
 
 
+def test_width_steered_shapes_land_in_their_bands(hg):
+    """The shapes of test_attention_widths.py, on host-only plans: the designed side of widths_W / its transpose runs at
+    lane-group width W and holds every threshold +-1, 0, 1 and 5000; a change of seg_width or of the constants that moves
+    a shape out of its band fails here, without a device."""
+    from hypergef_amd.plan import Plan, make_opts
+
+    def host_plan(inc):
+        return Plan.from_host(inc.N, inc.M, inc.csrptr, inc.colind, opts=make_opts(host_only=True))
+    for width, mean in ((4, 2.85), (8, 6.75), (16, 12.61)):
+        inc = ar.width_shape(width)
+        assert inc.M == 3081 and inc.nnz <= 48_000
+        for shape, side in ((inc, "hyperedge"), (ar.transpose(inc), "vertex")):
+            info = host_plan(shape).segment_info(side)
+            lens = ar.side_lengths(shape, side)
+            walked = lens[(lens > 0) & (lens <= info["long"])]
+            assert abs(walked.mean() - mean) < 0.005, (shape.name, side, walked.mean())
+            assert info["width"] == width, (shape.name, side, info)
+            assert ar.reaches_every_path(info, lens) is None, (shape.name, side, ar.reaches_every_path(info, lens))
+            assert lens.size % (256 // width) != 0  # the last workgroup has lane groups without a segment
+            np.testing.assert_array_equal(info["long_rows"], np.nonzero(lens > info["long"])[0])
+            other = ar.GROUPS[1 - ar.GROUPS.index(side)]
+            info = host_plan(shape).segment_info(other)  # the other side: short rows, kept entries only
+            assert info["width"] in (4, 8) and ar.longest(shape, other) < info["width"] * info["keep"]
+    dup = ar.with_duplicates(ar.width_shape(4))
+    assert host_plan(dup).segment_info("hyperedge")["width"] == 4 and dup.nnz > 1.02 * ar.width_shape(4).nnz
+    # every non-empty row is long: the mean of the rows a lane group walks is 0, the width 4
+    inc = synth._from_sizes(np.random.default_rng(5), 1100, [129, 0, 300, 1024], name="all_long")
+    info = host_plan(inc).segment_info("hyperedge")
+    assert info["width"] == 4
+    np.testing.assert_array_equal(info["long_rows"], [0, 2, 3])
+    empty = synth.Incidence(7, 5, np.zeros(6, np.int32), np.zeros(0, np.int32), name="no_entries")
+    for side in ar.GROUPS:
+        info = host_plan(empty).segment_info(side)
+        assert info["width"] == 4 and info["long_rows"].size == 0
+
+
 def test_host_only_plans_are_refused_by_the_device_entries(hg):
     from hypergef_amd import _lib
     from hypergef_amd.plan import Plan, make_opts
