@@ -38,6 +38,8 @@ SYMBOLS = (
     "hg_scatter_record_f32",
     "hg_aggr_incidence_workspace_bytes", "hg_aggr_incidence_f32", "hg_incidence_dot_f32", "hg_plan_get_incidence_perm",
     "hg_incidence_attention_f32", "hg_incidence_attention_bwd_f32", "hg_incidence_sum_f32", "hg_plan_get_segment_info",
+    "hg_incidence_attention_heads_f32", "hg_incidence_attention_heads_bwd_f32", "hg_incidence_sum_heads_f32",
+    "hg_aggr_incidence_heads_f32", "hg_incidence_dot_heads_f32",
 )
 
 
@@ -193,6 +195,18 @@ def lib():
         L.hg_incidence_sum_f32.argtypes = [vp, i32, vp, vp, vp, vp, vp]
         L.hg_plan_get_segment_info.restype = ctypes.c_int
         L.hg_plan_get_segment_info.argtypes = [vp, i32, vp, vp]
+    if hasattr(L, "hg_aggr_incidence_heads_f32"):  # likewise: the same entries with an int32 heads argument
+        L.hg_incidence_attention_heads_f32.restype = ctypes.c_int
+        L.hg_incidence_attention_heads_f32.argtypes = [vp, i32, i32, vp, vp, vp, vp, ctypes.c_float, vp, vp]
+        L.hg_incidence_attention_heads_bwd_f32.restype = ctypes.c_int
+        L.hg_incidence_attention_heads_bwd_f32.argtypes = [vp, i32, i32, vp, vp, vp, vp, ctypes.c_float, vp, vp, vp, vp,
+                                                           vp, vp]
+        L.hg_incidence_sum_heads_f32.restype = ctypes.c_int
+        L.hg_incidence_sum_heads_f32.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp]
+        L.hg_aggr_incidence_heads_f32.restype = ctypes.c_int
+        L.hg_aggr_incidence_heads_f32.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]
+        L.hg_incidence_dot_heads_f32.restype = ctypes.c_int
+        L.hg_incidence_dot_heads_f32.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, vp]
     L.hg_aggr_push_groups_f32.restype = ctypes.c_int
     L.hg_aggr_push_groups_f32.argtypes = [i32, i32, i32, i64, vp, vp, vp, vp, vp, vp,
                                           vp, vp, vp, vp, vp, vp]

@@ -429,8 +429,10 @@ int run_sched(const hg_plan *p, const hg::Sched &s, int32_t F, const int32_t *pt
               const int32_t *ind, const void *src, const float *scaleA, const float *scaleB,
               const int32_t *scale_map, const int32_t *dst_map, void *dst, float *partial,
               hipStream_t stream, bool nt_dst = false, bool src_bf16 = false, bool dst_bf16 = false,
-              const float *w = nullptr, const int32_t *wperm = nullptr) {
-  hg::WeightedGatherArgs a;
+              const float *w = nullptr, const int32_t *wperm = nullptr, int32_t heads = 1) {
+  hg::HeadsGatherArgs a;  // heads > 1: w is [nnz, heads] (hg_aggr_incidence_heads_f32)
+  a.heads = heads;
+  a.C = F / heads;
   a.nt_dst = nt_dst ? 1 : 0;
   a.w = w;  // per-entry weights (hg_aggr_incidence_f32): the weighted kernel instances
   a.wperm = wperm;
@@ -457,8 +459,10 @@ int run_sched(const hg_plan *p, const hg::Sched &s, int32_t F, const int32_t *pt
     hg::set_error("weighted row gather: fp32 rows only");
     return HG_ERR_UNSUPPORTED;
   }
-  hipError_t e = w ? hg::launch_gather_weighted(a, (int)s.fixups.size(), s.n_fix_l1, s.d_fixups, vec4, stream)
-                   : hg::launch_gather(a, (int)s.fixups.size(), s.n_fix_l1, s.d_fixups, vec4, stream, src_bf16, dst_bf16);
+  hipError_t e = (w && heads > 1)
+                     ? hg::launch_gather_heads(a, (int)s.fixups.size(), s.n_fix_l1, s.d_fixups, vec4, vec4 && a.C % 4 == 0, stream)
+                 : w ? hg::launch_gather_weighted(a, (int)s.fixups.size(), s.n_fix_l1, s.d_fixups, vec4, stream)
+                     : hg::launch_gather(a, (int)s.fixups.size(), s.n_fix_l1, s.d_fixups, vec4, stream, src_bf16, dst_bf16);
   if (e != hipSuccess) return hip_fail("gather_rows launch", e);
   return HG_OK;
 }
@@ -583,7 +587,7 @@ int check_segment_call(const char *who, const hg_plan *plan, int side, const int
 
 // One launch of the segment kernels on `side`: fills the side's arrays of `a` (scores: sv [N], se [M]) and runs `body`.
 int run_segments(const char *who, const hg_plan *plan, int body, int side, const int32_t *csrptr_t, const int32_t *colind_t,
-                 const float *sv, const float *se, hg::SegArgs a, hipStream_t stream) {
+                 const float *sv, const float *se, hg::SegArgs a, hipStream_t stream, int32_t heads = 1) {
   int rc;
   const int32_t *perm = nullptr;
   if (side == 1 && (rc = get_incidence_perm(plan, true, &perm)) != HG_OK) return rc;
@@ -595,8 +599,43 @@ int run_segments(const char *who, const hg_plan *plan, int body, int side, const
   a.nseg = side == 0 ? plan->M : plan->N;
   a.own = side == 0 ? se : sv;
   a.other = side == 0 ? sv : se;
-  hipError_t e = hg::launch_segments(body, side, width, a, stream);
+  hipError_t e;
+  if (heads > 1) {  // scores [*, heads], entry arrays [nnz, heads]
+    hg::SegHeadsArgs ah;
+    static_cast<hg::SegArgs &>(ah) = a;
+    ah.heads = heads;
+    e = hg::launch_segments_heads(body, side, width, ah, stream);
+  } else {
+    e = hg::launch_segments(body, side, width, a, stream);
+  }
   if (e != hipSuccess) return hip_fail(who, e);
+  return HG_OK;
+}
+
+// Refusals the *_heads_f32 entries decide before the single-head rules: a null or host-only plan, heads < 1, and a
+// feature width (F > 0 where the entry has one) that the heads do not divide.
+int check_heads(const char *who, const hg_plan *plan, int32_t heads, int32_t F) {
+  if (!plan) {
+    hg::set_error(std::string(who) + ": null plan");
+    return HG_ERR_INVALID;
+  }
+  if (heads < 1) {
+    hg::set_error(std::string(who) + ": heads must be at least 1");
+    return HG_ERR_INVALID;
+  }
+  if (F > 0 && F % heads != 0) {
+    hg::set_error(std::string(who) + ": the feature width " + std::to_string(F) + " is no multiple of heads = " +
+                  std::to_string(heads));
+    return HG_ERR_INVALID;
+  }
+  if (plan->opts.flags & HG_PLAN_HOST_ONLY) {
+    hg::set_error(std::string(who) + ": plan was built with HG_PLAN_HOST_ONLY and holds no device arrays");
+    return HG_ERR_UNSUPPORTED;
+  }
+  if (heads > 1 && (int64_t)std::max<int64_t>(plan->nnz, std::max(plan->N, plan->M)) * heads >= ((int64_t)1 << 40)) {
+    hg::set_error(std::string(who) + ": nnz * heads too large");
+    return HG_ERR_INVALID;
+  }
   return HG_OK;
 }
 
@@ -1589,12 +1628,36 @@ int hg_aggr_linear_f32(const hg_plan *plan, int32_t F_in, int32_t F_out, const i
 
 // ---- incidence-weighted aggregation ---------------------------------------------------------------------------------
 
+static int aggr_incidence(const hg_plan *plan, int32_t F, int32_t heads, const int32_t *csrptr_t, const int32_t *colind_t,
+                          const float *X, const float *v2e_val, const float *e2v_val, const float *degE,
+                          const float *degV, const float *W, float *Xe_out, float *Y, void *workspace,
+                          size_t workspace_bytes, hg_stream_t stream);
+
 size_t hg_aggr_incidence_workspace_bytes(const hg_plan *p, int32_t F) {
   if (!p || F <= 0) return 0;
   return carve(p, F).total;  // the pull layout: [Xe][partial rows of hop 1][partial rows of hop 2]
 }
 
 int hg_aggr_incidence_f32(const hg_plan *plan, int32_t F, const int32_t *csrptr_t, const int32_t *colind_t,
+                          const float *X, const float *v2e_val, const float *e2v_val, const float *degE,
+                          const float *degV, const float *W, float *Xe_out, float *Y, void *workspace,
+                          size_t workspace_bytes, hg_stream_t stream) {
+  return aggr_incidence(plan, F, 1, csrptr_t, colind_t, X, v2e_val, e2v_val, degE, degV, W, Xe_out, Y, workspace,
+                        workspace_bytes, stream);
+}
+
+int hg_aggr_incidence_heads_f32(const hg_plan *plan, int32_t F, int32_t heads, const int32_t *csrptr_t,
+                                const int32_t *colind_t, const float *X, const float *v2e_val, const float *e2v_val,
+                                const float *degE, const float *degV, const float *W, float *Xe_out, float *Y,
+                                void *workspace, size_t workspace_bytes, hg_stream_t stream) {
+  int rc = check_heads("hg_aggr_incidence_heads_f32", plan, heads, F);
+  if (rc != HG_OK) return rc;
+  return aggr_incidence(plan, F, heads, csrptr_t, colind_t, X, v2e_val, e2v_val, degE, degV, W, Xe_out, Y, workspace,
+                        workspace_bytes, stream);
+}
+
+// heads == 1: hg_aggr_incidence_f32 as it always was; heads > 1: v2e_val / e2v_val are [nnz, heads]
+static int aggr_incidence(const hg_plan *plan, int32_t F, int32_t heads, const int32_t *csrptr_t, const int32_t *colind_t,
                           const float *X, const float *v2e_val, const float *e2v_val, const float *degE,
                           const float *degV, const float *W, float *Xe_out, float *Y, void *workspace,
                           size_t workspace_bytes, hg_stream_t stream) {
@@ -1634,11 +1697,11 @@ int hg_aggr_incidence_f32(const hg_plan *plan, int32_t F, const int32_t *csrptr_
   const bool nt1 = rows_whole_64(Y, F);
   // hop 1: Xe[e] = ((sum_{p=(e,u)} v2e[p] X[u]) * degE[e]) * W[e]
   rc = run_sched(plan, s0, F, csrptr_t, colind_t, X, degE, W, nullptr, nullptr, Xe,
-                 reinterpret_cast<float *>(ws + c.part[0]), s, nt0, false, false, v2e_val, nullptr);
+                 reinterpret_cast<float *>(ws + c.part[0]), s, nt0, false, false, v2e_val, nullptr, heads);
   if (rc != HG_OK) return rc;
   // hop 2: Y[v] = (sum_{q=(v,e)} e2v[perm[q]] Xe[e]) * degV[v]
   return run_sched(plan, s1, F, plan->d_ptr_v, plan->d_ind_v, Xe, degV, nullptr, nullptr, nullptr, Y,
-                   reinterpret_cast<float *>(ws + c.part[1]), s, nt1, false, false, e2v_val, perm);
+                   reinterpret_cast<float *>(ws + c.part[1]), s, nt1, false, false, e2v_val, perm, heads);
 }
 
 int hg_incidence_dot_f32(const hg_plan *plan, int32_t F, const int32_t *csrptr_t, const int32_t *colind_t,
@@ -1653,6 +1716,24 @@ int hg_incidence_dot_f32(const hg_plan *plan, int32_t F, const int32_t *csrptr_t
   hipError_t e = hg::launch_incidence_dot(plan->M, plan->nnz, F, csrptr_t, colind_t, A, B, out, vec4,
                                           static_cast<hipStream_t>(stream));
   if (e != hipSuccess) return hip_fail("incidence_dot launch", e);
+  return HG_OK;
+}
+
+int hg_incidence_dot_heads_f32(const hg_plan *plan, int32_t F, int32_t heads, const int32_t *csrptr_t,
+                               const int32_t *colind_t, const float *A, const float *B, float *out, hg_stream_t stream) {
+  int rc = check_heads("hg_incidence_dot_heads_f32", plan, heads, F);
+  if (rc != HG_OK) return rc;
+  if (heads == 1) return hg_incidence_dot_f32(plan, F, csrptr_t, colind_t, A, B, out, stream);
+  if ((rc = check_call(plan, F, nullptr, 0, kSizeLater)) != HG_OK) return rc;
+  if (plan->nnz > 0 && (!csrptr_t || !colind_t || !A || !B || !out)) {
+    hg::set_error("hg_incidence_dot_heads_f32: null array");
+    return HG_ERR_INVALID;
+  }
+  const int32_t C = F / heads;
+  const bool lane4 = C % 4 == 0 && aligned16(A) && aligned16(B);  // a 16-byte lane must lie inside one head
+  hipError_t e = hg::launch_incidence_dot_heads(plan->M, plan->nnz, heads, C, csrptr_t, colind_t, A, B, out, lane4,
+                                                static_cast<hipStream_t>(stream));
+  if (e != hipSuccess) return hip_fail("incidence_dot_heads launch", e);
   return HG_OK;
 }
 
@@ -1671,7 +1752,16 @@ int hg_plan_get_incidence_perm(const hg_plan *plan, int32_t *perm_host) {
 
 int hg_incidence_attention_f32(const hg_plan *plan, int32_t group, const int32_t *csrptr_t, const int32_t *colind_t,
                                const float *sv, const float *se, float slope, float *alpha_out, hg_stream_t stream) {
-  int rc = check_segment_call("hg_incidence_attention_f32", plan, group, csrptr_t, colind_t);
+  return hg_incidence_attention_heads_f32(plan, group, 1, csrptr_t, colind_t, sv, se, slope, alpha_out, stream);
+}
+
+// heads == 1 runs exactly what hg_incidence_attention_f32 always ran (run_segments launches the single-head kernels)
+int hg_incidence_attention_heads_f32(const hg_plan *plan, int32_t group, int32_t heads, const int32_t *csrptr_t,
+                                     const int32_t *colind_t, const float *sv, const float *se, float slope,
+                                     float *alpha_out, hg_stream_t stream) {
+  int rc = check_heads("hg_incidence_attention_f32", plan, heads, 0);
+  if (rc != HG_OK) return rc;
+  rc = check_segment_call("hg_incidence_attention_f32", plan, group, csrptr_t, colind_t);
   if (rc != HG_OK) return rc;
   if ((plan->nnz > 0 && !alpha_out) || !(slope == slope) || slope - slope != 0.f) {
     hg::set_error("hg_incidence_attention_f32: null alpha_out or non-finite slope");
@@ -1682,13 +1772,23 @@ int hg_incidence_attention_f32(const hg_plan *plan, int32_t group, const int32_t
   a.slope = slope;
   a.out_entry = alpha_out;
   return run_segments("incidence_attention launch", plan, hg::kSegSoftmax, group, csrptr_t, colind_t, sv, se, a,
-                      static_cast<hipStream_t>(stream));
+                      static_cast<hipStream_t>(stream), heads);
 }
 
 int hg_incidence_attention_bwd_f32(const hg_plan *plan, int32_t group, const int32_t *csrptr_t, const int32_t *colind_t,
                                    const float *sv, const float *se, float slope, const float *alpha, const float *dalpha,
                                    float *ds_out, float *dsv_out, float *dse_out, hg_stream_t stream) {
-  int rc = check_segment_call("hg_incidence_attention_bwd_f32", plan, group, csrptr_t, colind_t);
+  return hg_incidence_attention_heads_bwd_f32(plan, group, 1, csrptr_t, colind_t, sv, se, slope, alpha, dalpha, ds_out,
+                                              dsv_out, dse_out, stream);
+}
+
+int hg_incidence_attention_heads_bwd_f32(const hg_plan *plan, int32_t group, int32_t heads, const int32_t *csrptr_t,
+                                         const int32_t *colind_t, const float *sv, const float *se, float slope,
+                                         const float *alpha, const float *dalpha, float *ds_out, float *dsv_out,
+                                         float *dse_out, hg_stream_t stream) {
+  int rc = check_heads("hg_incidence_attention_bwd_f32", plan, heads, 0);
+  if (rc != HG_OK) return rc;
+  rc = check_segment_call("hg_incidence_attention_bwd_f32", plan, group, csrptr_t, colind_t);
   if (rc != HG_OK) return rc;
   if ((plan->nnz > 0 && (!alpha || !dalpha || !ds_out)) || !(slope == slope) || slope - slope != 0.f) {
     hg::set_error("hg_incidence_attention_bwd_f32: null alpha / dalpha / ds_out or non-finite slope");
@@ -1701,7 +1801,8 @@ int hg_incidence_attention_bwd_f32(const hg_plan *plan, int32_t group, const int
   a.dval = dalpha;
   a.out_entry = ds_out;
   a.out_seg = group == 0 ? dse_out : dsv_out;  // the group's own end: summed by the kernel that forms ds
-  rc = run_segments("incidence_attention_bwd launch", plan, hg::kSegSoftmaxBwd, group, csrptr_t, colind_t, sv, se, a, s);
+  rc = run_segments("incidence_attention_bwd launch", plan, hg::kSegSoftmaxBwd, group, csrptr_t, colind_t, sv, se, a, s,
+                    heads);
   if (rc != HG_OK) return rc;
   float *other_out = group == 0 ? dsv_out : dse_out;  // the other end: a segment sum of ds over that side
   if (!other_out) return HG_OK;
@@ -1709,12 +1810,19 @@ int hg_incidence_attention_bwd_f32(const hg_plan *plan, int32_t group, const int
   b.val = ds_out;
   b.out_seg = other_out;
   return run_segments("incidence_attention_bwd sum launch", plan, hg::kSegSum, 1 - group, csrptr_t, colind_t, nullptr,
-                      nullptr, b, s);
+                      nullptr, b, s, heads);
 }
 
 int hg_incidence_sum_f32(const hg_plan *plan, int32_t side, const int32_t *csrptr_t, const int32_t *colind_t,
                          const float *val, float *out, hg_stream_t stream) {
-  int rc = check_segment_call("hg_incidence_sum_f32", plan, side, csrptr_t, colind_t);
+  return hg_incidence_sum_heads_f32(plan, side, 1, csrptr_t, colind_t, val, out, stream);
+}
+
+int hg_incidence_sum_heads_f32(const hg_plan *plan, int32_t side, int32_t heads, const int32_t *csrptr_t,
+                               const int32_t *colind_t, const float *val, float *out, hg_stream_t stream) {
+  int rc = check_heads("hg_incidence_sum_f32", plan, heads, 0);
+  if (rc != HG_OK) return rc;
+  rc = check_segment_call("hg_incidence_sum_f32", plan, side, csrptr_t, colind_t);
   if (rc != HG_OK) return rc;
   if ((plan->nnz > 0 && !val) || !out) {
     hg::set_error("hg_incidence_sum_f32: null array");
@@ -1724,7 +1832,7 @@ int hg_incidence_sum_f32(const hg_plan *plan, int32_t side, const int32_t *csrpt
   a.val = val;
   a.out_seg = out;
   return run_segments("incidence_sum launch", plan, hg::kSegSum, side, csrptr_t, colind_t, nullptr, nullptr, a,
-                      static_cast<hipStream_t>(stream));
+                      static_cast<hipStream_t>(stream), heads);
 }
 
 int hg_plan_get_segment_info(const hg_plan *plan, int32_t side, int32_t *info, int32_t *long_seg_host) {

@@ -29,9 +29,17 @@ struct SegArgs {
   float *out_seg;      // kSegSoftmaxBwd: the segments' own sums of ds (or null); kSegSum: out [nseg]
 };
 
+// The same arrays with `heads` columns, head fastest: own / other / out_seg [*, heads], val / dval / out_entry [nnz, heads].
+struct SegHeadsArgs : SegArgs {
+  int32_t heads;
+};
+
 // Lane-group width of a side whose segments of at most kSegLong entries hold `mean` entries on average.
 int seg_width(double mean);
 // body: kSeg*; side 0 / 1; width 4 / 8 / 16 (seg_width)
 hipError_t launch_segments(int body, int side, int width, const SegArgs &a, hipStream_t stream);
+// one lane group (or, for a long segment, one workgroup) per (segment, head): column h is reduced as launch_segments
+// reduces a single column
+hipError_t launch_segments_heads(int body, int side, int width, const SegHeadsArgs &a, hipStream_t stream);
 
 }  // namespace hg

@@ -17,9 +17,17 @@
 // No atomics.  A lane adds its entries in ascending order, the lanes of a group are combined by an xor butterfly
 // (commutative at every step: all lanes end with the same bits), a workgroup combines its four waves' results in wave
 // order through LDS.  The order depends on the segment's length and the side's width only: two calls give the same bits.
+//
+// Heads (segment_heads_kernel, the *_heads_f32 entries).  Scores are [nseg, H], entry arrays [nnz, H], head fastest.  A
+// lane group owns one (segment, head) pair, consecutive lane groups the consecutive heads of one segment, so the groups
+// of a wave read neighbouring words of the same rows; the long segments take one workgroup per (segment, head).  A pair
+// runs the single-head code on column h (Col<true>: element i of a column sits at i * H + h), so its order of reduction
+// is the single-head one -- it depends on the segment's length and W, not on H -- and column h of a result has the bits
+// of the single-head call on column h of the inputs.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
+#include <type_traits>
 
 #include "hg_attention.h"
 
@@ -31,6 +39,20 @@ struct OpMax {
 };
 struct OpSum {
   static __device__ __forceinline__ float apply(float a, float b) { return a + b; }
+};
+
+// Where element i of the column a lane group works on sits: the array itself (single head), or column h of an [*, H]
+// array.  The single-head form is the plain index, so those instances are what they were before heads existed.
+template <bool MH>
+struct Col;
+template <>
+struct Col<false> {
+  __device__ __forceinline__ int32_t operator()(int32_t i) const { return i; }
+};
+template <>
+struct Col<true> {
+  int32_t H, h;
+  __device__ __forceinline__ int64_t operator()(int32_t i) const { return (int64_t)i * H + h; }  // nnz * H may pass 2^31
 };
 
 // Combine one value per lane over the W lanes that share a segment; every lane gets the result.
@@ -57,18 +79,19 @@ __device__ __forceinline__ int32_t position(const SegArgs &a, int32_t i) {
 }
 
 // raw score of entry i: the segment's own score plus the gathered one of the entry's other end
-__device__ __forceinline__ float raw_score(const SegArgs &a, float own, int32_t i) {
-  return a.other ? own + a.other[a.ind[i]] : own;
+template <bool MH>
+__device__ __forceinline__ float raw_score(const SegArgs &a, Col<MH> col, float own, int32_t i) {
+  return a.other ? own + a.other[col(a.ind[i])] : own;
 }
 
 __device__ __forceinline__ float leaky(float raw, float slope) { return raw > 0.f ? raw : slope * raw; }
 
 // alpha = softmax over the segment of leaky(raw).  An empty segment runs no entry loop at all: nothing is written and no
 // exponential of (-inf) - (-inf) is formed.  A one-entry segment gives exp(0) / 1 = 1.0f exactly.
-template <int SIDE, int W>
-__device__ __forceinline__ void softmax_segment(const SegArgs &a, int32_t seg, int32_t beg, int32_t end, int lane,
+template <int SIDE, int W, bool MH>
+__device__ __forceinline__ void softmax_segment(const SegArgs &a, Col<MH> col, int32_t seg, int32_t beg, int32_t end, int lane,
                                                 float *lds) {
-  const float own = (a.own && beg < end) ? a.own[seg] : 0.f;
+  const float own = (a.own && beg < end) ? a.own[col(seg)] : 0.f;
   float sc[kSegKeep];
   int32_t pos[kSegKeep];
   float m = -INFINITY;
@@ -77,13 +100,13 @@ __device__ __forceinline__ void softmax_segment(const SegArgs &a, int32_t seg, i
     const int32_t i = beg + lane + k * W;
     if (i < end) {
       pos[k] = position<SIDE>(a, i);
-      sc[k] = leaky(raw_score(a, own, i), a.slope);
+      sc[k] = leaky(raw_score(a, col, own, i), a.slope);
       m = fmaxf(m, sc[k]);
     }
   }
   const int32_t tail = beg + lane + kSegKeep * W;
 #pragma unroll 4
-  for (int32_t i = tail; i < end; i += W) m = fmaxf(m, leaky(raw_score(a, own, i), a.slope));
+  for (int32_t i = tail; i < end; i += W) m = fmaxf(m, leaky(raw_score(a, col, own, i), a.slope));
   m = combine<W, OpMax>(m, lds);
   float sum = 0.f;
 #pragma unroll
@@ -94,24 +117,24 @@ __device__ __forceinline__ void softmax_segment(const SegArgs &a, int32_t seg, i
     }
   }
 #pragma unroll 4
-  for (int32_t i = tail; i < end; i += W) sum += __expf(leaky(raw_score(a, own, i), a.slope) - m);
+  for (int32_t i = tail; i < end; i += W) sum += __expf(leaky(raw_score(a, col, own, i), a.slope) - m);
   sum = combine<W, OpSum>(sum, lds);
   const float inv = 1.f / sum;  // the entry holding the maximum contributes exp(0) = 1: sum >= 1 wherever it is used
 #pragma unroll
   for (int k = 0; k < kSegKeep; k++)
-    if (beg + lane + k * W < end) a.out_entry[pos[k]] = sc[k] * inv;
+    if (beg + lane + k * W < end) a.out_entry[col(pos[k])] = sc[k] * inv;
 #pragma unroll 4
   for (int32_t i = tail; i < end; i += W)
-    a.out_entry[position<SIDE>(a, i)] = __expf(leaky(raw_score(a, own, i), a.slope) - m) * inv;
+    a.out_entry[col(position<SIDE>(a, i))] = __expf(leaky(raw_score(a, col, own, i), a.slope) - m) * inv;
 }
 
 // ds = alpha * (dalpha - t) * leaky'(raw), t = sum over the segment of alpha * dalpha; the segment's own sum of ds goes to
 // out_seg (0 for an empty segment).  slope == 1: the non-linearity is the identity and no score is gathered.
-template <int SIDE, int W>
-__device__ __forceinline__ void softmax_bwd_segment(const SegArgs &a, int32_t seg, int32_t beg, int32_t end, int lane,
+template <int SIDE, int W, bool MH>
+__device__ __forceinline__ void softmax_bwd_segment(const SegArgs &a, Col<MH> col, int32_t seg, int32_t beg, int32_t end, int lane,
                                                     float *lds, bool valid) {
   const bool need_raw = a.slope != 1.f;
-  const float own = (need_raw && a.own && beg < end) ? a.own[seg] : 0.f;
+  const float own = (need_raw && a.own && beg < end) ? a.own[col(seg)] : 0.f;
   float al[kSegKeep], da[kSegKeep], fac[kSegKeep];
   int32_t pos[kSegKeep];
   float t = 0.f;
@@ -120,9 +143,9 @@ __device__ __forceinline__ void softmax_bwd_segment(const SegArgs &a, int32_t se
     const int32_t i = beg + lane + k * W;
     if (i < end) {
       pos[k] = position<SIDE>(a, i);
-      al[k] = a.val[pos[k]];
-      da[k] = a.dval[pos[k]];
-      fac[k] = (need_raw && !(raw_score(a, own, i) > 0.f)) ? a.slope : 1.f;
+      al[k] = a.val[col(pos[k])];
+      da[k] = a.dval[col(pos[k])];
+      fac[k] = (need_raw && !(raw_score(a, col, own, i) > 0.f)) ? a.slope : 1.f;
       t += al[k] * da[k];
     }
   }
@@ -130,7 +153,7 @@ __device__ __forceinline__ void softmax_bwd_segment(const SegArgs &a, int32_t se
 #pragma unroll 4
   for (int32_t i = tail; i < end; i += W) {
     const int32_t p = position<SIDE>(a, i);
-    t += a.val[p] * a.dval[p];
+    t += a.val[col(p)] * a.dval[col(p)];
   }
   t = combine<W, OpSum>(t, lds);
   float dsum = 0.f;
@@ -138,40 +161,40 @@ __device__ __forceinline__ void softmax_bwd_segment(const SegArgs &a, int32_t se
   for (int k = 0; k < kSegKeep; k++) {
     if (beg + lane + k * W < end) {
       const float d = al[k] * (da[k] - t) * fac[k];
-      a.out_entry[pos[k]] = d;
+      a.out_entry[col(pos[k])] = d;
       dsum += d;
     }
   }
 #pragma unroll 4
   for (int32_t i = tail; i < end; i += W) {
     const int32_t p = position<SIDE>(a, i);
-    const float f = (need_raw && !(raw_score(a, own, i) > 0.f)) ? a.slope : 1.f;
-    const float d = a.val[p] * (a.dval[p] - t) * f;
-    a.out_entry[p] = d;
+    const float f = (need_raw && !(raw_score(a, col, own, i) > 0.f)) ? a.slope : 1.f;
+    const float d = a.val[col(p)] * (a.dval[col(p)] - t) * f;
+    a.out_entry[col(p)] = d;
     dsum += d;
   }
   if (a.out_seg) {
     dsum = combine<W, OpSum>(dsum, lds);
-    if (lane == 0 && valid) a.out_seg[seg] = dsum;
+    if (lane == 0 && valid) a.out_seg[col(seg)] = dsum;
   }
 }
 
-template <int SIDE, int W>
-__device__ __forceinline__ void sum_segment(const SegArgs &a, int32_t seg, int32_t beg, int32_t end, int lane, float *lds,
+template <int SIDE, int W, bool MH>
+__device__ __forceinline__ void sum_segment(const SegArgs &a, Col<MH> col, int32_t seg, int32_t beg, int32_t end, int lane, float *lds,
                                             bool valid) {
   float s = 0.f;
 #pragma unroll 4
-  for (int32_t i = beg + lane; i < end; i += W) s += a.val[position<SIDE>(a, i)];
+  for (int32_t i = beg + lane; i < end; i += W) s += a.val[col(position<SIDE>(a, i))];
   s = combine<W, OpSum>(s, lds);
-  if (lane == 0 && valid) a.out_seg[seg] = s;
+  if (lane == 0 && valid) a.out_seg[col(seg)] = s;
 }
 
-template <int BODY, int SIDE, int W>
-__device__ __forceinline__ void run_segment(const SegArgs &a, int32_t seg, int32_t beg, int32_t end, int lane, float *lds,
+template <int BODY, int SIDE, int W, bool MH>
+__device__ __forceinline__ void run_segment(const SegArgs &a, Col<MH> col, int32_t seg, int32_t beg, int32_t end, int lane, float *lds,
                                             bool valid) {
-  if constexpr (BODY == kSegSoftmax) softmax_segment<SIDE, W>(a, seg, beg, end, lane, lds);
-  else if constexpr (BODY == kSegSoftmaxBwd) softmax_bwd_segment<SIDE, W>(a, seg, beg, end, lane, lds, valid);
-  else sum_segment<SIDE, W>(a, seg, beg, end, lane, lds, valid);
+  if constexpr (BODY == kSegSoftmax) softmax_segment<SIDE, W>(a, col, seg, beg, end, lane, lds);
+  else if constexpr (BODY == kSegSoftmaxBwd) softmax_bwd_segment<SIDE, W>(a, col, seg, beg, end, lane, lds, valid);
+  else sum_segment<SIDE, W>(a, col, seg, beg, end, lane, lds, valid);
 }
 
 // Workgroups [0, nlong): one long segment each (they run longest, so they start first); the others: 256 / W lane groups,
@@ -182,7 +205,7 @@ __global__ __launch_bounds__(kSegBlock) void segment_kernel(SegArgs a) {
   __shared__ float lds[kSegBlock / 64];
   if ((int32_t)blockIdx.x < a.nlong) {
     const int32_t seg = a.long_seg[blockIdx.x];
-    run_segment<BODY, SIDE, kSegBlock>(a, seg, a.ptr[seg], a.ptr[seg + 1], (int)threadIdx.x, lds, true);
+    run_segment<BODY, SIDE, kSegBlock>(a, Col<false>{}, seg, a.ptr[seg], a.ptr[seg + 1], (int)threadIdx.x, lds, true);
     return;
   }
   constexpr int kGroups = kSegBlock / W;
@@ -198,23 +221,79 @@ __global__ __launch_bounds__(kSegBlock) void segment_kernel(SegArgs a) {
       valid = false;
     }
   }
-  run_segment<BODY, SIDE, W>(a, seg, beg, end, (int)threadIdx.x % W, lds, valid);
+  run_segment<BODY, SIDE, W>(a, Col<false>{}, seg, beg, end, (int)threadIdx.x % W, lds, valid);
 }
 
-template <int BODY, int SIDE>
-hipError_t launch_width(int width, unsigned nblocks, const SegArgs &a, hipStream_t stream) {
+// The same with heads: workgroups [0, nlong * H) take one (long segment, head) each, the lane groups of the others one
+// (segment, head) each, head fastest.
+template <int BODY, int SIDE, int W>
+__global__ __launch_bounds__(kSegBlock) void segment_heads_kernel(SegHeadsArgs a) {
+  __shared__ float lds[kSegBlock / 64];
+  const int32_t H = a.heads;
+  const int64_t nlong = (int64_t)a.nlong * H;
+  if ((int64_t)blockIdx.x < nlong) {
+    const int32_t seg = a.long_seg[blockIdx.x / H];
+    run_segment<BODY, SIDE, kSegBlock>(a, Col<true>{H, (int32_t)(blockIdx.x % H)}, seg, a.ptr[seg], a.ptr[seg + 1],
+                                       (int)threadIdx.x, lds, true);
+    return;
+  }
+  constexpr int kGroups = kSegBlock / W;
+  const int64_t s = ((int64_t)blockIdx.x - nlong) * kGroups + (int)threadIdx.x / W;
+  bool valid = s < (int64_t)a.nseg * H;
+  const int32_t seg = valid ? (int32_t)(s / H) : 0;
+  const int32_t h = valid ? (int32_t)(s % H) : 0;
+  int32_t beg = 0, end = 0;
+  if (valid) {
+    beg = a.ptr[seg];
+    end = a.ptr[seg + 1];
+    if (end - beg > kSegLong) {  // a workgroup of its own has it
+      beg = end = 0;
+      valid = false;
+    }
+  }
+  run_segment<BODY, SIDE, W>(a, Col<true>{H, h}, seg, beg, end, (int)threadIdx.x % W, lds, valid);
+}
+
+// ARGS = SegArgs: segment_kernel; ARGS = SegHeadsArgs: segment_heads_kernel
+template <int BODY, int SIDE, int W, typename ARGS>
+void launch_one(unsigned nblocks, const ARGS &a, hipStream_t stream) {
+  if constexpr (std::is_same_v<ARGS, SegHeadsArgs>)
+    hipLaunchKernelGGL((segment_heads_kernel<BODY, SIDE, W>), dim3(nblocks), dim3(kSegBlock), 0, stream, a);
+  else
+    hipLaunchKernelGGL((segment_kernel<BODY, SIDE, W>), dim3(nblocks), dim3(kSegBlock), 0, stream, a);
+}
+
+template <int BODY, int SIDE, typename ARGS>
+hipError_t launch_width(int width, unsigned nblocks, const ARGS &a, hipStream_t stream) {
   switch (width) {
-    case 4: hipLaunchKernelGGL((segment_kernel<BODY, SIDE, 4>), dim3(nblocks), dim3(kSegBlock), 0, stream, a); break;
-    case 8: hipLaunchKernelGGL((segment_kernel<BODY, SIDE, 8>), dim3(nblocks), dim3(kSegBlock), 0, stream, a); break;
-    case 16: hipLaunchKernelGGL((segment_kernel<BODY, SIDE, 16>), dim3(nblocks), dim3(kSegBlock), 0, stream, a); break;
+    case 4: launch_one<BODY, SIDE, 4>(nblocks, a, stream); break;
+    case 8: launch_one<BODY, SIDE, 8>(nblocks, a, stream); break;
+    case 16: launch_one<BODY, SIDE, 16>(nblocks, a, stream); break;
     default: return hipErrorInvalidValue;
   }
   return hipGetLastError();
 }
 
-template <int BODY>
-hipError_t launch_side(int side, int width, unsigned nblocks, const SegArgs &a, hipStream_t stream) {
+template <int BODY, typename ARGS>
+hipError_t launch_side(int side, int width, unsigned nblocks, const ARGS &a, hipStream_t stream) {
   return side == 0 ? launch_width<BODY, 0>(width, nblocks, a, stream) : launch_width<BODY, 1>(width, nblocks, a, stream);
+}
+
+// heads: the work items are (segment, head) pairs
+template <typename ARGS>
+hipError_t launch_body(int body, int side, int width, int64_t heads, const ARGS &a, hipStream_t stream) {
+  if (a.nseg <= 0) return hipSuccess;
+  if (side < 0 || side > 1 || a.nlong < 0 || !a.ptr || (a.nlong > 0 && !a.long_seg)) return hipErrorInvalidValue;
+  if (width != 4 && width != 8 && width != 16) return hipErrorInvalidValue;
+  const int64_t groups = kSegBlock / width;
+  const int64_t nblocks = a.nlong * heads + (a.nseg * heads + groups - 1) / groups;
+  if (nblocks > 0x7fffffff) return hipErrorInvalidValue;
+  switch (body) {
+    case kSegSoftmax: return launch_side<kSegSoftmax>(side, width, (unsigned)nblocks, a, stream);
+    case kSegSoftmaxBwd: return launch_side<kSegSoftmaxBwd>(side, width, (unsigned)nblocks, a, stream);
+    case kSegSum: return launch_side<kSegSum>(side, width, (unsigned)nblocks, a, stream);
+  }
+  return hipErrorInvalidValue;
 }
 
 }  // namespace
@@ -224,18 +303,12 @@ hipError_t launch_side(int side, int width, unsigned nblocks, const SegArgs &a, 
 int seg_width(double mean) { return mean <= 4.0 ? 4 : mean <= 8.0 ? 8 : 16; }
 
 hipError_t launch_segments(int body, int side, int width, const SegArgs &a, hipStream_t stream) {
-  if (a.nseg <= 0) return hipSuccess;
-  if (side < 0 || side > 1 || a.nlong < 0 || !a.ptr || (a.nlong > 0 && !a.long_seg)) return hipErrorInvalidValue;
-  if (width != 4 && width != 8 && width != 16) return hipErrorInvalidValue;
-  const int64_t groups = kSegBlock / width;
-  const int64_t nblocks = a.nlong + (a.nseg + groups - 1) / groups;
-  if (nblocks > 0x7fffffff) return hipErrorInvalidValue;
-  switch (body) {
-    case kSegSoftmax: return launch_side<kSegSoftmax>(side, width, (unsigned)nblocks, a, stream);
-    case kSegSoftmaxBwd: return launch_side<kSegSoftmaxBwd>(side, width, (unsigned)nblocks, a, stream);
-    case kSegSum: return launch_side<kSegSum>(side, width, (unsigned)nblocks, a, stream);
-  }
-  return hipErrorInvalidValue;
+  return launch_body(body, side, width, 1, a, stream);
+}
+
+hipError_t launch_segments_heads(int body, int side, int width, const SegHeadsArgs &a, hipStream_t stream) {
+  if (a.heads < 1) return hipErrorInvalidValue;
+  return launch_body(body, side, width, a.heads, a, stream);
 }
 
 }  // namespace hg

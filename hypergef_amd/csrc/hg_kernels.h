@@ -41,6 +41,12 @@ struct WeightedGatherArgs : GatherArgs {
   const int32_t *wperm = nullptr;  // null: w is in the walked CSR's own order
 };
 
+// A weight per entry and head (hg_aggr_incidence_heads_f32): w is [nnz, heads], head fastest, and head h owns columns
+// h * C .. (h + 1) * C - 1 of the F = heads * C wide rows.  Only gather_rows_kernel's WH instances take it.
+struct HeadsGatherArgs : WeightedGatherArgs {
+  int32_t heads = 1, C = 0;
+};
+
 // What happens to an aggregated row t = Aggr(X)[v] on its way through the linear epilogue:
 //   t' = ca * t + cb * R[v]   (R null: t' = ca * t),   T_out[v] = t' if wanted,
 //   Y[v] = act(t' * Wlin^T),  act = relu or identity.
@@ -142,6 +148,13 @@ hipError_t launch_gather(const GatherArgs &a, int nfix, int nfix_l1, const Fixup
 // the same with a.w (not null) on the weighted instances; fp32 rows
 hipError_t launch_gather_weighted(const WeightedGatherArgs &a, int nfix, int nfix_l1, const Fixup *fixups, bool vec4,
                                   hipStream_t stream);
+// a.w [nnz, heads] on the per-head instances.  vec4: as above; lane4: 16-byte lanes may be used (vec4 and C % 4 == 0, so
+// that a lane lies inside one head); otherwise 4-byte lanes on the single-head call's lane groups.
+hipError_t launch_gather_heads(const HeadsGatherArgs &a, int nfix, int nfix_l1, const Fixup *fixups, bool vec4, bool lane4,
+                               hipStream_t stream);
+// out[p, h] = <A[ind[p], hC .. (h+1)C), B[e, hC .. (h+1)C)>, out [nnz, H].  lane4: C % 4 == 0 and A, B 16-byte aligned.
+hipError_t launch_incidence_dot_heads(int32_t M, int64_t nnz, int32_t H, int32_t C, const int32_t *ptr, const int32_t *ind,
+                                      const float *A, const float *B, float *out, bool lane4, hipStream_t stream);
 // out[p] = <A[ind[p], :], B[e, :]> for every entry p of the CSR (ptr, ind) over M rows, e the row holding p (the weight
 // gradient of hg_aggr_incidence_f32).  vec4: F % 4 == 0 and A, B 16-byte aligned.
 hipError_t launch_incidence_dot(int32_t M, int64_t nnz, int32_t F, const int32_t *ptr, const int32_t *ind, const float *A,

@@ -143,8 +143,17 @@ template <> struct Rows<bf16, 4> {
 // WT: per-entry weights (WeightedGatherArgs, hg_aggr_incidence_f32): the same walk, each gathered row added as
 // acc = fma(row, weight, acc).  Wave tasks load the weight beside the index; panels stage the weights in LDS after
 // sind (launch_gather_t sizes those instances' LDS for it).  Partial rows leave already weighted: fixups are unchanged.
-template <int LPR, int VEC, typename TS = float, typename TD = float, bool WT = false>
-__global__ __launch_bounds__(256) void gather_rows_kernel(const std::conditional_t<WT, WeightedGatherArgs, GatherArgs> a) {
+// WH: a weight per entry and head (HeadsGatherArgs, hg_aggr_incidence_heads_f32): w is [nnz, H], head fastest, and head h
+// owns columns h * C .. (h + 1) * C - 1 of the rows; a lane multiplies its columns by the weight of the head that owns them, taken from the
+// lane's absolute column (a column tile may begin inside a head), acc = fma(row, w[pos * H + col / C], acc).  A 16-byte lane
+// lies inside one head (the launcher takes VEC = 4 only where C % 4 == 0).  The weights are read where they lie, beside the
+// row they scale (4 H contiguous bytes per entry, shared by the lanes of a row); panels stage the entries' positions
+// (hop 2: perm) where the WT instances stage the weights, so the LDS does not grow with H.
+template <bool WT, bool WH>
+using GatherArgsOf = std::conditional_t<WH, HeadsGatherArgs, std::conditional_t<WT, WeightedGatherArgs, GatherArgs>>;
+template <int LPR, int VEC, typename TS = float, typename TD = float, bool WT = false, bool WH = false>
+__global__ __launch_bounds__(256) void gather_rows_kernel(const GatherArgsOf<WT, WH> a) {
+  static_assert(!(WT && WH), "per-entry or per-head weights");
   constexpr int U = 4;           // row loads in flight per lane (8, or two batches in flight: within 3 %, profiles/r01_fused_experiments.md)
   constexpr int G = 64 / LPR;    // row groups per wave
   constexpr int NG = 256 / LPR;  // row groups per workgroup
@@ -161,6 +170,8 @@ __global__ __launch_bounds__(256) void gather_rows_kernel(const std::conditional
   const bool col_ok = col < a.F;
   const int64_t F = a.F;
   int b = blockIdx.x;
+  int hd = 0;  // the head of this lane's columns
+  if constexpr (WH) hd = col_ok ? col / a.C : 0;
 
   if (b < a.n_task_blocks) {
     const int t = __builtin_amdgcn_readfirstlane(b * 4 + (tid >> 6));
@@ -177,11 +188,12 @@ __global__ __launch_bounds__(256) void gather_rows_kernel(const std::conditional
         const bool ok = col_ok && q < tk.end;
         const int64_t idx = ok ? a.ind[q] : 0;
         if constexpr (WT) wv[k] = ok ? a.w[a.wperm ? a.wperm[q] : q] : 0.f;
+        if constexpr (WH) wv[k] = ok ? a.w[(int64_t)(a.wperm ? a.wperm[q] : q) * a.heads + hd] : 0.f;
         v[k] = ok ? RS::load(src + idx * F + col) : V::zero();
       }
 #pragma unroll
       for (int k = 0; k < U; k++) {
-        if constexpr (WT) acc.fma(v[k], wv[k]);
+        if constexpr (WT || WH) acc.fma(v[k], wv[k]);
         else acc.add(v[k]);
       }
     }
@@ -232,6 +244,11 @@ __global__ __launch_bounds__(256) void gather_rows_kernel(const std::conditional
       sw[i] = a.w[a.wperm ? a.wperm[q] : q];
     }
   }
+  const int32_t *swp = reinterpret_cast<const int32_t *>(sw);  // WH: the entries' positions in w, where perm gives them
+  if constexpr (WH) {
+    if (a.wperm)
+      for (int i = tid; i < pn.nnz_cnt; i += 256) reinterpret_cast<int32_t *>(sw)[i] = a.wperm[pn.nnz0 + i];
+  }
   __syncthreads();
 
   const int g = tid / LPR;
@@ -257,10 +274,15 @@ __global__ __launch_bounds__(256) void gather_rows_kernel(const std::conditional
   int row_end = sptr[r + 1];
   V acc = V::zero();
 
+  float wv[WH ? U : 1];  // WH: the weights of the rows in flight
   auto issue = [&](int p0, int n, V(&v)[U]) {
 #pragma unroll
     for (int k = 0; k < U; k++) {
       const int64_t idx = sind[p0 + min(k, n - 1)];
+      if constexpr (WH) {
+        const int64_t wp = a.wperm ? swp[p0 + min(k, n - 1)] : pn.nnz0 + p0 + min(k, n - 1);
+        wv[k] = col_ok ? a.w[wp * a.heads + hd] : 0.f;
+      }
       v[k] = col_ok ? RS::load(src + idx * F + col) : V::zero();
     }
   };
@@ -275,6 +297,7 @@ __global__ __launch_bounds__(256) void gather_rows_kernel(const std::conditional
           row_end = sptr[r + 1];
         }
         if constexpr (WT) acc.fma(v[k], sw[p0 + k]);
+        else if constexpr (WH) acc.fma(v[k], wv[k]);
         else acc.add(v[k]);
       }
     }
@@ -396,6 +419,68 @@ __global__ __launch_bounds__(256) void incidence_dot_kernel(const int32_t *ptr, 
 #pragma unroll
     for (int off = 1; off < LPR; off <<= 1) acc[k] += __shfl_xor(acc[k], off, 64);
     if (gl == 0 && k < n) out[p0 + k] = acc[k];
+  }
+}
+
+// The same per head: out[p, h] = <A[ind[p], hC .. (h+1)C), B[e, hC .. (h+1)C)>, out [nnz, H] with the head fastest.  A lane
+// group of LPH lanes (the lanes C columns need, up to 64) owns one head of kDotRun consecutive entries; consecutive lane
+// groups take the consecutive heads of the same entries, so a wave reads neighbouring pieces of the same rows.  The
+// butterfly runs over a group's LPH lanes only: the lanes of one head are reduced apart from their neighbours, in a
+// fixed order.
+template <int LPH, int VEC>
+__global__ __launch_bounds__(256) void incidence_dot_heads_kernel(const int32_t *ptr, const int32_t *ind, int32_t M,
+                                                                  int64_t nnz, int32_t H, int32_t C, const float *A,
+                                                                  const float *B, float *out) {
+  using V = Vec<VEC>;
+  constexpr int NG = 256 / LPH;
+  const int tid = threadIdx.x, gl = tid & (LPH - 1), g = tid / LPH;
+  const int64_t F = (int64_t)H * C;
+  const int64_t item0 = (int64_t)blockIdx.x * NG;  // items: (run of kDotRun entries, head), head fastest
+  const int64_t item = item0 + g;
+  const int64_t p0 = item / H * kDotRun;
+  const int h = (int)(item % H);
+  if (p0 >= nnz) return;
+  const int64_t c0 = item0 / H * kDotRun;
+  const int64_t c1 = std::min<int64_t>(((item0 + NG - 1) / H + 1) * kDotRun, nnz);
+  const int elo = row_of(ptr, 0, M, c0);
+  const int ehi = row_of(ptr, elo, M, c1 - 1);
+  int e = row_of(ptr, elo, ehi + 1, p0);
+  const int n = (int)std::min<int64_t>(kDotRun, nnz - p0);
+  int64_t ua[kDotRun], eb[kDotRun];
+#pragma unroll
+  for (int k = 0; k < kDotRun; k++) {
+    const int64_t p = p0 + std::min(k, n - 1);
+    while (ptr[e + 1] <= p) e++;
+    ua[k] = (int64_t)ind[p] * F + (int64_t)h * C;
+    eb[k] = (int64_t)e * F + (int64_t)h * C;
+  }
+  float acc[kDotRun];
+#pragma unroll
+  for (int k = 0; k < kDotRun; k++) acc[k] = 0.f;
+  for (int c = gl * VEC; c < C; c += LPH * VEC) {
+    V x[kDotRun], y[kDotRun];
+#pragma unroll
+    for (int k = 0; k < kDotRun; k++) {
+      x[k] = V::load(A + ua[k] + c);
+      y[k] = V::load(B + eb[k] + c);
+    }
+#pragma unroll
+    for (int k = 0; k < kDotRun; k++) {
+      if constexpr (VEC == 4) {
+        acc[k] = __builtin_fmaf(x[k].v.x, y[k].v.x, acc[k]);
+        acc[k] = __builtin_fmaf(x[k].v.y, y[k].v.y, acc[k]);
+        acc[k] = __builtin_fmaf(x[k].v.z, y[k].v.z, acc[k]);
+        acc[k] = __builtin_fmaf(x[k].v.w, y[k].v.w, acc[k]);
+      } else {
+        acc[k] = __builtin_fmaf(x[k].x, y[k].x, acc[k]);
+      }
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < kDotRun; k++) {
+#pragma unroll
+    for (int off = 1; off < LPH; off <<= 1) acc[k] += __shfl_xor(acc[k], off, 64);
+    if (gl == 0 && k < n) out[(p0 + k) * H + h] = acc[k];
   }
 }
 
@@ -2007,16 +2092,18 @@ static hipError_t launch_fixups_t(const GatherArgs &a, int nfix, int nfix_l1, co
   return hipGetLastError();
 }
 
-template <int LPR, int VEC, typename TS = float, typename TD = float, bool WT = false>
-static hipError_t launch_gather_t(const std::conditional_t<WT, WeightedGatherArgs, GatherArgs> &a, int nfix, int nfix_l1,
-                                  const Fixup *fixups, hipStream_t stream) {
+// WM: 0 no weights, 1 a weight per entry (the WT instances), 2 a weight per entry and head (the WH instances)
+template <int LPR, int VEC, typename TS = float, typename TD = float, int WM = 0>
+static hipError_t launch_gather_t(const GatherArgsOf<WM == 1, WM == 2> &a, int nfix, int nfix_l1, const Fixup *fixups,
+                                  hipStream_t stream) {
+  constexpr bool WT = WM != 0;
   const int col_tiles = (a.F + LPR * VEC - 1) / (LPR * VEC);
   const int nblocks = a.n_task_blocks + a.npanels;
   if (nblocks > 0) {
-    // the weighted instances stage one float per index entry beside sind
+    // the weighted instances stage one float (heads: one position) per index entry beside sind
     const size_t lds = (size_t)(4 * a.panel_rows + 1 + (WT ? 2 : 1) * a.panel_nnz) * sizeof(int32_t);
     const dim3 grid(nblocks, col_tiles);
-    const hipError_t e = launch_lds<gather_rows_kernel<LPR, VEC, TS, TD, WT>>(grid, lds, stream, a);
+    const hipError_t e = launch_lds<gather_rows_kernel<LPR, VEC, TS, TD, WM == 1, WM == 2>>(grid, lds, stream, a);
     if (e != hipSuccess) return e;
   }
   return launch_fixups_t<LPR, VEC, TD>(a, nfix, nfix_l1, fixups, stream);
@@ -2053,9 +2140,64 @@ hipError_t launch_gather_weighted(const WeightedGatherArgs &a, int nfix, int nfi
   const int lpr = std::min(64, next_pow2(std::max(lanes, 1)));
 #define HG_CASE(L)                                                                                     \
   case L:                                                                                              \
-    return vec4 ? launch_gather_t<L, 4, float, float, true>(a, nfix, nfix_l1, fixups, stream)          \
-                : launch_gather_t<L, 1, float, float, true>(a, nfix, nfix_l1, fixups, stream);
+    return vec4 ? launch_gather_t<L, 4, float, float, 1>(a, nfix, nfix_l1, fixups, stream)          \
+                : launch_gather_t<L, 1, float, float, 1>(a, nfix, nfix_l1, fixups, stream);
   switch (lpr) {
+    HG_CASE(1)
+    HG_CASE(2)
+    HG_CASE(4)
+    HG_CASE(8)
+    HG_CASE(16)
+    HG_CASE(32)
+    HG_CASE(64)
+  }
+#undef HG_CASE
+  return hipErrorInvalidValue;
+}
+
+// lane4: 16-byte lanes are legal (C % 4 == 0, rows and partial rows 16-byte aligned).  lpr: the lanes per row of the
+// single-head call of the same F -- the heads instances keep it on 4-byte lanes too and run more column tiles instead, so
+// that a wave task's entries are dealt to the same 64 / lpr row groups and every column is summed in the single-head order.
+hipError_t launch_gather_heads(const HeadsGatherArgs &a, int nfix, int nfix_l1, const Fixup *fixups, bool vec4, bool lane4,
+                               hipStream_t stream) {
+  if (!a.w || a.heads < 1 || a.C < 1 || (int64_t)a.heads * a.C != a.F || (lane4 && (!vec4 || a.C % 4))) return hipErrorInvalidValue;
+  const int lanes = vec4 ? a.F / 4 : a.F;
+  const int lpr = std::min(64, next_pow2(std::max(lanes, 1)));
+#define HG_CASE(L)                                                                                  \
+  case L:                                                                                           \
+    return lane4 ? launch_gather_t<L, 4, float, float, 2>(a, nfix, nfix_l1, fixups, stream)         \
+                 : launch_gather_t<L, 1, float, float, 2>(a, nfix, nfix_l1, fixups, stream);
+  switch (lpr) {
+    HG_CASE(1)
+    HG_CASE(2)
+    HG_CASE(4)
+    HG_CASE(8)
+    HG_CASE(16)
+    HG_CASE(32)
+    HG_CASE(64)
+  }
+#undef HG_CASE
+  return hipErrorInvalidValue;
+}
+
+hipError_t launch_incidence_dot_heads(int32_t M, int64_t nnz, int32_t H, int32_t C, const int32_t *ptr, const int32_t *ind,
+                                      const float *A, const float *B, float *out, bool lane4, hipStream_t stream) {
+  if (nnz == 0) return hipSuccess;
+  if (M <= 0 || H <= 0 || C <= 0 || (lane4 && C % 4)) return hipErrorInvalidValue;
+  const int lanes = lane4 ? C / 4 : C;
+  const int lph = std::min(64, next_pow2(std::max(lanes, 1)));
+  const int64_t items = (nnz + kDotRun - 1) / kDotRun * H;
+  const int64_t per_block = 256 / lph;
+  const int64_t nblocks = (items + per_block - 1) / per_block;
+  if (nblocks > 0x7fffffff) return hipErrorInvalidValue;
+#define HG_CASE(L)                                                                                                       \
+  case L:                                                                                                                \
+    if (lane4) hipLaunchKernelGGL((incidence_dot_heads_kernel<L, 4>), dim3((unsigned)nblocks), dim3(256), 0, stream, ptr, \
+                                  ind, M, nnz, H, C, A, B, out);                                                         \
+    else hipLaunchKernelGGL((incidence_dot_heads_kernel<L, 1>), dim3((unsigned)nblocks), dim3(256), 0, stream, ptr, ind,  \
+                            M, nnz, H, C, A, B, out);                                                                    \
+    return hipGetLastError();
+  switch (lph) {
     HG_CASE(1)
     HG_CASE(2)
     HG_CASE(4)

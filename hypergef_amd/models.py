@@ -103,43 +103,61 @@ class HyperGsysUniGCNII(nn.Module):
 
 
 class HypergraphAttnConv(nn.Module):
-    """A hypergraph attention layer (single head) whose coefficient path runs on this backend's segment kernels:
+    """A hypergraph attention layer whose coefficient path runs on this backend's segment kernels.  Single head:
         Z = X W^T,   sv = Z a_v,   se[e] = mean_{u in e} (Z a_e)[u]   (0 for an empty hyperedge),
         alpha = softmax over each group of leaky_relu(sv[u] + se[e], negative_slope)      (ops.incidence_softmax),
         Y = degV . H_alpha (degE . (H_alpha^T Z)) + bias                                  (ops.incidence_aggr).
     group: 'hyperedge' normalises over each hyperedge's members, 'vertex' over each vertex's hyperedges.  Parameters: the
-    linear's weight, a_v, a_e [out_channels] and bias [out_channels]."""
+    linear's weight, a_v, a_e [out_channels] and bias [out_channels].
+    heads = H > 1: the linear maps to H * out_channels, head h owns columns h C .. (h + 1) C - 1 of Z (C = out_channels),
+    a_v / a_e are flat [H * C], sv[u, h] = <Z[u, head h], a_v[head h]>, se the per-head hyperedge mean, alpha [nnz, H], and
+    every operator runs once for all heads (heads=H).  The output is [N, H * C] (concat=True) or the mean over the heads
+    [N, C]; the bias has the output's width.  heads = 1 is the single-head layer, parameter for parameter."""
 
-    def __init__(self, hyperg, in_channels, out_channels, group="hyperedge", negative_slope=0.2, options=None):
+    def __init__(self, hyperg, in_channels, out_channels, group="hyperedge", negative_slope=0.2, options=None, heads=1,
+                 concat=True):
         super().__init__()
         if group not in ("hyperedge", "vertex"):
             raise ValueError("group must be 'hyperedge' or 'vertex', got %r" % (group,))
+        if isinstance(heads, bool) or not isinstance(heads, int) or heads < 1:
+            raise ValueError("heads must be an integer >= 1, got %r" % (heads,))
         self.options, self.group, self.negative_slope = options, group, float(negative_slope)
         self.in_channels, self.out_channels = in_channels, out_channels
-        self.lin = ops.Linear(in_channels, out_channels, bias=False, options=options)
+        self.heads, self.concat = heads, bool(concat)
+        self.lin = ops.Linear(in_channels, heads * out_channels, bias=False, options=options)
         bound = math.sqrt(6.0 / (out_channels + 1))
-        self.a_v = nn.Parameter(torch.empty(out_channels).uniform_(-bound, bound))
-        self.a_e = nn.Parameter(torch.empty(out_channels).uniform_(-bound, bound))
-        self.bias = nn.Parameter(torch.zeros(out_channels))
+        self.a_v = nn.Parameter(torch.empty(heads * out_channels).uniform_(-bound, bound))
+        self.a_e = nn.Parameter(torch.empty(heads * out_channels).uniform_(-bound, bound))
+        self.bias = nn.Parameter(torch.zeros(heads * out_channels if self.concat else out_channels))
         self.hyperg, self.degE, self.degV = hyperg, hyperg.degE, hyperg.degV
         self.Wdiag = torch.ones(hyperg.degE.shape[0]).to(hyperg.device)
         self._members = hyperg.H_T_colind.long()                                 # vertex of every incidence
         self._inv_size = torch.nan_to_num(hyperg.degE.reshape(-1), posinf=0.0)   # 1 / |e|, 0 for an empty hyperedge
 
     def coefficients(self, Z):
-        """alpha [nnz] for the projected features Z."""
+        """alpha for the projected features Z: [nnz], or [nnz, heads]."""
         ptr, ind = self.hyperg.H_T_csrptr, self.hyperg.H_T_colind
-        sv = Z @ self.a_v
-        ze = (Z @ self.a_e)[self._members]
-        se = ops.incidence_sum(ptr, ind, ze, side="hyperedge", num_nodes=Z.shape[0]) * self._inv_size
+        if self.heads == 1:
+            sv = Z @ self.a_v
+            ze = (Z @ self.a_e)[self._members]
+            se = ops.incidence_sum(ptr, ind, ze, side="hyperedge", num_nodes=Z.shape[0]) * self._inv_size
+            return ops.incidence_softmax(ptr, ind, sv, se, group=self.group, negative_slope=self.negative_slope,
+                                         options=self.options, num_nodes=Z.shape[0])
+        H, C = self.heads, self.out_channels
+        Zh = Z.view(Z.shape[0], H, C)
+        sv = (Zh * self.a_v.view(H, C)).sum(-1)
+        ze = (Zh * self.a_e.view(H, C)).sum(-1)[self._members]
+        se = ops.incidence_sum(ptr, ind, ze, side="hyperedge", num_nodes=Z.shape[0], heads=H) * self._inv_size.reshape(-1, 1)
         return ops.incidence_softmax(ptr, ind, sv, se, group=self.group, negative_slope=self.negative_slope,
-                                     options=self.options, num_nodes=Z.shape[0])
+                                     options=self.options, num_nodes=Z.shape[0], heads=H)
 
     def forward(self, X):
         Z = self.lin(X)
         alpha = self.coefficients(Z)
         Y = ops.incidence_aggr(self.hyperg.H_T_csrptr, self.hyperg.H_T_colind, Z, alpha, alpha, self.degE, self.degV,
-                               self.Wdiag, options=self.options)
+                               self.Wdiag, options=self.options, heads=self.heads)
+        if self.heads > 1 and not self.concat:
+            Y = Y.view(Y.shape[0], self.heads, self.out_channels).mean(1)
         return Y + self.bias
 
 

@@ -132,6 +132,19 @@ def _flat(t):
     return None if t is None else t.reshape(-1)
 
 
+def _heads(heads):
+    """The `heads` keyword as an int >= 1: ValueError otherwise, before any tensor is looked at."""
+    if isinstance(heads, bool) or not isinstance(heads, int) or heads < 1:
+        raise ValueError("heads must be an integer >= 1, got %r" % (heads,))
+    return heads
+
+
+def _per_head(t, heads):
+    """A per-item array with `heads` columns as [*, heads] where its element count allows it (a wrong count is kept as it
+    is and refused by the length checks)."""
+    return t.reshape(-1, heads) if t.numel() % heads == 0 else t
+
+
 def _times_degV(g, degV):
     """g * degV per row (the adjoint backward's input).  A bf16 g is multiplied in fp32 and rounded to bf16 once: torch
     would promote the product to fp32 and send the backward through the fp32 kernels."""
@@ -434,23 +447,29 @@ def hgnnaggr_linear(csrptr_t, indices_t, node_feat, weight, degE=None, degV=None
 
 # ---- incidence-weighted aggregation (include/hg_aggr.h, hg_aggr_incidence_f32) ----------------------------------------
 
-def _incidence_args(csrptr_t, indices_t, node_feat, v2e, e2v, opt):
+def _incidence_args(csrptr_t, indices_t, node_feat, v2e, e2v, opt, heads=1):
     """Argument checks of incidence_aggr, in an order that decides every refusal before a device is touched: variant,
-    dtypes, shapes and lengths, then where the tensors live."""
+    heads, dtypes, shapes and lengths, then where the tensors live."""
     if opt.variant not in ("auto", "pull"):
         raise ValueError("incidence_aggr runs the pull kernels: variant must be 'auto' or 'pull', got %r" % opt.variant)
+    _heads(heads)
     for name, t in (("node_feat", node_feat), ("v2e_weight", v2e), ("e2v_weight", e2v)):
         if t is not None and (not isinstance(t, torch.Tensor) or t.dtype != torch.float32):
             raise TypeError("%s must be a float32 tensor (incidence_aggr has no bfloat16 form), got %s"
                             % (name, getattr(t, "dtype", type(t))))
     if node_feat.dim() != 2:
         raise ValueError("node_feat must be [N, F]")
+    if node_feat.shape[1] % heads:
+        raise ValueError("node_feat's width %d is no multiple of heads = %d" % (node_feat.shape[1], heads))
     if not isinstance(indices_t, torch.Tensor):
         raise TypeError("indices_t must be an int32 tensor")
     nnz = indices_t.numel()
     for name, t in (("v2e_weight", v2e), ("e2v_weight", e2v)):
-        if t is not None and t.numel() != nnz:
-            raise ValueError("%s must have one weight per incidence (nnz = %d), got %d" % (name, nnz, t.numel()))
+        if t is not None and t.numel() != nnz * heads:
+            if heads == 1:
+                raise ValueError("%s must have one weight per incidence (nnz = %d), got %d" % (name, nnz, t.numel()))
+            raise ValueError("%s must have one weight per incidence and head (nnz * heads = %d), got %d"
+                             % (name, nnz * heads, t.numel()))
     _check_index(csrptr_t, "csrptr_t")
     _check_index(indices_t, "indices_t")
     _check_feat(node_feat, "node_feat")
@@ -463,18 +482,20 @@ class _IncidenceAggr(torch.autograd.Function):
     """Y = Dv H_e2v De W H_v2e^T X with a weight per incidence, and its exact gradients for X and both weight arrays.
     With P = degV * dY:  G = the same call on P with the weights swapped and no degV (hop 1's table, De W H_e2v^T P, goes
     to xe_out); its output is dX.  dv2e[p = (e, u)] = <X[u], G[e]>, de2v[p = (e, v)] = <P[v], Xe[e]> (incidence_dot),
-    Xe the forward's hop-1 table, kept only when e2v needs a gradient.  degE / degV / W get none."""
+    Xe the forward's hop-1 table, kept only when e2v needs a gradient.  degE / degV / W get none.  With heads = H the
+    weights and their gradients are [nnz, H] and the products run over each head's own columns."""
 
     @staticmethod
-    def forward(ctx, csrptr_t, indices_t, node_feat, v2e, e2v, degE, degV, W):
+    def forward(ctx, csrptr_t, indices_t, node_feat, v2e, e2v, degE, degV, W, heads=1):
         N, F = node_feat.shape
         M = csrptr_t.numel() - 1
         plan = cached_plan(N, csrptr_t, indices_t)
         keep_xe = e2v is not None and ctx.needs_input_grad[4]
         Xe = torch.empty((M, F), dtype=torch.float32, device=node_feat.device) if keep_xe else None
-        out = plan.aggregate_incidence(csrptr_t, indices_t, node_feat, v2e, e2v, degE, degV, W, xe_out=Xe)
+        out = plan.aggregate_incidence(csrptr_t, indices_t, node_feat, v2e, e2v, degE, degV, W, xe_out=Xe, heads=heads)
         keep_x = v2e is not None and ctx.needs_input_grad[3]
         ctx.save_for_backward(csrptr_t, indices_t, node_feat if keep_x else None, v2e, e2v, degE, degV, W, Xe)
+        ctx.heads = heads
         return out
 
     @staticmethod
@@ -491,38 +512,47 @@ class _IncidenceAggr(torch.autograd.Function):
         gx = gv = ge = None
         if need_x or need_v2e:
             G = torch.empty((M, F), dtype=torch.float32, device=g.device) if need_v2e else None
-            gx = plan.aggregate_incidence(csrptr_t, indices_t, P, e2v, v2e, degE, None, W, xe_out=G)
+            gx = plan.aggregate_incidence(csrptr_t, indices_t, P, e2v, v2e, degE, None, W, xe_out=G, heads=ctx.heads)
             if need_v2e:
-                gv = plan.incidence_dot(csrptr_t, indices_t, X, G)
+                gv = plan.incidence_dot(csrptr_t, indices_t, X, G, heads=ctx.heads)
         if need_e2v:
-            ge = plan.incidence_dot(csrptr_t, indices_t, P, Xe)
-        return None, None, gx if need_x else None, gv, ge, None, None, None
+            ge = plan.incidence_dot(csrptr_t, indices_t, P, Xe, heads=ctx.heads)
+        return None, None, gx if need_x else None, gv, ge, None, None, None, None
 
 
 def incidence_aggr(csrptr_t, indices_t, node_feat, v2e_weight=None, e2v_weight=None, degE=None, degV=None, W=None,
-                   options=None):
+                   options=None, heads=1):
     """Y[v] = degV[v] * sum_{p=(e,v)} e2v[p] * (degE[e] * W[e] * sum_{p'=(e,u)} v2e[p'] * X[u]): the sum aggregation with a
     weight per (vertex, hyperedge) incidence, e.g. a probabilistic H or hypergraph attention's coefficients
     (include/hg_aggr.h, hg_aggr_incidence_f32).  v2e_weight / e2v_weight: float32 [nnz], aligned with indices_t, or None
     (unit weights); the same tensor twice for a symmetric weighting.  Gradients are exact for node_feat and both weight
     arrays -- the reference has no rule for this operator, so Options.backward does not apply; degE / degV / W get none.
     Options.variant 'auto' and 'pull' run (both are the pull kernels); 'fused', 'push_atomic', 'push_groups' raise
-    ValueError.  float32 only (TypeError for bfloat16)."""
+    ValueError.  float32 only (TypeError for bfloat16).
+    heads = H > 1: one call for H attention heads.  node_feat is [N, H * C] and head h owns columns h C .. (h + 1) C - 1;
+    the weights are [nnz, H] (nnz * H elements, head fastest) and column h weighs head h's columns; their gradients come
+    back [nnz, H].  F % H != 0 raises ValueError.  heads = 1 is the call above, unchanged."""
     opt = _opt(options)
-    v2e, e2v = (_flat(t) if isinstance(t, torch.Tensor) else t for t in (v2e_weight, e2v_weight))
-    _incidence_args(csrptr_t, indices_t, node_feat, v2e, e2v, opt)
+    if heads == 1:
+        v2e, e2v = (_flat(t) if isinstance(t, torch.Tensor) else t for t in (v2e_weight, e2v_weight))
+    else:
+        _heads(heads)
+        v2e, e2v = (_per_head(t, heads) if isinstance(t, torch.Tensor) else t for t in (v2e_weight, e2v_weight))
+    _incidence_args(csrptr_t, indices_t, node_feat, v2e, e2v, opt, heads)
     degE, degV, W = _flat(degE), _flat(degV), _flat(W)
     if not (torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad
                                             for t in (node_feat, v2e, e2v))):
         plan = cached_plan(node_feat.shape[0], csrptr_t, indices_t)
-        return plan.aggregate_incidence(csrptr_t, indices_t, node_feat, v2e, e2v, degE, degV, W)
-    return _IncidenceAggr.apply(csrptr_t, indices_t, node_feat, v2e, e2v, degE, degV, W)
+        return plan.aggregate_incidence(csrptr_t, indices_t, node_feat, v2e, e2v, degE, degV, W, heads=heads)
+    if heads == 1:
+        return _IncidenceAggr.apply(csrptr_t, indices_t, node_feat, v2e, e2v, degE, degV, W)
+    return _IncidenceAggr.apply(csrptr_t, indices_t, node_feat, v2e, e2v, degE, degV, W, heads)
 
 
-def HGNNAggrIncidence(hyperg, in_feat, v2e_weight, e2v_weight, degE, degV, Wdiag, options=None):
+def HGNNAggrIncidence(hyperg, in_feat, v2e_weight, e2v_weight, degE, degV, Wdiag, options=None, heads=1):
     """HGNNAggr with a weight per incidence (incidence_aggr) on a HyperGraph's H_T tensors."""
     return incidence_aggr(hyperg.H_T_csrptr, hyperg.H_T_colind, in_feat, v2e_weight, e2v_weight, degE, degV, Wdiag,
-                          options=options)
+                          options=options, heads=heads)
 
 
 # ---- hypergraph attention coefficients (include/hg_aggr.h, hg_incidence_attention_f32) --------------------------------
@@ -530,12 +560,13 @@ def HGNNAggrIncidence(hyperg, in_feat, v2e_weight, e2v_weight, degE, degV, Wdiag
 _GROUPS = ("hyperedge", "vertex")
 
 
-def _segment_args(what, csrptr_t, indices_t, floats, lengths, group, opt):
+def _segment_args(what, csrptr_t, indices_t, floats, lengths, group, opt, heads=1):
     """Argument checks of incidence_softmax / incidence_sum in _incidence_args' order: every refusal is decided before a
     device is touched.  floats: (name, tensor or None) pairs; lengths: the element count each must have."""
     if opt is not None and opt.variant not in ("auto", "pull"):
         raise ValueError("%s runs the atomic-free segment kernels: variant must be 'auto' or 'pull', got %r"
                          % (what, opt.variant))
+    _heads(heads)
     if group not in _GROUPS:
         raise ValueError("group / side must be 'hyperedge' or 'vertex', got %r" % (group,))
     for name, t in floats:
@@ -559,11 +590,11 @@ class _IncidenceSoftmax(torch.autograd.Function):
     ds = alpha (dalpha - sum_g alpha dalpha) leaky', dsv / dse = its sums over each vertex's / hyperedge's incidences."""
 
     @staticmethod
-    def forward(ctx, csrptr_t, indices_t, sv, se, N, group, slope):
+    def forward(ctx, csrptr_t, indices_t, sv, se, N, group, slope, heads=1):
         plan = cached_plan(N, csrptr_t, indices_t)
-        alpha = plan.incidence_attention(csrptr_t, indices_t, sv, se, group, slope)
+        alpha = plan.incidence_attention(csrptr_t, indices_t, sv, se, group, slope, heads=heads)
         ctx.save_for_backward(csrptr_t, indices_t, sv, se, alpha)
-        ctx.N, ctx.group, ctx.slope = N, group, slope
+        ctx.N, ctx.group, ctx.slope, ctx.heads = N, group, slope, heads
         return alpha
 
     @staticmethod
@@ -573,63 +604,81 @@ class _IncidenceSoftmax(torch.autograd.Function):
         need_sv = sv is not None and ctx.needs_input_grad[2]
         need_se = se is not None and ctx.needs_input_grad[3]
         _, dsv, dse = plan.incidence_attention_backward(csrptr_t, indices_t, alpha, dalpha.contiguous(), sv, se, ctx.group,
-                                                        ctx.slope, need_sv=need_sv, need_se=need_se)
-        return None, None, dsv, dse, None, None, None
+                                                        ctx.slope, need_sv=need_sv, need_se=need_se, heads=ctx.heads)
+        return None, None, dsv, dse, None, None, None, None
 
 
 def incidence_softmax(csrptr_t, indices_t, node_score=None, edge_score=None, group="hyperedge", negative_slope=0.2,
-                      options=None, num_nodes=None):
+                      options=None, num_nodes=None, heads=1):
     """Hypergraph attention's coefficients, alpha [nnz] aligned with indices_t: for every incidence p = (e, u)
     alpha[p] = softmax over p's group of leaky_relu(node_score[u] + edge_score[e], negative_slope); the group is p's
     hyperedge (group='hyperedge': the coefficients of a hyperedge's members sum to 1) or p's vertex (group='vertex').
     node_score [N] / edge_score [M]: float32, either may be None (0).  The result is what incidence_aggr takes as
     v2e_weight / e2v_weight.  Gradients are exact for both score vectors.  num_nodes: N; required when node_score is
-    None, otherwise optional (node_score's length is taken as N; given, node_score must have that length).  Options.variant 'auto' and 'pull' run; the others raise ValueError.  float32 only (TypeError for bfloat16)."""
+    None, otherwise optional (node_score's length is taken as N; given, node_score must have that length).  Options.variant 'auto' and 'pull' run; the others raise ValueError.  float32 only (TypeError for bfloat16).
+    heads = H > 1: a softmax per head in one call.  node_score holds N * H and edge_score M * H elements ([N, H] / [M, H],
+    head fastest), alpha comes back [nnz, H]; N is taken as node_score's element count / H.  heads = 1 is the call above,
+    unchanged."""
     opt = _opt(options)
-    sv, se = (_flat(t) if isinstance(t, torch.Tensor) else t for t in (node_score, edge_score))
+    if heads == 1:
+        sv, se = (_flat(t) if isinstance(t, torch.Tensor) else t for t in (node_score, edge_score))
+    else:
+        _heads(heads)
+        sv, se = (_per_head(t, heads) if isinstance(t, torch.Tensor) else t for t in (node_score, edge_score))
     if sv is None and num_nodes is None:
         raise ValueError("incidence_softmax needs node_score or num_nodes (the number of vertices)")
-    N = int(num_nodes) if num_nodes is not None else sv.numel()
+    N = int(num_nodes) if num_nodes is not None else sv.numel() // heads
     M = csrptr_t.numel() - 1 if isinstance(csrptr_t, torch.Tensor) else 0
-    _segment_args("incidence_softmax", csrptr_t, indices_t, (("node_score", sv), ("edge_score", se)), (N, M), group, opt)
+    _segment_args("incidence_softmax", csrptr_t, indices_t, (("node_score", sv), ("edge_score", se)),
+                  (N * heads, M * heads), group, opt, heads)
     slope = float(negative_slope)
     if not (torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (sv, se))):
-        return cached_plan(N, csrptr_t, indices_t).incidence_attention(csrptr_t, indices_t, sv, se, group, slope)
-    return _IncidenceSoftmax.apply(csrptr_t, indices_t, sv, se, N, group, slope)
+        return cached_plan(N, csrptr_t, indices_t).incidence_attention(csrptr_t, indices_t, sv, se, group, slope,
+                                                                       heads=heads)
+    if heads == 1:
+        return _IncidenceSoftmax.apply(csrptr_t, indices_t, sv, se, N, group, slope)
+    return _IncidenceSoftmax.apply(csrptr_t, indices_t, sv, se, N, group, slope, heads)
 
 
 class _IncidenceSum(torch.autograd.Function):
     """out[g] = sum of val over group g; the backward is the gather dout[group(p)] on the plan's cached segment ids."""
 
     @staticmethod
-    def forward(ctx, csrptr_t, indices_t, val, N, side):
+    def forward(ctx, csrptr_t, indices_t, val, N, side, heads=1):
         plan = cached_plan(N, csrptr_t, indices_t)
         ctx.save_for_backward(csrptr_t, indices_t)
         ctx.N, ctx.side = N, side
-        return plan.incidence_sum(csrptr_t, indices_t, val, side)
+        return plan.incidence_sum(csrptr_t, indices_t, val, side, heads=heads)
 
     @staticmethod
-    def backward(ctx, dout):
+    def backward(ctx, dout):  # heads: dout [groups, H] -> [nnz, H], the same row gather
         csrptr_t, indices_t = ctx.saved_tensors
         plan = cached_plan(ctx.N, csrptr_t, indices_t)
-        return None, None, dout[plan.segment_ids(csrptr_t, indices_t, ctx.side)], None, None
+        return None, None, dout[plan.segment_ids(csrptr_t, indices_t, ctx.side)], None, None, None
 
 
-def incidence_sum(csrptr_t, indices_t, val, side="hyperedge", num_nodes=None):
+def incidence_sum(csrptr_t, indices_t, val, side="hyperedge", num_nodes=None, heads=1):
     """Segment sums of a value per incidence (float32 [nnz], aligned with indices_t): out[e] = sum over hyperedge e's
     members (side='hyperedge', [M]) or out[v] = sum over vertex v's hyperedges (side='vertex', [N]) -- e.g. the weighted
     degrees of a probabilistic H.  Deterministic, no atomics (hg_incidence_sum_f32); differentiable in val.  num_nodes: N;
     without it N is taken as the largest member id + 1 (read back from the device on every call, and vertices beyond it,
-    which are in no hyperedge, get no row) -- pass it."""
-    v = _flat(val) if isinstance(val, torch.Tensor) else val
+    which are in no hyperedge, get no row) -- pass it.  heads = H > 1: val holds nnz * H elements ([nnz, H], head
+    fastest) and the sums come back [M, H] / [N, H], one column per head; heads = 1 is the call above, unchanged."""
+    if heads == 1:
+        v = _flat(val) if isinstance(val, torch.Tensor) else val
+    else:
+        _heads(heads)
+        v = _per_head(val, heads) if isinstance(val, torch.Tensor) else val
     nnz = indices_t.numel() if isinstance(indices_t, torch.Tensor) else 0
-    _segment_args("incidence_sum", csrptr_t, indices_t, (("val", v),), (nnz,), side, None)
+    _segment_args("incidence_sum", csrptr_t, indices_t, (("val", v),), (nnz * heads,), side, None, heads)
     if v is None:
         raise TypeError("val must be a float32 tensor")
     N = int(num_nodes) if num_nodes is not None else (int(indices_t.max()) + 1 if nnz else 0)
     if not (torch.is_grad_enabled() and v.requires_grad):
-        return cached_plan(N, csrptr_t, indices_t).incidence_sum(csrptr_t, indices_t, v, side)
-    return _IncidenceSum.apply(csrptr_t, indices_t, v, N, side)
+        return cached_plan(N, csrptr_t, indices_t).incidence_sum(csrptr_t, indices_t, v, side, heads=heads)
+    if heads == 1:
+        return _IncidenceSum.apply(csrptr_t, indices_t, v, N, side)
+    return _IncidenceSum.apply(csrptr_t, indices_t, v, N, side, heads)
 
 
 # ---- module `hgnnaggr` (hgnnaggr.cc:122-151) ---------------------------------

@@ -420,16 +420,20 @@ class Plan:
         return int(_lib.lib().hg_aggr_incidence_workspace_bytes(self._h, F))
 
     def aggregate_incidence(self, csrptr_t, colind_t, X, v2e=None, e2v=None, degE=None, degV=None, W=None,
-                            xe_out=None, out=None, workspace=None):
+                            xe_out=None, out=None, workspace=None, heads=1):
         """Y = degV . H_e2v (degE . W . (H_v2e^T X)) with a weight per incidence (hg_aggr_incidence_f32): v2e / e2v are
         float32 [nnz] aligned with colind_t, or None (unit weights).  xe_out ([M, F] float32) receives hop 1's table.
+        heads = H > 1 (hg_aggr_incidence_heads_f32): v2e / e2v are [nnz, H] and head h weighs columns h F/H .. (h+1) F/H - 1.
         The first call with e2v builds and uploads the plan's permutation: not capturable (make one call before a
         hipGraph capture)."""
+        heads = _heads(heads)
         _check_feat(X, "node_feat")
         if X.dim() != 2 or X.shape[0] != self.N:
             raise ValueError("node_feat must be [N = %d, F]" % self.N)
         F = X.shape[1]
-        for name, t, n in (("v2e", v2e, self.nnz), ("e2v", e2v, self.nnz), ("degE", degE, self.M),
+        if F % heads:
+            raise ValueError("F = %d is no multiple of heads = %d" % (F, heads))
+        for name, t, n in (("v2e", v2e, self.nnz * heads), ("e2v", e2v, self.nnz * heads), ("degE", degE, self.M),
                            ("degV", degV, self.N), ("W", W, self.M)):
             if t is not None:
                 _check_feat(t, name, device=X.device)
@@ -447,26 +451,40 @@ class Plan:
         else:
             nbytes = workspace.numel() * workspace.element_size()
         with torch.cuda.device(X.device):
-            _lib.check(_lib.lib().hg_aggr_incidence_f32(
-                self._h, F, _ptr(csrptr_t), _ptr(colind_t), _ptr(X), _ptr(v2e), _ptr(e2v), _ptr(degE), _ptr(degV),
-                _ptr(W), _ptr(xe_out), _ptr(Y), _ptr(workspace), nbytes, _stream_handle(X.device)))
+            if heads == 1:
+                _lib.check(_lib.lib().hg_aggr_incidence_f32(
+                    self._h, F, _ptr(csrptr_t), _ptr(colind_t), _ptr(X), _ptr(v2e), _ptr(e2v), _ptr(degE), _ptr(degV),
+                    _ptr(W), _ptr(xe_out), _ptr(Y), _ptr(workspace), nbytes, _stream_handle(X.device)))
+            else:
+                _lib.check(_lib.lib().hg_aggr_incidence_heads_f32(
+                    self._h, F, heads, _ptr(csrptr_t), _ptr(colind_t), _ptr(X), _ptr(v2e), _ptr(e2v), _ptr(degE),
+                    _ptr(degV), _ptr(W), _ptr(xe_out), _ptr(Y), _ptr(workspace), nbytes, _stream_handle(X.device)))
         return Y
 
-    def incidence_dot(self, csrptr_t, colind_t, A, B, out=None):
-        """out[p] = <A[u], B[e]> for every H_T entry p = (e, u) (hg_incidence_dot_f32): A [N, F], B [M, F]."""
+    def incidence_dot(self, csrptr_t, colind_t, A, B, out=None, heads=1):
+        """out[p] = <A[u], B[e]> for every H_T entry p = (e, u) (hg_incidence_dot_f32): A [N, F], B [M, F].  heads = H > 1
+        (hg_incidence_dot_heads_f32): out [nnz, H], out[p, h] the product over head h's columns h F/H .. (h+1) F/H - 1."""
+        heads = _heads(heads)
         _check_feat(A, "A")
         _check_feat(B, "B", device=A.device)
         if A.dim() != 2 or B.dim() != 2 or A.shape[0] != self.N or B.shape[0] != self.M or A.shape[1] != B.shape[1]:
             raise ValueError("A must be [N = %d, F] and B [M = %d, F]" % (self.N, self.M))
+        if A.shape[1] % heads:
+            raise ValueError("F = %d is no multiple of heads = %d" % (A.shape[1], heads))
         if out is None:
-            out = torch.empty(self.nnz, dtype=torch.float32, device=A.device)
+            out = torch.empty(_per_head(self.nnz, heads), dtype=torch.float32, device=A.device)
         else:
             _check_feat(out, "out", device=A.device)
-            if out.numel() != self.nnz:
-                raise ValueError("out must have nnz = %d elements" % self.nnz)
+            if out.numel() != self.nnz * heads:
+                raise ValueError("out must have nnz * heads = %d elements" % (self.nnz * heads))
         with torch.cuda.device(A.device):
-            _lib.check(_lib.lib().hg_incidence_dot_f32(self._h, A.shape[1], _ptr(csrptr_t), _ptr(colind_t), _ptr(A),
-                                                       _ptr(B), _ptr(out), _stream_handle(A.device)))
+            if heads == 1:
+                _lib.check(_lib.lib().hg_incidence_dot_f32(self._h, A.shape[1], _ptr(csrptr_t), _ptr(colind_t), _ptr(A),
+                                                           _ptr(B), _ptr(out), _stream_handle(A.device)))
+            else:
+                _lib.check(_lib.lib().hg_incidence_dot_heads_f32(self._h, A.shape[1], heads, _ptr(csrptr_t),
+                                                                 _ptr(colind_t), _ptr(A), _ptr(B), _ptr(out),
+                                                                 _stream_handle(A.device)))
         return out
 
     def segment_info(self, side):
@@ -480,8 +498,8 @@ class Plan:
         _lib.check(_lib.lib().hg_plan_get_segment_info(self._h, side, info, rows.ctypes.data_as(ctypes.c_void_p)))
         return {"width": info[0], "keep": info[1], "long": info[2], "long_rows": rows}
 
-    def _scores(self, sv, se, device=None):
-        for name, t, n in (("node_score", sv, self.N), ("edge_score", se, self.M)):
+    def _scores(self, sv, se, device=None, heads=1):
+        for name, t, n in (("node_score", sv, self.N * heads), ("edge_score", se, self.M * heads)):
             if t is not None:
                 _check_feat(t, name, device=device)
                 device = t.device
@@ -489,66 +507,88 @@ class Plan:
                     raise ValueError("%s must have %d elements, got %d" % (name, n, t.numel()))
         return device
 
-    def incidence_attention(self, csrptr_t, colind_t, sv=None, se=None, group="hyperedge", slope=0.2, out=None):
+    def incidence_attention(self, csrptr_t, colind_t, sv=None, se=None, group="hyperedge", slope=0.2, out=None, heads=1):
         """alpha [nnz] in H_T order: the softmax over each hyperedge's members (group 'hyperedge') or each vertex's
         hyperedges ('vertex') of leaky_relu(sv[u] + se[e], slope) (hg_incidence_attention_f32).  sv [N], se [M]: float32,
-        or None (0).  The first call of a form builds and uploads what it needs from the plan: not capturable."""
+        or None (0).  heads = H > 1 (hg_incidence_attention_heads_f32): sv [N, H], se [M, H], alpha [nnz, H], a softmax
+        per head.  The first call of a form builds and uploads what it needs from the plan: not capturable."""
+        heads = _heads(heads)
         group = _side(group)
         _check_index(csrptr_t, "csrptr_t")
         _check_index(colind_t, "indices_t")
-        device = self._scores(sv, se, csrptr_t.device)
+        device = self._scores(sv, se, csrptr_t.device, heads)
         if out is None:
-            out = torch.empty(self.nnz, dtype=torch.float32, device=device)
+            out = torch.empty(_per_head(self.nnz, heads), dtype=torch.float32, device=device)
         else:
             _check_feat(out, "out", device=device)
-            if out.numel() != self.nnz:
-                raise ValueError("out must have nnz = %d elements" % self.nnz)
+            if out.numel() != self.nnz * heads:
+                raise ValueError("out must have nnz * heads = %d elements" % (self.nnz * heads))
         with torch.cuda.device(device):
-            _lib.check(_lib.lib().hg_incidence_attention_f32(self._h, group, _ptr(csrptr_t), _ptr(colind_t), _ptr(sv),
-                                                             _ptr(se), float(slope), _ptr(out), _stream_handle(device)))
+            if heads == 1:
+                _lib.check(_lib.lib().hg_incidence_attention_f32(self._h, group, _ptr(csrptr_t), _ptr(colind_t), _ptr(sv),
+                                                                 _ptr(se), float(slope), _ptr(out), _stream_handle(device)))
+            else:
+                _lib.check(_lib.lib().hg_incidence_attention_heads_f32(
+                    self._h, group, heads, _ptr(csrptr_t), _ptr(colind_t), _ptr(sv), _ptr(se), float(slope), _ptr(out),
+                    _stream_handle(device)))
         return out
 
     def incidence_attention_backward(self, csrptr_t, colind_t, alpha, dalpha, sv=None, se=None, group="hyperedge",
-                                     slope=0.2, need_sv=True, need_se=True):
+                                     slope=0.2, need_sv=True, need_se=True, heads=1):
         """(ds [nnz], dsv [N] or None, dse [M] or None) for alpha = incidence_attention(...) and its gradient dalpha
-        (hg_incidence_attention_bwd_f32); sv / se as in the forward (they decide the leaky branch)."""
+        (hg_incidence_attention_bwd_f32); sv / se as in the forward (they decide the leaky branch).  heads = H > 1
+        (hg_incidence_attention_heads_bwd_f32): every array has a trailing dimension H."""
+        heads = _heads(heads)
         group = _side(group)
         _check_index(csrptr_t, "csrptr_t")
         _check_index(colind_t, "indices_t")
         _check_feat(alpha, "alpha")
         _check_feat(dalpha, "dalpha", device=alpha.device)
         for name, t in (("alpha", alpha), ("dalpha", dalpha)):
-            if t.numel() != self.nnz:
-                raise ValueError("%s must have nnz = %d elements, got %d" % (name, self.nnz, t.numel()))
-        device = self._scores(sv, se, alpha.device)
-        ds = torch.empty(self.nnz, dtype=torch.float32, device=device)
-        dsv = torch.empty(self.N, dtype=torch.float32, device=device) if need_sv else None
-        dse = torch.empty(self.M, dtype=torch.float32, device=device) if need_se else None
+            if t.numel() != self.nnz * heads:
+                raise ValueError("%s must have nnz%s = %d elements, got %d" % (name, " * heads" if heads > 1 else "",
+                                                                              self.nnz * heads, t.numel()))
+        device = self._scores(sv, se, alpha.device, heads)
+        ds = torch.empty(_per_head(self.nnz, heads), dtype=torch.float32, device=device)
+        dsv = torch.empty(_per_head(self.N, heads), dtype=torch.float32, device=device) if need_sv else None
+        dse = torch.empty(_per_head(self.M, heads), dtype=torch.float32, device=device) if need_se else None
         with torch.cuda.device(device):
-            _lib.check(_lib.lib().hg_incidence_attention_bwd_f32(
-                self._h, group, _ptr(csrptr_t), _ptr(colind_t), _ptr(sv), _ptr(se), float(slope), _ptr(alpha),
-                _ptr(dalpha), _ptr(ds), _ptr(dsv), _ptr(dse), _stream_handle(device)))
+            if heads == 1:
+                _lib.check(_lib.lib().hg_incidence_attention_bwd_f32(
+                    self._h, group, _ptr(csrptr_t), _ptr(colind_t), _ptr(sv), _ptr(se), float(slope), _ptr(alpha),
+                    _ptr(dalpha), _ptr(ds), _ptr(dsv), _ptr(dse), _stream_handle(device)))
+            else:
+                _lib.check(_lib.lib().hg_incidence_attention_heads_bwd_f32(
+                    self._h, group, heads, _ptr(csrptr_t), _ptr(colind_t), _ptr(sv), _ptr(se), float(slope), _ptr(alpha),
+                    _ptr(dalpha), _ptr(ds), _ptr(dsv), _ptr(dse), _stream_handle(device)))
         return ds, dsv, dse
 
-    def incidence_sum(self, csrptr_t, colind_t, val, side="hyperedge", out=None):
+    def incidence_sum(self, csrptr_t, colind_t, val, side="hyperedge", out=None, heads=1):
         """out[e] = sum of val over hyperedge e's incidences (side 'hyperedge', [M]) or out[v] = sum over vertex v's
-        (side 'vertex', [N]); val float32 [nnz] in H_T order (hg_incidence_sum_f32).  Deterministic, no atomics."""
+        (side 'vertex', [N]); val float32 [nnz] in H_T order (hg_incidence_sum_f32).  heads = H > 1
+        (hg_incidence_sum_heads_f32): val [nnz, H], out [M, H] / [N, H].  Deterministic, no atomics."""
+        heads = _heads(heads)
         side = _side(side)
         _check_index(csrptr_t, "csrptr_t")
         _check_index(colind_t, "indices_t")
         _check_feat(val, "val", device=csrptr_t.device)
-        if val.numel() != self.nnz:
-            raise ValueError("val must have nnz = %d elements, got %d" % (self.nnz, val.numel()))
+        if val.numel() != self.nnz * heads:
+            raise ValueError("val must have nnz%s = %d elements, got %d" % (" * heads" if heads > 1 else "",
+                                                                            self.nnz * heads, val.numel()))
         n = self.M if side == 0 else self.N
         if out is None:
-            out = torch.empty(n, dtype=torch.float32, device=val.device)
+            out = torch.empty(_per_head(n, heads), dtype=torch.float32, device=val.device)
         else:
             _check_feat(out, "out", device=val.device)
-            if out.numel() != n:
-                raise ValueError("out must have %d elements" % n)
+            if out.numel() != n * heads:
+                raise ValueError("out must have %d elements" % (n * heads))
         with torch.cuda.device(val.device):
-            _lib.check(_lib.lib().hg_incidence_sum_f32(self._h, side, _ptr(csrptr_t), _ptr(colind_t), _ptr(val), _ptr(out),
-                                                       _stream_handle(val.device)))
+            if heads == 1:
+                _lib.check(_lib.lib().hg_incidence_sum_f32(self._h, side, _ptr(csrptr_t), _ptr(colind_t), _ptr(val),
+                                                           _ptr(out), _stream_handle(val.device)))
+            else:
+                _lib.check(_lib.lib().hg_incidence_sum_heads_f32(self._h, side, heads, _ptr(csrptr_t), _ptr(colind_t),
+                                                                 _ptr(val), _ptr(out), _stream_handle(val.device)))
         return out
 
     def segment_ids(self, csrptr_t, colind_t, side):
@@ -576,6 +616,18 @@ def _side(side):
     if side not in SIDES:
         raise ValueError("group / side must be 'hyperedge' or 'vertex', got %r" % (side,))
     return SIDES[side]
+
+
+def _heads(heads):
+    """The `heads` argument as an int >= 1 (ValueError otherwise; decided before any tensor is looked at)."""
+    if isinstance(heads, bool) or not isinstance(heads, int) or heads < 1:
+        raise ValueError("heads must be an integer >= 1, got %r" % (heads,))
+    return heads
+
+
+def _per_head(n, heads):
+    """Shape of a per-item array: [n] for a single head (today's layout), [n, heads] otherwise."""
+    return (n,) if heads == 1 else (n, heads)
 
 
 def linear_supported(F_in, F_out):

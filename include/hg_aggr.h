@@ -449,6 +449,47 @@ HG_API int hg_incidence_sum_f32(const hg_plan *plan, int32_t side, const int32_t
                                 const float *val, float *out, hg_stream_t stream);
 HG_API int hg_plan_get_segment_info(const hg_plan *plan, int32_t side, int32_t *info, int32_t *long_seg_host);
 
+/* ---- several heads ---------------------------------------------------------------------------------------------------
+ * The incidence path with `heads` = H attention heads in one call each, fp32.  Layout everywhere: the head is the fastest
+ * index.  Scores are [N, H] / [M, H]; everything per incidence (alpha, dalpha, ds, val, v2e_val, e2v_val, the dot's out) is
+ * [nnz, H], row p aligned with colind_t[p]; feature rows are F = H * C wide and head h owns columns h * C .. (h + 1) * C - 1.
+ * heads = 1 is the single-head layout and runs the single-head entry's code: the same bits.
+ * hg_incidence_attention_heads_f32 / _bwd_f32 / hg_incidence_sum_heads_f32: for every head h the contract of the single-head
+ *   entry on column h of the score and entry arrays (dsv_out [N, H], dse_out [M, H], out [M, H] or [N, H]).  A lane group
+ *   (above 128 entries: a workgroup) reduces one (group, head) pair in the single-head order, which depends on the group's
+ *   length and the side's lane-group width, not on H: column h of a result has the bits of the single-head call on the
+ *   contiguous column h of the inputs.  No atomics; one launch per body.
+ * hg_aggr_incidence_heads_f32: hg_aggr_incidence_f32 with a weight per incidence and head,
+ *     Xe[e, c] = ((sum_{p=(e,u)} v2e[p, c / C] * X[u, c]) * degE[e]) * W[e],   Y[v, c] = (sum_{p=(e,v)} e2v[p, c / C] * Xe[e, c]) * degV[v]
+ *   on the same schedule, walk and fma order: the columns of head h equal, bit for bit, those of the single-head call of
+ *   the same F with v2e_val = v2e[:, h], e2v_val = e2v[:, h].  Lanes are 16 bytes wide where the single-head call's are and
+ *   C % 4 == 0 (a lane must lie inside one head), else 4 bytes.  Workspace: hg_aggr_incidence_workspace_bytes(plan, F).
+ *   The weights are read from global memory where they lie (4 H contiguous bytes per incidence), not staged, so the LDS
+ *   need does not depend on H: HG_ERR_UNSUPPORTED exactly where hg_aggr_incidence_f32 returns it.
+ * hg_incidence_dot_heads_f32: out[p, h] = <A[u, hC .. (h+1)C), B[e, hC .. (h+1)C)> for every H_T entry p = (e, u), out
+ *   [nnz, H]; each output is reduced by the lanes of its own head in a fixed order.
+ * Limits: any 1 <= heads with F % heads == 0 (there is no upper limit short of nnz * heads < 2^40).  Refusals, nothing
+ *   launched, message through hg_last_error: HG_ERR_INVALID for heads < 1 or F % heads != 0; HG_ERR_UNSUPPORTED for a plan
+ *   built with HG_PLAN_HOST_ONLY; otherwise the single-head entries' rules.  The first-call-allocates rule is theirs too;
+ *   the permutation and the long-row lists are shared with the single-head calls.
+ * Detect these entries by their exported symbols (HG_AGGR_VERSION does not change). */
+HG_API int hg_incidence_attention_heads_f32(const hg_plan *plan, int32_t group, int32_t heads, const int32_t *csrptr_t,
+                                            const int32_t *colind_t, const float *sv, const float *se, float slope,
+                                            float *alpha_out, hg_stream_t stream);
+HG_API int hg_incidence_attention_heads_bwd_f32(const hg_plan *plan, int32_t group, int32_t heads, const int32_t *csrptr_t,
+                                                const int32_t *colind_t, const float *sv, const float *se, float slope,
+                                                const float *alpha, const float *dalpha, float *ds_out, float *dsv_out,
+                                                float *dse_out, hg_stream_t stream);
+HG_API int hg_incidence_sum_heads_f32(const hg_plan *plan, int32_t side, int32_t heads, const int32_t *csrptr_t,
+                                      const int32_t *colind_t, const float *val, float *out, hg_stream_t stream);
+HG_API int hg_aggr_incidence_heads_f32(const hg_plan *plan, int32_t F, int32_t heads, const int32_t *csrptr_t,
+                                       const int32_t *colind_t, const float *X, const float *v2e_val, const float *e2v_val,
+                                       const float *degE, const float *degV, const float *W, float *Xe_out, float *Y,
+                                       void *workspace, size_t workspace_bytes, hg_stream_t stream);
+HG_API int hg_incidence_dot_heads_f32(const hg_plan *plan, int32_t F, int32_t heads, const int32_t *csrptr_t,
+                                      const int32_t *colind_t, const float *A, const float *B, float *out,
+                                      hg_stream_t stream);
+
 /* first_aggr = "max" pieces (hgnnaggr_max, source/hgnnaggr/hgnnaggr_cuda.cu:144-208).
  * hg_gather_max_f32: Xe[e,k] = (max_{u in e} X[u,k], start -1e5, strict >) * (degE[e]*W[e]),
  * record[e,k] = winning vertex (0 if none).  The second hop is hg_gather_rows_f32(hop = 1).
