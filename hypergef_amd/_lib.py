@@ -40,6 +40,7 @@ SYMBOLS = (
     "hg_incidence_attention_f32", "hg_incidence_attention_bwd_f32", "hg_incidence_sum_f32", "hg_plan_get_segment_info",
     "hg_incidence_attention_heads_f32", "hg_incidence_attention_heads_bwd_f32", "hg_incidence_sum_heads_f32",
     "hg_aggr_incidence_heads_f32", "hg_incidence_dot_heads_f32",
+    "hg_incidence_attention_dropout_heads_f32", "hg_incidence_attention_dropout_heads_bwd_f32", "hg_dropout_keep_host",
 )
 
 
@@ -207,6 +208,15 @@ def lib():
         L.hg_aggr_incidence_heads_f32.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]
         L.hg_incidence_dot_heads_f32.restype = ctypes.c_int
         L.hg_incidence_dot_heads_f32.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, vp]
+    if hasattr(L, "hg_incidence_attention_dropout_heads_f32"):  # likewise: + p_drop and the device address of the state
+        L.hg_incidence_attention_dropout_heads_f32.restype = ctypes.c_int
+        L.hg_incidence_attention_dropout_heads_f32.argtypes = [vp, i32, i32, vp, vp, vp, vp, ctypes.c_float, ctypes.c_float,
+                                                               vp, vp, vp, vp]
+        L.hg_incidence_attention_dropout_heads_bwd_f32.restype = ctypes.c_int
+        L.hg_incidence_attention_dropout_heads_bwd_f32.argtypes = [vp, i32, i32, vp, vp, vp, vp, ctypes.c_float,
+                                                                   ctypes.c_float, vp, vp, vp, vp, vp, vp, vp]
+        L.hg_dropout_keep_host.restype = ctypes.c_int
+        L.hg_dropout_keep_host.argtypes = [ctypes.c_uint64, ctypes.c_uint64, ctypes.c_float, i64, i32, vp]
     L.hg_aggr_push_groups_f32.restype = ctypes.c_int
     L.hg_aggr_push_groups_f32.argtypes = [i32, i32, i32, i64, vp, vp, vp, vp, vp, vp,
                                           vp, vp, vp, vp, vp, vp]

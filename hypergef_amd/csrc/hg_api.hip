@@ -10,6 +10,7 @@
 #include <string>
 
 #include "hg_attention.h"
+#include "hg_philox.h"
 #include "hg_kernels.h"
 
 namespace {
@@ -586,8 +587,10 @@ int check_segment_call(const char *who, const hg_plan *plan, int side, const int
 }
 
 // One launch of the segment kernels on `side`: fills the side's arrays of `a` (scores: sv [N], se [M]) and runs `body`.
+// drop: the dropout bodies' further arguments (kSegSoftmaxDrop / kSegSoftmaxDropBwd), null for the others.
 int run_segments(const char *who, const hg_plan *plan, int body, int side, const int32_t *csrptr_t, const int32_t *colind_t,
-                 const float *sv, const float *se, hg::SegArgs a, hipStream_t stream, int32_t heads = 1) {
+                 const float *sv, const float *se, hg::SegArgs a, hipStream_t stream, int32_t heads = 1,
+                 const hg::DropFields *drop = nullptr) {
   int rc;
   const int32_t *perm = nullptr;
   if (side == 1 && (rc = get_incidence_perm(plan, true, &perm)) != HG_OK) return rc;
@@ -600,7 +603,18 @@ int run_segments(const char *who, const hg_plan *plan, int body, int side, const
   a.own = side == 0 ? se : sv;
   a.other = side == 0 ? sv : se;
   hipError_t e;
-  if (heads > 1) {  // scores [*, heads], entry arrays [nnz, heads]
+  if (drop && heads > 1) {
+    hg::SegDropHeadsArgs ad;
+    static_cast<hg::SegArgs &>(ad) = a;
+    ad.heads = heads;
+    ad.drop = *drop;
+    e = hg::launch_segments_drop_heads(body, side, width, ad, stream);
+  } else if (drop) {
+    hg::SegDropArgs ad;
+    static_cast<hg::SegArgs &>(ad) = a;
+    ad.drop = *drop;
+    e = hg::launch_segments_drop(body, side, width, ad, stream);
+  } else if (heads > 1) {  // scores [*, heads], entry arrays [nnz, heads]
     hg::SegHeadsArgs ah;
     static_cast<hg::SegArgs &>(ah) = a;
     ah.heads = heads;
@@ -609,6 +623,22 @@ int run_segments(const char *who, const hg_plan *plan, int body, int side, const
     e = hg::launch_segments(body, side, width, a, stream);
   }
   if (e != hipSuccess) return hip_fail(who, e);
+  return HG_OK;
+}
+
+// Refusals of the dropout entries: p_drop in [0, 1) (NaN fails both comparisons) and the state's address; fills T and scale
+int check_dropout(const char *who, float p_drop, const uint64_t *rng_dev, hg::DropFields *d) {
+  if (!(p_drop >= 0.f && p_drop < 1.f)) {
+    hg::set_error(std::string(who) + ": p_drop must lie in [0, 1) (at 1 the scale 1 / (1 - p_drop) is infinite)");
+    return HG_ERR_INVALID;
+  }
+  if (!rng_dev || (reinterpret_cast<uintptr_t>(rng_dev) & 7) != 0) {
+    hg::set_error(std::string(who) + ": rng_dev is null or not 8-byte aligned");
+    return HG_ERR_INVALID;
+  }
+  d->rng = rng_dev;
+  d->T = hg::drop_threshold(p_drop);
+  d->scale = 1.0f / (1.0f - p_drop);
   return HG_OK;
 }
 
@@ -1811,6 +1841,77 @@ int hg_incidence_attention_heads_bwd_f32(const hg_plan *plan, int32_t group, int
   b.out_seg = other_out;
   return run_segments("incidence_attention_bwd sum launch", plan, hg::kSegSum, 1 - group, csrptr_t, colind_t, nullptr,
                       nullptr, b, s, heads);
+}
+
+// ---- attention dropout: the softmax and its backward with the mask of hg_philox.h fused in ---------------------------
+
+int hg_incidence_attention_dropout_heads_f32(const hg_plan *plan, int32_t group, int32_t heads, const int32_t *csrptr_t,
+                                             const int32_t *colind_t, const float *sv, const float *se, float slope,
+                                             float p_drop, const uint64_t *rng_dev, float *alpha_out,
+                                             float *alpha_drop_out, hg_stream_t stream) {
+  const char *who = "hg_incidence_attention_dropout_heads_f32";
+  int rc = check_heads(who, plan, heads, 0);
+  if (rc != HG_OK) return rc;
+  if ((rc = check_segment_call(who, plan, group, csrptr_t, colind_t)) != HG_OK) return rc;
+  hg::DropFields d = {};
+  if ((rc = check_dropout(who, p_drop, rng_dev, &d)) != HG_OK) return rc;
+  if (!alpha_out || !alpha_drop_out || !(slope == slope) || slope - slope != 0.f) {
+    hg::set_error(std::string(who) + ": null alpha_out / alpha_drop_out or non-finite slope");
+    return HG_ERR_INVALID;
+  }
+  if (plan->nnz == 0) return HG_OK;
+  hg::SegArgs a = {};
+  a.slope = slope;
+  a.out_entry = alpha_out;
+  d.out_drop = alpha_drop_out;
+  return run_segments("incidence_attention_dropout launch", plan, hg::kSegSoftmaxDrop, group, csrptr_t, colind_t, sv, se, a,
+                      static_cast<hipStream_t>(stream), heads, &d);
+}
+
+int hg_incidence_attention_dropout_heads_bwd_f32(const hg_plan *plan, int32_t group, int32_t heads,
+                                                 const int32_t *csrptr_t, const int32_t *colind_t, const float *sv,
+                                                 const float *se, float slope, float p_drop, const uint64_t *rng_dev,
+                                                 const float *alpha, const float *dout, float *ds_out, float *dsv_out,
+                                                 float *dse_out, hg_stream_t stream) {
+  const char *who = "hg_incidence_attention_dropout_heads_bwd_f32";
+  int rc = check_heads(who, plan, heads, 0);
+  if (rc != HG_OK) return rc;
+  if ((rc = check_segment_call(who, plan, group, csrptr_t, colind_t)) != HG_OK) return rc;
+  hg::DropFields d = {};
+  if ((rc = check_dropout(who, p_drop, rng_dev, &d)) != HG_OK) return rc;
+  if (!ds_out || (plan->nnz > 0 && (!alpha || !dout)) || !(slope == slope) || slope - slope != 0.f) {
+    hg::set_error(std::string(who) + ": null alpha / dout / ds_out or non-finite slope");
+    return HG_ERR_INVALID;
+  }
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  hg::SegArgs a = {};
+  a.slope = slope;
+  a.val = alpha;
+  a.dval = dout;
+  a.out_entry = ds_out;
+  a.out_seg = group == 0 ? dse_out : dsv_out;  // the group's own end: summed by the kernel that forms ds
+  rc = run_segments("incidence_attention_dropout_bwd launch", plan, hg::kSegSoftmaxDropBwd, group, csrptr_t, colind_t, sv, se,
+                    a, s, heads, &d);
+  if (rc != HG_OK) return rc;
+  float *other_out = group == 0 ? dsv_out : dse_out;  // the other end: the plain segment sum of ds over that side
+  if (!other_out) return HG_OK;
+  hg::SegArgs b = {};
+  b.val = ds_out;
+  b.out_seg = other_out;
+  return run_segments("incidence_attention_dropout_bwd sum launch", plan, hg::kSegSum, 1 - group, csrptr_t, colind_t,
+                      nullptr, nullptr, b, s, heads);
+}
+
+int hg_dropout_keep_host(uint64_t key, uint64_t sid, float p_drop, int64_t nnz, int32_t heads, uint8_t *keep_out) {
+  if (!(p_drop >= 0.f && p_drop < 1.f) || nnz < 0 || nnz > 0x7fffffff || heads < 1 || (nnz > 0 && !keep_out)) {
+    hg::set_error("hg_dropout_keep_host: p_drop outside [0, 1), nnz outside [0, 2^31), heads < 1 or null keep_out");
+    return HG_ERR_INVALID;
+  }
+  const hg::DropRng r = hg::drop_rng(key, sid);
+  const uint32_t T = hg::drop_threshold(p_drop);
+  for (int64_t p = 0; p < nnz; p++)
+    for (int32_t h = 0; h < heads; h++) keep_out[p * heads + h] = hg::drop_keep(r, T, (uint32_t)p, (uint32_t)h) ? 1 : 0;
+  return HG_OK;
 }
 
 int hg_incidence_sum_f32(const hg_plan *plan, int32_t side, const int32_t *csrptr_t, const int32_t *colind_t,

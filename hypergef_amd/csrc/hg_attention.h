@@ -12,7 +12,7 @@ constexpr int kSegBlock = 256;  // threads per workgroup: 256 / width lane group
 constexpr int kSegKeep = 4;     // entries per lane whose gathered values stay in registers across the passes
 constexpr int kSegLong = 128;   // segments of more entries leave the lane groups for a whole workgroup
 
-enum { kSegSoftmax = 0, kSegSoftmaxBwd = 1, kSegSum = 2 };
+enum { kSegSoftmax = 0, kSegSoftmaxBwd = 1, kSegSum = 2, kSegSoftmaxDrop = 3, kSegSoftmaxDropBwd = 4 };
 
 struct SegArgs {
   const int32_t *ptr;       // the side's CSR row pointers [nseg + 1]: csrptr_t, or the derived ptr_v
@@ -34,6 +34,22 @@ struct SegHeadsArgs : SegArgs {
   int32_t heads;
 };
 
+// What the two dropout bodies take beside the block of the body they extend.  The mask is a function of (rng, H_T
+// position, head) alone (hg_philox.h): kSegSoftmaxDrop writes alpha to out_entry as kSegSoftmax does and
+// keep ? alpha * scale : +0 to out_drop; kSegSoftmaxDropBwd runs kSegSoftmaxBwd on (val, keep ? dval * scale : +0).
+struct DropFields {
+  const uint64_t *rng;  // device memory, read when the kernel runs: {key, sid}
+  uint32_t T;           // an entry is kept where its Philox word >= T = floor(p_drop * 2^32)
+  float scale;          // 1 / (1 - p_drop), rounded once on the host
+  float *out_drop;      // kSegSoftmaxDrop: the dropped coefficients, H_T order; kSegSoftmaxDropBwd: unused
+};
+struct SegDropArgs : SegArgs {
+  DropFields drop;
+};
+struct SegDropHeadsArgs : SegHeadsArgs {
+  DropFields drop;
+};
+
 // Lane-group width of a side whose segments of at most kSegLong entries hold `mean` entries on average.
 int seg_width(double mean);
 // body: kSeg*; side 0 / 1; width 4 / 8 / 16 (seg_width)
@@ -41,5 +57,8 @@ hipError_t launch_segments(int body, int side, int width, const SegArgs &a, hipS
 // one lane group (or, for a long segment, one workgroup) per (segment, head): column h is reduced as launch_segments
 // reduces a single column
 hipError_t launch_segments_heads(int body, int side, int width, const SegHeadsArgs &a, hipStream_t stream);
+// body: kSegSoftmaxDrop / kSegSoftmaxDropBwd, the same cut of the work
+hipError_t launch_segments_drop(int body, int side, int width, const SegDropArgs &a, hipStream_t stream);
+hipError_t launch_segments_drop_heads(int body, int side, int width, const SegDropHeadsArgs &a, hipStream_t stream);
 
 }  // namespace hg

@@ -24,12 +24,21 @@
 // runs the single-head code on column h (Col<true>: element i of a column sits at i * H + h), so its order of reduction
 // is the single-head one -- it depends on the segment's length and W, not on H -- and column h of a result has the bits
 // of the single-head call on column h of the inputs.
+//
+// Dropout (kSegSoftmaxDrop / kSegSoftmaxDropBwd, segment_drop_kernel and its heads form).  The same two segment functions
+// with a Drop in place of NoDrop: the forward writes alpha as before and, beside it, keep ? alpha * scale : +0; the
+// backward masks and scales dalpha as it loads it and is the plain backward from there on.  keep is word 0 of
+// Philox4x32-10 on the counter (H_T position, head, sid) compared with a threshold (hg_philox.h): no mask is stored, both
+// sides and every width see the same one, and an entry beyond the kSegKeep kept ones recomputes it in each pass as it
+// gathers its score again.  The reductions are untouched, so alpha, t, ds and the sums have the bits of the plain bodies
+// on pre-masked input.  The instances above do not see any of this: NoDrop compiles to what was there.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
 #include <type_traits>
 
 #include "hg_attention.h"
+#include "hg_philox.h"
 
 namespace hg {
 namespace {
@@ -48,11 +57,13 @@ struct Col;
 template <>
 struct Col<false> {
   __device__ __forceinline__ int32_t operator()(int32_t i) const { return i; }
+  __device__ __forceinline__ uint32_t head() const { return 0; }
 };
 template <>
 struct Col<true> {
   int32_t H, h;
   __device__ __forceinline__ int64_t operator()(int32_t i) const { return (int64_t)i * H + h; }  // nnz * H may pass 2^31
+  __device__ __forceinline__ uint32_t head() const { return (uint32_t)h; }
 };
 
 // Combine one value per lane over the W lanes that share a segment; every lane gets the result.
@@ -86,11 +97,32 @@ __device__ __forceinline__ float raw_score(const SegArgs &a, Col<MH> col, float 
 
 __device__ __forceinline__ float leaky(float raw, float slope) { return raw > 0.f ? raw : slope * raw; }
 
+// The dropout of a launch as a lane holds it: the state read from device memory when the kernel runs (a seed passed by
+// value would be frozen into a captured launch), the threshold, the scale and the second output.
+struct NoDrop {};
+struct Drop {
+  DropRng rng;
+  uint32_t T;
+  float scale;
+  float *out;
+};
+__device__ __forceinline__ Drop load_drop(const DropFields &f) {
+  return Drop{drop_rng(f.rng[0], f.rng[1]), f.T, f.scale, f.out_drop};
+}
+// v as dropout leaves it at H_T position p of the column: fl(v * scale) where kept, else +0
+template <bool MH>
+__device__ __forceinline__ float dropped(const NoDrop &, Col<MH>, int32_t, float v) { return v; }
+template <bool MH>
+__device__ __forceinline__ float dropped(const Drop &d, Col<MH> col, int32_t p, float v) {
+  return drop_keep(d.rng, d.T, (uint32_t)p, col.head()) ? v * d.scale : 0.f;
+}
+
 // alpha = softmax over the segment of leaky(raw).  An empty segment runs no entry loop at all: nothing is written and no
 // exponential of (-inf) - (-inf) is formed.  A one-entry segment gives exp(0) / 1 = 1.0f exactly.
-template <int SIDE, int W, bool MH>
+template <int SIDE, int W, bool MH, typename DROP = NoDrop>
 __device__ __forceinline__ void softmax_segment(const SegArgs &a, Col<MH> col, int32_t seg, int32_t beg, int32_t end, int lane,
-                                                float *lds) {
+                                                float *lds, const DROP &d = DROP{}) {
+  constexpr bool kDrop = std::is_same_v<DROP, Drop>;
   const float own = (a.own && beg < end) ? a.own[col(seg)] : 0.f;
   float sc[kSegKeep];
   int32_t pos[kSegKeep];
@@ -122,17 +154,35 @@ __device__ __forceinline__ void softmax_segment(const SegArgs &a, Col<MH> col, i
   const float inv = 1.f / sum;  // the entry holding the maximum contributes exp(0) = 1: sum >= 1 wherever it is used
 #pragma unroll
   for (int k = 0; k < kSegKeep; k++)
-    if (beg + lane + k * W < end) a.out_entry[col(pos[k])] = sc[k] * inv;
+    if (beg + lane + k * W < end) {
+      if constexpr (kDrop) {  // the product that forms alpha is rounded first, then scaled
+        const float al = sc[k] * inv;
+        a.out_entry[col(pos[k])] = al;
+        d.out[col(pos[k])] = dropped(d, col, pos[k], al);
+      } else {
+        a.out_entry[col(pos[k])] = sc[k] * inv;
+      }
+    }
+  if constexpr (kDrop) {
+#pragma unroll 2
+    for (int32_t i = tail; i < end; i += W) {
+      const int32_t p = position<SIDE>(a, i);
+      const float al = __expf(leaky(raw_score(a, col, own, i), a.slope) - m) * inv;
+      a.out_entry[col(p)] = al;
+      d.out[col(p)] = dropped(d, col, p, al);
+    }
+  } else {
 #pragma unroll 4
-  for (int32_t i = tail; i < end; i += W)
-    a.out_entry[col(position<SIDE>(a, i))] = __expf(leaky(raw_score(a, col, own, i), a.slope) - m) * inv;
+    for (int32_t i = tail; i < end; i += W)
+      a.out_entry[col(position<SIDE>(a, i))] = __expf(leaky(raw_score(a, col, own, i), a.slope) - m) * inv;
+  }
 }
 
 // ds = alpha * (dalpha - t) * leaky'(raw), t = sum over the segment of alpha * dalpha; the segment's own sum of ds goes to
 // out_seg (0 for an empty segment).  slope == 1: the non-linearity is the identity and no score is gathered.
-template <int SIDE, int W, bool MH>
+template <int SIDE, int W, bool MH, typename DROP = NoDrop>
 __device__ __forceinline__ void softmax_bwd_segment(const SegArgs &a, Col<MH> col, int32_t seg, int32_t beg, int32_t end, int lane,
-                                                    float *lds, bool valid) {
+                                                    float *lds, bool valid, const DROP &d = DROP{}) {
   const bool need_raw = a.slope != 1.f;
   const float own = (need_raw && a.own && beg < end) ? a.own[col(seg)] : 0.f;
   float al[kSegKeep], da[kSegKeep], fac[kSegKeep];
@@ -144,7 +194,7 @@ __device__ __forceinline__ void softmax_bwd_segment(const SegArgs &a, Col<MH> co
     if (i < end) {
       pos[k] = position<SIDE>(a, i);
       al[k] = a.val[col(pos[k])];
-      da[k] = a.dval[col(pos[k])];
+      da[k] = dropped(d, col, pos[k], a.dval[col(pos[k])]);
       fac[k] = (need_raw && !(raw_score(a, col, own, i) > 0.f)) ? a.slope : 1.f;
       t += al[k] * da[k];
     }
@@ -153,25 +203,25 @@ __device__ __forceinline__ void softmax_bwd_segment(const SegArgs &a, Col<MH> co
 #pragma unroll 4
   for (int32_t i = tail; i < end; i += W) {
     const int32_t p = position<SIDE>(a, i);
-    t += a.val[col(p)] * a.dval[col(p)];
+    t += a.val[col(p)] * dropped(d, col, p, a.dval[col(p)]);
   }
   t = combine<W, OpSum>(t, lds);
   float dsum = 0.f;
 #pragma unroll
   for (int k = 0; k < kSegKeep; k++) {
     if (beg + lane + k * W < end) {
-      const float d = al[k] * (da[k] - t) * fac[k];
-      a.out_entry[col(pos[k])] = d;
-      dsum += d;
+      const float ds = al[k] * (da[k] - t) * fac[k];
+      a.out_entry[col(pos[k])] = ds;
+      dsum += ds;
     }
   }
 #pragma unroll 4
   for (int32_t i = tail; i < end; i += W) {
     const int32_t p = position<SIDE>(a, i);
     const float f = (need_raw && !(raw_score(a, col, own, i) > 0.f)) ? a.slope : 1.f;
-    const float d = a.val[col(p)] * (a.dval[col(p)] - t) * f;
-    a.out_entry[col(p)] = d;
-    dsum += d;
+    const float ds = a.val[col(p)] * (dropped(d, col, p, a.dval[col(p)]) - t) * f;
+    a.out_entry[col(p)] = ds;
+    dsum += ds;
   }
   if (a.out_seg) {
     dsum = combine<W, OpSum>(dsum, lds);
@@ -189,17 +239,22 @@ __device__ __forceinline__ void sum_segment(const SegArgs &a, Col<MH> col, int32
   if (lane == 0 && valid) a.out_seg[col(seg)] = s;
 }
 
-template <int BODY, int SIDE, int W, bool MH>
-__device__ __forceinline__ void run_segment(const SegArgs &a, Col<MH> col, int32_t seg, int32_t beg, int32_t end, int lane, float *lds,
+template <int BODY, int SIDE, int W, bool MH, typename ARGS>
+__device__ __forceinline__ void run_segment(const ARGS &a, Col<MH> col, int32_t seg, int32_t beg, int32_t end, int lane, float *lds,
                                             bool valid) {
   if constexpr (BODY == kSegSoftmax) softmax_segment<SIDE, W>(a, col, seg, beg, end, lane, lds);
   else if constexpr (BODY == kSegSoftmaxBwd) softmax_bwd_segment<SIDE, W>(a, col, seg, beg, end, lane, lds, valid);
+  else if constexpr (BODY == kSegSoftmaxDrop) softmax_segment<SIDE, W>(a, col, seg, beg, end, lane, lds, load_drop(a.drop));
+  else if constexpr (BODY == kSegSoftmaxDropBwd)
+    softmax_bwd_segment<SIDE, W>(a, col, seg, beg, end, lane, lds, valid, load_drop(a.drop));
   else sum_segment<SIDE, W>(a, col, seg, beg, end, lane, lds, valid);
 }
 
 // Workgroups [0, nlong): one long segment each (they run longest, so they start first); the others: 256 / W lane groups,
 // one segment each.  Lanes without a segment of their own (past the last one, or a long one's lane group) walk an empty
 // range and take part in the butterflies: no lane leaves before the last cross-lane step.
+// This cut of the work exists four times -- here, in segment_heads_kernel and in their two segment_drop_* copies below:
+// a change to it (the kSegLong rule, say) goes into all four.
 template <int BODY, int SIDE, int W>
 __global__ __launch_bounds__(kSegBlock) void segment_kernel(SegArgs a) {
   __shared__ float lds[kSegBlock / 64];
@@ -254,10 +309,68 @@ __global__ __launch_bounds__(kSegBlock) void segment_heads_kernel(SegHeadsArgs a
   run_segment<BODY, SIDE, W>(a, Col<true>{H, h}, seg, beg, end, (int)threadIdx.x % W, lds, valid);
 }
 
-// ARGS = SegArgs: segment_kernel; ARGS = SegHeadsArgs: segment_heads_kernel
+// The dropout bodies: the two kernels above on the longer argument blocks.  The cut of the work is repeated rather than
+// shared through a function, so that the instances above stay instruction for instruction what they were.
+template <int BODY, int SIDE, int W>
+__global__ __launch_bounds__(kSegBlock) void segment_drop_kernel(SegDropArgs a) {
+  __shared__ float lds[kSegBlock / 64];
+  if ((int32_t)blockIdx.x < a.nlong) {
+    const int32_t seg = a.long_seg[blockIdx.x];
+    run_segment<BODY, SIDE, kSegBlock>(a, Col<false>{}, seg, a.ptr[seg], a.ptr[seg + 1], (int)threadIdx.x, lds, true);
+    return;
+  }
+  constexpr int kGroups = kSegBlock / W;
+  const int64_t s = (int64_t)((int32_t)blockIdx.x - a.nlong) * kGroups + (int)threadIdx.x / W;
+  bool valid = s < a.nseg;
+  const int32_t seg = valid ? (int32_t)s : 0;
+  int32_t beg = 0, end = 0;
+  if (valid) {
+    beg = a.ptr[seg];
+    end = a.ptr[seg + 1];
+    if (end - beg > kSegLong) {  // a workgroup of its own has it
+      beg = end = 0;
+      valid = false;
+    }
+  }
+  run_segment<BODY, SIDE, W>(a, Col<false>{}, seg, beg, end, (int)threadIdx.x % W, lds, valid);
+}
+
+template <int BODY, int SIDE, int W>
+__global__ __launch_bounds__(kSegBlock) void segment_drop_heads_kernel(SegDropHeadsArgs a) {
+  __shared__ float lds[kSegBlock / 64];
+  const int32_t H = a.heads;
+  const int64_t nlong = (int64_t)a.nlong * H;
+  if ((int64_t)blockIdx.x < nlong) {
+    const int32_t seg = a.long_seg[blockIdx.x / H];
+    run_segment<BODY, SIDE, kSegBlock>(a, Col<true>{H, (int32_t)(blockIdx.x % H)}, seg, a.ptr[seg], a.ptr[seg + 1],
+                                       (int)threadIdx.x, lds, true);
+    return;
+  }
+  constexpr int kGroups = kSegBlock / W;
+  const int64_t s = ((int64_t)blockIdx.x - nlong) * kGroups + (int)threadIdx.x / W;
+  bool valid = s < (int64_t)a.nseg * H;
+  const int32_t seg = valid ? (int32_t)(s / H) : 0;
+  const int32_t h = valid ? (int32_t)(s % H) : 0;
+  int32_t beg = 0, end = 0;
+  if (valid) {
+    beg = a.ptr[seg];
+    end = a.ptr[seg + 1];
+    if (end - beg > kSegLong) {  // a workgroup of its own has it
+      beg = end = 0;
+      valid = false;
+    }
+  }
+  run_segment<BODY, SIDE, W>(a, Col<true>{H, h}, seg, beg, end, (int)threadIdx.x % W, lds, valid);
+}
+
+// ARGS = SegArgs: segment_kernel; ARGS = SegHeadsArgs: segment_heads_kernel; the dropout blocks: the *_drop_* kernels
 template <int BODY, int SIDE, int W, typename ARGS>
 void launch_one(unsigned nblocks, const ARGS &a, hipStream_t stream) {
-  if constexpr (std::is_same_v<ARGS, SegHeadsArgs>)
+  if constexpr (std::is_same_v<ARGS, SegDropHeadsArgs>)
+    hipLaunchKernelGGL((segment_drop_heads_kernel<BODY, SIDE, W>), dim3(nblocks), dim3(kSegBlock), 0, stream, a);
+  else if constexpr (std::is_same_v<ARGS, SegDropArgs>)
+    hipLaunchKernelGGL((segment_drop_kernel<BODY, SIDE, W>), dim3(nblocks), dim3(kSegBlock), 0, stream, a);
+  else if constexpr (std::is_same_v<ARGS, SegHeadsArgs>)
     hipLaunchKernelGGL((segment_heads_kernel<BODY, SIDE, W>), dim3(nblocks), dim3(kSegBlock), 0, stream, a);
   else
     hipLaunchKernelGGL((segment_kernel<BODY, SIDE, W>), dim3(nblocks), dim3(kSegBlock), 0, stream, a);
@@ -288,10 +401,18 @@ hipError_t launch_body(int body, int side, int width, int64_t heads, const ARGS 
   const int64_t groups = kSegBlock / width;
   const int64_t nblocks = a.nlong * heads + (a.nseg * heads + groups - 1) / groups;
   if (nblocks > 0x7fffffff) return hipErrorInvalidValue;
-  switch (body) {
-    case kSegSoftmax: return launch_side<kSegSoftmax>(side, width, (unsigned)nblocks, a, stream);
-    case kSegSoftmaxBwd: return launch_side<kSegSoftmaxBwd>(side, width, (unsigned)nblocks, a, stream);
-    case kSegSum: return launch_side<kSegSum>(side, width, (unsigned)nblocks, a, stream);
+  if constexpr (std::is_base_of_v<SegDropArgs, ARGS> || std::is_base_of_v<SegDropHeadsArgs, ARGS>) {
+    if (!a.drop.rng) return hipErrorInvalidValue;
+    switch (body) {
+      case kSegSoftmaxDrop: return launch_side<kSegSoftmaxDrop>(side, width, (unsigned)nblocks, a, stream);
+      case kSegSoftmaxDropBwd: return launch_side<kSegSoftmaxDropBwd>(side, width, (unsigned)nblocks, a, stream);
+    }
+  } else {
+    switch (body) {
+      case kSegSoftmax: return launch_side<kSegSoftmax>(side, width, (unsigned)nblocks, a, stream);
+      case kSegSoftmaxBwd: return launch_side<kSegSoftmaxBwd>(side, width, (unsigned)nblocks, a, stream);
+      case kSegSum: return launch_side<kSegSum>(side, width, (unsigned)nblocks, a, stream);
+    }
   }
   return hipErrorInvalidValue;
 }
@@ -307,6 +428,15 @@ hipError_t launch_segments(int body, int side, int width, const SegArgs &a, hipS
 }
 
 hipError_t launch_segments_heads(int body, int side, int width, const SegHeadsArgs &a, hipStream_t stream) {
+  if (a.heads < 1) return hipErrorInvalidValue;
+  return launch_body(body, side, width, a.heads, a, stream);
+}
+
+hipError_t launch_segments_drop(int body, int side, int width, const SegDropArgs &a, hipStream_t stream) {
+  return launch_body(body, side, width, 1, a, stream);
+}
+
+hipError_t launch_segments_drop_heads(int body, int side, int width, const SegDropHeadsArgs &a, hipStream_t stream) {
   if (a.heads < 1) return hipErrorInvalidValue;
   return launch_body(body, side, width, a.heads, a, stream);
 }

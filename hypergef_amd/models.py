@@ -112,11 +112,15 @@ class HypergraphAttnConv(nn.Module):
     heads = H > 1: the linear maps to H * out_channels, head h owns columns h C .. (h + 1) C - 1 of Z (C = out_channels),
     a_v / a_e are flat [H * C], sv[u, h] = <Z[u, head h], a_v[head h]>, se the per-head hyperedge mean, alpha [nnz, H], and
     every operator runs once for all heads (heads=H).  The output is [N, H * C] (concat=True) or the mean over the heads
-    [N, C]; the bias has the output's width.  heads = 1 is the single-head layer, parameter for parameter."""
+    [N, C]; the bias has the output's width.  heads = 1 is the single-head layer, parameter for parameter.
+    dropout = p in (0, 1): in training mode the coefficients are dropped with probability p and the kept ones scaled by
+    1 / (1 - p), inside the softmax kernels (ops.incidence_softmax(dropout=p)); the mask follows torch.manual_seed.  No
+    parameter and no buffer is added; eval() and dropout = 0.0 are the layer without it."""
 
     def __init__(self, hyperg, in_channels, out_channels, group="hyperedge", negative_slope=0.2, options=None, heads=1,
-                 concat=True):
+                 concat=True, dropout=0.0):
         super().__init__()
+        self.dropout = ops._dropout_p(dropout)
         if group not in ("hyperedge", "vertex"):
             raise ValueError("group must be 'hyperedge' or 'vertex', got %r" % (group,))
         if isinstance(heads, bool) or not isinstance(heads, int) or heads < 1:
@@ -135,21 +139,23 @@ class HypergraphAttnConv(nn.Module):
         self._inv_size = torch.nan_to_num(hyperg.degE.reshape(-1), posinf=0.0)   # 1 / |e|, 0 for an empty hyperedge
 
     def coefficients(self, Z):
-        """alpha for the projected features Z: [nnz], or [nnz, heads]."""
+        """alpha for the projected features Z: [nnz], or [nnz, heads]; after dropout where the layer trains with one."""
         ptr, ind = self.hyperg.H_T_csrptr, self.hyperg.H_T_colind
         if self.heads == 1:
             sv = Z @ self.a_v
             ze = (Z @ self.a_e)[self._members]
             se = ops.incidence_sum(ptr, ind, ze, side="hyperedge", num_nodes=Z.shape[0]) * self._inv_size
             return ops.incidence_softmax(ptr, ind, sv, se, group=self.group, negative_slope=self.negative_slope,
-                                         options=self.options, num_nodes=Z.shape[0])
+                                         options=self.options, num_nodes=Z.shape[0], dropout=self.dropout,
+                                         training=self.training)
         H, C = self.heads, self.out_channels
         Zh = Z.view(Z.shape[0], H, C)
         sv = (Zh * self.a_v.view(H, C)).sum(-1)
         ze = (Zh * self.a_e.view(H, C)).sum(-1)[self._members]
         se = ops.incidence_sum(ptr, ind, ze, side="hyperedge", num_nodes=Z.shape[0], heads=H) * self._inv_size.reshape(-1, 1)
         return ops.incidence_softmax(ptr, ind, sv, se, group=self.group, negative_slope=self.negative_slope,
-                                     options=self.options, num_nodes=Z.shape[0], heads=H)
+                                     options=self.options, num_nodes=Z.shape[0], heads=H, dropout=self.dropout,
+                                     training=self.training)
 
     def forward(self, X):
         Z = self.lin(X)

@@ -23,9 +23,11 @@ import torch
 
 from . import _lib
 from .plan import (cached_plan, linear_fusion_pays, linear_rows, linear_supported, linear_wgrad,
-                   wgrad_supported, _check_feat, _check_index, _ptr, _stream_handle)
+                   wgrad_supported, _check_feat, _check_index, _ptr, _rng_state_device, _rng_state_dtype,
+                   _rng_state_length, _stream_handle)
 
 import contextlib
+import numbers
 import dataclasses
 import os as _os
 import threading
@@ -560,9 +562,10 @@ def HGNNAggrIncidence(hyperg, in_feat, v2e_weight, e2v_weight, degE, degV, Wdiag
 _GROUPS = ("hyperedge", "vertex")
 
 
-def _segment_args(what, csrptr_t, indices_t, floats, lengths, group, opt, heads=1):
+def _segment_args(what, csrptr_t, indices_t, floats, lengths, group, opt, heads=1, rng_state=None):
     """Argument checks of incidence_softmax / incidence_sum in _incidence_args' order: every refusal is decided before a
-    device is touched.  floats: (name, tensor or None) pairs; lengths: the element count each must have."""
+    device is touched.  floats: (name, tensor or None) pairs; lengths: the element count each must have.  rng_state: the
+    dropout's state where one was passed: its dtype with the dtypes, its length with the lengths, its device last."""
     if opt is not None and opt.variant not in ("auto", "pull"):
         raise ValueError("%s runs the atomic-free segment kernels: variant must be 'auto' or 'pull', got %r"
                          % (what, opt.variant))
@@ -573,16 +576,22 @@ def _segment_args(what, csrptr_t, indices_t, floats, lengths, group, opt, heads=
         if t is not None and (not isinstance(t, torch.Tensor) or t.dtype != torch.float32):
             raise TypeError("%s must be a float32 tensor (%s has no bfloat16 form), got %s"
                             % (name, what, getattr(t, "dtype", type(t))))
+    if rng_state is not None:
+        _rng_state_dtype(rng_state)
     if not isinstance(csrptr_t, torch.Tensor) or not isinstance(indices_t, torch.Tensor):
         raise TypeError("csrptr_t and indices_t must be int32 tensors")
     for (name, t), n in zip(floats, lengths):
         if t is not None and t.numel() != n:
             raise ValueError("%s must have %d elements, got %d" % (name, n, t.numel()))
+    if rng_state is not None:
+        _rng_state_length(rng_state)
     _check_index(csrptr_t, "csrptr_t")
     _check_index(indices_t, "indices_t")
     for name, t in floats:
         if t is not None:
             _check_feat(t, name, device=csrptr_t.device)
+    if rng_state is not None:
+        _rng_state_device(rng_state, csrptr_t.device)
 
 
 class _IncidenceSoftmax(torch.autograd.Function):
@@ -608,8 +617,43 @@ class _IncidenceSoftmax(torch.autograd.Function):
         return None, None, dsv, dse, None, None, None, None
 
 
+class _IncidenceSoftmaxDropout(torch.autograd.Function):
+    """_IncidenceSoftmax with dropout on alpha fused into both kernels: returns keep ? alpha / (1 - p) : 0, saves the
+    undropped alpha and the two words of rng_state, from which the backward regenerates the mask.  Exact gradients for
+    both score vectors: the plain backward on dalpha = keep ? dout / (1 - p) : 0."""
+
+    @staticmethod
+    def forward(ctx, csrptr_t, indices_t, sv, se, N, group, slope, heads, p_drop, rng_state):
+        plan = cached_plan(N, csrptr_t, indices_t)
+        alpha, alpha_drop = plan.incidence_attention_dropout(csrptr_t, indices_t, sv, se, group, slope, p_drop, rng_state,
+                                                             heads=heads)
+        ctx.save_for_backward(csrptr_t, indices_t, sv, se, alpha, rng_state)
+        ctx.N, ctx.group, ctx.slope, ctx.heads, ctx.p_drop = N, group, slope, heads, p_drop
+        return alpha_drop
+
+    @staticmethod
+    def backward(ctx, dout):
+        csrptr_t, indices_t, sv, se, alpha, rng_state = ctx.saved_tensors
+        plan = cached_plan(ctx.N, csrptr_t, indices_t)
+        need_sv = sv is not None and ctx.needs_input_grad[2]
+        need_se = se is not None and ctx.needs_input_grad[3]
+        _, dsv, dse = plan.incidence_attention_dropout_backward(
+            csrptr_t, indices_t, alpha, dout.contiguous(), sv, se, ctx.group, ctx.slope, ctx.p_drop, rng_state,
+            need_sv=need_sv, need_se=need_se, heads=ctx.heads)
+        return None, None, dsv, dse, None, None, None, None, None, None
+
+
+def _dropout_p(dropout):
+    """The `dropout` keyword as a float in [0, 1): ValueError otherwise, before any tensor is looked at."""
+    if isinstance(dropout, bool) or not isinstance(dropout, numbers.Real) or not 0.0 <= float(dropout) < 1.0:
+        raise ValueError("dropout must be a real number in [0, 1), got %r (1.0 is refused: the scale 1 / (1 - dropout) "
+                         "of the kept coefficients would be infinite)" % (dropout,))
+    return float(dropout)
+
+
 def incidence_softmax(csrptr_t, indices_t, node_score=None, edge_score=None, group="hyperedge", negative_slope=0.2,
-                      options=None, num_nodes=None, heads=1):
+                      options=None, num_nodes=None, heads=1, dropout=0.0, training=True, rng_state=None,
+                      return_rng_state=False):
     """Hypergraph attention's coefficients, alpha [nnz] aligned with indices_t: for every incidence p = (e, u)
     alpha[p] = softmax over p's group of leaky_relu(node_score[u] + edge_score[e], negative_slope); the group is p's
     hyperedge (group='hyperedge': the coefficients of a hyperedge's members sum to 1) or p's vertex (group='vertex').
@@ -618,8 +662,16 @@ def incidence_softmax(csrptr_t, indices_t, node_score=None, edge_score=None, gro
     None, otherwise optional (node_score's length is taken as N; given, node_score must have that length).  Options.variant 'auto' and 'pull' run; the others raise ValueError.  float32 only (TypeError for bfloat16).
     heads = H > 1: a softmax per head in one call.  node_score holds N * H and edge_score M * H elements ([N, H] / [M, H],
     head fastest), alpha comes back [nnz, H]; N is taken as node_score's element count / H.  heads = 1 is the call above,
-    unchanged."""
+    unchanged.
+    dropout = p in (0, 1) with training=True: the coefficients after dropout, keep ? alpha / (1 - p) : 0, from the same
+    launch (hg_incidence_attention_dropout_heads_f32) -- no stored mask, no further pass; the gradients stay exact, the
+    backward regenerates the mask.  rng_state: int64 [2] on the scores' device, the {key, sid} of the Philox mask (keep
+    depends on it, the position in indices_t and the head alone); None draws one with torch.randint on that device: it
+    follows torch.manual_seed, costs no host synchronisation and, captured into a graph, gives every replay a new mask.
+    return_rng_state=True returns (coefficients, the state used -- None where no dropout ran).  dropout = 0.0 or
+    training=False is the call above: the same code path, the same bits, torch's generator untouched."""
     opt = _opt(options)
+    p_drop = _dropout_p(dropout)
     if heads == 1:
         sv, se = (_flat(t) if isinstance(t, torch.Tensor) else t for t in (node_score, edge_score))
     else:
@@ -629,15 +681,30 @@ def incidence_softmax(csrptr_t, indices_t, node_score=None, edge_score=None, gro
         raise ValueError("incidence_softmax needs node_score or num_nodes (the number of vertices)")
     N = int(num_nodes) if num_nodes is not None else sv.numel() // heads
     M = csrptr_t.numel() - 1 if isinstance(csrptr_t, torch.Tensor) else 0
+    drop = p_drop > 0.0 and bool(training)
     _segment_args("incidence_softmax", csrptr_t, indices_t, (("node_score", sv), ("edge_score", se)),
-                  (N * heads, M * heads), group, opt, heads)
+                  (N * heads, M * heads), group, opt, heads, rng_state if drop else None)
     slope = float(negative_slope)
-    if not (torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (sv, se))):
-        return cached_plan(N, csrptr_t, indices_t).incidence_attention(csrptr_t, indices_t, sv, se, group, slope,
-                                                                       heads=heads)
-    if heads == 1:
-        return _IncidenceSoftmax.apply(csrptr_t, indices_t, sv, se, N, group, slope)
-    return _IncidenceSoftmax.apply(csrptr_t, indices_t, sv, se, N, group, slope, heads)
+    if drop:
+        out, rng_state = _softmax_dropout(csrptr_t, indices_t, sv, se, N, group, slope, heads, p_drop, rng_state)
+    elif not (torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (sv, se))):
+        out = cached_plan(N, csrptr_t, indices_t).incidence_attention(csrptr_t, indices_t, sv, se, group, slope, heads=heads)
+    elif heads == 1:
+        out = _IncidenceSoftmax.apply(csrptr_t, indices_t, sv, se, N, group, slope)
+    else:
+        out = _IncidenceSoftmax.apply(csrptr_t, indices_t, sv, se, N, group, slope, heads)
+    return (out, rng_state if drop else None) if return_rng_state else out
+
+
+def _softmax_dropout(csrptr_t, indices_t, sv, se, N, group, slope, heads, p_drop, rng_state):
+    """(dropped coefficients, the state used) of incidence_softmax, its arguments checked."""
+    if rng_state is None:  # on the device: no synchronisation, and a captured draw is drawn again by every replay
+        info = torch.iinfo(torch.int64)  # randint's upper end is exclusive: every int64 but 2^63 - 1, which a key can spare
+        rng_state = torch.randint(info.min, info.max, (2,), dtype=torch.int64, device=csrptr_t.device)
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (sv, se)):
+        return _IncidenceSoftmaxDropout.apply(csrptr_t, indices_t, sv, se, N, group, slope, heads, p_drop, rng_state), rng_state
+    plan = cached_plan(N, csrptr_t, indices_t)
+    return plan.incidence_attention_dropout(csrptr_t, indices_t, sv, se, group, slope, p_drop, rng_state, heads=heads)[1], rng_state
 
 
 class _IncidenceSum(torch.autograd.Function):

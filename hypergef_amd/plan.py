@@ -563,6 +563,58 @@ class Plan:
                     _ptr(dalpha), _ptr(ds), _ptr(dsv), _ptr(dse), _stream_handle(device)))
         return ds, dsv, dse
 
+    def _rng_ptr(self, rng_state, device):
+        _rng_state_dtype(rng_state)
+        _rng_state_length(rng_state)
+        _rng_state_device(rng_state, device)
+        return _ptr(rng_state)
+
+    def incidence_attention_dropout(self, csrptr_t, colind_t, sv=None, se=None, group="hyperedge", slope=0.2, p_drop=0.5,
+                                    rng_state=None, heads=1):
+        """(alpha, alpha_drop): incidence_attention's coefficients and, from the same launch, the coefficients after dropout,
+        alpha_drop = keep ? alpha / (1 - p_drop) : 0 (hg_incidence_attention_dropout_heads_f32).  rng_state: int64 [2] on
+        the scores' device, {key, sid} of the Philox mask; the kernel reads it when it runs.  keep depends on (rng_state,
+        H_T position, head) alone; no mask is stored.  [nnz], or [nnz, heads]."""
+        heads = _heads(heads)
+        group = _side(group)
+        _check_index(csrptr_t, "csrptr_t")
+        _check_index(colind_t, "indices_t")
+        device = self._scores(sv, se, csrptr_t.device, heads)
+        rng = self._rng_ptr(rng_state, device)
+        alpha = torch.empty(_per_head(self.nnz, heads), dtype=torch.float32, device=device)
+        alpha_drop = torch.empty_like(alpha)
+        with torch.cuda.device(device):
+            _lib.check(_lib.lib().hg_incidence_attention_dropout_heads_f32(
+                self._h, group, heads, _ptr(csrptr_t), _ptr(colind_t), _ptr(sv), _ptr(se), float(slope), float(p_drop), rng,
+                _ptr(alpha), _ptr(alpha_drop), _stream_handle(device)))
+        return alpha, alpha_drop
+
+    def incidence_attention_dropout_backward(self, csrptr_t, colind_t, alpha, dout, sv=None, se=None, group="hyperedge",
+                                             slope=0.2, p_drop=0.5, rng_state=None, need_sv=True, need_se=True, heads=1):
+        """(ds, dsv or None, dse or None) for (alpha, alpha_drop) = incidence_attention_dropout(...) and dout, the gradient
+        of alpha_drop: incidence_attention_backward on dalpha = keep ? dout / (1 - p_drop) : 0, the mask regenerated from
+        rng_state (hg_incidence_attention_dropout_heads_bwd_f32)."""
+        heads = _heads(heads)
+        group = _side(group)
+        _check_index(csrptr_t, "csrptr_t")
+        _check_index(colind_t, "indices_t")
+        _check_feat(alpha, "alpha")
+        _check_feat(dout, "dout", device=alpha.device)
+        for name, t in (("alpha", alpha), ("dout", dout)):
+            if t.numel() != self.nnz * heads:
+                raise ValueError("%s must have nnz%s = %d elements, got %d" % (name, " * heads" if heads > 1 else "",
+                                                                              self.nnz * heads, t.numel()))
+        device = self._scores(sv, se, alpha.device, heads)
+        rng = self._rng_ptr(rng_state, device)
+        ds = torch.empty(_per_head(self.nnz, heads), dtype=torch.float32, device=device)
+        dsv = torch.empty(_per_head(self.N, heads), dtype=torch.float32, device=device) if need_sv else None
+        dse = torch.empty(_per_head(self.M, heads), dtype=torch.float32, device=device) if need_se else None
+        with torch.cuda.device(device):
+            _lib.check(_lib.lib().hg_incidence_attention_dropout_heads_bwd_f32(
+                self._h, group, heads, _ptr(csrptr_t), _ptr(colind_t), _ptr(sv), _ptr(se), float(slope), float(p_drop), rng,
+                _ptr(alpha), _ptr(dout), _ptr(ds), _ptr(dsv), _ptr(dse), _stream_handle(device)))
+        return ds, dsv, dse
+
     def incidence_sum(self, csrptr_t, colind_t, val, side="hyperedge", out=None, heads=1):
         """out[e] = sum of val over hyperedge e's incidences (side 'hyperedge', [M]) or out[v] = sum over vertex v's
         (side 'vertex', [N]); val float32 [nnz] in H_T order (hg_incidence_sum_f32).  heads = H > 1
@@ -771,6 +823,27 @@ def _check_feat(t, name, device=None, bf16_ok=False):
         raise RuntimeError("%s must be contiguous" % name)
     if device is not None and t.device != device:
         raise RuntimeError("%s is on %s, expected %s" % (name, t.device, device))
+
+
+# The attention dropout's state, int64 [2] = {key, sid}: the three refusals in the order every layer makes them (ops.
+# _segment_args interleaves them with those of the other arguments).
+def _rng_state_dtype(t):
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.int64:
+        raise TypeError("rng_state must be an int64 tensor of 2 elements {key, sid}, got %s" % (getattr(t, "dtype", type(t)),))
+
+
+def _rng_state_length(t):
+    if t.numel() != 2:
+        raise ValueError("rng_state must have 2 elements {key, sid}, got %d" % t.numel())
+
+
+def _rng_state_device(t, device=None):
+    if not t.is_cuda:
+        raise RuntimeError("rng_state must be on a GPU (no CPU fallback in this backend)")
+    if not t.is_contiguous():
+        raise RuntimeError("rng_state must be contiguous")
+    if device is not None and t.device != device:
+        raise RuntimeError("rng_state is on %s, expected %s" % (t.device, device))
 
 
 # ------------------------------------------------------------------ plan cache

@@ -490,6 +490,43 @@ HG_API int hg_incidence_dot_heads_f32(const hg_plan *plan, int32_t F, int32_t he
                                       const int32_t *colind_t, const float *A, const float *B, float *out,
                                       hg_stream_t stream);
 
+/* ---- attention dropout ------------------------------------------------------------------------------------------------
+ * Dropout on the attention coefficients, fused into the softmax and its backward: no stored mask, no further pass over
+ * the [nnz, heads] array.  With a[p, h] the coefficient hg_incidence_attention_heads_f32 computes for H_T position p and
+ * head h, p_drop in [0, 1) and the 128-bit state rng = {key, sid} (two uint64 in device memory):
+ *     w         = philox4x32_10(counter = (p, h, sid_lo, sid_hi), key = (key_lo, key_hi))[0]      (Random123's Philox)
+ *     keep      = w >= T,   T = (uint32) floor((double) p_drop * 2^32)
+ *     scale     = 1.0f / (1.0f - p_drop)                                                   (fp32, rounded on the host)
+ *     alpha_drop_out[p, h] = keep ? fl(a[p, h] * scale) : +0.0f,     alpha_out[p, h] = a[p, h]
+ *   alpha_out has the bits hg_incidence_attention_heads_f32 writes for the same scores: the backward needs the undropped
+ *   coefficient at the dropped positions too.  The mask depends on (rng, p, h) alone -- not on group, on the lane-group
+ *   width or on the lane that owns the entry -- so both groups drop the same positions for the same state.
+ * hg_incidence_attention_dropout_heads_bwd_f32: given alpha (alpha_out above) and dout, the gradient of alpha_drop_out,
+ *     dalpha[p, h] = keep ? fl(dout[p, h] * scale) : +0.0f
+ *   with the mask regenerated from rng_dev, then exactly hg_incidence_attention_heads_bwd_f32 on (alpha, dalpha): the same
+ *   t_g, ds, dsv, dse in the same order, so the results have the bits of that entry on the pre-masked gradient.
+ * rng_dev: two uint64 {key, sid}, 8-byte aligned, read by the kernel when it runs -- not by the call.  A launch captured
+ *   into a hipGraph therefore draws a new mask on every replay whose state was updated in between (by a captured device
+ *   operation, say), as cb_dev of hg_aggr_linear_res_dev_f32 lets a captured step change its coefficient.  The backward
+ *   must find the words its forward found.
+ * heads = 1 is the single-head layout.  Refusals (nothing launched, message through hg_last_error): HG_ERR_INVALID for
+ *   p_drop outside [0, 1) or NaN, for a null (or misaligned) rng_dev, a null alpha_out, alpha_drop_out or ds_out;
+ *   otherwise the rules of the *_heads_f32 entries above (HG_ERR_UNSUPPORTED for a plan built with HG_PLAN_HOST_ONLY,
+ *   heads < 1, ...).  The first-call-allocates rule is theirs, and what is allocated is shared with them.
+ * hg_dropout_keep_host: the mask itself, on the host, from the same source as the kernels: keep_out[p * heads + h] = 1
+ *   where (p, h) is kept, else 0, for p < nnz (< 2^31).  Needs neither a plan nor a device (tools, tests).
+ * Detect these entries by their exported symbols (HG_AGGR_VERSION does not change). */
+HG_API int hg_incidence_attention_dropout_heads_f32(const hg_plan *plan, int32_t group, int32_t heads,
+                                                    const int32_t *csrptr_t, const int32_t *colind_t, const float *sv,
+                                                    const float *se, float slope, float p_drop, const uint64_t *rng_dev,
+                                                    float *alpha_out, float *alpha_drop_out, hg_stream_t stream);
+HG_API int hg_incidence_attention_dropout_heads_bwd_f32(const hg_plan *plan, int32_t group, int32_t heads,
+                                                        const int32_t *csrptr_t, const int32_t *colind_t, const float *sv,
+                                                        const float *se, float slope, float p_drop, const uint64_t *rng_dev,
+                                                        const float *alpha, const float *dout, float *ds_out,
+                                                        float *dsv_out, float *dse_out, hg_stream_t stream);
+HG_API int hg_dropout_keep_host(uint64_t key, uint64_t sid, float p_drop, int64_t nnz, int32_t heads, uint8_t *keep_out);
+
 /* first_aggr = "max" pieces (hgnnaggr_max, source/hgnnaggr/hgnnaggr_cuda.cu:144-208).
  * hg_gather_max_f32: Xe[e,k] = (max_{u in e} X[u,k], start -1e5, strict >) * (degE[e]*W[e]),
  * record[e,k] = winning vertex (0 if none).  The second hop is hg_gather_rows_f32(hop = 1).
