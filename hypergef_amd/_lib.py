@@ -41,6 +41,9 @@ SYMBOLS = (
     "hg_incidence_attention_heads_f32", "hg_incidence_attention_heads_bwd_f32", "hg_incidence_sum_heads_f32",
     "hg_aggr_incidence_heads_f32", "hg_incidence_dot_heads_f32",
     "hg_incidence_attention_dropout_heads_f32", "hg_incidence_attention_dropout_heads_bwd_f32", "hg_dropout_keep_host",
+    "hg_incidence_attention_entry_heads_f32", "hg_incidence_attention_entry_heads_bwd_f32",
+    "hg_incidence_attention_entry_dropout_heads_f32", "hg_incidence_attention_entry_dropout_heads_bwd_f32",
+    "hg_gather_rows_incidence_heads_f32",
 )
 
 
@@ -217,6 +220,19 @@ def lib():
                                                                    ctypes.c_float, vp, vp, vp, vp, vp, vp, vp]
         L.hg_dropout_keep_host.restype = ctypes.c_int
         L.hg_dropout_keep_host.argtypes = [ctypes.c_uint64, ctypes.c_uint64, ctypes.c_float, i64, i32, vp]
+    if hasattr(L, "hg_incidence_attention_entry_heads_f32"):  # likewise: + entry_score after se; the one-hop weighted gather
+        f32 = ctypes.c_float
+        L.hg_incidence_attention_entry_heads_f32.restype = ctypes.c_int
+        L.hg_incidence_attention_entry_heads_f32.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, f32, vp, vp]
+        L.hg_incidence_attention_entry_heads_bwd_f32.restype = ctypes.c_int
+        L.hg_incidence_attention_entry_heads_bwd_f32.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, f32, vp, vp, vp, vp, vp, vp]
+        L.hg_incidence_attention_entry_dropout_heads_f32.restype = ctypes.c_int
+        L.hg_incidence_attention_entry_dropout_heads_f32.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, f32, f32, vp, vp, vp, vp]
+        L.hg_incidence_attention_entry_dropout_heads_bwd_f32.restype = ctypes.c_int
+        L.hg_incidence_attention_entry_dropout_heads_bwd_f32.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, f32, f32, vp, vp, vp,
+                                                                         vp, vp, vp, vp]
+        L.hg_gather_rows_incidence_heads_f32.restype = ctypes.c_int
+        L.hg_gather_rows_incidence_heads_f32.argtypes = [vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]
     L.hg_aggr_push_groups_f32.restype = ctypes.c_int
     L.hg_aggr_push_groups_f32.argtypes = [i32, i32, i32, i64, vp, vp, vp, vp, vp, vp,
                                           vp, vp, vp, vp, vp, vp]

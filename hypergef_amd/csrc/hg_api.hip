@@ -588,9 +588,10 @@ int check_segment_call(const char *who, const hg_plan *plan, int side, const int
 
 // One launch of the segment kernels on `side`: fills the side's arrays of `a` (scores: sv [N], se [M]) and runs `body`.
 // drop: the dropout bodies' further arguments (kSegSoftmaxDrop / kSegSoftmaxDropBwd), null for the others.
+// entry: the logit per incidence of the kSegSoftmaxEntry* bodies ([nnz, heads], H_T order), null for the others.
 int run_segments(const char *who, const hg_plan *plan, int body, int side, const int32_t *csrptr_t, const int32_t *colind_t,
                  const float *sv, const float *se, hg::SegArgs a, hipStream_t stream, int32_t heads = 1,
-                 const hg::DropFields *drop = nullptr) {
+                 const hg::DropFields *drop = nullptr, const float *entry = nullptr) {
   int rc;
   const int32_t *perm = nullptr;
   if (side == 1 && (rc = get_incidence_perm(plan, true, &perm)) != HG_OK) return rc;
@@ -603,7 +604,14 @@ int run_segments(const char *who, const hg_plan *plan, int body, int side, const
   a.own = side == 0 ? se : sv;
   a.other = side == 0 ? sv : se;
   hipError_t e;
-  if (drop && heads > 1) {
+  if (entry) {  // one block for every form: heads >= 1, drop or none
+    hg::SegEntryArgs ae = {};
+    static_cast<hg::SegArgs &>(ae) = a;
+    ae.heads = heads;
+    if (drop) ae.drop = *drop;
+    ae.entry = entry;
+    e = hg::launch_segments_entry(body, side, width, ae, stream);
+  } else if (drop && heads > 1) {
     hg::SegDropHeadsArgs ad;
     static_cast<hg::SegArgs &>(ad) = a;
     ad.heads = heads;
@@ -1663,6 +1671,36 @@ static int aggr_incidence(const hg_plan *plan, int32_t F, int32_t heads, const i
                           const float *degV, const float *W, float *Xe_out, float *Y, void *workspace,
                           size_t workspace_bytes, hg_stream_t stream);
 
+// what the weighted gather_rows_kernel stages per workgroup beside the panel must fit the CU's 160 KiB of LDS
+static bool weights_fit_lds(const hg_plan *plan) {
+  return (size_t)(4 * plan->opts.panel_rows + 1 + 2 * plan->opts.panel_nnz) * sizeof(int32_t) <= (size_t)160 * 1024;
+}
+
+// One hop of the incidence-weighted aggregation, shared by hg_aggr_incidence*_f32 (both hops) and
+// hg_gather_rows_incidence_heads_f32 (one): hop 0 walks H_T, dst[e] = ((sum_{p=(e,u)} w[p] src[u]) * scaleA[e]) * scaleB[e];
+// hop 1 walks H and reads w through the plan's permutation.  w null: the unweighted instances on the same schedule.
+static int incidence_hop(const hg_plan *plan, int hop, int32_t F, int32_t heads, const int32_t *csrptr_t,
+                         const int32_t *colind_t, const float *src, const float *w, const float *scaleA, const float *scaleB,
+                         float *dst, char *ws, const Carve &c, hipStream_t s) {
+  int rc;
+  const int32_t *perm = nullptr;
+  if (hop == 1 && w && (rc = get_incidence_perm(plan, true, &perm)) != HG_OK) return rc;
+  // the panels + wave-task kernel (the streaming row gather has no weighted form): sched[hop], or the latency schedule
+  // where hg_plan_tune_f32 pinned that kernel for this width -- what a forced pull call runs there
+  int kind = 1;
+  {
+    hg_plan *mp = const_cast<hg_plan *>(plan);
+    std::lock_guard<std::mutex> lock(mp->auto_mu);
+    auto it = mp->hop_kernel.find(F);
+    if (it != mp->hop_kernel.end()) kind = hop == 0 ? it->second % 3 : (it->second / 3) % 3;
+  }
+  const hg::Sched &sc = (kind == 2 && plan->has_lat) ? plan->sched_lat[hop] : plan->sched[hop];
+  // streaming stores as run_hop decides them
+  const bool nt = rows_whole_64(dst, F) && (hop == 1 || (int64_t)plan->M * F * 4 >= ((int64_t)192 << 20));
+  return run_sched(plan, sc, F, hop == 0 ? csrptr_t : plan->d_ptr_v, hop == 0 ? colind_t : plan->d_ind_v, src, scaleA, scaleB,
+                   nullptr, nullptr, dst, reinterpret_cast<float *>(ws + c.part[hop]), s, nt, false, false, w, perm, heads);
+}
+
 size_t hg_aggr_incidence_workspace_bytes(const hg_plan *p, int32_t F) {
   if (!p || F <= 0) return 0;
   return carve(p, F).total;  // the pull layout: [Xe][partial rows of hop 1][partial rows of hop 2]
@@ -1697,41 +1735,45 @@ static int aggr_incidence(const hg_plan *plan, int32_t F, int32_t heads, const i
     hg::set_error("hg_aggr_incidence_f32: null array");
     return HG_ERR_INVALID;
   }
-  if ((v2e_val || e2v_val) && (size_t)(4 * plan->opts.panel_rows + 1 + 2 * plan->opts.panel_nnz) * sizeof(int32_t) >
-                                  (size_t)160 * 1024) {
+  if ((v2e_val || e2v_val) && !weights_fit_lds(plan)) {
     hg::set_error("hg_aggr_incidence_f32: panel_rows / panel_nnz leave no LDS for the staged weights (160 KiB per workgroup)");
     return HG_ERR_UNSUPPORTED;
   }
-  const int32_t *perm = nullptr;
-  if (e2v_val && (rc = get_incidence_perm(plan, true, &perm)) != HG_OK) return rc;
+  // the permutation hop 2 will ask for: a failed upload is reported before hop 1 is launched
+  if (e2v_val && (rc = get_incidence_perm(plan, true, nullptr)) != HG_OK) return rc;
   hipStream_t s = static_cast<hipStream_t>(stream);
   const Carve c = carve(plan, F);
   char *ws = static_cast<char *>(workspace);
   float *Xe = Xe_out ? Xe_out : reinterpret_cast<float *>(ws + c.xe);
-  // the panels + wave-task kernel on both hops (the streaming row gather has no weighted form): sched[hop], or the
-  // latency schedule where hg_plan_tune_f32 pinned that kernel for this width -- what a forced pull call runs there
-  int kind[2] = {1, 1};
-  {
-    hg_plan *mp = const_cast<hg_plan *>(plan);
-    std::lock_guard<std::mutex> lock(mp->auto_mu);
-    auto it = mp->hop_kernel.find(F);
-    if (it != mp->hop_kernel.end()) {
-      kind[0] = it->second % 3;
-      kind[1] = (it->second / 3) % 3;
-    }
-  }
-  const hg::Sched &s0 = (kind[0] == 2 && plan->has_lat) ? plan->sched_lat[0] : plan->sched[0];
-  const hg::Sched &s1 = (kind[1] == 2 && plan->has_lat) ? plan->sched_lat[1] : plan->sched[1];
-  // streaming stores as run_hop decides them
-  const bool nt0 = rows_whole_64(Xe, F) && (int64_t)plan->M * F * 4 >= ((int64_t)192 << 20);
-  const bool nt1 = rows_whole_64(Y, F);
   // hop 1: Xe[e] = ((sum_{p=(e,u)} v2e[p] X[u]) * degE[e]) * W[e]
-  rc = run_sched(plan, s0, F, csrptr_t, colind_t, X, degE, W, nullptr, nullptr, Xe,
-                 reinterpret_cast<float *>(ws + c.part[0]), s, nt0, false, false, v2e_val, nullptr, heads);
+  rc = incidence_hop(plan, 0, F, heads, csrptr_t, colind_t, X, v2e_val, degE, W, Xe, ws, c, s);
   if (rc != HG_OK) return rc;
   // hop 2: Y[v] = (sum_{q=(v,e)} e2v[perm[q]] Xe[e]) * degV[v]
-  return run_sched(plan, s1, F, plan->d_ptr_v, plan->d_ind_v, Xe, degV, nullptr, nullptr, nullptr, Y,
-                   reinterpret_cast<float *>(ws + c.part[1]), s, nt1, false, false, e2v_val, perm, heads);
+  return incidence_hop(plan, 1, F, heads, csrptr_t, colind_t, Xe, e2v_val, degV, nullptr, Y, ws, c, s);
+}
+
+int hg_gather_rows_incidence_heads_f32(const hg_plan *plan, int32_t hop, int32_t F, int32_t heads, const int32_t *csrptr_t,
+                                       const int32_t *colind_t, const float *src, const float *w, const float *scaleA,
+                                       const float *scaleB, float *dst, void *workspace, size_t workspace_bytes,
+                                       hg_stream_t stream) {
+  const char *who = "hg_gather_rows_incidence_heads_f32";
+  if (hop != 0 && hop != 1) {  // before the plan is looked at, as heads < 1 is
+    hg::set_error(std::string(who) + ": hop must be 0 (to the hyperedges) or 1 (to the vertices)");
+    return HG_ERR_INVALID;
+  }
+  int rc = check_heads(who, plan, heads, F);
+  if (rc != HG_OK) return rc;
+  if ((rc = check_call(plan, F, workspace, workspace_bytes, kSizePull)) != HG_OK) return rc;
+  if (!csrptr_t || (plan->nnz > 0 && !colind_t) || !src || !dst) {
+    hg::set_error(std::string(who) + ": null array");
+    return HG_ERR_INVALID;
+  }
+  if (w && !weights_fit_lds(plan)) {
+    hg::set_error(std::string(who) + ": panel_rows / panel_nnz leave no LDS for the staged weights (160 KiB per workgroup)");
+    return HG_ERR_UNSUPPORTED;
+  }
+  return incidence_hop(plan, hop, F, heads, csrptr_t, colind_t, src, w, scaleA, scaleB, dst, static_cast<char *>(workspace),
+                       carve(plan, F), static_cast<hipStream_t>(stream));
 }
 
 int hg_incidence_dot_f32(const hg_plan *plan, int32_t F, const int32_t *csrptr_t, const int32_t *colind_t,
@@ -1900,6 +1942,124 @@ int hg_incidence_attention_dropout_heads_bwd_f32(const hg_plan *plan, int32_t gr
   b.out_seg = other_out;
   return run_segments("incidence_attention_dropout_bwd sum launch", plan, hg::kSegSum, 1 - group, csrptr_t, colind_t,
                       nullptr, nullptr, b, s, heads);
+}
+
+// ---- a logit per incidence: the four softmax entries with entry_score added to the score ------------------------------
+
+// Refusals of the entry-logit entries that need no look at the plan's contents, in the order: plan, heads, group,
+// entry_score; then the host-only plan and the arrays (check_segment_call).
+static int check_entry_call(const char *who, const hg_plan *plan, int32_t group, int32_t heads, const int32_t *csrptr_t,
+                            const int32_t *colind_t, const float *entry_score) {
+  if (!plan) {
+    hg::set_error(std::string(who) + ": null plan");
+    return HG_ERR_INVALID;
+  }
+  if (heads < 1) {
+    hg::set_error(std::string(who) + ": heads must be at least 1");
+    return HG_ERR_INVALID;
+  }
+  if (group != 0 && group != 1) {
+    hg::set_error(std::string(who) + ": group / side must be 0 (hyperedge) or 1 (vertex)");
+    return HG_ERR_INVALID;
+  }
+  if (!entry_score) {
+    hg::set_error(std::string(who) + ": null entry_score (the entries without one take sv / se alone)");
+    return HG_ERR_INVALID;
+  }
+  int rc = check_heads(who, plan, heads, 0);
+  if (rc != HG_OK) return rc;
+  return check_segment_call(who, plan, group, csrptr_t, colind_t);
+}
+
+static int entry_attention(const char *who, const hg_plan *plan, int32_t group, int32_t heads, const int32_t *csrptr_t,
+                           const int32_t *colind_t, const float *sv, const float *se, const float *entry_score, float slope,
+                           const hg::DropFields *drop, float *alpha_out, hg_stream_t stream) {
+  if (!alpha_out || (drop && !drop->out_drop) || !(slope == slope) || slope - slope != 0.f) {
+    hg::set_error(std::string(who) + ": null alpha_out / alpha_drop_out or non-finite slope");
+    return HG_ERR_INVALID;
+  }
+  if (plan->nnz == 0) return HG_OK;
+  hg::SegArgs a = {};
+  a.slope = slope;
+  a.out_entry = alpha_out;
+  return run_segments(who, plan, drop ? hg::kSegSoftmaxEntryDrop : hg::kSegSoftmaxEntry, group, csrptr_t, colind_t, sv, se, a,
+                      static_cast<hipStream_t>(stream), heads, drop, entry_score);
+}
+
+static int entry_attention_bwd(const char *who, const hg_plan *plan, int32_t group, int32_t heads, const int32_t *csrptr_t,
+                               const int32_t *colind_t, const float *sv, const float *se, const float *entry_score,
+                               float slope, const hg::DropFields *drop, const float *alpha, const float *dalpha,
+                               float *ds_out, float *dsv_out, float *dse_out, hg_stream_t stream) {
+  if (!ds_out || (plan->nnz > 0 && (!alpha || !dalpha)) || !(slope == slope) || slope - slope != 0.f) {
+    hg::set_error(std::string(who) + ": null alpha / dalpha / ds_out or non-finite slope");
+    return HG_ERR_INVALID;
+  }
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  hg::SegArgs a = {};
+  a.slope = slope;
+  a.val = alpha;
+  a.dval = dalpha;
+  a.out_entry = ds_out;
+  a.out_seg = group == 0 ? dse_out : dsv_out;  // the group's own end: summed by the kernel that forms ds
+  int rc = run_segments(who, plan, drop ? hg::kSegSoftmaxEntryDropBwd : hg::kSegSoftmaxEntryBwd, group, csrptr_t, colind_t,
+                        sv, se, a, s, heads, drop, entry_score);
+  if (rc != HG_OK) return rc;
+  float *other_out = group == 0 ? dsv_out : dse_out;  // the other end: the plain segment sum of ds over that side
+  if (!other_out) return HG_OK;
+  hg::SegArgs b = {};
+  b.val = ds_out;
+  b.out_seg = other_out;
+  return run_segments(who, plan, hg::kSegSum, 1 - group, csrptr_t, colind_t, nullptr, nullptr, b, s, heads);
+}
+
+int hg_incidence_attention_entry_heads_f32(const hg_plan *plan, int32_t group, int32_t heads, const int32_t *csrptr_t,
+                                           const int32_t *colind_t, const float *sv, const float *se,
+                                           const float *entry_score, float slope, float *alpha_out, hg_stream_t stream) {
+  const char *who = "hg_incidence_attention_entry_heads_f32";
+  int rc = check_entry_call(who, plan, group, heads, csrptr_t, colind_t, entry_score);
+  if (rc != HG_OK) return rc;
+  return entry_attention(who, plan, group, heads, csrptr_t, colind_t, sv, se, entry_score, slope, nullptr, alpha_out, stream);
+}
+
+int hg_incidence_attention_entry_heads_bwd_f32(const hg_plan *plan, int32_t group, int32_t heads, const int32_t *csrptr_t,
+                                               const int32_t *colind_t, const float *sv, const float *se,
+                                               const float *entry_score, float slope, const float *alpha,
+                                               const float *dalpha, float *ds_out, float *dsv_out, float *dse_out,
+                                               hg_stream_t stream) {
+  const char *who = "hg_incidence_attention_entry_heads_bwd_f32";
+  int rc = check_entry_call(who, plan, group, heads, csrptr_t, colind_t, entry_score);
+  if (rc != HG_OK) return rc;
+  return entry_attention_bwd(who, plan, group, heads, csrptr_t, colind_t, sv, se, entry_score, slope, nullptr, alpha, dalpha,
+                             ds_out, dsv_out, dse_out, stream);
+}
+
+int hg_incidence_attention_entry_dropout_heads_f32(const hg_plan *plan, int32_t group, int32_t heads,
+                                                   const int32_t *csrptr_t, const int32_t *colind_t, const float *sv,
+                                                   const float *se, const float *entry_score, float slope, float p_drop,
+                                                   const uint64_t *rng_dev, float *alpha_out, float *alpha_drop_out,
+                                                   hg_stream_t stream) {
+  const char *who = "hg_incidence_attention_entry_dropout_heads_f32";
+  int rc = check_entry_call(who, plan, group, heads, csrptr_t, colind_t, entry_score);
+  if (rc != HG_OK) return rc;
+  hg::DropFields d = {};
+  if ((rc = check_dropout(who, p_drop, rng_dev, &d)) != HG_OK) return rc;
+  d.out_drop = alpha_drop_out;
+  return entry_attention(who, plan, group, heads, csrptr_t, colind_t, sv, se, entry_score, slope, &d, alpha_out, stream);
+}
+
+int hg_incidence_attention_entry_dropout_heads_bwd_f32(const hg_plan *plan, int32_t group, int32_t heads,
+                                                       const int32_t *csrptr_t, const int32_t *colind_t, const float *sv,
+                                                       const float *se, const float *entry_score, float slope,
+                                                       float p_drop, const uint64_t *rng_dev, const float *alpha,
+                                                       const float *dout, float *ds_out, float *dsv_out, float *dse_out,
+                                                       hg_stream_t stream) {
+  const char *who = "hg_incidence_attention_entry_dropout_heads_bwd_f32";
+  int rc = check_entry_call(who, plan, group, heads, csrptr_t, colind_t, entry_score);
+  if (rc != HG_OK) return rc;
+  hg::DropFields d = {};
+  if ((rc = check_dropout(who, p_drop, rng_dev, &d)) != HG_OK) return rc;
+  return entry_attention_bwd(who, plan, group, heads, csrptr_t, colind_t, sv, se, entry_score, slope, &d, alpha, dout, ds_out,
+                             dsv_out, dse_out, stream);
 }
 
 int hg_dropout_keep_host(uint64_t key, uint64_t sid, float p_drop, int64_t nnz, int32_t heads, uint8_t *keep_out) {

@@ -12,7 +12,18 @@ constexpr int kSegBlock = 256;  // threads per workgroup: 256 / width lane group
 constexpr int kSegKeep = 4;     // entries per lane whose gathered values stay in registers across the passes
 constexpr int kSegLong = 128;   // segments of more entries leave the lane groups for a whole workgroup
 
-enum { kSegSoftmax = 0, kSegSoftmaxBwd = 1, kSegSum = 2, kSegSoftmaxDrop = 3, kSegSoftmaxDropBwd = 4 };
+enum {
+  kSegSoftmax = 0,
+  kSegSoftmaxBwd = 1,
+  kSegSum = 2,
+  kSegSoftmaxDrop = 3,
+  kSegSoftmaxDropBwd = 4,
+  // the four softmax bodies with a logit per incidence added to the score (SegEntryArgs)
+  kSegSoftmaxEntry = 5,
+  kSegSoftmaxEntryBwd = 6,
+  kSegSoftmaxEntryDrop = 7,
+  kSegSoftmaxEntryDropBwd = 8
+};
 
 struct SegArgs {
   const int32_t *ptr;       // the side's CSR row pointers [nseg + 1]: csrptr_t, or the derived ptr_v
@@ -50,6 +61,13 @@ struct SegDropHeadsArgs : SegHeadsArgs {
   DropFields drop;
 };
 
+// The entry-logit bodies (kSegSoftmaxEntry*): raw[p, h] = (own + other) + entry[p, h].  One block for all four, the most
+// general one (heads and dropout; heads = 1 and an unused `drop` are the special cases), so that the family has one more
+// copy of the work split, not four.
+struct SegEntryArgs : SegDropHeadsArgs {
+  const float *entry;  // [nnz, heads], H_T order, head fastest: side 0 streams it, side 1 reaches it through perm
+};
+
 // Lane-group width of a side whose segments of at most kSegLong entries hold `mean` entries on average.
 int seg_width(double mean);
 // body: kSeg*; side 0 / 1; width 4 / 8 / 16 (seg_width)
@@ -60,5 +78,7 @@ hipError_t launch_segments_heads(int body, int side, int width, const SegHeadsAr
 // body: kSegSoftmaxDrop / kSegSoftmaxDropBwd, the same cut of the work
 hipError_t launch_segments_drop(int body, int side, int width, const SegDropArgs &a, hipStream_t stream);
 hipError_t launch_segments_drop_heads(int body, int side, int width, const SegDropHeadsArgs &a, hipStream_t stream);
+// body: kSegSoftmaxEntry*; heads >= 1; drop.rng is needed by the two dropout bodies only
+hipError_t launch_segments_entry(int body, int side, int width, const SegEntryArgs &a, hipStream_t stream);
 
 }  // namespace hg

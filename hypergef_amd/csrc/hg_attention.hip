@@ -32,6 +32,14 @@
 // sides and every width see the same one, and an entry beyond the kSegKeep kept ones recomputes it in each pass as it
 // gathers its score again.  The reductions are untouched, so alpha, t, ds and the sums have the bits of the plain bodies
 // on pre-masked input.  The instances above do not see any of this: NoDrop compiles to what was there.
+//
+// Entry logits (kSegSoftmaxEntry*, segment_entry_kernel).  The four softmax bodies with a logit per incidence, t [nnz, H]
+// in H_T order: raw = (own + other) + t[p], the bracket formed first, as before.  An Entry in place of NoEntry adds t as
+// the score is gathered: a kept entry folds it into the value it keeps in registers, an entry beyond the kept ones looks
+// up its position (side 1: perm) and gathers t again in each pass, as it gathers the score again.  Everything after raw
+// -- leaky relu, maximum, exponentials, reduction order, the mask -- is the code above, so t = 0 gives the bits of the
+// plain bodies.  The backward's ds is the gradient of t itself.  The four bodies share one kernel on the most general
+// argument block (heads and dropout): 24 instances and one more copy of the work split instead of 96 and four.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -95,6 +103,24 @@ __device__ __forceinline__ float raw_score(const SegArgs &a, Col<MH> col, float 
   return a.other ? own + a.other[col(a.ind[i])] : own;
 }
 
+// The logit of the entry itself (kSegSoftmaxEntry*): raw = (own + other) + t[p], p the entry's H_T position.  With NoEntry
+// the segment functions take the `else` of every `if constexpr (kEnt)`, which is the line that was there: the instances
+// without an entry logit stay instruction for instruction what they were (a wrapper around raw_score does not: it
+// changes the order of inlining, and with it the register allocation).
+struct NoEntry {};
+struct Entry {
+  const float *t;
+};
+template <bool MH>
+__device__ __forceinline__ float raw_entry(const SegArgs &a, const Entry &en, Col<MH> col, float own, int32_t i, int32_t p) {
+  return raw_score(a, col, own, i) + en.t[col(p)];
+}
+// the same for an entry whose position has not been looked up: only the entry logit needs it
+template <int SIDE, bool MH>
+__device__ __forceinline__ float raw_entry(const SegArgs &a, const Entry &en, Col<MH> col, float own, int32_t i) {
+  return raw_score(a, col, own, i) + en.t[col(position<SIDE>(a, i))];
+}
+
 __device__ __forceinline__ float leaky(float raw, float slope) { return raw > 0.f ? raw : slope * raw; }
 
 // The dropout of a launch as a lane holds it: the state read from device memory when the kernel runs (a seed passed by
@@ -119,10 +145,11 @@ __device__ __forceinline__ float dropped(const Drop &d, Col<MH> col, int32_t p, 
 
 // alpha = softmax over the segment of leaky(raw).  An empty segment runs no entry loop at all: nothing is written and no
 // exponential of (-inf) - (-inf) is formed.  A one-entry segment gives exp(0) / 1 = 1.0f exactly.
-template <int SIDE, int W, bool MH, typename DROP = NoDrop>
+template <int SIDE, int W, bool MH, typename DROP = NoDrop, typename ENT = NoEntry>
 __device__ __forceinline__ void softmax_segment(const SegArgs &a, Col<MH> col, int32_t seg, int32_t beg, int32_t end, int lane,
-                                                float *lds, const DROP &d = DROP{}) {
+                                                float *lds, const DROP &d = DROP{}, const ENT &en = ENT{}) {
   constexpr bool kDrop = std::is_same_v<DROP, Drop>;
+  constexpr bool kEnt = std::is_same_v<ENT, Entry>;
   const float own = (a.own && beg < end) ? a.own[col(seg)] : 0.f;
   float sc[kSegKeep];
   int32_t pos[kSegKeep];
@@ -132,13 +159,17 @@ __device__ __forceinline__ void softmax_segment(const SegArgs &a, Col<MH> col, i
     const int32_t i = beg + lane + k * W;
     if (i < end) {
       pos[k] = position<SIDE>(a, i);
-      sc[k] = leaky(raw_score(a, col, own, i), a.slope);
+      if constexpr (kEnt) sc[k] = leaky(raw_entry(a, en, col, own, i, pos[k]), a.slope);
+      else sc[k] = leaky(raw_score(a, col, own, i), a.slope);
       m = fmaxf(m, sc[k]);
     }
   }
   const int32_t tail = beg + lane + kSegKeep * W;
 #pragma unroll 4
-  for (int32_t i = tail; i < end; i += W) m = fmaxf(m, leaky(raw_score(a, col, own, i), a.slope));
+  for (int32_t i = tail; i < end; i += W) {
+    if constexpr (kEnt) m = fmaxf(m, leaky(raw_entry<SIDE>(a, en, col, own, i), a.slope));
+    else m = fmaxf(m, leaky(raw_score(a, col, own, i), a.slope));
+  }
   m = combine<W, OpMax>(m, lds);
   float sum = 0.f;
 #pragma unroll
@@ -149,7 +180,10 @@ __device__ __forceinline__ void softmax_segment(const SegArgs &a, Col<MH> col, i
     }
   }
 #pragma unroll 4
-  for (int32_t i = tail; i < end; i += W) sum += __expf(leaky(raw_score(a, col, own, i), a.slope) - m);
+  for (int32_t i = tail; i < end; i += W) {
+    if constexpr (kEnt) sum += __expf(leaky(raw_entry<SIDE>(a, en, col, own, i), a.slope) - m);
+    else sum += __expf(leaky(raw_score(a, col, own, i), a.slope) - m);
+  }
   sum = combine<W, OpSum>(sum, lds);
   const float inv = 1.f / sum;  // the entry holding the maximum contributes exp(0) = 1: sum >= 1 wherever it is used
 #pragma unroll
@@ -167,22 +201,31 @@ __device__ __forceinline__ void softmax_segment(const SegArgs &a, Col<MH> col, i
 #pragma unroll 2
     for (int32_t i = tail; i < end; i += W) {
       const int32_t p = position<SIDE>(a, i);
-      const float al = __expf(leaky(raw_score(a, col, own, i), a.slope) - m) * inv;
+      float al;
+      if constexpr (kEnt) al = __expf(leaky(raw_entry(a, en, col, own, i, p), a.slope) - m) * inv;
+      else al = __expf(leaky(raw_score(a, col, own, i), a.slope) - m) * inv;
       a.out_entry[col(p)] = al;
       d.out[col(p)] = dropped(d, col, p, al);
     }
   } else {
 #pragma unroll 4
-    for (int32_t i = tail; i < end; i += W)
-      a.out_entry[col(position<SIDE>(a, i))] = __expf(leaky(raw_score(a, col, own, i), a.slope) - m) * inv;
+    for (int32_t i = tail; i < end; i += W) {
+      if constexpr (kEnt) {
+        const int32_t p = position<SIDE>(a, i);
+        a.out_entry[col(p)] = __expf(leaky(raw_entry(a, en, col, own, i, p), a.slope) - m) * inv;
+      } else {
+        a.out_entry[col(position<SIDE>(a, i))] = __expf(leaky(raw_score(a, col, own, i), a.slope) - m) * inv;
+      }
+    }
   }
 }
 
 // ds = alpha * (dalpha - t) * leaky'(raw), t = sum over the segment of alpha * dalpha; the segment's own sum of ds goes to
 // out_seg (0 for an empty segment).  slope == 1: the non-linearity is the identity and no score is gathered.
-template <int SIDE, int W, bool MH, typename DROP = NoDrop>
+template <int SIDE, int W, bool MH, typename DROP = NoDrop, typename ENT = NoEntry>
 __device__ __forceinline__ void softmax_bwd_segment(const SegArgs &a, Col<MH> col, int32_t seg, int32_t beg, int32_t end, int lane,
-                                                    float *lds, bool valid, const DROP &d = DROP{}) {
+                                                    float *lds, bool valid, const DROP &d = DROP{}, const ENT &en = ENT{}) {
+  constexpr bool kEnt = std::is_same_v<ENT, Entry>;
   const bool need_raw = a.slope != 1.f;
   const float own = (need_raw && a.own && beg < end) ? a.own[col(seg)] : 0.f;
   float al[kSegKeep], da[kSegKeep], fac[kSegKeep];
@@ -195,7 +238,8 @@ __device__ __forceinline__ void softmax_bwd_segment(const SegArgs &a, Col<MH> co
       pos[k] = position<SIDE>(a, i);
       al[k] = a.val[col(pos[k])];
       da[k] = dropped(d, col, pos[k], a.dval[col(pos[k])]);
-      fac[k] = (need_raw && !(raw_score(a, col, own, i) > 0.f)) ? a.slope : 1.f;
+      if constexpr (kEnt) fac[k] = (need_raw && !(raw_entry(a, en, col, own, i, pos[k]) > 0.f)) ? a.slope : 1.f;
+      else fac[k] = (need_raw && !(raw_score(a, col, own, i) > 0.f)) ? a.slope : 1.f;
       t += al[k] * da[k];
     }
   }
@@ -218,7 +262,9 @@ __device__ __forceinline__ void softmax_bwd_segment(const SegArgs &a, Col<MH> co
 #pragma unroll 4
   for (int32_t i = tail; i < end; i += W) {
     const int32_t p = position<SIDE>(a, i);
-    const float f = (need_raw && !(raw_score(a, col, own, i) > 0.f)) ? a.slope : 1.f;
+    float f;
+    if constexpr (kEnt) f = (need_raw && !(raw_entry(a, en, col, own, i, p) > 0.f)) ? a.slope : 1.f;
+    else f = (need_raw && !(raw_score(a, col, own, i) > 0.f)) ? a.slope : 1.f;
     const float ds = a.val[col(p)] * (dropped(d, col, p, a.dval[col(p)]) - t) * f;
     a.out_entry[col(p)] = ds;
     dsum += ds;
@@ -247,14 +293,21 @@ __device__ __forceinline__ void run_segment(const ARGS &a, Col<MH> col, int32_t 
   else if constexpr (BODY == kSegSoftmaxDrop) softmax_segment<SIDE, W>(a, col, seg, beg, end, lane, lds, load_drop(a.drop));
   else if constexpr (BODY == kSegSoftmaxDropBwd)
     softmax_bwd_segment<SIDE, W>(a, col, seg, beg, end, lane, lds, valid, load_drop(a.drop));
+  else if constexpr (BODY == kSegSoftmaxEntry) softmax_segment<SIDE, W>(a, col, seg, beg, end, lane, lds, NoDrop{}, Entry{a.entry});
+  else if constexpr (BODY == kSegSoftmaxEntryBwd)
+    softmax_bwd_segment<SIDE, W>(a, col, seg, beg, end, lane, lds, valid, NoDrop{}, Entry{a.entry});
+  else if constexpr (BODY == kSegSoftmaxEntryDrop)
+    softmax_segment<SIDE, W>(a, col, seg, beg, end, lane, lds, load_drop(a.drop), Entry{a.entry});
+  else if constexpr (BODY == kSegSoftmaxEntryDropBwd)
+    softmax_bwd_segment<SIDE, W>(a, col, seg, beg, end, lane, lds, valid, load_drop(a.drop), Entry{a.entry});
   else sum_segment<SIDE, W>(a, col, seg, beg, end, lane, lds, valid);
 }
 
 // Workgroups [0, nlong): one long segment each (they run longest, so they start first); the others: 256 / W lane groups,
 // one segment each.  Lanes without a segment of their own (past the last one, or a long one's lane group) walk an empty
 // range and take part in the butterflies: no lane leaves before the last cross-lane step.
-// This cut of the work exists four times -- here, in segment_heads_kernel and in their two segment_drop_* copies below:
-// a change to it (the kSegLong rule, say) goes into all four.
+// This cut of the work exists five times -- here, in segment_heads_kernel, in their two segment_drop_* copies and in
+// segment_entry_kernel below: a change to it (the kSegLong rule, say) goes into all five.
 template <int BODY, int SIDE, int W>
 __global__ __launch_bounds__(kSegBlock) void segment_kernel(SegArgs a) {
   __shared__ float lds[kSegBlock / 64];
@@ -363,10 +416,43 @@ __global__ __launch_bounds__(kSegBlock) void segment_drop_heads_kernel(SegDropHe
   run_segment<BODY, SIDE, W>(a, Col<true>{H, h}, seg, beg, end, (int)threadIdx.x % W, lds, valid);
 }
 
-// ARGS = SegArgs: segment_kernel; ARGS = SegHeadsArgs: segment_heads_kernel; the dropout blocks: the *_drop_* kernels
+// The entry-logit bodies: segment_drop_heads_kernel's cut on the block that carries `entry` as well.  One kernel for the
+// four bodies, with and without heads or dropout: a single-head call runs it with H = 1 (Col<true>{1, 0} is the plain
+// index in 64 bits), a call without dropout leaves `drop` unread.
+template <int BODY, int SIDE, int W>
+__global__ __launch_bounds__(kSegBlock) void segment_entry_kernel(SegEntryArgs a) {
+  __shared__ float lds[kSegBlock / 64];
+  const int32_t H = a.heads;
+  const int64_t nlong = (int64_t)a.nlong * H;
+  if ((int64_t)blockIdx.x < nlong) {
+    const int32_t seg = a.long_seg[blockIdx.x / H];
+    run_segment<BODY, SIDE, kSegBlock>(a, Col<true>{H, (int32_t)(blockIdx.x % H)}, seg, a.ptr[seg], a.ptr[seg + 1],
+                                       (int)threadIdx.x, lds, true);
+    return;
+  }
+  constexpr int kGroups = kSegBlock / W;
+  const int64_t s = ((int64_t)blockIdx.x - nlong) * kGroups + (int)threadIdx.x / W;
+  bool valid = s < (int64_t)a.nseg * H;
+  const int32_t seg = valid ? (int32_t)(s / H) : 0;
+  const int32_t h = valid ? (int32_t)(s % H) : 0;
+  int32_t beg = 0, end = 0;
+  if (valid) {
+    beg = a.ptr[seg];
+    end = a.ptr[seg + 1];
+    if (end - beg > kSegLong) {  // a workgroup of its own has it
+      beg = end = 0;
+      valid = false;
+    }
+  }
+  run_segment<BODY, SIDE, W>(a, Col<true>{H, h}, seg, beg, end, (int)threadIdx.x % W, lds, valid);
+}
+
+// ARGS = SegEntryArgs: segment_entry_kernel; ARGS = SegArgs: segment_kernel; ARGS = SegHeadsArgs: segment_heads_kernel; the dropout blocks: the *_drop_* kernels
 template <int BODY, int SIDE, int W, typename ARGS>
 void launch_one(unsigned nblocks, const ARGS &a, hipStream_t stream) {
-  if constexpr (std::is_same_v<ARGS, SegDropHeadsArgs>)
+  if constexpr (std::is_same_v<ARGS, SegEntryArgs>)
+    hipLaunchKernelGGL((segment_entry_kernel<BODY, SIDE, W>), dim3(nblocks), dim3(kSegBlock), 0, stream, a);
+  else if constexpr (std::is_same_v<ARGS, SegDropHeadsArgs>)
     hipLaunchKernelGGL((segment_drop_heads_kernel<BODY, SIDE, W>), dim3(nblocks), dim3(kSegBlock), 0, stream, a);
   else if constexpr (std::is_same_v<ARGS, SegDropArgs>)
     hipLaunchKernelGGL((segment_drop_kernel<BODY, SIDE, W>), dim3(nblocks), dim3(kSegBlock), 0, stream, a);
@@ -401,7 +487,16 @@ hipError_t launch_body(int body, int side, int width, int64_t heads, const ARGS 
   const int64_t groups = kSegBlock / width;
   const int64_t nblocks = a.nlong * heads + (a.nseg * heads + groups - 1) / groups;
   if (nblocks > 0x7fffffff) return hipErrorInvalidValue;
-  if constexpr (std::is_base_of_v<SegDropArgs, ARGS> || std::is_base_of_v<SegDropHeadsArgs, ARGS>) {
+  if constexpr (std::is_same_v<ARGS, SegEntryArgs>) {
+    if (!a.entry) return hipErrorInvalidValue;
+    if ((body == kSegSoftmaxEntryDrop || body == kSegSoftmaxEntryDropBwd) && !a.drop.rng) return hipErrorInvalidValue;
+    switch (body) {
+      case kSegSoftmaxEntry: return launch_side<kSegSoftmaxEntry>(side, width, (unsigned)nblocks, a, stream);
+      case kSegSoftmaxEntryBwd: return launch_side<kSegSoftmaxEntryBwd>(side, width, (unsigned)nblocks, a, stream);
+      case kSegSoftmaxEntryDrop: return launch_side<kSegSoftmaxEntryDrop>(side, width, (unsigned)nblocks, a, stream);
+      case kSegSoftmaxEntryDropBwd: return launch_side<kSegSoftmaxEntryDropBwd>(side, width, (unsigned)nblocks, a, stream);
+    }
+  } else if constexpr (std::is_base_of_v<SegDropArgs, ARGS> || std::is_base_of_v<SegDropHeadsArgs, ARGS>) {
     if (!a.drop.rng) return hipErrorInvalidValue;
     switch (body) {
       case kSegSoftmaxDrop: return launch_side<kSegSoftmaxDrop>(side, width, (unsigned)nblocks, a, stream);
@@ -437,6 +532,11 @@ hipError_t launch_segments_drop(int body, int side, int width, const SegDropArgs
 }
 
 hipError_t launch_segments_drop_heads(int body, int side, int width, const SegDropHeadsArgs &a, hipStream_t stream) {
+  if (a.heads < 1) return hipErrorInvalidValue;
+  return launch_body(body, side, width, a.heads, a, stream);
+}
+
+hipError_t launch_segments_entry(int body, int side, int width, const SegEntryArgs &a, hipStream_t stream) {
   if (a.heads < 1) return hipErrorInvalidValue;
   return launch_body(body, side, width, a.heads, a, stream);
 }

@@ -115,11 +115,20 @@ class HypergraphAttnConv(nn.Module):
     [N, C]; the bias has the output's width.  heads = 1 is the single-head layer, parameter for parameter.
     dropout = p in (0, 1): in training mode the coefficients are dropped with probability p and the kept ones scaled by
     1 / (1 - p), inside the softmax kernels (ops.incidence_softmax(dropout=p)); the mask follows torch.manual_seed.  No
-    parameter and no buffer is added; eval() and dropout = 0.0 are the layer without it."""
+    parameter and no buffer is added; eval() and dropout = 0.0 are the layer without it.
+    score = 'additive' is the layer above.  score = 'dot' is transformer-style attention of every vertex to the hyperedges'
+    own embeddings: no a_v / a_e but a second bias-free linear lin_k (in_channels -> H * C), and
+        Kv = lin_k(X),   Ke[e] = mean_{u in e} Kv[u]   (0 for an empty hyperedge)                 (ops.incidence_gather),
+        logit[p = (e, u), h] = <Z[u, head h], Ke[e, head h]> * C ** -0.5                           (ops.incidence_dot),
+        alpha = softmax over each group of leaky_relu(logit, negative_slope)   (ops.incidence_softmax(incidence_score=)),
+    and Y as above; negative_slope = 1.0 is the plain softmax of the logits.  Parameters: lin.weight, lin_k.weight, bias."""
 
     def __init__(self, hyperg, in_channels, out_channels, group="hyperedge", negative_slope=0.2, options=None, heads=1,
-                 concat=True, dropout=0.0):
+                 concat=True, dropout=0.0, score="additive"):
         super().__init__()
+        if score not in ("additive", "dot"):
+            raise ValueError("score must be 'additive' or 'dot', got %r" % (score,))
+        self.score = score
         self.dropout = ops._dropout_p(dropout)
         if group not in ("hyperedge", "vertex"):
             raise ValueError("group must be 'hyperedge' or 'vertex', got %r" % (group,))
@@ -129,18 +138,34 @@ class HypergraphAttnConv(nn.Module):
         self.in_channels, self.out_channels = in_channels, out_channels
         self.heads, self.concat = heads, bool(concat)
         self.lin = ops.Linear(in_channels, heads * out_channels, bias=False, options=options)
-        bound = math.sqrt(6.0 / (out_channels + 1))
-        self.a_v = nn.Parameter(torch.empty(heads * out_channels).uniform_(-bound, bound))
-        self.a_e = nn.Parameter(torch.empty(heads * out_channels).uniform_(-bound, bound))
+        if score == "dot":
+            self.lin_k = ops.Linear(in_channels, heads * out_channels, bias=False, options=options)
+        else:
+            bound = math.sqrt(6.0 / (out_channels + 1))
+            self.a_v = nn.Parameter(torch.empty(heads * out_channels).uniform_(-bound, bound))
+            self.a_e = nn.Parameter(torch.empty(heads * out_channels).uniform_(-bound, bound))
         self.bias = nn.Parameter(torch.zeros(heads * out_channels if self.concat else out_channels))
         self.hyperg, self.degE, self.degV = hyperg, hyperg.degE, hyperg.degV
         self.Wdiag = torch.ones(hyperg.degE.shape[0]).to(hyperg.device)
         self._members = hyperg.H_T_colind.long()                                 # vertex of every incidence
         self._inv_size = torch.nan_to_num(hyperg.degE.reshape(-1), posinf=0.0)   # 1 / |e|, 0 for an empty hyperedge
 
-    def coefficients(self, Z):
-        """alpha for the projected features Z: [nnz], or [nnz, heads]; after dropout where the layer trains with one."""
+    def hyperedge_keys(self, X):
+        """score = 'dot': the hyperedges' own embeddings Ke [M, H * C], the mean of lin_k(X) over each hyperedge's members."""
+        return ops.incidence_gather(self.hyperg.H_T_csrptr, self.hyperg.H_T_colind, self.lin_k(X), None, to="hyperedge",
+                                    scale_a=self._inv_size, options=self.options)
+
+    def coefficients(self, Z, X=None):
+        """alpha for the projected features Z: [nnz], or [nnz, heads]; after dropout where the layer trains with one.
+        score = 'dot' needs the layer's input X as well (the keys are projected from it)."""
         ptr, ind = self.hyperg.H_T_csrptr, self.hyperg.H_T_colind
+        if self.score == "dot":
+            if X is None:
+                raise ValueError("score='dot': coefficients(Z, X) needs the layer's input X for the hyperedge keys")
+            logits = ops.incidence_dot(ptr, ind, Z, self.hyperedge_keys(X), heads=self.heads) * self.out_channels ** -0.5
+            return ops.incidence_softmax(ptr, ind, None, None, group=self.group, negative_slope=self.negative_slope,
+                                         options=self.options, num_nodes=Z.shape[0], heads=self.heads, dropout=self.dropout,
+                                         training=self.training, incidence_score=logits)
         if self.heads == 1:
             sv = Z @ self.a_v
             ze = (Z @ self.a_e)[self._members]
@@ -159,7 +184,7 @@ class HypergraphAttnConv(nn.Module):
 
     def forward(self, X):
         Z = self.lin(X)
-        alpha = self.coefficients(Z)
+        alpha = self.coefficients(Z, X)
         Y = ops.incidence_aggr(self.hyperg.H_T_csrptr, self.hyperg.H_T_colind, Z, alpha, alpha, self.degE, self.degV,
                                self.Wdiag, options=self.options, heads=self.heads)
         if self.heads > 1 and not self.concat:

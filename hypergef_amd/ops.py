@@ -653,7 +653,7 @@ def _dropout_p(dropout):
 
 def incidence_softmax(csrptr_t, indices_t, node_score=None, edge_score=None, group="hyperedge", negative_slope=0.2,
                       options=None, num_nodes=None, heads=1, dropout=0.0, training=True, rng_state=None,
-                      return_rng_state=False):
+                      return_rng_state=False, incidence_score=None):
     """Hypergraph attention's coefficients, alpha [nnz] aligned with indices_t: for every incidence p = (e, u)
     alpha[p] = softmax over p's group of leaky_relu(node_score[u] + edge_score[e], negative_slope); the group is p's
     hyperedge (group='hyperedge': the coefficients of a hyperedge's members sum to 1) or p's vertex (group='vertex').
@@ -669,19 +669,35 @@ def incidence_softmax(csrptr_t, indices_t, node_score=None, edge_score=None, gro
     depends on it, the position in indices_t and the head alone); None draws one with torch.randint on that device: it
     follows torch.manual_seed, costs no host synchronisation and, captured into a graph, gives every replay a new mask.
     return_rng_state=True returns (coefficients, the state used -- None where no dropout ran).  dropout = 0.0 or
-    training=False is the call above: the same code path, the same bits, torch's generator untouched."""
+    training=False is the call above: the same code path, the same bits, torch's generator untouched.
+    incidence_score: float32, nnz * heads elements ([nnz] / [nnz, H], aligned with indices_t, head fastest): a logit per
+    (vertex, hyperedge) pair, added to the score -- leaky_relu((node_score[u] + edge_score[e]) + incidence_score[p]) -- for
+    the scores that do not split into a vertex and a hyperedge term: scaled dot products (incidence_dot), GATv2, anything
+    that depends on the pair (hg_incidence_attention_entry_heads_f32).  node_score and edge_score may then both be None
+    (num_nodes is required, as whenever node_score is None).  Gradients are exact for all three; the gradient of
+    incidence_score is the backward kernel's own output, no further pass.  It works with heads, both groups and dropout.
+    None is the call above: the same code path, the same bits."""
     opt = _opt(options)
     p_drop = _dropout_p(dropout)
     if heads == 1:
-        sv, se = (_flat(t) if isinstance(t, torch.Tensor) else t for t in (node_score, edge_score))
+        sv, se, t = (_flat(x) if isinstance(x, torch.Tensor) else x for x in (node_score, edge_score, incidence_score))
     else:
         _heads(heads)
-        sv, se = (_per_head(t, heads) if isinstance(t, torch.Tensor) else t for t in (node_score, edge_score))
+        sv, se, t = (_per_head(x, heads) if isinstance(x, torch.Tensor) else x
+                     for x in (node_score, edge_score, incidence_score))
     if sv is None and num_nodes is None:
         raise ValueError("incidence_softmax needs node_score or num_nodes (the number of vertices)")
     N = int(num_nodes) if num_nodes is not None else sv.numel() // heads
     M = csrptr_t.numel() - 1 if isinstance(csrptr_t, torch.Tensor) else 0
     drop = p_drop > 0.0 and bool(training)
+    if t is not None:
+        nnz = indices_t.numel() if isinstance(indices_t, torch.Tensor) else 0
+        _segment_args("incidence_softmax", csrptr_t, indices_t,
+                      (("node_score", sv), ("edge_score", se), ("incidence_score", t)),
+                      (N * heads, M * heads, nnz * heads), group, opt, heads, rng_state if drop else None)
+        out, rng_state = _softmax_entry(csrptr_t, indices_t, sv, se, t, N, group, float(negative_slope), heads,
+                                        p_drop if drop else 0.0, rng_state)
+        return (out, rng_state if drop else None) if return_rng_state else out
     _segment_args("incidence_softmax", csrptr_t, indices_t, (("node_score", sv), ("edge_score", se)),
                   (N * heads, M * heads), group, opt, heads, rng_state if drop else None)
     slope = float(negative_slope)
@@ -705,6 +721,214 @@ def _softmax_dropout(csrptr_t, indices_t, sv, se, N, group, slope, heads, p_drop
         return _IncidenceSoftmaxDropout.apply(csrptr_t, indices_t, sv, se, N, group, slope, heads, p_drop, rng_state), rng_state
     plan = cached_plan(N, csrptr_t, indices_t)
     return plan.incidence_attention_dropout(csrptr_t, indices_t, sv, se, group, slope, p_drop, rng_state, heads=heads)[1], rng_state
+
+
+class _IncidenceSoftmaxEntry(torch.autograd.Function):
+    """_IncidenceSoftmax / _IncidenceSoftmaxDropout (p_drop > 0) with a logit per incidence t added to the score.  The
+    backward kernel's ds = alpha (dalpha - sum_g alpha dalpha) leaky' is the gradient of t; dsv / dse are its sums."""
+
+    @staticmethod
+    def forward(ctx, csrptr_t, indices_t, sv, se, t, N, group, slope, heads, p_drop, rng_state):
+        plan = cached_plan(N, csrptr_t, indices_t)
+        if p_drop > 0.0:
+            alpha, out = plan.incidence_attention_dropout(csrptr_t, indices_t, sv, se, group, slope, p_drop, rng_state,
+                                                          heads=heads, entry=t)
+        else:
+            alpha = out = plan.incidence_attention(csrptr_t, indices_t, sv, se, group, slope, heads=heads, entry=t)
+        ctx.save_for_backward(csrptr_t, indices_t, sv, se, t, alpha, rng_state)
+        ctx.N, ctx.group, ctx.slope, ctx.heads, ctx.p_drop = N, group, slope, heads, p_drop
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        csrptr_t, indices_t, sv, se, t, alpha, rng_state = ctx.saved_tensors
+        plan = cached_plan(ctx.N, csrptr_t, indices_t)
+        need_sv = sv is not None and ctx.needs_input_grad[2]
+        need_se = se is not None and ctx.needs_input_grad[3]
+        if ctx.p_drop > 0.0:
+            ds, dsv, dse = plan.incidence_attention_dropout_backward(
+                csrptr_t, indices_t, alpha, dout.contiguous(), sv, se, ctx.group, ctx.slope, ctx.p_drop, rng_state,
+                need_sv=need_sv, need_se=need_se, heads=ctx.heads, entry=t)
+        else:
+            ds, dsv, dse = plan.incidence_attention_backward(csrptr_t, indices_t, alpha, dout.contiguous(), sv, se, ctx.group,
+                                                             ctx.slope, need_sv=need_sv, need_se=need_se, heads=ctx.heads,
+                                                             entry=t)
+        dt = ds.view_as(t) if ctx.needs_input_grad[4] else None
+        return None, None, dsv, dse, dt, None, None, None, None, None, None
+
+
+def _softmax_entry(csrptr_t, indices_t, sv, se, t, N, group, slope, heads, p_drop, rng_state):
+    """(coefficients, the dropout state used or None) of incidence_softmax with incidence_score, its arguments checked."""
+    if p_drop > 0.0 and rng_state is None:  # drawn as _softmax_dropout draws it
+        info = torch.iinfo(torch.int64)
+        rng_state = torch.randint(info.min, info.max, (2,), dtype=torch.int64, device=csrptr_t.device)
+    if torch.is_grad_enabled() and any(x is not None and x.requires_grad for x in (sv, se, t)):
+        return _IncidenceSoftmaxEntry.apply(csrptr_t, indices_t, sv, se, t, N, group, slope, heads, p_drop, rng_state), rng_state
+    plan = cached_plan(N, csrptr_t, indices_t)
+    if p_drop > 0.0:
+        return plan.incidence_attention_dropout(csrptr_t, indices_t, sv, se, group, slope, p_drop, rng_state, heads=heads,
+                                                entry=t)[1], rng_state
+    return plan.incidence_attention(csrptr_t, indices_t, sv, se, group, slope, heads=heads, entry=t), None
+
+
+# ---- one weighted hop and the dot product per incidence (hg_gather_rows_incidence_heads_f32, hg_incidence_dot_heads_f32) ----
+
+_HOPS = ("hyperedge", "vertex")
+
+
+def _scaled(g, scale_a, scale_b):
+    for sc in (scale_a, scale_b):
+        if sc is not None:
+            g = g * sc.reshape(-1, 1)
+    return g.contiguous()
+
+
+def _hop(plan, csrptr_t, indices_t, to, src, w, scale_a, scale_b, heads):
+    """One hop on the plan: the weighted panels kernel of incidence_aggr's hop, or without weights the library's
+    unweighted row gather (Plan.gather_rows, hg_gather_rows_f32)."""
+    if w is None:
+        return plan.gather_rows(_HOPS.index(to), csrptr_t, indices_t, src, scale_a, scale_b)
+    return plan.gather_rows_incidence(to, csrptr_t, indices_t, src, w, scale_a, scale_b, heads=heads)
+
+
+class _IncidenceGather(torch.autograd.Function):
+    """dst = scale . (H_w^T src) (to 'hyperedge') or scale . (H_w src) (to 'vertex') and its exact gradients: with
+    gs = grad * scale, d src is the opposite hop of gs with the same weights and d weight[p = (e, u)] the product of the
+    vertex row and the hyperedge row of (src, gs) over each head's columns (incidence_dot).  The scales get none."""
+
+    @staticmethod
+    def forward(ctx, csrptr_t, indices_t, src, w, scale_a, scale_b, N, to, heads):
+        plan = cached_plan(N, csrptr_t, indices_t)
+        keep_src = w is not None and ctx.needs_input_grad[3]
+        ctx.save_for_backward(csrptr_t, indices_t, src if keep_src else None, w, scale_a, scale_b)
+        ctx.N, ctx.to, ctx.heads = N, to, heads
+        return _hop(plan, csrptr_t, indices_t, to, src, w, scale_a, scale_b, heads)
+
+    @staticmethod
+    def backward(ctx, grad):
+        csrptr_t, indices_t, src, w, scale_a, scale_b = ctx.saved_tensors
+        plan = cached_plan(ctx.N, csrptr_t, indices_t)
+        gs = _scaled(grad, scale_a, scale_b)
+        back = _HOPS[1 - _HOPS.index(ctx.to)]
+        gsrc = gw = None
+        if ctx.needs_input_grad[2]:
+            gsrc = _hop(plan, csrptr_t, indices_t, back, gs, w, None, None, ctx.heads)
+        if w is not None and ctx.needs_input_grad[3]:
+            A, B = (src, gs) if ctx.to == "hyperedge" else (gs, src)  # A: the vertex rows, B: the hyperedge rows
+            gw = plan.incidence_dot(csrptr_t, indices_t, A, B, heads=ctx.heads).view_as(w)
+        return None, None, gsrc, gw, None, None, None, None, None
+
+
+def incidence_gather(csrptr_t, indices_t, src, weight=None, to="hyperedge", scale_a=None, scale_b=None, heads=1,
+                     options=None, num_nodes=None):
+    """One weighted hop of the incidence path as an operator of its own.  to='hyperedge': src is [N, F] and
+    dst[e] = ((sum_{p=(e,u)} weight[p] * src[u]) * scale_a[e]) * scale_b[e], [M, F] -- hyperedge embeddings, e.g. the member
+    mean with scale_a = 1 / |e|; to='vertex': src is [M, F] and dst[v] = ((sum_{p=(e,v)} weight[p] * src[e]) * scale_a[v]) *
+    scale_b[v], [N, F].  weight: float32 [nnz] aligned with indices_t ([nnz, H] with heads = H, column h weighing head h's
+    columns h F/H .. (h + 1) F/H - 1), or None (unit weights); the scales hold one factor per row of dst, or None.
+    With weights it runs incidence_aggr's kernels for that hop (hg_gather_rows_incidence_heads_f32): hop 'hyperedge' into
+    hop 'vertex' gives incidence_aggr's result bit for bit; without, the unweighted row gather (hg_gather_rows_f32).
+    Differentiable in src and weight; the scales get no gradient, as elsewhere.  Options.variant 'auto' and 'pull' run;
+    the others raise ValueError.  float32 only (TypeError for bfloat16).  num_nodes: N for to='vertex', where src does not
+    tell it; without it N is the length of a given scale, else the largest member id + 1, read back from the device."""
+    opt = _opt(options)
+    if opt.variant not in ("auto", "pull"):
+        raise ValueError("incidence_gather runs the pull kernels: variant must be 'auto' or 'pull', got %r" % opt.variant)
+    _heads(heads)
+    if to not in _HOPS:
+        raise ValueError("to must be 'hyperedge' or 'vertex', got %r" % (to,))
+    w = weight
+    if isinstance(w, torch.Tensor):
+        w = _flat(w) if heads == 1 else _per_head(w, heads)
+    scale_a, scale_b = _flat(scale_a), _flat(scale_b)
+    for name, t in (("src", src), ("weight", w), ("scale_a", scale_a), ("scale_b", scale_b)):
+        if (t is not None or name == "src") and (not isinstance(t, torch.Tensor) or t.dtype != torch.float32):
+            raise TypeError("%s must be a float32 tensor (incidence_gather has no bfloat16 form), got %s"
+                            % (name, getattr(t, "dtype", type(t))))
+    if src.dim() != 2:
+        raise ValueError("src must be [rows, F]")
+    if src.shape[1] % heads:
+        raise ValueError("src's width %d is no multiple of heads = %d" % (src.shape[1], heads))
+    if not isinstance(csrptr_t, torch.Tensor) or not isinstance(indices_t, torch.Tensor):
+        raise TypeError("csrptr_t and indices_t must be int32 tensors")
+    nnz, M = indices_t.numel(), csrptr_t.numel() - 1
+    if w is not None and w.numel() != nnz * heads:
+        raise ValueError("weight must have one weight per incidence%s (%d elements), got %d"
+                         % (" and head" if heads > 1 else "", nnz * heads, w.numel()))
+    if to == "hyperedge":
+        N = src.shape[0]
+        if num_nodes is not None and int(num_nodes) != N:
+            raise ValueError("src has %d rows, num_nodes is %d" % (N, int(num_nodes)))
+    elif src.shape[0] != M:
+        raise ValueError("src has %d rows, the hypergraph has %d hyperedges" % (src.shape[0], M))
+    else:
+        N = int(num_nodes) if num_nodes is not None else next((t.numel() for t in (scale_a, scale_b) if t is not None), None)
+    for name, t in (("scale_a", scale_a), ("scale_b", scale_b)):
+        if t is not None and t.numel() != (M if to == "hyperedge" else N):
+            raise ValueError("%s must have one factor per row of the result (%d), got %d"
+                             % (name, M if to == "hyperedge" else N, t.numel()))
+    _check_index(csrptr_t, "csrptr_t")
+    _check_index(indices_t, "indices_t")
+    _check_feat(src, "src")
+    for name, t in (("weight", w), ("scale_a", scale_a), ("scale_b", scale_b)):
+        if t is not None:
+            _check_feat(t, name, device=src.device)
+    if N is None:
+        N = int(indices_t.max()) + 1 if nnz else 0
+    if not (torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (src, w))):
+        return _hop(cached_plan(N, csrptr_t, indices_t), csrptr_t, indices_t, to, src, w, scale_a, scale_b, heads)
+    return _IncidenceGather.apply(csrptr_t, indices_t, src, w, scale_a, scale_b, N, to, heads)
+
+
+class _IncidenceDot(torch.autograd.Function):
+    """out[p, h] = <A[u, head h], B[e, head h]> and its gradients, one weighted hop each: dA = the hop to the vertices of B
+    weighted by the incoming gradient, dB = the hop to the hyperedges of A."""
+
+    @staticmethod
+    def forward(ctx, csrptr_t, indices_t, A, B, heads):
+        plan = cached_plan(A.shape[0], csrptr_t, indices_t)
+        ctx.save_for_backward(csrptr_t, indices_t, A if ctx.needs_input_grad[3] else None, B if ctx.needs_input_grad[2] else None)
+        ctx.N, ctx.heads = A.shape[0], heads
+        return plan.incidence_dot(csrptr_t, indices_t, A, B, heads=heads)
+
+    @staticmethod
+    def backward(ctx, grad):
+        csrptr_t, indices_t, A, B = ctx.saved_tensors
+        plan = cached_plan(ctx.N, csrptr_t, indices_t)
+        g = grad.contiguous()
+        dA = dB = None
+        if ctx.needs_input_grad[2]:
+            dA = plan.gather_rows_incidence("vertex", csrptr_t, indices_t, B, g, heads=ctx.heads)
+        if ctx.needs_input_grad[3]:
+            dB = plan.gather_rows_incidence("hyperedge", csrptr_t, indices_t, A, g, heads=ctx.heads)
+        return None, None, dA, dB, None
+
+
+def incidence_dot(csrptr_t, indices_t, A, B, heads=1):
+    """The dot-product logit of every incidence p = (e, u): out[p] = <A[u], B[e]> for A [N, F] (a row per vertex) and B [M, F]
+    (a row per hyperedge), [nnz] aligned with indices_t (hg_incidence_dot_f32).  heads = H > 1: A and B are [*, H * C],
+    out[p, h] is the product over head h's columns and comes back [nnz, H].  Scaled by C ** -0.5 it is what
+    incidence_softmax takes as incidence_score.  Differentiable in A and B: with g the incoming gradient,
+    dA = incidence_gather(B, g, to='vertex') and dB = incidence_gather(A, g, to='hyperedge').  float32 only."""
+    _heads(heads)
+    for name, t in (("A", A), ("B", B)):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32:
+            raise TypeError("%s must be a float32 tensor (incidence_dot has no bfloat16 form), got %s"
+                            % (name, getattr(t, "dtype", type(t))))
+    if not isinstance(csrptr_t, torch.Tensor) or not isinstance(indices_t, torch.Tensor):
+        raise TypeError("csrptr_t and indices_t must be int32 tensors")
+    M = csrptr_t.numel() - 1
+    if A.dim() != 2 or B.dim() != 2 or A.shape[1] != B.shape[1] or B.shape[0] != M:
+        raise ValueError("A must be [N, F] and B [M = %d, F] of one width, got %s and %s" % (M, tuple(A.shape), tuple(B.shape)))
+    if A.shape[1] % heads:
+        raise ValueError("the width %d is no multiple of heads = %d" % (A.shape[1], heads))
+    _check_index(csrptr_t, "csrptr_t")
+    _check_index(indices_t, "indices_t")
+    _check_feat(A, "A")
+    _check_feat(B, "B", device=A.device)
+    if not (torch.is_grad_enabled() and (A.requires_grad or B.requires_grad)):
+        return cached_plan(A.shape[0], csrptr_t, indices_t).incidence_dot(csrptr_t, indices_t, A, B, heads=heads)
+    return _IncidenceDot.apply(csrptr_t, indices_t, A, B, heads)
 
 
 class _IncidenceSum(torch.autograd.Function):

@@ -409,6 +409,43 @@ class Plan:
                 _ptr(dst), _ptr(workspace), nbytes, _stream_handle(src.device)))
         return dst
 
+    def gather_rows_incidence(self, hop, csrptr_t, colind_t, src, w=None, scaleA=None, scaleB=None, heads=1, out=None,
+                              workspace=None):
+        """One hop of aggregate_incidence as a call of its own (hg_gather_rows_incidence_heads_f32): hop 0 / 'hyperedge',
+        dst[e] = ((sum_{p=(e,u)} w[p] src[u]) * scaleA[e]) * scaleB[e] with src [N, F] and dst [M, F]; hop 1 / 'vertex' the
+        mirror, src [M, F] and dst [N, F].  w: float32 [nnz] in H_T order ([nnz, H] with heads = H, column h weighing head
+        h's columns), or None (unit weights); the scales have one factor per row of dst.  The schedule, kernels and bits
+        are those of aggregate_incidence's hop.  The first hop-1 call with w uploads the plan's permutation: not capturable."""
+        heads = _heads(heads)
+        hop = _side(hop)
+        _check_feat(src, "src")
+        nsrc, ndst = (self.N, self.M) if hop == 0 else (self.M, self.N)
+        if src.dim() != 2 or src.shape[0] != nsrc:
+            raise ValueError("src must be [%d, F]" % nsrc)
+        F = src.shape[1]
+        if F % heads:
+            raise ValueError("F = %d is no multiple of heads = %d" % (F, heads))
+        for name, t, n in (("w", w, self.nnz * heads), ("scaleA", scaleA, ndst), ("scaleB", scaleB, ndst)):
+            if t is not None:
+                _check_feat(t, name, device=src.device)
+                if t.numel() != n:
+                    raise ValueError("%s must have %d elements, got %d" % (name, n, t.numel()))
+        if out is not None:
+            _check_feat(out, "out", device=src.device)
+            if tuple(out.shape) != (ndst, F):
+                raise ValueError("out must be [%d, %d]" % (ndst, F))
+        dst = out if out is not None else torch.empty((ndst, F), dtype=torch.float32, device=src.device)
+        nbytes = self.incidence_workspace_bytes(F)
+        if workspace is None:
+            workspace = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=src.device)
+        else:
+            nbytes = workspace.numel() * workspace.element_size()
+        with torch.cuda.device(src.device):
+            _lib.check(_lib.lib().hg_gather_rows_incidence_heads_f32(
+                self._h, hop, F, heads, _ptr(csrptr_t), _ptr(colind_t), _ptr(src), _ptr(w), _ptr(scaleA), _ptr(scaleB),
+                _ptr(dst), _ptr(workspace), nbytes, _stream_handle(src.device)))
+        return dst
+
     def incidence_perm(self):
         """Host copy (numpy int32 [nnz]) of perm[q] = the H_T position of H entry q: the stable transpose behind
         vertex_csr(), by which hop 2 of aggregate_incidence reads e2v.  Works on host-only plans too."""
@@ -498,8 +535,9 @@ class Plan:
         _lib.check(_lib.lib().hg_plan_get_segment_info(self._h, side, info, rows.ctypes.data_as(ctypes.c_void_p)))
         return {"width": info[0], "keep": info[1], "long": info[2], "long_rows": rows}
 
-    def _scores(self, sv, se, device=None, heads=1):
-        for name, t, n in (("node_score", sv, self.N * heads), ("edge_score", se, self.M * heads)):
+    def _scores(self, sv, se, device=None, heads=1, entry=None):
+        for name, t, n in (("node_score", sv, self.N * heads), ("edge_score", se, self.M * heads),
+                           ("incidence_score", entry, self.nnz * heads)):
             if t is not None:
                 _check_feat(t, name, device=device)
                 device = t.device
@@ -507,16 +545,21 @@ class Plan:
                     raise ValueError("%s must have %d elements, got %d" % (name, n, t.numel()))
         return device
 
-    def incidence_attention(self, csrptr_t, colind_t, sv=None, se=None, group="hyperedge", slope=0.2, out=None, heads=1):
+    def incidence_attention(self, csrptr_t, colind_t, sv=None, se=None, group="hyperedge", slope=0.2, out=None, heads=1,
+                            entry=None):
         """alpha [nnz] in H_T order: the softmax over each hyperedge's members (group 'hyperedge') or each vertex's
         hyperedges ('vertex') of leaky_relu(sv[u] + se[e], slope) (hg_incidence_attention_f32).  sv [N], se [M]: float32,
         or None (0).  heads = H > 1 (hg_incidence_attention_heads_f32): sv [N, H], se [M, H], alpha [nnz, H], a softmax
-        per head.  The first call of a form builds and uploads what it needs from the plan: not capturable."""
+        per head.  The first call of a form builds and uploads what it needs from the plan: not capturable.
+        entry: float32 [nnz] / [nnz, H] in H_T order, a logit per incidence added to the score, raw = (sv[u] + se[e]) +
+        entry[p] (hg_incidence_attention_entry_heads_f32); None is the call without one."""
         heads = _heads(heads)
         group = _side(group)
         _check_index(csrptr_t, "csrptr_t")
         _check_index(colind_t, "indices_t")
-        device = self._scores(sv, se, csrptr_t.device, heads)
+        device = self._scores(sv, se, csrptr_t.device, heads, entry)
+        if self.nnz == 0:
+            entry = None  # nothing to add it to (and an empty tensor has no address to pass)
         if out is None:
             out = torch.empty(_per_head(self.nnz, heads), dtype=torch.float32, device=device)
         else:
@@ -524,7 +567,11 @@ class Plan:
             if out.numel() != self.nnz * heads:
                 raise ValueError("out must have nnz * heads = %d elements" % (self.nnz * heads))
         with torch.cuda.device(device):
-            if heads == 1:
+            if entry is not None:
+                _lib.check(_lib.lib().hg_incidence_attention_entry_heads_f32(
+                    self._h, group, heads, _ptr(csrptr_t), _ptr(colind_t), _ptr(sv), _ptr(se), _ptr(entry), float(slope),
+                    _ptr(out), _stream_handle(device)))
+            elif heads == 1:
                 _lib.check(_lib.lib().hg_incidence_attention_f32(self._h, group, _ptr(csrptr_t), _ptr(colind_t), _ptr(sv),
                                                                  _ptr(se), float(slope), _ptr(out), _stream_handle(device)))
             else:
@@ -534,10 +581,11 @@ class Plan:
         return out
 
     def incidence_attention_backward(self, csrptr_t, colind_t, alpha, dalpha, sv=None, se=None, group="hyperedge",
-                                     slope=0.2, need_sv=True, need_se=True, heads=1):
+                                     slope=0.2, need_sv=True, need_se=True, heads=1, entry=None):
         """(ds [nnz], dsv [N] or None, dse [M] or None) for alpha = incidence_attention(...) and its gradient dalpha
         (hg_incidence_attention_bwd_f32); sv / se as in the forward (they decide the leaky branch).  heads = H > 1
-        (hg_incidence_attention_heads_bwd_f32): every array has a trailing dimension H."""
+        (hg_incidence_attention_heads_bwd_f32): every array has a trailing dimension H.  entry: the forward's logit per
+        incidence (hg_incidence_attention_entry_heads_bwd_f32); ds is then its gradient."""
         heads = _heads(heads)
         group = _side(group)
         _check_index(csrptr_t, "csrptr_t")
@@ -548,12 +596,18 @@ class Plan:
             if t.numel() != self.nnz * heads:
                 raise ValueError("%s must have nnz%s = %d elements, got %d" % (name, " * heads" if heads > 1 else "",
                                                                               self.nnz * heads, t.numel()))
-        device = self._scores(sv, se, alpha.device, heads)
+        device = self._scores(sv, se, alpha.device, heads, entry)
+        if self.nnz == 0:
+            entry = None
         ds = torch.empty(_per_head(self.nnz, heads), dtype=torch.float32, device=device)
         dsv = torch.empty(_per_head(self.N, heads), dtype=torch.float32, device=device) if need_sv else None
         dse = torch.empty(_per_head(self.M, heads), dtype=torch.float32, device=device) if need_se else None
         with torch.cuda.device(device):
-            if heads == 1:
+            if entry is not None:
+                _lib.check(_lib.lib().hg_incidence_attention_entry_heads_bwd_f32(
+                    self._h, group, heads, _ptr(csrptr_t), _ptr(colind_t), _ptr(sv), _ptr(se), _ptr(entry), float(slope),
+                    _ptr(alpha), _ptr(dalpha), _ptr(ds), _ptr(dsv), _ptr(dse), _stream_handle(device)))
+            elif heads == 1:
                 _lib.check(_lib.lib().hg_incidence_attention_bwd_f32(
                     self._h, group, _ptr(csrptr_t), _ptr(colind_t), _ptr(sv), _ptr(se), float(slope), _ptr(alpha),
                     _ptr(dalpha), _ptr(ds), _ptr(dsv), _ptr(dse), _stream_handle(device)))
@@ -570,27 +624,34 @@ class Plan:
         return _ptr(rng_state)
 
     def incidence_attention_dropout(self, csrptr_t, colind_t, sv=None, se=None, group="hyperedge", slope=0.2, p_drop=0.5,
-                                    rng_state=None, heads=1):
+                                    rng_state=None, heads=1, entry=None):
         """(alpha, alpha_drop): incidence_attention's coefficients and, from the same launch, the coefficients after dropout,
         alpha_drop = keep ? alpha / (1 - p_drop) : 0 (hg_incidence_attention_dropout_heads_f32).  rng_state: int64 [2] on
         the scores' device, {key, sid} of the Philox mask; the kernel reads it when it runs.  keep depends on (rng_state,
-        H_T position, head) alone; no mask is stored.  [nnz], or [nnz, heads]."""
+        H_T position, head) alone; no mask is stored.  [nnz], or [nnz, heads].  entry: as in incidence_attention
+        (hg_incidence_attention_entry_dropout_heads_f32)."""
         heads = _heads(heads)
         group = _side(group)
         _check_index(csrptr_t, "csrptr_t")
         _check_index(colind_t, "indices_t")
-        device = self._scores(sv, se, csrptr_t.device, heads)
+        device = self._scores(sv, se, csrptr_t.device, heads, entry)
         rng = self._rng_ptr(rng_state, device)
         alpha = torch.empty(_per_head(self.nnz, heads), dtype=torch.float32, device=device)
         alpha_drop = torch.empty_like(alpha)
         with torch.cuda.device(device):
+            if entry is not None and self.nnz > 0:
+                _lib.check(_lib.lib().hg_incidence_attention_entry_dropout_heads_f32(
+                    self._h, group, heads, _ptr(csrptr_t), _ptr(colind_t), _ptr(sv), _ptr(se), _ptr(entry), float(slope),
+                    float(p_drop), rng, _ptr(alpha), _ptr(alpha_drop), _stream_handle(device)))
+                return alpha, alpha_drop
             _lib.check(_lib.lib().hg_incidence_attention_dropout_heads_f32(
                 self._h, group, heads, _ptr(csrptr_t), _ptr(colind_t), _ptr(sv), _ptr(se), float(slope), float(p_drop), rng,
                 _ptr(alpha), _ptr(alpha_drop), _stream_handle(device)))
         return alpha, alpha_drop
 
     def incidence_attention_dropout_backward(self, csrptr_t, colind_t, alpha, dout, sv=None, se=None, group="hyperedge",
-                                             slope=0.2, p_drop=0.5, rng_state=None, need_sv=True, need_se=True, heads=1):
+                                             slope=0.2, p_drop=0.5, rng_state=None, need_sv=True, need_se=True, heads=1,
+                                             entry=None):
         """(ds, dsv or None, dse or None) for (alpha, alpha_drop) = incidence_attention_dropout(...) and dout, the gradient
         of alpha_drop: incidence_attention_backward on dalpha = keep ? dout / (1 - p_drop) : 0, the mask regenerated from
         rng_state (hg_incidence_attention_dropout_heads_bwd_f32)."""
@@ -604,12 +665,17 @@ class Plan:
             if t.numel() != self.nnz * heads:
                 raise ValueError("%s must have nnz%s = %d elements, got %d" % (name, " * heads" if heads > 1 else "",
                                                                               self.nnz * heads, t.numel()))
-        device = self._scores(sv, se, alpha.device, heads)
+        device = self._scores(sv, se, alpha.device, heads, entry)
         rng = self._rng_ptr(rng_state, device)
         ds = torch.empty(_per_head(self.nnz, heads), dtype=torch.float32, device=device)
         dsv = torch.empty(_per_head(self.N, heads), dtype=torch.float32, device=device) if need_sv else None
         dse = torch.empty(_per_head(self.M, heads), dtype=torch.float32, device=device) if need_se else None
         with torch.cuda.device(device):
+            if entry is not None and self.nnz > 0:  # the forward's logit per incidence: ds is its gradient
+                _lib.check(_lib.lib().hg_incidence_attention_entry_dropout_heads_bwd_f32(
+                    self._h, group, heads, _ptr(csrptr_t), _ptr(colind_t), _ptr(sv), _ptr(se), _ptr(entry), float(slope),
+                    float(p_drop), rng, _ptr(alpha), _ptr(dout), _ptr(ds), _ptr(dsv), _ptr(dse), _stream_handle(device)))
+                return ds, dsv, dse
             _lib.check(_lib.lib().hg_incidence_attention_dropout_heads_bwd_f32(
                 self._h, group, heads, _ptr(csrptr_t), _ptr(colind_t), _ptr(sv), _ptr(se), float(slope), float(p_drop), rng,
                 _ptr(alpha), _ptr(dout), _ptr(ds), _ptr(dsv), _ptr(dse), _stream_handle(device)))

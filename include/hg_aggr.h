@@ -527,6 +527,58 @@ HG_API int hg_incidence_attention_dropout_heads_bwd_f32(const hg_plan *plan, int
                                                         float *dsv_out, float *dse_out, hg_stream_t stream);
 HG_API int hg_dropout_keep_host(uint64_t key, uint64_t sid, float p_drop, int64_t nnz, int32_t heads, uint8_t *keep_out);
 
+/* ---- a logit per incidence ------------------------------------------------------------------------------------------------
+ * The softmax entries above form raw = sv[u] + se[e] themselves, so a score must split into a vertex term plus a hyperedge
+ * term.  These take one more input, entry_score [nnz, heads] in H_T order (row p aligned with colind_t[p], head fastest):
+ *     raw[p, h] = (sv[u, h] + se[e, h]) + entry_score[p, h]          the bracket is formed first; a NULL sv / se adds +0
+ *   and are the *_heads_f32 / *_dropout_heads_f32 entries from there on: leaky relu, maximum, exponentials, order of
+ *   reduction, rows above 128 entries on a workgroup, the Philox mask.  entry_score = 0 gives their bits, and so does
+ *   entry_score = fl(sv[u] + se[e]) with sv = se = NULL (for scores without a -0.0).  A dot-product logit
+ *   (hg_incidence_dot_heads_f32), GATv2's, or any score of the pair (u, e) goes here.
+ * *_bwd_f32: the leaky factor takes the sign of the same three-term raw; ds_out [nnz, heads] is the gradient of entry_score
+ *   itself, no further pass; dsv_out / dse_out (NULL: not wanted) are its sums as above.
+ * Side 0 streams entry_score, side 1 reaches it through the plan's permutation as it reaches alpha.  No atomics; two
+ *   calls give the same bits.  heads = 1 is the single-head layout.
+ * Refusals, nothing launched: HG_ERR_INVALID for a null plan, heads < 1, a group other than 0 / 1 or a NULL entry_score
+ *   (decided in this order, before the plan is looked at); HG_ERR_UNSUPPORTED for a plan built with HG_PLAN_HOST_ONLY;
+ *   then HG_ERR_INVALID for a null array, a non-finite slope, p_drop outside [0, 1) or a bad rng_dev, as above.  The
+ *   first-call-allocates rule is the other entries', and what is allocated is shared with them: a call captured into a
+ *   hipGraph replays correctly after one warm call of the same group.
+ * hg_gather_rows_incidence_heads_f32: one hop of hg_aggr_incidence_heads_f32 as an entry of its own,
+ *     hop 0: dst[e, c] = ((sum_{p=(e,u)} w[p, c / C] * src[u, c]) * scaleA[e]) * scaleB[e]     src [N, F], dst [M, F]
+ *     hop 1: dst[v, c] = ((sum_{p=(e,v)} w[p, c / C] * src[e, c]) * scaleA[v]) * scaleB[v]     src [M, F], dst [N, F]
+ *   w: [nnz, heads] in H_T order (hop 1 reads it through the permutation), or NULL (unit weights); scaleA / scaleB: one
+ *   factor per row of dst, or NULL.  It is the function hg_aggr_incidence*_f32 runs twice: the same schedule choice, LDS
+ *   check, streaming-store choice and kernel instances, so hop 0 into hop 1 with (degE, W) and (degV, NULL) gives that
+ *   entry's Xe_out and Y bit for bit.  It is the backward of hg_incidence_dot_heads_f32: dB = hop 0 of (A, g), dA = hop 1
+ *   of (B, g).  workspace: hg_aggr_incidence_workspace_bytes(plan, F).  HG_ERR_INVALID for hop outside 0 / 1 (decided
+ *   first), heads < 1 or F % heads != 0; HG_ERR_UNSUPPORTED for a host-only plan and where hg_aggr_incidence_f32 returns it.
+ * Detect these entries by their exported symbols (HG_AGGR_VERSION does not change). */
+HG_API int hg_incidence_attention_entry_heads_f32(const hg_plan *plan, int32_t group, int32_t heads, const int32_t *csrptr_t,
+                                                  const int32_t *colind_t, const float *sv, const float *se,
+                                                  const float *entry_score, float slope, float *alpha_out,
+                                                  hg_stream_t stream);
+HG_API int hg_incidence_attention_entry_heads_bwd_f32(const hg_plan *plan, int32_t group, int32_t heads,
+                                                      const int32_t *csrptr_t, const int32_t *colind_t, const float *sv,
+                                                      const float *se, const float *entry_score, float slope,
+                                                      const float *alpha, const float *dalpha, float *ds_out,
+                                                      float *dsv_out, float *dse_out, hg_stream_t stream);
+HG_API int hg_incidence_attention_entry_dropout_heads_f32(const hg_plan *plan, int32_t group, int32_t heads,
+                                                          const int32_t *csrptr_t, const int32_t *colind_t, const float *sv,
+                                                          const float *se, const float *entry_score, float slope,
+                                                          float p_drop, const uint64_t *rng_dev, float *alpha_out,
+                                                          float *alpha_drop_out, hg_stream_t stream);
+HG_API int hg_incidence_attention_entry_dropout_heads_bwd_f32(const hg_plan *plan, int32_t group, int32_t heads,
+                                                              const int32_t *csrptr_t, const int32_t *colind_t,
+                                                              const float *sv, const float *se, const float *entry_score,
+                                                              float slope, float p_drop, const uint64_t *rng_dev,
+                                                              const float *alpha, const float *dout, float *ds_out,
+                                                              float *dsv_out, float *dse_out, hg_stream_t stream);
+HG_API int hg_gather_rows_incidence_heads_f32(const hg_plan *plan, int32_t hop, int32_t F, int32_t heads,
+                                              const int32_t *csrptr_t, const int32_t *colind_t, const float *src,
+                                              const float *w, const float *scaleA, const float *scaleB, float *dst,
+                                              void *workspace, size_t workspace_bytes, hg_stream_t stream);
+
 /* first_aggr = "max" pieces (hgnnaggr_max, source/hgnnaggr/hgnnaggr_cuda.cu:144-208).
  * hg_gather_max_f32: Xe[e,k] = (max_{u in e} X[u,k], start -1e5, strict >) * (degE[e]*W[e]),
  * record[e,k] = winning vertex (0 if none).  The second hop is hg_gather_rows_f32(hop = 1).
