@@ -32,6 +32,7 @@ SYMBOLS = (
     "hg_version", "hg_last_error", "hg_status_string", "hg_balance_schedule", "hg_mtx_read", "hg_free",
     "hg_plan_create_host", "hg_plan_create_device", "hg_plan_destroy", "hg_plan_get_info",
     "hg_plan_get_vertex_csr", "hg_plan_get_vertex_csr_device", "hg_plan_get_schedule", "hg_plan_prepare", "hg_plan_auto_variant", "hg_plan_bind_scales", "hg_plan_tune_f32",
+    "hg_plan_set_choice", "hg_plan_has_latency_schedule",
     "hg_plan_workspace_bytes",
     "hg_aggr_fused_f32", "hg_aggr_fused_bf16", "hg_linear_pack_f32", "hg_linear_pack_ex_f32", "hg_linear_pack_floats", "hg_linear_rows_f32", "hg_linear_wgrad_workspace_bytes", "hg_linear_wgrad_f32", "hg_aggr_linear_workspace_bytes", "hg_aggr_linear_f32", "hg_aggr_linear_res_f32", "hg_aggr_linear_res_dev_f32",
     "hg_gather_rows_f32", "hg_aggr_push_groups_f32", "hg_gather_max_f32",
@@ -143,6 +144,11 @@ def lib():
     L.hg_plan_prepare.argtypes = [vp, i32, ctypes.POINTER(FusedInfo)]
     L.hg_plan_tune_f32.restype = ctypes.c_int
     L.hg_plan_tune_f32.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, sz, i32, vp, ctypes.POINTER(TuneInfo)]
+    if hasattr(L, "hg_plan_set_choice"):  # detected by export (an HG_AGGR_LIB build of an older tree lacks them)
+        L.hg_plan_set_choice.restype = ctypes.c_int
+        L.hg_plan_set_choice.argtypes = [vp, i32, i32, i32]
+        L.hg_plan_has_latency_schedule.restype = ctypes.c_int
+        L.hg_plan_has_latency_schedule.argtypes = [vp]
     L.hg_linear_pack_f32.restype = ctypes.c_int
     L.hg_linear_pack_f32.argtypes = [i32, i32, vp, vp, vp]
     L.hg_linear_pack_ex_f32.restype = ctypes.c_int

@@ -1493,6 +1493,47 @@ int hg_plan_tune_f32(const hg_plan *plan, int32_t F, const int32_t *csrptr_t, co
   return rc;
 }
 
+int hg_plan_set_choice(const hg_plan *plan, int32_t F, int32_t variant, int32_t pull_hop_kernels) {
+  if (!plan || F < 1) {
+    hg::set_error("hg_plan_set_choice: null plan or feature width below 1");
+    return HG_ERR_INVALID;
+  }
+  hg_plan *mp = const_cast<hg_plan *>(plan);
+  if (variant == HG_VARIANT_AUTO) {  // back to the static rule (and to the streaming kernel where it applies)
+    std::lock_guard<std::mutex> lock(mp->auto_mu);
+    mp->auto_choice.erase((int64_t)F * 2);
+    mp->auto_choice.erase((int64_t)F * 2 + 1);
+    mp->hop_kernel.erase(F);
+    return HG_OK;
+  }
+  if (variant != HG_VARIANT_FUSED && variant != HG_VARIANT_PULL) {
+    hg::set_error("hg_plan_set_choice: variant must be HG_VARIANT_FUSED, HG_VARIANT_PULL or HG_VARIANT_AUTO (remove the pin)");
+    return HG_ERR_INVALID;
+  }
+  if (pull_hop_kernels < 0 || pull_hop_kernels > 8) {
+    hg::set_error("hg_plan_set_choice: pull_hop_kernels must be k0 + 3 * k1 with both kernels in 0 .. 2");
+    return HG_ERR_INVALID;
+  }
+  if (!plan->has_lat && (pull_hop_kernels % 3 == 2 || pull_hop_kernels / 3 == 2)) {
+    hg::set_error("hg_plan_set_choice: kernel 2 needs the latency schedule, which this plan does not have "
+                  "(hg_plan_has_latency_schedule)");
+    return HG_ERR_INVALID;
+  }
+  std::lock_guard<std::mutex> lock(mp->auto_mu);
+  mp->auto_choice[(int64_t)F * 2] = variant;
+  mp->auto_choice[(int64_t)F * 2 + 1] = variant;
+  mp->hop_kernel[F] = pull_hop_kernels;
+  return HG_OK;
+}
+
+int hg_plan_has_latency_schedule(const hg_plan *plan) {
+  if (!plan) {
+    hg::set_error("hg_plan_has_latency_schedule: null plan");
+    return HG_ERR_INVALID;
+  }
+  return plan->has_lat ? 1 : 0;
+}
+
 int hg_linear_pack_f32(int32_t F_out, int32_t F_in, const float *Wlin, float *wfrag, hg_stream_t stream) {
   if (!Wlin || !wfrag || F_out <= 0 || (F_out % 16) || (F_in != 32 && F_in != 64 && F_in != 128)) {
     hg::set_error("hg_linear_pack_f32: need F_in in {32, 64, 128}, F_out a positive multiple of 16");

@@ -126,17 +126,22 @@ class Plan:
             _lib.check(v)
         return {code: name for name, code in _lib.VARIANTS.items()}[v]
 
-    def tune(self, csrptr_t, colind_t, X, degE=None, degV=None, W=None, iters=20):
+    def tune(self, csrptr_t, colind_t, X, degE=None, degV=None, W=None, iters=20, out=None):
         """Timed choice of what variant="auto" runs for X's width (hg_plan_tune_f32): the fused schedule and the
         pull variant with each of its kernels per hop (three on launch-bound graphs) are run `iters` times each on these tensors and the fastest is
         pinned -- the counterpart of the reference's tuner (HyperGAggr_tune, hgnnAgg.cuh:1115-1157), worth calling
-        for a single dataset-sized hypergraph.  Returns {"variant", "pull_hop_kernels", "us": {...}}."""
+        for a single dataset-sized hypergraph.  Returns {"variant", "pull_hop_kernels", "us": {...}}; `pin` takes the first
+        two.  out ([N, F] float32, optional) receives what the winner computed, the result the call leaves behind."""
         _check_feat(X, "node_feat")
         F = X.shape[1]
         self.prepare(F)
         flat = lambda t: None if t is None else t.reshape(-1)
         degE, degV, W = flat(degE), flat(degV), flat(W)
-        Y = torch.empty((self.N, F), dtype=torch.float32, device=X.device)
+        if out is not None:
+            _check_feat(out, "out", device=X.device)
+            if tuple(out.shape) != (self.N, F):
+                raise ValueError("out must be [%d, %d]" % (self.N, F))
+        Y = out if out is not None else torch.empty((self.N, F), dtype=torch.float32, device=X.device)
         workspace, nbytes = self._workspace(F, X.device)
         info = _lib.TuneInfo()
         with torch.cuda.device(X.device):
@@ -152,6 +157,34 @@ class Plan:
         labels = ("fused", "pull") + tuple("pull/%s+%s" % (kinds[c % 3], kinds[c // 3]) for c in range(1, 9))
         return {"variant": names[info.variant], "pull_hop_kernels": info.pull_hop_kernels,
                 "us": {l: float(u) for l, u in zip(labels, info.us) if u >= 0}}
+
+    def pin(self, F, variant, pull_hop_kernels=0):
+        """Set what variant="auto" runs for feature width F, and the kernel of each pull hop, without timing anything
+        (hg_plan_set_choice): variant 'fused' or 'pull', pull_hop_kernels = k0 + 3 * k1 with k = 0 streaming row gather,
+        1 row panels + wave tasks, 2 the latency schedule (has_latency_schedule()) -- the two values `tune` returns, so
+        plan.pin(F, **{k: tuned[k] for k in ("variant", "pull_hop_kernels")}) repeats a tuned choice and its bits.
+        A forced variant="pull", gather_rows and the bf16 call use the pinned hop kernels too.  'auto' removes the pin
+        (see unpin).  Launches and allocates nothing; works on host-only plans."""
+        if variant not in _lib.VARIANTS:
+            raise ValueError("variant must be one of %s, got %r" % (sorted(_lib.VARIANTS), variant))
+        _lib.check(_lib.lib().hg_plan_set_choice(self._h, int(F), _lib.VARIANTS[variant], int(pull_hop_kernels)))
+        if hasattr(self, "_auto"):
+            self._auto.pop(F, None)  # the cached answer of auto_variant may have changed
+        for k in (F, ("lin", F)):
+            self.__dict__.setdefault("_ws_bytes", {}).pop(k, None)
+
+    def unpin(self, F):
+        """Remove width F's pinned or tuned choice: the static rule decides again, and the pull hops run their default
+        kernel."""
+        self.pin(F, "auto")
+
+    def has_latency_schedule(self):
+        """Whether the plan carries the latency schedule hop kernel 2 runs on (hg_plan_has_latency_schedule): graphs of
+        at most 2^18 incidences whose short_max is above the latency cut."""
+        v = _lib.lib().hg_plan_has_latency_schedule(self._h)
+        if v < 0:
+            _lib.check(v)
+        return bool(v)
 
     def _ensure_fused(self, F):
         if not hasattr(self, "_prepared"):

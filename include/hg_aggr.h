@@ -221,6 +221,26 @@ HG_API int hg_plan_tune_f32(const hg_plan *plan, int32_t F, const int32_t *csrpt
                             const float *X, const float *degE, const float *degV, const float *W, float *Y,
                             void *workspace, size_t workspace_bytes, int32_t iters, hg_stream_t stream,
                             hg_tune_info *info);
+/* The tuner's result without the timing: pins what HG_VARIANT_AUTO runs for feature width F, and the kernel of each
+ * pull hop, to a choice the caller names -- yesterday's hg_tune_info, say, for the same bits today, or one candidate at a
+ * time for a test that must know which kernel it checks.  variant is HG_VARIANT_FUSED or HG_VARIANT_PULL and
+ * pull_hop_kernels is k0 + 3 * k1, both with the meaning of hg_tune_info; the pin holds for both alignment classes of the
+ * width (rows that move as 16-byte lanes and rows that do not).  As after hg_plan_tune_f32, a forced HG_VARIANT_PULL,
+ * hg_gather_rows_f32 and the bf16 call use the pinned hop kernels even where the pinned variant is fused, and the
+ * incidence-weighted entries take the latency schedule where kernel 2 is pinned.  Kernel 0 falls through to kernel 1 where
+ * the streaming row gather does not apply (F <= 8 with F % 4 != 0, HG_PLAN_NO_ROW_STREAM).  variant = HG_VARIANT_AUTO
+ * removes the pin and the hop kernels of the width (pull_hop_kernels is ignored): the static rule decides again.
+ * Only the plan's host state changes, under the lock that guards the AUTO choice: nothing is launched or allocated, and
+ * host-only plans take the call.  A pinned HG_VARIANT_FUSED is not checked against the width here: where the fused
+ * schedule cannot be built, the AUTO call that needs it returns that error.  Size the workspace after pinning
+ * (hg_plan_workspace_bytes); do not call it while other threads run this width on the plan.
+ * HG_ERR_INVALID, message through hg_last_error, plan unchanged: a null plan, F < 1, pull_hop_kernels outside 0 .. 8 or
+ * naming kernel 2 on a plan without a latency schedule, any other variant (HG_VARIANT_PUSH_ATOMIC included).
+ * hg_plan_has_latency_schedule: 1 where the plan carries the latency schedule kernel 2 runs on -- built for graphs of at
+ * most 2^18 incidences whose short_max is above 8 -- else 0; negative hg_status for a null plan.
+ * Detect these entries by their exported symbols (HG_AGGR_VERSION does not change). */
+HG_API int hg_plan_set_choice(const hg_plan *plan, int32_t F, int32_t variant, int32_t pull_hop_kernels);
+HG_API int hg_plan_has_latency_schedule(const hg_plan *plan);
 /* Host copy of one hop's schedule as int32 quadruples (tests, tools): panels
  * {row0, nrows, nnz0, nnz_cnt}, tasks {row, beg, end, slot}, fixups {row,
  * first_slot, count, 0}; sizes from hg_plan_get_info.  Pointers may be NULL. */

@@ -173,3 +173,63 @@ def exact_mass(graph, X, v2e, e2v, heads=1):
         y = torch.zeros(graph.N, C, dtype=F64).index_add_(0, graph.V, xe[graph.E] * wb.reshape(-1, 1))
         top = [max(top[0], float(xe.max()) if xe.numel() else 0.0), max(top[1], float(y.max()) if y.numel() else 0.0)]
     return tuple(top)
+
+
+# ---- what the hop-kernel tests share (test_hop_kernels_host.py, test_hop_kernels_gpu.py) ---------------------------------
+# The pull variant's three kernels per hop, named by Plan.pin: k = 0 streaming row gather, 1 row panels + wave tasks on the
+# plan's schedule, 2 the same kernel on the latency schedule; a mask is k0 + 3 * k1 (hg_tune_info).
+
+HOP_OPTION_SETS = ("default", "wide", "dfs", "small", "odd")
+# what each set's short_max means for graphs of at most 2^18 incidences: `dfs` carries `small`'s short_max = 6
+HOP_SETS_WITH_LAT = {"default": True, "wide": True, "dfs": False, "small": False, "odd": False}
+HOP_WIDTHS = (1, 3, 4, 8, 12, 20, 33, 64, 128, 260)
+LAT_NNZ_MAX = 1 << 18  # plan_build (hg_api.hip): larger graphs get no latency schedule
+
+
+def hop_masks(has_lat):
+    """The masks Plan.pin accepts on a plan with / without a latency schedule: all nine, or the four of kinds 0 and 1."""
+    kinds = (0, 1, 2) if has_lat else (0, 1)
+    return tuple(k0 + 3 * k1 for k1 in kinds for k0 in kinds)
+
+
+def expect_latency_schedule(nnz, short_max):
+    """The rule as plan_build states it, on the resolved short_max (Plan.info)."""
+    return nnz <= LAT_NNZ_MAX and short_max > lat_short_max()
+
+
+def power_of_two_scales(inc, seed=23):
+    """(degE [M], degV [N], W [M]) float32 numpy: degE, degV in {0.25, 0.5, 1}, W in {0.5, 1, 2}.  Multiplying by them is
+    exact, so integer sums stay exact: hop 1's table is a multiple of 2^-3 of magnitude at most 2 * mass, Y a multiple of
+    2^-5 of magnitude at most 2 * mass."""
+    import numpy as np
+    rng = np.random.default_rng(seed)
+    pick = lambda n, vals: np.asarray(vals, np.float32)[rng.integers(0, len(vals), n)]  # noqa: E731
+    return pick(inc.M, (0.25, 0.5, 1.0)), pick(inc.N, (0.25, 0.5, 1.0)), pick(inc.M, (0.5, 1.0, 2.0))
+
+
+SCALE_PRODUCT_MAX = 2.0    # degE * W at most 1 * 2 (degV at most 1)
+SCALE_GRANULE = 2.0 ** -3  # degE * W at least 0.25 * 0.5: every term of hop 2's sums is a multiple of it
+
+
+def unweighted_mass_bound(inc):
+    """exact_mass for unit incidence weights and |X| = 1 everywhere: (max hyperedge size, max over vertices of the summed
+    sizes of their hyperedges).  It bounds the mass of any X in {-1, 0, 1} at any width."""
+    import numpy as np
+    import _grad_ref as gr
+    one = np.ones(inc.nnz, np.float32)
+    return exact_mass(gr.Graph(inc), np.ones((inc.N, 1), np.float32), one, one)
+
+
+def within_on_device(got, ref, mass, c, what=""):
+    """_grad_ref.assert_within's bound, |got - ref| <= c * max(mass, TINY) per element with non-finite values outside,
+    decided on the tensors' device; only a failure goes through assert_within (on the host) for its message.  Returns the
+    largest |got - ref| / max(mass, TINY)."""
+    import _grad_ref as gr
+    assert tuple(got.shape) == tuple(ref.shape), "%s: shape %s, want %s" % (what, tuple(got.shape), tuple(ref.shape))
+    if got.numel() == 0:
+        return 0.0
+    err, floor = (got.double() - ref).abs(), mass.clamp(min=TINY)
+    if not (bool(torch.isfinite(got).all()) and bool((err <= c * floor).all())):  # bad_elements' expression
+        gr.assert_within(got, ref, mass, c, what)
+        raise AssertionError("%s: outside %g of the mass on the device, inside on the host" % (what, c))
+    return float((err / floor).max())

@@ -1776,6 +1776,18 @@ def test_timed_choice_pins_auto_and_keeps_results(hg, oracle, dname):
         y = plan.aggregate(ptr, ind, Xd, variant=variant).cpu().numpy()
         assert (np.abs(y - _float64_truth(inc, X)) <= 1e-5 * np.maximum(1.0, mass)).all(), (dname, variant)
         _assert_close(y, ref)  # chains of at most a few hundred non-negative terms: the literal 1e-5 * max(1, |ref|)
+    # not only the winner: every pair of hop kernels the tuner timed, named with Plan.pin, under the same two bounds
+    assert plan.has_latency_schedule()
+    truth = _float64_truth(inc, X)
+    for mask in range(9):
+        plan.pin(F, "pull", mask)
+        assert plan.auto_variant(F) == "pull"
+        for variant in ("auto", "pull"):
+            y = plan.aggregate(ptr, ind, Xd, variant=variant).cpu().numpy()
+            assert (np.abs(y - truth) <= 1e-5 * np.maximum(1.0, mass)).all(), (dname, variant, mask)
+            _assert_close(y, ref)
+    plan.unpin(F)
+    assert plan.auto_variant(F) == before
     refw = oracle.hgnn_check(inc.N, inc.M, F, H_ptr, H_ind, inc.csrptr, inc.colind, X, degE, degV, W)
     info_w = plan.tune(ptr, ind, Xd, _dev(degE), _dev(degV), _dev(W), iters=5)
     yw = plan.aggregate(ptr, ind, Xd, _dev(degE), _dev(degV), _dev(W)).cpu().numpy()

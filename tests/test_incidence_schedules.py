@@ -325,3 +325,11 @@ def test_tuned_plan(case, graph):
     print("%s: tuned pull_hop_kernels %d, variant %s" % (graph, info["pull_hop_kernels"], info["variant"]))
     _check_unit_weights(c, plan, WIDE_KINDS, "%s/tuned" % graph)
     _check_accuracy(c, plan, WIDE_KINDS, "%s/tuned" % graph)
+    # and not left to the tuner: the plan's schedule, then the latency schedule, named on both hops with Plan.pin (kind 0
+    # is kind 1 on these row_stream=False plans; WIDE_KINDS are both 32 columns wide)
+    assert plan.has_latency_schedule()
+    for mask in (1 + 3 * 1, 2 + 3 * 2, 1 + 3 * 2, 2 + 3 * 1):
+        plan.pin(32, "pull", mask)
+        _check_unit_weights(c, plan, WIDE_KINDS, "%s/pinned %d" % (graph, mask))
+        _check_accuracy(c, plan, WIDE_KINDS, "%s/pinned %d" % (graph, mask))
+    plan.unpin(32)
