@@ -45,6 +45,7 @@ SYMBOLS = (
     "hg_incidence_attention_entry_heads_f32", "hg_incidence_attention_entry_heads_bwd_f32",
     "hg_incidence_attention_entry_dropout_heads_f32", "hg_incidence_attention_entry_dropout_heads_bwd_f32",
     "hg_gather_rows_incidence_heads_f32",
+    "hg_hyperedge_dot_heads_f32", "hg_rows_dot_f32",
 )
 
 
@@ -239,6 +240,11 @@ def lib():
                                                                          vp, vp, vp, vp]
         L.hg_gather_rows_incidence_heads_f32.restype = ctypes.c_int
         L.hg_gather_rows_incidence_heads_f32.argtypes = [vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]
+    if hasattr(L, "hg_hyperedge_dot_heads_f32"):  # likewise: the gradients of degE / W / degV
+        L.hg_hyperedge_dot_heads_f32.restype = ctypes.c_int
+        L.hg_hyperedge_dot_heads_f32.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp]
+        L.hg_rows_dot_f32.restype = ctypes.c_int
+        L.hg_rows_dot_f32.argtypes = [i64, i32, vp, vp, vp, vp]
     L.hg_aggr_push_groups_f32.restype = ctypes.c_int
     L.hg_aggr_push_groups_f32.argtypes = [i32, i32, i32, i64, vp, vp, vp, vp, vp, vp,
                                           vp, vp, vp, vp, vp, vp]

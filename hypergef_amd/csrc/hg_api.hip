@@ -2137,6 +2137,56 @@ int hg_incidence_sum_heads_f32(const hg_plan *plan, int32_t side, int32_t heads,
                       static_cast<hipStream_t>(stream), heads);
 }
 
+// ---- gradients of the per-hyperedge and per-vertex scales -------------------------------------------------------------
+
+int hg_hyperedge_dot_heads_f32(const hg_plan *plan, int32_t F, int32_t heads, const int32_t *csrptr_t, const int32_t *colind_t,
+                               const float *A, const float *wa, const float *B, const float *wb, float *out,
+                               hg_stream_t stream) {
+  const char *who = "hg_hyperedge_dot_heads_f32";
+  if (plan && F < 1) {
+    hg::set_error(std::string(who) + ": the feature width must be at least 1");
+    return HG_ERR_INVALID;
+  }
+  int rc = check_heads(who, plan, heads, F);  // null plan, heads < 1, F % heads; then a host-only plan
+  if (rc != HG_OK) return rc;
+  if (!A || !B || !out) {
+    hg::set_error(std::string(who) + ": null A, B or out");
+    return HG_ERR_INVALID;
+  }
+  if (!csrptr_t || (plan->nnz > 0 && !colind_t)) {
+    hg::set_error(std::string(who) + ": null array");
+    return HG_ERR_INVALID;
+  }
+  hg::EdgeDotArgs a = {};
+  if ((rc = get_segments(plan, 0, true, &a.long_seg, &a.nlong, nullptr)) != HG_OK) return rc;  // the segment entries' list
+  a.ptr = csrptr_t;
+  a.ind = colind_t;
+  a.M = plan->M;
+  a.F = F;
+  a.heads = heads;
+  a.C = F / heads;
+  a.A = A;
+  a.wa = wa;
+  a.B = B;
+  a.wb = wb;
+  a.out = out;
+  const bool lane4 = F % 4 == 0 && a.C % 4 == 0 && aligned16(A) && aligned16(B);  // a 16-byte lane lies inside one head
+  hipError_t e = hg::launch_hyperedge_dot(a, lane4, static_cast<hipStream_t>(stream));
+  if (e != hipSuccess) return hip_fail("hyperedge_dot launch", e);
+  return HG_OK;
+}
+
+int hg_rows_dot_f32(int64_t nrows, int32_t F, const float *A, const float *B, float *out, hg_stream_t stream) {
+  if (nrows < 0 || F < 1 || (nrows > 0 && (!A || !B || !out))) {
+    hg::set_error("hg_rows_dot_f32: nrows < 0, F < 1 or a null array");
+    return HG_ERR_INVALID;
+  }
+  const bool vec4 = F % 4 == 0 && aligned16(A) && aligned16(B);
+  hipError_t e = hg::launch_rows_dot(nrows, F, A, B, out, vec4, static_cast<hipStream_t>(stream));
+  if (e != hipSuccess) return hip_fail("rows_dot launch", e);
+  return HG_OK;
+}
+
 int hg_plan_get_segment_info(const hg_plan *plan, int32_t side, int32_t *info, int32_t *long_seg_host) {
   if (!plan || !info || (side != 0 && side != 1)) {
     hg::set_error("hg_plan_get_segment_info: null argument or side not 0 / 1");

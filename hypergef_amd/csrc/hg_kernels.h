@@ -159,6 +159,21 @@ hipError_t launch_incidence_dot_heads(int32_t M, int64_t nnz, int32_t H, int32_t
 // gradient of hg_aggr_incidence_f32).  vec4: F % 4 == 0 and A, B 16-byte aligned.
 hipError_t launch_incidence_dot(int32_t M, int64_t nnz, int32_t F, const int32_t *ptr, const int32_t *ind, const float *A,
                                 const float *B, float *out, bool vec4, hipStream_t stream);
+// hyperedge_dot_kernel (hg_hyperedge_dot_heads_f32): out[e] = sum_c (sum_{p=(e,u)} wa[p, c / C] A[u, c]) * (sum_p wb[p, c / C] B[u, c])
+struct EdgeDotArgs {
+  const int32_t *ptr, *ind;  // H_T
+  const int32_t *long_seg;   // hyperedges of more than kSegLong members (hg_attention.h), ascending [nlong]
+  int32_t nlong;
+  int32_t M, F, heads, C;    // F = heads * C
+  const float *A, *wa;       // [N, F]; [nnz, heads] in H_T order, head fastest, or null (unit weights)
+  const float *B, *wb;
+  float *out;                // [M]
+};
+// lane4: 16-byte lanes (F % 4 == 0, C % 4 == 0, A and B 16-byte aligned); one launch, and one more for the long rows
+hipError_t launch_hyperedge_dot(const EdgeDotArgs &a, bool lane4, hipStream_t stream);
+// out[r] = <A[r, :], B[r, :]> for r < nrows.  vec4: F % 4 == 0 and A, B 16-byte aligned.
+hipError_t launch_rows_dot(int64_t nrows, int32_t F, const float *A, const float *B, float *out, bool vec4,
+                           hipStream_t stream);
 hipError_t launch_fused(const FusedArgs &a, bool vec4, hipStream_t stream, bool xy_bf16 = false);
 hipError_t launch_hub_pass(const HubArgs &a, bool vec4, hipStream_t stream, bool x_bf16 = false);
 size_t hub_pass_lds_bytes(int32_t cap, int32_t row_floats, int32_t max_rec_words);

@@ -11,6 +11,7 @@
 #include <atomic>
 #include <type_traits>
 
+#include "hg_attention.h"  // kSegLong: the row length at which a hyperedge leaves the lane groups (hyperedge_dot_kernel)
 #include "hg_kernels.h"
 
 namespace hg {
@@ -2225,6 +2226,198 @@ hipError_t launch_incidence_dot(int32_t M, int64_t nnz, int32_t F, const int32_t
                                  nnz, F, A, B, out);                                                                 \
     else hipLaunchKernelGGL((incidence_dot_kernel<L, 1>), dim3((unsigned)nblocks), dim3(256), 0, stream, ptr, ind, M,   \
                             nnz, F, A, B, out);                                                                      \
+    return hipGetLastError();
+  switch (lpr) {
+    HG_CASE(1)
+    HG_CASE(2)
+    HG_CASE(4)
+    HG_CASE(8)
+    HG_CASE(16)
+    HG_CASE(32)
+    HG_CASE(64)
+  }
+#undef HG_CASE
+  return hipErrorInvalidValue;
+}
+
+// ---- the product of two hyperedge sums (hg_hyperedge_dot_heads_f32): the gradient of a per-hyperedge scale ---------------
+// out[e] = sum_c SA[e, c] * SB[e, c] with SA[e, :] = sum_{p=(e,u)} wa[p, c / C] * A[u, :] and SB likewise from (B, wb).
+// Both sums run over the same H_T row, so a lane group gathers the two member rows of an entry together and keeps both
+// sums in registers: neither [M, F] table exists in memory, one float per hyperedge leaves.
+//
+// Work split.  A row of F floats lies on LPR lanes of VEC floats, as in gather_rows_kernel (launch_gather's rule), and a
+// lane group owns one hyperedge, 256 / LPR hyperedges per workgroup, U = 4 member-row pairs in flight.  Rows wider than
+// the group's tile (LPR * VEC columns: more than 256 at 16-byte lanes) are walked once per column chunk; a lane adds the
+// chunk's products to its partial dot before the next chunk.  The lanes' partial dots meet in incidence_dot_kernel's
+// butterfly.  Hyperedges of more than kSegLong members are skipped here and taken by hyperedge_dot_long_kernel, one
+// workgroup each from the plan's side-0 long-row list: group g takes members g, g + NG, ...; the groups' sums of both
+// tables are added through LDS in group order 0 .. NG - 1 by group 0, which then forms the chunk's products.
+// No atomics; a lane adds its members in ascending order: the order depends on the row's length, F and heads only.
+// A unit weight is the factor 1.0f of the same fma (fma(x, 1, s) = s + x exactly): one instance for all four forms.
+template <int VEC>
+__device__ __forceinline__ void edge_dot_walk(const EdgeDotArgs &a, int64_t beg, int64_t end, int step, int col, bool col_ok,
+                                              int hd, Vec<VEC> &sa, Vec<VEC> &sb) {
+  constexpr int U = 4;  // member-row pairs in flight per lane
+  using V = Vec<VEC>;
+  const int64_t F = a.F;
+  for (int64_t p = beg; p < end; p += (int64_t)step * U) {
+    V va[U], vb[U];
+    float fa[U], fb[U];
+#pragma unroll
+    for (int k = 0; k < U; k++) {
+      const int64_t q = p + (int64_t)k * step;
+      const bool ok = col_ok && q < end;
+      const int64_t row = ok ? (int64_t)a.ind[q] * F + col : 0;
+      fa[k] = (ok && a.wa) ? a.wa[q * a.heads + hd] : 1.f;
+      fb[k] = (ok && a.wb) ? a.wb[q * a.heads + hd] : 1.f;
+      va[k] = ok ? V::load(a.A + row) : V::zero();
+      vb[k] = ok ? V::load(a.B + row) : V::zero();
+    }
+#pragma unroll
+    for (int k = 0; k < U; k++) {
+      if (p + (int64_t)k * step < end) {
+        sa.fma(va[k], fa[k]);
+        sb.fma(vb[k], fb[k]);
+      }
+    }
+  }
+}
+
+template <int VEC>
+__device__ __forceinline__ float edge_dot_add(const Vec<VEC> &x, const Vec<VEC> &y, float dot) {
+  if constexpr (VEC == 4) {
+    dot = __builtin_fmaf(x.v.x, y.v.x, dot);
+    dot = __builtin_fmaf(x.v.y, y.v.y, dot);
+    dot = __builtin_fmaf(x.v.z, y.v.z, dot);
+    return __builtin_fmaf(x.v.w, y.v.w, dot);
+  } else {
+    return __builtin_fmaf(x.x, y.x, dot);
+  }
+}
+
+template <int LPR, int VEC>
+__global__ __launch_bounds__(256) void hyperedge_dot_kernel(const EdgeDotArgs a) {
+  using V = Vec<VEC>;
+  constexpr int NG = 256 / LPR;
+  const int tid = threadIdx.x, gl = tid & (LPR - 1);
+  const int64_t e = (int64_t)blockIdx.x * NG + tid / LPR;
+  bool valid = e < a.M;
+  int32_t beg = 0, end = 0;
+  if (valid) {
+    beg = a.ptr[e];
+    end = a.ptr[e + 1];
+    if (end - beg > kSegLong) {  // a workgroup of its own has it
+      beg = end = 0;
+      valid = false;
+    }
+  }
+  float dot = 0.f;
+  for (int c0 = 0; c0 < a.F; c0 += LPR * VEC) {
+    const int col = c0 + gl * VEC;
+    const bool col_ok = col < a.F;
+    V sa = V::zero(), sb = V::zero();
+    edge_dot_walk<VEC>(a, beg, end, 1, col, col_ok, col_ok ? col / a.C : 0, sa, sb);
+    dot = edge_dot_add<VEC>(sa, sb, dot);
+  }
+#pragma unroll
+  for (int off = 1; off < LPR; off <<= 1) dot += __shfl_xor(dot, off, 64);
+  if (gl == 0 && valid) a.out[e] = dot;  // an empty hyperedge: no member, no product: +0.0f
+}
+
+template <int LPR, int VEC>
+__global__ __launch_bounds__(256) void hyperedge_dot_long_kernel(const EdgeDotArgs a) {
+  using V = Vec<VEC>;
+  constexpr int NG = 256 / LPR;
+  __shared__ __attribute__((aligned(16))) float lds[2 * 256 * VEC];  // [table][group][lane][VEC]
+  const int tid = threadIdx.x, gl = tid & (LPR - 1), g = tid / LPR;
+  const int32_t e = a.long_seg[blockIdx.x];
+  const int32_t beg = a.ptr[e], end = a.ptr[e + 1];
+  float dot = 0.f;
+  for (int c0 = 0; c0 < a.F; c0 += LPR * VEC) {
+    const int col = c0 + gl * VEC;
+    const bool col_ok = col < a.F;
+    V sa = V::zero(), sb = V::zero();
+    edge_dot_walk<VEC>(a, (int64_t)beg + g, end, NG, col, col_ok, col_ok ? col / a.C : 0, sa, sb);
+    sa.store(lds + tid * VEC);
+    sb.store(lds + (256 + tid) * VEC);
+    __syncthreads();
+    if (g == 0) {
+      V ta = V::zero(), tb = V::zero();
+      for (int k = 0; k < NG; k++) {
+        ta.add(V::load(lds + (k * LPR + gl) * VEC));
+        tb.add(V::load(lds + (256 + k * LPR + gl) * VEC));
+      }
+      dot = edge_dot_add<VEC>(ta, tb, dot);
+    }
+    __syncthreads();  // the sums have been read before the next chunk's are written
+  }
+#pragma unroll
+  for (int off = 1; off < LPR; off <<= 1) dot += __shfl_xor(dot, off, 64);
+  if (tid == 0) a.out[e] = dot;
+}
+
+hipError_t launch_hyperedge_dot(const EdgeDotArgs &a, bool lane4, hipStream_t stream) {
+  if (a.M <= 0) return hipSuccess;
+  if (a.F <= 0 || a.heads < 1 || a.C < 1 || (int64_t)a.heads * a.C != a.F || (lane4 && (a.F % 4 || a.C % 4)) || !a.ptr ||
+      !a.A || !a.B || !a.out || a.nlong < 0 || (a.nlong > 0 && !a.long_seg))
+    return hipErrorInvalidValue;
+  const int lanes = lane4 ? a.F / 4 : a.F;
+  const int lpr = std::min(64, next_pow2(std::max(lanes, 1)));
+  const unsigned nblocks = (unsigned)(((int64_t)a.M + 256 / lpr - 1) / (256 / lpr));
+#define HG_CASE(L)                                                                                                      \
+  case L:                                                                                                               \
+    if (lane4) {                                                                                                        \
+      hipLaunchKernelGGL((hyperedge_dot_kernel<L, 4>), dim3(nblocks), dim3(256), 0, stream, a);                         \
+      if (a.nlong > 0) hipLaunchKernelGGL((hyperedge_dot_long_kernel<L, 4>), dim3(a.nlong), dim3(256), 0, stream, a);   \
+    } else {                                                                                                            \
+      hipLaunchKernelGGL((hyperedge_dot_kernel<L, 1>), dim3(nblocks), dim3(256), 0, stream, a);                         \
+      if (a.nlong > 0) hipLaunchKernelGGL((hyperedge_dot_long_kernel<L, 1>), dim3(a.nlong), dim3(256), 0, stream, a);   \
+    }                                                                                                                   \
+    return hipGetLastError();
+  switch (lpr) {
+    HG_CASE(1)
+    HG_CASE(2)
+    HG_CASE(4)
+    HG_CASE(8)
+    HG_CASE(16)
+    HG_CASE(32)
+    HG_CASE(64)
+  }
+#undef HG_CASE
+  return hipErrorInvalidValue;
+}
+
+// out[r] = <A[r, :], B[r, :]>: one lane group per row, a lane's fma chain over its columns (ascending), then the same
+// butterfly.  The last step of the degV gradient, <dY[v], Z[v]>.
+template <int LPR, int VEC>
+__global__ __launch_bounds__(256) void rows_dot_kernel(int64_t nrows, int32_t F, const float *A, const float *B, float *out) {
+  using V = Vec<VEC>;
+  constexpr int NG = 256 / LPR;
+  const int tid = threadIdx.x, gl = tid & (LPR - 1);
+  const int64_t r = (int64_t)blockIdx.x * NG + tid / LPR;
+  const bool valid = r < nrows;
+  float dot = 0.f;
+  if (valid) {
+    const float *pa = A + r * F, *pb = B + r * F;
+    for (int c = gl * VEC; c < F; c += LPR * VEC) dot = edge_dot_add<VEC>(V::load(pa + c), V::load(pb + c), dot);
+  }
+#pragma unroll
+  for (int off = 1; off < LPR; off <<= 1) dot += __shfl_xor(dot, off, 64);
+  if (gl == 0 && valid) out[r] = dot;
+}
+
+hipError_t launch_rows_dot(int64_t nrows, int32_t F, const float *A, const float *B, float *out, bool vec4,
+                           hipStream_t stream) {
+  if (nrows <= 0) return hipSuccess;
+  if (F <= 0 || (vec4 && F % 4) || !A || !B || !out) return hipErrorInvalidValue;
+  const int lanes = vec4 ? F / 4 : F;
+  const int lpr = std::min(64, next_pow2(std::max(lanes, 1)));
+  const int64_t nblocks = (nrows + 256 / lpr - 1) / (256 / lpr);
+  if (nblocks > 0x7fffffff) return hipErrorInvalidValue;
+#define HG_CASE(L)                                                                                                        \
+  case L:                                                                                                                 \
+    if (vec4) hipLaunchKernelGGL((rows_dot_kernel<L, 4>), dim3((unsigned)nblocks), dim3(256), 0, stream, nrows, F, A, B, out); \
+    else hipLaunchKernelGGL((rows_dot_kernel<L, 1>), dim3((unsigned)nblocks), dim3(256), 0, stream, nrows, F, A, B, out);  \
     return hipGetLastError();
   switch (lpr) {
     HG_CASE(1)

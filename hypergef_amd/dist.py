@@ -59,7 +59,8 @@ def shared_vertices(inc, parts):
 class ShardedAggregator:
     """Per-rank object.  `local_op(inc_local, X, degE_local, degV, W_local) -> Y_partial`
     defaults to the HIP path; tests inject a CPU checker to exercise the sharding
-    and the collective over gloo without a GPU."""
+    and the collective over gloo without a GPU.  Forward only, as before: the gradients ops gives degE / degV / W
+    (ops._sum_scale_grads) are not sharded."""
 
     def __init__(self, inc, rank=None, world=None, device=None, local_op=None, exchange="allreduce",
                  column_chunks=1, force_collective=False):

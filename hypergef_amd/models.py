@@ -27,14 +27,24 @@ def _variant_of(options):
     return (options or ops.current_options()).variant
 
 
+def _hyperedge_weight(hyperg, learn):
+    """A layer's diagonal hyperedge weight: ones [M] on the hypergraph's device, an nn.Parameter where it is learned."""
+    w = torch.ones(hyperg.degE.shape[0]).to(hyperg.device)
+    return nn.Parameter(w) if learn else w
+
+
 class HyperGsysHGNN(nn.Module):
     # `options` (an ops.Options, or None = the caller's current options at every forward) is this backend's
     # addition to the reference's constructor arguments: per-model kernel family / backward rule / linear folding
-    def __init__(self, hyperg, in_channels, out_channels, first_aggr, heads=1, options=None):
+    # learn_hyperedge_weight=True makes HGNN's diagonal hyperedge weight `Wdiag` an nn.Parameter of ones (in state_dict,
+    # moved by the optimizer; its gradient is ops' dW); False is the reference's constant vector of ones.  The gradient
+    # reaches Wdiag whatever `first_aggr` says: both branches of forward() run the sum operator (HGNNAggr accepts
+    # first_aggr and ignores it, as the reference does), never ops.hgnnaggr_mean / hgnnaggr_max, which give W none
+    def __init__(self, hyperg, in_channels, out_channels, first_aggr, heads=1, options=None, learn_hyperedge_weight=False):
         super().__init__()
         self.options = options
         self.W = ops.Linear(in_channels, heads * out_channels, bias=False, options=options)
-        self.Wdiag = torch.ones(hyperg.degE.shape[0]).to(hyperg.device)
+        self.Wdiag = _hyperedge_weight(hyperg, learn_hyperedge_weight)
         self.heads, self.in_channels, self.out_channels = heads, in_channels, out_channels
         self.hyperg, self.degE, self.degV = hyperg, hyperg.degE, hyperg.degV
         self.first_aggr = first_aggr
@@ -121,10 +131,12 @@ class HypergraphAttnConv(nn.Module):
         Kv = lin_k(X),   Ke[e] = mean_{u in e} Kv[u]   (0 for an empty hyperedge)                 (ops.incidence_gather),
         logit[p = (e, u), h] = <Z[u, head h], Ke[e, head h]> * C ** -0.5                           (ops.incidence_dot),
         alpha = softmax over each group of leaky_relu(logit, negative_slope)   (ops.incidence_softmax(incidence_score=)),
-    and Y as above; negative_slope = 1.0 is the plain softmax of the logits.  Parameters: lin.weight, lin_k.weight, bias."""
+    and Y as above; negative_slope = 1.0 is the plain softmax of the logits.  Parameters: lin.weight, lin_k.weight, bias.
+    learn_hyperedge_weight=True: the aggregation's diagonal hyperedge weight `Wdiag` (ones [M]) is one more nn.Parameter,
+    Y = degV . H_alpha (degE . Wdiag . (H_alpha^T Z)); False is the layer above, parameter for parameter."""
 
     def __init__(self, hyperg, in_channels, out_channels, group="hyperedge", negative_slope=0.2, options=None, heads=1,
-                 concat=True, dropout=0.0, score="additive"):
+                 concat=True, dropout=0.0, score="additive", learn_hyperedge_weight=False):
         super().__init__()
         if score not in ("additive", "dot"):
             raise ValueError("score must be 'additive' or 'dot', got %r" % (score,))
@@ -146,7 +158,7 @@ class HypergraphAttnConv(nn.Module):
             self.a_e = nn.Parameter(torch.empty(heads * out_channels).uniform_(-bound, bound))
         self.bias = nn.Parameter(torch.zeros(heads * out_channels if self.concat else out_channels))
         self.hyperg, self.degE, self.degV = hyperg, hyperg.degE, hyperg.degV
-        self.Wdiag = torch.ones(hyperg.degE.shape[0]).to(hyperg.device)
+        self.Wdiag = _hyperedge_weight(hyperg, learn_hyperedge_weight)
         self._members = hyperg.H_T_colind.long()                                 # vertex of every incidence
         self._inv_size = torch.nan_to_num(hyperg.degE.reshape(-1), posinf=0.0)   # 1 / |e|, 0 for an empty hyperedge
 
@@ -269,6 +281,8 @@ class HGsysHGNN(nn.Module):
             import functools
             # args.options (an ops.Options) pins this model's kernel family / backward rule / linear folding
             Conv, g = functools.partial(__hgsys_convs__[args.model], options=getattr(args, "options", None)), hyperg
+            if args.model == "HGNN" and getattr(args, "learn_hyperedge_weight", False):  # HGNN's own diagonal W, trained
+                Conv = functools.partial(Conv, learn_hyperedge_weight=True)
         self.conv_out = Conv(g, nhid * nhead, nclass, first_aggr, nhead)
         self.convs = nn.ModuleList([Conv(g, nfeat, nhid, first_aggr, nhead)] +
                                    [Conv(g, nhid * nhead, nhid, first_aggr, nhead) for _ in range(nlayer - 2)])

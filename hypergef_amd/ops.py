@@ -155,7 +155,14 @@ def _times_degV(g, degV):
     return g * degV.reshape(-1, 1)
 
 
+def _any_requires_grad(*tensors):
+    return any(isinstance(t, torch.Tensor) and t.requires_grad for t in tensors)
+
+
 def _forward(sched, csrptr_t, indices_t, node_feat, degE, degV, W, opt):
+    # looked at before the scales are flattened: inside an autograd Function grad mode is off and a reshaped view of a
+    # trainable tensor no longer says that it requires a gradient
+    trainable = _any_requires_grad(degE, degV, W)
     _check_feat(node_feat, "node_feat", bf16_ok=True)
     _check_index(csrptr_t, "csrptr_t")
     _check_index(indices_t, "indices_t")
@@ -184,11 +191,46 @@ def _forward(sched, csrptr_t, indices_t, node_feat, degE, degV, W, opt):
                 _ptr(Y), _stream_handle(node_feat.device)))
         return Y
     plan = cached_plan(N, csrptr_t, indices_t)
-    return plan.aggregate(csrptr_t, indices_t, node_feat, degE, degV, W, variant=variant)
+    return plan.aggregate(csrptr_t, indices_t, node_feat, degE, degV, W, variant=variant, trainable_scales=trainable)
+
+
+def _edge_scale_grads(plan, csrptr_t, q, degE, W, need_e, need_w):
+    """(ddegE, dW) from q[e] = <S[e], Ge[e]> (Plan.hyperedge_dot): ddegE = q * W, dW = q * degE, the absent partner being
+    the factor 1.  An empty hyperedge has q = +0 exactly and a partner that may be inf (degE = 1 / |e|): the partner is
+    taken as 0 there, so no 0 * inf is formed and both gradients are exactly 0."""
+    live = plan.nonempty_edges(csrptr_t)
+    gE = gW = None
+    if need_e:
+        gE = (q if W is None else q * _flat(W).masked_fill(~live, 0.0)).view_as(degE)
+    if need_w:
+        gW = (q if degE is None else q * _flat(degE).masked_fill(~live, 0.0)).view_as(W)
+    return gE, gW
+
+
+def _sum_scale_grads(csrptr_t, indices_t, X, dY, degE, degV, W, need, opt):
+    """Exact gradients (ddegE, ddegV, dW) of Y = degV . H (degE . W . (H^T X)) for its gradient dY, each where `need` asks:
+    q[e] = <sum_{u in e} X[u], sum_{v in e} degV[v] dY[v]> in one kernel (Plan.hyperedge_dot; neither [M, F] table is
+    written), ddegV[v] = <dY[v], Z[v]> with Z the aggregation without degV (Plan.rows_dot).  They run on the cached plan
+    whatever variant the forward took.  bf16 rows are widened here (the two kernels are fp32); the results are fp32."""
+    need_e, need_v, need_w = need
+    plan = cached_plan(X.shape[0], csrptr_t, indices_t)
+    dY32 = dY.float()
+    gE = gV = gW = None
+    if need_e or need_w:
+        P = dY32 if degV is None else dY32 * _flat(degV).reshape(-1, 1)
+        q = plan.hyperedge_dot(csrptr_t, indices_t, X.detach().float().contiguous(), P)
+        gE, gW = _edge_scale_grads(plan, csrptr_t, q, degE, W, need_e, need_w)
+    if need_v:
+        variant = opt.variant if opt.variant in ("auto", "pull", "fused") else "auto"
+        Z = plan.aggregate(csrptr_t, indices_t, X.detach(), _flat(degE), None, _flat(W), variant=variant,
+                           trainable_scales=True)  # this code runs only where a scale is trainable
+        gV = plan.rows_dot(dY32, Z.float()).view_as(degV)
+    return gE, gV, gW
 
 
 class _SumAggr(torch.autograd.Function):
-    """One autograd node for all three sum operators (degE/degV/W optional)."""
+    """One autograd node for all three sum operators (degE/degV/W optional).  degE, degV and W get their exact gradients
+    where they require one (_sum_scale_grads), under both Options.backward rules: that option chooses dX's rule only."""
 
     @staticmethod
     def forward(ctx, balan_key, balan_row, group_st, group_ed, csrptr_t, indices_t, node_feat,
@@ -196,22 +238,30 @@ class _SumAggr(torch.autograd.Function):
         opt = ctx.opt = _opt(opt)
         out = _forward((balan_key, balan_row, group_st, group_ed), csrptr_t, indices_t, node_feat,
                        degE, degV, W, opt)
-        # The reference saves its inputs the same way (hgnnaggr.cc:44-46); node_feat is not needed
-        # (the operator is linear).  save_for_backward makes autograd raise if one of them is
-        # modified in place between forward and backward.
-        ctx.save_for_backward(balan_key, balan_row, group_st, group_ed, csrptr_t, indices_t, degE, degV, W)
+        # The reference saves its inputs the same way (hgnnaggr.cc:44-46); node_feat is not needed for dX
+        # (the operator is linear) and is kept only where a scale wants a gradient.  save_for_backward makes
+        # autograd raise if one of them is modified in place between forward and backward.
+        keep_x = any(t is not None and ctx.needs_input_grad[i] for i, t in ((7, degE), (8, degV), (9, W)))
+        ctx.save_for_backward(balan_key, balan_row, group_st, group_ed, csrptr_t, indices_t, degE, degV, W,
+                              node_feat if keep_x else None)
         return out
 
     @staticmethod
     def backward(ctx, grad_out):
         grad_out = grad_out.contiguous()
-        balan_key, balan_row, group_st, group_ed, csrptr_t, indices_t, degE, degV, W = ctx.saved_tensors
+        balan_key, balan_row, group_st, group_ed, csrptr_t, indices_t, degE, degV, W, X = ctx.saved_tensors
         sched = (balan_key, balan_row, group_st, group_ed)
-        if ctx.opt.backward == "reference" or degV is None:
-            g = _forward(sched, csrptr_t, indices_t, grad_out, degE, degV, W, ctx.opt)
-        else:
-            g = _forward(sched, csrptr_t, indices_t, _times_degV(grad_out, degV), degE, None, W, ctx.opt)
-        return (None,) * 6 + (g, None, None, None, None)
+        g = None
+        if ctx.needs_input_grad[6]:
+            if ctx.opt.backward == "reference" or degV is None:
+                g = _forward(sched, csrptr_t, indices_t, grad_out, degE, degV, W, ctx.opt)
+            else:
+                g = _forward(sched, csrptr_t, indices_t, _times_degV(grad_out, degV), degE, None, W, ctx.opt)
+        gE = gV = gW = None
+        if X is not None:
+            need = tuple(t is not None and ctx.needs_input_grad[i] for i, t in ((7, degE), (8, degV), (9, W)))
+            gE, gV, gW = _sum_scale_grads(csrptr_t, indices_t, X, grad_out, degE, degV, W, need, ctx.opt)
+        return (None,) * 6 + (g, gE, gV, gW, None)
 
 
 def _rows_times(A, B, mode="auto"):
@@ -287,7 +337,8 @@ class _SumAggrLinear(torch.autograd.Function):
     unigin.py:20-21).  Forward runs hg_aggr_linear_f32 -- aggregate the F_in-wide rows, multiply
     each finished row by Wlin^T on the matrix cores -- when the widths allow, else the two steps.
     Backward is the two-step one: dZ = aggregation backward of grad_out (reference or adjoint
-    mode, as _SumAggr), dX = dZ . Wlin, dWlin = dZ^T . X."""
+    mode, as _SumAggr), dX = dZ . Wlin, dWlin = dZ^T . X.  degE / degV / W get their exact gradients where they require
+    one: _sum_scale_grads on (X, dT) at F_in, dT = dY . Wlin the gradient of the aggregated rows."""
 
     @staticmethod
     def forward(ctx, csrptr_t, indices_t, node_feat, weight, degE, degV, W, opt=None):
@@ -301,6 +352,8 @@ class _SumAggrLinear(torch.autograd.Function):
         if weight.dtype != node_feat.dtype:
             raise TypeError("weight must have node_feat's dtype %s, got %s" % (node_feat.dtype, weight.dtype))
         f32 = node_feat.dtype == torch.float32  # bf16: torch's GEMM, then the bf16 aggregation (no bf16 MFMA epilogue)
+        ctx.scale_shapes = tuple(None if t is None else t.shape for t in (degE, degV, W))
+        trainable = ctx.trainable = _any_requires_grad(degE, degV, W)  # before flattening: see _forward
         degE, degV, W = _flat(degE), _flat(degV), _flat(W)
         N, F_in = node_feat.shape
         F_out = weight.shape[0]
@@ -311,21 +364,22 @@ class _SumAggrLinear(torch.autograd.Function):
                         (mode == "auto" and linear_fusion_pays(F_in, F_out)))
         if fuse and variant in ("auto", "pull", "fused"):
             out = plan.aggregate_linear(csrptr_t, indices_t, node_feat, weight.detach().contiguous(),
-                                        degE, degV, W, variant=variant, math=opt.linear_math)
+                                        degE, degV, W, variant=variant, math=opt.linear_math, trainable_scales=trainable)
         else:  # project, then aggregate at F_out (own MFMA rows kernel where it takes the widths)
             wd = weight.detach().contiguous()
             Z = linear_rows(node_feat, wd) if f32 and linear_supported(F_in, F_out) and mode != "never" \
                 else torch.nn.functional.linear(node_feat, wd)
-            out = _SumAggrLinear._aggr(csrptr_t, indices_t, Z, degE, degV, W, opt)
+            out = _SumAggrLinear._aggr(csrptr_t, indices_t, Z, degE, degV, W, opt, trainable)
         ctx.save_for_backward(node_feat, weight, csrptr_t, indices_t, degE, degV, W)
         return out
 
     @staticmethod
-    def _aggr(csrptr_t, indices_t, feat, degE, degV, W, opt):
+    def _aggr(csrptr_t, indices_t, feat, degE, degV, W, opt, trainable=False):
         # this operator has no group_* tensors: "push_groups" falls back to the plan's own schedule
         variant = opt.variant if opt.variant != "push_groups" else "auto"
         plan = cached_plan(feat.shape[0], csrptr_t, indices_t)
-        return plan.aggregate(csrptr_t, indices_t, feat.contiguous(), degE, degV, W, variant=variant)
+        return plan.aggregate(csrptr_t, indices_t, feat.contiguous(), degE, degV, W, variant=variant,
+                              trainable_scales=trainable or _any_requires_grad(degE, degV, W))
 
     @staticmethod
     def backward(ctx, grad_out):
@@ -333,12 +387,21 @@ class _SumAggrLinear(torch.autograd.Function):
         node_feat, weight, csrptr_t, indices_t, degE, degV, W = ctx.saved_tensors
         opt = ctx.opt
         if opt.backward == "reference" or degV is None:
-            dZ = _SumAggrLinear._aggr(csrptr_t, indices_t, grad_out, degE, degV, W, opt)
+            dZ = _SumAggrLinear._aggr(csrptr_t, indices_t, grad_out, degE, degV, W, opt, ctx.trainable)
         else:
-            dZ = _SumAggrLinear._aggr(csrptr_t, indices_t, _times_degV(grad_out, degV), degE, None, W, opt)
+            dZ = _SumAggrLinear._aggr(csrptr_t, indices_t, _times_degV(grad_out, degV), degE, None, W, opt, ctx.trainable)
         gx = _rows_times(dZ, weight, opt.fuse_linear) if ctx.needs_input_grad[2] else None
         gw = _wgrad(dZ, node_feat, opt.fuse_linear) if ctx.needs_input_grad[3] else None
-        return None, None, gx, gw, None, None, None, None
+        gE = gV = gW = None
+        need = tuple(t is not None and ctx.needs_input_grad[i] for i, t in ((4, degE), (5, degV), (6, W)))
+        if any(need):
+            # Y = Aggr(X) . Wlin^T: with dT = dY . Wlin, the gradient of the aggregated rows, the scales see the plain
+            # aggregation of X at F_in and its gradient dT
+            dT = _rows_times(grad_out, weight.detach(), opt.fuse_linear)
+            gE, gV, gW = (g if g is None else g.reshape(shape) for g, shape in zip(
+                _sum_scale_grads(csrptr_t, indices_t, node_feat, dT.contiguous(), degE, degV, W, need, opt),
+                ctx.scale_shapes))  # the saved scales are the flattened ones: give each gradient its input's shape
+        return None, None, gx, gw, gE, gV, gW, None
 
 
 # ca folds into M (backward of _AggrResLinear) only inside [2^-64, 2^64]: there M * ca and cb / ca stay far inside fp32's normal
@@ -353,7 +416,8 @@ class _AggrResLinear(torch.autograd.Function):
     ca = 1, cb = 1 + eps, R = X, M = W.  Falls back to the same formula in torch ops around the
     plain aggregation where the MFMA epilogue does not take the widths.  Backward: dP = dY (masked by
     the relu), dT = dP . M, dM = dP^T . T, dX = ca * (aggregation backward of dT), dR = cb * dT,
-    dcb = <dT, R> (cb may be a tensor, e.g. 1 + eps)."""
+    dcb = <dT, R> (cb may be a tensor, e.g. 1 + eps).  degE / degV / W get no gradient from this node (the scale gradients
+    of _SumAggr / _SumAggrLinear / _IncidenceAggr are not wired in here)."""
 
     @staticmethod
     def forward(ctx, csrptr_t, indices_t, node_feat, M, R, cb, degE, degV, W, ca, relu, need_t, opt=None):
@@ -484,8 +548,10 @@ class _IncidenceAggr(torch.autograd.Function):
     """Y = Dv H_e2v De W H_v2e^T X with a weight per incidence, and its exact gradients for X and both weight arrays.
     With P = degV * dY:  G = the same call on P with the weights swapped and no degV (hop 1's table, De W H_e2v^T P, goes
     to xe_out); its output is dX.  dv2e[p = (e, u)] = <X[u], G[e]>, de2v[p = (e, v)] = <P[v], Xe[e]> (incidence_dot),
-    Xe the forward's hop-1 table, kept only when e2v needs a gradient.  degE / degV / W get none.  With heads = H the
-    weights and their gradients are [nnz, H] and the products run over each head's own columns."""
+    Xe the forward's hop-1 table, kept only when e2v needs a gradient.  With heads = H the weights and their gradients are
+    [nnz, H] and the products run over each head's own columns.  degE / degV / W get their exact gradients where they require
+    one: q[e] = <sum_p v2e[p] X[u], sum_p e2v[p] P[v]> (Plan.hyperedge_dot), dW = q degE, ddegE = q W, and
+    ddegV[v] = <dY[v], Z[v]> with Z the same call without degV (Plan.rows_dot); X is then kept as for dv2e."""
 
     @staticmethod
     def forward(ctx, csrptr_t, indices_t, node_feat, v2e, e2v, degE, degV, W, heads=1):
@@ -495,7 +561,8 @@ class _IncidenceAggr(torch.autograd.Function):
         keep_xe = e2v is not None and ctx.needs_input_grad[4]
         Xe = torch.empty((M, F), dtype=torch.float32, device=node_feat.device) if keep_xe else None
         out = plan.aggregate_incidence(csrptr_t, indices_t, node_feat, v2e, e2v, degE, degV, W, xe_out=Xe, heads=heads)
-        keep_x = v2e is not None and ctx.needs_input_grad[3]
+        need_scale = any(t is not None and ctx.needs_input_grad[i] for i, t in ((5, degE), (6, degV), (7, W)))
+        keep_x = (v2e is not None and ctx.needs_input_grad[3]) or need_scale
         ctx.save_for_backward(csrptr_t, indices_t, node_feat if keep_x else None, v2e, e2v, degE, degV, W, Xe)
         ctx.heads = heads
         return out
@@ -519,7 +586,15 @@ class _IncidenceAggr(torch.autograd.Function):
                 gv = plan.incidence_dot(csrptr_t, indices_t, X, G, heads=ctx.heads)
         if need_e2v:
             ge = plan.incidence_dot(csrptr_t, indices_t, P, Xe, heads=ctx.heads)
-        return None, None, gx if need_x else None, gv, ge, None, None, None, None
+        need_dE, need_dV, need_dW = (t is not None and ctx.needs_input_grad[i] for i, t in ((5, degE), (6, degV), (7, W)))
+        gE = gV = gW = None
+        if need_dE or need_dW:  # q[e] = <sum_p v2e[p] X[u], sum_p e2v[p] P[v]>: both hyperedge sums in one kernel
+            q = plan.hyperedge_dot(csrptr_t, indices_t, X, P, v2e, e2v, heads=ctx.heads)
+            gE, gW = _edge_scale_grads(plan, csrptr_t, q, degE, W, need_dE, need_dW)
+        if need_dV:  # <dY[v], Z[v]>, Z the same call without degV
+            Z = plan.aggregate_incidence(csrptr_t, indices_t, X, v2e, e2v, degE, None, W, heads=ctx.heads)
+            gV = plan.rows_dot(g, Z)
+        return None, None, gx if need_x else None, gv, ge, gE, gV, gW, None
 
 
 def incidence_aggr(csrptr_t, indices_t, node_feat, v2e_weight=None, e2v_weight=None, degE=None, degV=None, W=None,
@@ -528,7 +603,8 @@ def incidence_aggr(csrptr_t, indices_t, node_feat, v2e_weight=None, e2v_weight=N
     weight per (vertex, hyperedge) incidence, e.g. a probabilistic H or hypergraph attention's coefficients
     (include/hg_aggr.h, hg_aggr_incidence_f32).  v2e_weight / e2v_weight: float32 [nnz], aligned with indices_t, or None
     (unit weights); the same tensor twice for a symmetric weighting.  Gradients are exact for node_feat and both weight
-    arrays -- the reference has no rule for this operator, so Options.backward does not apply; degE / degV / W get none.
+    arrays and, where they require one, for degE / degV / W -- the reference has no rule for this operator, so
+    Options.backward does not apply.
     Options.variant 'auto' and 'pull' run (both are the pull kernels); 'fused', 'push_atomic', 'push_groups' raise
     ValueError.  float32 only (TypeError for bfloat16).
     heads = H > 1: one call for H attention heads.  node_feat is [N, H * C] and head h owns columns h C .. (h + 1) C - 1;
@@ -542,8 +618,7 @@ def incidence_aggr(csrptr_t, indices_t, node_feat, v2e_weight=None, e2v_weight=N
         v2e, e2v = (_per_head(t, heads) if isinstance(t, torch.Tensor) else t for t in (v2e_weight, e2v_weight))
     _incidence_args(csrptr_t, indices_t, node_feat, v2e, e2v, opt, heads)
     degE, degV, W = _flat(degE), _flat(degV), _flat(W)
-    if not (torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad
-                                            for t in (node_feat, v2e, e2v))):
+    if not (torch.is_grad_enabled() and _any_requires_grad(node_feat, v2e, e2v, degE, degV, W)):
         plan = cached_plan(node_feat.shape[0], csrptr_t, indices_t)
         return plan.aggregate_incidence(csrptr_t, indices_t, node_feat, v2e, e2v, degE, degV, W, heads=heads)
     if heads == 1:
@@ -828,7 +903,7 @@ def incidence_gather(csrptr_t, indices_t, src, weight=None, to="hyperedge", scal
     columns h F/H .. (h + 1) F/H - 1), or None (unit weights); the scales hold one factor per row of dst, or None.
     With weights it runs incidence_aggr's kernels for that hop (hg_gather_rows_incidence_heads_f32): hop 'hyperedge' into
     hop 'vertex' gives incidence_aggr's result bit for bit; without, the unweighted row gather (hg_gather_rows_f32).
-    Differentiable in src and weight; the scales get no gradient, as elsewhere.  Options.variant 'auto' and 'pull' run;
+    Differentiable in src and weight; the scales get no gradient here.  Options.variant 'auto' and 'pull' run;
     the others raise ValueError.  float32 only (TypeError for bfloat16).  num_nodes: N for to='vertex', where src does not
     tell it; without it N is the length of a given scale, else the largest member id + 1, read back from the device."""
     opt = _opt(options)
@@ -984,7 +1059,7 @@ def _sum_aggr(balan_key, balan_row, group_st, group_ed, csrptr_t, indices_t, nod
     opt = _opt(options)
     # nothing to differentiate (inference, or a feature tensor outside the graph): the operator itself, without the
     # autograd node -- a third of the host cost of a launch-bound call
-    if not (torch.is_grad_enabled() and isinstance(node_feat, torch.Tensor) and node_feat.requires_grad):
+    if not (torch.is_grad_enabled() and _any_requires_grad(node_feat, degE, degV, W)):
         return _forward((balan_key, balan_row, group_st, group_ed), csrptr_t, indices_t, node_feat, degE, degV, W, opt)
     return _SumAggr.apply(balan_key, balan_row, group_st, group_ed, csrptr_t, indices_t, node_feat, degE, degV, W, opt)
 
@@ -997,7 +1072,7 @@ class _MeanF1(torch.autograd.Function):
     """first hop = mean (HGNNAggr_MeanF1, hgnnaggr.cc:66-90; kernels hgnnaggr_cuda.cu:86-142):
     the hyperedge sum is scaled by degE*W/|e| (one factor, as the reference computes it), the
     second hop is the ordinary one.  Backward = the same operator on grad_out (the reference's
-    backward kernel differs only in where it divides by |e|)."""
+    backward kernel differs only in where it divides by |e|).  degE / degV / W get no gradient from this node."""
 
     @staticmethod
     def forward(ctx, csrptr_t, indices_t, node_feat, degE, degV, W):
@@ -1018,7 +1093,8 @@ class _MeanF1(torch.autograd.Function):
 
 class _MaxF1(torch.autograd.Function):
     """first hop = per-column max with arg-max table (HGNNAggr_MaxF1, hgnnaggr.cc:92-120;
-    kernels hgnnaggr_cuda.cu:144-208).  Loop bounds use M, not the reference's N (defect D2)."""
+    kernels hgnnaggr_cuda.cu:144-208).  Loop bounds use M, not the reference's N (defect D2).  degE / degV / W get no
+    gradient from this node."""
 
     @staticmethod
     def forward(ctx, csrptr_t, indices_t, node_feat, degE, degV, W):

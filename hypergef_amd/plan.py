@@ -54,6 +54,7 @@ class Plan:
         _lib.check(_lib.lib().hg_plan_get_info(self._h, ctypes.byref(info)))
         self.info = info.as_dict()
         self.N, self.M, self.nnz = info.N, info.M, info.nnz
+        self._nonempty = None  # nonempty_edges' mask
 
     @classmethod
     def from_host(cls, N, M, csrptr_t, colind_t, opts=None, device=None):
@@ -217,7 +218,7 @@ class Plan:
         return torch.empty(max(nbytes, 256), dtype=torch.uint8, device=device), nbytes
 
     def aggregate(self, csrptr_t, colind_t, X, degE=None, degV=None, W=None, variant="auto",
-                  out=None, workspace=None, bind_scales=True):
+                  out=None, workspace=None, bind_scales=True, trainable_scales=False):
         """Y = degV . H (degE . W . (H^T X)) on X's device, current stream.
         bind_scales: see _bind_scales; pass False for scale vectors whose contents change
         without torch noticing (numpy / DLPack aliases, `.data` writes, other libraries).
@@ -226,7 +227,10 @@ class Plan:
         equals aggregate(X.float(), ...).to(torch.bfloat16) bit for bit.  bf16 rows of other widths are padded with zero
         columns to the next multiple of 4 and the result sliced back -- that path copies X and Y, and runs at the padded
         width F4: a caller's workspace is used there if it holds workspace_bytes(F4), else the call takes its own.  A
-        bf16 X or out whose data is not 8-byte aligned is copied too."""
+        bf16 X or out whose data is not 8-byte aligned is copied too.
+        trainable_scales: one of the scale vectors is being trained although the tensor passed does not say so (a view made
+        with grad mode off, as inside an autograd Function): the set is treated as one that requires a gradient -- never
+        bound, W not tested for all ones."""
         bf16 = isinstance(X, torch.Tensor) and X.dtype == torch.bfloat16
         _check_feat(X, "node_feat", bf16_ok=True)
         if X.shape[0] != self.N:
@@ -244,7 +248,8 @@ class Plan:
                 Xp[:, :F] = X
             if workspace is not None and workspace.numel() * workspace.element_size() < self.workspace_bytes(F4):
                 workspace = None  # sized for F, not for the padded width: this path copies anyway, take an own one
-            Yp = self.aggregate(csrptr_t, colind_t, Xp, degE, degV, W, variant, None, workspace, bind_scales)
+            Yp = self.aggregate(csrptr_t, colind_t, Xp, degE, degV, W, variant, None, workspace, bind_scales,
+                                trainable_scales)
             if out is None:
                 return Yp[:, :F].contiguous() if F4 != F else Yp
             out.copy_(Yp[:, :F])
@@ -254,10 +259,10 @@ class Plan:
                 _check_feat(t, name, device=X.device)
                 if t.numel() != n:
                     raise ValueError("%s must have %d elements, got %d" % (name, n, t.numel()))
-        W = self._drop_unit_weights(W, bind_scales)
+        W = self._drop_unit_weights(W, bind_scales and not trainable_scales)
         stream = torch.cuda.current_stream(X.device)  # looked up once per call: it is a measurable share of a launch-bound call
         if (degE is not None or degV is not None or W is not None) and variant in ("auto", "fused"):
-            self._bind_scales(F, degE, degV, W, X.device, bind_scales, stream)
+            self._bind_scales(F, degE, degV, W, X.device, bind_scales, stream, trainable_scales)
         Y = out if out is not None else torch.empty((self.N, F), dtype=X.dtype, device=X.device)
         if variant == "fused":  # hg_plan_workspace_bytes sizes for what AUTO runs; a forced fused call needs its schedule first
             self._ensure_fused(F)
@@ -282,7 +287,7 @@ class Plan:
 
     def aggregate_linear(self, csrptr_t, colind_t, X, weight, degE=None, degV=None, W=None,
                          variant="auto", out=None, workspace=None, packed=None, residual=None, ca=1.0,
-                         cb=0.0, relu=False, t_out=None, bind_scales=True, math="f32"):
+                         cb=0.0, relu=False, t_out=None, bind_scales=True, math="f32", trainable_scales=False):
         """Y[N, F_out] = Aggr(X) . weight^T in one pass (hg_aggr_linear_f32); weight = nn.Linear.weight,
         [F_out, F_in]; packed = pack_linear(weight) if the caller keeps it across calls.
         With residual / ca / cb / relu / t_out: Y = act((ca * Aggr(X) + cb * residual) . weight^T) and
@@ -315,9 +320,9 @@ class Plan:
                 _check_feat(t, name, device=X.device)
                 if t.numel() != n:
                     raise ValueError("%s must have %d elements, got %d" % (name, n, t.numel()))
-        W = self._drop_unit_weights(W, bind_scales)
+        W = self._drop_unit_weights(W, bind_scales and not trainable_scales)  # trainable_scales: as in aggregate()
         if (degE is not None or degV is not None or W is not None) and variant in ("auto", "fused"):
-            self._bind_scales(F_in, degE, degV, W, X.device, bind_scales)
+            self._bind_scales(F_in, degE, degV, W, X.device, bind_scales, trainable=trainable_scales)
         Y = out if out is not None else torch.empty((self.N, F_out), dtype=torch.float32, device=X.device)
         if variant == "fused":
             self._ensure_fused(F_in)
@@ -370,7 +375,7 @@ class Plan:
             self._unit_w_misses = 0 if hit[0] else self._unit_w_misses + 1
         return None if hit[0] else W
 
-    def _bind_scales(self, F, degE, degV, W, device, enable=True, stream=None):
+    def _bind_scales(self, F, degE, degV, W, device, enable=True, stream=None, trainable=False):
         """Degree / weight vectors are graph constants: pre-gather them into the fused
         schedule's panel order once (hg_plan_bind_scales) and again only when a tensor is
         replaced or modified in place (data_ptr / torch version counter).
@@ -391,6 +396,16 @@ class Plan:
             return
         if not enable:
             self.unbind(F)
+            return
+        if trainable or any(t is not None and t.requires_grad for t in (degE, degV, W)):
+            # A trainable scale changes at every optimizer step: binding it would re-gather, and synchronise, on every
+            # call.  Such a set is never bound -- the kernels gather it themselves -- and a binding of other tensors
+            # stays as it is (the library matches a binding by address).  Only a binding of these very addresses, made
+            # before the tensor was marked trainable, is dropped.
+            hit = self._bound.get(F)
+            if hit is not None and tuple(None if k is None else k[0] for k in hit[0]) == \
+                    tuple(None if t is None else t.data_ptr() for t in (degE, degV, W)):
+                self.unbind(F)
             return
         key = tuple(None if t is None else (t.data_ptr(), t._version) for t in (degE, degV, W))
         if stream is None:
@@ -556,6 +571,72 @@ class Plan:
                                                                  _ptr(colind_t), _ptr(A), _ptr(B), _ptr(out),
                                                                  _stream_handle(A.device)))
         return out
+
+    def hyperedge_dot(self, csrptr_t, colind_t, A, B, a_weight=None, b_weight=None, heads=1):
+        """out[e] = sum_c (sum_{p=(e,u)} a_weight[p, c/C] A[u, c]) * (sum_{p=(e,u)} b_weight[p, c/C] B[u, c]), float32 [M]
+        (hg_hyperedge_dot_heads_f32): the product of two hyperedge sums without either [M, F] table -- q of the degE / W
+        gradients with (A, a_weight) = (X, v2e) and (B, b_weight) = (degV * dY, e2v).  A, B: float32 [N, F]; the weights:
+        float32 with nnz * heads elements in H_T order (head fastest), or None (unit weights); C = F / heads.  A plain
+        kernel call, no autograd.  Refusals are decided in ops._incidence_args' order, before a device is touched.  The
+        first call on a plan uploads the long-row list the segment kernels share: not capturable."""
+        heads = _heads(heads)
+        floats = (("A", A), ("B", B), ("a_weight", a_weight), ("b_weight", b_weight))
+        for name, t in floats:
+            if (t is not None or name in ("A", "B")) and (not isinstance(t, torch.Tensor) or t.dtype != torch.float32):
+                raise TypeError("%s must be a float32 tensor (hyperedge_dot has no bfloat16 form), got %s"
+                                % (name, getattr(t, "dtype", type(t))))
+        if A.dim() != 2 or B.dim() != 2 or A.shape[0] != self.N or tuple(B.shape) != tuple(A.shape):
+            raise ValueError("A and B must both be [N = %d, F], got %s and %s" % (self.N, tuple(A.shape), tuple(B.shape)))
+        F = A.shape[1]
+        if F < 1:
+            raise ValueError("the feature width must be at least 1")
+        if F % heads:
+            raise ValueError("F = %d is no multiple of heads = %d" % (F, heads))
+        for name, t in floats[2:]:
+            if t is not None and t.numel() != self.nnz * heads:
+                raise ValueError("%s must have nnz * heads = %d elements, got %d" % (name, self.nnz * heads, t.numel()))
+        _check_index(csrptr_t, "csrptr_t")
+        _check_index(colind_t, "indices_t")
+        _check_feat(A, "A")
+        for name, t in floats[1:]:
+            if t is not None:
+                _check_feat(t, name, device=A.device)
+        out = torch.empty(self.M, dtype=torch.float32, device=A.device)
+        with torch.cuda.device(A.device):
+            _lib.check(_lib.lib().hg_hyperedge_dot_heads_f32(
+                self._h, F, heads, _ptr(csrptr_t), _ptr(colind_t), _ptr(A), _ptr(a_weight), _ptr(B), _ptr(b_weight),
+                _ptr(out), _stream_handle(A.device)))
+        return out
+
+    def rows_dot(self, A, B):
+        """out[r] = <A[r, :], B[r, :]>, float32 [rows], for two float32 [rows, F] tensors (hg_rows_dot_f32): the last step
+        of the degV gradient, <dY[v], Z[v]>.  One lane group per row, fixed order.  A plain kernel call, no autograd."""
+        for name, t in (("A", A), ("B", B)):
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float32:
+                raise TypeError("%s must be a float32 tensor (rows_dot has no bfloat16 form), got %s"
+                                % (name, getattr(t, "dtype", type(t))))
+        if A.dim() != 2 or tuple(B.shape) != tuple(A.shape) or A.shape[1] < 1:
+            raise ValueError("A and B must be [rows, F] of one shape with F >= 1, got %s and %s"
+                             % (tuple(A.shape), tuple(B.shape)))
+        _check_feat(A, "A")
+        _check_feat(B, "B", device=A.device)
+        out = torch.empty(A.shape[0], dtype=torch.float32, device=A.device)
+        with torch.cuda.device(A.device):
+            _lib.check(_lib.lib().hg_rows_dot_f32(A.shape[0], A.shape[1], _ptr(A), _ptr(B), _ptr(out),
+                                                  _stream_handle(A.device)))
+        return out
+
+    def nonempty_edges(self, csrptr_t):
+        """bool [M] device tensor: the hyperedges with at least one member (their scales take part in the result; an
+        empty one's degE may be inf).  Built by the first call outside a stream capture and kept with the plan; a call
+        inside a capture before that builds one for that graph alone (it would lie in the graph's private pool)."""
+        mask = self._nonempty
+        if mask is None or mask.device != csrptr_t.device:
+            mask = csrptr_t[1:] != csrptr_t[:-1]
+            # a mask made during a stream capture lives in that graph's private pool: it serves the capture and is not kept
+            if not torch.cuda.is_current_stream_capturing():
+                self._nonempty = mask
+        return mask
 
     def segment_info(self, side):
         """How the segment kernels cut one side ('hyperedge' / 'vertex', or 0 / 1): {"width": lanes per group, "keep":

@@ -599,6 +599,32 @@ HG_API int hg_gather_rows_incidence_heads_f32(const hg_plan *plan, int32_t hop, 
                                               const float *w, const float *scaleA, const float *scaleB, float *dst,
                                               void *workspace, size_t workspace_bytes, hg_stream_t stream);
 
+/* ---- gradients of the scales degE, W (one factor per hyperedge) and degV (one per vertex) ---------------------------------
+ * For Y = degV . H_e2v (degE . W . (H_v2e^T X)) and its gradient dY, with P[v] = degV[v] * dY[v]:
+ *     q[e] = < sum_{p=(e,u)} v2e[p] X[u],  sum_{p=(e,v)} e2v[p] P[v] >        dW[e] = q[e] * degE[e],  ddegE[e] = q[e] * W[e]
+ *     ddegV[v] = < dY[v], Z[v] >,   Z = the aggregation without degV
+ * hg_hyperedge_dot_heads_f32: out[e] = sum_c (sum_{p=(e,u)} wa[p, c / C] * A[u, c]) * (sum_{p=(e,u)} wb[p, c / C] * B[u, c]),
+ *   q with (A, wa) = (X, v2e) and (B, wb) = (P, e2v).  A, B: [N, F] fp32, any F >= 1, 4-byte aligned; wa, wb: [nnz, heads]
+ *   in H_T order, head fastest, or NULL (unit weights); C = F / heads; out [M], fully overwritten, an empty hyperedge
+ *   gives exactly +0.0f.  Both sums run over the same H_T row: one lane group per hyperedge gathers the two member rows of
+ *   an entry together and keeps both sums in registers, so neither [M, F] table is written.  Lanes are 16 bytes where
+ *   F % 4 == 0, C % 4 == 0 and A, B are 16-byte aligned, else 4 bytes; rows wider than a lane group's tile (256 columns
+ *   at 16-byte lanes) are walked once per column chunk.  Hyperedges of more than 128 members take one workgroup each (the
+ *   list behind hg_plan_get_segment_info, side 0), the lane groups' sums combined through LDS in a fixed order.  No
+ *   atomics; one launch plus at most one for the long rows; the order depends on the plan, F and heads only, so two
+ *   calls give the same bits, and exchanging (A, wa) with (B, wb) gives them too.
+ *   Refusals, nothing launched, in this order: HG_ERR_INVALID for a null plan, F < 1, heads < 1 or F % heads != 0;
+ *   HG_ERR_UNSUPPORTED for a plan built with HG_PLAN_HOST_ONLY; HG_ERR_INVALID for a null A, B or out, then for a null
+ *   csrptr_t / colind_t.  The first call on a plan builds and uploads the long-row list the segment entries share (not
+ *   capturable; one warm call of either makes every later one capturable).
+ * hg_rows_dot_f32: out[r] = <A[r, :], B[r, :]> for r < nrows, A and B [nrows, F]; one lane group per row, fixed order, no
+ *   plan: the last step of ddegV.  HG_ERR_INVALID for nrows < 0, F < 1 or a null array.
+ * Detect these entries by their exported symbols (HG_AGGR_VERSION does not change). */
+HG_API int hg_hyperedge_dot_heads_f32(const hg_plan *plan, int32_t F, int32_t heads, const int32_t *csrptr_t,
+                                      const int32_t *colind_t, const float *A, const float *wa, const float *B,
+                                      const float *wb, float *out, hg_stream_t stream);
+HG_API int hg_rows_dot_f32(int64_t nrows, int32_t F, const float *A, const float *B, float *out, hg_stream_t stream);
+
 /* first_aggr = "max" pieces (hgnnaggr_max, source/hgnnaggr/hgnnaggr_cuda.cu:144-208).
  * hg_gather_max_f32: Xe[e,k] = (max_{u in e} X[u,k], start -1e5, strict >) * (degE[e]*W[e]),
  * record[e,k] = winning vertex (0 if none).  The second hop is hg_gather_rows_f32(hop = 1).

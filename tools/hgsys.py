@@ -58,6 +58,9 @@ def parse():
                    help="hgsys backend, layers fused at nhid = 128 on batches: fp32 MFMA, or six bf16 products per fp32 product")
     p.add_argument("--dtype", default="float32", choices=["float32", "bfloat16"],
                    help="features and parameters (model.to(dtype)); the hypergraph's scale vectors stay fp32")
+    p.add_argument("--learn-hyperedge-weight", action="store_true",
+                   help="HGNN on the hgsys backend: train each layer's diagonal hyperedge weight Wdiag (an nn.Parameter of ones); "
+                        "the layers run the sum aggregation whatever --first-aggr says, so Wdiag always gets its gradient")
     p.add_argument("--output", type=str, default=None)
     return p.parse_args()
 
@@ -98,6 +101,9 @@ def main():
     model.to(dev)
     if dtype != torch.float32:
         model.to(dtype)
+        for m in model.modules():  # a learned Wdiag is a scale vector: those stay fp32
+            if isinstance(getattr(m, "Wdiag", None), torch.nn.Parameter):
+                m.Wdiag.data = m.Wdiag.data.float()
     if world > 1:
         model = torch.nn.parallel.DistributedDataParallel(
             model, device_ids=[dev.index] if dev.type == "cuda" else None)
