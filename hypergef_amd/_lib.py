@@ -35,6 +35,7 @@ SYMBOLS = (
     "hg_plan_set_choice", "hg_plan_has_latency_schedule",
     "hg_plan_workspace_bytes",
     "hg_aggr_fused_f32", "hg_aggr_fused_bf16", "hg_linear_pack_f32", "hg_linear_pack_ex_f32", "hg_linear_pack_floats", "hg_linear_rows_f32", "hg_linear_wgrad_workspace_bytes", "hg_linear_wgrad_f32", "hg_aggr_linear_workspace_bytes", "hg_aggr_linear_f32", "hg_aggr_linear_res_f32", "hg_aggr_linear_res_dev_f32",
+    "hg_linear_pack_bf16_bytes", "hg_linear_pack_bf16", "hg_aggr_linear_res_bf16", "hg_linear_rows_bf16", "hg_aggr_linear_bf16_path",
     "hg_gather_rows_f32", "hg_aggr_push_groups_f32", "hg_gather_max_f32",
     "hg_scatter_record_f32",
     "hg_aggr_incidence_workspace_bytes", "hg_aggr_incidence_f32", "hg_incidence_dot_f32", "hg_plan_get_incidence_perm",
@@ -172,6 +173,18 @@ def lib():
     L.hg_aggr_linear_res_dev_f32.restype = ctypes.c_int
     L.hg_aggr_linear_res_dev_f32.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, ctypes.c_float, vp,
                                              i32, vp, vp, vp, sz, i32, vp]
+    if hasattr(L, "hg_aggr_linear_res_bf16"):  # detected by export: the linear layer on bf16 rows
+        L.hg_linear_pack_bf16_bytes.restype = sz
+        L.hg_linear_pack_bf16_bytes.argtypes = [i32, i32]
+        L.hg_linear_pack_bf16.restype = ctypes.c_int
+        L.hg_linear_pack_bf16.argtypes = [i32, i32, vp, vp, vp]
+        L.hg_aggr_linear_res_bf16.restype = ctypes.c_int
+        L.hg_aggr_linear_res_bf16.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, ctypes.c_float, ctypes.c_float,
+                                              vp, i32, vp, vp, vp, sz, i32, vp]
+        L.hg_linear_rows_bf16.restype = ctypes.c_int
+        L.hg_linear_rows_bf16.argtypes = [i64, i32, i32, vp, vp, vp, vp]
+        L.hg_aggr_linear_bf16_path.restype = ctypes.c_int
+        L.hg_aggr_linear_bf16_path.argtypes = [vp, i32, i32, i32]
     L.hg_plan_bind_scales.restype = ctypes.c_int
     L.hg_plan_bind_scales.argtypes = [vp, i32, vp, vp, vp, vp]
     L.hg_plan_auto_variant.restype = ctypes.c_int

@@ -122,6 +122,7 @@ int fused_upload(hg::FusedSched &f, int64_t &bytes) {
   UP(rec_tab, d_rec_tab);
   UP(eid_all, d_eid_all);
   UP(fixups, d_fixups);
+  UP(fix_rows, d_fix_rows);
   UP(hub.vslot0, hub.d_vslot0);
   UP(hub.rec, hub.d_rec);
   UP(hub.rec_tab, hub.d_rec_tab);
@@ -135,7 +136,7 @@ int fused_upload(hg::FusedSched &f, int64_t &bytes) {
 
 void fused_free(hg::FusedSched &f) {
   void *ptrs[] = {f.d_prow, f.d_mat_ptr, f.d_mat_ind, f.d_mat_eid, f.d_rec, f.d_rec_tab, f.d_eid_all, f.d_bsA,
-                  f.d_bsB, f.d_bsD, f.d_fixups, f.hub.d_vslot0, f.hub.d_rec, f.hub.d_rec_tab, f.hub.d_wg_first, f.mat_stream.d_rec, f.mat_stream.d_rec_tab,
+                  f.d_bsB, f.d_bsD, f.d_fixups, f.d_fix_rows, f.hub.d_vslot0, f.hub.d_rec, f.hub.d_rec_tab, f.hub.d_wg_first, f.mat_stream.d_rec, f.mat_stream.d_rec_tab,
                   f.mat_stream.d_fixups};
   for (void *q : ptrs)
     if (q) (void)hipFree(q);
@@ -309,6 +310,9 @@ int get_fused(const hg_plan *cp, int32_t F, bool vec4, const hg::FusedSched **ou
                     std::to_string(lds_need) + " bytes of LDS per workgroup at this feature width (limit 163840)");
       return HG_ERR_INVALID;
     }
+    for (size_t i = (size_t)f.n_fix_l1; i < f.fixups.size(); i++) f.fix_rows.push_back(f.fixups[i].row);
+    std::sort(f.fix_rows.begin(), f.fix_rows.end());
+    f.fix_rows.erase(std::unique(f.fix_rows.begin(), f.fix_rows.end()), f.fix_rows.end());
     int rc = (p->opts.flags & HG_PLAN_HOST_ONLY) ? HG_OK : fused_upload(f, p->device_bytes);
     if (rc != HG_OK) {
       fused_free(f);
@@ -1179,12 +1183,20 @@ int hg_scatter_record_f32(int32_t N, int32_t M, int32_t F, const float *T, const
 // wants (aggregated rows) * Wlin^T in lin->Y: the fused panels do that in their epilogue when
 // they can (lin->done = true); otherwise the aggregated rows go to Y as usual and the caller
 // runs the standalone linear kernel over them.
+// b16 (hg_aggr_linear_res_bf16): X is bf16 and the aggregated rows the caller is left with are fp32 all the same; Wlin, Y,
+// epi.R and epi.T_out point at the bf16 fragments and rows of that entry.  Its panels take the epilogue even where hubs or
+// split vertices leave rows to the fixup pass (in_panel): those rows -- rowmap, nrows_left of them -- are then the only ones
+// the caller still has to multiply (done = false), read from the aggregated table by vertex id.
 struct LinReq {
   const float *Wlin;
   int32_t F_out;
   float *Y;
   bool done;
   hg::LinEpilogue epi;
+  bool b16 = false;
+  bool in_panel = false;
+  const int32_t *rowmap = nullptr;
+  int64_t nrows_left = 0;
 };
 
 // bf16: rows of X and Y are bf16 (hg_aggr_fused_bf16 has checked F % 4 == 0 and 8-byte alignment, so the lane layout is the one
@@ -1218,7 +1230,9 @@ static int aggr_impl(const hg_plan *plan, int32_t F, const int32_t *csrptr_t,
     hg::set_error(std::string(fn) + ": null array");
     return HG_ERR_INVALID;
   }
-  if (bf16 && (lin || F % 4 != 0 || !aligned_lane(X, true) || !aligned_lane(Y, true))) {
+  const bool lb16 = bf16 && lin && lin->b16;  // bf16 X, fp32 aggregated rows (hg_aggr_linear_res_bf16 has checked its arrays)
+  const bool ybf16 = bf16 && !lb16;           // element type of the rows this call's Y holds
+  if (bf16 && ((lin && !lb16) || F % 4 != 0 || !aligned_lane(X, true) || !aligned_lane(Y, ybf16))) {
     hg::set_error("hg_aggr_fused_bf16: F must be a multiple of 4 and X, Y 8-byte aligned");
     return HG_ERR_UNSUPPORTED;
   }
@@ -1226,7 +1240,7 @@ static int aggr_impl(const hg_plan *plan, int32_t F, const int32_t *csrptr_t,
   const Carve c = carve(plan, F);
   char *ws = static_cast<char *>(workspace);
   float *Xe = reinterpret_cast<float *>(ws + c.xe);
-  const bool aligned = (F % 4 == 0) && aligned_lane(X, bf16) && aligned_lane(Y, bf16) && aligned16(Xe);
+  const bool aligned = (F % 4 == 0) && aligned_lane(X, bf16) && aligned_lane(Y, ybf16) && aligned16(Xe);
   const bool vec4 = aligned || wide_rows_ok(plan, F);  // the fused chain's lane layout; the pull kernels decide for themselves
   const hg::FusedSched *f = nullptr;
   if (variant == HG_VARIANT_AUTO) {
@@ -1350,30 +1364,35 @@ static int aggr_impl(const hg_plan *plan, int32_t F, const int32_t *csrptr_t,
     a.mat_bytes = mat_bytes;
     a.nrows_x = plan->N;
     a.nrows_mat = f->n_mat;
-    a.y_nt = rows_whole_64(Y, F, bf16);
+    a.y_nt = rows_whole_64(Y, F, ybf16);
     // a pre-pass that read at least a quarter of the incidences' member rows: see fused_packed_kernel's run order
     a.reverse_runs = f->n_mat > 0 && !f->mat_ptr.empty() && (int64_t)f->mat_ptr.back() * 4 >= plan->nnz;
     a.bsA = bound ? f->d_bsA : nullptr;
     a.bsB = bound ? f->d_bsB : nullptr;
     a.bsD = bound ? f->d_bsD : nullptr;
     // rows produced outside the panels (hubs, split vertices) get no epilogue: two-step then
-    if (lin && f->fixups.empty() && aligned) {
+    // (the bf16 epilogue's panels leave such rows to the fixup pass and the caller's rows kernel: LinReq)
+    if (lin && (f->fixups.empty() || lb16) && aligned) {
       a.Wlin = lin->Wlin;
       a.F_out = lin->F_out;
       a.epi = lin->epi;
-      if (hg::fused_linear_ok(a)) {
+      if (lb16 ? hg::fused_linear_b16_ok(a) : hg::fused_linear_ok(a)) {
         a.Y = lin->Y;
-        lin->done = true;
+        lin->done = f->fixups.empty();
+        lin->in_panel = true;
+        lin->rowmap = f->d_fix_rows;
+        lin->nrows_left = (int64_t)f->fix_rows.size();
+        if (lb16) a.y_nt = rows_whole_64(lin->Y, lin->F_out, true);
       } else {
         a.Wlin = nullptr;
       }
     }
-    hipError_t e = hg::launch_fused(a, vec4, s, bf16);
+    hipError_t e = hg::launch_fused(a, vec4, s, bf16, lb16 && !a.Wlin);
     if (e != hipSuccess) return hip_fail("fused_panel launch", e);
     // (d) hubs and split vertices: Y[v] = degV[v] * (sum of the vertex's partial rows), fixed order
     if (!f->fixups.empty()) {
       e = hg::launch_fixups(f->d_fixups, (int)f->fixups.size(), f->n_fix_l1, F, partial, Y, degV, nullptr, nullptr, vec4, s,
-                            rows_whole_64(Y, F, bf16), bf16);
+                            rows_whole_64(Y, F, ybf16), ybf16);
       if (e != hipSuccess) return hip_fail("fixup launch", e);
     }
     return HG_OK;
@@ -1388,7 +1407,7 @@ static int aggr_impl(const hg_plan *plan, int32_t F, const int32_t *csrptr_t,
   if (rc != HG_OK) return rc;
   // hop 2: Y[v] = (sum_{e contains v} Xe[e]) * degV[v]
   return run_hop(plan, 1, F, plan->d_ptr_v, plan->d_ind_v, Xe, degV, nullptr, Y,
-                 reinterpret_cast<float *>(ws + c.part[1]), s, false, bf16);
+                 reinterpret_cast<float *>(ws + c.part[1]), s, false, ybf16);
 }
 
 int hg_aggr_fused_f32(const hg_plan *plan, int32_t F, const int32_t *csrptr_t,
@@ -1703,6 +1722,167 @@ int hg_aggr_linear_f32(const hg_plan *plan, int32_t F_in, int32_t F_out, const i
                        size_t workspace_bytes, int32_t variant, hg_stream_t stream) {
   return hg_aggr_linear_res_f32(plan, F_in, F_out, csrptr_t, colind_t, X, degE, degV, W, wfrag, nullptr, 1.f, 0.f,
                                 0, nullptr, Y, workspace, workspace_bytes, variant, stream);
+}
+
+// ---- the linear layer on bf16 rows (native bf16 MFMA epilogue) --------------------------------------------------------
+
+static bool b16_widths_ok(int32_t F_in, int32_t F_out) {
+  return F_out > 0 && (F_out % 16) == 0 && (F_in == 32 || F_in == 64 || F_in == 128);
+}
+
+size_t hg_linear_pack_bf16_bytes(int32_t F_out, int32_t F_in) {
+  return b16_widths_ok(F_in, F_out) ? (size_t)F_out * F_in * 2 : 0;
+}
+
+int hg_linear_pack_bf16(int32_t F_out, int32_t F_in, const uint16_t *Wlin, void *wfrag, hg_stream_t stream) {
+  if (!Wlin || !wfrag) {
+    hg::set_error("hg_linear_pack_bf16: null argument");
+    return HG_ERR_INVALID;
+  }
+  if (!b16_widths_ok(F_in, F_out) || !aligned16(wfrag)) {
+    hg::set_error("hg_linear_pack_bf16: need F_in in {32, 64, 128}, F_out a positive multiple of 16, wfrag 16-byte aligned");
+    return HG_ERR_UNSUPPORTED;
+  }
+  hipError_t e = hg::launch_linear_pack_bf16(F_out, F_in, Wlin, wfrag, static_cast<hipStream_t>(stream));
+  if (e != hipSuccess) return hip_fail("linear_pack_bf16 launch", e);
+  return HG_OK;
+}
+
+int hg_linear_rows_bf16(int64_t nrows, int32_t F_in, int32_t F_out, const uint16_t *T, const void *wfrag, uint16_t *Y,
+                        hg_stream_t stream) {
+  if (nrows < 0 || !wfrag || (nrows > 0 && (!T || !Y))) {
+    hg::set_error("hg_linear_rows_bf16: bad argument");
+    return HG_ERR_INVALID;
+  }
+  if (!b16_widths_ok(F_in, F_out)) {
+    hg::set_error("hg_linear_rows_bf16: need F_in in {32, 64, 128}, F_out a positive multiple of 16");
+    return HG_ERR_UNSUPPORTED;
+  }
+  if (!aligned_lane(T, true) || !aligned_lane(Y, true) || !aligned16(wfrag)) {
+    hg::set_error("hg_linear_rows_bf16: T and Y must be 8-byte aligned, wfrag 16-byte aligned");
+    return HG_ERR_UNSUPPORTED;
+  }
+  hg::LinearB16Args la;
+  la.T = T;
+  la.wfrag = wfrag;
+  la.rowmap = nullptr;
+  la.Y = reinterpret_cast<hg::bf16 *>(Y);
+  la.nrows = nrows;
+  la.F_in = F_in;
+  la.F_out = F_out;
+  la.y_nt = rows_whole_64(Y, F_out, true) ? 1 : 0;
+  hipError_t e = hg::launch_linear_bf16(la, false, static_cast<hipStream_t>(stream));
+  if (e != hipSuccess) return hip_fail("linear_rows_bf16 launch", e);
+  return HG_OK;
+}
+
+// Which kernels hg_aggr_linear_res_bf16 runs for these widths: the fp32 entry's variant and schedule (the epilogue's own
+// where one exists), then the bf16 panels' own eligibility.  *fs: the schedule, if fused.
+static int b16_path(const hg_plan *plan, int32_t F_in, int32_t F_out, int32_t variant, const hg::FusedSched **fs) {
+  const bool vec4 = true;  // the entry takes aligned arrays of whole 16-byte (fp32) lanes only
+  const hg::FusedSched *f = nullptr;
+  int rc;
+  if (variant == HG_VARIANT_AUTO && (rc = pick_variant(plan, F_in, vec4, &variant, &f)) != HG_OK) return rc;
+  if (variant != HG_VARIANT_FUSED) return 2;
+  if (!f && (rc = get_fused(plan, F_in, vec4, &f)) != HG_OK) return rc;
+  if (f->fixups.empty()) {
+    const hg::FusedSched *fl = nullptr;
+    if ((rc = get_fused(plan, F_in, vec4, &fl, true)) != HG_OK) return rc;
+    if (fl != f && fl->fixups.empty()) f = fl;
+  }
+  if (fs) *fs = f;
+  const int64_t xb = (int64_t)plan->N * F_in * 2, mb = (int64_t)f->n_mat * F_in * 4;
+  hg::FusedArgs a{};
+  a.F = F_in;
+  a.F_out = F_out;
+  a.ng = f->ng;
+  a.cap = f->cap;
+  a.rows_cap = f->rows_cap;
+  a.nrows_x = plan->N;
+  a.x_bytes = xb < ((int64_t)1 << 31) ? (int32_t)xb : 0;
+  const bool mat_ok = f->n_mat == 0 || (mb < ((int64_t)1 << 31) && f->n_mat < (1 << 24));
+  const bool in_panel = mat_ok && hg::fused_linear_b16_ok(a);
+  return (in_panel ? 1 : 0) | ((!in_panel || !f->fixups.empty()) ? 2 : 0);
+}
+
+int hg_aggr_linear_bf16_path(const hg_plan *plan, int32_t F_in, int32_t F_out, int32_t variant) {
+  if (!plan) {
+    hg::set_error("hg_aggr_linear_bf16_path: null plan");
+    return HG_ERR_INVALID;
+  }
+  if (variant == HG_VARIANT_PUSH_ATOMIC || !b16_widths_ok(F_in, F_out) ||
+      (variant != HG_VARIANT_AUTO && variant != HG_VARIANT_PULL && variant != HG_VARIANT_FUSED)) {
+    hg::set_error("hg_aggr_linear_bf16_path: need variant auto, pull or fused, F_in in {32, 64, 128}, F_out a positive multiple of 16");
+    return HG_ERR_UNSUPPORTED;
+  }
+  return b16_path(plan, F_in, F_out, variant, nullptr);
+}
+
+int hg_aggr_linear_res_bf16(const hg_plan *plan, int32_t F_in, int32_t F_out, const int32_t *csrptr_t,
+                            const int32_t *colind_t, const uint16_t *X, const float *degE, const float *degV,
+                            const float *W, const void *wfrag, const uint16_t *R, float ca, float cb, const float *cb_dev,
+                            int32_t flags, uint16_t *T_out, uint16_t *Y, void *workspace, size_t workspace_bytes,
+                            int32_t variant, hg_stream_t stream) {
+  // refusals, in the order include/hg_aggr.h documents; nothing is launched before the last of them has passed
+  if (!plan || !csrptr_t || (plan->nnz > 0 && !colind_t) || !X || !wfrag || !Y) {
+    hg::set_error("hg_aggr_linear_res_bf16: null argument");
+    return HG_ERR_INVALID;
+  }
+  if (flags & ~HG_LIN_RELU) {
+    hg::set_error("hg_aggr_linear_res_bf16: flags takes HG_LIN_RELU only");
+    return HG_ERR_INVALID;
+  }
+  if (variant == HG_VARIANT_PUSH_ATOMIC || (variant != HG_VARIANT_AUTO && variant != HG_VARIANT_PULL && variant != HG_VARIANT_FUSED)) {
+    hg::set_error("hg_aggr_linear_res_bf16: variant must be auto, pull or fused (the push kernels are fp32 only)");
+    return HG_ERR_UNSUPPORTED;
+  }
+  if (!b16_widths_ok(F_in, F_out)) {
+    hg::set_error("hg_aggr_linear_res_bf16: need F_in in {32, 64, 128}, F_out a positive multiple of 16");
+    return HG_ERR_UNSUPPORTED;
+  }
+  if (!aligned_lane(X, true) || !aligned_lane(Y, true) || !aligned_lane(R, true) || !aligned_lane(T_out, true) || !aligned16(wfrag)) {
+    hg::set_error("hg_aggr_linear_res_bf16: X, Y, R and T_out must be 8-byte aligned, wfrag 16-byte aligned");
+    return HG_ERR_UNSUPPORTED;
+  }
+  if (plan->opts.flags & HG_PLAN_HOST_ONLY) {
+    hg::set_error("hg_aggr_linear_res_bf16: plan was built with HG_PLAN_HOST_ONLY and holds no device schedule");
+    return HG_ERR_UNSUPPORTED;
+  }
+  const size_t base = linear_base_bytes(plan, F_in);
+  if (!workspace || !aligned16(workspace) || workspace_bytes < base + round256((size_t)plan->N * F_in * sizeof(float))) {
+    hg::set_error("hg_aggr_linear_res_bf16: workspace smaller than hg_aggr_linear_workspace_bytes (or not 16-byte aligned)");
+    return HG_ERR_WORKSPACE;
+  }
+  float *T = reinterpret_cast<float *>(static_cast<char *>(workspace) + round256(base));
+  LinReq lin{static_cast<const float *>(wfrag), F_out, reinterpret_cast<float *>(Y), false, {}};
+  lin.b16 = true;
+  lin.epi.R = reinterpret_cast<const float *>(R);
+  lin.epi.ca = ca;
+  lin.epi.cb = R ? cb : 0.f;
+  lin.epi.cb_dev = R ? cb_dev : nullptr;
+  lin.epi.relu = (flags & HG_LIN_RELU) ? 1 : 0;
+  lin.epi.T_out = reinterpret_cast<float *>(T_out);
+  int rc = aggr_impl(plan, F_in, csrptr_t, colind_t, X, degE, degV, W, T, workspace, base, variant, stream, &lin, true);
+  if (rc != HG_OK || lin.done) return rc;
+  // the rows the panels did not take: all of them, or (in_panel) the hubs' and split vertices', by vertex id
+  hg::LinearB16Args la;
+  la.T = T;
+  la.wfrag = wfrag;
+  la.rowmap = lin.in_panel ? lin.rowmap : nullptr;
+  la.Y = reinterpret_cast<hg::bf16 *>(Y);
+  la.nrows = lin.in_panel ? lin.nrows_left : plan->N;
+  la.F_in = F_in;
+  la.F_out = F_out;
+  la.R = reinterpret_cast<const hg::bf16 *>(R);
+  la.ca = lin.epi.ca;
+  la.cb = lin.epi.cb;
+  la.cb_dev = lin.epi.cb_dev;
+  la.relu = lin.epi.relu;
+  la.T_out = reinterpret_cast<hg::bf16 *>(T_out);
+  la.y_nt = rows_whole_64(Y, F_out, true) ? 1 : 0;
+  hipError_t e = hg::launch_linear_bf16(la, true, static_cast<hipStream_t>(stream));
+  if (e != hipSuccess) return hip_fail("linear_rows_bf16 launch", e);
+  return HG_OK;
 }
 
 // ---- incidence-weighted aggregation ---------------------------------------------------------------------------------

@@ -163,6 +163,10 @@ struct FusedSched {
   std::vector<Fixup> fixups;  // rows = vertex ids (hubs and split vertices); first-level ones first
   int32_t n_fix_l1 = 0;
   Fixup *d_fixups = nullptr;
+  // the vertices the final fixups write, ascending: the rows hg_aggr_linear_res_bf16 sends through its rows kernel when the
+  // panels ran the epilogue themselves
+  std::vector<int32_t> fix_rows;
+  int32_t *d_fix_rows = nullptr;
   // device copies (the panel lists above stay on the host: the kernel reads the packed records)
   int32_t *d_prow = nullptr;
   int32_t *d_mat_ptr = nullptr, *d_mat_ind = nullptr, *d_mat_eid = nullptr;

@@ -101,6 +101,24 @@ struct LinearArgs {
   LinEpilogue epi;
 };
 
+// linear_rows_bf16_kernel (hg_aggr_linear_res_bf16's fallback, hg_linear_rows_bf16): row i of the call is row
+// rowmap[i] (null: i) of T, R, T_out and Y alike.  Y = round_bf16(act(t . Wb^T)), t = T's row if T is bf16, else
+// round_bf16(ca * T + cb * R) of the fp32 row (written to T_out where wanted).
+struct LinearB16Args {
+  const void *T;          // [*, F_in] bf16, or fp32 (launch_linear_bf16's t_f32)
+  const void *wfrag;      // Wb [F_out, F_in] in fragment order (launch_linear_pack_bf16)
+  const int32_t *rowmap;
+  bf16 *Y;                // [*, F_out]
+  int64_t nrows;
+  int32_t F_in, F_out;
+  const bf16 *R = nullptr;  // t_f32 only, as LinEpilogue's
+  float ca = 1.f, cb = 0.f;
+  const float *cb_dev = nullptr;
+  int32_t relu = 0;
+  bf16 *T_out = nullptr;    // t_f32 only
+  int32_t y_nt = 0;         // rows of Y are whole 64-byte units: streaming stores
+};
+
 // The hub pass (HubPass, hg_internal.h): persistent workgroups, register accumulators.
 struct HubArgs {
   const int32_t *rec;       // round records (hg_fused.cpp, build_hub_pass)
@@ -174,7 +192,10 @@ hipError_t launch_hyperedge_dot(const EdgeDotArgs &a, bool lane4, hipStream_t st
 // out[r] = <A[r, :], B[r, :]> for r < nrows.  vec4: F % 4 == 0 and A, B 16-byte aligned.
 hipError_t launch_rows_dot(int64_t nrows, int32_t F, const float *A, const float *B, float *out, bool vec4,
                            hipStream_t stream);
-hipError_t launch_fused(const FusedArgs &a, bool vec4, hipStream_t stream, bool xy_bf16 = false);
+// y_f32 (with xy_bf16, F in {32, 64, 128}): rows of X are bf16, rows of Y fp32 -- the aggregated rows of the bf16 linear
+// layer on their way to linear_rows_bf16_kernel.  xy_bf16 with a.Wlin: the native bf16 epilogue (fused_linear_b16_ok);
+// a.Wlin is then the bf16 fragments of launch_linear_pack_bf16, a.epi.R / a.epi.T_out point at bf16 rows, a.Y is bf16.
+hipError_t launch_fused(const FusedArgs &a, bool vec4, hipStream_t stream, bool xy_bf16 = false, bool y_f32 = false);
 hipError_t launch_hub_pass(const HubArgs &a, bool vec4, hipStream_t stream, bool x_bf16 = false);
 size_t hub_pass_lds_bytes(int32_t cap, int32_t row_floats, int32_t max_rec_words);
 // Y[fx.row] = scale[fx.row] * (sum of the fixup's partial rows); first-level fixups first.  Y_bf16: rows of Y are bf16.
@@ -185,6 +206,9 @@ bool stream_rows_ok(const StreamArgs &a, bool vec4);  // buffer-addressable tabl
 hipError_t launch_stream_rows(const StreamArgs &a, hipStream_t stream, bool src_bf16 = false, bool dst_bf16 = false);
 bool fused_linear_ok(const FusedArgs &a);  // can launch_fused run this call's linear epilogue?
 hipError_t launch_linear(const LinearArgs &a, hipStream_t stream);
+bool fused_linear_b16_ok(const FusedArgs &a);  // fused_linear_ok, and the panels take the native bf16 epilogue (F = 128, F_out <= 128)
+hipError_t launch_linear_bf16(const LinearB16Args &a, bool t_f32, hipStream_t stream);
+hipError_t launch_linear_pack_bf16(int32_t F_out, int32_t F_in, const uint16_t *Wlin, void *wfrag, hipStream_t stream);
 int wgrad_parts(int64_t nrows, int32_t Fa, int32_t Fb);
 bool wgrad_shape_ok(int32_t Fa, int32_t Fb);  // <= 16 tiles of 16 x 16, or both widths multiples of 64 up to 512 (64 x 64 blocks)
 hipError_t launch_wgrad(int64_t nrows, int32_t Fa, int32_t Fb, const float *A, const float *B, float *C,

@@ -972,6 +972,107 @@ __device__ __forceinline__ void panel_times_wt_split(float *t, int pstride, int 
   }
 }
 
+// ---- native bf16 epilogue (hg_aggr_linear_res_bf16, K = 128) ---------------------------------------------------------
+// The split matrix phase with one plane and one product: the combined row, rounded to bf16 once, IS its own h plane, and a
+// bf16 weight is its own h plane -- one MFMA per (k-step, row tile, column tile) where the bf16x6 form issues six, one
+// ds_read_b128 per A fragment, one dwordx4 per B fragment.  The plane keeps split_off's swizzle (plane stride 0).
+//   wb[(nt * K/32 + ks) * 64 + lane] = 8 bf16: Wb[nt*16 + (lane & 15)][ks*32 + 8*(lane >> 4) + j]   (linear_pack_bf16_kernel)
+__device__ __forceinline__ unsigned round_bf16x2(float x, float y) {  // v_cvt_pk_bf16_f32: round to nearest even
+  return __builtin_bit_cast(unsigned, __builtin_convertvector(hg_f2{x, y}, hg_bf2));
+}
+__device__ __forceinline__ uint2 round_bf16x4(const float4 &v) { return make_uint2(round_bf16x2(v.x, v.y), round_bf16x2(v.z, v.w)); }
+
+// Steps of B fragments in registers (4 VGPRs each); as in the split form the first kB16Depth are loaded BEFORE hop 2 and
+// arrive during it.  Two steps, the split form's depth; a depth of four (every step of a narrow output) compiled to 6-8 more
+// VGPRs through hop 2 and was not timed.
+constexpr int kB16Depth = 2;
+// Row gathers in flight per lane in the bf16 epilogue's instances: twelve (kLinU32, the fp32 epilogue's) spilled 20 bytes per
+// lane in the instance with materialised slots and scales at the six-wave budget; ten and eight are scratch-free (66-72 VGPRs).
+constexpr int kB16U = 10;
+__device__ __forceinline__ uint4 load_b16_step(const uint4 *wb, const LinSplit &sp, int NT, int npw, int t, int lane) {
+  const int ni = npw == 2 ? (t & 1) : 0, ks = npw == 2 ? (t >> 1) : t;
+  return wb[((int64_t)min(sp.nt_first + ni * sp.nt_step, NT - 1) * 4 + ks) * 64 + lane];
+}
+
+// mfma_rows_split's walk: iteration i = (step t, row tile j), here one MFMA on one A fragment, the next iteration's fragment
+// read while it runs (a second fragment is 4 registers here, not 12).
+template <int NPW, int NRT, int D>
+__device__ __forceinline__ void mfma_rows_b16(const char *plane, const uint4 *wb, const LinSplit &sp, int NT, int lane, uint4 (&bq)[D],
+                                              hg_f4 *acc) {
+  constexpr int RPN = 4 / NPW, NS = 4 * NPW, NI = NS * NRT;
+  const int r = lane & 15, kb = lane >> 4;
+  const char *prow = plane + (sp.rt_first * 16 + r) * 256;
+  const int rstep = sp.rt_step * 16 * 256;
+  auto a_ptr = [&](int i) { const int t = i / NRT, j = i % NRT; return prow + j * rstep + ((((t / NPW * 4 + kb) ^ r) & 15) << 4); };
+  uint4 an = *reinterpret_cast<const uint4 *>(a_ptr(0));
+#pragma unroll
+  for (int i = 0; i < NI; i++) {
+    const int t = i / NRT, j = i % NRT, ni = t % NPW;
+    const uint4 ac = an;
+    if (i + 1 < NI) an = *reinterpret_cast<const uint4 *>(a_ptr(i + 1));
+    acc[ni * RPN + j] = mfma_bf16(ac, bq[t % D], acc[ni * RPN + j]);
+    if (j == NRT - 1 && t + D < NS) bq[t % D] = load_b16_step(wb, sp, NT, NPW, t + D, lane);
+  }
+}
+
+// panel_times_wt_split on the one plane: the fp32 results go back into the tile region as [rows][K + 4] floats; then the
+// optional relu, one rounding to bf16, and the values leave as whole rows of Y.  A row whose rowmap entry has bit 31 set is a
+// piece of a split vertex (its sum went to a partial row): multiplied with the others, never stored.
+template <int NPW>
+__device__ __forceinline__ void panel_times_wt_b16(float *t, int nrows, int F_out, const uint4 *wb, const int32_t *rowmap, bf16 *Y, int tid,
+                                                   uint4 (&bq)[kB16Depth], int relu, int y_nt) {
+  constexpr int K = 128, LD = K + 4, RPN = 4 / NPW;
+  const int lane = tid & 63;
+  const int NT = F_out >> 4, RT = (nrows + 15) >> 4;
+  const LinSplit sp = lin_split(tid >> 6, NT);
+  hg_f4 acc[4];
+#pragma unroll
+  for (int j = 0; j < 4; j++) acc[j] = hg_f4{0.f, 0.f, 0.f, 0.f};
+  int nrt = 0;
+  if (sp.active) {
+    nrt = min(2, max(0, (RT - sp.rt_first + sp.rt_step - 1) / sp.rt_step));  // at most 32 rows (launcher)
+    const char *plane = reinterpret_cast<const char *>(t);
+    if constexpr (NPW == 2) {  // both row tiles always, as the split form (the second tile of a short panel is never stored)
+      nrt = RT;
+      mfma_rows_b16<NPW, 2, kB16Depth>(plane, wb, sp, NT, lane, bq, acc);
+    } else if (nrt == 2) {
+      mfma_rows_b16<NPW, 2, kB16Depth>(plane, wb, sp, NT, lane, bq, acc);
+    } else if (nrt == 1) {
+      mfma_rows_b16<NPW, 1, kB16Depth>(plane, wb, sp, NT, lane, bq, acc);
+    }
+  }
+  __syncthreads();  // every wave has read its A fragments: the plane can be overwritten
+  if (sp.active) {
+#pragma unroll
+    for (int ni = 0; ni < NPW; ni++) {
+      const int nt = sp.nt_first + ni * sp.nt_step;
+      if (nt < NT) {
+#pragma unroll
+        for (int j = 0; j < RPN; j++)
+          if (j < nrt) {
+            float *d = t + ((sp.rt_first + j * sp.rt_step) * 16 + 4 * (lane >> 4)) * LD + nt * 16 + (lane & 15);
+#pragma unroll
+            for (int i = 0; i < 4; i++) d[i * LD] = acc[ni * RPN + j][i];
+          }
+      }
+    }
+  }
+  __syncthreads();
+  const int q = F_out >> 2;  // four-column pieces per row: 8 bytes of Y
+  for (int i = tid; i < nrows * q; i += 256) {
+    const int r = i / q, c = (i - r * q) * 4;
+    const int pr = rowmap[r];
+    if (pr < 0) continue;
+    float4 o = *reinterpret_cast<const float4 *>(t + r * LD + c);
+    if (relu) o = make_float4(fmaxf(o.x, 0.f), fmaxf(o.y, 0.f), fmaxf(o.z, 0.f), fmaxf(o.w, 0.f));
+    const uint2 ob = round_bf16x4(o);
+    typedef unsigned u2 __attribute__((ext_vector_type(2)));
+    u2 *dst = reinterpret_cast<u2 *>(Y + (int64_t)pr * F_out + c);
+    if (y_nt) __builtin_nontemporal_store(u2{ob.x, ob.y}, dst);
+    else *dst = u2{ob.x, ob.y};
+  }
+}
+
 // WIDE = false: the caller guarantees the staged form applies (F_out <= K and few enough row tiles); the direct form
 // for wider outputs is then not compiled in -- its registers would set the budget of the whole kernel.
 template <int KSTEPS, bool WIDE = true>
@@ -1113,6 +1214,112 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(KSTEPS >= 3
   __syncthreads();
   panel_times_wt<KSTEPS>(t, nrows, a.F_out, a.Wlin, a.rowmap ? a.rowmap + row0 : nullptr, row0, a.Y,
                          threadIdx.x, bv, a.epi.relu);
+}
+
+// ---- bf16 rows times Wb^T (hg_linear_rows_bf16; the rows hg_aggr_linear_res_bf16's panels do not take) -----------------
+// Wb [F_out, F_in] bf16 in fragment order, linear_pack_split_kernel's layout with one plane and F_in / 32 k-steps:
+//   wfrag[(nt * K/32 + ks) * 64 + lane] = 8 bf16: Wb[nt*16 + (lane & 15)][ks*32 + 8*(lane >> 4) + j]
+__global__ __launch_bounds__(256) void linear_pack_bf16_kernel(int32_t F_out, int32_t F_in, const uint16_t *Wlin, uint4 *wfrag) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;  // (nt, ks, lane)
+  const int k32 = F_in >> 5;
+  if (i >= (int64_t)(F_out >> 4) * k32 * 64) return;
+  const int lane = (int)(i & 63), ks = (int)((i >> 6) % k32), nt = (int)((i >> 6) / k32);
+  const uint16_t *w = Wlin + (int64_t)(nt * 16 + (lane & 15)) * F_in + ks * 32 + 8 * (lane >> 4);
+  unsigned u[4];
+#pragma unroll
+  for (int j = 0; j < 4; j++) u[j] = (unsigned)w[2 * j] | ((unsigned)w[2 * j + 1] << 16);
+  wfrag[i] = make_uint4(u[0], u[1], u[2], u[3]);
+}
+
+// A wave owns 16 rows and computes the TRANSPOSED tiles, D = Wb_tile . t^T: the weight fragment is the A operand, the wave's
+// rows the B operand -- both maps put 8 consecutive k of row (lane & 15) in a lane, so a row's fragment is 16 contiguous
+// bytes of it, loaded straight from memory (no LDS, no barrier), and lane l ends up with FOUR CONSECUTIVE COLUMNS
+// 16 nt + 4 (l >> 4) .. + 3 of row l & 15: one 8-byte store per column tile.  The K/32 row fragments stay in registers for
+// every column tile; the tiles' weight fragments come from the L2 (NB tiles in flight).  fp32 accumulation, k-steps in
+// ascending order: the bits depend on the widths only.
+// TF32: T holds fp32 rows (the aggregation's workspace); t = round_bf16(ca * T + cb * R) formed as the panels form it
+// (separate fp32 operations), rounded once, written to T_out where wanted.
+typedef unsigned hg_u4a8 __attribute__((ext_vector_type(4), aligned(8)));  // rows of the bf16 entries are 8-byte aligned
+template <int KS, bool TF32>
+__global__ __launch_bounds__(256) void linear_rows_bf16_kernel(const LinearB16Args a) {
+  constexpr int K = KS * 32, NB = KS == 4 ? 2 : 4;
+  const int lane = threadIdx.x & 63, kb = lane >> 4;
+  const int64_t i0 = ((int64_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * 16;
+  if (i0 >= a.nrows) return;  // wave-uniform; the kernel has no barrier
+  const bool row_ok = i0 + (lane & 15) < a.nrows;
+  const int64_t ri = min(i0 + (lane & 15), a.nrows - 1);  // a row past the end repeats the last one and stores nothing
+  const int64_t row = a.rowmap ? (int64_t)a.rowmap[ri] : ri;
+  const uint4 *wb = static_cast<const uint4 *>(a.wfrag);
+  uint4 tf[KS];
+  if constexpr (TF32) {
+    const float *tp = static_cast<const float *>(a.T) + row * K + 8 * kb;
+    float4 lo[KS], hi[KS];
+#pragma unroll
+    for (int ks = 0; ks < KS; ks++) {
+      lo[ks] = *reinterpret_cast<const float4 *>(tp + ks * 32);
+      hi[ks] = *reinterpret_cast<const float4 *>(tp + ks * 32 + 4);
+    }
+    hg_u4a8 rb[KS];
+    if (a.R) {
+#pragma unroll
+      for (int ks = 0; ks < KS; ks++) rb[ks] = *reinterpret_cast<const hg_u4a8 *>(a.R + row * K + ks * 32 + 8 * kb);
+    }
+    const bool comb = a.R || a.ca != 1.f;  // as the fp32 entry: t' = ca * t + cb * R only where asked for
+    const float cb = a.R ? (a.cb_dev ? *a.cb_dev : a.cb) : 0.f;
+#pragma unroll
+    for (int ks = 0; ks < KS; ks++) {
+      float v[8] = {lo[ks].x, lo[ks].y, lo[ks].z, lo[ks].w, hi[ks].x, hi[ks].y, hi[ks].z, hi[ks].w};
+      if (comb) {
+#pragma unroll
+        for (int e = 0; e < 8; e++) v[e] *= a.ca;
+        if (a.R) {
+#pragma unroll
+          for (int e = 0; e < 4; e++) {
+            const unsigned w = rb[ks][e];
+            const float r0 = __uint_as_float(w << 16) * cb, r1 = __uint_as_float(w & 0xffff0000u) * cb;
+            v[2 * e] += r0;
+            v[2 * e + 1] += r1;
+          }
+        }
+      }
+      tf[ks] = make_uint4(round_bf16x2(v[0], v[1]), round_bf16x2(v[2], v[3]), round_bf16x2(v[4], v[5]), round_bf16x2(v[6], v[7]));
+      if (a.T_out && row_ok)
+        *reinterpret_cast<hg_u4a8 *>(a.T_out + row * K + ks * 32 + 8 * kb) = hg_u4a8{tf[ks].x, tf[ks].y, tf[ks].z, tf[ks].w};
+    }
+  } else {
+    const bf16 *tp = static_cast<const bf16 *>(a.T) + row * K + 8 * kb;
+#pragma unroll
+    for (int ks = 0; ks < KS; ks++) {
+      const hg_u4a8 u = *reinterpret_cast<const hg_u4a8 *>(tp + ks * 32);
+      tf[ks] = make_uint4(u.x, u.y, u.z, u.w);
+    }
+  }
+  const int NT = a.F_out >> 4;
+  typedef unsigned u2 __attribute__((ext_vector_type(2)));
+  for (int nt0 = 0; nt0 < NT; nt0 += NB) {
+    uint4 b[NB][KS];
+#pragma unroll
+    for (int n = 0; n < NB; n++)
+#pragma unroll
+      for (int ks = 0; ks < KS; ks++) b[n][ks] = wb[((int64_t)min(nt0 + n, NT - 1) * KS + ks) * 64 + lane];  // past the last tile: clamped, not stored
+    hg_f4 acc[NB];
+#pragma unroll
+    for (int n = 0; n < NB; n++) acc[n] = hg_f4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int ks = 0; ks < KS; ks++)
+#pragma unroll
+      for (int n = 0; n < NB; n++) acc[n] = mfma_bf16(b[n][ks], tf[ks], acc[n]);
+#pragma unroll
+    for (int n = 0; n < NB; n++)
+      if (nt0 + n < NT && row_ok) {
+        float4 o = make_float4(acc[n][0], acc[n][1], acc[n][2], acc[n][3]);
+        if (a.relu) o = make_float4(fmaxf(o.x, 0.f), fmaxf(o.y, 0.f), fmaxf(o.z, 0.f), fmaxf(o.w, 0.f));
+        const uint2 ob = round_bf16x4(o);
+        u2 *dst = reinterpret_cast<u2 *>(a.Y + row * a.F_out + (nt0 + n) * 16 + 4 * kb);
+        if (a.y_nt) __builtin_nontemporal_store(u2{ob.x, ob.y}, dst);
+        else *dst = u2{ob.x, ob.y};
+      }
+  }
 }
 
 // ---- weight gradient of the layer's linear: C[Fa, Fb] = A^T B over N rows --------------------
@@ -1323,13 +1530,22 @@ __host__ __device__ inline int lin_tile_floats(int cap, int rows_cap, int tw) {
 // instance (natural demand 85-92 VGPRs, 5-6 waves).
 // SPLIT (LIN, !LINW, K = 128 only): the matrix phase as six bf16 products per fp32 product (mfma_rows_split); a.epi.wsplit.
 // T: element type of the rows of X and Y (Rows; bf16 without LIN only).  Tile, materialised rows and partial rows are fp32.
+// BLIN (T = bf16, LIN, !LINW, K = 128): the native bf16 epilogue of hg_aggr_linear_res_bf16 -- the combined row is rounded to bf16
+// once, the same bits go to T_out and into ONE operand plane, and the matrix phase is one bf16 MFMA per (k-step, row tile,
+// column tile) (panel_times_wt_b16); a.Wlin holds the bf16 fragments, a.epi.R / a.epi.T_out / a.Y point at bf16 rows.  Unlike the
+// fp32 epilogue it takes panels with pieces of split vertices: a piece's sum goes to its partial row and gets no epilogue.
+// TY: element type of the rows of Y where it is not T's (bf16 X, fp32 Y: the aggregated rows on their way to
+// linear_rows_bf16_kernel); never with LIN.
 template <int LPR, int VEC, int U, bool FAST, bool MAT, bool SCALED, bool LIN = false, int BS = 256, bool LINW = true, bool SPLIT = false,
-          typename T = float>
+          typename T = float, bool BLIN = false, typename TY = T>
 __global__ __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(LIN ? (!LINW ? (LPR >= 32 ? kLinWavesStaged32 : kLinWavesStaged) : LPR >= 32 ? kLinWaves32 : LPR == 16 ? kLinWaves16 : kLinWaves8) : 1, 8))) void fused_packed_kernel(const FusedArgs a) {
   static_assert(!LIN || BS == 256, "the linear epilogue is written for four waves");
   static_assert(!SPLIT || (LIN && !LINW && LPR == 32 && VEC == 4), "bf16x6 matrix phase: K = 128 staged instances");
-  static_assert(!LIN || std::is_same_v<T, float>, "the linear epilogue takes fp32 rows");
+  static_assert(!LIN || std::is_same_v<T, float> || BLIN, "the fp32 linear epilogue takes fp32 rows");
+  static_assert(!BLIN || (LIN && !LINW && !SPLIT && LPR == 32 && VEC == 4 && std::is_same_v<T, bf16>), "bf16 epilogue: K = 128 staged instances on bf16 rows");
+  static_assert(std::is_same_v<TY, T> || (!LIN && std::is_same_v<TY, float>), "rows of Y: T's type, or fp32 without an epilogue");
   constexpr bool XF32 = std::is_same_v<T, float>;
+  constexpr bool YF32 = std::is_same_v<TY, float>;
   constexpr int NG = BS / LPR;
   constexpr int TW = LPR * VEC;
   using V = Vec<VEC>;
@@ -1563,7 +1779,68 @@ __global__ __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(LIN ? (!LINW
     }
   }
   __syncthreads();
-  if constexpr (LIN) {  // ---- hop 2 into registers, then rows * Wlin^T on the matrix cores
+  if constexpr (BLIN) {  // ---- hop 2 into registers, one rounding to bf16, then rows * Wb^T on the bf16 MFMA
+    const uint4 *wb = reinterpret_cast<const uint4 *>(a.Wlin);
+    const T *Rb = reinterpret_cast<const T *>(a.epi.R);
+    T *Tb = reinterpret_cast<T *>(a.epi.T_out);
+    const int NT = a.F_out >> 4;
+    const LinSplit sp = lin_split(tid >> 6, NT);
+    uint4 bq[kB16Depth];  // the first steps' B fragments: in flight during hop 2
+    if (sp.active) {
+#pragma unroll
+      for (int t = 0; t < kB16Depth; t++) bq[t] = load_b16_step(wb, sp, NT, a.F_out > 64 ? 2 : 1, t, tid & 63);
+    }
+    const int rpg = (nrows + NG - 1) / NG;  // <= 4 (launcher)
+    const int r0 = min(g * rpg, nrows), r1 = min(r0 + rpg, nrows);
+    int pr[4];  // vertex id, or bit 31 | partial row; a row past the group's range repeats the panel's last row and is not used
+#pragma unroll
+    for (int i = 0; i < 4; i++) pr[i] = prow[min(r0 + i, nrows - 1)];
+    V rr[4];  // the residual rows, bf16, before hop 2 as in the fp32 epilogue (a piece has none: row 0 is read and not used)
+    if (Rb) {
+#pragma unroll
+      for (int i = 0; i < 4; i++) rr[i] = RX::load(Rb + (int64_t)max(pr[i], 0) * F + col);
+    }
+    V outr[4];
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+      outr[i] = V::zero();
+      const int r = r0 + i;
+      if (r < r1) {
+        const int pb = r ? pend[r - 1] : 0, pe = pend[r];
+        for (int p = pb; p < pe; p++) outr[i].add(V::load(tile + (int)pvs[p] * TW + lcol));
+        if (a.degV && pe > pb) outr[i].mul(dv_regs ? dv[i] : sdeg[r]);
+        if (pr[i] < 0) outr[i].store(a.partial + (int64_t)(pr[i] & 0x7fffffff) * F + col);  // summed and scaled by the fixup pass
+      }
+    }
+    if (Rb || a.epi.ca != 1.f) {  // t' = ca * t + cb * R[v], the fp32 epilogue's operations in its order
+      const float cb = a.epi.cb_dev ? *a.epi.cb_dev : a.epi.cb;
+#pragma unroll
+      for (int i = 0; i < 4; i++)
+        if (r0 + i < r1) {
+          outr[i].mul(a.epi.ca);
+          if (Rb) {
+            rr[i].mul(cb);
+            outr[i].add(rr[i]);
+          }
+        }
+    }
+    uint2 tb[4];  // the ONE rounding: these bits are T_out's and the operand's
+#pragma unroll
+    for (int i = 0; i < 4; i++) tb[i] = round_bf16x4(outr[i].v);
+    if (Tb) {
+#pragma unroll
+      for (int i = 0; i < 4; i++)
+        if (r0 + i < r1 && pr[i] >= 0) *reinterpret_cast<uint2 *>(Tb + (int64_t)pr[i] * TW + lcol) = tb[i];
+    }
+    __syncthreads();  // every slot row has been read: the tile becomes the operand plane
+#pragma unroll
+    for (int i = 0; i < 4; i++)
+      if (r0 + i < r1) *reinterpret_cast<uint2 *>(reinterpret_cast<char *>(tile) + split_off(r0 + i, lcol)) = tb[i];
+    __syncthreads();
+    if (a.F_out > 64) panel_times_wt_b16<2>(tile, nrows, a.F_out, wb, prow, static_cast<T *>(a.Y), tid, bq, a.epi.relu, a.y_nt);
+    else panel_times_wt_b16<1>(tile, nrows, a.F_out, wb, prow, static_cast<T *>(a.Y), tid, bq, a.epi.relu, a.y_nt);
+    return;
+  } else if constexpr (LIN) {  // ---- hop 2 into registers, then rows * Wlin^T on the matrix cores
     // the B fragments of this wave's first column tile are issued after hop 2 and fly across the two barriers that
     // follow (issued before hop 2 they would hold K/4 more registers through it: 78 instead of 64 VGPRs)
     [[maybe_unused]] float bv[BPre<TW / 4>::N];
@@ -1652,7 +1929,7 @@ __global__ __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(LIN ? (!LINW
       if (a.degV && pe > pb) acc.mul(dv_regs ? dscale : sdeg[r]);
       if (col_ok) {
         const int pr = prow[r];  // vertex id, or bit 31 | partial row (a piece of a split vertex)
-        if constexpr (XF32) {
+        if constexpr (YF32) {
           float *dst = (pr < 0 ? a.partial + (int64_t)(pr & 0x7fffffff) * F : static_cast<float *>(a.Y) + (int64_t)pr * F) + col;
           if (a.y_nt && pr >= 0) acc.store_n_nt(dst, a.F - col);  // partial rows are read back by the fixup pass: plain
           else acc.store_n(dst, a.F - col);
@@ -2560,8 +2837,9 @@ static int fused_dv_regs(const FusedArgs &a, int ng, size_t lds_without_scales, 
   return fit_without > fit_with ? 1 : 0;
 }
 
-// T: element type of the rows of X and Y.  bf16 (VEC = 4 only) takes the fp32 instances' decisions.
-template <int LPR, int VEC, typename T = float>
+// T: element type of the rows of X and Y.  bf16 (VEC = 4 only) takes the fp32 instances' decisions.  TY: rows of Y where they
+// are not T's (bf16 X, fp32 Y; no epilogue).
+template <int LPR, int VEC, typename T = float, typename TY = T>
 static hipError_t launch_fused_t(const FusedArgs &a, hipStream_t stream) {
   if (a.npanels == 0) return hipSuccess;
   constexpr int TW = LPR * VEC;
@@ -2573,8 +2851,8 @@ static hipError_t launch_fused_t(const FusedArgs &a, hipStream_t stream) {
       if (!fast || a.Wlin || a.Xe_mat) return hipErrorInvalidValue;
       const dim3 grid(a.npanels, (a.F + TW - 1) / TW);
       const size_t lds = (size_t)a.cap * TW * 4 + (size_t)a.max_rec_words * 4 + fused_scale_floats(a) * 4 + 16;  // dv_regs = 0
-      if (a.degE || a.W) return launch_lds<fused_packed_kernel<LPR, VEC, 8, true, false, true, false, 1024, true, false, T>, 1024>(grid, lds, stream, a);
-      return launch_lds<fused_packed_kernel<LPR, VEC, 8, true, false, false, false, 1024, true, false, T>, 1024>(grid, lds, stream, a);
+      if (a.degE || a.W) return launch_lds<fused_packed_kernel<LPR, VEC, 8, true, false, true, false, 1024, true, false, T, false, TY>, 1024>(grid, lds, stream, a);
+      return launch_lds<fused_packed_kernel<LPR, VEC, 8, true, false, false, false, 1024, true, false, T, false, TY>, 1024>(grid, lds, stream, a);
     }
   }
   if (a.ng != 256 / LPR) return hipErrorInvalidValue;  // records were packed for another lane layout
@@ -2619,6 +2897,21 @@ static hipError_t launch_fused_t(const FusedArgs &a, hipStream_t stream) {
           default: HG_PKL(true, true);
         }
 #undef HG_PKL
+      } else if constexpr (!XF32 && std::is_same_v<TY, T> && TW == 128) {
+        // the native bf16 epilogue (fused_linear_b16_ok): K = 128 staged, at most 32 rows -- the one operand plane (32 rows of
+        // 256 bytes, read whole) and the [rows][132] fp32 results both fit the tile region, which holds at least 16 x 132 floats
+        if (!fast || !fused_linear_b16_ok(a)) return hipErrorInvalidValue;
+        const size_t lds_l = lds_p - (size_t)a.cap * TW * 4 + (size_t)lin_tile_floats(a.cap, a.rows_cap, TW) * 4;
+        if ((size_t)lin_tile_floats(a.cap, a.rows_cap, TW) * 4 < 32 * 256) return hipErrorInvalidValue;
+        const int spec = (a.Xe_mat ? 1 : 0) | ((a.degE || a.W) ? 2 : 0);
+#define HG_PKB(M, S) return launch_lds<fused_packed_kernel<LPR, VEC, kB16U, true, M, S, true, 256, false, false, T, true>>(grid, lds_l, stream, ad)
+        switch (spec) {
+          case 0: HG_PKB(false, false);
+          case 1: HG_PKB(true, false);
+          case 2: HG_PKB(false, true);
+          default: HG_PKB(true, true);
+        }
+#undef HG_PKB
       } else {
         return hipErrorInvalidValue;
       }
@@ -2628,7 +2921,7 @@ static hipError_t launch_fused_t(const FusedArgs &a, hipStream_t stream) {
       // put every row gather of a group in flight at once (U = 16) instead of two batches.
       const bool u16 = a.npanels <= 512;
       const int spec = (a.Xe_mat ? 1 : 0) | ((a.degE || a.W) ? 2 : 0);
-#define HG_PK(UU, M, S) return launch_lds<fused_packed_kernel<LPR, VEC, UU, true, M, S, false, 256, true, false, T>>(grid, lds_p, stream, ad)
+#define HG_PK(UU, M, S) return launch_lds<fused_packed_kernel<LPR, VEC, UU, true, M, S, false, 256, true, false, T, false, TY>>(grid, lds_p, stream, ad)
       if (u16) {
         switch (spec) {
           case 0: HG_PK(16, false, false);
@@ -2659,7 +2952,39 @@ static hipError_t launch_fused_t(const FusedArgs &a, hipStream_t stream) {
       return launch_lds<fused_packed_kernel<LPR, VEC, 8, true, true, true>>(grid, lds_p, stream, ad);
     }
   }
-  return launch_lds<fused_packed_kernel<LPR, VEC, 8, false, true, true, false, 256, true, false, T>>(grid, lds_p, stream, ad);
+  return launch_lds<fused_packed_kernel<LPR, VEC, 8, false, true, true, false, 256, true, false, T, false, TY>>(grid, lds_p, stream, ad);
+}
+
+bool fused_linear_b16_ok(const FusedArgs &a) {
+  return fused_linear_ok(a) && a.F == 128 && a.F_out <= 128 && a.rows_cap > 0 && a.rows_cap <= 32;
+}
+
+hipError_t launch_linear_pack_bf16(int32_t F_out, int32_t F_in, const uint16_t *Wlin, void *wfrag, hipStream_t stream) {
+  if (F_out <= 0 || (F_out & 15) || (F_in != 32 && F_in != 64 && F_in != 128)) return hipErrorInvalidValue;
+  const int64_t n = (int64_t)(F_out >> 4) * (F_in >> 5) * 64;
+  hipLaunchKernelGGL(linear_pack_bf16_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, F_out, F_in, Wlin,
+                     static_cast<uint4 *>(wfrag));
+  return hipGetLastError();
+}
+
+hipError_t launch_linear_bf16(const LinearB16Args &a, bool t_f32, hipStream_t stream) {
+  if (a.nrows == 0) return hipSuccess;
+  if ((a.F_out & 15) || a.F_out <= 0) return hipErrorInvalidValue;
+  const int64_t nb = (a.nrows + 63) / 64;  // four waves of 16 rows
+  if (nb > 0x7fffffffLL) return hipErrorInvalidValue;
+  const dim3 grid((unsigned)nb), block(256);
+#define HG_LRB(KS_)                                                                                   \
+  if (t_f32) hipLaunchKernelGGL((linear_rows_bf16_kernel<KS_, true>), grid, block, 0, stream, a);     \
+  else hipLaunchKernelGGL((linear_rows_bf16_kernel<KS_, false>), grid, block, 0, stream, a);          \
+  break
+  switch (a.F_in) {
+    case 32: HG_LRB(1);
+    case 64: HG_LRB(2);
+    case 128: HG_LRB(4);
+    default: return hipErrorInvalidValue;
+  }
+#undef HG_LRB
+  return hipGetLastError();
 }
 
 hipError_t launch_linear_pack_split(int32_t F_out, int32_t F_in, const float *Wlin, void *wsplit, hipStream_t stream) {
@@ -2756,9 +3081,18 @@ hipError_t launch_linear(const LinearArgs &a, hipStream_t stream) {
 
 int fused_tile_row_floats(int F, bool vec4);
 
-hipError_t launch_fused(const FusedArgs &a, bool vec4, hipStream_t stream, bool xy_bf16) {
+hipError_t launch_fused(const FusedArgs &a, bool vec4, hipStream_t stream, bool xy_bf16, bool y_f32) {
   const int lpr = fused_tile_row_floats(a.F, vec4) / (vec4 ? 4 : 1);
-  if (xy_bf16 && (!vec4 || a.Wlin || (a.F & 3))) return hipErrorInvalidValue;
+  if (xy_bf16 && (!vec4 || (a.Wlin && (y_f32 || a.F != 128)) || (a.F & 3))) return hipErrorInvalidValue;
+  if (y_f32) {  // bf16 X, fp32 Y: the widths of the bf16 linear layer only
+    if (!xy_bf16) return hipErrorInvalidValue;
+    switch (a.F) {
+      case 32: return launch_fused_t<8, 4, bf16, float>(a, stream);
+      case 64: return launch_fused_t<16, 4, bf16, float>(a, stream);
+      case 128: return launch_fused_t<32, 4, bf16, float>(a, stream);
+      default: return hipErrorInvalidValue;
+    }
+  }
 #define HG_CASE(L)                                              \
   case L:                                                       \
     if (xy_bf16) return launch_fused_t<L, 4, bf16>(a, stream);   \

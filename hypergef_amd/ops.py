@@ -22,7 +22,7 @@ H diag(degE W) H^T diag(degV) grad instead.  Default: "reference".
 import torch
 
 from . import _lib
-from .plan import (cached_plan, linear_fusion_pays, linear_rows, linear_supported, linear_wgrad,
+from .plan import (cached_plan, linear_bf16_fusion_pays, linear_fusion_pays, linear_rows, linear_supported, linear_wgrad,
                    wgrad_supported, _check_feat, _check_index, _ptr, _rng_state_device, _rng_state_dtype,
                    _rng_state_length, _stream_handle)
 
@@ -45,6 +45,10 @@ class Options:
     linear_math: 'f32' = the folded projection on fp32 MFMA; 'bf16x6' = at F_in = 128 each fp32 product as six bf16
                  products on the bf16 MFMA (HG_LIN_BF16X6, include/hg_aggr.h): the same error bound, 3/8 of the matrix-pipe
                  cycles.  Forward of the fused layer only; every other width and kernel stays fp32 MFMA.
+    linear_bf16: how a bfloat16 layer's linear runs.  'torch' = torch's GEMM around the bf16 aggregation; 'mfma' = folded
+                 into the aggregation on the bf16 MFMA (hg_aggr_linear_res_bf16: fp32 accumulation, one rounding of the
+                 combined row and one of the result) wherever fuse_linear folds -- 'always' at every supported width,
+                 'auto' under plan.linear_bf16_fusion_pays; variants auto, pull and fused.  float32 layers ignore it.
 
     Every operator resolves its options per call -- an explicit `options=` argument, else the innermost
     `with ops.options(...)` block of the calling thread, else the process defaults -- and an autograd node keeps
@@ -54,10 +58,11 @@ class Options:
     backward: str = "reference"
     fuse_linear: str = "auto"
     linear_math: str = "f32"
+    linear_bf16: str = "torch"
 
     _CHOICES = {"variant": ("auto", "pull", "fused", "push_atomic", "push_groups"),
                 "backward": ("reference", "adjoint"), "fuse_linear": ("auto", "always", "never"),
-                "linear_math": ("f32", "bf16x6")}
+                "linear_math": ("f32", "bf16x6"), "linear_bf16": ("torch", "mfma")}
 
     def __post_init__(self):
         for k, allowed in Options._CHOICES.items():
@@ -72,7 +77,9 @@ _DEFAULTS_LOCK = threading.Lock()
 _DEFAULTS = Options(fuse_linear=_os.environ["HG_FUSE_LINEAR"]
                     if _os.environ.get("HG_FUSE_LINEAR") in ("auto", "always", "never") else "auto",  # A/B runs of the drivers
                     linear_math=_os.environ["HG_LINEAR_MATH"]
-                    if _os.environ.get("HG_LINEAR_MATH") in ("f32", "bf16x6") else "f32")
+                    if _os.environ.get("HG_LINEAR_MATH") in ("f32", "bf16x6") else "f32",
+                    linear_bf16=_os.environ["HG_LINEAR_BF16"]
+                    if _os.environ.get("HG_LINEAR_BF16") in ("torch", "mfma") else "torch")
 _TLS = threading.local()
 
 
@@ -127,6 +134,11 @@ def set_fuse_linear(mode):
 def set_linear_math(mode):
     """Process default of Options.linear_math."""
     _set_default(linear_math=mode)
+
+
+def set_linear_bf16(mode):
+    """Process default of Options.linear_bf16."""
+    _set_default(linear_bf16=mode)
 
 
 def _flat(t):
@@ -351,7 +363,8 @@ class _SumAggrLinear(torch.autograd.Function):
             raise ValueError("node_feat must be [N, F_in] and weight [F_out, F_in]")
         if weight.dtype != node_feat.dtype:
             raise TypeError("weight must have node_feat's dtype %s, got %s" % (node_feat.dtype, weight.dtype))
-        f32 = node_feat.dtype == torch.float32  # bf16: torch's GEMM, then the bf16 aggregation (no bf16 MFMA epilogue)
+        f32 = node_feat.dtype == torch.float32  # bf16: torch's GEMM, then the bf16 aggregation, unless linear_bf16 = 'mfma'
+        mfma16 = not f32 and opt.linear_bf16 == "mfma"  # the linear folded in on the bf16 MFMA (hg_aggr_linear_res_bf16)
         ctx.scale_shapes = tuple(None if t is None else t.shape for t in (degE, degV, W))
         trainable = ctx.trainable = _any_requires_grad(degE, degV, W)  # before flattening: see _forward
         degE, degV, W = _flat(degE), _flat(degV), _flat(W)
@@ -360,9 +373,12 @@ class _SumAggrLinear(torch.autograd.Function):
         variant = opt.variant
         plan = cached_plan(N, csrptr_t, indices_t)
         mode = opt.fuse_linear
-        fuse = f32 and ((mode == "always" and linear_supported(F_in, F_out)) or
-                        (mode == "auto" and linear_fusion_pays(F_in, F_out)))
-        if fuse and variant in ("auto", "pull", "fused"):
+        fuse = (f32 or mfma16) and ((mode == "always" and linear_supported(F_in, F_out)) or
+                                    (mode == "auto" and (linear_fusion_pays if f32 else linear_bf16_fusion_pays)(F_in, F_out)))
+        if fuse and mfma16 and variant in ("auto", "pull", "fused"):
+            out = plan.aggregate_linear_bf16(csrptr_t, indices_t, node_feat.contiguous(), weight.detach().contiguous(),
+                                             degE, degV, W, variant=variant, trainable_scales=trainable)
+        elif fuse and variant in ("auto", "pull", "fused"):
             out = plan.aggregate_linear(csrptr_t, indices_t, node_feat, weight.detach().contiguous(),
                                         degE, degV, W, variant=variant, math=opt.linear_math, trainable_scales=trainable)
         else:  # project, then aggregate at F_out (own MFMA rows kernel where it takes the widths)
@@ -428,7 +444,8 @@ class _AggrResLinear(torch.autograd.Function):
         degE, degV, W = _flat(degE), _flat(degV), _flat(W)
         N, F_in = node_feat.shape
         F_out = M.shape[0]
-        f32 = node_feat.dtype == torch.float32  # bf16: the torch form around the bf16 aggregation (no bf16 MFMA epilogue)
+        f32 = node_feat.dtype == torch.float32  # bf16: the torch form around the bf16 aggregation, unless linear_bf16 = 'mfma'
+        mfma16 = not f32 and opt.linear_bf16 == "mfma" and M.dtype == node_feat.dtype and (R is None or R.dtype == node_feat.dtype)
         # cb is a Python float except where it is learned (UniGIN's 1 + eps): then it stays on the device -- the
         # kernel reads it there (hg_aggr_linear_res_dev_f32), nothing is read back, and the step can be captured
         if R is None:
@@ -441,9 +458,16 @@ class _AggrResLinear(torch.autograd.Function):
         Md = M.detach().contiguous()
         Rd = None if R is None else R.detach().contiguous()
         mode = opt.fuse_linear
-        fuse = f32 and ((mode == "always" and linear_supported(F_in, F_out)) or
-                        (mode == "auto" and linear_fusion_pays(F_in, F_out)))
-        if fuse and variant in ("auto", "pull", "fused"):
+        fuse = (f32 or mfma16) and ((mode == "always" and linear_supported(F_in, F_out)) or
+                                    (mode == "auto" and (linear_fusion_pays if f32 else linear_bf16_fusion_pays)(F_in, F_out)))
+        if fuse and mfma16 and variant in ("auto", "pull", "fused"):
+            plan = cached_plan(N, csrptr_t, indices_t)
+            T = torch.empty_like(node_feat, memory_format=torch.contiguous_format) if need_t else None  # bf16: the kernel's T_out
+            # the kernel reads a learned cb as a float32 device scalar; the backward keeps cbf, the layer's own dtype, as the torch form
+            cbk = cb.detach().to(torch.float32).reshape(1).contiguous() if (R is not None and isinstance(cb, torch.Tensor)) else cbf
+            out = plan.aggregate_linear_bf16(csrptr_t, indices_t, node_feat.detach().contiguous(), Md, degE, degV, W,
+                                             variant=variant, residual=Rd, ca=ca, cb=cbk, relu=relu, t_out=T)
+        elif fuse and variant in ("auto", "pull", "fused"):
             plan = cached_plan(N, csrptr_t, indices_t)
             T = torch.empty_like(node_feat) if need_t else None
             out = plan.aggregate_linear(csrptr_t, indices_t, node_feat.detach(), Md, degE, degV, W, variant=variant,

@@ -355,6 +355,89 @@ class Plan:
             _lib.check(st)
         return Y
 
+    def linear_bf16_path(self, F_in, F_out, variant="auto"):
+        """hg_aggr_linear_bf16_path: which kernels aggregate_linear_bf16 runs for these widths, as a bit mask -- 1: the
+        fused panels run the bf16 epilogue themselves, 2: some or all rows go through the bf16 rows kernel."""
+        v = _lib.lib().hg_aggr_linear_bf16_path(self._h, F_in, F_out, _lib.VARIANTS[variant])
+        if v < 0:
+            _lib.check(v)
+        return v
+
+    def aggregate_linear_bf16(self, csrptr_t, colind_t, X, weight, degE=None, degV=None, W=None,
+                              variant="auto", out=None, workspace=None, packed=None, residual=None, ca=1.0,
+                              cb=0.0, relu=False, t_out=None, bind_scales=True, trainable_scales=False):
+        """aggregate_linear on bfloat16 rows with the linear on the bf16 MFMA (hg_aggr_linear_res_bf16): X, weight,
+        residual, t_out and the result are bfloat16, degE / degV / W float32, accumulation fp32.  t_out receives
+        (ca * Aggr(X) + cb * residual) of the fp32 call on the widened operands, rounded to bf16 once -- bit for bit
+        aggregate_linear(X.float(), ..., t_out=).to(bfloat16) -- and Y = round_bf16(act(t_out . weight^T)) (include/hg_aggr.h).
+        cb may be a one-element float32 device tensor.  packed = pack_linear_bf16(weight) if the caller keeps it.
+        Dtypes and shapes are refused (TypeError, ValueError) before any device is touched."""
+        for name, t in (("node_feat", X), ("weight", weight), ("residual", residual), ("t_out", t_out), ("out", out)):
+            if t is not None and (not isinstance(t, torch.Tensor) or t.dtype != torch.bfloat16):
+                raise TypeError("%s must be a bfloat16 tensor, got %s" % (name, getattr(t, "dtype", type(t))))
+        if isinstance(cb, torch.Tensor) and cb.dtype != torch.float32:
+            raise TypeError("a tensor cb must be float32, got %s" % cb.dtype)
+        if X.dim() != 2 or X.shape[0] != self.N:
+            raise ValueError("node_feat must be [N = %d, F_in], got %s" % (self.N, tuple(X.shape)))
+        F_in = X.shape[1]
+        if weight.dim() != 2 or weight.shape[1] != F_in:
+            raise ValueError("weight must be [F_out, F_in = %d]" % F_in)
+        F_out = weight.shape[0]
+        if not linear_supported(F_in, F_out):
+            raise ValueError("aggregate_linear_bf16 takes F_in in {32, 64, 128} and F_out a positive multiple of 16, got %d -> %d"
+                             % (F_in, F_out))
+        for name, t in (("residual", residual), ("t_out", t_out)):
+            if t is not None and tuple(t.shape) != (self.N, F_in):
+                raise ValueError("%s must be [N, F_in]" % name)
+        if out is not None and tuple(out.shape) != (self.N, F_out):
+            raise ValueError("out must be [N, F_out]")
+        if isinstance(cb, torch.Tensor) and cb.numel() != 1:
+            raise ValueError("a tensor cb must hold one element")
+        if packed is not None and packed.numel() * packed.element_size() != 2 * F_out * F_in:
+            raise ValueError("packed does not belong to this weight")
+        _check_feat(X, "node_feat", bf16_ok=True)
+        for name, t in (("weight", weight), ("residual", residual), ("t_out", t_out), ("out", out)):
+            if t is not None:
+                _check_feat(t, name, device=X.device, bf16_ok=True)
+        for name, t, n in (("degE", degE, self.M), ("degV", degV, self.N), ("W", W, self.M)):
+            if t is not None:
+                _check_feat(t, name, device=X.device)
+                if t.numel() != n:
+                    raise ValueError("%s must have %d elements, got %d" % (name, n, t.numel()))
+        if X.data_ptr() % 8 != 0:  # the entry takes 8-byte aligned rows (torch's own allocations are; views need not be)
+            X = X.clone()
+        if residual is not None and residual.data_ptr() % 8 != 0:
+            residual = residual.clone()
+        if packed is None:
+            packed = packed_linear_bf16_cached(weight)
+        W = self._drop_unit_weights(W, bind_scales and not trainable_scales)
+        if (degE is not None or degV is not None or W is not None) and variant in ("auto", "fused"):
+            self._bind_scales(F_in, degE, degV, W, X.device, bind_scales, trainable=trainable_scales)
+        Y = out if out is not None else torch.empty((self.N, F_out), dtype=torch.bfloat16, device=X.device)
+        if variant == "fused":
+            self._ensure_fused(F_in)
+        own_ws = workspace is None
+        if own_ws:
+            workspace = torch.empty(max(self.linear_workspace_bytes(F_in), 256), dtype=torch.uint8, device=X.device)
+        nbytes = workspace.numel() * workspace.element_size()
+        with torch.cuda.device(X.device):
+            if isinstance(cb, torch.Tensor):
+                _check_feat(cb, "cb", device=X.device)
+                cb_host, cb_dev = 0.0, _ptr(cb)
+            else:
+                cb_host, cb_dev = float(cb), None
+            head = (self._h, F_in, F_out, _ptr(csrptr_t), _ptr(colind_t), _ptr(X), _ptr(degE), _ptr(degV), _ptr(W),
+                    _ptr(packed), _ptr(residual), float(ca), cb_host, cb_dev, LIN_RELU if relu else 0, _ptr(t_out), _ptr(Y))
+            fn = _lib.lib().hg_aggr_linear_res_bf16
+            stream = _stream_handle(X.device)
+            st = fn(*head, _ptr(workspace), nbytes, _lib.VARIANTS[variant], stream)
+            if st == _lib.HG_ERR_WORKSPACE and own_ws:  # stale cached size: see aggregate()
+                self.__dict__.setdefault("_ws_bytes", {}).pop(("lin", F_in), None)
+                workspace = torch.empty(max(self.linear_workspace_bytes(F_in), 256), dtype=torch.uint8, device=X.device)
+                st = fn(*head, _ptr(workspace), workspace.numel(), _lib.VARIANTS[variant], stream)
+            _lib.check(st)
+        return Y
+
     def _drop_unit_weights(self, W, enable=True):
         """The reference's layers each carry their own all-ones `Wdiag` (model/ugsys/hgnn.py:12): multiplying by
         exactly 1.0f is the identity, so such a W is not passed on at all -- same bits, no multiply, and the
@@ -875,6 +958,14 @@ def linear_fusion_pays(F_in, F_out):
     return linear_supported(F_in, F_out) and (F_in <= 64 or F_out >= F_in)
 
 
+def linear_bf16_fusion_pays(F_in, F_out):
+    """The 'auto' rule of Options.linear_bf16 = 'mfma': linear_fusion_pays' rule, taken over unmeasured.  What decides
+    it is which width the aggregation runs at -- folded it gathers F_in-wide rows, unfolded F_out-wide ones -- and that
+    ratio is the same at two bytes per element as at four; the table of tools/bf16_linear_probe.py
+    (profiles/r12_bf16_linear.md) is what a later change of this rule should be taken from."""
+    return linear_fusion_pays(F_in, F_out)
+
+
 LIN_RELU, LIN_BF16X6 = 1, 2  # include/hg_aggr.h: flags of the linear epilogue
 
 
@@ -946,6 +1037,71 @@ def linear_rows(X, weight, packed=None, out=None):
     with torch.cuda.device(X.device):
         _lib.check(_lib.lib().hg_linear_rows_f32(X.shape[0], F_in, F_out, _ptr(X), _ptr(packed), _ptr(Y),
                                                  _stream_handle(X.device)))
+    return Y
+
+
+def _check_bf16_weight(weight):
+    if not isinstance(weight, torch.Tensor) or weight.dtype != torch.bfloat16:
+        raise TypeError("weight must be a bfloat16 tensor, got %s" % getattr(weight, "dtype", type(weight)))
+    if weight.dim() != 2 or not linear_supported(weight.shape[1], weight.shape[0]):
+        raise ValueError("weight must be [F_out, F_in] with F_in in {32, 64, 128} and F_out a positive multiple of 16")
+    _check_feat(weight, "weight", bf16_ok=True)
+
+
+def pack_linear_bf16(weight):
+    """A bfloat16 nn.Linear.weight [F_out, F_in] -> the fragment order of the bf16 MFMA (hg_linear_pack_bf16; one tiny
+    kernel): what aggregate_linear_bf16 and linear_rows_bf16 read.  Re-pack after every weight update."""
+    _check_bf16_weight(weight)
+    F_out, F_in = weight.shape
+    L = _lib.lib()
+    wfrag = torch.empty(max(int(L.hg_linear_pack_bf16_bytes(F_out, F_in)) // 2, 8), dtype=torch.bfloat16, device=weight.device)
+    with torch.cuda.device(weight.device):
+        _lib.check(L.hg_linear_pack_bf16(F_out, F_in, _ptr(weight), _ptr(wfrag), _stream_handle(weight.device)))
+    return wfrag
+
+
+def packed_linear_bf16_cached(weight):
+    """pack_linear_bf16(weight), cached as packed_linear_cached caches the fp32 packings (same key, same cache)."""
+    _check_bf16_weight(weight)
+    key = (weight.data_ptr(), weight._version, tuple(weight.shape), str(weight.device), "bf16")
+    stream = torch.cuda.current_stream(weight.device)
+    with _CACHE_LOCK:
+        hit = _PACK_CACHE.get(key)
+        if hit is not None:
+            _PACK_CACHE.move_to_end(key)
+    if hit is not None:
+        if hit[2] != stream.cuda_stream:  # packed on another stream: order this one behind the pack kernel
+            stream.wait_event(hit[3])
+        return hit[0]
+    packed = pack_linear_bf16(weight)
+    with torch.cuda.device(weight.device):
+        ev = torch.cuda.Event()
+        ev.record(stream)
+    with _CACHE_LOCK:
+        _PACK_CACHE[key] = (packed, weight, stream.cuda_stream, ev)
+        while len(_PACK_CACHE) > _PACK_CACHE_MAX:
+            _PACK_CACHE.popitem(last=False)
+    return packed
+
+
+def linear_rows_bf16(X, weight, packed=None, out=None):
+    """round_bf16(X . weight^T) for bfloat16 X [rows, F_in] and weight [F_out, F_in] on the library's bf16-MFMA rows kernel
+    (hg_linear_rows_bf16): exact products, fp32 accumulation, one rounding."""
+    if not isinstance(X, torch.Tensor) or X.dtype != torch.bfloat16:
+        raise TypeError("X must be a bfloat16 tensor, got %s" % getattr(X, "dtype", type(X)))
+    _check_bf16_weight(weight)
+    _check_feat(X, "X", device=weight.device, bf16_ok=True)
+    F_out, F_in = weight.shape
+    if X.dim() != 2 or X.shape[1] != F_in:
+        raise ValueError("X must be [rows, F_in = %d]" % F_in)
+    if packed is None:
+        packed = packed_linear_bf16_cached(weight)
+    if X.data_ptr() % 8 != 0:
+        X = X.clone()
+    Y = out if out is not None else torch.empty((X.shape[0], F_out), dtype=torch.bfloat16, device=X.device)
+    with torch.cuda.device(X.device):
+        _lib.check(_lib.lib().hg_linear_rows_bf16(X.shape[0], F_in, F_out, _ptr(X), _ptr(packed), _ptr(Y),
+                                                  _stream_handle(X.device)))
     return Y
 
 

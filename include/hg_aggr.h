@@ -387,6 +387,48 @@ HG_API int hg_aggr_linear_f32(const hg_plan *plan, int32_t F_in, int32_t F_out,
                               const float *wfrag, float *Y, void *workspace, size_t workspace_bytes,
                               int32_t variant, hg_stream_t stream);
 
+/* The same layer on bf16 rows, its linear on the bf16 MFMA (v_mfma_f32_16x16x32_bf16) with fp32 accumulation.
+ * X, R, T_out [N, F_in] and Y [N, F_out] are bf16 (bit patterns); Wlin [F_out, F_in] is bf16 and reaches the kernels
+ * packed: hg_linear_pack_bf16 writes hg_linear_pack_bf16_bytes(F_out, F_in) = 2 F_out F_in bytes (0 for widths the
+ * entries do not take) into wfrag.  degE, degV and W stay fp32.  F_in in {32, 64, 128}, F_out a positive multiple of 16.
+ * The call runs the variant (the AUTO choice included) and the schedule hg_aggr_linear_res_f32 runs for the same
+ * widths, with its hg_plan_bind_scales binding, and takes the same workspace, hg_aggr_linear_workspace_bytes(plan, F_in).
+ * cb_dev != NULL overrides cb (a device scalar, as in hg_aggr_linear_res_dev_f32).  flags: HG_LIN_RELU or 0.
+ *
+ * Numerical contract.  With t32 the combined fp32 row ca * Aggr(X) + cb * R of hg_aggr_linear_res_f32 on the widened X
+ * and R (same plan, variant, ca, cb):
+ *   T_out[v] == round_bf16(t32[v]) bit for bit (round to nearest even, once);
+ *   Y[v, n]  =  round_bf16(act(sum_k T_out[v, k] * Wb[n, k])): the products are exact in fp32, the sum is accumulated in
+ *               fp32 in an order that depends on the plan and the widths only -- two calls give the same bits -- and the
+ *               result is rounded to bf16 once, after the optional relu;
+ *   a vertex in no hyperedge, with R == NULL, gives Y[v, :] = +0.
+ * Non-finite operands are not special-cased: a NaN or infinity in X or R reaches T_out as round_bf16 leaves it (NaN stays
+ * NaN, a finite fp32 value above bf16's range becomes infinity) and spreads to every Y[v, :] of its row through the
+ * products (inf * 0 = NaN); relu maps NaN to 0, as the fp32 entry's does.  Rows of other vertices are not affected.
+ *
+ * Refusals launch nothing, set hg_last_error, and are decided in this order: HG_ERR_INVALID for a null plan, csrptr_t,
+ * colind_t (nnz > 0), X, wfrag or Y, or for a flag other than HG_LIN_RELU; HG_ERR_UNSUPPORTED for
+ * HG_VARIANT_PUSH_ATOMIC (or an unknown variant), for F_in outside {32, 64, 128} and for F_out % 16 != 0;
+ * HG_ERR_UNSUPPORTED when X, Y, R or T_out is not 8-byte aligned or wfrag not 16-byte aligned; HG_ERR_UNSUPPORTED for a
+ * plan built with HG_PLAN_HOST_ONLY; HG_ERR_WORKSPACE for a null, too small or not 16-byte aligned workspace.
+ *
+ * hg_aggr_linear_bf16_path tells which kernels such a call runs, as a bit mask: 1 = the fused panels run the epilogue
+ * themselves (F_in = 128, F_out <= 128, fused variant, panels of at most 32 rows); 2 = some or all rows -- every row at
+ * F_in = 32 / 64 and on the pull variant, hub and split vertices otherwise -- are aggregated in fp32 and go through the
+ * rows kernel of hg_linear_rows_bf16.  A negative value is an hg_status.  It may build the schedule (host work), launches
+ * nothing, and works on a host-only plan.
+ * hg_linear_rows_bf16: Y[nrows, F_out] = round_bf16(T[nrows, F_in] . Wb^T) on that kernel; T and Y 8-byte aligned. */
+HG_API size_t hg_linear_pack_bf16_bytes(int32_t F_out, int32_t F_in);
+HG_API int hg_linear_pack_bf16(int32_t F_out, int32_t F_in, const uint16_t *Wlin, void *wfrag, hg_stream_t stream);
+HG_API int hg_aggr_linear_res_bf16(const hg_plan *plan, int32_t F_in, int32_t F_out, const int32_t *csrptr_t,
+                                   const int32_t *colind_t, const uint16_t *X, const float *degE, const float *degV,
+                                   const float *W, const void *wfrag, const uint16_t *R, float ca, float cb,
+                                   const float *cb_dev, int32_t flags, uint16_t *T_out, uint16_t *Y, void *workspace,
+                                   size_t workspace_bytes, int32_t variant, hg_stream_t stream);
+HG_API int hg_linear_rows_bf16(int64_t nrows, int32_t F_in, int32_t F_out, const uint16_t *T, const void *wfrag,
+                               uint16_t *Y, hg_stream_t stream);
+HG_API int hg_aggr_linear_bf16_path(const hg_plan *plan, int32_t F_in, int32_t F_out, int32_t variant);
+
 /* One hop only (CSR times dense with unit values, optional row scales):
  *   dst[r,:] = scaleB[r] * scaleA[r] * sum_{p in row r} src[ind[p],:]
  * hop = 0 walks H_T (nrows = M, src has N rows), hop = 1 walks the derived H

@@ -56,6 +56,9 @@ def parse():
                         "such an epoch is ~100 launches of host latency; the eager figures are printed beside the replays")
     p.add_argument("--linear-math", default="f32", choices=["f32", "bf16x6"],
                    help="hgsys backend, layers fused at nhid = 128 on batches: fp32 MFMA, or six bf16 products per fp32 product")
+    p.add_argument("--linear-bf16", default="torch", choices=["torch", "mfma"],
+                   help="hgsys backend with --dtype bfloat16: the layers' linear as torch's GEMM around the bf16 aggregation, or "
+                        "folded into it on the bf16 MFMA (ops.Options.linear_bf16)")
     p.add_argument("--dtype", default="float32", choices=["float32", "bfloat16"],
                    help="features and parameters (model.to(dtype)); the hypergraph's scale vectors stay fp32")
     p.add_argument("--learn-hyperedge-weight", action="store_true",
@@ -71,6 +74,7 @@ def main():
     import hypergef_amd as hg
     from hypergef_amd import models, ops, synth
     ops.set_linear_math(args.linear_math)  # process default: the models resolve their options at every forward
+    ops.set_linear_bf16(args.linear_bf16)
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
