@@ -10,8 +10,8 @@ from . import ops, plan, synth  # noqa: F401
 from .balancer import balance_schedule  # noqa: F401
 from .hypergraph import HyperGraph  # noqa: F401
 from .ops import (HGNNAggr, HGNNAggrIncidence, HGNNAggrLinear, UniGNNConv, UniGNNConvdeg,  # noqa: F401
-                  UniGNNConvLinear, hgnnaggr_linear, incidence_aggr, incidence_dot, incidence_gather, incidence_softmax,
-                  incidence_sum)
+                  UniGNNConvLinear, hgnnaggr_linear, incidence_aggr, incidence_attention_aggr, incidence_dot,
+                  incidence_gather, incidence_softmax, incidence_sum)
 from .plan import Plan  # noqa: F401
 
 from .models import HypergraphAttnConv  # noqa: F401

@@ -47,6 +47,8 @@ SYMBOLS = (
     "hg_incidence_attention_entry_dropout_heads_f32", "hg_incidence_attention_entry_dropout_heads_bwd_f32",
     "hg_gather_rows_incidence_heads_f32",
     "hg_hyperedge_dot_heads_f32", "hg_rows_dot_f32",
+    "hg_incidence_attention_stats_heads_f32", "hg_aggr_incidence_attention_heads_f32",
+    "hg_gather_rows_attention_heads_f32",
 )
 
 
@@ -258,6 +260,15 @@ def lib():
         L.hg_hyperedge_dot_heads_f32.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp]
         L.hg_rows_dot_f32.restype = ctypes.c_int
         L.hg_rows_dot_f32.argtypes = [i64, i32, vp, vp, vp, vp]
+    if hasattr(L, "hg_aggr_incidence_attention_heads_f32"):  # likewise: the attention coefficients formed in the gather
+        L.hg_incidence_attention_stats_heads_f32.restype = ctypes.c_int
+        L.hg_incidence_attention_stats_heads_f32.argtypes = [vp, i32, i32, vp, vp, vp, vp, ctypes.c_float, vp, vp, vp]
+        L.hg_aggr_incidence_attention_heads_f32.restype = ctypes.c_int
+        L.hg_aggr_incidence_attention_heads_f32.argtypes = [vp, i32, i32, i32, vp, vp, vp, vp, vp, ctypes.c_float, vp, vp,
+                                                            vp, vp, vp, vp, vp, vp, sz, vp]
+        L.hg_gather_rows_attention_heads_f32.restype = ctypes.c_int
+        L.hg_gather_rows_attention_heads_f32.argtypes = [vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, ctypes.c_float, vp, vp,
+                                                         vp, vp, vp, vp, sz, vp]
     L.hg_aggr_push_groups_f32.restype = ctypes.c_int
     L.hg_aggr_push_groups_f32.argtypes = [i32, i32, i32, i64, vp, vp, vp, vp, vp, vp,
                                           vp, vp, vp, vp, vp, vp]

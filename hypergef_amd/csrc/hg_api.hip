@@ -434,7 +434,8 @@ int run_sched(const hg_plan *p, const hg::Sched &s, int32_t F, const int32_t *pt
               const int32_t *ind, const void *src, const float *scaleA, const float *scaleB,
               const int32_t *scale_map, const int32_t *dst_map, void *dst, float *partial,
               hipStream_t stream, bool nt_dst = false, bool src_bf16 = false, bool dst_bf16 = false,
-              const float *w = nullptr, const int32_t *wperm = nullptr, int32_t heads = 1) {
+              const float *w = nullptr, const int32_t *wperm = nullptr, int32_t heads = 1,
+              const hg::AttnGatherArgs *attn = nullptr) {
   hg::HeadsGatherArgs a;  // heads > 1: w is [nnz, heads] (hg_aggr_incidence_heads_f32)
   a.heads = heads;
   a.C = F / heads;
@@ -460,9 +461,19 @@ int run_sched(const hg_plan *p, const hg::Sched &s, int32_t F, const int32_t *pt
   a.panel_nnz = p->opts.panel_nnz;
   a.xcd_remap = (p->opts.flags & HG_PLAN_NO_XCD_REMAP) ? 0 : 1;
   const bool vec4 = (F % 4 == 0) && aligned_lane(src, src_bf16) && aligned_lane(dst, dst_bf16) && aligned16(partial);
-  if (w && (src_bf16 || dst_bf16)) {
+  if ((w || attn) && (src_bf16 || dst_bf16)) {
     hg::set_error("weighted row gather: fp32 rows only");
     return HG_ERR_UNSUPPORTED;
+  }
+  if (attn) {  // the weights are formed in the lanes (hg_aggr_incidence_attention_heads_f32): the heads instances' lane rule
+    hg::AttnGatherArgs aa = *attn;
+    static_cast<hg::GatherArgs &>(aa) = a;
+    aa.heads = heads;
+    aa.C = a.C;
+    const hipError_t e =
+        hg::launch_gather_attention(aa, (int)s.fixups.size(), s.n_fix_l1, s.d_fixups, vec4, vec4 && aa.C % 4 == 0, stream);
+    if (e != hipSuccess) return hip_fail("gather_rows attention launch", e);
+    return HG_OK;
   }
   hipError_t e = (w && heads > 1)
                      ? hg::launch_gather_heads(a, (int)s.fixups.size(), s.n_fix_l1, s.d_fixups, vec4, vec4 && a.C % 4 == 0, stream)
@@ -598,7 +609,8 @@ int run_segments(const char *who, const hg_plan *plan, int body, int side, const
                  const hg::DropFields *drop = nullptr, const float *entry = nullptr) {
   int rc;
   const int32_t *perm = nullptr;
-  if (side == 1 && (rc = get_incidence_perm(plan, true, &perm)) != HG_OK) return rc;
+  // kSegStats writes per segment and looks no position up: side 1 runs without the permutation
+  if (side == 1 && body != hg::kSegStats && (rc = get_incidence_perm(plan, true, &perm)) != HG_OK) return rc;
   int32_t width = 4;
   if ((rc = get_segments(plan, side, true, &a.long_seg, &a.nlong, &width)) != HG_OK) return rc;
   a.ptr = side == 0 ? csrptr_t : plan->d_ptr_v;
@@ -2104,6 +2116,160 @@ int hg_incidence_attention_heads_bwd_f32(const hg_plan *plan, int32_t group, int
   b.out_seg = other_out;
   return run_segments("incidence_attention_bwd sum launch", plan, hg::kSegSum, 1 - group, csrptr_t, colind_t, nullptr,
                       nullptr, b, s, heads);
+}
+
+// ---- fused attention aggregation: the coefficients formed inside the gather ----------------------------------------------
+
+// The refusals the three entries share, in the documented order; has_F false: the entry has no feature width.
+static int check_attention_call(const char *who, const hg_plan *plan, int32_t hop, int32_t group, int32_t heads, int32_t F,
+                                bool has_F = true) {
+  if (!plan) {
+    hg::set_error(std::string(who) + ": null plan");
+    return HG_ERR_INVALID;
+  }
+  if (hop != 0 && hop != 1) {
+    hg::set_error(std::string(who) + ": hop must be 0 (to the hyperedges) or 1 (to the vertices)");
+    return HG_ERR_INVALID;
+  }
+  if (group != 0 && group != 1) {
+    hg::set_error(std::string(who) + ": group must be 0 (hyperedge) or 1 (vertex)");
+    return HG_ERR_INVALID;
+  }
+  if (heads < 1) {
+    hg::set_error(std::string(who) + ": heads must be at least 1");
+    return HG_ERR_INVALID;
+  }
+  if (has_F && (F < 1 || F % heads != 0)) {
+    hg::set_error(std::string(who) + ": the feature width " + std::to_string(F) + " must be a positive multiple of heads = " +
+                  std::to_string(heads));
+    return HG_ERR_INVALID;
+  }
+  if ((int64_t)std::max<int64_t>(plan->nnz, std::max(plan->N, plan->M)) * heads >= ((int64_t)1 << 40) ||
+      (int64_t)std::max(plan->N, plan->M) * std::max(F, 1) >= ((int64_t)1 << 40)) {
+    hg::set_error(std::string(who) + ": nnz * heads or the feature matrix too large");
+    return HG_ERR_INVALID;
+  }
+  return HG_OK;
+}
+
+int hg_incidence_attention_stats_heads_f32(const hg_plan *plan, int32_t group, int32_t heads, const int32_t *csrptr_t,
+                                           const int32_t *colind_t, const float *sv, const float *se, float slope,
+                                           float *seg_max_out, float *seg_inv_out, hg_stream_t stream) {
+  const char *who = "hg_incidence_attention_stats_heads_f32";
+  int rc = check_attention_call(who, plan, 0, group, heads, 1, false);
+  if (rc != HG_OK) return rc;
+  if (!csrptr_t || (plan->nnz > 0 && !colind_t) || !seg_max_out || !seg_inv_out) {
+    hg::set_error(std::string(who) + ": null array");
+    return HG_ERR_INVALID;
+  }
+  if (!(slope == slope) || slope - slope != 0.f) {
+    hg::set_error(std::string(who) + ": non-finite slope");
+    return HG_ERR_INVALID;
+  }
+  if (plan->opts.flags & HG_PLAN_HOST_ONLY) {
+    hg::set_error(std::string(who) + ": plan was built with HG_PLAN_HOST_ONLY and holds no device arrays");
+    return HG_ERR_UNSUPPORTED;
+  }
+  hg::SegArgs a = {};  // run even without incidences: every segment is empty and gets (0, 0)
+  a.slope = slope;
+  a.out_entry = seg_max_out;
+  a.out_seg = seg_inv_out;
+  return run_segments("incidence_attention_stats launch", plan, hg::kSegStats, group, csrptr_t, colind_t, sv, se, a,
+                      static_cast<hipStream_t>(stream), heads);
+}
+
+// One hop with the coefficients formed in the gather: incidence_hop's schedule and streaming-store choice, the WA
+// instances.  The destination row is the segment on hop == group; otherwise the statistics are gathered with the entry.
+static int attention_hop(const hg_plan *plan, int hop, int group, int32_t F, int32_t heads, const int32_t *csrptr_t,
+                         const int32_t *colind_t, const float *src, const float *sv, const float *se, float slope,
+                         const float *seg_max, const float *seg_inv, const float *scaleA, const float *scaleB, float *dst,
+                         char *ws, const Carve &c, hipStream_t s) {
+  int kind = 1;
+  {
+    hg_plan *mp = const_cast<hg_plan *>(plan);
+    std::lock_guard<std::mutex> lock(mp->auto_mu);
+    auto it = mp->hop_kernel.find(F);
+    if (it != mp->hop_kernel.end()) kind = hop == 0 ? it->second % 3 : (it->second / 3) % 3;
+  }
+  const hg::Sched &sc = (kind == 2 && plan->has_lat) ? plan->sched_lat[hop] : plan->sched[hop];
+  const bool nt = rows_whole_64(dst, F) && (hop == 1 || (int64_t)plan->M * F * 4 >= ((int64_t)192 << 20));
+  hg::AttnGatherArgs at;
+  at.row_score = hop == 0 ? se : sv;
+  at.ent_score = hop == 0 ? sv : se;
+  at.seg_max = seg_max;
+  at.seg_inv = seg_inv;
+  at.stat_row = hop == group ? 1 : 0;
+  at.slope = slope;
+  return run_sched(plan, sc, F, hop == 0 ? csrptr_t : plan->d_ptr_v, hop == 0 ? colind_t : plan->d_ind_v, src, scaleA, scaleB,
+                   nullptr, nullptr, dst, reinterpret_cast<float *>(ws + c.part[hop]), s, nt, false, false, nullptr, nullptr,
+                   heads, &at);
+}
+
+// What both gather entries refuse after check_attention_call: null arrays, the workspace, a host-only plan, panels whose
+// per-row scalars leave no LDS.
+static int check_attention_gather(const char *who, const hg_plan *plan, int32_t F, int32_t heads, bool arrays_ok, float slope,
+                                  const void *workspace, size_t workspace_bytes) {
+  if (!arrays_ok) {
+    hg::set_error(std::string(who) + ": null array");
+    return HG_ERR_INVALID;
+  }
+  if (!(slope == slope) || slope - slope != 0.f) {
+    hg::set_error(std::string(who) + ": non-finite slope");
+    return HG_ERR_INVALID;
+  }
+  const size_t need = carve(plan, F).total;
+  if (need > 0 && (!workspace || workspace_bytes < need)) {
+    hg::set_error(std::string(who) + ": workspace too small: need " + std::to_string(need) + " bytes, got " +
+                  std::to_string(workspace_bytes));
+    return HG_ERR_WORKSPACE;
+  }
+  if (reinterpret_cast<uintptr_t>(workspace) & 255) {
+    hg::set_error(std::string(who) + ": workspace must be 256-byte aligned");
+    return HG_ERR_INVALID;
+  }
+  if (plan->opts.flags & HG_PLAN_HOST_ONLY) {
+    hg::set_error(std::string(who) + ": plan was built with HG_PLAN_HOST_ONLY and holds no device schedule");
+    return HG_ERR_UNSUPPORTED;
+  }
+  if (hg::attn_gather_lds_bytes(plan->opts.panel_rows, plan->opts.panel_nnz, heads, true) > (size_t)160 * 1024) {
+    hg::set_error(std::string(who) + ": panel_rows * heads leaves no LDS for the rows' scores and statistics (160 KiB per workgroup)");
+    return HG_ERR_UNSUPPORTED;
+  }
+  return HG_OK;
+}
+
+int hg_gather_rows_attention_heads_f32(const hg_plan *plan, int32_t hop, int32_t group, int32_t F, int32_t heads,
+                                       const int32_t *csrptr_t, const int32_t *colind_t, const float *src, const float *sv,
+                                       const float *se, float slope, const float *seg_max, const float *seg_inv,
+                                       const float *scaleA, const float *scaleB, float *dst, void *workspace,
+                                       size_t workspace_bytes, hg_stream_t stream) {
+  const char *who = "hg_gather_rows_attention_heads_f32";
+  int rc = check_attention_call(who, plan, hop, group, heads, F);
+  if (rc != HG_OK) return rc;
+  const bool arrays_ok = csrptr_t && (plan->nnz == 0 || colind_t) && src && dst && seg_max && seg_inv;
+  if ((rc = check_attention_gather(who, plan, F, heads, arrays_ok, slope, workspace, workspace_bytes)) != HG_OK) return rc;
+  return attention_hop(plan, hop, group, F, heads, csrptr_t, colind_t, src, sv, se, slope, seg_max, seg_inv, scaleA, scaleB, dst,
+                       static_cast<char *>(workspace), carve(plan, F), static_cast<hipStream_t>(stream));
+}
+
+int hg_aggr_incidence_attention_heads_f32(const hg_plan *plan, int32_t F, int32_t heads, int32_t group, const int32_t *csrptr_t,
+                                          const int32_t *colind_t, const float *X, const float *sv, const float *se, float slope,
+                                          const float *seg_max, const float *seg_inv, const float *degE, const float *degV,
+                                          const float *W, float *Xe_out, float *Y, void *workspace, size_t workspace_bytes,
+                                          hg_stream_t stream) {
+  const char *who = "hg_aggr_incidence_attention_heads_f32";
+  int rc = check_attention_call(who, plan, 0, group, heads, F);
+  if (rc != HG_OK) return rc;
+  const bool arrays_ok = csrptr_t && (plan->nnz == 0 || colind_t) && X && Y && seg_max && seg_inv;
+  if ((rc = check_attention_gather(who, plan, F, heads, arrays_ok, slope, workspace, workspace_bytes)) != HG_OK) return rc;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const Carve c = carve(plan, F);
+  char *ws = static_cast<char *>(workspace);
+  float *Xe = Xe_out ? Xe_out : reinterpret_cast<float *>(ws + c.xe);
+  // hop 1: Xe[e] = ((sum_{p=(e,u)} alpha[p] X[u]) * degE[e]) * W[e]; hop 2: Y[v] = (sum_{p=(e,v)} alpha[p] Xe[e]) * degV[v]
+  rc = attention_hop(plan, 0, group, F, heads, csrptr_t, colind_t, X, sv, se, slope, seg_max, seg_inv, degE, W, Xe, ws, c, s);
+  if (rc != HG_OK) return rc;
+  return attention_hop(plan, 1, group, F, heads, csrptr_t, colind_t, Xe, sv, se, slope, seg_max, seg_inv, degV, nullptr, Y, ws, c, s);
 }
 
 // ---- attention dropout: the softmax and its backward with the mask of hg_philox.h fused in ---------------------------

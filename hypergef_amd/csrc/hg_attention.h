@@ -22,8 +22,24 @@ enum {
   kSegSoftmaxEntry = 5,
   kSegSoftmaxEntryBwd = 6,
   kSegSoftmaxEntryDrop = 7,
-  kSegSoftmaxEntryDropBwd = 8
+  kSegSoftmaxEntryDropBwd = 8,
+  // kSegSoftmax's maximum and sum passes alone: out_entry [nseg] receives every segment's maximum, out_seg [nseg] the
+  // reciprocal of its sum (0 and 0 for an empty segment); no alpha is written and perm is not read
+  kSegStats = 9
 };
+
+// The score's non-linearity and the coefficient of one incidence from its segment's statistics (kSegStats): what
+// softmax_segment forms entry by entry -- raw = own + other with the segment's own score first (absent: 0) and the
+// other end's absent meaning no addition, leaky relu, __expf of the difference to the maximum, times the reciprocal of
+// the sum -- in that order, so that a kernel that forms its weights here (gather_rows_kernel's attention instances) has
+// the bits kSegSoftmax would have written.  The library is built without floating-point contraction: the product
+// slope * raw and the subtraction stay two roundings here as there.
+__device__ __forceinline__ float leaky(float raw, float slope) { return raw > 0.f ? raw : slope * raw; }
+__device__ __forceinline__ float attention_weight(float own, float other, bool has_other, float slope, float seg_max,
+                                                  float seg_inv) {
+  const float raw = has_other ? own + other : own;
+  return __expf(leaky(raw, slope) - seg_max) * seg_inv;
+}
 
 struct SegArgs {
   const int32_t *ptr;       // the side's CSR row pointers [nseg + 1]: csrptr_t, or the derived ptr_v
@@ -36,8 +52,8 @@ struct SegArgs {
   float slope;
   const float *val;    // kSegSoftmaxBwd: alpha; kSegSum: the summed values; H_T order
   const float *dval;   // kSegSoftmaxBwd: dalpha, H_T order
-  float *out_entry;    // kSegSoftmax: alpha; kSegSoftmaxBwd: ds; H_T order
-  float *out_seg;      // kSegSoftmaxBwd: the segments' own sums of ds (or null); kSegSum: out [nseg]
+  float *out_entry;    // kSegSoftmax: alpha; kSegSoftmaxBwd: ds; H_T order.  kSegStats: the segments' maxima [nseg]
+  float *out_seg;      // kSegSoftmaxBwd: the segments' own sums of ds (or null); kSegSum: out [nseg]; kSegStats: 1 / sum [nseg]
 };
 
 // The same arrays with `heads` columns, head fastest: own / other / out_seg [*, heads], val / dval / out_entry [nnz, heads].

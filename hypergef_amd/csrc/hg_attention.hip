@@ -40,6 +40,11 @@
 // -- leaky relu, maximum, exponentials, reduction order, the mask -- is the code above, so t = 0 gives the bits of the
 // plain bodies.  The backward's ds is the gradient of t itself.  The four bodies share one kernel on the most general
 // argument block (heads and dropout): 24 instances and one more copy of the work split instead of 96 and four.
+//
+// Segment statistics (kSegStats, on segment_kernel / segment_heads_kernel).  The softmax body up to the reciprocal of the
+// sum, which then leaves with the maximum, [nseg, H]: lane groups, the workgroup path and the order of reduction are the
+// softmax's, so attention_weight (hg_attention.h) on the two gives alpha's bits and no [nnz, H] array need exist
+// (hg_aggr_incidence_attention_heads_f32).  Positions are not looked up: side 1 runs without perm.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -121,8 +126,6 @@ __device__ __forceinline__ float raw_entry(const SegArgs &a, const Entry &en, Co
   return raw_score(a, col, own, i) + en.t[col(position<SIDE>(a, i))];
 }
 
-__device__ __forceinline__ float leaky(float raw, float slope) { return raw > 0.f ? raw : slope * raw; }
-
 // The dropout of a launch as a lane holds it: the state read from device memory when the kernel runs (a seed passed by
 // value would be frozen into a captured launch), the threshold, the scale and the second output.
 struct NoDrop {};
@@ -145,9 +148,11 @@ __device__ __forceinline__ float dropped(const Drop &d, Col<MH> col, int32_t p, 
 
 // alpha = softmax over the segment of leaky(raw).  An empty segment runs no entry loop at all: nothing is written and no
 // exponential of (-inf) - (-inf) is formed.  A one-entry segment gives exp(0) / 1 = 1.0f exactly.
-template <int SIDE, int W, bool MH, typename DROP = NoDrop, typename ENT = NoEntry>
+// STATS (kSegStats): the maximum and sum passes as they stand, then the segment's m and 1 / sum go out in place of alpha
+// (0 and 0 for an empty segment, whose m is -inf and whose sum is 0); positions are not looked up, so perm is not read.
+template <int SIDE, int W, bool MH, typename DROP = NoDrop, typename ENT = NoEntry, bool STATS = false>
 __device__ __forceinline__ void softmax_segment(const SegArgs &a, Col<MH> col, int32_t seg, int32_t beg, int32_t end, int lane,
-                                                float *lds, const DROP &d = DROP{}, const ENT &en = ENT{}) {
+                                                float *lds, const DROP &d = DROP{}, const ENT &en = ENT{}, bool valid = true) {
   constexpr bool kDrop = std::is_same_v<DROP, Drop>;
   constexpr bool kEnt = std::is_same_v<ENT, Entry>;
   const float own = (a.own && beg < end) ? a.own[col(seg)] : 0.f;
@@ -158,7 +163,7 @@ __device__ __forceinline__ void softmax_segment(const SegArgs &a, Col<MH> col, i
   for (int k = 0; k < kSegKeep; k++) {
     const int32_t i = beg + lane + k * W;
     if (i < end) {
-      pos[k] = position<SIDE>(a, i);
+      if constexpr (!STATS) pos[k] = position<SIDE>(a, i);
       if constexpr (kEnt) sc[k] = leaky(raw_entry(a, en, col, own, i, pos[k]), a.slope);
       else sc[k] = leaky(raw_score(a, col, own, i), a.slope);
       m = fmaxf(m, sc[k]);
@@ -186,6 +191,13 @@ __device__ __forceinline__ void softmax_segment(const SegArgs &a, Col<MH> col, i
   }
   sum = combine<W, OpSum>(sum, lds);
   const float inv = 1.f / sum;  // the entry holding the maximum contributes exp(0) = 1: sum >= 1 wherever it is used
+  if constexpr (STATS) {
+    if (lane == 0 && valid) {
+      a.out_entry[col(seg)] = beg < end ? m : 0.f;
+      a.out_seg[col(seg)] = beg < end ? inv : 0.f;
+    }
+    return;
+  }
 #pragma unroll
   for (int k = 0; k < kSegKeep; k++)
     if (beg + lane + k * W < end) {
@@ -300,6 +312,8 @@ __device__ __forceinline__ void run_segment(const ARGS &a, Col<MH> col, int32_t 
     softmax_segment<SIDE, W>(a, col, seg, beg, end, lane, lds, load_drop(a.drop), Entry{a.entry});
   else if constexpr (BODY == kSegSoftmaxEntryDropBwd)
     softmax_bwd_segment<SIDE, W>(a, col, seg, beg, end, lane, lds, valid, load_drop(a.drop), Entry{a.entry});
+  else if constexpr (BODY == kSegStats)
+    softmax_segment<SIDE, W, MH, NoDrop, NoEntry, true>(a, col, seg, beg, end, lane, lds, NoDrop{}, NoEntry{}, valid);
   else sum_segment<SIDE, W>(a, col, seg, beg, end, lane, lds, valid);
 }
 
@@ -507,6 +521,9 @@ hipError_t launch_body(int body, int side, int width, int64_t heads, const ARGS 
       case kSegSoftmax: return launch_side<kSegSoftmax>(side, width, (unsigned)nblocks, a, stream);
       case kSegSoftmaxBwd: return launch_side<kSegSoftmaxBwd>(side, width, (unsigned)nblocks, a, stream);
       case kSegSum: return launch_side<kSegSum>(side, width, (unsigned)nblocks, a, stream);
+      case kSegStats:
+        if (!a.out_entry || !a.out_seg) return hipErrorInvalidValue;
+        return launch_side<kSegStats>(side, width, (unsigned)nblocks, a, stream);
     }
   }
   return hipErrorInvalidValue;

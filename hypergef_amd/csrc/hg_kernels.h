@@ -47,6 +47,20 @@ struct HeadsGatherArgs : WeightedGatherArgs {
   int32_t heads = 1, C = 0;
 };
 
+// The attention coefficients formed in the gather (hg_aggr_incidence_attention_heads_f32): the weight of entry p of row r
+// for head h is attention_weight (hg_attention.h) of the row's score, the score of the entry's other end ind[p], and the
+// statistics of p's segment -- the row (stat_row) or the entry's other end.  All four arrays are [*, heads], head fastest.
+// Only gather_rows_kernel's WA instances take it; they stage no weights and read no permutation.
+struct AttnGatherArgs : GatherArgs {
+  const float *row_score = nullptr;  // [nrows, heads], or null (0)
+  const float *ent_score = nullptr;  // [rows of src, heads], or null (0)
+  const float *seg_max = nullptr;    // stat_row: [nrows, heads]; else [rows of src, heads]
+  const float *seg_inv = nullptr;
+  int32_t stat_row = 0;
+  float slope = 0.f;
+  int32_t heads = 1, C = 0;
+};
+
 // What happens to an aggregated row t = Aggr(X)[v] on its way through the linear epilogue:
 //   t' = ca * t + cb * R[v]   (R null: t' = ca * t),   T_out[v] = t' if wanted,
 //   Y[v] = act(t' * Wlin^T),  act = relu or identity.
@@ -170,6 +184,11 @@ hipError_t launch_gather_weighted(const WeightedGatherArgs &a, int nfix, int nfi
 // that a lane lies inside one head); otherwise 4-byte lanes on the single-head call's lane groups.
 hipError_t launch_gather_heads(const HeadsGatherArgs &a, int nfix, int nfix_l1, const Fixup *fixups, bool vec4, bool lane4,
                                hipStream_t stream);
+// the attention instances: launch_gather_heads' lanes and order of summation, the weights formed from a's scores and statistics
+hipError_t launch_gather_attention(const AttnGatherArgs &a, int nfix, int nfix_l1, const Fixup *fixups, bool vec4, bool lane4,
+                                   hipStream_t stream);
+// the LDS one of their workgroups asks for: the unweighted panel plus one (stat_row: three) float per row and head
+size_t attn_gather_lds_bytes(int32_t panel_rows, int32_t panel_nnz, int32_t heads, bool stat_row);
 // out[p, h] = <A[ind[p], hC .. (h+1)C), B[e, hC .. (h+1)C)>, out [nnz, H].  lane4: C % 4 == 0 and A, B 16-byte aligned.
 hipError_t launch_incidence_dot_heads(int32_t M, int64_t nnz, int32_t H, int32_t C, const int32_t *ptr, const int32_t *ind,
                                       const float *A, const float *B, float *out, bool lane4, hipStream_t stream);

@@ -132,6 +132,14 @@ template <> struct Rows<bf16, 4> {
   }
 };
 
+// The attention coefficient of one gathered entry for the lane's head (gather_rows_kernel's WA instances): the scores of
+// the row and of the entry in the order the segment softmax adds them -- the segment's own end first, taken as 0 where
+// absent; the other end absent: no addition -- then attention_weight.
+__device__ __forceinline__ float attn_weight(const AttnGatherArgs &a, float row_s, float ent_s, float seg_max, float seg_inv) {
+  return a.stat_row ? attention_weight(row_s, ent_s, a.ent_score != nullptr, a.slope, seg_max, seg_inv)
+                    : attention_weight(ent_s, row_s, a.row_score != nullptr, a.slope, seg_max, seg_inv);
+}
+
 // dst[r,:] = scaleB[r] * (scaleA[r] * sum_{p in row r} src[ind[p],:])
 //
 // Workgroups [0, n_task_blocks) run wave tasks (one long-row slice per wave, its
@@ -150,11 +158,18 @@ template <> struct Rows<bf16, 4> {
 // lies inside one head (the launcher takes VEC = 4 only where C % 4 == 0).  The weights are read where they lie, beside the
 // row they scale (4 H contiguous bytes per entry, shared by the lanes of a row); panels stage the entries' positions
 // (hop 2: perm) where the WT instances stage the weights, so the LDS does not grow with H.
-template <bool WT, bool WH>
-using GatherArgsOf = std::conditional_t<WH, HeadsGatherArgs, std::conditional_t<WT, WeightedGatherArgs, GatherArgs>>;
-template <int LPR, int VEC, typename TS = float, typename TD = float, bool WT = false, bool WH = false>
-__global__ __launch_bounds__(256) void gather_rows_kernel(const GatherArgsOf<WT, WH> a) {
-  static_assert(!(WT && WH), "per-entry or per-head weights");
+// WA: the WH walk with the weight formed in the lane (AttnGatherArgs, hg_aggr_incidence_attention_heads_f32): the
+// attention coefficient of the entry and the lane's head from the two ends' scores and the segment's statistics,
+// attention_weight (hg_attention.h) -- the bits kSegSoftmax writes, so the sums are those of the WH instance on alpha.  What
+// belongs to the destination row (its score, and the statistics where the row is the segment) is read once per row: a
+// wave task's lanes hold it in registers, a panel stages its rows' [nrows, H] slices behind sind; what belongs to the entry
+// is gathered beside the row it weighs.  No weight array, no positions, no perm.
+template <bool WT, bool WH, bool WA = false>
+using GatherArgsOf =
+    std::conditional_t<WA, AttnGatherArgs, std::conditional_t<WH, HeadsGatherArgs, std::conditional_t<WT, WeightedGatherArgs, GatherArgs>>>;
+template <int LPR, int VEC, typename TS = float, typename TD = float, bool WT = false, bool WH = false, bool WA = false>
+__global__ __launch_bounds__(256) void gather_rows_kernel(const GatherArgsOf<WT, WH, WA> a) {
+  static_assert(!(WT && WH) && !(WA && (WT || WH)), "per-entry, per-head or computed weights");
   constexpr int U = 4;           // row loads in flight per lane (8, or two batches in flight: within 3 %, profiles/r01_fused_experiments.md)
   constexpr int G = 64 / LPR;    // row groups per wave
   constexpr int NG = 256 / LPR;  // row groups per workgroup
@@ -172,7 +187,7 @@ __global__ __launch_bounds__(256) void gather_rows_kernel(const GatherArgsOf<WT,
   const int64_t F = a.F;
   int b = blockIdx.x;
   int hd = 0;  // the head of this lane's columns
-  if constexpr (WH) hd = col_ok ? col / a.C : 0;
+  if constexpr (WH || WA) hd = col_ok ? col / a.C : 0;
 
   if (b < a.n_task_blocks) {
     const int t = __builtin_amdgcn_readfirstlane(b * 4 + (tid >> 6));
@@ -180,9 +195,16 @@ __global__ __launch_bounds__(256) void gather_rows_kernel(const GatherArgsOf<WT,
     const Task tk = a.tasks[t];
     const int g = (tid & 63) / LPR;
     V acc = V::zero();
+    float rs = 0.f, rm = 0.f, ri = 0.f;  // WA: the row's score and, where the row is the segment, its statistics
+    if constexpr (WA) {
+      const int64_t rh = (int64_t)tk.row * a.heads + hd;
+      if (a.row_score) rs = a.row_score[rh];
+      if (a.stat_row) rm = a.seg_max[rh], ri = a.seg_inv[rh];
+    }
     for (int p = tk.beg + g; p < tk.end; p += G * U) {
       V v[U];
       float wv[U];
+      float es[WA ? U : 1], em[WA ? U : 1], ei[WA ? U : 1];  // WA: the entries' scores and statistics
 #pragma unroll
       for (int k = 0; k < U; k++) {
         const int q = p + k * G;
@@ -190,11 +212,21 @@ __global__ __launch_bounds__(256) void gather_rows_kernel(const GatherArgsOf<WT,
         const int64_t idx = ok ? a.ind[q] : 0;
         if constexpr (WT) wv[k] = ok ? a.w[a.wperm ? a.wperm[q] : q] : 0.f;
         if constexpr (WH) wv[k] = ok ? a.w[(int64_t)(a.wperm ? a.wperm[q] : q) * a.heads + hd] : 0.f;
+        if constexpr (WA) {
+          const int64_t eh = idx * a.heads + hd;
+          es[k] = (ok && a.ent_score) ? a.ent_score[eh] : 0.f;
+          em[k] = (ok && !a.stat_row) ? a.seg_max[eh] : rm;
+          ei[k] = (ok && !a.stat_row) ? a.seg_inv[eh] : ri;
+        }
         v[k] = ok ? RS::load(src + idx * F + col) : V::zero();
       }
 #pragma unroll
       for (int k = 0; k < U; k++) {
-        if constexpr (WT || WH) acc.fma(v[k], wv[k]);
+        if constexpr (WA) {
+          const bool ok = col_ok && p + k * G < tk.end;
+          wv[k] = ok ? attn_weight(a, rs, es[k], em[k], ei[k]) : 0.f;
+        }
+        if constexpr (WT || WH || WA) acc.fma(v[k], wv[k]);
         else acc.add(v[k]);
       }
     }
@@ -250,6 +282,22 @@ __global__ __launch_bounds__(256) void gather_rows_kernel(const GatherArgsOf<WT,
     if (a.wperm)
       for (int i = tid; i < pn.nnz_cnt; i += 256) reinterpret_cast<int32_t *>(sw)[i] = a.wperm[pn.nnz0 + i];
   }
+  // WA: the rows' scores [panel_rows, heads] and, where the rows are the segments, their statistics behind them: a panel's
+  // rows are consecutive, so each is one contiguous slice of its [rows, heads] array
+  float *srs = sw, *srm = sw, *sri = sw;
+  if constexpr (WA) {
+    srm = srs + (int64_t)a.panel_rows * a.heads;
+    sri = srm + (int64_t)a.panel_rows * a.heads;
+    const int64_t r0 = (int64_t)pn.row0 * a.heads;
+    const int nrh = pn.nrows * a.heads;
+    if (a.row_score)
+      for (int i = tid; i < nrh; i += 256) srs[i] = a.row_score[r0 + i];
+    if (a.stat_row)
+      for (int i = tid; i < nrh; i += 256) {
+        srm[i] = a.seg_max[r0 + i];
+        sri[i] = a.seg_inv[r0 + i];
+      }
+  }
   __syncthreads();
 
   const int g = tid / LPR;
@@ -276,6 +324,15 @@ __global__ __launch_bounds__(256) void gather_rows_kernel(const GatherArgsOf<WT,
   V acc = V::zero();
 
   float wv[WH ? U : 1];  // WH: the weights of the rows in flight
+  float es[WA ? U : 1], em[WA ? U : 1], ei[WA ? U : 1];  // WA: their entries' scores and statistics
+  float rs = 0.f, rm = 0.f, ri = 0.f;                    // WA: what row r itself contributes, read when r changes
+  auto load_row = [&](int row) {
+    if constexpr (WA) {
+      if (a.row_score) rs = srs[row * a.heads + hd];
+      if (a.stat_row) rm = srm[row * a.heads + hd], ri = sri[row * a.heads + hd];
+    }
+  };
+  if constexpr (WA) load_row(r);
   auto issue = [&](int p0, int n, V(&v)[U]) {
 #pragma unroll
     for (int k = 0; k < U; k++) {
@@ -283,6 +340,12 @@ __global__ __launch_bounds__(256) void gather_rows_kernel(const GatherArgsOf<WT,
       if constexpr (WH) {
         const int64_t wp = a.wperm ? swp[p0 + min(k, n - 1)] : pn.nnz0 + p0 + min(k, n - 1);
         wv[k] = col_ok ? a.w[wp * a.heads + hd] : 0.f;
+      }
+      if constexpr (WA) {
+        const int64_t eh = idx * a.heads + hd;
+        es[k] = (col_ok && a.ent_score) ? a.ent_score[eh] : 0.f;
+        em[k] = (col_ok && !a.stat_row) ? a.seg_max[eh] : 0.f;
+        ei[k] = (col_ok && !a.stat_row) ? a.seg_inv[eh] : 0.f;
       }
       v[k] = col_ok ? RS::load(src + idx * F + col) : V::zero();
     }
@@ -296,9 +359,12 @@ __global__ __launch_bounds__(256) void gather_rows_kernel(const GatherArgsOf<WT,
           acc = V::zero();
           r++;
           row_end = sptr[r + 1];
+          if constexpr (WA) load_row(r);
         }
         if constexpr (WT) acc.fma(v[k], sw[p0 + k]);
         else if constexpr (WH) acc.fma(v[k], wv[k]);
+        else if constexpr (WA)
+          acc.fma(v[k], col_ok ? attn_weight(a, rs, es[k], a.stat_row ? rm : em[k], a.stat_row ? ri : ei[k]) : 0.f);
         else acc.add(v[k]);
       }
     }
@@ -2370,18 +2436,21 @@ static hipError_t launch_fixups_t(const GatherArgs &a, int nfix, int nfix_l1, co
   return hipGetLastError();
 }
 
-// WM: 0 no weights, 1 a weight per entry (the WT instances), 2 a weight per entry and head (the WH instances)
+// WM: 0 no weights, 1 a weight per entry (the WT instances), 2 a weight per entry and head (the WH instances), 3 the
+// attention coefficient formed in the lane (the WA instances)
 template <int LPR, int VEC, typename TS = float, typename TD = float, int WM = 0>
-static hipError_t launch_gather_t(const GatherArgsOf<WM == 1, WM == 2> &a, int nfix, int nfix_l1, const Fixup *fixups,
+static hipError_t launch_gather_t(const GatherArgsOf<WM == 1, WM == 2, WM == 3> &a, int nfix, int nfix_l1, const Fixup *fixups,
                                   hipStream_t stream) {
-  constexpr bool WT = WM != 0;
+  constexpr bool WT = WM == 1 || WM == 2;
   const int col_tiles = (a.F + LPR * VEC - 1) / (LPR * VEC);
   const int nblocks = a.n_task_blocks + a.npanels;
   if (nblocks > 0) {
-    // the weighted instances stage one float (heads: one position) per index entry beside sind
-    const size_t lds = (size_t)(4 * a.panel_rows + 1 + (WT ? 2 : 1) * a.panel_nnz) * sizeof(int32_t);
+    // the weighted instances stage one float (heads: one position) per index entry beside sind; the attention instances
+    // stage nothing per entry: the unweighted layout, then the rows' scalars (attn_gather_lds_bytes)
+    size_t lds = (size_t)(4 * a.panel_rows + 1 + (WT ? 2 : 1) * a.panel_nnz) * sizeof(int32_t);
+    if constexpr (WM == 3) lds = attn_gather_lds_bytes(a.panel_rows, a.panel_nnz, a.heads, a.stat_row != 0);
     const dim3 grid(nblocks, col_tiles);
-    const hipError_t e = launch_lds<gather_rows_kernel<LPR, VEC, TS, TD, WM == 1, WM == 2>>(grid, lds, stream, a);
+    const hipError_t e = launch_lds<gather_rows_kernel<LPR, VEC, TS, TD, WM == 1, WM == 2, WM == 3>>(grid, lds, stream, a);
     if (e != hipSuccess) return e;
   }
   return launch_fixups_t<LPR, VEC, TD>(a, nfix, nfix_l1, fixups, stream);
@@ -2445,6 +2514,34 @@ hipError_t launch_gather_heads(const HeadsGatherArgs &a, int nfix, int nfix_l1, 
   case L:                                                                                           \
     return lane4 ? launch_gather_t<L, 4, float, float, 2>(a, nfix, nfix_l1, fixups, stream)         \
                  : launch_gather_t<L, 1, float, float, 2>(a, nfix, nfix_l1, fixups, stream);
+  switch (lpr) {
+    HG_CASE(1)
+    HG_CASE(2)
+    HG_CASE(4)
+    HG_CASE(8)
+    HG_CASE(16)
+    HG_CASE(32)
+    HG_CASE(64)
+  }
+#undef HG_CASE
+  return hipErrorInvalidValue;
+}
+
+size_t attn_gather_lds_bytes(int32_t panel_rows, int32_t panel_nnz, int32_t heads, bool stat_row) {
+  return ((size_t)4 * panel_rows + 1 + panel_nnz + (size_t)(stat_row ? 3 : 1) * panel_rows * heads) * sizeof(int32_t);
+}
+
+// launch_gather_heads' lane rule (lane4, lpr), so that every column is summed in the order of the WH instance on alpha
+hipError_t launch_gather_attention(const AttnGatherArgs &a, int nfix, int nfix_l1, const Fixup *fixups, bool vec4, bool lane4,
+                                   hipStream_t stream) {
+  if (!a.seg_max || !a.seg_inv || a.heads < 1 || a.C < 1 || (int64_t)a.heads * a.C != a.F || (lane4 && (!vec4 || a.C % 4)))
+    return hipErrorInvalidValue;
+  const int lanes = vec4 ? a.F / 4 : a.F;
+  const int lpr = std::min(64, next_pow2(std::max(lanes, 1)));
+#define HG_CASE(L)                                                                                  \
+  case L:                                                                                           \
+    return lane4 ? launch_gather_t<L, 4, float, float, 3>(a, nfix, nfix_l1, fixups, stream)         \
+                 : launch_gather_t<L, 1, float, float, 3>(a, nfix, nfix_l1, fixups, stream);
   switch (lpr) {
     HG_CASE(1)
     HG_CASE(2)

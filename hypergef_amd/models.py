@@ -133,11 +133,16 @@ class HypergraphAttnConv(nn.Module):
         alpha = softmax over each group of leaky_relu(logit, negative_slope)   (ops.incidence_softmax(incidence_score=)),
     and Y as above; negative_slope = 1.0 is the plain softmax of the logits.  Parameters: lin.weight, lin_k.weight, bias.
     learn_hyperedge_weight=True: the aggregation's diagonal hyperedge weight `Wdiag` (ones [M]) is one more nn.Parameter,
-    Y = degV . H_alpha (degE . Wdiag . (H_alpha^T Z)); False is the layer above, parameter for parameter."""
+    Y = degV . H_alpha (degE . Wdiag . (H_alpha^T Z)); False is the layer above, parameter for parameter.
+    fuse_attention=True: softmax and aggregation run as ops.incidence_attention_aggr -- the same output and gradient bits,
+    with no alpha [nnz, heads] written, read or kept for the backward -- where that operator applies: score = 'additive' and
+    no dropout active (dropout = 0.0, or eval()).  Elsewhere the layer takes the path above without a word.  No parameter
+    or buffer is added; False (the default) is the layer above."""
 
     def __init__(self, hyperg, in_channels, out_channels, group="hyperedge", negative_slope=0.2, options=None, heads=1,
-                 concat=True, dropout=0.0, score="additive", learn_hyperedge_weight=False):
+                 concat=True, dropout=0.0, score="additive", learn_hyperedge_weight=False, fuse_attention=False):
         super().__init__()
+        self.fuse_attention = bool(fuse_attention)
         if score not in ("additive", "dot"):
             raise ValueError("score must be 'additive' or 'dot', got %r" % (score,))
         self.score = score
@@ -178,24 +183,40 @@ class HypergraphAttnConv(nn.Module):
             return ops.incidence_softmax(ptr, ind, None, None, group=self.group, negative_slope=self.negative_slope,
                                          options=self.options, num_nodes=Z.shape[0], heads=self.heads, dropout=self.dropout,
                                          training=self.training, incidence_score=logits)
+        sv, se = self.scores(Z)
+        if self.heads == 1:
+            return ops.incidence_softmax(ptr, ind, sv, se, group=self.group, negative_slope=self.negative_slope,
+                                         options=self.options, num_nodes=Z.shape[0], dropout=self.dropout,
+                                         training=self.training)
+        return ops.incidence_softmax(ptr, ind, sv, se, group=self.group, negative_slope=self.negative_slope,
+                                     options=self.options, num_nodes=Z.shape[0], heads=self.heads, dropout=self.dropout,
+                                     training=self.training)
+
+    def scores(self, Z):
+        """score = 'additive': (sv [N] / [N, heads], se [M] / [M, heads]) for the projected features Z."""
+        ptr, ind = self.hyperg.H_T_csrptr, self.hyperg.H_T_colind
         if self.heads == 1:
             sv = Z @ self.a_v
             ze = (Z @ self.a_e)[self._members]
             se = ops.incidence_sum(ptr, ind, ze, side="hyperedge", num_nodes=Z.shape[0]) * self._inv_size
-            return ops.incidence_softmax(ptr, ind, sv, se, group=self.group, negative_slope=self.negative_slope,
-                                         options=self.options, num_nodes=Z.shape[0], dropout=self.dropout,
-                                         training=self.training)
+            return sv, se
         H, C = self.heads, self.out_channels
         Zh = Z.view(Z.shape[0], H, C)
         sv = (Zh * self.a_v.view(H, C)).sum(-1)
         ze = (Zh * self.a_e.view(H, C)).sum(-1)[self._members]
         se = ops.incidence_sum(ptr, ind, ze, side="hyperedge", num_nodes=Z.shape[0], heads=H) * self._inv_size.reshape(-1, 1)
-        return ops.incidence_softmax(ptr, ind, sv, se, group=self.group, negative_slope=self.negative_slope,
-                                     options=self.options, num_nodes=Z.shape[0], heads=H, dropout=self.dropout,
-                                     training=self.training)
+        return sv, se
 
     def forward(self, X):
         Z = self.lin(X)
+        if self.fuse_attention and self.score == "additive" and not (self.dropout > 0.0 and self.training):
+            sv, se = self.scores(Z)
+            Y = ops.incidence_attention_aggr(self.hyperg.H_T_csrptr, self.hyperg.H_T_colind, Z, sv, se, group=self.group,
+                                             negative_slope=self.negative_slope, degE=self.degE, degV=self.degV,
+                                             W=self.Wdiag, heads=self.heads, options=self.options)
+            if self.heads > 1 and not self.concat:
+                Y = Y.view(Y.shape[0], self.heads, self.out_channels).mean(1)
+            return Y + self.bias
         alpha = self.coefficients(Z, X)
         Y = ops.incidence_aggr(self.hyperg.H_T_csrptr, self.hyperg.H_T_colind, Z, alpha, alpha, self.degE, self.degV,
                                self.Wdiag, options=self.options, heads=self.heads)

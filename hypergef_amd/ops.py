@@ -870,6 +870,126 @@ def _softmax_entry(csrptr_t, indices_t, sv, se, t, N, group, slope, heads, p_dro
     return plan.incidence_attention(csrptr_t, indices_t, sv, se, group, slope, heads=heads, entry=t), None
 
 
+# ---- fused attention aggregation (include/hg_aggr.h, hg_aggr_incidence_attention_heads_f32) -------------------------------
+
+class _IncidenceAttentionAggr(torch.autograd.Function):
+    """incidence_aggr(X, alpha, alpha) on alpha = incidence_softmax(sv, se) as one node that never holds alpha between
+    forward and backward.  The forward keeps X, the scores, the two statistics per segment and head and the scales; the
+    backward forms alpha from the same scores with the softmax kernel (the bits the gather used), runs _IncidenceAggr's
+    formulas with v2e = e2v = alpha -- hop 1's table Xe is gathered again for de2v -- and hands dalpha = dv2e + de2v to
+    the softmax's backward.  Exact gradients for X, both scores and, where they require one, degE / degV / W."""
+
+    @staticmethod
+    def forward(ctx, csrptr_t, indices_t, node_feat, sv, se, degE, degV, W, group, slope, heads):
+        plan = cached_plan(node_feat.shape[0], csrptr_t, indices_t)
+        seg_max, seg_inv = plan.incidence_attention_stats(csrptr_t, indices_t, sv, se, group, slope, heads=heads)
+        out = plan.aggregate_incidence_attention(csrptr_t, indices_t, node_feat, sv, se, group, slope, seg_max, seg_inv,
+                                                 degE, degV, W, heads=heads)
+        need_score = any(t is not None and ctx.needs_input_grad[i] for i, t in ((3, sv), (4, se)))
+        need_scale = any(t is not None and ctx.needs_input_grad[i] for i, t in ((5, degE), (6, degV), (7, W)))
+        ctx.save_for_backward(csrptr_t, indices_t, node_feat if need_score or need_scale else None, sv, se, seg_max, seg_inv,
+                              degE, degV, W)
+        ctx.group, ctx.slope, ctx.heads = group, slope, heads
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        csrptr_t, indices_t, X, sv, se, seg_max, seg_inv, degE, degV, W = ctx.saved_tensors
+        g = grad_out.contiguous()
+        N, F = g.shape
+        M = csrptr_t.numel() - 1
+        heads = ctx.heads
+        plan = cached_plan(N, csrptr_t, indices_t)
+        P = g if degV is None else g * degV.reshape(-1, 1)
+        need_x = ctx.needs_input_grad[2]
+        need_sv = sv is not None and ctx.needs_input_grad[3]
+        need_se = se is not None and ctx.needs_input_grad[4]
+        need_dE, need_dV, need_dW = (t is not None and ctx.needs_input_grad[i] for i, t in ((5, degE), (6, degV), (7, W)))
+        need_score = need_sv or need_se
+        gx = dsv = dse = gE = gV = gW = None
+        if not (need_score or need_dE or need_dV or need_dW):  # dX alone: the adjoint is the fused call itself
+            gx = plan.aggregate_incidence_attention(csrptr_t, indices_t, P, sv, se, ctx.group, ctx.slope, seg_max, seg_inv,
+                                                    degE, None, W, heads=heads)
+            return None, None, gx if need_x else None, None, None, None, None, None, None, None, None
+        alpha = plan.incidence_attention(csrptr_t, indices_t, sv, se, ctx.group, ctx.slope, heads=heads)
+        if need_x or need_score:
+            G = torch.empty((M, F), dtype=torch.float32, device=g.device) if need_score else None
+            gx = plan.aggregate_incidence(csrptr_t, indices_t, P, alpha, alpha, degE, None, W, xe_out=G, heads=heads)
+        if need_score:
+            dalpha = plan.incidence_dot(csrptr_t, indices_t, X, G, heads=heads)
+            Xe = plan.gather_rows_incidence(0, csrptr_t, indices_t, X, alpha, degE, W, heads=heads)
+            dalpha += plan.incidence_dot(csrptr_t, indices_t, P, Xe, heads=heads)  # dv2e + de2v, as autograd would add them
+            del G, Xe
+            _, dsv, dse = plan.incidence_attention_backward(csrptr_t, indices_t, alpha, dalpha, sv, se, ctx.group, ctx.slope,
+                                                            need_sv=need_sv, need_se=need_se, heads=heads)
+        if need_dE or need_dW:
+            q = plan.hyperedge_dot(csrptr_t, indices_t, X, P, alpha, alpha, heads=heads)
+            gE, gW = _edge_scale_grads(plan, csrptr_t, q, degE, W, need_dE, need_dW)
+        if need_dV:
+            Z = plan.aggregate_incidence(csrptr_t, indices_t, X, alpha, alpha, degE, None, W, heads=heads)
+            gV = plan.rows_dot(g, Z)
+        return None, None, gx if need_x else None, dsv, dse, gE, gV, gW, None, None, None
+
+
+def incidence_attention_aggr(csrptr_t, indices_t, node_feat, node_score, edge_score, group="hyperedge", negative_slope=0.2,
+                             degE=None, degV=None, W=None, heads=1, num_nodes=None, options=None):
+    """Hypergraph attention's aggregation in one call: what
+        alpha = incidence_softmax(csrptr_t, indices_t, node_score, edge_score, group=group, negative_slope=negative_slope,
+                                  heads=heads, num_nodes=N)
+        Y = incidence_aggr(csrptr_t, indices_t, node_feat, alpha, alpha, degE, degV, W, heads=heads)
+    returns, bit for bit, without alpha [nnz, heads] ever existing: a segment kernel writes the softmax's maximum and
+    reciprocal sum per group and head (two [M, heads] or [N, heads] arrays), and each lane of the two row gathers forms its
+    coefficient from the two scores and those two numbers as it gathers the row (hg_aggr_incidence_attention_heads_f32).
+    The plan's incidence permutation is not used.  node_score [N] / [N, heads], edge_score [M] / [M, heads]: float32,
+    either may be None (0).  Gradients are exact for node_feat, both scores and, where they require one, degE / degV / W;
+    nothing of nnz * heads elements is kept from forward to backward (the backward forms alpha again, and frees it).
+    num_nodes: optional, must equal node_feat's row count.  Options.variant 'auto' and 'pull' run; the others raise
+    ValueError.  float32 only (TypeError for bfloat16).  Not covered, use the two calls above: attention dropout, a logit
+    per incidence (incidence_score is itself an [nnz, heads] array), bfloat16."""
+    opt = _opt(options)
+    if opt.variant not in ("auto", "pull"):
+        raise ValueError("incidence_attention_aggr runs the pull kernels: variant must be 'auto' or 'pull', got %r"
+                         % opt.variant)
+    _heads(heads)
+    if group not in _GROUPS:
+        raise ValueError("group / side must be 'hyperedge' or 'vertex', got %r" % (group,))
+    if heads == 1:
+        sv, se = (_flat(x) if isinstance(x, torch.Tensor) else x for x in (node_score, edge_score))
+    else:
+        sv, se = (_per_head(x, heads) if isinstance(x, torch.Tensor) else x for x in (node_score, edge_score))
+    floats = (("node_feat", node_feat), ("node_score", sv), ("edge_score", se))
+    for name, t in floats:
+        if (t is not None or name == "node_feat") and (not isinstance(t, torch.Tensor) or t.dtype != torch.float32):
+            raise TypeError("%s must be a float32 tensor (incidence_attention_aggr has no bfloat16 form), got %s"
+                            % (name, getattr(t, "dtype", type(t))))
+    if node_feat.dim() != 2:
+        raise ValueError("node_feat must be [N, F]")
+    N, F = node_feat.shape
+    if F % heads:
+        raise ValueError("node_feat's width %d is no multiple of heads = %d" % (F, heads))
+    if num_nodes is not None and int(num_nodes) != N:
+        raise ValueError("num_nodes = %d, but node_feat has %d rows" % (int(num_nodes), N))
+    if not isinstance(csrptr_t, torch.Tensor) or not isinstance(indices_t, torch.Tensor):
+        raise TypeError("csrptr_t and indices_t must be int32 tensors")
+    M = csrptr_t.numel() - 1
+    for (name, t), n in zip(floats[1:], (N * heads, M * heads)):
+        if t is not None and t.numel() != n:
+            raise ValueError("%s must have %d elements, got %d" % (name, n, t.numel()))
+    _check_index(csrptr_t, "csrptr_t")
+    _check_index(indices_t, "indices_t")
+    _check_feat(node_feat, "node_feat")
+    for name, t in floats[1:]:
+        if t is not None:
+            _check_feat(t, name, device=node_feat.device)
+    degE, degV, W = _flat(degE), _flat(degV), _flat(W)
+    slope = float(negative_slope)
+    if not (torch.is_grad_enabled() and _any_requires_grad(node_feat, sv, se, degE, degV, W)):
+        plan = cached_plan(N, csrptr_t, indices_t)
+        return plan.aggregate_incidence_attention(csrptr_t, indices_t, node_feat, sv, se, group, slope, None, None,
+                                                  degE, degV, W, heads=heads)
+    return _IncidenceAttentionAggr.apply(csrptr_t, indices_t, node_feat, sv, se, degE, degV, W, group, slope, heads)
+
+
 # ---- one weighted hop and the dot product per incidence (hg_gather_rows_incidence_heads_f32, hg_incidence_dot_heads_f32) ----
 
 _HOPS = ("hyperedge", "vertex")

@@ -814,6 +814,116 @@ class Plan:
                     _ptr(dalpha), _ptr(ds), _ptr(dsv), _ptr(dse), _stream_handle(device)))
         return ds, dsv, dse
 
+    def incidence_attention_stats(self, csrptr_t, colind_t, sv=None, se=None, group="hyperedge", slope=0.2, heads=1,
+                                  out=None):
+        """(seg_max, seg_inv) of incidence_attention's softmax, one pair per segment and head: the maximum of
+        leaky_relu(sv[u] + se[e], slope) over the segment and the reciprocal of its sum of exponentials, float32 [M] /
+        [M, H] for group 'hyperedge', [N] / [N, H] for 'vertex'; (0, 0) for an empty segment
+        (hg_incidence_attention_stats_heads_f32).  alpha[p] = exp(leaky(raw[p]) - seg_max[g]) * seg_inv[g] has
+        incidence_attention's bits; aggregate_incidence_attention forms it in the gather.  out: a pair of such tensors.
+        The first call on a side uploads the long-row list the segment kernels share: not capturable."""
+        heads = _heads(heads)
+        group = _side(group)
+        _check_index(csrptr_t, "csrptr_t")
+        _check_index(colind_t, "indices_t")
+        device = self._scores(sv, se, csrptr_t.device, heads)
+        nseg = self.M if group == 0 else self.N
+        if out is None:
+            out = tuple(torch.empty(_per_head(nseg, heads), dtype=torch.float32, device=device) for _ in range(2))
+        else:
+            for t in out:
+                _check_feat(t, "out", device=device)
+                if t.numel() != nseg * heads:
+                    raise ValueError("out must be two tensors of %d elements" % (nseg * heads))
+        seg_max, seg_inv = out
+        with torch.cuda.device(device):
+            _lib.check(_lib.lib().hg_incidence_attention_stats_heads_f32(
+                self._h, group, heads, _ptr(csrptr_t), _ptr(colind_t), _ptr(sv), _ptr(se), float(slope), _ptr(seg_max),
+                _ptr(seg_inv), _stream_handle(device)))
+        return seg_max, seg_inv
+
+    def _attention_args(self, X, nrows, sv, se, seg_max, seg_inv, group, heads):
+        _check_feat(X, "node_feat")
+        if X.dim() != 2 or X.shape[0] != nrows:
+            raise ValueError("the feature rows must be [%d, F]" % nrows)
+        F = X.shape[1]
+        if F % heads:
+            raise ValueError("F = %d is no multiple of heads = %d" % (F, heads))
+        self._scores(sv, se, X.device, heads)
+        nseg = self.M if group == 0 else self.N
+        for name, t in (("seg_max", seg_max), ("seg_inv", seg_inv)):
+            _check_feat(t, name, device=X.device)
+            if t.numel() != nseg * heads:
+                raise ValueError("%s must have %d elements, got %d" % (name, nseg * heads, t.numel()))
+        return F
+
+    def aggregate_incidence_attention(self, csrptr_t, colind_t, X, sv=None, se=None, group="hyperedge", slope=0.2,
+                                      seg_max=None, seg_inv=None, degE=None, degV=None, W=None, xe_out=None, out=None,
+                                      workspace=None, heads=1):
+        """aggregate_incidence(X, alpha, alpha, degE, degV, W) for alpha = incidence_attention(sv, se, group, slope), bit
+        for bit, without alpha: each gathering lane forms its coefficient from the two scores and the segment's
+        statistics (hg_aggr_incidence_attention_heads_f32).  seg_max / seg_inv: incidence_attention_stats' pair for the
+        same scores; None computes them here.  No [nnz, H] array exists and the plan's permutation is not used."""
+        heads = _heads(heads)
+        group = _side(group)
+        if seg_max is None or seg_inv is None:
+            seg_max, seg_inv = self.incidence_attention_stats(csrptr_t, colind_t, sv, se, group, slope, heads=heads)
+        F = self._attention_args(X, self.N, sv, se, seg_max, seg_inv, group, heads)
+        for name, t, n in (("degE", degE, self.M), ("degV", degV, self.N), ("W", W, self.M)):
+            if t is not None:
+                _check_feat(t, name, device=X.device)
+                if t.numel() != n:
+                    raise ValueError("%s must have %d elements, got %d" % (name, n, t.numel()))
+        for name, t, rows in (("xe_out", xe_out, self.M), ("out", out, self.N)):
+            if t is not None:
+                _check_feat(t, name, device=X.device)
+                if tuple(t.shape) != (rows, F):
+                    raise ValueError("%s must be [%d, %d]" % (name, rows, F))
+        Y = out if out is not None else torch.empty((self.N, F), dtype=torch.float32, device=X.device)
+        nbytes = self.incidence_workspace_bytes(F)
+        if workspace is None:
+            workspace = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=X.device)
+        else:
+            nbytes = workspace.numel() * workspace.element_size()
+        with torch.cuda.device(X.device):
+            _lib.check(_lib.lib().hg_aggr_incidence_attention_heads_f32(
+                self._h, F, heads, group, _ptr(csrptr_t), _ptr(colind_t), _ptr(X), _ptr(sv), _ptr(se), float(slope),
+                _ptr(seg_max), _ptr(seg_inv), _ptr(degE), _ptr(degV), _ptr(W), _ptr(xe_out), _ptr(Y), _ptr(workspace),
+                nbytes, _stream_handle(X.device)))
+        return Y
+
+    def gather_rows_attention(self, hop, csrptr_t, colind_t, src, seg_max, seg_inv, sv=None, se=None, group="hyperedge",
+                              slope=0.2, scaleA=None, scaleB=None, heads=1, out=None, workspace=None):
+        """One hop of aggregate_incidence_attention as a call of its own (hg_gather_rows_attention_heads_f32), as
+        gather_rows_incidence is of aggregate_incidence: hop 0 / 'hyperedge' with (degE, W) into hop 1 / 'vertex' with
+        (degV, None) gives the two-hop call's bits."""
+        heads = _heads(heads)
+        hop = _side(hop)
+        group = _side(group)
+        nsrc, ndst = (self.N, self.M) if hop == 0 else (self.M, self.N)
+        F = self._attention_args(src, nsrc, sv, se, seg_max, seg_inv, group, heads)
+        for name, t in (("scaleA", scaleA), ("scaleB", scaleB)):
+            if t is not None:
+                _check_feat(t, name, device=src.device)
+                if t.numel() != ndst:
+                    raise ValueError("%s must have %d elements, got %d" % (name, ndst, t.numel()))
+        if out is not None:
+            _check_feat(out, "out", device=src.device)
+            if tuple(out.shape) != (ndst, F):
+                raise ValueError("out must be [%d, %d]" % (ndst, F))
+        dst = out if out is not None else torch.empty((ndst, F), dtype=torch.float32, device=src.device)
+        nbytes = self.incidence_workspace_bytes(F)
+        if workspace is None:
+            workspace = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=src.device)
+        else:
+            nbytes = workspace.numel() * workspace.element_size()
+        with torch.cuda.device(src.device):
+            _lib.check(_lib.lib().hg_gather_rows_attention_heads_f32(
+                self._h, hop, group, F, heads, _ptr(csrptr_t), _ptr(colind_t), _ptr(src), _ptr(sv), _ptr(se), float(slope),
+                _ptr(seg_max), _ptr(seg_inv), _ptr(scaleA), _ptr(scaleB), _ptr(dst), _ptr(workspace), nbytes,
+                _stream_handle(src.device)))
+        return dst
+
     def _rng_ptr(self, rng_state, device):
         _rng_state_dtype(rng_state)
         _rng_state_length(rng_state)

@@ -641,6 +641,49 @@ HG_API int hg_gather_rows_incidence_heads_f32(const hg_plan *plan, int32_t hop, 
                                               const float *w, const float *scaleA, const float *scaleB, float *dst,
                                               void *workspace, size_t workspace_bytes, hg_stream_t stream);
 
+/* ---- fused attention aggregation: the coefficients formed inside the gather -------------------------------------------------
+ * hg_incidence_attention_heads_f32 into hg_aggr_incidence_heads_f32(v2e = e2v = alpha) writes alpha [nnz, heads] once and
+ * reads it twice, the second time through the plan's permutation.  Every value of it is a function of four small numbers:
+ *     alpha[p = (e, u), h] = exp(leaky(sv[u, h] + se[e, h]) - seg_max[g, h]) * seg_inv[g, h]      g = e (group 0) or u (group 1)
+ * These entries keep the two per-segment numbers instead and form alpha in the lane that gathers the row it weighs.
+ * hg_incidence_attention_stats_heads_f32: the maximum and sum passes of hg_incidence_attention_heads_f32 -- the same lane
+ *   groups, workgroup path for rows above 128 entries and order of reduction -- writing seg_max = m and seg_inv = 1 / sum
+ *   per segment and head: [M, heads] for group 0, [N, heads] for group 1, head fastest, fully overwritten, (0, 0) for an
+ *   empty segment.  sv / se may be NULL (0).  It reads no permutation, with either group.
+ * hg_aggr_incidence_attention_heads_f32: Y = hg_aggr_incidence_heads_f32(X, alpha, alpha, degE, degV, W) for the alpha of
+ *   (group, sv, se, slope), bit for bit, Xe_out included, from seg_max / seg_inv of the stats entry.  Both hops run
+ *   hg_aggr_incidence_heads_f32's schedules (a pinned latency schedule included), lanes and streaming-store choice on
+ *   instances of the row gather that form w with the softmax kernel's own arithmetic.  What belongs to the destination row
+ *   (its score; the statistics where the row is the segment) is read once per row; what belongs to the entry is gathered
+ *   beside its row:
+ *       hop 0, group 0: row se[e], seg_*[e]; entry sv[u]            hop 1, group 0: row sv[v]; entry se[e], seg_*[e]
+ *       hop 0, group 1: row se[e]; entry sv[u], seg_*[u]            hop 1, group 1: row sv[v], seg_*[v]; entry se[e]
+ *   No weights are staged and no permutation is read or uploaded; a panel's LDS is the unweighted one plus up to three
+ *   floats per row and head.  workspace: hg_aggr_incidence_workspace_bytes(plan, F).
+ * hg_gather_rows_attention_heads_f32: one hop of it as an entry of its own, as hg_gather_rows_incidence_heads_f32 is of
+ *   hg_aggr_incidence_heads_f32: hop 0 with (degE, W) into hop 1 with (degV, NULL) gives the two-hop entry's bits.
+ * Refusals, nothing launched, in this order: HG_ERR_INVALID for a null plan, hop outside 0 / 1, group outside 0 / 1,
+ *   heads < 1, F < 1 or F % heads != 0, a null array (sv and se may both be NULL, seg_max / seg_inv may not), a non-finite
+ *   slope; HG_ERR_WORKSPACE; HG_ERR_UNSUPPORTED for a plan built with HG_PLAN_HOST_ONLY, and where panel_rows * heads
+ *   leaves no room in the 160 KiB of LDS.  The first stats call on a side uploads the long-row list the segment entries
+ *   share (not capturable; one warm call makes every later one capturable); the two gather entries allocate nothing.
+ * Not covered: dropout, a logit per incidence (entry_score is itself an [nnz, heads] stream) and bf16 rows.
+ * Detect these entries by their exported symbols (HG_AGGR_VERSION does not change). */
+HG_API int hg_incidence_attention_stats_heads_f32(const hg_plan *plan, int32_t group, int32_t heads, const int32_t *csrptr_t,
+                                                  const int32_t *colind_t, const float *sv, const float *se, float slope,
+                                                  float *seg_max_out, float *seg_inv_out, hg_stream_t stream);
+HG_API int hg_aggr_incidence_attention_heads_f32(const hg_plan *plan, int32_t F, int32_t heads, int32_t group,
+                                                 const int32_t *csrptr_t, const int32_t *colind_t, const float *X,
+                                                 const float *sv, const float *se, float slope, const float *seg_max,
+                                                 const float *seg_inv, const float *degE, const float *degV, const float *W,
+                                                 float *Xe_out, float *Y, void *workspace, size_t workspace_bytes,
+                                                 hg_stream_t stream);
+HG_API int hg_gather_rows_attention_heads_f32(const hg_plan *plan, int32_t hop, int32_t group, int32_t F, int32_t heads,
+                                              const int32_t *csrptr_t, const int32_t *colind_t, const float *src,
+                                              const float *sv, const float *se, float slope, const float *seg_max,
+                                              const float *seg_inv, const float *scaleA, const float *scaleB, float *dst,
+                                              void *workspace, size_t workspace_bytes, hg_stream_t stream);
+
 /* ---- gradients of the scales degE, W (one factor per hyperedge) and degV (one per vertex) ---------------------------------
  * For Y = degV . H_e2v (degE . W . (H_v2e^T X)) and its gradient dY, with P[v] = degV[v] * dY[v]:
  *     q[e] = < sum_{p=(e,u)} v2e[p] X[u],  sum_{p=(e,v)} e2v[p] P[v] >        dW[e] = q[e] * degE[e],  ddegE[e] = q[e] * W[e]
