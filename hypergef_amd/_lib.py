@@ -49,7 +49,12 @@ SYMBOLS = (
     "hg_hyperedge_dot_heads_f32", "hg_rows_dot_f32",
     "hg_incidence_attention_stats_heads_f32", "hg_aggr_incidence_attention_heads_f32",
     "hg_gather_rows_attention_heads_f32",
+    "hg_gather_rows_incidence_heads_bf16", "hg_aggr_incidence_heads_bf16", "hg_incidence_dot_heads_bf16",
 )
+HG_ROWS_SRC_BF16 = 1
+HG_ROWS_DST_BF16 = 2
+HG_DOT_A_BF16 = 1
+HG_DOT_B_BF16 = 2
 
 
 class HgError(RuntimeError):
@@ -269,6 +274,13 @@ def lib():
         L.hg_gather_rows_attention_heads_f32.restype = ctypes.c_int
         L.hg_gather_rows_attention_heads_f32.argtypes = [vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, ctypes.c_float, vp, vp,
                                                          vp, vp, vp, vp, sz, vp]
+    if hasattr(L, "hg_aggr_incidence_heads_bf16"):  # likewise: bf16 feature rows on the incidence path (+ an int32 io mask)
+        L.hg_gather_rows_incidence_heads_bf16.restype = ctypes.c_int
+        L.hg_gather_rows_incidence_heads_bf16.argtypes = [vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, sz, i32, vp]
+        L.hg_aggr_incidence_heads_bf16.restype = ctypes.c_int
+        L.hg_aggr_incidence_heads_bf16.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]
+        L.hg_incidence_dot_heads_bf16.restype = ctypes.c_int
+        L.hg_incidence_dot_heads_bf16.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, i32, vp]
     L.hg_aggr_push_groups_f32.restype = ctypes.c_int
     L.hg_aggr_push_groups_f32.argtypes = [i32, i32, i32, i64, vp, vp, vp, vp, vp, vp,
                                           vp, vp, vp, vp, vp, vp]

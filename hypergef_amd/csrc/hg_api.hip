@@ -6,6 +6,7 @@
 #include <cstdio>
 #include <cstring>
 #include <algorithm>
+#include <initializer_list>
 #include <new>
 #include <string>
 
@@ -429,7 +430,7 @@ int pick_variant_uncached(const hg_plan *plan, int32_t F, bool vec4, int32_t *va
   return HG_OK;
 }
 
-// src_bf16 / dst_bf16: rows of src / dst are bf16 (at most one of them; they take 16-byte lanes only)
+// src_bf16 / dst_bf16: rows of src / dst are bf16 (either or both; they take 16-byte lanes only)
 int run_sched(const hg_plan *p, const hg::Sched &s, int32_t F, const int32_t *ptr,
               const int32_t *ind, const void *src, const float *scaleA, const float *scaleB,
               const int32_t *scale_map, const int32_t *dst_map, void *dst, float *partial,
@@ -461,7 +462,8 @@ int run_sched(const hg_plan *p, const hg::Sched &s, int32_t F, const int32_t *pt
   a.panel_nnz = p->opts.panel_nnz;
   a.xcd_remap = (p->opts.flags & HG_PLAN_NO_XCD_REMAP) ? 0 : 1;
   const bool vec4 = (F % 4 == 0) && aligned_lane(src, src_bf16) && aligned_lane(dst, dst_bf16) && aligned16(partial);
-  if ((w || attn) && (src_bf16 || dst_bf16)) {
+  // weighted bf16 rows (hg_gather_rows_incidence_heads_bf16): whole 16-byte lanes inside one head; the attention instances are fp32
+  if ((w || attn) && (src_bf16 || dst_bf16) && (attn || !vec4 || a.C % 4 != 0)) {
     hg::set_error("weighted row gather: fp32 rows only");
     return HG_ERR_UNSUPPORTED;
   }
@@ -476,8 +478,9 @@ int run_sched(const hg_plan *p, const hg::Sched &s, int32_t F, const int32_t *pt
     return HG_OK;
   }
   hipError_t e = (w && heads > 1)
-                     ? hg::launch_gather_heads(a, (int)s.fixups.size(), s.n_fix_l1, s.d_fixups, vec4, vec4 && a.C % 4 == 0, stream)
-                 : w ? hg::launch_gather_weighted(a, (int)s.fixups.size(), s.n_fix_l1, s.d_fixups, vec4, stream)
+                     ? hg::launch_gather_heads(a, (int)s.fixups.size(), s.n_fix_l1, s.d_fixups, vec4, vec4 && a.C % 4 == 0, stream,
+                                               src_bf16, dst_bf16)
+                 : w ? hg::launch_gather_weighted(a, (int)s.fixups.size(), s.n_fix_l1, s.d_fixups, vec4, stream, src_bf16, dst_bf16)
                      : hg::launch_gather(a, (int)s.fixups.size(), s.n_fix_l1, s.d_fixups, vec4, stream, src_bf16, dst_bf16);
   if (e != hipSuccess) return hip_fail("gather_rows launch", e);
   return HG_OK;
@@ -1900,9 +1903,9 @@ int hg_aggr_linear_res_bf16(const hg_plan *plan, int32_t F_in, int32_t F_out, co
 // ---- incidence-weighted aggregation ---------------------------------------------------------------------------------
 
 static int aggr_incidence(const hg_plan *plan, int32_t F, int32_t heads, const int32_t *csrptr_t, const int32_t *colind_t,
-                          const float *X, const float *v2e_val, const float *e2v_val, const float *degE,
-                          const float *degV, const float *W, float *Xe_out, float *Y, void *workspace,
-                          size_t workspace_bytes, hg_stream_t stream);
+                          const void *X, const float *v2e_val, const float *e2v_val, const float *degE,
+                          const float *degV, const float *W, float *Xe_out, void *Y, void *workspace,
+                          size_t workspace_bytes, hg_stream_t stream, bool bf16 = false);
 
 // what the weighted gather_rows_kernel stages per workgroup beside the panel must fit the CU's 160 KiB of LDS
 static bool weights_fit_lds(const hg_plan *plan) {
@@ -1912,9 +1915,11 @@ static bool weights_fit_lds(const hg_plan *plan) {
 // One hop of the incidence-weighted aggregation, shared by hg_aggr_incidence*_f32 (both hops) and
 // hg_gather_rows_incidence_heads_f32 (one): hop 0 walks H_T, dst[e] = ((sum_{p=(e,u)} w[p] src[u]) * scaleA[e]) * scaleB[e];
 // hop 1 walks H and reads w through the plan's permutation.  w null: the unweighted instances on the same schedule.
+// src_bf16 / dst_bf16: rows of src / dst are bf16 (the _bf16 entries, which have checked widths and alignment): the same
+// schedule, lanes and order, fp32 partial rows, one rounding into a bf16 dst.
 static int incidence_hop(const hg_plan *plan, int hop, int32_t F, int32_t heads, const int32_t *csrptr_t,
-                         const int32_t *colind_t, const float *src, const float *w, const float *scaleA, const float *scaleB,
-                         float *dst, char *ws, const Carve &c, hipStream_t s) {
+                         const int32_t *colind_t, const void *src, const float *w, const float *scaleA, const float *scaleB,
+                         void *dst, char *ws, const Carve &c, hipStream_t s, bool src_bf16 = false, bool dst_bf16 = false) {
   int rc;
   const int32_t *perm = nullptr;
   if (hop == 1 && w && (rc = get_incidence_perm(plan, true, &perm)) != HG_OK) return rc;
@@ -1928,10 +1933,10 @@ static int incidence_hop(const hg_plan *plan, int hop, int32_t F, int32_t heads,
     if (it != mp->hop_kernel.end()) kind = hop == 0 ? it->second % 3 : (it->second / 3) % 3;
   }
   const hg::Sched &sc = (kind == 2 && plan->has_lat) ? plan->sched_lat[hop] : plan->sched[hop];
-  // streaming stores as run_hop decides them
-  const bool nt = rows_whole_64(dst, F) && (hop == 1 || (int64_t)plan->M * F * 4 >= ((int64_t)192 << 20));
+  // streaming stores as run_hop decides them (on the bytes of dst's rows; the choice moves no bits)
+  const bool nt = rows_whole_64(dst, F, dst_bf16) && (hop == 1 || (int64_t)plan->M * F * 4 >= ((int64_t)192 << 20));
   return run_sched(plan, sc, F, hop == 0 ? csrptr_t : plan->d_ptr_v, hop == 0 ? colind_t : plan->d_ind_v, src, scaleA, scaleB,
-                   nullptr, nullptr, dst, reinterpret_cast<float *>(ws + c.part[hop]), s, nt, false, false, w, perm, heads);
+                   nullptr, nullptr, dst, reinterpret_cast<float *>(ws + c.part[hop]), s, nt, src_bf16, dst_bf16, w, perm, heads);
 }
 
 size_t hg_aggr_incidence_workspace_bytes(const hg_plan *p, int32_t F) {
@@ -1957,21 +1962,41 @@ int hg_aggr_incidence_heads_f32(const hg_plan *plan, int32_t F, int32_t heads, c
                         workspace_bytes, stream);
 }
 
-// heads == 1: hg_aggr_incidence_f32 as it always was; heads > 1: v2e_val / e2v_val are [nnz, heads]
+// What the _bf16 entries of the incidence path add to their fp32 twins' checks, after those: bf16 rows lie on 16-byte
+// lanes only -- whole four-column lanes inside one head, bf16 arrays 8-byte aligned, fp32 row arrays 16-byte aligned (so
+// that the fp32 twin takes the same lanes).  rows: (array or null, is bf16) pairs.
+static int check_rows_bf16(const char *who, int32_t F, int32_t heads,
+                           std::initializer_list<std::pair<const void *, bool>> rows) {
+  if (F % 4 != 0 || (F / heads) % 4 != 0) {
+    hg::set_error(std::string(who) + ": bf16 rows need F % 4 == 0 and C = F / heads with C % 4 == 0 (widen, call the fp32 entry, round)");
+    return HG_ERR_UNSUPPORTED;
+  }
+  for (const auto &r : rows)
+    if (r.first && !aligned_lane(r.first, r.second)) {
+      hg::set_error(std::string(who) + ": bf16 row arrays must be 8-byte aligned, fp32 row arrays 16-byte aligned");
+      return HG_ERR_UNSUPPORTED;
+    }
+  return HG_OK;
+}
+
+// heads == 1: hg_aggr_incidence_f32 as it always was; heads > 1: v2e_val / e2v_val are [nnz, heads].  bf16
+// (hg_aggr_incidence_heads_bf16): rows of X and Y are bf16, hop 1's table stays fp32.
 static int aggr_incidence(const hg_plan *plan, int32_t F, int32_t heads, const int32_t *csrptr_t, const int32_t *colind_t,
-                          const float *X, const float *v2e_val, const float *e2v_val, const float *degE,
-                          const float *degV, const float *W, float *Xe_out, float *Y, void *workspace,
-                          size_t workspace_bytes, hg_stream_t stream) {
+                          const void *X, const float *v2e_val, const float *e2v_val, const float *degE,
+                          const float *degV, const float *W, float *Xe_out, void *Y, void *workspace,
+                          size_t workspace_bytes, hg_stream_t stream, bool bf16) {
+  const std::string who = bf16 ? "hg_aggr_incidence_heads_bf16" : "hg_aggr_incidence_f32";
   int rc = check_call(plan, F, workspace, workspace_bytes, kSizePull);
   if (rc != HG_OK) return rc;
   if (!csrptr_t || (plan->nnz > 0 && !colind_t) || !X || !Y) {
-    hg::set_error("hg_aggr_incidence_f32: null array");
+    hg::set_error(who + ": null array");
     return HG_ERR_INVALID;
   }
   if ((v2e_val || e2v_val) && !weights_fit_lds(plan)) {
-    hg::set_error("hg_aggr_incidence_f32: panel_rows / panel_nnz leave no LDS for the staged weights (160 KiB per workgroup)");
+    hg::set_error(who + ": panel_rows / panel_nnz leave no LDS for the staged weights (160 KiB per workgroup)");
     return HG_ERR_UNSUPPORTED;
   }
+  if (bf16 && (rc = check_rows_bf16(who.c_str(), F, heads, {{X, true}, {Y, true}, {Xe_out, false}})) != HG_OK) return rc;
   // the permutation hop 2 will ask for: a failed upload is reported before hop 1 is launched
   if (e2v_val && (rc = get_incidence_perm(plan, true, nullptr)) != HG_OK) return rc;
   hipStream_t s = static_cast<hipStream_t>(stream);
@@ -1979,17 +2004,27 @@ static int aggr_incidence(const hg_plan *plan, int32_t F, int32_t heads, const i
   char *ws = static_cast<char *>(workspace);
   float *Xe = Xe_out ? Xe_out : reinterpret_cast<float *>(ws + c.xe);
   // hop 1: Xe[e] = ((sum_{p=(e,u)} v2e[p] X[u]) * degE[e]) * W[e]
-  rc = incidence_hop(plan, 0, F, heads, csrptr_t, colind_t, X, v2e_val, degE, W, Xe, ws, c, s);
+  rc = incidence_hop(plan, 0, F, heads, csrptr_t, colind_t, X, v2e_val, degE, W, Xe, ws, c, s, bf16, false);
   if (rc != HG_OK) return rc;
   // hop 2: Y[v] = (sum_{q=(v,e)} e2v[perm[q]] Xe[e]) * degV[v]
-  return incidence_hop(plan, 1, F, heads, csrptr_t, colind_t, Xe, e2v_val, degV, nullptr, Y, ws, c, s);
+  return incidence_hop(plan, 1, F, heads, csrptr_t, colind_t, Xe, e2v_val, degV, nullptr, Y, ws, c, s, false, bf16);
 }
 
-int hg_gather_rows_incidence_heads_f32(const hg_plan *plan, int32_t hop, int32_t F, int32_t heads, const int32_t *csrptr_t,
-                                       const int32_t *colind_t, const float *src, const float *w, const float *scaleA,
-                                       const float *scaleB, float *dst, void *workspace, size_t workspace_bytes,
-                                       hg_stream_t stream) {
-  const char *who = "hg_gather_rows_incidence_heads_f32";
+int hg_aggr_incidence_heads_bf16(const hg_plan *plan, int32_t F, int32_t heads, const int32_t *csrptr_t,
+                                 const int32_t *colind_t, const uint16_t *X, const float *v2e_val, const float *e2v_val,
+                                 const float *degE, const float *degV, const float *W, float *Xe_out, uint16_t *Y,
+                                 void *workspace, size_t workspace_bytes, hg_stream_t stream) {
+  int rc = check_heads("hg_aggr_incidence_heads_bf16", plan, heads, F);
+  if (rc != HG_OK) return rc;
+  return aggr_incidence(plan, F, heads, csrptr_t, colind_t, X, v2e_val, e2v_val, degE, degV, W, Xe_out, Y, workspace,
+                        workspace_bytes, stream, true);
+}
+
+// io: HG_ROWS_SRC_BF16 | HG_ROWS_DST_BF16 (hg_gather_rows_incidence_heads_bf16), 0 the fp32 entry
+static int gather_rows_incidence(const char *who, const hg_plan *plan, int32_t hop, int32_t F, int32_t heads,
+                                 const int32_t *csrptr_t, const int32_t *colind_t, const void *src, const float *w,
+                                 const float *scaleA, const float *scaleB, void *dst, void *workspace, size_t workspace_bytes,
+                                 int32_t io, hg_stream_t stream) {
   if (hop != 0 && hop != 1) {  // before the plan is looked at, as heads < 1 is
     hg::set_error(std::string(who) + ": hop must be 0 (to the hyperedges) or 1 (to the vertices)");
     return HG_ERR_INVALID;
@@ -2005,8 +2040,31 @@ int hg_gather_rows_incidence_heads_f32(const hg_plan *plan, int32_t hop, int32_t
     hg::set_error(std::string(who) + ": panel_rows / panel_nnz leave no LDS for the staged weights (160 KiB per workgroup)");
     return HG_ERR_UNSUPPORTED;
   }
+  const bool src_bf16 = io & HG_ROWS_SRC_BF16, dst_bf16 = io & HG_ROWS_DST_BF16;
+  if (io != 0 && (rc = check_rows_bf16(who, F, heads, {{src, src_bf16}, {dst, dst_bf16}})) != HG_OK) return rc;
   return incidence_hop(plan, hop, F, heads, csrptr_t, colind_t, src, w, scaleA, scaleB, dst, static_cast<char *>(workspace),
-                       carve(plan, F), static_cast<hipStream_t>(stream));
+                       carve(plan, F), static_cast<hipStream_t>(stream), src_bf16, dst_bf16);
+}
+
+int hg_gather_rows_incidence_heads_f32(const hg_plan *plan, int32_t hop, int32_t F, int32_t heads, const int32_t *csrptr_t,
+                                       const int32_t *colind_t, const float *src, const float *w, const float *scaleA,
+                                       const float *scaleB, float *dst, void *workspace, size_t workspace_bytes,
+                                       hg_stream_t stream) {
+  return gather_rows_incidence("hg_gather_rows_incidence_heads_f32", plan, hop, F, heads, csrptr_t, colind_t, src, w, scaleA,
+                               scaleB, dst, workspace, workspace_bytes, 0, stream);
+}
+
+int hg_gather_rows_incidence_heads_bf16(const hg_plan *plan, int32_t hop, int32_t F, int32_t heads, const int32_t *csrptr_t,
+                                        const int32_t *colind_t, const void *src, const float *w, const float *scaleA,
+                                        const float *scaleB, void *dst, void *workspace, size_t workspace_bytes, int32_t io,
+                                        hg_stream_t stream) {
+  const char *who = "hg_gather_rows_incidence_heads_bf16";
+  if (io < 1 || io > (HG_ROWS_SRC_BF16 | HG_ROWS_DST_BF16)) {  // an argument like hop: before the plan is looked at
+    hg::set_error(std::string(who) + ": io must be HG_ROWS_SRC_BF16, HG_ROWS_DST_BF16 or both (fp32 rows: hg_gather_rows_incidence_heads_f32)");
+    return HG_ERR_INVALID;
+  }
+  return gather_rows_incidence(who, plan, hop, F, heads, csrptr_t, colind_t, src, w, scaleA, scaleB, dst, workspace,
+                               workspace_bytes, io, stream);
 }
 
 int hg_incidence_dot_f32(const hg_plan *plan, int32_t F, const int32_t *csrptr_t, const int32_t *colind_t,
@@ -2039,6 +2097,32 @@ int hg_incidence_dot_heads_f32(const hg_plan *plan, int32_t F, int32_t heads, co
   hipError_t e = hg::launch_incidence_dot_heads(plan->M, plan->nnz, heads, C, csrptr_t, colind_t, A, B, out, lane4,
                                                 static_cast<hipStream_t>(stream));
   if (e != hipSuccess) return hip_fail("incidence_dot_heads launch", e);
+  return HG_OK;
+}
+
+int hg_incidence_dot_heads_bf16(const hg_plan *plan, int32_t F, int32_t heads, const int32_t *csrptr_t,
+                                const int32_t *colind_t, const void *A, const void *B, float *out, int32_t io,
+                                hg_stream_t stream) {
+  const char *who = "hg_incidence_dot_heads_bf16";
+  if (io < 1 || io > (HG_DOT_A_BF16 | HG_DOT_B_BF16)) {
+    hg::set_error(std::string(who) + ": io must be HG_DOT_A_BF16, HG_DOT_B_BF16 or both (fp32 rows: hg_incidence_dot_heads_f32)");
+    return HG_ERR_INVALID;
+  }
+  int rc = check_heads(who, plan, heads, F);
+  if (rc != HG_OK) return rc;
+  if ((rc = check_call(plan, F, nullptr, 0, kSizeLater)) != HG_OK) return rc;
+  if (plan->nnz > 0 && (!csrptr_t || !colind_t || !A || !B || !out)) {
+    hg::set_error(std::string(who) + ": null array");
+    return HG_ERR_INVALID;
+  }
+  const bool a_bf16 = io & HG_DOT_A_BF16, b_bf16 = io & HG_DOT_B_BF16;
+  if ((rc = check_rows_bf16(who, F, heads, {{A, a_bf16}, {B, b_bf16}})) != HG_OK) return rc;
+  // heads == 1 on the single-head kernel, as the fp32 entry: the lanes of a row of F columns, not of a head
+  hipError_t e = heads == 1 ? hg::launch_incidence_dot(plan->M, plan->nnz, F, csrptr_t, colind_t, A, B, out, true,
+                                                       static_cast<hipStream_t>(stream), a_bf16, b_bf16)
+                            : hg::launch_incidence_dot_heads(plan->M, plan->nnz, heads, F / heads, csrptr_t, colind_t, A, B, out,
+                                                             true, static_cast<hipStream_t>(stream), a_bf16, b_bf16);
+  if (e != hipSuccess) return hip_fail("incidence_dot_bf16 launch", e);
   return HG_OK;
 }
 

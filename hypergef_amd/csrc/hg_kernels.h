@@ -177,13 +177,14 @@ struct PushArgs {
 // materialised table stay fp32).  At most one of src_bf16 and dst_bf16.
 hipError_t launch_gather(const GatherArgs &a, int nfix, int nfix_l1, const Fixup *fixups, bool vec4,
                          hipStream_t stream, bool src_bf16 = false, bool dst_bf16 = false);
-// the same with a.w (not null) on the weighted instances; fp32 rows
+// the same with a.w (not null) on the weighted instances.  src_bf16 / dst_bf16 (either or both): as launch_gather's, vec4 only
 hipError_t launch_gather_weighted(const WeightedGatherArgs &a, int nfix, int nfix_l1, const Fixup *fixups, bool vec4,
-                                  hipStream_t stream);
+                                  hipStream_t stream, bool src_bf16 = false, bool dst_bf16 = false);
 // a.w [nnz, heads] on the per-head instances.  vec4: as above; lane4: 16-byte lanes may be used (vec4 and C % 4 == 0, so
 // that a lane lies inside one head); otherwise 4-byte lanes on the single-head call's lane groups.
+// src_bf16 / dst_bf16: bf16 rows, lane4 only.
 hipError_t launch_gather_heads(const HeadsGatherArgs &a, int nfix, int nfix_l1, const Fixup *fixups, bool vec4, bool lane4,
-                               hipStream_t stream);
+                               hipStream_t stream, bool src_bf16 = false, bool dst_bf16 = false);
 // the attention instances: launch_gather_heads' lanes and order of summation, the weights formed from a's scores and statistics
 hipError_t launch_gather_attention(const AttnGatherArgs &a, int nfix, int nfix_l1, const Fixup *fixups, bool vec4, bool lane4,
                                    hipStream_t stream);
@@ -191,11 +192,14 @@ hipError_t launch_gather_attention(const AttnGatherArgs &a, int nfix, int nfix_l
 size_t attn_gather_lds_bytes(int32_t panel_rows, int32_t panel_nnz, int32_t heads, bool stat_row);
 // out[p, h] = <A[ind[p], hC .. (h+1)C), B[e, hC .. (h+1)C)>, out [nnz, H].  lane4: C % 4 == 0 and A, B 16-byte aligned.
 hipError_t launch_incidence_dot_heads(int32_t M, int64_t nnz, int32_t H, int32_t C, const int32_t *ptr, const int32_t *ind,
-                                      const float *A, const float *B, float *out, bool lane4, hipStream_t stream);
+                                      const void *A, const void *B, float *out, bool lane4, hipStream_t stream,
+                                      bool a_bf16 = false, bool b_bf16 = false);
 // out[p] = <A[ind[p], :], B[e, :]> for every entry p of the CSR (ptr, ind) over M rows, e the row holding p (the weight
-// gradient of hg_aggr_incidence_f32).  vec4: F % 4 == 0 and A, B 16-byte aligned.
-hipError_t launch_incidence_dot(int32_t M, int64_t nnz, int32_t F, const int32_t *ptr, const int32_t *ind, const float *A,
-                                const float *B, float *out, bool vec4, hipStream_t stream);
+// gradient of hg_aggr_incidence_f32).  vec4: F % 4 == 0 and A, B 16-byte aligned.  a_bf16 / b_bf16: rows of A / B are bf16
+// (vec4 / lane4 only, 8-byte aligned), widened in the load: the fp32 call's lanes, fma chain and butterfly.
+hipError_t launch_incidence_dot(int32_t M, int64_t nnz, int32_t F, const int32_t *ptr, const int32_t *ind, const void *A,
+                                const void *B, float *out, bool vec4, hipStream_t stream, bool a_bf16 = false,
+                                bool b_bf16 = false);
 // hyperedge_dot_kernel (hg_hyperedge_dot_heads_f32): out[e] = sum_c (sum_{p=(e,u)} wa[p, c / C] A[u, c]) * (sum_p wb[p, c / C] B[u, c])
 struct EdgeDotArgs {
   const int32_t *ptr, *ind;  // H_T

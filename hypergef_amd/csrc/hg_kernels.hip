@@ -427,7 +427,8 @@ __global__ __launch_bounds__(256) void fixup_rows_kernel(const GatherArgs a, con
 // entries): a lane group of LPR lanes owns kDotRun consecutive entries.  It finds the row of its first entry by a
 // binary search inside the workgroup's row range (itself two uniform searches over ptr), then steps along.  Each output
 // is one lane group's: the lanes' fma chains over their columns, then a fixed butterfly over the LPR lanes --
-// deterministic.  The kDotRun entries' row loads are issued together.
+// deterministic.  The kDotRun entries' row loads are issued together.  TA / TB: element types of A's / B's rows (Rows): a
+// bf16 operand is widened in the load (exact), so the fma chain and the butterfly see the floats the fp32 instance sees.
 constexpr int kDotRun = 4;
 __device__ __forceinline__ int row_of(const int32_t *ptr, int lo, int hi, int64_t p) {  // ptr[lo] <= p < ptr[hi]
   while (hi - lo > 1) {
@@ -437,9 +438,9 @@ __device__ __forceinline__ int row_of(const int32_t *ptr, int lo, int hi, int64_
   }
   return lo;
 }
-template <int LPR, int VEC>
+template <int LPR, int VEC, typename TA = float, typename TB = float>
 __global__ __launch_bounds__(256) void incidence_dot_kernel(const int32_t *ptr, const int32_t *ind, int32_t M, int64_t nnz,
-                                                            int32_t F, const float *A, const float *B, float *out) {
+                                                            int32_t F, const TA *A, const TB *B, float *out) {
   using V = Vec<VEC>;
   constexpr int NG = 256 / LPR;
   const int tid = threadIdx.x, gl = tid & (LPR - 1), g = tid / LPR;
@@ -466,8 +467,8 @@ __global__ __launch_bounds__(256) void incidence_dot_kernel(const int32_t *ptr, 
     V x[kDotRun], y[kDotRun];
 #pragma unroll
     for (int k = 0; k < kDotRun; k++) {
-      x[k] = V::load(A + ua[k] + c);
-      y[k] = V::load(B + eb[k] + c);
+      x[k] = Rows<TA, VEC>::load(A + ua[k] + c);
+      y[k] = Rows<TB, VEC>::load(B + eb[k] + c);
     }
 #pragma unroll
     for (int k = 0; k < kDotRun; k++) {
@@ -494,10 +495,10 @@ __global__ __launch_bounds__(256) void incidence_dot_kernel(const int32_t *ptr, 
 // groups take the consecutive heads of the same entries, so a wave reads neighbouring pieces of the same rows.  The
 // butterfly runs over a group's LPH lanes only: the lanes of one head are reduced apart from their neighbours, in a
 // fixed order.
-template <int LPH, int VEC>
+template <int LPH, int VEC, typename TA = float, typename TB = float>
 __global__ __launch_bounds__(256) void incidence_dot_heads_kernel(const int32_t *ptr, const int32_t *ind, int32_t M,
-                                                                  int64_t nnz, int32_t H, int32_t C, const float *A,
-                                                                  const float *B, float *out) {
+                                                                  int64_t nnz, int32_t H, int32_t C, const TA *A,
+                                                                  const TB *B, float *out) {
   using V = Vec<VEC>;
   constexpr int NG = 256 / LPH;
   const int tid = threadIdx.x, gl = tid & (LPH - 1), g = tid / LPH;
@@ -528,8 +529,8 @@ __global__ __launch_bounds__(256) void incidence_dot_heads_kernel(const int32_t 
     V x[kDotRun], y[kDotRun];
 #pragma unroll
     for (int k = 0; k < kDotRun; k++) {
-      x[k] = V::load(A + ua[k] + c);
-      y[k] = V::load(B + eb[k] + c);
+      x[k] = Rows<TA, VEC>::load(A + ua[k] + c);
+      y[k] = Rows<TB, VEC>::load(B + eb[k] + c);
     }
 #pragma unroll
     for (int k = 0; k < kDotRun; k++) {
@@ -2460,9 +2461,10 @@ hipError_t launch_gather(const GatherArgs &a, int nfix, int nfix_l1, const Fixup
                          hipStream_t stream, bool src_bf16, bool dst_bf16) {
   const int lanes = vec4 ? a.F / 4 : a.F;
   const int lpr = std::min(64, next_pow2(std::max(lanes, 1)));
-  if ((src_bf16 || dst_bf16) && (!vec4 || (src_bf16 && dst_bf16))) return hipErrorInvalidValue;
+  if ((src_bf16 || dst_bf16) && !vec4) return hipErrorInvalidValue;
 #define HG_CASE(L)                                                                                       \
   case L:                                                                                                \
+    if (src_bf16 && dst_bf16) return launch_gather_t<L, 4, bf16, bf16>(a, nfix, nfix_l1, fixups, stream); \
     if (src_bf16) return launch_gather_t<L, 4, bf16, float>(a, nfix, nfix_l1, fixups, stream);            \
     if (dst_bf16) return launch_gather_t<L, 4, float, bf16>(a, nfix, nfix_l1, fixups, stream);            \
     return vec4 ? launch_gather_t<L, 4>(a, nfix, nfix_l1, fixups, stream)                                \
@@ -2480,13 +2482,20 @@ hipError_t launch_gather(const GatherArgs &a, int nfix, int nfix_l1, const Fixup
   return hipErrorInvalidValue;
 }
 
+// bf16 rows on the weighted (WM = 1) and per-head (WM = 2) instances: the three forms of (src, dst), 16-byte lanes only
+#define HG_ROWS_BF16(L, WM)                                                                                           \
+  if (src_bf16 && dst_bf16) return launch_gather_t<L, 4, bf16, bf16, WM>(a, nfix, nfix_l1, fixups, stream);            \
+  if (src_bf16) return launch_gather_t<L, 4, bf16, float, WM>(a, nfix, nfix_l1, fixups, stream);                       \
+  if (dst_bf16) return launch_gather_t<L, 4, float, bf16, WM>(a, nfix, nfix_l1, fixups, stream);
+
 hipError_t launch_gather_weighted(const WeightedGatherArgs &a, int nfix, int nfix_l1, const Fixup *fixups, bool vec4,
-                                  hipStream_t stream) {
-  if (!a.w) return hipErrorInvalidValue;
+                                  hipStream_t stream, bool src_bf16, bool dst_bf16) {
+  if (!a.w || ((src_bf16 || dst_bf16) && !vec4)) return hipErrorInvalidValue;
   const int lanes = vec4 ? a.F / 4 : a.F;
   const int lpr = std::min(64, next_pow2(std::max(lanes, 1)));
 #define HG_CASE(L)                                                                                     \
   case L:                                                                                              \
+    HG_ROWS_BF16(L, 1)                                                                                 \
     return vec4 ? launch_gather_t<L, 4, float, float, 1>(a, nfix, nfix_l1, fixups, stream)          \
                 : launch_gather_t<L, 1, float, float, 1>(a, nfix, nfix_l1, fixups, stream);
   switch (lpr) {
@@ -2506,12 +2515,14 @@ hipError_t launch_gather_weighted(const WeightedGatherArgs &a, int nfix, int nfi
 // single-head call of the same F -- the heads instances keep it on 4-byte lanes too and run more column tiles instead, so
 // that a wave task's entries are dealt to the same 64 / lpr row groups and every column is summed in the single-head order.
 hipError_t launch_gather_heads(const HeadsGatherArgs &a, int nfix, int nfix_l1, const Fixup *fixups, bool vec4, bool lane4,
-                               hipStream_t stream) {
+                               hipStream_t stream, bool src_bf16, bool dst_bf16) {
   if (!a.w || a.heads < 1 || a.C < 1 || (int64_t)a.heads * a.C != a.F || (lane4 && (!vec4 || a.C % 4))) return hipErrorInvalidValue;
+  if ((src_bf16 || dst_bf16) && !lane4) return hipErrorInvalidValue;
   const int lanes = vec4 ? a.F / 4 : a.F;
   const int lpr = std::min(64, next_pow2(std::max(lanes, 1)));
 #define HG_CASE(L)                                                                                  \
   case L:                                                                                           \
+    HG_ROWS_BF16(L, 2)                                                                              \
     return lane4 ? launch_gather_t<L, 4, float, float, 2>(a, nfix, nfix_l1, fixups, stream)         \
                  : launch_gather_t<L, 1, float, float, 2>(a, nfix, nfix_l1, fixups, stream);
   switch (lpr) {
@@ -2526,6 +2537,7 @@ hipError_t launch_gather_heads(const HeadsGatherArgs &a, int nfix, int nfix_l1, 
 #undef HG_CASE
   return hipErrorInvalidValue;
 }
+#undef HG_ROWS_BF16
 
 size_t attn_gather_lds_bytes(int32_t panel_rows, int32_t panel_nnz, int32_t heads, bool stat_row) {
   return ((size_t)4 * panel_rows + 1 + panel_nnz + (size_t)(stat_row ? 3 : 1) * panel_rows * heads) * sizeof(int32_t);
@@ -2555,22 +2567,37 @@ hipError_t launch_gather_attention(const AttnGatherArgs &a, int nfix, int nfix_l
   return hipErrorInvalidValue;
 }
 
+// a_bf16 / b_bf16: rows of A / B are bf16 (16-byte lanes only: the caller has checked widths and alignment)
+#define HG_DOT_BF16(KERN, L, ...)                                                                                          \
+  if (a_bf16 && b_bf16)                                                                                                    \
+    hipLaunchKernelGGL((KERN<L, 4, bf16, bf16>), dim3((unsigned)nblocks), dim3(256), 0, stream, ptr, ind, M, nnz, __VA_ARGS__, \
+                       static_cast<const bf16 *>(A), static_cast<const bf16 *>(B), out);                                   \
+  else if (a_bf16)                                                                                                         \
+    hipLaunchKernelGGL((KERN<L, 4, bf16, float>), dim3((unsigned)nblocks), dim3(256), 0, stream, ptr, ind, M, nnz, __VA_ARGS__, \
+                       static_cast<const bf16 *>(A), static_cast<const float *>(B), out);                                  \
+  else if (b_bf16)                                                                                                         \
+    hipLaunchKernelGGL((KERN<L, 4, float, bf16>), dim3((unsigned)nblocks), dim3(256), 0, stream, ptr, ind, M, nnz, __VA_ARGS__, \
+                       static_cast<const float *>(A), static_cast<const bf16 *>(B), out);
+
 hipError_t launch_incidence_dot_heads(int32_t M, int64_t nnz, int32_t H, int32_t C, const int32_t *ptr, const int32_t *ind,
-                                      const float *A, const float *B, float *out, bool lane4, hipStream_t stream) {
+                                      const void *A, const void *B, float *out, bool lane4, hipStream_t stream, bool a_bf16,
+                                      bool b_bf16) {
   if (nnz == 0) return hipSuccess;
-  if (M <= 0 || H <= 0 || C <= 0 || (lane4 && C % 4)) return hipErrorInvalidValue;
+  if (M <= 0 || H <= 0 || C <= 0 || (lane4 && C % 4) || ((a_bf16 || b_bf16) && !lane4)) return hipErrorInvalidValue;
   const int lanes = lane4 ? C / 4 : C;
   const int lph = std::min(64, next_pow2(std::max(lanes, 1)));
   const int64_t items = (nnz + kDotRun - 1) / kDotRun * H;
   const int64_t per_block = 256 / lph;
   const int64_t nblocks = (items + per_block - 1) / per_block;
   if (nblocks > 0x7fffffff) return hipErrorInvalidValue;
+  const float *Af = static_cast<const float *>(A), *Bf = static_cast<const float *>(B);
 #define HG_CASE(L)                                                                                                       \
   case L:                                                                                                                \
-    if (lane4) hipLaunchKernelGGL((incidence_dot_heads_kernel<L, 4>), dim3((unsigned)nblocks), dim3(256), 0, stream, ptr, \
-                                  ind, M, nnz, H, C, A, B, out);                                                         \
+    HG_DOT_BF16(incidence_dot_heads_kernel, L, H, C)                                                                     \
+    else if (lane4) hipLaunchKernelGGL((incidence_dot_heads_kernel<L, 4>), dim3((unsigned)nblocks), dim3(256), 0, stream, ptr, \
+                                       ind, M, nnz, H, C, Af, Bf, out);                                                  \
     else hipLaunchKernelGGL((incidence_dot_heads_kernel<L, 1>), dim3((unsigned)nblocks), dim3(256), 0, stream, ptr, ind,  \
-                            M, nnz, H, C, A, B, out);                                                                    \
+                            M, nnz, H, C, Af, Bf, out);                                                                  \
     return hipGetLastError();
   switch (lph) {
     HG_CASE(1)
@@ -2585,21 +2612,23 @@ hipError_t launch_incidence_dot_heads(int32_t M, int64_t nnz, int32_t H, int32_t
   return hipErrorInvalidValue;
 }
 
-hipError_t launch_incidence_dot(int32_t M, int64_t nnz, int32_t F, const int32_t *ptr, const int32_t *ind, const float *A,
-                                const float *B, float *out, bool vec4, hipStream_t stream) {
+hipError_t launch_incidence_dot(int32_t M, int64_t nnz, int32_t F, const int32_t *ptr, const int32_t *ind, const void *A,
+                                const void *B, float *out, bool vec4, hipStream_t stream, bool a_bf16, bool b_bf16) {
   if (nnz == 0) return hipSuccess;
-  if (M <= 0 || F <= 0 || (vec4 && F % 4)) return hipErrorInvalidValue;
+  if (M <= 0 || F <= 0 || (vec4 && F % 4) || ((a_bf16 || b_bf16) && !vec4)) return hipErrorInvalidValue;
   const int lanes = vec4 ? F / 4 : F;
   const int lpr = std::min(64, next_pow2(std::max(lanes, 1)));
   const int64_t per_block = (int64_t)(256 / lpr) * kDotRun;
   const int64_t nblocks = (nnz + per_block - 1) / per_block;
   if (nblocks > 0x7fffffff) return hipErrorInvalidValue;
+  const float *Af = static_cast<const float *>(A), *Bf = static_cast<const float *>(B);
 #define HG_CASE(L)                                                                                                   \
   case L:                                                                                                            \
-    if (vec4) hipLaunchKernelGGL((incidence_dot_kernel<L, 4>), dim3((unsigned)nblocks), dim3(256), 0, stream, ptr, ind, M, \
-                                 nnz, F, A, B, out);                                                                 \
+    HG_DOT_BF16(incidence_dot_kernel, L, F)                                                                          \
+    else if (vec4) hipLaunchKernelGGL((incidence_dot_kernel<L, 4>), dim3((unsigned)nblocks), dim3(256), 0, stream, ptr, ind, M, \
+                                      nnz, F, Af, Bf, out);                                                          \
     else hipLaunchKernelGGL((incidence_dot_kernel<L, 1>), dim3((unsigned)nblocks), dim3(256), 0, stream, ptr, ind, M,   \
-                            nnz, F, A, B, out);                                                                      \
+                            nnz, F, Af, Bf, out);                                                                    \
     return hipGetLastError();
   switch (lpr) {
     HG_CASE(1)
@@ -2613,6 +2642,7 @@ hipError_t launch_incidence_dot(int32_t M, int64_t nnz, int32_t F, const int32_t
 #undef HG_CASE
   return hipErrorInvalidValue;
 }
+#undef HG_DOT_BF16
 
 // ---- the product of two hyperedge sums (hg_hyperedge_dot_heads_f32): the gradient of a per-hyperedge scale ---------------
 // out[e] = sum_c SA[e, c] * SB[e, c] with SA[e, :] = sum_{p=(e,u)} wa[p, c / C] * A[u, :] and SB likewise from (B, wb).

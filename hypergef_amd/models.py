@@ -137,7 +137,12 @@ class HypergraphAttnConv(nn.Module):
     fuse_attention=True: softmax and aggregation run as ops.incidence_attention_aggr -- the same output and gradient bits,
     with no alpha [nnz, heads] written, read or kept for the backward -- where that operator applies: score = 'additive' and
     no dropout active (dropout = 0.0, or eval()).  Elsewhere the layer takes the path above without a word.  No parameter
-    or buffer is added; False (the default) is the layer above."""
+    or buffer is added; False (the default) is the layer above.
+    After .to(torch.bfloat16) the layer runs on bfloat16 rows: it turns Options.incidence_bf16 = 'rows' on for its own calls,
+    so Z, the hyperedge keys and Y are bfloat16 rows on the library's bf16-row kernels (fp32 sums, one rounding), while
+    sv, se, the dot logits and alpha are formed in float32 from the widened Z; a learned Wdiag is widened too.
+    fuse_attention=True then takes the composed path (ops.incidence_attention_aggr is float32 only).  float32 layers are
+    untouched."""
 
     def __init__(self, hyperg, in_channels, out_channels, group="hyperedge", negative_slope=0.2, options=None, heads=1,
                  concat=True, dropout=0.0, score="additive", learn_hyperedge_weight=False, fuse_attention=False):
@@ -167,10 +172,18 @@ class HypergraphAttnConv(nn.Module):
         self._members = hyperg.H_T_colind.long()                                 # vertex of every incidence
         self._inv_size = torch.nan_to_num(hyperg.degE.reshape(-1), posinf=0.0)   # 1 / |e|, 0 for an empty hyperedge
 
+    def _options(self, rows):
+        """The layer's options for one call: its own (or the caller's), with bfloat16 feature rows let through where `rows`
+        (Z, or the keys' input) is bfloat16."""
+        if rows.dtype != torch.bfloat16:
+            return self.options
+        return (self.options if self.options is not None else ops.current_options()).replace(incidence_bf16="rows")
+
     def hyperedge_keys(self, X):
         """score = 'dot': the hyperedges' own embeddings Ke [M, H * C], the mean of lin_k(X) over each hyperedge's members."""
-        return ops.incidence_gather(self.hyperg.H_T_csrptr, self.hyperg.H_T_colind, self.lin_k(X), None, to="hyperedge",
-                                    scale_a=self._inv_size, options=self.options)
+        Kv = self.lin_k(X)
+        return ops.incidence_gather(self.hyperg.H_T_csrptr, self.hyperg.H_T_colind, Kv, None, to="hyperedge",
+                                    scale_a=self._inv_size, options=self._options(Kv))
 
     def coefficients(self, Z, X=None):
         """alpha for the projected features Z: [nnz], or [nnz, heads]; after dropout where the layer trains with one.
@@ -179,7 +192,11 @@ class HypergraphAttnConv(nn.Module):
         if self.score == "dot":
             if X is None:
                 raise ValueError("score='dot': coefficients(Z, X) needs the layer's input X for the hyperedge keys")
-            logits = ops.incidence_dot(ptr, ind, Z, self.hyperedge_keys(X), heads=self.heads) * self.out_channels ** -0.5
+            if Z.dtype == torch.bfloat16:  # both operands bfloat16 rows, the logits float32
+                logits = ops.incidence_dot(ptr, ind, Z, self.hyperedge_keys(X), heads=self.heads,
+                                           options=self._options(Z)) * self.out_channels ** -0.5
+            else:
+                logits = ops.incidence_dot(ptr, ind, Z, self.hyperedge_keys(X), heads=self.heads) * self.out_channels ** -0.5
             return ops.incidence_softmax(ptr, ind, None, None, group=self.group, negative_slope=self.negative_slope,
                                          options=self.options, num_nodes=Z.shape[0], heads=self.heads, dropout=self.dropout,
                                          training=self.training, incidence_score=logits)
@@ -195,21 +212,28 @@ class HypergraphAttnConv(nn.Module):
     def scores(self, Z):
         """score = 'additive': (sv [N] / [N, heads], se [M] / [M, heads]) for the projected features Z."""
         ptr, ind = self.hyperg.H_T_csrptr, self.hyperg.H_T_colind
+        if Z.dtype == torch.bfloat16:  # the scores are float32, from the widened rows and vectors
+            return self._scores(Z.float(), self.a_v.float(), self.a_e.float())
+        return self._scores(Z, self.a_v, self.a_e)
+
+    def _scores(self, Z, a_v, a_e):
+        ptr, ind = self.hyperg.H_T_csrptr, self.hyperg.H_T_colind
         if self.heads == 1:
-            sv = Z @ self.a_v
-            ze = (Z @ self.a_e)[self._members]
+            sv = Z @ a_v
+            ze = (Z @ a_e)[self._members]
             se = ops.incidence_sum(ptr, ind, ze, side="hyperedge", num_nodes=Z.shape[0]) * self._inv_size
             return sv, se
         H, C = self.heads, self.out_channels
         Zh = Z.view(Z.shape[0], H, C)
-        sv = (Zh * self.a_v.view(H, C)).sum(-1)
-        ze = (Zh * self.a_e.view(H, C)).sum(-1)[self._members]
+        sv = (Zh * a_v.view(H, C)).sum(-1)
+        ze = (Zh * a_e.view(H, C)).sum(-1)[self._members]
         se = ops.incidence_sum(ptr, ind, ze, side="hyperedge", num_nodes=Z.shape[0], heads=H) * self._inv_size.reshape(-1, 1)
         return sv, se
 
     def forward(self, X):
         Z = self.lin(X)
-        if self.fuse_attention and self.score == "additive" and not (self.dropout > 0.0 and self.training):
+        if self.fuse_attention and self.score == "additive" and not (self.dropout > 0.0 and self.training) \
+                and Z.dtype == torch.float32:
             sv, se = self.scores(Z)
             Y = ops.incidence_attention_aggr(self.hyperg.H_T_csrptr, self.hyperg.H_T_colind, Z, sv, se, group=self.group,
                                              negative_slope=self.negative_slope, degE=self.degE, degV=self.degV,
@@ -218,8 +242,9 @@ class HypergraphAttnConv(nn.Module):
                 Y = Y.view(Y.shape[0], self.heads, self.out_channels).mean(1)
             return Y + self.bias
         alpha = self.coefficients(Z, X)
+        Wdiag = self.Wdiag.float() if Z.dtype == torch.bfloat16 else self.Wdiag  # the scales stay float32
         Y = ops.incidence_aggr(self.hyperg.H_T_csrptr, self.hyperg.H_T_colind, Z, alpha, alpha, self.degE, self.degV,
-                               self.Wdiag, options=self.options, heads=self.heads)
+                               Wdiag, options=self._options(Z), heads=self.heads)
         if self.heads > 1 and not self.concat:
             Y = Y.view(Y.shape[0], self.heads, self.out_channels).mean(1)
         return Y + self.bias

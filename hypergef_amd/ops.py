@@ -49,6 +49,12 @@ class Options:
                  into the aggregation on the bf16 MFMA (hg_aggr_linear_res_bf16: fp32 accumulation, one rounding of the
                  combined row and one of the result) wherever fuse_linear folds -- 'always' at every supported width,
                  'auto' under plan.linear_bf16_fusion_pays; variants auto, pull and fused.  float32 layers ignore it.
+    incidence_bf16: what the incidence operators do with bfloat16 feature rows.  'refuse' = the TypeError they always
+                 raised; 'rows' = incidence_aggr / HGNNAggrIncidence, incidence_gather and incidence_dot take bfloat16
+                 node_feat / src / A / B on the library's bf16-row kernels (hg_aggr_incidence_heads_bf16 and its
+                 neighbours): fp32 sums in the float32 call's order, one rounding of a bfloat16 result.  The weights, scales
+                 and the dot's result stay float32; incidence_softmax, incidence_sum, incidence_attention_aggr and
+                 hyperedge_dot stay float32 only.
 
     Every operator resolves its options per call -- an explicit `options=` argument, else the innermost
     `with ops.options(...)` block of the calling thread, else the process defaults -- and an autograd node keeps
@@ -59,10 +65,12 @@ class Options:
     fuse_linear: str = "auto"
     linear_math: str = "f32"
     linear_bf16: str = "torch"
+    incidence_bf16: str = "refuse"
 
     _CHOICES = {"variant": ("auto", "pull", "fused", "push_atomic", "push_groups"),
                 "backward": ("reference", "adjoint"), "fuse_linear": ("auto", "always", "never"),
-                "linear_math": ("f32", "bf16x6"), "linear_bf16": ("torch", "mfma")}
+                "linear_math": ("f32", "bf16x6"), "linear_bf16": ("torch", "mfma"),
+                "incidence_bf16": ("refuse", "rows")}
 
     def __post_init__(self):
         for k, allowed in Options._CHOICES.items():
@@ -79,7 +87,9 @@ _DEFAULTS = Options(fuse_linear=_os.environ["HG_FUSE_LINEAR"]
                     linear_math=_os.environ["HG_LINEAR_MATH"]
                     if _os.environ.get("HG_LINEAR_MATH") in ("f32", "bf16x6") else "f32",
                     linear_bf16=_os.environ["HG_LINEAR_BF16"]
-                    if _os.environ.get("HG_LINEAR_BF16") in ("torch", "mfma") else "torch")
+                    if _os.environ.get("HG_LINEAR_BF16") in ("torch", "mfma") else "torch",
+                    incidence_bf16=_os.environ["HG_INCIDENCE_BF16"]
+                    if _os.environ.get("HG_INCIDENCE_BF16") in ("refuse", "rows") else "refuse")
 _TLS = threading.local()
 
 
@@ -139,6 +149,17 @@ def set_linear_math(mode):
 def set_linear_bf16(mode):
     """Process default of Options.linear_bf16."""
     _set_default(linear_bf16=mode)
+
+
+def set_incidence_bf16(mode):
+    """Process default of Options.incidence_bf16."""
+    _set_default(incidence_bf16=mode)
+
+
+def _rows_dtype_ok(t, opt):
+    """float32, or bfloat16 feature rows where Options.incidence_bf16 = 'rows' lets the incidence operators take them."""
+    return isinstance(t, torch.Tensor) and (t.dtype == torch.float32 or
+                                            (opt.incidence_bf16 == "rows" and t.dtype == torch.bfloat16))
 
 
 def _flat(t):
@@ -544,7 +565,8 @@ def _incidence_args(csrptr_t, indices_t, node_feat, v2e, e2v, opt, heads=1):
         raise ValueError("incidence_aggr runs the pull kernels: variant must be 'auto' or 'pull', got %r" % opt.variant)
     _heads(heads)
     for name, t in (("node_feat", node_feat), ("v2e_weight", v2e), ("e2v_weight", e2v)):
-        if t is not None and (not isinstance(t, torch.Tensor) or t.dtype != torch.float32):
+        if t is not None and (not isinstance(t, torch.Tensor) or t.dtype != torch.float32) \
+                and not (name == "node_feat" and _rows_dtype_ok(t, opt)):  # Options.incidence_bf16 = 'rows': bf16 rows, never weights
             raise TypeError("%s must be a float32 tensor (incidence_aggr has no bfloat16 form), got %s"
                             % (name, getattr(t, "dtype", type(t))))
     if node_feat.dim() != 2:
@@ -562,7 +584,7 @@ def _incidence_args(csrptr_t, indices_t, node_feat, v2e, e2v, opt, heads=1):
                              % (name, nnz * heads, t.numel()))
     _check_index(csrptr_t, "csrptr_t")
     _check_index(indices_t, "indices_t")
-    _check_feat(node_feat, "node_feat")
+    _check_feat(node_feat, "node_feat", bf16_ok=opt.incidence_bf16 == "rows")
     for name, t in (("v2e_weight", v2e), ("e2v_weight", e2v)):
         if t is not None:
             _check_feat(t, name, device=node_feat.device)
@@ -575,7 +597,10 @@ class _IncidenceAggr(torch.autograd.Function):
     Xe the forward's hop-1 table, kept only when e2v needs a gradient.  With heads = H the weights and their gradients are
     [nnz, H] and the products run over each head's own columns.  degE / degV / W get their exact gradients where they require
     one: q[e] = <sum_p v2e[p] X[u], sum_p e2v[p] P[v]> (Plan.hyperedge_dot), dW = q degE, ddegE = q W, and
-    ddegV[v] = <dY[v], Z[v]> with Z the same call without degV (Plan.rows_dot); X is then kept as for dv2e."""
+    ddegV[v] = <dY[v], Z[v]> with Z the same call without degV (Plan.rows_dot); X is then kept as for dv2e.
+    bfloat16 node_feat (Options.incidence_bf16 = 'rows'): the same node on the bf16-row kernels.  Y and dX are bfloat16;
+    P is rounded to bfloat16 once (_times_degV), Xe and G stay float32, the weight gradients come from the mixed dots
+    (bfloat16 X or P against float32 G or Xe) in float32; the scale gradients widen X and P for the float32 kernels."""
 
     @staticmethod
     def forward(ctx, csrptr_t, indices_t, node_feat, v2e, e2v, degE, degV, W, heads=1):
@@ -598,7 +623,7 @@ class _IncidenceAggr(torch.autograd.Function):
         N, F = g.shape
         M = csrptr_t.numel() - 1
         plan = cached_plan(N, csrptr_t, indices_t)
-        P = g if degV is None else g * degV.reshape(-1, 1)
+        P = g if degV is None else _times_degV(g, degV)
         need_x = ctx.needs_input_grad[2]
         need_v2e = v2e is not None and ctx.needs_input_grad[3]
         need_e2v = e2v is not None and ctx.needs_input_grad[4]
@@ -613,11 +638,11 @@ class _IncidenceAggr(torch.autograd.Function):
         need_dE, need_dV, need_dW = (t is not None and ctx.needs_input_grad[i] for i, t in ((5, degE), (6, degV), (7, W)))
         gE = gV = gW = None
         if need_dE or need_dW:  # q[e] = <sum_p v2e[p] X[u], sum_p e2v[p] P[v]>: both hyperedge sums in one kernel
-            q = plan.hyperedge_dot(csrptr_t, indices_t, X, P, v2e, e2v, heads=ctx.heads)
+            q = plan.hyperedge_dot(csrptr_t, indices_t, X.float(), P.float(), v2e, e2v, heads=ctx.heads)  # float(): bf16 rows widened
             gE, gW = _edge_scale_grads(plan, csrptr_t, q, degE, W, need_dE, need_dW)
         if need_dV:  # <dY[v], Z[v]>, Z the same call without degV
-            Z = plan.aggregate_incidence(csrptr_t, indices_t, X, v2e, e2v, degE, None, W, heads=ctx.heads)
-            gV = plan.rows_dot(g, Z)
+            Z = plan.aggregate_incidence(csrptr_t, indices_t, X.float(), v2e, e2v, degE, None, W, heads=ctx.heads)
+            gV = plan.rows_dot(g.float(), Z)
         return None, None, gx if need_x else None, gv, ge, gE, gV, gW, None
 
 
@@ -630,7 +655,9 @@ def incidence_aggr(csrptr_t, indices_t, node_feat, v2e_weight=None, e2v_weight=N
     arrays and, where they require one, for degE / degV / W -- the reference has no rule for this operator, so
     Options.backward does not apply.
     Options.variant 'auto' and 'pull' run (both are the pull kernels); 'fused', 'push_atomic', 'push_groups' raise
-    ValueError.  float32 only (TypeError for bfloat16).
+    ValueError.  float32 only (TypeError for bfloat16) unless Options.incidence_bf16 = 'rows': then node_feat may be bfloat16
+    and Y comes back bfloat16 -- Y = round_bf16(the float32 call on node_feat.float()) bit for bit -- with float32 weights,
+    scales and weight / scale gradients, and a bfloat16 gradient for node_feat.
     heads = H > 1: one call for H attention heads.  node_feat is [N, H * C] and head h owns columns h C .. (h + 1) C - 1;
     the weights are [nnz, H] (nnz * H elements, head fastest) and column h weighs head h's columns; their gradients come
     back [nnz, H].  F % H != 0 raises ValueError.  heads = 1 is the call above, unchanged."""
@@ -998,16 +1025,21 @@ _HOPS = ("hyperedge", "vertex")
 def _scaled(g, scale_a, scale_b):
     for sc in (scale_a, scale_b):
         if sc is not None:
-            g = g * sc.reshape(-1, 1)
+            g = g * sc.reshape(-1, 1)  # a bfloat16 g is promoted: the scaled gradient stays float32 for the mixed hop and dot
     return g.contiguous()
 
 
-def _hop(plan, csrptr_t, indices_t, to, src, w, scale_a, scale_b, heads):
+def _hop(plan, csrptr_t, indices_t, to, src, w, scale_a, scale_b, heads, dtype=None):
     """One hop on the plan: the weighted panels kernel of incidence_aggr's hop, or without weights the library's
-    unweighted row gather (Plan.gather_rows, hg_gather_rows_f32)."""
-    if w is None:
+    unweighted row gather (Plan.gather_rows, hg_gather_rows_f32).  dtype: the result's (default: src's); bfloat16 rows on
+    either side take the panels kernel's bf16-row instances, weighted or not (hg_gather_rows_incidence_heads_bf16)."""
+    dtype = src.dtype if dtype is None else dtype
+    if w is None and src.dtype == dtype == torch.float32:
         return plan.gather_rows(_HOPS.index(to), csrptr_t, indices_t, src, scale_a, scale_b)
-    return plan.gather_rows_incidence(to, csrptr_t, indices_t, src, w, scale_a, scale_b, heads=heads)
+    out = None
+    if dtype != src.dtype:
+        out = torch.empty((plan.M if to == "hyperedge" else plan.N, src.shape[1]), dtype=dtype, device=src.device)
+    return plan.gather_rows_incidence(to, csrptr_t, indices_t, src, w, scale_a, scale_b, heads=heads, out=out)
 
 
 class _IncidenceGather(torch.autograd.Function):
@@ -1020,7 +1052,7 @@ class _IncidenceGather(torch.autograd.Function):
         plan = cached_plan(N, csrptr_t, indices_t)
         keep_src = w is not None and ctx.needs_input_grad[3]
         ctx.save_for_backward(csrptr_t, indices_t, src if keep_src else None, w, scale_a, scale_b)
-        ctx.N, ctx.to, ctx.heads = N, to, heads
+        ctx.N, ctx.to, ctx.heads, ctx.dtype = N, to, heads, src.dtype
         return _hop(plan, csrptr_t, indices_t, to, src, w, scale_a, scale_b, heads)
 
     @staticmethod
@@ -1031,7 +1063,7 @@ class _IncidenceGather(torch.autograd.Function):
         back = _HOPS[1 - _HOPS.index(ctx.to)]
         gsrc = gw = None
         if ctx.needs_input_grad[2]:
-            gsrc = _hop(plan, csrptr_t, indices_t, back, gs, w, None, None, ctx.heads)
+            gsrc = _hop(plan, csrptr_t, indices_t, back, gs, w, None, None, ctx.heads, ctx.dtype)
         if w is not None and ctx.needs_input_grad[3]:
             A, B = (src, gs) if ctx.to == "hyperedge" else (gs, src)  # A: the vertex rows, B: the hyperedge rows
             gw = plan.incidence_dot(csrptr_t, indices_t, A, B, heads=ctx.heads).view_as(w)
@@ -1048,7 +1080,9 @@ def incidence_gather(csrptr_t, indices_t, src, weight=None, to="hyperedge", scal
     With weights it runs incidence_aggr's kernels for that hop (hg_gather_rows_incidence_heads_f32): hop 'hyperedge' into
     hop 'vertex' gives incidence_aggr's result bit for bit; without, the unweighted row gather (hg_gather_rows_f32).
     Differentiable in src and weight; the scales get no gradient here.  Options.variant 'auto' and 'pull' run;
-    the others raise ValueError.  float32 only (TypeError for bfloat16).  num_nodes: N for to='vertex', where src does not
+    the others raise ValueError.  float32 only (TypeError for bfloat16) unless Options.incidence_bf16 = 'rows': a bfloat16 src
+    gives a bfloat16 dst = round_bf16(the float32 call on src.float()), weighted or not, and gets a bfloat16 gradient; weight,
+    scales and the weight's gradient stay float32.  num_nodes: N for to='vertex', where src does not
     tell it; without it N is the length of a given scale, else the largest member id + 1, read back from the device."""
     opt = _opt(options)
     if opt.variant not in ("auto", "pull"):
@@ -1061,7 +1095,8 @@ def incidence_gather(csrptr_t, indices_t, src, weight=None, to="hyperedge", scal
         w = _flat(w) if heads == 1 else _per_head(w, heads)
     scale_a, scale_b = _flat(scale_a), _flat(scale_b)
     for name, t in (("src", src), ("weight", w), ("scale_a", scale_a), ("scale_b", scale_b)):
-        if (t is not None or name == "src") and (not isinstance(t, torch.Tensor) or t.dtype != torch.float32):
+        if (t is not None or name == "src") and (not isinstance(t, torch.Tensor) or t.dtype != torch.float32) \
+                and not (name == "src" and _rows_dtype_ok(t, opt)):
             raise TypeError("%s must be a float32 tensor (incidence_gather has no bfloat16 form), got %s"
                             % (name, getattr(t, "dtype", type(t))))
     if src.dim() != 2:
@@ -1088,7 +1123,7 @@ def incidence_gather(csrptr_t, indices_t, src, weight=None, to="hyperedge", scal
                              % (name, M if to == "hyperedge" else N, t.numel()))
     _check_index(csrptr_t, "csrptr_t")
     _check_index(indices_t, "indices_t")
-    _check_feat(src, "src")
+    _check_feat(src, "src", bf16_ok=opt.incidence_bf16 == "rows")
     for name, t in (("weight", w), ("scale_a", scale_a), ("scale_b", scale_b)):
         if t is not None:
             _check_feat(t, name, device=src.device)
@@ -1107,7 +1142,7 @@ class _IncidenceDot(torch.autograd.Function):
     def forward(ctx, csrptr_t, indices_t, A, B, heads):
         plan = cached_plan(A.shape[0], csrptr_t, indices_t)
         ctx.save_for_backward(csrptr_t, indices_t, A if ctx.needs_input_grad[3] else None, B if ctx.needs_input_grad[2] else None)
-        ctx.N, ctx.heads = A.shape[0], heads
+        ctx.N, ctx.heads, ctx.dtypes = A.shape[0], heads, (A.dtype, B.dtype)
         return plan.incidence_dot(csrptr_t, indices_t, A, B, heads=heads)
 
     @staticmethod
@@ -1116,22 +1151,25 @@ class _IncidenceDot(torch.autograd.Function):
         plan = cached_plan(ctx.N, csrptr_t, indices_t)
         g = grad.contiguous()
         dA = dB = None
-        if ctx.needs_input_grad[2]:
-            dA = plan.gather_rows_incidence("vertex", csrptr_t, indices_t, B, g, heads=ctx.heads)
+        if ctx.needs_input_grad[2]:  # each gradient in its operand's dtype: the mixed forms of the hop where A and B differ
+            dA = _hop(plan, csrptr_t, indices_t, "vertex", B, g, None, None, ctx.heads, ctx.dtypes[0])
         if ctx.needs_input_grad[3]:
-            dB = plan.gather_rows_incidence("hyperedge", csrptr_t, indices_t, A, g, heads=ctx.heads)
+            dB = _hop(plan, csrptr_t, indices_t, "hyperedge", A, g, None, None, ctx.heads, ctx.dtypes[1])
         return None, None, dA, dB, None
 
 
-def incidence_dot(csrptr_t, indices_t, A, B, heads=1):
+def incidence_dot(csrptr_t, indices_t, A, B, heads=1, options=None):
     """The dot-product logit of every incidence p = (e, u): out[p] = <A[u], B[e]> for A [N, F] (a row per vertex) and B [M, F]
     (a row per hyperedge), [nnz] aligned with indices_t (hg_incidence_dot_f32).  heads = H > 1: A and B are [*, H * C],
     out[p, h] is the product over head h's columns and comes back [nnz, H].  Scaled by C ** -0.5 it is what
     incidence_softmax takes as incidence_score.  Differentiable in A and B: with g the incoming gradient,
-    dA = incidence_gather(B, g, to='vertex') and dB = incidence_gather(A, g, to='hyperedge').  float32 only."""
+    dA = incidence_gather(B, g, to='vertex') and dB = incidence_gather(A, g, to='hyperedge').  float32 only, unless
+    Options.incidence_bf16 = 'rows': A and B may each be bfloat16; out stays float32 -- the float32 call on A.float(),
+    B.float() bit for bit -- and each gradient comes back in its operand's dtype."""
+    opt = _opt(options)
     _heads(heads)
     for name, t in (("A", A), ("B", B)):
-        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32:
+        if not _rows_dtype_ok(t, opt):
             raise TypeError("%s must be a float32 tensor (incidence_dot has no bfloat16 form), got %s"
                             % (name, getattr(t, "dtype", type(t))))
     if not isinstance(csrptr_t, torch.Tensor) or not isinstance(indices_t, torch.Tensor):
@@ -1143,8 +1181,8 @@ def incidence_dot(csrptr_t, indices_t, A, B, heads=1):
         raise ValueError("the width %d is no multiple of heads = %d" % (A.shape[1], heads))
     _check_index(csrptr_t, "csrptr_t")
     _check_index(indices_t, "indices_t")
-    _check_feat(A, "A")
-    _check_feat(B, "B", device=A.device)
+    _check_feat(A, "A", bf16_ok=opt.incidence_bf16 == "rows")
+    _check_feat(B, "B", device=A.device, bf16_ok=opt.incidence_bf16 == "rows")
     if not (torch.is_grad_enabled() and (A.requires_grad or B.requires_grad)):
         return cached_plan(A.shape[0], csrptr_t, indices_t).incidence_dot(csrptr_t, indices_t, A, B, heads=heads)
     return _IncidenceDot.apply(csrptr_t, indices_t, A, B, heads)

@@ -546,10 +546,14 @@ class Plan:
         dst[e] = ((sum_{p=(e,u)} w[p] src[u]) * scaleA[e]) * scaleB[e] with src [N, F] and dst [M, F]; hop 1 / 'vertex' the
         mirror, src [M, F] and dst [N, F].  w: float32 [nnz] in H_T order ([nnz, H] with heads = H, column h weighing head
         h's columns), or None (unit weights); the scales have one factor per row of dst.  The schedule, kernels and bits
-        are those of aggregate_incidence's hop.  The first hop-1 call with w uploads the plan's permutation: not capturable."""
+        are those of aggregate_incidence's hop.  The first hop-1 call with w uploads the plan's permutation: not capturable.
+        src and out may each be float32 or bfloat16 (hg_gather_rows_incidence_heads_bf16); dst has src's dtype unless out says
+        otherwise.  w and the scales stay float32.  Sums are fp32 in the float32 call's order and a bfloat16 dst is rounded once:
+        the result equals the float32 call on src.float(), rounded where dst is bfloat16, bit for bit.  Where the bf16 lanes do
+        not exist (F % 4 or (F / heads) % 4 != 0, or data not 8- / 16-byte aligned) exactly that is run: widen, float32 call, round."""
         heads = _heads(heads)
         hop = _side(hop)
-        _check_feat(src, "src")
+        _check_feat(src, "src", bf16_ok=True)
         nsrc, ndst = (self.N, self.M) if hop == 0 else (self.M, self.N)
         if src.dim() != 2 or src.shape[0] != nsrc:
             raise ValueError("src must be [%d, F]" % nsrc)
@@ -562,19 +566,29 @@ class Plan:
                 if t.numel() != n:
                     raise ValueError("%s must have %d elements, got %d" % (name, n, t.numel()))
         if out is not None:
-            _check_feat(out, "out", device=src.device)
+            _check_feat(out, "out", device=src.device, bf16_ok=True)
             if tuple(out.shape) != (ndst, F):
                 raise ValueError("out must be [%d, %d]" % (ndst, F))
-        dst = out if out is not None else torch.empty((ndst, F), dtype=torch.float32, device=src.device)
+        dst = out if out is not None else torch.empty((ndst, F), dtype=src.dtype, device=src.device)
+        io = (_lib.HG_ROWS_SRC_BF16 if src.dtype == torch.bfloat16 else 0) | (_lib.HG_ROWS_DST_BF16 if dst.dtype == torch.bfloat16 else 0)
+        if io and not _bf16_lanes(F, heads, src, dst):
+            got = self.gather_rows_incidence(hop, csrptr_t, colind_t, src.float(), w, scaleA, scaleB, heads,
+                                             dst if dst.dtype == torch.float32 else None, workspace)
+            return got if got is dst else dst.copy_(got)  # copy_ rounds to nearest even, as the kernel's store does
         nbytes = self.incidence_workspace_bytes(F)
         if workspace is None:
             workspace = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=src.device)
         else:
             nbytes = workspace.numel() * workspace.element_size()
         with torch.cuda.device(src.device):
-            _lib.check(_lib.lib().hg_gather_rows_incidence_heads_f32(
-                self._h, hop, F, heads, _ptr(csrptr_t), _ptr(colind_t), _ptr(src), _ptr(w), _ptr(scaleA), _ptr(scaleB),
-                _ptr(dst), _ptr(workspace), nbytes, _stream_handle(src.device)))
+            if io:
+                _lib.check(_lib.lib().hg_gather_rows_incidence_heads_bf16(
+                    self._h, hop, F, heads, _ptr(csrptr_t), _ptr(colind_t), _ptr(src), _ptr(w), _ptr(scaleA), _ptr(scaleB),
+                    _ptr(dst), _ptr(workspace), nbytes, io, _stream_handle(src.device)))
+            else:
+                _lib.check(_lib.lib().hg_gather_rows_incidence_heads_f32(
+                    self._h, hop, F, heads, _ptr(csrptr_t), _ptr(colind_t), _ptr(src), _ptr(w), _ptr(scaleA), _ptr(scaleB),
+                    _ptr(dst), _ptr(workspace), nbytes, _stream_handle(src.device)))
         return dst
 
     def incidence_perm(self):
@@ -593,9 +607,14 @@ class Plan:
         float32 [nnz] aligned with colind_t, or None (unit weights).  xe_out ([M, F] float32) receives hop 1's table.
         heads = H > 1 (hg_aggr_incidence_heads_f32): v2e / e2v are [nnz, H] and head h weighs columns h F/H .. (h+1) F/H - 1.
         The first call with e2v builds and uploads the plan's permutation: not capturable (make one call before a
-        hipGraph capture)."""
+        hipGraph capture).
+        X may be bfloat16 (hg_aggr_incidence_heads_bf16): Y (and out) are then bfloat16, the weights, the scales and xe_out
+        stay float32.  Hop 1's table and every sum are fp32 in the float32 call's order, Y is rounded once: Y equals
+        aggregate_incidence(X.float(), ...).to(bfloat16) and xe_out the float32 call's, bit for bit.  Where the bf16 lanes do
+        not exist (F % 4 or (F / heads) % 4 != 0, data not 8- / 16-byte aligned) exactly that is run."""
         heads = _heads(heads)
-        _check_feat(X, "node_feat")
+        bf16 = isinstance(X, torch.Tensor) and X.dtype == torch.bfloat16
+        _check_feat(X, "node_feat", bf16_ok=True)
         if X.dim() != 2 or X.shape[0] != self.N:
             raise ValueError("node_feat must be [N = %d, F]" % self.N)
         F = X.shape[1]
@@ -609,17 +628,26 @@ class Plan:
                     raise ValueError("%s must have %d elements, got %d" % (name, n, t.numel()))
         for name, t, rows in (("xe_out", xe_out, self.M), ("out", out, self.N)):
             if t is not None:
-                _check_feat(t, name, device=X.device)
+                _check_feat(t, name, device=X.device, bf16_ok=bf16 and name == "out")
                 if tuple(t.shape) != (rows, F):
                     raise ValueError("%s must be [%d, %d]" % (name, rows, F))
-        Y = out if out is not None else torch.empty((self.N, F), dtype=torch.float32, device=X.device)
+        if out is not None and out.dtype != X.dtype:
+            raise TypeError("out must have node_feat's dtype %s, got %s" % (X.dtype, out.dtype))
+        if bf16 and not _bf16_lanes(F, heads, X, out, xe_out):
+            Y32 = self.aggregate_incidence(csrptr_t, colind_t, X.float(), v2e, e2v, degE, degV, W, xe_out, None, workspace, heads)
+            return Y32.to(torch.bfloat16) if out is None else out.copy_(Y32)
+        Y = out if out is not None else torch.empty((self.N, F), dtype=X.dtype, device=X.device)
         nbytes = self.incidence_workspace_bytes(F)
         if workspace is None:
             workspace = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=X.device)
         else:
             nbytes = workspace.numel() * workspace.element_size()
         with torch.cuda.device(X.device):
-            if heads == 1:
+            if bf16:
+                _lib.check(_lib.lib().hg_aggr_incidence_heads_bf16(
+                    self._h, F, heads, _ptr(csrptr_t), _ptr(colind_t), _ptr(X), _ptr(v2e), _ptr(e2v), _ptr(degE),
+                    _ptr(degV), _ptr(W), _ptr(xe_out), _ptr(Y), _ptr(workspace), nbytes, _stream_handle(X.device)))
+            elif heads == 1:
                 _lib.check(_lib.lib().hg_aggr_incidence_f32(
                     self._h, F, _ptr(csrptr_t), _ptr(colind_t), _ptr(X), _ptr(v2e), _ptr(e2v), _ptr(degE), _ptr(degV),
                     _ptr(W), _ptr(xe_out), _ptr(Y), _ptr(workspace), nbytes, _stream_handle(X.device)))
@@ -631,10 +659,13 @@ class Plan:
 
     def incidence_dot(self, csrptr_t, colind_t, A, B, out=None, heads=1):
         """out[p] = <A[u], B[e]> for every H_T entry p = (e, u) (hg_incidence_dot_f32): A [N, F], B [M, F].  heads = H > 1
-        (hg_incidence_dot_heads_f32): out [nnz, H], out[p, h] the product over head h's columns h F/H .. (h+1) F/H - 1."""
+        (hg_incidence_dot_heads_f32): out [nnz, H], out[p, h] the product over head h's columns h F/H .. (h+1) F/H - 1.
+        A and B may each be float32 or bfloat16 (hg_incidence_dot_heads_bf16); out is float32 and equals the float32 call on
+        A.float(), B.float() bit for bit (that call is what runs where F % 4, (F / heads) % 4 or the alignment rule out the
+        bf16 lanes)."""
         heads = _heads(heads)
-        _check_feat(A, "A")
-        _check_feat(B, "B", device=A.device)
+        _check_feat(A, "A", bf16_ok=True)
+        _check_feat(B, "B", device=A.device, bf16_ok=True)
         if A.dim() != 2 or B.dim() != 2 or A.shape[0] != self.N or B.shape[0] != self.M or A.shape[1] != B.shape[1]:
             raise ValueError("A must be [N = %d, F] and B [M = %d, F]" % (self.N, self.M))
         if A.shape[1] % heads:
@@ -645,8 +676,14 @@ class Plan:
             _check_feat(out, "out", device=A.device)
             if out.numel() != self.nnz * heads:
                 raise ValueError("out must have nnz * heads = %d elements" % (self.nnz * heads))
+        io = (_lib.HG_DOT_A_BF16 if A.dtype == torch.bfloat16 else 0) | (_lib.HG_DOT_B_BF16 if B.dtype == torch.bfloat16 else 0)
+        if io and not _bf16_lanes(A.shape[1], heads, A, B):
+            return self.incidence_dot(csrptr_t, colind_t, A.float(), B.float(), out, heads)
         with torch.cuda.device(A.device):
-            if heads == 1:
+            if io:
+                _lib.check(_lib.lib().hg_incidence_dot_heads_bf16(self._h, A.shape[1], heads, _ptr(csrptr_t), _ptr(colind_t),
+                                                                  _ptr(A), _ptr(B), _ptr(out), io, _stream_handle(A.device)))
+            elif heads == 1:
                 _lib.check(_lib.lib().hg_incidence_dot_f32(self._h, A.shape[1], _ptr(csrptr_t), _ptr(colind_t), _ptr(A),
                                                            _ptr(B), _ptr(out), _stream_handle(A.device)))
             else:
@@ -1258,6 +1295,14 @@ def _check_index(t, name):
         raise RuntimeError("%s must be on a GPU (no CPU fallback in this backend)" % name)
     if not t.is_contiguous():
         raise RuntimeError("%s must be contiguous" % name)
+
+
+def _bf16_lanes(F, heads, *rows):
+    """Whether the bf16 entries of the incidence path take these row arrays (None: absent): whole four-column lanes inside one
+    head, bfloat16 data 8-byte and float32 data 16-byte aligned (include/hg_aggr.h)."""
+    if F % 4 or (F // heads) % 4:
+        return False
+    return all(t is None or t.data_ptr() % (8 if t.dtype == torch.bfloat16 else 16) == 0 for t in rows)
 
 
 def _check_feat(t, name, device=None, bf16_ok=False):

@@ -710,6 +710,50 @@ HG_API int hg_hyperedge_dot_heads_f32(const hg_plan *plan, int32_t F, int32_t he
                                       const float *wb, float *out, hg_stream_t stream);
 HG_API int hg_rows_dot_f32(int64_t nrows, int32_t F, const float *A, const float *B, float *out, hg_stream_t stream);
 
+/* ---- bf16 feature rows on the incidence path -----------------------------------------------------------------------------------
+ * The weighted row gather, the two-hop aggregation and the per-incidence dot with feature rows in bf16, on hg_aggr_fused_bf16's
+ * contract -- fp32 in between, the fp32 call's order, one rounding:
+ *   - per-incidence weights, scaleA / scaleB, degE / degV / W and the dot's out stay fp32;
+ *   - a bf16 row is widened in the load (exact); lane accumulators, wave-task partial rows, the workspace and hop 1's table are
+ *     fp32, summed on the fp32 entry's schedule, lanes and order; a bf16 destination is rounded once, to nearest even (NaN
+ *     stays NaN).
+ * So each entry equals its _f32 twin called on 16-byte aligned widened copies of the bf16 arrays: fp32 outputs bit for bit,
+ * bf16 outputs the fp32 output rounded to bf16, bit for bit.  Only 16-byte lanes (four columns: 8 bytes of bf16) exist for
+ * bf16 rows: F % 4 == 0, C = F / heads with C % 4 == 0, bf16 row arrays 8-byte aligned and fp32 row arrays 16-byte aligned
+ * (where the fp32 twin takes those lanes too); anything else is HG_ERR_UNSUPPORTED, decided after the twin's own refusals,
+ * in the twin's order, nothing launched -- widen, call the fp32 entry and round instead.
+ * hg_gather_rows_incidence_heads_bf16: hg_gather_rows_incidence_heads_f32 with io saying which of src / dst holds bf16 rows:
+ *   HG_ROWS_SRC_BF16, HG_ROWS_DST_BF16 or both; io = 0 (or another bit) is HG_ERR_INVALID, decided with hop: use the fp32
+ *   entry.  w NULL: the unweighted instances.  The pinned latency schedule, the LDS check and the workspace
+ *   (hg_aggr_incidence_workspace_bytes(plan, F)) are the fp32 entry's; streaming stores are chosen on the bytes of a row of
+ *   dst, which moves no bits.
+ * hg_aggr_incidence_heads_bf16: hg_aggr_incidence_heads_f32 with X and Y bf16 (heads = 1: hg_aggr_incidence_f32): hop 1 reads
+ *   bf16 rows into the fp32 table -- Xe_out if given, else the workspace; Xe_out has the fp32 call's bits -- and hop 2
+ *   rounds its fp32 sums into Y.  v2e_val = e2v_val = NULL gives the bits of hg_aggr_fused_bf16 on the pull kernels of the
+ *   same schedule.
+ * hg_incidence_dot_heads_bf16: hg_incidence_dot_heads_f32 (heads = 1: hg_incidence_dot_f32) with io saying which of A / B
+ *   holds bf16 rows: HG_DOT_A_BF16, HG_DOT_B_BF16 or both; io = 0 is HG_ERR_INVALID, decided first.  out is fp32
+ *   [nnz, heads]; lane count, run length, fma chain and butterfly are the fp32 kernel's.
+ * Not covered: bf16 weights, the attention instances (hg_aggr_incidence_attention_heads_f32), the segment kernels,
+ *   hg_hyperedge_dot_heads_f32 and hg_rows_dot_f32.
+ * Detect these entries by their exported symbols (HG_AGGR_VERSION does not change). */
+#define HG_ROWS_SRC_BF16 1
+#define HG_ROWS_DST_BF16 2
+#define HG_DOT_A_BF16 1
+#define HG_DOT_B_BF16 2
+HG_API int hg_gather_rows_incidence_heads_bf16(const hg_plan *plan, int32_t hop, int32_t F, int32_t heads,
+                                               const int32_t *csrptr_t, const int32_t *colind_t, const void *src,
+                                               const float *w, const float *scaleA, const float *scaleB, void *dst,
+                                               void *workspace, size_t workspace_bytes, int32_t io, hg_stream_t stream);
+HG_API int hg_aggr_incidence_heads_bf16(const hg_plan *plan, int32_t F, int32_t heads, const int32_t *csrptr_t,
+                                        const int32_t *colind_t, const uint16_t *X, const float *v2e_val,
+                                        const float *e2v_val, const float *degE, const float *degV, const float *W,
+                                        float *Xe_out, uint16_t *Y, void *workspace, size_t workspace_bytes,
+                                        hg_stream_t stream);
+HG_API int hg_incidence_dot_heads_bf16(const hg_plan *plan, int32_t F, int32_t heads, const int32_t *csrptr_t,
+                                       const int32_t *colind_t, const void *A, const void *B, float *out, int32_t io,
+                                       hg_stream_t stream);
+
 /* first_aggr = "max" pieces (hgnnaggr_max, source/hgnnaggr/hgnnaggr_cuda.cu:144-208).
  * hg_gather_max_f32: Xe[e,k] = (max_{u in e} X[u,k], start -1e5, strict >) * (degE[e]*W[e]),
  * record[e,k] = winning vertex (0 if none).  The second hop is hg_gather_rows_f32(hop = 1).
