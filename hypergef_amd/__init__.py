@@ -11,10 +11,10 @@ from .balancer import balance_schedule  # noqa: F401
 from .hypergraph import HyperGraph  # noqa: F401
 from .ops import (HGNNAggr, HGNNAggrIncidence, HGNNAggrLinear, UniGNNConv, UniGNNConvdeg,  # noqa: F401
                   UniGNNConvLinear, hgnnaggr_linear, incidence_aggr, incidence_attention_aggr, incidence_dot,
-                  incidence_gather, incidence_softmax, incidence_sum)
+                  incidence_gather, incidence_softmax, incidence_sum, reduce_aggr)
 from .plan import Plan  # noqa: F401
 
-from .models import HypergraphAttnConv  # noqa: F401
+from .models import HypergraphAttnConv, HyperGsysUniSAGE  # noqa: F401
 
 # The reference builds two top-level extension modules (setup.py:18,32-33).  They ship as real
 # files next to this package (`hgnnaggr.py`, `unignnaggr.py`: repo root, or site-packages after

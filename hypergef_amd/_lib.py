@@ -50,7 +50,10 @@ SYMBOLS = (
     "hg_incidence_attention_stats_heads_f32", "hg_aggr_incidence_attention_heads_f32",
     "hg_gather_rows_attention_heads_f32",
     "hg_gather_rows_incidence_heads_bf16", "hg_aggr_incidence_heads_bf16", "hg_incidence_dot_heads_bf16",
+    "hg_gather_rows_reduce_workspace_bytes", "hg_gather_rows_reduce_f32", "hg_gather_rows_select_f32",
 )
+HG_REDUCE_MAX = 1
+HG_REDUCE_MIN = 2
 HG_ROWS_SRC_BF16 = 1
 HG_ROWS_DST_BF16 = 2
 HG_DOT_A_BF16 = 1
@@ -281,6 +284,13 @@ def lib():
         L.hg_aggr_incidence_heads_bf16.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]
         L.hg_incidence_dot_heads_bf16.restype = ctypes.c_int
         L.hg_incidence_dot_heads_bf16.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, i32, vp]
+    if hasattr(L, "hg_gather_rows_reduce_f32"):  # likewise: max / min in the row gather and the select-gather backward
+        L.hg_gather_rows_reduce_workspace_bytes.restype = sz
+        L.hg_gather_rows_reduce_workspace_bytes.argtypes = [vp, i32]
+        L.hg_gather_rows_reduce_f32.restype = ctypes.c_int
+        L.hg_gather_rows_reduce_f32.argtypes = [vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]
+        L.hg_gather_rows_select_f32.restype = ctypes.c_int
+        L.hg_gather_rows_select_f32.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, vp, sz, vp]
     L.hg_aggr_push_groups_f32.restype = ctypes.c_int
     L.hg_aggr_push_groups_f32.argtypes = [i32, i32, i32, i64, vp, vp, vp, vp, vp, vp,
                                           vp, vp, vp, vp, vp, vp]

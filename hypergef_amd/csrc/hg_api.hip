@@ -2067,6 +2067,129 @@ int hg_gather_rows_incidence_heads_bf16(const hg_plan *plan, int32_t hop, int32_
                                workspace_bytes, io, stream);
 }
 
+// ---- max / min in the row gather and their select-gather backward ------------------------------------------------------
+// Workspace of both entries: [float partial rows][int32 partial rows], each sized for the hop and schedule (default or
+// latency) with the most partial slots; the select uses the float half only.
+static size_t reduce_part_bytes(const hg_plan *p, int32_t F) {
+  int32_t nslots = 0;
+  for (int h = 0; h < 2; h++) nslots = std::max(nslots, std::max(p->sched[h].nslots, p->sched_lat[h].nslots));
+  return round256((size_t)nslots * F * sizeof(float) + 16);  // + 16: fixup_rows_kernel's lanes may load past the last row's end
+}
+
+size_t hg_gather_rows_reduce_workspace_bytes(const hg_plan *p, int32_t F) {
+  if (!p || F <= 0) return 0;
+  return 2 * reduce_part_bytes(p, F);
+}
+
+// The refusals both entries share, in the order include/hg_aggr.h gives; op = 0: the select (no op to check).
+static int check_reduce_call(const char *who, const hg_plan *plan, int32_t hop, int32_t F, int32_t op, bool arrays_ok,
+                             const void *workspace, size_t workspace_bytes) {
+  if (!plan) {
+    hg::set_error(std::string(who) + ": null plan");
+    return HG_ERR_INVALID;
+  }
+  if (hop != 0 && hop != 1) {
+    hg::set_error(std::string(who) + ": hop must be 0 (to the hyperedges) or 1 (to the vertices)");
+    return HG_ERR_INVALID;
+  }
+  if (op != 0 && op != HG_REDUCE_MAX && op != HG_REDUCE_MIN) {
+    hg::set_error(std::string(who) + ": op must be HG_REDUCE_MAX or HG_REDUCE_MIN");
+    return HG_ERR_INVALID;
+  }
+  if (plan->opts.flags & HG_PLAN_HOST_ONLY) {
+    hg::set_error(std::string(who) + ": plan was built with HG_PLAN_HOST_ONLY and holds no device arrays");
+    return HG_ERR_UNSUPPORTED;
+  }
+  if (F <= 0 || (int64_t)std::max(plan->N, plan->M) * F >= ((int64_t)1 << 40)) {
+    hg::set_error(std::string(who) + ": feature width must be positive and the feature matrix below 2^40 elements");
+    return HG_ERR_INVALID;
+  }
+  if (!arrays_ok) {
+    hg::set_error(std::string(who) + ": null array");
+    return HG_ERR_INVALID;
+  }
+  if (!weights_fit_lds(plan)) {  // the panels stage an entry's position where the weighted instances stage its weight
+    hg::set_error(std::string(who) + ": panel_rows / panel_nnz leave no LDS for the staged positions (160 KiB per workgroup)");
+    return HG_ERR_UNSUPPORTED;
+  }
+  const size_t need = hg_gather_rows_reduce_workspace_bytes(plan, F);
+  if (!workspace || workspace_bytes < need) {
+    hg::set_error(std::string(who) + ": workspace too small: need " + std::to_string(need) + " bytes, got " +
+                  std::to_string(workspace_bytes));
+    return HG_ERR_WORKSPACE;
+  }
+  if (reinterpret_cast<uintptr_t>(workspace) & 255) {
+    hg::set_error(std::string(who) + ": workspace must be 256-byte aligned");
+    return HG_ERR_INVALID;
+  }
+  return HG_OK;
+}
+
+// walk: the CSR the kernel walks (0: H_T, 1: H).  rmode 1 / 2: src -> (dst, arg_out); 3: (src = gs, arg_in) -> dst.
+static int reduce_hop(const hg_plan *plan, int walk, int rmode, int32_t F, const int32_t *csrptr_t, const int32_t *colind_t,
+                      const float *src, const float *scaleA, const float *scaleB, float *dst, int32_t *arg_out,
+                      const int32_t *arg_in, void *workspace, hipStream_t stream) {
+  int rc;
+  const int32_t *perm = nullptr;
+  if (walk == 1 && (rc = get_incidence_perm(plan, true, &perm)) != HG_OK) return rc;
+  int kind = 1;  // the panels + wave-task schedule, or the latency schedule where it is pinned for this width (incidence_hop)
+  {
+    hg_plan *mp = const_cast<hg_plan *>(plan);
+    std::lock_guard<std::mutex> lock(mp->auto_mu);
+    auto it = mp->hop_kernel.find(F);
+    if (it != mp->hop_kernel.end()) kind = walk == 0 ? it->second % 3 : (it->second / 3) % 3;
+  }
+  const hg::Sched &s = (kind == 2 && plan->has_lat) ? plan->sched_lat[walk] : plan->sched[walk];
+  hg::ReduceGatherArgs a;
+  a.ptr = walk == 0 ? csrptr_t : plan->d_ptr_v;
+  a.ind = walk == 0 ? colind_t : plan->d_ind_v;
+  a.src = src;
+  a.dst = dst;
+  a.scaleA = scaleA;
+  a.scaleB = scaleB;
+  a.partial = static_cast<float *>(workspace);
+  a.ipartial = reinterpret_cast<int32_t *>(static_cast<char *>(workspace) + reduce_part_bytes(plan, F));
+  a.scale_map = nullptr;
+  a.dst_map = nullptr;
+  a.panels = s.d_panels;
+  a.tasks = s.d_tasks;
+  a.npanels = (int32_t)s.panels.size();
+  a.ntasks = (int32_t)s.tasks.size();
+  a.n_task_blocks = (a.ntasks + 3) / 4;
+  a.F = F;
+  a.panel_rows = plan->opts.panel_rows;
+  a.panel_nnz = plan->opts.panel_nnz;
+  a.xcd_remap = (plan->opts.flags & HG_PLAN_NO_XCD_REMAP) ? 0 : 1;
+  a.pperm = perm;
+  a.arg_out = arg_out;
+  a.arg_in = arg_in;
+  const bool vec4 = F % 4 == 0 && aligned16(src) && aligned16(dst) && aligned16(rmode == 3 ? (const void *)arg_in : (const void *)arg_out);
+  const hipError_t e = hg::launch_gather_reduce(a, rmode, (int)s.fixups.size(), s.n_fix_l1, s.d_fixups, vec4, stream);
+  if (e != hipSuccess) return hip_fail("gather_rows reduce launch", e);
+  return HG_OK;
+}
+
+int hg_gather_rows_reduce_f32(const hg_plan *plan, int32_t hop, int32_t F, int32_t op, const int32_t *csrptr_t,
+                              const int32_t *colind_t, const float *src, const float *scaleA, const float *scaleB,
+                              float *dst, int32_t *arg_out, void *workspace, size_t workspace_bytes, hg_stream_t stream) {
+  const bool arrays_ok = csrptr_t && (!plan || plan->nnz == 0 || colind_t) && src && dst && arg_out;
+  int rc = check_reduce_call("hg_gather_rows_reduce_f32", plan, hop, F, op == 0 ? -1 : op, arrays_ok, workspace, workspace_bytes);
+  if (rc != HG_OK) return rc;
+  return reduce_hop(plan, hop, op, F, csrptr_t, colind_t, src, scaleA, scaleB, dst, arg_out, nullptr, workspace,
+                    static_cast<hipStream_t>(stream));
+}
+
+int hg_gather_rows_select_f32(const hg_plan *plan, int32_t hop, int32_t F, const int32_t *csrptr_t, const int32_t *colind_t,
+                              const float *gs, const int32_t *arg, float *dsrc, void *workspace, size_t workspace_bytes,
+                              hg_stream_t stream) {
+  const bool arrays_ok = csrptr_t && (!plan || plan->nnz == 0 || colind_t) && gs && arg && dsrc;
+  int rc = check_reduce_call("hg_gather_rows_select_f32", plan, hop, F, 0, arrays_ok, workspace, workspace_bytes);
+  if (rc != HG_OK) return rc;
+  // the gradient of hop's source rows is gathered over the other hop's CSR
+  return reduce_hop(plan, 1 - hop, 3, F, csrptr_t, colind_t, gs, nullptr, nullptr, dsrc, nullptr, arg, workspace,
+                    static_cast<hipStream_t>(stream));
+}
+
 int hg_incidence_dot_f32(const hg_plan *plan, int32_t F, const int32_t *csrptr_t, const int32_t *colind_t,
                          const float *A, const float *B, float *out, hg_stream_t stream) {
   int rc = check_call(plan, F, nullptr, 0, kSizeLater);

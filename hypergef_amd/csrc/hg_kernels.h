@@ -61,6 +61,17 @@ struct AttnGatherArgs : GatherArgs {
   int32_t heads = 1, C = 0;
 };
 
+// GatherArgs for gather_rows_reduce_kernel (hg_gather_rows_reduce_f32, hg_gather_rows_select_f32), fp32 rows, no
+// scale_map / dst_map.  An entry's position is its H_T position: its own index q in the walked CSR, or pperm[q].
+// max / min: arg_out [nrows, F] receives the winner's position (-1: empty row), ipartial [nslots, F] holds the positions
+// beside partial's values.  select: src is gs, arg_in [rows of src, F] the forward's arg; scales are not applied.
+struct ReduceGatherArgs : GatherArgs {
+  const int32_t *pperm = nullptr;
+  int32_t *arg_out = nullptr;
+  int32_t *ipartial = nullptr;
+  const int32_t *arg_in = nullptr;
+};
+
 // What happens to an aggregated row t = Aggr(X)[v] on its way through the linear epilogue:
 //   t' = ca * t + cb * R[v]   (R null: t' = ca * t),   T_out[v] = t' if wanted,
 //   Y[v] = act(t' * Wlin^T),  act = relu or identity.
@@ -188,6 +199,10 @@ hipError_t launch_gather_heads(const HeadsGatherArgs &a, int nfix, int nfix_l1, 
 // the attention instances: launch_gather_heads' lanes and order of summation, the weights formed from a's scores and statistics
 hipError_t launch_gather_attention(const AttnGatherArgs &a, int nfix, int nfix_l1, const Fixup *fixups, bool vec4, bool lane4,
                                    hipStream_t stream);
+// rmode 1 / 2: the max / min instances and their fixups; 3: the select instances and the sum gather's fixups.  Lanes as
+// launch_gather's (vec4: F % 4 == 0 and src, dst, arg and both partial tables 16-byte aligned); LDS as the weighted instances'.
+hipError_t launch_gather_reduce(const ReduceGatherArgs &a, int rmode, int nfix, int nfix_l1, const Fixup *fixups, bool vec4,
+                                hipStream_t stream);
 // the LDS one of their workgroups asks for: the unweighted panel plus one (stat_row: three) float per row and head
 size_t attn_gather_lds_bytes(int32_t panel_rows, int32_t panel_nnz, int32_t heads, bool stat_row);
 // out[p, h] = <A[ind[p], hC .. (h+1)C), B[e, hC .. (h+1)C)>, out [nnz, H].  lane4: C % 4 == 0 and A, B 16-byte aligned.

@@ -422,6 +422,271 @@ __global__ __launch_bounds__(256) void fixup_rows_kernel(const GatherArgs a, con
   else RD::store_n(acc, dst + drow * F + col, a.F - col);
 }
 
+// ---- comparison reductions in the row gather and their select-gather backward ------------------------------------------
+// gather_rows_reduce_kernel is gather_rows_kernel's schedule -- the same panels, wave tasks, partial slots and LDS carve-up
+// (the WH instances': an entry's position where those keep its weight's) -- with another reducer.  RMODE 1 / 2 (max / min,
+// hg_gather_rows_reduce_f32): a lane carries, per column, the winning value and the winner's position in indices_t (an
+// entry's own index on H_T, perm[index] on H), from (-inf / +inf, kNoPos).  An entry (x, p) replaces (v, q) where x > v
+// (x < v), or x == v and p < q: -0.0 ties +0.0, the smallest position wins a tie, and an entry of -inf beats the start
+// because any position is below kNoPos -- a non-empty row always has a winner.  The order is total, so the lane's walk, the
+// butterfly over a wave task's row groups and the fixups over partial slots give the same winner in whatever order they
+// meet the entries: every schedule writes the same bits.  The value is never computed with, only copied, then scaled as the
+// sum is: dst = (src[ind[p*]] * scaleA) * scaleB, arg = p*; an empty row gets +0.0 and -1, no scale.  NaN: unspecified.
+// RMODE 3 (select, hg_gather_rows_select_f32): the sum gather over the other hop's CSR with a select per column, src = gs
+// and arg_in = the forward's arg, acc += (arg_in[ind[q], c] == pos(q)) ? gs[ind[q], c] : 0, gs and arg loaded side by side:
+// the sum gather's order of addition, float partial slots, fixup_rows_kernel.
+constexpr int32_t kNoPos = 0x7fffffff;
+template <bool MAX> __device__ __forceinline__ bool beats(float x, int32_t p, float v, int32_t q) {
+  return (MAX ? x > v : x < v) || (x == v && p < q);
+}
+template <int VEC> struct Lane;  // a lane's VEC columns as arrays, floats and int32 positions
+template <> struct Lane<1> {
+  __device__ __forceinline__ static void unpack(const Vec<1> &v, float (&f)[1]) { f[0] = v.x; }
+  __device__ __forceinline__ static Vec<1> pack(const float (&f)[1]) { return Vec<1>{f[0]}; }
+  __device__ __forceinline__ static void iload(const int32_t *p, int32_t (&o)[1]) { o[0] = *p; }
+  __device__ __forceinline__ static void istore(int32_t *p, const int32_t (&o)[1]) { *p = o[0]; }
+};
+template <> struct Lane<4> {
+  __device__ __forceinline__ static void unpack(const Vec<4> &v, float (&f)[4]) {
+    f[0] = v.v.x, f[1] = v.v.y, f[2] = v.v.z, f[3] = v.v.w;
+  }
+  __device__ __forceinline__ static Vec<4> pack(const float (&f)[4]) { return Vec<4>{make_float4(f[0], f[1], f[2], f[3])}; }
+  __device__ __forceinline__ static void iload(const int32_t *p, int32_t (&o)[4]) {
+    const int4 t = *reinterpret_cast<const int4 *>(p);
+    o[0] = t.x, o[1] = t.y, o[2] = t.z, o[3] = t.w;
+  }
+  __device__ __forceinline__ static void istore(int32_t *p, const int32_t (&o)[4]) {
+    *reinterpret_cast<int4 *>(p) = make_int4(o[0], o[1], o[2], o[3]);
+  }
+};
+
+template <int LPR, int VEC, int RMODE>
+__global__ __launch_bounds__(256) void gather_rows_reduce_kernel(const ReduceGatherArgs a) {
+  static_assert(RMODE >= 1 && RMODE <= 3, "max, min or select");
+  constexpr bool SEL = RMODE == 3, MAX = RMODE == 1;
+  constexpr int U = 4;
+  constexpr int G = 64 / LPR;
+  constexpr int NG = 256 / LPR;
+  using V = Vec<VEC>;
+  using L = Lane<VEC>;
+  extern __shared__ int32_t smem[];
+  const float *src = static_cast<const float *>(a.src);
+  float *dst = static_cast<float *>(a.dst);
+
+  const int tid = threadIdx.x;
+  const int gl = tid & (LPR - 1);
+  const int col = (blockIdx.y * LPR + gl) * VEC;
+  const bool col_ok = col < a.F;
+  const int64_t F = a.F;
+  int b = blockIdx.x;
+
+  float bv[VEC];    // max / min: the winner so far
+  int32_t bp[VEC];  // and its position
+  V acc;            // select: the sum so far
+  auto reset = [&]() {
+#pragma unroll
+    for (int i = 0; i < VEC; i++) bv[i] = MAX ? -__builtin_inff() : __builtin_inff(), bp[i] = kNoPos;
+    acc = V::zero();
+  };
+  // one gathered entry: its row (of src, or of gs), its position, and for the select the forward's arg row
+  auto take = [&](const V &v, const int32_t (&ar)[VEC], int32_t pos, bool ok) {
+    float f[VEC];
+    L::unpack(v, f);
+    if constexpr (SEL) {
+#pragma unroll
+      for (int i = 0; i < VEC; i++) f[i] = (ok && ar[i] == pos) ? f[i] : 0.f;
+      acc.add(L::pack(f));
+    } else {
+#pragma unroll
+      for (int i = 0; i < VEC; i++)
+        if (ok && beats<MAX>(f[i], pos, bv[i], bp[i])) bv[i] = f[i], bp[i] = pos;
+    }
+  };
+  // a finished row: scaled value and winner (an empty row: +0.0 and -1, no scale), or the selected sum
+  auto store_row = [&](int64_t drow, float sa, float sb) {
+    if constexpr (SEL) {
+      acc.store(dst + drow * F + col);
+    } else {
+      float f[VEC];
+      int32_t o[VEC];
+#pragma unroll
+      for (int i = 0; i < VEC; i++) {
+        const bool any = bp[i] != kNoPos;
+        f[i] = any ? (bv[i] * sa) * sb : 0.f;
+        o[i] = any ? bp[i] : -1;
+      }
+      L::pack(f).store(dst + drow * F + col);
+      L::istore(a.arg_out + drow * F + col, o);
+    }
+  };
+  reset();
+
+  if (b < a.n_task_blocks) {
+    const int t = __builtin_amdgcn_readfirstlane(b * 4 + (tid >> 6));
+    if (t >= a.ntasks) return;
+    const Task tk = a.tasks[t];
+    const int g = (tid & 63) / LPR;
+    for (int p = tk.beg + g; p < tk.end; p += G * U) {
+      V v[U];
+      int32_t ar[U][VEC], ps[U];
+#pragma unroll
+      for (int k = 0; k < U; k++) {
+        const int q = p + k * G;
+        const bool ok = col_ok && q < tk.end;
+        const int64_t idx = ok ? a.ind[q] : 0;
+        ps[k] = ok ? (a.pperm ? a.pperm[q] : q) : kNoPos;
+        v[k] = ok ? V::load(src + idx * F + col) : V::zero();
+#pragma unroll
+        for (int i = 0; i < VEC; i++) ar[k][i] = -1;
+        if constexpr (SEL) {
+          if (ok) L::iload(a.arg_in + idx * F + col, ar[k]);
+        }
+      }
+#pragma unroll
+      for (int k = 0; k < U; k++) take(v[k], ar[k], ps[k], ps[k] != kNoPos);
+    }
+    // across the row groups: the select adds as the sum gather does; max / min combine (value, position) by the same rule
+#pragma unroll
+    for (int off = LPR; off < 64; off <<= 1) {
+      if constexpr (SEL) {
+        acc.xor_reduce(off);
+      } else {
+#pragma unroll
+        for (int i = 0; i < VEC; i++) {
+          const float ov = __shfl_xor(bv[i], off, 64);
+          const int32_t op = __shfl_xor(bp[i], off, 64);
+          if (beats<MAX>(ov, op, bv[i], bp[i])) bv[i] = ov, bp[i] = op;
+        }
+      }
+    }
+    if (g == 0 && col_ok) {
+      if (tk.slot < 0) {
+        store_row(tk.row, a.scaleA ? a.scaleA[tk.row] : 1.f, a.scaleB ? a.scaleB[tk.row] : 1.f);
+      } else if constexpr (SEL) {
+        acc.store(a.partial + (int64_t)tk.slot * F + col);
+      } else {
+        L::pack(bv).store(a.partial + (int64_t)tk.slot * F + col);
+        L::istore(a.ipartial + (int64_t)tk.slot * F + col, bp);
+      }
+    }
+    return;
+  }
+
+  b -= a.n_task_blocks;
+  if (a.xcd_remap) {  // as gather_rows_kernel: each XCD one contiguous run of panels
+    const int x = b & 7, i = b >> 3;
+    const int cpx = a.npanels >> 3, rem = a.npanels & 7;
+    b = x * cpx + (x < rem ? x : rem) + i;
+  }
+  const Panel pn = a.panels[b];
+  int32_t *sptr = smem;                                            // [panel_rows + 1]
+  float *sA = reinterpret_cast<float *>(smem + a.panel_rows + 1);  // [panel_rows]
+  float *sB = sA + a.panel_rows;                                   // [panel_rows]
+  int32_t *sind = reinterpret_cast<int32_t *>(sB + 2 * a.panel_rows);  // [panel_nnz] (gather_rows_kernel's layout)
+  int32_t *spos = sind + a.panel_nnz;                              // [panel_nnz]: the entries' positions, where perm gives them
+
+  for (int i = tid; i <= pn.nrows; i += 256) sptr[i] = a.ptr[pn.row0 + i] - pn.nnz0;
+  for (int i = tid; i < pn.nrows; i += 256) {
+    sA[i] = a.scaleA ? a.scaleA[pn.row0 + i] : 1.f;
+    sB[i] = a.scaleB ? a.scaleB[pn.row0 + i] : 1.f;
+  }
+  for (int i = tid; i < pn.nnz_cnt; i += 256) sind[i] = a.ind[pn.nnz0 + i];
+  if (a.pperm)
+    for (int i = tid; i < pn.nnz_cnt; i += 256) spos[i] = a.pperm[pn.nnz0 + i];
+  __syncthreads();
+
+  const int g = tid / LPR;
+  const int rpg = (pn.nrows + NG - 1) / NG;
+  int r = min(g * rpg, pn.nrows);
+  const int re = min(r + rpg, pn.nrows);
+  if (r >= re || !col_ok) return;
+
+  int pos = sptr[r];
+  const int stop = sptr[re];
+  int row_end = sptr[r + 1];
+  while (pos < stop) {  // the flat walk is in position order
+    const int n = min(U, stop - pos);
+    V v[U];
+    int32_t ar[U][VEC];
+#pragma unroll
+    for (int k = 0; k < U; k++) {
+      const int64_t idx = sind[pos + min(k, n - 1)];
+      v[k] = V::load(src + idx * F + col);
+#pragma unroll
+      for (int i = 0; i < VEC; i++) ar[k][i] = -1;
+      if constexpr (SEL) L::iload(a.arg_in + idx * F + col, ar[k]);
+    }
+#pragma unroll
+    for (int k = 0; k < U; k++) {
+      if (k < n) {
+        while (row_end <= pos + k) {
+          store_row(pn.row0 + r, sA[r], sB[r]);
+          reset();
+          r++;
+          row_end = sptr[r + 1];
+        }
+        take(v[k], ar[k], a.pperm ? spos[pos + k] : pn.nnz0 + pos + k, true);
+      }
+    }
+    pos += n;
+  }
+  while (r < re) {
+    store_row(pn.row0 + r, sA[r], sB[r]);
+    reset();
+    r++;
+  }
+}
+
+// The fixups of a max / min gather: the winner among a row's partial slots by the same rule, slot order immaterial; a
+// first-level fixup (pad > 0) leaves (value, position) in slot pad - 1 of both tables for the final one.
+template <int LPR, int VEC, bool MAX>
+__global__ __launch_bounds__(256) void fixup_rows_reduce_kernel(const ReduceGatherArgs a, const Fixup *fixups, int nfix) {
+  using V = Vec<VEC>;
+  using L = Lane<VEC>;
+  const int tid = threadIdx.x;
+  const int gl = tid & (LPR - 1);
+  const int col = (blockIdx.y * LPR + gl) * VEC;
+  const int f = blockIdx.x * (256 / LPR) + tid / LPR;
+  if (f >= nfix || col >= a.F) return;
+  const Fixup fx = fixups[f];
+  const int64_t F = a.F;
+  const float *pv = a.partial + (int64_t)fx.first * F + col;
+  const int32_t *pp = a.ipartial + (int64_t)fx.first * F + col;
+  float bv[VEC];
+  int32_t bp[VEC];
+#pragma unroll
+  for (int i = 0; i < VEC; i++) bv[i] = MAX ? -__builtin_inff() : __builtin_inff(), bp[i] = kNoPos;
+  for (int k = 0; k < fx.count; k += 4) {  // four slots' loads in flight
+    float x[4][VEC];
+    int32_t p[4][VEC];
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+      const int64_t s = min(k + j, fx.count - 1);  // past the end: the last slot again, which changes nothing
+      L::unpack(V::load(pv + s * F), x[j]);
+      L::iload(pp + s * F, p[j]);
+    }
+#pragma unroll
+    for (int j = 0; j < 4; j++)
+#pragma unroll
+      for (int i = 0; i < VEC; i++)
+        if (beats<MAX>(x[j][i], p[j][i], bv[i], bp[i])) bv[i] = x[j][i], bp[i] = p[j][i];
+  }
+  if (fx.pad > 0) {
+    L::pack(bv).store(a.partial + (int64_t)(fx.pad - 1) * F + col);
+    L::istore(a.ipartial + (int64_t)(fx.pad - 1) * F + col, bp);
+    return;
+  }
+  const float sa = a.scaleA ? a.scaleA[fx.row] : 1.f, sb = a.scaleB ? a.scaleB[fx.row] : 1.f;
+  int32_t o[VEC];
+#pragma unroll
+  for (int i = 0; i < VEC; i++) {  // a split row has entries: every column has a winner
+    bv[i] = (bv[i] * sa) * sb;
+    o[i] = bp[i];
+  }
+  L::pack(bv).store(static_cast<float *>(a.dst) + (int64_t)fx.row * F + col);
+  L::istore(a.arg_out + (int64_t)fx.row * F + col, o);
+}
+
 // out[p] = <A[ind[p], :], B[e, :]> for every entry p of the CSR (ptr, ind), e the row that holds p: the gradient of
 // a per-entry weight of hg_aggr_incidence_f32.  Work is cut by entries, not rows (a power-law row reaches 4096
 // entries): a lane group of LPR lanes owns kDotRun consecutive entries.  It finds the row of its first entry by a
@@ -2564,6 +2829,56 @@ hipError_t launch_gather_attention(const AttnGatherArgs &a, int nfix, int nfix_l
     HG_CASE(64)
   }
 #undef HG_CASE
+  return hipErrorInvalidValue;
+}
+
+template <int LPR, int VEC, int RMODE>
+static hipError_t launch_gather_reduce_t(const ReduceGatherArgs &a, int nfix, int nfix_l1, const Fixup *fixups, hipStream_t stream) {
+  const int col_tiles = (a.F + LPR * VEC - 1) / (LPR * VEC);
+  const int nblocks = a.n_task_blocks + a.npanels;
+  if (nblocks > 0) {
+    const size_t lds = (size_t)(4 * a.panel_rows + 1 + 2 * a.panel_nnz) * sizeof(int32_t);  // the weighted instances' carve-up
+    const hipError_t e = launch_lds<gather_rows_reduce_kernel<LPR, VEC, RMODE>>(dim3(nblocks, col_tiles), lds, stream, a);
+    if (e != hipSuccess) return e;
+  }
+  if constexpr (RMODE == 3) {
+    return launch_fixups_t<LPR, VEC>(a, nfix, nfix_l1, fixups, stream);  // float partial rows, summed in slot order
+  } else {
+    const int per_block = 256 / LPR;
+    if (nfix_l1 > 0)
+      hipLaunchKernelGGL((fixup_rows_reduce_kernel<LPR, VEC, RMODE == 1>), dim3((nfix_l1 + per_block - 1) / per_block, col_tiles),
+                         dim3(256), 0, stream, a, fixups, nfix_l1);
+    if (nfix > nfix_l1)
+      hipLaunchKernelGGL((fixup_rows_reduce_kernel<LPR, VEC, RMODE == 1>),
+                         dim3((nfix - nfix_l1 + per_block - 1) / per_block, col_tiles), dim3(256), 0, stream, a,
+                         fixups + nfix_l1, nfix - nfix_l1);
+    return hipGetLastError();
+  }
+}
+
+hipError_t launch_gather_reduce(const ReduceGatherArgs &a, int rmode, int nfix, int nfix_l1, const Fixup *fixups, bool vec4,
+                                hipStream_t stream) {
+  if (rmode < 1 || rmode > 3 || (rmode == 3 ? !a.arg_in : (!a.arg_out || (nfix > 0 && !a.ipartial)))) return hipErrorInvalidValue;
+  const int lanes = vec4 ? a.F / 4 : a.F;
+  const int lpr = std::min(64, next_pow2(std::max(lanes, 1)));
+#define HG_RED(L, VV)                                                                              \
+  (rmode == 1   ? launch_gather_reduce_t<L, VV, 1>(a, nfix, nfix_l1, fixups, stream)               \
+   : rmode == 2 ? launch_gather_reduce_t<L, VV, 2>(a, nfix, nfix_l1, fixups, stream)               \
+                : launch_gather_reduce_t<L, VV, 3>(a, nfix, nfix_l1, fixups, stream))
+#define HG_CASE(L) \
+  case L:          \
+    return vec4 ? HG_RED(L, 4) : HG_RED(L, 1);
+  switch (lpr) {
+    HG_CASE(1)
+    HG_CASE(2)
+    HG_CASE(4)
+    HG_CASE(8)
+    HG_CASE(16)
+    HG_CASE(32)
+    HG_CASE(64)
+  }
+#undef HG_CASE
+#undef HG_RED
   return hipErrorInvalidValue;
 }
 

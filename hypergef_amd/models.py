@@ -112,6 +112,28 @@ class HyperGsysUniGCNII(nn.Module):
         return torch.relu(out) if relu else out
 
 
+class HyperGsysUniSAGE(nn.Module):
+    """UniSAGE, the UniGNN family's member with a choice of aggregator in either hop, next to UniGIN and UniGCNII above:
+        Z = lin(X),   Y = Z + reduce_aggr(Z, first_aggr, second_aggr)
+    first_aggr reduces the members of every hyperedge, second_aggr the hyperedges of every vertex, each 'sum', 'mean',
+    'max' or 'min' (ops.reduce_aggr; no degree scales).  The one parameter is the bias-free linear's weight."""
+
+    def __init__(self, hyperg, in_channels, out_channels, first_aggr="mean", second_aggr="sum", options=None):
+        super().__init__()
+        for name, r in (("first_aggr", first_aggr), ("second_aggr", second_aggr)):
+            if r not in ("sum", "mean", "max", "min"):
+                raise ValueError("%s must be 'sum', 'mean', 'max' or 'min', got %r" % (name, r))
+        self.options = options
+        self.W = ops.Linear(in_channels, out_channels, bias=False, options=options)
+        self.in_channels, self.out_channels = in_channels, out_channels
+        self.hyperg, self.first_aggr, self.second_aggr = hyperg, first_aggr, second_aggr
+
+    def forward(self, X):
+        Z = self.W(X)
+        return Z + ops.reduce_aggr(self.hyperg.H_T_csrptr, self.hyperg.H_T_colind, Z, self.first_aggr, self.second_aggr,
+                                   options=self.options)
+
+
 class HypergraphAttnConv(nn.Module):
     """A hypergraph attention layer whose coefficient path runs on this backend's segment kernels.  Single head:
         Z = X W^T,   sv = Z a_v,   se[e] = mean_{u in e} (Z a_e)[u]   (0 for an empty hyperedge),

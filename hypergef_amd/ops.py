@@ -1070,8 +1070,35 @@ class _IncidenceGather(torch.autograd.Function):
         return None, None, gsrc, gw, None, None, None, None, None
 
 
+class _IncidenceReduce(torch.autograd.Function):
+    """dst = scale . (max or min over each row's entries of src) with the winner's position recorded, and its exact
+    gradient: dsrc is the select-gather of gs = grad * scale over the opposite hop (Plan.gather_rows_select), so the whole
+    gradient goes to the winner, the smallest position among ties.  The node keeps arg and the scales, no source rows."""
+
+    @staticmethod
+    def forward(ctx, csrptr_t, indices_t, src, scale_a, scale_b, N, to, op):
+        plan = cached_plan(N, csrptr_t, indices_t)
+        dst, arg = plan.gather_rows_reduce(to, csrptr_t, indices_t, src, op, scale_a, scale_b)
+        ctx.save_for_backward(csrptr_t, indices_t, arg, scale_a, scale_b)
+        ctx.N, ctx.to = N, to
+        ctx.mark_non_differentiable(arg)
+        return dst, arg
+
+    @staticmethod
+    def backward(ctx, grad, _grad_arg):
+        csrptr_t, indices_t, arg, scale_a, scale_b = ctx.saved_tensors
+        plan = cached_plan(ctx.N, csrptr_t, indices_t)
+        gsrc = None
+        if ctx.needs_input_grad[2]:
+            gsrc = plan.gather_rows_select(ctx.to, csrptr_t, indices_t, _scaled(grad, scale_a, scale_b), arg)
+        return None, None, gsrc, None, None, None, None, None
+
+
+_REDUCES = ("sum", "mean", "max", "min")
+
+
 def incidence_gather(csrptr_t, indices_t, src, weight=None, to="hyperedge", scale_a=None, scale_b=None, heads=1,
-                     options=None, num_nodes=None):
+                     options=None, num_nodes=None, reduce="sum", return_index=False):
     """One weighted hop of the incidence path as an operator of its own.  to='hyperedge': src is [N, F] and
     dst[e] = ((sum_{p=(e,u)} weight[p] * src[u]) * scale_a[e]) * scale_b[e], [M, F] -- hyperedge embeddings, e.g. the member
     mean with scale_a = 1 / |e|; to='vertex': src is [M, F] and dst[v] = ((sum_{p=(e,v)} weight[p] * src[e]) * scale_a[v]) *
@@ -1083,13 +1110,35 @@ def incidence_gather(csrptr_t, indices_t, src, weight=None, to="hyperedge", scal
     the others raise ValueError.  float32 only (TypeError for bfloat16) unless Options.incidence_bf16 = 'rows': a bfloat16 src
     gives a bfloat16 dst = round_bf16(the float32 call on src.float()), weighted or not, and gets a bfloat16 gradient; weight,
     scales and the weight's gradient stay float32.  num_nodes: N for to='vertex', where src does not
-    tell it; without it N is the length of a given scale, else the largest member id + 1, read back from the device."""
+    tell it; without it N is the length of a given scale, else the largest member id + 1, read back from the device.
+    reduce: 'sum' is the call above on its code path.  'mean' runs the same kernels with 1 / (row length) in the first scale
+    slot and the caller's scale_a in the second, dst = (sum * (1 / len)) * scale_a; a scale_b raises ValueError; an empty row
+    gives 0.  'max' / 'min' take the greatest / smallest entry of every row and column instead of the sum, scaled the same way
+    (Plan.gather_rows_reduce): weight must be None and heads 1 (ValueError), float32 only (TypeError for bfloat16 whatever
+    Options.incidence_bf16 says); the winner is chosen under > (<), the smallest position in indices_t among ties, an empty
+    row gives +0.0 whatever its scale, and NaN inputs are unspecified.  The gradient goes to the winner alone -- not torch's
+    amax rule, which shares it among ties -- through a select-gather without atomics.  return_index=True (max / min only)
+    returns (dst, arg), arg int32 [rows, F] the winner's position in indices_t (-1: empty row), not differentiable."""
     opt = _opt(options)
     if opt.variant not in ("auto", "pull"):
         raise ValueError("incidence_gather runs the pull kernels: variant must be 'auto' or 'pull', got %r" % opt.variant)
     _heads(heads)
     if to not in _HOPS:
         raise ValueError("to must be 'hyperedge' or 'vertex', got %r" % (to,))
+    if reduce not in _REDUCES:
+        raise ValueError("reduce must be one of %s, got %r" % (", ".join(repr(r) for r in _REDUCES), reduce))
+    if reduce in ("max", "min"):
+        if weight is not None:
+            raise ValueError("reduce=%r takes no weight (a comparison has no weighted form here)" % reduce)
+        if heads != 1:
+            raise ValueError("reduce=%r takes heads = 1" % reduce)
+        if isinstance(src, torch.Tensor) and src.dtype == torch.bfloat16:
+            raise TypeError("src must be a float32 tensor (reduce=%r has no bfloat16 form), got %s" % (reduce, src.dtype))
+    elif return_index:
+        raise ValueError("return_index needs reduce='max' or 'min', got %r" % reduce)
+    if reduce == "mean" and scale_b is not None:
+        raise ValueError("reduce='mean' keeps 1 / (row length) in the first scale slot and scale_a in the second: "
+                         "scale_b must be None")
     w = weight
     if isinstance(w, torch.Tensor):
         w = _flat(w) if heads == 1 else _per_head(w, heads)
@@ -1129,9 +1178,50 @@ def incidence_gather(csrptr_t, indices_t, src, weight=None, to="hyperedge", scal
             _check_feat(t, name, device=src.device)
     if N is None:
         N = int(indices_t.max()) + 1 if nnz else 0
+    if reduce in ("max", "min"):
+        if torch.is_grad_enabled() and src.requires_grad:
+            dst, arg = _IncidenceReduce.apply(csrptr_t, indices_t, src, scale_a, scale_b, N, to, reduce)
+        else:
+            dst, arg = cached_plan(N, csrptr_t, indices_t).gather_rows_reduce(to, csrptr_t, indices_t, src, reduce,
+                                                                              scale_a, scale_b)
+        return (dst, arg) if return_index else dst
+    if reduce == "mean":
+        scale_a, scale_b = cached_plan(N, csrptr_t, indices_t).row_recip(to, csrptr_t), scale_a
     if not (torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (src, w))):
         return _hop(cached_plan(N, csrptr_t, indices_t), csrptr_t, indices_t, to, src, w, scale_a, scale_b, heads)
     return _IncidenceGather.apply(csrptr_t, indices_t, src, w, scale_a, scale_b, N, to, heads)
+
+
+def reduce_aggr(csrptr_t, indices_t, X, first="sum", second="sum", degE=None, degV=None, W=None, num_nodes=None,
+                options=None):
+    """The two hops with a reduction each, composed of incidence_gather calls: first ('sum', 'mean', 'max', 'min') takes the
+    members of every hyperedge, Xe[e] = ((first_{u in e} X[u]) * degE[e]) * W[e]; second takes the hyperedges of every vertex,
+    Y[v] = (second_{e contains v} Xe[e]) * degV[v].  first='mean' scales the sum by the single factor degE * W / |e| as
+    hgnnaggr_mean forms it (non-finite values, which only an empty hyperedge has, set to 0); second='mean' divides by the
+    vertex's number of incidences before degV.  UniSAGE's mean / max aggregators in either hop are such calls.  float32;
+    differentiable in X (max / min: the gradient goes to the winner alone); degE / degV / W get no gradient here."""
+    for name, r in (("first", first), ("second", second)):
+        if r not in _REDUCES:
+            raise ValueError("%s must be one of %s, got %r" % (name, ", ".join(repr(x) for x in _REDUCES), r))
+    if not isinstance(X, torch.Tensor) or X.dtype != torch.float32:
+        raise TypeError("X must be a float32 tensor (reduce_aggr has no bfloat16 form), got %s" % (getattr(X, "dtype", type(X)),))
+    if X.dim() != 2:
+        raise ValueError("X must be [N, F]")
+    N = X.shape[0]
+    if num_nodes is not None and int(num_nodes) != N:
+        raise ValueError("X has %d rows, num_nodes is %d" % (N, int(num_nodes)))
+    if first == "mean":
+        _check_index(csrptr_t, "csrptr_t")
+        num = None  # degE * W / |e|, in _MeanF1's order of operations
+        for sc in (degE, W):
+            if sc is not None:
+                num = _flat(sc) if num is None else num * _flat(sc)
+        s = (1.0 if num is None else num) / _edge_sizes(csrptr_t)
+        s = torch.where(torch.isfinite(s), s, torch.zeros_like(s))
+        Xe = incidence_gather(csrptr_t, indices_t, X, to="hyperedge", scale_a=s, options=options)
+    else:
+        Xe = incidence_gather(csrptr_t, indices_t, X, to="hyperedge", scale_a=degE, scale_b=W, options=options, reduce=first)
+    return incidence_gather(csrptr_t, indices_t, Xe, to="vertex", scale_a=degV, options=options, num_nodes=N, reduce=second)
 
 
 class _IncidenceDot(torch.autograd.Function):

@@ -591,6 +591,100 @@ class Plan:
                     _ptr(dst), _ptr(workspace), nbytes, _stream_handle(src.device)))
         return dst
 
+    def reduce_workspace_bytes(self, F):
+        return int(_lib.lib().hg_gather_rows_reduce_workspace_bytes(self._h, F))
+
+    def _reduce_args(self, hop, rows, arg, out, F=None):
+        """Checks gather_rows_reduce and gather_rows_select share: rows [nsrc, F] float32 on a GPU, the int32 table beside
+        it, the result's shape.  Returns (hop, nsrc, ndst, F)."""
+        hop = _side(hop)
+        _check_feat(rows, "src")
+        nsrc, ndst = (self.N, self.M) if hop == 0 else (self.M, self.N)
+        if rows.dim() != 2:
+            raise ValueError("src must be [rows, F]")
+        F = rows.shape[1]
+        if arg is not None:
+            if not isinstance(arg, torch.Tensor) or arg.dtype != torch.int32:
+                raise TypeError("arg must be an int32 tensor")
+            if not arg.is_cuda or arg.device != rows.device or not arg.is_contiguous():
+                raise RuntimeError("arg must be contiguous and on %s" % rows.device)
+        if out is not None:
+            _check_feat(out, "out", device=rows.device)
+        return hop, nsrc, ndst, F
+
+    def gather_rows_reduce(self, hop, csrptr_t, colind_t, src, op, scaleA=None, scaleB=None, out=None, arg_out=None,
+                           workspace=None):
+        """One hop with max or min in place of the sum (hg_gather_rows_reduce_f32): hop 0 / 'hyperedge',
+        dst[e, c] = ((op over the members u of e of src[u, c]) * scaleA[e]) * scaleB[e] with src [N, F] and dst [M, F]; hop 1 /
+        'vertex' the mirror.  op: 'max' or 'min'.  Returns (dst, arg): arg int32 [rows of dst, F] holds the winning
+        incidence's position in colind_t -- the greatest (smallest) value under > (<), the smallest position among ties, so
+        -0.0 ties +0.0 -- and dst is src[colind[arg]] scaled, bit for bit.  An empty row gets +0.0 and arg = -1 whatever its
+        scale.  NaN inputs: unspecified.  float32 only; every schedule and every call give the same bits.  The first hop-1
+        call uploads the plan's permutation: not capturable."""
+        if op not in ("max", "min"):
+            raise ValueError("op must be 'max' or 'min', got %r" % (op,))
+        hop, nsrc, ndst, F = self._reduce_args(hop, src, arg_out, out)
+        if src.shape[0] != nsrc:
+            raise ValueError("src must be [%d, F]" % nsrc)
+        for name, t in (("scaleA", scaleA), ("scaleB", scaleB)):
+            if t is not None:
+                _check_feat(t, name, device=src.device)
+                if t.numel() != ndst:
+                    raise ValueError("%s must have %d elements, got %d" % (name, ndst, t.numel()))
+        for name, t in (("out", out), ("arg_out", arg_out)):
+            if t is not None and tuple(t.shape) != (ndst, F):
+                raise ValueError("%s must be [%d, %d]" % (name, ndst, F))
+        dst = out if out is not None else torch.empty((ndst, F), dtype=torch.float32, device=src.device)
+        arg = arg_out if arg_out is not None else torch.empty((ndst, F), dtype=torch.int32, device=src.device)
+        nbytes = self.reduce_workspace_bytes(F)
+        if workspace is None:
+            workspace = torch.empty(nbytes, dtype=torch.uint8, device=src.device)
+        with torch.cuda.device(src.device):
+            _lib.check(_lib.lib().hg_gather_rows_reduce_f32(
+                self._h, hop, F, _lib.HG_REDUCE_MAX if op == "max" else _lib.HG_REDUCE_MIN, _ptr(csrptr_t), _ptr(colind_t),
+                _ptr(src), _ptr(scaleA), _ptr(scaleB), _ptr(dst), _ptr(arg), _ptr(workspace),
+                workspace.numel() * workspace.element_size(), _stream_handle(src.device)))
+        return dst, arg
+
+    def gather_rows_select(self, hop, csrptr_t, colind_t, gs, arg, out=None, workspace=None):
+        """The gradient of gather_rows_reduce's src (hg_gather_rows_select_f32).  hop names the hop being differentiated;
+        gs (the incoming gradient times the hop's scales) and arg (its winners) are [rows of that hop's dst, F].  Every row
+        of the result gathers, over the other hop's CSR and in the sum gather's order, the gs of the rows it won:
+        dsrc[u, c] = sum_q (arg[r_q, c] == pos(q)) ? gs[r_q, c] : 0.  No atomics: two calls give the same bits."""
+        hop, nsrc, ndst, F = self._reduce_args(hop, gs, arg, out)
+        if arg is None or tuple(gs.shape) != (ndst, F) or tuple(arg.shape) != (ndst, F):
+            raise ValueError("gs and arg must be [%d, F]" % ndst)
+        if out is not None and tuple(out.shape) != (nsrc, F):
+            raise ValueError("out must be [%d, %d]" % (nsrc, F))
+        dsrc = out if out is not None else torch.empty((nsrc, F), dtype=torch.float32, device=gs.device)
+        if workspace is None:
+            workspace = torch.empty(self.reduce_workspace_bytes(F), dtype=torch.uint8, device=gs.device)
+        with torch.cuda.device(gs.device):
+            _lib.check(_lib.lib().hg_gather_rows_select_f32(
+                self._h, hop, F, _ptr(csrptr_t), _ptr(colind_t), _ptr(gs), _ptr(arg), _ptr(dsrc), _ptr(workspace),
+                workspace.numel() * workspace.element_size(), _stream_handle(gs.device)))
+        return dsrc
+
+    def row_recip(self, hop, csrptr_t):
+        """float32 device tensor of 1 / (row length) of one side -- [M], 1 / |e|, for hop 0 / 'hyperedge'; [N], one over a
+        vertex's number of incidences, for hop 1 / 'vertex' -- with 0 for an empty row: the mean's scale.  Built by the
+        first call outside a stream capture and kept with the plan (nonempty_edges' rule inside one)."""
+        hop = _side(hop)
+        cache = self.__dict__.setdefault("_row_recip", {})
+        key = (hop, str(csrptr_t.device))
+        hit = cache.get(key)
+        if hit is not None:
+            return hit
+        if hop == 0:
+            length = (csrptr_t[1:] - csrptr_t[:-1]).to(torch.float32)
+        else:
+            ptr_v = torch.from_numpy(self.vertex_csr()[0]).to(csrptr_t.device)
+            length = (ptr_v[1:] - ptr_v[:-1]).to(torch.float32)
+        recip = torch.where(length > 0, 1.0 / length, torch.zeros_like(length))
+        if not torch.cuda.is_current_stream_capturing():
+            cache[key] = recip
+        return recip
+
     def incidence_perm(self):
         """Host copy (numpy int32 [nnz]) of perm[q] = the H_T position of H entry q: the stable transpose behind
         vertex_csr(), by which hop 2 of aggregate_incidence reads e2v.  Works on host-only plans too."""

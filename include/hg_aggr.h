@@ -754,6 +754,45 @@ HG_API int hg_incidence_dot_heads_bf16(const hg_plan *plan, int32_t F, int32_t h
                                        const int32_t *colind_t, const void *A, const void *B, float *out, int32_t io,
                                        hg_stream_t stream);
 
+/* ---- max and min in the row gather, with the winner recorded --------------------------------------------------------------
+ * hg_gather_rows_reduce_f32: one hop with a comparison in place of the sum, op = HG_REDUCE_MAX or HG_REDUCE_MIN, fp32:
+ *     hop 0: dst[e, c] = ((op_{p=(e,u)} src[u, c]) * scaleA[e]) * scaleB[e]     arg_out[e, c] = p*      src [N, F], dst [M, F]
+ *     hop 1: dst[v, c] = ((op_{p=(e,v)} src[e, c]) * scaleA[v]) * scaleB[v]     arg_out[v, c] = p*      src [M, F], dst [N, F]
+ *   arg_out: int32 [rows of dst, F], the winning incidence's position in colind_t (the convention of the [nnz] weight
+ *   arrays; hop 1 finds it through the plan's permutation).  The winner is the entry with the greatest (smallest) value
+ *   under > (<), so -0.0 ties +0.0; among ties the smallest position wins.  The value before scaling is src[ind[p*], c] bit
+ *   for bit.  A non-empty row always has a winner (all -inf under max: its first position).  An empty row gets exactly +0.0
+ *   and arg_out = -1, no scale applied (degE may be inf).  NaN in src: unspecified (which entry wins, and so dst and arg_out
+ *   of that column).  scaleA / scaleB: one factor per row of dst, or NULL.
+ *   It runs on the schedules of hg_gather_rows_incidence_heads_f32 -- panels, wave tasks, partial slots and fixups, a pinned
+ *   latency schedule honoured, the same LDS check -- with (value, position) carried per column; the comparison is exact and
+ *   the tie rule total, so every schedule and every call give the same bits.  No atomics.  16-byte lanes where F % 4 == 0 and
+ *   src, dst and arg_out are 16-byte aligned, else 4-byte lanes on the sum gather's lane groups (column tiles above 64 lanes).
+ *   workspace: hg_gather_rows_reduce_workspace_bytes(plan, F), 256-byte aligned: a float and an int32 table of partial slots.
+ * hg_gather_rows_select_f32: the gradient of that hop's src, as a row gather over the OTHER hop's CSR -- no scatter, no
+ *   atomics, the sum gather's order of addition.  hop names the hop being differentiated; arg is its arg_out and gs its
+ *   incoming gradient times the scales (the caller multiplies), both [rows of dst, F]; dsrc is [rows of src, F]:
+ *     dsrc[u, c] = sum over the entries q of row u of the opposite CSR, in row order, of (arg[r_q, c] == pos(q)) ? gs[r_q, c] : 0
+ *   with r_q the entry's other end and pos(q) its colind_t position.  A duplicate incidence is two positions, of which the
+ *   winner is one: its gradient arrives once.  dsrc is fully overwritten.  Lanes as above (gs, arg, dsrc); the same workspace.
+ * Both: the first call that walks H (reduce hop 1, select of hop 0) uploads the plan's permutation and so cannot be
+ *   captured into a hipGraph; make one such call before capturing.  Refusals, nothing launched, in this order:
+ *   HG_ERR_INVALID for a null plan, a hop outside 0 / 1, an op other than the two; HG_ERR_UNSUPPORTED for a plan built with
+ *   HG_PLAN_HOST_ONLY; HG_ERR_INVALID for F < 1 or a null array; HG_ERR_UNSUPPORTED where hg_aggr_incidence_f32 returns it
+ *   (LDS); HG_ERR_WORKSPACE.
+ * Not covered: bf16 rows, per-incidence weights, and hg_gather_max_f32 below, which keeps the reference's arithmetic.
+ * Detect these entries by their exported symbols (HG_AGGR_VERSION does not change). */
+#define HG_REDUCE_MAX 1
+#define HG_REDUCE_MIN 2
+HG_API size_t hg_gather_rows_reduce_workspace_bytes(const hg_plan *plan, int32_t F);
+HG_API int hg_gather_rows_reduce_f32(const hg_plan *plan, int32_t hop, int32_t F, int32_t op, const int32_t *csrptr_t,
+                                     const int32_t *colind_t, const float *src, const float *scaleA, const float *scaleB,
+                                     float *dst, int32_t *arg_out, void *workspace, size_t workspace_bytes,
+                                     hg_stream_t stream);
+HG_API int hg_gather_rows_select_f32(const hg_plan *plan, int32_t hop, int32_t F, const int32_t *csrptr_t,
+                                     const int32_t *colind_t, const float *gs, const int32_t *arg, float *dsrc,
+                                     void *workspace, size_t workspace_bytes, hg_stream_t stream);
+
 /* first_aggr = "max" pieces (hgnnaggr_max, source/hgnnaggr/hgnnaggr_cuda.cu:144-208).
  * hg_gather_max_f32: Xe[e,k] = (max_{u in e} X[u,k], start -1e5, strict >) * (degE[e]*W[e]),
  * record[e,k] = winning vertex (0 if none).  The second hop is hg_gather_rows_f32(hop = 1).
