@@ -25,8 +25,8 @@ Inputs: randn; values from {-1, -0.0, +0.0, 1}; randn with +-inf sprinkled in an
    vertex has four hyperedges: hgnnaggr_max's backward is the reference's rule, T[e] * degV[winner] with T = the hyperedge
    sums of the unscaled gradient, and equals the adjoint (degV applied to each member's gradient before the sum) only where
    degV is the same for the members of a hyperedge -- on the cora shape the two differ by that rule, not by rounding.
-6. HyperGsysUniSAGE for (mean, sum), (max, mean), (sum, max) against a float64 restatement whose max takes the winner-only
-   gradient of _reduce_ref; the inputs are small integers, so Z = X W^T is exact in both precisions and the winners cannot
+6. HyperGsysUniSAGE for (mean, sum), (max, mean), (sum, max) against a float64 restatement (_reduce_ref.hop64) whose max takes the
+   winner-only gradient; the inputs are small integers, so Z = X W^T is exact in both precisions and the winners cannot
    differ by rounding.  A captured training step replays to the bits of the eager step.
 """
 import os
@@ -417,38 +417,6 @@ def test_against_hgnnaggr_max(graph, name):
 
 # ---- 6: the layer ------------------------------------------------------------------------------------------------------------
 
-class _Reduce64(torch.autograd.Function):
-    """One max / min hop in float64 with the winner-only gradient of _reduce_ref.  winners: a list; empty, it receives this
-    hop's arg; holding one, that arg is used instead of a comparison -- the mass pass, on absolute values, must follow the
-    winners of the real pass."""
-
-    @staticmethod
-    def forward(ctx, src, g, hop, op, winners):
-        if winners:
-            arg = winners[0]
-            cols = torch.arange(src.shape[1], device=src.device).reshape(1, -1).expand_as(arg)
-            val = src[(g.V if hop == 0 else g.E)[arg.clamp(min=0)], cols]
-            val = torch.where(arg < 0, torch.zeros_like(val), val)
-        else:
-            val, arg = rr.reduce_hop(g.inc, hop, src, op, g.E, g.V)
-            winners.append(arg)
-        ctx.g, ctx.hop, ctx.arg = g, hop, arg
-        return val
-
-    @staticmethod
-    def backward(ctx, grad):
-        return rr.select_grad(ctx.g.inc, ctx.hop, grad, ctx.arg, ctx.g.E, ctx.g.V), None, None, None, None
-
-
-def _hop64(g, hop, src, op, winners):
-    """One hop in float64: max / min as above, or the plain sum / mean."""
-    if op in OPS:
-        return _Reduce64.apply(src, g, hop, op, winners)
-    rows, other = (g.E, g.V) if hop == 0 else (g.V, g.E)
-    out = torch.zeros(g.nrows(hop)[0], src.shape[1], dtype=src.dtype, device=src.device).index_add(0, rows, src[other])
-    return out / g.len[hop].clamp(min=1).reshape(-1, 1).to(src.dtype) if op == "mean" else out
-
-
 @pytest.mark.parametrize("first,second", [("mean", "sum"), ("max", "mean"), ("sum", "max")])
 def test_unisage(graph, first, second):
     g = graph("random")
@@ -470,7 +438,7 @@ def test_unisage(graph, first, second):
 
     def f64_layer(x64, w64):
         z = x64 @ w64.t()
-        return z + _hop64(g, 1, _hop64(g, 0, z, first, win[0]), second, win[1])
+        return z + rr.hop64(g, 1, rr.hop64(g, 0, z, first, win[0]), second, win[1])
 
     x64, w64 = X.double().requires_grad_(True), W0.double().requires_grad_(True)
     y64 = f64_layer(x64, w64)
