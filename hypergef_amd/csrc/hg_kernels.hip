@@ -2664,12 +2664,57 @@ __global__ __launch_bounds__(256) void push_tasks_kernel(const PushArgs a) {
   }
 }
 
-int fused_tile_row_floats(int F, bool vec4);
-
 static inline int next_pow2(int x) {
   int p = 1;
   while (p < x) p <<= 1;
   return p;
+}
+
+// The lane rule: a row of F floats lies on a power of two of lanes, 64 at the most (wider rows take more column tiles), of
+// four floats each (vec4: 16-byte lanes) or one.  lanes_per_row is for rows of whole lanes (vec4: F % 4 == 0);
+// lanes_per_row_up covers rows of any width with 16-byte lanes (loadu / store_n) and so counts the last, partial lane.
+static inline int lanes_pow2(int lanes) { return std::min(64, next_pow2(std::max(lanes, 1))); }
+static inline int lanes_per_row(int F, bool vec4) { return lanes_pow2(vec4 ? F / 4 : F); }
+static inline int lanes_per_row_up(int F, bool vec4) { return lanes_pow2(vec4 ? (F + 3) / 4 : F); }
+
+// Runtime launch arguments to template arguments.  dispatch_lpr calls fn with the lanes per row (a power of two from MIN to
+// 64; anything else is an invalid value) as a std::integral_constant, dispatch_vec with the floats per lane, and both
+// return what fn returns.  The constants convert to int where fn names a kernel: fn<L, V>.
+template <int N> using Int = std::integral_constant<int, N>;
+template <int L, int MIN, typename Fn> static hipError_t call_lpr(Fn &fn) {
+  if constexpr (L >= MIN) return fn(Int<L>{});
+  else return hipErrorInvalidValue;
+}
+template <int MIN = 1, typename Fn> static hipError_t dispatch_lpr(int lpr, Fn fn) {
+  switch (lpr) {
+    case 1: return call_lpr<1, MIN>(fn);
+    case 2: return call_lpr<2, MIN>(fn);
+    case 4: return call_lpr<4, MIN>(fn);
+    case 8: return call_lpr<8, MIN>(fn);
+    case 16: return call_lpr<16, MIN>(fn);
+    case 32: return call_lpr<32, MIN>(fn);
+    case 64: return call_lpr<64, MIN>(fn);
+  }
+  return hipErrorInvalidValue;
+}
+template <typename Fn> static hipError_t dispatch_vec(bool vec4, Fn fn) { return vec4 ? fn(Int<4>{}) : fn(Int<1>{}); }
+template <typename Fn> static hipError_t dispatch_flag(bool flag, Fn fn) { return flag ? fn(std::true_type{}) : fn(std::false_type{}); }
+// the MAT and SCALED of the fused panels and the hub pass: a materialised table is read; hyperedge scales (degE, W) are applied
+template <typename Args, typename Fn> static hipError_t dispatch_mat_scaled(const Args &a, Fn fn) {
+  return dispatch_flag(a.Xe_mat != nullptr, [&](auto M) { return dispatch_flag(a.degE || a.W, [&](auto S) { return fn(M, S); }); });
+}
+
+// The element types of two row tables, fn(TA{}, TB{}) with each of float and bf16.  bf16 rows exist on 16-byte lanes only:
+// at VEC = 1 no bf16 pair is formed (so no such kernel is instantiated) and a bf16 flag is an invalid value.
+template <int VEC, typename Fn> static hipError_t dispatch_rows(bool a_bf16, bool b_bf16, Fn fn) {
+  if constexpr (VEC == 4) {
+    if (a_bf16 && b_bf16) return fn(bf16{}, bf16{});
+    if (a_bf16) return fn(bf16{}, float{});
+    if (b_bf16) return fn(float{}, bf16{});
+  } else if (a_bf16 || b_bf16) {
+    return hipErrorInvalidValue;
+  }
+  return fn(float{}, float{});
 }
 
 // Dynamic LDS above the 64 KiB default is an opt-in per kernel; gfx950 has 160 KiB per CU.
@@ -2688,18 +2733,30 @@ static hipError_t launch_lds(dim3 grid, size_t lds, hipStream_t stream, const Ar
   return hipGetLastError();
 }
 
+// The dynamic LDS of a panel gather, the carve-up of gather_rows_kernel and gather_rows_reduce_kernel: sptr
+// [panel_rows + 1], three more words per row, then entry_words per index entry -- 1: sind alone; 2: a float (a position)
+// beside it, the weighted (reduce) instances -- and last the attention instances' row_extras scalars per row.
+static size_t panel_lds_bytes(int32_t panel_rows, int32_t panel_nnz, int entry_words, size_t row_extras = 0) {
+  return ((size_t)4 * panel_rows + 1 + (size_t)entry_words * panel_nnz + row_extras * panel_rows) * sizeof(int32_t);
+}
+
+// The two-level fixup sums, lane groups of LPR lanes: the first level's fixups [0, nfix_l1) (rows cut into very many
+// tasks), then the rest in a launch of their own.  Kern: fixup_rows_kernel or fixup_rows_reduce_kernel.
+template <auto Kern, int LPR, typename Args>
+static hipError_t launch_fixup_levels(const Args &a, int col_tiles, int nfix, int nfix_l1, const Fixup *fixups, hipStream_t stream) {
+  const int per_block = 256 / LPR;
+  if (nfix_l1 > 0)
+    hipLaunchKernelGGL(Kern, dim3((nfix_l1 + per_block - 1) / per_block, col_tiles), dim3(256), 0, stream, a, fixups, nfix_l1);
+  if (nfix > nfix_l1)
+    hipLaunchKernelGGL(Kern, dim3((nfix - nfix_l1 + per_block - 1) / per_block, col_tiles), dim3(256), 0, stream, a,
+                       fixups + nfix_l1, nfix - nfix_l1);
+  return hipGetLastError();
+}
+
 template <int LPR, int VEC, typename TD = float>
 static hipError_t launch_fixups_t(const GatherArgs &a, int nfix, int nfix_l1, const Fixup *fixups, hipStream_t stream) {
   const int col_tiles = (a.F + LPR * VEC - 1) / (LPR * VEC);
-  const int per_block = 256 / LPR;
-  if (nfix_l1 > 0)  // first level of the two-level sums (rows cut into very many tasks)
-    hipLaunchKernelGGL((fixup_rows_kernel<LPR, VEC, TD>), dim3((nfix_l1 + per_block - 1) / per_block, col_tiles),
-                       dim3(256), 0, stream, a, fixups, nfix_l1);
-  if (nfix > nfix_l1)
-    hipLaunchKernelGGL((fixup_rows_kernel<LPR, VEC, TD>),
-                       dim3((nfix - nfix_l1 + per_block - 1) / per_block, col_tiles), dim3(256), 0, stream, a,
-                       fixups + nfix_l1, nfix - nfix_l1);
-  return hipGetLastError();
+  return launch_fixup_levels<fixup_rows_kernel<LPR, VEC, TD>, LPR>(a, col_tiles, nfix, nfix_l1, fixups, stream);
 }
 
 // WM: 0 no weights, 1 a weight per entry (the WT instances), 2 a weight per entry and head (the WH instances), 3 the
@@ -2707,13 +2764,12 @@ static hipError_t launch_fixups_t(const GatherArgs &a, int nfix, int nfix_l1, co
 template <int LPR, int VEC, typename TS = float, typename TD = float, int WM = 0>
 static hipError_t launch_gather_t(const GatherArgsOf<WM == 1, WM == 2, WM == 3> &a, int nfix, int nfix_l1, const Fixup *fixups,
                                   hipStream_t stream) {
-  constexpr bool WT = WM == 1 || WM == 2;
   const int col_tiles = (a.F + LPR * VEC - 1) / (LPR * VEC);
   const int nblocks = a.n_task_blocks + a.npanels;
   if (nblocks > 0) {
     // the weighted instances stage one float (heads: one position) per index entry beside sind; the attention instances
-    // stage nothing per entry: the unweighted layout, then the rows' scalars (attn_gather_lds_bytes)
-    size_t lds = (size_t)(4 * a.panel_rows + 1 + (WT ? 2 : 1) * a.panel_nnz) * sizeof(int32_t);
+    // stage nothing per entry: the unweighted layout, then the rows' scalars
+    size_t lds = panel_lds_bytes(a.panel_rows, a.panel_nnz, WM == 1 || WM == 2 ? 2 : 1);
     if constexpr (WM == 3) lds = attn_gather_lds_bytes(a.panel_rows, a.panel_nnz, a.heads, a.stat_row != 0);
     const dim3 grid(nblocks, col_tiles);
     const hipError_t e = launch_lds<gather_rows_kernel<LPR, VEC, TS, TD, WM == 1, WM == 2, WM == 3>>(grid, lds, stream, a);
@@ -2722,58 +2778,30 @@ static hipError_t launch_gather_t(const GatherArgsOf<WM == 1, WM == 2, WM == 3> 
   return launch_fixups_t<LPR, VEC, TD>(a, nfix, nfix_l1, fixups, stream);
 }
 
-hipError_t launch_gather(const GatherArgs &a, int nfix, int nfix_l1, const Fixup *fixups, bool vec4,
-                         hipStream_t stream, bool src_bf16, bool dst_bf16) {
-  const int lanes = vec4 ? a.F / 4 : a.F;
-  const int lpr = std::min(64, next_pow2(std::max(lanes, 1)));
-  if ((src_bf16 || dst_bf16) && !vec4) return hipErrorInvalidValue;
-#define HG_CASE(L)                                                                                       \
-  case L:                                                                                                \
-    if (src_bf16 && dst_bf16) return launch_gather_t<L, 4, bf16, bf16>(a, nfix, nfix_l1, fixups, stream); \
-    if (src_bf16) return launch_gather_t<L, 4, bf16, float>(a, nfix, nfix_l1, fixups, stream);            \
-    if (dst_bf16) return launch_gather_t<L, 4, float, bf16>(a, nfix, nfix_l1, fixups, stream);            \
-    return vec4 ? launch_gather_t<L, 4>(a, nfix, nfix_l1, fixups, stream)                                \
-                : launch_gather_t<L, 1>(a, nfix, nfix_l1, fixups, stream);
-  switch (lpr) {
-    HG_CASE(1)
-    HG_CASE(2)
-    HG_CASE(4)
-    HG_CASE(8)
-    HG_CASE(16)
-    HG_CASE(32)
-    HG_CASE(64)
-  }
-#undef HG_CASE
-  return hipErrorInvalidValue;
+// gather_rows_kernel's WM = 0 .. 2 instances on lpr lanes of VEC = (lane4 ? 4 : 1) floats and, on 16-byte lanes, every form
+// of (src_bf16, dst_bf16); a bf16 form on 4-byte lanes is an invalid value
+template <int WM>
+static hipError_t launch_gather_rows(const GatherArgsOf<WM == 1, WM == 2, false> &a, int nfix, int nfix_l1, const Fixup *fixups,
+                                     int lpr, bool lane4, hipStream_t stream, bool src_bf16, bool dst_bf16) {
+  return dispatch_lpr(lpr, [&](auto L) {
+    return dispatch_vec(lane4, [&](auto V) {
+      return dispatch_rows<V>(src_bf16, dst_bf16, [&](auto ts, auto td) {
+        return launch_gather_t<L, V, decltype(ts), decltype(td), WM>(a, nfix, nfix_l1, fixups, stream);
+      });
+    });
+  });
 }
 
-// bf16 rows on the weighted (WM = 1) and per-head (WM = 2) instances: the three forms of (src, dst), 16-byte lanes only
-#define HG_ROWS_BF16(L, WM)                                                                                           \
-  if (src_bf16 && dst_bf16) return launch_gather_t<L, 4, bf16, bf16, WM>(a, nfix, nfix_l1, fixups, stream);            \
-  if (src_bf16) return launch_gather_t<L, 4, bf16, float, WM>(a, nfix, nfix_l1, fixups, stream);                       \
-  if (dst_bf16) return launch_gather_t<L, 4, float, bf16, WM>(a, nfix, nfix_l1, fixups, stream);
+hipError_t launch_gather(const GatherArgs &a, int nfix, int nfix_l1, const Fixup *fixups, bool vec4,
+                         hipStream_t stream, bool src_bf16, bool dst_bf16) {
+  if ((src_bf16 || dst_bf16) && !vec4) return hipErrorInvalidValue;
+  return launch_gather_rows<0>(a, nfix, nfix_l1, fixups, lanes_per_row(a.F, vec4), vec4, stream, src_bf16, dst_bf16);
+}
 
 hipError_t launch_gather_weighted(const WeightedGatherArgs &a, int nfix, int nfix_l1, const Fixup *fixups, bool vec4,
                                   hipStream_t stream, bool src_bf16, bool dst_bf16) {
   if (!a.w || ((src_bf16 || dst_bf16) && !vec4)) return hipErrorInvalidValue;
-  const int lanes = vec4 ? a.F / 4 : a.F;
-  const int lpr = std::min(64, next_pow2(std::max(lanes, 1)));
-#define HG_CASE(L)                                                                                     \
-  case L:                                                                                              \
-    HG_ROWS_BF16(L, 1)                                                                                 \
-    return vec4 ? launch_gather_t<L, 4, float, float, 1>(a, nfix, nfix_l1, fixups, stream)          \
-                : launch_gather_t<L, 1, float, float, 1>(a, nfix, nfix_l1, fixups, stream);
-  switch (lpr) {
-    HG_CASE(1)
-    HG_CASE(2)
-    HG_CASE(4)
-    HG_CASE(8)
-    HG_CASE(16)
-    HG_CASE(32)
-    HG_CASE(64)
-  }
-#undef HG_CASE
-  return hipErrorInvalidValue;
+  return launch_gather_rows<1>(a, nfix, nfix_l1, fixups, lanes_per_row(a.F, vec4), vec4, stream, src_bf16, dst_bf16);
 }
 
 // lane4: 16-byte lanes are legal (C % 4 == 0, rows and partial rows 16-byte aligned).  lpr: the lanes per row of the
@@ -2783,29 +2811,11 @@ hipError_t launch_gather_heads(const HeadsGatherArgs &a, int nfix, int nfix_l1, 
                                hipStream_t stream, bool src_bf16, bool dst_bf16) {
   if (!a.w || a.heads < 1 || a.C < 1 || (int64_t)a.heads * a.C != a.F || (lane4 && (!vec4 || a.C % 4))) return hipErrorInvalidValue;
   if ((src_bf16 || dst_bf16) && !lane4) return hipErrorInvalidValue;
-  const int lanes = vec4 ? a.F / 4 : a.F;
-  const int lpr = std::min(64, next_pow2(std::max(lanes, 1)));
-#define HG_CASE(L)                                                                                  \
-  case L:                                                                                           \
-    HG_ROWS_BF16(L, 2)                                                                              \
-    return lane4 ? launch_gather_t<L, 4, float, float, 2>(a, nfix, nfix_l1, fixups, stream)         \
-                 : launch_gather_t<L, 1, float, float, 2>(a, nfix, nfix_l1, fixups, stream);
-  switch (lpr) {
-    HG_CASE(1)
-    HG_CASE(2)
-    HG_CASE(4)
-    HG_CASE(8)
-    HG_CASE(16)
-    HG_CASE(32)
-    HG_CASE(64)
-  }
-#undef HG_CASE
-  return hipErrorInvalidValue;
+  return launch_gather_rows<2>(a, nfix, nfix_l1, fixups, lanes_per_row(a.F, vec4), lane4, stream, src_bf16, dst_bf16);
 }
-#undef HG_ROWS_BF16
 
 size_t attn_gather_lds_bytes(int32_t panel_rows, int32_t panel_nnz, int32_t heads, bool stat_row) {
-  return ((size_t)4 * panel_rows + 1 + panel_nnz + (size_t)(stat_row ? 3 : 1) * panel_rows * heads) * sizeof(int32_t);
+  return panel_lds_bytes(panel_rows, panel_nnz, 1, (size_t)(stat_row ? 3 : 1) * heads);
 }
 
 // launch_gather_heads' lane rule (lane4, lpr), so that every column is summed in the order of the WH instance on alpha
@@ -2813,23 +2823,9 @@ hipError_t launch_gather_attention(const AttnGatherArgs &a, int nfix, int nfix_l
                                    hipStream_t stream) {
   if (!a.seg_max || !a.seg_inv || a.heads < 1 || a.C < 1 || (int64_t)a.heads * a.C != a.F || (lane4 && (!vec4 || a.C % 4)))
     return hipErrorInvalidValue;
-  const int lanes = vec4 ? a.F / 4 : a.F;
-  const int lpr = std::min(64, next_pow2(std::max(lanes, 1)));
-#define HG_CASE(L)                                                                                  \
-  case L:                                                                                           \
-    return lane4 ? launch_gather_t<L, 4, float, float, 3>(a, nfix, nfix_l1, fixups, stream)         \
-                 : launch_gather_t<L, 1, float, float, 3>(a, nfix, nfix_l1, fixups, stream);
-  switch (lpr) {
-    HG_CASE(1)
-    HG_CASE(2)
-    HG_CASE(4)
-    HG_CASE(8)
-    HG_CASE(16)
-    HG_CASE(32)
-    HG_CASE(64)
-  }
-#undef HG_CASE
-  return hipErrorInvalidValue;
+  return dispatch_lpr(lanes_per_row(a.F, vec4), [&](auto L) {
+    return dispatch_vec(lane4, [&](auto V) { return launch_gather_t<L, V, float, float, 3>(a, nfix, nfix_l1, fixups, stream); });
+  });
 }
 
 template <int LPR, int VEC, int RMODE>
@@ -2837,127 +2833,69 @@ static hipError_t launch_gather_reduce_t(const ReduceGatherArgs &a, int nfix, in
   const int col_tiles = (a.F + LPR * VEC - 1) / (LPR * VEC);
   const int nblocks = a.n_task_blocks + a.npanels;
   if (nblocks > 0) {
-    const size_t lds = (size_t)(4 * a.panel_rows + 1 + 2 * a.panel_nnz) * sizeof(int32_t);  // the weighted instances' carve-up
+    const size_t lds = panel_lds_bytes(a.panel_rows, a.panel_nnz, 2);  // a position beside every index entry
     const hipError_t e = launch_lds<gather_rows_reduce_kernel<LPR, VEC, RMODE>>(dim3(nblocks, col_tiles), lds, stream, a);
     if (e != hipSuccess) return e;
   }
-  if constexpr (RMODE == 3) {
+  if constexpr (RMODE == 3)
     return launch_fixups_t<LPR, VEC>(a, nfix, nfix_l1, fixups, stream);  // float partial rows, summed in slot order
-  } else {
-    const int per_block = 256 / LPR;
-    if (nfix_l1 > 0)
-      hipLaunchKernelGGL((fixup_rows_reduce_kernel<LPR, VEC, RMODE == 1>), dim3((nfix_l1 + per_block - 1) / per_block, col_tiles),
-                         dim3(256), 0, stream, a, fixups, nfix_l1);
-    if (nfix > nfix_l1)
-      hipLaunchKernelGGL((fixup_rows_reduce_kernel<LPR, VEC, RMODE == 1>),
-                         dim3((nfix - nfix_l1 + per_block - 1) / per_block, col_tiles), dim3(256), 0, stream, a,
-                         fixups + nfix_l1, nfix - nfix_l1);
-    return hipGetLastError();
-  }
+  else
+    return launch_fixup_levels<fixup_rows_reduce_kernel<LPR, VEC, RMODE == 1>, LPR>(a, col_tiles, nfix, nfix_l1, fixups, stream);
 }
 
 hipError_t launch_gather_reduce(const ReduceGatherArgs &a, int rmode, int nfix, int nfix_l1, const Fixup *fixups, bool vec4,
                                 hipStream_t stream) {
   if (rmode < 1 || rmode > 3 || (rmode == 3 ? !a.arg_in : (!a.arg_out || (nfix > 0 && !a.ipartial)))) return hipErrorInvalidValue;
-  const int lanes = vec4 ? a.F / 4 : a.F;
-  const int lpr = std::min(64, next_pow2(std::max(lanes, 1)));
-#define HG_RED(L, VV)                                                                              \
-  (rmode == 1   ? launch_gather_reduce_t<L, VV, 1>(a, nfix, nfix_l1, fixups, stream)               \
-   : rmode == 2 ? launch_gather_reduce_t<L, VV, 2>(a, nfix, nfix_l1, fixups, stream)               \
-                : launch_gather_reduce_t<L, VV, 3>(a, nfix, nfix_l1, fixups, stream))
-#define HG_CASE(L) \
-  case L:          \
-    return vec4 ? HG_RED(L, 4) : HG_RED(L, 1);
-  switch (lpr) {
-    HG_CASE(1)
-    HG_CASE(2)
-    HG_CASE(4)
-    HG_CASE(8)
-    HG_CASE(16)
-    HG_CASE(32)
-    HG_CASE(64)
-  }
-#undef HG_CASE
-#undef HG_RED
-  return hipErrorInvalidValue;
+  return dispatch_lpr(lanes_per_row(a.F, vec4), [&](auto L) {
+    return dispatch_vec(vec4, [&](auto V) {
+      return rmode == 1   ? launch_gather_reduce_t<L, V, 1>(a, nfix, nfix_l1, fixups, stream)
+             : rmode == 2 ? launch_gather_reduce_t<L, V, 2>(a, nfix, nfix_l1, fixups, stream)
+                          : launch_gather_reduce_t<L, V, 3>(a, nfix, nfix_l1, fixups, stream);
+    });
+  });
 }
 
 // a_bf16 / b_bf16: rows of A / B are bf16 (16-byte lanes only: the caller has checked widths and alignment)
-#define HG_DOT_BF16(KERN, L, ...)                                                                                          \
-  if (a_bf16 && b_bf16)                                                                                                    \
-    hipLaunchKernelGGL((KERN<L, 4, bf16, bf16>), dim3((unsigned)nblocks), dim3(256), 0, stream, ptr, ind, M, nnz, __VA_ARGS__, \
-                       static_cast<const bf16 *>(A), static_cast<const bf16 *>(B), out);                                   \
-  else if (a_bf16)                                                                                                         \
-    hipLaunchKernelGGL((KERN<L, 4, bf16, float>), dim3((unsigned)nblocks), dim3(256), 0, stream, ptr, ind, M, nnz, __VA_ARGS__, \
-                       static_cast<const bf16 *>(A), static_cast<const float *>(B), out);                                  \
-  else if (b_bf16)                                                                                                         \
-    hipLaunchKernelGGL((KERN<L, 4, float, bf16>), dim3((unsigned)nblocks), dim3(256), 0, stream, ptr, ind, M, nnz, __VA_ARGS__, \
-                       static_cast<const float *>(A), static_cast<const bf16 *>(B), out);
-
 hipError_t launch_incidence_dot_heads(int32_t M, int64_t nnz, int32_t H, int32_t C, const int32_t *ptr, const int32_t *ind,
                                       const void *A, const void *B, float *out, bool lane4, hipStream_t stream, bool a_bf16,
                                       bool b_bf16) {
   if (nnz == 0) return hipSuccess;
   if (M <= 0 || H <= 0 || C <= 0 || (lane4 && C % 4) || ((a_bf16 || b_bf16) && !lane4)) return hipErrorInvalidValue;
-  const int lanes = lane4 ? C / 4 : C;
-  const int lph = std::min(64, next_pow2(std::max(lanes, 1)));
+  const int lph = lanes_per_row(C, lane4);
   const int64_t items = (nnz + kDotRun - 1) / kDotRun * H;
   const int64_t per_block = 256 / lph;
   const int64_t nblocks = (items + per_block - 1) / per_block;
   if (nblocks > 0x7fffffff) return hipErrorInvalidValue;
-  const float *Af = static_cast<const float *>(A), *Bf = static_cast<const float *>(B);
-#define HG_CASE(L)                                                                                                       \
-  case L:                                                                                                                \
-    HG_DOT_BF16(incidence_dot_heads_kernel, L, H, C)                                                                     \
-    else if (lane4) hipLaunchKernelGGL((incidence_dot_heads_kernel<L, 4>), dim3((unsigned)nblocks), dim3(256), 0, stream, ptr, \
-                                       ind, M, nnz, H, C, Af, Bf, out);                                                  \
-    else hipLaunchKernelGGL((incidence_dot_heads_kernel<L, 1>), dim3((unsigned)nblocks), dim3(256), 0, stream, ptr, ind,  \
-                            M, nnz, H, C, Af, Bf, out);                                                                  \
-    return hipGetLastError();
-  switch (lph) {
-    HG_CASE(1)
-    HG_CASE(2)
-    HG_CASE(4)
-    HG_CASE(8)
-    HG_CASE(16)
-    HG_CASE(32)
-    HG_CASE(64)
-  }
-#undef HG_CASE
-  return hipErrorInvalidValue;
+  return dispatch_lpr(lph, [&](auto L) {
+    return dispatch_vec(lane4, [&](auto V) {
+      return dispatch_rows<V>(a_bf16, b_bf16, [&](auto ta, auto tb) {
+        hipLaunchKernelGGL((incidence_dot_heads_kernel<L, V, decltype(ta), decltype(tb)>), dim3((unsigned)nblocks), dim3(256), 0,
+                           stream, ptr, ind, M, nnz, H, C, static_cast<const decltype(ta) *>(A),
+                           static_cast<const decltype(tb) *>(B), out);
+        return hipGetLastError();
+      });
+    });
+  });
 }
 
 hipError_t launch_incidence_dot(int32_t M, int64_t nnz, int32_t F, const int32_t *ptr, const int32_t *ind, const void *A,
                                 const void *B, float *out, bool vec4, hipStream_t stream, bool a_bf16, bool b_bf16) {
   if (nnz == 0) return hipSuccess;
   if (M <= 0 || F <= 0 || (vec4 && F % 4) || ((a_bf16 || b_bf16) && !vec4)) return hipErrorInvalidValue;
-  const int lanes = vec4 ? F / 4 : F;
-  const int lpr = std::min(64, next_pow2(std::max(lanes, 1)));
+  const int lpr = lanes_per_row(F, vec4);
   const int64_t per_block = (int64_t)(256 / lpr) * kDotRun;
   const int64_t nblocks = (nnz + per_block - 1) / per_block;
   if (nblocks > 0x7fffffff) return hipErrorInvalidValue;
-  const float *Af = static_cast<const float *>(A), *Bf = static_cast<const float *>(B);
-#define HG_CASE(L)                                                                                                   \
-  case L:                                                                                                            \
-    HG_DOT_BF16(incidence_dot_kernel, L, F)                                                                          \
-    else if (vec4) hipLaunchKernelGGL((incidence_dot_kernel<L, 4>), dim3((unsigned)nblocks), dim3(256), 0, stream, ptr, ind, M, \
-                                      nnz, F, Af, Bf, out);                                                          \
-    else hipLaunchKernelGGL((incidence_dot_kernel<L, 1>), dim3((unsigned)nblocks), dim3(256), 0, stream, ptr, ind, M,   \
-                            nnz, F, Af, Bf, out);                                                                    \
-    return hipGetLastError();
-  switch (lpr) {
-    HG_CASE(1)
-    HG_CASE(2)
-    HG_CASE(4)
-    HG_CASE(8)
-    HG_CASE(16)
-    HG_CASE(32)
-    HG_CASE(64)
-  }
-#undef HG_CASE
-  return hipErrorInvalidValue;
+  return dispatch_lpr(lpr, [&](auto L) {
+    return dispatch_vec(vec4, [&](auto V) {
+      return dispatch_rows<V>(a_bf16, b_bf16, [&](auto ta, auto tb) {
+        hipLaunchKernelGGL((incidence_dot_kernel<L, V, decltype(ta), decltype(tb)>), dim3((unsigned)nblocks), dim3(256), 0, stream,
+                           ptr, ind, M, nnz, F, static_cast<const decltype(ta) *>(A), static_cast<const decltype(tb) *>(B), out);
+        return hipGetLastError();
+      });
+    });
+  });
 }
-#undef HG_DOT_BF16
 
 // ---- the product of two hyperedge sums (hg_hyperedge_dot_heads_f32): the gradient of a per-hyperedge scale ---------------
 // out[e] = sum_c SA[e, c] * SB[e, c] with SA[e, :] = sum_{p=(e,u)} wa[p, c / C] * A[u, :] and SB likewise from (B, wb).
@@ -3080,30 +3018,15 @@ hipError_t launch_hyperedge_dot(const EdgeDotArgs &a, bool lane4, hipStream_t st
   if (a.F <= 0 || a.heads < 1 || a.C < 1 || (int64_t)a.heads * a.C != a.F || (lane4 && (a.F % 4 || a.C % 4)) || !a.ptr ||
       !a.A || !a.B || !a.out || a.nlong < 0 || (a.nlong > 0 && !a.long_seg))
     return hipErrorInvalidValue;
-  const int lanes = lane4 ? a.F / 4 : a.F;
-  const int lpr = std::min(64, next_pow2(std::max(lanes, 1)));
+  const int lpr = lanes_per_row(a.F, lane4);
   const unsigned nblocks = (unsigned)(((int64_t)a.M + 256 / lpr - 1) / (256 / lpr));
-#define HG_CASE(L)                                                                                                      \
-  case L:                                                                                                               \
-    if (lane4) {                                                                                                        \
-      hipLaunchKernelGGL((hyperedge_dot_kernel<L, 4>), dim3(nblocks), dim3(256), 0, stream, a);                         \
-      if (a.nlong > 0) hipLaunchKernelGGL((hyperedge_dot_long_kernel<L, 4>), dim3(a.nlong), dim3(256), 0, stream, a);   \
-    } else {                                                                                                            \
-      hipLaunchKernelGGL((hyperedge_dot_kernel<L, 1>), dim3(nblocks), dim3(256), 0, stream, a);                         \
-      if (a.nlong > 0) hipLaunchKernelGGL((hyperedge_dot_long_kernel<L, 1>), dim3(a.nlong), dim3(256), 0, stream, a);   \
-    }                                                                                                                   \
-    return hipGetLastError();
-  switch (lpr) {
-    HG_CASE(1)
-    HG_CASE(2)
-    HG_CASE(4)
-    HG_CASE(8)
-    HG_CASE(16)
-    HG_CASE(32)
-    HG_CASE(64)
-  }
-#undef HG_CASE
-  return hipErrorInvalidValue;
+  return dispatch_lpr(lpr, [&](auto L) {
+    return dispatch_vec(lane4, [&](auto V) {
+      hipLaunchKernelGGL((hyperedge_dot_kernel<L, V>), dim3(nblocks), dim3(256), 0, stream, a);
+      if (a.nlong > 0) hipLaunchKernelGGL((hyperedge_dot_long_kernel<L, V>), dim3(a.nlong), dim3(256), 0, stream, a);
+      return hipGetLastError();
+    });
+  });
 }
 
 // out[r] = <A[r, :], B[r, :]>: one lane group per row, a lane's fma chain over its columns (ascending), then the same
@@ -3129,26 +3052,15 @@ hipError_t launch_rows_dot(int64_t nrows, int32_t F, const float *A, const float
                            hipStream_t stream) {
   if (nrows <= 0) return hipSuccess;
   if (F <= 0 || (vec4 && F % 4) || !A || !B || !out) return hipErrorInvalidValue;
-  const int lanes = vec4 ? F / 4 : F;
-  const int lpr = std::min(64, next_pow2(std::max(lanes, 1)));
+  const int lpr = lanes_per_row(F, vec4);
   const int64_t nblocks = (nrows + 256 / lpr - 1) / (256 / lpr);
   if (nblocks > 0x7fffffff) return hipErrorInvalidValue;
-#define HG_CASE(L)                                                                                                        \
-  case L:                                                                                                                 \
-    if (vec4) hipLaunchKernelGGL((rows_dot_kernel<L, 4>), dim3((unsigned)nblocks), dim3(256), 0, stream, nrows, F, A, B, out); \
-    else hipLaunchKernelGGL((rows_dot_kernel<L, 1>), dim3((unsigned)nblocks), dim3(256), 0, stream, nrows, F, A, B, out);  \
-    return hipGetLastError();
-  switch (lpr) {
-    HG_CASE(1)
-    HG_CASE(2)
-    HG_CASE(4)
-    HG_CASE(8)
-    HG_CASE(16)
-    HG_CASE(32)
-    HG_CASE(64)
-  }
-#undef HG_CASE
-  return hipErrorInvalidValue;
+  return dispatch_lpr(lpr, [&](auto L) {
+    return dispatch_vec(vec4, [&](auto V) {
+      hipLaunchKernelGGL((rows_dot_kernel<L, V>), dim3((unsigned)nblocks), dim3(256), 0, stream, nrows, F, A, B, out);
+      return hipGetLastError();
+    });
+  });
 }
 
 hipError_t launch_fixups(const Fixup *fixups, int nfix, int nfix_l1, int32_t F, float *partial, void *Y,
@@ -3164,29 +3076,16 @@ hipError_t launch_fixups(const Fixup *fixups, int nfix, int nfix_l1, int32_t F, 
   a.scaleA = scaleA;
   a.scaleB = scaleB;
   a.scale_map = scale_map;
-  const int lanes = vec4 ? (F + 3) / 4 : F;  // vec4 here: 16-byte lanes over rows of any width (loadu / store_n)
-  const int lpr = std::min(64, next_pow2(std::max(lanes, 1)));
-#define HG_CASE(L)                                                                      \
-  case L:                                                                               \
-    if (Y_bf16) return launch_fixups_t<L, 4, bf16>(a, nfix, nfix_l1, fixups, stream);   \
-    return vec4 ? launch_fixups_t<L, 4>(a, nfix, nfix_l1, fixups, stream) : launch_fixups_t<L, 1>(a, nfix, nfix_l1, fixups, stream);
-  switch (lpr) {
-    HG_CASE(1)
-    HG_CASE(2)
-    HG_CASE(4)
-    HG_CASE(8)
-    HG_CASE(16)
-    HG_CASE(32)
-    HG_CASE(64)
-  }
-#undef HG_CASE
-  return hipErrorInvalidValue;
+  // vec4 here: 16-byte lanes over rows of any width (loadu / store_n)
+  return dispatch_lpr(lanes_per_row_up(F, vec4), [&](auto L) {
+    if (Y_bf16) return launch_fixups_t<L, 4, bf16>(a, nfix, nfix_l1, fixups, stream);
+    return dispatch_vec(vec4, [&](auto V) { return launch_fixups_t<L, V>(a, nfix, nfix_l1, fixups, stream); });
+  });
 }
 
 bool stream_rows_ok(const StreamArgs &a, bool vec4) {
   return vec4 && a.nrec > 0 && a.src_bytes > 0 && a.nrows_src < (1 << 24) && a.F < (1 << 22) &&
-         a.ng == 256 / (fused_tile_row_floats(a.F, true) / 4) &&
-         (size_t)a.max_rec_words * 4 + (size_t)2 * a.cap * 4 <= kLdsMax;
+         a.ng == 256 / lanes_per_row_up(a.F, true) && (size_t)a.max_rec_words * 4 + (size_t)2 * a.cap * 4 <= kLdsMax;
 }
 
 template <int LPR>
@@ -3194,24 +3093,18 @@ static hipError_t launch_stream_t(const StreamArgs &a, hipStream_t stream, bool 
   constexpr int TW = LPR * 4;
   const dim3 grid(a.nrec, (a.F + TW - 1) / TW);
   const size_t lds = (size_t)a.max_rec_words * 4 + (size_t)2 * a.cap * 4;
-  if (src_bf16) return launch_lds<stream_rows_kernel<LPR, 4, 8, bf16, float>>(grid, lds, stream, a);
-  if (dst_bf16) return launch_lds<stream_rows_kernel<LPR, 4, 8, float, bf16>>(grid, lds, stream, a);
-  return launch_lds<stream_rows_kernel<LPR, 4, 8>>(grid, lds, stream, a);
+  return dispatch_rows<4>(src_bf16, dst_bf16, [&](auto ts, auto td) {
+    using TS = decltype(ts);
+    using TD = decltype(td);
+    if constexpr (std::is_same_v<TS, bf16> && std::is_same_v<TD, bf16>) return hipErrorInvalidValue;  // no such instance
+    else return launch_lds<stream_rows_kernel<LPR, 4, 8, TS, TD>>(grid, lds, stream, a);
+  });
 }
 
 hipError_t launch_stream_rows(const StreamArgs &a, hipStream_t stream, bool src_bf16, bool dst_bf16) {
   if (a.nrec == 0) return hipSuccess;
   if ((src_bf16 && dst_bf16) || ((src_bf16 || dst_bf16) && (a.F & 3))) return hipErrorInvalidValue;
-  switch (fused_tile_row_floats(a.F, true) / 4) {
-    case 1: return launch_stream_t<1>(a, stream, src_bf16, dst_bf16);
-    case 2: return launch_stream_t<2>(a, stream, src_bf16, dst_bf16);
-    case 4: return launch_stream_t<4>(a, stream, src_bf16, dst_bf16);
-    case 8: return launch_stream_t<8>(a, stream, src_bf16, dst_bf16);
-    case 16: return launch_stream_t<16>(a, stream, src_bf16, dst_bf16);
-    case 32: return launch_stream_t<32>(a, stream, src_bf16, dst_bf16);
-    case 64: return launch_stream_t<64>(a, stream, src_bf16, dst_bf16);
-  }
-  return hipErrorInvalidValue;
+  return dispatch_lpr(lanes_per_row_up(a.F, true), [&](auto L) { return launch_stream_t<L>(a, stream, src_bf16, dst_bf16); });
 }
 
 size_t hub_pass_lds_bytes(int32_t cap, int32_t row_floats, int32_t max_rec_words) {
@@ -3228,37 +3121,20 @@ static hipError_t launch_hub_t(const HubArgs &a, hipStream_t stream) {
   const dim3 grid(a.nwg, (a.F + TW - 1) / TW);
   const size_t lds = hub_pass_lds_bytes(a.cap, TW, a.max_rec_words);
   if (a.cap < 1024 / LPR) return hipErrorInvalidValue;  // the end-of-launch reduction parks one row per lane group in the tile
-  const int spec = (a.Xe_mat ? 1 : 0) | ((a.degE || a.W) ? 2 : 0) | (a.n_heavy > 0 ? 4 : 0);
-#define HG_HUB(M, S, H) return launch_lds<hub_pass_kernel<LPR, 4, 4, M, S, H, T>, 1024>(grid, lds, stream, a)
-  switch (spec) {
-    case 0: HG_HUB(false, false, false);
-    case 1: HG_HUB(true, false, false);
-    case 2: HG_HUB(false, true, false);
-    case 3: HG_HUB(true, true, false);
-    case 4: HG_HUB(false, false, true);
-    case 5: HG_HUB(true, false, true);
-    case 6: HG_HUB(false, true, true);
-    default: HG_HUB(true, true, true);
-  }
-#undef HG_HUB
+  return dispatch_mat_scaled(a, [&](auto M, auto S) {
+    return dispatch_flag(a.n_heavy > 0, [&](auto H) {  // HEAVY: hubs fed by stream flags
+      return launch_lds<hub_pass_kernel<LPR, 4, 4, M, S, H, T>, 1024>(grid, lds, stream, a);
+    });
+  });
 }
 
 hipError_t launch_hub_pass(const HubArgs &a, bool vec4, hipStream_t stream, bool x_bf16) {
   if (a.nwg == 0) return hipSuccess;
   if (!vec4) return hipErrorInvalidValue;
   if (x_bf16 && (a.F & 3)) return hipErrorInvalidValue;
-  const int lpr = fused_tile_row_floats(a.F, true) / 4;
-#define HG_CASE(L) \
-  case L: return x_bf16 ? launch_hub_t<L, bf16>(a, stream) : launch_hub_t<L, float>(a, stream);
-  switch (lpr) {
-    HG_CASE(4)
-    HG_CASE(8)
-    HG_CASE(16)
-    HG_CASE(32)
-    HG_CASE(64)
-  }
-#undef HG_CASE
-  return hipErrorInvalidValue;
+  return dispatch_lpr<4>(lanes_per_row_up(a.F, true), [&](auto L) {  // no instances of 1 and 2 lanes
+    return x_bf16 ? launch_hub_t<L, bf16>(a, stream) : launch_hub_t<L, float>(a, stream);
+  });
 }
 
 // floats of LDS the panel kernel stages scales in (its sA / sB / sdeg carve-up): degE and W per slot where present, degV per
@@ -3313,7 +3189,6 @@ static hipError_t launch_fused_t(const FusedArgs &a, hipStream_t stream) {
       if constexpr (XF32 && (TW == 32 || TW == 64 || TW == 128)) {
         if (!fast || a.F != TW || a.rows_cap > 4 * (256 / LPR) || (a.F_out & 15)) return hipErrorInvalidValue;
         const size_t lds_l = lds_p - (size_t)a.cap * TW * 4 + (size_t)lin_tile_floats(a.cap, a.rows_cap, TW) * 4;  // slot tile / padded operand rows
-        const int spec = (a.Xe_mat ? 1 : 0) | ((a.degE || a.W) ? 2 : 0);
         // the staged matrix phase alone serves this call (as panel_times_wt decides per panel, for the fullest panel)
         const int nt_all = a.F_out >> 4, nwr = nt_all >= 3 ? 1 : 4 / nt_all;
         const bool staged = a.F_out <= TW && (((a.rows_cap + 15) >> 4) + nwr - 1) / nwr <= (a.F_out > 64 ? 2 : 4);
@@ -3327,33 +3202,21 @@ static hipError_t launch_fused_t(const FusedArgs &a, hipStream_t stream) {
           split = a.epi.wsplit && staged && a.rows_cap > 0 && a.rows_cap <= 32 && 3 * ps <= tile_b && 2 * ps + 32 * 256 <= (int)lds_l;
         }
         if (!split) ad.epi.wsplit = nullptr;
-#define HG_PKL(M, S)                                                                                                          \
-  if constexpr (TW == 128)                                                                                                    \
-    if (split) return launch_lds<fused_packed_kernel<LPR, VEC, UL, true, M, S, true, 256, false, true>>(grid, lds_l, stream, ad); \
-  return staged ? launch_lds<fused_packed_kernel<LPR, VEC, UL, true, M, S, true, 256, false>>(grid, lds_l, stream, ad) \
-                : launch_lds<fused_packed_kernel<LPR, VEC, 8, true, M, S, true, 256, true>>(grid, lds_l, stream, ad)
-        switch (spec) {
-          case 0: HG_PKL(false, false);
-          case 1: HG_PKL(true, false);
-          case 2: HG_PKL(false, true);
-          default: HG_PKL(true, true);
-        }
-#undef HG_PKL
+        return dispatch_mat_scaled(a, [&](auto M, auto S) {
+          if constexpr (TW == 128)
+            if (split) return launch_lds<fused_packed_kernel<LPR, VEC, UL, true, M, S, true, 256, false, true>>(grid, lds_l, stream, ad);
+          return staged ? launch_lds<fused_packed_kernel<LPR, VEC, UL, true, M, S, true, 256, false>>(grid, lds_l, stream, ad)
+                        : launch_lds<fused_packed_kernel<LPR, VEC, 8, true, M, S, true, 256, true>>(grid, lds_l, stream, ad);
+        });
       } else if constexpr (!XF32 && std::is_same_v<TY, T> && TW == 128) {
         // the native bf16 epilogue (fused_linear_b16_ok): K = 128 staged, at most 32 rows -- the one operand plane (32 rows of
         // 256 bytes, read whole) and the [rows][132] fp32 results both fit the tile region, which holds at least 16 x 132 floats
         if (!fast || !fused_linear_b16_ok(a)) return hipErrorInvalidValue;
         const size_t lds_l = lds_p - (size_t)a.cap * TW * 4 + (size_t)lin_tile_floats(a.cap, a.rows_cap, TW) * 4;
         if ((size_t)lin_tile_floats(a.cap, a.rows_cap, TW) * 4 < 32 * 256) return hipErrorInvalidValue;
-        const int spec = (a.Xe_mat ? 1 : 0) | ((a.degE || a.W) ? 2 : 0);
-#define HG_PKB(M, S) return launch_lds<fused_packed_kernel<LPR, VEC, kB16U, true, M, S, true, 256, false, false, T, true>>(grid, lds_l, stream, ad)
-        switch (spec) {
-          case 0: HG_PKB(false, false);
-          case 1: HG_PKB(true, false);
-          case 2: HG_PKB(false, true);
-          default: HG_PKB(true, true);
-        }
-#undef HG_PKB
+        return dispatch_mat_scaled(a, [&](auto M, auto S) {
+          return launch_lds<fused_packed_kernel<LPR, VEC, kB16U, true, M, S, true, 256, false, false, T, true>>(grid, lds_l, stream, ad);
+        });
       } else {
         return hipErrorInvalidValue;
       }
@@ -3362,24 +3225,10 @@ static hipError_t launch_fused_t(const FusedArgs &a, hipStream_t stream) {
       // A grid that does not even fill the chip once is latency-bound, not occupancy-bound:
       // put every row gather of a group in flight at once (U = 16) instead of two batches.
       const bool u16 = a.npanels <= 512;
-      const int spec = (a.Xe_mat ? 1 : 0) | ((a.degE || a.W) ? 2 : 0);
-#define HG_PK(UU, M, S) return launch_lds<fused_packed_kernel<LPR, VEC, UU, true, M, S, false, 256, true, false, T, false, TY>>(grid, lds_p, stream, ad)
-      if (u16) {
-        switch (spec) {
-          case 0: HG_PK(16, false, false);
-          case 1: HG_PK(16, true, false);
-          case 2: HG_PK(16, false, true);
-          default: HG_PK(16, true, true);
-        }
-      } else {
-        switch (spec) {
-          case 0: HG_PK(8, false, false);
-          case 1: HG_PK(8, true, false);
-          case 2: HG_PK(8, false, true);
-          default: HG_PK(8, true, true);
-        }
-      }
-#undef HG_PK
+      return dispatch_mat_scaled(a, [&](auto M, auto S) {
+        return u16 ? launch_lds<fused_packed_kernel<LPR, VEC, 16, true, M, S, false, 256, true, false, T, false, TY>>(grid, lds_p, stream, ad)
+                   : launch_lds<fused_packed_kernel<LPR, VEC, 8, true, M, S, false, 256, true, false, T, false, TY>>(grid, lds_p, stream, ad);
+      });
     }
     if (a.F & 3) return hipErrorInvalidValue;  // other widths ride on the range-checked buffer loads only (hg_api: wide_rows_ok)
   }
@@ -3520,11 +3369,7 @@ hipError_t launch_linear(const LinearArgs &a, hipStream_t stream) {
   return hipGetLastError();
 }
 
-
-int fused_tile_row_floats(int F, bool vec4);
-
 hipError_t launch_fused(const FusedArgs &a, bool vec4, hipStream_t stream, bool xy_bf16, bool y_f32) {
-  const int lpr = fused_tile_row_floats(a.F, vec4) / (vec4 ? 4 : 1);
   if (xy_bf16 && (!vec4 || (a.Wlin && (y_f32 || a.F != 128)) || (a.F & 3))) return hipErrorInvalidValue;
   if (y_f32) {  // bf16 X, fp32 Y: the widths of the bf16 linear layer only
     if (!xy_bf16) return hipErrorInvalidValue;
@@ -3535,53 +3380,27 @@ hipError_t launch_fused(const FusedArgs &a, bool vec4, hipStream_t stream, bool 
       default: return hipErrorInvalidValue;
     }
   }
-#define HG_CASE(L)                                              \
-  case L:                                                       \
-    if (xy_bf16) return launch_fused_t<L, 4, bf16>(a, stream);   \
-    return vec4 ? launch_fused_t<L, 4>(a, stream) : launch_fused_t<L, 1>(a, stream);
-  switch (lpr) {
-    HG_CASE(1)
-    HG_CASE(2)
-    HG_CASE(4)
-    HG_CASE(8)
-    HG_CASE(16)
-    HG_CASE(32)
-    HG_CASE(64)
-  }
-#undef HG_CASE
-  return hipErrorInvalidValue;
+  return dispatch_lpr(lanes_per_row_up(a.F, vec4), [&](auto L) {
+    if (xy_bf16) return launch_fused_t<L, 4, bf16>(a, stream);
+    return dispatch_vec(vec4, [&](auto V) { return launch_fused_t<L, V>(a, stream); });
+  });
 }
 
 // floats per LDS tile row for feature width F (what launch_fused will use): the whole row up to 64 lanes.  Cutting wide
 // rows into 128-byte column tiles (the F = 32 panel shape for every width) lost 7 % at F >= 64.
-int fused_tile_row_floats(int F, bool vec4) {
-  const int lanes = vec4 ? (F + 3) / 4 : F;
-  return std::min(64, next_pow2(std::max(lanes, 1))) * (vec4 ? 4 : 1);
-}
+int fused_tile_row_floats(int F, bool vec4) { return lanes_per_row_up(F, vec4) * (vec4 ? 4 : 1); }
 
 hipError_t launch_push(const PushArgs &a, hipStream_t stream) {
-  const int lpr = std::min(64, next_pow2(std::max(a.F, 1)));
+  const int lpr = lanes_per_row(a.F, false);  // a 4-byte lane per column
   const int per_block = 256 / lpr;
   const int col_tiles = (a.F + lpr - 1) / lpr;
   const int64_t nblocks = (a.n_group + per_block - 1) / per_block;
   if (nblocks == 0) return hipSuccess;
   if (nblocks > 0x7fffffffLL) return hipErrorInvalidValue;
-#define HG_CASE(L)                                                                              \
-  case L:                                                                                       \
-    hipLaunchKernelGGL((push_tasks_kernel<L>), dim3((unsigned)nblocks, col_tiles), dim3(256), 0, \
-                       stream, a);                                                              \
-    break;
-  switch (lpr) {
-    HG_CASE(1)
-    HG_CASE(2)
-    HG_CASE(4)
-    HG_CASE(8)
-    HG_CASE(16)
-    HG_CASE(32)
-    HG_CASE(64)
-  }
-#undef HG_CASE
-  return hipGetLastError();
+  return dispatch_lpr(lpr, [&](auto L) {
+    hipLaunchKernelGGL((push_tasks_kernel<L>), dim3((unsigned)nblocks, col_tiles), dim3(256), 0, stream, a);
+    return hipGetLastError();
+  });
 }
 
 // first_aggr = max (HGNNAggr_f1max_forward_kernel, hgnnaggr_cuda.cu:144-177): per
