@@ -6,15 +6,15 @@ import sys
 import types
 
 from . import _lib  # noqa: F401
-from . import ops, plan, synth  # noqa: F401
+from . import knn_graph, ops, plan, synth  # noqa: F401
 from .balancer import balance_schedule  # noqa: F401
 from .hypergraph import HyperGraph  # noqa: F401
 from .ops import (HGNNAggr, HGNNAggrIncidence, HGNNAggrLinear, UniGNNConv, UniGNNConvdeg,  # noqa: F401
                   UniGNNConvLinear, hgnnaggr_linear, incidence_aggr, incidence_attention_aggr, incidence_dot,
-                  incidence_gather, incidence_softmax, incidence_sum, reduce_aggr)
+                  incidence_gather, incidence_softmax, incidence_sum, knn, knn_incidence_weights, reduce_aggr)
 from .plan import Plan  # noqa: F401
 
-from .models import HypergraphAttnConv, HyperGsysUniSAGE  # noqa: F401
+from .models import DynamicHypergraphConv, HypergraphAttnConv, HyperGsysUniSAGE  # noqa: F401
 
 # The reference builds two top-level extension modules (setup.py:18,32-33).  They ship as real
 # files next to this package (`hgnnaggr.py`, `unignnaggr.py`: repo root, or site-packages after

@@ -51,6 +51,7 @@ SYMBOLS = (
     "hg_gather_rows_attention_heads_f32",
     "hg_gather_rows_incidence_heads_bf16", "hg_aggr_incidence_heads_bf16", "hg_incidence_dot_heads_bf16",
     "hg_gather_rows_reduce_workspace_bytes", "hg_gather_rows_reduce_f32", "hg_gather_rows_select_f32",
+    "hg_knn_f32", "hg_knn_workspace_bytes",
 )
 HG_REDUCE_MAX = 1
 HG_REDUCE_MIN = 2
@@ -291,6 +292,11 @@ def lib():
         L.hg_gather_rows_reduce_f32.argtypes = [vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]
         L.hg_gather_rows_select_f32.restype = ctypes.c_int
         L.hg_gather_rows_select_f32.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, vp, sz, vp]
+    if hasattr(L, "hg_knn_f32"):  # likewise: k nearest neighbours (seg is a host array)
+        L.hg_knn_workspace_bytes.restype = sz
+        L.hg_knn_workspace_bytes.argtypes = [i32, i32, i32, i32, i32]
+        L.hg_knn_f32.restype = ctypes.c_int
+        L.hg_knn_f32.argtypes = [vp, i32, vp, i32, i32, i32, vp, i32, i32, i32, vp, vp, vp, vp, sz, vp]
     L.hg_aggr_push_groups_f32.restype = ctypes.c_int
     L.hg_aggr_push_groups_f32.argtypes = [i32, i32, i32, i64, vp, vp, vp, vp, vp, vp,
                                           vp, vp, vp, vp, vp, vp]

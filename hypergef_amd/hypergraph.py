@@ -50,6 +50,31 @@ class HyperGraph:
         self._init(inc, device, data_name or inc.name, ngs)
         return self
 
+    @classmethod
+    def from_knn(cls, X, k, device, segments=None, data_name="knn", ngs=None):
+        """The hypergraph whose hyperedge i holds vertex i and its k - 1 nearest neighbours among the rows of X [N, F]
+        (float32; HGNN's construction for ModelNet40 / NTU2012, which come without an incidence): ops.knn with
+        self_first on `device`, then M = N, H_T_csrptr = arange(0, N k + 1, k), H_T_colind = idx flattened.  segments:
+        ops.knn's -- many point sets in one tensor, neighbours within a set.  The neighbour table is read back once (the
+        plan is built on the host).  Keeps knn_dist [N, k] (squared), knn_mean [N] and knn_weights()."""
+        from . import knn_graph as _knn
+        Xd = torch.as_tensor(X).detach()
+        if Xd.dtype == torch.float32:  # anything else is ops.knn's refusal
+            Xd = Xd.to(device).contiguous()
+        idx, dist, mean = _knn.knn(Xd, k, segments=segments, self_first=True, return_mean=True)
+        self = cls.__new__(cls)
+        self._init(_knn.incidence_from_knn(idx.cpu().numpy(), data_name), device, data_name, ngs)
+        self.k, self.knn_dist, self.knn_mean = int(k), dist, mean
+        return self
+
+    def knn_weights(self, m_prob=1.0):
+        """HGNN's probabilistic incidence entries of a from_knn hypergraph, [N k] aligned with H_T_colind
+        (ops.knn_incidence_weights): v2e_weight / e2v_weight of HGNNAggrIncidence."""
+        from . import knn_graph as _knn
+        if getattr(self, "knn_dist", None) is None:
+            raise ValueError("knn_weights needs a hypergraph built by HyperGraph.from_knn")
+        return _knn.knn_incidence_weights(self.knn_dist, self.knn_mean, m_prob)
+
     def _init(self, inc, device, data_name, ngs):
         self.device = torch.device(device)
         self.data_name = data_name

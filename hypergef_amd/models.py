@@ -134,6 +134,35 @@ class HyperGsysUniSAGE(nn.Module):
                                    options=self.options)
 
 
+class DynamicHypergraphConv(nn.Module):
+    """A layer that rebuilds its hypergraph from its own input, as DHGNN's layers do: hyperedge i = vertex i and its k - 1
+    nearest neighbours among the rows of X (detached: the search has no gradient),
+        Z = lin(X),   Y = degV . H (degE . (H^T Z))          (HGNNAggr on HyperGraph.from_knn(X, k)),
+    or, with probabilistic=True, the same sums weighted by HGNN's exp(-d2 / mean^2) entries on both hops
+    (HGNNAggrIncidence with hyperg.knn_weights(m_prob)).  segments: ops.knn's host offsets -- a batch of point sets in
+    one tensor, every set its own hypergraph.  The hypergraph of the last forward stays in `hyperg`."""
+
+    def __init__(self, in_channels, out_channels, k, probabilistic=False, segments=None, m_prob=1.0, options=None):
+        super().__init__()
+        if not isinstance(k, int) or not 1 <= k <= 64:
+            raise ValueError("k must be an integer in 1 .. 64, got %r" % (k,))
+        self.options = options
+        self.lin = ops.Linear(in_channels, out_channels, bias=False, options=options)
+        self.in_channels, self.out_channels, self.k = in_channels, out_channels, k
+        self.probabilistic, self.segments, self.m_prob = probabilistic, segments, m_prob
+        self.hyperg = None
+
+    def forward(self, X):
+        from .hypergraph import HyperGraph
+        hyperg = self.hyperg = HyperGraph.from_knn(X.detach(), self.k, X.device, segments=self.segments)
+        Z = self.lin(X)
+        Wdiag = torch.ones(hyperg.num_edges, device=X.device)
+        if self.probabilistic:
+            w = hyperg.knn_weights(self.m_prob)
+            return ops.HGNNAggrIncidence(hyperg, Z, w, w, hyperg.degE, hyperg.degV, Wdiag, options=self.options)
+        return HGNNAggr(hyperg, Z, hyperg.degE, hyperg.degV, Wdiag, "sum", options=self.options)
+
+
 class HypergraphAttnConv(nn.Module):
     """A hypergraph attention layer whose coefficient path runs on this backend's segment kernels.  Single head:
         Z = X W^T,   sv = Z a_v,   se[e] = mean_{u in e} (Z a_e)[u]   (0 for an empty hyperedge),

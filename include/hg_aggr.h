@@ -818,6 +818,40 @@ HG_API int hg_aggr_push_groups_f32(int32_t N, int32_t M, int32_t F, int64_t n_gr
                             const float *degV, const float *W, float *Y,
                             hg_stream_t stream);
 
+/* k nearest neighbours in feature space, without the nq x n distance matrix (csrc/hg_knn.hip): the hyperedges of HGNN's
+ * ModelNet40 / NTU2012 hypergraphs and of DHGNN's layers ("each vertex and its k nearest neighbours").  float32 only.
+ *
+ * Q [nq, F] are the query rows and X [n, F] the candidates, row-major, 4-byte aligned (device memory).
+ *   d2(i, j) = sum_c (Q[i, c] - X[j, c])^2 in float32, in the difference form -- never |q|^2 + |x|^2 - 2 q.x -- summed
+ * over c = 0 .. F - 1 in that order into one accumulator with an explicit fma.  Identical rows give exactly +0.0; inputs
+ * of integer value with d2 < 2^24 give exact results; -0.0 cannot occur; the bits of d2(i, j) are the same on every call,
+ * in every tile and under every cand_slices.
+ * Selection: row i of idx / dist [nq, k] holds the k smallest candidates under the TOTAL ORDER (d2, j) -- the smaller
+ * distance first, among equal distances the smaller index -- written in that order, ascending.  Because the order is
+ * total the result is one bit pattern for every tiling, every cand_slices and every call.  No atomics are used.
+ * self_first != 0 (needs Q == X: the same pointer and nq == n): candidate j == i is ranked before everything else, so
+ * slot 0 of row i is (i, 0.0) even where an exact duplicate of row i has a smaller index.
+ * seg != NULL (HOST memory, [B + 1], ascending, seg[0] = 0, seg[B] = n; needs Q == X): row i competes with the rows of
+ * its own segment only -- many small point sets in one tensor.  A segment of fewer than k rows is HG_ERR_INVALID.  The
+ * offsets are copied to the workspace and the stream is waited for once, before the launch.
+ * mean_dist != NULL: mean_dist[i] = the mean of sqrt(d2(i, j)) (the hardware's square root: 1 ulp, a d2 below the smallest
+ * normal number counts as 0) over every candidate j of row i (its segment, or all n; itself included), summed in an order that is fixed for given (nq, n, seg, cand_slices): bit-identical across calls; it
+ * may differ in the last bits across cand_slices.
+ * cand_slices > 1 gives every workgroup one slice of its candidate tiles; the slices' lists go to the workspace and a
+ * second kernel merges them under the same order.  0 picks 1 or 2 from nq and n (never more: see the workspace bound).
+ * workspace: hg_knn_workspace_bytes(nq, n, F, k, cand_slices) bytes of device memory, at most
+ * 16 * nq * k * max(cand_slices, 1) + 4096; it may be NULL when that is what seg == NULL and one slice need (nothing).
+ * hg_knn_workspace_bytes returns 0 for arguments hg_knn_f32 refuses.
+ * Refusals launch nothing and touch no device, set hg_last_error, and are decided in this order: HG_ERR_INVALID for a
+ * null Q, X, idx or dist; nq, n or F < 1; k outside 1 .. 64; k > n; cand_slices < 0; self_first with Q != X; seg with
+ * Q != X, with B < 1, seg[0] != 0 or seg[B] != n, not ascending, or with a segment shorter than k.  Then
+ * HG_ERR_UNSUPPORTED for cand_slices > 32 or a pointer that is not 4-byte aligned, and HG_ERR_WORKSPACE for a workspace
+ * that is null or too small when one is needed.  NaN inputs: unspecified. */
+HG_API int hg_knn_f32(const float *Q, int32_t nq, const float *X, int32_t n, int32_t F, int32_t k, const int32_t *seg,
+                      int32_t B, int32_t self_first, int32_t cand_slices, int32_t *idx, float *dist, float *mean_dist,
+                      void *workspace, size_t workspace_bytes, hg_stream_t stream);
+HG_API size_t hg_knn_workspace_bytes(int32_t nq, int32_t n, int32_t F, int32_t k, int32_t cand_slices);
+
 #ifdef __cplusplus
 }
 #endif
