@@ -37,6 +37,39 @@ bool aligned_lane(const void *p, bool bf16) { return (reinterpret_cast<uintptr_t
 bool rows_whole_64(const void *base, int32_t F, bool bf16 = false) {
   return ((int64_t)F * (bf16 ? 2 : 4)) % 64 == 0 && (reinterpret_cast<uintptr_t>(base) & 63) == 0;
 }
+bool is_finite(float x) { return x == x && x - x == 0.f; }  // NaN fails the first test, an infinity the second
+// byte size of a table if it fits a buffer descriptor (< 2 GiB), else 0
+int32_t buffer_bytes(int64_t rows, int32_t F, int elem) {
+  const int64_t b = rows * F * elem;
+  return b < ((int64_t)1 << 31) ? (int32_t)b : 0;
+}
+// what the MFMA linear kernels take, fp32 and bf16 alike
+bool linear_widths_ok(int32_t F_in, int32_t F_out) {
+  return F_out > 0 && (F_out % 16) == 0 && (F_in == 32 || F_in == 64 || F_in == 128);
+}
+
+// The refusals below are shared; WHICH of them an entry makes, in which order, with which status and under which name is
+// the entry's own (tests/test_api_refusals_host.py pins it).
+int refuse(int status, const std::string &msg) {
+  hg::set_error(msg);
+  return status;
+}
+bool csr_null(const hg_plan *plan, const int32_t *csrptr_t, const int32_t *colind_t) {
+  return !csrptr_t || (plan->nnz > 0 && !colind_t);
+}
+bool host_only(const hg_plan *plan) { return plan->opts.flags & HG_PLAN_HOST_ONLY; }
+// prefix: "<entry>: " or empty; lacks: "arrays" or "schedule"
+int refuse_host_only(const std::string &prefix, const char *lacks, int status) {
+  return refuse(status, prefix + "plan was built with HG_PLAN_HOST_ONLY and holds no device " + lacks);
+}
+// size, then alignment (a null workspace passes where nothing is needed)
+int check_workspace(const std::string &prefix, const void *workspace, size_t workspace_bytes, size_t need) {
+  if (need > 0 && (!workspace || workspace_bytes < need))
+    return refuse(HG_ERR_WORKSPACE, prefix + "workspace too small: need " + std::to_string(need) + " bytes, got " +
+                                        std::to_string(workspace_bytes));
+  if (reinterpret_cast<uintptr_t>(workspace) & 255) return refuse(HG_ERR_INVALID, prefix + "workspace must be 256-byte aligned");
+  return HG_OK;
+}
 
 int resolve_opts(const hg_plan_opts *in, hg::Opts &o) {
   if (in) {
@@ -430,21 +463,11 @@ int pick_variant_uncached(const hg_plan *plan, int32_t F, bool vec4, int32_t *va
   return HG_OK;
 }
 
-// src_bf16 / dst_bf16: rows of src / dst are bf16 (either or both; they take 16-byte lanes only)
-int run_sched(const hg_plan *p, const hg::Sched &s, int32_t F, const int32_t *ptr,
-              const int32_t *ind, const void *src, const float *scaleA, const float *scaleB,
-              const int32_t *scale_map, const int32_t *dst_map, void *dst, float *partial,
-              hipStream_t stream, bool nt_dst = false, bool src_bf16 = false, bool dst_bf16 = false,
-              const float *w = nullptr, const int32_t *wperm = nullptr, int32_t heads = 1,
-              const hg::AttnGatherArgs *attn = nullptr) {
-  hg::HeadsGatherArgs a;  // heads > 1: w is [nnz, heads] (hg_aggr_incidence_heads_f32)
-  a.heads = heads;
-  a.C = F / heads;
-  a.nt_dst = nt_dst ? 1 : 0;
-  a.w = w;  // per-entry weights (hg_aggr_incidence_f32): the weighted kernel instances
-  a.wperm = wperm;
-  a.scale_map = scale_map;
-  a.dst_map = dst_map;
+int xcd_remap(const hg_plan *p) { return (p->opts.flags & HG_PLAN_NO_XCD_REMAP) ? 0 : 1; }
+
+// What every gather over a panels + wave-task schedule takes from the schedule and the plan's options; no row maps.
+void fill_gather(hg::GatherArgs &a, const hg_plan *p, const hg::Sched &s, int32_t F, const int32_t *ptr, const int32_t *ind,
+                 const void *src, const float *scaleA, const float *scaleB, void *dst, float *partial) {
   a.ptr = ptr;
   a.ind = ind;
   a.src = src;
@@ -452,6 +475,8 @@ int run_sched(const hg_plan *p, const hg::Sched &s, int32_t F, const int32_t *pt
   a.scaleA = scaleA;
   a.scaleB = scaleB;
   a.partial = partial;
+  a.scale_map = nullptr;
+  a.dst_map = nullptr;
   a.panels = s.d_panels;
   a.tasks = s.d_tasks;
   a.npanels = (int32_t)s.panels.size();
@@ -460,7 +485,69 @@ int run_sched(const hg_plan *p, const hg::Sched &s, int32_t F, const int32_t *pt
   a.F = F;
   a.panel_rows = p->opts.panel_rows;
   a.panel_nnz = p->opts.panel_nnz;
-  a.xcd_remap = (p->opts.flags & HG_PLAN_NO_XCD_REMAP) ? 0 : 1;
+  a.xcd_remap = xcd_remap(p);
+}
+
+// The streaming row gather's arguments for schedule rs; nt_dst is the caller's.
+void fill_stream(hg::StreamArgs &sa, const hg_plan *p, const hg::RowStream &rs, int32_t F, const void *src, int32_t src_bytes,
+                 int32_t nrows_src, const float *scaleA, const float *scaleB, void *dst, float *partial) {
+  sa.rec = rs.d_rec;
+  sa.rec_tab = rs.d_rec_tab;
+  sa.nrec = (int32_t)rs.rec_tab.size();
+  sa.ng = rs.ng;
+  sa.cap = rs.cap;
+  sa.max_rec_words = rs.max_rec_words;
+  sa.src = src;
+  sa.src_bytes = src_bytes;
+  sa.nrows_src = nrows_src;
+  sa.scaleA = scaleA;
+  sa.scaleB = scaleB;
+  sa.dst = dst;
+  sa.partial = partial;
+  sa.F = F;
+  sa.xcd_remap = xcd_remap(p);
+}
+
+// The schedule a pull hop runs on, from hg_plan_tune_f32's / hg_plan_set_choice's choice for this width and hop -- kind 0:
+// the streaming row gather, 1: panels + wave tasks, 2: the same kernel on the latency schedule -- or default_kind where
+// nothing is pinned.  Kind 0 is the caller's business (run_hop); every other caller has no streaming form and runs sched[hop].
+const hg::Sched &pull_sched(const hg_plan *p, int hop, int32_t F, int default_kind, int *kind_out = nullptr) {
+  int kind = default_kind;
+  {
+    hg_plan *mp = const_cast<hg_plan *>(p);
+    std::lock_guard<std::mutex> lock(mp->auto_mu);
+    auto it = mp->hop_kernel.find(F);
+    if (it != mp->hop_kernel.end()) kind = hop == 0 ? it->second % 3 : (it->second / 3) % 3;
+  }
+  if (kind_out) *kind_out = kind;
+  return (kind == 2 && p->has_lat) ? p->sched_lat[hop] : p->sched[hop];
+}
+
+// Streaming (nt) stores for a pull hop's output: always for hop 2 (rows of Y); for hop 1 when Xe [M, F] is larger than
+// about three quarters of the 256 MiB Infinity Cache -- a smaller table is read straight back from it by hop 2 and plain stores keep it
+// there (same-box A/B, profiles/r03_experiments.md: 348-695 MB tables -3..-6 %, 2-143 MB tables +9..+16 % with nt)
+// -- and only for rows of whole 64-byte units (F % 16 == 0): others lose with the hint (hg_kernels.hip).  Decided on the
+// bytes of dst's rows; the choice moves no bits.
+bool nt_rows(const hg_plan *p, int hop, const void *dst, int32_t F, bool dst_bf16 = false) {
+  return rows_whole_64(dst, F, dst_bf16) && (hop == 1 || (int64_t)p->M * F * 4 >= ((int64_t)192 << 20));
+}
+
+// src_bf16 / dst_bf16: rows of src / dst are bf16 (either or both; they take 16-byte lanes only)
+int run_sched(const hg_plan *p, const hg::Sched &s, int32_t F, const int32_t *ptr,
+              const int32_t *ind, const void *src, const float *scaleA, const float *scaleB,
+              const int32_t *scale_map, const int32_t *dst_map, void *dst, float *partial,
+              hipStream_t stream, bool nt_dst = false, bool src_bf16 = false, bool dst_bf16 = false,
+              const float *w = nullptr, const int32_t *wperm = nullptr, int32_t heads = 1,
+              const hg::AttnGatherArgs *attn = nullptr) {
+  hg::HeadsGatherArgs a;  // heads > 1: w is [nnz, heads] (hg_aggr_incidence_heads_f32)
+  fill_gather(a, p, s, F, ptr, ind, src, scaleA, scaleB, dst, partial);
+  a.heads = heads;
+  a.C = F / heads;
+  a.nt_dst = nt_dst ? 1 : 0;
+  a.w = w;  // per-entry weights (hg_aggr_incidence_f32): the weighted kernel instances
+  a.wperm = wperm;
+  a.scale_map = scale_map;
+  a.dst_map = dst_map;
   const bool vec4 = (F % 4 == 0) && aligned_lane(src, src_bf16) && aligned_lane(dst, dst_bf16) && aligned16(partial);
   // weighted bf16 rows (hg_gather_rows_incidence_heads_bf16): whole 16-byte lanes inside one head; the attention instances are fp32
   if ((w || attn) && (src_bf16 || dst_bf16) && (attn || !vec4 || a.C % 4 != 0)) {
@@ -585,22 +672,11 @@ int get_segments(const hg_plan *cp, int side, bool upload_it, const int32_t **d_
 
 // Common refusals of the three segment entries; *skip: nothing to do.
 int check_segment_call(const char *who, const hg_plan *plan, int side, const int32_t *csrptr_t, const int32_t *colind_t) {
-  if (!plan) {
-    hg::set_error(std::string(who) + ": null plan");
-    return HG_ERR_INVALID;
-  }
-  if (plan->opts.flags & HG_PLAN_HOST_ONLY) {
-    hg::set_error(std::string(who) + ": plan was built with HG_PLAN_HOST_ONLY and holds no device arrays");
-    return HG_ERR_UNSUPPORTED;
-  }
-  if (side != 0 && side != 1) {
-    hg::set_error(std::string(who) + ": group / side must be 0 (hyperedge) or 1 (vertex)");
-    return HG_ERR_INVALID;
-  }
-  if (!csrptr_t || (plan->nnz > 0 && !colind_t)) {
-    hg::set_error(std::string(who) + ": null array");
-    return HG_ERR_INVALID;
-  }
+  const std::string pre = std::string(who) + ": ";
+  if (!plan) return refuse(HG_ERR_INVALID, pre + "null plan");
+  if (host_only(plan)) return refuse_host_only(pre, "arrays", HG_ERR_UNSUPPORTED);
+  if (side != 0 && side != 1) return refuse(HG_ERR_INVALID, pre + "group / side must be 0 (hyperedge) or 1 (vertex)");
+  if (csr_null(plan, csrptr_t, colind_t)) return refuse(HG_ERR_INVALID, pre + "null array");
   return HG_OK;
 }
 
@@ -685,10 +761,7 @@ int check_heads(const char *who, const hg_plan *plan, int32_t heads, int32_t F) 
                   std::to_string(heads));
     return HG_ERR_INVALID;
   }
-  if (plan->opts.flags & HG_PLAN_HOST_ONLY) {
-    hg::set_error(std::string(who) + ": plan was built with HG_PLAN_HOST_ONLY and holds no device arrays");
-    return HG_ERR_UNSUPPORTED;
-  }
+  if (host_only(plan)) return refuse_host_only(std::string(who) + ": ", "arrays", HG_ERR_UNSUPPORTED);
   if (heads > 1 && (int64_t)std::max<int64_t>(plan->nnz, std::max(plan->N, plan->M)) * heads >= ((int64_t)1 << 40)) {
     hg::set_error(std::string(who) + ": nnz * heads too large");
     return HG_ERR_INVALID;
@@ -703,39 +776,16 @@ int run_hop(const hg_plan *p, int hop, int32_t F, const int32_t *ptr, const int3
   // kernel loads through a range-checked descriptor and stores only the columns that exist
   const bool lanes16 = F % 4 == 0 || F > 8;
   const int64_t nsrc = hop == 0 ? p->N : p->M, sb = nsrc * F * (src_bf16 ? 2 : 4);
-  // Streaming (nt) stores for the hop's output: always for hop 2 (rows of Y); for hop 1 when Xe [M, F] is larger than
-  // about three quarters of the 256 MiB Infinity Cache -- a smaller table is read straight back from it by hop 2 and plain stores keep it
-  // there (same-box A/B, profiles/r03_experiments.md: 348-695 MB tables -3..-6 %, 2-143 MB tables +9..+16 % with nt)
-  // -- and only for rows of whole 64-byte units (F % 16 == 0): others lose with the hint (hg_kernels.hip)
-  const bool nt_out = rows_whole_64(dst, F, dst_bf16) && (hop == 1 || (int64_t)p->M * F * 4 >= ((int64_t)192 << 20));
-  int kind = 0;  // hg_plan_tune_f32's choice for this hop and width: 0 streaming, 1 panels + tasks, 2 latency schedule
-  {
-    hg_plan *mp = const_cast<hg_plan *>(p);
-    std::lock_guard<std::mutex> lock(mp->auto_mu);
-    auto it = mp->hop_kernel.find(F);
-    if (it != mp->hop_kernel.end()) kind = hop == 0 ? it->second % 3 : (it->second / 3) % 3;
-  }
+  const bool nt_out = nt_rows(p, hop, dst, F, dst_bf16);
+  int kind = 0;
+  const hg::Sched &sched = pull_sched(p, hop, F, 0, &kind);
   if (kind == 0 && lanes16 && F < (1 << 22) && nsrc < (1 << 24) && sb > 0 && sb < ((int64_t)1 << 31) && !(p->opts.flags & HG_PLAN_NO_ROW_STREAM)) {
     const int32_t ng = 256 / (hg::fused_tile_row_floats(F, true) / 4);
     const hg::RowStream *rs = nullptr;
     int rc = get_row_stream(p, hop, ng, &rs);
     if (rc != HG_OK) return rc;
     hg::StreamArgs sa;
-    sa.rec = rs->d_rec;
-    sa.rec_tab = rs->d_rec_tab;
-    sa.nrec = (int32_t)rs->rec_tab.size();
-    sa.ng = rs->ng;
-    sa.cap = rs->cap;
-    sa.max_rec_words = rs->max_rec_words;
-    sa.src = src;
-    sa.src_bytes = (int32_t)sb;
-    sa.nrows_src = (int32_t)nsrc;
-    sa.scaleA = scaleA;
-    sa.scaleB = scaleB;
-    sa.dst = dst;
-    sa.partial = partial;
-    sa.F = F;
-    sa.xcd_remap = (p->opts.flags & HG_PLAN_NO_XCD_REMAP) ? 0 : 1;
+    fill_stream(sa, p, *rs, F, src, (int32_t)sb, (int32_t)nsrc, scaleA, scaleB, dst, partial);
     sa.nt_dst = nt_out;
     if (sa.nrec == 0) return HG_OK;
     if (hg::stream_rows_ok(sa, true)) {
@@ -747,8 +797,8 @@ int run_hop(const hg_plan *p, int hop, int32_t F, const int32_t *ptr, const int3
       return HG_OK;
     }
   }
-  return run_sched(p, (kind == 2 && p->has_lat) ? p->sched_lat[hop] : p->sched[hop], F, ptr, ind, src, scaleA, scaleB,
-                   nullptr, nullptr, dst, partial, stream, nt_out, src_bf16, dst_bf16);
+  return run_sched(p, sched, F, ptr, ind, src, scaleA, scaleB, nullptr, nullptr, dst, partial, stream, nt_out, src_bf16,
+                   dst_bf16);
 }
 
 // pull_only: the call runs the pull layout whatever schedules exist (a forced HG_VARIANT_PULL, a single hop): a
@@ -759,10 +809,7 @@ int check_call(const hg_plan *plan, int32_t F, const void *workspace, size_t wor
     hg::set_error("null plan");
     return HG_ERR_INVALID;
   }
-  if (plan->opts.flags & HG_PLAN_HOST_ONLY) {
-    hg::set_error("plan was built with HG_PLAN_HOST_ONLY and holds no device schedule");
-    return HG_ERR_INVALID;
-  }
+  if (host_only(plan)) return refuse_host_only("", "schedule", HG_ERR_INVALID);  // INVALID here, UNSUPPORTED everywhere else
   if (F <= 0) {
     hg::set_error("feature width must be positive");
     return HG_ERR_INVALID;
@@ -771,17 +818,7 @@ int check_call(const hg_plan *plan, int32_t F, const void *workspace, size_t wor
     hg::set_error("feature matrix too large");
     return HG_ERR_INVALID;
   }
-  const size_t need = size_mode == kSizeLater ? 0 : workspace_need(plan, F, size_mode == kSizePull);
-  if (need > 0 && (!workspace || workspace_bytes < need)) {
-    hg::set_error("workspace too small: need " + std::to_string(need) + " bytes, got " +
-                  std::to_string(workspace_bytes));
-    return HG_ERR_WORKSPACE;
-  }
-  if (workspace && (reinterpret_cast<uintptr_t>(workspace) & 255)) {
-    hg::set_error("workspace must be 256-byte aligned");
-    return HG_ERR_INVALID;
-  }
-  return HG_OK;
+  return check_workspace("", workspace, workspace_bytes, size_mode == kSizeLater ? 0 : workspace_need(plan, F, size_mode == kSizePull));
 }
 
 int plan_build(hg_plan **out, int32_t N, int32_t M, const int32_t *csrptr_t,
@@ -1121,7 +1158,7 @@ int hg_gather_rows_f32(const hg_plan *plan, int32_t hop, int32_t F, const int32_
                        hg_stream_t stream) {
   int rc = check_call(plan, F, workspace, workspace_bytes, kSizePull);
   if (rc != HG_OK) return rc;
-  if ((hop != 0 && hop != 1) || !src || !dst || (hop == 0 && (!csrptr_t || (plan->nnz > 0 && !colind_t)))) {
+  if ((hop != 0 && hop != 1) || !src || !dst || (hop == 0 && csr_null(plan, csrptr_t, colind_t))) {
     hg::set_error("hg_gather_rows_f32: bad argument");
     return HG_ERR_INVALID;
   }
@@ -1214,6 +1251,157 @@ struct LinReq {
   int64_t nrows_left = 0;
 };
 
+// the caller bound exactly these arrays to schedule f (hg_plan_bind_scales)
+static bool scales_bound(const hg::FusedSched *f, const float *degE, const float *degV, const float *W) {
+  return (degE || degV || W) && f->bound_degE == degE && f->bound_W == W && f->bound_degV == degV;
+}
+
+// The schedule a fused call with a linear epilogue runs: the epilogue's own (whole 16-row tiles per panel, get_fused) in
+// place of *f where one exists.  Its scales follow the default schedule's binding -- gathered here on first use, on this
+// call's stream, which every later use is ordered behind or waits for through the caller's binding event (plan.py,
+// _bind_scales).
+static int lin_sched(const hg_plan *plan, int32_t F, bool vec4, const float *degE, const float *degV, const float *W,
+                     hipStream_t s, const hg::FusedSched **f) {
+  const hg::FusedSched *fl = nullptr;
+  int rc = get_fused(plan, F, vec4, &fl, true);
+  if (rc != HG_OK) return rc;
+  if (fl == *f || !fl->fixups.empty()) return HG_OK;
+  if (scales_bound(*f, degE, degV, W) && !scales_bound(fl, degE, degV, W)) {
+    hg::FusedSched *m = const_cast<hg::FusedSched *>(fl);
+    std::lock_guard<std::mutex> lock(const_cast<hg_plan *>(plan)->fused_mu);
+    if ((rc = gather_bound_scales(m, degE, degV, W, s)) != HG_OK) return rc;
+    // first use only (it also allocated): wait for the gather, so that a later call on ANY stream finds the arrays
+    // complete -- the caller's binding event (plan.py) covers the default schedule's gather, not this one
+    (void)hipStreamSynchronize(s);
+    m->bound_degE = degE;
+    m->bound_W = W;
+    m->bound_degV = degV;
+    m->bound_W_is_one = (*f)->bound_W_is_one;
+  }
+  *f = fl;
+  return HG_OK;
+}
+
+// One fused call, as its four parts see it: the schedule, the tables and the workspace's carve-up.
+struct FusedCall {
+  const hg_plan *plan;
+  const hg::FusedSched *f;
+  int32_t F;
+  bool vec4, bf16, ybf16;  // lane layout; rows of X are bf16; rows of Y are bf16
+  const void *X;
+  const float *degE, *degV, *W;
+  void *Y;
+  float *Xe, *mat_partial, *partial;
+  int32_t x_bytes, mat_bytes;
+  hipStream_t s;
+};
+
+// (a) materialised hyperedges (more than t_big members): Xe_mat rows
+static int fused_materialise(const FusedCall &c) {
+  const hg::FusedSched *f = c.f;
+  hg::StreamArgs sa;
+  fill_stream(sa, c.plan, f->mat_stream, c.F, c.X, c.x_bytes, c.plan->N, c.degE, c.W, c.Xe, c.mat_partial);
+  if (!hg::stream_rows_ok(sa, c.vec4))  // the streaming row gather; else the general kernel
+    return run_sched(c.plan, f->mat_sched, c.F, f->d_mat_ptr, f->d_mat_ind, c.X, c.degE, c.W, f->d_mat_eid, nullptr, c.Xe,
+                     c.mat_partial, c.s, false, c.bf16);
+  hipError_t e = hg::launch_stream_rows(sa, c.s, c.bf16, false);
+  if (e == hipSuccess)
+    e = hg::launch_fixups(f->mat_stream.d_fixups, (int)f->mat_stream.fixups.size(), f->mat_stream.n_fix_l1, c.F, sa.partial,
+                          c.Xe, c.degE, c.W, f->d_mat_eid, c.vec4, c.s);
+  if (e != hipSuccess) return hip_fail("stream_rows launch", e);
+  return HG_OK;
+}
+
+// (b) register hubs: persistent workgroups stream the hyperedges, running sums in registers
+static int fused_hub_pass(const FusedCall &c) {
+  const hg::FusedSched *f = c.f;
+  hg::HubArgs h;
+  h.rec = f->hub.d_rec;
+  h.rec_tab = f->hub.d_rec_tab;
+  h.wg_first = f->hub.d_wg_first;
+  h.vslot0 = f->hub.d_vslot0;
+  h.nwg = f->hub.nwg;
+  h.ng = f->hub.ng;
+  h.cap = f->hub.cap;
+  h.max_rec_words = f->hub.max_rec_words;
+  h.X = c.X;
+  h.Xe_mat = f->n_mat > 0 ? c.Xe : nullptr;
+  h.degE = c.degE;
+  h.W = c.W;
+  h.partial = c.partial;
+  h.F = c.F;
+  h.x_bytes = c.x_bytes;
+  h.mat_bytes = c.mat_bytes;
+  h.nrows_x = c.plan->N;
+  h.nrows_mat = f->n_mat;
+  h.n_heavy = f->hub.n_heavy;
+  for (int q = 0; q < hg::kHubHeavy; q++) h.hslot0[q] = f->hub.hslot0[q];
+  hipError_t e = hg::launch_hub_pass(h, c.vec4, c.s, c.bf16);
+  if (e != hipSuccess) return hip_fail("hub_pass launch", e);
+  return HG_OK;
+}
+
+// (c) everything else: vertex panels with the hyperedge sums staged in LDS.  bound: the scales pre-gathered into panel
+// order are these arrays'; lin, where not null: the panels run its linear epilogue if the kernel takes these widths; lb16:
+// the call is hg_aggr_linear_res_bf16's.
+static int fused_panels(const FusedCall &c, bool bound, LinReq *lin, bool lb16) {
+  const hg::FusedSched *f = c.f;
+  hg::FusedArgs a;
+  a.npanels = (int32_t)f->panels.size();
+  a.X = c.X;
+  a.Xe_mat = f->n_mat > 0 ? c.Xe : nullptr;  // null = no materialised rows: kernels skip that path
+  a.degE = c.degE;
+  a.W = c.W;
+  a.degV = c.degV;
+  a.Y = c.Y;
+  a.partial = c.partial;
+  a.F = c.F;
+  a.cap = f->cap;
+  a.rows_cap = f->rows_cap;
+  a.xcd_remap = xcd_remap(c.plan);
+  a.rec = f->d_rec;
+  a.rec_tab = f->d_rec_tab;
+  a.eid_all = f->d_eid_all;
+  a.max_rec_words = f->max_rec_words;
+  a.ng = f->ng;
+  a.x_bytes = c.x_bytes;
+  a.mat_bytes = c.mat_bytes;
+  a.nrows_x = c.plan->N;
+  a.nrows_mat = f->n_mat;
+  a.y_nt = rows_whole_64(c.Y, c.F, c.ybf16);
+  // a pre-pass that read at least a quarter of the incidences' member rows: see fused_packed_kernel's run order
+  a.reverse_runs = f->n_mat > 0 && !f->mat_ptr.empty() && (int64_t)f->mat_ptr.back() * 4 >= c.plan->nnz;
+  a.bsA = bound ? f->d_bsA : nullptr;
+  a.bsB = bound ? f->d_bsB : nullptr;
+  a.bsD = bound ? f->d_bsD : nullptr;
+  if (lin) {
+    a.Wlin = lin->Wlin;
+    a.F_out = lin->F_out;
+    a.epi = lin->epi;
+    if (lb16 ? hg::fused_linear_b16_ok(a) : hg::fused_linear_ok(a)) {
+      a.Y = lin->Y;
+      lin->done = f->fixups.empty();
+      lin->in_panel = true;
+      lin->rowmap = f->d_fix_rows;
+      lin->nrows_left = (int64_t)f->fix_rows.size();
+      if (lb16) a.y_nt = rows_whole_64(lin->Y, lin->F_out, true);
+    } else {
+      a.Wlin = nullptr;
+    }
+  }
+  hipError_t e = hg::launch_fused(a, c.vec4, c.s, c.bf16, lb16 && !a.Wlin);
+  if (e != hipSuccess) return hip_fail("fused_panel launch", e);
+  return HG_OK;
+}
+
+// (d) hubs and split vertices: Y[v] = degV[v] * (sum of the vertex's partial rows), fixed order
+static int fused_fixups(const FusedCall &c) {
+  const hipError_t e = hg::launch_fixups(c.f->d_fixups, (int)c.f->fixups.size(), c.f->n_fix_l1, c.F, c.partial, c.Y, c.degV,
+                                         nullptr, nullptr, c.vec4, c.s, rows_whole_64(c.Y, c.F, c.ybf16), c.ybf16);
+  if (e != hipSuccess) return hip_fail("fixup launch", e);
+  return HG_OK;
+}
+
 // bf16: rows of X and Y are bf16 (hg_aggr_fused_bf16 has checked F % 4 == 0 and 8-byte alignment, so the lane layout is the one
 // an fp32 call of the same width takes); everything between them is fp32 as in an fp32 call.  No linear epilogue.
 static int aggr_impl(const hg_plan *plan, int32_t F, const int32_t *csrptr_t,
@@ -1241,7 +1429,7 @@ static int aggr_impl(const hg_plan *plan, int32_t F, const int32_t *csrptr_t,
   // the size is checked against the layout that actually runs, once the variant is resolved
   int rc = check_call(plan, F, workspace, workspace_bytes, kSizeLater);
   if (rc != HG_OK) return rc;
-  if (!csrptr_t || (plan->nnz > 0 && !colind_t) || !X || !Y) {
+  if (csr_null(plan, csrptr_t, colind_t) || !X || !Y) {
     hg::set_error(std::string(fn) + ": null array");
     return HG_ERR_INVALID;
   }
@@ -1263,29 +1451,7 @@ static int aggr_impl(const hg_plan *plan, int32_t F, const int32_t *csrptr_t,
   }
   if (variant == HG_VARIANT_FUSED) {
     if (!f && (rc = get_fused(plan, F, vec4, &f)) != HG_OK) return rc;
-    if (lin && aligned && f->fixups.empty()) {
-      // the epilogue's own schedule (whole 16-row tiles per panel, get_fused); its scales follow the default
-      // schedule's binding -- gathered here on first use, on this call's stream, which every later use is ordered behind
-      // or waits for through the caller's binding event (plan.py, _bind_scales)
-      const hg::FusedSched *fl = nullptr;
-      if ((rc = get_fused(plan, F, vec4, &fl, true)) != HG_OK) return rc;
-      if (fl != f && fl->fixups.empty()) {
-        const bool dflt_bound = (degE || degV || W) && f->bound_degE == degE && f->bound_W == W && f->bound_degV == degV;
-        if (dflt_bound && !(fl->bound_degE == degE && fl->bound_W == W && fl->bound_degV == degV)) {
-          hg::FusedSched *m = const_cast<hg::FusedSched *>(fl);
-          std::lock_guard<std::mutex> lock(const_cast<hg_plan *>(plan)->fused_mu);
-          if ((rc = gather_bound_scales(m, degE, degV, W, s)) != HG_OK) return rc;
-          // first use only (it also allocated): wait for the gather, so that a later call on ANY stream finds the arrays
-          // complete -- the caller's binding event (plan.py) covers the default schedule's gather, not this one
-          (void)hipStreamSynchronize(s);
-          m->bound_degE = degE;
-          m->bound_W = W;
-          m->bound_degV = degV;
-          m->bound_W_is_one = f->bound_W_is_one;
-        }
-        f = fl;
-      }
-    }
+    if (lin && aligned && f->fixups.empty() && (rc = lin_sched(plan, F, vec4, degE, degV, W, s, &f)) != HG_OK) return rc;
     const FusedCarve fc = fused_carve(*f, F);
     if (fc.total > 0 && (!workspace || fc.total > workspace_bytes)) {
       hg::set_error("workspace too small for the fused schedule: need " + std::to_string(fc.total) + " bytes, got " +
@@ -1293,129 +1459,21 @@ static int aggr_impl(const hg_plan *plan, int32_t F, const int32_t *csrptr_t,
                     " (hg_plan_workspace_bytes covers it once hg_plan_prepare has built the schedule)");
       return HG_ERR_WORKSPACE;
     }
-    float *partial = reinterpret_cast<float *>(ws + fc.part);
     // scales pre-gathered into panel order, if the caller bound exactly these arrays
-    const bool bound = (degE || degV || W) && f->bound_degE == degE && f->bound_W == W && f->bound_degV == degV;
+    const bool bound = scales_bound(f, degE, degV, W);
     if (bound && W && f->bound_W_is_one) W = nullptr;  // multiplying by exactly 1.0f is the identity: same bits, less work
-    const int64_t xb = (int64_t)plan->N * F * (bf16 ? 2 : 4), mb = (int64_t)f->n_mat * F * 4;
-    const int32_t x_bytes = xb < ((int64_t)1 << 31) ? (int32_t)xb : 0;
-    const int32_t mat_bytes = mb < ((int64_t)1 << 31) ? (int32_t)mb : 0;
-    // (a) materialised hyperedges (more than t_big members): Xe_mat rows
-    if (f->n_mat > 0) {
-      hg::StreamArgs sa;
-      sa.rec = f->mat_stream.d_rec;
-      sa.rec_tab = f->mat_stream.d_rec_tab;
-      sa.nrec = (int32_t)f->mat_stream.rec_tab.size();
-      sa.ng = f->mat_stream.ng;
-      sa.cap = f->mat_stream.cap;
-      sa.max_rec_words = f->mat_stream.max_rec_words;
-      sa.src = X;
-      sa.src_bytes = x_bytes;
-      sa.nrows_src = plan->N;
-      sa.scaleA = degE;
-      sa.scaleB = W;
-      sa.dst = Xe;
-      sa.partial = reinterpret_cast<float *>(ws + fc.mat_part);
-      sa.F = F;
-      sa.xcd_remap = (plan->opts.flags & HG_PLAN_NO_XCD_REMAP) ? 0 : 1;
-      if (hg::stream_rows_ok(sa, vec4)) {  // the streaming row gather; else the general kernel
-        hipError_t e = hg::launch_stream_rows(sa, s, bf16, false);
-        if (e == hipSuccess)
-          e = hg::launch_fixups(f->mat_stream.d_fixups, (int)f->mat_stream.fixups.size(), f->mat_stream.n_fix_l1, F,
-                                sa.partial, Xe, degE, W, f->d_mat_eid, vec4, s);
-        if (e != hipSuccess) return hip_fail("stream_rows launch", e);
-      } else {
-        rc = run_sched(plan, f->mat_sched, F, f->d_mat_ptr, f->d_mat_ind, X, degE, W, f->d_mat_eid,
-                       nullptr, Xe, reinterpret_cast<float *>(ws + fc.mat_part), s, false, bf16);
-        if (rc != HG_OK) return rc;
-      }
-    }
-    // (b) register hubs: persistent workgroups stream the hyperedges, running sums in registers
-    if (f->hub.K > 0) {
-      hg::HubArgs h;
-      h.rec = f->hub.d_rec;
-      h.rec_tab = f->hub.d_rec_tab;
-      h.wg_first = f->hub.d_wg_first;
-      h.vslot0 = f->hub.d_vslot0;
-      h.nwg = f->hub.nwg;
-      h.ng = f->hub.ng;
-      h.cap = f->hub.cap;
-      h.max_rec_words = f->hub.max_rec_words;
-      h.X = X;
-      h.Xe_mat = f->n_mat > 0 ? Xe : nullptr;
-      h.degE = degE;
-      h.W = W;
-      h.partial = partial;
-      h.F = F;
-      h.x_bytes = x_bytes;
-      h.mat_bytes = mat_bytes;
-      h.nrows_x = plan->N;
-      h.nrows_mat = f->n_mat;
-      h.n_heavy = f->hub.n_heavy;
-      for (int q = 0; q < hg::kHubHeavy; q++) h.hslot0[q] = f->hub.hslot0[q];
-      hipError_t e = hg::launch_hub_pass(h, vec4, s, bf16);
-      if (e != hipSuccess) return hip_fail("hub_pass launch", e);
-    }
-    // (c) everything else: vertex panels with the hyperedge sums staged in LDS
-    hg::FusedArgs a;
-    a.npanels = (int32_t)f->panels.size();
-    a.X = X;
-    a.Xe_mat = f->n_mat > 0 ? Xe : nullptr;  // null = no materialised rows: kernels skip that path
-    a.degE = degE;
-    a.W = W;
-    a.degV = degV;
-    a.Y = Y;
-    a.partial = partial;
-    a.F = F;
-    a.cap = f->cap;
-    a.rows_cap = f->rows_cap;
-    a.xcd_remap = (plan->opts.flags & HG_PLAN_NO_XCD_REMAP) ? 0 : 1;
-    a.rec = f->d_rec;
-    a.rec_tab = f->d_rec_tab;
-    a.eid_all = f->d_eid_all;
-    a.max_rec_words = f->max_rec_words;
-    a.ng = f->ng;
-    a.x_bytes = x_bytes;
-    a.mat_bytes = mat_bytes;
-    a.nrows_x = plan->N;
-    a.nrows_mat = f->n_mat;
-    a.y_nt = rows_whole_64(Y, F, ybf16);
-    // a pre-pass that read at least a quarter of the incidences' member rows: see fused_packed_kernel's run order
-    a.reverse_runs = f->n_mat > 0 && !f->mat_ptr.empty() && (int64_t)f->mat_ptr.back() * 4 >= plan->nnz;
-    a.bsA = bound ? f->d_bsA : nullptr;
-    a.bsB = bound ? f->d_bsB : nullptr;
-    a.bsD = bound ? f->d_bsD : nullptr;
+    const FusedCall fu = {plan, f, F, vec4, bf16, ybf16, X, degE, degV, W, Y, Xe, reinterpret_cast<float *>(ws + fc.mat_part),
+                          reinterpret_cast<float *>(ws + fc.part), buffer_bytes(plan->N, F, bf16 ? 2 : 4),
+                          buffer_bytes(f->n_mat, F, 4), s};
+    if (f->n_mat > 0 && (rc = fused_materialise(fu)) != HG_OK) return rc;
+    if (f->hub.K > 0 && (rc = fused_hub_pass(fu)) != HG_OK) return rc;
     // rows produced outside the panels (hubs, split vertices) get no epilogue: two-step then
     // (the bf16 epilogue's panels leave such rows to the fixup pass and the caller's rows kernel: LinReq)
-    if (lin && (f->fixups.empty() || lb16) && aligned) {
-      a.Wlin = lin->Wlin;
-      a.F_out = lin->F_out;
-      a.epi = lin->epi;
-      if (lb16 ? hg::fused_linear_b16_ok(a) : hg::fused_linear_ok(a)) {
-        a.Y = lin->Y;
-        lin->done = f->fixups.empty();
-        lin->in_panel = true;
-        lin->rowmap = f->d_fix_rows;
-        lin->nrows_left = (int64_t)f->fix_rows.size();
-        if (lb16) a.y_nt = rows_whole_64(lin->Y, lin->F_out, true);
-      } else {
-        a.Wlin = nullptr;
-      }
-    }
-    hipError_t e = hg::launch_fused(a, vec4, s, bf16, lb16 && !a.Wlin);
-    if (e != hipSuccess) return hip_fail("fused_panel launch", e);
-    // (d) hubs and split vertices: Y[v] = degV[v] * (sum of the vertex's partial rows), fixed order
-    if (!f->fixups.empty()) {
-      e = hg::launch_fixups(f->d_fixups, (int)f->fixups.size(), f->n_fix_l1, F, partial, Y, degV, nullptr, nullptr, vec4, s,
-                            rows_whole_64(Y, F, ybf16), ybf16);
-      if (e != hipSuccess) return hip_fail("fixup launch", e);
-    }
-    return HG_OK;
+    const bool may_lin = lin && (f->fixups.empty() || lb16) && aligned;
+    if ((rc = fused_panels(fu, bound, may_lin ? lin : nullptr, lb16)) != HG_OK) return rc;
+    return f->fixups.empty() ? HG_OK : fused_fixups(fu);
   }
-  if (c.total > 0 && (!workspace || workspace_bytes < c.total)) {
-    hg::set_error("workspace too small: need " + std::to_string(c.total) + " bytes, got " + std::to_string(workspace_bytes));
-    return HG_ERR_WORKSPACE;
-  }
+  if ((rc = check_workspace("", workspace, workspace_bytes, c.total)) != HG_OK) return rc;
   // hop 1: Xe[e] = ((sum_{u in e} X[u]) * degE[e]) * W[e]
   rc = run_hop(plan, 0, F, csrptr_t, colind_t, X, degE, W, Xe,
                reinterpret_cast<float *>(ws + c.part[0]), s, bf16, false);
@@ -1569,7 +1627,7 @@ int hg_plan_has_latency_schedule(const hg_plan *plan) {
 }
 
 int hg_linear_pack_f32(int32_t F_out, int32_t F_in, const float *Wlin, float *wfrag, hg_stream_t stream) {
-  if (!Wlin || !wfrag || F_out <= 0 || (F_out % 16) || (F_in != 32 && F_in != 64 && F_in != 128)) {
+  if (!Wlin || !wfrag || !linear_widths_ok(F_in, F_out)) {
     hg::set_error("hg_linear_pack_f32: need F_in in {32, 64, 128}, F_out a positive multiple of 16");
     return Wlin && wfrag ? HG_ERR_UNSUPPORTED : HG_ERR_INVALID;
   }
@@ -1592,20 +1650,9 @@ int hg_linear_pack_ex_f32(int32_t F_out, int32_t F_in, const float *Wlin, float 
   return HG_OK;
 }
 
-int hg_linear_rows_f32(int64_t nrows, int32_t F_in, int32_t F_out, const float *T, const float *wfrag, float *Y,
-                       hg_stream_t stream) {
-  if (nrows < 0 || !wfrag || (nrows > 0 && (!T || !Y))) {
-    hg::set_error("hg_linear_rows_f32: bad argument");
-    return HG_ERR_INVALID;
-  }
-  if (F_out <= 0 || (F_out % 16) || (F_in != 32 && F_in != 64 && F_in != 128)) {
-    hg::set_error("hg_linear_rows_f32: need F_in in {32, 64, 128}, F_out a positive multiple of 16");
-    return HG_ERR_UNSUPPORTED;
-  }
-  if (!aligned16(T) || !aligned16(wfrag) || !aligned16(Y)) {
-    hg::set_error("hg_linear_rows_f32: arrays must be 16-byte aligned");
-    return HG_ERR_INVALID;
-  }
+// Y = epilogue(T) . Wlin^T over nrows whole rows of T on the standalone MFMA kernel
+static int linear_rows(int64_t nrows, int32_t F_in, int32_t F_out, const float *T, const float *wfrag, float *Y,
+                       const hg::LinEpilogue &epi, hipStream_t stream) {
   hg::LinearArgs la;
   la.T = T;
   la.Wlin = wfrag;
@@ -1614,9 +1661,27 @@ int hg_linear_rows_f32(int64_t nrows, int32_t F_in, int32_t F_out, const float *
   la.nrows = nrows;
   la.F_in = F_in;
   la.F_out = F_out;
-  hipError_t e = hg::launch_linear(la, static_cast<hipStream_t>(stream));
+  la.epi = epi;
+  hipError_t e = hg::launch_linear(la, stream);
   if (e != hipSuccess) return hip_fail("linear_rows launch", e);
   return HG_OK;
+}
+
+int hg_linear_rows_f32(int64_t nrows, int32_t F_in, int32_t F_out, const float *T, const float *wfrag, float *Y,
+                       hg_stream_t stream) {
+  if (nrows < 0 || !wfrag || (nrows > 0 && (!T || !Y))) {
+    hg::set_error("hg_linear_rows_f32: bad argument");
+    return HG_ERR_INVALID;
+  }
+  if (!linear_widths_ok(F_in, F_out)) {
+    hg::set_error("hg_linear_rows_f32: need F_in in {32, 64, 128}, F_out a positive multiple of 16");
+    return HG_ERR_UNSUPPORTED;
+  }
+  if (!aligned16(T) || !aligned16(wfrag) || !aligned16(Y)) {
+    hg::set_error("hg_linear_rows_f32: arrays must be 16-byte aligned");
+    return HG_ERR_INVALID;
+  }
+  return linear_rows(nrows, F_in, F_out, T, wfrag, Y, hg::LinEpilogue(), static_cast<hipStream_t>(stream));
 }
 
 size_t hg_linear_wgrad_workspace_bytes(int64_t nrows, int32_t F_a, int32_t F_b) {
@@ -1667,7 +1732,7 @@ static int aggr_linear_res(const hg_plan *plan, int32_t F_in, int32_t F_out, con
     hg::set_error("hg_aggr_linear_f32: null argument");
     return HG_ERR_INVALID;
   }
-  if (F_out <= 0 || (F_out % 16) || (F_in != 32 && F_in != 64 && F_in != 128)) {
+  if (!linear_widths_ok(F_in, F_out)) {
     hg::set_error("hg_aggr_linear_f32: need F_in in {32, 64, 128}, F_out a positive multiple of 16");
     return HG_ERR_UNSUPPORTED;
   }
@@ -1695,18 +1760,7 @@ static int aggr_linear_res(const hg_plan *plan, int32_t F_in, int32_t F_out, con
   lin.epi.T_out = T_out;
   int rc = aggr_impl(plan, F_in, csrptr_t, colind_t, X, degE, degV, W, T, workspace, base, variant, stream, &lin);
   if (rc != HG_OK || lin.done) return rc;
-  hg::LinearArgs la;
-  la.T = T;
-  la.Wlin = wfrag;
-  la.rowmap = nullptr;
-  la.Y = Y;
-  la.nrows = plan->N;
-  la.F_in = F_in;
-  la.F_out = F_out;
-  la.epi = lin.epi;
-  hipError_t e = hg::launch_linear(la, static_cast<hipStream_t>(stream));
-  if (e != hipSuccess) return hip_fail("linear_rows launch", e);
-  return HG_OK;
+  return linear_rows(plan->N, F_in, F_out, T, wfrag, Y, lin.epi, static_cast<hipStream_t>(stream));
 }
 
 int hg_aggr_linear_res_f32(const hg_plan *plan, int32_t F_in, int32_t F_out, const int32_t *csrptr_t,
@@ -1741,12 +1795,8 @@ int hg_aggr_linear_f32(const hg_plan *plan, int32_t F_in, int32_t F_out, const i
 
 // ---- the linear layer on bf16 rows (native bf16 MFMA epilogue) --------------------------------------------------------
 
-static bool b16_widths_ok(int32_t F_in, int32_t F_out) {
-  return F_out > 0 && (F_out % 16) == 0 && (F_in == 32 || F_in == 64 || F_in == 128);
-}
-
 size_t hg_linear_pack_bf16_bytes(int32_t F_out, int32_t F_in) {
-  return b16_widths_ok(F_in, F_out) ? (size_t)F_out * F_in * 2 : 0;
+  return linear_widths_ok(F_in, F_out) ? (size_t)F_out * F_in * 2 : 0;
 }
 
 int hg_linear_pack_bf16(int32_t F_out, int32_t F_in, const uint16_t *Wlin, void *wfrag, hg_stream_t stream) {
@@ -1754,7 +1804,7 @@ int hg_linear_pack_bf16(int32_t F_out, int32_t F_in, const uint16_t *Wlin, void 
     hg::set_error("hg_linear_pack_bf16: null argument");
     return HG_ERR_INVALID;
   }
-  if (!b16_widths_ok(F_in, F_out) || !aligned16(wfrag)) {
+  if (!linear_widths_ok(F_in, F_out) || !aligned16(wfrag)) {
     hg::set_error("hg_linear_pack_bf16: need F_in in {32, 64, 128}, F_out a positive multiple of 16, wfrag 16-byte aligned");
     return HG_ERR_UNSUPPORTED;
   }
@@ -1763,13 +1813,28 @@ int hg_linear_pack_bf16(int32_t F_out, int32_t F_in, const uint16_t *Wlin, void 
   return HG_OK;
 }
 
+// What both callers of linear_rows_bf16_kernel fill alike: row i of the call is row rowmap[i] (null: i) of T and Y.
+static hg::LinearB16Args linear_b16_args(int64_t nrows, int32_t F_in, int32_t F_out, const void *T, const void *wfrag,
+                                         const int32_t *rowmap, uint16_t *Y) {
+  hg::LinearB16Args la;
+  la.T = T;
+  la.wfrag = wfrag;
+  la.rowmap = rowmap;
+  la.Y = reinterpret_cast<hg::bf16 *>(Y);
+  la.nrows = nrows;
+  la.F_in = F_in;
+  la.F_out = F_out;
+  la.y_nt = rows_whole_64(Y, F_out, true) ? 1 : 0;
+  return la;
+}
+
 int hg_linear_rows_bf16(int64_t nrows, int32_t F_in, int32_t F_out, const uint16_t *T, const void *wfrag, uint16_t *Y,
                         hg_stream_t stream) {
   if (nrows < 0 || !wfrag || (nrows > 0 && (!T || !Y))) {
     hg::set_error("hg_linear_rows_bf16: bad argument");
     return HG_ERR_INVALID;
   }
-  if (!b16_widths_ok(F_in, F_out)) {
+  if (!linear_widths_ok(F_in, F_out)) {
     hg::set_error("hg_linear_rows_bf16: need F_in in {32, 64, 128}, F_out a positive multiple of 16");
     return HG_ERR_UNSUPPORTED;
   }
@@ -1777,15 +1842,7 @@ int hg_linear_rows_bf16(int64_t nrows, int32_t F_in, int32_t F_out, const uint16
     hg::set_error("hg_linear_rows_bf16: T and Y must be 8-byte aligned, wfrag 16-byte aligned");
     return HG_ERR_UNSUPPORTED;
   }
-  hg::LinearB16Args la;
-  la.T = T;
-  la.wfrag = wfrag;
-  la.rowmap = nullptr;
-  la.Y = reinterpret_cast<hg::bf16 *>(Y);
-  la.nrows = nrows;
-  la.F_in = F_in;
-  la.F_out = F_out;
-  la.y_nt = rows_whole_64(Y, F_out, true) ? 1 : 0;
+  const hg::LinearB16Args la = linear_b16_args(nrows, F_in, F_out, T, wfrag, nullptr, Y);
   hipError_t e = hg::launch_linear_bf16(la, false, static_cast<hipStream_t>(stream));
   if (e != hipSuccess) return hip_fail("linear_rows_bf16 launch", e);
   return HG_OK;
@@ -1806,7 +1863,6 @@ static int b16_path(const hg_plan *plan, int32_t F_in, int32_t F_out, int32_t va
     if (fl != f && fl->fixups.empty()) f = fl;
   }
   if (fs) *fs = f;
-  const int64_t xb = (int64_t)plan->N * F_in * 2, mb = (int64_t)f->n_mat * F_in * 4;
   hg::FusedArgs a{};
   a.F = F_in;
   a.F_out = F_out;
@@ -1814,8 +1870,8 @@ static int b16_path(const hg_plan *plan, int32_t F_in, int32_t F_out, int32_t va
   a.cap = f->cap;
   a.rows_cap = f->rows_cap;
   a.nrows_x = plan->N;
-  a.x_bytes = xb < ((int64_t)1 << 31) ? (int32_t)xb : 0;
-  const bool mat_ok = f->n_mat == 0 || (mb < ((int64_t)1 << 31) && f->n_mat < (1 << 24));
+  a.x_bytes = buffer_bytes(plan->N, F_in, 2);
+  const bool mat_ok = f->n_mat == 0 || (buffer_bytes(f->n_mat, F_in, 4) != 0 && f->n_mat < (1 << 24));
   const bool in_panel = mat_ok && hg::fused_linear_b16_ok(a);
   return (in_panel ? 1 : 0) | ((!in_panel || !f->fixups.empty()) ? 2 : 0);
 }
@@ -1825,7 +1881,7 @@ int hg_aggr_linear_bf16_path(const hg_plan *plan, int32_t F_in, int32_t F_out, i
     hg::set_error("hg_aggr_linear_bf16_path: null plan");
     return HG_ERR_INVALID;
   }
-  if (variant == HG_VARIANT_PUSH_ATOMIC || !b16_widths_ok(F_in, F_out) ||
+  if (variant == HG_VARIANT_PUSH_ATOMIC || !linear_widths_ok(F_in, F_out) ||
       (variant != HG_VARIANT_AUTO && variant != HG_VARIANT_PULL && variant != HG_VARIANT_FUSED)) {
     hg::set_error("hg_aggr_linear_bf16_path: need variant auto, pull or fused, F_in in {32, 64, 128}, F_out a positive multiple of 16");
     return HG_ERR_UNSUPPORTED;
@@ -1839,7 +1895,7 @@ int hg_aggr_linear_res_bf16(const hg_plan *plan, int32_t F_in, int32_t F_out, co
                             int32_t flags, uint16_t *T_out, uint16_t *Y, void *workspace, size_t workspace_bytes,
                             int32_t variant, hg_stream_t stream) {
   // refusals, in the order include/hg_aggr.h documents; nothing is launched before the last of them has passed
-  if (!plan || !csrptr_t || (plan->nnz > 0 && !colind_t) || !X || !wfrag || !Y) {
+  if (!plan || csr_null(plan, csrptr_t, colind_t) || !X || !wfrag || !Y) {
     hg::set_error("hg_aggr_linear_res_bf16: null argument");
     return HG_ERR_INVALID;
   }
@@ -1851,7 +1907,7 @@ int hg_aggr_linear_res_bf16(const hg_plan *plan, int32_t F_in, int32_t F_out, co
     hg::set_error("hg_aggr_linear_res_bf16: variant must be auto, pull or fused (the push kernels are fp32 only)");
     return HG_ERR_UNSUPPORTED;
   }
-  if (!b16_widths_ok(F_in, F_out)) {
+  if (!linear_widths_ok(F_in, F_out)) {
     hg::set_error("hg_aggr_linear_res_bf16: need F_in in {32, 64, 128}, F_out a positive multiple of 16");
     return HG_ERR_UNSUPPORTED;
   }
@@ -1859,10 +1915,7 @@ int hg_aggr_linear_res_bf16(const hg_plan *plan, int32_t F_in, int32_t F_out, co
     hg::set_error("hg_aggr_linear_res_bf16: X, Y, R and T_out must be 8-byte aligned, wfrag 16-byte aligned");
     return HG_ERR_UNSUPPORTED;
   }
-  if (plan->opts.flags & HG_PLAN_HOST_ONLY) {
-    hg::set_error("hg_aggr_linear_res_bf16: plan was built with HG_PLAN_HOST_ONLY and holds no device schedule");
-    return HG_ERR_UNSUPPORTED;
-  }
+  if (host_only(plan)) return refuse_host_only("hg_aggr_linear_res_bf16: ", "schedule", HG_ERR_UNSUPPORTED);
   const size_t base = linear_base_bytes(plan, F_in);
   if (!workspace || !aligned16(workspace) || workspace_bytes < base + round256((size_t)plan->N * F_in * sizeof(float))) {
     hg::set_error("hg_aggr_linear_res_bf16: workspace smaller than hg_aggr_linear_workspace_bytes (or not 16-byte aligned)");
@@ -1880,21 +1933,14 @@ int hg_aggr_linear_res_bf16(const hg_plan *plan, int32_t F_in, int32_t F_out, co
   int rc = aggr_impl(plan, F_in, csrptr_t, colind_t, X, degE, degV, W, T, workspace, base, variant, stream, &lin, true);
   if (rc != HG_OK || lin.done) return rc;
   // the rows the panels did not take: all of them, or (in_panel) the hubs' and split vertices', by vertex id
-  hg::LinearB16Args la;
-  la.T = T;
-  la.wfrag = wfrag;
-  la.rowmap = lin.in_panel ? lin.rowmap : nullptr;
-  la.Y = reinterpret_cast<hg::bf16 *>(Y);
-  la.nrows = lin.in_panel ? lin.nrows_left : plan->N;
-  la.F_in = F_in;
-  la.F_out = F_out;
+  hg::LinearB16Args la = linear_b16_args(lin.in_panel ? lin.nrows_left : plan->N, F_in, F_out, T, wfrag,
+                                         lin.in_panel ? lin.rowmap : nullptr, Y);
   la.R = reinterpret_cast<const hg::bf16 *>(R);
   la.ca = lin.epi.ca;
   la.cb = lin.epi.cb;
   la.cb_dev = lin.epi.cb_dev;
   la.relu = lin.epi.relu;
   la.T_out = reinterpret_cast<hg::bf16 *>(T_out);
-  la.y_nt = rows_whole_64(Y, F_out, true) ? 1 : 0;
   hipError_t e = hg::launch_linear_bf16(la, true, static_cast<hipStream_t>(stream));
   if (e != hipSuccess) return hip_fail("linear_rows_bf16 launch", e);
   return HG_OK;
@@ -1925,16 +1971,8 @@ static int incidence_hop(const hg_plan *plan, int hop, int32_t F, int32_t heads,
   if (hop == 1 && w && (rc = get_incidence_perm(plan, true, &perm)) != HG_OK) return rc;
   // the panels + wave-task kernel (the streaming row gather has no weighted form): sched[hop], or the latency schedule
   // where hg_plan_tune_f32 pinned that kernel for this width -- what a forced pull call runs there
-  int kind = 1;
-  {
-    hg_plan *mp = const_cast<hg_plan *>(plan);
-    std::lock_guard<std::mutex> lock(mp->auto_mu);
-    auto it = mp->hop_kernel.find(F);
-    if (it != mp->hop_kernel.end()) kind = hop == 0 ? it->second % 3 : (it->second / 3) % 3;
-  }
-  const hg::Sched &sc = (kind == 2 && plan->has_lat) ? plan->sched_lat[hop] : plan->sched[hop];
-  // streaming stores as run_hop decides them (on the bytes of dst's rows; the choice moves no bits)
-  const bool nt = rows_whole_64(dst, F, dst_bf16) && (hop == 1 || (int64_t)plan->M * F * 4 >= ((int64_t)192 << 20));
+  const hg::Sched &sc = pull_sched(plan, hop, F, 1);
+  const bool nt = nt_rows(plan, hop, dst, F, dst_bf16);
   return run_sched(plan, sc, F, hop == 0 ? csrptr_t : plan->d_ptr_v, hop == 0 ? colind_t : plan->d_ind_v, src, scaleA, scaleB,
                    nullptr, nullptr, dst, reinterpret_cast<float *>(ws + c.part[hop]), s, nt, src_bf16, dst_bf16, w, perm, heads);
 }
@@ -1988,7 +2026,7 @@ static int aggr_incidence(const hg_plan *plan, int32_t F, int32_t heads, const i
   const std::string who = bf16 ? "hg_aggr_incidence_heads_bf16" : "hg_aggr_incidence_f32";
   int rc = check_call(plan, F, workspace, workspace_bytes, kSizePull);
   if (rc != HG_OK) return rc;
-  if (!csrptr_t || (plan->nnz > 0 && !colind_t) || !X || !Y) {
+  if (csr_null(plan, csrptr_t, colind_t) || !X || !Y) {
     hg::set_error(who + ": null array");
     return HG_ERR_INVALID;
   }
@@ -2032,7 +2070,7 @@ static int gather_rows_incidence(const char *who, const hg_plan *plan, int32_t h
   int rc = check_heads(who, plan, heads, F);
   if (rc != HG_OK) return rc;
   if ((rc = check_call(plan, F, workspace, workspace_bytes, kSizePull)) != HG_OK) return rc;
-  if (!csrptr_t || (plan->nnz > 0 && !colind_t) || !src || !dst) {
+  if (csr_null(plan, csrptr_t, colind_t) || !src || !dst) {
     hg::set_error(std::string(who) + ": null array");
     return HG_ERR_INVALID;
   }
@@ -2096,10 +2134,7 @@ static int check_reduce_call(const char *who, const hg_plan *plan, int32_t hop, 
     hg::set_error(std::string(who) + ": op must be HG_REDUCE_MAX or HG_REDUCE_MIN");
     return HG_ERR_INVALID;
   }
-  if (plan->opts.flags & HG_PLAN_HOST_ONLY) {
-    hg::set_error(std::string(who) + ": plan was built with HG_PLAN_HOST_ONLY and holds no device arrays");
-    return HG_ERR_UNSUPPORTED;
-  }
+  if (host_only(plan)) return refuse_host_only(std::string(who) + ": ", "arrays", HG_ERR_UNSUPPORTED);
   if (F <= 0 || (int64_t)std::max(plan->N, plan->M) * F >= ((int64_t)1 << 40)) {
     hg::set_error(std::string(who) + ": feature width must be positive and the feature matrix below 2^40 elements");
     return HG_ERR_INVALID;
@@ -2112,17 +2147,7 @@ static int check_reduce_call(const char *who, const hg_plan *plan, int32_t hop, 
     hg::set_error(std::string(who) + ": panel_rows / panel_nnz leave no LDS for the staged positions (160 KiB per workgroup)");
     return HG_ERR_UNSUPPORTED;
   }
-  const size_t need = hg_gather_rows_reduce_workspace_bytes(plan, F);
-  if (!workspace || workspace_bytes < need) {
-    hg::set_error(std::string(who) + ": workspace too small: need " + std::to_string(need) + " bytes, got " +
-                  std::to_string(workspace_bytes));
-    return HG_ERR_WORKSPACE;
-  }
-  if (reinterpret_cast<uintptr_t>(workspace) & 255) {
-    hg::set_error(std::string(who) + ": workspace must be 256-byte aligned");
-    return HG_ERR_INVALID;
-  }
-  return HG_OK;
+  return check_workspace(std::string(who) + ": ", workspace, workspace_bytes, hg_gather_rows_reduce_workspace_bytes(plan, F));  // never 0
 }
 
 // walk: the CSR the kernel walks (0: H_T, 1: H).  rmode 1 / 2: src -> (dst, arg_out); 3: (src = gs, arg_in) -> dst.
@@ -2132,34 +2157,11 @@ static int reduce_hop(const hg_plan *plan, int walk, int rmode, int32_t F, const
   int rc;
   const int32_t *perm = nullptr;
   if (walk == 1 && (rc = get_incidence_perm(plan, true, &perm)) != HG_OK) return rc;
-  int kind = 1;  // the panels + wave-task schedule, or the latency schedule where it is pinned for this width (incidence_hop)
-  {
-    hg_plan *mp = const_cast<hg_plan *>(plan);
-    std::lock_guard<std::mutex> lock(mp->auto_mu);
-    auto it = mp->hop_kernel.find(F);
-    if (it != mp->hop_kernel.end()) kind = walk == 0 ? it->second % 3 : (it->second / 3) % 3;
-  }
-  const hg::Sched &s = (kind == 2 && plan->has_lat) ? plan->sched_lat[walk] : plan->sched[walk];
+  const hg::Sched &s = pull_sched(plan, walk, F, 1);  // as incidence_hop
   hg::ReduceGatherArgs a;
-  a.ptr = walk == 0 ? csrptr_t : plan->d_ptr_v;
-  a.ind = walk == 0 ? colind_t : plan->d_ind_v;
-  a.src = src;
-  a.dst = dst;
-  a.scaleA = scaleA;
-  a.scaleB = scaleB;
-  a.partial = static_cast<float *>(workspace);
+  fill_gather(a, plan, s, F, walk == 0 ? csrptr_t : plan->d_ptr_v, walk == 0 ? colind_t : plan->d_ind_v, src, scaleA, scaleB,
+              dst, static_cast<float *>(workspace));
   a.ipartial = reinterpret_cast<int32_t *>(static_cast<char *>(workspace) + reduce_part_bytes(plan, F));
-  a.scale_map = nullptr;
-  a.dst_map = nullptr;
-  a.panels = s.d_panels;
-  a.tasks = s.d_tasks;
-  a.npanels = (int32_t)s.panels.size();
-  a.ntasks = (int32_t)s.tasks.size();
-  a.n_task_blocks = (a.ntasks + 3) / 4;
-  a.F = F;
-  a.panel_rows = plan->opts.panel_rows;
-  a.panel_nnz = plan->opts.panel_nnz;
-  a.xcd_remap = (plan->opts.flags & HG_PLAN_NO_XCD_REMAP) ? 0 : 1;
   a.pperm = perm;
   a.arg_out = arg_out;
   a.arg_in = arg_in;
@@ -2262,6 +2264,49 @@ int hg_plan_get_incidence_perm(const hg_plan *plan, int32_t *perm_host) {
 
 // ---- hypergraph attention coefficients ------------------------------------------------------------------------------
 
+// The segment softmax of every attention entry, after the entry's own refusals: drop (or null) adds the dropout mask,
+// entry_score (or null) a logit per incidence.  outs_ok / outs: the entry's rule for its output arrays and their names in
+// its refusal, which the slope shares.  launch: the name a failed launch is reported under.
+static int softmax_fwd(const char *who, const char *launch, bool outs_ok, const char *outs, const hg_plan *plan, int32_t group,
+                       int32_t heads, const int32_t *csrptr_t, const int32_t *colind_t, const float *sv, const float *se,
+                       const float *entry_score, float slope, const hg::DropFields *drop, float *alpha_out, hg_stream_t stream) {
+  if (!outs_ok || !is_finite(slope)) return refuse(HG_ERR_INVALID, std::string(who) + ": null " + outs + " or non-finite slope");
+  if (plan->nnz == 0) return HG_OK;
+  hg::SegArgs a = {};
+  a.slope = slope;
+  a.out_entry = alpha_out;
+  const int body = entry_score ? (drop ? hg::kSegSoftmaxEntryDrop : hg::kSegSoftmaxEntry) : (drop ? hg::kSegSoftmaxDrop : hg::kSegSoftmax);
+  return run_segments(launch, plan, body, group, csrptr_t, colind_t, sv, se, a, static_cast<hipStream_t>(stream), heads, drop,
+                      entry_score);
+}
+
+// Its backward: ds per incidence; the group's own end is summed by the kernel that forms ds, the other end is a segment
+// sum of ds over that side (sum_launch).  dalpha: the gradient of what the forward returned (alpha, or alpha_drop).
+static int softmax_bwd(const char *who, const char *launch, const char *sum_launch, bool arrays_ok, const char *arrays,
+                       const hg_plan *plan, int32_t group, int32_t heads, const int32_t *csrptr_t, const int32_t *colind_t,
+                       const float *sv, const float *se, const float *entry_score, float slope, const hg::DropFields *drop,
+                       const float *alpha, const float *dalpha, float *ds_out, float *dsv_out, float *dse_out,
+                       hg_stream_t stream) {
+  if (!arrays_ok || !is_finite(slope)) return refuse(HG_ERR_INVALID, std::string(who) + ": null " + arrays + " or non-finite slope");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  hg::SegArgs a = {};
+  a.slope = slope;
+  a.val = alpha;
+  a.dval = dalpha;
+  a.out_entry = ds_out;
+  a.out_seg = group == 0 ? dse_out : dsv_out;
+  const int body = entry_score ? (drop ? hg::kSegSoftmaxEntryDropBwd : hg::kSegSoftmaxEntryBwd)
+                               : (drop ? hg::kSegSoftmaxDropBwd : hg::kSegSoftmaxBwd);
+  int rc = run_segments(launch, plan, body, group, csrptr_t, colind_t, sv, se, a, s, heads, drop, entry_score);
+  if (rc != HG_OK) return rc;
+  float *other_out = group == 0 ? dsv_out : dse_out;
+  if (!other_out) return HG_OK;
+  hg::SegArgs b = {};
+  b.val = ds_out;
+  b.out_seg = other_out;
+  return run_segments(sum_launch, plan, hg::kSegSum, 1 - group, csrptr_t, colind_t, nullptr, nullptr, b, s, heads);
+}
+
 int hg_incidence_attention_f32(const hg_plan *plan, int32_t group, const int32_t *csrptr_t, const int32_t *colind_t,
                                const float *sv, const float *se, float slope, float *alpha_out, hg_stream_t stream) {
   return hg_incidence_attention_heads_f32(plan, group, 1, csrptr_t, colind_t, sv, se, slope, alpha_out, stream);
@@ -2275,16 +2320,8 @@ int hg_incidence_attention_heads_f32(const hg_plan *plan, int32_t group, int32_t
   if (rc != HG_OK) return rc;
   rc = check_segment_call("hg_incidence_attention_f32", plan, group, csrptr_t, colind_t);
   if (rc != HG_OK) return rc;
-  if ((plan->nnz > 0 && !alpha_out) || !(slope == slope) || slope - slope != 0.f) {
-    hg::set_error("hg_incidence_attention_f32: null alpha_out or non-finite slope");
-    return HG_ERR_INVALID;
-  }
-  if (plan->nnz == 0) return HG_OK;
-  hg::SegArgs a = {};
-  a.slope = slope;
-  a.out_entry = alpha_out;
-  return run_segments("incidence_attention launch", plan, hg::kSegSoftmax, group, csrptr_t, colind_t, sv, se, a,
-                      static_cast<hipStream_t>(stream), heads);
+  return softmax_fwd("hg_incidence_attention_f32", "incidence_attention launch", plan->nnz == 0 || alpha_out, "alpha_out", plan,
+                     group, heads, csrptr_t, colind_t, sv, se, nullptr, slope, nullptr, alpha_out, stream);
 }
 
 int hg_incidence_attention_bwd_f32(const hg_plan *plan, int32_t group, const int32_t *csrptr_t, const int32_t *colind_t,
@@ -2302,27 +2339,9 @@ int hg_incidence_attention_heads_bwd_f32(const hg_plan *plan, int32_t group, int
   if (rc != HG_OK) return rc;
   rc = check_segment_call("hg_incidence_attention_bwd_f32", plan, group, csrptr_t, colind_t);
   if (rc != HG_OK) return rc;
-  if ((plan->nnz > 0 && (!alpha || !dalpha || !ds_out)) || !(slope == slope) || slope - slope != 0.f) {
-    hg::set_error("hg_incidence_attention_bwd_f32: null alpha / dalpha / ds_out or non-finite slope");
-    return HG_ERR_INVALID;
-  }
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  hg::SegArgs a = {};
-  a.slope = slope;
-  a.val = alpha;
-  a.dval = dalpha;
-  a.out_entry = ds_out;
-  a.out_seg = group == 0 ? dse_out : dsv_out;  // the group's own end: summed by the kernel that forms ds
-  rc = run_segments("incidence_attention_bwd launch", plan, hg::kSegSoftmaxBwd, group, csrptr_t, colind_t, sv, se, a, s,
-                    heads);
-  if (rc != HG_OK) return rc;
-  float *other_out = group == 0 ? dsv_out : dse_out;  // the other end: a segment sum of ds over that side
-  if (!other_out) return HG_OK;
-  hg::SegArgs b = {};
-  b.val = ds_out;
-  b.out_seg = other_out;
-  return run_segments("incidence_attention_bwd sum launch", plan, hg::kSegSum, 1 - group, csrptr_t, colind_t, nullptr,
-                      nullptr, b, s, heads);
+  return softmax_bwd("hg_incidence_attention_bwd_f32", "incidence_attention_bwd launch", "incidence_attention_bwd sum launch",
+                     plan->nnz == 0 || (alpha && dalpha && ds_out), "alpha / dalpha / ds_out", plan, group, heads, csrptr_t,
+                     colind_t, sv, se, nullptr, slope, nullptr, alpha, dalpha, ds_out, dsv_out, dse_out, stream);
 }
 
 // ---- fused attention aggregation: the coefficients formed inside the gather ----------------------------------------------
@@ -2365,18 +2384,10 @@ int hg_incidence_attention_stats_heads_f32(const hg_plan *plan, int32_t group, i
   const char *who = "hg_incidence_attention_stats_heads_f32";
   int rc = check_attention_call(who, plan, 0, group, heads, 1, false);
   if (rc != HG_OK) return rc;
-  if (!csrptr_t || (plan->nnz > 0 && !colind_t) || !seg_max_out || !seg_inv_out) {
-    hg::set_error(std::string(who) + ": null array");
-    return HG_ERR_INVALID;
-  }
-  if (!(slope == slope) || slope - slope != 0.f) {
-    hg::set_error(std::string(who) + ": non-finite slope");
-    return HG_ERR_INVALID;
-  }
-  if (plan->opts.flags & HG_PLAN_HOST_ONLY) {
-    hg::set_error(std::string(who) + ": plan was built with HG_PLAN_HOST_ONLY and holds no device arrays");
-    return HG_ERR_UNSUPPORTED;
-  }
+  const std::string pre = std::string(who) + ": ";
+  if (csr_null(plan, csrptr_t, colind_t) || !seg_max_out || !seg_inv_out) return refuse(HG_ERR_INVALID, pre + "null array");
+  if (!is_finite(slope)) return refuse(HG_ERR_INVALID, pre + "non-finite slope");
+  if (host_only(plan)) return refuse_host_only(pre, "arrays", HG_ERR_UNSUPPORTED);
   hg::SegArgs a = {};  // run even without incidences: every segment is empty and gets (0, 0)
   a.slope = slope;
   a.out_entry = seg_max_out;
@@ -2391,15 +2402,8 @@ static int attention_hop(const hg_plan *plan, int hop, int group, int32_t F, int
                          const int32_t *colind_t, const float *src, const float *sv, const float *se, float slope,
                          const float *seg_max, const float *seg_inv, const float *scaleA, const float *scaleB, float *dst,
                          char *ws, const Carve &c, hipStream_t s) {
-  int kind = 1;
-  {
-    hg_plan *mp = const_cast<hg_plan *>(plan);
-    std::lock_guard<std::mutex> lock(mp->auto_mu);
-    auto it = mp->hop_kernel.find(F);
-    if (it != mp->hop_kernel.end()) kind = hop == 0 ? it->second % 3 : (it->second / 3) % 3;
-  }
-  const hg::Sched &sc = (kind == 2 && plan->has_lat) ? plan->sched_lat[hop] : plan->sched[hop];
-  const bool nt = rows_whole_64(dst, F) && (hop == 1 || (int64_t)plan->M * F * 4 >= ((int64_t)192 << 20));
+  const hg::Sched &sc = pull_sched(plan, hop, F, 1);
+  const bool nt = nt_rows(plan, hop, dst, F);
   hg::AttnGatherArgs at;
   at.row_score = hop == 0 ? se : sv;
   at.ent_score = hop == 0 ? sv : se;
@@ -2416,28 +2420,12 @@ static int attention_hop(const hg_plan *plan, int hop, int group, int32_t F, int
 // per-row scalars leave no LDS.
 static int check_attention_gather(const char *who, const hg_plan *plan, int32_t F, int32_t heads, bool arrays_ok, float slope,
                                   const void *workspace, size_t workspace_bytes) {
-  if (!arrays_ok) {
-    hg::set_error(std::string(who) + ": null array");
-    return HG_ERR_INVALID;
-  }
-  if (!(slope == slope) || slope - slope != 0.f) {
-    hg::set_error(std::string(who) + ": non-finite slope");
-    return HG_ERR_INVALID;
-  }
-  const size_t need = carve(plan, F).total;
-  if (need > 0 && (!workspace || workspace_bytes < need)) {
-    hg::set_error(std::string(who) + ": workspace too small: need " + std::to_string(need) + " bytes, got " +
-                  std::to_string(workspace_bytes));
-    return HG_ERR_WORKSPACE;
-  }
-  if (reinterpret_cast<uintptr_t>(workspace) & 255) {
-    hg::set_error(std::string(who) + ": workspace must be 256-byte aligned");
-    return HG_ERR_INVALID;
-  }
-  if (plan->opts.flags & HG_PLAN_HOST_ONLY) {
-    hg::set_error(std::string(who) + ": plan was built with HG_PLAN_HOST_ONLY and holds no device schedule");
-    return HG_ERR_UNSUPPORTED;
-  }
+  const std::string pre = std::string(who) + ": ";
+  if (!arrays_ok) return refuse(HG_ERR_INVALID, pre + "null array");
+  if (!is_finite(slope)) return refuse(HG_ERR_INVALID, pre + "non-finite slope");
+  int rc = check_workspace(pre, workspace, workspace_bytes, carve(plan, F).total);
+  if (rc != HG_OK) return rc;
+  if (host_only(plan)) return refuse_host_only(pre, "schedule", HG_ERR_UNSUPPORTED);
   if (hg::attn_gather_lds_bytes(plan->opts.panel_rows, plan->opts.panel_nnz, heads, true) > (size_t)160 * 1024) {
     hg::set_error(std::string(who) + ": panel_rows * heads leaves no LDS for the rows' scores and statistics (160 KiB per workgroup)");
     return HG_ERR_UNSUPPORTED;
@@ -2453,7 +2441,7 @@ int hg_gather_rows_attention_heads_f32(const hg_plan *plan, int32_t hop, int32_t
   const char *who = "hg_gather_rows_attention_heads_f32";
   int rc = check_attention_call(who, plan, hop, group, heads, F);
   if (rc != HG_OK) return rc;
-  const bool arrays_ok = csrptr_t && (plan->nnz == 0 || colind_t) && src && dst && seg_max && seg_inv;
+  const bool arrays_ok = !csr_null(plan, csrptr_t, colind_t) && src && dst && seg_max && seg_inv;
   if ((rc = check_attention_gather(who, plan, F, heads, arrays_ok, slope, workspace, workspace_bytes)) != HG_OK) return rc;
   return attention_hop(plan, hop, group, F, heads, csrptr_t, colind_t, src, sv, se, slope, seg_max, seg_inv, scaleA, scaleB, dst,
                        static_cast<char *>(workspace), carve(plan, F), static_cast<hipStream_t>(stream));
@@ -2467,7 +2455,7 @@ int hg_aggr_incidence_attention_heads_f32(const hg_plan *plan, int32_t F, int32_
   const char *who = "hg_aggr_incidence_attention_heads_f32";
   int rc = check_attention_call(who, plan, 0, group, heads, F);
   if (rc != HG_OK) return rc;
-  const bool arrays_ok = csrptr_t && (plan->nnz == 0 || colind_t) && X && Y && seg_max && seg_inv;
+  const bool arrays_ok = !csr_null(plan, csrptr_t, colind_t) && X && Y && seg_max && seg_inv;
   if ((rc = check_attention_gather(who, plan, F, heads, arrays_ok, slope, workspace, workspace_bytes)) != HG_OK) return rc;
   hipStream_t s = static_cast<hipStream_t>(stream);
   const Carve c = carve(plan, F);
@@ -2491,17 +2479,9 @@ int hg_incidence_attention_dropout_heads_f32(const hg_plan *plan, int32_t group,
   if ((rc = check_segment_call(who, plan, group, csrptr_t, colind_t)) != HG_OK) return rc;
   hg::DropFields d = {};
   if ((rc = check_dropout(who, p_drop, rng_dev, &d)) != HG_OK) return rc;
-  if (!alpha_out || !alpha_drop_out || !(slope == slope) || slope - slope != 0.f) {
-    hg::set_error(std::string(who) + ": null alpha_out / alpha_drop_out or non-finite slope");
-    return HG_ERR_INVALID;
-  }
-  if (plan->nnz == 0) return HG_OK;
-  hg::SegArgs a = {};
-  a.slope = slope;
-  a.out_entry = alpha_out;
   d.out_drop = alpha_drop_out;
-  return run_segments("incidence_attention_dropout launch", plan, hg::kSegSoftmaxDrop, group, csrptr_t, colind_t, sv, se, a,
-                      static_cast<hipStream_t>(stream), heads, &d);
+  return softmax_fwd(who, "incidence_attention_dropout launch", alpha_out && alpha_drop_out, "alpha_out / alpha_drop_out", plan,
+                     group, heads, csrptr_t, colind_t, sv, se, nullptr, slope, &d, alpha_out, stream);
 }
 
 int hg_incidence_attention_dropout_heads_bwd_f32(const hg_plan *plan, int32_t group, int32_t heads,
@@ -2515,27 +2495,9 @@ int hg_incidence_attention_dropout_heads_bwd_f32(const hg_plan *plan, int32_t gr
   if ((rc = check_segment_call(who, plan, group, csrptr_t, colind_t)) != HG_OK) return rc;
   hg::DropFields d = {};
   if ((rc = check_dropout(who, p_drop, rng_dev, &d)) != HG_OK) return rc;
-  if (!ds_out || (plan->nnz > 0 && (!alpha || !dout)) || !(slope == slope) || slope - slope != 0.f) {
-    hg::set_error(std::string(who) + ": null alpha / dout / ds_out or non-finite slope");
-    return HG_ERR_INVALID;
-  }
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  hg::SegArgs a = {};
-  a.slope = slope;
-  a.val = alpha;
-  a.dval = dout;
-  a.out_entry = ds_out;
-  a.out_seg = group == 0 ? dse_out : dsv_out;  // the group's own end: summed by the kernel that forms ds
-  rc = run_segments("incidence_attention_dropout_bwd launch", plan, hg::kSegSoftmaxDropBwd, group, csrptr_t, colind_t, sv, se,
-                    a, s, heads, &d);
-  if (rc != HG_OK) return rc;
-  float *other_out = group == 0 ? dsv_out : dse_out;  // the other end: the plain segment sum of ds over that side
-  if (!other_out) return HG_OK;
-  hg::SegArgs b = {};
-  b.val = ds_out;
-  b.out_seg = other_out;
-  return run_segments("incidence_attention_dropout_bwd sum launch", plan, hg::kSegSum, 1 - group, csrptr_t, colind_t,
-                      nullptr, nullptr, b, s, heads);
+  return softmax_bwd(who, "incidence_attention_dropout_bwd launch", "incidence_attention_dropout_bwd sum launch",
+                     ds_out && (plan->nnz == 0 || (alpha && dout)), "alpha / dout / ds_out", plan, group, heads, csrptr_t,
+                     colind_t, sv, se, nullptr, slope, &d, alpha, dout, ds_out, dsv_out, dse_out, stream);
 }
 
 // ---- a logit per incidence: the four softmax entries with entry_score added to the score ------------------------------
@@ -2565,45 +2527,22 @@ static int check_entry_call(const char *who, const hg_plan *plan, int32_t group,
   return check_segment_call(who, plan, group, csrptr_t, colind_t);
 }
 
+// The four entries after check_entry_call: one rule for the outputs whether or not there is a mask; a failed launch is
+// reported under the entry's name.
 static int entry_attention(const char *who, const hg_plan *plan, int32_t group, int32_t heads, const int32_t *csrptr_t,
                            const int32_t *colind_t, const float *sv, const float *se, const float *entry_score, float slope,
                            const hg::DropFields *drop, float *alpha_out, hg_stream_t stream) {
-  if (!alpha_out || (drop && !drop->out_drop) || !(slope == slope) || slope - slope != 0.f) {
-    hg::set_error(std::string(who) + ": null alpha_out / alpha_drop_out or non-finite slope");
-    return HG_ERR_INVALID;
-  }
-  if (plan->nnz == 0) return HG_OK;
-  hg::SegArgs a = {};
-  a.slope = slope;
-  a.out_entry = alpha_out;
-  return run_segments(who, plan, drop ? hg::kSegSoftmaxEntryDrop : hg::kSegSoftmaxEntry, group, csrptr_t, colind_t, sv, se, a,
-                      static_cast<hipStream_t>(stream), heads, drop, entry_score);
+  return softmax_fwd(who, who, alpha_out && (!drop || drop->out_drop), "alpha_out / alpha_drop_out", plan, group, heads,
+                     csrptr_t, colind_t, sv, se, entry_score, slope, drop, alpha_out, stream);
 }
 
 static int entry_attention_bwd(const char *who, const hg_plan *plan, int32_t group, int32_t heads, const int32_t *csrptr_t,
                                const int32_t *colind_t, const float *sv, const float *se, const float *entry_score,
                                float slope, const hg::DropFields *drop, const float *alpha, const float *dalpha,
                                float *ds_out, float *dsv_out, float *dse_out, hg_stream_t stream) {
-  if (!ds_out || (plan->nnz > 0 && (!alpha || !dalpha)) || !(slope == slope) || slope - slope != 0.f) {
-    hg::set_error(std::string(who) + ": null alpha / dalpha / ds_out or non-finite slope");
-    return HG_ERR_INVALID;
-  }
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  hg::SegArgs a = {};
-  a.slope = slope;
-  a.val = alpha;
-  a.dval = dalpha;
-  a.out_entry = ds_out;
-  a.out_seg = group == 0 ? dse_out : dsv_out;  // the group's own end: summed by the kernel that forms ds
-  int rc = run_segments(who, plan, drop ? hg::kSegSoftmaxEntryDropBwd : hg::kSegSoftmaxEntryBwd, group, csrptr_t, colind_t,
-                        sv, se, a, s, heads, drop, entry_score);
-  if (rc != HG_OK) return rc;
-  float *other_out = group == 0 ? dsv_out : dse_out;  // the other end: the plain segment sum of ds over that side
-  if (!other_out) return HG_OK;
-  hg::SegArgs b = {};
-  b.val = ds_out;
-  b.out_seg = other_out;
-  return run_segments(who, plan, hg::kSegSum, 1 - group, csrptr_t, colind_t, nullptr, nullptr, b, s, heads);
+  return softmax_bwd(who, who, who, ds_out && (plan->nnz == 0 || (alpha && dalpha)), "alpha / dalpha / ds_out", plan, group,
+                     heads, csrptr_t, colind_t, sv, se, entry_score, slope, drop, alpha, dalpha, ds_out, dsv_out, dse_out,
+                     stream);
 }
 
 int hg_incidence_attention_entry_heads_f32(const hg_plan *plan, int32_t group, int32_t heads, const int32_t *csrptr_t,
@@ -2706,7 +2645,7 @@ int hg_hyperedge_dot_heads_f32(const hg_plan *plan, int32_t F, int32_t heads, co
     hg::set_error(std::string(who) + ": null A, B or out");
     return HG_ERR_INVALID;
   }
-  if (!csrptr_t || (plan->nnz > 0 && !colind_t)) {
+  if (csr_null(plan, csrptr_t, colind_t)) {
     hg::set_error(std::string(who) + ": null array");
     return HG_ERR_INVALID;
   }

@@ -116,8 +116,7 @@ class Plan:
         """Build the feature-width dependent (fused) schedule now; returns its shape."""
         info = _lib.FusedInfo()
         _lib.check(_lib.lib().hg_plan_prepare(self._h, F, ctypes.byref(info)))
-        for k in (F, ("lin", F)):
-            self.__dict__.setdefault("_ws_bytes", {}).pop(k, None)
+        self._drop_ws_cache(F)
         return info.as_dict()
 
     def auto_variant(self, F):
@@ -151,9 +150,8 @@ class Plan:
                 _ptr(workspace), nbytes, int(iters), _stream_handle(X.device), ctypes.byref(info)))
         if hasattr(self, "_auto"):
             self._auto.pop(F, None)  # the cached answer of auto_variant may have changed
-        for k in (F, ("lin", F)):
-            self.__dict__.setdefault("_ws_bytes", {}).pop(k, None)
-        names = {code: name for name, code in _lib.VARIANTS.items()}
+        self._drop_ws_cache(F)
+        names ={code: name for name, code in _lib.VARIANTS.items()}
         kinds = ("stream", "panels", "tasks")  # per hop: streaming row gather, row panels + wave tasks, latency schedule
         labels = ("fused", "pull") + tuple("pull/%s+%s" % (kinds[c % 3], kinds[c // 3]) for c in range(1, 9))
         return {"variant": names[info.variant], "pull_hop_kernels": info.pull_hop_kernels,
@@ -171,8 +169,7 @@ class Plan:
         _lib.check(_lib.lib().hg_plan_set_choice(self._h, int(F), _lib.VARIANTS[variant], int(pull_hop_kernels)))
         if hasattr(self, "_auto"):
             self._auto.pop(F, None)  # the cached answer of auto_variant may have changed
-        for k in (F, ("lin", F)):
-            self.__dict__.setdefault("_ws_bytes", {}).pop(k, None)
+        self._drop_ws_cache(F)
 
     def unpin(self, F):
         """Remove width F's pinned or tuned choice: the static rule decides again, and the pull hops run their default
@@ -217,6 +214,32 @@ class Plan:
         # torch's caching allocator returns 512-byte aligned blocks and is stream-ordered
         return torch.empty(max(nbytes, 256), dtype=torch.uint8, device=device), nbytes
 
+    def _drop_ws_cache(self, F):
+        """Forget width F's cached workspace sizes: something may have built a larger layout for it."""
+        for k in (F, ("lin", F)):
+            self.__dict__.setdefault("_ws_bytes", {}).pop(k, None)
+
+    def _run_with_workspace(self, entry, head, tail, F, workspace, device, size):
+        """Call entry(*head, workspace, bytes, *tail) on the caller's workspace, or on an own one of size(F) bytes
+        (workspace_bytes or linear_workspace_bytes, both cached), and raise on a bad status.  HG_ERR_WORKSPACE on an own
+        one means the cached size is stale: the call itself built a layout for this width that needs more (e.g. AUTO on an
+        unaligned view of X with N >= 2^24 takes another schedule than the one the size was asked for).  Nothing was
+        written; ask again and retry once.  No closure and no tensor method on the own path: this runs once per
+        launch-bound call."""
+        own = workspace is None
+        if own:
+            nbytes = size(F)
+            workspace = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=device)
+        else:
+            nbytes = workspace.numel() * workspace.element_size()
+        st = entry(*head, _ptr(workspace), nbytes, *tail)
+        if st == _lib.HG_ERR_WORKSPACE and own:
+            self._drop_ws_cache(F)
+            nbytes = size(F)
+            workspace = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=device)
+            st = entry(*head, _ptr(workspace), nbytes, *tail)
+        _lib.check(st)
+
     def aggregate(self, csrptr_t, colind_t, X, degE=None, degV=None, W=None, variant="auto",
                   out=None, workspace=None, bind_scales=True, trainable_scales=False):
         """Y = degV . H (degE . W . (H^T X)) on X's device, current stream.
@@ -254,11 +277,7 @@ class Plan:
                 return Yp[:, :F].contiguous() if F4 != F else Yp
             out.copy_(Yp[:, :F])
             return out
-        for name, t, n in (("degE", degE, self.M), ("degV", degV, self.N), ("W", W, self.M)):
-            if t is not None:
-                _check_feat(t, name, device=X.device)
-                if t.numel() != n:
-                    raise ValueError("%s must have %d elements, got %d" % (name, n, t.numel()))
+        _check_scales((("degE", degE, self.M), ("degV", degV, self.N), ("W", W, self.M)), X.device)
         W = self._drop_unit_weights(W, bind_scales and not trainable_scales)
         stream = torch.cuda.current_stream(X.device)  # looked up once per call: it is a measurable share of a launch-bound call
         if (degE is not None or degV is not None or W is not None) and variant in ("auto", "fused"):
@@ -266,23 +285,11 @@ class Plan:
         Y = out if out is not None else torch.empty((self.N, F), dtype=X.dtype, device=X.device)
         if variant == "fused":  # hg_plan_workspace_bytes sizes for what AUTO runs; a forced fused call needs its schedule first
             self._ensure_fused(F)
-        own_ws = workspace is None
-        if own_ws:
-            workspace, nbytes = self._workspace(F, X.device)
-        else:
-            nbytes = workspace.numel() * workspace.element_size()
         with torch.cuda.device(X.device):
             args = (self._h, F, _ptr(csrptr_t), _ptr(colind_t), _ptr(X), _ptr(degE), _ptr(degV), _ptr(W), _ptr(Y))
             entry = _lib.lib().hg_aggr_fused_bf16 if bf16 else _lib.lib().hg_aggr_fused_f32
-            st = entry(*args, _ptr(workspace), nbytes, _lib.VARIANTS[variant], ctypes.c_void_p(stream.cuda_stream))
-            if st == _lib.HG_ERR_WORKSPACE and own_ws:
-                # The cached size is stale: the call itself built a layout for this width that needs more (e.g. AUTO on an
-                # unaligned view of X with N >= 2^24 takes another schedule than the one the size was asked for).  Nothing
-                # was written; ask again and retry once.
-                self.__dict__.setdefault("_ws_bytes", {}).pop(F, None)
-                workspace, nbytes = self._workspace(F, X.device)
-                st = entry(*args, _ptr(workspace), nbytes, _lib.VARIANTS[variant], ctypes.c_void_p(stream.cuda_stream))
-            _lib.check(st)
+            self._run_with_workspace(entry, args, (_lib.VARIANTS[variant], ctypes.c_void_p(stream.cuda_stream)), F, workspace,
+                                     X.device, self.workspace_bytes)
         return Y
 
     def aggregate_linear(self, csrptr_t, colind_t, X, weight, degE=None, degV=None, W=None,
@@ -315,21 +322,13 @@ class Plan:
         if math == "bf16x6" and F_in == 128 and packed.numel() == _lib.lib().hg_linear_pack_floats(F_out, F_in, LIN_BF16X6):
             flags |= LIN_BF16X6
         weight = packed
-        for name, t, n in (("degE", degE, self.M), ("degV", degV, self.N), ("W", W, self.M)):
-            if t is not None:
-                _check_feat(t, name, device=X.device)
-                if t.numel() != n:
-                    raise ValueError("%s must have %d elements, got %d" % (name, n, t.numel()))
+        _check_scales((("degE", degE, self.M), ("degV", degV, self.N), ("W", W, self.M)), X.device)
         W = self._drop_unit_weights(W, bind_scales and not trainable_scales)  # trainable_scales: as in aggregate()
         if (degE is not None or degV is not None or W is not None) and variant in ("auto", "fused"):
             self._bind_scales(F_in, degE, degV, W, X.device, bind_scales, trainable=trainable_scales)
         Y = out if out is not None else torch.empty((self.N, F_out), dtype=torch.float32, device=X.device)
         if variant == "fused":
             self._ensure_fused(F_in)
-        own_ws = workspace is None
-        if own_ws:
-            workspace = torch.empty(max(self.linear_workspace_bytes(F_in), 256), dtype=torch.uint8, device=X.device)
-        nbytes = workspace.numel() * workspace.element_size()
         with torch.cuda.device(X.device):
             for name, t in (("residual", residual), ("t_out", t_out)):
                 if t is not None:
@@ -345,14 +344,8 @@ class Plan:
                 fn, cb_arg = _lib.lib().hg_aggr_linear_res_f32, float(cb)
             head = (self._h, F_in, F_out, _ptr(csrptr_t), _ptr(colind_t), _ptr(X), _ptr(degE), _ptr(degV),
                     _ptr(W), _ptr(weight), _ptr(residual), float(ca), cb_arg, flags, _ptr(t_out), _ptr(Y))
-            stream = _stream_handle(X.device)
-            st = fn(*head, _ptr(workspace), nbytes, _lib.VARIANTS[variant], stream)
-            if st == _lib.HG_ERR_WORKSPACE and own_ws:  # stale cached size: see aggregate()
-                self.__dict__.setdefault("_ws_bytes", {}).pop(("lin", F_in), None)
-                workspace = torch.empty(max(self.linear_workspace_bytes(F_in), 256), dtype=torch.uint8, device=X.device)
-                nbytes = workspace.numel()
-                st = fn(*head, _ptr(workspace), nbytes, _lib.VARIANTS[variant], stream)
-            _lib.check(st)
+            self._run_with_workspace(fn, head, (_lib.VARIANTS[variant], _stream_handle(X.device)), F_in, workspace, X.device,
+                                     self.linear_workspace_bytes)
         return Y
 
     def linear_bf16_path(self, F_in, F_out, variant="auto"):
@@ -399,11 +392,7 @@ class Plan:
         for name, t in (("weight", weight), ("residual", residual), ("t_out", t_out), ("out", out)):
             if t is not None:
                 _check_feat(t, name, device=X.device, bf16_ok=True)
-        for name, t, n in (("degE", degE, self.M), ("degV", degV, self.N), ("W", W, self.M)):
-            if t is not None:
-                _check_feat(t, name, device=X.device)
-                if t.numel() != n:
-                    raise ValueError("%s must have %d elements, got %d" % (name, n, t.numel()))
+        _check_scales((("degE", degE, self.M), ("degV", degV, self.N), ("W", W, self.M)), X.device)
         if X.data_ptr() % 8 != 0:  # the entry takes 8-byte aligned rows (torch's own allocations are; views need not be)
             X = X.clone()
         if residual is not None and residual.data_ptr() % 8 != 0:
@@ -416,10 +405,6 @@ class Plan:
         Y = out if out is not None else torch.empty((self.N, F_out), dtype=torch.bfloat16, device=X.device)
         if variant == "fused":
             self._ensure_fused(F_in)
-        own_ws = workspace is None
-        if own_ws:
-            workspace = torch.empty(max(self.linear_workspace_bytes(F_in), 256), dtype=torch.uint8, device=X.device)
-        nbytes = workspace.numel() * workspace.element_size()
         with torch.cuda.device(X.device):
             if isinstance(cb, torch.Tensor):
                 _check_feat(cb, "cb", device=X.device)
@@ -429,13 +414,8 @@ class Plan:
             head = (self._h, F_in, F_out, _ptr(csrptr_t), _ptr(colind_t), _ptr(X), _ptr(degE), _ptr(degV), _ptr(W),
                     _ptr(packed), _ptr(residual), float(ca), cb_host, cb_dev, LIN_RELU if relu else 0, _ptr(t_out), _ptr(Y))
             fn = _lib.lib().hg_aggr_linear_res_bf16
-            stream = _stream_handle(X.device)
-            st = fn(*head, _ptr(workspace), nbytes, _lib.VARIANTS[variant], stream)
-            if st == _lib.HG_ERR_WORKSPACE and own_ws:  # stale cached size: see aggregate()
-                self.__dict__.setdefault("_ws_bytes", {}).pop(("lin", F_in), None)
-                workspace = torch.empty(max(self.linear_workspace_bytes(F_in), 256), dtype=torch.uint8, device=X.device)
-                st = fn(*head, _ptr(workspace), workspace.numel(), _lib.VARIANTS[variant], stream)
-            _lib.check(st)
+            self._run_with_workspace(fn, head, (_lib.VARIANTS[variant], _stream_handle(X.device)), F_in, workspace, X.device,
+                                     self.linear_workspace_bytes)
         return Y
 
     def _drop_unit_weights(self, W, enable=True):
@@ -560,11 +540,7 @@ class Plan:
         F = src.shape[1]
         if F % heads:
             raise ValueError("F = %d is no multiple of heads = %d" % (F, heads))
-        for name, t, n in (("w", w, self.nnz * heads), ("scaleA", scaleA, ndst), ("scaleB", scaleB, ndst)):
-            if t is not None:
-                _check_feat(t, name, device=src.device)
-                if t.numel() != n:
-                    raise ValueError("%s must have %d elements, got %d" % (name, n, t.numel()))
+        _check_scales((("w", w, self.nnz * heads), ("scaleA", scaleA, ndst), ("scaleB", scaleB, ndst)), src.device)
         if out is not None:
             _check_feat(out, "out", device=src.device, bf16_ok=True)
             if tuple(out.shape) != (ndst, F):
@@ -626,11 +602,7 @@ class Plan:
         hop, nsrc, ndst, F = self._reduce_args(hop, src, arg_out, out)
         if src.shape[0] != nsrc:
             raise ValueError("src must be [%d, F]" % nsrc)
-        for name, t in (("scaleA", scaleA), ("scaleB", scaleB)):
-            if t is not None:
-                _check_feat(t, name, device=src.device)
-                if t.numel() != ndst:
-                    raise ValueError("%s must have %d elements, got %d" % (name, ndst, t.numel()))
+        _check_scales((("scaleA", scaleA, ndst), ("scaleB", scaleB, ndst)), src.device)
         for name, t in (("out", out), ("arg_out", arg_out)):
             if t is not None and tuple(t.shape) != (ndst, F):
                 raise ValueError("%s must be [%d, %d]" % (name, ndst, F))
@@ -714,12 +686,8 @@ class Plan:
         F = X.shape[1]
         if F % heads:
             raise ValueError("F = %d is no multiple of heads = %d" % (F, heads))
-        for name, t, n in (("v2e", v2e, self.nnz * heads), ("e2v", e2v, self.nnz * heads), ("degE", degE, self.M),
-                           ("degV", degV, self.N), ("W", W, self.M)):
-            if t is not None:
-                _check_feat(t, name, device=X.device)
-                if t.numel() != n:
-                    raise ValueError("%s must have %d elements, got %d" % (name, n, t.numel()))
+        _check_scales((("v2e", v2e, self.nnz * heads), ("e2v", e2v, self.nnz * heads), ("degE", degE, self.M),
+                       ("degV", degV, self.N), ("W", W, self.M)), X.device)
         for name, t, rows in (("xe_out", xe_out, self.M), ("out", out, self.N)):
             if t is not None:
                 _check_feat(t, name, device=X.device, bf16_ok=bf16 and name == "out")
@@ -1000,11 +968,7 @@ class Plan:
         if seg_max is None or seg_inv is None:
             seg_max, seg_inv = self.incidence_attention_stats(csrptr_t, colind_t, sv, se, group, slope, heads=heads)
         F = self._attention_args(X, self.N, sv, se, seg_max, seg_inv, group, heads)
-        for name, t, n in (("degE", degE, self.M), ("degV", degV, self.N), ("W", W, self.M)):
-            if t is not None:
-                _check_feat(t, name, device=X.device)
-                if t.numel() != n:
-                    raise ValueError("%s must have %d elements, got %d" % (name, n, t.numel()))
+        _check_scales((("degE", degE, self.M), ("degV", degV, self.N), ("W", W, self.M)), X.device)
         for name, t, rows in (("xe_out", xe_out, self.M), ("out", out, self.N)):
             if t is not None:
                 _check_feat(t, name, device=X.device)
@@ -1033,11 +997,7 @@ class Plan:
         group = _side(group)
         nsrc, ndst = (self.N, self.M) if hop == 0 else (self.M, self.N)
         F = self._attention_args(src, nsrc, sv, se, seg_max, seg_inv, group, heads)
-        for name, t in (("scaleA", scaleA), ("scaleB", scaleB)):
-            if t is not None:
-                _check_feat(t, name, device=src.device)
-                if t.numel() != ndst:
-                    raise ValueError("%s must have %d elements, got %d" % (name, ndst, t.numel()))
+        _check_scales((("scaleA", scaleA, ndst), ("scaleB", scaleB, ndst)), src.device)
         if out is not None:
             _check_feat(out, "out", device=src.device)
             if tuple(out.shape) != (ndst, F):
@@ -1397,6 +1357,15 @@ def _bf16_lanes(F, heads, *rows):
     if F % 4 or (F // heads) % 4:
         return False
     return all(t is None or t.data_ptr() % (8 if t.dtype == torch.bfloat16 else 16) == 0 for t in rows)
+
+
+def _check_scales(pairs, device):
+    """pairs of (name, tensor or None, elements): every tensor given is a float32 feature tensor on `device` of that size."""
+    for name, t, n in pairs:
+        if t is not None:
+            _check_feat(t, name, device=device)
+            if t.numel() != n:
+                raise ValueError("%s must have %d elements, got %d" % (name, n, t.numel()))
 
 
 def _check_feat(t, name, device=None, bf16_ok=False):
