@@ -52,6 +52,8 @@ SYMBOLS = (
     "hg_gather_rows_incidence_heads_bf16", "hg_aggr_incidence_heads_bf16", "hg_incidence_dot_heads_bf16",
     "hg_gather_rows_reduce_workspace_bytes", "hg_gather_rows_reduce_f32", "hg_gather_rows_select_f32",
     "hg_knn_f32", "hg_knn_workspace_bytes",
+    "hg_table_seq_max", "hg_table_transpose_workspace_bytes", "hg_table_transpose", "hg_table_gather_f32",
+    "hg_table_gather_t_f32",
 )
 HG_REDUCE_MAX = 1
 HG_REDUCE_MIN = 2
@@ -297,6 +299,17 @@ def lib():
         L.hg_knn_workspace_bytes.argtypes = [i32, i32, i32, i32, i32]
         L.hg_knn_f32.restype = ctypes.c_int
         L.hg_knn_f32.argtypes = [vp, i32, vp, i32, i32, i32, vp, i32, i32, i32, vp, vp, vp, vp, sz, vp]
+    if hasattr(L, "hg_table_transpose"):  # likewise: aggregation over a neighbour table, no plan
+        L.hg_table_seq_max.restype = ctypes.c_int
+        L.hg_table_seq_max.argtypes = []
+        L.hg_table_transpose_workspace_bytes.restype = sz
+        L.hg_table_transpose_workspace_bytes.argtypes = [i32, i32, i32]
+        L.hg_table_transpose.restype = ctypes.c_int
+        L.hg_table_transpose.argtypes = [vp, i32, i32, i32, vp, vp, vp, sz, vp]
+        L.hg_table_gather_f32.restype = ctypes.c_int
+        L.hg_table_gather_f32.argtypes = [vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp]
+        L.hg_table_gather_t_f32.restype = ctypes.c_int
+        L.hg_table_gather_t_f32.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp]
     L.hg_aggr_push_groups_f32.restype = ctypes.c_int
     L.hg_aggr_push_groups_f32.argtypes = [i32, i32, i32, i64, vp, vp, vp, vp, vp, vp,
                                           vp, vp, vp, vp, vp, vp]

@@ -1,0 +1,478 @@
+// Aggregation over a dense neighbour table idx [rows, k] (include/hg_aggr.h, hg_table_*): the table's transpose and the
+// two row gathers, with no plan and no host step.  hg_table.h has the layout of the work; the order of every sum is in
+// include/hg_aggr.h.  The library is built without contraction, and nothing here asks for an fma: every term is rounded
+// on its own and added with one rounded add.  No floating-point atomics; the transpose's only atomics count integers in
+// LDS.
+#include <hip/hip_runtime.h>
+
+#include <string>
+
+#include "hg_aggr.h"
+#include "hg_internal.h"
+#include "hg_table.h"
+
+namespace hg {
+
+TableLayout table_layout(int64_t rows, int k, int64_t n) {
+  TableLayout L;
+  L.entries = rows * k;
+  L.tiles = (L.entries + kTableTile - 1) / kTableTile;
+  int bits = 0;
+  while (((int64_t)1 << bits) <= n) ++bits;  // the largest key is n itself
+  L.passes = (bits + kTableRadixBits - 1) / kTableRadixBits;
+  L.alt = 0;
+  L.hist = ((size_t)L.entries * 4 + 255) / 256 * 256;
+  L.total = L.hist + (size_t)kTableBins * (size_t)L.tiles * 4;
+  return L;
+}
+
+namespace {
+
+static_assert(kTableBlock == kTableBins, "one thread per bin");
+static_assert(kTableBlock == 64 * 4, "four waves rank a tile");
+
+// ---- transpose --------------------------------------------------------------------------------------------------------
+
+struct SortArgs {
+  const int32_t *idx;
+  const int32_t *in;  // the positions in the order of the pass before, or null: 0, 1, 2 ..
+  int32_t *out;
+  int32_t *hist;      // [kTableBins, tiles]: counts, then (scanned) where each tile's run of a digit starts
+  int32_t entries, n, tiles, shift;
+};
+
+// an entry that names no vertex sorts behind every vertex
+__device__ __forceinline__ int table_key(const int32_t *idx, int n, int p) {
+  const unsigned v = (unsigned)idx[p];
+  return v < (unsigned)n ? (int)v : n;
+}
+
+__global__ __launch_bounds__(kTableBlock) void table_hist_kernel(SortArgs a) {
+  __shared__ int cnt[kTableBins];
+  const int t = threadIdx.x;
+  cnt[t] = 0;
+  __syncthreads();
+  const unsigned base = blockIdx.x * (unsigned)kTableTile;
+#pragma unroll
+  for (int e = 0; e < kTableItems; ++e) {
+    const unsigned i = base + e * kTableBlock + t;
+    if (i < (unsigned)a.entries) {
+      const int p = a.in ? a.in[i] : (int)i;
+      atomicAdd(&cnt[(table_key(a.idx, a.n, p) >> a.shift) & (kTableBins - 1)], 1);
+    }
+  }
+  __syncthreads();
+  a.hist[(size_t)t * a.tiles + blockIdx.x] = cnt[t];
+}
+
+// exclusive scan of h[0 .. m) in place, by one workgroup
+__global__ __launch_bounds__(kTableScanBlock) void table_scan_kernel(int32_t *h, int64_t m) {
+  constexpr int kWaves = kTableScanBlock / 64;
+  __shared__ int wsum[kWaves];
+  const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+  int carry = 0;
+  for (int64_t b = 0; b < m; b += kTableScanBlock * 4) {
+    const int64_t i0 = b + (int64_t)t * 4;
+    int v[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) v[u] = i0 + u < m ? h[i0 + u] : 0;
+    const int s = v[0] + v[1] + v[2] + v[3];
+    int inc = s;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+      const int x = __shfl_up(inc, o, 64);
+      if (lane >= o) inc += x;
+    }
+    if (lane == 63) wsum[w] = inc;
+    __syncthreads();
+    int before = 0, total = 0;
+#pragma unroll
+    for (int j = 0; j < kWaves; ++j) {
+      const int x = wsum[j];
+      if (j < w) before += x;
+      total += x;
+    }
+    int ex = carry + before + inc - s;
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      if (i0 + u < m) h[i0 + u] = ex;
+      ex += v[u];
+    }
+    carry += total;
+    __syncthreads();
+  }
+}
+
+// A tile's positions in ascending order are (wave w, round e, lane): slot w kTableItems + e holds 64 of them.  A position's
+// place is its digit's start for this tile, plus the digit's count in the slots before, plus its rank among the slot's
+// lanes with the same digit: the order within a digit is the order of the input.
+__global__ __launch_bounds__(kTableBlock) void table_scatter_kernel(SortArgs a) {
+  constexpr int kSlots = 4 * kTableItems;
+  __shared__ int cnt[kSlots][kTableBins];
+  const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+#pragma unroll
+  for (int s = 0; s < kSlots; ++s) cnt[s][t] = 0;
+  __syncthreads();
+  const unsigned base = blockIdx.x * (unsigned)kTableTile;
+  int pv[kTableItems], dg[kTableItems], rk[kTableItems];
+#pragma unroll
+  for (int e = 0; e < kTableItems; ++e) {
+    const int slot = w * kTableItems + e;
+    const unsigned i = base + slot * 64 + lane;
+    const bool ok = i < (unsigned)a.entries;
+    const int p = ok ? (a.in ? a.in[i] : (int)i) : 0;
+    const int d = (table_key(a.idx, a.n, p) >> a.shift) & (kTableBins - 1);
+    unsigned long long same = __ballot(ok);
+#pragma unroll
+    for (int b = 0; b < kTableRadixBits; ++b) {
+      const bool bit = (d >> b) & 1;
+      const unsigned long long have = __ballot(ok && bit);
+      same &= bit ? have : ~have;
+    }
+    const int rank = __popcll(same & ((1ull << lane) - 1ull));
+    if (ok && rank == 0) cnt[slot][d] = __popcll(same);
+    pv[e] = p;
+    dg[e] = ok ? d : -1;
+    rk[e] = rank;
+  }
+  __syncthreads();
+  {
+    int run = a.hist[(size_t)t * a.tiles + blockIdx.x];
+#pragma unroll
+    for (int s = 0; s < kSlots; ++s) {
+      const int c = cnt[s][t];
+      cnt[s][t] = run;
+      run += c;
+    }
+  }
+  __syncthreads();
+#pragma unroll
+  for (int e = 0; e < kTableItems; ++e)
+    if (dg[e] >= 0) {
+      const unsigned at = (unsigned)(cnt[w * kTableItems + e][dg[e]] + rk[e]);
+      if (at < (unsigned)a.entries) a.out[at] = pv[e];
+    }
+}
+
+// pos is sorted by key: vertex u's entries start where the first key >= u stands
+__global__ __launch_bounds__(256) void table_ptr_kernel(const int32_t *idx, const int32_t *pos, int32_t entries, int32_t n,
+                                                       int32_t *ptr_v) {
+  const unsigned q = blockIdx.x * 256u + threadIdx.x;
+  if (q > (unsigned)entries) return;
+  const int before = q == 0 ? -1 : table_key(idx, n, pos[q - 1]);
+  const int here = q == (unsigned)entries ? n : table_key(idx, n, pos[q]);
+  for (int u = before + 1; u <= here; ++u) ptr_v[u] = (int32_t)q;
+}
+
+// ---- gathers ----------------------------------------------------------------------------------------------------------
+
+struct TableGatherArgs {
+  const int32_t *idx;            // the table [rows, k] (the hyperedge gather)
+  const int32_t *ptr_v, *pos_v;  // its transpose (the vertex gather)
+  const float *src, *w, *src_scale, *dst_scale;
+  float *dst;
+  int32_t nrows, nsrc;  // destination and source rows
+  int32_t k, F, entries;
+  int32_t L, R;         // lanes per row, rows per wave
+  int32_t P2;           // the power of two at or above kTableWaves R
+};
+
+template <int V>
+struct Cols {
+  float v[V];
+};
+
+template <int V>
+__device__ __forceinline__ Cols<V> cols_load(const float *p) {
+  Cols<V> r;
+  if constexpr (V == 4) {
+    const float4 x = *reinterpret_cast<const float4 *>(p);
+    r.v[0] = x.x;
+    r.v[1] = x.y;
+    r.v[2] = x.z;
+    r.v[3] = x.w;
+  } else {
+    r.v[0] = *p;
+  }
+  return r;
+}
+
+template <int V>
+__device__ __forceinline__ void cols_store(float *p, const float (&v)[V]) {
+  if constexpr (V == 4) *reinterpret_cast<float4 *>(p) = float4{v[0], v[1], v[2], v[3]};
+  else *p = v[0];
+}
+
+// acc += the terms of the entries [beg, end), ascending, for the columns c .. c + V - 1.  T: an entry q is position
+// pos_v[q] of the table and gathers the hyperedge's row; else it is position q itself and gathers row idx[q].  A batch of
+// row loads is issued, then added in order.  An entry that is out of range loads row 0 and is not added.
+template <bool T, int V>
+__device__ __forceinline__ void table_row_sum(const TableGatherArgs &a, int beg, int end, int c, float (&acc)[V]) {
+  for (int b = beg; b < end; b += kTableBatch) {
+    Cols<V> x[kTableBatch];
+    float wv[kTableBatch], sv[kTableBatch];
+    bool ok[kTableBatch];
+#pragma unroll
+    for (int u = 0; u < kTableBatch; ++u) {
+      const int q = b + u;
+      bool o = q < end;
+      int p, j;
+      if (T) {
+        p = a.pos_v[o ? q : 0];
+        o = o && (unsigned)p < (unsigned)a.entries;
+        p = o ? p : 0;
+        j = p / a.k;
+      } else {
+        p = o ? q : 0;
+        j = a.idx[p];
+        o = o && (unsigned)j < (unsigned)a.nsrc;
+        j = o ? j : 0;
+      }
+      ok[u] = o;
+      wv[u] = a.w ? a.w[p] : 1.f;
+      sv[u] = a.src_scale ? a.src_scale[j] : 1.f;
+      x[u] = cols_load<V>(a.src + (size_t)j * a.F + c);
+    }
+#pragma unroll
+    for (int u = 0; u < kTableBatch; ++u)
+#pragma unroll
+      for (int i = 0; i < V; ++i) {
+        float term = x[u].v[i];
+        if (a.src_scale) term = term * sv[u];
+        if (a.w) term = term * wv[u];
+        acc[i] = ok[u] ? acc[i] + term : acc[i];
+      }
+  }
+}
+
+template <bool T, int V>
+__global__ __launch_bounds__(64 * kTableWaves) void table_gather_kernel(TableGatherArgs a) {
+  const int t = threadIdx.x, w = t >> 6, lane = t & 63;
+  const int L = a.L, R = a.R, F = a.F;
+  const int sub = lane / L, cl = lane - sub * L;
+  const bool lane_on = sub < R;
+  const int RW = R * kTableWaves;
+  const int64_t row0 = (int64_t)blockIdx.x * RW;
+  const int64_t row64 = row0 + w * R + sub;
+  const bool row_on = lane_on && row64 < a.nrows;
+  const int row = row_on ? (int)row64 : 0;
+  int beg = 0, end = 0;
+  if (row_on) {
+    if (T) {
+      beg = max(a.ptr_v[row], 0);
+      end = min(a.ptr_v[row + 1], a.entries);
+    } else {
+      beg = row * a.k;
+      end = beg + a.k;
+    }
+  }
+  const bool is_long = T && end - beg > kTableSeqMax;
+
+  if (row_on && !is_long) {
+    const float ds = a.dst_scale ? a.dst_scale[row] : 1.f;
+    for (int c0 = 0; c0 < F; c0 += L * V) {
+      const int c = c0 + cl * V;
+      if (c >= F) continue;
+      float acc[V];
+#pragma unroll
+      for (int i = 0; i < V; ++i) acc[i] = 0.f;
+      table_row_sum<T, V>(a, beg, end, c, acc);
+      if (a.dst_scale && end > beg) {  // an empty row stays +0.0 whatever its scale
+#pragma unroll
+        for (int i = 0; i < V; ++i) acc[i] = ds * acc[i];
+      }
+      cols_store<V>(a.dst + (size_t)row * F + c, acc);
+    }
+  }
+
+  if constexpr (T) {
+    // the tile's long rows, one after the other, by the whole workgroup
+    __shared__ __attribute__((aligned(16))) float part[kTableWaves * 64 * V];
+    __shared__ unsigned long long long_rows[kTableWaves];
+    const unsigned long long mine = __ballot(row_on && is_long && cl == 0);
+    if (lane == 0) long_rows[w] = mine;
+    __syncthreads();
+    const int P = RW, g = w * R + sub;
+    for (int ww = 0; ww < kTableWaves; ++ww) {
+      const unsigned long long mm = long_rows[ww];
+      unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)mm), hi = __builtin_amdgcn_readfirstlane((unsigned)(mm >> 32));
+      unsigned long long m = ((unsigned long long)hi << 32) | lo;
+      while (m) {
+        const int ln = __ffsll((long long)m) - 1;
+        m &= m - 1;
+        const int lrow = (int)(row0 + ww * R + ln / L);
+        const int lbeg = max(a.ptr_v[lrow], 0), lend = min(a.ptr_v[lrow + 1], a.entries);
+        const int64_t len = lend - lbeg, chunk = (len + P - 1) / P;
+        const int gb = lbeg + (int)min((int64_t)g * chunk, len), ge = lbeg + (int)min((int64_t)(g + 1) * chunk, len);
+        const float ds = a.dst_scale ? a.dst_scale[lrow] : 1.f;
+        for (int c0 = 0; c0 < F; c0 += L * V) {
+          const int c = c0 + cl * V;
+          const bool on = lane_on && c < F;
+          float *mypart = part + (size_t)(g * L + cl) * V;
+          if (on) {
+            float acc[V];
+#pragma unroll
+            for (int i = 0; i < V; ++i) acc[i] = 0.f;
+            table_row_sum<T, V>(a, gb, ge, c, acc);
+#pragma unroll
+            for (int i = 0; i < V; ++i) mypart[i] = acc[i];
+          }
+          __syncthreads();
+          for (int s = a.P2 >> 1; s >= 1; s >>= 1) {
+            if (on && g < s && g + s < P) {
+              const float *other = part + (size_t)((g + s) * L + cl) * V;
+#pragma unroll
+              for (int i = 0; i < V; ++i) mypart[i] = mypart[i] + other[i];
+            }
+            __syncthreads();
+          }
+          if (on && g == 0) {
+            float out[V];
+#pragma unroll
+            for (int i = 0; i < V; ++i) out[i] = a.dst_scale ? ds * mypart[i] : mypart[i];
+            cols_store<V>(a.dst + (size_t)lrow * F + c, out);
+          }
+          __syncthreads();
+        }
+      }
+    }
+  }
+}
+
+int fail(const char *entry, int status, const std::string &msg) {
+  set_error(std::string(entry) + ": " + msg);
+  return status;
+}
+
+// what both gathers refuse about the table and the rows, in the order include/hg_aggr.h gives
+int gather_refusal(const char *entry, int32_t rows, int32_t k, int32_t n, int32_t F, const float *src, const float *w,
+                   const float *src_scale, const float *dst_scale, const float *dst) {
+  if (!src || !dst) return fail(entry, HG_ERR_INVALID, "null src or dst");
+  if (rows < 1 || n < 1 || F < 1) return fail(entry, HG_ERR_INVALID, "rows, n and F must be at least 1");
+  if (k < 1 || k > kTableMaxK) return fail(entry, HG_ERR_INVALID, "k must be in 1 .. 64, got " + std::to_string(k));
+  if ((int64_t)rows * k > INT32_MAX) return fail(entry, HG_ERR_INVALID, "rows * k must be below 2^31");
+  for (const void *p : {(const void *)src, (const void *)w, (const void *)src_scale, (const void *)dst_scale, (const void *)dst})
+    if ((uintptr_t)p % 4) return fail(entry, HG_ERR_UNSUPPORTED, "src, w, the scales and dst must be 4-byte aligned");
+  return HG_OK;
+}
+
+template <bool T>
+int launch_table_gather(const char *entry, TableGatherArgs a, hipStream_t s) {
+  const bool vec4 = a.F % 4 == 0 && (uintptr_t)a.src % 16 == 0 && (uintptr_t)a.dst % 16 == 0;
+  const int V = vec4 ? 4 : 1;
+  a.L = std::min((a.F + V - 1) / V, 64);
+  a.R = 64 / a.L;
+  a.P2 = 1;
+  while (a.P2 < a.R * kTableWaves) a.P2 <<= 1;
+  const int RW = a.R * kTableWaves;
+  const dim3 grid((unsigned)(((int64_t)a.nrows + RW - 1) / RW)), block(64 * kTableWaves);
+  if (vec4) hipLaunchKernelGGL((table_gather_kernel<T, 4>), grid, block, 0, s, a);
+  else hipLaunchKernelGGL((table_gather_kernel<T, 1>), grid, block, 0, s, a);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail(entry, HG_ERR_HIP, std::string("launch: ") + hipGetErrorString(e));
+  return HG_OK;
+}
+
+}  // namespace
+}  // namespace hg
+
+extern "C" {
+
+int hg_table_seq_max(void) { return hg::kTableSeqMax; }
+
+size_t hg_table_transpose_workspace_bytes(int32_t rows, int32_t k, int32_t n) {
+  if (rows < 1 || n < 1 || k < 1 || k > hg::kTableMaxK || (int64_t)rows * k > INT32_MAX) return 0;
+  return hg::table_layout(rows, k, n).total;
+}
+
+int hg_table_transpose(const int32_t *idx, int32_t rows, int32_t k, int32_t n, int32_t *ptr_v, int32_t *pos_v,
+                       void *workspace, size_t workspace_bytes, hg_stream_t stream) {
+  using namespace hg;
+  const char *entry = "hg_table_transpose";
+  if (!idx || !ptr_v || !pos_v) return fail(entry, HG_ERR_INVALID, "null idx, ptr_v or pos_v");
+  if (rows < 1 || n < 1) return fail(entry, HG_ERR_INVALID, "rows and n must be at least 1");
+  if (k < 1 || k > kTableMaxK) return fail(entry, HG_ERR_INVALID, "k must be in 1 .. 64, got " + std::to_string(k));
+  if ((int64_t)rows * k > INT32_MAX) return fail(entry, HG_ERR_INVALID, "rows * k must be below 2^31");
+  for (const void *p : {(const void *)idx, (const void *)ptr_v, (const void *)pos_v})
+    if ((uintptr_t)p % 4) return fail(entry, HG_ERR_UNSUPPORTED, "idx, ptr_v and pos_v must be 4-byte aligned");
+  const TableLayout L = table_layout(rows, k, n);
+  if (!workspace || workspace_bytes < L.total || (uintptr_t)workspace % 4) {
+    set_error(std::string(entry) + ": workspace of " + std::to_string(workspace_bytes) +
+              " bytes, hg_table_transpose_workspace_bytes asks for " + std::to_string(L.total) + " (4-byte aligned)");
+    return HG_ERR_WORKSPACE;
+  }
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  unsigned char *ws = static_cast<unsigned char *>(workspace);
+  int32_t *alt = reinterpret_cast<int32_t *>(ws + L.alt);
+  SortArgs a{};
+  a.idx = idx;
+  a.hist = reinterpret_cast<int32_t *>(ws + L.hist);
+  a.entries = (int32_t)L.entries;
+  a.n = n;
+  a.tiles = (int32_t)L.tiles;
+  hipError_t e = hipSuccess;
+  for (int pass = 0; pass < L.passes && e == hipSuccess; ++pass) {
+    a.shift = pass * kTableRadixBits;
+    a.out = (L.passes - 1 - pass) % 2 == 0 ? pos_v : alt;  // the last pass writes pos_v
+    hipLaunchKernelGGL(table_hist_kernel, dim3((unsigned)L.tiles), dim3(kTableBlock), 0, s, a);
+    hipLaunchKernelGGL(table_scan_kernel, dim3(1), dim3(kTableScanBlock), 0, s, a.hist, (int64_t)kTableBins * L.tiles);
+    hipLaunchKernelGGL(table_scatter_kernel, dim3((unsigned)L.tiles), dim3(kTableBlock), 0, s, a);
+    e = hipGetLastError();
+    a.in = a.out;
+  }
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(table_ptr_kernel, dim3((unsigned)(L.entries / 256 + 1)), dim3(256), 0, s, idx, (const int32_t *)pos_v,
+                       a.entries, n, ptr_v);
+    e = hipGetLastError();
+  }
+  if (e != hipSuccess) return fail(entry, HG_ERR_HIP, std::string("launch: ") + hipGetErrorString(e));
+  return HG_OK;
+}
+
+int hg_table_gather_f32(const int32_t *idx, int32_t rows, int32_t k, int32_t n, int32_t F, const float *src, const float *w,
+                        const float *src_scale, const float *dst_scale, float *dst, hg_stream_t stream) {
+  using namespace hg;
+  const char *entry = "hg_table_gather_f32";
+  if (!idx) return fail(entry, HG_ERR_INVALID, "null idx");
+  if (const int st = gather_refusal(entry, rows, k, n, F, src, w, src_scale, dst_scale, dst)) return st;
+  if ((uintptr_t)idx % 4) return fail(entry, HG_ERR_UNSUPPORTED, "idx must be 4-byte aligned");
+  TableGatherArgs a{};
+  a.idx = idx;
+  a.src = src;
+  a.w = w;
+  a.src_scale = src_scale;
+  a.dst_scale = dst_scale;
+  a.dst = dst;
+  a.nrows = rows;
+  a.nsrc = n;
+  a.k = k;
+  a.F = F;
+  a.entries = rows * k;
+  return launch_table_gather<false>(entry, a, static_cast<hipStream_t>(stream));
+}
+
+int hg_table_gather_t_f32(const int32_t *ptr_v, const int32_t *pos_v, int32_t rows, int32_t k, int32_t n, int32_t F,
+                          const float *src, const float *w, const float *src_scale, const float *dst_scale, float *dst,
+                          hg_stream_t stream) {
+  using namespace hg;
+  const char *entry = "hg_table_gather_t_f32";
+  if (!ptr_v || !pos_v) return fail(entry, HG_ERR_INVALID, "null ptr_v or pos_v");
+  if (const int st = gather_refusal(entry, rows, k, n, F, src, w, src_scale, dst_scale, dst)) return st;
+  if ((uintptr_t)ptr_v % 4 || (uintptr_t)pos_v % 4) return fail(entry, HG_ERR_UNSUPPORTED, "ptr_v and pos_v must be 4-byte aligned");
+  TableGatherArgs a{};
+  a.ptr_v = ptr_v;
+  a.pos_v = pos_v;
+  a.src = src;
+  a.w = w;
+  a.src_scale = src_scale;
+  a.dst_scale = dst_scale;
+  a.dst = dst;
+  a.nrows = n;
+  a.nsrc = rows;
+  a.k = k;
+  a.F = F;
+  a.entries = rows * k;
+  return launch_table_gather<true>(entry, a, static_cast<hipStream_t>(stream));
+}
+
+}  // extern "C"

@@ -4,6 +4,9 @@ device without the N x N distance matrix.
 
 `knn` and `knn_incidence_weights` are exported as `ops.knn` / `ops.knn_incidence_weights`; `incidence_from_knn` is the
 host-side layout step of `HyperGraph.from_knn`.
+
+`knn_transpose` and `knn_aggr` (`ops.knn_transpose` / `ops.knn_aggr`; hg_table_* in include/hg_aggr.h) aggregate over the
+neighbour table itself, with no plan and no host step, and `KnnHypergraph` is the device-only hypergraph they serve.
 """
 import ctypes
 import numbers
@@ -121,3 +124,235 @@ def incidence_from_knn(idx, name="knn"):
     if idx.size and (idx.min() < 0 or idx.max() >= N):
         raise ValueError("idx must hold row numbers in 0 .. %d" % (N - 1))
     return Incidence(N, N, np.arange(0, N * k + 1, k, dtype=np.int64), idx.reshape(-1), name)
+
+
+# ---- aggregation over the neighbour table itself, no plan (include/hg_aggr.h, hg_table_*) ---------------------------------
+
+def _table_shape(idx):
+    """(rows, k) of a neighbour table, checked: the dtype first (TypeError), then the shape and k (ValueError)."""
+    if not isinstance(idx, torch.Tensor) or idx.dtype != torch.int32:
+        raise TypeError("idx must be an int32 tensor [rows, k] (ops.knn's table), got %s" % (getattr(idx, "dtype", type(idx)),))
+    return idx.shape
+
+
+def _table_shape_values(idx):
+    if idx.dim() != 2 or idx.shape[0] < 1:
+        raise ValueError("idx must be [rows >= 1, k], got %s" % (tuple(idx.shape),))
+    rows, k = idx.shape
+    if not 1 <= k <= K_MAX:
+        raise ValueError("k must be in 1 .. %d, got idx of %s" % (K_MAX, tuple(idx.shape)))
+    if rows * k >= 2 ** 31:
+        raise ValueError("rows * k must be below 2^31, got %d x %d" % (rows, k))
+    return rows, k
+
+
+def _check_table_index(t, name):
+    if not t.is_cuda:
+        raise RuntimeError("%s must be on a GPU (no CPU fallback in this backend)" % name)
+    if not t.is_contiguous():
+        raise RuntimeError("%s must be contiguous" % name)
+
+
+def knn_transpose(idx, n=None):
+    """The transpose of a neighbour table idx [rows, k] (int32, ops.knn's) over n vertices (default: rows), on the device:
+    (ptr_v int32 [n + 1], pos_v int32 [rows * k]).  pos_v[ptr_v[v] : ptr_v[v + 1]] are the positions p = i * k + s with
+    idx[i, s] == v in ascending p -- the stable sort of the positions by vertex, so hyperedge p // k and slot p % k come
+    from the position and pos_v indexes a weight [rows * k] directly.  An entry outside 0 .. n - 1 is ignored: ptr_v[n] is
+    the number of valid entries and pos_v is unspecified from there on.  Nothing is read back and nothing waits.
+    Refusals, before a device is touched: TypeError for anything but int32, ValueError for the shape, k or n, RuntimeError
+    for a CPU tensor."""
+    _table_shape(idx)
+    rows, k = _table_shape_values(idx)
+    if n is None:
+        n = rows
+    if not isinstance(n, numbers.Integral) or isinstance(n, bool) or not 1 <= n < 2 ** 31 - 1:
+        raise ValueError("n must be a positive integer, got %r" % (n,))
+    _check_table_index(idx, "idx")
+    n = int(n)
+    dev = idx.device
+    L = _lib.lib()
+    ptr_v = torch.empty(n + 1, dtype=torch.int32, device=dev)
+    pos_v = torch.empty(rows * k, dtype=torch.int32, device=dev)
+    ws_bytes = L.hg_table_transpose_workspace_bytes(rows, k, n)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(L.hg_table_transpose(_ptr(idx), rows, k, n, _ptr(ptr_v), _ptr(pos_v), _ptr(ws), ws_bytes,
+                                        _stream_handle(dev)))
+    return ptr_v, pos_v
+
+
+def _flat_or_none(t, name, count, dev):
+    """A float32 device tensor of `count` elements (any shape) as the kernels take it, or None."""
+    if t is None:
+        return None
+    _check_feat(t, name, device=dev)
+    if t.numel() != count:
+        raise ValueError("%s must have %d elements, got %s" % (name, count, tuple(t.shape)))
+    return t
+
+
+def table_gather(idx, src, w=None, src_scale=None, dst_scale=None):
+    """dst[i] = dst_scale[i] * sum_s (src[idx[i, s]] * src_scale[idx[i, s]]) * w[i * k + s] over a table idx [rows, k] and rows
+    src [n, F]: hg_table_gather_f32, every row summed in ascending s.  Any of w [rows * k], src_scale [n], dst_scale [rows]
+    may be None (no multiplication).  An entry outside 0 .. n - 1 adds nothing.  No gradient."""
+    _table_shape(idx)
+    rows, k = _table_shape_values(idx)
+    _check_table_index(idx, "idx")
+    _check_feat(src, "src", device=idx.device)
+    if src.dim() != 2 or src.shape[0] < 1 or src.shape[1] < 1:
+        raise ValueError("src must be [n >= 1, F >= 1], got %s" % (tuple(src.shape),))
+    n, F = src.shape
+    dev = idx.device
+    w = _flat_or_none(w, "w", rows * k, dev)
+    src_scale = _flat_or_none(src_scale, "src_scale", n, dev)
+    dst_scale = _flat_or_none(dst_scale, "dst_scale", rows, dev)
+    dst = torch.empty((rows, F), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().hg_table_gather_f32(_ptr(idx), rows, k, n, F, _ptr(src), _ptr(w), _ptr(src_scale),
+                                                  _ptr(dst_scale), _ptr(dst), _stream_handle(dev)))
+    return dst
+
+
+def table_gather_t(ptr_v, pos_v, k, src, w=None, src_scale=None, dst_scale=None):
+    """dst[v] = dst_scale[v] * sum_q (src[pos_v[q] // k] * src_scale[pos_v[q] // k]) * w[pos_v[q]], q over ptr_v[v] ..
+    ptr_v[v + 1] - 1, for the transpose (ptr_v [n + 1], pos_v [rows * k]) of a table of k columns and rows src [rows, F]:
+    hg_table_gather_t_f32.  A row of at most TABLE_SEQ_MAX entries is summed in ascending q; a longer one by its whole
+    workgroup in an order fixed by its length and F.  A vertex with no entry is +0.0 whatever dst_scale.  No gradient."""
+    for name, t in (("ptr_v", ptr_v), ("pos_v", pos_v)):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.int32:
+            raise TypeError("%s must be an int32 tensor, got %s" % (name, getattr(t, "dtype", type(t))))
+    if not isinstance(k, numbers.Integral) or isinstance(k, bool) or not 1 <= k <= K_MAX:
+        raise ValueError("k must be an integer in 1 .. %d, got %r" % (K_MAX, k))
+    if ptr_v.dim() != 1 or ptr_v.shape[0] < 2 or pos_v.dim() != 1:
+        raise ValueError("ptr_v must be [n + 1] and pos_v [rows * k], got %s and %s" % (tuple(ptr_v.shape), tuple(pos_v.shape)))
+    _check_table_index(ptr_v, "ptr_v")
+    _check_table_index(pos_v, "pos_v")
+    dev = ptr_v.device
+    _check_feat(src, "src", device=dev)
+    if src.dim() != 2 or src.shape[0] < 1 or src.shape[1] < 1 or src.shape[0] * int(k) != pos_v.shape[0]:
+        raise ValueError("src must be [rows, F >= 1] with rows * k = %d positions, got %s" % (pos_v.shape[0], tuple(src.shape)))
+    rows, F = src.shape
+    n = ptr_v.shape[0] - 1
+    w = _flat_or_none(w, "w", rows * int(k), dev)
+    src_scale = _flat_or_none(src_scale, "src_scale", rows, dev)
+    dst_scale = _flat_or_none(dst_scale, "dst_scale", n, dev)
+    dst = torch.empty((n, F), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().hg_table_gather_t_f32(_ptr(ptr_v), _ptr(pos_v), rows, int(k), n, F, _ptr(src), _ptr(w),
+                                                    _ptr(src_scale), _ptr(dst_scale), _ptr(dst), _stream_handle(dev)))
+    return dst
+
+
+class _KnnAggr(torch.autograd.Function):
+    """Y = degV . H_w (degE . (H_w^T X)) over a neighbour table; the gradient of X is the same two gathers swapped.  Saves the
+    table, its transpose, the weight and the scales -- nothing of rows * F elements."""
+
+    @staticmethod
+    def forward(ctx, X, idx, ptr_v, pos_v, w, degE, degV):
+        k = idx.shape[1]
+        Xe = table_gather(idx, X, w, None, degE)
+        Y = table_gather_t(ptr_v, pos_v, k, Xe, w, None, degV)
+        ctx.save_for_backward(idx, ptr_v, pos_v, w, degE, degV)
+        return Y
+
+    @staticmethod
+    def backward(ctx, dY):
+        idx, ptr_v, pos_v, w, degE, degV = ctx.saved_tensors
+        G = table_gather(idx, dY.contiguous(), w, degV, degE)
+        dX = table_gather_t(ptr_v, pos_v, idx.shape[1], G, w)
+        return dX, None, None, None, None, None, None
+
+
+def knn_aggr(idx, X, weight=None, degE=None, degV=None, transpose=None):
+    """Y = degV . H_w (degE . (H_w^T X)) over the hypergraph of a neighbour table idx [rows, k] (int32, ops.knn's: hyperedge
+    i = the vertices idx[i, :]) and features X [n, F] (float32), with no plan and no host step: two launches of the table
+    gathers (include/hg_aggr.h, hg_table_gather_f32 / hg_table_gather_t_f32) and, where `transpose` is None, the transpose.
+    weight [rows * k] or [rows, k] weights entry (i, s) in both hops, as HGNNAggrIncidence(hyperg, Z, w, w, ..) does for a
+    probabilistic kNN hypergraph (ops.knn_incidence_weights); degE [rows] or [rows, 1] scales the hyperedges, degV [n] or
+    [n, 1] the vertices; each may be None (no multiplication).  transpose: the (ptr_v, pos_v) of ops.knn_transpose(idx, n)
+    to reuse.  The gradient of X is exact: G = table_gather(dY, src_scale=degV, dst_scale=degE, w), dX = table_gather_t(G,
+    w).  weight, degE and degV get no gradient -- kNN weights come from detached distances -- and one that requires a
+    gradient is refused.  Deterministic: the order of every sum is hg_aggr.h's, two calls give the same bits.
+    Refusals, in this order and before a device is touched: TypeError for an idx (ptr_v, pos_v) that is not int32 and for
+    an X, weight, degE or degV that is not float32; ValueError for the shapes and k; RuntimeError for a weight, degE or
+    degV that requires a gradient, and for CPU tensors."""
+    _table_shape(idx)
+    if not isinstance(X, torch.Tensor) or X.dtype != torch.float32:
+        raise TypeError("X must be a float32 tensor (knn_aggr has no bfloat16 / float16 / float64 form), got %s"
+                        % (getattr(X, "dtype", type(X)),))
+    scales = (("weight", weight), ("degE", degE), ("degV", degV))
+    for name, t in scales:
+        if t is not None and (not isinstance(t, torch.Tensor) or t.dtype != torch.float32):
+            raise TypeError("%s must be a float32 tensor, got %s" % (name, getattr(t, "dtype", type(t))))
+    if transpose is not None:
+        if not isinstance(transpose, (tuple, list)) or len(transpose) != 2:
+            raise TypeError("transpose must be the pair (ptr_v, pos_v) of knn_transpose")
+        for name, t in zip(("ptr_v", "pos_v"), transpose):
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.int32:
+                raise TypeError("transpose's %s must be an int32 tensor, got %s" % (name, getattr(t, "dtype", type(t))))
+    rows, k = _table_shape_values(idx)
+    if X.dim() != 2 or X.shape[0] < 1 or X.shape[1] < 1:
+        raise ValueError("X must be [n >= 1, F >= 1], got %s" % (tuple(X.shape),))
+    n = X.shape[0]
+    if weight is not None and tuple(weight.shape) not in ((rows * k,), (rows, k)):
+        raise ValueError("weight must be [rows * k] = [%d] or [rows, k] = [%d, %d], got %s" % (rows * k, rows, k, tuple(weight.shape)))
+    for name, t, count in (("degE", degE, rows), ("degV", degV, n)):
+        if t is not None and tuple(t.shape) not in ((count,), (count, 1)):
+            raise ValueError("%s must be [%d] or [%d, 1], got %s" % (name, count, count, tuple(t.shape)))
+    if transpose is not None and (tuple(transpose[0].shape) != (n + 1,) or tuple(transpose[1].shape) != (rows * k,)):
+        raise ValueError("transpose must be (ptr_v [%d], pos_v [%d]), got %s and %s"
+                         % (n + 1, rows * k, tuple(transpose[0].shape), tuple(transpose[1].shape)))
+    if torch.is_grad_enabled():
+        for name, t in scales:
+            if t is not None and t.requires_grad:
+                raise RuntimeError("%s gets no gradient from knn_aggr: pass %s.detach()" % (name, name))
+    _check_table_index(idx, "idx")
+    _check_feat(X, "X", device=idx.device)
+    for name, t in scales:
+        if t is not None:
+            _check_feat(t, name, device=idx.device)
+    if transpose is None:
+        transpose = knn_transpose(idx, n)
+    ptr_v, pos_v = transpose
+    _check_table_index(ptr_v, "ptr_v")
+    _check_table_index(pos_v, "pos_v")
+    detach = [None if t is None else t.detach() for _, t in scales]
+    return _KnnAggr.apply(X, idx, ptr_v, pos_v, *detach)
+
+
+class KnnHypergraph:
+    """The hypergraph "each vertex and its k - 1 nearest neighbours" as a device-only object: what HyperGraph.from_knn builds,
+    without the read-back, the host transpose and the plan.  Nothing here reads a tensor back; with segments=None nothing
+    waits for the device either (ops.knn waits once for its segment offsets).
+      idx [N, k], dist [N, k] (squared), mean [N]: ops.knn(X, k, self_first=True, return_mean=True)
+      ptr_v [N + 1], pos_v [N k]: ops.knn_transpose(idx)
+      degE [N, 1] = 1 / k and degV [N, 1] = in-degree^-1/2, 1 where no hyperedge names the vertex (HyperGraph's formulas)
+      weights(m_prob): HGNN's exp(-d2 / (m_prob mean)^2) entries [N k]
+      aggregate(Z, probabilistic=False, m_prob=1.0): ops.knn_aggr over the table."""
+
+    @classmethod
+    def build(cls, X, k, segments=None):
+        self = cls.__new__(cls)
+        if isinstance(X, torch.Tensor):  # anything else is ops.knn's refusal
+            X = X.detach().contiguous()
+        self.idx, self.dist, self.mean = knn(X, k, segments=segments, self_first=True, return_mean=True)
+        N = self.idx.shape[0]
+        self.k, self.num_nodes, self.num_edges, self.nnz = int(k), N, N, N * int(k)
+        self.device = self.idx.device
+        self.ptr_v, self.pos_v = knn_transpose(self.idx, N)
+        self.degE = torch.full((N, 1), 1.0 / int(k), dtype=torch.float32, device=self.device)
+        deg = (self.ptr_v[1:] - self.ptr_v[:-1]).to(torch.float32).reshape(N, 1)
+        self.degV = torch.where(deg > 0, deg.pow(-0.5), torch.ones_like(deg))
+        return self
+
+    def weights(self, m_prob=1.0):
+        return knn_incidence_weights(self.dist, self.mean, m_prob)
+
+    def aggregate(self, Z, probabilistic=False, m_prob=1.0):
+        w = self.weights(m_prob) if probabilistic else None
+        return knn_aggr(self.idx, Z, w, self.degE, self.degV, transpose=(self.ptr_v, self.pos_v))
+
+
+def table_seq_max():
+    """HG_TABLE_SEQ_MAX of the library as built: the longest row one lane group sums in ascending order."""
+    return int(_lib.lib().hg_table_seq_max())

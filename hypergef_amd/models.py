@@ -140,9 +140,17 @@ class DynamicHypergraphConv(nn.Module):
         Z = lin(X),   Y = degV . H (degE . (H^T Z))          (HGNNAggr on HyperGraph.from_knn(X, k)),
     or, with probabilistic=True, the same sums weighted by HGNN's exp(-d2 / mean^2) entries on both hops
     (HGNNAggrIncidence with hyperg.knn_weights(m_prob)).  segments: ops.knn's host offsets -- a batch of point sets in
-    one tensor, every set its own hypergraph.  The hypergraph of the last forward stays in `hyperg`."""
+    one tensor, every set its own hypergraph.  The hypergraph of the last forward stays in `hyperg`.
+    device_graph=True: the hypergraph never leaves the device -- knn_graph.KnnHypergraph (table, transpose and degrees
+    built on the device) and ops.knn_aggr (two gathers over the table, no plan) in place of HyperGraph.from_knn and the
+    planned operators; `hyperg` is then the KnnHypergraph.  The same layer, parameter for parameter, and the same sums in
+    another order.  With segments=None a forward and backward then waits for the device nowhere and allocates only through
+    torch, so the layer can be recorded into a hipGraph (torch.cuda.graph) and the neighbours are searched again on every
+    replay.  With segments, ops.knn still waits once for its offsets: such a layer runs eagerly only.  False (the default)
+    is the layer above, untouched."""
 
-    def __init__(self, in_channels, out_channels, k, probabilistic=False, segments=None, m_prob=1.0, options=None):
+    def __init__(self, in_channels, out_channels, k, probabilistic=False, segments=None, m_prob=1.0, options=None,
+                 device_graph=False):
         super().__init__()
         if not isinstance(k, int) or not 1 <= k <= 64:
             raise ValueError("k must be an integer in 1 .. 64, got %r" % (k,))
@@ -150,9 +158,14 @@ class DynamicHypergraphConv(nn.Module):
         self.lin = ops.Linear(in_channels, out_channels, bias=False, options=options)
         self.in_channels, self.out_channels, self.k = in_channels, out_channels, k
         self.probabilistic, self.segments, self.m_prob = probabilistic, segments, m_prob
+        self.device_graph = bool(device_graph)
         self.hyperg = None
 
     def forward(self, X):
+        if self.device_graph:
+            from .knn_graph import KnnHypergraph
+            hyperg = self.hyperg = KnnHypergraph.build(X, self.k, segments=self.segments)
+            return hyperg.aggregate(self.lin(X), probabilistic=self.probabilistic, m_prob=self.m_prob)
         from .hypergraph import HyperGraph
         hyperg = self.hyperg = HyperGraph.from_knn(X.detach(), self.k, X.device, segments=self.segments)
         Z = self.lin(X)

@@ -852,6 +852,50 @@ HG_API int hg_knn_f32(const float *Q, int32_t nq, const float *X, int32_t n, int
                       void *workspace, size_t workspace_bytes, hg_stream_t stream);
 HG_API size_t hg_knn_workspace_bytes(int32_t nq, int32_t n, int32_t F, int32_t k, int32_t cand_slices);
 
+/* Aggregation over a dense neighbour table, with no plan (csrc/hg_table.hip).  idx [rows, k] int32 is what hg_knn_f32
+ * writes: hyperedge i has the k members idx[i, 0 .. k - 1], so H_T is the table itself (csrptr_t an arange) and position
+ * p = i k + s of the table is entry s of hyperedge i.  1 <= k <= 64 and rows * k < 2^31.  None of the three entries
+ * allocates, synchronises or copies to or from the host: each launches on `stream` and returns, so each can be recorded
+ * into a hipGraph.  float32 only.
+ *
+ * hg_table_transpose: ptr_v [n + 1] receives the CSR offsets of the n vertices and pos_v[ptr_v[v] .. ptr_v[v + 1]) the
+ *   positions p with idx[p] == v in ASCENDING p: the stable sort of the positions by vertex, a function of idx alone.
+ *   Hyperedge p / k and slot p % k come from the position, so pos_v is column index and weight index in one.  An entry of
+ *   idx outside 0 .. n - 1 is counted nowhere: ptr_v[n] is the number of valid entries and pos_v [rows * k] is
+ *   unspecified from there on.  A vertex named twice by one row has both positions.  workspace:
+ *   hg_table_transpose_workspace_bytes(rows, k, n) bytes of device memory (a pure host function; 0 for arguments the
+ *   entry refuses), 4-byte aligned.
+ * hg_table_gather_f32 (a hyperedge's members):  dst[i] = dst_scale[i] * sum_{s = 0 .. k-1} term(i k + s, idx[i, s]),
+ *   i < rows, src [n, F], dst [rows, F].
+ * hg_table_gather_t_f32 (a vertex's hyperedges): dst[v] = dst_scale[v] * sum_{q = ptr_v[v] .. ptr_v[v+1]-1}
+ *   term(pos_v[q], pos_v[q] / k),  v < n, src [rows, F], dst [n, F].
+ *   term(p, j) = (src[j] * src_scale[j]) * w[p]; w [rows * k], src_scale [source rows] and dst_scale [destination rows]
+ *   may each be NULL, and an absent factor is no multiplication.  The accumulator starts at +0.0, every term is rounded
+ *   and added with one rounded add (no fma), dst_scale is applied once at the end.  A vertex with no entry is exactly
+ *   +0.0 whatever its scale.  An entry of idx outside 0 .. n - 1 (of pos_v outside 0 .. rows k - 1) contributes nothing
+ *   and is not read through.
+ *   ORDER: a row of at most HG_TABLE_SEQ_MAX entries -- every row of hg_table_gather_f32 -- is summed in ascending s / q
+ *   into one accumulator per column: a float32 loop reproduces it bit for bit.  A longer vertex row is cut into P
+ *   consecutive pieces of ceil(len / P) entries, each summed in ascending q from +0.0, and the P partial rows are added in
+ *   the tree part[g] += part[g + s], s = P' / 2, P' / 4 .. 1 (P' the power of two at or above P); P = 4 * (64 / L) with
+ *   L = min(ceil(F / c), 64) and c = 4 columns a lane where F % 4 == 0 and src and dst are 16-byte aligned, else 1.  So
+ *   the bits of a row depend on its entries, its length, F and the alignment alone -- not on the launch, the other rows or
+ *   where the row stands.  No floating-point atomics: two calls give the same bits.
+ * Refusals launch nothing, set hg_last_error, in this order: HG_ERR_INVALID for a null idx (ptr_v, pos_v), src or dst,
+ *   for rows, n or F < 1, for k outside 1 .. 64, for rows * k >= 2^31; HG_ERR_UNSUPPORTED for a pointer that is not
+ *   4-byte aligned; HG_ERR_WORKSPACE (the transpose) for a null, small or misaligned workspace. */
+#define HG_TABLE_SEQ_MAX 128
+HG_API int hg_table_seq_max(void); /* HG_TABLE_SEQ_MAX of the library as built */
+HG_API size_t hg_table_transpose_workspace_bytes(int32_t rows, int32_t k, int32_t n);
+HG_API int hg_table_transpose(const int32_t *idx, int32_t rows, int32_t k, int32_t n, int32_t *ptr_v, int32_t *pos_v,
+                              void *workspace, size_t workspace_bytes, hg_stream_t stream);
+HG_API int hg_table_gather_f32(const int32_t *idx, int32_t rows, int32_t k, int32_t n, int32_t F, const float *src,
+                               const float *w, const float *src_scale, const float *dst_scale, float *dst,
+                               hg_stream_t stream);
+HG_API int hg_table_gather_t_f32(const int32_t *ptr_v, const int32_t *pos_v, int32_t rows, int32_t k, int32_t n, int32_t F,
+                                 const float *src, const float *w, const float *src_scale, const float *dst_scale,
+                                 float *dst, hg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
