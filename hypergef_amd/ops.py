@@ -674,8 +674,6 @@ def incidence_aggr(csrptr_t, indices_t, node_feat, v2e_weight=None, e2v_weight=N
     if not (torch.is_grad_enabled() and _any_requires_grad(node_feat, v2e, e2v, degE, degV, W)):
         plan = cached_plan(node_feat.shape[0], csrptr_t, indices_t)
         return plan.aggregate_incidence(csrptr_t, indices_t, node_feat, v2e, e2v, degE, degV, W, heads=heads)
-    if heads == 1:
-        return _IncidenceAggr.apply(csrptr_t, indices_t, node_feat, v2e, e2v, degE, degV, W)
     return _IncidenceAggr.apply(csrptr_t, indices_t, node_feat, v2e, e2v, degE, degV, W, heads)
 
 
@@ -723,52 +721,40 @@ def _segment_args(what, csrptr_t, indices_t, floats, lengths, group, opt, heads=
 
 
 class _IncidenceSoftmax(torch.autograd.Function):
-    """alpha = softmax over each group of leaky_relu(sv[u] + se[e]) and its exact gradients for both score vectors:
-    ds = alpha (dalpha - sum_g alpha dalpha) leaky', dsv / dse = its sums over each vertex's / hyperedge's incidences."""
+    """alpha = softmax over each group of leaky_relu((sv[u] + se[e]) + t[p]) and its exact gradients: the backward kernel's
+    ds = alpha (dalpha - sum_g alpha dalpha) leaky' is the gradient of t, dsv / dse are its sums over each vertex's /
+    hyperedge's incidences.  sv, se and t (the logit per incidence) may each be None.  p_drop > 0: dropout on alpha fused
+    into both kernels -- returns keep ? alpha / (1 - p) : 0, saves the undropped alpha and the two words of rng_state, from
+    which the backward regenerates the mask: the plain backward on dalpha = keep ? dout / (1 - p) : 0."""
 
     @staticmethod
-    def forward(ctx, csrptr_t, indices_t, sv, se, N, group, slope, heads=1):
+    def forward(ctx, csrptr_t, indices_t, sv, se, t, N, group, slope, heads, p_drop, rng_state):
         plan = cached_plan(N, csrptr_t, indices_t)
-        alpha = plan.incidence_attention(csrptr_t, indices_t, sv, se, group, slope, heads=heads)
-        ctx.save_for_backward(csrptr_t, indices_t, sv, se, alpha)
-        ctx.N, ctx.group, ctx.slope, ctx.heads = N, group, slope, heads
-        return alpha
-
-    @staticmethod
-    def backward(ctx, dalpha):
-        csrptr_t, indices_t, sv, se, alpha = ctx.saved_tensors
-        plan = cached_plan(ctx.N, csrptr_t, indices_t)
-        need_sv = sv is not None and ctx.needs_input_grad[2]
-        need_se = se is not None and ctx.needs_input_grad[3]
-        _, dsv, dse = plan.incidence_attention_backward(csrptr_t, indices_t, alpha, dalpha.contiguous(), sv, se, ctx.group,
-                                                        ctx.slope, need_sv=need_sv, need_se=need_se, heads=ctx.heads)
-        return None, None, dsv, dse, None, None, None, None
-
-
-class _IncidenceSoftmaxDropout(torch.autograd.Function):
-    """_IncidenceSoftmax with dropout on alpha fused into both kernels: returns keep ? alpha / (1 - p) : 0, saves the
-    undropped alpha and the two words of rng_state, from which the backward regenerates the mask.  Exact gradients for
-    both score vectors: the plain backward on dalpha = keep ? dout / (1 - p) : 0."""
-
-    @staticmethod
-    def forward(ctx, csrptr_t, indices_t, sv, se, N, group, slope, heads, p_drop, rng_state):
-        plan = cached_plan(N, csrptr_t, indices_t)
-        alpha, alpha_drop = plan.incidence_attention_dropout(csrptr_t, indices_t, sv, se, group, slope, p_drop, rng_state,
-                                                             heads=heads)
-        ctx.save_for_backward(csrptr_t, indices_t, sv, se, alpha, rng_state)
-        ctx.N, ctx.group, ctx.slope, ctx.heads, ctx.p_drop = N, group, slope, heads, p_drop
-        return alpha_drop
+        if p_drop > 0.0:
+            alpha, out = plan.incidence_attention_dropout(csrptr_t, indices_t, sv, se, group, slope, p_drop, rng_state,
+                                                          heads=heads, entry=t)
+        else:
+            alpha = out = plan.incidence_attention(csrptr_t, indices_t, sv, se, group, slope, heads=heads, entry=t)
+        ctx.save_for_backward(csrptr_t, indices_t, sv, se, t, alpha, rng_state)
+        ctx.plan, ctx.group, ctx.slope, ctx.heads, ctx.p_drop = plan, group, slope, heads, p_drop  # the backward runs on this plan
+        return out
 
     @staticmethod
     def backward(ctx, dout):
-        csrptr_t, indices_t, sv, se, alpha, rng_state = ctx.saved_tensors
-        plan = cached_plan(ctx.N, csrptr_t, indices_t)
+        csrptr_t, indices_t, sv, se, t, alpha, rng_state = ctx.saved_tensors
+        plan = ctx.plan
         need_sv = sv is not None and ctx.needs_input_grad[2]
         need_se = se is not None and ctx.needs_input_grad[3]
-        _, dsv, dse = plan.incidence_attention_dropout_backward(
-            csrptr_t, indices_t, alpha, dout.contiguous(), sv, se, ctx.group, ctx.slope, ctx.p_drop, rng_state,
-            need_sv=need_sv, need_se=need_se, heads=ctx.heads)
-        return None, None, dsv, dse, None, None, None, None, None, None
+        if ctx.p_drop > 0.0:
+            ds, dsv, dse = plan.incidence_attention_dropout_backward(
+                csrptr_t, indices_t, alpha, dout.contiguous(), sv, se, ctx.group, ctx.slope, ctx.p_drop, rng_state,
+                need_sv=need_sv, need_se=need_se, heads=ctx.heads, entry=t)
+        else:
+            ds, dsv, dse = plan.incidence_attention_backward(csrptr_t, indices_t, alpha, dout.contiguous(), sv, se, ctx.group,
+                                                             ctx.slope, need_sv=need_sv, need_se=need_se, heads=ctx.heads,
+                                                             entry=t)
+        dt = ds.view_as(t) if ctx.needs_input_grad[4] else None  # never set for t = None
+        return None, None, dsv, dse, dt, None, None, None, None, None, None
 
 
 def _dropout_p(dropout):
@@ -817,86 +803,26 @@ def incidence_softmax(csrptr_t, indices_t, node_score=None, edge_score=None, gro
         raise ValueError("incidence_softmax needs node_score or num_nodes (the number of vertices)")
     N = int(num_nodes) if num_nodes is not None else sv.numel() // heads
     M = csrptr_t.numel() - 1 if isinstance(csrptr_t, torch.Tensor) else 0
-    drop = p_drop > 0.0 and bool(training)
+    if p_drop == 0.0 or not training:  # no dropout: the state is neither looked at nor drawn nor returned
+        p_drop, rng_state = 0.0, None
+    floats, lengths = (("node_score", sv), ("edge_score", se)), (N * heads, M * heads)
     if t is not None:
         nnz = indices_t.numel() if isinstance(indices_t, torch.Tensor) else 0
-        _segment_args("incidence_softmax", csrptr_t, indices_t,
-                      (("node_score", sv), ("edge_score", se), ("incidence_score", t)),
-                      (N * heads, M * heads, nnz * heads), group, opt, heads, rng_state if drop else None)
-        out, rng_state = _softmax_entry(csrptr_t, indices_t, sv, se, t, N, group, float(negative_slope), heads,
-                                        p_drop if drop else 0.0, rng_state)
-        return (out, rng_state if drop else None) if return_rng_state else out
-    _segment_args("incidence_softmax", csrptr_t, indices_t, (("node_score", sv), ("edge_score", se)),
-                  (N * heads, M * heads), group, opt, heads, rng_state if drop else None)
+        floats, lengths = floats + (("incidence_score", t),), lengths + (nnz * heads,)
+    _segment_args("incidence_softmax", csrptr_t, indices_t, floats, lengths, group, opt, heads, rng_state)
     slope = float(negative_slope)
-    if drop:
-        out, rng_state = _softmax_dropout(csrptr_t, indices_t, sv, se, N, group, slope, heads, p_drop, rng_state)
-    elif not (torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (sv, se))):
-        out = cached_plan(N, csrptr_t, indices_t).incidence_attention(csrptr_t, indices_t, sv, se, group, slope, heads=heads)
-    elif heads == 1:
-        out = _IncidenceSoftmax.apply(csrptr_t, indices_t, sv, se, N, group, slope)
-    else:
-        out = _IncidenceSoftmax.apply(csrptr_t, indices_t, sv, se, N, group, slope, heads)
-    return (out, rng_state if drop else None) if return_rng_state else out
-
-
-def _softmax_dropout(csrptr_t, indices_t, sv, se, N, group, slope, heads, p_drop, rng_state):
-    """(dropped coefficients, the state used) of incidence_softmax, its arguments checked."""
-    if rng_state is None:  # on the device: no synchronisation, and a captured draw is drawn again by every replay
+    if p_drop > 0.0 and rng_state is None:  # on the device: no synchronisation, and a captured draw is drawn again by every replay
         info = torch.iinfo(torch.int64)  # randint's upper end is exclusive: every int64 but 2^63 - 1, which a key can spare
         rng_state = torch.randint(info.min, info.max, (2,), dtype=torch.int64, device=csrptr_t.device)
-    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (sv, se)):
-        return _IncidenceSoftmaxDropout.apply(csrptr_t, indices_t, sv, se, N, group, slope, heads, p_drop, rng_state), rng_state
-    plan = cached_plan(N, csrptr_t, indices_t)
-    return plan.incidence_attention_dropout(csrptr_t, indices_t, sv, se, group, slope, p_drop, rng_state, heads=heads)[1], rng_state
-
-
-class _IncidenceSoftmaxEntry(torch.autograd.Function):
-    """_IncidenceSoftmax / _IncidenceSoftmaxDropout (p_drop > 0) with a logit per incidence t added to the score.  The
-    backward kernel's ds = alpha (dalpha - sum_g alpha dalpha) leaky' is the gradient of t; dsv / dse are its sums."""
-
-    @staticmethod
-    def forward(ctx, csrptr_t, indices_t, sv, se, t, N, group, slope, heads, p_drop, rng_state):
-        plan = cached_plan(N, csrptr_t, indices_t)
-        if p_drop > 0.0:
-            alpha, out = plan.incidence_attention_dropout(csrptr_t, indices_t, sv, se, group, slope, p_drop, rng_state,
-                                                          heads=heads, entry=t)
-        else:
-            alpha = out = plan.incidence_attention(csrptr_t, indices_t, sv, se, group, slope, heads=heads, entry=t)
-        ctx.save_for_backward(csrptr_t, indices_t, sv, se, t, alpha, rng_state)
-        ctx.N, ctx.group, ctx.slope, ctx.heads, ctx.p_drop = N, group, slope, heads, p_drop
-        return out
-
-    @staticmethod
-    def backward(ctx, dout):
-        csrptr_t, indices_t, sv, se, t, alpha, rng_state = ctx.saved_tensors
-        plan = cached_plan(ctx.N, csrptr_t, indices_t)
-        need_sv = sv is not None and ctx.needs_input_grad[2]
-        need_se = se is not None and ctx.needs_input_grad[3]
-        if ctx.p_drop > 0.0:
-            ds, dsv, dse = plan.incidence_attention_dropout_backward(
-                csrptr_t, indices_t, alpha, dout.contiguous(), sv, se, ctx.group, ctx.slope, ctx.p_drop, rng_state,
-                need_sv=need_sv, need_se=need_se, heads=ctx.heads, entry=t)
-        else:
-            ds, dsv, dse = plan.incidence_attention_backward(csrptr_t, indices_t, alpha, dout.contiguous(), sv, se, ctx.group,
-                                                             ctx.slope, need_sv=need_sv, need_se=need_se, heads=ctx.heads,
-                                                             entry=t)
-        dt = ds.view_as(t) if ctx.needs_input_grad[4] else None
-        return None, None, dsv, dse, dt, None, None, None, None, None, None
-
-
-def _softmax_entry(csrptr_t, indices_t, sv, se, t, N, group, slope, heads, p_drop, rng_state):
-    """(coefficients, the dropout state used or None) of incidence_softmax with incidence_score, its arguments checked."""
-    if p_drop > 0.0 and rng_state is None:  # drawn as _softmax_dropout draws it
-        info = torch.iinfo(torch.int64)
-        rng_state = torch.randint(info.min, info.max, (2,), dtype=torch.int64, device=csrptr_t.device)
     if torch.is_grad_enabled() and any(x is not None and x.requires_grad for x in (sv, se, t)):
-        return _IncidenceSoftmaxEntry.apply(csrptr_t, indices_t, sv, se, t, N, group, slope, heads, p_drop, rng_state), rng_state
-    plan = cached_plan(N, csrptr_t, indices_t)
-    if p_drop > 0.0:
-        return plan.incidence_attention_dropout(csrptr_t, indices_t, sv, se, group, slope, p_drop, rng_state, heads=heads,
-                                                entry=t)[1], rng_state
-    return plan.incidence_attention(csrptr_t, indices_t, sv, se, group, slope, heads=heads, entry=t), None
+        out = _IncidenceSoftmax.apply(csrptr_t, indices_t, sv, se, t, N, group, slope, heads, p_drop, rng_state)
+    elif p_drop > 0.0:  # nothing to differentiate: the operator itself, without the autograd node
+        out = cached_plan(N, csrptr_t, indices_t).incidence_attention_dropout(csrptr_t, indices_t, sv, se, group, slope, p_drop,
+                                                                             rng_state, heads=heads, entry=t)[1]
+    else:
+        out = cached_plan(N, csrptr_t, indices_t).incidence_attention(csrptr_t, indices_t, sv, se, group, slope, heads=heads,
+                                                                     entry=t)
+    return (out, rng_state) if return_rng_state else out
 
 
 # ---- fused attention aggregation (include/hg_aggr.h, hg_aggr_incidence_attention_heads_f32) -------------------------------
@@ -1316,8 +1242,6 @@ def incidence_sum(csrptr_t, indices_t, val, side="hyperedge", num_nodes=None, he
     N = int(num_nodes) if num_nodes is not None else (int(indices_t.max()) + 1 if nnz else 0)
     if not (torch.is_grad_enabled() and v.requires_grad):
         return cached_plan(N, csrptr_t, indices_t).incidence_sum(csrptr_t, indices_t, v, side, heads=heads)
-    if heads == 1:
-        return _IncidenceSum.apply(csrptr_t, indices_t, v, N, side)
     return _IncidenceSum.apply(csrptr_t, indices_t, v, N, side, heads)
 
 

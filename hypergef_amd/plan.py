@@ -551,11 +551,7 @@ class Plan:
             got = self.gather_rows_incidence(hop, csrptr_t, colind_t, src.float(), w, scaleA, scaleB, heads,
                                              dst if dst.dtype == torch.float32 else None, workspace)
             return got if got is dst else dst.copy_(got)  # copy_ rounds to nearest even, as the kernel's store does
-        nbytes = self.incidence_workspace_bytes(F)
-        if workspace is None:
-            workspace = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=src.device)
-        else:
-            nbytes = workspace.numel() * workspace.element_size()
+        workspace, nbytes = self._incidence_workspace(F, workspace, src.device)
         with torch.cuda.device(src.device):
             if io:
                 _lib.check(_lib.lib().hg_gather_rows_incidence_heads_bf16(
@@ -667,6 +663,14 @@ class Plan:
     def incidence_workspace_bytes(self, F):
         return int(_lib.lib().hg_aggr_incidence_workspace_bytes(self._h, F))
 
+    def _incidence_workspace(self, F, workspace, device):
+        """(workspace, the bytes of it to pass on) of an incidence call at width F: the caller's with its own size, or a new
+        one of incidence_workspace_bytes(F)."""
+        if workspace is not None:
+            return workspace, workspace.numel() * workspace.element_size()
+        nbytes = self.incidence_workspace_bytes(F)
+        return torch.empty(max(nbytes, 256), dtype=torch.uint8, device=device), nbytes
+
     def aggregate_incidence(self, csrptr_t, colind_t, X, v2e=None, e2v=None, degE=None, degV=None, W=None,
                             xe_out=None, out=None, workspace=None, heads=1):
         """Y = degV . H_e2v (degE . W . (H_v2e^T X)) with a weight per incidence (hg_aggr_incidence_f32): v2e / e2v are
@@ -699,11 +703,7 @@ class Plan:
             Y32 = self.aggregate_incidence(csrptr_t, colind_t, X.float(), v2e, e2v, degE, degV, W, xe_out, None, workspace, heads)
             return Y32.to(torch.bfloat16) if out is None else out.copy_(Y32)
         Y = out if out is not None else torch.empty((self.N, F), dtype=X.dtype, device=X.device)
-        nbytes = self.incidence_workspace_bytes(F)
-        if workspace is None:
-            workspace = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=X.device)
-        else:
-            nbytes = workspace.numel() * workspace.element_size()
+        workspace, nbytes = self._incidence_workspace(F, workspace, X.device)
         with torch.cuda.device(X.device):
             if bf16:
                 _lib.check(_lib.lib().hg_aggr_incidence_heads_bf16(
@@ -841,6 +841,71 @@ class Plan:
                     raise ValueError("%s must have %d elements, got %d" % (name, n, t.numel()))
         return device
 
+    def _rng_ptr(self, rng_state, device):
+        _rng_state_dtype(rng_state)
+        _rng_state_length(rng_state)
+        _rng_state_device(rng_state, device)
+        return _ptr(rng_state)
+
+    def _softmax_entry(self, bwd, group, heads, csrptr_t, colind_t, sv, se, entry, slope, p_drop, rng):
+        """(the softmax's C entry for a form, its leading arguments).  The eight entries, named by the four methods below,
+        differ in their argument lists only by entry after se and (p_drop, rng) after slope; the arrays follow."""
+        if entry is not None and self.nnz == 0:
+            entry = None  # nothing to add it to (and an empty tensor has no address to pass)
+        fn = getattr(_lib.lib(), _SOFTMAX_ENTRIES[entry is not None, rng is not None, bwd])
+        head = (self._h, group, heads, _ptr(csrptr_t), _ptr(colind_t), _ptr(sv), _ptr(se))
+        if rng is None:
+            return fn, head + ((float(slope),) if entry is None else (_ptr(entry), float(slope)))
+        return fn, head + ((float(slope), float(p_drop), rng) if entry is None else (_ptr(entry), float(slope), float(p_drop), rng))
+
+    def _softmax(self, csrptr_t, colind_t, sv, se, group, slope, heads, entry=None, p_drop=None, rng_state=None, out=None):
+        """incidence_attention (p_drop None: alpha, written to `out` where one is given) and incidence_attention_dropout
+        ((alpha, alpha_drop)): the checks in their one order, the allocations, the launch."""
+        heads = _heads(heads)
+        group = _side(group)
+        _check_index(csrptr_t, "csrptr_t")
+        _check_index(colind_t, "indices_t")
+        device = self._scores(sv, se, csrptr_t.device, heads, entry)
+        rng = None if p_drop is None else self._rng_ptr(rng_state, device)
+        if out is None:
+            out = torch.empty(_per_head(self.nnz, heads), dtype=torch.float32, device=device)
+        else:
+            _check_feat(out, "out", device=device)
+            if out.numel() != self.nnz * heads:
+                raise ValueError("out must have nnz * heads = %d elements" % (self.nnz * heads))
+        fn, args = self._softmax_entry(False, group, heads, csrptr_t, colind_t, sv, se, entry, slope, p_drop, rng)
+        with torch.cuda.device(device):
+            if rng is None:
+                _lib.check(fn(*args, _ptr(out), _stream_handle(device)))
+                return out
+            alpha_drop = torch.empty_like(out)
+            _lib.check(fn(*args, _ptr(out), _ptr(alpha_drop), _stream_handle(device)))
+        return out, alpha_drop
+
+    def _softmax_backward(self, csrptr_t, colind_t, alpha, grad, grad_name, sv, se, group, slope, need_sv, need_se, heads,
+                          entry=None, p_drop=None, rng_state=None):
+        """incidence_attention_backward (p_drop None) and incidence_attention_dropout_backward: (ds, dsv or None, dse or
+        None).  grad_name: the name under which the incoming gradient is refused, 'dalpha' or 'dout'."""
+        heads = _heads(heads)
+        group = _side(group)
+        _check_index(csrptr_t, "csrptr_t")
+        _check_index(colind_t, "indices_t")
+        _check_feat(alpha, "alpha")
+        _check_feat(grad, grad_name, device=alpha.device)
+        for name, t in (("alpha", alpha), (grad_name, grad)):
+            if t.numel() != self.nnz * heads:
+                raise ValueError("%s must have nnz%s = %d elements, got %d" % (name, " * heads" if heads > 1 else "",
+                                                                              self.nnz * heads, t.numel()))
+        device = self._scores(sv, se, alpha.device, heads, entry)
+        rng = None if p_drop is None else self._rng_ptr(rng_state, device)
+        ds = torch.empty(_per_head(self.nnz, heads), dtype=torch.float32, device=device)
+        dsv = torch.empty(_per_head(self.N, heads), dtype=torch.float32, device=device) if need_sv else None
+        dse = torch.empty(_per_head(self.M, heads), dtype=torch.float32, device=device) if need_se else None
+        fn, args = self._softmax_entry(True, group, heads, csrptr_t, colind_t, sv, se, entry, slope, p_drop, rng)
+        with torch.cuda.device(device):
+            _lib.check(fn(*args, _ptr(alpha), _ptr(grad), _ptr(ds), _ptr(dsv), _ptr(dse), _stream_handle(device)))
+        return ds, dsv, dse
+
     def incidence_attention(self, csrptr_t, colind_t, sv=None, se=None, group="hyperedge", slope=0.2, out=None, heads=1,
                             entry=None):
         """alpha [nnz] in H_T order: the softmax over each hyperedge's members (group 'hyperedge') or each vertex's
@@ -849,32 +914,7 @@ class Plan:
         per head.  The first call of a form builds and uploads what it needs from the plan: not capturable.
         entry: float32 [nnz] / [nnz, H] in H_T order, a logit per incidence added to the score, raw = (sv[u] + se[e]) +
         entry[p] (hg_incidence_attention_entry_heads_f32); None is the call without one."""
-        heads = _heads(heads)
-        group = _side(group)
-        _check_index(csrptr_t, "csrptr_t")
-        _check_index(colind_t, "indices_t")
-        device = self._scores(sv, se, csrptr_t.device, heads, entry)
-        if self.nnz == 0:
-            entry = None  # nothing to add it to (and an empty tensor has no address to pass)
-        if out is None:
-            out = torch.empty(_per_head(self.nnz, heads), dtype=torch.float32, device=device)
-        else:
-            _check_feat(out, "out", device=device)
-            if out.numel() != self.nnz * heads:
-                raise ValueError("out must have nnz * heads = %d elements" % (self.nnz * heads))
-        with torch.cuda.device(device):
-            if entry is not None:
-                _lib.check(_lib.lib().hg_incidence_attention_entry_heads_f32(
-                    self._h, group, heads, _ptr(csrptr_t), _ptr(colind_t), _ptr(sv), _ptr(se), _ptr(entry), float(slope),
-                    _ptr(out), _stream_handle(device)))
-            elif heads == 1:
-                _lib.check(_lib.lib().hg_incidence_attention_f32(self._h, group, _ptr(csrptr_t), _ptr(colind_t), _ptr(sv),
-                                                                 _ptr(se), float(slope), _ptr(out), _stream_handle(device)))
-            else:
-                _lib.check(_lib.lib().hg_incidence_attention_heads_f32(
-                    self._h, group, heads, _ptr(csrptr_t), _ptr(colind_t), _ptr(sv), _ptr(se), float(slope), _ptr(out),
-                    _stream_handle(device)))
-        return out
+        return self._softmax(csrptr_t, colind_t, sv, se, group, slope, heads, entry, out=out)
 
     def incidence_attention_backward(self, csrptr_t, colind_t, alpha, dalpha, sv=None, se=None, group="hyperedge",
                                      slope=0.2, need_sv=True, need_se=True, heads=1, entry=None):
@@ -882,36 +922,8 @@ class Plan:
         (hg_incidence_attention_bwd_f32); sv / se as in the forward (they decide the leaky branch).  heads = H > 1
         (hg_incidence_attention_heads_bwd_f32): every array has a trailing dimension H.  entry: the forward's logit per
         incidence (hg_incidence_attention_entry_heads_bwd_f32); ds is then its gradient."""
-        heads = _heads(heads)
-        group = _side(group)
-        _check_index(csrptr_t, "csrptr_t")
-        _check_index(colind_t, "indices_t")
-        _check_feat(alpha, "alpha")
-        _check_feat(dalpha, "dalpha", device=alpha.device)
-        for name, t in (("alpha", alpha), ("dalpha", dalpha)):
-            if t.numel() != self.nnz * heads:
-                raise ValueError("%s must have nnz%s = %d elements, got %d" % (name, " * heads" if heads > 1 else "",
-                                                                              self.nnz * heads, t.numel()))
-        device = self._scores(sv, se, alpha.device, heads, entry)
-        if self.nnz == 0:
-            entry = None
-        ds = torch.empty(_per_head(self.nnz, heads), dtype=torch.float32, device=device)
-        dsv = torch.empty(_per_head(self.N, heads), dtype=torch.float32, device=device) if need_sv else None
-        dse = torch.empty(_per_head(self.M, heads), dtype=torch.float32, device=device) if need_se else None
-        with torch.cuda.device(device):
-            if entry is not None:
-                _lib.check(_lib.lib().hg_incidence_attention_entry_heads_bwd_f32(
-                    self._h, group, heads, _ptr(csrptr_t), _ptr(colind_t), _ptr(sv), _ptr(se), _ptr(entry), float(slope),
-                    _ptr(alpha), _ptr(dalpha), _ptr(ds), _ptr(dsv), _ptr(dse), _stream_handle(device)))
-            elif heads == 1:
-                _lib.check(_lib.lib().hg_incidence_attention_bwd_f32(
-                    self._h, group, _ptr(csrptr_t), _ptr(colind_t), _ptr(sv), _ptr(se), float(slope), _ptr(alpha),
-                    _ptr(dalpha), _ptr(ds), _ptr(dsv), _ptr(dse), _stream_handle(device)))
-            else:
-                _lib.check(_lib.lib().hg_incidence_attention_heads_bwd_f32(
-                    self._h, group, heads, _ptr(csrptr_t), _ptr(colind_t), _ptr(sv), _ptr(se), float(slope), _ptr(alpha),
-                    _ptr(dalpha), _ptr(ds), _ptr(dsv), _ptr(dse), _stream_handle(device)))
-        return ds, dsv, dse
+        return self._softmax_backward(csrptr_t, colind_t, alpha, dalpha, "dalpha", sv, se, group, slope, need_sv, need_se, heads,
+                                      entry)
 
     def incidence_attention_stats(self, csrptr_t, colind_t, sv=None, se=None, group="hyperedge", slope=0.2, heads=1,
                                   out=None):
@@ -975,11 +987,7 @@ class Plan:
                 if tuple(t.shape) != (rows, F):
                     raise ValueError("%s must be [%d, %d]" % (name, rows, F))
         Y = out if out is not None else torch.empty((self.N, F), dtype=torch.float32, device=X.device)
-        nbytes = self.incidence_workspace_bytes(F)
-        if workspace is None:
-            workspace = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=X.device)
-        else:
-            nbytes = workspace.numel() * workspace.element_size()
+        workspace, nbytes = self._incidence_workspace(F, workspace, X.device)
         with torch.cuda.device(X.device):
             _lib.check(_lib.lib().hg_aggr_incidence_attention_heads_f32(
                 self._h, F, heads, group, _ptr(csrptr_t), _ptr(colind_t), _ptr(X), _ptr(sv), _ptr(se), float(slope),
@@ -1003,23 +1011,13 @@ class Plan:
             if tuple(out.shape) != (ndst, F):
                 raise ValueError("out must be [%d, %d]" % (ndst, F))
         dst = out if out is not None else torch.empty((ndst, F), dtype=torch.float32, device=src.device)
-        nbytes = self.incidence_workspace_bytes(F)
-        if workspace is None:
-            workspace = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=src.device)
-        else:
-            nbytes = workspace.numel() * workspace.element_size()
+        workspace, nbytes = self._incidence_workspace(F, workspace, src.device)
         with torch.cuda.device(src.device):
             _lib.check(_lib.lib().hg_gather_rows_attention_heads_f32(
                 self._h, hop, group, F, heads, _ptr(csrptr_t), _ptr(colind_t), _ptr(src), _ptr(sv), _ptr(se), float(slope),
                 _ptr(seg_max), _ptr(seg_inv), _ptr(scaleA), _ptr(scaleB), _ptr(dst), _ptr(workspace), nbytes,
                 _stream_handle(src.device)))
         return dst
-
-    def _rng_ptr(self, rng_state, device):
-        _rng_state_dtype(rng_state)
-        _rng_state_length(rng_state)
-        _rng_state_device(rng_state, device)
-        return _ptr(rng_state)
 
     def incidence_attention_dropout(self, csrptr_t, colind_t, sv=None, se=None, group="hyperedge", slope=0.2, p_drop=0.5,
                                     rng_state=None, heads=1, entry=None):
@@ -1028,24 +1026,7 @@ class Plan:
         the scores' device, {key, sid} of the Philox mask; the kernel reads it when it runs.  keep depends on (rng_state,
         H_T position, head) alone; no mask is stored.  [nnz], or [nnz, heads].  entry: as in incidence_attention
         (hg_incidence_attention_entry_dropout_heads_f32)."""
-        heads = _heads(heads)
-        group = _side(group)
-        _check_index(csrptr_t, "csrptr_t")
-        _check_index(colind_t, "indices_t")
-        device = self._scores(sv, se, csrptr_t.device, heads, entry)
-        rng = self._rng_ptr(rng_state, device)
-        alpha = torch.empty(_per_head(self.nnz, heads), dtype=torch.float32, device=device)
-        alpha_drop = torch.empty_like(alpha)
-        with torch.cuda.device(device):
-            if entry is not None and self.nnz > 0:
-                _lib.check(_lib.lib().hg_incidence_attention_entry_dropout_heads_f32(
-                    self._h, group, heads, _ptr(csrptr_t), _ptr(colind_t), _ptr(sv), _ptr(se), _ptr(entry), float(slope),
-                    float(p_drop), rng, _ptr(alpha), _ptr(alpha_drop), _stream_handle(device)))
-                return alpha, alpha_drop
-            _lib.check(_lib.lib().hg_incidence_attention_dropout_heads_f32(
-                self._h, group, heads, _ptr(csrptr_t), _ptr(colind_t), _ptr(sv), _ptr(se), float(slope), float(p_drop), rng,
-                _ptr(alpha), _ptr(alpha_drop), _stream_handle(device)))
-        return alpha, alpha_drop
+        return self._softmax(csrptr_t, colind_t, sv, se, group, slope, heads, entry, p_drop, rng_state)
 
     def incidence_attention_dropout_backward(self, csrptr_t, colind_t, alpha, dout, sv=None, se=None, group="hyperedge",
                                              slope=0.2, p_drop=0.5, rng_state=None, need_sv=True, need_se=True, heads=1,
@@ -1053,31 +1034,8 @@ class Plan:
         """(ds, dsv or None, dse or None) for (alpha, alpha_drop) = incidence_attention_dropout(...) and dout, the gradient
         of alpha_drop: incidence_attention_backward on dalpha = keep ? dout / (1 - p_drop) : 0, the mask regenerated from
         rng_state (hg_incidence_attention_dropout_heads_bwd_f32)."""
-        heads = _heads(heads)
-        group = _side(group)
-        _check_index(csrptr_t, "csrptr_t")
-        _check_index(colind_t, "indices_t")
-        _check_feat(alpha, "alpha")
-        _check_feat(dout, "dout", device=alpha.device)
-        for name, t in (("alpha", alpha), ("dout", dout)):
-            if t.numel() != self.nnz * heads:
-                raise ValueError("%s must have nnz%s = %d elements, got %d" % (name, " * heads" if heads > 1 else "",
-                                                                              self.nnz * heads, t.numel()))
-        device = self._scores(sv, se, alpha.device, heads, entry)
-        rng = self._rng_ptr(rng_state, device)
-        ds = torch.empty(_per_head(self.nnz, heads), dtype=torch.float32, device=device)
-        dsv = torch.empty(_per_head(self.N, heads), dtype=torch.float32, device=device) if need_sv else None
-        dse = torch.empty(_per_head(self.M, heads), dtype=torch.float32, device=device) if need_se else None
-        with torch.cuda.device(device):
-            if entry is not None and self.nnz > 0:  # the forward's logit per incidence: ds is its gradient
-                _lib.check(_lib.lib().hg_incidence_attention_entry_dropout_heads_bwd_f32(
-                    self._h, group, heads, _ptr(csrptr_t), _ptr(colind_t), _ptr(sv), _ptr(se), _ptr(entry), float(slope),
-                    float(p_drop), rng, _ptr(alpha), _ptr(dout), _ptr(ds), _ptr(dsv), _ptr(dse), _stream_handle(device)))
-                return ds, dsv, dse
-            _lib.check(_lib.lib().hg_incidence_attention_dropout_heads_bwd_f32(
-                self._h, group, heads, _ptr(csrptr_t), _ptr(colind_t), _ptr(sv), _ptr(se), float(slope), float(p_drop), rng,
-                _ptr(alpha), _ptr(dout), _ptr(ds), _ptr(dsv), _ptr(dse), _stream_handle(device)))
-        return ds, dsv, dse
+        return self._softmax_backward(csrptr_t, colind_t, alpha, dout, "dout", sv, se, group, slope, need_sv, need_se, heads,
+                                      entry, p_drop, rng_state)
 
     def incidence_sum(self, csrptr_t, colind_t, val, side="hyperedge", out=None, heads=1):
         """out[e] = sum of val over hyperedge e's incidences (side 'hyperedge', [M]) or out[v] = sum over vertex v's
@@ -1099,12 +1057,8 @@ class Plan:
             if out.numel() != n * heads:
                 raise ValueError("out must have %d elements" % (n * heads))
         with torch.cuda.device(val.device):
-            if heads == 1:
-                _lib.check(_lib.lib().hg_incidence_sum_f32(self._h, side, _ptr(csrptr_t), _ptr(colind_t), _ptr(val),
-                                                           _ptr(out), _stream_handle(val.device)))
-            else:
-                _lib.check(_lib.lib().hg_incidence_sum_heads_f32(self._h, side, heads, _ptr(csrptr_t), _ptr(colind_t),
-                                                                 _ptr(val), _ptr(out), _stream_handle(val.device)))
+            _lib.check(_lib.lib().hg_incidence_sum_heads_f32(self._h, side, heads, _ptr(csrptr_t), _ptr(colind_t), _ptr(val),
+                                                             _ptr(out), _stream_handle(val.device)))
         return out
 
     def segment_ids(self, csrptr_t, colind_t, side):
@@ -1124,6 +1078,9 @@ class Plan:
 
 
 SIDES = {"hyperedge": 0, "vertex": 1}
+# (entry logit, dropout, backward) -> hg_incidence_attention_[entry_][dropout_]heads_[bwd_]f32
+_SOFTMAX_ENTRIES = {(e, d, b): "hg_incidence_attention_%s%sheads_%sf32" % ("entry_" * e, "dropout_" * d, "bwd_" * b)
+                    for e in (False, True) for d in (False, True) for b in (False, True)}
 
 
 def _side(side):

@@ -51,6 +51,20 @@ def test_exports(hg):
         assert "entry" in inspect.signature(getattr(Plan, m)).parameters, m
 
 
+def test_every_softmax_form_has_its_exported_entry(hg):
+    """The Plan picks the C entry of a form from a table of names: all eight exist, with their argument types declared."""
+    from hypergef_amd import _lib, plan
+    L = _lib.lib()
+    names = plan._SOFTMAX_ENTRIES
+    assert sorted(names) == [(e, d, b) for e in (False, True) for d in (False, True) for b in (False, True)]
+    assert len(set(names.values())) == 8
+    for (entry, dropout, bwd), name in names.items():
+        assert name in _lib.SYMBOLS and getattr(L, name).argtypes is not None, name
+        assert ("_entry_" in name, "_dropout_" in name, "_bwd_" in name) == (entry, dropout, bwd), name
+        # plan, group, heads, the CSR pair, sv, se [, entry], slope [, p_drop, rng], the arrays (1 / 2 forward, 5 backward), stream
+        assert len(getattr(L, name).argtypes) == 7 + entry + 1 + 2 * dropout + (5 if bwd else 1 + dropout) + 1, name
+
+
 def test_c_entries_refuse_on_a_host_only_plan(hg):
     from hypergef_amd import _lib
     from hypergef_amd.plan import Plan, make_opts
