@@ -30,4 +30,33 @@ KnnLayout knn_layout(int64_t nq, int64_t n, int k, int slices);
 // else 1.  Never more than 2: hg_knn_workspace_bytes(.., cand_slices = 0) promises 16 nq k + 4096 bytes at the most.
 int knn_auto_slices(int64_t nq, int64_t n);
 
+// The dot-form prefilter (hg_knn_dot.hip, hg_knn_dot_f32): a workgroup of kDotBlock threads owns kDotTQ query rows, one wave
+// 32 of them, and walks its candidate rows kDotTC at a time on v_mfma_f32_32x32x2_f32; both are staged through LDS kDotFC
+// columns at a time, row-major with a row pitch of kDotLd floats.  A query row's shortlist lives in the 32 lanes of the
+// half wave that holds the row's accumulators: lane t holds slots t, t + 32 and t + 64.
+constexpr int kDotBlock = 256;
+constexpr int kDotTQ = 128;
+constexpr int kDotTC = 128;
+constexpr int kDotFC = 32;
+constexpr int kDotLd = 33;          // odd: the 32 rows and the two columns of an operand read land in 64 different banks
+constexpr int kDotNormRows = 64;    // rows per workgroup of the norm kernel (one block maximum each)
+constexpr int kDotMaxF = 65536;     // the error bound's derivation assumes (F + 1) 2^-24 <= 2^-8 + 2^-24
+constexpr int kDotRerankRows = 64;  // the rerank kernel's batch: one candidate row per lane
+
+// Shortlist slots per lane for k: the shortlist holds 32 * knn_dot_slots(k) entries, at least k + 16 (slack 16 .. 47).
+inline int knn_dot_slots(int k) { return (k + 16 + 31) / 32; }
+
+// Where the pieces of hg_knn_dot_f32's workspace start (bytes); kp = min(n, 32 * knn_dot_slots(k)) shortlist entries:
+//   [n2x, float n][n2q, float nq][block maxima of n2x, float ceil(n / 64)][n2max, one float]
+//   [shortlist idx, slices x nq x kp int32][shortlist estimates, the same in float][partial means, slices x nq]
+struct KnnDotLayout {
+  size_t n2x, n2q, bmax, n2max, idx, est, mean, total;
+  int kp;
+};
+KnnDotLayout knn_dot_layout(int64_t nq, int64_t n, int k, int slices);
+
+// cand_slices = 0: as many slices as fill about two workgroups per compute unit, at most one per candidate tile.
+// Every other value is clipped to the number of candidate tiles (a slice without a tile has nothing to list).
+int knn_dot_slices(int64_t nq, int64_t n, int cand_slices);
+
 }  // namespace hg

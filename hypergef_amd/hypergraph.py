@@ -51,17 +51,18 @@ class HyperGraph:
         return self
 
     @classmethod
-    def from_knn(cls, X, k, device, segments=None, data_name="knn", ngs=None):
+    def from_knn(cls, X, k, device, segments=None, data_name="knn", ngs=None, form="difference"):
         """The hypergraph whose hyperedge i holds vertex i and its k - 1 nearest neighbours among the rows of X [N, F]
         (float32; HGNN's construction for ModelNet40 / NTU2012, which come without an incidence): ops.knn with
         self_first on `device`, then M = N, H_T_csrptr = arange(0, N k + 1, k), H_T_colind = idx flattened.  segments:
         ops.knn's -- many point sets in one tensor, neighbours within a set.  The neighbour table is read back once (the
-        plan is built on the host).  Keeps knn_dist [N, k] (squared), knn_mean [N] and knn_weights()."""
+        plan is built on the host).  Keeps knn_dist [N, k] (squared), knn_mean [N] and knn_weights().  form: ops.knn's -- "dot"
+        builds the same hypergraph and knn_dist through the matrix-unit prefilter; knn_mean is then the dot form's."""
         from . import knn_graph as _knn
         Xd = torch.as_tensor(X).detach()
         if Xd.dtype == torch.float32:  # anything else is ops.knn's refusal
             Xd = Xd.to(device).contiguous()
-        idx, dist, mean = _knn.knn(Xd, k, segments=segments, self_first=True, return_mean=True)
+        idx, dist, mean = _knn.knn(Xd, k, segments=segments, self_first=True, return_mean=True, form=form)
         self = cls.__new__(cls)
         self._init(_knn.incidence_from_knn(idx.cpu().numpy(), data_name), device, data_name, ngs)
         self.k, self.knn_dist, self.knn_mean = int(k), dist, mean

@@ -20,6 +20,8 @@ from .synth import Incidence
 
 K_MAX = 64        # include/hg_aggr.h: k in 1 .. 64
 SLICES_MAX = 32   # cand_slices in 0 .. 32
+FORMS = ("difference", "dot")
+DOT_F_MAX = 65536  # form="dot": the widest rows the error bound is derived for (hg_knn.h, kDotMaxF)
 
 
 def _segment_offsets(segments, n, k):
@@ -38,7 +40,8 @@ def _segment_offsets(segments, n, k):
     return seg.astype(np.int32)
 
 
-def knn(X, k, queries=None, segments=None, self_first=None, return_mean=False, cand_slices=0):
+def knn(X, k, queries=None, segments=None, self_first=None, return_mean=False, cand_slices=0, form="difference",
+        return_fallback=False):
     """The k nearest rows of X [n, F] for every row of `queries` [nq, F] (None: for every row of X itself), by the squared
     Euclidean distance d2(i, j) = sum_c (Q[i, c] - X[j, c])^2 in float32 -- the difference form, so identical rows are at
     exactly 0 and integer-valued rows give exact distances.  Returns (idx int32 [nq, k], dist float32 [nq, k]) and, with
@@ -54,10 +57,22 @@ def knn(X, k, queries=None, segments=None, self_first=None, return_mean=False, c
     the call then waits for the stream once.  cand_slices: 0 (1 or 2, picked from nq and n) or 1 .. 32 slices of the
     candidates per query tile, merged by a second kernel; more slices fill the device when nq is small.
 
+    form: "difference" (the default) is the search above.  "dot" (hg_knn_dot_f32, for wide rows) returns the same idx and
+    dist, bit for bit, for the same arguments: the dot form |q|^2 + |x|^2 - 2 q.x on the f32 matrix unit only shortlists
+    32 ceil((k + 16) / 32) candidates per row, the difference form ranks them, an error bound certifies row by row that
+    nothing outside the shortlist could have entered the top k, and a row that is not certified is searched exhaustively
+    in the difference form (include/hg_aggr.h has the bound).  dist never holds a dot-form estimate.  Under "dot" the
+    mean is another number: mean[i] = the float32 mean over all candidates of sqrt(max(d~(i, j), 0)) with d~ the dot-form
+    estimate and the self pair exactly 0 when queries is None -- within mean_j sqrt(E1(i)) + the float32 summation error
+    of the float64 mean, E1 = hg_aggr.h's bound on |d~ - d2|; one bit pattern per (form, cand_slices).  "dot" takes no
+    segments and rows of at most 65536 columns, and neither waits nor reads back.  return_fallback: one more result,
+    int32 [nq], 1 where the row was not certified and took the exhaustive path, else 0 (all 0 under "difference").
+
     Not differentiable: raises if X (or queries) requires a gradient while grad mode is on; call it under
     torch.no_grad() or on X.detach().  Refusals, in this order and before a device is touched: TypeError for anything
-    but float32; ValueError for k outside 1 .. min(64, n), for segments or self_first together with queries, for a segment
-    shorter than k; RuntimeError for CPU tensors."""
+    but float32; ValueError for an unknown form, for k outside 1 .. min(64, n), for segments or self_first together with
+    queries, for form="dot" with segments or with F above 65536, for a segment shorter than k; RuntimeError for CPU
+    tensors."""
     for name, t in (("X", X), ("queries", queries)):
         if t is None and name == "queries":
             continue
@@ -67,6 +82,8 @@ def knn(X, k, queries=None, segments=None, self_first=None, return_mean=False, c
     if X.dim() != 2 or X.shape[1] < 1:
         raise ValueError("X must be [n, F] with F >= 1, got %s" % (tuple(X.shape),))
     n, F = X.shape
+    if form not in FORMS:
+        raise ValueError("form must be one of %s, got %r" % (", ".join(repr(f) for f in FORMS), form))
     if not isinstance(k, numbers.Integral) or isinstance(k, bool) or not 1 <= k <= K_MAX:
         raise ValueError("k must be an integer in 1 .. %d, got %r" % (K_MAX, k))
     if k > n:
@@ -78,6 +95,13 @@ def knn(X, k, queries=None, segments=None, self_first=None, return_mean=False, c
             raise ValueError("self_first cannot be combined with queries (a query row is no candidate)")
         if queries.dim() != 2 or queries.shape[1] != F or queries.shape[0] < 1:
             raise ValueError("queries must be [nq >= 1, F = %d], got %s" % (F, tuple(queries.shape)))
+    if form == "dot":
+        if segments is not None:
+            raise ValueError('form="dot" cannot be combined with segments (batches of point sets have narrow rows: use '
+                             'form="difference")')
+        if F > DOT_F_MAX:
+            raise ValueError('form="dot" takes rows of at most %d columns (the width its error bound is derived for), got '
+                             "F = %d" % (DOT_F_MAX, F))
     seg = None if segments is None else _segment_offsets(segments, n, k)
     if not isinstance(cand_slices, numbers.Integral) or isinstance(cand_slices, bool) or not 0 <= cand_slices <= SLICES_MAX:
         raise ValueError("cand_slices must be 0 (auto) or 1 .. %d, got %r" % (SLICES_MAX, cand_slices))
@@ -95,14 +119,24 @@ def knn(X, k, queries=None, segments=None, self_first=None, return_mean=False, c
     idx = torch.empty((nq, k), dtype=torch.int32, device=dev)
     dist = torch.empty((nq, k), dtype=torch.float32, device=dev)
     mean = torch.empty(nq, dtype=torch.float32, device=dev) if return_mean else None
-    ws_bytes = L.hg_knn_workspace_bytes(nq, n, F, k, cand_slices)
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev) if ws_bytes else None
-    seg_ptr = None if seg is None else seg.ctypes.data_as(ctypes.c_void_p)
-    with torch.cuda.device(dev):
-        _lib.check(L.hg_knn_f32(_ptr(Q), nq, _ptr(X), n, F, k, seg_ptr, 0 if seg is None else seg.shape[0] - 1,
-                                1 if self_first else 0, cand_slices, _ptr(idx), _ptr(dist), _ptr(mean), _ptr(ws), ws_bytes,
-                                _stream_handle(dev)))
-    return (idx, dist, mean) if return_mean else (idx, dist)
+    if form == "dot":
+        fallback = torch.empty(nq, dtype=torch.int32, device=dev) if return_fallback else None
+        ws_bytes = L.hg_knn_dot_workspace_bytes(nq, n, F, k, cand_slices)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        with torch.cuda.device(dev):
+            _lib.check(L.hg_knn_dot_f32(_ptr(Q), nq, _ptr(X), n, F, k, 1 if self_first else 0, cand_slices, _ptr(idx),
+                                        _ptr(dist), _ptr(mean), _ptr(fallback), _ptr(ws), ws_bytes, _stream_handle(dev)))
+    else:
+        ws_bytes = L.hg_knn_workspace_bytes(nq, n, F, k, cand_slices)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev) if ws_bytes else None
+        seg_ptr = None if seg is None else seg.ctypes.data_as(ctypes.c_void_p)
+        with torch.cuda.device(dev):
+            _lib.check(L.hg_knn_f32(_ptr(Q), nq, _ptr(X), n, F, k, seg_ptr, 0 if seg is None else seg.shape[0] - 1,
+                                    1 if self_first else 0, cand_slices, _ptr(idx), _ptr(dist), _ptr(mean), _ptr(ws), ws_bytes,
+                                    _stream_handle(dev)))
+        fallback = torch.zeros(nq, dtype=torch.int32, device=dev) if return_fallback else None
+    out = (idx, dist) + ((mean,) if return_mean else ()) + ((fallback,) if return_fallback else ())
+    return out
 
 
 def knn_incidence_weights(dist, mean, m_prob=1.0):
@@ -328,14 +362,15 @@ class KnnHypergraph:
       ptr_v [N + 1], pos_v [N k]: ops.knn_transpose(idx)
       degE [N, 1] = 1 / k and degV [N, 1] = in-degree^-1/2, 1 where no hyperedge names the vertex (HyperGraph's formulas)
       weights(m_prob): HGNN's exp(-d2 / (m_prob mean)^2) entries [N k]
-      aggregate(Z, probabilistic=False, m_prob=1.0): ops.knn_aggr over the table."""
+      aggregate(Z, probabilistic=False, m_prob=1.0): ops.knn_aggr over the table.
+    form: ops.knn's -- "dot" gives the same idx and dist through the matrix-unit prefilter, and its own mean."""
 
     @classmethod
-    def build(cls, X, k, segments=None):
+    def build(cls, X, k, segments=None, form="difference"):
         self = cls.__new__(cls)
         if isinstance(X, torch.Tensor):  # anything else is ops.knn's refusal
             X = X.detach().contiguous()
-        self.idx, self.dist, self.mean = knn(X, k, segments=segments, self_first=True, return_mean=True)
+        self.idx, self.dist, self.mean = knn(X, k, segments=segments, self_first=True, return_mean=True, form=form)
         N = self.idx.shape[0]
         self.k, self.num_nodes, self.num_edges, self.nnz = int(k), N, N, N * int(k)
         self.device = self.idx.device

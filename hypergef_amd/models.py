@@ -147,10 +147,11 @@ class DynamicHypergraphConv(nn.Module):
     another order.  With segments=None a forward and backward then waits for the device nowhere and allocates only through
     torch, so the layer can be recorded into a hipGraph (torch.cuda.graph) and the neighbours are searched again on every
     replay.  With segments, ops.knn still waits once for its offsets: such a layer runs eagerly only.  False (the default)
-    is the layer above, untouched."""
+    is the layer above, untouched.  knn_form: ops.knn's `form` -- "dot" searches the same neighbours through the
+    matrix-unit prefilter (no segments); with probabilistic=True the weights then use the dot form's mean."""
 
     def __init__(self, in_channels, out_channels, k, probabilistic=False, segments=None, m_prob=1.0, options=None,
-                 device_graph=False):
+                 device_graph=False, knn_form="difference"):
         super().__init__()
         if not isinstance(k, int) or not 1 <= k <= 64:
             raise ValueError("k must be an integer in 1 .. 64, got %r" % (k,))
@@ -159,15 +160,16 @@ class DynamicHypergraphConv(nn.Module):
         self.in_channels, self.out_channels, self.k = in_channels, out_channels, k
         self.probabilistic, self.segments, self.m_prob = probabilistic, segments, m_prob
         self.device_graph = bool(device_graph)
+        self.knn_form = knn_form
         self.hyperg = None
 
     def forward(self, X):
         if self.device_graph:
             from .knn_graph import KnnHypergraph
-            hyperg = self.hyperg = KnnHypergraph.build(X, self.k, segments=self.segments)
+            hyperg = self.hyperg = KnnHypergraph.build(X, self.k, segments=self.segments, form=self.knn_form)
             return hyperg.aggregate(self.lin(X), probabilistic=self.probabilistic, m_prob=self.m_prob)
         from .hypergraph import HyperGraph
-        hyperg = self.hyperg = HyperGraph.from_knn(X.detach(), self.k, X.device, segments=self.segments)
+        hyperg = self.hyperg = HyperGraph.from_knn(X.detach(), self.k, X.device, segments=self.segments, form=self.knn_form)
         Z = self.lin(X)
         Wdiag = torch.ones(hyperg.num_edges, device=X.device)
         if self.probabilistic:

@@ -852,6 +852,37 @@ HG_API int hg_knn_f32(const float *Q, int32_t nq, const float *X, int32_t n, int
                       void *workspace, size_t workspace_bytes, hg_stream_t stream);
 HG_API size_t hg_knn_workspace_bytes(int32_t nq, int32_t n, int32_t F, int32_t k, int32_t cand_slices);
 
+/* hg_knn_f32's search with a dot-form prefilter on the f32 matrix unit (csrc/hg_knn_dot.hip), for wide rows.  idx and dist
+ * are hg_knn_f32's for the same arguments, BIT FOR BIT, on every input: dist holds the difference-form float32 values and
+ * the order is the same total order (d2, j).  The dot form never decides the result:
+ *   n2[j] = sum_c X[j, c]^2 (float32, one fma per column, c ascending), s~(i, j) = sum_c Q[i, c] X[j, c] on
+ *   v_mfma_f32_32x32x2_f32 (an fma chain in ascending c: the same bits in every tiling), d~ = (n2q[i] + n2[j]) - 2 s~;
+ *   every row shortlists its kp = min(n, 32 ceil((k + 16) / 32)) smallest candidates under (d~, j) -- with self_first row i
+ *   itself always -- and the shortlist's d2 is computed and ranked exactly as hg_knn_f32 does;
+ *   with T the largest shortlisted d~, u = 2^-24, C = (2 F + 4)(1 + 1/64) rounded up to an integer, and
+ *     E1 = C u (n2q[i] + max_j n2[j]) + (F + 2) 2^-146,   Ei = E1 + (F + 4) u max(T, 0),
+ *   every candidate outside the shortlist has d2 >= T - Ei (|d~ - d2_exact| <= E1, and d2 >= d2_exact (1 - (F + 2) u)).  The row
+ *   is certified iff its k-th d2 is strictly below T - Ei, or nothing was left out (n <= kp); a row that is not certified
+ *   is searched over all n candidates in the difference form by the same launch, and fallback[i] (nullable, int32 [nq])
+ *   is 1 for such a row and 0 for a certified one.
+ * There is no seg: rows of point-set batches are narrow.  F is at most 65536 (the bound's derivation: HG_ERR_INVALID).
+ * mean_dist != NULL: mean_dist[i] = the float32 mean over all n candidates of sqrt(max(d~(i, j), 0)) (the hardware's square
+ * root), the pair (i, i) counting as exactly 0 when Q == X: within mean_j sqrt(E1) and the float32 summation error of the
+ * exact mean; one bit pattern per cand_slices.  It is NOT hg_knn_f32's mean_dist bit for bit.
+ * cand_slices: as hg_knn_f32's, clipped to the number of 128-row candidate tiles; 0 picks about 512 workgroups.  idx and dist
+ * do not depend on it, and neither does fallback: the slices' shortlists are merged before T is taken.
+ * workspace: hg_knn_dot_workspace_bytes(nq, n, F, k, cand_slices) bytes of device memory, always needed:
+ * 4 (n + nq + n / 64) + slices nq (8 kp + 4) + 2048 at the most, kp <= 96 -- O(nq (k + shortlist) + nq + n), nothing of
+ * nq x n.  It returns 0 for arguments hg_knn_dot_f32 refuses.
+ * Nothing is allocated, copied to or from the host or waited for: five launches on `stream` (four when Q == X), recordable
+ * into a hipGraph.  Refusals as hg_knn_f32's, in its order, with F > 65536 after F < 1: HG_ERR_INVALID for the arguments,
+ * then HG_ERR_UNSUPPORTED for cand_slices > 32 or a misaligned pointer, then HG_ERR_WORKSPACE.  NaN inputs: unspecified;
+ * norms that overflow are handled (such rows take the exhaustive path). */
+HG_API int hg_knn_dot_f32(const float *Q, int32_t nq, const float *X, int32_t n, int32_t F, int32_t k, int32_t self_first,
+                          int32_t cand_slices, int32_t *idx, float *dist, float *mean_dist, int32_t *fallback,
+                          void *workspace, size_t workspace_bytes, hg_stream_t stream);
+HG_API size_t hg_knn_dot_workspace_bytes(int32_t nq, int32_t n, int32_t F, int32_t k, int32_t cand_slices);
+
 /* Aggregation over a dense neighbour table, with no plan (csrc/hg_table.hip).  idx [rows, k] int32 is what hg_knn_f32
  * writes: hyperedge i has the k members idx[i, 0 .. k - 1], so H_T is the table itself (csrptr_t an arange) and position
  * p = i k + s of the table is entry s of hyperedge i.  1 <= k <= 64 and rows * k < 2^31.  None of the three entries
