@@ -1,9 +1,17 @@
 """numpy references for the neighbour-table operators (include/hg_aggr.h, hg_table_*): test infrastructure, numpy only.
 
 transpose: the stable argsort of the valid positions by vertex.  gather / gather_t: float32 loops in the contract's order
-for rows one lane group sums (every row of gather; rows of gather_t up to HG_TABLE_SEQ_MAX entries).  aggr / aggr_grad:
-the whole operator Y = degV . H_w (degE . (H_w^T X)) and its X-gradient in float64."""
+for rows one lane group sums (every row of gather; rows of gather_t up to HG_TABLE_SEQ_MAX entries).  gather_t_ordered:
+gather_t with the longer rows in the pieces and the tree of the header's ORDER paragraph, written from that paragraph
+alone, so float32 and bit for bit on every row; hub_table builds the tables that put such rows in every place of a
+workgroup.  aggr / aggr_grad: the whole operator Y = degV . H_w (degE . (H_w^T X)) and its X-gradient in float64."""
 import numpy as np
+
+# (F, src and dst on 16-byte boundaries, P): the widths at which the long-row path takes another shape -- 64 lane groups a
+# wave (F = 1; F = 4 aligned), P below its power of two (F = 3, 5, 12), the scalar columns of a width divisible by 4 on rows
+# off a 16-byte boundary, and more than one column pass (F = 130; F = 260 aligned).  P is the header's 4 * (64 / L).
+LONG_ROW_WIDTHS = ((1, True, 256), (3, True, 84), (4, True, 256), (4, False, 64), (5, True, 48), (12, True, 84),
+                   (130, True, 4), (260, True, 4))
 
 
 def transpose(idx, n=None):
@@ -75,6 +83,117 @@ def gather_t(ptr_v, pos_v, k, src, w=None, src_scale=None, dst_scale=None):
                 acc = (np.float32(dst_scale[v]) * acc).astype(np.float32)
             out[v] = acc
     return out
+
+
+def long_row_shape(F, aligned16=True):
+    """(c, L, R, P, P') of the header's ORDER paragraph: c columns a lane, L lanes a row, R = 64 // L rows a wave, P = 4 R
+    pieces of a long row, P' the power of two at or above P."""
+    c = 4 if F % 4 == 0 and aligned16 else 1
+    L = min(-(-F // c), 64)
+    R = 64 // L
+    P = 4 * R
+    P2 = 1
+    while P2 < P:
+        P2 *= 2
+    return c, L, R, P, P2
+
+
+def long_row_sum(terms, live, P, first_stride=None):
+    """The sum of one long row in the header's order, float32 [F].  terms [len, F] float32 are the row's rounded terms in
+    ascending q and live [len] says which entries count: the row is cut into P consecutive pieces of ceil(len / P) entries
+    (the last ones may be short or empty), each summed in ascending q from +0.0 with one rounded add a term, and the P
+    partial rows are added in the tree part[g] += part[g + s], s = P' / 2, P' / 4 .. 1, for g < s and g + s < P.
+    first_stride: where the tree starts, P' / 2 unless a test wants to see that another tree gives other bits."""
+    length, F = terms.shape
+    chunk = -(-length // P)
+    part = np.zeros((P, F), np.float32)
+    for g in range(P):
+        for q in range(min(g * chunk, length), min((g + 1) * chunk, length)):
+            if live[q]:
+                part[g] = (part[g] + terms[q]).astype(np.float32)
+    P2 = 1
+    while P2 < P:
+        P2 *= 2
+    s = P2 // 2 if first_stride is None else first_stride
+    while s >= 1:
+        for g in range(max(0, min(s, P - s))):  # g < s and g + s < P; a stride reads no row it writes
+            part[g] = (part[g] + part[g + s]).astype(np.float32)
+        s //= 2
+    return part[0]
+
+
+def gather_t_ordered(ptr_v, pos_v, k, src, w=None, src_scale=None, dst_scale=None, aligned16=True, seq_max=128):
+    """gather_t with every row in the order include/hg_aggr.h documents, float32 [n, F]: a row of at most seq_max entries
+    as gather_t sums it, a longer one as long_row_sum does with P = long_row_shape(F, aligned16)[3]; dst_scale once at the
+    end.  aligned16: whether src and dst stand on 16-byte boundaries on the device (it picks c, and so P).
+    An entry of pos_v outside 0 .. rows k - 1 is ignored the way the kernel ignores it: it keeps its place -- it counts in the
+    row's length, which decides between the two orders and sets the pieces' size, and it occupies its slot of its piece --
+    and adds nothing.  A row that holds only such entries is not empty: dst_scale is applied to its +0.0."""
+    src = np.asarray(src, np.float32)
+    rows, F = src.shape
+    n = len(ptr_v) - 1
+    P = long_row_shape(F, aligned16)[3]
+    pos = np.asarray(pos_v).astype(np.int64)
+    live_all = (pos >= 0) & (pos < rows * k)
+    out = np.zeros((n, F), np.float32)
+    with np.errstate(invalid="ignore", over="ignore"):
+        for v in range(n):
+            beg, end = int(ptr_v[v]), int(ptr_v[v + 1])
+            live = live_all[beg:end]
+            terms = np.zeros((end - beg, F), np.float32)
+            for q in np.flatnonzero(live):
+                p = int(pos[beg + q])
+                terms[q] = _term(src, p // k, p, w, src_scale)
+            if end - beg > seq_max:
+                acc = long_row_sum(terms, live, P)
+            else:
+                acc = np.zeros(F, np.float32)
+                for q in np.flatnonzero(live):
+                    acc = (acc + terms[q]).astype(np.float32)
+            if dst_scale is not None and end > beg:
+                acc = (np.float32(dst_scale[v]) * acc).astype(np.float32)
+            out[v] = acc
+    return out
+
+
+def hub_table(F, aligned16=True, seq_max=128, seed=0, lengths=None):
+    """A table [rows, 2] over n vertices whose vertex rows reach every place of the long-row path at width F.  Slot 0 of
+    every row names a hub, slot 1 a vertex that is no hub.  With R rows a wave (long_row_shape), n = max(8 R + 3, 43) is no
+    multiple of the 4 R rows of a workgroup, and the hubs are the vertices {0, 1, R, 4 R - 1, 4 R, n - 1}: two lane groups
+    of one wave, the next wave, the last row of workgroup 0, the first of workgroup 1, the last vertex of a partial tile.
+    Their lengths cycle through `lengths` (seq_max + 1, seq_max + 2, 4 seq_max + 3, 1000).  Of the other vertices the first
+    has exactly seq_max entries, the second none, the rest share what is left in turn (short rows); the rows are shuffled.
+    Returns a dict: idx, n, hubs, lens, full, empty, and R, P of the width."""
+    _, _, R, P, _ = long_row_shape(F, aligned16)
+    rng = np.random.default_rng(seed)
+    n = max(8 * R + 3, 43)
+    assert n % (4 * R)
+    hubs = sorted({0, 1, R, 4 * R - 1, 4 * R, n - 1})
+    if lengths is None:
+        lengths = (seq_max + 1, seq_max + 2, 4 * seq_max + 3, max(1000, 4 * seq_max + 7))
+    lens = [lengths[i % len(lengths)] for i in range(len(hubs))]
+    others = [v for v in range(n) if v not in hubs]
+    full, empty, rest = others[0], others[1], others[2:]
+    rows = sum(lens)
+    slot0 = np.repeat(hubs, lens)
+    slot1 = np.concatenate([np.full(seq_max, full), np.asarray(rest)[np.arange(rows - seq_max) % len(rest)]])
+    assert -(-(rows - seq_max) // len(rest)) <= seq_max
+    idx = np.stack([rng.permutation(slot0), rng.permutation(slot1)], axis=1).astype(np.int32)
+    return dict(idx=idx, n=n, hubs=hubs, lens=lens, full=full, empty=empty, R=R, P=P)
+
+
+def hub_operator_case(F, seq_max=128, seed=70):
+    """hub_table(F) with what ops.knn_aggr takes: randn X and output gradient G [n, F], weights in [0.5, 1.5), degE = 1 / k
+    and degV = in-degree^-1/2 (1 for a vertex with no entry), the scales of the kNN hypergraph."""
+    t = hub_table(F, True, seq_max, seed)
+    rng = np.random.default_rng(seed + F)
+    idx, n = t["idx"], t["n"]
+    rows, k = idx.shape
+    deg = np.bincount(idx.reshape(-1), minlength=n).astype(np.float64)
+    t.update(X=rng.standard_normal((n, F)).astype(np.float32), G=rng.standard_normal((n, F)).astype(np.float32),
+             w=(rng.random(rows * k) + 0.5).astype(np.float32), degE=np.full(rows, 1.0 / k, np.float32),
+             degV=np.where(deg > 0, np.maximum(deg, 1) ** -0.5, 1.0).astype(np.float32))
+    return t
 
 
 def _dense64(idx, n, w):

@@ -1,7 +1,8 @@
 """ops.knn(form="dot") on the device: idx and dist are form="difference"'s, bit for bit, on every input -- through the
 shortlist and the certificate where the row is certified, through the exhaustive path where it is not (return_fallback says
 which; tests/_knn_dot_ref.py says from the inputs alone which it must be).  The prefilter's tile is 128 query rows by 128
-candidates, 32 columns per LDS chunk, two columns per MFMA; the rerank stages 64 rows by 64 columns."""
+candidates, 32 columns per LDS chunk, two columns per MFMA; the rerank stages 64 rows by 64 columns.  Also: 32 slices over
+33 candidate tiles (the workspace size says that 32 were taken), and norms that overflow or pass the bound's 1e37."""
 import os
 import sys
 
@@ -108,6 +109,83 @@ def test_cand_slices(hg, kind):
         assert torch.equal(fb, fb0), "the merged shortlist, and so the certificate, does not depend on the slices"
     for kk in (33, 64):  # two and three shortlist slots per lane, merged
         _same(hg.ops.knn(x, kk, cand_slices=8, form="dot"), hg.ops.knn(x, kk, cand_slices=1), "k=%d" % kk)
+
+
+@pytest.mark.parametrize("kind", ["integer", "randn"])
+@pytest.mark.parametrize("nq", [5, 130])
+def test_merge_of_32_slices(hg, nq, kind):
+    """Few queries against 4100 candidates: 33 candidate tiles of 128 rows, so cand_slices = 32 is not clipped, and the
+    default picks it too (512 workgroups over one or two query tiles).  The rerank merges 32 shortlists a row."""
+    from hypergef_amd import _lib
+    n, F = 4100, 3
+    make = _ints if kind == "integer" else _randn
+    X, Q = make(n, F, 91), make(nq, F, 92)
+    x, q = _dev(X), _dev(Q)
+    D = kr.distances(Q, X) if kind == "integer" else None
+    L = _lib.lib()
+    for k in (10, 64):
+        # the workspace says how many slices the call takes: slices nq (8 kp + 4) bytes of lists and partial means, each of
+        # the three pieces rounded up by less than 256 bytes, beside what does not depend on the slices
+        kp = 32 * dr.slots(k)
+        bytes_of = {cs: L.hg_knn_dot_workspace_bytes(nq, n, F, k, cs) for cs in (0, 1, 31, 32)}
+        per = nq * (8 * kp + 4)
+        assert abs(bytes_of[32] - bytes_of[1] - 31 * per) < 3 * 256, bytes_of
+        assert bytes_of[32] > bytes_of[31], "32 slices were clipped"
+        assert bytes_of[0] == bytes_of[32], "the default did not pick 32 slices"
+        want = hg.ops.knn(x, k, queries=q, form="difference")
+        one = hg.ops.knn(x, k, queries=q, form="dot", cand_slices=1, return_fallback=True)
+        _same(one, want, "%s nq=%d k=%d, one slice" % (kind, nq, k))
+        for cs in (0, 32):
+            got = hg.ops.knn(x, k, queries=q, form="dot", cand_slices=cs, return_fallback=True)
+            _same(got, want, "%s nq=%d k=%d cand_slices=%d" % (kind, nq, k, cs))
+            assert torch.equal(got[2], one[2]), "fallback differs from one slice's, cand_slices=%d" % cs
+            if kind == "integer":
+                assert np.array_equal(got[0].cpu().numpy(), kr.knn(X, k, queries=Q, D=D)[0])
+
+
+def _overflow_case(name, n=dr.CASE_N):
+    """overflow: randn with row 7 times 1e19 -- its norm is infinite, every difference with it is finite and every distance
+    to it +inf, never NaN.  huge: randn times 4e17 -- every norm and every distance is finite, and n2q + n2max >= 1e37."""
+    X = np.random.default_rng({"overflow": 6, "huge": 7}[name]).standard_normal((n, dr.CASE_F)).astype(np.float32)
+    if name == "overflow":
+        X[7] *= np.float32(1e19)
+    else:
+        X *= np.float32(4e17)
+    with np.errstate(over="ignore", invalid="ignore"):
+        total = dr._bound(X, X)[1]
+        D = dr.d2_f32(X, X)
+    assert np.isfinite(X).all() and not np.isnan(D).any()
+    if name == "overflow":
+        assert np.isinf(total).all() and np.isinf(D[7, np.arange(n) != 7]).all() and D[7, 7] == 0
+        assert np.isfinite(np.delete(np.delete(D, 7, 0), 7, 1)).all()
+    else:
+        assert np.isfinite(total).all() and (total >= 1e37).all() and np.isfinite(D).all()
+    return X
+
+
+@pytest.mark.parametrize("name", ["overflow", "huge"])
+def test_norms_that_overflow_take_the_exhaustive_path(hg, name):
+    X = _overflow_case(name)
+    x = _dev(X)
+    n, k = dr.CASE_N, dr.CASE_K
+    for self_first in (True, False):
+        want = hg.ops.knn(x, k, self_first=self_first)
+        got = hg.ops.knn(x, k, self_first=self_first, form="dot", return_fallback=True)
+        _same(got, want, "%s self_first=%s" % (name, self_first))
+        assert int(got[2].sum()) == n, "%s: %d rows were certified" % (name, n - int(got[2].sum()))
+        idx, dist = got[0].cpu().numpy(), got[1].cpu().numpy()
+        assert not np.isnan(dist).any()
+        if name == "overflow":
+            assert not (np.delete(idx, 7, 0) == 7).any(), "row 7, at +inf from every other row, is in another row's list"
+            assert np.isfinite(np.delete(dist, 7, 0)).all()
+            if self_first:  # all others tie at +inf: the index decides
+                assert idx[7].tolist() == [7] + [j for j in range(n) if j != 7][:k - 1]
+                assert dist[7, 0] == 0 and np.isposinf(dist[7, 1:]).all()
+    # n <= kp: nothing is left out of the shortlist and no certificate is taken
+    small = _dev(_overflow_case(name, 20))
+    for self_first in (True, False):
+        _same(hg.ops.knn(small, k, self_first=self_first, form="dot"), hg.ops.knn(small, k, self_first=self_first),
+              "%s, n = 20, self_first=%s" % (name, self_first))
 
 
 def _run_case(hg, name, self_first=True):

@@ -4,6 +4,7 @@ Exact class: inputs randint(-4, 5) as float32, so every d2 is an integer fp32 ho
 are everywhere: idx and dist must equal the reference, whose selection is np.lexsort((j, d2)).  Float class: randn inputs
 against the float64 distances D with eps = (F + 3) 2^-23, the fp32 rounding bound of an F-term sum of squared differences,
 doubled.  The kernel's query tile is 64 rows and its candidate tile 256 (hg_knn.h): the sizes straddle both.
+cand_slices runs up to its limit of 32, where most slices own no candidate tile and the merge reads lists of unused slots.
 """
 import os
 import sys
@@ -117,6 +118,46 @@ def test_split_invariance(hg, kind):
         assert torch.equal(a[0], b[0]) and torch.equal(a[1].view(torch.int32), b[1].view(torch.int32))
         if kind == "integer":
             _assert_exact(a, kr.knn(X, kk), "k=%d" % kk)
+
+
+@pytest.mark.parametrize("k", [1, 33, 64])
+def test_merge_of_32_slices(hg, k):
+    """cand_slices = 32 over 700 candidates: three candidate tiles, so 29 of the 32 slices -- slice 0 among them -- own no
+    tile and hand the merge lists of unused slots only; at k = 64 the merge's LDS is the 64 KiB its launch allows for."""
+    n, F = 700, 33
+    X = _ints(n, F, 5)
+    x = _dev(X)
+    D = kr.distances(X, X)
+    for self_first in (True, False):
+        got = hg.ops.knn(x, k, self_first=self_first, cand_slices=32)
+        _assert_exact(got, kr.knn(X, k, self_first=self_first, D=D), "32 slices, k=%d self_first=%s" % (k, self_first))
+    r = _dev(np.random.default_rng(6).standard_normal((n, F)).astype(np.float32))
+    for self_first in (True, False):
+        one = hg.ops.knn(r, k, self_first=self_first, cand_slices=1)
+        idx, dist, mean = hg.ops.knn(r, k, self_first=self_first, cand_slices=32, return_mean=True)
+        assert torch.equal(idx, one[0]), "idx differs from one slice's, k=%d self_first=%s" % (k, self_first)
+        assert torch.equal(dist.view(torch.int32), one[1].view(torch.int32)), "dist differs from one slice's, k=%d" % k
+        again = hg.ops.knn(r, k, self_first=self_first, cand_slices=32, return_mean=True)
+        for a, b in zip((idx, dist, mean), again):
+            assert torch.equal(a.view(torch.int32), b.view(torch.int32)), "two calls differ, k=%d self_first=%s" % (k, self_first)
+
+
+def test_merge_of_32_slices_over_short_segments(hg):
+    """Segments of 64, 1 and 235 rows under 32 slices at k = 1: a query tile has one candidate tile at the most, so all but one
+    of its 32 lists are unused slots."""
+    n, F, seg = 300, 33, [0, 64, 65, 300]
+    X = _ints(n, F, 31)
+    x = _dev(X)
+    D = kr.distances(X, X)
+    lo, hi = kr.candidate_ranges(n, n, seg)
+    for self_first in (True, False):
+        idx, dist, mean = hg.ops.knn(x, 1, segments=seg, self_first=self_first, return_mean=True, cand_slices=32)
+        want = kr.knn(X, 1, segments=seg, self_first=self_first, D=D)
+        _assert_exact((idx, dist), want, "32 slices, seg=%s self_first=%s" % (seg, self_first))
+        i = idx.cpu().numpy()
+        assert (i >= lo[:, None]).all() and (i < hi[:, None]).all(), "an index left its segment"
+        m = mean.cpu().numpy().astype(np.float64)
+        assert (np.abs(m - want[2]) <= (n + F) * U23 * np.maximum(want[2], 1e-300)).all()
 
 
 @pytest.mark.parametrize("F", [3, 64, 260])

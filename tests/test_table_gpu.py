@@ -1,6 +1,8 @@
 """Aggregation over a neighbour table on the device (-m gpu): hg_table_transpose against the stable argsort, the two gathers
-bit for bit against float32 loops in the contract's order (rows one lane group sums) and against float64 where a whole
-workgroup sums a long row, ops.knn_aggr and its gradient against float64 and against the planned operators on
+bit for bit against float32 loops in the contract's order -- rows one lane group sums, and rows a whole workgroup sums in
+the pieces and the tree of the header's ORDER paragraph (tests/_table_ref.py, gather_t_ordered), at every width where that
+path changes shape, wherever the row stands, with ignored positions in it -- and against float64,
+ops.knn_aggr and its gradient against float64 and against the planned operators on
 HyperGraph.from_knn, DynamicHypergraphConv(device_graph=True) against the layer as it was, and its hipGraph capture."""
 import os
 import sys
@@ -69,6 +71,25 @@ def test_transpose_of_hand_made_tables(hg):
     idx[:, 0] = 0  # every row names vertex 0
     _check_transpose(hg, idx, 1500)
     _check_transpose(hg, rng.integers(0, 70000, (3000, 7)).astype(np.int32), 70000)  # keys of 17 bits: three passes, many tiles
+
+
+def test_transpose_where_the_scan_carries_and_the_key_widens(hg):
+    rng = np.random.default_rng(1)
+    # 19 tiles of 2048 entries: 4864 counters, more than the 4096 one trip of the scan takes, so the second trip starts from
+    # the first one's carry; -1 and n = 999 are ignored and sort behind every vertex
+    idx = rng.integers(-1, 1000, (600, 64)).astype(np.int32)
+    assert (idx == -1).any() and (idx == 999).any()
+    _check_transpose(hg, idx, 999)
+    # exactly one tile, and one tile and one entry
+    _check_transpose(hg, rng.integers(0, 50, (32, 64)).astype(np.int32), 50)
+    _check_transpose(hg, rng.integers(0, 50, (2049, 1)).astype(np.int32), 50)
+    # the key of an ignored entry is n itself: 8 bits at n = 255 and 9 at 256 (one radix pass, then two), 16 and 17 (three)
+    for n in (255, 256, 65535, 65536):
+        idx = rng.integers(-1, n + 1, (40, 5)).astype(np.int32)
+        idx[0, :2], idx[39, 3:] = (-1, n), (n, -1)
+        idx[1, 0], idx[38, 4] = 0, n - 1
+        assert (idx == -1).any() and (idx == n).any()
+        _check_transpose(hg, idx, n)
 
 
 @pytest.fixture(scope="module")
@@ -158,6 +179,131 @@ def test_long_rows(hg, F):
             padded = kg.table_gather_t(ptr2, pos2, k, _dev(src2))
             assert torch.equal(padded[0], plain[0])
             assert np.array_equal(_np(pos2)[:length], _np(pos_d)[:length])
+
+
+def _dev_rows(a, aligned16=True):
+    """A [rows, F] array on the device, on a 16-byte boundary or one float past one."""
+    if aligned16:
+        t = _dev(a)
+        assert t.data_ptr() % 16 == 0
+        return t
+    buf = torch.zeros(a.size + 1, dtype=torch.float32, device=DEV)
+    assert buf.data_ptr() % 16 == 0
+    t = buf[1:].view(*a.shape)
+    t.copy_(torch.from_numpy(a))
+    assert t.data_ptr() % 16 == 4 and t.is_contiguous()
+    return t
+
+
+FACTORS = ((0, 0, 0), (1, 0, 0), (0, 1, 0), (0, 0, 1), (1, 1, 1))  # which of w, src_scale, dst_scale a call is given
+
+
+@pytest.mark.parametrize("F,aligned,P", tr.LONG_ROW_WIDTHS)
+def test_long_rows_bit_exact_wherever_they_stand(hg, F, aligned, P):
+    """Vertex rows above HG_TABLE_SEQ_MAX in the header's order, bit for bit: in another lane group, another wave and another
+    workgroup than the first, two in one tile, the last vertex of a partial tile, beside short rows, a row of exactly
+    HG_TABLE_SEQ_MAX entries and an empty one -- and the same entries under another vertex number give the same bits."""
+    from hypergef_amd import knn_graph as kg
+    seq = kg.table_seq_max()
+    c, L, R, got_P, P2 = tr.long_row_shape(F, aligned)
+    assert got_P == P, "the header's P = 4 * (64 / L) at F = %d is %d, the table of widths says %d" % (F, got_P, P)
+    t = tr.hub_table(F, aligned, seq, seed=F)
+    idx, n, hubs, k = t["idx"], t["n"], t["hubs"], 2
+    rows = idx.shape[0]
+    ptr, pos = tr.transpose(idx, n)
+    lens = np.diff(ptr)
+    assert n % (4 * R) and set(hubs) == {0, 1, R, 4 * R - 1, 4 * R, n - 1} and (lens[hubs] > seq).all()
+    assert {seq + 1, seq + 2, 4 * seq + 3} <= set(lens[hubs].tolist()) and lens[hubs].max() >= 1000
+    assert lens[t["full"]] == seq and lens[t["empty"]] == 0 and (np.delete(lens, hubs) <= seq).all()
+    rng = np.random.default_rng(300 + F)
+    src = rng.standard_normal((rows, F)).astype(np.float32)
+    w = (rng.random(rows * k) + 0.5).astype(np.float32)
+    ss, ds = rng.standard_normal(rows).astype(np.float32), rng.standard_normal(n).astype(np.float32)
+    # the second table: vertex v is called perm[v]; the positions and the source rows stay, every row moves
+    perm = (np.arange(n) + 2 * R + 1) % n
+    assert (perm[hubs] != hubs).all()
+    inv = np.argsort(perm)
+    ptr_d, pos_d = hg.ops.knn_transpose(_dev(idx), n)
+    ptr2_d, pos2_d = hg.ops.knn_transpose(_dev(perm[idx].astype(np.int32)), n)
+    assert np.array_equal(_np(ptr_d), ptr) and np.array_equal(_np(pos_d), pos)
+    ptr2, pos2 = _np(ptr2_d), _np(pos2_d)
+    for h in hubs:
+        assert np.array_equal(pos2[ptr2[perm[h]]:ptr2[perm[h] + 1]], pos[ptr[h]:ptr[h + 1]])
+    src_d = _dev_rows(src, aligned)
+    for use_w, use_src, use_dst in FACTORS:
+        what = "F = %d, w %d, src_scale %d, dst_scale %d" % (F, use_w, use_src, use_dst)
+        a = (w if use_w else None, ss if use_src else None, ds if use_dst else None)
+        got = kg.table_gather_t(ptr_d, pos_d, k, src_d, *[_dev(x) for x in a])
+        assert got.data_ptr() % 16 == 0
+        want = tr.gather_t_ordered(ptr, pos, k, src, *a, aligned16=aligned, seq_max=seq)
+        bad = np.flatnonzero((_np(got) != want).any(1))
+        assert np.array_equal(_np(got), want), "%s: rows %s differ (hubs %s)" % (what, bad.tolist(), hubs)
+        assert not _np(got)[t["empty"]].any() and not np.signbit(_np(got)[t["empty"]]).any(), what
+        again = kg.table_gather_t(ptr_d, pos_d, k, src_d, *[_dev(x) for x in a])
+        assert torch.equal(got.view(torch.int32), again.view(torch.int32)), what + ": two calls differ"
+        a2 = (a[0], a[1], None if a[2] is None else a[2][inv])
+        moved = kg.table_gather_t(ptr2_d, pos2_d, k, src_d, *[_dev(x) for x in a2])
+        for h in hubs:
+            assert torch.equal(moved[perm[h]], got[h]), "%s: hub %d as vertex %d has other bits" % (what, h, perm[h])
+        assert torch.equal(moved[_dev(perm)], got), what + ": a short row moved with its place"
+
+
+@pytest.mark.parametrize("F", [3, 32])
+def test_ignored_positions_of_a_hand_made_transpose(hg, F):
+    """pos_v entries outside 0 .. rows k - 1 in a short row and in the first, a middle and the last piece of a long one: each
+    keeps its place in the row's length and pieces, adds nothing and is not read through."""
+    from hypergef_amd import knn_graph as kg
+    seq = kg.table_seq_max()
+    t = tr.hub_table(F, True, seq, seed=50 + F)
+    idx, n, k = t["idx"], t["n"], 2
+    rows = idx.shape[0]
+    ptr, pos = tr.transpose(idx, n)
+    pos = pos.copy()
+    assert pos.shape[0] == rows * k
+    outside = (-1, rows * k, 2 ** 31 - 1)
+    lens = np.diff(ptr)
+    hub = t["hubs"][int(np.argmax(lens[t["hubs"]]))]
+    length, P = int(lens[hub]), t["P"]
+    chunk = -(-length // P)
+    last = (length - 1) // chunk  # the last piece that holds an entry
+    assert last > P // 2 > 0 and length > seq
+    for g, bad in zip((0, P // 2, last), outside):
+        pos[ptr[hub] + g * chunk + (min(chunk, length - g * chunk) - 1) * (g % 2)] = bad  # a piece's first or last entry
+    pos[ptr[hub] + 1] = outside[1]
+    short = next(v for v in range(n) if v not in t["hubs"] and 4 <= lens[v] < seq)
+    pos[ptr[short]:ptr[short] + 3] = outside
+    lonely = next(v for v in range(n) if v not in t["hubs"] and v != short and 1 <= lens[v] < seq)
+    pos[ptr[lonely]:ptr[lonely + 1]] = -1  # a row of ignored entries only: not empty, +0.0 times its scale
+    rng = np.random.default_rng(400 + F)
+    src = rng.standard_normal((rows, F)).astype(np.float32)
+    w = (rng.random(rows * k) + 0.5).astype(np.float32)
+    ss, ds = rng.standard_normal(rows).astype(np.float32), np.abs(rng.standard_normal(n)).astype(np.float32) + 0.5
+    ptr_d, pos_d, src_d = _dev(ptr), _dev(pos), _dev(src)
+    for use_w, use_src, use_dst in FACTORS:
+        a = (w if use_w else None, ss if use_src else None, ds if use_dst else None)
+        got = _np(kg.table_gather_t(ptr_d, pos_d, k, src_d, *[_dev(x) for x in a]))
+        want = tr.gather_t_ordered(ptr, pos, k, src, *a, seq_max=seq)
+        assert np.array_equal(got, want), (F, use_w, use_src, use_dst, np.flatnonzero((got != want).any(1)).tolist())
+        assert not got[lonely].any() and not np.signbit(got[lonely]).any()
+
+
+@pytest.mark.parametrize("F", [5, 32])
+def test_operator_and_gradient_over_hubs(hg, F):
+    """ops.knn_aggr over a table with long vertex rows: both the forward's and the backward's table_gather_t take the long
+    path.  Against float64 at the file's tolerance, and the forward bit for bit against the two launches in float32."""
+    from hypergef_amd import knn_graph as kg
+    t = tr.hub_operator_case(F, kg.table_seq_max())
+    idx, n, w, degE, degV = t["idx"], t["n"], t["w"], t["degE"], t["degV"]
+    X = _dev(t["X"]).requires_grad_(True)
+    Y = hg.ops.knn_aggr(_dev(idx), X, _dev(w), _dev(degE), _dev(degV))
+    (dX,) = torch.autograd.grad(Y, X, _dev(t["G"]))
+    _assert_close(Y, tr.aggr(idx, t["X"], w, degE, degV), "Y over hubs, F = %d" % F)
+    _assert_close(dX, tr.aggr_grad(idx, t["G"], w, degE, degV), "dX over hubs, F = %d" % F)
+    ptr, pos = tr.transpose(idx, n)
+    want = tr.gather_t_ordered(ptr, pos, 2, tr.gather(idx, t["X"], w, None, degE), w, None, degV, seq_max=kg.table_seq_max())
+    assert np.array_equal(_np(Y), want)
+    want = tr.gather_t_ordered(ptr, pos, 2, tr.gather(idx, t["G"], w, degV, degE), w, seq_max=kg.table_seq_max())
+    assert np.array_equal(_np(dX), want)
 
 
 @pytest.fixture(scope="module")

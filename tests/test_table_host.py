@@ -1,5 +1,6 @@
 """Aggregation over a neighbour table, without a device: the exported names, tests/_table_ref.py's transpose against the
-definition written as loops, HG_TABLE_SEQ_MAX as the library was built, the workspace size and the C entries' refusals
+definition written as loops, its float32 reference of the long-row order (every entry summed once, inside the device
+tests' tolerance of float64, other bits under another tree), HG_TABLE_SEQ_MAX as the library was built, the workspace size and the C entries' refusals
 (decided before any device call: every pointer here is host memory), and what ops.knn_transpose / ops.knn_aggr refuse
 before a device is touched, in which order."""
 import ctypes
@@ -79,6 +80,105 @@ def test_reference_gathers_are_one_another_s_transpose():
     empty = tr.gather_t(np.array([0, 0, 2], np.int32), np.array([0, 1], np.int32), 1, X[:2], None, None,
                         np.array([np.inf, 1.0], np.float32))
     assert not empty[0].any() and not np.signbit(empty[0]).any()
+
+
+def _hub_inputs(t, F, seed, integer):
+    """src [rows, F], w [rows k], src_scale [rows], dst_scale [n] for a hub table: small integers (every order of a sum is
+    exact) or randn with weights in [0.5, 1.5)."""
+    rng = np.random.default_rng(seed)
+    rows, k = t["idx"].shape
+    if integer:
+        draw = lambda lo, hi, size: rng.integers(lo, hi, size).astype(np.float32)  # noqa: E731
+        return draw(-4, 5, (rows, F)), draw(1, 4, rows * k), draw(-2, 3, rows), draw(-2, 3, t["n"])
+    return (rng.standard_normal((rows, F)).astype(np.float32), (rng.random(rows * k) + 0.5).astype(np.float32),
+            rng.standard_normal(rows).astype(np.float32), rng.standard_normal(t["n"]).astype(np.float32))
+
+
+def test_long_row_shapes_of_the_header():
+    for F, aligned, P in tr.LONG_ROW_WIDTHS:
+        c, L, R, got, P2 = tr.long_row_shape(F, aligned)
+        assert got == P == 4 * R and R == 64 // L and L == min(-(-F // c), 64), (F, aligned)
+        assert P2 >= P > P2 // 2 and P2 & (P2 - 1) == 0
+    assert [tr.long_row_shape(F, a)[4] for F, a, _ in tr.LONG_ROW_WIDTHS] == [256, 128, 256, 64, 64, 128, 4, 4]
+    assert tr.long_row_shape(32)[3] == 32 and tr.long_row_shape(33)[3] == 4  # the widths of test_long_rows
+
+
+@pytest.mark.parametrize("F,aligned,P", tr.LONG_ROW_WIDTHS)
+def test_ordered_reference_sums_every_entry_once(F, aligned, P):
+    """Integer-valued rows, weights and scales: every partial sum is an integer below 2^24, so every order gives the same
+    bits and the pieces-and-tree reference must equal the sequential one -- unless it drops or repeats an entry."""
+    t = tr.hub_table(F, aligned, lengths=(129, 130, 515, 1000))
+    assert sorted(set(t["lens"])) == [129, 130, 515, 1000] and t["P"] == P
+    ptr, pos = tr.transpose(t["idx"], t["n"])
+    assert [int(ptr[h + 1] - ptr[h]) for h in t["hubs"]] == t["lens"]
+    assert ptr[t["full"] + 1] - ptr[t["full"]] == 128 and ptr[t["empty"] + 1] == ptr[t["empty"]]
+    src, w, ss, ds = _hub_inputs(t, F, 100 + F, integer=True)
+    for args in ((None, None, None), (w, ss, ds)):
+        want = tr.gather_t(ptr, pos, 2, src, *args)
+        got = tr.gather_t_ordered(ptr, pos, 2, src, *args, aligned16=aligned)
+        assert np.abs(want).max() < 2 ** 24 and np.abs(want[t["hubs"]]).max() > 0
+        assert np.array_equal(got, want) and np.array_equal(np.signbit(got), np.signbit(want))
+
+
+@pytest.mark.parametrize("F,aligned,P", tr.LONG_ROW_WIDTHS)
+def test_ordered_reference_is_within_the_device_tolerance_of_float64(F, aligned, P):
+    from test_table_gpu import _assert_close
+    t = tr.hub_table(F, aligned)
+    idx, n = t["idx"], t["n"]
+    ptr, pos = tr.transpose(idx, n)
+    src, w, _, _ = _hub_inputs(t, F, 200 + F, integer=False)
+    deg = np.diff(ptr).astype(np.float64)
+    degV = np.where(deg > 0, np.maximum(deg, 1) ** -0.5, 1.0).astype(np.float32)  # the operator's vertex scale
+    got = tr.gather_t_ordered(ptr, pos, 2, src, w, None, degV, aligned16=aligned)
+    ref = np.zeros((n, F))
+    for v in range(n):
+        p = pos[ptr[v]:ptr[v + 1]]
+        ref[v] = degV[v].astype(np.float64) * (src[p // 2].astype(np.float64) * w[p].astype(np.float64)[:, None]).sum(0)
+    _assert_close(got, ref, "gather_t_ordered, F = %d" % F)
+    # rows up to seq_max entries, the one of exactly seq_max included, are gather_t's
+    seq = tr.gather_t(ptr, pos, 2, src, w, None, degV)
+    short = np.diff(ptr) <= 128
+    assert short[t["full"]] and not short[t["hubs"]].any()
+    assert np.array_equal(got[short], seq[short])
+    if F == 3:  # the same rows under a longer sequential limit: a hub of 129 and one of 130 entries become gather_t's too
+        got = tr.gather_t_ordered(ptr, pos, 2, src, w, None, degV, seq_max=130)
+        short = np.diff(ptr) <= 130
+        assert short.sum() == n - len(t["hubs"]) + 4 and np.array_equal(got[short], seq[short])
+
+
+def test_ordered_reference_tells_another_tree_apart():
+    """A tree that starts at P / 2 instead of P' / 2 (F = 3: P = 84, P' = 128) gives other bits on one randn hub, so the
+    bit-for-bit device test can fail on a wrong order."""
+    rng = np.random.default_rng(9)
+    P, P2 = tr.long_row_shape(3)[3:]
+    assert (P, P2) == (84, 128)
+    terms = rng.standard_normal((1000, 3)).astype(np.float32)
+    live = np.ones(1000, bool)
+    right = tr.long_row_sum(terms, live, P)
+    assert np.array_equal(right, tr.long_row_sum(terms, live, P, first_stride=P2 // 2))
+    assert not np.array_equal(right, tr.long_row_sum(terms, live, P, first_stride=P // 2))
+    assert not np.array_equal(right, np.add.accumulate(terms, axis=0, dtype=np.float32)[-1])  # nor the sequential sum
+    # an ignored entry keeps its place: the pieces are those of the whole length, not of the live entries
+    live[[0, 500, 999]] = False
+    kept = tr.long_row_sum(terms, live, P)
+    zeroed = terms.copy()
+    zeroed[~live] = 0
+    assert np.array_equal(kept, tr.long_row_sum(zeroed, np.ones(1000, bool), P))
+    assert not np.array_equal(kept, tr.long_row_sum(terms[live], np.ones(997, bool), P))
+
+
+@pytest.mark.parametrize("F", [5, 32])
+def test_composed_float32_operator_is_within_the_device_tolerance(F):
+    """gather then gather_t_ordered, the device's two launches in float32 on the CPU, against the float64 operator and its
+    gradient over the hub table the device test uses: the tolerance has room for the order before the device is asked."""
+    from test_table_gpu import _assert_close
+    t = tr.hub_operator_case(F)
+    idx, n, w, degE, degV = t["idx"], t["n"], t["w"], t["degE"], t["degV"]
+    ptr, pos = tr.transpose(idx, n)
+    Y = tr.gather_t_ordered(ptr, pos, 2, tr.gather(idx, t["X"], w, None, degE), w, None, degV)
+    _assert_close(Y, tr.aggr(idx, t["X"], w, degE, degV), "Y, F = %d" % F)
+    dX = tr.gather_t_ordered(ptr, pos, 2, tr.gather(idx, t["G"], w, degV, degE), w)
+    _assert_close(dX, tr.aggr_grad(idx, t["G"], w, degE, degV), "dX, F = %d" % F)
 
 
 def test_workspace_and_c_refusals_before_any_device_call(hg):
