@@ -363,6 +363,8 @@ class Plan:
         residual, t_out and the result are bfloat16, degE / degV / W float32, accumulation fp32.  t_out receives
         (ca * Aggr(X) + cb * residual) of the fp32 call on the widened operands, rounded to bf16 once -- bit for bit
         aggregate_linear(X.float(), ..., t_out=).to(bfloat16) -- and Y = round_bf16(act(t_out . weight^T)) (include/hg_aggr.h).
+        (Both calls must run the same pull hop kernels for that: X.float() beyond 2^31 bytes leaves the streaming row gather
+        while a bfloat16 X of half the size stays on it, and a long hyperedge is then summed in another order; pin them.)
         cb may be a one-element float32 device tensor.  packed = pack_linear_bf16(weight) if the caller keeps it.
         Dtypes and shapes are refused (TypeError, ValueError) before any device is touched."""
         for name, t in (("node_feat", X), ("weight", weight), ("residual", residual), ("t_out", t_out), ("out", out)):

@@ -1516,7 +1516,8 @@ def test_tables_beyond_2GiB_use_64bit_offsets(hg, oracle, K, F):
     pointer arithmetic) and of 8.6 GB (N*F beyond 2^31 ELEMENTS: where the reference's `int` index math
     `v*F+k` overflows, hgnnaggr_cuda.cu:34).  The batch is block-diagonal, so every hypergraph of
     it can be checked on its own: first, middle and last against the oracle on one cora-shape graph, bit for
-    bit (their hyperedges are short: the CPU order is kept), fused and pull."""
+    bit (their hyperedges are short: the CPU order is kept), fused and pull.  The incidence operators at these sizes:
+    test_large_offsets_gpu.py."""
     from hypergef_amd.plan import Plan
     one = synth.cora_shape()
     inc = synth.replicate_block_diagonal(one, K)
