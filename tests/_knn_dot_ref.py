@@ -223,3 +223,99 @@ def case(name):
         X = rng.standard_normal((n, F))
         X[240:] = 10.0 + 1e-3 * rng.standard_normal((60, F))
     return np.ascontiguousarray(X, F32)
+
+
+# ---- the prefilter's slices, their shortlists and the rerank over them (csrc/hg_knn_dot.hip), as a host model ---------------
+
+def estimates(Q, X):
+    """d~ = (n2q + n2x) - 2 s~ in float32 as the kernels form it: float32 norms and an fma chain over the columns for q.x.
+    Exact on integer-valued rows."""
+    Q, X = np.asarray(Q, F32), np.asarray(X, F32)
+    s = np.zeros((Q.shape[0], X.shape[0]), F32)
+    for c in range(X.shape[1]):
+        s = _fma32(np.broadcast_to(Q[:, c][:, None], s.shape), np.broadcast_to(X[:, c][None, :], s.shape), s)
+    return ((norms(Q)[:, None] + norms(X)[None, :]).astype(F32) - F32(2) * s).astype(F32)
+
+
+def dot_kp(n, k):
+    return min(n, 32 * slots(k))
+
+
+def dot_slices(nq, n, cand_slices):
+    """knn_dot_slices: 0 asks for about 512 workgroups; every value is clipped to 32 and to the candidate tiles."""
+    groups, tiles = -(-nq // kr.DOT_TQ), -(-n // kr.DOT_TC)
+    s = cand_slices if cand_slices else 512 // groups
+    return max(1, min(s, kr.KNN_MAX_SLICES, tiles))
+
+
+def dot_workspace_bytes(nq, n, k, slices):
+    """knn_dot_layout's total: the norms, the block maxima and their maximum, the slices' shortlists and partial means, each
+    piece rounded up to 256 bytes."""
+    def up(b):
+        return (b + 255) // 256 * 256
+    lists = slices * nq * dot_kp(n, k) * 4
+    return up(n * 4) + up(nq * 4) + up(-(-n // kr.DOT_NORM_ROWS) * 4) + 256 + 2 * up(lists) + up(slices * nq * 4)
+
+
+def shortlists(est, k, slices, self_first):
+    """The slices' shortlists as the prefilter leaves them: (ld float32, lj int32, used bool), each [nq, slices, kp].  Slice s
+    owns the candidate tiles [tiles s / slices, tiles (s + 1) / slices) of DOT_TC rows and lists its kp smallest candidates
+    under (d~, j), the row itself at -inf under self_first; a slot past them holds (+inf, INT_MAX)."""
+    est = np.asarray(est, F32)
+    nq, n = est.shape
+    kp = dot_kp(n, k)
+    tiles = -(-n // kr.DOT_TC)
+    ld = np.full((nq, slices, kp), np.inf, F32)
+    lj = np.full((nq, slices, kp), kr.INT_MAX, np.int32)
+    used = np.zeros((nq, slices, kp), bool)
+    for s in range(slices):
+        a, b = min(n, (tiles * s // slices) * kr.DOT_TC), min(n, (tiles * (s + 1) // slices) * kr.DOT_TC)
+        j = np.arange(a, b)
+        for i in range(nq):
+            key = est[i, a:b].copy()
+            if self_first and a <= i < b:
+                key[i - a] = -np.inf
+            order = np.lexsort((j, key))[:kp]
+            m = order.shape[0]
+            ld[i, s, :m], lj[i, s, :m], used[i, s, :m] = key[order], j[order], True
+    return ld, lj, used
+
+
+def rerank(X, k, ld, lj, queries=None, self_first=None, D32=None):
+    """The model of knn_dot_rerank_kernel over given shortlists: (idx, dist, fallback) as `scheme` returns them.  The lists are
+    merged with the rank search of knn_merge_kernel (the same code in both kernels); the first kp entries are the row's
+    shortlist, a slot no entry ranked into holds no candidate; an entry outside 0 .. n - 1 makes the row fall back; the
+    others are ranked by d2_f32 with every copy of a repeated index offered; then the certificate as in `scheme`."""
+    X = np.asarray(X, F32)
+    Q = X if queries is None else np.asarray(queries, F32)
+    if self_first is None:
+        self_first = queries is None
+    nq, n, F = Q.shape[0], X.shape[0], X.shape[1]
+    kp = ld.shape[2]
+    if D32 is None:
+        D32 = d2_f32(Q, X)
+    E1, total = _bound(Q, X)
+    idx = np.empty((nq, k), np.int32)
+    dist = np.empty((nq, k), F32)
+    fallback = np.zeros(nq, np.int32)
+    with np.errstate(invalid="ignore", over="ignore"):
+        for i in range(nq):
+            rank = kr.merge_ranks(ld[i], lj[i])
+            cd, cj = np.full(kp, np.nan, F32), np.full(kp, -1, np.int64)
+            w = rank < kp
+            cd[rank[w]], cj[rank[w]] = ld[i].reshape(-1)[w], lj[i].reshape(-1)[w]
+            exact = D32[i].astype(np.float64)
+            if self_first:
+                exact[i] = -1.0
+            ok = (cj >= 0) & (cj < n)
+            short = cj[ok]
+            pick = short[np.lexsort((short, exact[short]))[:k]]
+            certified = bool(ok.all()) and pick.shape[0] == k
+            if certified and n > kp:
+                certified = bool(total[i] < F32(1e37)) and bool(exact[pick[-1]] < _lower(cd[kp - 1], E1[i], F))
+            if not certified:
+                fallback[i] = 1
+                pick = _select(exact, k)
+            idx[i] = pick
+            dist[i] = np.maximum(D32[i, pick], 0)
+    return idx, dist, fallback

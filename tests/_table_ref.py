@@ -196,6 +196,62 @@ def hub_operator_case(F, seq_max=128, seed=70):
     return t
 
 
+TABLE_TILE, TABLE_RADIX_BITS = 2048, 8  # csrc/hg_table.h: kTableTile = kTableBlock * kTableItems, kTableRadixBits
+
+
+def radix_passes(n):
+    """The passes of the transpose's sort: the keys 0 .. n (n itself: an ignored entry) have ceil(log2(n + 1)) bits."""
+    bits = 0
+    while (1 << bits) <= n:
+        bits += 1
+    return -(-bits // TABLE_RADIX_BITS)
+
+
+def transpose_workspace_bytes(rows, k, n):
+    """hg_table_transpose_workspace_bytes: the second position buffer rounded up to 256 bytes, then 256 counters a tile."""
+    entries = rows * k
+    return (entries * 4 + 255) // 256 * 256 + (1 << TABLE_RADIX_BITS) * -(-entries // TABLE_TILE) * 4
+
+
+def _wrap32(a):
+    return ((np.asarray(a, np.int64) + 2 ** 31) % 2 ** 32) - 2 ** 31
+
+
+def radix_model(idx, n, hist0=0, fill=0):
+    """The transpose's sort as hg_table.hip runs it, with every tile counter starting at the int32 `hist0` instead of 0 and the
+    position buffers holding `fill` before a pass writes them: per pass and per tile of TABLE_TILE positions a count of each
+    digit, one exclusive scan over [digit, tile], and a stable scatter that drops what lands outside the buffer.  Returns the
+    final positions int64 [rows k], or None where a pass read a position outside the table (the kernel would have read
+    idx out of bounds).  hist0 = 0 is the stable sort by key."""
+    flat = np.asarray(idx).reshape(-1).astype(np.int64)
+    entries = flat.shape[0]
+    key = np.where((flat >= 0) & (flat < n), flat, n)
+    bins = 1 << TABLE_RADIX_BITS
+    tiles = -(-entries // TABLE_TILE)
+    order = np.arange(entries)
+    for p in range(radix_passes(n)):
+        if ((order < 0) | (order >= entries)).any():
+            return None
+        digit = (key[order] >> (p * TABLE_RADIX_BITS)) & (bins - 1)
+        hist = np.full((bins, tiles), hist0, np.int64)
+        for t in range(tiles):
+            hist[:, t] += np.bincount(digit[t * TABLE_TILE:(t + 1) * TABLE_TILE], minlength=bins)
+        hist = _wrap32(hist)
+        start = _wrap32(np.concatenate([[0], np.cumsum(hist.reshape(-1))[:-1]])).reshape(bins, tiles)
+        out = np.full(entries, fill, np.int64)
+        for t in range(tiles):
+            d = digit[t * TABLE_TILE:(t + 1) * TABLE_TILE]
+            within = np.zeros(d.shape[0], np.int64)
+            for b in np.unique(d):
+                m = d == b
+                within[m] = np.arange(int(m.sum()))
+            at = _wrap32(start[d, t] + within)
+            w = (at >= 0) & (at < entries)
+            out[at[w]] = order[t * TABLE_TILE:(t + 1) * TABLE_TILE][w]
+        order = out
+    return order
+
+
 def _dense64(idx, n, w):
     """H_w^T as a dense float64 [rows, n] matrix (duplicates within a row add up)."""
     idx = np.asarray(idx)
