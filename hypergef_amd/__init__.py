@@ -11,7 +11,8 @@ from .balancer import balance_schedule  # noqa: F401
 from .hypergraph import HyperGraph  # noqa: F401
 from .ops import (HGNNAggr, HGNNAggrIncidence, HGNNAggrLinear, UniGNNConv, UniGNNConvdeg,  # noqa: F401
                   UniGNNConvLinear, hgnnaggr_linear, incidence_aggr, incidence_attention_aggr, incidence_dot,
-                  incidence_gather, incidence_softmax, incidence_sum, knn, knn_aggr, knn_incidence_weights, knn_transpose, reduce_aggr)
+                  incidence_gather, incidence_softmax, incidence_sum, knn, knn_aggr, knn_dist, knn_incidence_weights,
+                  knn_transpose, reduce_aggr)
 from .knn_graph import KnnHypergraph  # noqa: F401
 from .plan import Plan  # noqa: F401
 

@@ -54,6 +54,7 @@ SYMBOLS = (
     "hg_knn_f32", "hg_knn_workspace_bytes", "hg_knn_dot_f32", "hg_knn_dot_workspace_bytes",
     "hg_table_seq_max", "hg_table_transpose_workspace_bytes", "hg_table_transpose", "hg_table_gather_f32",
     "hg_table_gather_t_f32",
+    "hg_table_dist_f32", "hg_table_gather_diff_f32", "hg_table_gather_t_diff_f32", "hg_table_dot_f32",
 )
 HG_REDUCE_MAX = 1
 HG_REDUCE_MIN = 2
@@ -315,6 +316,15 @@ def lib():
         L.hg_table_gather_f32.argtypes = [vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp]
         L.hg_table_gather_t_f32.restype = ctypes.c_int
         L.hg_table_gather_t_f32.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp]
+    if hasattr(L, "hg_table_dot_f32"):  # likewise: a table's distances, their gradient's gathers and the weight gradient
+        L.hg_table_dist_f32.restype = ctypes.c_int
+        L.hg_table_dist_f32.argtypes = [vp, i32, i32, i32, i32, vp, vp, vp, vp]
+        L.hg_table_gather_diff_f32.restype = ctypes.c_int
+        L.hg_table_gather_diff_f32.argtypes = [vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp]
+        L.hg_table_gather_t_diff_f32.restype = ctypes.c_int
+        L.hg_table_gather_t_diff_f32.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp]
+        L.hg_table_dot_f32.restype = ctypes.c_int
+        L.hg_table_dot_f32.argtypes = [vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp]
     L.hg_aggr_push_groups_f32.restype = ctypes.c_int
     L.hg_aggr_push_groups_f32.argtypes = [i32, i32, i32, i64, vp, vp, vp, vp, vp, vp,
                                           vp, vp, vp, vp, vp, vp]

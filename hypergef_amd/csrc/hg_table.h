@@ -13,6 +13,15 @@
 // the transposed gather is summed by the whole workgroup that owns it: lane group g of the P = kTableWaves (64 / L) takes
 // the entries [g c, (g + 1) c), c = ceil(len / P), in ascending order, and the P partial rows are added through LDS in
 // the fixed tree part[g] += part[g + s], s = P' / 2, P' / 4 .. 1 (P' the power of two at or above P).
+// The difference gathers (hg_table_gather_diff_f32 / hg_table_gather_t_diff_f32) are the same kernel under a template flag:
+// the term starts from ctr[destination row] - src[j], the centre's column chunk loaded once per (row, column chunk).
+//
+// Distances (hg_table_dist_f32): one lane per table position walks the query row and the gathered row, kTableDistLoads
+// loads of each in flight, one fma chain in ascending c -- hg_knn_f32's d2, bit for bit.
+//
+// Dot products (hg_table_dot_f32): a lane group of L lanes (the power of two at or above min(ceil(F / V), 64)) owns a table
+// row, keeps its B / D chunk in registers over the row's k entries, gathers kTableDotBatch rows of A / C at a time, and
+// adds the lanes' fma chains in an xor butterfly L / 2 .. 1.
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -25,7 +34,9 @@ constexpr int kTableSeqMax = HG_TABLE_SEQ_MAX;  // rows up to this long: one lan
 constexpr int kTableMaxK = 64;
 constexpr int kTableWaves = 4;                  // gather: waves per workgroup
 constexpr int kTableBatch = 8;                  // gather: row loads issued before the first add
-constexpr int kTableBlock = 256;                // transpose: threads per workgroup
+constexpr int kTableDistLoads = 4;              // dist: loads of each of the two rows a lane issues before the first fma
+constexpr int kTableDotBatch = 4;               // dot: gathered rows in flight per lane group
+constexpr int kTableBlock = 256;                // transpose and dist: threads per workgroup
 constexpr int kTableItems = 8;                  // transpose: positions per thread and pass
 constexpr int kTableTile = kTableBlock * kTableItems;
 constexpr int kTableRadixBits = 8;

@@ -175,6 +175,7 @@ struct TableGatherArgs {
   int32_t k, F, entries;
   int32_t L, R;         // lanes per row, rows per wave
   int32_t P2;           // the power of two at or above kTableWaves R
+  const float *ctr;     // the difference gathers' centre rows [destination rows, F]; last: the plain instances' offsets stay
 };
 
 template <int V>
@@ -205,9 +206,11 @@ __device__ __forceinline__ void cols_store(float *p, const float (&v)[V]) {
 
 // acc += the terms of the entries [beg, end), ascending, for the columns c .. c + V - 1.  T: an entry q is position
 // pos_v[q] of the table and gathers the hyperedge's row; else it is position q itself and gathers row idx[q].  A batch of
-// row loads is issued, then added in order.  An entry that is out of range loads row 0 and is not added.
-template <bool T, int V>
-__device__ __forceinline__ void table_row_sum(const TableGatherArgs &a, int beg, int end, int c, float (&acc)[V]) {
+// row loads is issued, then added in order.  An entry that is out of range loads row 0 and is not added.  D (the
+// difference gathers): the term starts from cv - src[j], cv the destination row's centre columns, rounded on its own.
+template <bool T, int V, bool D>
+__device__ __forceinline__ void table_row_sum(const TableGatherArgs &a, int beg, int end, int c, const Cols<V> &cv,
+                                              float (&acc)[V]) {
   for (int b = beg; b < end; b += kTableBatch) {
     Cols<V> x[kTableBatch];
     float wv[kTableBatch], sv[kTableBatch];
@@ -238,6 +241,7 @@ __device__ __forceinline__ void table_row_sum(const TableGatherArgs &a, int beg,
 #pragma unroll
       for (int i = 0; i < V; ++i) {
         float term = x[u].v[i];
+        if constexpr (D) term = cv.v[i] - term;
         if (a.src_scale) term = term * sv[u];
         if (a.w) term = term * wv[u];
         acc[i] = ok[u] ? acc[i] + term : acc[i];
@@ -245,7 +249,7 @@ __device__ __forceinline__ void table_row_sum(const TableGatherArgs &a, int beg,
   }
 }
 
-template <bool T, int V>
+template <bool T, int V, bool D = false>
 __global__ __launch_bounds__(64 * kTableWaves) void table_gather_kernel(TableGatherArgs a) {
   const int t = threadIdx.x, w = t >> 6, lane = t & 63;
   const int L = a.L, R = a.R, F = a.F;
@@ -276,7 +280,9 @@ __global__ __launch_bounds__(64 * kTableWaves) void table_gather_kernel(TableGat
       float acc[V];
 #pragma unroll
       for (int i = 0; i < V; ++i) acc[i] = 0.f;
-      table_row_sum<T, V>(a, beg, end, c, acc);
+      Cols<V> cv{};
+      if constexpr (D) cv = cols_load<V>(a.ctr + (size_t)row * F + c);
+      table_row_sum<T, V, D>(a, beg, end, c, cv, acc);
       if (a.dst_scale && end > beg) {  // an empty row stays +0.0 whatever its scale
 #pragma unroll
         for (int i = 0; i < V; ++i) acc[i] = ds * acc[i];
@@ -313,7 +319,9 @@ __global__ __launch_bounds__(64 * kTableWaves) void table_gather_kernel(TableGat
             float acc[V];
 #pragma unroll
             for (int i = 0; i < V; ++i) acc[i] = 0.f;
-            table_row_sum<T, V>(a, gb, ge, c, acc);
+            Cols<V> cv{};
+            if constexpr (D) cv = cols_load<V>(a.ctr + (size_t)lrow * F + c);
+            table_row_sum<T, V, D>(a, gb, ge, c, cv, acc);
 #pragma unroll
             for (int i = 0; i < V; ++i) mypart[i] = acc[i];
           }
@@ -339,6 +347,133 @@ __global__ __launch_bounds__(64 * kTableWaves) void table_gather_kernel(TableGat
   }
 }
 
+// ---- distances of a table, and the dot products of its entries -------------------------------------------------------------
+
+struct TableDistArgs {
+  const int32_t *idx;
+  const float *Q, *X;
+  float *dist;
+  int32_t n, k, F, entries;
+};
+
+// One lane per table position p: the chain d2 = fma(q - x, q - x, d2) over c = 0 .. F - 1 cannot be cut without moving
+// bits, so a lane walks both rows, kTableDistLoads loads of each in flight.  V columns a load; the bits do not depend on V.
+template <int V>
+__global__ __launch_bounds__(kTableBlock) void table_dist_kernel(TableDistArgs a) {
+  const int64_t p64 = (int64_t)blockIdx.x * kTableBlock + threadIdx.x;
+  if (p64 >= a.entries) return;
+  const int p = (int)p64, F = a.F;
+  const int j = a.idx[p];
+  if ((unsigned)j >= (unsigned)a.n) {  // names no row: +0.0, and nothing is read through it
+    a.dist[p] = 0.f;
+    return;
+  }
+  const float *q = a.Q + (size_t)(p / a.k) * F, *x = a.X + (size_t)j * F;
+  constexpr int kStep = V * kTableDistLoads;
+  float acc = 0.f;
+  int c = 0;
+  for (; c + kStep <= F; c += kStep) {
+    Cols<V> qv[kTableDistLoads], xv[kTableDistLoads];
+#pragma unroll
+    for (int u = 0; u < kTableDistLoads; ++u) {
+      qv[u] = cols_load<V>(q + c + u * V);
+      xv[u] = cols_load<V>(x + c + u * V);
+    }
+#pragma unroll
+    for (int u = 0; u < kTableDistLoads; ++u)
+#pragma unroll
+      for (int i = 0; i < V; ++i) {
+        const float d = qv[u].v[i] - xv[u].v[i];
+        acc = __builtin_fmaf(d, d, acc);
+      }
+  }
+  for (; c < F; c += V) {
+    const Cols<V> qv = cols_load<V>(q + c), xv = cols_load<V>(x + c);
+#pragma unroll
+    for (int i = 0; i < V; ++i) {
+      const float d = qv.v[i] - xv.v[i];
+      acc = __builtin_fmaf(d, d, acc);
+    }
+  }
+  a.dist[p] = acc;
+}
+
+struct TableDotArgs {
+  const int32_t *idx;
+  const float *A, *a_scale, *B, *C, *D;
+  float *out;
+  int32_t rows, n, k, F;
+  int32_t L, R;  // lanes per table row (a power of two), rows per wave
+};
+
+// out[p] = a_scale[j] <A[j], B[i]> + <C[j], D[i]> for p = (i, s), j = idx[p].  A lane group of L lanes owns table row i;
+// lane l of it owns the columns c0 + l V .. + V - 1 of every pass c0 = 0, L V, 2 L V ..  Per entry a lane runs one fma
+// chain per product over its columns in ascending order, forms t = a_scale[j] * s1 + s2 (each step rounded, no fma) and
+// the group adds the t in the xor butterfly t += t[lane ^ o], o = L / 2 .. 1.  B[i] / D[i] of the first pass stay in
+// registers over the row's entries (every pass where F <= L V); kTableDotBatch gathered rows are in flight per group.
+template <int V, bool TWO>
+__global__ __launch_bounds__(64 * kTableWaves) void table_dot_kernel(TableDotArgs a) {
+  const int t = threadIdx.x, w = t >> 6, lane = t & 63;
+  const int L = a.L, R = a.R, F = a.F, k = a.k;
+  const int sub = lane / L, cl = lane - sub * L;
+  const int64_t row64 = ((int64_t)blockIdx.x * kTableWaves + w) * R + sub;
+  const bool row_on = row64 < a.rows;  // a whole lane group is on or off; an off group computes row 0 and stores nothing
+  const int row = row_on ? (int)row64 : 0;
+  const int step = L * V;
+  const bool one_pass = F <= step;
+  const int cfirst = cl * V;
+  const bool on0 = cfirst < F;
+  const size_t brow = (size_t)row * F;
+  const Cols<V> b0 = cols_load<V>(a.B + brow + (on0 ? cfirst : 0));
+  Cols<V> d0{};
+  if constexpr (TWO) d0 = cols_load<V>(a.D + brow + (on0 ? cfirst : 0));
+  for (int s0 = 0; s0 < k; s0 += kTableDotBatch) {
+    int jv[kTableDotBatch];
+    bool ok[kTableDotBatch];
+    float sc[kTableDotBatch], s1[kTableDotBatch], s2[kTableDotBatch];
+#pragma unroll
+    for (int u = 0; u < kTableDotBatch; ++u) {
+      const int s = s0 + u;
+      const int j = a.idx[(size_t)row * k + (s < k ? s : 0)];
+      ok[u] = s < k && (unsigned)j < (unsigned)a.n;
+      jv[u] = ok[u] ? j : 0;
+      sc[u] = a.a_scale ? a.a_scale[jv[u]] : 1.f;
+      s1[u] = 0.f;
+      s2[u] = 0.f;
+    }
+    for (int c0 = 0; c0 < F; c0 += step) {
+      const int c = c0 + cfirst;
+      const bool on = c < F;
+      const int ce = on ? c : 0;
+      Cols<V> bv = b0, dv = d0;
+      if (!one_pass && c0 > 0) {
+        bv = cols_load<V>(a.B + brow + ce);
+        if constexpr (TWO) dv = cols_load<V>(a.D + brow + ce);
+      }
+      Cols<V> av[kTableDotBatch], cv[kTableDotBatch];
+#pragma unroll
+      for (int u = 0; u < kTableDotBatch; ++u) {
+        av[u] = cols_load<V>(a.A + (size_t)jv[u] * F + ce);
+        if constexpr (TWO) cv[u] = cols_load<V>(a.C + (size_t)jv[u] * F + ce);
+      }
+#pragma unroll
+      for (int u = 0; u < kTableDotBatch; ++u)
+#pragma unroll
+        for (int i = 0; i < V; ++i) {
+          s1[u] = on ? __builtin_fmaf(av[u].v[i], bv.v[i], s1[u]) : s1[u];
+          if constexpr (TWO) s2[u] = on ? __builtin_fmaf(cv[u].v[i], dv.v[i], s2[u]) : s2[u];
+        }
+    }
+#pragma unroll
+    for (int u = 0; u < kTableDotBatch; ++u) {
+      float tt = a.a_scale ? sc[u] * s1[u] : s1[u];
+      if constexpr (TWO) tt = tt + s2[u];
+      for (int o = L >> 1; o >= 1; o >>= 1) tt = tt + __shfl_xor(tt, o, 64);
+      if (row_on && cl == 0 && s0 + u < k) a.out[(size_t)row * k + s0 + u] = ok[u] ? tt : 0.f;
+    }
+  }
+}
+
 int fail(const char *entry, int status, const std::string &msg) {
   set_error(std::string(entry) + ": " + msg);
   return status;
@@ -356,9 +491,9 @@ int gather_refusal(const char *entry, int32_t rows, int32_t k, int32_t n, int32_
   return HG_OK;
 }
 
-template <bool T>
+template <bool T, bool D = false>
 int launch_table_gather(const char *entry, TableGatherArgs a, hipStream_t s) {
-  const bool vec4 = a.F % 4 == 0 && (uintptr_t)a.src % 16 == 0 && (uintptr_t)a.dst % 16 == 0;
+  const bool vec4 = a.F % 4 == 0 && (uintptr_t)a.src % 16 == 0 && (uintptr_t)a.dst % 16 == 0 && (!D || (uintptr_t)a.ctr % 16 == 0);
   const int V = vec4 ? 4 : 1;
   a.L = std::min((a.F + V - 1) / V, 64);
   a.R = 64 / a.L;
@@ -366,8 +501,22 @@ int launch_table_gather(const char *entry, TableGatherArgs a, hipStream_t s) {
   while (a.P2 < a.R * kTableWaves) a.P2 <<= 1;
   const int RW = a.R * kTableWaves;
   const dim3 grid((unsigned)(((int64_t)a.nrows + RW - 1) / RW)), block(64 * kTableWaves);
-  if (vec4) hipLaunchKernelGGL((table_gather_kernel<T, 4>), grid, block, 0, s, a);
-  else hipLaunchKernelGGL((table_gather_kernel<T, 1>), grid, block, 0, s, a);
+  if (vec4) hipLaunchKernelGGL((table_gather_kernel<T, 4, D>), grid, block, 0, s, a);
+  else hipLaunchKernelGGL((table_gather_kernel<T, 1, D>), grid, block, 0, s, a);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail(entry, HG_ERR_HIP, std::string("launch: ") + hipGetErrorString(e));
+  return HG_OK;
+}
+
+// the sizes' refusals of every table entry, in gather_refusal's order
+int size_refusal(const char *entry, int32_t rows, int32_t k, int32_t n, int32_t F) {
+  if (rows < 1 || n < 1 || F < 1) return fail(entry, HG_ERR_INVALID, "rows, n and F must be at least 1");
+  if (k < 1 || k > kTableMaxK) return fail(entry, HG_ERR_INVALID, "k must be in 1 .. 64, got " + std::to_string(k));
+  if ((int64_t)rows * k > INT32_MAX) return fail(entry, HG_ERR_INVALID, "rows * k must be below 2^31");
+  return HG_OK;
+}
+
+int launch_check(const char *entry) {
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail(entry, HG_ERR_HIP, std::string("launch: ") + hipGetErrorString(e));
   return HG_OK;
@@ -473,6 +622,122 @@ int hg_table_gather_t_f32(const int32_t *ptr_v, const int32_t *pos_v, int32_t ro
   a.F = F;
   a.entries = rows * k;
   return launch_table_gather<true>(entry, a, static_cast<hipStream_t>(stream));
+}
+
+int hg_table_gather_diff_f32(const int32_t *idx, int32_t rows, int32_t k, int32_t n, int32_t F, const float *src,
+                             const float *w, const float *src_scale, const float *dst_scale, const float *ctr, float *dst,
+                             hg_stream_t stream) {
+  using namespace hg;
+  const char *entry = "hg_table_gather_diff_f32";
+  if (!idx) return fail(entry, HG_ERR_INVALID, "null idx");
+  if (!ctr) return fail(entry, HG_ERR_INVALID, "null ctr");
+  if (const int st = gather_refusal(entry, rows, k, n, F, src, w, src_scale, dst_scale, dst)) return st;
+  if ((uintptr_t)idx % 4 || (uintptr_t)ctr % 4) return fail(entry, HG_ERR_UNSUPPORTED, "idx and ctr must be 4-byte aligned");
+  TableGatherArgs a{};
+  a.idx = idx;
+  a.src = src;
+  a.w = w;
+  a.src_scale = src_scale;
+  a.dst_scale = dst_scale;
+  a.ctr = ctr;
+  a.dst = dst;
+  a.nrows = rows;
+  a.nsrc = n;
+  a.k = k;
+  a.F = F;
+  a.entries = rows * k;
+  return launch_table_gather<false, true>(entry, a, static_cast<hipStream_t>(stream));
+}
+
+int hg_table_gather_t_diff_f32(const int32_t *ptr_v, const int32_t *pos_v, int32_t rows, int32_t k, int32_t n, int32_t F,
+                               const float *src, const float *w, const float *src_scale, const float *dst_scale,
+                               const float *ctr, float *dst, hg_stream_t stream) {
+  using namespace hg;
+  const char *entry = "hg_table_gather_t_diff_f32";
+  if (!ptr_v || !pos_v) return fail(entry, HG_ERR_INVALID, "null ptr_v or pos_v");
+  if (!ctr) return fail(entry, HG_ERR_INVALID, "null ctr");
+  if (const int st = gather_refusal(entry, rows, k, n, F, src, w, src_scale, dst_scale, dst)) return st;
+  if ((uintptr_t)ptr_v % 4 || (uintptr_t)pos_v % 4 || (uintptr_t)ctr % 4)
+    return fail(entry, HG_ERR_UNSUPPORTED, "ptr_v, pos_v and ctr must be 4-byte aligned");
+  TableGatherArgs a{};
+  a.ptr_v = ptr_v;
+  a.pos_v = pos_v;
+  a.src = src;
+  a.w = w;
+  a.src_scale = src_scale;
+  a.dst_scale = dst_scale;
+  a.ctr = ctr;
+  a.dst = dst;
+  a.nrows = n;
+  a.nsrc = rows;
+  a.k = k;
+  a.F = F;
+  a.entries = rows * k;
+  return launch_table_gather<true, true>(entry, a, static_cast<hipStream_t>(stream));
+}
+
+int hg_table_dist_f32(const int32_t *idx, int32_t rows, int32_t k, int32_t n, int32_t F, const float *Q, const float *X,
+                      float *dist, hg_stream_t stream) {
+  using namespace hg;
+  const char *entry = "hg_table_dist_f32";
+  if (!idx || !Q || !X || !dist) return fail(entry, HG_ERR_INVALID, "null idx, Q, X or dist");
+  if (const int st = size_refusal(entry, rows, k, n, F)) return st;
+  for (const void *p : {(const void *)idx, (const void *)Q, (const void *)X, (const void *)dist})
+    if ((uintptr_t)p % 4) return fail(entry, HG_ERR_UNSUPPORTED, "idx, Q, X and dist must be 4-byte aligned");
+  TableDistArgs a{};
+  a.idx = idx;
+  a.Q = Q;
+  a.X = X;
+  a.dist = dist;
+  a.n = n;
+  a.k = k;
+  a.F = F;
+  a.entries = rows * k;
+  const bool vec4 = F % 4 == 0 && (uintptr_t)Q % 16 == 0 && (uintptr_t)X % 16 == 0;
+  const dim3 grid((unsigned)(((int64_t)a.entries + kTableBlock - 1) / kTableBlock)), block(kTableBlock);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (vec4) hipLaunchKernelGGL(table_dist_kernel<4>, grid, block, 0, s, a);
+  else hipLaunchKernelGGL(table_dist_kernel<1>, grid, block, 0, s, a);
+  return launch_check(entry);
+}
+
+int hg_table_dot_f32(const int32_t *idx, int32_t rows, int32_t k, int32_t n, int32_t F, const float *A, const float *a_scale,
+                     const float *B, const float *C, const float *D, float *out, hg_stream_t stream) {
+  using namespace hg;
+  const char *entry = "hg_table_dot_f32";
+  if (!idx) return fail(entry, HG_ERR_INVALID, "null idx");
+  if (!A || !B || !out) return fail(entry, HG_ERR_INVALID, "null A, B or out");
+  if (!C != !D) return fail(entry, HG_ERR_INVALID, "C and D must both be given or both be null");
+  if (const int st = size_refusal(entry, rows, k, n, F)) return st;
+  for (const void *p : {(const void *)idx, (const void *)A, (const void *)a_scale, (const void *)B, (const void *)C,
+                        (const void *)D, (const void *)out})
+    if ((uintptr_t)p % 4) return fail(entry, HG_ERR_UNSUPPORTED, "idx, A, a_scale, B, C, D and out must be 4-byte aligned");
+  TableDotArgs a{};
+  a.idx = idx;
+  a.A = A;
+  a.a_scale = a_scale;
+  a.B = B;
+  a.C = C;
+  a.D = D;
+  a.out = out;
+  a.rows = rows;
+  a.n = n;
+  a.k = k;
+  a.F = F;
+  bool vec4 = F % 4 == 0;
+  for (const void *p : {(const void *)A, (const void *)B, (const void *)C, (const void *)D}) vec4 = vec4 && (uintptr_t)p % 16 == 0;
+  const int V = vec4 ? 4 : 1;
+  a.L = 1;
+  while (a.L < std::min((F + V - 1) / V, 64)) a.L <<= 1;
+  a.R = 64 / a.L;
+  const int RW = a.R * kTableWaves;
+  const dim3 grid((unsigned)(((int64_t)rows + RW - 1) / RW)), block(64 * kTableWaves);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (vec4 && C) hipLaunchKernelGGL((table_dot_kernel<4, true>), grid, block, 0, s, a);
+  else if (vec4) hipLaunchKernelGGL((table_dot_kernel<4, false>), grid, block, 0, s, a);
+  else if (C) hipLaunchKernelGGL((table_dot_kernel<1, true>), grid, block, 0, s, a);
+  else hipLaunchKernelGGL((table_dot_kernel<1, false>), grid, block, 0, s, a);
+  return launch_check(entry);
 }
 
 }  // extern "C"

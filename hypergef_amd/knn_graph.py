@@ -7,6 +7,8 @@ host-side layout step of `HyperGraph.from_knn`.
 
 `knn_transpose` and `knn_aggr` (`ops.knn_transpose` / `ops.knn_aggr`; hg_table_* in include/hg_aggr.h) aggregate over the
 neighbour table itself, with no plan and no host step, and `KnnHypergraph` is the device-only hypergraph they serve.
+`knn_dist` (`ops.knn_dist`) gives a table's distances with a gradient, and `knn_aggr(weight_grad=True)` the gradient of its
+weights: together they train through the weights of a probabilistic kNN hypergraph.
 """
 import ctypes
 import numbers
@@ -225,10 +227,11 @@ def _flat_or_none(t, name, count, dev):
     return t
 
 
-def table_gather(idx, src, w=None, src_scale=None, dst_scale=None):
+def table_gather(idx, src, w=None, src_scale=None, dst_scale=None, ctr=None):
     """dst[i] = dst_scale[i] * sum_s (src[idx[i, s]] * src_scale[idx[i, s]]) * w[i * k + s] over a table idx [rows, k] and rows
     src [n, F]: hg_table_gather_f32, every row summed in ascending s.  Any of w [rows * k], src_scale [n], dst_scale [rows]
-    may be None (no multiplication).  An entry outside 0 .. n - 1 adds nothing.  No gradient."""
+    may be None (no multiplication).  An entry outside 0 .. n - 1 adds nothing.  No gradient.
+    ctr [rows, F]: the difference gather hg_table_gather_diff_f32 -- the term starts from ctr[i] - src[idx[i, s]]."""
     _table_shape(idx)
     rows, k = _table_shape_values(idx)
     _check_table_index(idx, "idx")
@@ -240,18 +243,24 @@ def table_gather(idx, src, w=None, src_scale=None, dst_scale=None):
     w = _flat_or_none(w, "w", rows * k, dev)
     src_scale = _flat_or_none(src_scale, "src_scale", n, dev)
     dst_scale = _flat_or_none(dst_scale, "dst_scale", rows, dev)
+    ctr = _flat_or_none(ctr, "ctr", rows * F, dev)
     dst = torch.empty((rows, F), dtype=torch.float32, device=dev)
     with torch.cuda.device(dev):
-        _lib.check(_lib.lib().hg_table_gather_f32(_ptr(idx), rows, k, n, F, _ptr(src), _ptr(w), _ptr(src_scale),
-                                                  _ptr(dst_scale), _ptr(dst), _stream_handle(dev)))
+        if ctr is None:
+            _lib.check(_lib.lib().hg_table_gather_f32(_ptr(idx), rows, k, n, F, _ptr(src), _ptr(w), _ptr(src_scale),
+                                                      _ptr(dst_scale), _ptr(dst), _stream_handle(dev)))
+        else:
+            _lib.check(_lib.lib().hg_table_gather_diff_f32(_ptr(idx), rows, k, n, F, _ptr(src), _ptr(w), _ptr(src_scale),
+                                                           _ptr(dst_scale), _ptr(ctr), _ptr(dst), _stream_handle(dev)))
     return dst
 
 
-def table_gather_t(ptr_v, pos_v, k, src, w=None, src_scale=None, dst_scale=None):
+def table_gather_t(ptr_v, pos_v, k, src, w=None, src_scale=None, dst_scale=None, ctr=None):
     """dst[v] = dst_scale[v] * sum_q (src[pos_v[q] // k] * src_scale[pos_v[q] // k]) * w[pos_v[q]], q over ptr_v[v] ..
     ptr_v[v + 1] - 1, for the transpose (ptr_v [n + 1], pos_v [rows * k]) of a table of k columns and rows src [rows, F]:
     hg_table_gather_t_f32.  A row of at most TABLE_SEQ_MAX entries is summed in ascending q; a longer one by its whole
-    workgroup in an order fixed by its length and F.  A vertex with no entry is +0.0 whatever dst_scale.  No gradient."""
+    workgroup in an order fixed by its length and F.  A vertex with no entry is +0.0 whatever dst_scale.  No gradient.
+    ctr [n, F]: the difference gather hg_table_gather_t_diff_f32 -- the term starts from ctr[v] - src[pos_v[q] // k]."""
     for name, t in (("ptr_v", ptr_v), ("pos_v", pos_v)):
         if not isinstance(t, torch.Tensor) or t.dtype != torch.int32:
             raise TypeError("%s must be an int32 tensor, got %s" % (name, getattr(t, "dtype", type(t))))
@@ -270,11 +279,128 @@ def table_gather_t(ptr_v, pos_v, k, src, w=None, src_scale=None, dst_scale=None)
     w = _flat_or_none(w, "w", rows * int(k), dev)
     src_scale = _flat_or_none(src_scale, "src_scale", rows, dev)
     dst_scale = _flat_or_none(dst_scale, "dst_scale", n, dev)
+    ctr = _flat_or_none(ctr, "ctr", n * F, dev)
     dst = torch.empty((n, F), dtype=torch.float32, device=dev)
     with torch.cuda.device(dev):
-        _lib.check(_lib.lib().hg_table_gather_t_f32(_ptr(ptr_v), _ptr(pos_v), rows, int(k), n, F, _ptr(src), _ptr(w),
-                                                    _ptr(src_scale), _ptr(dst_scale), _ptr(dst), _stream_handle(dev)))
+        if ctr is None:
+            _lib.check(_lib.lib().hg_table_gather_t_f32(_ptr(ptr_v), _ptr(pos_v), rows, int(k), n, F, _ptr(src), _ptr(w),
+                                                        _ptr(src_scale), _ptr(dst_scale), _ptr(dst), _stream_handle(dev)))
+        else:
+            _lib.check(_lib.lib().hg_table_gather_t_diff_f32(_ptr(ptr_v), _ptr(pos_v), rows, int(k), n, F, _ptr(src), _ptr(w),
+                                                             _ptr(src_scale), _ptr(dst_scale), _ptr(ctr), _ptr(dst),
+                                                             _stream_handle(dev)))
     return dst
+
+
+def table_dot(idx, A, B, a_scale=None, C=None, D=None):
+    """out[i * k + s] = a_scale[j] * <A[j], B[i]> + <C[j], D[i]>, j = idx[i, s], over a table idx [rows, k]: hg_table_dot_f32,
+    one launch and no [rows * k, F] array.  A, C [n, F]; B, D [rows, F]; a_scale [n] or None; C and D both or neither.  An
+    entry outside 0 .. n - 1 gives +0.0.  The order of the sum is include/hg_aggr.h's DOT ORDER.  No gradient."""
+    _table_shape(idx)
+    rows, k = _table_shape_values(idx)
+    _check_table_index(idx, "idx")
+    dev = idx.device
+    if (C is None) != (D is None):
+        raise ValueError("C and D must both be given or both be None")
+    _check_feat(A, "A", device=dev)
+    if A.dim() != 2 or A.shape[0] < 1 or A.shape[1] < 1:
+        raise ValueError("A must be [n >= 1, F >= 1], got %s" % (tuple(A.shape),))
+    n, F = A.shape
+    for name, t, shape in (("B", B, (rows, F)), ("C", C, (n, F)), ("D", D, (rows, F))):
+        if t is not None:
+            _check_feat(t, name, device=dev)
+            if tuple(t.shape) != shape:
+                raise ValueError("%s must be [%d, %d], got %s" % (name, shape[0], shape[1], tuple(t.shape)))
+    a_scale = _flat_or_none(a_scale, "a_scale", n, dev)
+    out = torch.empty(rows * k, dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().hg_table_dot_f32(_ptr(idx), rows, k, n, F, _ptr(A), _ptr(a_scale), _ptr(B), _ptr(C), _ptr(D),
+                                               _ptr(out), _stream_handle(dev)))
+    return out
+
+
+class _KnnDist(torch.autograd.Function):
+    """dist[i, s] = |Q[i] - X[idx[i, s]]|^2 over a fixed table; the gradients are the two difference gathers with g = 2 dDist.
+    Saves the table, its transpose and the inputs X and Q -- nothing new of rows * k * F elements."""
+
+    @staticmethod
+    def forward(ctx, X, Q, idx, ptr_v, pos_v):
+        rows, k = idx.shape
+        n, F = X.shape
+        Qr = X if Q is None else Q
+        dist = torch.empty((rows, k), dtype=torch.float32, device=X.device)
+        with torch.cuda.device(X.device):
+            _lib.check(_lib.lib().hg_table_dist_f32(_ptr(idx), rows, k, n, F, _ptr(Qr), _ptr(X), _ptr(dist),
+                                                    _stream_handle(X.device)))
+        ctx.same = Q is None
+        ctx.save_for_backward(X, Qr, idx, ptr_v, pos_v)
+        return dist
+
+    @staticmethod
+    def backward(ctx, dDist):
+        X, Q, idx, ptr_v, pos_v = ctx.saved_tensors
+        g = (dDist * 2.0).contiguous()  # exact: the factor of d (q - x)^2 folded into the weight
+        dX = dQ = None
+        if ctx.needs_input_grad[0]:
+            dX = table_gather_t(ptr_v, pos_v, idx.shape[1], Q, g, ctr=X)
+        if ctx.same:
+            if ctx.needs_input_grad[0]:
+                dX = dX + table_gather(idx, X, g, ctr=X)
+        elif ctx.needs_input_grad[1]:
+            dQ = table_gather(idx, X, g, ctr=Q)
+        return dX, dQ, None, None, None
+
+
+def knn_dist(idx, X, queries=None, transpose=None):
+    """The squared distances of a GIVEN neighbour table, differentiable: dist float32 [rows, k] with dist[i, s] =
+    sum_c (Q[i, c] - X[idx[i, s], c])^2, Q = `queries` [rows, F] or X itself (None; then rows = n).  The sum runs in ops.knn's
+    order (include/hg_aggr.h, hg_table_dist_f32), so for the idx that ops.knn(X, k) returned -- under either form, with
+    self_first, with queries -- it is the dist ops.knn returned, bit for bit.  An entry of idx outside 0 .. n - 1 gives +0.0.
+    The search stays non-differentiable; over a fixed table this is the true gradient wherever the selection does not
+    change (almost everywhere):  with g = 2 dDist, dQ[i] = sum_s (Q[i] - X[idx[i, s]]) g[i, s] and dX[j] =
+    sum_{(i, s): idx[i, s] = j} (X[j] - Q[i]) g[i, s] -- the difference gathers hg_table_gather_diff_f32 /
+    hg_table_gather_t_diff_f32, in the gathers' documented order, no atomics: two calls give the same bits, and identical
+    rows (every self_first entry) contribute exactly 0.  With queries None the two are added with one torch add.
+    transpose: the (ptr_v, pos_v) of ops.knn_transpose(idx, n) to reuse; computed when X needs a gradient and it is None.
+    float32 only.  Refusals, in this order and before a device is touched: TypeError for an idx (ptr_v, pos_v) that is not
+    int32 and an X or queries that is not float32; ValueError for the shapes and k; RuntimeError for CPU tensors."""
+    _table_shape(idx)
+    for name, t in (("X", X), ("queries", queries)):
+        if t is None and name == "queries":
+            continue
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32:
+            raise TypeError("%s must be a float32 tensor (knn_dist has no bfloat16 / float16 / float64 form), got %s"
+                            % (name, getattr(t, "dtype", type(t))))
+    if transpose is not None:
+        if not isinstance(transpose, (tuple, list)) or len(transpose) != 2:
+            raise TypeError("transpose must be the pair (ptr_v, pos_v) of knn_transpose")
+        for name, t in zip(("ptr_v", "pos_v"), transpose):
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.int32:
+                raise TypeError("transpose's %s must be an int32 tensor, got %s" % (name, getattr(t, "dtype", type(t))))
+    rows, k = _table_shape_values(idx)
+    if X.dim() != 2 or X.shape[0] < 1 or X.shape[1] < 1:
+        raise ValueError("X must be [n >= 1, F >= 1], got %s" % (tuple(X.shape),))
+    n, F = X.shape
+    if queries is None:
+        if rows != n:
+            raise ValueError("without queries idx must have one row per row of X: %d rows, X has %d" % (rows, n))
+    elif tuple(queries.shape) != (rows, F):
+        raise ValueError("queries must be [rows, F] = [%d, %d], got %s" % (rows, F, tuple(queries.shape)))
+    if transpose is not None and (tuple(transpose[0].shape) != (n + 1,) or tuple(transpose[1].shape) != (rows * k,)):
+        raise ValueError("transpose must be (ptr_v [%d], pos_v [%d]), got %s and %s"
+                         % (n + 1, rows * k, tuple(transpose[0].shape), tuple(transpose[1].shape)))
+    _check_table_index(idx, "idx")
+    _check_feat(X, "X", device=idx.device)
+    if queries is not None:
+        _check_feat(queries, "queries", device=idx.device)
+    ptr_v = pos_v = None
+    if torch.is_grad_enabled() and X.requires_grad:
+        if transpose is None:
+            transpose = knn_transpose(idx, n)
+        ptr_v, pos_v = transpose
+        _check_table_index(ptr_v, "ptr_v")
+        _check_table_index(pos_v, "pos_v")
+    return _KnnDist.apply(X, queries, idx, ptr_v, pos_v)
 
 
 class _KnnAggr(torch.autograd.Function):
@@ -297,7 +423,32 @@ class _KnnAggr(torch.autograd.Function):
         return dX, None, None, None, None, None, None
 
 
-def knn_aggr(idx, X, weight=None, degE=None, degV=None, transpose=None):
+class _KnnAggrWeighted(torch.autograd.Function):
+    """_KnnAggr with the gradient of the weight: dw[p = (i, s)] = degV[v] <dY[v], Xe[i]> + <X[v], G[i]>, v = idx[i, s], one
+    launch of hg_table_dot_f32.  Xe is computed again in the backward; what is saved beyond _KnnAggr's is the input X."""
+
+    @staticmethod
+    def forward(ctx, X, w, idx, ptr_v, pos_v, degE, degV):
+        k = idx.shape[1]
+        Xe = table_gather(idx, X, w, None, degE)
+        Y = table_gather_t(ptr_v, pos_v, k, Xe, w, None, degV)
+        ctx.save_for_backward(X, w, idx, ptr_v, pos_v, degE, degV)
+        return Y
+
+    @staticmethod
+    def backward(ctx, dY):
+        X, w, idx, ptr_v, pos_v, degE, degV = ctx.saved_tensors
+        dY = dY.contiguous()
+        G = table_gather(idx, dY, w, degV, degE)
+        dX = table_gather_t(ptr_v, pos_v, idx.shape[1], G, w) if ctx.needs_input_grad[0] else None
+        dw = None
+        if ctx.needs_input_grad[1]:
+            Xe = table_gather(idx, X, w, None, degE)
+            dw = table_dot(idx, dY, Xe, degV, X, G).view(w.shape)
+        return dX, dw, None, None, None, None, None
+
+
+def knn_aggr(idx, X, weight=None, degE=None, degV=None, transpose=None, weight_grad=False):
     """Y = degV . H_w (degE . (H_w^T X)) over the hypergraph of a neighbour table idx [rows, k] (int32, ops.knn's: hyperedge
     i = the vertices idx[i, :]) and features X [n, F] (float32), with no plan and no host step: two launches of the table
     gathers (include/hg_aggr.h, hg_table_gather_f32 / hg_table_gather_t_f32) and, where `transpose` is None, the transpose.
@@ -307,6 +458,10 @@ def knn_aggr(idx, X, weight=None, degE=None, degV=None, transpose=None):
     to reuse.  The gradient of X is exact: G = table_gather(dY, src_scale=degV, dst_scale=degE, w), dX = table_gather_t(G,
     w).  weight, degE and degV get no gradient -- kNN weights come from detached distances -- and one that requires a
     gradient is refused.  Deterministic: the order of every sum is hg_aggr.h's, two calls give the same bits.
+    weight_grad=True: `weight` may require a gradient (degE and degV are still refused), and gets
+    dw[p = (i, s)] = degV[v] <dY[v], Xe[i]> + <X[v], G[i]>, v = idx[i, s], Xe = table_gather(X, w, dst_scale=degE) computed
+    again in the backward -- one launch of hg_table_dot_f32, no [rows * k, F] array, no atomics.  Y and dX keep the bits of
+    the default call; the backward then also keeps X, an input.
     Refusals, in this order and before a device is touched: TypeError for an idx (ptr_v, pos_v) that is not int32 and for
     an X, weight, degE or degV that is not float32; ValueError for the shapes and k; RuntimeError for a weight, degE or
     degV that requires a gradient, and for CPU tensors."""
@@ -338,7 +493,7 @@ def knn_aggr(idx, X, weight=None, degE=None, degV=None, transpose=None):
                          % (n + 1, rows * k, tuple(transpose[0].shape), tuple(transpose[1].shape)))
     if torch.is_grad_enabled():
         for name, t in scales:
-            if t is not None and t.requires_grad:
+            if t is not None and t.requires_grad and not (weight_grad and name == "weight"):
                 raise RuntimeError("%s gets no gradient from knn_aggr: pass %s.detach()" % (name, name))
     _check_table_index(idx, "idx")
     _check_feat(X, "X", device=idx.device)
@@ -351,6 +506,8 @@ def knn_aggr(idx, X, weight=None, degE=None, degV=None, transpose=None):
     _check_table_index(ptr_v, "ptr_v")
     _check_table_index(pos_v, "pos_v")
     detach = [None if t is None else t.detach() for _, t in scales]
+    if weight_grad and weight is not None and weight.requires_grad and torch.is_grad_enabled():
+        return _KnnAggrWeighted.apply(X, weight, idx, ptr_v, pos_v, *detach[1:])
     return _KnnAggr.apply(X, idx, ptr_v, pos_v, *detach)
 
 
@@ -361,8 +518,11 @@ class KnnHypergraph:
       idx [N, k], dist [N, k] (squared), mean [N]: ops.knn(X, k, self_first=True, return_mean=True)
       ptr_v [N + 1], pos_v [N k]: ops.knn_transpose(idx)
       degE [N, 1] = 1 / k and degV [N, 1] = in-degree^-1/2, 1 where no hyperedge names the vertex (HyperGraph's formulas)
-      weights(m_prob): HGNN's exp(-d2 / (m_prob mean)^2) entries [N k]
-      aggregate(Z, probabilistic=False, m_prob=1.0): ops.knn_aggr over the table.
+      weights(m_prob, X=None): HGNN's exp(-d2 / (m_prob mean)^2) entries [N k].  With X (the rows the table was built
+        from, attached to the graph) d2 is ops.knn_dist(idx, X) -- the same bits as `dist`, with a gradient into X; `mean`
+        stays detached: its gradient is an N x N sum and HGNN treats avg_dis as a constant of the construction.
+      aggregate(Z, probabilistic=False, m_prob=1.0, X=None): ops.knn_aggr over the table; X goes to weights, and the
+        weights then get their gradient (weight_grad=True).
     form: ops.knn's -- "dot" gives the same idx and dist through the matrix-unit prefilter, and its own mean."""
 
     @classmethod
@@ -380,12 +540,14 @@ class KnnHypergraph:
         self.degV = torch.where(deg > 0, deg.pow(-0.5), torch.ones_like(deg))
         return self
 
-    def weights(self, m_prob=1.0):
-        return knn_incidence_weights(self.dist, self.mean, m_prob)
+    def weights(self, m_prob=1.0, X=None):
+        if X is None:
+            return knn_incidence_weights(self.dist, self.mean, m_prob)
+        return knn_incidence_weights(knn_dist(self.idx, X, transpose=(self.ptr_v, self.pos_v)), self.mean, m_prob)
 
-    def aggregate(self, Z, probabilistic=False, m_prob=1.0):
-        w = self.weights(m_prob) if probabilistic else None
-        return knn_aggr(self.idx, Z, w, self.degE, self.degV, transpose=(self.ptr_v, self.pos_v))
+    def aggregate(self, Z, probabilistic=False, m_prob=1.0, X=None):
+        w = self.weights(m_prob, X) if probabilistic else None
+        return knn_aggr(self.idx, Z, w, self.degE, self.degV, transpose=(self.ptr_v, self.pos_v), weight_grad=X is not None)
 
 
 def table_seq_max():

@@ -148,13 +148,23 @@ class DynamicHypergraphConv(nn.Module):
     torch, so the layer can be recorded into a hipGraph (torch.cuda.graph) and the neighbours are searched again on every
     replay.  With segments, ops.knn still waits once for its offsets: such a layer runs eagerly only.  False (the default)
     is the layer above, untouched.  knn_form: ops.knn's `form` -- "dot" searches the same neighbours through the
-    matrix-unit prefilter (no segments); with probabilistic=True the weights then use the dot form's mean."""
+    matrix-unit prefilter (no segments); with probabilistic=True the weights then use the dot form's mean.
+    learn_distances=True (needs probabilistic=True and device_graph=True): the weights exp(-d2 / (m_prob mean)^2) are
+    differentiated through d2 = ops.knn_dist(idx, X), so the gradient of X gains the path through the weights of both hops
+    -- what a learnable metric needs.  The output keeps its bits; the table is still searched on detached rows (the
+    selection has no gradient) and `mean` is a constant of the construction.  No parameter is added, the layer still
+    waits nowhere with segments=None and is still recorded into a hipGraph.  False (the default) is the layer above, bit for
+    bit, with the same saved tensors."""
 
     def __init__(self, in_channels, out_channels, k, probabilistic=False, segments=None, m_prob=1.0, options=None,
-                 device_graph=False, knn_form="difference"):
+                 device_graph=False, knn_form="difference", learn_distances=False):
         super().__init__()
         if not isinstance(k, int) or not 1 <= k <= 64:
             raise ValueError("k must be an integer in 1 .. 64, got %r" % (k,))
+        if learn_distances and not (probabilistic and device_graph):
+            raise ValueError("learn_distances=True needs probabilistic=True (the distances only enter the weights) and "
+                             "device_graph=True (ops.knn_dist and the weight gradient run over the device table)")
+        self.learn_distances = bool(learn_distances)
         self.options = options
         self.lin = ops.Linear(in_channels, out_channels, bias=False, options=options)
         self.in_channels, self.out_channels, self.k = in_channels, out_channels, k
@@ -167,6 +177,8 @@ class DynamicHypergraphConv(nn.Module):
         if self.device_graph:
             from .knn_graph import KnnHypergraph
             hyperg = self.hyperg = KnnHypergraph.build(X, self.k, segments=self.segments, form=self.knn_form)
+            if self.learn_distances:
+                return hyperg.aggregate(self.lin(X), True, self.m_prob, X=X)
             return hyperg.aggregate(self.lin(X), probabilistic=self.probabilistic, m_prob=self.m_prob)
         from .hypergraph import HyperGraph
         hyperg = self.hyperg = HyperGraph.from_knn(X.detach(), self.k, X.device, segments=self.segments, form=self.knn_form)

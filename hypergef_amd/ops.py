@@ -23,7 +23,7 @@ import torch
 
 from . import _lib
 from .knn_graph import knn, knn_incidence_weights  # noqa: F401  (ops.knn / ops.knn_incidence_weights)
-from .knn_graph import knn_aggr, knn_transpose  # noqa: F401  (ops.knn_aggr / ops.knn_transpose: no plan, no host step)
+from .knn_graph import knn_aggr, knn_dist, knn_transpose  # noqa: F401  (ops.knn_aggr / ops.knn_transpose: no plan, no host step)
 from .plan import (cached_plan, linear_bf16_fusion_pays, linear_fusion_pays, linear_rows, linear_supported, linear_wgrad,
                    wgrad_supported, _check_feat, _check_index, _ptr, _rng_state_device, _rng_state_dtype,
                    _rng_state_length, _stream_handle)

@@ -927,6 +927,52 @@ HG_API int hg_table_gather_t_f32(const int32_t *ptr_v, const int32_t *pos_v, int
                                  const float *src, const float *w, const float *src_scale, const float *dst_scale,
                                  float *dst, hg_stream_t stream);
 
+/* Training through the weights of a neighbour table (csrc/hg_table.hip): the distances of a given table, the two
+ * "difference gathers" that are their gradient, and the dot products that are the gradient of the table's weights.  Like
+ * the entries above, each launches once on `stream`, allocates and waits for nothing and can be recorded into a hipGraph;
+ * float32 only; no floating-point atomics, so two calls give the same bits.
+ *
+ * hg_table_dist_f32: dist[i, s] = d2(i, idx[i, s]) = sum_c (Q[i, c] - X[idx[i, s], c])^2 for Q [rows, F], X [n, F],
+ *   dist [rows, k], in hg_knn_f32's arithmetic (its d2(i, j) paragraph above): the difference form, c = 0 .. F - 1 in that
+ *   order, one accumulator from +0.0, the difference rounded and then one explicit fma.  So for the idx that hg_knn_f32 or
+ *   hg_knn_dot_f32 returned, dist is the dist they returned, BIT FOR BIT, under self_first too; identical rows give +0.0.
+ *   The bits depend on the two rows alone -- not on F % 4, the alignment or the launch.  An entry of idx outside 0 .. n - 1
+ *   gives +0.0 and is not read through.
+ * hg_table_gather_diff_f32 / hg_table_gather_t_diff_f32: hg_table_gather_f32 / hg_table_gather_t_f32 with a centre row,
+ *   dst[r] = dst_scale[r] * sum_entries term(p, j),   term(p, j) = ((ctr[r] - src[j]) * src_scale[j]) * w[p],
+ *   ctr [destination rows, F] (never NULL): the subtraction and every multiplication are rounded on their own, and the term
+ *   is added with one rounded add (no fma).  Everything else is the plain gathers': which entries a row has, the absent
+ *   factors, the +0.0 of an empty row, the ignored entries, and the ORDER paragraph above word for word, with c = 4 only
+ *   where ctr is 16-byte aligned as well.  A source row equal to the centre contributes exactly 0.
+ *   With g = 2 dDist these are the gradients of hg_table_dist_f32: dQ = gather_diff(idx; ctr = Q, src = X, w = g) and
+ *   dX = gather_t_diff(ptr_v, pos_v; ctr = X, src = Q, w = g).
+ * hg_table_dot_f32: out[p] = a_scale[j] * <A[j], B[i]> + <C[j], D[i]> for every position p = i k + s, j = idx[p]; A, C
+ *   [n, F], B, D [rows, F], a_scale [n], out [rows * k].  a_scale may be NULL (no multiplication); C and D are both NULL
+ *   (no second product and no addition) or both given.  An entry outside 0 .. n - 1 writes +0.0 and is not read through.
+ *   DOT ORDER: c = 4 columns a lane where F % 4 == 0 and A, B, C and D are 16-byte aligned, else 1; L = the power of two
+ *   at or above min(ceil(F / c), 64) lanes share a position.  Lane l owns the columns m L c + l c .. m L c + l c + c - 1
+ *   below F, m = 0, 1 ..; over them, ascending, it runs s1 = fma(A[j, x], B[i, x], s1) and s2 = fma(C[j, x], D[i, x], s2),
+ *   each from +0.0, and forms t[l] = a_scale[j] * s1 + s2 (the product rounded, then one rounded add; no fma).  Then
+ *   t[l] = t[l] + t[l xor o] for o = L / 2, L / 4 .. 1, every lane at once, and out[p] = t[0].  So the bits of out[p] depend
+ *   on the two pairs of rows, a_scale[j], F and the alignment alone -- not on k, the launch or where the row stands.
+ *   With Xe = gather(idx, X, w, NULL, degE) and G = gather(idx, dY, w, degV, degE), the gradient of the weights of
+ *   Y = degV . H_w (degE . (H_w^T X)) is dw = hg_table_dot_f32(A = dY, a_scale = degV, B = Xe, C = X, D = G).
+ * Refusals launch nothing, set hg_last_error, in gather_refusal's order: HG_ERR_INVALID for a null idx (ptr_v, pos_v), then
+ *   a null ctr (the difference gathers), a null src or dst / Q, X or dist / A, B or out, C without D or D without C; for
+ *   rows, n or F < 1, k outside 1 .. 64, rows * k >= 2^31; then HG_ERR_UNSUPPORTED for a pointer that is not 4-byte
+ *   aligned. */
+HG_API int hg_table_dist_f32(const int32_t *idx, int32_t rows, int32_t k, int32_t n, int32_t F, const float *Q, const float *X,
+                             float *dist, hg_stream_t stream);
+HG_API int hg_table_gather_diff_f32(const int32_t *idx, int32_t rows, int32_t k, int32_t n, int32_t F, const float *src,
+                                    const float *w, const float *src_scale, const float *dst_scale, const float *ctr,
+                                    float *dst, hg_stream_t stream);
+HG_API int hg_table_gather_t_diff_f32(const int32_t *ptr_v, const int32_t *pos_v, int32_t rows, int32_t k, int32_t n,
+                                      int32_t F, const float *src, const float *w, const float *src_scale,
+                                      const float *dst_scale, const float *ctr, float *dst, hg_stream_t stream);
+HG_API int hg_table_dot_f32(const int32_t *idx, int32_t rows, int32_t k, int32_t n, int32_t F, const float *A,
+                            const float *a_scale, const float *B, const float *C, const float *D, float *out,
+                            hg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
