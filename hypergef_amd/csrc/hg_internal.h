@@ -213,6 +213,11 @@ struct Opts {
 };
 
 void set_error(const std::string &msg);
+// a refusal of the C entry `entry`: the message is "<entry>: <msg>", the return value `status`
+inline int fail(const char *entry, int status, const std::string &msg) {
+  set_error(std::string(entry) + ": " + msg);
+  return status;
+}
 
 // Host algorithms (hg_schedule.cpp); all validate and return hg_status.
 int balance_schedule(int32_t nrow, int32_t ngs, const int32_t *csrptr,

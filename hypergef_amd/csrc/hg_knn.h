@@ -59,4 +59,16 @@ KnnDotLayout knn_dot_layout(int64_t nq, int64_t n, int k, int slices);
 // Every other value is clipped to the number of candidate tiles (a slice without a tile has nothing to list).
 int knn_dot_slices(int64_t nq, int64_t n, int cand_slices);
 
+// The arguments hg_knn_f32 and hg_knn_dot_f32 have in common, and what both refuse about them (hg_knn.hip).
+struct KnnCall {
+  const char *entry;
+  const void *Q, *X, *idx, *dist;
+  int32_t nq, n, F, k, self_first, cand_slices;
+};
+// The sizes a *_workspace_bytes entry answers for (max_F: the entry's widest row, 0: no limit); it returns 0 for the others.
+bool knn_sizes_ok(int32_t nq, int32_t n, int32_t F, int32_t k, int32_t cand_slices, int32_t max_F);
+// The refusals up to the entry's own alignment check, in the order include/hg_aggr.h gives: HG_OK, or the status with the
+// error set.  max_F: as above, refused where the dot entry refuses it; seg / B: the difference entry's segments (null: none).
+int knn_refusal(const KnnCall &c, int32_t max_F, const int32_t *seg, int32_t B);
+
 }  // namespace hg

@@ -11,8 +11,9 @@
 // candidates 4 tx .. 4 tx + 3 and 128 + 4 tx .. 128 + 4 tx + 3 of the tile: the 256 candidates of a query row sit in the
 // 32 lanes of one half wave.  Those 32 lanes also hold the row's best-k list, sorted, slot s in lane s % 32: an offer
 // is one compare against the row's k-th distance (kept in every lane); the rare survivor is inserted by the half wave
-// with one shift by a lane.  The other slices' lists go to the workspace and knn_merge_kernel ranks every entry of a
-// row's lists against the others under the same order.
+// with one shift by a lane (list_offer<KS, 32>).  The other slices' lists go to the workspace and knn_merge_kernel ranks
+// every entry of a row's lists against the others under the same order (merged_rank).  The list and the rank are
+// hg_knn_list.h's, shared with hg_knn_dot.hip.
 #include <hip/hip_runtime.h>
 
 #include <climits>
@@ -22,6 +23,7 @@
 #include "hg_aggr.h"
 #include "hg_internal.h"
 #include "hg_knn.h"
+#include "hg_knn_list.h"
 
 namespace hg {
 
@@ -42,6 +44,37 @@ int knn_auto_slices(int64_t nq, int64_t n) {
   return groups <= 128 && tiles >= 2 ? 2 : 1;
 }
 
+bool knn_sizes_ok(int32_t nq, int32_t n, int32_t F, int32_t k, int32_t cand_slices, int32_t max_F) {
+  return nq >= 1 && n >= 1 && F >= 1 && (!max_F || F <= max_F) && k >= 1 && k <= kKnnMaxK && k <= n && cand_slices >= 0 &&
+         cand_slices <= kKnnMaxSlices;
+}
+
+int knn_refusal(const KnnCall &c, int32_t max_F, const int32_t *seg, int32_t B) {
+  const int32_t n = c.n, k = c.k;
+  if (!c.Q || !c.X || !c.idx || !c.dist) return fail(c.entry, HG_ERR_INVALID, "null Q, X, idx or dist");
+  if (c.nq < 1 || n < 1 || c.F < 1) return fail(c.entry, HG_ERR_INVALID, "nq, n and F must be at least 1");
+  if (max_F && c.F > max_F)
+    return fail(c.entry, HG_ERR_INVALID, "F = " + std::to_string(c.F) + " is above " + std::to_string(max_F) + ", the width the error bound is derived for");
+  if (k < 1 || k > kKnnMaxK) return fail(c.entry, HG_ERR_INVALID, "k must be in 1 .. 64, got " + std::to_string(k));
+  if (k > n) return fail(c.entry, HG_ERR_INVALID, "k = " + std::to_string(k) + " exceeds the n = " + std::to_string(n) + " candidates");
+  if (c.cand_slices < 0) return fail(c.entry, HG_ERR_INVALID, "cand_slices must be 0 (auto) or positive");
+  const bool same = c.Q == c.X && c.nq == n;
+  if (c.self_first && !same) return fail(c.entry, HG_ERR_INVALID, "self_first needs Q == X (the same pointer, nq == n)");
+  if (seg) {
+    if (!same) return fail(c.entry, HG_ERR_INVALID, "seg needs Q == X (the same pointer, nq == n)");
+    if (B < 1 || seg[0] != 0 || seg[B] != n) return fail(c.entry, HG_ERR_INVALID, "seg must have B >= 1, seg[0] = 0 and seg[B] = n");
+    for (int32_t b = 0; b < B; ++b)
+      if (seg[b + 1] < seg[b]) return fail(c.entry, HG_ERR_INVALID, "seg must ascend (seg[" + std::to_string(b + 1) + "] < seg[" + std::to_string(b) + "])");
+    for (int32_t b = 0; b < B; ++b)
+      if (seg[b + 1] - seg[b] < k)
+        return fail(c.entry, HG_ERR_INVALID, "segment " + std::to_string(b) + " has " + std::to_string(seg[b + 1] - seg[b]) +
+                                                 " rows, fewer than k = " + std::to_string(k));
+  }
+  if (c.cand_slices > kKnnMaxSlices)
+    return fail(c.entry, HG_ERR_UNSUPPORTED, "cand_slices above " + std::to_string(kKnnMaxSlices) + " is not implemented");
+  return HG_OK;
+}
+
 namespace {
 
 typedef float v2f __attribute__((ext_vector_type(2)));
@@ -57,8 +90,6 @@ struct KnnArgs {
   float *ws_dist;
   float *ws_mean;  // [slices - 1, nq]
 };
-
-__device__ __forceinline__ bool key_less(float ad, int aj, float bd, int bj) { return ad < bd || (ad == bd && aj < bj); }
 
 // the candidates [lo, hi) of row i: its segment, or all n
 __device__ __forceinline__ void row_range(const int32_t *seg, int B, int n, int i, int &lo, int &hi) {
@@ -114,8 +145,6 @@ __global__ __launch_bounds__(kKnnBlock) void knn_kernel(KnnArgs a) {
     thr[qi] = INFINITY;
     msum[qi] = 0.f;
   }
-  const int thr_lane = (k - 1) & 31;
-  const bool thr_hi = KS == 2 && k > 32;
 
   for (int tile = t_begin; tile < t_end; ++tile) {
     const int cb = c_lo + tile * kKnnTC;
@@ -186,49 +215,11 @@ __global__ __launch_bounds__(kKnnBlock) void knn_kernel(KnnArgs a) {
       }
       if (__ballot(any)) {
         float td = thr[qi];
-        int tj = __shfl(thr_hi ? lj[qi][KS - 1] : lj[qi][0], thr_lane, 32);
+        int tj = list_slot<KS, 32>(lj[qi], k - 1);
 #pragma unroll
         for (int jj = 0; jj < 8; ++jj) {
           const int j = cb + (jj < 4 ? tx * 4 + jj : 128 + tx * 4 + (jj - 4));
-          bool pass = key_less(dm[jj], j, td, tj);
-          unsigned long long wm = __ballot(pass);
-          while (wm) {
-            const unsigned hm = (unsigned)(wm >> (t & 32));  // this half wave's offers
-            const bool act = hm != 0;
-            const int src = act ? __ffs(hm) - 1 : 0;
-            const float nd = __shfl(dm[jj], src, 32);
-            const int nj = __shfl(j, src, 32);
-            // slot s keeps its entry if that is smaller than the new one, else takes the larger of slot s - 1's and the new
-            float pd[KS];
-            int pj[KS];
-            pd[0] = __shfl_up(ld[qi][0], 1, 32);
-            pj[0] = __shfl_up(lj[qi][0], 1, 32);
-            if (tx == 0) {
-              pd[0] = -INFINITY;
-              pj[0] = -1;
-            }
-            if (KS == 2) {
-              pd[KS - 1] = __shfl_up(ld[qi][KS - 1], 1, 32);
-              pj[KS - 1] = __shfl_up(lj[qi][KS - 1], 1, 32);
-              const float wd = __shfl(ld[qi][0], 31, 32);
-              const int wj = __shfl(lj[qi][0], 31, 32);
-              if (tx == 0) {
-                pd[KS - 1] = wd;
-                pj[KS - 1] = wj;
-              }
-            }
-#pragma unroll
-            for (int m = 0; m < KS; ++m) {
-              const bool keep = !act || key_less(ld[qi][m], lj[qi][m], nd, nj);
-              const bool take_new = key_less(pd[m], pj[m], nd, nj);
-              ld[qi][m] = keep ? ld[qi][m] : (take_new ? nd : pd[m]);
-              lj[qi][m] = keep ? lj[qi][m] : (take_new ? nj : pj[m]);
-            }
-            td = __shfl(thr_hi ? ld[qi][KS - 1] : ld[qi][0], thr_lane, 32);
-            tj = __shfl(thr_hi ? lj[qi][KS - 1] : lj[qi][0], thr_lane, 32);
-            pass = pass && !(act && tx == src) && key_less(dm[jj], j, td, tj);
-            wm = __ballot(pass);
-          }
+          list_offer<KS, 32>(ld[qi], lj[qi], dm[jj], j, k, td, tj);
         }
         thr[qi] = td;
       }
@@ -288,20 +279,7 @@ __global__ __launch_bounds__(64 * kKnnMergeRows) void knn_merge_kernel(KnnArgs a
     const int s = e / k, p = e - s * k;
     const float d = sd[e];
     const int j = sj[e];
-    int rank = p;
-    for (int o = 0; o < a.slices; ++o) {
-      if (o == s) continue;
-      const float *od = sd + o * k;
-      const int *oj = sj + o * k;
-      int lo = 0, hi = k;  // entries [0, lo) are before this one, [hi, k) are not
-      while (lo < hi) {
-        const int m = (lo + hi) >> 1;
-        const bool before = o < s ? !key_less(d, j, od[m], oj[m]) : key_less(od[m], oj[m], d, j);
-        if (before) lo = m + 1;
-        else hi = m;
-      }
-      rank += lo;
-    }
+    const int rank = merged_rank(sd, sj, a.slices, k, s, p);
     if (rank < k) {
       a.idx[(size_t)row * k + rank] = j;
       a.dist[(size_t)row * k + rank] = d < 0.f ? 0.f : d;
@@ -316,19 +294,13 @@ __global__ __launch_bounds__(64 * kKnnMergeRows) void knn_merge_kernel(KnnArgs a
   }
 }
 
-int fail(int status, const std::string &msg) {
-  set_error("hg_knn_f32: " + msg);
-  return status;
-}
-
 }  // namespace
 }  // namespace hg
 
 extern "C" {
 
 size_t hg_knn_workspace_bytes(int32_t nq, int32_t n, int32_t F, int32_t k, int32_t cand_slices) {
-  if (nq < 1 || n < 1 || F < 1 || k < 1 || k > hg::kKnnMaxK || k > n || cand_slices < 0 || cand_slices > hg::kKnnMaxSlices)
-    return 0;
+  if (!hg::knn_sizes_ok(nq, n, F, k, cand_slices, 0)) return 0;
   const int slices = cand_slices ? cand_slices : hg::knn_auto_slices(nq, n);
   return hg::knn_layout(nq, n, k, slices).total;
 }
@@ -337,36 +309,17 @@ int hg_knn_f32(const float *Q, int32_t nq, const float *X, int32_t n, int32_t F,
                int32_t self_first, int32_t cand_slices, int32_t *idx, float *dist, float *mean_dist, void *workspace,
                size_t workspace_bytes, hg_stream_t stream) {
   using namespace hg;
-  if (!Q || !X || !idx || !dist) return fail(HG_ERR_INVALID, "null Q, X, idx or dist");
-  if (nq < 1 || n < 1 || F < 1) return fail(HG_ERR_INVALID, "nq, n and F must be at least 1");
-  if (k < 1 || k > kKnnMaxK) return fail(HG_ERR_INVALID, "k must be in 1 .. 64, got " + std::to_string(k));
-  if (k > n) return fail(HG_ERR_INVALID, "k = " + std::to_string(k) + " exceeds the n = " + std::to_string(n) + " candidates");
-  if (cand_slices < 0) return fail(HG_ERR_INVALID, "cand_slices must be 0 (auto) or positive");
-  const bool same = Q == X && nq == n;
-  if (self_first && !same) return fail(HG_ERR_INVALID, "self_first needs Q == X (the same pointer, nq == n)");
-  if (seg) {
-    if (!same) return fail(HG_ERR_INVALID, "seg needs Q == X (the same pointer, nq == n)");
-    if (B < 1 || seg[0] != 0 || seg[B] != n) return fail(HG_ERR_INVALID, "seg must have B >= 1, seg[0] = 0 and seg[B] = n");
-    for (int32_t b = 0; b < B; ++b)
-      if (seg[b + 1] < seg[b]) return fail(HG_ERR_INVALID, "seg must ascend (seg[" + std::to_string(b + 1) + "] < seg[" + std::to_string(b) + "])");
-    for (int32_t b = 0; b < B; ++b)
-      if (seg[b + 1] - seg[b] < k)
-        return fail(HG_ERR_INVALID, "segment " + std::to_string(b) + " has " + std::to_string(seg[b + 1] - seg[b]) +
-                                        " rows, fewer than k = " + std::to_string(k));
-  }
-  if (cand_slices > kKnnMaxSlices)
-    return fail(HG_ERR_UNSUPPORTED, "cand_slices above " + std::to_string(kKnnMaxSlices) + " is not implemented");
+  const char *entry = "hg_knn_f32";
+  if (const int st = knn_refusal({entry, Q, X, idx, dist, nq, n, F, k, self_first, cand_slices}, 0, seg, B)) return st;
   for (const void *p : {(const void *)Q, (const void *)X, (const void *)idx, (const void *)dist, (const void *)mean_dist,
                         (const void *)workspace})
-    if ((uintptr_t)p % 4) return fail(HG_ERR_UNSUPPORTED, "Q, X, idx, dist, mean_dist and the workspace must be 4-byte aligned");
+    if ((uintptr_t)p % 4) return fail(entry, HG_ERR_UNSUPPORTED, "Q, X, idx, dist, mean_dist and the workspace must be 4-byte aligned");
   const int slices = cand_slices ? cand_slices : knn_auto_slices(nq, n);
   const KnnLayout L = knn_layout(nq, n, k, slices);
   const bool need_ws = seg || slices > 1;
-  if (need_ws && (!workspace || workspace_bytes < L.total)) {
-    set_error("hg_knn_f32: workspace of " + std::to_string(workspace_bytes) + " bytes, hg_knn_workspace_bytes asks for " +
-              std::to_string(L.total));
-    return HG_ERR_WORKSPACE;
-  }
+  if (need_ws && (!workspace || workspace_bytes < L.total))
+    return fail(entry, HG_ERR_WORKSPACE, "workspace of " + std::to_string(workspace_bytes) + " bytes, hg_knn_workspace_bytes asks for " +
+                                             std::to_string(L.total));
 
   hipStream_t s = static_cast<hipStream_t>(stream);
   unsigned char *ws = static_cast<unsigned char *>(workspace);
@@ -387,7 +340,7 @@ int hg_knn_f32(const float *Q, int32_t nq, const float *X, int32_t n, int32_t F,
     // the offsets are the caller's host memory: the copy has left it when this returns
     hipError_t e = hipMemcpyAsync(ws + L.seg, seg, ((size_t)B + 1) * 4, hipMemcpyHostToDevice, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e != hipSuccess) return fail(HG_ERR_HIP, std::string("copy of seg: ") + hipGetErrorString(e));
+    if (e != hipSuccess) return fail(entry, HG_ERR_HIP, std::string("copy of seg: ") + hipGetErrorString(e));
     a.seg = reinterpret_cast<const int32_t *>(ws + L.seg);
   }
   if (slices > 1) {
@@ -408,7 +361,7 @@ int hg_knn_f32(const float *Q, int32_t nq, const float *X, int32_t n, int32_t F,
                        lds, s, a, mean ? 1 : 0);
     e = hipGetLastError();
   }
-  if (e != hipSuccess) return fail(HG_ERR_HIP, std::string("launch: ") + hipGetErrorString(e));
+  if (e != hipSuccess) return fail(entry, HG_ERR_HIP, std::string("launch: ") + hipGetErrorString(e));
   return HG_OK;
 }
 

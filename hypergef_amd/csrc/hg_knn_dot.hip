@@ -10,6 +10,9 @@
 //   knn_dot_rerank_kernel    one wave per query row: merges the slices' shortlists, computes the shortlist's d2 with
 //                            knn_kernel's arithmetic (q - x, then one fma into one accumulator, c = 0 .. F - 1), selects
 //                            the k smallest under (d2, j), certifies, and otherwise scans all n candidates
+// The prefilter keeps a row's shortlist in the 32 lanes of the half wave that holds the row's accumulators (list_offer<KS,
+// 32>, as knn_kernel keeps its list), the rerank its best-k list in the 64 lanes of the row's wave (list_offer<1, 64>); the
+// slices' shortlists are merged by merged_rank, as knn_merge_kernel merges.  All three are hg_knn_list.h's.
 // No atomics; every sum has a fixed order, so two calls give the same bits.
 #include <hip/hip_runtime.h>
 
@@ -20,6 +23,7 @@
 #include "hg_aggr.h"
 #include "hg_internal.h"
 #include "hg_knn.h"
+#include "hg_knn_list.h"
 
 namespace hg {
 
@@ -63,8 +67,6 @@ struct DotArgs {
   float *dist, *mean;
   int32_t *fallback;
 };
-
-__device__ __forceinline__ bool key_less(float ad, int aj, float bd, int bj) { return ad < bd || (ad == bd && aj < bj); }
 
 __global__ __launch_bounds__(256) void knn_dot_norm_kernel(const float *__restrict__ X, int n, int F, float *__restrict__ n2,
                                                            float *__restrict__ bmax) {
@@ -133,7 +135,6 @@ __global__ __launch_bounds__(kDotBlock) void knn_dot_prefilter_kernel(DotArgs a)
     const int row = row0 + (r & 3) + 8 * (r >> 2);
     nq[r] = row < a.nq ? a.n2q[row] : 0.f;
   }
-  const int thr_lane = (kp - 1) & 31, thr_m = (kp - 1) >> 5;
 
   // staging: a chunk is 128 query rows and 128 candidate rows of kDotFC columns.  Thirty-two lanes read one row's 128
   // bytes, so a wave's load touches two rows; thread t holds column t & 31 of rows (t >> 5) + 8 i, i < 16 of each.  Rows past
@@ -207,62 +208,9 @@ __global__ __launch_bounds__(kDotBlock) void knn_dot_prefilter_kernel(DotArgs a)
       }
       if (__ballot(any)) {
         float td = thr[r];
-        int sel = lj[r][0];
+        int tj = list_slot<KS, 32>(lj[r], kp - 1);
 #pragma unroll
-        for (int m = 1; m < KS; ++m) sel = thr_m == m ? lj[r][m] : sel;
-        int tj = __shfl(sel, thr_lane, 32);
-#pragma unroll
-        for (int b = 0; b < 4; ++b) {
-          const int j = cb + b * 32 + tx;
-          bool pass = key_less(dm[b], j, td, tj);
-          unsigned long long wm = __ballot(pass);
-          while (wm) {
-            const unsigned hm = (unsigned)(wm >> (lane & 32));  // this half wave's offers
-            const bool act = hm != 0;
-            const int src = act ? __ffs(hm) - 1 : 0;
-            const float nd = __shfl(dm[b], src, 32);
-            const int nj = __shfl(j, src, 32);
-            // slot s keeps its entry if that is smaller than the new one, else takes the larger of slot s - 1's and the new
-            float pd[KS];
-            int pj[KS];
-#pragma unroll
-            for (int m = 0; m < KS; ++m) {
-              pd[m] = __shfl_up(ld[r][m], 1, 32);
-              pj[m] = __shfl_up(lj[r][m], 1, 32);
-            }
-#pragma unroll
-            for (int m = KS - 1; m > 0; --m) {
-              const float wd = __shfl(ld[r][m - 1], 31, 32);
-              const int wj = __shfl(lj[r][m - 1], 31, 32);
-              if (tx == 0) {
-                pd[m] = wd;
-                pj[m] = wj;
-              }
-            }
-            if (tx == 0) {
-              pd[0] = -INFINITY;
-              pj[0] = -1;
-            }
-#pragma unroll
-            for (int m = 0; m < KS; ++m) {
-              const bool keep = !act || key_less(ld[r][m], lj[r][m], nd, nj);
-              const bool take_new = key_less(pd[m], pj[m], nd, nj);
-              ld[r][m] = keep ? ld[r][m] : (take_new ? nd : pd[m]);
-              lj[r][m] = keep ? lj[r][m] : (take_new ? nj : pj[m]);
-            }
-            float seld = ld[r][0];
-            sel = lj[r][0];
-#pragma unroll
-            for (int m = 1; m < KS; ++m) {
-              seld = thr_m == m ? ld[r][m] : seld;
-              sel = thr_m == m ? lj[r][m] : sel;
-            }
-            td = __shfl(seld, thr_lane, 32);
-            tj = __shfl(sel, thr_lane, 32);
-            pass = pass && !(act && tx == src) && key_less(dm[b], j, td, tj);
-            wm = __ballot(pass);
-          }
-        }
+        for (int b = 0; b < 4; ++b) list_offer<KS, 32>(ld[r], lj[r], dm[b], cb + b * 32 + tx, kp, td, tj);
         thr[r] = td;
       }
       __builtin_amdgcn_sched_barrier(0);  // one row at a time, as in knn_kernel
@@ -291,34 +239,6 @@ __global__ __launch_bounds__(kDotBlock) void knn_dot_prefilter_kernel(DotArgs a)
   }
 }
 
-// The wave's best-k list under (d2, j), slot s in lane s: the offers of all 64 lanes, smallest first.
-__device__ __forceinline__ void offer(bool valid, float key, int j, int k, float &bd, int &bj) {
-  const int lane = threadIdx.x;
-  float td = __shfl(bd, k - 1);
-  int tj = __shfl(bj, k - 1);
-  bool pass = valid && key_less(key, j, td, tj);
-  unsigned long long wm = __ballot(pass);
-  while (wm) {
-    const int src = __ffsll((long long)wm) - 1;
-    const float nd = __shfl(key, src);
-    const int nj = __shfl(j, src);
-    float pd = __shfl_up(bd, 1);
-    int pj = __shfl_up(bj, 1);
-    if (lane == 0) {
-      pd = -INFINITY;
-      pj = -1;
-    }
-    const bool keep = key_less(bd, bj, nd, nj);
-    const bool take_new = key_less(pd, pj, nd, nj);
-    bd = keep ? bd : (take_new ? nd : pd);
-    bj = keep ? bj : (take_new ? nj : pj);
-    td = __shfl(bd, k - 1);
-    tj = __shfl(bj, k - 1);
-    pass = pass && lane != src && key_less(key, j, td, tj);
-    wm = __ballot(pass);
-  }
-}
-
 // d2(row, j) of this lane's candidate j (j < 0: none) in knn_kernel's arithmetic.  The 64 candidate rows are staged through
 // LDS 64 columns at a time with coalesced reads, then every lane walks its own row in column order.
 __device__ __forceinline__ float exact_batch(const DotArgs &a, int row, int j, float (*tile)[kDotRerankRows + 1], float *qs) {
@@ -343,6 +263,16 @@ __device__ __forceinline__ float exact_batch(const DotArgs &a, int row, int j, f
   return acc;
 }
 
+// This lane's candidate j (ok: it has one) goes to the wave's best-k list under (d2, j), slot s in lane s, at its exact
+// distance; the row's own pair goes before every distance and is written out as 0.
+__device__ __forceinline__ void rerank_offer(const DotArgs &a, int row, bool ok, int j, float (&bd)[1], int (&bj)[1],
+                                             float (*tile)[kDotRerankRows + 1], float *qs) {
+  const float d2 = exact_batch(a, row, ok ? j : -1, tile, qs);
+  float td = list_slot<1, 64>(bd, a.k - 1);
+  int tj = list_slot<1, 64>(bj, a.k - 1);
+  list_offer<1, 64>(bd, bj, !ok ? NAN : (a.self_first && j == row) ? -1.f : d2, j, a.k, td, tj);
+}
+
 __global__ __launch_bounds__(kDotRerankRows) void knn_dot_rerank_kernel(DotArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char dot_smem[];
   float(*tile)[kDotRerankRows + 1] = reinterpret_cast<float(*)[kDotRerankRows + 1]>(dot_smem);
@@ -361,43 +291,27 @@ __global__ __launch_bounds__(kDotRerankRows) void knn_dot_rerank_kernel(DotArgs 
     sj[e] = a.l_idx[at];
   }
   __syncthreads();
-  // every entry counts the entries before it under (d~, j) -- equal keys, which only unused slots have, by slice
+  // every entry goes to its place in the merge under (d~, j)
   for (int e = lane; e < L; e += 64) {
     const int s = e / kp, p = e - s * kp;
-    const float d = sd[e];
-    const int j = sj[e];
-    int rank = p;
-    for (int o = 0; o < a.slices; ++o) {
-      if (o == s) continue;
-      const float *od = sd + o * kp;
-      const int *oj = sj + o * kp;
-      int lo = 0, hi = kp;
-      while (lo < hi) {
-        const int m = (lo + hi) >> 1;
-        const bool before = o < s ? !key_less(d, j, od[m], oj[m]) : key_less(od[m], oj[m], d, j);
-        if (before) lo = m + 1;
-        else hi = m;
-      }
-      rank += lo;
-    }
+    const int rank = merged_rank(sd, sj, a.slices, kp, s, p);
     if (rank < kp) {
-      cd[rank] = d;
-      cj[rank] = j;
+      cd[rank] = sd[e];
+      cj[rank] = sj[e];
     }
   }
   __syncthreads();
 
   // rank the shortlist by the exact distances
-  float bd = INFINITY;
-  int bj = INT_MAX;
+  float bd[1] = {INFINITY};
+  int bj[1] = {INT_MAX};
   bool bad = false;  // a slot that holds no candidate: an estimate was not a number
   for (int base = 0; base < kp; base += 64) {
     const int e = base + lane;
     const int j = e < kp ? cj[e] : -1;
     const bool ok = j >= 0 && j < n;
     bad |= e < kp && !ok;
-    const float d2 = exact_batch(a, row, ok ? j : -1, tile, qs);
-    offer(ok, (a.self_first && j == row) ? -1.f : d2, j, k, bd, bj);
+    rerank_offer(a, row, ok, j, bd, bj, tile, qs);
   }
 
   // Every candidate outside the shortlist has d~ >= T, so d2 >= (T - E1) (1 - (F + 2) u) >= T - Ei:
@@ -407,7 +321,7 @@ __global__ __launch_bounds__(kDotRerankRows) void knn_dot_rerank_kernel(DotArgs 
   if (certified && n > kp) {
     const float u = 5.9604644775390625e-8f;  // 2^-24
     const float T = cd[kp - 1];
-    const float kth = __shfl(bd, k - 1);
+    const float kth = list_slot<1, 64>(bd, k - 1);
     const float sum = a.n2q[row] + a.n2max[0];
     const int c2 = 2 * a.F + 4;
     const float C = (float)(c2 + (c2 >> 6) + 1) * u;
@@ -416,18 +330,16 @@ __global__ __launch_bounds__(kDotRerankRows) void knn_dot_rerank_kernel(DotArgs 
     certified = sum < 1e37f && kth < T - Ei;  // strictly; an infinite or NaN bound fails both
   }
   if (!certified) {
-    bd = INFINITY;
-    bj = INT_MAX;
+    bd[0] = INFINITY;
+    bj[0] = INT_MAX;
     for (int base = 0; base < n; base += 64) {
       const int j = base + lane;
-      const bool ok = j < n;
-      const float d2 = exact_batch(a, row, ok ? j : -1, tile, qs);
-      offer(ok, (a.self_first && j == row) ? -1.f : d2, j, k, bd, bj);
+      rerank_offer(a, row, j < n, j, bd, bj, tile, qs);
     }
   }
   if (lane < k) {
-    a.idx[(size_t)row * k + lane] = bj;
-    a.dist[(size_t)row * k + lane] = bd < 0.f ? 0.f : bd;
+    a.idx[(size_t)row * k + lane] = bj[0];
+    a.dist[(size_t)row * k + lane] = bd[0] < 0.f ? 0.f : bd[0];
   }
   if (lane == 0) {
     if (a.fallback) a.fallback[row] = certified ? 0 : 1;
@@ -437,11 +349,6 @@ __global__ __launch_bounds__(kDotRerankRows) void knn_dot_rerank_kernel(DotArgs 
       a.mean[row] = v / (float)n;
     }
   }
-}
-
-int fail(int status, const std::string &msg) {
-  set_error("hg_knn_dot_f32: " + msg);
-  return status;
 }
 
 template <int KS>
@@ -456,9 +363,7 @@ void launch_prefilter(const DotArgs &a, dim3 grid, bool mean, hipStream_t s) {
 extern "C" {
 
 size_t hg_knn_dot_workspace_bytes(int32_t nq, int32_t n, int32_t F, int32_t k, int32_t cand_slices) {
-  if (nq < 1 || n < 1 || F < 1 || F > hg::kDotMaxF || k < 1 || k > hg::kKnnMaxK || k > n || cand_slices < 0 ||
-      cand_slices > hg::kKnnMaxSlices)
-    return 0;
+  if (!hg::knn_sizes_ok(nq, n, F, k, cand_slices, hg::kDotMaxF)) return 0;
   return hg::knn_dot_layout(nq, n, k, hg::knn_dot_slices(nq, n, cand_slices)).total;
 }
 
@@ -466,28 +371,18 @@ int hg_knn_dot_f32(const float *Q, int32_t nq, const float *X, int32_t n, int32_
                    int32_t cand_slices, int32_t *idx, float *dist, float *mean_dist, int32_t *fallback, void *workspace,
                    size_t workspace_bytes, hg_stream_t stream) {
   using namespace hg;
-  if (!Q || !X || !idx || !dist) return fail(HG_ERR_INVALID, "null Q, X, idx or dist");
-  if (nq < 1 || n < 1 || F < 1) return fail(HG_ERR_INVALID, "nq, n and F must be at least 1");
-  if (F > kDotMaxF)
-    return fail(HG_ERR_INVALID, "F = " + std::to_string(F) + " is above " + std::to_string(kDotMaxF) + ", the width the error bound is derived for");
-  if (k < 1 || k > kKnnMaxK) return fail(HG_ERR_INVALID, "k must be in 1 .. 64, got " + std::to_string(k));
-  if (k > n) return fail(HG_ERR_INVALID, "k = " + std::to_string(k) + " exceeds the n = " + std::to_string(n) + " candidates");
-  if (cand_slices < 0) return fail(HG_ERR_INVALID, "cand_slices must be 0 (auto) or positive");
+  const char *entry = "hg_knn_dot_f32";
+  if (const int st = knn_refusal({entry, Q, X, idx, dist, nq, n, F, k, self_first, cand_slices}, kDotMaxF, nullptr, 0)) return st;
   const bool same = Q == X && nq == n;
-  if (self_first && !same) return fail(HG_ERR_INVALID, "self_first needs Q == X (the same pointer, nq == n)");
-  if (cand_slices > kKnnMaxSlices)
-    return fail(HG_ERR_UNSUPPORTED, "cand_slices above " + std::to_string(kKnnMaxSlices) + " is not implemented");
   for (const void *p : {(const void *)Q, (const void *)X, (const void *)idx, (const void *)dist, (const void *)mean_dist,
                         (const void *)fallback, (const void *)workspace})
     if ((uintptr_t)p % 4)
-      return fail(HG_ERR_UNSUPPORTED, "Q, X, idx, dist, mean_dist, fallback and the workspace must be 4-byte aligned");
+      return fail(entry, HG_ERR_UNSUPPORTED, "Q, X, idx, dist, mean_dist, fallback and the workspace must be 4-byte aligned");
   const int slices = knn_dot_slices(nq, n, cand_slices);
   const KnnDotLayout L = knn_dot_layout(nq, n, k, slices);
-  if (!workspace || workspace_bytes < L.total) {
-    set_error("hg_knn_dot_f32: workspace of " + std::to_string(workspace_bytes) + " bytes, hg_knn_dot_workspace_bytes asks for " +
-              std::to_string(L.total));
-    return HG_ERR_WORKSPACE;
-  }
+  if (!workspace || workspace_bytes < L.total)
+    return fail(entry, HG_ERR_WORKSPACE, "workspace of " + std::to_string(workspace_bytes) +
+                                             " bytes, hg_knn_dot_workspace_bytes asks for " + std::to_string(L.total));
 
   hipStream_t s = static_cast<hipStream_t>(stream);
   unsigned char *ws = static_cast<unsigned char *>(workspace);
@@ -530,7 +425,7 @@ int hg_knn_dot_f32(const float *Q, int32_t nq, const float *X, int32_t n, int32_
   const size_t lds = (size_t)(kDotRerankRows * (kDotRerankRows + 1) + kDotRerankRows + 2 * 96) * 4 + (size_t)slices * L.kp * 8;
   hipLaunchKernelGGL(knn_dot_rerank_kernel, dim3((unsigned)nq), dim3(kDotRerankRows), lds, s, a);
   const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(HG_ERR_HIP, std::string("launch: ") + hipGetErrorString(e));
+  if (e != hipSuccess) return fail(entry, HG_ERR_HIP, std::string("launch: ") + hipGetErrorString(e));
   return HG_OK;
 }
 

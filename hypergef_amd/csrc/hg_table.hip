@@ -474,45 +474,26 @@ __global__ __launch_bounds__(64 * kTableWaves) void table_dot_kernel(TableDotArg
   }
 }
 
-int fail(const char *entry, int status, const std::string &msg) {
-  set_error(std::string(entry) + ": " + msg);
-  return status;
+// what every table entry refuses about k and the table's size
+int table_refusal(const char *entry, int32_t rows, int32_t k) {
+  if (k < 1 || k > kTableMaxK) return fail(entry, HG_ERR_INVALID, "k must be in 1 .. 64, got " + std::to_string(k));
+  if ((int64_t)rows * k > INT32_MAX) return fail(entry, HG_ERR_INVALID, "rows * k must be below 2^31");
+  return HG_OK;
 }
 
-// what both gathers refuse about the table and the rows, in the order include/hg_aggr.h gives
+// the sizes' refusals of every entry that takes rows of F columns, in the order include/hg_aggr.h gives
+int size_refusal(const char *entry, int32_t rows, int32_t k, int32_t n, int32_t F) {
+  if (rows < 1 || n < 1 || F < 1) return fail(entry, HG_ERR_INVALID, "rows, n and F must be at least 1");
+  return table_refusal(entry, rows, k);
+}
+
+// what the four gathers refuse about the table and the rows, in the same order
 int gather_refusal(const char *entry, int32_t rows, int32_t k, int32_t n, int32_t F, const float *src, const float *w,
                    const float *src_scale, const float *dst_scale, const float *dst) {
   if (!src || !dst) return fail(entry, HG_ERR_INVALID, "null src or dst");
-  if (rows < 1 || n < 1 || F < 1) return fail(entry, HG_ERR_INVALID, "rows, n and F must be at least 1");
-  if (k < 1 || k > kTableMaxK) return fail(entry, HG_ERR_INVALID, "k must be in 1 .. 64, got " + std::to_string(k));
-  if ((int64_t)rows * k > INT32_MAX) return fail(entry, HG_ERR_INVALID, "rows * k must be below 2^31");
+  if (const int st = size_refusal(entry, rows, k, n, F)) return st;
   for (const void *p : {(const void *)src, (const void *)w, (const void *)src_scale, (const void *)dst_scale, (const void *)dst})
     if ((uintptr_t)p % 4) return fail(entry, HG_ERR_UNSUPPORTED, "src, w, the scales and dst must be 4-byte aligned");
-  return HG_OK;
-}
-
-template <bool T, bool D = false>
-int launch_table_gather(const char *entry, TableGatherArgs a, hipStream_t s) {
-  const bool vec4 = a.F % 4 == 0 && (uintptr_t)a.src % 16 == 0 && (uintptr_t)a.dst % 16 == 0 && (!D || (uintptr_t)a.ctr % 16 == 0);
-  const int V = vec4 ? 4 : 1;
-  a.L = std::min((a.F + V - 1) / V, 64);
-  a.R = 64 / a.L;
-  a.P2 = 1;
-  while (a.P2 < a.R * kTableWaves) a.P2 <<= 1;
-  const int RW = a.R * kTableWaves;
-  const dim3 grid((unsigned)(((int64_t)a.nrows + RW - 1) / RW)), block(64 * kTableWaves);
-  if (vec4) hipLaunchKernelGGL((table_gather_kernel<T, 4, D>), grid, block, 0, s, a);
-  else hipLaunchKernelGGL((table_gather_kernel<T, 1, D>), grid, block, 0, s, a);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(entry, HG_ERR_HIP, std::string("launch: ") + hipGetErrorString(e));
-  return HG_OK;
-}
-
-// the sizes' refusals of every table entry, in gather_refusal's order
-int size_refusal(const char *entry, int32_t rows, int32_t k, int32_t n, int32_t F) {
-  if (rows < 1 || n < 1 || F < 1) return fail(entry, HG_ERR_INVALID, "rows, n and F must be at least 1");
-  if (k < 1 || k > kTableMaxK) return fail(entry, HG_ERR_INVALID, "k must be in 1 .. 64, got " + std::to_string(k));
-  if ((int64_t)rows * k > INT32_MAX) return fail(entry, HG_ERR_INVALID, "rows * k must be below 2^31");
   return HG_OK;
 }
 
@@ -520,6 +501,42 @@ int launch_check(const char *entry) {
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail(entry, HG_ERR_HIP, std::string("launch: ") + hipGetErrorString(e));
   return HG_OK;
+}
+
+// One of the four gathers over a table of [rows, k] entries that name n vertices.  T: the vertex gather through the
+// transpose (ptr_v, pos_v; idx is null), n destination rows out of `rows` source rows; else the hyperedge gather through
+// idx, the other way round.  D: the difference gather, with the destination rows' centres ctr (else null).
+template <bool T, bool D>
+int launch_table_gather(const char *entry, const int32_t *idx, const int32_t *ptr_v, const int32_t *pos_v, int32_t rows, int32_t k,
+                        int32_t n, int32_t F, const float *src, const float *w, const float *src_scale, const float *dst_scale,
+                        const float *ctr, float *dst, hg_stream_t stream) {
+  TableGatherArgs a{};
+  a.idx = idx;
+  a.ptr_v = ptr_v;
+  a.pos_v = pos_v;
+  a.src = src;
+  a.w = w;
+  a.src_scale = src_scale;
+  a.dst_scale = dst_scale;
+  a.ctr = ctr;
+  a.dst = dst;
+  a.nrows = T ? n : rows;
+  a.nsrc = T ? rows : n;
+  a.k = k;
+  a.F = F;
+  a.entries = rows * k;
+  const bool vec4 = F % 4 == 0 && (uintptr_t)src % 16 == 0 && (uintptr_t)dst % 16 == 0 && (!D || (uintptr_t)ctr % 16 == 0);
+  const int V = vec4 ? 4 : 1;
+  a.L = std::min((F + V - 1) / V, 64);
+  a.R = 64 / a.L;
+  a.P2 = 1;
+  while (a.P2 < a.R * kTableWaves) a.P2 <<= 1;
+  const int RW = a.R * kTableWaves;
+  const dim3 grid((unsigned)(((int64_t)a.nrows + RW - 1) / RW)), block(64 * kTableWaves);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (vec4) hipLaunchKernelGGL((table_gather_kernel<T, 4, D>), grid, block, 0, s, a);
+  else hipLaunchKernelGGL((table_gather_kernel<T, 1, D>), grid, block, 0, s, a);
+  return launch_check(entry);
 }
 
 }  // namespace
@@ -540,16 +557,14 @@ int hg_table_transpose(const int32_t *idx, int32_t rows, int32_t k, int32_t n, i
   const char *entry = "hg_table_transpose";
   if (!idx || !ptr_v || !pos_v) return fail(entry, HG_ERR_INVALID, "null idx, ptr_v or pos_v");
   if (rows < 1 || n < 1) return fail(entry, HG_ERR_INVALID, "rows and n must be at least 1");
-  if (k < 1 || k > kTableMaxK) return fail(entry, HG_ERR_INVALID, "k must be in 1 .. 64, got " + std::to_string(k));
-  if ((int64_t)rows * k > INT32_MAX) return fail(entry, HG_ERR_INVALID, "rows * k must be below 2^31");
+  if (const int st = table_refusal(entry, rows, k)) return st;
   for (const void *p : {(const void *)idx, (const void *)ptr_v, (const void *)pos_v})
     if ((uintptr_t)p % 4) return fail(entry, HG_ERR_UNSUPPORTED, "idx, ptr_v and pos_v must be 4-byte aligned");
   const TableLayout L = table_layout(rows, k, n);
-  if (!workspace || workspace_bytes < L.total || (uintptr_t)workspace % 4) {
-    set_error(std::string(entry) + ": workspace of " + std::to_string(workspace_bytes) +
-              " bytes, hg_table_transpose_workspace_bytes asks for " + std::to_string(L.total) + " (4-byte aligned)");
-    return HG_ERR_WORKSPACE;
-  }
+  if (!workspace || workspace_bytes < L.total || (uintptr_t)workspace % 4)
+    return fail(entry, HG_ERR_WORKSPACE, "workspace of " + std::to_string(workspace_bytes) +
+                                             " bytes, hg_table_transpose_workspace_bytes asks for " + std::to_string(L.total) +
+                                             " (4-byte aligned)");
   hipStream_t s = static_cast<hipStream_t>(stream);
   unsigned char *ws = static_cast<unsigned char *>(workspace);
   int32_t *alt = reinterpret_cast<int32_t *>(ws + L.alt);
@@ -559,23 +574,18 @@ int hg_table_transpose(const int32_t *idx, int32_t rows, int32_t k, int32_t n, i
   a.entries = (int32_t)L.entries;
   a.n = n;
   a.tiles = (int32_t)L.tiles;
-  hipError_t e = hipSuccess;
-  for (int pass = 0; pass < L.passes && e == hipSuccess; ++pass) {
+  for (int pass = 0; pass < L.passes; ++pass) {
     a.shift = pass * kTableRadixBits;
     a.out = (L.passes - 1 - pass) % 2 == 0 ? pos_v : alt;  // the last pass writes pos_v
     hipLaunchKernelGGL(table_hist_kernel, dim3((unsigned)L.tiles), dim3(kTableBlock), 0, s, a);
     hipLaunchKernelGGL(table_scan_kernel, dim3(1), dim3(kTableScanBlock), 0, s, a.hist, (int64_t)kTableBins * L.tiles);
     hipLaunchKernelGGL(table_scatter_kernel, dim3((unsigned)L.tiles), dim3(kTableBlock), 0, s, a);
-    e = hipGetLastError();
+    if (const int st = launch_check(entry)) return st;
     a.in = a.out;
   }
-  if (e == hipSuccess) {
-    hipLaunchKernelGGL(table_ptr_kernel, dim3((unsigned)(L.entries / 256 + 1)), dim3(256), 0, s, idx, (const int32_t *)pos_v,
-                       a.entries, n, ptr_v);
-    e = hipGetLastError();
-  }
-  if (e != hipSuccess) return fail(entry, HG_ERR_HIP, std::string("launch: ") + hipGetErrorString(e));
-  return HG_OK;
+  hipLaunchKernelGGL(table_ptr_kernel, dim3((unsigned)(L.entries / 256 + 1)), dim3(256), 0, s, idx, (const int32_t *)pos_v,
+                     a.entries, n, ptr_v);
+  return launch_check(entry);
 }
 
 int hg_table_gather_f32(const int32_t *idx, int32_t rows, int32_t k, int32_t n, int32_t F, const float *src, const float *w,
@@ -585,19 +595,7 @@ int hg_table_gather_f32(const int32_t *idx, int32_t rows, int32_t k, int32_t n, 
   if (!idx) return fail(entry, HG_ERR_INVALID, "null idx");
   if (const int st = gather_refusal(entry, rows, k, n, F, src, w, src_scale, dst_scale, dst)) return st;
   if ((uintptr_t)idx % 4) return fail(entry, HG_ERR_UNSUPPORTED, "idx must be 4-byte aligned");
-  TableGatherArgs a{};
-  a.idx = idx;
-  a.src = src;
-  a.w = w;
-  a.src_scale = src_scale;
-  a.dst_scale = dst_scale;
-  a.dst = dst;
-  a.nrows = rows;
-  a.nsrc = n;
-  a.k = k;
-  a.F = F;
-  a.entries = rows * k;
-  return launch_table_gather<false>(entry, a, static_cast<hipStream_t>(stream));
+  return launch_table_gather<false, false>(entry, idx, nullptr, nullptr, rows, k, n, F, src, w, src_scale, dst_scale, nullptr, dst, stream);
 }
 
 int hg_table_gather_t_f32(const int32_t *ptr_v, const int32_t *pos_v, int32_t rows, int32_t k, int32_t n, int32_t F,
@@ -608,20 +606,7 @@ int hg_table_gather_t_f32(const int32_t *ptr_v, const int32_t *pos_v, int32_t ro
   if (!ptr_v || !pos_v) return fail(entry, HG_ERR_INVALID, "null ptr_v or pos_v");
   if (const int st = gather_refusal(entry, rows, k, n, F, src, w, src_scale, dst_scale, dst)) return st;
   if ((uintptr_t)ptr_v % 4 || (uintptr_t)pos_v % 4) return fail(entry, HG_ERR_UNSUPPORTED, "ptr_v and pos_v must be 4-byte aligned");
-  TableGatherArgs a{};
-  a.ptr_v = ptr_v;
-  a.pos_v = pos_v;
-  a.src = src;
-  a.w = w;
-  a.src_scale = src_scale;
-  a.dst_scale = dst_scale;
-  a.dst = dst;
-  a.nrows = n;
-  a.nsrc = rows;
-  a.k = k;
-  a.F = F;
-  a.entries = rows * k;
-  return launch_table_gather<true>(entry, a, static_cast<hipStream_t>(stream));
+  return launch_table_gather<true, false>(entry, nullptr, ptr_v, pos_v, rows, k, n, F, src, w, src_scale, dst_scale, nullptr, dst, stream);
 }
 
 int hg_table_gather_diff_f32(const int32_t *idx, int32_t rows, int32_t k, int32_t n, int32_t F, const float *src,
@@ -633,20 +618,7 @@ int hg_table_gather_diff_f32(const int32_t *idx, int32_t rows, int32_t k, int32_
   if (!ctr) return fail(entry, HG_ERR_INVALID, "null ctr");
   if (const int st = gather_refusal(entry, rows, k, n, F, src, w, src_scale, dst_scale, dst)) return st;
   if ((uintptr_t)idx % 4 || (uintptr_t)ctr % 4) return fail(entry, HG_ERR_UNSUPPORTED, "idx and ctr must be 4-byte aligned");
-  TableGatherArgs a{};
-  a.idx = idx;
-  a.src = src;
-  a.w = w;
-  a.src_scale = src_scale;
-  a.dst_scale = dst_scale;
-  a.ctr = ctr;
-  a.dst = dst;
-  a.nrows = rows;
-  a.nsrc = n;
-  a.k = k;
-  a.F = F;
-  a.entries = rows * k;
-  return launch_table_gather<false, true>(entry, a, static_cast<hipStream_t>(stream));
+  return launch_table_gather<false, true>(entry, idx, nullptr, nullptr, rows, k, n, F, src, w, src_scale, dst_scale, ctr, dst, stream);
 }
 
 int hg_table_gather_t_diff_f32(const int32_t *ptr_v, const int32_t *pos_v, int32_t rows, int32_t k, int32_t n, int32_t F,
@@ -659,21 +631,7 @@ int hg_table_gather_t_diff_f32(const int32_t *ptr_v, const int32_t *pos_v, int32
   if (const int st = gather_refusal(entry, rows, k, n, F, src, w, src_scale, dst_scale, dst)) return st;
   if ((uintptr_t)ptr_v % 4 || (uintptr_t)pos_v % 4 || (uintptr_t)ctr % 4)
     return fail(entry, HG_ERR_UNSUPPORTED, "ptr_v, pos_v and ctr must be 4-byte aligned");
-  TableGatherArgs a{};
-  a.ptr_v = ptr_v;
-  a.pos_v = pos_v;
-  a.src = src;
-  a.w = w;
-  a.src_scale = src_scale;
-  a.dst_scale = dst_scale;
-  a.ctr = ctr;
-  a.dst = dst;
-  a.nrows = n;
-  a.nsrc = rows;
-  a.k = k;
-  a.F = F;
-  a.entries = rows * k;
-  return launch_table_gather<true, true>(entry, a, static_cast<hipStream_t>(stream));
+  return launch_table_gather<true, true>(entry, nullptr, ptr_v, pos_v, rows, k, n, F, src, w, src_scale, dst_scale, ctr, dst, stream);
 }
 
 int hg_table_dist_f32(const int32_t *idx, int32_t rows, int32_t k, int32_t n, int32_t F, const float *Q, const float *X,

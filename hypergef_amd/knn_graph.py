@@ -26,6 +26,34 @@ FORMS = ("difference", "dot")
 DOT_F_MAX = 65536  # form="dot": the widest rows the error bound is derived for (hg_knn.h, kDotMaxF)
 
 
+_NO_FORM = " (%s has no bfloat16 / float16 / float64 form)"
+
+
+def _check_dtype(t, label, dtype, note=""):
+    """TypeError unless t is a tensor of `dtype`, torch.float32 or torch.int32; `note` follows "tensor" in the text."""
+    if not isinstance(t, torch.Tensor) or t.dtype != dtype:
+        raise TypeError("%s must be %s tensor%s, got %s" % (label, "a float32" if dtype == torch.float32 else "an int32", note,
+                                                            getattr(t, "dtype", type(t))))
+
+
+def _check_transpose_types(transpose):
+    """The first phase of the check of a `transpose` argument, with the caller's other TypeErrors: None, or the pair
+    (ptr_v, pos_v) of int32 tensors."""
+    if transpose is None:
+        return
+    if not isinstance(transpose, (tuple, list)) or len(transpose) != 2:
+        raise TypeError("transpose must be the pair (ptr_v, pos_v) of knn_transpose")
+    for name, t in zip(("ptr_v", "pos_v"), transpose):
+        _check_dtype(t, "transpose's " + name, torch.int32)
+
+
+def _check_transpose_shapes(transpose, n, entries):
+    """The second phase, with the caller's other ValueErrors: ptr_v [n + 1] and pos_v [entries]."""
+    if transpose is not None and (tuple(transpose[0].shape) != (n + 1,) or tuple(transpose[1].shape) != (entries,)):
+        raise ValueError("transpose must be (ptr_v [%d], pos_v [%d]), got %s and %s"
+                         % (n + 1, entries, tuple(transpose[0].shape), tuple(transpose[1].shape)))
+
+
 def _segment_offsets(segments, n, k):
     """The host offsets [B + 1] of `segments` as int32, checked: 0 first, n last, ascending, every segment of at least k rows."""
     if isinstance(segments, torch.Tensor):
@@ -75,12 +103,9 @@ def knn(X, k, queries=None, segments=None, self_first=None, return_mean=False, c
     but float32; ValueError for an unknown form, for k outside 1 .. min(64, n), for segments or self_first together with
     queries, for form="dot" with segments or with F above 65536, for a segment shorter than k; RuntimeError for CPU
     tensors."""
-    for name, t in (("X", X), ("queries", queries)):
-        if t is None and name == "queries":
-            continue
-        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32:
-            raise TypeError("%s must be a float32 tensor (knn has no bfloat16 / float16 / float64 form), got %s"
-                            % (name, getattr(t, "dtype", type(t))))
+    _check_dtype(X, "X", torch.float32, _NO_FORM % "knn")
+    if queries is not None:
+        _check_dtype(queries, "queries", torch.float32, _NO_FORM % "knn")
     if X.dim() != 2 or X.shape[1] < 1:
         raise ValueError("X must be [n, F] with F >= 1, got %s" % (tuple(X.shape),))
     n, F = X.shape
@@ -165,13 +190,12 @@ def incidence_from_knn(idx, name="knn"):
 # ---- aggregation over the neighbour table itself, no plan (include/hg_aggr.h, hg_table_*) ---------------------------------
 
 def _table_shape(idx):
-    """(rows, k) of a neighbour table, checked: the dtype first (TypeError), then the shape and k (ValueError)."""
-    if not isinstance(idx, torch.Tensor) or idx.dtype != torch.int32:
-        raise TypeError("idx must be an int32 tensor [rows, k] (ops.knn's table), got %s" % (getattr(idx, "dtype", type(idx)),))
-    return idx.shape
+    """The first phase of a neighbour table's check, with the caller's other TypeErrors: the dtype."""
+    _check_dtype(idx, "idx", torch.int32, " [rows, k] (ops.knn's table)")
 
 
 def _table_shape_values(idx):
+    """The second phase: (rows, k), with the shape and k checked (ValueError)."""
     if idx.dim() != 2 or idx.shape[0] < 1:
         raise ValueError("idx must be [rows >= 1, k], got %s" % (tuple(idx.shape),))
     rows, k = idx.shape
@@ -245,13 +269,11 @@ def table_gather(idx, src, w=None, src_scale=None, dst_scale=None, ctr=None):
     dst_scale = _flat_or_none(dst_scale, "dst_scale", rows, dev)
     ctr = _flat_or_none(ctr, "ctr", rows * F, dev)
     dst = torch.empty((rows, F), dtype=torch.float32, device=dev)
+    L = _lib.lib()
+    entry, centre = (L.hg_table_gather_f32, ()) if ctr is None else (L.hg_table_gather_diff_f32, (_ptr(ctr),))
     with torch.cuda.device(dev):
-        if ctr is None:
-            _lib.check(_lib.lib().hg_table_gather_f32(_ptr(idx), rows, k, n, F, _ptr(src), _ptr(w), _ptr(src_scale),
-                                                      _ptr(dst_scale), _ptr(dst), _stream_handle(dev)))
-        else:
-            _lib.check(_lib.lib().hg_table_gather_diff_f32(_ptr(idx), rows, k, n, F, _ptr(src), _ptr(w), _ptr(src_scale),
-                                                           _ptr(dst_scale), _ptr(ctr), _ptr(dst), _stream_handle(dev)))
+        _lib.check(entry(_ptr(idx), rows, k, n, F, _ptr(src), _ptr(w), _ptr(src_scale), _ptr(dst_scale), *centre, _ptr(dst),
+                         _stream_handle(dev)))
     return dst
 
 
@@ -261,9 +283,8 @@ def table_gather_t(ptr_v, pos_v, k, src, w=None, src_scale=None, dst_scale=None,
     hg_table_gather_t_f32.  A row of at most TABLE_SEQ_MAX entries is summed in ascending q; a longer one by its whole
     workgroup in an order fixed by its length and F.  A vertex with no entry is +0.0 whatever dst_scale.  No gradient.
     ctr [n, F]: the difference gather hg_table_gather_t_diff_f32 -- the term starts from ctr[v] - src[pos_v[q] // k]."""
-    for name, t in (("ptr_v", ptr_v), ("pos_v", pos_v)):
-        if not isinstance(t, torch.Tensor) or t.dtype != torch.int32:
-            raise TypeError("%s must be an int32 tensor, got %s" % (name, getattr(t, "dtype", type(t))))
+    _check_dtype(ptr_v, "ptr_v", torch.int32)
+    _check_dtype(pos_v, "pos_v", torch.int32)
     if not isinstance(k, numbers.Integral) or isinstance(k, bool) or not 1 <= k <= K_MAX:
         raise ValueError("k must be an integer in 1 .. %d, got %r" % (K_MAX, k))
     if ptr_v.dim() != 1 or ptr_v.shape[0] < 2 or pos_v.dim() != 1:
@@ -281,14 +302,11 @@ def table_gather_t(ptr_v, pos_v, k, src, w=None, src_scale=None, dst_scale=None,
     dst_scale = _flat_or_none(dst_scale, "dst_scale", n, dev)
     ctr = _flat_or_none(ctr, "ctr", n * F, dev)
     dst = torch.empty((n, F), dtype=torch.float32, device=dev)
+    L = _lib.lib()
+    entry, centre = (L.hg_table_gather_t_f32, ()) if ctr is None else (L.hg_table_gather_t_diff_f32, (_ptr(ctr),))
     with torch.cuda.device(dev):
-        if ctr is None:
-            _lib.check(_lib.lib().hg_table_gather_t_f32(_ptr(ptr_v), _ptr(pos_v), rows, int(k), n, F, _ptr(src), _ptr(w),
-                                                        _ptr(src_scale), _ptr(dst_scale), _ptr(dst), _stream_handle(dev)))
-        else:
-            _lib.check(_lib.lib().hg_table_gather_t_diff_f32(_ptr(ptr_v), _ptr(pos_v), rows, int(k), n, F, _ptr(src), _ptr(w),
-                                                             _ptr(src_scale), _ptr(dst_scale), _ptr(ctr), _ptr(dst),
-                                                             _stream_handle(dev)))
+        _lib.check(entry(_ptr(ptr_v), _ptr(pos_v), rows, int(k), n, F, _ptr(src), _ptr(w), _ptr(src_scale), _ptr(dst_scale),
+                         *centre, _ptr(dst), _stream_handle(dev)))
     return dst
 
 
@@ -365,18 +383,10 @@ def knn_dist(idx, X, queries=None, transpose=None):
     float32 only.  Refusals, in this order and before a device is touched: TypeError for an idx (ptr_v, pos_v) that is not
     int32 and an X or queries that is not float32; ValueError for the shapes and k; RuntimeError for CPU tensors."""
     _table_shape(idx)
-    for name, t in (("X", X), ("queries", queries)):
-        if t is None and name == "queries":
-            continue
-        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32:
-            raise TypeError("%s must be a float32 tensor (knn_dist has no bfloat16 / float16 / float64 form), got %s"
-                            % (name, getattr(t, "dtype", type(t))))
-    if transpose is not None:
-        if not isinstance(transpose, (tuple, list)) or len(transpose) != 2:
-            raise TypeError("transpose must be the pair (ptr_v, pos_v) of knn_transpose")
-        for name, t in zip(("ptr_v", "pos_v"), transpose):
-            if not isinstance(t, torch.Tensor) or t.dtype != torch.int32:
-                raise TypeError("transpose's %s must be an int32 tensor, got %s" % (name, getattr(t, "dtype", type(t))))
+    _check_dtype(X, "X", torch.float32, _NO_FORM % "knn_dist")
+    if queries is not None:
+        _check_dtype(queries, "queries", torch.float32, _NO_FORM % "knn_dist")
+    _check_transpose_types(transpose)
     rows, k = _table_shape_values(idx)
     if X.dim() != 2 or X.shape[0] < 1 or X.shape[1] < 1:
         raise ValueError("X must be [n >= 1, F >= 1], got %s" % (tuple(X.shape),))
@@ -386,9 +396,7 @@ def knn_dist(idx, X, queries=None, transpose=None):
             raise ValueError("without queries idx must have one row per row of X: %d rows, X has %d" % (rows, n))
     elif tuple(queries.shape) != (rows, F):
         raise ValueError("queries must be [rows, F] = [%d, %d], got %s" % (rows, F, tuple(queries.shape)))
-    if transpose is not None and (tuple(transpose[0].shape) != (n + 1,) or tuple(transpose[1].shape) != (rows * k,)):
-        raise ValueError("transpose must be (ptr_v [%d], pos_v [%d]), got %s and %s"
-                         % (n + 1, rows * k, tuple(transpose[0].shape), tuple(transpose[1].shape)))
+    _check_transpose_shapes(transpose, n, rows * k)
     _check_table_index(idx, "idx")
     _check_feat(X, "X", device=idx.device)
     if queries is not None:
@@ -405,44 +413,26 @@ def knn_dist(idx, X, queries=None, transpose=None):
 
 class _KnnAggr(torch.autograd.Function):
     """Y = degV . H_w (degE . (H_w^T X)) over a neighbour table; the gradient of X is the same two gathers swapped.  Saves the
-    table, its transpose, the weight and the scales -- nothing of rows * F elements."""
-
-    @staticmethod
-    def forward(ctx, X, idx, ptr_v, pos_v, w, degE, degV):
-        k = idx.shape[1]
-        Xe = table_gather(idx, X, w, None, degE)
-        Y = table_gather_t(ptr_v, pos_v, k, Xe, w, None, degV)
-        ctx.save_for_backward(idx, ptr_v, pos_v, w, degE, degV)
-        return Y
-
-    @staticmethod
-    def backward(ctx, dY):
-        idx, ptr_v, pos_v, w, degE, degV = ctx.saved_tensors
-        G = table_gather(idx, dY.contiguous(), w, degV, degE)
-        dX = table_gather_t(ptr_v, pos_v, idx.shape[1], G, w)
-        return dX, None, None, None, None, None, None
-
-
-class _KnnAggrWeighted(torch.autograd.Function):
-    """_KnnAggr with the gradient of the weight: dw[p = (i, s)] = degV[v] <dY[v], Xe[i]> + <X[v], G[i]>, v = idx[i, s], one
-    launch of hg_table_dot_f32.  Xe is computed again in the backward; what is saved beyond _KnnAggr's is the input X."""
+    table, its transpose, the weight and the scales -- nothing of rows * F elements.  Where the weight asks for its gradient,
+    dw[p = (i, s)] = degV[v] <dY[v], Xe[i]> + <X[v], G[i]>, v = idx[i, s], one launch of hg_table_dot_f32: Xe is computed
+    again in the backward, and the input X is saved as well."""
 
     @staticmethod
     def forward(ctx, X, w, idx, ptr_v, pos_v, degE, degV):
-        k = idx.shape[1]
         Xe = table_gather(idx, X, w, None, degE)
-        Y = table_gather_t(ptr_v, pos_v, k, Xe, w, None, degV)
-        ctx.save_for_backward(X, w, idx, ptr_v, pos_v, degE, degV)
+        Y = table_gather_t(ptr_v, pos_v, idx.shape[1], Xe, w, None, degV)
+        ctx.save_for_backward(idx, ptr_v, pos_v, w, degE, degV, *((X,) if ctx.needs_input_grad[1] else ()))
         return Y
 
     @staticmethod
     def backward(ctx, dY):
-        X, w, idx, ptr_v, pos_v, degE, degV = ctx.saved_tensors
+        idx, ptr_v, pos_v, w, degE, degV = ctx.saved_tensors[:6]
         dY = dY.contiguous()
         G = table_gather(idx, dY, w, degV, degE)
         dX = table_gather_t(ptr_v, pos_v, idx.shape[1], G, w) if ctx.needs_input_grad[0] else None
         dw = None
         if ctx.needs_input_grad[1]:
+            X = ctx.saved_tensors[6]
             Xe = table_gather(idx, X, w, None, degE)
             dw = table_dot(idx, dY, Xe, degV, X, G).view(w.shape)
         return dX, dw, None, None, None, None, None
@@ -466,19 +456,12 @@ def knn_aggr(idx, X, weight=None, degE=None, degV=None, transpose=None, weight_g
     an X, weight, degE or degV that is not float32; ValueError for the shapes and k; RuntimeError for a weight, degE or
     degV that requires a gradient, and for CPU tensors."""
     _table_shape(idx)
-    if not isinstance(X, torch.Tensor) or X.dtype != torch.float32:
-        raise TypeError("X must be a float32 tensor (knn_aggr has no bfloat16 / float16 / float64 form), got %s"
-                        % (getattr(X, "dtype", type(X)),))
+    _check_dtype(X, "X", torch.float32, _NO_FORM % "knn_aggr")
     scales = (("weight", weight), ("degE", degE), ("degV", degV))
     for name, t in scales:
-        if t is not None and (not isinstance(t, torch.Tensor) or t.dtype != torch.float32):
-            raise TypeError("%s must be a float32 tensor, got %s" % (name, getattr(t, "dtype", type(t))))
-    if transpose is not None:
-        if not isinstance(transpose, (tuple, list)) or len(transpose) != 2:
-            raise TypeError("transpose must be the pair (ptr_v, pos_v) of knn_transpose")
-        for name, t in zip(("ptr_v", "pos_v"), transpose):
-            if not isinstance(t, torch.Tensor) or t.dtype != torch.int32:
-                raise TypeError("transpose's %s must be an int32 tensor, got %s" % (name, getattr(t, "dtype", type(t))))
+        if t is not None:
+            _check_dtype(t, name, torch.float32)
+    _check_transpose_types(transpose)
     rows, k = _table_shape_values(idx)
     if X.dim() != 2 or X.shape[0] < 1 or X.shape[1] < 1:
         raise ValueError("X must be [n >= 1, F >= 1], got %s" % (tuple(X.shape),))
@@ -488,9 +471,7 @@ def knn_aggr(idx, X, weight=None, degE=None, degV=None, transpose=None, weight_g
     for name, t, count in (("degE", degE, rows), ("degV", degV, n)):
         if t is not None and tuple(t.shape) not in ((count,), (count, 1)):
             raise ValueError("%s must be [%d] or [%d, 1], got %s" % (name, count, count, tuple(t.shape)))
-    if transpose is not None and (tuple(transpose[0].shape) != (n + 1,) or tuple(transpose[1].shape) != (rows * k,)):
-        raise ValueError("transpose must be (ptr_v [%d], pos_v [%d]), got %s and %s"
-                         % (n + 1, rows * k, tuple(transpose[0].shape), tuple(transpose[1].shape)))
+    _check_transpose_shapes(transpose, n, rows * k)
     if torch.is_grad_enabled():
         for name, t in scales:
             if t is not None and t.requires_grad and not (weight_grad and name == "weight"):
@@ -505,10 +486,10 @@ def knn_aggr(idx, X, weight=None, degE=None, degV=None, transpose=None, weight_g
     ptr_v, pos_v = transpose
     _check_table_index(ptr_v, "ptr_v")
     _check_table_index(pos_v, "pos_v")
-    detach = [None if t is None else t.detach() for _, t in scales]
-    if weight_grad and weight is not None and weight.requires_grad and torch.is_grad_enabled():
-        return _KnnAggrWeighted.apply(X, weight, idx, ptr_v, pos_v, *detach[1:])
-    return _KnnAggr.apply(X, idx, ptr_v, pos_v, *detach)
+    w, degE, degV = (None if t is None else t.detach() for _, t in scales)
+    if weight_grad and weight is not None and weight.requires_grad:
+        w = weight  # the one scale whose gradient is wanted
+    return _KnnAggr.apply(X, w, idx, ptr_v, pos_v, degE, degV)
 
 
 class KnnHypergraph:
