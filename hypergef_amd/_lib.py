@@ -52,6 +52,7 @@ SYMBOLS = (
     "hg_gather_rows_incidence_heads_bf16", "hg_aggr_incidence_heads_bf16", "hg_incidence_dot_heads_bf16",
     "hg_gather_rows_reduce_workspace_bytes", "hg_gather_rows_reduce_f32", "hg_gather_rows_select_f32",
     "hg_knn_f32", "hg_knn_workspace_bytes", "hg_knn_dot_f32", "hg_knn_dot_workspace_bytes",
+    "hg_knn_dot_bf16", "hg_knn_dot_bf16_workspace_bytes", "hg_knn_dot_estimates_bf16",
     "hg_table_seq_max", "hg_table_transpose_workspace_bytes", "hg_table_transpose", "hg_table_gather_f32",
     "hg_table_gather_t_f32",
     "hg_table_dist_f32", "hg_table_gather_diff_f32", "hg_table_gather_t_diff_f32", "hg_table_dot_f32",
@@ -305,6 +306,13 @@ def lib():
         L.hg_knn_dot_workspace_bytes.argtypes = [i32, i32, i32, i32, i32]
         L.hg_knn_dot_f32.restype = ctypes.c_int
         L.hg_knn_dot_f32.argtypes = [vp, i32, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, sz, vp]
+    if hasattr(L, "hg_knn_dot_bf16"):  # likewise: that search on bfloat16 rows, and its diagnostic (est, e1)
+        L.hg_knn_dot_bf16_workspace_bytes.restype = sz
+        L.hg_knn_dot_bf16_workspace_bytes.argtypes = [i32, i32, i32, i32, i32]
+        L.hg_knn_dot_bf16.restype = ctypes.c_int
+        L.hg_knn_dot_bf16.argtypes = [vp, i32, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, sz, vp]
+        L.hg_knn_dot_estimates_bf16.restype = ctypes.c_int
+        L.hg_knn_dot_estimates_bf16.argtypes = [vp, i32, vp, i32, i32, vp, vp, vp]
     if hasattr(L, "hg_table_transpose"):  # likewise: aggregation over a neighbour table, no plan
         L.hg_table_seq_max.restype = ctypes.c_int
         L.hg_table_seq_max.argtypes = []

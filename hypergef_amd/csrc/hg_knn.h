@@ -42,6 +42,10 @@ constexpr int kDotLd = 33;          // odd: the 32 rows and the two columns of a
 constexpr int kDotNormRows = 64;    // rows per workgroup of the norm kernel (one block maximum each)
 constexpr int kDotMaxF = 65536;     // the error bound's derivation assumes (F + 1) 2^-24 <= 2^-8 + 2^-24
 constexpr int kDotRerankRows = 64;  // the rerank kernel's batch: one candidate row per lane
+// bfloat16 rows (hg_knn_dot_bf16): the same workgroup and tiles on v_mfma_f32_32x32x16_bf16, 16 columns per instruction
+constexpr int kDotBfFC = 64;        // columns per LDS chunk: 128 bytes a row, four instructions
+constexpr int kDotBfLd = 72;        // row pitch in elements, 144 bytes: nine 16-byte slots, odd, for the 16-byte operand reads
+constexpr int64_t kDotEstimatesMax = 1 << 22;  // hg_knn_dot_estimates_bf16 (a diagnostic): nq * n above this is refused
 
 // Shortlist slots per lane for k: the shortlist holds 32 * knn_dot_slots(k) entries, at least k + 16 (slack 16 .. 47).
 inline int knn_dot_slots(int k) { return (k + 16 + 31) / 32; }

@@ -57,10 +57,11 @@ class HyperGraph:
         self_first on `device`, then M = N, H_T_csrptr = arange(0, N k + 1, k), H_T_colind = idx flattened.  segments:
         ops.knn's -- many point sets in one tensor, neighbours within a set.  The neighbour table is read back once (the
         plan is built on the host).  Keeps knn_dist [N, k] (squared), knn_mean [N] and knn_weights().  form: ops.knn's -- "dot"
-        builds the same hypergraph and knn_dist through the matrix-unit prefilter; knn_mean is then the dot form's."""
+        builds the same hypergraph and knn_dist through the matrix-unit prefilter; knn_mean is then the dot form's.  Under
+        "dot" X may be bfloat16 (ops.knn's bfloat16 rows): the hypergraph and knn_dist (float32) are those of X.float()."""
         from . import knn_graph as _knn
         Xd = torch.as_tensor(X).detach()
-        if Xd.dtype == torch.float32:  # anything else is ops.knn's refusal
+        if Xd.dtype == torch.float32 or (form == "dot" and Xd.dtype == torch.bfloat16):  # anything else is ops.knn's refusal
             Xd = Xd.to(device).contiguous()
         idx, dist, mean = _knn.knn(Xd, k, segments=segments, self_first=True, return_mean=True, form=form)
         self = cls.__new__(cls)

@@ -27,6 +27,7 @@ DOT_F_MAX = 65536  # form="dot": the widest rows the error bound is derived for 
 
 
 _NO_FORM = " (%s has no bfloat16 / float16 / float64 form)"
+_KNN_NO_FORM = ' (knn has no float16 / float64 form; form="dot" takes bfloat16 rows, X and queries alike)'
 
 
 def _check_dtype(t, label, dtype, note=""):
@@ -98,14 +99,25 @@ def knn(X, k, queries=None, segments=None, self_first=None, return_mean=False, c
     segments and rows of at most 65536 columns, and neither waits nor reads back.  return_fallback: one more result,
     int32 [nq], 1 where the row was not certified and took the exhaustive path, else 0 (all 0 under "difference").
 
+    bfloat16 rows: form="dot" takes a bfloat16 X (queries, where given, bfloat16 too; hg_knn_dot_bf16).  idx and dist
+    (float32, never an estimate, never rounded) are what knn(X.float(), ..., form="difference") returns, bit for bit, for
+    the same arguments; the prefilter runs on the bf16 matrix unit under its own bound E1b (include/hg_aggr.h), mean is
+    the mean of those estimates, and everything else above holds.  Under every other form bfloat16 is refused.
+
     Not differentiable: raises if X (or queries) requires a gradient while grad mode is on; call it under
     torch.no_grad() or on X.detach().  Refusals, in this order and before a device is touched: TypeError for anything
-    but float32; ValueError for an unknown form, for k outside 1 .. min(64, n), for segments or self_first together with
-    queries, for form="dot" with segments or with F above 65536, for a segment shorter than k; RuntimeError for CPU
-    tensors."""
-    _check_dtype(X, "X", torch.float32, _NO_FORM % "knn")
-    if queries is not None:
-        _check_dtype(queries, "queries", torch.float32, _NO_FORM % "knn")
+    but float32 (or, under form="dot", bfloat16 for X and queries alike); ValueError for an unknown form, for k outside
+    1 .. min(64, n), for segments or self_first together with queries, for form="dot" with segments or with F above
+    65536, for a segment shorter than k; RuntimeError for CPU tensors."""
+    bf16 = form == "dot" and isinstance(X, torch.Tensor) and X.dtype == torch.bfloat16
+    if bf16:
+        if queries is not None and not (isinstance(queries, torch.Tensor) and queries.dtype == torch.bfloat16):
+            raise TypeError("queries must be a bfloat16 tensor where X is one (X and queries are both float32 or both "
+                            "bfloat16), got %s" % getattr(queries, "dtype", type(queries)))
+    else:
+        _check_dtype(X, "X", torch.float32, _KNN_NO_FORM)
+        if queries is not None:
+            _check_dtype(queries, "queries", torch.float32, _KNN_NO_FORM)
     if X.dim() != 2 or X.shape[1] < 1:
         raise ValueError("X must be [n, F] with F >= 1, got %s" % (tuple(X.shape),))
     n, F = X.shape
@@ -134,9 +146,9 @@ def knn(X, k, queries=None, segments=None, self_first=None, return_mean=False, c
         raise ValueError("cand_slices must be 0 (auto) or 1 .. %d, got %r" % (SLICES_MAX, cand_slices))
     if torch.is_grad_enabled() and (X.requires_grad or (queries is not None and queries.requires_grad)):
         raise RuntimeError("knn is not differentiable: call it under torch.no_grad() or on X.detach()")
-    _check_feat(X, "X")
+    _check_feat(X, "X", bf16_ok=bf16)
     if queries is not None:
-        _check_feat(queries, "queries", device=X.device)
+        _check_feat(queries, "queries", device=X.device, bf16_ok=bf16)
     if self_first is None:
         self_first = queries is None
     Q = X if queries is None else queries
@@ -148,11 +160,15 @@ def knn(X, k, queries=None, segments=None, self_first=None, return_mean=False, c
     mean = torch.empty(nq, dtype=torch.float32, device=dev) if return_mean else None
     if form == "dot":
         fallback = torch.empty(nq, dtype=torch.int32, device=dev) if return_fallback else None
-        ws_bytes = L.hg_knn_dot_workspace_bytes(nq, n, F, k, cand_slices)
+        if bf16 and not hasattr(L, "hg_knn_dot_bf16"):
+            raise RuntimeError("this build of libhgaggr has no hg_knn_dot_bf16 (bfloat16 rows under form=\"dot\")")
+        entry, sizes = ((L.hg_knn_dot_bf16, L.hg_knn_dot_bf16_workspace_bytes) if bf16 else
+                        (L.hg_knn_dot_f32, L.hg_knn_dot_workspace_bytes))
+        ws_bytes = sizes(nq, n, F, k, cand_slices)
         ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
         with torch.cuda.device(dev):
-            _lib.check(L.hg_knn_dot_f32(_ptr(Q), nq, _ptr(X), n, F, k, 1 if self_first else 0, cand_slices, _ptr(idx),
-                                        _ptr(dist), _ptr(mean), _ptr(fallback), _ptr(ws), ws_bytes, _stream_handle(dev)))
+            _lib.check(entry(_ptr(Q), nq, _ptr(X), n, F, k, 1 if self_first else 0, cand_slices, _ptr(idx), _ptr(dist),
+                             _ptr(mean), _ptr(fallback), _ptr(ws), ws_bytes, _stream_handle(dev)))
     else:
         ws_bytes = L.hg_knn_workspace_bytes(nq, n, F, k, cand_slices)
         ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev) if ws_bytes else None
@@ -504,7 +520,9 @@ class KnnHypergraph:
         stays detached: its gradient is an N x N sum and HGNN treats avg_dis as a constant of the construction.
       aggregate(Z, probabilistic=False, m_prob=1.0, X=None): ops.knn_aggr over the table; X goes to weights, and the
         weights then get their gradient (weight_grad=True).
-    form: ops.knn's -- "dot" gives the same idx and dist through the matrix-unit prefilter, and its own mean."""
+    form: ops.knn's -- "dot" gives the same idx and dist through the matrix-unit prefilter, and its own mean.  Under "dot" X
+    may be bfloat16: the table, dist, mean, transpose and degrees are int32 / float32 as always; aggregate, ops.knn_aggr and
+    ops.knn_dist stay float32 only."""
 
     @classmethod
     def build(cls, X, k, segments=None, form="difference"):

@@ -154,7 +154,13 @@ class DynamicHypergraphConv(nn.Module):
     -- what a learnable metric needs.  The output keeps its bits; the table is still searched on detached rows (the
     selection has no gradient) and `mean` is a constant of the construction.  No parameter is added, the layer still
     waits nowhere with segments=None and is still recorded into a hipGraph.  False (the default) is the layer above, bit for
-    bit, with the same saved tensors."""
+    bit, with the same saved tensors.
+    After .to(torch.bfloat16), with knn_form="dot" and device_graph=False, the layer runs on bfloat16 rows: the neighbours are
+    searched on the bfloat16 input itself (ops.knn's bfloat16 rows: the hypergraph of X.float(), float32 distances), the
+    unweighted sums run on the bfloat16 HGNNAggr, and probabilistic=True turns Options.incidence_bf16 = 'rows' on for the
+    layer's own HGNNAggrIncidence call, the weights staying float32.  device_graph=True on bfloat16 input still raises
+    ops.knn_aggr's TypeError (the table gathers are float32 only), and under knn_form="difference" the search refuses
+    bfloat16.  float32 layers are untouched."""
 
     def __init__(self, in_channels, out_channels, k, probabilistic=False, segments=None, m_prob=1.0, options=None,
                  device_graph=False, knn_form="difference", learn_distances=False):
@@ -186,7 +192,10 @@ class DynamicHypergraphConv(nn.Module):
         Wdiag = torch.ones(hyperg.num_edges, device=X.device)
         if self.probabilistic:
             w = hyperg.knn_weights(self.m_prob)
-            return ops.HGNNAggrIncidence(hyperg, Z, w, w, hyperg.degE, hyperg.degV, Wdiag, options=self.options)
+            options = self.options
+            if Z.dtype == torch.bfloat16:  # bfloat16 rows for this call, as HypergraphAttnConv does; w stays float32
+                options = (options if options is not None else ops.current_options()).replace(incidence_bf16="rows")
+            return ops.HGNNAggrIncidence(hyperg, Z, w, w, hyperg.degE, hyperg.degV, Wdiag, options=options)
         return HGNNAggr(hyperg, Z, hyperg.degE, hyperg.degV, Wdiag, "sum", options=self.options)
 
 

@@ -883,6 +883,44 @@ HG_API int hg_knn_dot_f32(const float *Q, int32_t nq, const float *X, int32_t n,
                           void *workspace, size_t workspace_bytes, hg_stream_t stream);
 HG_API size_t hg_knn_dot_workspace_bytes(int32_t nq, int32_t n, int32_t F, int32_t k, int32_t cand_slices);
 
+/* hg_knn_dot_f32 for bfloat16 rows (Q, X: bfloat16 bits, row-major, 2-byte aligned), the prefilter on
+ * v_mfma_f32_32x32x16_bf16.  idx and dist are what hg_knn_f32 -- and so hg_knn_dot_f32 -- returns for the rows widened to
+ * float32, BIT FOR BIT, on every input: the rerank and the exhaustive path read the bfloat16 rows, widen each element at
+ * the load (exact) and then run hg_knn_f32's arithmetic.  dist is float32 and never holds an estimate.  Everything said of
+ * hg_knn_dot_f32 holds -- kp, the shortlists, self_first, cand_slices, fallback, mean_dist (the mean of the bf16 estimates:
+ * within mean_j sqrt(E1b) and the float32 summation error of the exact mean), the workspace (the same size:
+ * hg_knn_dot_bf16_workspace_bytes), five launches, nothing allocated, copied or waited for, the refusals and their order
+ * (the alignment: 2 bytes for Q and X, 4 for the rest) -- with this estimate and this bound in place of E1:
+ *   n2[j] as above on the widened values (the bits of hg_knn_dot_f32's norm of the widened row); s~(i, j) accumulated by
+ *   G = ceil(F / 16) instructions, instruction g taking columns 16 g .. 16 g + 15 (zeros past F) in every tiling;
+ *   d~ = (n2q[i] + n2[j]) - 2 s~.
+ *   Products of bfloat16 values are exact in float32.  The order and rounding of the instruction's sum are not documented;
+ *   the bound rests on one HYPOTHESIS H: for exact products p_0 .. p_15 the result acc' of one instruction satisfies
+ *     |acc' - (acc + sum p_i)| <= 17 v (|acc| + sum |p_i|),  v = 2^-23,
+ *   up to quantities flushed to zero (below), and bfloat16 subnormal inputs are read at their value.  H holds for
+ *   round-to-nearest additions in any order (at most 8 v) and for alignment to the largest exponent with truncation and no
+ *   guard bit (16 v for the other sixteen terms, v for the result).  Over G instructions
+ *     |s~ - S| <= ((1 + 17 v)^G - 1) sum_c |q_c x_c| <= 34 G u 1.0042 (Nq + Nx) / 2,  u = 2^-24, G <= 4096,
+ *   and with the norms' F-term fma chains, as for E1,
+ *     E1b = C_b u (n2q[i] + max_j n2[j]) + (65 G + 1) 2^-126,   C_b = (F + 34 G + 4)(1 + 1/64) rounded up to an integer,
+ *     Ei  = E1b + (F + 4) u max(T, 0).
+ *   The absolute term is sized for a matrix unit that flushes subnormal products and partial sums to zero: at most 2^-126 is
+ *   lost per flushed quantity, an instruction has 16 products and 16 partial sums, so s~ loses at most 32 G 2^-126 (1 + 17 v)^G
+ *   and d~ twice that, below (65 G) 2^-126; the last 2^-126 covers the gradual underflow of the fewer than 4 F + 8 vector
+ *   operations.  The certificate is hg_knn_dot_f32's with E1b: the k-th d2 strictly below T - Ei, or n <= kp; and
+ *   n2q + n2max < 1e37 and every shortlist slot filled. */
+HG_API int hg_knn_dot_bf16(const uint16_t *Q, int32_t nq, const uint16_t *X, int32_t n, int32_t F, int32_t k, int32_t self_first,
+                           int32_t cand_slices, int32_t *idx, float *dist, float *mean_dist, int32_t *fallback,
+                           void *workspace, size_t workspace_bytes, hg_stream_t stream);
+HG_API size_t hg_knn_dot_bf16_workspace_bytes(int32_t nq, int32_t n, int32_t F, int32_t k, int32_t cand_slices);
+/* A DIAGNOSTIC, not part of any computation: est [nq, n] receives the raw estimate d~(i, j) of every pair (no self_first, no
+ * clamp) and e1 [nq] the rows' E1b, from the same device code that forms the prefilter's tiles, so that H can be checked
+ * against the hardware: |est - d2_exact| <= e1 must hold for every pair.  Unlike every other entry it allocates (the norms),
+ * and it waits for `stream` before it returns.  HG_ERR_INVALID for a null pointer, nq, n or F < 1, F > 65536;
+ * HG_ERR_UNSUPPORTED for nq * n above 2^22 or a misaligned pointer. */
+HG_API int hg_knn_dot_estimates_bf16(const uint16_t *Q, int32_t nq, const uint16_t *X, int32_t n, int32_t F, float *est,
+                                     float *e1, hg_stream_t stream);
+
 /* Aggregation over a dense neighbour table, with no plan (csrc/hg_table.hip).  idx [rows, k] int32 is what hg_knn_f32
  * writes: hyperedge i has the k members idx[i, 0 .. k - 1], so H_T is the table itself (csrptr_t an arange) and position
  * p = i k + s of the table is entry s of hyperedge i.  1 <= k <= 64 and rows * k < 2^31.  None of the three entries
