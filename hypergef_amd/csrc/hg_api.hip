@@ -698,47 +698,26 @@ int run_segments(const char *who, const hg_plan *plan, int body, int side, const
   a.nseg = side == 0 ? plan->M : plan->N;
   a.own = side == 0 ? se : sv;
   a.other = side == 0 ? sv : se;
-  hipError_t e;
-  if (entry) {  // one block for every form: heads >= 1, drop or none
-    hg::SegEntryArgs ae = {};
-    static_cast<hg::SegArgs &>(ae) = a;
-    ae.heads = heads;
-    if (drop) ae.drop = *drop;
-    ae.entry = entry;
-    e = hg::launch_segments_entry(body, side, width, ae, stream);
-  } else if (drop && heads > 1) {
-    hg::SegDropHeadsArgs ad;
-    static_cast<hg::SegArgs &>(ad) = a;
-    ad.heads = heads;
-    ad.drop = *drop;
-    e = hg::launch_segments_drop_heads(body, side, width, ad, stream);
-  } else if (drop) {
-    hg::SegDropArgs ad;
-    static_cast<hg::SegArgs &>(ad) = a;
-    ad.drop = *drop;
-    e = hg::launch_segments_drop(body, side, width, ad, stream);
-  } else if (heads > 1) {  // scores [*, heads], entry arrays [nnz, heads]
-    hg::SegHeadsArgs ah;
-    static_cast<hg::SegArgs &>(ah) = a;
-    ah.heads = heads;
-    e = hg::launch_segments_heads(body, side, width, ah, stream);
-  } else {
-    e = hg::launch_segments(body, side, width, a, stream);
-  }
+  // heads = 1 without dropout or entry logit runs the SegArgs instances; an entry logit takes the one block that has it
+  // (heads >= 1, drop or none)
+  const auto launch = [&](const auto &block) { return hg::launch_segments(body, side, width, block, stream); };
+  const hg::SegHeadsArgs ah = {a, heads};  // scores [*, heads], entry arrays [nnz, heads]
+  const hipError_t e = entry                ? launch(hg::SegEntryArgs{{ah, drop ? *drop : hg::DropFields{}}, entry})
+                       : drop && heads > 1 ? launch(hg::SegDropHeadsArgs{ah, *drop})
+                       : drop              ? launch(hg::SegDropArgs{a, *drop})
+                       : heads > 1         ? launch(ah)
+                                           : launch(a);
   if (e != hipSuccess) return hip_fail(who, e);
   return HG_OK;
 }
 
 // Refusals of the dropout entries: p_drop in [0, 1) (NaN fails both comparisons) and the state's address; fills T and scale
 int check_dropout(const char *who, float p_drop, const uint64_t *rng_dev, hg::DropFields *d) {
-  if (!(p_drop >= 0.f && p_drop < 1.f)) {
-    hg::set_error(std::string(who) + ": p_drop must lie in [0, 1) (at 1 the scale 1 / (1 - p_drop) is infinite)");
-    return HG_ERR_INVALID;
-  }
-  if (!rng_dev || (reinterpret_cast<uintptr_t>(rng_dev) & 7) != 0) {
-    hg::set_error(std::string(who) + ": rng_dev is null or not 8-byte aligned");
-    return HG_ERR_INVALID;
-  }
+  const std::string pre = std::string(who) + ": ";
+  if (!(p_drop >= 0.f && p_drop < 1.f))
+    return refuse(HG_ERR_INVALID, pre + "p_drop must lie in [0, 1) (at 1 the scale 1 / (1 - p_drop) is infinite)");
+  if (!rng_dev || (reinterpret_cast<uintptr_t>(rng_dev) & 7) != 0)
+    return refuse(HG_ERR_INVALID, pre + "rng_dev is null or not 8-byte aligned");
   d->rng = rng_dev;
   d->T = hg::drop_threshold(p_drop);
   d->scale = 1.0f / (1.0f - p_drop);
@@ -748,24 +727,14 @@ int check_dropout(const char *who, float p_drop, const uint64_t *rng_dev, hg::Dr
 // Refusals the *_heads_f32 entries decide before the single-head rules: a null or host-only plan, heads < 1, and a
 // feature width (F > 0 where the entry has one) that the heads do not divide.
 int check_heads(const char *who, const hg_plan *plan, int32_t heads, int32_t F) {
-  if (!plan) {
-    hg::set_error(std::string(who) + ": null plan");
-    return HG_ERR_INVALID;
-  }
-  if (heads < 1) {
-    hg::set_error(std::string(who) + ": heads must be at least 1");
-    return HG_ERR_INVALID;
-  }
-  if (F > 0 && F % heads != 0) {
-    hg::set_error(std::string(who) + ": the feature width " + std::to_string(F) + " is no multiple of heads = " +
-                  std::to_string(heads));
-    return HG_ERR_INVALID;
-  }
-  if (host_only(plan)) return refuse_host_only(std::string(who) + ": ", "arrays", HG_ERR_UNSUPPORTED);
-  if (heads > 1 && (int64_t)std::max<int64_t>(plan->nnz, std::max(plan->N, plan->M)) * heads >= ((int64_t)1 << 40)) {
-    hg::set_error(std::string(who) + ": nnz * heads too large");
-    return HG_ERR_INVALID;
-  }
+  const std::string pre = std::string(who) + ": ";
+  if (!plan) return refuse(HG_ERR_INVALID, pre + "null plan");
+  if (heads < 1) return refuse(HG_ERR_INVALID, pre + "heads must be at least 1");
+  if (F > 0 && F % heads != 0)
+    return refuse(HG_ERR_INVALID, pre + "the feature width " + std::to_string(F) + " is no multiple of heads = " + std::to_string(heads));
+  if (host_only(plan)) return refuse_host_only(pre, "arrays", HG_ERR_UNSUPPORTED);
+  if (heads > 1 && (int64_t)std::max<int64_t>(plan->nnz, std::max(plan->N, plan->M)) * heads >= ((int64_t)1 << 40))
+    return refuse(HG_ERR_INVALID, pre + "nnz * heads too large");
   return HG_OK;
 }
 
@@ -2312,7 +2281,7 @@ int hg_incidence_attention_f32(const hg_plan *plan, int32_t group, const int32_t
   return hg_incidence_attention_heads_f32(plan, group, 1, csrptr_t, colind_t, sv, se, slope, alpha_out, stream);
 }
 
-// heads == 1 runs exactly what hg_incidence_attention_f32 always ran (run_segments launches the single-head kernels)
+// heads == 1 runs exactly what hg_incidence_attention_f32 always ran (run_segments launches the SegArgs instances)
 int hg_incidence_attention_heads_f32(const hg_plan *plan, int32_t group, int32_t heads, const int32_t *csrptr_t,
                                      const int32_t *colind_t, const float *sv, const float *se, float slope,
                                      float *alpha_out, hg_stream_t stream) {
@@ -2349,32 +2318,17 @@ int hg_incidence_attention_heads_bwd_f32(const hg_plan *plan, int32_t group, int
 // The refusals the three entries share, in the documented order; has_F false: the entry has no feature width.
 static int check_attention_call(const char *who, const hg_plan *plan, int32_t hop, int32_t group, int32_t heads, int32_t F,
                                 bool has_F = true) {
-  if (!plan) {
-    hg::set_error(std::string(who) + ": null plan");
-    return HG_ERR_INVALID;
-  }
-  if (hop != 0 && hop != 1) {
-    hg::set_error(std::string(who) + ": hop must be 0 (to the hyperedges) or 1 (to the vertices)");
-    return HG_ERR_INVALID;
-  }
-  if (group != 0 && group != 1) {
-    hg::set_error(std::string(who) + ": group must be 0 (hyperedge) or 1 (vertex)");
-    return HG_ERR_INVALID;
-  }
-  if (heads < 1) {
-    hg::set_error(std::string(who) + ": heads must be at least 1");
-    return HG_ERR_INVALID;
-  }
-  if (has_F && (F < 1 || F % heads != 0)) {
-    hg::set_error(std::string(who) + ": the feature width " + std::to_string(F) + " must be a positive multiple of heads = " +
-                  std::to_string(heads));
-    return HG_ERR_INVALID;
-  }
+  const std::string pre = std::string(who) + ": ";
+  if (!plan) return refuse(HG_ERR_INVALID, pre + "null plan");
+  if (hop != 0 && hop != 1) return refuse(HG_ERR_INVALID, pre + "hop must be 0 (to the hyperedges) or 1 (to the vertices)");
+  if (group != 0 && group != 1) return refuse(HG_ERR_INVALID, pre + "group must be 0 (hyperedge) or 1 (vertex)");
+  if (heads < 1) return refuse(HG_ERR_INVALID, pre + "heads must be at least 1");
+  if (has_F && (F < 1 || F % heads != 0))
+    return refuse(HG_ERR_INVALID, pre + "the feature width " + std::to_string(F) + " must be a positive multiple of heads = " +
+                                      std::to_string(heads));
   if ((int64_t)std::max<int64_t>(plan->nnz, std::max(plan->N, plan->M)) * heads >= ((int64_t)1 << 40) ||
-      (int64_t)std::max(plan->N, plan->M) * std::max(F, 1) >= ((int64_t)1 << 40)) {
-    hg::set_error(std::string(who) + ": nnz * heads or the feature matrix too large");
-    return HG_ERR_INVALID;
-  }
+      (int64_t)std::max(plan->N, plan->M) * std::max(F, 1) >= ((int64_t)1 << 40))
+    return refuse(HG_ERR_INVALID, pre + "nnz * heads or the feature matrix too large");
   return HG_OK;
 }
 
@@ -2426,10 +2380,8 @@ static int check_attention_gather(const char *who, const hg_plan *plan, int32_t 
   int rc = check_workspace(pre, workspace, workspace_bytes, carve(plan, F).total);
   if (rc != HG_OK) return rc;
   if (host_only(plan)) return refuse_host_only(pre, "schedule", HG_ERR_UNSUPPORTED);
-  if (hg::attn_gather_lds_bytes(plan->opts.panel_rows, plan->opts.panel_nnz, heads, true) > (size_t)160 * 1024) {
-    hg::set_error(std::string(who) + ": panel_rows * heads leaves no LDS for the rows' scores and statistics (160 KiB per workgroup)");
-    return HG_ERR_UNSUPPORTED;
-  }
+  if (hg::attn_gather_lds_bytes(plan->opts.panel_rows, plan->opts.panel_nnz, heads, true) > (size_t)160 * 1024)
+    return refuse(HG_ERR_UNSUPPORTED, pre + "panel_rows * heads leaves no LDS for the rows' scores and statistics (160 KiB per workgroup)");
   return HG_OK;
 }
 
@@ -2506,22 +2458,11 @@ int hg_incidence_attention_dropout_heads_bwd_f32(const hg_plan *plan, int32_t gr
 // entry_score; then the host-only plan and the arrays (check_segment_call).
 static int check_entry_call(const char *who, const hg_plan *plan, int32_t group, int32_t heads, const int32_t *csrptr_t,
                             const int32_t *colind_t, const float *entry_score) {
-  if (!plan) {
-    hg::set_error(std::string(who) + ": null plan");
-    return HG_ERR_INVALID;
-  }
-  if (heads < 1) {
-    hg::set_error(std::string(who) + ": heads must be at least 1");
-    return HG_ERR_INVALID;
-  }
-  if (group != 0 && group != 1) {
-    hg::set_error(std::string(who) + ": group / side must be 0 (hyperedge) or 1 (vertex)");
-    return HG_ERR_INVALID;
-  }
-  if (!entry_score) {
-    hg::set_error(std::string(who) + ": null entry_score (the entries without one take sv / se alone)");
-    return HG_ERR_INVALID;
-  }
+  const std::string pre = std::string(who) + ": ";
+  if (!plan) return refuse(HG_ERR_INVALID, pre + "null plan");
+  if (heads < 1) return refuse(HG_ERR_INVALID, pre + "heads must be at least 1");
+  if (group != 0 && group != 1) return refuse(HG_ERR_INVALID, pre + "group / side must be 0 (hyperedge) or 1 (vertex)");
+  if (!entry_score) return refuse(HG_ERR_INVALID, pre + "null entry_score (the entries without one take sv / se alone)");
   int rc = check_heads(who, plan, heads, 0);
   if (rc != HG_OK) return rc;
   return check_segment_call(who, plan, group, csrptr_t, colind_t);
@@ -2596,10 +2537,8 @@ int hg_incidence_attention_entry_dropout_heads_bwd_f32(const hg_plan *plan, int3
 }
 
 int hg_dropout_keep_host(uint64_t key, uint64_t sid, float p_drop, int64_t nnz, int32_t heads, uint8_t *keep_out) {
-  if (!(p_drop >= 0.f && p_drop < 1.f) || nnz < 0 || nnz > 0x7fffffff || heads < 1 || (nnz > 0 && !keep_out)) {
-    hg::set_error("hg_dropout_keep_host: p_drop outside [0, 1), nnz outside [0, 2^31), heads < 1 or null keep_out");
-    return HG_ERR_INVALID;
-  }
+  if (!(p_drop >= 0.f && p_drop < 1.f) || nnz < 0 || nnz > 0x7fffffff || heads < 1 || (nnz > 0 && !keep_out))
+    return refuse(HG_ERR_INVALID, "hg_dropout_keep_host: p_drop outside [0, 1), nnz outside [0, 2^31), heads < 1 or null keep_out");
   const hg::DropRng r = hg::drop_rng(key, sid);
   const uint32_t T = hg::drop_threshold(p_drop);
   for (int64_t p = 0; p < nnz; p++)
@@ -2618,10 +2557,7 @@ int hg_incidence_sum_heads_f32(const hg_plan *plan, int32_t side, int32_t heads,
   if (rc != HG_OK) return rc;
   rc = check_segment_call("hg_incidence_sum_f32", plan, side, csrptr_t, colind_t);
   if (rc != HG_OK) return rc;
-  if ((plan->nnz > 0 && !val) || !out) {
-    hg::set_error("hg_incidence_sum_f32: null array");
-    return HG_ERR_INVALID;
-  }
+  if ((plan->nnz > 0 && !val) || !out) return refuse(HG_ERR_INVALID, "hg_incidence_sum_f32: null array");
   hg::SegArgs a = {};
   a.val = val;
   a.out_seg = out;

@@ -78,23 +78,26 @@ struct SegDropHeadsArgs : SegHeadsArgs {
 };
 
 // The entry-logit bodies (kSegSoftmaxEntry*): raw[p, h] = (own + other) + entry[p, h].  One block for all four, the most
-// general one (heads and dropout; heads = 1 and an unused `drop` are the special cases), so that the family has one more
-// copy of the work split, not four.
+// general one (heads and dropout; heads = 1 and an unused `drop` are the special cases), so that the family has 24
+// instances, not 96.
 struct SegEntryArgs : SegDropHeadsArgs {
   const float *entry;  // [nnz, heads], H_T order, head fastest: side 0 streams it, side 1 reaches it through perm
 };
 
 // Lane-group width of a side whose segments of at most kSegLong entries hold `mean` entries on average.
 int seg_width(double mean);
-// body: kSeg*; side 0 / 1; width 4 / 8 / 16 (seg_width)
-hipError_t launch_segments(int body, int side, int width, const SegArgs &a, hipStream_t stream);
-// one lane group (or, for a long segment, one workgroup) per (segment, head): column h is reduced as launch_segments
-// reduces a single column
-hipError_t launch_segments_heads(int body, int side, int width, const SegHeadsArgs &a, hipStream_t stream);
-// body: kSegSoftmaxDrop / kSegSoftmaxDropBwd, the same cut of the work
-hipError_t launch_segments_drop(int body, int side, int width, const SegDropArgs &a, hipStream_t stream);
-hipError_t launch_segments_drop_heads(int body, int side, int width, const SegDropHeadsArgs &a, hipStream_t stream);
-// body: kSegSoftmaxEntry*; heads >= 1; drop.rng is needed by the two dropout bodies only
-hipError_t launch_segments_entry(int body, int side, int width, const SegEntryArgs &a, hipStream_t stream);
+
+// One launch of segment_kernel on any of the five blocks.  body: kSeg*, among those of the block -- kSegSoftmax,
+// kSegSoftmaxBwd, kSegSum and kSegStats on SegArgs / SegHeadsArgs, the two kSegSoftmaxDrop* on the dropout blocks (drop.rng
+// needed), the four kSegSoftmaxEntry* on SegEntryArgs (entry needed; drop.rng by its two dropout bodies only); side 0 / 1;
+// width 4 / 8 / 16 (seg_width).  A block with heads (>= 1) gives one lane group or, for a long segment, one workgroup
+// to every (segment, head): column h is reduced as a block without heads reduces its single column.
+template <typename ARGS>
+hipError_t launch_segments(int body, int side, int width, const ARGS &a, hipStream_t stream);
+extern template hipError_t launch_segments(int, int, int, const SegArgs &, hipStream_t);
+extern template hipError_t launch_segments(int, int, int, const SegHeadsArgs &, hipStream_t);
+extern template hipError_t launch_segments(int, int, int, const SegDropArgs &, hipStream_t);
+extern template hipError_t launch_segments(int, int, int, const SegDropHeadsArgs &, hipStream_t);
+extern template hipError_t launch_segments(int, int, int, const SegEntryArgs &, hipStream_t);
 
 }  // namespace hg

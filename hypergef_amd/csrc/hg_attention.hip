@@ -18,32 +18,37 @@
 // (commutative at every step: all lanes end with the same bits), a workgroup combines its four waves' results in wave
 // order through LDS.  The order depends on the segment's length and the side's width only: two calls give the same bits.
 //
-// Heads (segment_heads_kernel, the *_heads_f32 entries).  Scores are [nseg, H], entry arrays [nnz, H], head fastest.  A
-// lane group owns one (segment, head) pair, consecutive lane groups the consecutive heads of one segment, so the groups
-// of a wave read neighbouring words of the same rows; the long segments take one workgroup per (segment, head).  A pair
-// runs the single-head code on column h (Col<true>: element i of a column sits at i * H + h), so its order of reduction
-// is the single-head one -- it depends on the segment's length and W, not on H -- and column h of a result has the bits
-// of the single-head call on column h of the inputs.
+// One kernel, segment_kernel<BODY, SIDE, W, ARGS>, carries that split for every body and every argument block
+// (hg_attention.h); what a block adds to SegArgs selects, at compile time, what the kernel does beside it.
 //
-// Dropout (kSegSoftmaxDrop / kSegSoftmaxDropBwd, segment_drop_kernel and its heads form).  The same two segment functions
-// with a Drop in place of NoDrop: the forward writes alpha as before and, beside it, keep ? alpha * scale : +0; the
-// backward masks and scales dalpha as it loads it and is the plain backward from there on.  keep is word 0 of
-// Philox4x32-10 on the counter (H_T position, head, sid) compared with a threshold (hg_philox.h): no mask is stored, both
-// sides and every width see the same one, and an entry beyond the kSegKeep kept ones recomputes it in each pass as it
-// gathers its score again.  The reductions are untouched, so alpha, t, ds and the sums have the bits of the plain bodies
-// on pre-masked input.  The instances above do not see any of this: NoDrop compiles to what was there.
+// Heads (the blocks derived from SegHeadsArgs, the *_heads_f32 entries).  Scores are [nseg, H], entry arrays [nnz, H],
+// head fastest.  A lane group owns one (segment, head) pair, consecutive lane groups the consecutive heads of one
+// segment, so the groups of a wave read neighbouring words of the same rows; the long segments take one workgroup per
+// (segment, head).  A pair runs the single-head code on column h (Col<true>: element i of a column sits at i * H + h), so
+// its order of reduction is the single-head one -- it depends on the segment's length and W, not on H -- and column h of
+// a result has the bits of the single-head call on column h of the inputs.  The other blocks count segments in 32 bits
+// and index with Col<false>, the plain index.
 //
-// Entry logits (kSegSoftmaxEntry*, segment_entry_kernel).  The four softmax bodies with a logit per incidence, t [nnz, H]
-// in H_T order: raw = (own + other) + t[p], the bracket formed first, as before.  An Entry in place of NoEntry adds t as
-// the score is gathered: a kept entry folds it into the value it keeps in registers, an entry beyond the kept ones looks
-// up its position (side 1: perm) and gathers t again in each pass, as it gathers the score again.  Everything after raw
-// -- leaky relu, maximum, exponentials, reduction order, the mask -- is the code above, so t = 0 gives the bits of the
-// plain bodies.  The backward's ds is the gradient of t itself.  The four bodies share one kernel on the most general
-// argument block (heads and dropout): 24 instances and one more copy of the work split instead of 96 and four.
+// Dropout (kSegSoftmaxDrop / kSegSoftmaxDropBwd, the blocks with DropFields).  The same two segment functions with a
+// Drop in place of NoDrop: the forward writes alpha as before and, beside it, keep ? alpha * scale : +0; the backward
+// masks and scales dalpha as it loads it and is the plain backward from there on.  keep is word 0 of Philox4x32-10 on
+// the counter (H_T position, head, sid) compared with a threshold (hg_philox.h): no mask is stored, both sides and every
+// width see the same one, and an entry beyond the kSegKeep kept ones recomputes it in each pass as it gathers its score
+// again.  The reductions are untouched, so alpha, t, ds and the sums have the bits of the plain bodies on pre-masked
+// input.  The plain bodies do not see any of this: NoDrop compiles to nothing.
 //
-// Segment statistics (kSegStats, on segment_kernel / segment_heads_kernel).  The softmax body up to the reciprocal of the
-// sum, which then leaves with the maximum, [nseg, H]: lane groups, the workgroup path and the order of reduction are the
-// softmax's, so attention_weight (hg_attention.h) on the two gives alpha's bits and no [nnz, H] array need exist
+// Entry logits (kSegSoftmaxEntry*, SegEntryArgs).  The four softmax bodies with a logit per incidence, t [nnz, H] in H_T
+// order: raw = (own + other) + t[p], the bracket formed first, as before.  An Entry in place of NoEntry adds t as the
+// score is gathered: a kept entry folds it into the value it keeps in registers, an entry beyond the kept ones looks up
+// its position (side 1: perm) and gathers t again in each pass, as it gathers the score again.  Everything after raw --
+// leaky relu, maximum, exponentials, reduction order, the mask -- is the code above, so t = 0 gives the bits of the plain
+// bodies.  The backward's ds is the gradient of t itself.  The four bodies run on the most general block alone (heads
+// and dropout): a single-head call has H = 1 (Col<true>{1, 0} is the plain index in 64 bits), a call without dropout
+// leaves `drop` unread -- 24 instances instead of 96.
+//
+// Segment statistics (kSegStats, on SegArgs / SegHeadsArgs).  The softmax body up to the reciprocal of the sum, which
+// then leaves with the maximum, [nseg, H]: lane groups, the workgroup path and the order of reduction are the softmax's,
+// so attention_weight (hg_attention.h) on the two gives alpha's bits and no [nnz, H] array need exist
 // (hg_aggr_incidence_attention_heads_f32).  Positions are not looked up: side 1 runs without perm.
 #include <hip/hip_runtime.h>
 
@@ -317,50 +322,39 @@ __device__ __forceinline__ void run_segment(const ARGS &a, Col<MH> col, int32_t 
   else sum_segment<SIDE, W>(a, col, seg, beg, end, lane, lds, valid);
 }
 
-// Workgroups [0, nlong): one long segment each (they run longest, so they start first); the others: 256 / W lane groups,
-// one segment each.  Lanes without a segment of their own (past the last one, or a long one's lane group) walk an empty
-// range and take part in the butterflies: no lane leaves before the last cross-lane step.
-// This cut of the work exists five times -- here, in segment_heads_kernel, in their two segment_drop_* copies and in
-// segment_entry_kernel below: a change to it (the kSegLong rule, say) goes into all five.
-template <int BODY, int SIDE, int W>
-__global__ __launch_bounds__(kSegBlock) void segment_kernel(SegArgs a) {
-  __shared__ float lds[kSegBlock / 64];
-  if ((int32_t)blockIdx.x < a.nlong) {
-    const int32_t seg = a.long_seg[blockIdx.x];
-    run_segment<BODY, SIDE, kSegBlock>(a, Col<false>{}, seg, a.ptr[seg], a.ptr[seg + 1], (int)threadIdx.x, lds, true);
-    return;
-  }
-  constexpr int kGroups = kSegBlock / W;
-  const int64_t s = (int64_t)((int32_t)blockIdx.x - a.nlong) * kGroups + (int)threadIdx.x / W;
-  bool valid = s < a.nseg;
-  const int32_t seg = valid ? (int32_t)s : 0;
-  int32_t beg = 0, end = 0;
-  if (valid) {
-    beg = a.ptr[seg];
-    end = a.ptr[seg + 1];
-    if (end - beg > kSegLong) {  // a workgroup of its own has it
-      beg = end = 0;
-      valid = false;
-    }
-  }
-  run_segment<BODY, SIDE, W>(a, Col<false>{}, seg, beg, end, (int)threadIdx.x % W, lds, valid);
+// The heads of a block: those derived from SegHeadsArgs carry the count, the others have one.
+template <typename ARGS>
+constexpr bool kHasHeads = std::is_base_of_v<SegHeadsArgs, ARGS>;
+template <typename ARGS>
+__host__ __device__ __forceinline__ int32_t heads_of(const ARGS &a) {
+  if constexpr (kHasHeads<ARGS>) return a.heads;
+  else return 1;
+}
+template <bool MH>
+__device__ __forceinline__ Col<MH> column(int32_t H, int32_t h) {
+  if constexpr (MH) return Col<true>{H, h};
+  else return Col<false>{};
 }
 
-// The same with heads: workgroups [0, nlong * H) take one (long segment, head) each, the lane groups of the others one
-// (segment, head) each, head fastest.
-template <int BODY, int SIDE, int W>
-__global__ __launch_bounds__(kSegBlock) void segment_heads_kernel(SegHeadsArgs a) {
+// Workgroups [0, nlong * H): one (long segment, head) each (they run longest, so they start first); the others: 256 / W
+// lane groups, one (segment, head) each, head fastest.  Lanes without a pair of their own (past the last one, or a long
+// segment's lane group) walk an empty range and take part in the butterflies: no lane leaves before the last cross-lane
+// step.  A block without heads has H = 1 at compile time and counts in 32 bits; nseg * H may pass 2^31.
+template <int BODY, int SIDE, int W, typename ARGS>
+__global__ __launch_bounds__(kSegBlock) void segment_kernel(ARGS a) {
+  constexpr bool kHeads = kHasHeads<ARGS>;
+  using count_t = std::conditional_t<kHeads, int64_t, int32_t>;
   __shared__ float lds[kSegBlock / 64];
-  const int32_t H = a.heads;
-  const int64_t nlong = (int64_t)a.nlong * H;
-  if ((int64_t)blockIdx.x < nlong) {
+  const int32_t H = heads_of(a);
+  const count_t nlong = (count_t)a.nlong * H;
+  if ((count_t)blockIdx.x < nlong) {
     const int32_t seg = a.long_seg[blockIdx.x / H];
-    run_segment<BODY, SIDE, kSegBlock>(a, Col<true>{H, (int32_t)(blockIdx.x % H)}, seg, a.ptr[seg], a.ptr[seg + 1],
+    run_segment<BODY, SIDE, kSegBlock>(a, column<kHeads>(H, (int32_t)(blockIdx.x % H)), seg, a.ptr[seg], a.ptr[seg + 1],
                                        (int)threadIdx.x, lds, true);
     return;
   }
   constexpr int kGroups = kSegBlock / W;
-  const int64_t s = ((int64_t)blockIdx.x - nlong) * kGroups + (int)threadIdx.x / W;
+  const int64_t s = (int64_t)((count_t)blockIdx.x - nlong) * kGroups + (int)threadIdx.x / W;
   bool valid = s < (int64_t)a.nseg * H;
   const int32_t seg = valid ? (int32_t)(s / H) : 0;
   const int32_t h = valid ? (int32_t)(s % H) : 0;
@@ -373,107 +367,12 @@ __global__ __launch_bounds__(kSegBlock) void segment_heads_kernel(SegHeadsArgs a
       valid = false;
     }
   }
-  run_segment<BODY, SIDE, W>(a, Col<true>{H, h}, seg, beg, end, (int)threadIdx.x % W, lds, valid);
+  run_segment<BODY, SIDE, W>(a, column<kHeads>(H, h), seg, beg, end, (int)threadIdx.x % W, lds, valid);
 }
 
-// The dropout bodies: the two kernels above on the longer argument blocks.  The cut of the work is repeated rather than
-// shared through a function, so that the instances above stay instruction for instruction what they were.
-template <int BODY, int SIDE, int W>
-__global__ __launch_bounds__(kSegBlock) void segment_drop_kernel(SegDropArgs a) {
-  __shared__ float lds[kSegBlock / 64];
-  if ((int32_t)blockIdx.x < a.nlong) {
-    const int32_t seg = a.long_seg[blockIdx.x];
-    run_segment<BODY, SIDE, kSegBlock>(a, Col<false>{}, seg, a.ptr[seg], a.ptr[seg + 1], (int)threadIdx.x, lds, true);
-    return;
-  }
-  constexpr int kGroups = kSegBlock / W;
-  const int64_t s = (int64_t)((int32_t)blockIdx.x - a.nlong) * kGroups + (int)threadIdx.x / W;
-  bool valid = s < a.nseg;
-  const int32_t seg = valid ? (int32_t)s : 0;
-  int32_t beg = 0, end = 0;
-  if (valid) {
-    beg = a.ptr[seg];
-    end = a.ptr[seg + 1];
-    if (end - beg > kSegLong) {  // a workgroup of its own has it
-      beg = end = 0;
-      valid = false;
-    }
-  }
-  run_segment<BODY, SIDE, W>(a, Col<false>{}, seg, beg, end, (int)threadIdx.x % W, lds, valid);
-}
-
-template <int BODY, int SIDE, int W>
-__global__ __launch_bounds__(kSegBlock) void segment_drop_heads_kernel(SegDropHeadsArgs a) {
-  __shared__ float lds[kSegBlock / 64];
-  const int32_t H = a.heads;
-  const int64_t nlong = (int64_t)a.nlong * H;
-  if ((int64_t)blockIdx.x < nlong) {
-    const int32_t seg = a.long_seg[blockIdx.x / H];
-    run_segment<BODY, SIDE, kSegBlock>(a, Col<true>{H, (int32_t)(blockIdx.x % H)}, seg, a.ptr[seg], a.ptr[seg + 1],
-                                       (int)threadIdx.x, lds, true);
-    return;
-  }
-  constexpr int kGroups = kSegBlock / W;
-  const int64_t s = ((int64_t)blockIdx.x - nlong) * kGroups + (int)threadIdx.x / W;
-  bool valid = s < (int64_t)a.nseg * H;
-  const int32_t seg = valid ? (int32_t)(s / H) : 0;
-  const int32_t h = valid ? (int32_t)(s % H) : 0;
-  int32_t beg = 0, end = 0;
-  if (valid) {
-    beg = a.ptr[seg];
-    end = a.ptr[seg + 1];
-    if (end - beg > kSegLong) {  // a workgroup of its own has it
-      beg = end = 0;
-      valid = false;
-    }
-  }
-  run_segment<BODY, SIDE, W>(a, Col<true>{H, h}, seg, beg, end, (int)threadIdx.x % W, lds, valid);
-}
-
-// The entry-logit bodies: segment_drop_heads_kernel's cut on the block that carries `entry` as well.  One kernel for the
-// four bodies, with and without heads or dropout: a single-head call runs it with H = 1 (Col<true>{1, 0} is the plain
-// index in 64 bits), a call without dropout leaves `drop` unread.
-template <int BODY, int SIDE, int W>
-__global__ __launch_bounds__(kSegBlock) void segment_entry_kernel(SegEntryArgs a) {
-  __shared__ float lds[kSegBlock / 64];
-  const int32_t H = a.heads;
-  const int64_t nlong = (int64_t)a.nlong * H;
-  if ((int64_t)blockIdx.x < nlong) {
-    const int32_t seg = a.long_seg[blockIdx.x / H];
-    run_segment<BODY, SIDE, kSegBlock>(a, Col<true>{H, (int32_t)(blockIdx.x % H)}, seg, a.ptr[seg], a.ptr[seg + 1],
-                                       (int)threadIdx.x, lds, true);
-    return;
-  }
-  constexpr int kGroups = kSegBlock / W;
-  const int64_t s = ((int64_t)blockIdx.x - nlong) * kGroups + (int)threadIdx.x / W;
-  bool valid = s < (int64_t)a.nseg * H;
-  const int32_t seg = valid ? (int32_t)(s / H) : 0;
-  const int32_t h = valid ? (int32_t)(s % H) : 0;
-  int32_t beg = 0, end = 0;
-  if (valid) {
-    beg = a.ptr[seg];
-    end = a.ptr[seg + 1];
-    if (end - beg > kSegLong) {  // a workgroup of its own has it
-      beg = end = 0;
-      valid = false;
-    }
-  }
-  run_segment<BODY, SIDE, W>(a, Col<true>{H, h}, seg, beg, end, (int)threadIdx.x % W, lds, valid);
-}
-
-// ARGS = SegEntryArgs: segment_entry_kernel; ARGS = SegArgs: segment_kernel; ARGS = SegHeadsArgs: segment_heads_kernel; the dropout blocks: the *_drop_* kernels
 template <int BODY, int SIDE, int W, typename ARGS>
 void launch_one(unsigned nblocks, const ARGS &a, hipStream_t stream) {
-  if constexpr (std::is_same_v<ARGS, SegEntryArgs>)
-    hipLaunchKernelGGL((segment_entry_kernel<BODY, SIDE, W>), dim3(nblocks), dim3(kSegBlock), 0, stream, a);
-  else if constexpr (std::is_same_v<ARGS, SegDropHeadsArgs>)
-    hipLaunchKernelGGL((segment_drop_heads_kernel<BODY, SIDE, W>), dim3(nblocks), dim3(kSegBlock), 0, stream, a);
-  else if constexpr (std::is_same_v<ARGS, SegDropArgs>)
-    hipLaunchKernelGGL((segment_drop_kernel<BODY, SIDE, W>), dim3(nblocks), dim3(kSegBlock), 0, stream, a);
-  else if constexpr (std::is_same_v<ARGS, SegHeadsArgs>)
-    hipLaunchKernelGGL((segment_heads_kernel<BODY, SIDE, W>), dim3(nblocks), dim3(kSegBlock), 0, stream, a);
-  else
-    hipLaunchKernelGGL((segment_kernel<BODY, SIDE, W>), dim3(nblocks), dim3(kSegBlock), 0, stream, a);
+  hipLaunchKernelGGL((segment_kernel<BODY, SIDE, W, ARGS>), dim3(nblocks), dim3(kSegBlock), 0, stream, a);
 }
 
 template <int BODY, int SIDE, typename ARGS>
@@ -492,9 +391,16 @@ hipError_t launch_side(int side, int width, unsigned nblocks, const ARGS &a, hip
   return side == 0 ? launch_width<BODY, 0>(width, nblocks, a, stream) : launch_width<BODY, 1>(width, nblocks, a, stream);
 }
 
-// heads: the work items are (segment, head) pairs
+}  // namespace
+
+// The narrowest lane group that covers an average segment in one step: a wider one idles lanes on the typical segment
+// (mean lengths are 3-6), a narrower one walks it in several dependent steps.
+int seg_width(double mean) { return mean <= 4.0 ? 4 : mean <= 8.0 ? 8 : 16; }
+
 template <typename ARGS>
-hipError_t launch_body(int body, int side, int width, int64_t heads, const ARGS &a, hipStream_t stream) {
+hipError_t launch_segments(int body, int side, int width, const ARGS &a, hipStream_t stream) {
+  const int64_t heads = heads_of(a);  // the work items are (segment, head) pairs
+  if (heads < 1) return hipErrorInvalidValue;
   if (a.nseg <= 0) return hipSuccess;
   if (side < 0 || side > 1 || a.nlong < 0 || !a.ptr || (a.nlong > 0 && !a.long_seg)) return hipErrorInvalidValue;
   if (width != 4 && width != 8 && width != 16) return hipErrorInvalidValue;
@@ -529,33 +435,10 @@ hipError_t launch_body(int body, int side, int width, int64_t heads, const ARGS 
   return hipErrorInvalidValue;
 }
 
-}  // namespace
-
-// The narrowest lane group that covers an average segment in one step: a wider one idles lanes on the typical segment
-// (mean lengths are 3-6), a narrower one walks it in several dependent steps.
-int seg_width(double mean) { return mean <= 4.0 ? 4 : mean <= 8.0 ? 8 : 16; }
-
-hipError_t launch_segments(int body, int side, int width, const SegArgs &a, hipStream_t stream) {
-  return launch_body(body, side, width, 1, a, stream);
-}
-
-hipError_t launch_segments_heads(int body, int side, int width, const SegHeadsArgs &a, hipStream_t stream) {
-  if (a.heads < 1) return hipErrorInvalidValue;
-  return launch_body(body, side, width, a.heads, a, stream);
-}
-
-hipError_t launch_segments_drop(int body, int side, int width, const SegDropArgs &a, hipStream_t stream) {
-  return launch_body(body, side, width, 1, a, stream);
-}
-
-hipError_t launch_segments_drop_heads(int body, int side, int width, const SegDropHeadsArgs &a, hipStream_t stream) {
-  if (a.heads < 1) return hipErrorInvalidValue;
-  return launch_body(body, side, width, a.heads, a, stream);
-}
-
-hipError_t launch_segments_entry(int body, int side, int width, const SegEntryArgs &a, hipStream_t stream) {
-  if (a.heads < 1) return hipErrorInvalidValue;
-  return launch_body(body, side, width, a.heads, a, stream);
-}
+template hipError_t launch_segments(int, int, int, const SegArgs &, hipStream_t);
+template hipError_t launch_segments(int, int, int, const SegHeadsArgs &, hipStream_t);
+template hipError_t launch_segments(int, int, int, const SegDropArgs &, hipStream_t);
+template hipError_t launch_segments(int, int, int, const SegDropHeadsArgs &, hipStream_t);
+template hipError_t launch_segments(int, int, int, const SegEntryArgs &, hipStream_t);
 
 }  // namespace hg
