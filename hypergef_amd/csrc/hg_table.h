@@ -22,6 +22,15 @@
 // Dot products (hg_table_dot_f32): a lane group of L lanes (the power of two at or above min(ceil(F / V), 64)) owns a table
 // row, keeps its B / D chunk in registers over the row's k entries, gathers kTableDotBatch rows of A / C at a time, and
 // adds the lanes' fma chains in an xor butterfly L / 2 .. 1.
+//
+// bfloat16 rows (hg_table_bf16.hip; F % 8 == 0 and 16-byte aligned rows): the gathers keep 16-byte lanes, so a lane owns
+// V = 8 columns -- one access of a bfloat16 side, two of a float32 side -- and a lane group is L8 = min(F / 8, 64) lanes,
+// 64 / L8 rows a wave (sixteen at F = 32); kTableBatch packed row loads in flight, widened where they are added.  A long row
+// of the transposed gather is NOT summed in that geometry: its P pieces and its tree are a function of the float32 call's
+// (L, R, P', 4 columns a lane), so the launcher computes those from F as hg_table_gather_t_f32 would and the long-row
+// phase runs in them, with 8-byte loads of the bfloat16 side.  Distances: one lane per position, 8 columns a load.  Dot
+// products: the DOT ORDER names the lane of every column, so the geometry is the float32 call's at 4 columns a lane and
+// only the gathered rows' loads narrow.
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -52,5 +61,10 @@ struct TableLayout {
   int passes;  // radix passes: the keys 0 .. n have ceil(log2(n + 1)) bits
 };
 TableLayout table_layout(int64_t rows, int k, int64_t n);
+
+// Host: the refusals every table entry shares, in include/hg_aggr.h's order, and the check after a launch
+int table_refusal(const char *entry, int32_t rows, int32_t k);
+int size_refusal(const char *entry, int32_t rows, int32_t k, int32_t n, int32_t F);
+int launch_check(const char *entry);
 
 }  // namespace hg

@@ -474,7 +474,9 @@ __global__ __launch_bounds__(64 * kTableWaves) void table_dot_kernel(TableDotArg
   }
 }
 
-// what every table entry refuses about k and the table's size
+}  // namespace
+
+// what every table entry refuses about k and the table's size (hg_table.h: hg_table_bf16.hip's entries refuse the same)
 int table_refusal(const char *entry, int32_t rows, int32_t k) {
   if (k < 1 || k > kTableMaxK) return fail(entry, HG_ERR_INVALID, "k must be in 1 .. 64, got " + std::to_string(k));
   if ((int64_t)rows * k > INT32_MAX) return fail(entry, HG_ERR_INVALID, "rows * k must be below 2^31");
@@ -487,6 +489,14 @@ int size_refusal(const char *entry, int32_t rows, int32_t k, int32_t n, int32_t 
   return table_refusal(entry, rows, k);
 }
 
+int launch_check(const char *entry) {
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail(entry, HG_ERR_HIP, std::string("launch: ") + hipGetErrorString(e));
+  return HG_OK;
+}
+
+namespace {
+
 // what the four gathers refuse about the table and the rows, in the same order
 int gather_refusal(const char *entry, int32_t rows, int32_t k, int32_t n, int32_t F, const float *src, const float *w,
                    const float *src_scale, const float *dst_scale, const float *dst) {
@@ -494,12 +504,6 @@ int gather_refusal(const char *entry, int32_t rows, int32_t k, int32_t n, int32_
   if (const int st = size_refusal(entry, rows, k, n, F)) return st;
   for (const void *p : {(const void *)src, (const void *)w, (const void *)src_scale, (const void *)dst_scale, (const void *)dst})
     if ((uintptr_t)p % 4) return fail(entry, HG_ERR_UNSUPPORTED, "src, w, the scales and dst must be 4-byte aligned");
-  return HG_OK;
-}
-
-int launch_check(const char *entry) {
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(entry, HG_ERR_HIP, std::string("launch: ") + hipGetErrorString(e));
   return HG_OK;
 }
 

@@ -8,7 +8,8 @@ host-side layout step of `HyperGraph.from_knn`.
 `knn_transpose` and `knn_aggr` (`ops.knn_transpose` / `ops.knn_aggr`; hg_table_* in include/hg_aggr.h) aggregate over the
 neighbour table itself, with no plan and no host step, and `KnnHypergraph` is the device-only hypergraph they serve.
 `knn_dist` (`ops.knn_dist`) gives a table's distances with a gradient, and `knn_aggr(weight_grad=True)` the gradient of its
-weights: together they train through the weights of a probabilistic kNN hypergraph.
+weights: together they train through the weights of a probabilistic kNN hypergraph.  Both take bfloat16 rows under
+Options.incidence_bf16 = 'rows' (hg_table_*_bf16): the float32 call on the widened rows, bit for bit, rounded once.
 """
 import ctypes
 import numbers
@@ -26,7 +27,7 @@ FORMS = ("difference", "dot")
 DOT_F_MAX = 65536  # form="dot": the widest rows the error bound is derived for (hg_knn.h, kDotMaxF)
 
 
-_NO_FORM = " (%s has no bfloat16 / float16 / float64 form)"
+_NO_FORM = " (%s has no float16 / float64 form; bfloat16 rows need Options.incidence_bf16 = 'rows')"
 _KNN_NO_FORM = ' (knn has no float16 / float64 form; form="dot" takes bfloat16 rows, X and queries alike)'
 
 
@@ -257,25 +258,66 @@ def knn_transpose(idx, n=None):
     return ptr_v, pos_v
 
 
-def _flat_or_none(t, name, count, dev):
+def _flat_or_none(t, name, count, dev, bf16_ok=False):
     """A float32 device tensor of `count` elements (any shape) as the kernels take it, or None."""
     if t is None:
         return None
-    _check_feat(t, name, device=dev)
+    _check_feat(t, name, device=dev, bf16_ok=bf16_ok)
     if t.numel() != count:
         raise ValueError("%s must have %d elements, got %s" % (name, count, tuple(t.shape)))
     return t
 
 
-def table_gather(idx, src, w=None, src_scale=None, dst_scale=None, ctr=None):
+BF16 = torch.bfloat16
+
+
+def _bf16_entry(name):
+    """An hg_table_*_bf16 entry of the library; a build without it is an error, never another path."""
+    L = _lib.lib()
+    if not hasattr(L, name):
+        raise RuntimeError("this build of libhgaggr has no %s (bfloat16 rows over a neighbour table)" % name)
+    return getattr(L, name)
+
+
+def _whole_lanes(F, *rows):
+    """Whether the hg_table_*_bf16 entries take these row arrays (None: absent): F % 8 == 0 and 16-byte aligned rows
+    (include/hg_aggr.h).  Otherwise the caller widens, runs the float32 entry and rounds once: the same bits, torch ops only."""
+    return F % 8 == 0 and all(t is None or t.data_ptr() % 16 == 0 for t in rows)
+
+
+def _gather_io(src, ctr, dst_dtype):
+    """The row types of one gather: (the io mask, or 0 for the float32 entry; the result's dtype), with the refusals."""
+    if dst_dtype not in (None, torch.float32, BF16):
+        raise TypeError("dst_dtype must be torch.float32 or torch.bfloat16, got %s" % (dst_dtype,))
+    if ctr is not None and ctr.dtype != src.dtype:
+        raise TypeError("ctr must have src's dtype %s, got %s" % (src.dtype, ctr.dtype))
+    if src.dtype == BF16:
+        if dst_dtype == BF16:
+            raise ValueError("bfloat16 src gives a float32 result (the hyperedge rows between the hops stay float32)")
+        return _lib.HG_ROWS_SRC_BF16, torch.float32
+    if dst_dtype == BF16:
+        if ctr is not None:
+            raise ValueError("the difference gather has no bfloat16 result: its float32 sums are added before the one rounding")
+        return _lib.HG_ROWS_DST_BF16, BF16
+    return 0, torch.float32
+
+
+def _widened(t):
+    return t.float() if t is not None and t.dtype == BF16 else t
+
+
+def table_gather(idx, src, w=None, src_scale=None, dst_scale=None, ctr=None, dst_dtype=None):
     """dst[i] = dst_scale[i] * sum_s (src[idx[i, s]] * src_scale[idx[i, s]]) * w[i * k + s] over a table idx [rows, k] and rows
     src [n, F]: hg_table_gather_f32, every row summed in ascending s.  Any of w [rows * k], src_scale [n], dst_scale [rows]
     may be None (no multiplication).  An entry outside 0 .. n - 1 adds nothing.  No gradient.
-    ctr [rows, F]: the difference gather hg_table_gather_diff_f32 -- the term starts from ctr[i] - src[idx[i, s]]."""
+    ctr [rows, F]: the difference gather hg_table_gather_diff_f32 -- the term starts from ctr[i] - src[idx[i, s]].
+    bfloat16 rows (hg_table_gather_bf16): a bfloat16 src (ctr bfloat16 too) gives the float32 result of the call on
+    src.float(); dst_dtype=torch.bfloat16 rounds a float32 src's result once (no ctr).  Bit for bit; w and the scales stay
+    float32."""
     _table_shape(idx)
     rows, k = _table_shape_values(idx)
     _check_table_index(idx, "idx")
-    _check_feat(src, "src", device=idx.device)
+    _check_feat(src, "src", device=idx.device, bf16_ok=True)
     if src.dim() != 2 or src.shape[0] < 1 or src.shape[1] < 1:
         raise ValueError("src must be [n >= 1, F >= 1], got %s" % (tuple(src.shape),))
     n, F = src.shape
@@ -283,22 +325,31 @@ def table_gather(idx, src, w=None, src_scale=None, dst_scale=None, ctr=None):
     w = _flat_or_none(w, "w", rows * k, dev)
     src_scale = _flat_or_none(src_scale, "src_scale", n, dev)
     dst_scale = _flat_or_none(dst_scale, "dst_scale", rows, dev)
-    ctr = _flat_or_none(ctr, "ctr", rows * F, dev)
-    dst = torch.empty((rows, F), dtype=torch.float32, device=dev)
+    ctr = _flat_or_none(ctr, "ctr", rows * F, dev, bf16_ok=True)
+    io, out_dtype = _gather_io(src, ctr, dst_dtype)
+    dst = torch.empty((rows, F), dtype=out_dtype, device=dev)
+    if io and not _whole_lanes(F, src, ctr, dst):
+        return table_gather(idx, _widened(src), w, src_scale, dst_scale, _widened(ctr)).to(out_dtype)
     L = _lib.lib()
-    entry, centre = (L.hg_table_gather_f32, ()) if ctr is None else (L.hg_table_gather_diff_f32, (_ptr(ctr),))
+    if io:
+        entry, tail = _bf16_entry("hg_table_gather_bf16"), (_ptr(ctr), _ptr(dst), io)
+    elif ctr is None:
+        entry, tail = L.hg_table_gather_f32, (_ptr(dst),)
+    else:
+        entry, tail = L.hg_table_gather_diff_f32, (_ptr(ctr), _ptr(dst))
     with torch.cuda.device(dev):
-        _lib.check(entry(_ptr(idx), rows, k, n, F, _ptr(src), _ptr(w), _ptr(src_scale), _ptr(dst_scale), *centre, _ptr(dst),
+        _lib.check(entry(_ptr(idx), rows, k, n, F, _ptr(src), _ptr(w), _ptr(src_scale), _ptr(dst_scale), *tail,
                          _stream_handle(dev)))
     return dst
 
 
-def table_gather_t(ptr_v, pos_v, k, src, w=None, src_scale=None, dst_scale=None, ctr=None):
+def table_gather_t(ptr_v, pos_v, k, src, w=None, src_scale=None, dst_scale=None, ctr=None, dst_dtype=None):
     """dst[v] = dst_scale[v] * sum_q (src[pos_v[q] // k] * src_scale[pos_v[q] // k]) * w[pos_v[q]], q over ptr_v[v] ..
     ptr_v[v + 1] - 1, for the transpose (ptr_v [n + 1], pos_v [rows * k]) of a table of k columns and rows src [rows, F]:
     hg_table_gather_t_f32.  A row of at most TABLE_SEQ_MAX entries is summed in ascending q; a longer one by its whole
     workgroup in an order fixed by its length and F.  A vertex with no entry is +0.0 whatever dst_scale.  No gradient.
-    ctr [n, F]: the difference gather hg_table_gather_t_diff_f32 -- the term starts from ctr[v] - src[pos_v[q] // k]."""
+    ctr [n, F]: the difference gather hg_table_gather_t_diff_f32 -- the term starts from ctr[v] - src[pos_v[q] // k].
+    bfloat16 rows (hg_table_gather_t_bf16): as table_gather; a long row keeps the float32 call's order, so its bits too."""
     _check_dtype(ptr_v, "ptr_v", torch.int32)
     _check_dtype(pos_v, "pos_v", torch.int32)
     if not isinstance(k, numbers.Integral) or isinstance(k, bool) or not 1 <= k <= K_MAX:
@@ -308,7 +359,7 @@ def table_gather_t(ptr_v, pos_v, k, src, w=None, src_scale=None, dst_scale=None,
     _check_table_index(ptr_v, "ptr_v")
     _check_table_index(pos_v, "pos_v")
     dev = ptr_v.device
-    _check_feat(src, "src", device=dev)
+    _check_feat(src, "src", device=dev, bf16_ok=True)
     if src.dim() != 2 or src.shape[0] < 1 or src.shape[1] < 1 or src.shape[0] * int(k) != pos_v.shape[0]:
         raise ValueError("src must be [rows, F >= 1] with rows * k = %d positions, got %s" % (pos_v.shape[0], tuple(src.shape)))
     rows, F = src.shape
@@ -316,46 +367,63 @@ def table_gather_t(ptr_v, pos_v, k, src, w=None, src_scale=None, dst_scale=None,
     w = _flat_or_none(w, "w", rows * int(k), dev)
     src_scale = _flat_or_none(src_scale, "src_scale", rows, dev)
     dst_scale = _flat_or_none(dst_scale, "dst_scale", n, dev)
-    ctr = _flat_or_none(ctr, "ctr", n * F, dev)
-    dst = torch.empty((n, F), dtype=torch.float32, device=dev)
+    ctr = _flat_or_none(ctr, "ctr", n * F, dev, bf16_ok=True)
+    io, out_dtype = _gather_io(src, ctr, dst_dtype)
+    dst = torch.empty((n, F), dtype=out_dtype, device=dev)
+    if io and not _whole_lanes(F, src, ctr, dst):
+        return table_gather_t(ptr_v, pos_v, k, _widened(src), w, src_scale, dst_scale, _widened(ctr)).to(out_dtype)
     L = _lib.lib()
-    entry, centre = (L.hg_table_gather_t_f32, ()) if ctr is None else (L.hg_table_gather_t_diff_f32, (_ptr(ctr),))
+    if io:
+        entry, tail = _bf16_entry("hg_table_gather_t_bf16"), (_ptr(ctr), _ptr(dst), io)
+    elif ctr is None:
+        entry, tail = L.hg_table_gather_t_f32, (_ptr(dst),)
+    else:
+        entry, tail = L.hg_table_gather_t_diff_f32, (_ptr(ctr), _ptr(dst))
     with torch.cuda.device(dev):
         _lib.check(entry(_ptr(ptr_v), _ptr(pos_v), rows, int(k), n, F, _ptr(src), _ptr(w), _ptr(src_scale), _ptr(dst_scale),
-                         *centre, _ptr(dst), _stream_handle(dev)))
+                         *tail, _stream_handle(dev)))
     return dst
 
 
 def table_dot(idx, A, B, a_scale=None, C=None, D=None):
     """out[i * k + s] = a_scale[j] * <A[j], B[i]> + <C[j], D[i]>, j = idx[i, s], over a table idx [rows, k]: hg_table_dot_f32,
     one launch and no [rows * k, F] array.  A, C [n, F]; B, D [rows, F]; a_scale [n] or None; C and D both or neither.  An
-    entry outside 0 .. n - 1 gives +0.0.  The order of the sum is include/hg_aggr.h's DOT ORDER.  No gradient."""
+    entry outside 0 .. n - 1 gives +0.0.  The order of the sum is include/hg_aggr.h's DOT ORDER.  No gradient.
+    A (and C with it) may be bfloat16 (hg_table_dot_bf16): out is the float32 call's on A.float() / C.float(), bit for bit;
+    B, D and a_scale stay float32."""
     _table_shape(idx)
     rows, k = _table_shape_values(idx)
     _check_table_index(idx, "idx")
     dev = idx.device
     if (C is None) != (D is None):
         raise ValueError("C and D must both be given or both be None")
-    _check_feat(A, "A", device=dev)
+    _check_feat(A, "A", device=dev, bf16_ok=True)
+    if C is not None and isinstance(C, torch.Tensor) and C.dtype != A.dtype:
+        raise TypeError("C must have A's dtype %s, got %s" % (A.dtype, C.dtype))
     if A.dim() != 2 or A.shape[0] < 1 or A.shape[1] < 1:
         raise ValueError("A must be [n >= 1, F >= 1], got %s" % (tuple(A.shape),))
     n, F = A.shape
     for name, t, shape in (("B", B, (rows, F)), ("C", C, (n, F)), ("D", D, (rows, F))):
         if t is not None:
-            _check_feat(t, name, device=dev)
+            _check_feat(t, name, device=dev, bf16_ok=name == "C")
             if tuple(t.shape) != shape:
                 raise ValueError("%s must be [%d, %d], got %s" % (name, shape[0], shape[1], tuple(t.shape)))
     a_scale = _flat_or_none(a_scale, "a_scale", n, dev)
+    if A.dtype == BF16 and not _whole_lanes(F, A, B, C, D):
+        return table_dot(idx, A.float(), B, a_scale, _widened(C), D)
+    entry = _bf16_entry("hg_table_dot_bf16") if A.dtype == BF16 else _lib.lib().hg_table_dot_f32
     out = torch.empty(rows * k, dtype=torch.float32, device=dev)
     with torch.cuda.device(dev):
-        _lib.check(_lib.lib().hg_table_dot_f32(_ptr(idx), rows, k, n, F, _ptr(A), _ptr(a_scale), _ptr(B), _ptr(C), _ptr(D),
-                                               _ptr(out), _stream_handle(dev)))
+        _lib.check(entry(_ptr(idx), rows, k, n, F, _ptr(A), _ptr(a_scale), _ptr(B), _ptr(C), _ptr(D), _ptr(out),
+                         _stream_handle(dev)))
     return out
 
 
 class _KnnDist(torch.autograd.Function):
     """dist[i, s] = |Q[i] - X[idx[i, s]]|^2 over a fixed table; the gradients are the two difference gathers with g = 2 dDist.
-    Saves the table, its transpose and the inputs X and Q -- nothing new of rows * k * F elements."""
+    Saves the table, its transpose and the inputs X and Q -- nothing new of rows * k * F elements.
+    bfloat16 X (and Q): dist and both difference gathers are float32 -- those of the widened rows -- and dX (with Q None
+    the float32 sum of the two gathers) and dQ are rounded once."""
 
     @staticmethod
     def forward(ctx, X, Q, idx, ptr_v, pos_v):
@@ -363,9 +431,11 @@ class _KnnDist(torch.autograd.Function):
         n, F = X.shape
         Qr = X if Q is None else Q
         dist = torch.empty((rows, k), dtype=torch.float32, device=X.device)
+        bf16 = X.dtype == BF16
+        Xk, Qk = (X.float(), Qr.float()) if bf16 and not _whole_lanes(F, X, Qr) else (X, Qr)
+        entry = _bf16_entry("hg_table_dist_bf16") if Xk.dtype == BF16 else _lib.lib().hg_table_dist_f32
         with torch.cuda.device(X.device):
-            _lib.check(_lib.lib().hg_table_dist_f32(_ptr(idx), rows, k, n, F, _ptr(Qr), _ptr(X), _ptr(dist),
-                                                    _stream_handle(X.device)))
+            _lib.check(entry(_ptr(idx), rows, k, n, F, _ptr(Qk), _ptr(Xk), _ptr(dist), _stream_handle(X.device)))
         ctx.same = Q is None
         ctx.save_for_backward(X, Qr, idx, ptr_v, pos_v)
         return dist
@@ -381,11 +451,19 @@ class _KnnDist(torch.autograd.Function):
             if ctx.needs_input_grad[0]:
                 dX = dX + table_gather(idx, X, g, ctr=X)
         elif ctx.needs_input_grad[1]:
-            dQ = table_gather(idx, X, g, ctr=Q)
+            dQ = table_gather(idx, X, g, ctr=Q).to(Q.dtype)
+        if dX is not None:
+            dX = dX.to(X.dtype)  # bfloat16 rows: the one rounding, after the float32 add
         return dX, dQ, None, None, None
 
 
-def knn_dist(idx, X, queries=None, transpose=None):
+def _rows_bf16(X, options):
+    """Whether X is a bfloat16 tensor that the caller's options (Options.incidence_bf16 = 'rows') let through."""
+    from . import ops
+    return ops._opt(options).incidence_bf16 == "rows" and isinstance(X, torch.Tensor) and X.dtype == BF16
+
+
+def knn_dist(idx, X, queries=None, transpose=None, options=None):
     """The squared distances of a GIVEN neighbour table, differentiable: dist float32 [rows, k] with dist[i, s] =
     sum_c (Q[i, c] - X[idx[i, s], c])^2, Q = `queries` [rows, F] or X itself (None; then rows = n).  The sum runs in ops.knn's
     order (include/hg_aggr.h, hg_table_dist_f32), so for the idx that ops.knn(X, k) returned -- under either form, with
@@ -396,12 +474,23 @@ def knn_dist(idx, X, queries=None, transpose=None):
     hg_table_gather_t_diff_f32, in the gathers' documented order, no atomics: two calls give the same bits, and identical
     rows (every self_first entry) contribute exactly 0.  With queries None the two are added with one torch add.
     transpose: the (ptr_v, pos_v) of ops.knn_transpose(idx, n) to reuse; computed when X needs a gradient and it is None.
-    float32 only.  Refusals, in this order and before a device is touched: TypeError for an idx (ptr_v, pos_v) that is not
-    int32 and an X or queries that is not float32; ValueError for the shapes and k; RuntimeError for CPU tensors."""
+    bfloat16 rows: under Options.incidence_bf16 = 'rows' (options=, resolved as every operator resolves it) X may be
+    bfloat16, and queries with it -- both or neither (hg_table_dist_bf16).  dist stays float32 and is knn_dist on X.float(),
+    bit for bit, so for the idx of ops.knn(Xb, k, form="dot") it is the dist that call returned; dX and dQ are the float32
+    call's, rounded once (with queries None after the one float32 add).  By default bfloat16 is refused.
+    Refusals, in this order and before a device is touched: TypeError for an idx (ptr_v, pos_v) that is not int32 and an X
+    or queries that is not float32 (or, under the option, bfloat16 for both alike); ValueError for the shapes and k;
+    RuntimeError for CPU tensors."""
+    bf16 = _rows_bf16(X, options)
     _table_shape(idx)
-    _check_dtype(X, "X", torch.float32, _NO_FORM % "knn_dist")
-    if queries is not None:
-        _check_dtype(queries, "queries", torch.float32, _NO_FORM % "knn_dist")
+    if bf16:
+        if queries is not None and not (isinstance(queries, torch.Tensor) and queries.dtype == BF16):
+            raise TypeError("queries must be a bfloat16 tensor where X is one (X and queries are both float32 or both "
+                            "bfloat16), got %s" % getattr(queries, "dtype", type(queries)))
+    else:
+        _check_dtype(X, "X", torch.float32, _NO_FORM % "knn_dist")
+        if queries is not None:
+            _check_dtype(queries, "queries", torch.float32, _NO_FORM % "knn_dist")
     _check_transpose_types(transpose)
     rows, k = _table_shape_values(idx)
     if X.dim() != 2 or X.shape[0] < 1 or X.shape[1] < 1:
@@ -414,9 +503,9 @@ def knn_dist(idx, X, queries=None, transpose=None):
         raise ValueError("queries must be [rows, F] = [%d, %d], got %s" % (rows, F, tuple(queries.shape)))
     _check_transpose_shapes(transpose, n, rows * k)
     _check_table_index(idx, "idx")
-    _check_feat(X, "X", device=idx.device)
+    _check_feat(X, "X", device=idx.device, bf16_ok=bf16)
     if queries is not None:
-        _check_feat(queries, "queries", device=idx.device)
+        _check_feat(queries, "queries", device=idx.device, bf16_ok=bf16)
     ptr_v = pos_v = None
     if torch.is_grad_enabled() and X.requires_grad:
         if transpose is None:
@@ -431,12 +520,14 @@ class _KnnAggr(torch.autograd.Function):
     """Y = degV . H_w (degE . (H_w^T X)) over a neighbour table; the gradient of X is the same two gathers swapped.  Saves the
     table, its transpose, the weight and the scales -- nothing of rows * F elements.  Where the weight asks for its gradient,
     dw[p = (i, s)] = degV[v] <dY[v], Xe[i]> + <X[v], G[i]>, v = idx[i, s], one launch of hg_table_dot_f32: Xe is computed
-    again in the backward, and the input X is saved as well."""
+    again in the backward, and the input X is saved as well.
+    bfloat16 X: Xe and G stay float32, Y and dX are rounded once in the second gather's store, dw (float32) comes from
+    hg_table_dot_bf16 -- the float32 node on X.float() and dY.float(), bit for bit, with the same saved tensors."""
 
     @staticmethod
     def forward(ctx, X, w, idx, ptr_v, pos_v, degE, degV):
         Xe = table_gather(idx, X, w, None, degE)
-        Y = table_gather_t(ptr_v, pos_v, idx.shape[1], Xe, w, None, degV)
+        Y = table_gather_t(ptr_v, pos_v, idx.shape[1], Xe, w, None, degV, dst_dtype=X.dtype)
         ctx.save_for_backward(idx, ptr_v, pos_v, w, degE, degV, *((X,) if ctx.needs_input_grad[1] else ()))
         return Y
 
@@ -445,7 +536,7 @@ class _KnnAggr(torch.autograd.Function):
         idx, ptr_v, pos_v, w, degE, degV = ctx.saved_tensors[:6]
         dY = dY.contiguous()
         G = table_gather(idx, dY, w, degV, degE)
-        dX = table_gather_t(ptr_v, pos_v, idx.shape[1], G, w) if ctx.needs_input_grad[0] else None
+        dX = table_gather_t(ptr_v, pos_v, idx.shape[1], G, w, dst_dtype=dY.dtype) if ctx.needs_input_grad[0] else None
         dw = None
         if ctx.needs_input_grad[1]:
             X = ctx.saved_tensors[6]
@@ -454,7 +545,7 @@ class _KnnAggr(torch.autograd.Function):
         return dX, dw, None, None, None, None, None
 
 
-def knn_aggr(idx, X, weight=None, degE=None, degV=None, transpose=None, weight_grad=False):
+def knn_aggr(idx, X, weight=None, degE=None, degV=None, transpose=None, weight_grad=False, options=None):
     """Y = degV . H_w (degE . (H_w^T X)) over the hypergraph of a neighbour table idx [rows, k] (int32, ops.knn's: hyperedge
     i = the vertices idx[i, :]) and features X [n, F] (float32), with no plan and no host step: two launches of the table
     gathers (include/hg_aggr.h, hg_table_gather_f32 / hg_table_gather_t_f32) and, where `transpose` is None, the transpose.
@@ -468,11 +559,17 @@ def knn_aggr(idx, X, weight=None, degE=None, degV=None, transpose=None, weight_g
     dw[p = (i, s)] = degV[v] <dY[v], Xe[i]> + <X[v], G[i]>, v = idx[i, s], Xe = table_gather(X, w, dst_scale=degE) computed
     again in the backward -- one launch of hg_table_dot_f32, no [rows * k, F] array, no atomics.  Y and dX keep the bits of
     the default call; the backward then also keeps X, an input.
+    bfloat16 rows: under Options.incidence_bf16 = 'rows' (options=, resolved as every operator resolves it) X may be
+    bfloat16 (hg_table_gather_bf16 / hg_table_gather_t_bf16 / hg_table_dot_bf16).  Y and dX are bfloat16: the float32 call
+    on X.float() (upstream dY.float()), rounded once; the hyperedge rows between the hops, dw and every sum stay float32,
+    and so do weight, degE and degV whatever the option.  By default bfloat16 is refused.
     Refusals, in this order and before a device is touched: TypeError for an idx (ptr_v, pos_v) that is not int32 and for
-    an X, weight, degE or degV that is not float32; ValueError for the shapes and k; RuntimeError for a weight, degE or
-    degV that requires a gradient, and for CPU tensors."""
+    an X (bfloat16 under the option apart), weight, degE or degV that is not float32; ValueError for the shapes and k;
+    RuntimeError for a weight, degE or degV that requires a gradient, and for CPU tensors."""
+    bf16 = _rows_bf16(X, options)
     _table_shape(idx)
-    _check_dtype(X, "X", torch.float32, _NO_FORM % "knn_aggr")
+    if not bf16:
+        _check_dtype(X, "X", torch.float32, _NO_FORM % "knn_aggr")
     scales = (("weight", weight), ("degE", degE), ("degV", degV))
     for name, t in scales:
         if t is not None:
@@ -493,7 +590,7 @@ def knn_aggr(idx, X, weight=None, degE=None, degV=None, transpose=None, weight_g
             if t is not None and t.requires_grad and not (weight_grad and name == "weight"):
                 raise RuntimeError("%s gets no gradient from knn_aggr: pass %s.detach()" % (name, name))
     _check_table_index(idx, "idx")
-    _check_feat(X, "X", device=idx.device)
+    _check_feat(X, "X", device=idx.device, bf16_ok=bf16)
     for name, t in scales:
         if t is not None:
             _check_feat(t, name, device=idx.device)
@@ -521,8 +618,9 @@ class KnnHypergraph:
       aggregate(Z, probabilistic=False, m_prob=1.0, X=None): ops.knn_aggr over the table; X goes to weights, and the
         weights then get their gradient (weight_grad=True).
     form: ops.knn's -- "dot" gives the same idx and dist through the matrix-unit prefilter, and its own mean.  Under "dot" X
-    may be bfloat16: the table, dist, mean, transpose and degrees are int32 / float32 as always; aggregate, ops.knn_aggr and
-    ops.knn_dist stay float32 only."""
+    may be bfloat16: the table, dist, mean, transpose and degrees are int32 / float32 as always, and aggregate / weights take
+    bfloat16 Z / X where `options` (or the caller's) has Options.incidence_bf16 = 'rows' -- ops.knn_aggr's and ops.knn_dist's
+    bfloat16 rows, the weights float32."""
 
     @classmethod
     def build(cls, X, k, segments=None, form="difference"):
@@ -539,14 +637,16 @@ class KnnHypergraph:
         self.degV = torch.where(deg > 0, deg.pow(-0.5), torch.ones_like(deg))
         return self
 
-    def weights(self, m_prob=1.0, X=None):
+    def weights(self, m_prob=1.0, X=None, options=None):
         if X is None:
             return knn_incidence_weights(self.dist, self.mean, m_prob)
-        return knn_incidence_weights(knn_dist(self.idx, X, transpose=(self.ptr_v, self.pos_v)), self.mean, m_prob)
+        dist = knn_dist(self.idx, X, transpose=(self.ptr_v, self.pos_v), options=options)
+        return knn_incidence_weights(dist, self.mean, m_prob)
 
-    def aggregate(self, Z, probabilistic=False, m_prob=1.0, X=None):
-        w = self.weights(m_prob, X) if probabilistic else None
-        return knn_aggr(self.idx, Z, w, self.degE, self.degV, transpose=(self.ptr_v, self.pos_v), weight_grad=X is not None)
+    def aggregate(self, Z, probabilistic=False, m_prob=1.0, X=None, options=None):
+        w = self.weights(m_prob, X, options) if probabilistic else None
+        return knn_aggr(self.idx, Z, w, self.degE, self.degV, transpose=(self.ptr_v, self.pos_v), weight_grad=X is not None,
+                        options=options)
 
 
 def table_seq_max():

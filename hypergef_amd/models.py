@@ -155,12 +155,13 @@ class DynamicHypergraphConv(nn.Module):
     selection has no gradient) and `mean` is a constant of the construction.  No parameter is added, the layer still
     waits nowhere with segments=None and is still recorded into a hipGraph.  False (the default) is the layer above, bit for
     bit, with the same saved tensors.
-    After .to(torch.bfloat16), with knn_form="dot" and device_graph=False, the layer runs on bfloat16 rows: the neighbours are
-    searched on the bfloat16 input itself (ops.knn's bfloat16 rows: the hypergraph of X.float(), float32 distances), the
-    unweighted sums run on the bfloat16 HGNNAggr, and probabilistic=True turns Options.incidence_bf16 = 'rows' on for the
-    layer's own HGNNAggrIncidence call, the weights staying float32.  device_graph=True on bfloat16 input still raises
-    ops.knn_aggr's TypeError (the table gathers are float32 only), and under knn_form="difference" the search refuses
-    bfloat16.  float32 layers are untouched."""
+    After .to(torch.bfloat16), with knn_form="dot", the layer runs on bfloat16 rows: the neighbours are searched on the
+    bfloat16 input itself (ops.knn's bfloat16 rows: the hypergraph of X.float(), float32 distances).  device_graph=False:
+    the unweighted sums run on the bfloat16 HGNNAggr, and probabilistic=True turns Options.incidence_bf16 = 'rows' on for the
+    layer's own HGNNAggrIncidence call.  device_graph=True: the layer turns the same option on for its own ops.knn_aggr /
+    ops.knn_dist calls (the table kernels' bfloat16 rows: the float32 layer's aggregate on Z.float(), rounded once), still
+    waits nowhere, is still recorded into a hipGraph, and learn_distances=True works.  The weights stay float32 everywhere.
+    Under knn_form="difference" the search refuses bfloat16.  float32 layers are untouched."""
 
     def __init__(self, in_channels, out_channels, k, probabilistic=False, segments=None, m_prob=1.0, options=None,
                  device_graph=False, knn_form="difference", learn_distances=False):
@@ -183,9 +184,13 @@ class DynamicHypergraphConv(nn.Module):
         if self.device_graph:
             from .knn_graph import KnnHypergraph
             hyperg = self.hyperg = KnnHypergraph.build(X, self.k, segments=self.segments, form=self.knn_form)
+            Z = self.lin(X)
+            options = self.options
+            if Z.dtype == torch.bfloat16:  # bfloat16 rows for the layer's own table calls; the weights stay float32
+                options = (options if options is not None else ops.current_options()).replace(incidence_bf16="rows")
             if self.learn_distances:
-                return hyperg.aggregate(self.lin(X), True, self.m_prob, X=X)
-            return hyperg.aggregate(self.lin(X), probabilistic=self.probabilistic, m_prob=self.m_prob)
+                return hyperg.aggregate(Z, True, self.m_prob, X=X, options=options)
+            return hyperg.aggregate(Z, probabilistic=self.probabilistic, m_prob=self.m_prob, options=options)
         from .hypergraph import HyperGraph
         hyperg = self.hyperg = HyperGraph.from_knn(X.detach(), self.k, X.device, segments=self.segments, form=self.knn_form)
         Z = self.lin(X)

@@ -56,7 +56,8 @@ class Options:
                  node_feat / src / A / B on the library's bf16-row kernels (hg_aggr_incidence_heads_bf16 and its
                  neighbours): fp32 sums in the float32 call's order, one rounding of a bfloat16 result.  The weights, scales
                  and the dot's result stay float32; incidence_softmax, incidence_sum, incidence_attention_aggr and
-                 hyperedge_dot stay float32 only.
+                 hyperedge_dot stay float32 only.  'rows' also lets ops.knn_aggr and ops.knn_dist (and KnnHypergraph's
+                 aggregate / weights) take bfloat16 X / queries on the table kernels' bf16-row instances.
 
     Every operator resolves its options per call -- an explicit `options=` argument, else the innermost
     `with ops.options(...)` block of the calling thread, else the process defaults -- and an autograd node keeps

@@ -925,7 +925,7 @@ HG_API int hg_knn_dot_estimates_bf16(const uint16_t *Q, int32_t nq, const uint16
  * writes: hyperedge i has the k members idx[i, 0 .. k - 1], so H_T is the table itself (csrptr_t an arange) and position
  * p = i k + s of the table is entry s of hyperedge i.  1 <= k <= 64 and rows * k < 2^31.  None of the three entries
  * allocates, synchronises or copies to or from the host: each launches on `stream` and returns, so each can be recorded
- * into a hipGraph.  float32 only.
+ * into a hipGraph.  float32 rows; the hg_table_*_bf16 entries below take bfloat16 rows.
  *
  * hg_table_transpose: ptr_v [n + 1] receives the CSR offsets of the n vertices and pos_v[ptr_v[v] .. ptr_v[v + 1]) the
  *   positions p with idx[p] == v in ASCENDING p: the stable sort of the positions by vertex, a function of idx alone.
@@ -968,7 +968,7 @@ HG_API int hg_table_gather_t_f32(const int32_t *ptr_v, const int32_t *pos_v, int
 /* Training through the weights of a neighbour table (csrc/hg_table.hip): the distances of a given table, the two
  * "difference gathers" that are their gradient, and the dot products that are the gradient of the table's weights.  Like
  * the entries above, each launches once on `stream`, allocates and waits for nothing and can be recorded into a hipGraph;
- * float32 only; no floating-point atomics, so two calls give the same bits.
+ * float32 rows (bfloat16 rows: the hg_table_*_bf16 entries below); no floating-point atomics, so two calls give the same bits.
  *
  * hg_table_dist_f32: dist[i, s] = d2(i, idx[i, s]) = sum_c (Q[i, c] - X[idx[i, s], c])^2 for Q [rows, F], X [n, F],
  *   dist [rows, k], in hg_knn_f32's arithmetic (its d2(i, j) paragraph above): the difference form, c = 0 .. F - 1 in that
@@ -1010,6 +1010,44 @@ HG_API int hg_table_gather_t_diff_f32(const int32_t *ptr_v, const int32_t *pos_v
 HG_API int hg_table_dot_f32(const int32_t *idx, int32_t rows, int32_t k, int32_t n, int32_t F, const float *A,
                             const float *a_scale, const float *B, const float *C, const float *D, float *out,
                             hg_stream_t stream);
+
+/* bfloat16 feature rows over a neighbour table (csrc/hg_table_bf16.hip): the entries above on rows of half the bytes.  Like
+ * them each launches once on `stream`, allocates and waits for nothing and can be recorded into a hipGraph.
+ * THE CONTRACT: a call equals the float32 call on the widened rows, BIT FOR BIT -- "widened" is the exact conversion of
+ * every bfloat16 element to float32, and a bfloat16 result is that call's float32 result rounded once, to nearest-even, in
+ * the store.  It holds on every input: rows longer than HG_TABLE_SEQ_MAX, entries out of range (nothing added, nothing read
+ * through), empty vertex rows (+0.0 whatever the scale).  w, the scales, dist, out, the hyperedge rows between the hops and
+ * every accumulator are float32.
+ *
+ * hg_table_gather_bf16 / hg_table_gather_t_bf16: hg_table_gather_f32 / hg_table_gather_t_f32, and with a non-NULL ctr the
+ *   difference gathers hg_table_gather_diff_f32 / hg_table_gather_t_diff_f32.  io is exactly one of
+ *     HG_ROWS_SRC_BF16: src (and ctr) bfloat16, dst float32 -- hop 0, the backward's G, both difference gathers;
+ *     HG_ROWS_DST_BF16: src float32, dst bfloat16 rounded once -- hop 1 and dX; ctr must be NULL.
+ *   A lane owns 8 columns (16 bytes of the bfloat16 side), a lane group is min(F / 8, 64) lanes.  LONG ROWS: the ORDER
+ *   paragraph above cuts a vertex row longer than HG_TABLE_SEQ_MAX into P pieces with P a function of the float32 call's
+ *   lanes per row; these entries sum such a row in exactly that call's pieces and tree (L = min(F / 4, 64), P = 4 * (64 /
+ *   L), 4 columns a lane), so its bits are the float32 call's too.
+ * hg_table_dist_bf16: hg_table_dist_f32 on bfloat16 Q and X; dist is float32, so for the idx that hg_knn_dot_bf16 returned
+ *   it is the dist that call returned, bit for bit.
+ * hg_table_dot_bf16: hg_table_dot_f32 with bfloat16 A and C (the gathered rows) and float32 a_scale, B, D and out, in the
+ *   DOT ORDER at c = 4.
+ * Refusals launch nothing, set hg_last_error, in the float32 entries' order: HG_ERR_INVALID for a null idx (ptr_v, pos_v),
+ *   a null src or dst / Q, X or dist / A, B or out, C without D; for rows, n or F < 1, k outside 1 .. 64, rows * k >= 2^31;
+ *   for an io that is not exactly one of the two (0, 3, another bit), for ctr with HG_ROWS_DST_BF16; then
+ *   HG_ERR_UNSUPPORTED for a float32 pointer that is not 4-byte or a bfloat16 pointer that is not 2-byte aligned, and for
+ *   F % 8 != 0 or row arrays that are not 16-byte aligned: the caller then widens, runs the float32 entry and rounds,
+ *   which gives the same bits. */
+HG_API int hg_table_gather_bf16(const int32_t *idx, int32_t rows, int32_t k, int32_t n, int32_t F, const void *src,
+                                const float *w, const float *src_scale, const float *dst_scale, const void *ctr, void *dst,
+                                int32_t io, hg_stream_t stream);
+HG_API int hg_table_gather_t_bf16(const int32_t *ptr_v, const int32_t *pos_v, int32_t rows, int32_t k, int32_t n, int32_t F,
+                                  const void *src, const float *w, const float *src_scale, const float *dst_scale,
+                                  const void *ctr, void *dst, int32_t io, hg_stream_t stream);
+HG_API int hg_table_dist_bf16(const int32_t *idx, int32_t rows, int32_t k, int32_t n, int32_t F, const uint16_t *Q,
+                              const uint16_t *X, float *dist, hg_stream_t stream);
+HG_API int hg_table_dot_bf16(const int32_t *idx, int32_t rows, int32_t k, int32_t n, int32_t F, const uint16_t *A,
+                             const float *a_scale, const float *B, const uint16_t *C, const float *D, float *out,
+                             hg_stream_t stream);
 
 #ifdef __cplusplus
 }
