@@ -7,6 +7,8 @@ host-side layout step of `HyperGraph.from_knn`.
 
 `knn_transpose` and `knn_aggr` (`ops.knn_transpose` / `ops.knn_aggr`; hg_table_* in include/hg_aggr.h) aggregate over the
 neighbour table itself, with no plan and no host step, and `KnnHypergraph` is the device-only hypergraph they serve.
+`knn_gather` (`ops.knn_gather`) is one hop over the table with a choice of sum, mean, max or min (hg_table_reduce_* /
+hg_table_select_*: the comparison kernels and their exact gradient), and `knn_aggr(first=, second=)` composes two of them.
 `knn_dist` (`ops.knn_dist`) gives a table's distances with a gradient, and `knn_aggr(weight_grad=True)` the gradient of its
 weights: together they train through the weights of a probabilistic kNN hypergraph.  Both take bfloat16 rows under
 Options.incidence_bf16 = 'rows' (hg_table_*_bf16): the float32 call on the widened rows, bit for bit, rounded once.
@@ -516,6 +518,239 @@ def knn_dist(idx, X, queries=None, transpose=None, options=None):
     return _KnnDist.apply(X, queries, idx, ptr_v, pos_v)
 
 
+# ---- one hop over the table with a choice of reduction (hg_table_reduce_* / hg_table_select_*) -------------------------------
+
+REDUCES = ("sum", "mean", "max", "min")
+HOPS = ("hyperedge", "vertex")
+_OPS = {"max": _lib.HG_REDUCE_MAX, "min": _lib.HG_REDUCE_MIN}
+
+
+def _reduce_entry(name):
+    """An hg_table_reduce_* / hg_table_select_* entry of the library; a build without it is an error, never another path."""
+    L = _lib.lib()
+    if not hasattr(L, name):
+        raise RuntimeError("this build of libhgaggr has no %s (max / min over a neighbour table)" % name)
+    return getattr(L, name)
+
+
+def table_reduce(idx, src, op, dst_scale=None, want_arg=True):
+    """(dst [rows, F], arg int32 [rows, F] or None): the greatest (op 'max') or smallest ('min') src[idx[i, s], c] over s, times
+    dst_scale[i], and the winner's position i k + s -- hg_table_reduce_f32 and its total order.  No checks, no gradient."""
+    rows, k = idx.shape
+    n, F = src.shape
+    dst = torch.empty((rows, F), dtype=torch.float32, device=src.device)
+    arg = torch.empty((rows, F), dtype=torch.int32, device=src.device) if want_arg else None
+    with torch.cuda.device(src.device):
+        _lib.check(_reduce_entry("hg_table_reduce_f32")(_ptr(idx), rows, k, n, F, _OPS[op], _ptr(src), _ptr(dst_scale), _ptr(dst),
+                                                        _ptr(arg), _stream_handle(src.device)))
+    return dst, arg
+
+
+def table_reduce_t(ptr_v, pos_v, k, src, op, dst_scale=None, want_arg=True):
+    """The same over a vertex's hyperedges, through the transpose: (dst [n, F], arg [n, F] or None) of src [rows, F] --
+    hg_table_reduce_t_f32.  A vertex with no entry is +0.0 and arg -1."""
+    rows, F = src.shape
+    n = ptr_v.shape[0] - 1
+    dst = torch.empty((n, F), dtype=torch.float32, device=src.device)
+    arg = torch.empty((n, F), dtype=torch.int32, device=src.device) if want_arg else None
+    with torch.cuda.device(src.device):
+        _lib.check(_reduce_entry("hg_table_reduce_t_f32")(_ptr(ptr_v), _ptr(pos_v), rows, int(k), n, F, _OPS[op], _ptr(src),
+                                                          _ptr(dst_scale), _ptr(dst), _ptr(arg), _stream_handle(src.device)))
+    return dst, arg
+
+
+def table_select(idx, gs, arg):
+    """dsrc [rows, F] of table_reduce_t's src: row i sums gs[idx[i, s]] where arg[idx[i, s]] is the position i k + s, ascending
+    s (hg_table_select_f32).  gs and arg are [n, F]."""
+    rows, k = idx.shape
+    n, F = gs.shape
+    dsrc = torch.empty((rows, F), dtype=torch.float32, device=gs.device)
+    with torch.cuda.device(gs.device):
+        _lib.check(_reduce_entry("hg_table_select_f32")(_ptr(idx), rows, k, n, F, _ptr(gs), _ptr(arg), _ptr(dsrc),
+                                                        _stream_handle(gs.device)))
+    return dsrc
+
+
+def table_select_t(ptr_v, pos_v, k, gs, arg):
+    """dsrc [n, F] of table_reduce's src: vertex v sums gs[p // k] over its positions p that won their row, in table_gather_t's
+    order (hg_table_select_t_f32).  gs and arg are [rows, F]."""
+    rows, F = gs.shape
+    n = ptr_v.shape[0] - 1
+    dsrc = torch.empty((n, F), dtype=torch.float32, device=gs.device)
+    with torch.cuda.device(gs.device):
+        _lib.check(_reduce_entry("hg_table_select_t_f32")(_ptr(ptr_v), _ptr(pos_v), rows, int(k), n, F, _ptr(gs), _ptr(arg),
+                                                          _ptr(dsrc), _stream_handle(gs.device)))
+    return dsrc
+
+
+class _KnnGatherSum(torch.autograd.Function):
+    """One sum hop over the table; the gradient is the other hop with the scale moved to the source side.  Saves the table,
+    its transpose and the scale."""
+
+    @staticmethod
+    def forward(ctx, src, idx, ptr_v, pos_v, scale, to):
+        ctx.to = to
+        ctx.save_for_backward(idx, ptr_v, pos_v, scale)
+        if to == "hyperedge":
+            return table_gather(idx, src, None, None, scale)
+        return table_gather_t(ptr_v, pos_v, idx.shape[1], src, None, None, scale)
+
+    @staticmethod
+    def backward(ctx, grad):
+        idx, ptr_v, pos_v, scale = ctx.saved_tensors
+        grad = grad.contiguous()
+        if ctx.to == "hyperedge":
+            dsrc = table_gather_t(ptr_v, pos_v, idx.shape[1], grad, None, scale)
+        else:
+            dsrc = table_gather(idx, grad, None, scale)
+        return dsrc, None, None, None, None, None
+
+
+class _KnnGatherReduce(torch.autograd.Function):
+    """One max / min hop over the table.  Saves arg, the table, its transpose and the scale -- no source rows; the backward
+    is the select kernel of the other walk on grad * scale."""
+
+    @staticmethod
+    def forward(ctx, src, idx, ptr_v, pos_v, scale, to, op):
+        ctx.to = to
+        if to == "hyperedge":
+            dst, arg = table_reduce(idx, src, op, scale)
+        else:
+            dst, arg = table_reduce_t(ptr_v, pos_v, idx.shape[1], src, op, scale)
+        ctx.save_for_backward(idx, ptr_v, pos_v, scale, arg)
+        ctx.mark_non_differentiable(arg)
+        return dst, arg
+
+    @staticmethod
+    def backward(ctx, grad, _):
+        idx, ptr_v, pos_v, scale, arg = ctx.saved_tensors
+        gs = (grad if scale is None else grad * scale[:, None]).contiguous()
+        if ctx.to == "hyperedge":
+            dsrc = table_select_t(ptr_v, pos_v, idx.shape[1], gs, arg)
+        else:
+            dsrc = table_select(idx, gs, arg)
+        return dsrc, None, None, None, None, None, None
+
+
+def knn_gather(idx, src, to="hyperedge", reduce="sum", scale=None, transpose=None, num_nodes=None, return_index=False):
+    """One hop over a neighbour table idx [rows, k] (int32, ops.knn's) as an operator of its own, with no plan and no host step,
+    differentiable in src.  to='hyperedge': src is [n, F] and dst[i] = scale[i] * reduce_s src[idx[i, s]], [rows, F];
+    to='vertex': src is [rows, F] and dst[v] = scale[v] * reduce over the positions p with idx[p] == v of src[p // k], [n, F]
+    with n = num_nodes (default: rows), through `transpose` = ops.knn_transpose(idx, n), computed where it is needed and not
+    given.  scale: one float32 factor per row of dst ([count] or [count, 1]), or None; it gets no gradient.
+    reduce: 'sum' is hg_table_gather_f32 / hg_table_gather_t_f32 bit for bit, and its gradient the other of the two with the
+    scale on the source side.  'mean' runs the same kernels with dst_scale = scale * (1 / len) formed in float32 by torch, len
+    = k for a hyperedge and the vertex's number of entries for a vertex (none: 0); nothing is read back.  'max' / 'min'
+    (hg_table_reduce_f32 / hg_table_reduce_t_f32) take the greatest / smallest entry of every row and column under the total
+    order (value, then the smaller position p = i k + s): -0.0 ties +0.0, a row of -inf has a winner, an entry outside
+    0 .. n - 1 is no candidate, a row with no candidate is +0.0 whatever its scale, NaN is unspecified; every call gives the
+    same bits.  Their gradient goes to the winner alone -- a duplicate entry gets it once -- through the select kernels
+    (hg_table_select_*), no atomics; the node keeps arg, the table, its transpose and the scale, and no source rows.
+    return_index=True (max / min only) returns (dst, arg), arg int32 the winner's position (-1: no candidate), not
+    differentiable.  float32 only: no bfloat16 rows, no weights, no heads.
+    Refusals, in this order and before a device is touched: TypeError for an idx (ptr_v, pos_v) that is not int32 and a src
+    or scale that is not float32 (bfloat16 too, whatever Options.incidence_bf16 says); ValueError for an unknown to or
+    reduce, for the shapes and k, for return_index with 'sum' / 'mean'; RuntimeError for a scale that requires a gradient
+    and for CPU tensors."""
+    _table_shape(idx)
+    _check_dtype(src, "src", torch.float32, " (knn_gather has no bfloat16, float16 or float64 form)")
+    if scale is not None:
+        _check_dtype(scale, "scale", torch.float32)
+    _check_transpose_types(transpose)
+    if to not in HOPS:
+        raise ValueError("to must be 'hyperedge' or 'vertex', got %r" % (to,))
+    if reduce not in REDUCES:
+        raise ValueError("reduce must be one of %s, got %r" % (", ".join(repr(r) for r in REDUCES), reduce))
+    rows, k = _table_shape_values(idx)
+    if src.dim() != 2 or src.shape[0] < 1 or src.shape[1] < 1:
+        raise ValueError("src must be [%s, F >= 1], got %s" % ("n >= 1" if to == "hyperedge" else "rows", tuple(src.shape)))
+    if to == "hyperedge":
+        n, count = src.shape[0], rows
+        if num_nodes is not None and num_nodes != n:
+            raise ValueError("src has %d rows, num_nodes is %r" % (n, num_nodes))
+    else:
+        if src.shape[0] != rows:
+            raise ValueError("to='vertex' takes one row of src per row of idx: %d rows, src has %d" % (rows, src.shape[0]))
+        n = rows if num_nodes is None else num_nodes
+        if not isinstance(n, numbers.Integral) or isinstance(n, bool) or not 1 <= n < 2 ** 31 - 1:
+            raise ValueError("num_nodes must be a positive integer, got %r" % (num_nodes,))
+        n = count = int(n)
+    if scale is not None and tuple(scale.shape) not in ((count,), (count, 1)):
+        raise ValueError("scale must be [%d] or [%d, 1], got %s" % (count, count, tuple(scale.shape)))
+    _check_transpose_shapes(transpose, n, rows * k)
+    if return_index and reduce not in _OPS:
+        raise ValueError("return_index needs reduce='max' or 'min', got %r" % reduce)
+    if torch.is_grad_enabled() and scale is not None and scale.requires_grad:
+        raise RuntimeError("scale gets no gradient from knn_gather: pass scale.detach()")
+    _check_table_index(idx, "idx")
+    _check_feat(src, "src", device=idx.device)
+    if scale is not None:
+        _check_feat(scale, "scale", device=idx.device)
+        scale = scale.detach().reshape(-1)
+    needs_grad = torch.is_grad_enabled() and src.requires_grad
+    ptr_v = pos_v = None
+    if to == "vertex" or needs_grad:
+        if transpose is None:
+            transpose = knn_transpose(idx, n)
+        ptr_v, pos_v = transpose
+        _check_table_index(ptr_v, "ptr_v")
+        _check_table_index(pos_v, "pos_v")
+    if reduce in _OPS:
+        if needs_grad:
+            dst, arg = _KnnGatherReduce.apply(src, idx, ptr_v, pos_v, scale, to, reduce)
+        elif to == "hyperedge":
+            dst, arg = table_reduce(idx, src, reduce, scale, want_arg=return_index)
+        else:
+            dst, arg = table_reduce_t(ptr_v, pos_v, k, src, reduce, scale, want_arg=return_index)
+        return (dst, arg) if return_index else dst
+    if reduce == "mean":
+        if to == "hyperedge":
+            recip = torch.full((rows,), 1.0 / k, dtype=torch.float32, device=idx.device)
+        else:
+            recip = 1.0 / (ptr_v[1:] - ptr_v[:-1]).to(torch.float32).clamp(min=1.0)  # no entry: the kernels write +0.0 themselves
+        scale = recip if scale is None else scale * recip
+    if needs_grad:
+        return _KnnGatherSum.apply(src, idx, ptr_v, pos_v, scale, to)
+    if to == "hyperedge":
+        return table_gather(idx, src, None, None, scale)
+    return table_gather_t(ptr_v, pos_v, k, src, None, None, scale)
+
+
+def _knn_aggr_reduced(idx, X, weight, degE, degV, transpose, first, second):
+    """knn_aggr with a reduction other than the two sums: two knn_gather calls, degE the first hop's scale and degV the second's."""
+    _table_shape(idx)
+    _check_dtype(X, "X", torch.float32, " (knn_aggr with first / second other than 'sum' has no bfloat16 form)")
+    scales = (("weight", weight), ("degE", degE), ("degV", degV))
+    for name, t in scales:
+        if t is not None:
+            _check_dtype(t, name, torch.float32)
+    _check_transpose_types(transpose)
+    for name, r in (("first", first), ("second", second)):
+        if r not in REDUCES:
+            raise ValueError("%s must be one of %s, got %r" % (name, ", ".join(repr(x) for x in REDUCES), r))
+    if weight is not None:
+        raise ValueError("first=%r, second=%r take no weight (a comparison has no weighted form here, and the means keep the "
+                         "sums' weights out as well)" % (first, second))
+    rows, k = _table_shape_values(idx)
+    if X.dim() != 2 or X.shape[0] < 1 or X.shape[1] < 1:
+        raise ValueError("X must be [n >= 1, F >= 1], got %s" % (tuple(X.shape),))
+    n = X.shape[0]
+    for name, t, count in (("degE", degE, rows), ("degV", degV, n)):
+        if t is not None and tuple(t.shape) not in ((count,), (count, 1)):
+            raise ValueError("%s must be [%d] or [%d, 1], got %s" % (name, count, count, tuple(t.shape)))
+    _check_transpose_shapes(transpose, n, rows * k)
+    if torch.is_grad_enabled():
+        for name, t in scales:
+            if t is not None and t.requires_grad:
+                raise RuntimeError("%s gets no gradient from knn_aggr: pass %s.detach()" % (name, name))
+    _check_table_index(idx, "idx")
+    _check_feat(X, "X", device=idx.device)
+    if transpose is None:
+        transpose = knn_transpose(idx, n)
+    Xe = knn_gather(idx, X, "hyperedge", first, degE, transpose)
+    return knn_gather(idx, Xe, "vertex", second, degV, transpose, num_nodes=n)
+
+
 class _KnnAggr(torch.autograd.Function):
     """Y = degV . H_w (degE . (H_w^T X)) over a neighbour table; the gradient of X is the same two gathers swapped.  Saves the
     table, its transpose, the weight and the scales -- nothing of rows * F elements.  Where the weight asks for its gradient,
@@ -545,7 +780,8 @@ class _KnnAggr(torch.autograd.Function):
         return dX, dw, None, None, None, None, None
 
 
-def knn_aggr(idx, X, weight=None, degE=None, degV=None, transpose=None, weight_grad=False, options=None):
+def knn_aggr(idx, X, weight=None, degE=None, degV=None, transpose=None, weight_grad=False, options=None, first="sum",
+             second="sum"):
     """Y = degV . H_w (degE . (H_w^T X)) over the hypergraph of a neighbour table idx [rows, k] (int32, ops.knn's: hyperedge
     i = the vertices idx[i, :]) and features X [n, F] (float32), with no plan and no host step: two launches of the table
     gathers (include/hg_aggr.h, hg_table_gather_f32 / hg_table_gather_t_f32) and, where `transpose` is None, the transpose.
@@ -563,9 +799,16 @@ def knn_aggr(idx, X, weight=None, degE=None, degV=None, transpose=None, weight_g
     bfloat16 (hg_table_gather_bf16 / hg_table_gather_t_bf16 / hg_table_dot_bf16).  Y and dX are bfloat16: the float32 call
     on X.float() (upstream dY.float()), rounded once; the hyperedge rows between the hops, dw and every sum stay float32,
     and so do weight, degE and degV whatever the option.  By default bfloat16 is refused.
+    first / second ('sum', 'mean', 'max', 'min'): the reduction over a hyperedge's members / over a vertex's hyperedges.  With
+    both at 'sum' the call is the one above, on its code path and with its bits.  Otherwise it is two ops.knn_gather calls,
+    Xe = knn_gather(X, to='hyperedge', reduce=first, scale=degE) and Y = knn_gather(Xe, to='vertex', reduce=second,
+    scale=degV): UniSAGE's mean / max and EdgeConv's max on the device table.  A weight then raises ValueError and bfloat16
+    TypeError, whatever the option; the gradient of X is knn_gather's (max / min: to the winner alone).
     Refusals, in this order and before a device is touched: TypeError for an idx (ptr_v, pos_v) that is not int32 and for
     an X (bfloat16 under the option apart), weight, degE or degV that is not float32; ValueError for the shapes and k;
     RuntimeError for a weight, degE or degV that requires a gradient, and for CPU tensors."""
+    if first != "sum" or second != "sum":
+        return _knn_aggr_reduced(idx, X, weight, degE, degV, transpose, first, second)
     bf16 = _rows_bf16(X, options)
     _table_shape(idx)
     if not bf16:
@@ -615,8 +858,9 @@ class KnnHypergraph:
       weights(m_prob, X=None): HGNN's exp(-d2 / (m_prob mean)^2) entries [N k].  With X (the rows the table was built
         from, attached to the graph) d2 is ops.knn_dist(idx, X) -- the same bits as `dist`, with a gradient into X; `mean`
         stays detached: its gradient is an N x N sum and HGNN treats avg_dis as a constant of the construction.
-      aggregate(Z, probabilistic=False, m_prob=1.0, X=None): ops.knn_aggr over the table; X goes to weights, and the
-        weights then get their gradient (weight_grad=True).
+      aggregate(Z, probabilistic=False, m_prob=1.0, X=None, first="sum", second="sum"): ops.knn_aggr over the table; X goes
+        to weights, and the weights then get their gradient (weight_grad=True); first / second are ops.knn_aggr's reductions
+        (no weights with anything but the two sums).
     form: ops.knn's -- "dot" gives the same idx and dist through the matrix-unit prefilter, and its own mean.  Under "dot" X
     may be bfloat16: the table, dist, mean, transpose and degrees are int32 / float32 as always, and aggregate / weights take
     bfloat16 Z / X where `options` (or the caller's) has Options.incidence_bf16 = 'rows' -- ops.knn_aggr's and ops.knn_dist's
@@ -643,10 +887,10 @@ class KnnHypergraph:
         dist = knn_dist(self.idx, X, transpose=(self.ptr_v, self.pos_v), options=options)
         return knn_incidence_weights(dist, self.mean, m_prob)
 
-    def aggregate(self, Z, probabilistic=False, m_prob=1.0, X=None, options=None):
+    def aggregate(self, Z, probabilistic=False, m_prob=1.0, X=None, options=None, first="sum", second="sum"):
         w = self.weights(m_prob, X, options) if probabilistic else None
         return knn_aggr(self.idx, Z, w, self.degE, self.degV, transpose=(self.ptr_v, self.pos_v), weight_grad=X is not None,
-                        options=options)
+                        options=options, first=first, second=second)
 
 
 def table_seq_max():

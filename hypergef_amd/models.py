@@ -161,13 +161,27 @@ class DynamicHypergraphConv(nn.Module):
     layer's own HGNNAggrIncidence call.  device_graph=True: the layer turns the same option on for its own ops.knn_aggr /
     ops.knn_dist calls (the table kernels' bfloat16 rows: the float32 layer's aggregate on Z.float(), rounded once), still
     waits nowhere, is still recorded into a hipGraph, and learn_distances=True works.  The weights stay float32 everywhere.
-    Under knn_form="difference" the search refuses bfloat16.  float32 layers are untouched."""
+    Under knn_form="difference" the search refuses bfloat16.  float32 layers are untouched.
+    first_aggr / second_aggr ('sum', 'mean', 'max', 'min'): the reduction over a hyperedge's members / over a vertex's
+    hyperedges, degE and degV still scaling the two hops -- UniSAGE's aggregators and EdgeConv's max on a hypergraph that is
+    rebuilt every forward.  device_graph=True: ops.knn_aggr(first=, second=) on the device table (the comparison kernels
+    hg_table_reduce_*; still nothing waits, still recorded into a hipGraph).  device_graph=False: ops.reduce_aggr on the
+    planned hypergraph.  Anything but the two sums is float32 only and takes no weights: probabilistic=True then raises
+    ValueError here.  The defaults are the layer above."""
 
     def __init__(self, in_channels, out_channels, k, probabilistic=False, segments=None, m_prob=1.0, options=None,
-                 device_graph=False, knn_form="difference", learn_distances=False):
+                 device_graph=False, knn_form="difference", learn_distances=False, first_aggr="sum", second_aggr="sum"):
         super().__init__()
         if not isinstance(k, int) or not 1 <= k <= 64:
             raise ValueError("k must be an integer in 1 .. 64, got %r" % (k,))
+        for name, r in (("first_aggr", first_aggr), ("second_aggr", second_aggr)):
+            if r not in ("sum", "mean", "max", "min"):
+                raise ValueError("%s must be 'sum', 'mean', 'max' or 'min', got %r" % (name, r))
+        self.first_aggr, self.second_aggr = first_aggr, second_aggr
+        self.sums = first_aggr == "sum" and second_aggr == "sum"
+        if probabilistic and not self.sums:
+            raise ValueError("probabilistic=True needs first_aggr = second_aggr = 'sum' (max, min and mean take no weights), "
+                             "got %r and %r" % (first_aggr, second_aggr))
         if learn_distances and not (probabilistic and device_graph):
             raise ValueError("learn_distances=True needs probabilistic=True (the distances only enter the weights) and "
                              "device_graph=True (ops.knn_dist and the weight gradient run over the device table)")
@@ -190,10 +204,15 @@ class DynamicHypergraphConv(nn.Module):
                 options = (options if options is not None else ops.current_options()).replace(incidence_bf16="rows")
             if self.learn_distances:
                 return hyperg.aggregate(Z, True, self.m_prob, X=X, options=options)
+            if not self.sums:
+                return hyperg.aggregate(Z, options=options, first=self.first_aggr, second=self.second_aggr)
             return hyperg.aggregate(Z, probabilistic=self.probabilistic, m_prob=self.m_prob, options=options)
         from .hypergraph import HyperGraph
         hyperg = self.hyperg = HyperGraph.from_knn(X.detach(), self.k, X.device, segments=self.segments, form=self.knn_form)
         Z = self.lin(X)
+        if not self.sums:
+            return ops.reduce_aggr(hyperg.H_T_csrptr, hyperg.H_T_colind, Z, self.first_aggr, self.second_aggr, hyperg.degE,
+                                   hyperg.degV, options=self.options)
         Wdiag = torch.ones(hyperg.num_edges, device=X.device)
         if self.probabilistic:
             w = hyperg.knn_weights(self.m_prob)

@@ -1049,6 +1049,51 @@ HG_API int hg_table_dot_bf16(const int32_t *idx, int32_t rows, int32_t k, int32_
                              const float *a_scale, const float *B, const uint16_t *C, const float *D, float *out,
                              hg_stream_t stream);
 
+/* Max and min over a neighbour table, with the winner recorded, and the gradient (csrc/hg_table_reduce.hip).  Like the
+ * entries above each launches once on `stream`, allocates and waits for nothing, takes no workspace, uses no atomics and can
+ * be recorded into a hipGraph.  float32 rows only; op = HG_REDUCE_MAX or HG_REDUCE_MIN.
+ *
+ * hg_table_reduce_f32 (a hyperedge's members): destination row i < rows takes the entries p = i k + s, s < k, with the
+ *   candidate (src[idx[p], c], p); src [n, F], dst and arg [rows, F].
+ * hg_table_reduce_t_f32 (a vertex's hyperedges): destination row v < n takes q = ptr_v[v] .. ptr_v[v + 1] - 1, p = pos_v[q],
+ *   with the candidate (src[p / k, c], p); src [rows, F], dst and arg [n, F].
+ *   THE ORDER: per column, a candidate replaces the best when its value is > (< for min) the best's, or equal to it at a
+ *   smaller position p.  That is a total order on (value, p) -- -0.0 ties +0.0 and the smaller position wins -- so the winner
+ *   does not depend on how a row is cut: every row length, every F, every alignment and every call give the same bits.  The
+ *   best starts as "none", not as a value: a row whose entries are all -inf under max has a winner, its first position.
+ *   An entry of idx outside 0 .. n - 1 (of pos_v outside 0 .. rows k - 1) is no candidate and is not read through.
+ *   dst[r, c] = dst_scale[r] * value (one multiplication; none where dst_scale is NULL; the value itself is src's bits) and
+ *   arg[r, c] = the winner's p, int32.  A row with no candidate -- a vertex with no entry, a row of ignored entries -- gets
+ *   exactly +0.0 and arg = -1 whatever its scale.  arg may be NULL: no position is stored.  NaN in src: unspecified.
+ *   Lanes are the table gathers' (4 columns a lane where F % 4 == 0 and src, dst and arg are 16-byte aligned, else 1).  A
+ *   vertex row longer than HG_TABLE_SEQ_MAX is read by its whole workgroup in interleaved batches and joined in registers
+ *   and one LDS slot per wave; being free of the order, it needs no fixed pieces.
+ * hg_table_select_f32 / hg_table_select_t_f32: the gradient of a reduce's src, all of it to the winner, as a row gather over
+ *   the OTHER walk -- no scatter.  gs is the reduce's incoming gradient times its scale (the caller multiplies), arg its arg:
+ *   select_t (the gradient of hg_table_reduce_f32; gs, arg [rows, F], dsrc [n, F]):
+ *     dsrc[v, c] = sum_{q = ptr_v[v] .. ptr_v[v + 1] - 1} (arg[i, c] == p ? gs[i, c] : nothing),  p = pos_v[q], i = p / k
+ *   select (the gradient of hg_table_reduce_t_f32; gs, arg [n, F], dsrc [rows, F]):
+ *     dsrc[i, c] = sum_{s < k} (arg[idx[i, s], c] == i k + s ? gs[idx[i, s], c] : nothing)
+ *   A select, not a product with 0 or 1: an entry that did not win adds nothing, whatever gs holds (inf, NaN).  A vertex that
+ *   one row names twice has two positions, of which the winner is one (the smaller, on a tie): its gradient arrives once.
+ *   SUMMATION ORDER: the ORDER paragraph of hg_table_gather_f32 / hg_table_gather_t_f32 word for word -- from +0.0, ascending
+ *   s / q, one rounded add a selected term; a vertex row longer than HG_TABLE_SEQ_MAX in P consecutive pieces and the tree
+ *   part[g] += part[g + s], with c = 4 where F % 4 == 0 and gs, arg and dsrc are 16-byte aligned, else 1.  dsrc is fully
+ *   overwritten; ignored entries as above.
+ * Refusals launch nothing, set hg_last_error, in the table gathers' order: HG_ERR_INVALID for a null idx (ptr_v, pos_v), a
+ *   null src or dst (gs, arg or dsrc); for rows, n or F < 1, k outside 1 .. 64, rows * k >= 2^31; for an op other than the
+ *   two; then HG_ERR_UNSUPPORTED for a pointer that is not 4-byte aligned.
+ * Not covered: bfloat16 rows, per-entry weights, heads.  Detect these entries by their exported symbols. */
+HG_API int hg_table_reduce_f32(const int32_t *idx, int32_t rows, int32_t k, int32_t n, int32_t F, int32_t op, const float *src,
+                               const float *dst_scale, float *dst, int32_t *arg /* may be NULL */, hg_stream_t stream);
+HG_API int hg_table_reduce_t_f32(const int32_t *ptr_v, const int32_t *pos_v, int32_t rows, int32_t k, int32_t n, int32_t F,
+                                 int32_t op, const float *src, const float *dst_scale, float *dst, int32_t *arg,
+                                 hg_stream_t stream);
+HG_API int hg_table_select_f32(const int32_t *idx, int32_t rows, int32_t k, int32_t n, int32_t F, const float *gs,
+                               const int32_t *arg, float *dsrc, hg_stream_t stream);
+HG_API int hg_table_select_t_f32(const int32_t *ptr_v, const int32_t *pos_v, int32_t rows, int32_t k, int32_t n, int32_t F,
+                                 const float *gs, const int32_t *arg, float *dsrc, hg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
