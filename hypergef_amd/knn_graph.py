@@ -12,6 +12,8 @@ hg_table_select_*: the comparison kernels and their exact gradient), and `knn_ag
 `knn_dist` (`ops.knn_dist`) gives a table's distances with a gradient, and `knn_aggr(weight_grad=True)` the gradient of its
 weights: together they train through the weights of a probabilistic kNN hypergraph.  Both take bfloat16 rows under
 Options.incidence_bf16 = 'rows' (hg_table_*_bf16): the float32 call on the widened rows, bit for bit, rounded once.
+`knn_softmax` (`ops.knn_softmax`; hg_table_softmax_*) turns scores into attention coefficients over the table, per hyperedge
+or per vertex, with exact gradients: its alpha is `knn_aggr`'s weight.
 """
 import ctypes
 import numbers
@@ -716,6 +718,150 @@ def knn_gather(idx, src, to="hyperedge", reduce="sum", scale=None, transpose=Non
     return table_gather_t(ptr_v, pos_v, k, src, None, None, scale)
 
 
+# ---- attention softmax over the table (hg_table_softmax_f32 / hg_table_softmax_bwd_f32 / hg_table_sum_f32) -------------------
+
+_GROUPS = {"hyperedge": _lib.HG_TABLE_HYPEREDGE, "vertex": _lib.HG_TABLE_VERTEX}
+
+
+def _softmax_entry(name):
+    """An hg_table_softmax_* / hg_table_sum_f32 entry of the library; a build without it is an error, never another path."""
+    L = _lib.lib()
+    if not hasattr(L, name):
+        raise RuntimeError("this build of libhgaggr has no %s (attention softmax over a neighbour table)" % name)
+    return getattr(L, name)
+
+
+def table_softmax(idx, n, group, node_score=None, edge_score=None, entry_score=None, slope=0.2, ptr_v=None, pos_v=None):
+    """alpha [rows, k] of hg_table_softmax_f32 over n vertices: the softmax over each hyperedge's members ('hyperedge') or each
+    vertex's positions ('vertex', through ptr_v / pos_v) of leaky_relu((own + other) + entry).  No checks, no gradient."""
+    rows, k = idx.shape
+    alpha = torch.empty((rows, k), dtype=torch.float32, device=idx.device)
+    with torch.cuda.device(idx.device):
+        _lib.check(_softmax_entry("hg_table_softmax_f32")(_ptr(idx), rows, k, n, _GROUPS[group], _ptr(node_score), _ptr(edge_score),
+                                                          _ptr(entry_score), slope, _ptr(ptr_v), _ptr(pos_v), _ptr(alpha),
+                                                          _stream_handle(idx.device)))
+    return alpha
+
+
+def table_softmax_bwd(idx, n, group, alpha, dalpha, node_score=None, edge_score=None, entry_score=None, slope=0.2, ptr_v=None,
+                      pos_v=None, want_group=True):
+    """(ds [rows, k], dgroup or None) of hg_table_softmax_bwd_f32: the gradient of every position's raw score and, per segment,
+    its own sum -- [rows] for 'hyperedge', [n] for 'vertex'."""
+    rows, k = idx.shape
+    ds = torch.empty((rows, k), dtype=torch.float32, device=idx.device)
+    dgroup = torch.empty(rows if group == "hyperedge" else n, dtype=torch.float32, device=idx.device) if want_group else None
+    with torch.cuda.device(idx.device):
+        _lib.check(_softmax_entry("hg_table_softmax_bwd_f32")(_ptr(idx), rows, k, n, _GROUPS[group], _ptr(node_score),
+                                                              _ptr(edge_score), _ptr(entry_score), slope, _ptr(ptr_v), _ptr(pos_v),
+                                                              _ptr(alpha), _ptr(dalpha), _ptr(ds), _ptr(dgroup),
+                                                              _stream_handle(idx.device)))
+    return ds, dgroup
+
+
+def table_sum(idx, n, side, val, ptr_v=None, pos_v=None):
+    """out[seg] = the sum of val [rows, k] over the segment's candidates (hg_table_sum_f32): [rows] for 'hyperedge', [n] for
+    'vertex' (through ptr_v / pos_v)."""
+    rows, k = idx.shape
+    out = torch.empty(rows if side == "hyperedge" else n, dtype=torch.float32, device=idx.device)
+    with torch.cuda.device(idx.device):
+        _lib.check(_softmax_entry("hg_table_sum_f32")(_ptr(idx), rows, k, n, _GROUPS[side], _ptr(ptr_v), _ptr(pos_v), _ptr(val),
+                                                      _ptr(out), _stream_handle(idx.device)))
+    return out
+
+
+class _KnnSoftmax(torch.autograd.Function):
+    """alpha over a fixed table.  Saves alpha, the scores given, the table and its transpose; the backward is one launch of the
+    backward kernel (ds and the own side's gradient) and, where the other end's score wants one, one segment sum over the
+    other side."""
+
+    @staticmethod
+    def forward(ctx, node_score, edge_score, entry_score, idx, ptr_v, pos_v, group, slope, n):
+        ctx.group, ctx.slope, ctx.n = group, slope, n
+        alpha = table_softmax(idx, n, group, node_score, edge_score, entry_score, slope, ptr_v, pos_v)
+        ctx.save_for_backward(alpha, node_score, edge_score, entry_score, idx, ptr_v, pos_v)
+        return alpha
+
+    @staticmethod
+    def backward(ctx, dalpha):
+        alpha, node_score, edge_score, entry_score, idx, ptr_v, pos_v = ctx.saved_tensors
+        hyperedge = ctx.group == "hyperedge"
+        own, other = (1, 0) if hyperedge else (0, 1)  # positions of the two scores among the inputs
+        ds, dgroup = table_softmax_bwd(idx, ctx.n, ctx.group, alpha, dalpha.contiguous(), node_score, edge_score, entry_score,
+                                       ctx.slope, ptr_v, pos_v, want_group=ctx.needs_input_grad[own])
+        grads = [None, None, None]
+        grads[own] = dgroup
+        if ctx.needs_input_grad[other]:
+            grads[other] = table_sum(idx, ctx.n, "vertex" if hyperedge else "hyperedge", ds, ptr_v, pos_v)
+        if ctx.needs_input_grad[2]:
+            grads[2] = ds.view(entry_score.shape)
+        return (*grads, None, None, None, None, None, None)
+
+
+def knn_softmax(idx, node_score=None, edge_score=None, group="hyperedge", negative_slope=0.2, entry_score=None, transpose=None,
+                num_nodes=None):
+    """Attention coefficients over a neighbour table idx [rows, k] (int32, ops.knn's), with no plan and no host step: alpha
+    float32 [rows, k], the softmax over each group of leaky_relu(raw, negative_slope) with
+        raw[i, s] = (own + other) + entry_score[i, s]
+    group='hyperedge': a group is a table row, own = edge_score[i], other = node_score[idx[i, s]].  group='vertex': a group is
+    the positions that name one vertex v (any number, through `transpose` = ops.knn_transpose(idx, n)), own = node_score[v],
+    other = edge_score[i].  node_score [n], edge_score [rows], entry_score [rows, k] or [rows * k], float32; any may be None
+    (no addition), not all.  n is node_score's length, else num_nodes, else rows.  ops.incidence_softmax's formula, operation
+    for operation (hg_table_softmax_f32); alpha keeps the table's layout whichever the group, so it is ops.knn_aggr's weight.
+    An entry of idx outside 0 .. n - 1 is no candidate: exactly +0.0, in alpha and in every gradient.
+    Differentiable in the three scores, exactly: one launch of hg_table_softmax_bwd_f32 (ds, the gradient of entry_score, and
+    its sum per group, the gradient of the group's own score) and one of hg_table_sum_f32 over the other side (the other
+    end's).  The transpose is computed where it is needed and not given: for group='vertex', and for a node_score gradient
+    under group='hyperedge'.  Deterministic: include/hg_aggr.h has the order of every sum, two calls give the same bits.
+    Nothing waits, nothing is read back.  float32 only: no heads, no dropout, no bfloat16 scores.
+    Refusals, in this order and before a device is touched: TypeError for an idx (ptr_v, pos_v) that is not int32 and a score
+    that is not float32 (bfloat16 too, whatever Options.incidence_bf16 says); ValueError for an unknown group, for the shapes
+    and k, for no score at all; RuntimeError for CPU tensors."""
+    _table_shape(idx)
+    scores = (("node_score", node_score), ("edge_score", edge_score), ("entry_score", entry_score))
+    for name, t in scores:
+        if t is not None:
+            _check_dtype(t, name, torch.float32, " (knn_softmax has no bfloat16, float16 or float64 form)")
+    _check_transpose_types(transpose)
+    if group not in _GROUPS:
+        raise ValueError("group must be 'hyperedge' or 'vertex', got %r" % (group,))
+    rows, k = _table_shape_values(idx)
+    if all(t is None for _, t in scores):
+        raise ValueError("knn_softmax needs at least one of node_score, edge_score and entry_score")
+    if node_score is not None:
+        if node_score.dim() != 1 or node_score.shape[0] < 1:
+            raise ValueError("node_score must be [n >= 1], got %s" % (tuple(node_score.shape),))
+        n = node_score.shape[0]
+        if num_nodes is not None and num_nodes != n:
+            raise ValueError("node_score has %d elements, num_nodes is %r" % (n, num_nodes))
+    else:
+        n = rows if num_nodes is None else num_nodes
+        if not isinstance(n, numbers.Integral) or isinstance(n, bool) or not 1 <= n < 2 ** 31 - 1:
+            raise ValueError("num_nodes must be a positive integer, got %r" % (num_nodes,))
+        n = int(n)
+    if edge_score is not None and tuple(edge_score.shape) != (rows,):
+        raise ValueError("edge_score must be [rows] = [%d], got %s" % (rows, tuple(edge_score.shape)))
+    if entry_score is not None and tuple(entry_score.shape) not in ((rows, k), (rows * k,)):
+        raise ValueError("entry_score must be [rows, k] = [%d, %d] or [rows * k] = [%d], got %s"
+                         % (rows, k, rows * k, tuple(entry_score.shape)))
+    _check_transpose_shapes(transpose, n, rows * k)
+    _check_table_index(idx, "idx")
+    for name, t in scores:
+        if t is not None:
+            _check_feat(t, name, device=idx.device)
+    grad = torch.is_grad_enabled()
+    ptr_v = pos_v = None
+    if group == "vertex" or (grad and node_score is not None and node_score.requires_grad):
+        if transpose is None:
+            transpose = knn_transpose(idx, n)
+        ptr_v, pos_v = transpose
+        _check_table_index(ptr_v, "ptr_v")
+        _check_table_index(pos_v, "pos_v")
+    slope = float(negative_slope)
+    if grad and any(t is not None and t.requires_grad for _, t in scores):
+        return _KnnSoftmax.apply(node_score, edge_score, entry_score, idx, ptr_v, pos_v, group, slope, n)
+    return table_softmax(idx, n, group, node_score, edge_score, entry_score, slope, ptr_v, pos_v)
+
+
 def _knn_aggr_reduced(idx, X, weight, degE, degV, transpose, first, second):
     """knn_aggr with a reduction other than the two sums: two knn_gather calls, degE the first hop's scale and degV the second's."""
     _table_shape(idx)
@@ -860,7 +1006,10 @@ class KnnHypergraph:
         stays detached: its gradient is an N x N sum and HGNN treats avg_dis as a constant of the construction.
       aggregate(Z, probabilistic=False, m_prob=1.0, X=None, first="sum", second="sum"): ops.knn_aggr over the table; X goes
         to weights, and the weights then get their gradient (weight_grad=True); first / second are ops.knn_aggr's reductions
-        (no weights with anything but the two sums).
+        (no weights with anything but the two sums).  weight=: explicit weights [N k] (or [N, k]) in place of the
+        probabilistic ones, passed with weight_grad=True -- attention's alpha; exclusive with probabilistic.
+      attention(node_score, edge_score, group="hyperedge", negative_slope=0.2): ops.knn_softmax over the table with the stored
+        transpose: alpha [N, k].
     form: ops.knn's -- "dot" gives the same idx and dist through the matrix-unit prefilter, and its own mean.  Under "dot" X
     may be bfloat16: the table, dist, mean, transpose and degrees are int32 / float32 as always, and aggregate / weights take
     bfloat16 Z / X where `options` (or the caller's) has Options.incidence_bf16 = 'rows' -- ops.knn_aggr's and ops.knn_dist's
@@ -887,10 +1036,19 @@ class KnnHypergraph:
         dist = knn_dist(self.idx, X, transpose=(self.ptr_v, self.pos_v), options=options)
         return knn_incidence_weights(dist, self.mean, m_prob)
 
-    def aggregate(self, Z, probabilistic=False, m_prob=1.0, X=None, options=None, first="sum", second="sum"):
+    def aggregate(self, Z, probabilistic=False, m_prob=1.0, X=None, options=None, weight=None, first="sum", second="sum"):
+        if weight is not None:
+            if probabilistic:
+                raise ValueError("weight and probabilistic=True exclude each other (both are the table's weights)")
+            return knn_aggr(self.idx, Z, weight, self.degE, self.degV, transpose=(self.ptr_v, self.pos_v), weight_grad=True,
+                            options=options, first=first, second=second)
         w = self.weights(m_prob, X, options) if probabilistic else None
         return knn_aggr(self.idx, Z, w, self.degE, self.degV, transpose=(self.ptr_v, self.pos_v), weight_grad=X is not None,
                         options=options, first=first, second=second)
+
+    def attention(self, node_score=None, edge_score=None, group="hyperedge", negative_slope=0.2):
+        return knn_softmax(self.idx, node_score, edge_score, group, negative_slope, transpose=(self.ptr_v, self.pos_v),
+                           num_nodes=self.num_nodes)
 
 
 def table_seq_max():

@@ -167,10 +167,20 @@ class DynamicHypergraphConv(nn.Module):
     rebuilt every forward.  device_graph=True: ops.knn_aggr(first=, second=) on the device table (the comparison kernels
     hg_table_reduce_*; still nothing waits, still recorded into a hipGraph).  device_graph=False: ops.reduce_aggr on the
     planned hypergraph.  Anything but the two sums is float32 only and takes no weights: probabilistic=True then raises
-    ValueError here.  The defaults are the layer above."""
+    ValueError here.  The defaults are the layer above.
+    attention='hyperedge' or 'vertex' (needs device_graph=True, both reductions 'sum' and probabilistic=False): the sums are
+    weighted by attention coefficients formed on the device table, HypergraphAttnConv's single-head additive layer without
+    bias on a hypergraph rebuilt every forward:
+        Z = lin(X),   sv = Z a_v,   se = ops.knn_gather(idx, (Z a_e)[:, None], 'hyperedge', 'mean'),
+        alpha = ops.knn_softmax(idx, sv, se, group=attention, negative_slope),   Y = ops.knn_aggr(idx, Z, alpha, degE, degV),
+    with alpha's gradient from ops.knn_aggr(weight_grad=True) and the scores' from ops.knn_softmax.  Two more parameters,
+    a_v and a_e [out_channels], initialised as HypergraphAttnConv's; they exist only where attention is set.  With
+    segments=None the layer still waits nowhere and is recorded into a hipGraph.  float32 only: a bfloat16 input raises
+    TypeError.  No heads, no dropout.  None (the default) is the layer above: same bits, same parameters."""
 
     def __init__(self, in_channels, out_channels, k, probabilistic=False, segments=None, m_prob=1.0, options=None,
-                 device_graph=False, knn_form="difference", learn_distances=False, first_aggr="sum", second_aggr="sum"):
+                 device_graph=False, knn_form="difference", learn_distances=False, first_aggr="sum", second_aggr="sum",
+                 attention=None, negative_slope=0.2):
         super().__init__()
         if not isinstance(k, int) or not 1 <= k <= 64:
             raise ValueError("k must be an integer in 1 .. 64, got %r" % (k,))
@@ -193,8 +203,37 @@ class DynamicHypergraphConv(nn.Module):
         self.device_graph = bool(device_graph)
         self.knn_form = knn_form
         self.hyperg = None
+        if attention not in (None, "hyperedge", "vertex"):
+            raise ValueError("attention must be None, 'hyperedge' or 'vertex', got %r" % (attention,))
+        self.attention, self.negative_slope = attention, float(negative_slope)
+        if attention is not None:
+            if not device_graph:
+                raise ValueError("attention=%r needs device_graph=True (ops.knn_softmax runs over the device table; on a "
+                                 "planned hypergraph use HypergraphAttnConv)" % (attention,))
+            if not self.sums:
+                raise ValueError("attention=%r needs first_aggr = second_aggr = 'sum' (the coefficients weight the sums), got %r "
+                                 "and %r" % (attention, first_aggr, second_aggr))
+            if probabilistic:
+                raise ValueError("attention=%r needs probabilistic=False (the coefficients are the table's weights)" % (attention,))
+            bound = math.sqrt(6.0 / (out_channels + 1))
+            self.a_v = nn.Parameter(torch.empty(out_channels).uniform_(-bound, bound))
+            self.a_e = nn.Parameter(torch.empty(out_channels).uniform_(-bound, bound))
+
+    def _attention_forward(self, X):
+        from .knn_graph import KnnHypergraph, knn_gather
+        if X.dtype != torch.float32:
+            raise TypeError("attention=%r takes float32 rows (ops.knn_softmax has no bfloat16 form), got %s" % (self.attention, X.dtype))
+        hyperg = self.hyperg = KnnHypergraph.build(X, self.k, segments=self.segments, form=self.knn_form)
+        Z = self.lin(X)
+        transpose = (hyperg.ptr_v, hyperg.pos_v)
+        sv = Z @ self.a_v
+        se = knn_gather(hyperg.idx, (Z @ self.a_e)[:, None].contiguous(), "hyperedge", "mean", transpose=transpose).reshape(-1)
+        alpha = hyperg.attention(sv, se, self.attention, self.negative_slope)
+        return hyperg.aggregate(Z, options=self.options, weight=alpha)
 
     def forward(self, X):
+        if self.attention is not None:
+            return self._attention_forward(X)
         if self.device_graph:
             from .knn_graph import KnnHypergraph
             hyperg = self.hyperg = KnnHypergraph.build(X, self.k, segments=self.segments, form=self.knn_form)

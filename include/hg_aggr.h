@@ -1094,6 +1094,50 @@ HG_API int hg_table_select_f32(const int32_t *idx, int32_t rows, int32_t k, int3
 HG_API int hg_table_select_t_f32(const int32_t *ptr_v, const int32_t *pos_v, int32_t rows, int32_t k, int32_t n, int32_t F,
                                  const float *gs, const int32_t *arg, float *dsrc, hg_stream_t stream);
 
+/* Attention softmax over a neighbour table, its backward and the segment sum (csrc/hg_table_softmax.hip): the coefficients
+ * of hg_incidence_attention_f32 for the hypergraph of a table, with no plan.  Like the entries above each launches once on
+ * `stream`, allocates and waits for nothing, takes no workspace, uses no atomics and can be recorded into a hipGraph.
+ * float32 only.  group / side: HG_TABLE_HYPEREDGE -- segment i < rows is the table row, the positions p = i k + s, s < k, own
+ * score edge_score[i], other end's score node_score[idx[p]]; HG_TABLE_VERTEX -- segment v < n is pos_v[ptr_v[v] ..
+ * ptr_v[v + 1]) of hg_table_transpose, own score node_score[v], other end's score edge_score[p / k].  Whichever the group,
+ * alpha, dalpha, ds and entry_score are [rows, k] in the table's own layout.  An entry of idx outside 0 .. n - 1 (of pos_v
+ * outside 0 .. rows k - 1) is no candidate: it enters no maximum and no sum, is not read through, and its alpha and ds are
+ * exactly +0.0; a segment with no candidate writes only +0.0.  ptr_v / pos_v are read on the vertex side only.
+ *
+ * hg_table_softmax_f32: raw[p] = (own + other) + entry_score[p], the segment's own score first, an absent (NULL) score no
+ *   addition; x = raw > 0 ? raw : slope * raw; alpha[p] = __expf(x - max_seg x) * (1 / sum_seg __expf(x - max_seg x)) --
+ *   hg_incidence_attention_f32's formula, operation for operation.  At least one score must be given.
+ * hg_table_softmax_bwd_f32: ds[p] = (alpha[p] * (dalpha[p] - sum_seg alpha * dalpha)) * (raw[p] > 0 ? 1 : slope), the gradient
+ *   of raw[p], so of entry_score[p]; dgroup (may be NULL; [rows] / [n]) receives the segment's own sum of ds, the gradient of
+ *   the segment's own score.
+ * hg_table_sum_f32: out[seg] = sum over the segment's candidates of val[p]; out is [rows] / [n].  On the ds of a call of the
+ *   OTHER group it is the gradient of the other end's score: side VERTEX gives d node_score of a hyperedge-group softmax,
+ *   side HYPEREDGE d edge_score of a vertex-group one.
+ *   SEGMENT ORDER: every sum starts from +0.0 and adds rounded terms with rounded adds (no fma); the maximum is free of the
+ *   order.  A lane group of L lanes owns a segment: L = the power of two at or above k (HYPEREDGE), max(8, that power)
+ *   (VERTEX).  A segment of at most HG_TABLE_SEQ_MAX entries (every HYPEREDGE one): lane l adds its entries q = l, l + L,
+ *   l + 2 L .. of the segment in ascending q (a non-candidate keeps its place and adds nothing), then t[l] = t[l] + t[l xor o]
+ *   for o = L / 2, L / 4 .. 1, every lane at once.  A longer VERTEX segment is taken by its workgroup of 256 threads: thread t
+ *   adds q = t, t + 256 .. in ascending q, then t = t + t[xor o] for o = 32 .. 1 within each wave of 64, then the four
+ *   waves' values are added as ((w0 + w1) + w2) + w3.  So the bits of a segment depend on its entries, its length and k
+ *   alone, and two calls give the same bits.
+ * Refusals launch nothing, set hg_last_error, in the table entries' order: HG_ERR_INVALID for a null idx, a null alpha
+ *   (dalpha, ds; val, out) or no score at all, null ptr_v or pos_v under HG_TABLE_VERTEX; for rows or n < 1, k outside
+ *   1 .. 64, rows * k >= 2^31; for a group / side other than the two; then HG_ERR_UNSUPPORTED for a pointer that is not
+ *   4-byte aligned.
+ * Not covered: heads, dropout, bfloat16 scores.  Detect these entries by their exported symbols. */
+#define HG_TABLE_HYPEREDGE 0
+#define HG_TABLE_VERTEX 1
+HG_API int hg_table_softmax_f32(const int32_t *idx, int32_t rows, int32_t k, int32_t n, int32_t group, const float *node_score,
+                                const float *edge_score, const float *entry_score, float slope, const int32_t *ptr_v,
+                                const int32_t *pos_v, float *alpha, hg_stream_t stream);
+HG_API int hg_table_softmax_bwd_f32(const int32_t *idx, int32_t rows, int32_t k, int32_t n, int32_t group,
+                                    const float *node_score, const float *edge_score, const float *entry_score, float slope,
+                                    const int32_t *ptr_v, const int32_t *pos_v, const float *alpha, const float *dalpha,
+                                    float *ds, float *dgroup /* may be NULL */, hg_stream_t stream);
+HG_API int hg_table_sum_f32(const int32_t *idx, int32_t rows, int32_t k, int32_t n, int32_t side, const int32_t *ptr_v,
+                            const int32_t *pos_v, const float *val, float *out, hg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
