@@ -59,6 +59,8 @@ SYMBOLS = (
     "hg_table_gather_bf16", "hg_table_gather_t_bf16", "hg_table_dist_bf16", "hg_table_dot_bf16",
     "hg_table_reduce_f32", "hg_table_reduce_t_f32", "hg_table_select_f32", "hg_table_select_t_f32",
     "hg_table_softmax_f32", "hg_table_softmax_bwd_f32", "hg_table_sum_f32",
+    "hg_table_softmax_heads_f32", "hg_table_softmax_bwd_heads_f32", "hg_table_sum_heads_f32",
+    "hg_table_gather_heads_f32", "hg_table_gather_t_heads_f32", "hg_table_dot_heads_f32",
 )
 HG_TABLE_HYPEREDGE = 0
 HG_TABLE_VERTEX = 1
@@ -363,6 +365,20 @@ def lib():
         L.hg_table_softmax_bwd_f32.argtypes = [vp, i32, i32, i32, i32, vp, vp, vp, ctypes.c_float, vp, vp, vp, vp, vp, vp, vp]
         L.hg_table_sum_f32.restype = ctypes.c_int
         L.hg_table_sum_f32.argtypes = [vp, i32, i32, i32, i32, vp, vp, vp, vp, vp]
+    if hasattr(L, "hg_table_softmax_heads_f32"):  # likewise: several heads over the table (+ an int32 heads after n / F)
+        L.hg_table_softmax_heads_f32.restype = ctypes.c_int
+        L.hg_table_softmax_heads_f32.argtypes = [vp, i32, i32, i32, i32, i32, vp, vp, vp, ctypes.c_float, vp, vp, vp, vp]
+        L.hg_table_softmax_bwd_heads_f32.restype = ctypes.c_int
+        L.hg_table_softmax_bwd_heads_f32.argtypes = [vp, i32, i32, i32, i32, i32, vp, vp, vp, ctypes.c_float, vp, vp, vp, vp, vp,
+                                                     vp, vp]
+        L.hg_table_sum_heads_f32.restype = ctypes.c_int
+        L.hg_table_sum_heads_f32.argtypes = [vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp]
+        L.hg_table_gather_heads_f32.restype = ctypes.c_int
+        L.hg_table_gather_heads_f32.argtypes = [vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp]
+        L.hg_table_gather_t_heads_f32.restype = ctypes.c_int
+        L.hg_table_gather_t_heads_f32.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp]
+        L.hg_table_dot_heads_f32.restype = ctypes.c_int
+        L.hg_table_dot_heads_f32.argtypes = [vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp]
     L.hg_aggr_push_groups_f32.restype = ctypes.c_int
     L.hg_aggr_push_groups_f32.argtypes = [i32, i32, i32, i64, vp, vp, vp, vp, vp, vp,
                                           vp, vp, vp, vp, vp, vp]

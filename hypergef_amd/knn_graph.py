@@ -13,7 +13,9 @@ hg_table_select_*: the comparison kernels and their exact gradient), and `knn_ag
 weights: together they train through the weights of a probabilistic kNN hypergraph.  Both take bfloat16 rows under
 Options.incidence_bf16 = 'rows' (hg_table_*_bf16): the float32 call on the widened rows, bit for bit, rounded once.
 `knn_softmax` (`ops.knn_softmax`; hg_table_softmax_*) turns scores into attention coefficients over the table, per hyperedge
-or per vertex, with exact gradients: its alpha is `knn_aggr`'s weight.
+or per vertex, with exact gradients: its alpha is `knn_aggr`'s weight.  Several heads (hg_table_*_heads_f32): `knn_softmax(heads=H)` takes
+scores with the head as their last dimension, and `knn_aggr` a weight [rows, k, H]; every head in the same launch and with the
+single-head call's bits.
 """
 import ctypes
 import numbers
@@ -283,10 +285,35 @@ def _bf16_entry(name):
     return getattr(L, name)
 
 
+def _heads_entry(name):
+    """An hg_table_*_heads_f32 entry of the library; a build without it is an error, never another path."""
+    L = _lib.lib()
+    if not hasattr(L, name):
+        raise RuntimeError("this build of libhgaggr has no %s (several heads over a neighbour table)" % name)
+    return getattr(L, name)
+
+
+def _heads_value(heads):
+    """heads as the kernels take it: an integer >= 1 (ValueError)."""
+    if isinstance(heads, bool) or not isinstance(heads, numbers.Integral) or heads < 1:
+        raise ValueError("heads must be an integer >= 1, got %r" % (heads,))
+    return int(heads)
+
+
 def _whole_lanes(F, *rows):
     """Whether the hg_table_*_bf16 entries take these row arrays (None: absent): F % 8 == 0 and 16-byte aligned rows
     (include/hg_aggr.h).  Otherwise the caller widens, runs the float32 entry and rounds once: the same bits, torch ops only."""
     return F % 8 == 0 and all(t is None or t.data_ptr() % 16 == 0 for t in rows)
+
+
+def _heads_rows(F, heads, w, io, ctr):
+    """What the several-heads gathers refuse beyond the plain ones' refusals."""
+    if io or ctr is not None:
+        raise TypeError("heads=%d takes float32 rows and no ctr (hg_table_gather_heads_f32 has no bfloat16 or difference form)" % heads)
+    if w is None:
+        raise ValueError("heads=%d needs w [rows * k, heads] (without weights the heads are the plain gather)" % heads)
+    if F % heads:
+        raise ValueError("F = %d is no multiple of heads = %d" % (F, heads))
 
 
 def _gather_io(src, ctr, dst_dtype):
@@ -310,14 +337,16 @@ def _widened(t):
     return t.float() if t is not None and t.dtype == BF16 else t
 
 
-def table_gather(idx, src, w=None, src_scale=None, dst_scale=None, ctr=None, dst_dtype=None):
+def table_gather(idx, src, w=None, src_scale=None, dst_scale=None, ctr=None, dst_dtype=None, heads=1):
     """dst[i] = dst_scale[i] * sum_s (src[idx[i, s]] * src_scale[idx[i, s]]) * w[i * k + s] over a table idx [rows, k] and rows
     src [n, F]: hg_table_gather_f32, every row summed in ascending s.  Any of w [rows * k], src_scale [n], dst_scale [rows]
     may be None (no multiplication).  An entry outside 0 .. n - 1 adds nothing.  No gradient.
     ctr [rows, F]: the difference gather hg_table_gather_diff_f32 -- the term starts from ctr[i] - src[idx[i, s]].
     bfloat16 rows (hg_table_gather_bf16): a bfloat16 src (ctr bfloat16 too) gives the float32 result of the call on
     src.float(); dst_dtype=torch.bfloat16 rounds a float32 src's result once (no ctr).  Bit for bit; w and the scales stay
-    float32."""
+    float32.
+    heads = H > 1 (hg_table_gather_heads_f32): w [rows * k, H] (never None) and column c is weighted by w[p, c // (F // H)];
+    float32 rows only, no ctr."""
     _table_shape(idx)
     rows, k = _table_shape_values(idx)
     _check_table_index(idx, "idx")
@@ -326,12 +355,18 @@ def table_gather(idx, src, w=None, src_scale=None, dst_scale=None, ctr=None, dst
         raise ValueError("src must be [n >= 1, F >= 1], got %s" % (tuple(src.shape),))
     n, F = src.shape
     dev = idx.device
-    w = _flat_or_none(w, "w", rows * k, dev)
+    w = _flat_or_none(w, "w", rows * k * heads, dev)
     src_scale = _flat_or_none(src_scale, "src_scale", n, dev)
     dst_scale = _flat_or_none(dst_scale, "dst_scale", rows, dev)
     ctr = _flat_or_none(ctr, "ctr", rows * F, dev, bf16_ok=True)
     io, out_dtype = _gather_io(src, ctr, dst_dtype)
     dst = torch.empty((rows, F), dtype=out_dtype, device=dev)
+    if heads > 1:
+        _heads_rows(F, heads, w, io, ctr)
+        with torch.cuda.device(dev):
+            _lib.check(_heads_entry("hg_table_gather_heads_f32")(_ptr(idx), rows, k, n, F, heads, _ptr(src), _ptr(w), _ptr(src_scale),
+                                                                 _ptr(dst_scale), _ptr(dst), _stream_handle(dev)))
+        return dst
     if io and not _whole_lanes(F, src, ctr, dst):
         return table_gather(idx, _widened(src), w, src_scale, dst_scale, _widened(ctr)).to(out_dtype)
     L = _lib.lib()
@@ -347,13 +382,14 @@ def table_gather(idx, src, w=None, src_scale=None, dst_scale=None, ctr=None, dst
     return dst
 
 
-def table_gather_t(ptr_v, pos_v, k, src, w=None, src_scale=None, dst_scale=None, ctr=None, dst_dtype=None):
+def table_gather_t(ptr_v, pos_v, k, src, w=None, src_scale=None, dst_scale=None, ctr=None, dst_dtype=None, heads=1):
     """dst[v] = dst_scale[v] * sum_q (src[pos_v[q] // k] * src_scale[pos_v[q] // k]) * w[pos_v[q]], q over ptr_v[v] ..
     ptr_v[v + 1] - 1, for the transpose (ptr_v [n + 1], pos_v [rows * k]) of a table of k columns and rows src [rows, F]:
     hg_table_gather_t_f32.  A row of at most TABLE_SEQ_MAX entries is summed in ascending q; a longer one by its whole
     workgroup in an order fixed by its length and F.  A vertex with no entry is +0.0 whatever dst_scale.  No gradient.
     ctr [n, F]: the difference gather hg_table_gather_t_diff_f32 -- the term starts from ctr[v] - src[pos_v[q] // k].
-    bfloat16 rows (hg_table_gather_t_bf16): as table_gather; a long row keeps the float32 call's order, so its bits too."""
+    bfloat16 rows (hg_table_gather_t_bf16): as table_gather; a long row keeps the float32 call's order, so its bits too.
+    heads = H > 1 (hg_table_gather_t_heads_f32): as table_gather; a long row keeps the plain call's order at the same F."""
     _check_dtype(ptr_v, "ptr_v", torch.int32)
     _check_dtype(pos_v, "pos_v", torch.int32)
     if not isinstance(k, numbers.Integral) or isinstance(k, bool) or not 1 <= k <= K_MAX:
@@ -368,12 +404,19 @@ def table_gather_t(ptr_v, pos_v, k, src, w=None, src_scale=None, dst_scale=None,
         raise ValueError("src must be [rows, F >= 1] with rows * k = %d positions, got %s" % (pos_v.shape[0], tuple(src.shape)))
     rows, F = src.shape
     n = ptr_v.shape[0] - 1
-    w = _flat_or_none(w, "w", rows * int(k), dev)
+    w = _flat_or_none(w, "w", rows * int(k) * heads, dev)
     src_scale = _flat_or_none(src_scale, "src_scale", rows, dev)
     dst_scale = _flat_or_none(dst_scale, "dst_scale", n, dev)
     ctr = _flat_or_none(ctr, "ctr", n * F, dev, bf16_ok=True)
     io, out_dtype = _gather_io(src, ctr, dst_dtype)
     dst = torch.empty((n, F), dtype=out_dtype, device=dev)
+    if heads > 1:
+        _heads_rows(F, heads, w, io, ctr)
+        with torch.cuda.device(dev):
+            _lib.check(_heads_entry("hg_table_gather_t_heads_f32")(_ptr(ptr_v), _ptr(pos_v), rows, int(k), n, F, heads, _ptr(src),
+                                                                   _ptr(w), _ptr(src_scale), _ptr(dst_scale), _ptr(dst),
+                                                                   _stream_handle(dev)))
+        return dst
     if io and not _whole_lanes(F, src, ctr, dst):
         return table_gather_t(ptr_v, pos_v, k, _widened(src), w, src_scale, dst_scale, _widened(ctr)).to(out_dtype)
     L = _lib.lib()
@@ -389,12 +432,13 @@ def table_gather_t(ptr_v, pos_v, k, src, w=None, src_scale=None, dst_scale=None,
     return dst
 
 
-def table_dot(idx, A, B, a_scale=None, C=None, D=None):
+def table_dot(idx, A, B, a_scale=None, C=None, D=None, heads=1):
     """out[i * k + s] = a_scale[j] * <A[j], B[i]> + <C[j], D[i]>, j = idx[i, s], over a table idx [rows, k]: hg_table_dot_f32,
     one launch and no [rows * k, F] array.  A, C [n, F]; B, D [rows, F]; a_scale [n] or None; C and D both or neither.  An
     entry outside 0 .. n - 1 gives +0.0.  The order of the sum is include/hg_aggr.h's DOT ORDER.  No gradient.
     A (and C with it) may be bfloat16 (hg_table_dot_bf16): out is the float32 call's on A.float() / C.float(), bit for bit;
-    B, D and a_scale stay float32."""
+    B, D and a_scale stay float32.
+    heads = H > 1 (hg_table_dot_heads_f32): out [rows * k, H], out[p, h] the call on head h's F // H columns; float32 only."""
     _table_shape(idx)
     rows, k = _table_shape_values(idx)
     _check_table_index(idx, "idx")
@@ -413,6 +457,16 @@ def table_dot(idx, A, B, a_scale=None, C=None, D=None):
             if tuple(t.shape) != shape:
                 raise ValueError("%s must be [%d, %d], got %s" % (name, shape[0], shape[1], tuple(t.shape)))
     a_scale = _flat_or_none(a_scale, "a_scale", n, dev)
+    if heads > 1:
+        if A.dtype == BF16:
+            raise TypeError("heads=%d takes float32 rows (hg_table_dot_heads_f32 has no bfloat16 form)" % heads)
+        if F % heads:
+            raise ValueError("F = %d is no multiple of heads = %d" % (F, heads))
+        out = torch.empty((rows * k, heads), dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            _lib.check(_heads_entry("hg_table_dot_heads_f32")(_ptr(idx), rows, k, n, F, heads, _ptr(A), _ptr(a_scale), _ptr(B), _ptr(C),
+                                                              _ptr(D), _ptr(out), _stream_handle(dev)))
+        return out
     if A.dtype == BF16 and not _whole_lanes(F, A, B, C, D):
         return table_dot(idx, A.float(), B, a_scale, _widened(C), D)
     entry = _bf16_entry("hg_table_dot_bf16") if A.dtype == BF16 else _lib.lib().hg_table_dot_f32
@@ -731,10 +785,18 @@ def _softmax_entry(name):
     return getattr(L, name)
 
 
-def table_softmax(idx, n, group, node_score=None, edge_score=None, entry_score=None, slope=0.2, ptr_v=None, pos_v=None):
+def table_softmax(idx, n, group, node_score=None, edge_score=None, entry_score=None, slope=0.2, ptr_v=None, pos_v=None, heads=1):
     """alpha [rows, k] of hg_table_softmax_f32 over n vertices: the softmax over each hyperedge's members ('hyperedge') or each
-    vertex's positions ('vertex', through ptr_v / pos_v) of leaky_relu((own + other) + entry).  No checks, no gradient."""
+    vertex's positions ('vertex', through ptr_v / pos_v) of leaky_relu((own + other) + entry).  No checks, no gradient.
+    heads = H > 1: alpha [rows, k, H] of hg_table_softmax_heads_f32 on scores with the head as their last dimension."""
     rows, k = idx.shape
+    if heads > 1:
+        alpha = torch.empty((rows, k, heads), dtype=torch.float32, device=idx.device)
+        with torch.cuda.device(idx.device):
+            _lib.check(_heads_entry("hg_table_softmax_heads_f32")(_ptr(idx), rows, k, n, heads, _GROUPS[group], _ptr(node_score),
+                                                                  _ptr(edge_score), _ptr(entry_score), slope, _ptr(ptr_v),
+                                                                  _ptr(pos_v), _ptr(alpha), _stream_handle(idx.device)))
+        return alpha
     alpha = torch.empty((rows, k), dtype=torch.float32, device=idx.device)
     with torch.cuda.device(idx.device):
         _lib.check(_softmax_entry("hg_table_softmax_f32")(_ptr(idx), rows, k, n, _GROUPS[group], _ptr(node_score), _ptr(edge_score),
@@ -744,10 +806,21 @@ def table_softmax(idx, n, group, node_score=None, edge_score=None, entry_score=N
 
 
 def table_softmax_bwd(idx, n, group, alpha, dalpha, node_score=None, edge_score=None, entry_score=None, slope=0.2, ptr_v=None,
-                      pos_v=None, want_group=True):
+                      pos_v=None, want_group=True, heads=1):
     """(ds [rows, k], dgroup or None) of hg_table_softmax_bwd_f32: the gradient of every position's raw score and, per segment,
-    its own sum -- [rows] for 'hyperedge', [n] for 'vertex'."""
+    its own sum -- [rows] for 'hyperedge', [n] for 'vertex'.  heads = H > 1: hg_table_softmax_bwd_heads_f32, one more dimension
+    H at the end of each."""
     rows, k = idx.shape
+    if heads > 1:
+        ds = torch.empty((rows, k, heads), dtype=torch.float32, device=idx.device)
+        nseg = rows if group == "hyperedge" else n
+        dgroup = torch.empty((nseg, heads), dtype=torch.float32, device=idx.device) if want_group else None
+        with torch.cuda.device(idx.device):
+            _lib.check(_heads_entry("hg_table_softmax_bwd_heads_f32")(_ptr(idx), rows, k, n, heads, _GROUPS[group], _ptr(node_score),
+                                                                      _ptr(edge_score), _ptr(entry_score), slope, _ptr(ptr_v),
+                                                                      _ptr(pos_v), _ptr(alpha), _ptr(dalpha), _ptr(ds),
+                                                                      _ptr(dgroup), _stream_handle(idx.device)))
+        return ds, dgroup
     ds = torch.empty((rows, k), dtype=torch.float32, device=idx.device)
     dgroup = torch.empty(rows if group == "hyperedge" else n, dtype=torch.float32, device=idx.device) if want_group else None
     with torch.cuda.device(idx.device):
@@ -758,10 +831,16 @@ def table_softmax_bwd(idx, n, group, alpha, dalpha, node_score=None, edge_score=
     return ds, dgroup
 
 
-def table_sum(idx, n, side, val, ptr_v=None, pos_v=None):
+def table_sum(idx, n, side, val, ptr_v=None, pos_v=None, heads=1):
     """out[seg] = the sum of val [rows, k] over the segment's candidates (hg_table_sum_f32): [rows] for 'hyperedge', [n] for
-    'vertex' (through ptr_v / pos_v)."""
+    'vertex' (through ptr_v / pos_v).  heads = H > 1: val [rows, k, H], out [segments, H] (hg_table_sum_heads_f32)."""
     rows, k = idx.shape
+    if heads > 1:
+        out = torch.empty((rows if side == "hyperedge" else n, heads), dtype=torch.float32, device=idx.device)
+        with torch.cuda.device(idx.device):
+            _lib.check(_heads_entry("hg_table_sum_heads_f32")(_ptr(idx), rows, k, n, heads, _GROUPS[side], _ptr(ptr_v), _ptr(pos_v),
+                                                              _ptr(val), _ptr(out), _stream_handle(idx.device)))
+        return out
     out = torch.empty(rows if side == "hyperedge" else n, dtype=torch.float32, device=idx.device)
     with torch.cuda.device(idx.device):
         _lib.check(_softmax_entry("hg_table_sum_f32")(_ptr(idx), rows, k, n, _GROUPS[side], _ptr(ptr_v), _ptr(pos_v), _ptr(val),
@@ -772,12 +851,12 @@ def table_sum(idx, n, side, val, ptr_v=None, pos_v=None):
 class _KnnSoftmax(torch.autograd.Function):
     """alpha over a fixed table.  Saves alpha, the scores given, the table and its transpose; the backward is one launch of the
     backward kernel (ds and the own side's gradient) and, where the other end's score wants one, one segment sum over the
-    other side."""
+    other side.  heads = H > 1: the same launches on the several-heads entries."""
 
     @staticmethod
-    def forward(ctx, node_score, edge_score, entry_score, idx, ptr_v, pos_v, group, slope, n):
-        ctx.group, ctx.slope, ctx.n = group, slope, n
-        alpha = table_softmax(idx, n, group, node_score, edge_score, entry_score, slope, ptr_v, pos_v)
+    def forward(ctx, node_score, edge_score, entry_score, idx, ptr_v, pos_v, group, slope, n, heads=1):
+        ctx.group, ctx.slope, ctx.n, ctx.heads = group, slope, n, heads
+        alpha = table_softmax(idx, n, group, node_score, edge_score, entry_score, slope, ptr_v, pos_v, heads)
         ctx.save_for_backward(alpha, node_score, edge_score, entry_score, idx, ptr_v, pos_v)
         return alpha
 
@@ -787,18 +866,18 @@ class _KnnSoftmax(torch.autograd.Function):
         hyperedge = ctx.group == "hyperedge"
         own, other = (1, 0) if hyperedge else (0, 1)  # positions of the two scores among the inputs
         ds, dgroup = table_softmax_bwd(idx, ctx.n, ctx.group, alpha, dalpha.contiguous(), node_score, edge_score, entry_score,
-                                       ctx.slope, ptr_v, pos_v, want_group=ctx.needs_input_grad[own])
+                                       ctx.slope, ptr_v, pos_v, want_group=ctx.needs_input_grad[own], heads=ctx.heads)
         grads = [None, None, None]
         grads[own] = dgroup
         if ctx.needs_input_grad[other]:
-            grads[other] = table_sum(idx, ctx.n, "vertex" if hyperedge else "hyperedge", ds, ptr_v, pos_v)
+            grads[other] = table_sum(idx, ctx.n, "vertex" if hyperedge else "hyperedge", ds, ptr_v, pos_v, ctx.heads)
         if ctx.needs_input_grad[2]:
             grads[2] = ds.view(entry_score.shape)
-        return (*grads, None, None, None, None, None, None)
+        return (*grads, None, None, None, None, None, None, None)
 
 
 def knn_softmax(idx, node_score=None, edge_score=None, group="hyperedge", negative_slope=0.2, entry_score=None, transpose=None,
-                num_nodes=None):
+                num_nodes=None, heads=1):
     """Attention coefficients over a neighbour table idx [rows, k] (int32, ops.knn's), with no plan and no host step: alpha
     float32 [rows, k], the softmax over each group of leaky_relu(raw, negative_slope) with
         raw[i, s] = (own + other) + entry_score[i, s]
@@ -812,10 +891,14 @@ def knn_softmax(idx, node_score=None, edge_score=None, group="hyperedge", negati
     its sum per group, the gradient of the group's own score) and one of hg_table_sum_f32 over the other side (the other
     end's).  The transpose is computed where it is needed and not given: for group='vertex', and for a node_score gradient
     under group='hyperedge'.  Deterministic: include/hg_aggr.h has the order of every sum, two calls give the same bits.
-    Nothing waits, nothing is read back.  float32 only: no heads, no dropout, no bfloat16 scores.
+    Nothing waits, nothing is read back.  float32 only: no dropout, no bfloat16 scores.
+    heads = H > 1: ops.incidence_softmax's layout on the table -- node_score [n, H], edge_score [rows, H], entry_score
+    [rows, k, H] or [rows * k, H], alpha [rows, k, H] -- every head in the same launch (hg_table_softmax_heads_f32; the
+    gradients through hg_table_softmax_bwd_heads_f32 and hg_table_sum_heads_f32, one launch each as above).  alpha[..., h]
+    and every gradient's column h are, bit for bit, the single-head call's on column h.  heads = 1 is the call above.
     Refusals, in this order and before a device is touched: TypeError for an idx (ptr_v, pos_v) that is not int32 and a score
-    that is not float32 (bfloat16 too, whatever Options.incidence_bf16 says); ValueError for an unknown group, for the shapes
-    and k, for no score at all; RuntimeError for CPU tensors."""
+    that is not float32 (bfloat16 too, whatever Options.incidence_bf16 says); ValueError for an unknown group, for heads, for
+    the shapes and k, for no score at all; RuntimeError for CPU tensors."""
     _table_shape(idx)
     scores = (("node_score", node_score), ("edge_score", edge_score), ("entry_score", entry_score))
     for name, t in scores:
@@ -824,12 +907,15 @@ def knn_softmax(idx, node_score=None, edge_score=None, group="hyperedge", negati
     _check_transpose_types(transpose)
     if group not in _GROUPS:
         raise ValueError("group must be 'hyperedge' or 'vertex', got %r" % (group,))
+    H = _heads_value(heads)
+    tail = (H,) if H > 1 else ()  # the head is the last dimension of every score
     rows, k = _table_shape_values(idx)
     if all(t is None for _, t in scores):
         raise ValueError("knn_softmax needs at least one of node_score, edge_score and entry_score")
     if node_score is not None:
-        if node_score.dim() != 1 or node_score.shape[0] < 1:
-            raise ValueError("node_score must be [n >= 1], got %s" % (tuple(node_score.shape),))
+        if node_score.dim() != 1 + len(tail) or node_score.shape[0] < 1 or tuple(node_score.shape[1:]) != tail:
+            raise ValueError("node_score must be %s, got %s" % ("[n >= 1, heads = %d]" % H if tail else "[n >= 1]",
+                                                                 tuple(node_score.shape)))
         n = node_score.shape[0]
         if num_nodes is not None and num_nodes != n:
             raise ValueError("node_score has %d elements, num_nodes is %r" % (n, num_nodes))
@@ -838,11 +924,13 @@ def knn_softmax(idx, node_score=None, edge_score=None, group="hyperedge", negati
         if not isinstance(n, numbers.Integral) or isinstance(n, bool) or not 1 <= n < 2 ** 31 - 1:
             raise ValueError("num_nodes must be a positive integer, got %r" % (num_nodes,))
         n = int(n)
-    if edge_score is not None and tuple(edge_score.shape) != (rows,):
-        raise ValueError("edge_score must be [rows] = [%d], got %s" % (rows, tuple(edge_score.shape)))
-    if entry_score is not None and tuple(entry_score.shape) not in ((rows, k), (rows * k,)):
-        raise ValueError("entry_score must be [rows, k] = [%d, %d] or [rows * k] = [%d], got %s"
-                         % (rows, k, rows * k, tuple(entry_score.shape)))
+    if edge_score is not None and tuple(edge_score.shape) != (rows, *tail):
+        raise ValueError("edge_score must be %s, got %s" % ("[rows, heads] = [%d, %d]" % (rows, H) if tail else "[rows] = [%d]" % rows,
+                                                             tuple(edge_score.shape)))
+    if entry_score is not None and tuple(entry_score.shape) not in ((rows, k, *tail), (rows * k, *tail)):
+        want = "[rows, k, heads] = [%d, %d, %d] or [rows * k, heads] = [%d, %d]" % (rows, k, H, rows * k, H) if tail \
+            else "[rows, k] = [%d, %d] or [rows * k] = [%d]" % (rows, k, rows * k)
+        raise ValueError("entry_score must be %s, got %s" % (want, tuple(entry_score.shape)))
     _check_transpose_shapes(transpose, n, rows * k)
     _check_table_index(idx, "idx")
     for name, t in scores:
@@ -858,8 +946,8 @@ def knn_softmax(idx, node_score=None, edge_score=None, group="hyperedge", negati
         _check_table_index(pos_v, "pos_v")
     slope = float(negative_slope)
     if grad and any(t is not None and t.requires_grad for _, t in scores):
-        return _KnnSoftmax.apply(node_score, edge_score, entry_score, idx, ptr_v, pos_v, group, slope, n)
-    return table_softmax(idx, n, group, node_score, edge_score, entry_score, slope, ptr_v, pos_v)
+        return _KnnSoftmax.apply(node_score, edge_score, entry_score, idx, ptr_v, pos_v, group, slope, n, H)
+    return table_softmax(idx, n, group, node_score, edge_score, entry_score, slope, ptr_v, pos_v, H)
 
 
 def _knn_aggr_reduced(idx, X, weight, degE, degV, transpose, first, second):
@@ -897,18 +985,32 @@ def _knn_aggr_reduced(idx, X, weight, degE, degV, transpose, first, second):
     return knn_gather(idx, Xe, "vertex", second, degV, transpose, num_nodes=n)
 
 
+def _weight_heads(idx, weight):
+    """H of a knn_aggr weight: its last dimension where it is [rows * k, H] or [rows, k, H] with H > 1, else 1 (a weight of
+    any other shape is the single-head call's to accept or refuse).  Looks at shapes only and raises nothing."""
+    if not isinstance(idx, torch.Tensor) or not isinstance(weight, torch.Tensor) or idx.dim() != 2 or weight.dim() < 2:
+        return 1
+    rows, k = idx.shape
+    lead, H = tuple(weight.shape[:-1]), weight.shape[-1]
+    if H > 1 and lead in ((rows * k,), (rows, k)) and tuple(weight.shape) != (rows, k):
+        return int(H)
+    return 1
+
+
 class _KnnAggr(torch.autograd.Function):
     """Y = degV . H_w (degE . (H_w^T X)) over a neighbour table; the gradient of X is the same two gathers swapped.  Saves the
     table, its transpose, the weight and the scales -- nothing of rows * F elements.  Where the weight asks for its gradient,
     dw[p = (i, s)] = degV[v] <dY[v], Xe[i]> + <X[v], G[i]>, v = idx[i, s], one launch of hg_table_dot_f32: Xe is computed
     again in the backward, and the input X is saved as well.
     bfloat16 X: Xe and G stay float32, Y and dX are rounded once in the second gather's store, dw (float32) comes from
-    hg_table_dot_bf16 -- the float32 node on X.float() and dY.float(), bit for bit, with the same saved tensors."""
+    hg_table_dot_bf16 -- the float32 node on X.float() and dY.float(), bit for bit, with the same saved tensors.
+    heads = H > 1: w [.., H]; the same gathers and the same dot on the several-heads entries, the same saved tensors."""
 
     @staticmethod
-    def forward(ctx, X, w, idx, ptr_v, pos_v, degE, degV):
-        Xe = table_gather(idx, X, w, None, degE)
-        Y = table_gather_t(ptr_v, pos_v, idx.shape[1], Xe, w, None, degV, dst_dtype=X.dtype)
+    def forward(ctx, X, w, idx, ptr_v, pos_v, degE, degV, heads=1):
+        ctx.heads = heads
+        Xe = table_gather(idx, X, w, None, degE, heads=heads)
+        Y = table_gather_t(ptr_v, pos_v, idx.shape[1], Xe, w, None, degV, dst_dtype=X.dtype, heads=heads)
         ctx.save_for_backward(idx, ptr_v, pos_v, w, degE, degV, *((X,) if ctx.needs_input_grad[1] else ()))
         return Y
 
@@ -916,14 +1018,15 @@ class _KnnAggr(torch.autograd.Function):
     def backward(ctx, dY):
         idx, ptr_v, pos_v, w, degE, degV = ctx.saved_tensors[:6]
         dY = dY.contiguous()
-        G = table_gather(idx, dY, w, degV, degE)
-        dX = table_gather_t(ptr_v, pos_v, idx.shape[1], G, w, dst_dtype=dY.dtype) if ctx.needs_input_grad[0] else None
+        H = ctx.heads
+        G = table_gather(idx, dY, w, degV, degE, heads=H)
+        dX = table_gather_t(ptr_v, pos_v, idx.shape[1], G, w, dst_dtype=dY.dtype, heads=H) if ctx.needs_input_grad[0] else None
         dw = None
         if ctx.needs_input_grad[1]:
             X = ctx.saved_tensors[6]
-            Xe = table_gather(idx, X, w, None, degE)
-            dw = table_dot(idx, dY, Xe, degV, X, G).view(w.shape)
-        return dX, dw, None, None, None, None, None
+            Xe = table_gather(idx, X, w, None, degE, heads=H)
+            dw = table_dot(idx, dY, Xe, degV, X, G, heads=H).view(w.shape)
+        return dX, dw, None, None, None, None, None, None
 
 
 def knn_aggr(idx, X, weight=None, degE=None, degV=None, transpose=None, weight_grad=False, options=None, first="sum",
@@ -950,14 +1053,25 @@ def knn_aggr(idx, X, weight=None, degE=None, degV=None, transpose=None, weight_g
     Xe = knn_gather(X, to='hyperedge', reduce=first, scale=degE) and Y = knn_gather(Xe, to='vertex', reduce=second,
     scale=degV): UniSAGE's mean / max and EdgeConv's max on the device table.  A weight then raises ValueError and bfloat16
     TypeError, whatever the option; the gradient of X is knn_gather's (max / min: to the winner alone).
+    Several heads: a weight with one more dimension at its end, [rows * k, H] or [rows, k, H] with H > 1, is one weight per
+    entry and head, and H is taken from it (the call has no argument of its own for it).  ops.incidence_aggr's layout on the
+    table -- X [n, H * Ch], column c weighted by head c // Ch's weights in both hops -- every head in the same two launches
+    (hg_table_gather_heads_f32 / hg_table_gather_t_heads_f32), and weight_grad=True gives dw [.., H] from one launch of
+    hg_table_dot_heads_f32.  Head h's columns of Y and dX are, bit for bit, the same columns of the call at the full width
+    with weight[..., h]; dw[..., h] is the single-head call's on head h's columns.  It needs F % H == 0 and both reductions
+    'sum' (ValueError) and float32 rows (bfloat16 raises TypeError whatever the option).  Any other weight is the call above.
     Refusals, in this order and before a device is touched: TypeError for an idx (ptr_v, pos_v) that is not int32 and for
     an X (bfloat16 under the option apart), weight, degE or degV that is not float32; ValueError for the shapes and k;
     RuntimeError for a weight, degE or degV that requires a gradient, and for CPU tensors."""
     if first != "sum" or second != "sum":
         return _knn_aggr_reduced(idx, X, weight, degE, degV, transpose, first, second)
-    bf16 = _rows_bf16(X, options)
+    H = _weight_heads(idx, weight)
+    several = H > 1
+    bf16 = not several and _rows_bf16(X, options)
     _table_shape(idx)
-    if not bf16:
+    if several:
+        _check_dtype(X, "X", torch.float32, " (knn_aggr with heads has no bfloat16, float16 or float64 form)")
+    elif not bf16:
         _check_dtype(X, "X", torch.float32, _NO_FORM % "knn_aggr")
     scales = (("weight", weight), ("degE", degE), ("degV", degV))
     for name, t in scales:
@@ -968,7 +1082,9 @@ def knn_aggr(idx, X, weight=None, degE=None, degV=None, transpose=None, weight_g
     if X.dim() != 2 or X.shape[0] < 1 or X.shape[1] < 1:
         raise ValueError("X must be [n >= 1, F >= 1], got %s" % (tuple(X.shape),))
     n = X.shape[0]
-    if weight is not None and tuple(weight.shape) not in ((rows * k,), (rows, k)):
+    if X.shape[1] % H:
+        raise ValueError("X has F = %d columns, no multiple of heads = %d (weight is %s)" % (X.shape[1], H, tuple(weight.shape)))
+    if H == 1 and weight is not None and tuple(weight.shape) not in ((rows * k,), (rows, k)):
         raise ValueError("weight must be [rows * k] = [%d] or [rows, k] = [%d, %d], got %s" % (rows * k, rows, k, tuple(weight.shape)))
     for name, t, count in (("degE", degE, rows), ("degV", degV, n)):
         if t is not None and tuple(t.shape) not in ((count,), (count, 1)):
@@ -991,7 +1107,7 @@ def knn_aggr(idx, X, weight=None, degE=None, degV=None, transpose=None, weight_g
     w, degE, degV = (None if t is None else t.detach() for _, t in scales)
     if weight_grad and weight is not None and weight.requires_grad:
         w = weight  # the one scale whose gradient is wanted
-    return _KnnAggr.apply(X, w, idx, ptr_v, pos_v, degE, degV)
+    return _KnnAggr.apply(X, w, idx, ptr_v, pos_v, degE, degV, H)
 
 
 class KnnHypergraph:
@@ -1007,9 +1123,10 @@ class KnnHypergraph:
       aggregate(Z, probabilistic=False, m_prob=1.0, X=None, first="sum", second="sum"): ops.knn_aggr over the table; X goes
         to weights, and the weights then get their gradient (weight_grad=True); first / second are ops.knn_aggr's reductions
         (no weights with anything but the two sums).  weight=: explicit weights [N k] (or [N, k]) in place of the
-        probabilistic ones, passed with weight_grad=True -- attention's alpha; exclusive with probabilistic.
-      attention(node_score, edge_score, group="hyperedge", negative_slope=0.2): ops.knn_softmax over the table with the stored
-        transpose: alpha [N, k].
+        probabilistic ones, passed with weight_grad=True -- attention's alpha; exclusive with probabilistic.  heads=H:
+        the weight must be ops.knn_aggr's several-heads weight [N k, H] or [N, k, H] (ValueError otherwise).
+      attention(node_score, edge_score, group="hyperedge", negative_slope=0.2, heads=1): ops.knn_softmax over the table with
+        the stored transpose: alpha [N, k], or [N, k, H].
     form: ops.knn's -- "dot" gives the same idx and dist through the matrix-unit prefilter, and its own mean.  Under "dot" X
     may be bfloat16: the table, dist, mean, transpose and degrees are int32 / float32 as always, and aggregate / weights take
     bfloat16 Z / X where `options` (or the caller's) has Options.incidence_bf16 = 'rows' -- ops.knn_aggr's and ops.knn_dist's
@@ -1036,19 +1153,24 @@ class KnnHypergraph:
         dist = knn_dist(self.idx, X, transpose=(self.ptr_v, self.pos_v), options=options)
         return knn_incidence_weights(dist, self.mean, m_prob)
 
-    def aggregate(self, Z, probabilistic=False, m_prob=1.0, X=None, options=None, weight=None, first="sum", second="sum"):
+    def aggregate(self, Z, probabilistic=False, m_prob=1.0, X=None, options=None, weight=None, heads=1, first="sum",
+                  second="sum"):
+        if weight is not None and probabilistic:
+            raise ValueError("weight and probabilistic=True exclude each other (both are the table's weights)")
+        H = _heads_value(heads)
+        if H != _weight_heads(self.idx, weight):
+            raise ValueError("heads=%d needs weight [N k, %d] or [N, k, %d], got %s"
+                             % (H, H, H, None if weight is None else tuple(weight.shape)))
         if weight is not None:
-            if probabilistic:
-                raise ValueError("weight and probabilistic=True exclude each other (both are the table's weights)")
             return knn_aggr(self.idx, Z, weight, self.degE, self.degV, transpose=(self.ptr_v, self.pos_v), weight_grad=True,
                             options=options, first=first, second=second)
         w = self.weights(m_prob, X, options) if probabilistic else None
         return knn_aggr(self.idx, Z, w, self.degE, self.degV, transpose=(self.ptr_v, self.pos_v), weight_grad=X is not None,
                         options=options, first=first, second=second)
 
-    def attention(self, node_score=None, edge_score=None, group="hyperedge", negative_slope=0.2):
+    def attention(self, node_score=None, edge_score=None, group="hyperedge", negative_slope=0.2, heads=1):
         return knn_softmax(self.idx, node_score, edge_score, group, negative_slope, transpose=(self.ptr_v, self.pos_v),
-                           num_nodes=self.num_nodes)
+                           num_nodes=self.num_nodes, heads=heads)
 
 
 def table_seq_max():

@@ -176,12 +176,24 @@ class DynamicHypergraphConv(nn.Module):
     with alpha's gradient from ops.knn_aggr(weight_grad=True) and the scores' from ops.knn_softmax.  Two more parameters,
     a_v and a_e [out_channels], initialised as HypergraphAttnConv's; they exist only where attention is set.  With
     segments=None the layer still waits nowhere and is recorded into a hipGraph.  float32 only: a bfloat16 input raises
-    TypeError.  No heads, no dropout.  None (the default) is the layer above: same bits, same parameters."""
+    TypeError.  No dropout.  None (the default) is the layer above: same bits, same parameters.
+    heads = H > 1 (needs attention set): HypergraphAttnConv's multi-head additive layer, without bias, on the table.  lin maps
+    to H * out_channels, head h owns columns h C .. (h + 1) C - 1 of Z (C = out_channels), a_v / a_e are flat [H * C] with
+    the same initialisation bound, sv[u, h] = <Z[u, head h], a_v[head h]>, se the per-head hyperedge mean (ops.knn_gather on
+    an [N, H] source), alpha [N, k, H] = hyperg.attention(sv, se, heads=H) and Y = hyperg.aggregate(Z, weight=alpha, heads=H):
+    every table operator runs once for all heads (hg_table_*_heads_f32).  The output is [N, H * C] (concat=True) or the mean
+    over the heads [N, C].  With segments=None the layer still waits nowhere and is recorded into a hipGraph.  heads = 1 is the
+    layer above: same bits, same state_dict."""
 
     def __init__(self, in_channels, out_channels, k, probabilistic=False, segments=None, m_prob=1.0, options=None,
                  device_graph=False, knn_form="difference", learn_distances=False, first_aggr="sum", second_aggr="sum",
-                 attention=None, negative_slope=0.2):
+                 attention=None, negative_slope=0.2, heads=1, concat=True):
         super().__init__()
+        if isinstance(heads, bool) or not isinstance(heads, int) or heads < 1:
+            raise ValueError("heads must be an integer >= 1, got %r" % (heads,))
+        if heads > 1 and attention is None:
+            raise ValueError("heads=%d needs attention='hyperedge' or 'vertex' (the heads are attention heads)" % heads)
+        self.heads, self.concat = heads, bool(concat)
         if not isinstance(k, int) or not 1 <= k <= 64:
             raise ValueError("k must be an integer in 1 .. 64, got %r" % (k,))
         for name, r in (("first_aggr", first_aggr), ("second_aggr", second_aggr)):
@@ -197,7 +209,7 @@ class DynamicHypergraphConv(nn.Module):
                              "device_graph=True (ops.knn_dist and the weight gradient run over the device table)")
         self.learn_distances = bool(learn_distances)
         self.options = options
-        self.lin = ops.Linear(in_channels, out_channels, bias=False, options=options)
+        self.lin = ops.Linear(in_channels, heads * out_channels, bias=False, options=options)
         self.in_channels, self.out_channels, self.k = in_channels, out_channels, k
         self.probabilistic, self.segments, self.m_prob = probabilistic, segments, m_prob
         self.device_graph = bool(device_graph)
@@ -216,8 +228,8 @@ class DynamicHypergraphConv(nn.Module):
             if probabilistic:
                 raise ValueError("attention=%r needs probabilistic=False (the coefficients are the table's weights)" % (attention,))
             bound = math.sqrt(6.0 / (out_channels + 1))
-            self.a_v = nn.Parameter(torch.empty(out_channels).uniform_(-bound, bound))
-            self.a_e = nn.Parameter(torch.empty(out_channels).uniform_(-bound, bound))
+            self.a_v = nn.Parameter(torch.empty(heads * out_channels).uniform_(-bound, bound))
+            self.a_e = nn.Parameter(torch.empty(heads * out_channels).uniform_(-bound, bound))
 
     def _attention_forward(self, X):
         from .knn_graph import KnnHypergraph, knn_gather
@@ -226,6 +238,15 @@ class DynamicHypergraphConv(nn.Module):
         hyperg = self.hyperg = KnnHypergraph.build(X, self.k, segments=self.segments, form=self.knn_form)
         Z = self.lin(X)
         transpose = (hyperg.ptr_v, hyperg.pos_v)
+        if self.heads > 1:
+            H, C = self.heads, self.out_channels
+            Zh = Z.view(Z.shape[0], H, C)
+            sv = (Zh * self.a_v.view(H, C)).sum(-1)
+            ze = (Zh * self.a_e.view(H, C)).sum(-1)
+            se = knn_gather(hyperg.idx, ze, "hyperedge", "mean", transpose=transpose)
+            alpha = hyperg.attention(sv, se, self.attention, self.negative_slope, heads=H)
+            Y = hyperg.aggregate(Z, options=self.options, weight=alpha, heads=H)
+            return Y if self.concat else Y.view(Y.shape[0], H, C).mean(1)
         sv = Z @ self.a_v
         se = knn_gather(hyperg.idx, (Z @ self.a_e)[:, None].contiguous(), "hyperedge", "mean", transpose=transpose).reshape(-1)
         alpha = hyperg.attention(sv, se, self.attention, self.negative_slope)

@@ -1138,6 +1138,58 @@ HG_API int hg_table_softmax_bwd_f32(const int32_t *idx, int32_t rows, int32_t k,
 HG_API int hg_table_sum_f32(const int32_t *idx, int32_t rows, int32_t k, int32_t n, int32_t side, const int32_t *ptr_v,
                             const int32_t *pos_v, const float *val, float *out, hg_stream_t stream);
 
+/* Several heads over a neighbour table (csrc/hg_table_heads.hip): the attention softmax family, the two weighted sum gathers
+ * and the weight gradient's dot products for `heads` = H heads in ONE launch each.  Like the entries above each launches once
+ * on `stream`, allocates and waits for nothing, takes no workspace, uses no atomics and can be recorded into a hipGraph.
+ * float32 only.  The layout is the several-heads section's above, on the table: head is the FASTEST dimension of every
+ * score and coefficient array -- node_score [n, H], edge_score [rows, H], entry_score, alpha, dalpha, ds, val and w
+ * [rows * k, H], dgroup and out [segments, H] -- and head h owns the columns h Ch .. (h + 1) Ch - 1 of every feature row,
+ * F = H Ch.  heads = 1 is the single-head entry's result.
+ *
+ * hg_table_softmax_heads_f32 / hg_table_softmax_bwd_heads_f32 / hg_table_sum_heads_f32: head h of every output is, BIT FOR
+ *   BIT, what hg_table_softmax_f32 / hg_table_softmax_bwd_f32 / hg_table_sum_f32 give on column h of the inputs: the same
+ *   formula operation for operation, and the SEGMENT ORDER paragraph per head, word for word -- the same L, the same entry
+ *   of a lane, the same butterfly, the same 256-thread order ((w0 + w1) + w2) + w3 of a long VERTEX segment.  A lane carries
+ *   a slab of 4 consecutive heads of its entry (16-byte accesses) where H % 4 == 0 and the head-fastest arrays are 16-byte
+ *   aligned, else one head; the bits do not depend on which.  An entry that is no candidate is exactly +0.0 in every head.
+ * hg_table_gather_heads_f32 / hg_table_gather_t_heads_f32: hg_table_gather_f32 / hg_table_gather_t_f32 with
+ *   term(p, j)[col] = (src[j, col] * src_scale[j]) * w[p, col / Ch];
+ *   everything else is the plain gathers' text, the ORDER paragraph AT THE SAME F included.  So head h's columns of dst are,
+ *   bit for bit, the same columns of the plain call at the full width F with the single weight array w[:, h] -- a vertex row
+ *   longer than HG_TABLE_SEQ_MAX too: its pieces and tree depend on F and the alignment alone.  A lane keeps its c = 4
+ *   columns where the plain call has them; it loads one weight an entry where Ch % 4 == 0 and one per column where its
+ *   columns straddle two heads.  w may not be NULL (the plain entry is that call).
+ * hg_table_dot_heads_f32: out[p, h] = a_scale[j] * <A[j, head h], B[i, head h]> + <C[j, head h], D[i, head h]>, out
+ *   [rows * k, H]; the DOT ORDER paragraph at width Ch: c = 4 where Ch % 4 == 0 and A, B, C and D are 16-byte aligned, else 1,
+ *   L = the power of two at or above min(ceil(Ch / c), 64) lanes per (position, head).  So out[:, h] is, bit for bit,
+ *   hg_table_dot_f32 on contiguous copies of head h's columns.  With Xe = gather_heads(idx, X, w, NULL, degE) and
+ *   G = gather_heads(idx, dY, w, degV, degE), dw = hg_table_dot_heads_f32(A = dY, a_scale = degV, B = Xe, C = X, D = G).
+ * Refusals launch nothing, set hg_last_error, in the single-head entries' order with, after the sizes (rows, n or F < 1, k
+ *   outside 1 .. 64, rows * k >= 2^31): HG_ERR_INVALID for heads < 1 and for F % heads != 0; a null w is refused with the
+ *   other null pointers.
+ * Not covered: dropout, bfloat16 scores or rows, max / min.  Detect these entries by their exported symbols. */
+HG_API int hg_table_softmax_heads_f32(const int32_t *idx, int32_t rows, int32_t k, int32_t n, int32_t heads, int32_t group,
+                                      const float *node_score, const float *edge_score, const float *entry_score,
+                                      float slope, const int32_t *ptr_v, const int32_t *pos_v, float *alpha,
+                                      hg_stream_t stream);
+HG_API int hg_table_softmax_bwd_heads_f32(const int32_t *idx, int32_t rows, int32_t k, int32_t n, int32_t heads, int32_t group,
+                                          const float *node_score, const float *edge_score, const float *entry_score,
+                                          float slope, const int32_t *ptr_v, const int32_t *pos_v, const float *alpha,
+                                          const float *dalpha, float *ds, float *dgroup /* may be NULL */,
+                                          hg_stream_t stream);
+HG_API int hg_table_sum_heads_f32(const int32_t *idx, int32_t rows, int32_t k, int32_t n, int32_t heads, int32_t side,
+                                  const int32_t *ptr_v, const int32_t *pos_v, const float *val, float *out,
+                                  hg_stream_t stream);
+HG_API int hg_table_gather_heads_f32(const int32_t *idx, int32_t rows, int32_t k, int32_t n, int32_t F, int32_t heads,
+                                     const float *src, const float *w, const float *src_scale, const float *dst_scale,
+                                     float *dst, hg_stream_t stream);
+HG_API int hg_table_gather_t_heads_f32(const int32_t *ptr_v, const int32_t *pos_v, int32_t rows, int32_t k, int32_t n,
+                                       int32_t F, int32_t heads, const float *src, const float *w, const float *src_scale,
+                                       const float *dst_scale, float *dst, hg_stream_t stream);
+HG_API int hg_table_dot_heads_f32(const int32_t *idx, int32_t rows, int32_t k, int32_t n, int32_t F, int32_t heads,
+                                  const float *A, const float *a_scale, const float *B, const float *C, const float *D,
+                                  float *out, hg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
