@@ -74,5 +74,16 @@ bool knn_sizes_ok(int32_t nq, int32_t n, int32_t F, int32_t k, int32_t cand_slic
 // The refusals up to the entry's own alignment check, in the order include/hg_aggr.h gives: HG_OK, or the status with the
 // error set.  max_F: as above, refused where the dot entry refuses it; seg / B: the difference entry's segments (null: none).
 int knn_refusal(const KnnCall &c, int32_t max_F, const int32_t *seg, int32_t B);
+// What the *_sets_* entries refuse after knn_refusal, in this order: set_rows < 1, n % set_rows != 0, set_rows < k.
+int knn_sets_refusal(const char *entry, int32_t n, int32_t k, int32_t set_rows);
+
+// Uniform sets (set_rows = m, B = n / m sets of m consecutive rows) under the dot form: every stage of hg_knn_dot_f32 runs
+// on a set as on a problem of its own -- n = nq = m, kp = min(m, 32 * knn_dot_slots(k)), ceil(m / kDotTQ) query tiles -- with
+// its argument block rebased onto the set.  The workspace is knn_dot_layout(n, n, ..)'s with these differences: no block
+// maxima, n2max holds B floats, the shortlists are [B, slices, m, kp] with set-relative row numbers, the partial means
+// [B, slices, m].
+KnnDotLayout knn_dot_sets_layout(int64_t n, int64_t set_rows, int k, int slices);
+// knn_dot_slices for B sets: B * ceil(m / kDotTQ) workgroups to fill the device with, ceil(m / kDotTC) tiles to share.
+int knn_dot_sets_slices(int64_t n, int64_t set_rows, int cand_slices);
 
 }  // namespace hg

@@ -14,6 +14,8 @@
 // with one shift by a lane (list_offer<KS, 32>).  The other slices' lists go to the workspace and knn_merge_kernel ranks
 // every entry of a row's lists against the others under the same order (merged_rank).  The list and the rank are
 // hg_knn_list.h's, shared with hg_knn_dot.hip.
+// A row's candidates are all n, its segment (offsets copied from the host), or its set of set_rows rows (hg_knn_sets_f32:
+// the range is computed from the row number, nothing is copied or waited for); row_range is the one place that differs.
 #include <hip/hip_runtime.h>
 
 #include <climits>
@@ -75,6 +77,15 @@ int knn_refusal(const KnnCall &c, int32_t max_F, const int32_t *seg, int32_t B) 
   return HG_OK;
 }
 
+int knn_sets_refusal(const char *entry, int32_t n, int32_t k, int32_t set_rows) {
+  if (set_rows < 1) return fail(entry, HG_ERR_INVALID, "set_rows must be at least 1, got " + std::to_string(set_rows));
+  if (n % set_rows)
+    return fail(entry, HG_ERR_INVALID, "n = " + std::to_string(n) + " is no multiple of set_rows = " + std::to_string(set_rows));
+  if (set_rows < k)
+    return fail(entry, HG_ERR_INVALID, "a set has " + std::to_string(set_rows) + " rows, fewer than k = " + std::to_string(k));
+  return HG_OK;
+}
+
 namespace {
 
 typedef float v2f __attribute__((ext_vector_type(2)));
@@ -83,6 +94,7 @@ struct KnnArgs {
   const float *Q, *X;
   const int32_t *seg;  // device copy of the offsets [B + 1], or null: every row competes with all n
   int32_t nq, n, F, k, B, slices, self_first;
+  int32_t set_rows;  // above 0 (seg is null then): row i competes with the set_rows rows of its own set, no offsets anywhere
   // slice 0's list and partial mean, and the final result (no __restrict__: the merge reads and writes them)
   int32_t *idx;
   float *dist, *mean;
@@ -91,14 +103,20 @@ struct KnnArgs {
   float *ws_mean;  // [slices - 1, nq]
 };
 
-// the candidates [lo, hi) of row i: its segment, or all n
-__device__ __forceinline__ void row_range(const int32_t *seg, int B, int n, int i, int &lo, int &hi) {
-  if (!seg) {
-    lo = 0;
-    hi = n;
+// the candidates [lo, hi) of row i: its segment, its set of a.set_rows rows, or all n
+__device__ __forceinline__ void row_range(const KnnArgs &args, int i, int &lo, int &hi) {
+  const int32_t *seg = args.seg;
+  if (args.set_rows > 0) {
+    lo = i / args.set_rows * args.set_rows;
+    hi = lo + args.set_rows;
     return;
   }
-  int a = 0, b = B;  // seg[a] <= i < seg[b]
+  if (!seg) {
+    lo = 0;
+    hi = args.n;
+    return;
+  }
+  int a = 0, b = args.B;  // seg[a] <= i < seg[b]
   while (b - a > 1) {
     const int m = (a + b) >> 1;
     if (seg[m] <= i) a = m;
@@ -121,12 +139,12 @@ __global__ __launch_bounds__(kKnnBlock) void knn_kernel(KnnArgs a) {
 
   if (t < kKnnTQ) {
     int lo, hi;
-    row_range(a.seg, a.B, a.n, min(q0 + t, a.nq - 1), lo, hi);
+    row_range(a, min(q0 + t, a.nq - 1), lo, hi);
     s_lo[t] = lo;
     s_hi[t] = hi;
   }
   __syncthreads();
-  // segments ascend with the rows: the tile's candidates are one range, cut into tiles from its own start
+  // segments and sets ascend with the rows: the tile's candidates are one range, cut into tiles from its own start
   const int c_lo = s_lo[0], c_hi = s_hi[kKnnTQ - 1];
   const int tiles = (c_hi - c_lo + kKnnTC - 1) / kKnnTC;
   const int t_begin = (int)((int64_t)tiles * slice / a.slices), t_end = (int)((int64_t)tiles * (slice + 1) / a.slices);
@@ -289,31 +307,19 @@ __global__ __launch_bounds__(64 * kKnnMergeRows) void knn_merge_kernel(KnnArgs a
     float v = a.mean[row];
     for (int s = 1; s < a.slices; ++s) v += a.ws_mean[(size_t)(s - 1) * a.nq + row];
     int lo, hi;
-    row_range(a.seg, a.B, a.n, row, lo, hi);
+    row_range(a, row, lo, hi);
     a.mean[row] = v / (float)(hi - lo);
   }
 }
 
-}  // namespace
-}  // namespace hg
-
-extern "C" {
-
-size_t hg_knn_workspace_bytes(int32_t nq, int32_t n, int32_t F, int32_t k, int32_t cand_slices) {
-  if (!hg::knn_sizes_ok(nq, n, F, k, cand_slices, 0)) return 0;
-  const int slices = cand_slices ? cand_slices : hg::knn_auto_slices(nq, n);
-  return hg::knn_layout(nq, n, k, slices).total;
-}
-
-int hg_knn_f32(const float *Q, int32_t nq, const float *X, int32_t n, int32_t F, int32_t k, const int32_t *seg, int32_t B,
-               int32_t self_first, int32_t cand_slices, int32_t *idx, float *dist, float *mean_dist, void *workspace,
-               size_t workspace_bytes, hg_stream_t stream) {
-  using namespace hg;
-  const char *entry = "hg_knn_f32";
-  if (const int st = knn_refusal({entry, Q, X, idx, dist, nq, n, F, k, self_first, cand_slices}, 0, seg, B)) return st;
+// hg_knn_f32 and hg_knn_sets_f32 past their refusals: the workspace and the launches.  seg (host offsets) or set_rows, not both.
+int knn_run(const char *entry, const float *Q, int32_t nq, const float *X, int32_t n, int32_t F, int32_t k, const int32_t *seg,
+            int32_t B, int32_t set_rows, int32_t self_first, int32_t cand_slices, int32_t *idx, float *dist, float *mean_dist,
+            void *workspace, size_t workspace_bytes, hg_stream_t stream) {
   for (const void *p : {(const void *)Q, (const void *)X, (const void *)idx, (const void *)dist, (const void *)mean_dist,
                         (const void *)workspace})
-    if ((uintptr_t)p % 4) return fail(entry, HG_ERR_UNSUPPORTED, "Q, X, idx, dist, mean_dist and the workspace must be 4-byte aligned");
+    if ((uintptr_t)p % 4)
+      return fail(entry, HG_ERR_UNSUPPORTED, std::string(set_rows ? "" : "Q, ") + "X, idx, dist, mean_dist and the workspace must be 4-byte aligned");
   const int slices = cand_slices ? cand_slices : knn_auto_slices(nq, n);
   const KnnLayout L = knn_layout(nq, n, k, slices);
   const bool need_ws = seg || slices > 1;
@@ -333,6 +339,7 @@ int hg_knn_f32(const float *Q, int32_t nq, const float *X, int32_t n, int32_t F,
   a.B = B;
   a.slices = slices;
   a.self_first = self_first ? 1 : 0;
+  a.set_rows = set_rows;
   a.idx = idx;
   a.dist = dist;
   a.mean = mean_dist;
@@ -363,6 +370,36 @@ int hg_knn_f32(const float *Q, int32_t nq, const float *X, int32_t n, int32_t F,
   }
   if (e != hipSuccess) return fail(entry, HG_ERR_HIP, std::string("launch: ") + hipGetErrorString(e));
   return HG_OK;
+}
+
+}  // namespace
+}  // namespace hg
+
+extern "C" {
+
+size_t hg_knn_workspace_bytes(int32_t nq, int32_t n, int32_t F, int32_t k, int32_t cand_slices) {
+  if (!hg::knn_sizes_ok(nq, n, F, k, cand_slices, 0)) return 0;
+  const int slices = cand_slices ? cand_slices : hg::knn_auto_slices(nq, n);
+  return hg::knn_layout(nq, n, k, slices).total;
+}
+
+int hg_knn_f32(const float *Q, int32_t nq, const float *X, int32_t n, int32_t F, int32_t k, const int32_t *seg, int32_t B,
+               int32_t self_first, int32_t cand_slices, int32_t *idx, float *dist, float *mean_dist, void *workspace,
+               size_t workspace_bytes, hg_stream_t stream) {
+  using namespace hg;
+  const char *entry = "hg_knn_f32";
+  if (const int st = knn_refusal({entry, Q, X, idx, dist, nq, n, F, k, self_first, cand_slices}, 0, seg, B)) return st;
+  return knn_run(entry, Q, nq, X, n, F, k, seg, B, 0, self_first, cand_slices, idx, dist, mean_dist, workspace, workspace_bytes, stream);
+}
+
+int hg_knn_sets_f32(const float *X, int32_t n, int32_t F, int32_t k, int32_t set_rows, int32_t self_first, int32_t cand_slices,
+                    int32_t *idx, float *dist, float *mean_dist, void *workspace, size_t workspace_bytes, hg_stream_t stream) {
+  using namespace hg;
+  const char *entry = "hg_knn_sets_f32";
+  if (const int st = knn_refusal({entry, X, X, idx, dist, n, n, F, k, self_first, cand_slices}, 0, nullptr, 0)) return st;
+  if (const int st = knn_sets_refusal(entry, n, k, set_rows)) return st;
+  return knn_run(entry, X, n, X, n, F, k, nullptr, 0, set_rows, self_first, cand_slices, idx, dist, mean_dist, workspace,
+                 workspace_bytes, stream);
 }
 
 }  // extern "C"

@@ -21,6 +21,12 @@
 // (offer_tile, write_lists); the certificate uses the bound E1b (dot_e1b).  The float32 instances are instruction for
 // instruction what they were before R existed -- which is why knn_dot_prefilter_kernel keeps its body inline: calling
 // offer_tile / write_lists from it changed its register allocation.  knn_dot_estimates_bf16_kernel is the diagnostic entry's.
+//
+// Uniform sets (hg_knn_dot_sets_f32 / _bf16): B sets of m rows, every set searched as a problem of its own.
+// The prefilter and the rerank have SETS instances whose only added code is rebase_to_set: the argument block holds one
+// set's sizes and the whole call's arrays, and the workgroup moves the pointers to its set before the unchanged body runs.
+// knn_dot_set_max_kernel gives every set its own norm maximum for the certificate.  The SETS = false instances are the
+// kernels above, instruction for instruction.
 #include <hip/hip_runtime.h>
 
 #include <climits>
@@ -51,12 +57,35 @@ KnnDotLayout knn_dot_layout(int64_t nq, int64_t n, int k, int slices) {
   return L;
 }
 
-int knn_dot_slices(int64_t nq, int64_t n, int cand_slices) {
-  const int64_t groups = (nq + kDotTQ - 1) / kDotTQ, tiles = (n + kDotTC - 1) / kDotTC;
+static int dot_slices(int64_t groups, int64_t tiles, int cand_slices) {
   int64_t s = cand_slices ? cand_slices : 512 / groups;
   if (s > kKnnMaxSlices) s = kKnnMaxSlices;
   if (s > tiles) s = tiles;
   return s < 1 ? 1 : (int)s;
+}
+
+int knn_dot_slices(int64_t nq, int64_t n, int cand_slices) {
+  return dot_slices((nq + kDotTQ - 1) / kDotTQ, (n + kDotTC - 1) / kDotTC, cand_slices);
+}
+
+int knn_dot_sets_slices(int64_t n, int64_t set_rows, int cand_slices) {
+  return dot_slices(n / set_rows * ((set_rows + kDotTQ - 1) / kDotTQ), (set_rows + kDotTC - 1) / kDotTC, cand_slices);
+}
+
+KnnDotLayout knn_dot_sets_layout(int64_t n, int64_t set_rows, int k, int slices) {
+  KnnDotLayout L;
+  auto up = [](size_t b) { return (b + 255) / 256 * 256; };
+  const int64_t cap = 32 * (int64_t)knn_dot_slots(k);
+  L.kp = (int)(set_rows < cap ? set_rows : cap);
+  const size_t lists = (size_t)slices * (size_t)n * (size_t)L.kp * 4;
+  L.n2x = L.n2q = 0;  // Q is X
+  L.bmax = 0;         // unused: no block maxima (the norm kernel gets a null bmax, the sets' maxima are knn_dot_set_max_kernel's)
+  L.n2max = up((size_t)n * 4);
+  L.idx = L.n2max + up((size_t)(n / set_rows) * 4);
+  L.est = L.idx + up(lists);
+  L.mean = L.est + up(lists);
+  L.total = L.mean + up((size_t)slices * (size_t)n * 4);
+  return L;
 }
 
 namespace {
@@ -78,6 +107,39 @@ struct DotArgsT {
 };
 typedef DotArgsT<float> DotArgs;
 typedef DotArgsT<uint16_t> DotArgsBf16;
+
+// Uniform sets (the SETS instances; hg_knn_dot_sets_f32 / _bf16): a's n = nq = m, the rows of one set, and every array is the
+// whole call's.  This moves a's pointers to set b, so that the kernel's body runs on the set as on a problem of its own:
+// rows and candidates are numbered 0 .. m - 1 from the set's first row, the only candidate mask stays j < n, and the set's
+// shortlists [slices, m, kp], partial means [slices, m] and norm maximum are the ones the body's own indexing reaches.
+template <typename R>
+__device__ __forceinline__ void rebase_to_set(DotArgsT<R> &a, int b) {
+  const size_t lo = (size_t)b * a.n;
+  a.Q += lo * a.F;
+  a.X += lo * a.F;
+  a.n2q += lo;
+  a.n2x += lo;
+  a.n2max += b;
+  a.l_idx += lo * a.slices * a.kp;
+  a.l_est += lo * a.slices * a.kp;
+  if (a.l_mean) a.l_mean += lo * a.slices;
+  a.idx += lo * a.k;
+  a.dist += lo * a.k;
+  if (a.mean) a.mean += lo;
+  if (a.fallback) a.fallback += lo;
+}
+
+// one wave per set: the maximum candidate norm of the set, n2max[b] = max n2[b m .. b m + m - 1]
+__global__ __launch_bounds__(256) void knn_dot_set_max_kernel(const float *__restrict__ n2, int B, int m, float *__restrict__ n2max) {
+  const int lane = threadIdx.x & 63, b = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (b >= B) return;
+  const float *row = n2 + (size_t)b * m;
+  float v = 0.f;
+  for (int i = lane; i < m; i += 64) v = fmaxf(v, row[i]);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
+  if (lane == 0) n2max[b] = v;
+}
 
 __device__ __forceinline__ float widen(float v) { return v; }
 __device__ __forceinline__ float widen(uint16_t v) { return __uint_as_float((uint32_t)v << 16); }  // exact
@@ -147,13 +209,20 @@ __global__ __launch_bounds__(256) void knn_dot_max_kernel(const float *__restric
   if (t == 0) out[0] = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
 }
 
-// KS: shortlist slots per lane (kp <= 32 KS); MEAN: also sum sqrt(max(d~, 0)) over every candidate of the row
-template <int KS, bool MEAN>
+// KS: shortlist slots per lane (kp <= 32 KS); MEAN: also sum sqrt(max(d~, 0)) over every candidate of the row; SETS: workgroup x
+// is query tile x % ceil(n / 128) of set x / ceil(n / 128) (rebase_to_set) -- its 128 rows never straddle two sets
+template <int KS, bool MEAN, bool SETS>
 __global__ __launch_bounds__(kDotBlock) void knn_dot_prefilter_kernel(DotArgs a) {
   __shared__ float Qs[kDotTQ][kDotLd];
   __shared__ float Xs[kDotTC][kDotLd];
   const int t = threadIdx.x, lane = t & 63, w = t >> 6, tx = lane & 31, h = lane >> 5;
-  const int q0 = blockIdx.x * kDotTQ, slice = blockIdx.y;
+  int qt = blockIdx.x;
+  if constexpr (SETS) {
+    const int per_set = (a.n + kDotTQ - 1) / kDotTQ;
+    rebase_to_set(a, qt / per_set);
+    qt %= per_set;
+  }
+  const int q0 = qt * kDotTQ, slice = blockIdx.y;
   const int F = a.F, kp = a.kp, n = a.n;
   const int tiles = (n + kDotTC - 1) / kDotTC;
   const int t_begin = (int)((int64_t)tiles * slice / a.slices), t_end = (int)((int64_t)tiles * (slice + 1) / a.slices);
@@ -435,12 +504,18 @@ __device__ __forceinline__ void write_lists(const DotArgsT<R> &a, int slice, int
 }
 
 // knn_dot_prefilter_kernel for bfloat16 rows: the same workgroup, tiles, slices, shortlists and mean
-template <int KS, bool MEAN>
+template <int KS, bool MEAN, bool SETS>
 __global__ __launch_bounds__(kDotBlock) void knn_dot_prefilter_bf16_kernel(DotArgsBf16 a) {
   __shared__ __attribute__((aligned(16))) uint16_t Qs[kDotTQ][kDotBfLd];
   __shared__ __attribute__((aligned(16))) uint16_t Xs[kDotTC][kDotBfLd];
   const int t = threadIdx.x, lane = t & 63, w = t >> 6, h = lane >> 5;
-  const int q0 = blockIdx.x * kDotTQ, slice = blockIdx.y;
+  int qt = blockIdx.x;
+  if constexpr (SETS) {  // as knn_dot_prefilter_kernel's; F % 8 == 0 where bf_vec holds, so a set's rows stay 16-byte aligned
+    const int per_set = (a.n + kDotTQ - 1) / kDotTQ;
+    rebase_to_set(a, qt / per_set);
+    qt %= per_set;
+  }
+  const int q0 = qt * kDotTQ, slice = blockIdx.y;
   const int tiles = (a.n + kDotTC - 1) / kDotTC;
   const int t_begin = (int)((int64_t)tiles * slice / a.slices), t_end = (int)((int64_t)tiles * (slice + 1) / a.slices);
   const bool vec = bf_vec(a);
@@ -537,7 +612,9 @@ __device__ __forceinline__ void rerank_offer(const DotArgsT<R> &a, int row, bool
   list_offer<1, 64>(bd, bj, !ok ? NAN : (a.self_first && j == row) ? -1.f : d2, j, a.k, td, tj);
 }
 
-template <typename R>
+// SETS: workgroup x is row x % n of set x / n (rebase_to_set): the shortlist, the norm maximum of the certificate, the
+// exhaustive scan and the mean are the set's; idx goes out in the whole call's row numbers
+template <typename R, bool SETS>
 __global__ __launch_bounds__(kDotRerankRows) void knn_dot_rerank_kernel(DotArgsT<R> a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char dot_smem[];
   float(*tile)[kDotRerankRows + 1] = reinterpret_cast<float(*)[kDotRerankRows + 1]>(dot_smem);
@@ -545,7 +622,14 @@ __global__ __launch_bounds__(kDotRerankRows) void knn_dot_rerank_kernel(DotArgsT
   float *cd = qs + kDotRerankRows;                  // the merged shortlist [kp <= 96]
   int *cj = reinterpret_cast<int *>(cd + 96);
   float *sd = reinterpret_cast<float *>(cj + 96);  // the slices' lists [slices, kp]
-  const int lane = threadIdx.x, row = blockIdx.x;
+  int row = blockIdx.x, first = 0;  // first: the set's first row
+  if constexpr (SETS) {
+    const int b = row / a.n;
+    rebase_to_set(a, b);
+    first = b * a.n;
+    row -= first;
+  }
+  const int lane = threadIdx.x;
   const int k = a.k, kp = a.kp, n = a.n, L = a.slices * kp;
   int *sj = reinterpret_cast<int *>(sd + L);
 
@@ -608,7 +692,7 @@ __global__ __launch_bounds__(kDotRerankRows) void knn_dot_rerank_kernel(DotArgsT
     }
   }
   if (lane < k) {
-    a.idx[(size_t)row * k + lane] = bj[0];
+    a.idx[(size_t)row * k + lane] = SETS ? bj[0] + first : bj[0];
     a.dist[(size_t)row * k + lane] = bd[0] < 0.f ? 0.f : bd[0];
   }
   if (lane == 0) {
@@ -622,12 +706,25 @@ __global__ __launch_bounds__(kDotRerankRows) void knn_dot_rerank_kernel(DotArgsT
 }
 
 // the row type's prefilter kernel
-template <int KS, typename R>
+template <int KS, bool SETS, typename R>
 void launch_prefilter(const DotArgsT<R> &a, dim3 grid, bool mean, hipStream_t s) {
   void (*kernel)(DotArgsT<R>);
-  if constexpr (sizeof(R) == 4) kernel = mean ? knn_dot_prefilter_kernel<KS, true> : knn_dot_prefilter_kernel<KS, false>;
-  else kernel = mean ? knn_dot_prefilter_bf16_kernel<KS, true> : knn_dot_prefilter_bf16_kernel<KS, false>;
+  if constexpr (sizeof(R) == 4) kernel = mean ? knn_dot_prefilter_kernel<KS, true, SETS> : knn_dot_prefilter_kernel<KS, false, SETS>;
+  else kernel = mean ? knn_dot_prefilter_bf16_kernel<KS, true, SETS> : knn_dot_prefilter_bf16_kernel<KS, false, SETS>;
   hipLaunchKernelGGL(kernel, grid, dim3(kDotBlock), 0, s, a);
+}
+
+// the prefilter of the shortlist depth kp and the rerank, over `groups` query tiles and `rows` rows
+template <bool SETS, typename R>
+void launch_search(const DotArgsT<R> &a, unsigned groups, unsigned rows, hipStream_t s) {
+  const dim3 grid(groups, (unsigned)a.slices);
+  const bool mean = a.mean != nullptr;
+  const int ks = (a.kp + 31) / 32;
+  if (ks == 1) launch_prefilter<1, SETS>(a, grid, mean, s);
+  else if (ks == 2) launch_prefilter<2, SETS>(a, grid, mean, s);
+  else launch_prefilter<3, SETS>(a, grid, mean, s);
+  const size_t lds = (size_t)(kDotRerankRows * (kDotRerankRows + 1) + kDotRerankRows + 2 * 96) * 4 + (size_t)a.slices * a.kp * 8;
+  hipLaunchKernelGGL((knn_dot_rerank_kernel<R, SETS>), dim3(rows), dim3(kDotRerankRows), lds, s, a);
 }
 
 // The norms of the candidates, their maximum and (Q != X) the norms of the query rows, into a's n2x / n2max / n2q; bmax is
@@ -687,14 +784,59 @@ int knn_dot_run(const char *entry, const char *ws_entry, const R *Q, int32_t nq,
   a.fallback = fallback;
 
   launch_norms(a, reinterpret_cast<float *>(ws + L.bmax), s);
-  const dim3 grid((unsigned)((nq + kDotTQ - 1) / kDotTQ), (unsigned)slices);
-  const bool mean = mean_dist != nullptr;
-  const int ks = (L.kp + 31) / 32;
-  if (ks == 1) launch_prefilter<1>(a, grid, mean, s);
-  else if (ks == 2) launch_prefilter<2>(a, grid, mean, s);
-  else launch_prefilter<3>(a, grid, mean, s);
-  const size_t lds = (size_t)(kDotRerankRows * (kDotRerankRows + 1) + kDotRerankRows + 2 * 96) * 4 + (size_t)slices * L.kp * 8;
-  hipLaunchKernelGGL(knn_dot_rerank_kernel<R>, dim3((unsigned)nq), dim3(kDotRerankRows), lds, s, a);
+  launch_search<false>(a, (unsigned)((nq + kDotTQ - 1) / kDotTQ), (unsigned)nq, s);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail(entry, HG_ERR_HIP, std::string("launch: ") + hipGetErrorString(e));
+  return HG_OK;
+}
+
+// hg_knn_dot_sets_f32 and hg_knn_dot_sets_bf16: B = n / set_rows sets, each searched as a problem of its own by the SETS
+// instances.  Four launches: the norms, the sets' norm maxima, the prefilter, the rerank.
+template <typename R>
+int knn_dot_sets_run(const char *entry, const R *X, int32_t n, int32_t F, int32_t k, int32_t set_rows, int32_t self_first,
+                     int32_t cand_slices, int32_t *idx, float *dist, float *mean_dist, int32_t *fallback, void *workspace,
+                     size_t workspace_bytes, hg_stream_t stream) {
+  if (const int st = knn_refusal({entry, X, X, idx, dist, n, n, F, k, self_first, cand_slices}, kDotMaxF, nullptr, 0)) return st;
+  if (const int st = knn_sets_refusal(entry, n, k, set_rows)) return st;
+  if (sizeof(R) == 2 && (uintptr_t)X % 2) return fail(entry, HG_ERR_UNSUPPORTED, "X must be 2-byte aligned");
+  for (const void *p : {sizeof(R) == 4 ? (const void *)X : nullptr, (const void *)idx, (const void *)dist, (const void *)mean_dist,
+                        (const void *)fallback, (const void *)workspace})
+    if ((uintptr_t)p % 4)
+      return fail(entry, HG_ERR_UNSUPPORTED,
+                  std::string(sizeof(R) == 4 ? "X, " : "") + "idx, dist, mean_dist, fallback and the workspace must be 4-byte aligned");
+  const int slices = knn_dot_sets_slices(n, set_rows, cand_slices);
+  const KnnDotLayout L = knn_dot_sets_layout(n, set_rows, k, slices);
+  if (!workspace || workspace_bytes < L.total)
+    return fail(entry, HG_ERR_WORKSPACE, "workspace of " + std::to_string(workspace_bytes) +
+                                             " bytes, hg_knn_dot_sets_workspace_bytes asks for " + std::to_string(L.total));
+
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  unsigned char *ws = static_cast<unsigned char *>(workspace);
+  const int32_t B = n / set_rows;
+  DotArgsT<R> a{};  // one set's sizes, the whole call's arrays (rebase_to_set)
+  a.Q = a.X = X;
+  a.nq = a.n = set_rows;
+  a.F = F;
+  a.k = k;
+  a.kp = L.kp;
+  a.slices = slices;
+  a.self_first = self_first ? 1 : 0;
+  a.same = 1;
+  a.n2x = a.n2q = reinterpret_cast<float *>(ws + L.n2x);
+  a.n2max = reinterpret_cast<float *>(ws + L.n2max);
+  a.l_idx = reinterpret_cast<int32_t *>(ws + L.idx);
+  a.l_est = reinterpret_cast<float *>(ws + L.est);
+  a.l_mean = mean_dist ? reinterpret_cast<float *>(ws + L.mean) : nullptr;
+  a.idx = idx;
+  a.dist = dist;
+  a.mean = mean_dist;
+  a.fallback = fallback;
+
+  hipLaunchKernelGGL(knn_dot_norm_kernel<R>, dim3((unsigned)((n + kDotNormRows - 1) / kDotNormRows)), dim3(256), 0, s, X, n, F,
+                     const_cast<float *>(a.n2x), (float *)nullptr);
+  hipLaunchKernelGGL(knn_dot_set_max_kernel, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, s, a.n2x, B, set_rows,
+                     const_cast<float *>(a.n2max));
+  launch_search<true>(a, (unsigned)(B * ((set_rows + kDotTQ - 1) / kDotTQ)), (unsigned)n, s);
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail(entry, HG_ERR_HIP, std::string("launch: ") + hipGetErrorString(e));
   return HG_OK;
@@ -726,6 +868,25 @@ int hg_knn_dot_bf16(const uint16_t *Q, int32_t nq, const uint16_t *X, int32_t n,
                     size_t workspace_bytes, hg_stream_t stream) {
   return hg::knn_dot_run("hg_knn_dot_bf16", "hg_knn_dot_bf16_workspace_bytes", Q, nq, X, n, F, k, self_first, cand_slices, idx,
                          dist, mean_dist, fallback, workspace, workspace_bytes, stream);
+}
+
+size_t hg_knn_dot_sets_workspace_bytes(int32_t n, int32_t F, int32_t k, int32_t cand_slices, int32_t set_rows) {
+  if (!hg::knn_sizes_ok(n, n, F, k, cand_slices, hg::kDotMaxF) || set_rows < k || n % set_rows) return 0;
+  return hg::knn_dot_sets_layout(n, set_rows, k, hg::knn_dot_sets_slices(n, set_rows, cand_slices)).total;
+}
+
+int hg_knn_dot_sets_f32(const float *X, int32_t n, int32_t F, int32_t k, int32_t set_rows, int32_t self_first, int32_t cand_slices,
+                        int32_t *idx, float *dist, float *mean_dist, int32_t *fallback, void *workspace, size_t workspace_bytes,
+                        hg_stream_t stream) {
+  return hg::knn_dot_sets_run("hg_knn_dot_sets_f32", X, n, F, k, set_rows, self_first, cand_slices, idx, dist, mean_dist, fallback,
+                              workspace, workspace_bytes, stream);
+}
+
+int hg_knn_dot_sets_bf16(const uint16_t *X, int32_t n, int32_t F, int32_t k, int32_t set_rows, int32_t self_first,
+                         int32_t cand_slices, int32_t *idx, float *dist, float *mean_dist, int32_t *fallback, void *workspace,
+                         size_t workspace_bytes, hg_stream_t stream) {
+  return hg::knn_dot_sets_run("hg_knn_dot_sets_bf16", X, n, F, k, set_rows, self_first, cand_slices, idx, dist, mean_dist, fallback,
+                              workspace, workspace_bytes, stream);
 }
 
 int hg_knn_dot_estimates_bf16(const uint16_t *Q, int32_t nq, const uint16_t *X, int32_t n, int32_t F, float *est, float *e1,

@@ -79,7 +79,7 @@ def _segment_offsets(segments, n, k):
 
 
 def knn(X, k, queries=None, segments=None, self_first=None, return_mean=False, cand_slices=0, form="difference",
-        return_fallback=False):
+        return_fallback=False, set_rows=None):
     """The k nearest rows of X [n, F] for every row of `queries` [nq, F] (None: for every row of X itself), by the squared
     Euclidean distance d2(i, j) = sum_c (Q[i, c] - X[j, c])^2 in float32 -- the difference form, so identical rows are at
     exactly 0 and integer-valued rows give exact distances.  Returns (idx int32 [nq, k], dist float32 [nq, k]) and, with
@@ -111,11 +111,24 @@ def knn(X, k, queries=None, segments=None, self_first=None, return_mean=False, c
     the same arguments; the prefilter runs on the bf16 matrix unit under its own bound E1b (include/hg_aggr.h), mean is
     the mean of those estimates, and everything else above holds.  Under every other form bfloat16 is refused.
 
+    set_rows = m: X is B = n / m point sets of exactly m consecutive rows each -- the batch of equal-sized point clouds of
+    DGCNN / DHGNN -- and row i competes with rows (i // m) * m .. (i // m) * m + m - 1 only (hg_knn_sets_f32,
+    hg_knn_dot_sets_f32 / _bf16).  No offsets exist, on the host or on the device: the call neither waits nor reads back
+    under either form and is recorded by torch.cuda.graph.  idx holds row numbers of X, as segments gives them.  idx and
+    dist are those of knn(X, k, segments=range(0, n + 1, m), form="difference") bit for bit, for the same self_first
+    and cand_slices, under "difference", under "dot" and under "dot" on bfloat16 rows (then: of the call on X.float());
+    m = n is the call without set_rows.  mean: under "difference" the segments call's bits; under "dot" the mean over the
+    row's own set of sqrt(max(d~, 0)), the number above with n replaced by m.  Under "dot" every set is searched as a
+    problem of its own -- kp = min(m, 32 ceil((k + 16) / 32)), the certificate against the largest norm of the row's own
+    set, the exhaustive path over the set -- so a set far from the origin costs the others nothing; a set of fewer than
+    128 rows still takes a whole 128-row workgroup of the prefilter.
+
     Not differentiable: raises if X (or queries) requires a gradient while grad mode is on; call it under
     torch.no_grad() or on X.detach().  Refusals, in this order and before a device is touched: TypeError for anything
     but float32 (or, under form="dot", bfloat16 for X and queries alike); ValueError for an unknown form, for k outside
     1 .. min(64, n), for segments or self_first together with queries, for form="dot" with segments or with F above
-    65536, for a segment shorter than k; RuntimeError for CPU tensors."""
+    65536, for a segment shorter than k, for cand_slices, and then for set_rows: not an integer, k above it, n no
+    multiple of it, together with queries or with segments; RuntimeError for CPU tensors."""
     bf16 = form == "dot" and isinstance(X, torch.Tensor) and X.dtype == torch.bfloat16
     if bf16:
         if queries is not None and not (isinstance(queries, torch.Tensor) and queries.dtype == torch.bfloat16):
@@ -151,6 +164,18 @@ def knn(X, k, queries=None, segments=None, self_first=None, return_mean=False, c
     seg = None if segments is None else _segment_offsets(segments, n, k)
     if not isinstance(cand_slices, numbers.Integral) or isinstance(cand_slices, bool) or not 0 <= cand_slices <= SLICES_MAX:
         raise ValueError("cand_slices must be 0 (auto) or 1 .. %d, got %r" % (SLICES_MAX, cand_slices))
+    if set_rows is not None:
+        if not isinstance(set_rows, numbers.Integral) or isinstance(set_rows, bool):
+            raise ValueError("set_rows must be an integer (the rows of every point set), got %r" % (set_rows,))
+        if not k <= set_rows:
+            raise ValueError("k = %d exceeds the set_rows = %d rows of a set" % (k, set_rows))
+        if n % set_rows:
+            raise ValueError("the %d rows of X are no multiple of set_rows = %d" % (n, set_rows))
+        if queries is not None:
+            raise ValueError("set_rows cannot be combined with queries (a set is a range of rows of X itself)")
+        if segments is not None:
+            raise ValueError("set_rows cannot be combined with segments (uniform sets need no offsets)")
+        set_rows = int(set_rows)
     if torch.is_grad_enabled() and (X.requires_grad or (queries is not None and queries.requires_grad)):
         raise RuntimeError("knn is not differentiable: call it under torch.no_grad() or on X.detach()")
     _check_feat(X, "X", bf16_ok=bf16)
@@ -165,7 +190,25 @@ def knn(X, k, queries=None, segments=None, self_first=None, return_mean=False, c
     idx = torch.empty((nq, k), dtype=torch.int32, device=dev)
     dist = torch.empty((nq, k), dtype=torch.float32, device=dev)
     mean = torch.empty(nq, dtype=torch.float32, device=dev) if return_mean else None
-    if form == "dot":
+    if set_rows is not None:  # the sets entries: X alone, no offsets
+        if not hasattr(L, "hg_knn_sets_f32"):
+            raise RuntimeError("this build of libhgaggr has no hg_knn_sets_f32 (set_rows)")
+        if form == "dot":
+            fallback = torch.empty(nq, dtype=torch.int32, device=dev) if return_fallback else None
+            entry = L.hg_knn_dot_sets_bf16 if bf16 else L.hg_knn_dot_sets_f32
+            ws_bytes = L.hg_knn_dot_sets_workspace_bytes(n, F, k, cand_slices, set_rows)
+            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+            with torch.cuda.device(dev):
+                _lib.check(entry(_ptr(X), n, F, k, set_rows, 1 if self_first else 0, cand_slices, _ptr(idx), _ptr(dist),
+                                 _ptr(mean), _ptr(fallback), _ptr(ws), ws_bytes, _stream_handle(dev)))
+        else:
+            ws_bytes = L.hg_knn_workspace_bytes(n, n, F, k, cand_slices)
+            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev) if ws_bytes else None
+            with torch.cuda.device(dev):
+                _lib.check(L.hg_knn_sets_f32(_ptr(X), n, F, k, set_rows, 1 if self_first else 0, cand_slices, _ptr(idx),
+                                             _ptr(dist), _ptr(mean), _ptr(ws), ws_bytes, _stream_handle(dev)))
+            fallback = torch.zeros(nq, dtype=torch.int32, device=dev) if return_fallback else None
+    elif form == "dot":
         fallback = torch.empty(nq, dtype=torch.int32, device=dev) if return_fallback else None
         if bf16 and not hasattr(L, "hg_knn_dot_bf16"):
             raise RuntimeError("this build of libhgaggr has no hg_knn_dot_bf16 (bfloat16 rows under form=\"dot\")")
@@ -1113,7 +1156,8 @@ def knn_aggr(idx, X, weight=None, degE=None, degV=None, transpose=None, weight_g
 class KnnHypergraph:
     """The hypergraph "each vertex and its k - 1 nearest neighbours" as a device-only object: what HyperGraph.from_knn builds,
     without the read-back, the host transpose and the plan.  Nothing here reads a tensor back; with segments=None nothing
-    waits for the device either (ops.knn waits once for its segment offsets).
+    waits for the device either (ops.knn waits once for its segment offsets; with set_rows, ops.knn's uniform sets, there
+    are no offsets and nothing waits).
       idx [N, k], dist [N, k] (squared), mean [N]: ops.knn(X, k, self_first=True, return_mean=True)
       ptr_v [N + 1], pos_v [N k]: ops.knn_transpose(idx)
       degE [N, 1] = 1 / k and degV [N, 1] = in-degree^-1/2, 1 where no hyperedge names the vertex (HyperGraph's formulas)
@@ -1133,11 +1177,12 @@ class KnnHypergraph:
     bfloat16 rows, the weights float32."""
 
     @classmethod
-    def build(cls, X, k, segments=None, form="difference"):
+    def build(cls, X, k, segments=None, form="difference", set_rows=None):
         self = cls.__new__(cls)
         if isinstance(X, torch.Tensor):  # anything else is ops.knn's refusal
             X = X.detach().contiguous()
-        self.idx, self.dist, self.mean = knn(X, k, segments=segments, self_first=True, return_mean=True, form=form)
+        self.idx, self.dist, self.mean = knn(X, k, segments=segments, self_first=True, return_mean=True, form=form,
+                                            set_rows=set_rows)
         N = self.idx.shape[0]
         self.k, self.num_nodes, self.num_edges, self.nnz = int(k), N, N, N * int(k)
         self.device = self.idx.device

@@ -146,9 +146,14 @@ class DynamicHypergraphConv(nn.Module):
     planned operators; `hyperg` is then the KnnHypergraph.  The same layer, parameter for parameter, and the same sums in
     another order.  With segments=None a forward and backward then waits for the device nowhere and allocates only through
     torch, so the layer can be recorded into a hipGraph (torch.cuda.graph) and the neighbours are searched again on every
-    replay.  With segments, ops.knn still waits once for its offsets: such a layer runs eagerly only.  False (the default)
-    is the layer above, untouched.  knn_form: ops.knn's `form` -- "dot" searches the same neighbours through the
+    replay.  With segments, ops.knn still waits once for its offsets: a layer with segments runs eagerly only.  False (the
+    default) is the layer above, untouched.  knn_form: ops.knn's `form` -- "dot" searches the same neighbours through the
     matrix-unit prefilter (no segments); with probabilistic=True the weights then use the dot form's mean.
+    set_rows = m: ops.knn's -- the input is a batch of N / m point sets of exactly m rows each, every set its own hypergraph,
+    with no offsets anywhere.  Wherever this text says "with segments=None" it holds with set_rows too: under
+    device_graph=True the layer waits nowhere and is recorded into a hipGraph, replaying the search -- float32 under either
+    knn_form, bfloat16 under knn_form="dot" -- with attention, heads, max / min and learn_distances, which work on any table.
+    Exclusive with segments (ops.knn's refusal, at the first forward).  None (the default) is the layer above.
     learn_distances=True (needs probabilistic=True and device_graph=True): the weights exp(-d2 / (m_prob mean)^2) are
     differentiated through d2 = ops.knn_dist(idx, X), so the gradient of X gains the path through the weights of both hops
     -- what a learnable metric needs.  The output keeps its bits; the table is still searched on detached rows (the
@@ -187,7 +192,7 @@ class DynamicHypergraphConv(nn.Module):
 
     def __init__(self, in_channels, out_channels, k, probabilistic=False, segments=None, m_prob=1.0, options=None,
                  device_graph=False, knn_form="difference", learn_distances=False, first_aggr="sum", second_aggr="sum",
-                 attention=None, negative_slope=0.2, heads=1, concat=True):
+                 attention=None, negative_slope=0.2, heads=1, concat=True, set_rows=None):
         super().__init__()
         if isinstance(heads, bool) or not isinstance(heads, int) or heads < 1:
             raise ValueError("heads must be an integer >= 1, got %r" % (heads,))
@@ -213,7 +218,7 @@ class DynamicHypergraphConv(nn.Module):
         self.in_channels, self.out_channels, self.k = in_channels, out_channels, k
         self.probabilistic, self.segments, self.m_prob = probabilistic, segments, m_prob
         self.device_graph = bool(device_graph)
-        self.knn_form = knn_form
+        self.knn_form, self.set_rows = knn_form, set_rows
         self.hyperg = None
         if attention not in (None, "hyperedge", "vertex"):
             raise ValueError("attention must be None, 'hyperedge' or 'vertex', got %r" % (attention,))
@@ -235,7 +240,7 @@ class DynamicHypergraphConv(nn.Module):
         from .knn_graph import KnnHypergraph, knn_gather
         if X.dtype != torch.float32:
             raise TypeError("attention=%r takes float32 rows (ops.knn_softmax has no bfloat16 form), got %s" % (self.attention, X.dtype))
-        hyperg = self.hyperg = KnnHypergraph.build(X, self.k, segments=self.segments, form=self.knn_form)
+        hyperg = self.hyperg = KnnHypergraph.build(X, self.k, segments=self.segments, form=self.knn_form, set_rows=self.set_rows)
         Z = self.lin(X)
         transpose = (hyperg.ptr_v, hyperg.pos_v)
         if self.heads > 1:
@@ -257,7 +262,7 @@ class DynamicHypergraphConv(nn.Module):
             return self._attention_forward(X)
         if self.device_graph:
             from .knn_graph import KnnHypergraph
-            hyperg = self.hyperg = KnnHypergraph.build(X, self.k, segments=self.segments, form=self.knn_form)
+            hyperg = self.hyperg = KnnHypergraph.build(X, self.k, segments=self.segments, form=self.knn_form, set_rows=self.set_rows)
             Z = self.lin(X)
             options = self.options
             if Z.dtype == torch.bfloat16:  # bfloat16 rows for the layer's own table calls; the weights stay float32
@@ -268,7 +273,8 @@ class DynamicHypergraphConv(nn.Module):
                 return hyperg.aggregate(Z, options=options, first=self.first_aggr, second=self.second_aggr)
             return hyperg.aggregate(Z, probabilistic=self.probabilistic, m_prob=self.m_prob, options=options)
         from .hypergraph import HyperGraph
-        hyperg = self.hyperg = HyperGraph.from_knn(X.detach(), self.k, X.device, segments=self.segments, form=self.knn_form)
+        hyperg = self.hyperg = HyperGraph.from_knn(X.detach(), self.k, X.device, segments=self.segments, form=self.knn_form,
+                                                      set_rows=self.set_rows)
         Z = self.lin(X)
         if not self.sums:
             return ops.reduce_aggr(hyperg.H_T_csrptr, hyperg.H_T_colind, Z, self.first_aggr, self.second_aggr, hyperg.degE,

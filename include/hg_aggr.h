@@ -921,6 +921,47 @@ HG_API size_t hg_knn_dot_bf16_workspace_bytes(int32_t nq, int32_t n, int32_t F, 
 HG_API int hg_knn_dot_estimates_bf16(const uint16_t *Q, int32_t nq, const uint16_t *X, int32_t n, int32_t F, float *est,
                                      float *e1, hg_stream_t stream);
 
+/* UNIFORM SETS: X [n, F] is B = n / set_rows point sets of exactly set_rows = m consecutive rows each, and row i competes
+ * with rows (i / m) m .. (i / m) m + m - 1 only (Q is X).  There is no offsets array, on the host or on the device: nothing
+ * is copied and nothing is waited for under either form, and every entry is recordable into a hipGraph.  idx holds row
+ * numbers of X (not of the set), as seg gives them.
+ *
+ * hg_knn_sets_f32 (csrc/hg_knn.hip): hg_knn_f32(X, n, X, n, .., seg = {0, m, 2 m, .. n}, B, ..) without seg -- the same
+ * kernels, the same tiles and slices, the row's range computed from i and m.  idx, dist and mean_dist are that call's BIT
+ * FOR BIT for the same self_first and cand_slices; m == n is hg_knn_f32 without seg.  workspace:
+ * hg_knn_workspace_bytes(n, n, F, k, cand_slices); it may be NULL where one slice runs (cand_slices 1, or 0 where
+ * hg_knn_f32 would pick 1).
+ *
+ * hg_knn_dot_sets_f32 / hg_knn_dot_sets_bf16 (csrc/hg_knn_dot.hip): hg_knn_dot_f32 / hg_knn_dot_bf16 on every set as a
+ * problem of its own, in one call.  idx and dist are hg_knn_sets_f32's (for bfloat16 rows: on the rows widened to float32)
+ * BIT FOR BIT.  Everything said of hg_knn_dot_f32 / hg_knn_dot_bf16 holds with n and nq replaced by m:
+ *   kp = min(m, 32 ceil((k + 16) / 32)); a workgroup of the prefilter owns 128 rows of ONE set (ceil(m / 128) workgroups a
+ *   set, the last partly empty; sets never share a workgroup) and its candidate tiles are cut from the set's first row, so
+ *   an estimate's bits are those of the single-set call; the slice count is the single call's rule for B ceil(m / 128)
+ *   workgroups and ceil(m / 128) candidate tiles;
+ *   the certificate of row i uses the norm maximum of ITS OWN SET, E1 (E1b) = C u (n2[i] + max_{j in set} n2[j]) + .. --
+ *   the formulas are unchanged, they depend on F and the two norms only -- so a set far from the origin costs the other
+ *   sets nothing; a row is certified iff its k-th d2 is strictly below T - Ei, or m <= kp; a row that is not certified is
+ *   searched over the m rows of its set; fallback[i] as above, and for every set it is what the single call on the set gives;
+ *   mean_dist[i] = the float32 mean over the m rows of the set of sqrt(max(d~(i, j), 0)), the pair (i, i) exactly 0, in
+ *   the bits of the single call on the set with the same slice count.
+ * workspace: hg_knn_dot_sets_workspace_bytes(n, F, k, cand_slices, set_rows), always needed: 4 (n + B) + slices n (8 kp + 4)
+ * + 1280 at the most.  It returns 0 for arguments the entries refuse.  Four launches: the norms, one wave per set for the
+ * sets' norm maxima, the prefilter, the rerank.  No atomics: two calls give the same bits.
+ * Refusals of all three: their single-set sibling's up to cand_slices > 32, in its order (with Q = X, nq = n); then
+ * HG_ERR_INVALID for set_rows < 1, for n % set_rows != 0, for set_rows < k; then the sibling's HG_ERR_UNSUPPORTED for a
+ * misaligned pointer and HG_ERR_WORKSPACE. */
+HG_API int hg_knn_sets_f32(const float *X, int32_t n, int32_t F, int32_t k, int32_t set_rows, int32_t self_first,
+                           int32_t cand_slices, int32_t *idx, float *dist, float *mean_dist, void *workspace,
+                           size_t workspace_bytes, hg_stream_t stream);
+HG_API int hg_knn_dot_sets_f32(const float *X, int32_t n, int32_t F, int32_t k, int32_t set_rows, int32_t self_first,
+                               int32_t cand_slices, int32_t *idx, float *dist, float *mean_dist, int32_t *fallback,
+                               void *workspace, size_t workspace_bytes, hg_stream_t stream);
+HG_API int hg_knn_dot_sets_bf16(const uint16_t *X, int32_t n, int32_t F, int32_t k, int32_t set_rows, int32_t self_first,
+                                int32_t cand_slices, int32_t *idx, float *dist, float *mean_dist, int32_t *fallback,
+                                void *workspace, size_t workspace_bytes, hg_stream_t stream);
+HG_API size_t hg_knn_dot_sets_workspace_bytes(int32_t n, int32_t F, int32_t k, int32_t cand_slices, int32_t set_rows);
+
 /* Aggregation over a dense neighbour table, with no plan (csrc/hg_table.hip).  idx [rows, k] int32 is what hg_knn_f32
  * writes: hyperedge i has the k members idx[i, 0 .. k - 1], so H_T is the table itself (csrptr_t an arange) and position
  * p = i k + s of the table is entry s of hyperedge i.  1 <= k <= 64 and rows * k < 2^31.  None of the three entries
