@@ -13,6 +13,14 @@
 // A vertex segment of more than HG_TABLE_SEQ_MAX entries is taken by the whole workgroup, slab after slab, in the same
 // launch.  No workspace, no atomics, no host list.
 //
+// Attention dropout (DROP, the hg_table_softmax_dropout_*_heads_f32 entries): a compile-time variant of the softmax and of its
+// backward -- the same ownership, lanes, passes and reductions, so alpha, ds and dgroup keep their bits.  The mask of
+// hg_philox.h is a function of (rng, p, h) alone.  A thread loads the two state words once, ahead of every segment.  The
+// forward forms the mask only in its store pass, once per candidate (p, h), beside the alpha it scales: the maximum and sum
+// passes know nothing of it.  The backward of a short segment masks dout where it loads it, into the registers that already
+// hold the entry across the two passes -- one Philox per candidate (p, h); a long workgroup segment keeps no entries, so it
+// forms the mask again in its second pass.  Non-candidates run no Philox: their lanes are off where it is computed.
+//
 // Gathers: table_gather_kernel's shape (16-byte lanes, kTableBatch row loads in flight, long rows through the LDS tree in
 // the pieces the plain call has at the same F), the one weight per entry replaced by the weight of the lane's own head:
 // w[p, c / Ch].  A 16-byte lane whose four columns share a head (Ch % 4 == 0) loads one weight an entry; one that straddles
@@ -27,10 +35,12 @@
 #include <cmath>
 #include <initializer_list>
 #include <string>
+#include <type_traits>
 
 #include "hg_aggr.h"
 #include "hg_attention.h"
 #include "hg_internal.h"
+#include "hg_philox.h"
 #include "hg_table.h"
 
 namespace hg {
@@ -78,6 +88,10 @@ struct HeadsSoftmaxArgs {
   const float *val, *dval;           // backward: alpha and dalpha; sum: the summed values; [rows k, H]
   float *out_entry;                  // softmax: alpha; backward: ds; [rows k, H]
   float *out_seg;                    // backward: the segments' own sums of ds, or null; sum: out; [segments, H]
+  const uint64_t *rng;               // dropout: {key, sid} in device memory, read when the kernel runs
+  float *out_drop;                   // dropout, softmax: alpha after dropout; [rows k, H]
+  uint32_t T;                        // dropout: an entry is kept where its Philox word >= T = floor(p_drop * 2^32)
+  float scale;                       // dropout: 1 / (1 - p_drop), rounded once on the host
   float slope;
   int32_t rows, k, n, entries, nseg, H;
   int32_t L, R;                      // lanes per segment, segments per wave
@@ -164,11 +178,28 @@ __device__ __forceinline__ void block_join(float (&v)[HV], float (*slot)[kTableW
   buf ^= 1;
 }
 
+// The dropout of a launch as a thread holds it: the state words, loaded once
+struct NoDrop {};
+struct Drop {
+  DropRng rng;
+  uint32_t T;
+  float scale;
+};
+
+// v, the heads h0 .. h0 + HV - 1 of table position p, as dropout leaves it: fl(v * scale) where kept, else +0.  The caller
+// runs it for candidates only.
+template <int HV>
+__device__ __forceinline__ void drop_slab(const Drop &d, int p, int h0, float (&v)[HV]) {
+#pragma unroll
+  for (int i = 0; i < HV; ++i) v[i] = drop_keep(d.rng, d.T, (uint32_t)p, (uint32_t)(h0 + i)) ? v[i] * d.scale : 0.f;
+}
+
 // The heads h0 .. h0 + HV - 1 of the segment a lane group owns whole: entries [beg, end) (none where the group is off),
 // lane cl of L takes beg + cl + u L.  Every lane of the wave runs this, for the shuffles; NS: the entries a lane can hold.
-template <int SIDE, int BODY, int NS, int HV>
-__device__ __forceinline__ void group_segment(const HeadsSoftmaxArgs &a, int h0, int seg, bool act, int beg, int end, int L,
-                                              int cl) {
+template <int SIDE, int BODY, int NS, int HV, typename DROP>
+__device__ __forceinline__ void group_segment(const HeadsSoftmaxArgs &a, const DROP &drop, int h0, int seg, bool act, int beg,
+                                              int end, int L, int cl) {
+  constexpr bool kDrop = std::is_same_v<DROP, Drop>;
   const int len = end - beg;
   const size_t H = (size_t)a.H;
   const float *own_score = SIDE ? a.node : a.edge;
@@ -223,6 +254,14 @@ __device__ __forceinline__ void group_segment(const HeadsSoftmaxArgs &a, int h0,
       } else if (on) {
         vec_store<HV>(a.out_entry + (size_t)(beg + cl + u * L) * H + h0, o4);
       }
+      if constexpr (kDrop) {  // the mask: here and nowhere else, once per candidate (p, h); o4 is +0 elsewhere
+        if (pp[u] >= 0) drop_slab<HV>(drop, pp[u], h0, o4);
+        if (SIDE) {
+          if (pp[u] >= 0) vec_store<HV>(a.out_drop + (size_t)pp[u] * H + h0, o4);
+        } else if (on) {
+          vec_store<HV>(a.out_drop + (size_t)(beg + cl + u * L) * H + h0, o4);
+        }
+      }
     }
   } else if constexpr (BODY == kBodySoftmaxBwd) {
     float av[NS][HV], dv[NS][HV], gv[NS][HV], dot[HV], dsum[HV], o4[HV];
@@ -235,7 +274,11 @@ __device__ __forceinline__ void group_segment(const HeadsSoftmaxArgs &a, int h0,
       int p, j;
       const bool ok = seg_entry<SIDE>(a, beg + cl + u * L, on, p, j);
       const Vec<HV> raw = seg_raw<SIDE, HV>(a, own, p, j, h0);
-      const Vec<HV> al = vec_load<HV>(a.val + (size_t)p * H + h0), da = vec_load<HV>(a.dval + (size_t)p * H + h0);
+      const Vec<HV> al = vec_load<HV>(a.val + (size_t)p * H + h0);
+      Vec<HV> da = vec_load<HV>(a.dval + (size_t)p * H + h0);
+      if constexpr (kDrop) {  // dalpha = keep ? fl(dout * scale) : +0, kept in dv for both passes
+        if (ok) drop_slab<HV>(drop, p, h0, da.v);
+      }
       pp[u] = ok ? p : -1;
 #pragma unroll
       for (int i = 0; i < HV; ++i) {
@@ -289,9 +332,10 @@ __device__ __forceinline__ void group_segment(const HeadsSoftmaxArgs &a, int h0,
 
 // The heads h0 .. h0 + HV - 1 of one side-1 segment of more than HG_TABLE_SEQ_MAX entries, by the whole workgroup: thread
 // t takes beg + t, beg + t + 256 .. and gathers its logits again in every pass.
-template <int BODY, int HV>
-__device__ __forceinline__ void block_segment(const HeadsSoftmaxArgs &a, int h0, int seg, int beg, int end, int t,
-                                              float (*slot)[kTableWaves][kMaxHV], int &buf) {
+template <int BODY, int HV, typename DROP>
+__device__ __forceinline__ void block_segment(const HeadsSoftmaxArgs &a, const DROP &drop, int h0, int seg, int beg, int end,
+                                              int t, float (*slot)[kTableWaves][kMaxHV], int &buf) {
+  constexpr bool kDrop = std::is_same_v<DROP, Drop>;
   const int w = t >> 6, lane = t & 63;
   const unsigned len = (unsigned)(end - beg);
   const size_t H = (size_t)a.H;
@@ -329,6 +373,12 @@ __device__ __forceinline__ void block_segment(const HeadsSoftmaxArgs &a, int h0,
 #pragma unroll
       for (int i = 0; i < HV; ++i) o4[i] = __expf(leaky(raw.v[i], a.slope) - m[i]) * inv[i];
       if (ok) vec_store<HV>(a.out_entry + (size_t)p * H + h0, o4);
+      if constexpr (kDrop) {
+        if (ok) {
+          drop_slab<HV>(drop, p, h0, o4);
+          vec_store<HV>(a.out_drop + (size_t)p * H + h0, o4);
+        }
+      }
     }
   } else if constexpr (BODY == kBodySoftmaxBwd) {
     float dot[HV], dsum[HV], o4[HV];
@@ -336,7 +386,11 @@ __device__ __forceinline__ void block_segment(const HeadsSoftmaxArgs &a, int h0,
     for (int i = 0; i < HV; ++i) dot[i] = 0.f;
     for (unsigned o = t; o < len; o += kSoftBlock) {
       const bool ok = seg_entry<1>(a, beg + (int)o, true, p, j);
-      const Vec<HV> al = vec_load<HV>(a.val + (size_t)p * H + h0), da = vec_load<HV>(a.dval + (size_t)p * H + h0);
+      const Vec<HV> al = vec_load<HV>(a.val + (size_t)p * H + h0);
+      Vec<HV> da = vec_load<HV>(a.dval + (size_t)p * H + h0);
+      if constexpr (kDrop) {
+        if (ok) drop_slab<HV>(drop, p, h0, da.v);
+      }
 #pragma unroll
       for (int i = 0; i < HV; ++i) {
         const float term = al.v[i] * da.v[i];
@@ -349,7 +403,11 @@ __device__ __forceinline__ void block_segment(const HeadsSoftmaxArgs &a, int h0,
     for (unsigned o = t; o < len; o += kSoftBlock) {
       const bool ok = seg_entry<1>(a, beg + (int)o, true, p, j);
       const Vec<HV> raw = seg_raw<1, HV>(a, own, p, j, h0);
-      const Vec<HV> al = vec_load<HV>(a.val + (size_t)p * H + h0), da = vec_load<HV>(a.dval + (size_t)p * H + h0);
+      const Vec<HV> al = vec_load<HV>(a.val + (size_t)p * H + h0);
+      Vec<HV> da = vec_load<HV>(a.dval + (size_t)p * H + h0);
+      if constexpr (kDrop) {  // no entry is kept between the passes of a long segment: the mask is formed again
+        if (ok) drop_slab<HV>(drop, p, h0, da.v);
+      }
 #pragma unroll
       for (int i = 0; i < HV; ++i) {
         const float g = raw.v[i] > 0.f ? 1.f : a.slope;
@@ -378,19 +436,25 @@ __device__ __forceinline__ void block_segment(const HeadsSoftmaxArgs &a, int h0,
   }
 }
 
-template <int SIDE, int BODY, int HV>
+template <int SIDE, int BODY, int HV, bool DROP = false>
 __global__ __launch_bounds__(kSoftBlock) void table_softmax_heads_kernel(HeadsSoftmaxArgs a) {
   const int t = threadIdx.x, w = t >> 6, lane = t & 63;
   const int L = a.L, R = a.R, H = a.H;
   const int sub = lane / L, cl = lane - sub * L;
   const int RW = R * kTableWaves;
+  using DropT = std::conditional_t<DROP, Drop, NoDrop>;
+  DropT drop{};
+  if constexpr (DROP) drop = Drop{drop_rng(a.rng[0], a.rng[1]), a.T, a.scale};  // both state words, once per thread
 
   if constexpr (SIDE == 1 && BODY != kBodySum) {
     // the positions no vertex owns, every head of them: this workgroup's slice of the table
     const int64_t chunk = ((int64_t)a.entries + gridDim.x - 1) / gridDim.x;
     const int64_t pb = (int64_t)blockIdx.x * chunk, pe = min(pb + chunk, (int64_t)a.entries);
     for (int64_t e = pb * H + t; e < pe * H; e += kSoftBlock)
-      if ((unsigned)a.idx[e / H] >= (unsigned)a.n) a.out_entry[e] = 0.f;
+      if ((unsigned)a.idx[e / H] >= (unsigned)a.n) {
+        a.out_entry[e] = 0.f;
+        if constexpr (DROP && BODY == kBodySoftmax) a.out_drop[e] = 0.f;
+      }
   }
 
   const int64_t seg0 = (int64_t)blockIdx.x * RW;
@@ -402,7 +466,7 @@ __global__ __launch_bounds__(kSoftBlock) void table_softmax_heads_kernel(HeadsSo
   const bool is_long = SIDE == 1 && end - beg > kTableSeqMax;
   const bool act = seg_on && !is_long;
   for (int h0 = 0; h0 < H; h0 += HV)
-    group_segment<SIDE, BODY, SIDE ? kSoftKeep : 1, HV>(a, h0, seg, act, beg, act ? end : beg, L, cl);
+    group_segment<SIDE, BODY, SIDE ? kSoftKeep : 1, HV>(a, drop, h0, seg, act, beg, act ? end : beg, L, cl);
 
   if constexpr (SIDE == 1) {
     __shared__ float slot[2][kTableWaves][kMaxHV];
@@ -421,7 +485,7 @@ __global__ __launch_bounds__(kSoftBlock) void table_softmax_heads_kernel(HeadsSo
         const int lseg = (int)(seg0 + ww * R + ln / L);
         int lbeg, lend;
         seg_range<1>(a, lseg, lbeg, lend);
-        for (int h0 = 0; h0 < H; h0 += HV) block_segment<BODY, HV>(a, h0, lseg, lbeg, lend, t, slot, buf);
+        for (int h0 = 0; h0 < H; h0 += HV) block_segment<BODY, HV>(a, drop, h0, lseg, lbeg, lend, t, slot, buf);
       }
     }
   }
@@ -439,20 +503,20 @@ bool aligned16(std::initializer_list<const void *> arrays) {
   return true;
 }
 
-template <int BODY>
+template <int BODY, bool DROP = false>
 int launch_softmax_heads(const char *entry, int side, HeadsSoftmaxArgs a, hg_stream_t stream) {
   a.entries = a.rows * a.k;
   a.nseg = side ? a.n : a.rows;
   a.L = side ? std::max(kSoftMinL, pow2_at_least(a.k)) : pow2_at_least(a.k);  // the single-head call's, per head
   a.R = 64 / a.L;
   const int RW = a.R * kTableWaves;
-  const bool slab4 = a.H % 4 == 0 && aligned16({a.node, a.edge, a.entry, a.val, a.dval, a.out_entry, a.out_seg});
+  const bool slab4 = a.H % 4 == 0 && aligned16({a.node, a.edge, a.entry, a.val, a.dval, a.out_entry, a.out_seg, a.out_drop});
   const dim3 grid((unsigned)(((int64_t)a.nseg + RW - 1) / RW)), block(kSoftBlock);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (side && slab4) hipLaunchKernelGGL((table_softmax_heads_kernel<1, BODY, 4>), grid, block, 0, s, a);
-  else if (side) hipLaunchKernelGGL((table_softmax_heads_kernel<1, BODY, 1>), grid, block, 0, s, a);
-  else if (slab4) hipLaunchKernelGGL((table_softmax_heads_kernel<0, BODY, 4>), grid, block, 0, s, a);
-  else hipLaunchKernelGGL((table_softmax_heads_kernel<0, BODY, 1>), grid, block, 0, s, a);
+  if (side && slab4) hipLaunchKernelGGL((table_softmax_heads_kernel<1, BODY, 4, DROP>), grid, block, 0, s, a);
+  else if (side) hipLaunchKernelGGL((table_softmax_heads_kernel<1, BODY, 1, DROP>), grid, block, 0, s, a);
+  else if (slab4) hipLaunchKernelGGL((table_softmax_heads_kernel<0, BODY, 4, DROP>), grid, block, 0, s, a);
+  else hipLaunchKernelGGL((table_softmax_heads_kernel<0, BODY, 1, DROP>), grid, block, 0, s, a);
   return launch_check(entry);
 }
 
@@ -462,13 +526,24 @@ int heads_refusal(const char *entry, int32_t heads) {
 }
 
 // what the three entries refuse, in the single-head entries' order with the heads after the sizes
+struct DropCall {  // what a dropout entry adds to the call
+  float p_drop;
+  const uint64_t *rng_dev;
+};
+
+// drop (the dropout entries; else null): p_drop and the state's address, after the null pointers and before the sizes
 int softmax_refusal(const char *entry, const int32_t *idx, int32_t rows, int32_t k, int32_t n, int32_t heads, int32_t side,
                     const char *side_name, const int32_t *ptr_v, const int32_t *pos_v, bool arrays_given, const char *null_text,
-                    std::initializer_list<const void *> arrays) {
+                    std::initializer_list<const void *> arrays, const DropCall *drop = nullptr) {
   if (!idx) return fail(entry, HG_ERR_INVALID, "null idx");
   if (!arrays_given) return fail(entry, HG_ERR_INVALID, null_text);
   if (side == HG_TABLE_VERTEX && (!ptr_v || !pos_v))
     return fail(entry, HG_ERR_INVALID, std::string("null ptr_v or pos_v (") + side_name + " = HG_TABLE_VERTEX walks the transpose)");
+  if (drop) {
+    if (!(drop->p_drop >= 0.f && drop->p_drop < 1.f))  // NaN fails both comparisons
+      return fail(entry, HG_ERR_INVALID, "p_drop must lie in [0, 1) (at 1 the scale 1 / (1 - p_drop) is infinite)");
+    if (!drop->rng_dev || (uintptr_t)drop->rng_dev % 8) return fail(entry, HG_ERR_INVALID, "rng_dev is null or not 8-byte aligned");
+  }
   if (const int st = size_refusal(entry, rows, k, n, 1)) return st;
   if (const int st = heads_refusal(entry, heads)) return st;
   if (side != HG_TABLE_HYPEREDGE && side != HG_TABLE_VERTEX)
@@ -814,6 +889,51 @@ int hg_table_softmax_bwd_heads_f32(const int32_t *idx, int32_t rows, int32_t k, 
   a.out_entry = ds;
   a.out_seg = dgroup;
   return launch_softmax_heads<kBodySoftmaxBwd>(entry, group, a, stream);
+}
+
+int hg_table_softmax_dropout_heads_f32(const int32_t *idx, int32_t rows, int32_t k, int32_t n, int32_t heads, int32_t group,
+                                       const float *node_score, const float *edge_score, const float *entry_score, float slope,
+                                       float p_drop, const uint64_t *rng_dev, const int32_t *ptr_v, const int32_t *pos_v,
+                                       float *alpha_out, float *alpha_drop_out, hg_stream_t stream) {
+  using namespace hg;
+  const char *entry = "hg_table_softmax_dropout_heads_f32";
+  const DropCall drop{p_drop, rng_dev};
+  if (const int st = softmax_refusal(entry, idx, rows, k, n, heads, group, "group", ptr_v, pos_v,
+                                     alpha_out && alpha_drop_out && (node_score || edge_score || entry_score),
+                                     "null alpha_out or alpha_drop_out, or node_score, edge_score and entry_score all null",
+                                     {node_score, edge_score, entry_score, alpha_out, alpha_drop_out}, &drop))
+    return st;
+  HeadsSoftmaxArgs a = softmax_args(idx, rows, k, n, heads, node_score, edge_score, entry_score, slope, ptr_v, pos_v);
+  a.out_entry = alpha_out;
+  a.out_drop = alpha_drop_out;
+  a.rng = rng_dev;
+  a.T = drop_threshold(p_drop);
+  a.scale = 1.0f / (1.0f - p_drop);
+  return launch_softmax_heads<kBodySoftmax, true>(entry, group, a, stream);
+}
+
+int hg_table_softmax_dropout_bwd_heads_f32(const int32_t *idx, int32_t rows, int32_t k, int32_t n, int32_t heads, int32_t group,
+                                           const float *node_score, const float *edge_score, const float *entry_score,
+                                           float slope, float p_drop, const uint64_t *rng_dev, const int32_t *ptr_v,
+                                           const int32_t *pos_v, const float *alpha, const float *dout, float *ds, float *dgroup,
+                                           hg_stream_t stream) {
+  using namespace hg;
+  const char *entry = "hg_table_softmax_dropout_bwd_heads_f32";
+  const DropCall drop{p_drop, rng_dev};
+  if (const int st = softmax_refusal(entry, idx, rows, k, n, heads, group, "group", ptr_v, pos_v,
+                                     alpha && dout && ds && (node_score || edge_score || entry_score),
+                                     "null alpha, dout or ds, or node_score, edge_score and entry_score all null",
+                                     {node_score, edge_score, entry_score, alpha, dout, ds, dgroup}, &drop))
+    return st;
+  HeadsSoftmaxArgs a = softmax_args(idx, rows, k, n, heads, node_score, edge_score, entry_score, slope, ptr_v, pos_v);
+  a.val = alpha;
+  a.dval = dout;
+  a.out_entry = ds;
+  a.out_seg = dgroup;
+  a.rng = rng_dev;
+  a.T = drop_threshold(p_drop);
+  a.scale = 1.0f / (1.0f - p_drop);
+  return launch_softmax_heads<kBodySoftmaxBwd, true>(entry, group, a, stream);
 }
 
 int hg_table_sum_heads_f32(const int32_t *idx, int32_t rows, int32_t k, int32_t n, int32_t heads, int32_t side,

@@ -15,7 +15,8 @@ Options.incidence_bf16 = 'rows' (hg_table_*_bf16): the float32 call on the widen
 `knn_softmax` (`ops.knn_softmax`; hg_table_softmax_*) turns scores into attention coefficients over the table, per hyperedge
 or per vertex, with exact gradients: its alpha is `knn_aggr`'s weight.  Several heads (hg_table_*_heads_f32): `knn_softmax(heads=H)` takes
 scores with the head as their last dimension, and `knn_aggr` a weight [rows, k, H]; every head in the same launch and with the
-single-head call's bits.
+single-head call's bits.  `knn_softmax(dropout=p)` drops coefficients inside the softmax launch and its backward
+(hg_table_softmax_dropout_*_heads_f32): a Philox mask that is never stored.
 """
 import ctypes
 import numbers
@@ -24,7 +25,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .plan import _check_feat, _ptr, _stream_handle
+from .plan import _check_feat, _ptr, _rng_state_device, _rng_state_dtype, _rng_state_length, _stream_handle
 from .synth import Incidence
 
 K_MAX = 64        # include/hg_aggr.h: k in 1 .. 64
@@ -891,36 +892,84 @@ def table_sum(idx, n, side, val, ptr_v=None, pos_v=None, heads=1):
     return out
 
 
+def _head_shape(idx, heads, segments=None):
+    """The shape of a per-position ([rows, k]) or per-segment array, with the head as one more dimension where heads > 1."""
+    lead = tuple(idx.shape) if segments is None else (segments,)
+    return lead + (heads,) if heads > 1 else lead
+
+
+def table_softmax_dropout(idx, n, group, p_drop, rng_state, node_score=None, edge_score=None, entry_score=None, slope=0.2,
+                          ptr_v=None, pos_v=None, heads=1):
+    """(alpha, alpha after dropout) of hg_table_softmax_dropout_heads_f32, both [rows, k] or [rows, k, H]: table_softmax's alpha,
+    bit for bit, and keep ? alpha / (1 - p_drop) : 0 for the Philox mask of rng_state (int64 [2] on the device, read by the
+    kernel).  One launch for any heads >= 1.  No checks, no gradient."""
+    rows, k = idx.shape
+    alpha = torch.empty(_head_shape(idx, heads), dtype=torch.float32, device=idx.device)
+    out = torch.empty_like(alpha)
+    with torch.cuda.device(idx.device):
+        _lib.check(_heads_entry("hg_table_softmax_dropout_heads_f32")(
+            _ptr(idx), rows, k, n, heads, _GROUPS[group], _ptr(node_score), _ptr(edge_score), _ptr(entry_score), slope,
+            float(p_drop), _ptr(rng_state), _ptr(ptr_v), _ptr(pos_v), _ptr(alpha), _ptr(out), _stream_handle(idx.device)))
+    return alpha, out
+
+
+def table_softmax_dropout_bwd(idx, n, group, p_drop, rng_state, alpha, dout, node_score=None, edge_score=None, entry_score=None,
+                              slope=0.2, ptr_v=None, pos_v=None, want_group=True, heads=1):
+    """(ds, dgroup or None) of hg_table_softmax_dropout_bwd_heads_f32: table_softmax_bwd on dalpha = keep ? dout / (1 - p_drop) : 0,
+    the mask formed again from rng_state inside the launch."""
+    rows, k = idx.shape
+    ds = torch.empty(_head_shape(idx, heads), dtype=torch.float32, device=idx.device)
+    nseg = rows if group == "hyperedge" else n
+    dgroup = torch.empty(_head_shape(idx, heads, nseg), dtype=torch.float32, device=idx.device) if want_group else None
+    with torch.cuda.device(idx.device):
+        _lib.check(_heads_entry("hg_table_softmax_dropout_bwd_heads_f32")(
+            _ptr(idx), rows, k, n, heads, _GROUPS[group], _ptr(node_score), _ptr(edge_score), _ptr(entry_score), slope,
+            float(p_drop), _ptr(rng_state), _ptr(ptr_v), _ptr(pos_v), _ptr(alpha), _ptr(dout), _ptr(ds), _ptr(dgroup),
+            _stream_handle(idx.device)))
+    return ds, dgroup
+
+
 class _KnnSoftmax(torch.autograd.Function):
     """alpha over a fixed table.  Saves alpha, the scores given, the table and its transpose; the backward is one launch of the
     backward kernel (ds and the own side's gradient) and, where the other end's score wants one, one segment sum over the
-    other side.  heads = H > 1: the same launches on the several-heads entries."""
+    other side.  heads = H > 1: the same launches on the several-heads entries.  p_drop > 0: dropout on alpha fused into both
+    kernels -- returns keep ? alpha / (1 - p) : 0, saves the undropped alpha and the two words of rng_state, from which the
+    backward launch forms the mask again."""
 
     @staticmethod
-    def forward(ctx, node_score, edge_score, entry_score, idx, ptr_v, pos_v, group, slope, n, heads=1):
-        ctx.group, ctx.slope, ctx.n, ctx.heads = group, slope, n, heads
-        alpha = table_softmax(idx, n, group, node_score, edge_score, entry_score, slope, ptr_v, pos_v, heads)
-        ctx.save_for_backward(alpha, node_score, edge_score, entry_score, idx, ptr_v, pos_v)
-        return alpha
+    def forward(ctx, node_score, edge_score, entry_score, idx, ptr_v, pos_v, group, slope, n, heads=1, p_drop=0.0, rng_state=None):
+        ctx.group, ctx.slope, ctx.n, ctx.heads, ctx.p_drop = group, slope, n, heads, p_drop
+        if p_drop > 0.0:
+            alpha, out = table_softmax_dropout(idx, n, group, p_drop, rng_state, node_score, edge_score, entry_score, slope,
+                                               ptr_v, pos_v, heads)
+        else:
+            alpha = out = table_softmax(idx, n, group, node_score, edge_score, entry_score, slope, ptr_v, pos_v, heads)
+        ctx.save_for_backward(alpha, node_score, edge_score, entry_score, idx, ptr_v, pos_v, rng_state)
+        return out
 
     @staticmethod
     def backward(ctx, dalpha):
-        alpha, node_score, edge_score, entry_score, idx, ptr_v, pos_v = ctx.saved_tensors
+        alpha, node_score, edge_score, entry_score, idx, ptr_v, pos_v, rng_state = ctx.saved_tensors
         hyperedge = ctx.group == "hyperedge"
         own, other = (1, 0) if hyperedge else (0, 1)  # positions of the two scores among the inputs
-        ds, dgroup = table_softmax_bwd(idx, ctx.n, ctx.group, alpha, dalpha.contiguous(), node_score, edge_score, entry_score,
-                                       ctx.slope, ptr_v, pos_v, want_group=ctx.needs_input_grad[own], heads=ctx.heads)
+        if ctx.p_drop > 0.0:
+            ds, dgroup = table_softmax_dropout_bwd(idx, ctx.n, ctx.group, ctx.p_drop, rng_state, alpha, dalpha.contiguous(),
+                                                   node_score, edge_score, entry_score, ctx.slope, ptr_v, pos_v,
+                                                   want_group=ctx.needs_input_grad[own], heads=ctx.heads)
+        else:
+            ds, dgroup = table_softmax_bwd(idx, ctx.n, ctx.group, alpha, dalpha.contiguous(), node_score, edge_score, entry_score,
+                                           ctx.slope, ptr_v, pos_v, want_group=ctx.needs_input_grad[own], heads=ctx.heads)
         grads = [None, None, None]
         grads[own] = dgroup
         if ctx.needs_input_grad[other]:
             grads[other] = table_sum(idx, ctx.n, "vertex" if hyperedge else "hyperedge", ds, ptr_v, pos_v, ctx.heads)
         if ctx.needs_input_grad[2]:
             grads[2] = ds.view(entry_score.shape)
-        return (*grads, None, None, None, None, None, None, None)
+        return (*grads, None, None, None, None, None, None, None, None, None)
 
 
 def knn_softmax(idx, node_score=None, edge_score=None, group="hyperedge", negative_slope=0.2, entry_score=None, transpose=None,
-                num_nodes=None, heads=1):
+                num_nodes=None, heads=1, dropout=0.0, training=True, rng_state=None, return_rng_state=False):
     """Attention coefficients over a neighbour table idx [rows, k] (int32, ops.knn's), with no plan and no host step: alpha
     float32 [rows, k], the softmax over each group of leaky_relu(raw, negative_slope) with
         raw[i, s] = (own + other) + entry_score[i, s]
@@ -934,20 +983,35 @@ def knn_softmax(idx, node_score=None, edge_score=None, group="hyperedge", negati
     its sum per group, the gradient of the group's own score) and one of hg_table_sum_f32 over the other side (the other
     end's).  The transpose is computed where it is needed and not given: for group='vertex', and for a node_score gradient
     under group='hyperedge'.  Deterministic: include/hg_aggr.h has the order of every sum, two calls give the same bits.
-    Nothing waits, nothing is read back.  float32 only: no dropout, no bfloat16 scores.
+    Nothing waits, nothing is read back.  float32 only: no bfloat16 scores.
     heads = H > 1: ops.incidence_softmax's layout on the table -- node_score [n, H], edge_score [rows, H], entry_score
     [rows, k, H] or [rows * k, H], alpha [rows, k, H] -- every head in the same launch (hg_table_softmax_heads_f32; the
     gradients through hg_table_softmax_bwd_heads_f32 and hg_table_sum_heads_f32, one launch each as above).  alpha[..., h]
     and every gradient's column h are, bit for bit, the single-head call's on column h.  heads = 1 is the call above.
-    Refusals, in this order and before a device is touched: TypeError for an idx (ptr_v, pos_v) that is not int32 and a score
-    that is not float32 (bfloat16 too, whatever Options.incidence_bf16 says); ValueError for an unknown group, for heads, for
-    the shapes and k, for no score at all; RuntimeError for CPU tensors."""
+    dropout = p in (0, 1) with training=True: the coefficients after dropout, keep ? alpha / (1 - p) : 0, from the same
+    launch (hg_table_softmax_dropout_heads_f32, any heads) -- no stored mask, no further pass; the gradients stay exact, the
+    one backward launch (hg_table_softmax_dropout_bwd_heads_f32) forms the mask again.  rng_state: int64 [2] on idx's device,
+    the {key, sid} of the Philox mask (keep depends on it, the table position i k + s and the head alone -- not on the
+    group); None draws one with torch.randint on that device: it follows torch.manual_seed, costs no host synchronisation
+    and, captured into a graph, gives every replay a new mask.  return_rng_state=True returns (coefficients, the state used
+    -- None where no dropout ran).  dropout = 0.0 or training=False is the call above: the same code path, the same bits,
+    torch's generator untouched.  Still nothing waits and nothing is read back.
+    Refusals, in this order and before a device is touched: ValueError for a dropout outside [0, 1); TypeError for an idx
+    (ptr_v, pos_v) that is not int32, a score that is not float32 (bfloat16 too, whatever Options.incidence_bf16 says) and an
+    rng_state that is not int64; ValueError for an unknown group, for heads, for the shapes and k, for no score at all, for
+    an rng_state of other than 2 elements; RuntimeError for CPU tensors and an rng_state off idx's device."""
+    from .ops import _dropout_p  # ops imports this module
+    p_drop = _dropout_p(dropout)
+    if p_drop == 0.0 or not training:  # no dropout: the state is neither looked at nor drawn nor returned
+        p_drop, rng_state = 0.0, None
     _table_shape(idx)
     scores = (("node_score", node_score), ("edge_score", edge_score), ("entry_score", entry_score))
     for name, t in scores:
         if t is not None:
             _check_dtype(t, name, torch.float32, " (knn_softmax has no bfloat16, float16 or float64 form)")
     _check_transpose_types(transpose)
+    if rng_state is not None:
+        _rng_state_dtype(rng_state)
     if group not in _GROUPS:
         raise ValueError("group must be 'hyperedge' or 'vertex', got %r" % (group,))
     H = _heads_value(heads)
@@ -975,10 +1039,14 @@ def knn_softmax(idx, node_score=None, edge_score=None, group="hyperedge", negati
             else "[rows, k] = [%d, %d] or [rows * k] = [%d]" % (rows, k, rows * k)
         raise ValueError("entry_score must be %s, got %s" % (want, tuple(entry_score.shape)))
     _check_transpose_shapes(transpose, n, rows * k)
+    if rng_state is not None:
+        _rng_state_length(rng_state)
     _check_table_index(idx, "idx")
     for name, t in scores:
         if t is not None:
             _check_feat(t, name, device=idx.device)
+    if rng_state is not None:
+        _rng_state_device(rng_state, idx.device)
     grad = torch.is_grad_enabled()
     ptr_v = pos_v = None
     if group == "vertex" or (grad and node_score is not None and node_score.requires_grad):
@@ -988,9 +1056,16 @@ def knn_softmax(idx, node_score=None, edge_score=None, group="hyperedge", negati
         _check_table_index(ptr_v, "ptr_v")
         _check_table_index(pos_v, "pos_v")
     slope = float(negative_slope)
+    if p_drop > 0.0 and rng_state is None:  # on the device: no synchronisation, and a captured draw is drawn again by every replay
+        info = torch.iinfo(torch.int64)  # randint's upper end is exclusive: every int64 but 2^63 - 1, which a key can spare
+        rng_state = torch.randint(info.min, info.max, (2,), dtype=torch.int64, device=idx.device)
     if grad and any(t is not None and t.requires_grad for _, t in scores):
-        return _KnnSoftmax.apply(node_score, edge_score, entry_score, idx, ptr_v, pos_v, group, slope, n, H)
-    return table_softmax(idx, n, group, node_score, edge_score, entry_score, slope, ptr_v, pos_v, H)
+        out = _KnnSoftmax.apply(node_score, edge_score, entry_score, idx, ptr_v, pos_v, group, slope, n, H, p_drop, rng_state)
+    elif p_drop > 0.0:  # nothing to differentiate: the operator itself, without the autograd node
+        out = table_softmax_dropout(idx, n, group, p_drop, rng_state, node_score, edge_score, entry_score, slope, ptr_v, pos_v, H)[1]
+    else:
+        out = table_softmax(idx, n, group, node_score, edge_score, entry_score, slope, ptr_v, pos_v, H)
+    return (out, rng_state) if return_rng_state else out
 
 
 def _knn_aggr_reduced(idx, X, weight, degE, degV, transpose, first, second):
@@ -1169,8 +1244,9 @@ class KnnHypergraph:
         (no weights with anything but the two sums).  weight=: explicit weights [N k] (or [N, k]) in place of the
         probabilistic ones, passed with weight_grad=True -- attention's alpha; exclusive with probabilistic.  heads=H:
         the weight must be ops.knn_aggr's several-heads weight [N k, H] or [N, k, H] (ValueError otherwise).
-      attention(node_score, edge_score, group="hyperedge", negative_slope=0.2, heads=1): ops.knn_softmax over the table with
-        the stored transpose: alpha [N, k], or [N, k, H].
+      attention(node_score, edge_score, group="hyperedge", negative_slope=0.2, heads=1, dropout=0.0, training=True,
+        rng_state=None): ops.knn_softmax over the table with the stored transpose: alpha [N, k], or [N, k, H]; dropout,
+        training and rng_state are ops.knn_softmax's (the coefficients after dropout, from the softmax's own launch).
     form: ops.knn's -- "dot" gives the same idx and dist through the matrix-unit prefilter, and its own mean.  Under "dot" X
     may be bfloat16: the table, dist, mean, transpose and degrees are int32 / float32 as always, and aggregate / weights take
     bfloat16 Z / X where `options` (or the caller's) has Options.incidence_bf16 = 'rows' -- ops.knn_aggr's and ops.knn_dist's
@@ -1213,9 +1289,10 @@ class KnnHypergraph:
         return knn_aggr(self.idx, Z, w, self.degE, self.degV, transpose=(self.ptr_v, self.pos_v), weight_grad=X is not None,
                         options=options, first=first, second=second)
 
-    def attention(self, node_score=None, edge_score=None, group="hyperedge", negative_slope=0.2, heads=1):
+    def attention(self, node_score=None, edge_score=None, group="hyperedge", negative_slope=0.2, heads=1, dropout=0.0,
+                  training=True, rng_state=None):
         return knn_softmax(self.idx, node_score, edge_score, group, negative_slope, transpose=(self.ptr_v, self.pos_v),
-                           num_nodes=self.num_nodes, heads=heads)
+                           num_nodes=self.num_nodes, heads=heads, dropout=dropout, training=training, rng_state=rng_state)
 
 
 def table_seq_max():

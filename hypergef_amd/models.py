@@ -181,19 +181,27 @@ class DynamicHypergraphConv(nn.Module):
     with alpha's gradient from ops.knn_aggr(weight_grad=True) and the scores' from ops.knn_softmax.  Two more parameters,
     a_v and a_e [out_channels], initialised as HypergraphAttnConv's; they exist only where attention is set.  With
     segments=None the layer still waits nowhere and is recorded into a hipGraph.  float32 only: a bfloat16 input raises
-    TypeError.  No dropout.  None (the default) is the layer above: same bits, same parameters.
+    TypeError.  None (the default) is the layer above: same bits, same parameters.
     heads = H > 1 (needs attention set): HypergraphAttnConv's multi-head additive layer, without bias, on the table.  lin maps
     to H * out_channels, head h owns columns h C .. (h + 1) C - 1 of Z (C = out_channels), a_v / a_e are flat [H * C] with
     the same initialisation bound, sv[u, h] = <Z[u, head h], a_v[head h]>, se the per-head hyperedge mean (ops.knn_gather on
     an [N, H] source), alpha [N, k, H] = hyperg.attention(sv, se, heads=H) and Y = hyperg.aggregate(Z, weight=alpha, heads=H):
     every table operator runs once for all heads (hg_table_*_heads_f32).  The output is [N, H * C] (concat=True) or the mean
     over the heads [N, C].  With segments=None the layer still waits nowhere and is recorded into a hipGraph.  heads = 1 is the
-    layer above: same bits, same state_dict."""
+    layer above: same bits, same state_dict.
+    dropout = p in (0, 1) (needs attention set): in training mode the coefficients are dropped with probability p and the kept
+    ones scaled by 1 / (1 - p), inside the table softmax's own launch and its backward (ops.knn_softmax(dropout=p)): no mask
+    is stored and alpha is not passed over again.  The mask follows torch.manual_seed.  No parameter and no buffer is added;
+    eval() and dropout = 0.0 are the layer above, bit for bit.  With segments=None or set_rows the layer still waits nowhere
+    and is recorded into a hipGraph: the state's draw is recorded with it, so every replay has a new mask."""
 
     def __init__(self, in_channels, out_channels, k, probabilistic=False, segments=None, m_prob=1.0, options=None,
                  device_graph=False, knn_form="difference", learn_distances=False, first_aggr="sum", second_aggr="sum",
-                 attention=None, negative_slope=0.2, heads=1, concat=True, set_rows=None):
+                 attention=None, negative_slope=0.2, heads=1, concat=True, set_rows=None, dropout=0.0):
         super().__init__()
+        self.dropout = ops._dropout_p(dropout)
+        if self.dropout > 0.0 and attention is None:
+            raise ValueError("dropout=%r needs attention='hyperedge' or 'vertex' (it drops attention coefficients)" % (dropout,))
         if isinstance(heads, bool) or not isinstance(heads, int) or heads < 1:
             raise ValueError("heads must be an integer >= 1, got %r" % (heads,))
         if heads > 1 and attention is None:
@@ -249,12 +257,13 @@ class DynamicHypergraphConv(nn.Module):
             sv = (Zh * self.a_v.view(H, C)).sum(-1)
             ze = (Zh * self.a_e.view(H, C)).sum(-1)
             se = knn_gather(hyperg.idx, ze, "hyperedge", "mean", transpose=transpose)
-            alpha = hyperg.attention(sv, se, self.attention, self.negative_slope, heads=H)
+            alpha = hyperg.attention(sv, se, self.attention, self.negative_slope, heads=H, dropout=self.dropout,
+                                     training=self.training)
             Y = hyperg.aggregate(Z, options=self.options, weight=alpha, heads=H)
             return Y if self.concat else Y.view(Y.shape[0], H, C).mean(1)
         sv = Z @ self.a_v
         se = knn_gather(hyperg.idx, (Z @ self.a_e)[:, None].contiguous(), "hyperedge", "mean", transpose=transpose).reshape(-1)
-        alpha = hyperg.attention(sv, se, self.attention, self.negative_slope)
+        alpha = hyperg.attention(sv, se, self.attention, self.negative_slope, dropout=self.dropout, training=self.training)
         return hyperg.aggregate(Z, options=self.options, weight=alpha)
 
     def forward(self, X):

@@ -1166,7 +1166,8 @@ HG_API int hg_table_select_t_f32(const int32_t *ptr_v, const int32_t *pos_v, int
  *   (dalpha, ds; val, out) or no score at all, null ptr_v or pos_v under HG_TABLE_VERTEX; for rows or n < 1, k outside
  *   1 .. 64, rows * k >= 2^31; for a group / side other than the two; then HG_ERR_UNSUPPORTED for a pointer that is not
  *   4-byte aligned.
- * Not covered: heads, dropout, bfloat16 scores.  Detect these entries by their exported symbols. */
+ * Not covered: bfloat16 scores.  Heads and dropout: the several-heads entries below, of which heads = 1 is this layout.
+ *   Detect these entries by their exported symbols. */
 #define HG_TABLE_HYPEREDGE 0
 #define HG_TABLE_VERTEX 1
 HG_API int hg_table_softmax_f32(const int32_t *idx, int32_t rows, int32_t k, int32_t n, int32_t group, const float *node_score,
@@ -1208,7 +1209,8 @@ HG_API int hg_table_sum_f32(const int32_t *idx, int32_t rows, int32_t k, int32_t
  * Refusals launch nothing, set hg_last_error, in the single-head entries' order with, after the sizes (rows, n or F < 1, k
  *   outside 1 .. 64, rows * k >= 2^31): HG_ERR_INVALID for heads < 1 and for F % heads != 0; a null w is refused with the
  *   other null pointers.
- * Not covered: dropout, bfloat16 scores or rows, max / min.  Detect these entries by their exported symbols. */
+ * Not covered: bfloat16 scores or rows, max / min; dropout in the gathers and dot products (the softmax has it: the
+ *   section after this one).  Detect these entries by their exported symbols. */
 HG_API int hg_table_softmax_heads_f32(const int32_t *idx, int32_t rows, int32_t k, int32_t n, int32_t heads, int32_t group,
                                       const float *node_score, const float *edge_score, const float *entry_score,
                                       float slope, const int32_t *ptr_v, const int32_t *pos_v, float *alpha,
@@ -1230,6 +1232,43 @@ HG_API int hg_table_gather_t_heads_f32(const int32_t *ptr_v, const int32_t *pos_
 HG_API int hg_table_dot_heads_f32(const int32_t *idx, int32_t rows, int32_t k, int32_t n, int32_t F, int32_t heads,
                                   const float *A, const float *a_scale, const float *B, const float *C, const float *D,
                                   float *out, hg_stream_t stream);
+
+/* Attention dropout over a neighbour table (csrc/hg_table_heads.hip): the "attention dropout" section above, moved to the
+ * table -- dropout on the coefficients inside hg_table_softmax_heads_f32 and hg_table_softmax_bwd_heads_f32, with no stored
+ * mask and no further pass over the [rows * k, heads] array.  One launch each on `stream`; nothing is allocated or waited
+ * for, no workspace, no atomics; both can be recorded into a hipGraph.  float32 only.  heads >= 1, and heads = 1 is the
+ * single-head layout: there is no separate single-head entry.  With p = i k + s the table position, h the head, p_drop in
+ * [0, 1) and rng = {key, sid}, two uint64 in device memory:
+ *     keep  = philox4x32_10(counter = (p, h, sid_lo, sid_hi), key = (key_lo, key_hi))[0] >= (uint32) floor((double) p_drop * 2^32)
+ *     scale = 1.0f / (1.0f - p_drop)                                                       (fp32, rounded on the host)
+ * hg_table_softmax_dropout_heads_f32: alpha_out[p, h] has exactly the bits hg_table_softmax_heads_f32 writes for the same
+ *   scores (the backward needs the undropped coefficient at the dropped positions too), and
+ *     alpha_drop_out[p, h] = keep ? fl(alpha_out[p, h] * scale) : +0.0f.
+ *   An entry that is no candidate (idx outside 0 .. n - 1, pos_v outside 0 .. rows k - 1) is +0.0 in both outputs, and no
+ *   Philox value is computed for it.  The mask depends on (rng, p, h) alone -- not on the group, the lane-group width, the
+ *   slab of heads a lane carries, or whether a vertex segment is short or long -- so both groups drop the same positions for
+ *   the same state, and hg_dropout_keep_host(key, sid, p_drop, rows * k, heads, ..) states the mask for the table too.
+ * hg_table_softmax_dropout_bwd_heads_f32: given alpha (alpha_out above) and dout, the gradient of alpha_drop_out,
+ *     dalpha[p, h] = keep ? fl(dout[p, h] * scale) : +0.0f
+ *   with the mask regenerated from rng_dev, then exactly hg_table_softmax_bwd_heads_f32 on (alpha, dalpha): the same
+ *   SEGMENT ORDER, so ds and dgroup have the bits of that entry on the pre-masked gradient.
+ * rng_dev: 8-byte aligned, read by the kernel when it runs -- not by the call -- so a captured launch draws a new mask on
+ *   every replay whose state a captured device operation updated.  The backward must find the words its forward found.
+ * Refusals launch nothing, set hg_last_error, in the several-heads softmax entries' order with, after their null-pointer
+ *   checks (a null alpha_out, alpha_drop_out or ds is one of those) and before the sizes: HG_ERR_INVALID for p_drop outside
+ *   [0, 1) or NaN, then HG_ERR_INVALID for a null rng_dev or one that is not 8-byte aligned.
+ * Detect these entries by their exported symbols (HG_AGGR_VERSION does not change). */
+HG_API int hg_table_softmax_dropout_heads_f32(const int32_t *idx, int32_t rows, int32_t k, int32_t n, int32_t heads,
+                                              int32_t group, const float *node_score, const float *edge_score,
+                                              const float *entry_score, float slope, float p_drop, const uint64_t *rng_dev,
+                                              const int32_t *ptr_v, const int32_t *pos_v, float *alpha_out,
+                                              float *alpha_drop_out, hg_stream_t stream);
+HG_API int hg_table_softmax_dropout_bwd_heads_f32(const int32_t *idx, int32_t rows, int32_t k, int32_t n, int32_t heads,
+                                                  int32_t group, const float *node_score, const float *edge_score,
+                                                  const float *entry_score, float slope, float p_drop,
+                                                  const uint64_t *rng_dev, const int32_t *ptr_v, const int32_t *pos_v,
+                                                  const float *alpha, const float *dout, float *ds,
+                                                  float *dgroup /* may be NULL */, hg_stream_t stream);
 
 #ifdef __cplusplus
 }
