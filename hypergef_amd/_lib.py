@@ -53,6 +53,7 @@ SYMBOLS = (
     "hg_gather_rows_reduce_workspace_bytes", "hg_gather_rows_reduce_f32", "hg_gather_rows_select_f32",
     "hg_knn_f32", "hg_knn_workspace_bytes", "hg_knn_dot_f32", "hg_knn_dot_workspace_bytes",
     "hg_knn_dot_bf16", "hg_knn_dot_bf16_workspace_bytes", "hg_knn_dot_estimates_bf16",
+    "hg_knn_dot_split_f32", "hg_knn_dot_estimates_split_f32",
     "hg_knn_sets_f32", "hg_knn_dot_sets_f32", "hg_knn_dot_sets_bf16", "hg_knn_dot_sets_workspace_bytes",
     "hg_table_seq_max", "hg_table_transpose_workspace_bytes", "hg_table_transpose", "hg_table_gather_f32",
     "hg_table_gather_t_f32",
@@ -322,6 +323,11 @@ def lib():
         L.hg_knn_dot_bf16.argtypes = [vp, i32, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, sz, vp]
         L.hg_knn_dot_estimates_bf16.restype = ctypes.c_int
         L.hg_knn_dot_estimates_bf16.argtypes = [vp, i32, vp, i32, i32, vp, vp, vp]
+    if hasattr(L, "hg_knn_dot_split_f32"):  # likewise: float32 rows split onto the bf16 matrix unit, and its diagnostic
+        L.hg_knn_dot_split_f32.restype = ctypes.c_int
+        L.hg_knn_dot_split_f32.argtypes = [vp, i32, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, sz, vp]
+        L.hg_knn_dot_estimates_split_f32.restype = ctypes.c_int
+        L.hg_knn_dot_estimates_split_f32.argtypes = [vp, i32, vp, i32, i32, vp, vp, vp]
     if hasattr(L, "hg_knn_sets_f32"):  # likewise: the three searches over uniform sets (X, n, F, k, set_rows, ..; no Q, no seg)
         L.hg_knn_sets_f32.restype = ctypes.c_int
         L.hg_knn_sets_f32.argtypes = [vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, sz, vp]

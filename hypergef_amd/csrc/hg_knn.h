@@ -45,6 +45,9 @@ constexpr int kDotRerankRows = 64;  // the rerank kernel's batch: one candidate 
 // bfloat16 rows (hg_knn_dot_bf16): the same workgroup and tiles on v_mfma_f32_32x32x16_bf16, 16 columns per instruction
 constexpr int kDotBfFC = 64;        // columns per LDS chunk: 128 bytes a row, four instructions
 constexpr int kDotBfLd = 72;        // row pitch in elements, 144 bytes: nine 16-byte slots, odd, for the 16-byte operand reads
+// float32 rows under the split form (hg_knn_dot_split_f32): the same again, every element as two bfloat16 parts, three
+// instructions per 16 columns; a hi and a lo LDS image of each operand, each with the pitch above
+constexpr int kDotSplitFC = 64;     // float32 columns per LDS chunk: 256 bytes a row from memory, four column groups
 constexpr int64_t kDotEstimatesMax = 1 << 22;  // hg_knn_dot_estimates_bf16 (a diagnostic): nq * n above this is refused
 
 // Shortlist slots per lane for k: the shortlist holds 32 * knn_dot_slots(k) entries, at least k + 16 (slack 16 .. 47).

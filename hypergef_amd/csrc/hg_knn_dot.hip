@@ -22,6 +22,12 @@
 // instruction what they were before R existed -- which is why knn_dot_prefilter_kernel keeps its body inline: calling
 // offer_tile / write_lists from it changed its register allocation.  knn_dot_estimates_bf16_kernel is the diagnostic entry's.
 //
+// float32 rows on the bf16 unit (hg_knn_dot_split_f32): the row type SplitF32 is a float read under the split
+// form.  The norms are the float32 instance's and the rerank is the float32 arithmetic with the bound E1s (dot_e1s); the
+// prefilter (knn_dot_prefilter_split_kernel) reads the float32 rows once, splits every element into two bfloat16 parts in
+// registers (split2), keeps a hi and a lo image of each operand in LDS, and sums hi.hi + hi.lo + lo.hi on
+// v_mfma_f32_32x32x16_bf16 (split_tile).  knn_dot_estimates_split_kernel is the diagnostic entry's.
+//
 // Uniform sets (hg_knn_dot_sets_f32 / _bf16): B sets of m rows, every set searched as a problem of its own.
 // The prefilter and the rerank have SETS instances whose only added code is rebase_to_set: the argument block holds one
 // set's sizes and the whole call's arrays, and the workgroup moves the pointers to its set before the unchanged body runs.
@@ -32,6 +38,7 @@
 #include <climits>
 #include <cmath>
 #include <string>
+#include <type_traits>
 
 #include "hg_aggr.h"
 #include "hg_internal.h"
@@ -576,6 +583,205 @@ __global__ __launch_bounds__(kDotBlock) void knn_dot_estimates_bf16_kernel(DotAr
   }
 }
 
+// ---- float32 rows, split into two bfloat16 parts, on v_mfma_f32_32x32x16_bf16 ----------------------------------
+
+// A float32 element of a row searched under the split form: the memory is a float's, the type selects the instances.
+struct SplitF32 {
+  float v;
+};
+typedef DotArgsT<SplitF32> DotArgsSplit;
+__device__ __forceinline__ float widen(SplitF32 e) { return e.v; }
+
+// float32 rows under the split form: the two-sided bound on |d~ - D| of a row with sum = fl(n2q + n2max),
+//   E1s = C_s u (n2q + n2max) + (328 G + 1) 2^-126,  G = ceil(F / 16),  C_s = (775 + F + 104 G) (1 + 1/64) rounded up
+// 775 = 771 + 4: 771 u >= 3.00785 2^-16, the three products the estimate leaves out (ql.xl, (qh + ql).xr, qr.x); 104 G: H over
+// 3 G instructions on sum |parts' products| <= 1.0157 sum |q_c x_c|
+__device__ __forceinline__ float dot_e1s(int F, float sum) {
+  const float u = 5.9604644775390625e-8f;  // 2^-24
+  const int G = (F + 15) >> 4, c2 = 775 + F + 104 * G;
+  const float C = (float)(c2 + (c2 >> 6) + 1) * u;  // an integer below 2^24 times a power of two: exact
+  return C * sum + (float)(328 * G + 1) * 1.1754943508222875e-38f;  // 2^-126
+}
+
+typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+
+// Two elements into their parts: hi = bf16(v) and lo = bf16(v - hi), both round to nearest even (v_cvt_pk_bf16_f32), packed
+// with a in the low half; v - hi is exact in float32.
+__device__ __forceinline__ void split2(float a, float b, uint32_t &hi, uint32_t &lo) {
+  const f32x2 v = {a, b};
+  hi = __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2));
+  const f32x2 r = {a - __uint_as_float(hi << 16), b - __uint_as_float(hi & 0xffff0000u)};
+  lo = __builtin_bit_cast(uint32_t, __builtin_convertvector(r, bf16x2));
+}
+
+// A chunk is 128 query rows and 128 candidate rows of kDotSplitFC = 64 float32 columns, 256 bytes a row.  Sixteen lanes read
+// one row's 256 bytes, sixteen bytes each; thread t holds columns 4 (t & 15) .. + 3 of rows (t >> 4) + 16 i, i < 8, of each.
+struct SplitStage {
+  float4 q[8], x[8];
+};
+
+// Columns c .. c + 3 of a row, zeros past F and for a row that does not exist.  vec (the same in every thread): the base and
+// every row are 16-byte aligned and F is a multiple of 4, so the four are one load, inside the row or past it; otherwise they
+// are read one by one (a base that is only 4-byte aligned, any F).
+__device__ __forceinline__ float4 split_load4(const SplitF32 *base, int g, bool live, int c, int F, bool vec) {
+  float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+  if (live && c < F) {
+    const float *row = reinterpret_cast<const float *>(base) + (size_t)g * F;
+    if (vec) return *reinterpret_cast<const float4 *>(row + c);
+    v.x = row[c];
+    if (c + 1 < F) v.y = row[c + 1];
+    if (c + 2 < F) v.z = row[c + 2];
+    if (c + 3 < F) v.w = row[c + 3];
+  }
+  return v;
+}
+
+__device__ __forceinline__ void split_fetch(const DotArgsSplit &a, bool vec, int q0, int tile, int f0, SplitStage &pre) {
+  const int t = threadIdx.x, c = f0 + 4 * (t & 15), sr = t >> 4;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    const int g = q0 + sr + 16 * i;
+    pre.q[i] = split_load4(a.Q, g, g < a.nq, c, a.F, vec);
+  }
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    const int g = tile * kDotTC + sr + 16 * i;
+    pre.x[i] = split_load4(a.X, g, g < a.n, c, a.F, vec);
+  }
+}
+
+__device__ __forceinline__ bool split_vec(const DotArgsSplit &a) {
+  return ((uintptr_t)a.Q | (uintptr_t)a.X | (uintptr_t)(4 * (size_t)a.F)) % 16 == 0;
+}
+
+// The LDS images of a chunk: S[0] / S[1] the hi / lo parts of the query rows, S[2] / S[3] of the candidate rows, each bf_tile's
+// image (bfloat16, row-major, pitch kDotBfLd: conflict-free 16-byte operand reads).  4 x 18 432 = 73 728 bytes.
+typedef uint16_t SplitImages[4][kDotTQ][kDotBfLd];
+
+// s~ of the workgroup's 128 query rows (from q0) against candidate tile `tile`, in acc: the one piece of code that forms a
+// pair's sum under the split form, for the prefilter and for the diagnostic entry.  A pair's sum is 3 ceil(F / 16)
+// instructions into one accumulator: for column group g, ascending, qh.xh, then qh.xl, then ql.xh over columns 16 g .. 16 g +
+// 15, zeros past F -- whatever the tile, the slice or the position in the tile.  The float32 chunk in `pre` is split when it
+// is stored to LDS (a thread's four columns of a row: 8 bytes to the hi image, 8 to the lo image), so the split rows exist in
+// registers and LDS only; the next float32 chunk, or the first of tile + 1 (below t_end), is read into `pre` while the MFMAs of
+// this one run.
+__device__ __forceinline__ void split_tile(const DotArgsSplit &a, bool vec, int q0, int tile, int t_end, SplitStage &pre,
+                                           f32x16 (&acc)[4], SplitImages &S) {
+  const int t = threadIdx.x, lane = t & 63, w = t >> 6, tx = lane & 31, h = lane >> 5;
+  const int sc = 4 * (t & 15), sr = t >> 4, F = a.F;
+#pragma unroll
+  for (int b = 0; b < 4; ++b)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[b][r] = 0.f;
+  for (int f0 = 0; f0 < F; f0 += kDotSplitFC) {
+    __syncthreads();  // the readers of the chunk before
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      uint2 hi, lo;
+      split2(pre.q[i].x, pre.q[i].y, hi.x, lo.x);
+      split2(pre.q[i].z, pre.q[i].w, hi.y, lo.y);
+      *reinterpret_cast<uint2 *>(&S[0][sr + 16 * i][sc]) = hi;
+      *reinterpret_cast<uint2 *>(&S[1][sr + 16 * i][sc]) = lo;
+      split2(pre.x[i].x, pre.x[i].y, hi.x, lo.x);
+      split2(pre.x[i].z, pre.x[i].w, hi.y, lo.y);
+      *reinterpret_cast<uint2 *>(&S[2][sr + 16 * i][sc]) = hi;
+      *reinterpret_cast<uint2 *>(&S[3][sr + 16 * i][sc]) = lo;
+    }
+    __syncthreads();
+    int nt = tile, nf = f0 + kDotSplitFC;
+    if (nf >= F) {
+      nt = tile + 1;
+      nf = 0;
+    }
+    if (nt < t_end) split_fetch(a, vec, q0, nt, nf, pre);
+    const int left = (F - f0 + 15) >> 4, steps = left < kDotSplitFC / 16 ? left : kDotSplitFC / 16;
+    for (int kk = 0; kk < steps; ++kk) {  // columns f0 + 16 kk + 8 h .. + 7 in this lane's fragments
+      const int c = 16 * kk + 8 * h;
+      const bf16x8 qh = *reinterpret_cast<const bf16x8 *>(&S[0][w * 32 + tx][c]);
+      const bf16x8 ql = *reinterpret_cast<const bf16x8 *>(&S[1][w * 32 + tx][c]);
+      bf16x8 xh[4], xl[4];
+#pragma unroll
+      for (int b = 0; b < 4; ++b) {
+        xh[b] = *reinterpret_cast<const bf16x8 *>(&S[2][b * 32 + tx][c]);
+        xl[b] = *reinterpret_cast<const bf16x8 *>(&S[3][b * 32 + tx][c]);
+      }
+      // every accumulator takes hi.hi, hi.lo, lo.hi in this order; the four are independent, so the terms interleave
+#pragma unroll
+      for (int b = 0; b < 4; ++b) acc[b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(qh, xh[b], acc[b], 0, 0, 0);
+#pragma unroll
+      for (int b = 0; b < 4; ++b) acc[b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(qh, xl[b], acc[b], 0, 0, 0);
+#pragma unroll
+      for (int b = 0; b < 4; ++b) acc[b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ql, xh[b], acc[b], 0, 0, 0);
+    }
+  }
+}
+
+// knn_dot_prefilter_kernel for float32 rows under the split form: the same workgroup, tiles, slices, shortlists and mean
+template <int KS, bool MEAN>
+__global__ __launch_bounds__(kDotBlock) void knn_dot_prefilter_split_kernel(DotArgsSplit a) {
+  __shared__ __attribute__((aligned(16))) SplitImages S;
+  const int t = threadIdx.x, lane = t & 63, w = t >> 6, h = lane >> 5;
+  const int q0 = blockIdx.x * kDotTQ, slice = blockIdx.y;
+  const int tiles = (a.n + kDotTC - 1) / kDotTC;
+  const int t_begin = (int)((int64_t)tiles * slice / a.slices), t_end = (int)((int64_t)tiles * (slice + 1) / a.slices);
+  const bool vec = split_vec(a);
+
+  const int row0 = q0 + w * 32 + 4 * h;
+  float ld[16][KS];
+  int lj[16][KS];
+  float thr[16];
+  float nq[16], msum[16];
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+#pragma unroll
+    for (int m = 0; m < KS; ++m) {
+      ld[r][m] = INFINITY;
+      lj[r][m] = INT_MAX;
+    }
+    thr[r] = INFINITY;
+    msum[r] = 0.f;
+    const int row = row0 + (r & 3) + 8 * (r >> 2);
+    nq[r] = row < a.nq ? a.n2q[row] : 0.f;
+  }
+
+  SplitStage pre;
+  if (t_begin < t_end) split_fetch(a, vec, q0, t_begin, 0, pre);
+  for (int tile = t_begin; tile < t_end; ++tile) {
+    f32x16 acc[4];
+    split_tile(a, vec, q0, tile, t_end, pre, acc, S);
+    offer_tile<KS, MEAN>(a, tile * kDotTC, row0, acc, ld, lj, thr, nq, msum);
+  }
+  write_lists<KS, MEAN>(a, slice, row0, ld, lj, msum);
+}
+
+// The split diagnostic entry's kernel: every pair's raw estimate d~ from split_tile's sums, workgroup (x, y) the 128 query
+// rows x and the candidate tile y, and the rows' E1s.
+__global__ __launch_bounds__(kDotBlock) void knn_dot_estimates_split_kernel(DotArgsSplit a, float *__restrict__ est,
+                                                                            float *__restrict__ e1) {
+  __shared__ __attribute__((aligned(16))) SplitImages S;
+  const int t = threadIdx.x, lane = t & 63, w = t >> 6, tx = lane & 31, h = lane >> 5;
+  const int q0 = blockIdx.x * kDotTQ, tile = blockIdx.y, cb = tile * kDotTC;
+  const int row0 = q0 + w * 32 + 4 * h;
+  const bool vec = split_vec(a);
+  SplitStage pre;
+  split_fetch(a, vec, q0, tile, 0, pre);
+  f32x16 acc[4];
+  split_tile(a, vec, q0, tile, tile + 1, pre, acc, S);
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    const int row = row0 + (r & 3) + 8 * (r >> 2);
+    if (row >= a.nq) continue;
+    const float nq = a.n2q[row];
+#pragma unroll
+    for (int b = 0; b < 4; ++b) {
+      const int j = cb + b * 32 + tx;
+      if (j < a.n) est[(size_t)row * a.n + j] = (nq + a.n2x[j]) - 2.f * acc[b][r];
+    }
+    if (tile == 0 && tx == 0) e1[row] = dot_e1s(a.F, nq + a.n2max[0]);
+  }
+}
+
 // d2(row, j) of this lane's candidate j (j < 0: none) in knn_kernel's arithmetic.  The 64 candidate rows are staged through
 // LDS 64 columns at a time with coalesced reads, then every lane walks its own row in column order.
 template <typename R>
@@ -664,7 +870,8 @@ __global__ __launch_bounds__(kDotRerankRows) void knn_dot_rerank_kernel(DotArgsT
   }
 
   // Every candidate outside the shortlist has d~ >= T, so d2 >= (T - E1) (1 - (F + 2) u) >= T - Ei:
-  //   E1 = C u (n2q + n2max) + (F + 2) 2^-146,  C = (2 F + 4) (1 + 1/64) rounded up,  u = 2^-24;  bfloat16 rows: dot_e1b
+  //   E1 = C u (n2q + n2max) + (F + 2) 2^-146,  C = (2 F + 4) (1 + 1/64) rounded up,  u = 2^-24;  bfloat16 rows: dot_e1b;
+  //   float32 rows under the split form: dot_e1s
   //   Ei = E1 + (F + 4) u max(T, 0)
   bool certified = !__any(bad);
   if (certified && n > kp) {
@@ -673,10 +880,12 @@ __global__ __launch_bounds__(kDotRerankRows) void knn_dot_rerank_kernel(DotArgsT
     const float kth = list_slot<1, 64>(bd, k - 1);
     const float sum = a.n2q[row] + a.n2max[0];
     float E1;
-    if constexpr (sizeof(R) == 4) {
+    if constexpr (std::is_same_v<R, float>) {
       const int c2 = 2 * a.F + 4;
       const float C = (float)(c2 + (c2 >> 6) + 1) * u;
       E1 = C * sum + (float)(a.F + 2) * 1.1210387714598537e-44f;  // 2^-146
+    } else if constexpr (std::is_same_v<R, SplitF32>) {
+      E1 = dot_e1s(a.F, sum);
     } else {
       E1 = dot_e1b(a.F, sum);
     }
@@ -709,7 +918,8 @@ __global__ __launch_bounds__(kDotRerankRows) void knn_dot_rerank_kernel(DotArgsT
 template <int KS, bool SETS, typename R>
 void launch_prefilter(const DotArgsT<R> &a, dim3 grid, bool mean, hipStream_t s) {
   void (*kernel)(DotArgsT<R>);
-  if constexpr (sizeof(R) == 4) kernel = mean ? knn_dot_prefilter_kernel<KS, true, SETS> : knn_dot_prefilter_kernel<KS, false, SETS>;
+  if constexpr (std::is_same_v<R, float>) kernel = mean ? knn_dot_prefilter_kernel<KS, true, SETS> : knn_dot_prefilter_kernel<KS, false, SETS>;
+  else if constexpr (std::is_same_v<R, SplitF32>) kernel = mean ? knn_dot_prefilter_split_kernel<KS, true> : knn_dot_prefilter_split_kernel<KS, false>;  // no sets
   else kernel = mean ? knn_dot_prefilter_bf16_kernel<KS, true, SETS> : knn_dot_prefilter_bf16_kernel<KS, false, SETS>;
   hipLaunchKernelGGL(kernel, grid, dim3(kDotBlock), 0, s, a);
 }
@@ -728,14 +938,16 @@ void launch_search(const DotArgsT<R> &a, unsigned groups, unsigned rows, hipStre
 }
 
 // The norms of the candidates, their maximum and (Q != X) the norms of the query rows, into a's n2x / n2max / n2q; bmax is
-// scratch of ceil(n / 64) floats.
+// scratch of ceil(n / 64) floats.  Under the split form the norms are the float32 kernel's, of the unsplit rows.
 template <typename R>
 void launch_norms(const DotArgsT<R> &a, float *bmax, hipStream_t s) {
+  typedef std::conditional_t<std::is_same_v<R, SplitF32>, float, R> N;
+  const N *X = reinterpret_cast<const N *>(a.X), *Q = reinterpret_cast<const N *>(a.Q);
   const int nb = (a.n + kDotNormRows - 1) / kDotNormRows;
-  hipLaunchKernelGGL(knn_dot_norm_kernel<R>, dim3((unsigned)nb), dim3(256), 0, s, a.X, a.n, a.F, const_cast<float *>(a.n2x), bmax);
+  hipLaunchKernelGGL(knn_dot_norm_kernel<N>, dim3((unsigned)nb), dim3(256), 0, s, X, a.n, a.F, const_cast<float *>(a.n2x), bmax);
   hipLaunchKernelGGL(knn_dot_max_kernel, dim3(1), dim3(256), 0, s, (const float *)bmax, nb, const_cast<float *>(a.n2max));
   if (!a.same)
-    hipLaunchKernelGGL(knn_dot_norm_kernel<R>, dim3((unsigned)((a.nq + kDotNormRows - 1) / kDotNormRows)), dim3(256), 0, s, a.Q,
+    hipLaunchKernelGGL(knn_dot_norm_kernel<N>, dim3((unsigned)((a.nq + kDotNormRows - 1) / kDotNormRows)), dim3(256), 0, s, Q,
                        a.nq, a.F, const_cast<float *>(a.n2q), (float *)nullptr);
 }
 
@@ -842,6 +1054,44 @@ int knn_dot_sets_run(const char *entry, const R *X, int32_t n, int32_t F, int32_
   return HG_OK;
 }
 
+// hg_knn_dot_estimates_bf16 and hg_knn_dot_estimates_split_f32: the refusals, the norms and the row type's diagnostic kernel
+template <typename R>
+int knn_dot_estimates_run(const char *entry, const R *Q, int32_t nq, const R *X, int32_t n, int32_t F, float *est, float *e1,
+                          hg_stream_t stream) {
+  if (!Q || !X || !est || !e1) return fail(entry, HG_ERR_INVALID, "null Q, X, est or e1");
+  if (nq < 1 || n < 1 || F < 1) return fail(entry, HG_ERR_INVALID, "nq, n and F must be at least 1");
+  if (F > kDotMaxF)
+    return fail(entry, HG_ERR_INVALID, "F = " + std::to_string(F) + " is above " + std::to_string(kDotMaxF) + ", the width the error bound is derived for");
+  if ((int64_t)nq * n > kDotEstimatesMax)
+    return fail(entry, HG_ERR_UNSUPPORTED, "a diagnostic: nq * n must be at most " + std::to_string(kDotEstimatesMax));
+  if ((uintptr_t)Q % sizeof(R) || (uintptr_t)X % sizeof(R) || (uintptr_t)est % 4 || (uintptr_t)e1 % 4)
+    return fail(entry, HG_ERR_UNSUPPORTED, "Q and X must be " + std::to_string(sizeof(R)) + "-byte aligned, est and e1 4-byte aligned");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const KnnDotLayout L = knn_dot_layout(nq, n, 1, 1);  // for the norms' places; the lists are not used
+  unsigned char *ws = nullptr;
+  hipError_t e = hipMalloc(reinterpret_cast<void **>(&ws), L.idx);
+  if (e != hipSuccess) return fail(entry, HG_ERR_HIP, std::string("hipMalloc: ") + hipGetErrorString(e));
+  DotArgsT<R> a{};
+  a.Q = Q;
+  a.X = X;
+  a.nq = nq;
+  a.n = n;
+  a.F = F;
+  a.same = Q == X && nq == n;
+  a.n2x = reinterpret_cast<float *>(ws + L.n2x);
+  a.n2q = a.same ? a.n2x : reinterpret_cast<float *>(ws + L.n2q);
+  a.n2max = reinterpret_cast<float *>(ws + L.n2max);
+  launch_norms(a, reinterpret_cast<float *>(ws + L.bmax), s);
+  const dim3 grid((unsigned)((nq + kDotTQ - 1) / kDotTQ), (unsigned)((n + kDotTC - 1) / kDotTC));
+  if constexpr (std::is_same_v<R, SplitF32>) hipLaunchKernelGGL(knn_dot_estimates_split_kernel, grid, dim3(kDotBlock), 0, s, a, est, e1);
+  else hipLaunchKernelGGL(knn_dot_estimates_bf16_kernel, grid, dim3(kDotBlock), 0, s, a, est, e1);
+  e = hipGetLastError();
+  if (e == hipSuccess) e = hipStreamSynchronize(s);  // the norms' memory goes back below
+  (void)hipFree(ws);
+  if (e != hipSuccess) return fail(entry, HG_ERR_HIP, std::string("launch: ") + hipGetErrorString(e));
+  return HG_OK;
+}
+
 }  // namespace
 }  // namespace hg
 
@@ -891,39 +1141,21 @@ int hg_knn_dot_sets_bf16(const uint16_t *X, int32_t n, int32_t F, int32_t k, int
 
 int hg_knn_dot_estimates_bf16(const uint16_t *Q, int32_t nq, const uint16_t *X, int32_t n, int32_t F, float *est, float *e1,
                               hg_stream_t stream) {
-  using namespace hg;
-  const char *entry = "hg_knn_dot_estimates_bf16";
-  if (!Q || !X || !est || !e1) return fail(entry, HG_ERR_INVALID, "null Q, X, est or e1");
-  if (nq < 1 || n < 1 || F < 1) return fail(entry, HG_ERR_INVALID, "nq, n and F must be at least 1");
-  if (F > kDotMaxF)
-    return fail(entry, HG_ERR_INVALID, "F = " + std::to_string(F) + " is above " + std::to_string(kDotMaxF) + ", the width the error bound is derived for");
-  if ((int64_t)nq * n > kDotEstimatesMax)
-    return fail(entry, HG_ERR_UNSUPPORTED, "a diagnostic: nq * n must be at most " + std::to_string(kDotEstimatesMax));
-  if ((uintptr_t)Q % 2 || (uintptr_t)X % 2 || (uintptr_t)est % 4 || (uintptr_t)e1 % 4)
-    return fail(entry, HG_ERR_UNSUPPORTED, "Q and X must be 2-byte aligned, est and e1 4-byte aligned");
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  const KnnDotLayout L = knn_dot_layout(nq, n, 1, 1);  // for the norms' places; the lists are not used
-  unsigned char *ws = nullptr;
-  hipError_t e = hipMalloc(reinterpret_cast<void **>(&ws), L.idx);
-  if (e != hipSuccess) return fail(entry, HG_ERR_HIP, std::string("hipMalloc: ") + hipGetErrorString(e));
-  DotArgsBf16 a{};
-  a.Q = Q;
-  a.X = X;
-  a.nq = nq;
-  a.n = n;
-  a.F = F;
-  a.same = Q == X && nq == n;
-  a.n2x = reinterpret_cast<float *>(ws + L.n2x);
-  a.n2q = a.same ? a.n2x : reinterpret_cast<float *>(ws + L.n2q);
-  a.n2max = reinterpret_cast<float *>(ws + L.n2max);
-  launch_norms(a, reinterpret_cast<float *>(ws + L.bmax), s);
-  const dim3 grid((unsigned)((nq + kDotTQ - 1) / kDotTQ), (unsigned)((n + kDotTC - 1) / kDotTC));
-  hipLaunchKernelGGL(knn_dot_estimates_bf16_kernel, grid, dim3(kDotBlock), 0, s, a, est, e1);
-  e = hipGetLastError();
-  if (e == hipSuccess) e = hipStreamSynchronize(s);  // the norms' memory goes back below
-  (void)hipFree(ws);
-  if (e != hipSuccess) return fail(entry, HG_ERR_HIP, std::string("launch: ") + hipGetErrorString(e));
-  return HG_OK;
+  return hg::knn_dot_estimates_run("hg_knn_dot_estimates_bf16", Q, nq, X, n, F, est, e1, stream);
+}
+
+int hg_knn_dot_split_f32(const float *Q, int32_t nq, const float *X, int32_t n, int32_t F, int32_t k, int32_t self_first,
+                         int32_t cand_slices, int32_t *idx, float *dist, float *mean_dist, int32_t *fallback, void *workspace,
+                         size_t workspace_bytes, hg_stream_t stream) {
+  return hg::knn_dot_run("hg_knn_dot_split_f32", "hg_knn_dot_workspace_bytes", reinterpret_cast<const hg::SplitF32 *>(Q), nq,
+                         reinterpret_cast<const hg::SplitF32 *>(X), n, F, k, self_first, cand_slices, idx, dist, mean_dist, fallback,
+                         workspace, workspace_bytes, stream);
+}
+
+int hg_knn_dot_estimates_split_f32(const float *Q, int32_t nq, const float *X, int32_t n, int32_t F, float *est, float *e1,
+                                   hg_stream_t stream) {
+  return hg::knn_dot_estimates_run("hg_knn_dot_estimates_split_f32", reinterpret_cast<const hg::SplitF32 *>(Q), nq,
+                                   reinterpret_cast<const hg::SplitF32 *>(X), n, F, est, e1, stream);
 }
 
 }  // extern "C"

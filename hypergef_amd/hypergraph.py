@@ -58,7 +58,8 @@ class HyperGraph:
         ops.knn's -- many point sets in one tensor, neighbours within a set; set_rows: ops.knn's -- the same for sets of
         exactly set_rows rows each, without offsets and under either form.  The neighbour table is read back once (the
         plan is built on the host).  Keeps knn_dist [N, k] (squared), knn_mean [N] and knn_weights().  form: ops.knn's -- "dot"
-        builds the same hypergraph and knn_dist through the matrix-unit prefilter; knn_mean is then the dot form's.  Under
+        builds the same hypergraph and knn_dist through the matrix-unit prefilter; knn_mean is then the dot form's; "dot_split"
+        likewise on the bf16 matrix unit, float32 rows only, no set_rows, knn_mean that form's own.  Under
         "dot" X may be bfloat16 (ops.knn's bfloat16 rows): the hypergraph and knn_dist (float32) are those of X.float()."""
         from . import knn_graph as _knn
         Xd = torch.as_tensor(X).detach()

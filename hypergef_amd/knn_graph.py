@@ -30,8 +30,8 @@ from .synth import Incidence
 
 K_MAX = 64        # include/hg_aggr.h: k in 1 .. 64
 SLICES_MAX = 32   # cand_slices in 0 .. 32
-FORMS = ("difference", "dot")
-DOT_F_MAX = 65536  # form="dot": the widest rows the error bound is derived for (hg_knn.h, kDotMaxF)
+FORMS = ("difference", "dot", "dot_split")
+DOT_F_MAX = 65536  # form="dot" and "dot_split": the widest rows the error bound is derived for (hg_knn.h, kDotMaxF)
 
 
 _NO_FORM = " (%s has no float16 / float64 form; bfloat16 rows need Options.incidence_bf16 = 'rows')"
@@ -112,6 +112,15 @@ def knn(X, k, queries=None, segments=None, self_first=None, return_mean=False, c
     the same arguments; the prefilter runs on the bf16 matrix unit under its own bound E1b (include/hg_aggr.h), mean is
     the mean of those estimates, and everything else above holds.  Under every other form bfloat16 is refused.
 
+    form="dot_split" (hg_knn_dot_split_f32; float32 rows only): "dot" with the prefilter's sums on the bf16 matrix unit.  Every
+    element is split into two bfloat16 parts in registers, q = qh + ql + a remainder below 2^-16 |q|, and the estimate sums
+    qh.xh + qh.xl + ql.xh, three bf16 instructions per 16 columns in place of eight f32 ones.  idx and dist are form=
+    "difference"'s for the same arguments, bit for bit, on every input, and dist never holds an estimate: the looser estimate
+    only shortlists, under its own bound E1s (include/hg_aggr.h).  queries, self_first, cand_slices, return_fallback and
+    return_mean behave as under "dot"; mean is this form's own, the float32 mean over all candidates of sqrt(max(d~, 0)) of its
+    estimates -- within mean_j sqrt(E1s(i)) + the float32 summation error of the float64 mean, one bit pattern per cand_slices.
+    It neither waits nor reads back; it takes no segments, no set_rows and rows of at most 65536 columns.
+
     set_rows = m: X is B = n / m point sets of exactly m consecutive rows each -- the batch of equal-sized point clouds of
     DGCNN / DHGNN -- and row i competes with rows (i // m) * m .. (i // m) * m + m - 1 only (hg_knn_sets_f32,
     hg_knn_dot_sets_f32 / _bf16).  No offsets exist, on the host or on the device: the call neither waits nor reads back
@@ -127,8 +136,8 @@ def knn(X, k, queries=None, segments=None, self_first=None, return_mean=False, c
     Not differentiable: raises if X (or queries) requires a gradient while grad mode is on; call it under
     torch.no_grad() or on X.detach().  Refusals, in this order and before a device is touched: TypeError for anything
     but float32 (or, under form="dot", bfloat16 for X and queries alike); ValueError for an unknown form, for k outside
-    1 .. min(64, n), for segments or self_first together with queries, for form="dot" with segments or with F above
-    65536, for a segment shorter than k, for cand_slices, and then for set_rows: not an integer, k above it, n no
+    1 .. min(64, n), for segments or self_first together with queries, for form="dot" or "dot_split" with segments, "dot_split" with
+    set_rows, either with F above 65536, for a segment shorter than k, for cand_slices, and then for set_rows: not an integer, k above it, n no
     multiple of it, together with queries or with segments; RuntimeError for CPU tensors."""
     bf16 = form == "dot" and isinstance(X, torch.Tensor) and X.dtype == torch.bfloat16
     if bf16:
@@ -155,13 +164,16 @@ def knn(X, k, queries=None, segments=None, self_first=None, return_mean=False, c
             raise ValueError("self_first cannot be combined with queries (a query row is no candidate)")
         if queries.dim() != 2 or queries.shape[1] != F or queries.shape[0] < 1:
             raise ValueError("queries must be [nq >= 1, F = %d], got %s" % (F, tuple(queries.shape)))
-    if form == "dot":
+    if form in ("dot", "dot_split"):
         if segments is not None:
-            raise ValueError('form="dot" cannot be combined with segments (batches of point sets have narrow rows: use '
-                             'form="difference")')
+            raise ValueError('form="%s" cannot be combined with segments (batches of point sets have narrow rows: use '
+                             'form="difference")' % form)
+        if form == "dot_split" and set_rows is not None:
+            raise ValueError('form="dot_split" cannot be combined with set_rows (uniform sets are searched under "difference" '
+                             'and "dot")')
         if F > DOT_F_MAX:
-            raise ValueError('form="dot" takes rows of at most %d columns (the width its error bound is derived for), got '
-                             "F = %d" % (DOT_F_MAX, F))
+            raise ValueError('form="%s" takes rows of at most %d columns (the width its error bound is derived for), got '
+                             "F = %d" % (form, DOT_F_MAX, F))
     seg = None if segments is None else _segment_offsets(segments, n, k)
     if not isinstance(cand_slices, numbers.Integral) or isinstance(cand_slices, bool) or not 0 <= cand_slices <= SLICES_MAX:
         raise ValueError("cand_slices must be 0 (auto) or 1 .. %d, got %r" % (SLICES_MAX, cand_slices))
@@ -209,11 +221,14 @@ def knn(X, k, queries=None, segments=None, self_first=None, return_mean=False, c
                 _lib.check(L.hg_knn_sets_f32(_ptr(X), n, F, k, set_rows, 1 if self_first else 0, cand_slices, _ptr(idx),
                                              _ptr(dist), _ptr(mean), _ptr(ws), ws_bytes, _stream_handle(dev)))
             fallback = torch.zeros(nq, dtype=torch.int32, device=dev) if return_fallback else None
-    elif form == "dot":
+    elif form in ("dot", "dot_split"):
         fallback = torch.empty(nq, dtype=torch.int32, device=dev) if return_fallback else None
         if bf16 and not hasattr(L, "hg_knn_dot_bf16"):
             raise RuntimeError("this build of libhgaggr has no hg_knn_dot_bf16 (bfloat16 rows under form=\"dot\")")
+        if form == "dot_split" and not hasattr(L, "hg_knn_dot_split_f32"):
+            raise RuntimeError("this build of libhgaggr has no hg_knn_dot_split_f32 (form=\"dot_split\")")
         entry, sizes = ((L.hg_knn_dot_bf16, L.hg_knn_dot_bf16_workspace_bytes) if bf16 else
+                        (L.hg_knn_dot_split_f32, L.hg_knn_dot_workspace_bytes) if form == "dot_split" else
                         (L.hg_knn_dot_f32, L.hg_knn_dot_workspace_bytes))
         ws_bytes = sizes(nq, n, F, k, cand_slices)
         ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
@@ -1247,7 +1262,7 @@ class KnnHypergraph:
       attention(node_score, edge_score, group="hyperedge", negative_slope=0.2, heads=1, dropout=0.0, training=True,
         rng_state=None): ops.knn_softmax over the table with the stored transpose: alpha [N, k], or [N, k, H]; dropout,
         training and rng_state are ops.knn_softmax's (the coefficients after dropout, from the softmax's own launch).
-    form: ops.knn's -- "dot" gives the same idx and dist through the matrix-unit prefilter, and its own mean.  Under "dot" X
+    form: ops.knn's -- "dot" and "dot_split" give the same idx and dist through a matrix-unit prefilter, and their own mean.  Under "dot" X
     may be bfloat16: the table, dist, mean, transpose and degrees are int32 / float32 as always, and aggregate / weights take
     bfloat16 Z / X where `options` (or the caller's) has Options.incidence_bf16 = 'rows' -- ops.knn_aggr's and ops.knn_dist's
     bfloat16 rows, the weights float32."""

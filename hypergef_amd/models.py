@@ -148,7 +148,8 @@ class DynamicHypergraphConv(nn.Module):
     torch, so the layer can be recorded into a hipGraph (torch.cuda.graph) and the neighbours are searched again on every
     replay.  With segments, ops.knn still waits once for its offsets: a layer with segments runs eagerly only.  False (the
     default) is the layer above, untouched.  knn_form: ops.knn's `form` -- "dot" searches the same neighbours through the
-    matrix-unit prefilter (no segments); with probabilistic=True the weights then use the dot form's mean.
+    matrix-unit prefilter (no segments); with probabilistic=True the weights then use the dot form's mean.  "dot_split" is
+    "dot" with float32 rows split onto the bf16 matrix unit: the same neighbours and distances, no segments, no set_rows.
     set_rows = m: ops.knn's -- the input is a batch of N / m point sets of exactly m rows each, every set its own hypergraph,
     with no offsets anywhere.  Wherever this text says "with segments=None" it holds with set_rows too: under
     device_graph=True the layer waits nowhere and is recorded into a hipGraph, replaying the search -- float32 under either

@@ -921,6 +921,43 @@ HG_API size_t hg_knn_dot_bf16_workspace_bytes(int32_t nq, int32_t n, int32_t F, 
 HG_API int hg_knn_dot_estimates_bf16(const uint16_t *Q, int32_t nq, const uint16_t *X, int32_t n, int32_t F, float *est,
                                      float *e1, hg_stream_t stream);
 
+/* hg_knn_dot_f32 with the prefilter's sums on v_mfma_f32_32x32x16_bf16: float32 rows, every element split into two bfloat16
+ * parts (csrc/hg_knn_dot.hip).  idx and dist are hg_knn_f32's -- and so hg_knn_dot_f32's -- for the same
+ * arguments, BIT FOR BIT, on every input; dist never holds an estimate.  Everything said of hg_knn_dot_f32 holds -- the
+ * parameters, kp, the shortlists, self_first, cand_slices, fallback, the workspace (hg_knn_dot_workspace_bytes), five
+ * launches, nothing allocated, copied or waited for, the refusals and their order -- with this estimate and this bound:
+ *   n2[j] is hg_knn_dot_f32's norm of the unsplit row, bit for bit.  For an element q: qh = bf16(q), ql = bf16(q - qh), both
+ *   round to nearest even (q - qh is exact in float32), qr = q - qh - ql; likewise x.  The split rows exist in registers and
+ *   LDS only.  s~(i, j) is accumulated by 3 G instructions, G = ceil(F / 16), into one accumulator: for g = 0 .. G - 1,
+ *   ascending, qh.xh, then qh.xl, then ql.xh over columns 16 g .. 16 g + 15 (zeros past F), in every tiling;
+ *   d~ = (n2q[i] + n2[j]) - 2 s~.  The products of the parts are exact in float32.
+ *   What the three terms leave out is ql xl + (qh + ql) xr + qr x per column, at most
+ *     2^-16 ((1 + 2^-8)^2 + (1 + 2^-16) + 1) |q_c x_c| <= 3.00785 2^-16 |q_c x_c| < 771 u |q_c x_c|,  u = 2^-24;
+ *   the sum of the magnitudes of the products that are taken is at most (1 + 2^-8)^2 (1 + 2^-7) sum |q_c x_c| <= 1.0157 sum |q_c x_c|,
+ *   and under hg_knn_dot_bf16's HYPOTHESIS H the 3 G instructions err by at most ((1 + 17 v)^(3 G) - 1) times that,
+ *   <= 102 G u 1.0126 * 1.0157 sum |q_c x_c| for G <= 4096.  With sum |q_c x_c| <= (Nq + Nx) / 2 and the norms' F-term fma
+ *   chains as for E1,
+ *     E1s = C_s u (n2q[i] + max_j n2[j]) + (328 G + 1) 2^-126,   C_s = (775 + F + 104 G)(1 + 1/64) rounded up to an integer,
+ *     Ei  = E1s + (F + 4) u max(T, 0).
+ *   The absolute term: a part below 2^-126 in magnitude may be rounded with an absolute error, flushed by the conversion or read
+ *   as zero by the matrix unit, so an element's two parts move it by at most 4 * 2^-126; against the other operand (|x| <=
+ *   (1 + x^2) / 2) that is at most 1.012 * 2^-124 (F + (Nq + Nx) / 2) on s~ -- 130 G 2^-126 on d~, the part with the norms far
+ *   inside C_s's margin; a matrix unit that flushes subnormal products and partial sums loses 32 quantities of at most 2^-126
+ *   per instruction, 2 * 96 G * (1 + 17 v)^(3 G) <= 197 G on d~; the last 2^-126 is E1b's, for the vector operations.
+ *   The certificate is hg_knn_dot_f32's with E1s: the k-th d2 strictly below T - Ei, or n <= kp; and n2q + n2max < 1e37 -- which
+ *   fails every row once an element is so large that its hi part rounds to infinity -- and every shortlist slot filled.
+ * mean_dist: the mean of these estimates, within mean_j sqrt(E1s) and the float32 summation error of the exact mean; one bit
+ * pattern per cand_slices, not hg_knn_dot_f32's.  Q and X are 4-byte aligned; rows that are 16-byte aligned (and F % 4 == 0)
+ * are read with 16-byte loads, others element by element, with the same results. */
+HG_API int hg_knn_dot_split_f32(const float *Q, int32_t nq, const float *X, int32_t n, int32_t F, int32_t k, int32_t self_first,
+                                int32_t cand_slices, int32_t *idx, float *dist, float *mean_dist, int32_t *fallback,
+                                void *workspace, size_t workspace_bytes, hg_stream_t stream);
+/* hg_knn_dot_estimates_bf16 for the split form on float32 rows (Q, X 4-byte aligned): est [nq, n] receives every pair's raw
+ * d~ from the device code that forms hg_knn_dot_split_f32's tiles and e1 [nq] the rows' E1s; |est - d2_exact| <= e1 must
+ * hold for every pair.  A diagnostic: it allocates and waits as that entry does, and refuses what it refuses. */
+HG_API int hg_knn_dot_estimates_split_f32(const float *Q, int32_t nq, const float *X, int32_t n, int32_t F, float *est,
+                                          float *e1, hg_stream_t stream);
+
 /* UNIFORM SETS: X [n, F] is B = n / set_rows point sets of exactly set_rows = m consecutive rows each, and row i competes
  * with rows (i / m) m .. (i / m) m + m - 1 only (Q is X).  There is no offsets array, on the host or on the device: nothing
  * is copied and nothing is waited for under either form, and every entry is recordable into a hipGraph.  idx holds row
