@@ -13,6 +13,10 @@
 // A vertex segment of more than HG_TABLE_SEQ_MAX entries is taken by the whole workgroup, slab after slab, in the same
 // launch.  No workspace, no atomics, no host list.
 //
+// Statistics (kBodyStats, hg_table_attention_stats_heads_f32): the softmax body stopped after its sum pass -- the same lanes,
+// entries, butterflies and workgroup join, so the maximum m and inv = 1 / sum it stores per (segment, head) are the numbers
+// the softmax multiplies with.  hg_table_attention.hip's gathers form alpha from them.
+//
 // Attention dropout (DROP, the hg_table_softmax_dropout_*_heads_f32 entries): a compile-time variant of the softmax and of its
 // backward -- the same ownership, lanes, passes and reductions, so alpha, ds and dgroup keep their bits.  The mask of
 // hg_philox.h is a function of (rng, p, h) alone.  A thread loads the two state words once, ahead of every segment.  The
@@ -51,7 +55,7 @@ constexpr int kSoftMinL = 8;                         // side 1: the narrowest la
 constexpr int kSoftKeep = kTableSeqMax / kSoftMinL;  // side 1: entries a lane keeps in registers, each HV heads wide
 constexpr int kMaxHV = 4;
 
-enum { kBodySoftmax = 0, kBodySoftmaxBwd = 1, kBodySum = 2 };
+enum { kBodySoftmax = 0, kBodySoftmaxBwd = 1, kBodySum = 2, kBodyStats = 3 };
 
 // V consecutive floats, one 16-byte access where V == 4
 template <int V>
@@ -95,6 +99,7 @@ struct HeadsSoftmaxArgs {
   float slope;
   int32_t rows, k, n, entries, nseg, H;
   int32_t L, R;                      // lanes per segment, segments per wave
+  float *out_inv;                    // stats: 1 / the segment's sum, beside its maximum in out_seg; [segments, H]
 };
 
 template <int SIDE>
@@ -209,7 +214,7 @@ __device__ __forceinline__ void group_segment(const HeadsSoftmaxArgs &a, const D
 #pragma unroll
   for (int u = 0; u < NS; ++u) pp[u] = -1;
 
-  if constexpr (BODY == kBodySoftmax) {
+  if constexpr (BODY == kBodySoftmax || BODY == kBodyStats) {
     float x[NS][HV], m[HV], s[HV], o4[HV];
 #pragma unroll
     for (int i = 0; i < HV; ++i) m[i] = -INFINITY;
@@ -243,6 +248,18 @@ __device__ __forceinline__ void group_segment(const HeadsSoftmaxArgs &a, const D
     float inv[HV];  // the maximum's entry contributes exp(0) = 1: s >= 1 wherever inv is used
 #pragma unroll
     for (int i = 0; i < HV; ++i) inv[i] = 1.f / s[i];
+    if constexpr (BODY == kBodyStats) {  // s == 0: no candidate added anything, and nothing reads the pair
+#pragma unroll
+      for (int i = 0; i < HV; ++i) {
+        o4[i] = s[i] == 0.f ? 0.f : m[i];
+        inv[i] = s[i] == 0.f ? 0.f : inv[i];
+      }
+      if (act && cl == 0) {
+        vec_store<HV>(a.out_seg + (size_t)seg * H + h0, o4);
+        vec_store<HV>(a.out_inv + (size_t)seg * H + h0, inv);
+      }
+      return;
+    }
 #pragma unroll
     for (int u = 0; u < NS; ++u) {
       const bool on = cl + u * L < len;
@@ -342,7 +359,7 @@ __device__ __forceinline__ void block_segment(const HeadsSoftmaxArgs &a, const D
   Vec<HV> own{};
   if (BODY != kBodySum && a.node) own = vec_load<HV>(a.node + (size_t)seg * H + h0);
   int p, j;
-  if constexpr (BODY == kBodySoftmax) {
+  if constexpr (BODY == kBodySoftmax || BODY == kBodyStats) {
     float m[HV], s[HV], inv[HV], o4[HV];
 #pragma unroll
     for (int i = 0; i < HV; ++i) m[i] = -INFINITY;
@@ -367,6 +384,18 @@ __device__ __forceinline__ void block_segment(const HeadsSoftmaxArgs &a, const D
     block_join<false, HV>(s, slot, buf, w, lane);
 #pragma unroll
     for (int i = 0; i < HV; ++i) inv[i] = 1.f / s[i];
+    if constexpr (BODY == kBodyStats) {
+#pragma unroll
+      for (int i = 0; i < HV; ++i) {
+        o4[i] = s[i] == 0.f ? 0.f : m[i];
+        inv[i] = s[i] == 0.f ? 0.f : inv[i];
+      }
+      if (t == 0) {
+        vec_store<HV>(a.out_seg + (size_t)seg * H + h0, o4);
+        vec_store<HV>(a.out_inv + (size_t)seg * H + h0, inv);
+      }
+      return;
+    }
     for (unsigned o = t; o < len; o += kSoftBlock) {
       const bool ok = seg_entry<1>(a, beg + (int)o, true, p, j);
       const Vec<HV> raw = seg_raw<1, HV>(a, own, p, j, h0);
@@ -446,7 +475,7 @@ __global__ __launch_bounds__(kSoftBlock) void table_softmax_heads_kernel(HeadsSo
   DropT drop{};
   if constexpr (DROP) drop = Drop{drop_rng(a.rng[0], a.rng[1]), a.T, a.scale};  // both state words, once per thread
 
-  if constexpr (SIDE == 1 && BODY != kBodySum) {
+  if constexpr (SIDE == 1 && BODY != kBodySum && BODY != kBodyStats) {
     // the positions no vertex owns, every head of them: this workgroup's slice of the table
     const int64_t chunk = ((int64_t)a.entries + gridDim.x - 1) / gridDim.x;
     const int64_t pb = (int64_t)blockIdx.x * chunk, pe = min(pb + chunk, (int64_t)a.entries);
@@ -510,7 +539,7 @@ int launch_softmax_heads(const char *entry, int side, HeadsSoftmaxArgs a, hg_str
   a.L = side ? std::max(kSoftMinL, pow2_at_least(a.k)) : pow2_at_least(a.k);  // the single-head call's, per head
   a.R = 64 / a.L;
   const int RW = a.R * kTableWaves;
-  const bool slab4 = a.H % 4 == 0 && aligned16({a.node, a.edge, a.entry, a.val, a.dval, a.out_entry, a.out_seg, a.out_drop});
+  const bool slab4 = a.H % 4 == 0 && aligned16({a.node, a.edge, a.entry, a.val, a.dval, a.out_entry, a.out_seg, a.out_drop, a.out_inv});
   const dim3 grid((unsigned)(((int64_t)a.nseg + RW - 1) / RW)), block(kSoftBlock);
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (side && slab4) hipLaunchKernelGGL((table_softmax_heads_kernel<1, BODY, 4, DROP>), grid, block, 0, s, a);
@@ -947,6 +976,22 @@ int hg_table_sum_heads_f32(const int32_t *idx, int32_t rows, int32_t k, int32_t 
   a.val = val;
   a.out_seg = out;
   return launch_softmax_heads<kBodySum>(entry, side, a, stream);
+}
+
+int hg_table_attention_stats_heads_f32(const int32_t *idx, int32_t rows, int32_t k, int32_t n, int32_t heads, int32_t group,
+                                       const float *node_score, const float *edge_score, float slope, const int32_t *ptr_v,
+                                       const int32_t *pos_v, float *seg_max, float *seg_inv, hg_stream_t stream) {
+  using namespace hg;
+  const char *entry = "hg_table_attention_stats_heads_f32";
+  if (const int st = softmax_refusal(entry, idx, rows, k, n, heads, group, "group", ptr_v, pos_v,
+                                     seg_max && seg_inv && (node_score || edge_score),
+                                     "null seg_max or seg_inv, or node_score and edge_score both null",
+                                     {node_score, edge_score, seg_max, seg_inv}))
+    return st;
+  HeadsSoftmaxArgs a = softmax_args(idx, rows, k, n, heads, node_score, edge_score, nullptr, slope, ptr_v, pos_v);
+  a.out_seg = seg_max;
+  a.out_inv = seg_inv;
+  return launch_softmax_heads<kBodyStats>(entry, group, a, stream);
 }
 
 int hg_table_gather_heads_f32(const int32_t *idx, int32_t rows, int32_t k, int32_t n, int32_t F, int32_t heads, const float *src,

@@ -17,6 +17,8 @@ or per vertex, with exact gradients: its alpha is `knn_aggr`'s weight.  Several 
 scores with the head as their last dimension, and `knn_aggr` a weight [rows, k, H]; every head in the same launch and with the
 single-head call's bits.  `knn_softmax(dropout=p)` drops coefficients inside the softmax launch and its backward
 (hg_table_softmax_dropout_*_heads_f32): a Philox mask that is never stored.
+`knn_attention_aggr` (`ops.knn_attention_aggr`; hg_table_attention_*) is `knn_aggr` on `knn_softmax`'s alpha in one call, bit
+for bit, without alpha: two statistics per segment and head, and every coefficient formed inside the gather that uses it.
 """
 import ctypes
 import numbers
@@ -1243,6 +1245,161 @@ def knn_aggr(idx, X, weight=None, degE=None, degV=None, transpose=None, weight_g
     return _KnnAggr.apply(X, w, idx, ptr_v, pos_v, degE, degV, H)
 
 
+def _attention_entry(name):
+    """An hg_table_attention_* entry of the library; a build without it is an error, never another path."""
+    L = _lib.lib()
+    if not hasattr(L, name):
+        raise RuntimeError("this build of libhgaggr has no %s (fused attention aggregation over a neighbour table)" % name)
+    return getattr(L, name)
+
+
+def table_attention_stats(idx, n, group, node_score=None, edge_score=None, slope=0.2, ptr_v=None, pos_v=None, heads=1):
+    """(seg_max, seg_inv) of hg_table_attention_stats_heads_f32, both [segments, heads] -- segments = rows for 'hyperedge', n for
+    'vertex': table_softmax's maximum and reciprocal sum per segment and head, bit for bit.  No checks, no gradient."""
+    rows, k = idx.shape
+    nseg = rows if group == "hyperedge" else n
+    seg_max = torch.empty((nseg, heads), dtype=torch.float32, device=idx.device)
+    seg_inv = torch.empty_like(seg_max)
+    with torch.cuda.device(idx.device):
+        _lib.check(_attention_entry("hg_table_attention_stats_heads_f32")(
+            _ptr(idx), rows, k, n, heads, _GROUPS[group], _ptr(node_score), _ptr(edge_score), slope, _ptr(ptr_v), _ptr(pos_v),
+            _ptr(seg_max), _ptr(seg_inv), _stream_handle(idx.device)))
+    return seg_max, seg_inv
+
+
+def table_attention_gather(idx, ptr_v, pos_v, n, src, group, node_score, edge_score, slope, seg_max, seg_inv, src_scale=None,
+                           dst_scale=None, heads=1, transposed=False):
+    """One hop of the fused attention aggregation: table_gather (transposed=False: src [n, F] -> [rows, F]) or table_gather_t
+    (src [rows, F] -> [n, F]) with w = table_softmax's alpha, formed inside hg_table_attention_gather(_t)_heads_f32 from the
+    scores and table_attention_stats' pair.  No checks, no gradient."""
+    rows, k = idx.shape
+    F = src.shape[1]
+    dst = torch.empty((n if transposed else rows, F), dtype=torch.float32, device=idx.device)
+    tail = (rows, k, n, F, heads, _GROUPS[group], _ptr(src), _ptr(node_score), _ptr(edge_score), slope, _ptr(seg_max),
+            _ptr(seg_inv), _ptr(src_scale), _ptr(dst_scale), _ptr(dst), _stream_handle(idx.device))
+    with torch.cuda.device(idx.device):
+        if transposed:
+            _lib.check(_attention_entry("hg_table_attention_gather_t_heads_f32")(_ptr(ptr_v), _ptr(pos_v), _ptr(idx), *tail))
+        else:
+            _lib.check(_attention_entry("hg_table_attention_gather_heads_f32")(_ptr(idx), *tail))
+    return dst
+
+
+class _KnnAttentionAggr(torch.autograd.Function):
+    """knn_aggr(X, alpha, weight_grad=True) on alpha = knn_softmax(node_score, edge_score) as one node that never holds alpha
+    between forward and backward.  Saves X, the scores, the two statistics per segment and head, the scales, the table and its
+    transpose.  Where only X wants a gradient the backward is the two fused gathers swapped.  Where a score wants one it forms
+    alpha again with the softmax kernel (the bits the gathers used), runs _KnnAggr's dX / dw formulas and _KnnSoftmax's backward
+    on the existing kernels, and frees alpha: every gradient has the two-call path's bits."""
+
+    @staticmethod
+    def forward(ctx, X, node_score, edge_score, idx, ptr_v, pos_v, degE, degV, group, slope, heads):
+        n = X.shape[0]
+        ctx.group, ctx.slope, ctx.heads = group, slope, heads
+        seg_max, seg_inv = table_attention_stats(idx, n, group, node_score, edge_score, slope, ptr_v, pos_v, heads)
+        call = (group, node_score, edge_score, slope, seg_max, seg_inv)
+        Xe = table_attention_gather(idx, ptr_v, pos_v, n, X, *call, None, degE, heads)
+        Y = table_attention_gather(idx, ptr_v, pos_v, n, Xe, *call, None, degV, heads, transposed=True)
+        need_score = ctx.needs_input_grad[1] or ctx.needs_input_grad[2]
+        ctx.save_for_backward(X if need_score else None, node_score, edge_score, seg_max, seg_inv, idx, ptr_v, pos_v, degE, degV)
+        return Y
+
+    @staticmethod
+    def backward(ctx, dY):
+        X, node_score, edge_score, seg_max, seg_inv, idx, ptr_v, pos_v, degE, degV = ctx.saved_tensors
+        dY = dY.contiguous()
+        n, k, H, group = dY.shape[0], idx.shape[1], ctx.heads, ctx.group
+        need_x, need_node, need_edge = ctx.needs_input_grad[:3]
+        tail = (None,) * 8
+        if not (need_node or need_edge):  # dX alone: the adjoint is the fused pair itself, swapped
+            call = (group, node_score, edge_score, ctx.slope, seg_max, seg_inv)
+            G = table_attention_gather(idx, ptr_v, pos_v, n, dY, *call, degV, degE, H)
+            return (table_attention_gather(idx, ptr_v, pos_v, n, G, *call, None, None, H, transposed=True), None, None, *tail)
+        alpha = table_softmax(idx, n, group, node_score, edge_score, None, ctx.slope, ptr_v, pos_v, H)
+        G = table_gather(idx, dY, alpha, degV, degE, heads=H)
+        Xe = table_gather(idx, X, alpha, None, degE, heads=H)
+        dalpha = table_dot(idx, dY, Xe, degV, X, G, heads=H).view(alpha.shape)
+        del Xe  # before dX is allocated: one [rows, F] array fewer at the backward's peak
+        dX = table_gather_t(ptr_v, pos_v, k, G, alpha, heads=H) if need_x else None
+        del G
+        hyperedge = group == "hyperedge"
+        need_own, need_other = (need_edge, need_node) if hyperedge else (need_node, need_edge)
+        ds, d_own = table_softmax_bwd(idx, n, group, alpha, dalpha, node_score, edge_score, None, ctx.slope, ptr_v, pos_v,
+                                      want_group=need_own, heads=H)
+        del alpha, dalpha
+        d_other = table_sum(idx, n, "vertex" if hyperedge else "hyperedge", ds, ptr_v, pos_v, H) if need_other else None
+        d_edge, d_node = (d_own, d_other) if hyperedge else (d_other, d_own)
+        return (dX, d_node, d_edge, *tail)
+
+
+def knn_attention_aggr(idx, X, node_score=None, edge_score=None, group="hyperedge", negative_slope=0.2, degE=None, degV=None,
+                       transpose=None, heads=1):
+    """Hypergraph attention's aggregation over a neighbour table in one call: what
+        knn_aggr(idx, X, knn_softmax(idx, node_score, edge_score, group, negative_slope, heads=heads), degE, degV,
+                 weight_grad=True)
+    returns, bit for bit, with no [rows, k, heads] array formed in the forward and none saved for the backward.  Forward: one
+    launch of hg_table_attention_stats_heads_f32 -- the softmax's maximum and reciprocal sum per segment and head, two
+    [rows, heads] or [n, heads] arrays -- and the two fused gathers hg_table_attention_gather_heads_f32 /
+    hg_table_attention_gather_t_heads_f32, which form every coefficient from the two scores and those two numbers as they
+    gather the row (csrc/hg_table_attention.hip: once per wave in LDS where the lanes of a row share a head, else per lane).
+    idx [rows, k] int32; X [n, F] float32; node_score [n] / [n, heads], edge_score [rows] / [rows, heads], either may be None,
+    not both; degE [rows] or [rows, 1], degV [n] or [n, 1] or None; transpose: ops.knn_transpose(idx, n) to reuse.
+    Gradients are exact for X and both scores and have the two-call path's bits.  Where only X wants one, the backward is the
+    two fused gathers swapped; where a score wants one, it forms alpha again with the softmax kernel, runs knn_aggr's and
+    knn_softmax's backward kernels on it, and frees it before returning.  degE and degV get no gradient, as in knn_aggr.
+    Nothing waits and nothing is read back.
+    float32 only.  Not covered, use the two calls above: a logit per entry (entry_score is itself a [rows, k, heads] array),
+    attention dropout, bfloat16 rows.
+    Refusals, in this order and before a device is touched: TypeError for an idx (ptr_v, pos_v) that is not int32 and for an X,
+    score, degE or degV that is not float32; ValueError for an unknown group, for heads, for the shapes and k, for F no
+    multiple of heads, for no score at all; RuntimeError for a degE or degV that requires a gradient, and for CPU tensors.  A
+    build of the library without the entries raises RuntimeError: there is no other path."""
+    _table_shape(idx)
+    _check_dtype(X, "X", torch.float32, " (knn_attention_aggr has no bfloat16, float16 or float64 form)")
+    scores = (("node_score", node_score), ("edge_score", edge_score))
+    scales = (("degE", degE), ("degV", degV))
+    for name, t in scores + scales:
+        if t is not None:
+            _check_dtype(t, name, torch.float32)
+    _check_transpose_types(transpose)
+    if group not in _GROUPS:
+        raise ValueError("group must be 'hyperedge' or 'vertex', got %r" % (group,))
+    H = _heads_value(heads)
+    tail = (H,) if H > 1 else ()
+    rows, k = _table_shape_values(idx)
+    if X.dim() != 2 or X.shape[0] < 1 or X.shape[1] < 1:
+        raise ValueError("X must be [n >= 1, F >= 1], got %s" % (tuple(X.shape),))
+    n, F = X.shape
+    if F % H:
+        raise ValueError("X has F = %d columns, no multiple of heads = %d" % (F, H))
+    if node_score is None and edge_score is None:
+        raise ValueError("knn_attention_aggr needs at least one of node_score and edge_score")
+    for name, t, count in (("node_score", node_score, n), ("edge_score", edge_score, rows)):
+        if t is not None and tuple(t.shape) != (count, *tail):
+            raise ValueError("%s must be %s, got %s" % (name, list((count, *tail)), tuple(t.shape)))
+    for name, t, count in (("degE", degE, rows), ("degV", degV, n)):
+        if t is not None and tuple(t.shape) not in ((count,), (count, 1)):
+            raise ValueError("%s must be [%d] or [%d, 1], got %s" % (name, count, count, tuple(t.shape)))
+    _check_transpose_shapes(transpose, n, rows * k)
+    if torch.is_grad_enabled():
+        for name, t in scales:
+            if t is not None and t.requires_grad:
+                raise RuntimeError("%s gets no gradient from knn_attention_aggr: pass %s.detach()" % (name, name))
+    _check_table_index(idx, "idx")
+    _check_feat(X, "X", device=idx.device)
+    for name, t in scores + scales:
+        if t is not None:
+            _check_feat(t, name, device=idx.device)
+    _attention_entry("hg_table_attention_gather_heads_f32")
+    if transpose is None:
+        transpose = knn_transpose(idx, n)
+    ptr_v, pos_v = transpose
+    _check_table_index(ptr_v, "ptr_v")
+    _check_table_index(pos_v, "pos_v")
+    degE, degV = (None if t is None else t.detach() for _, t in scales)
+    return _KnnAttentionAggr.apply(X, node_score, edge_score, idx, ptr_v, pos_v, degE, degV, group, float(negative_slope), H)
+
+
 class KnnHypergraph:
     """The hypergraph "each vertex and its k - 1 nearest neighbours" as a device-only object: what HyperGraph.from_knn builds,
     without the read-back, the host transpose and the plan.  Nothing here reads a tensor back; with segments=None nothing
@@ -1262,6 +1419,9 @@ class KnnHypergraph:
       attention(node_score, edge_score, group="hyperedge", negative_slope=0.2, heads=1, dropout=0.0, training=True,
         rng_state=None): ops.knn_softmax over the table with the stored transpose: alpha [N, k], or [N, k, H]; dropout,
         training and rng_state are ops.knn_softmax's (the coefficients after dropout, from the softmax's own launch).
+      attention_aggregate(Z, node_score, edge_score, group="hyperedge", negative_slope=0.2, heads=1): ops.knn_attention_aggr
+        with the stored table, transpose and degrees -- aggregate(Z, weight=attention(..), heads=heads), bit for bit, with no
+        [N, k, heads] array in the forward or kept for the backward.
     form: ops.knn's -- "dot" and "dot_split" give the same idx and dist through a matrix-unit prefilter, and their own mean.  Under "dot" X
     may be bfloat16: the table, dist, mean, transpose and degrees are int32 / float32 as always, and aggregate / weights take
     bfloat16 Z / X where `options` (or the caller's) has Options.incidence_bf16 = 'rows' -- ops.knn_aggr's and ops.knn_dist's
@@ -1308,6 +1468,10 @@ class KnnHypergraph:
                   training=True, rng_state=None):
         return knn_softmax(self.idx, node_score, edge_score, group, negative_slope, transpose=(self.ptr_v, self.pos_v),
                            num_nodes=self.num_nodes, heads=heads, dropout=dropout, training=training, rng_state=rng_state)
+
+    def attention_aggregate(self, Z, node_score=None, edge_score=None, group="hyperedge", negative_slope=0.2, heads=1):
+        return knn_attention_aggr(self.idx, Z, node_score, edge_score, group, negative_slope, self.degE, self.degV,
+                                  transpose=(self.ptr_v, self.pos_v), heads=heads)
 
 
 def table_seq_max():

@@ -194,15 +194,28 @@ class DynamicHypergraphConv(nn.Module):
     ones scaled by 1 / (1 - p), inside the table softmax's own launch and its backward (ops.knn_softmax(dropout=p)): no mask
     is stored and alpha is not passed over again.  The mask follows torch.manual_seed.  No parameter and no buffer is added;
     eval() and dropout = 0.0 are the layer above, bit for bit.  With segments=None or set_rows the layer still waits nowhere
-    and is recorded into a hipGraph: the state's draw is recorded with it, so every replay has a new mask."""
+    and is recorded into a hipGraph: the state's draw is recorded with it, so every replay has a new mask.
+    fused_attention=True (needs attention set and dropout = 0.0): hyperg.attention_aggregate(Z, sv, se, ..) in place of
+    hyperg.attention and hyperg.aggregate -- ops.knn_attention_aggr, the coefficients formed inside the two gathers
+    (hg_table_attention_*), so alpha [N, k, H] is neither written in the forward nor kept for the backward.  The same
+    parameters, the same state_dict, and the same output and gradients, bit for bit; still nothing waits and the layer is
+    still recorded into a hipGraph.  Attention dropout is the unfused path's (ValueError here).  False (the default) is the
+    layer above, untouched."""
 
     def __init__(self, in_channels, out_channels, k, probabilistic=False, segments=None, m_prob=1.0, options=None,
                  device_graph=False, knn_form="difference", learn_distances=False, first_aggr="sum", second_aggr="sum",
-                 attention=None, negative_slope=0.2, heads=1, concat=True, set_rows=None, dropout=0.0):
+                 attention=None, negative_slope=0.2, heads=1, concat=True, set_rows=None, dropout=0.0, fused_attention=False):
         super().__init__()
         self.dropout = ops._dropout_p(dropout)
         if self.dropout > 0.0 and attention is None:
             raise ValueError("dropout=%r needs attention='hyperedge' or 'vertex' (it drops attention coefficients)" % (dropout,))
+        self.fused_attention = bool(fused_attention)
+        if self.fused_attention and attention is None:
+            raise ValueError("fused_attention=True needs attention='hyperedge' or 'vertex' (it forms the attention coefficients "
+                             "inside the aggregation)")
+        if self.fused_attention and self.dropout > 0.0:
+            raise ValueError("fused_attention=True has no attention dropout (the coefficients are never stored): dropout=%r needs "
+                             "the unfused path, fused_attention=False" % (dropout,))
         if isinstance(heads, bool) or not isinstance(heads, int) or heads < 1:
             raise ValueError("heads must be an integer >= 1, got %r" % (heads,))
         if heads > 1 and attention is None:
@@ -258,12 +271,17 @@ class DynamicHypergraphConv(nn.Module):
             sv = (Zh * self.a_v.view(H, C)).sum(-1)
             ze = (Zh * self.a_e.view(H, C)).sum(-1)
             se = knn_gather(hyperg.idx, ze, "hyperedge", "mean", transpose=transpose)
+            if self.fused_attention:
+                Y = hyperg.attention_aggregate(Z, sv, se, self.attention, self.negative_slope, heads=H)
+                return Y if self.concat else Y.view(Y.shape[0], H, C).mean(1)
             alpha = hyperg.attention(sv, se, self.attention, self.negative_slope, heads=H, dropout=self.dropout,
                                      training=self.training)
             Y = hyperg.aggregate(Z, options=self.options, weight=alpha, heads=H)
             return Y if self.concat else Y.view(Y.shape[0], H, C).mean(1)
         sv = Z @ self.a_v
         se = knn_gather(hyperg.idx, (Z @ self.a_e)[:, None].contiguous(), "hyperedge", "mean", transpose=transpose).reshape(-1)
+        if self.fused_attention:
+            return hyperg.attention_aggregate(Z, sv, se, self.attention, self.negative_slope)
         alpha = hyperg.attention(sv, se, self.attention, self.negative_slope, dropout=self.dropout, training=self.training)
         return hyperg.aggregate(Z, options=self.options, weight=alpha)
 

@@ -1307,6 +1307,58 @@ HG_API int hg_table_softmax_dropout_bwd_heads_f32(const int32_t *idx, int32_t ro
                                                   const float *alpha, const float *dout, float *ds,
                                                   float *dgroup /* may be NULL */, hg_stream_t stream);
 
+/* Fused attention aggregation over a neighbour table (csrc/hg_table_attention.hip; the statistics in csrc/hg_table_heads.hip):
+ * hg_table_softmax_heads_f32 into hg_table_gather_heads_f32 / hg_table_gather_t_heads_f32 (w = alpha) writes alpha
+ * [rows * k, heads] once and reads it in both gathers.  These entries give the same dst, bit for bit, without alpha ever
+ * existing: two numbers per (segment, head), and every coefficient formed in the gather that uses it.  One launch each on
+ * `stream`; nothing is allocated or waited for, no workspace, no atomics; all three can be recorded into a hipGraph.  float32
+ * only, no entry_score (it is itself a [rows * k, heads] array), no dropout.  heads >= 1; heads = 1 is the single-head layout
+ * and gives the plain gathers' bits on hg_table_softmax_f32's alpha.  group, the segments, node_score [n, H] and edge_score
+ * [rows, H] are the softmax section's; either score may be NULL (no addition), not both.
+ *
+ * hg_table_attention_stats_heads_f32: seg_max[seg, h] = m and seg_inv[seg, h] = 1 / s, the segment maximum of x = leaky(raw)
+ *   and the reciprocal of s = sum_seg __expf(x - m) that hg_table_softmax_heads_f32 computes for the same arguments with
+ *   entry_score = NULL, BIT FOR BIT: the same kernel stopped after its sum pass, so the SEGMENT ORDER paragraph holds word for
+ *   word -- L lanes a segment, lane l's entries l, l + L .., the xor butterfly, a VERTEX segment longer than HG_TABLE_SEQ_MAX
+ *   by its workgroup as ((w0 + w1) + w2) + w3.  seg_max and seg_inv are [rows, H] (HG_TABLE_HYPEREDGE) or [n, H]
+ *   (HG_TABLE_VERTEX).  A segment with no candidate writes +0.0, +0.0; no gather reads them.
+ * hg_table_attention_gather_heads_f32 / hg_table_attention_gather_t_heads_f32: hg_table_gather_heads_f32 /
+ *   hg_table_gather_t_heads_f32 with w[p, h] replaced, for the position p = i k + s, j = idx[p] and h = col / Ch, by
+ *     alpha(p, h) = __expf(leaky((own + other), slope) - seg_max[seg, h]) * seg_inv[seg, h]
+ *   seg = i, own = edge_score[i, h], other = node_score[j, h] under HG_TABLE_HYPEREDGE; seg = j, own = node_score[j, h], other =
+ *   edge_score[i, h] under HG_TABLE_VERTEX; the segment's own score first, an absent score no addition, leaky(x) = x > 0 ? x :
+ *   slope * x -- hg_table_softmax_f32's formula, operation for operation, on the stored m and 1 / s.
+ *   term(p, j)[col] = (src[., col] * src_scale[.]) * alpha(p, col / Ch); everything else is the heads gathers' text: the ORDER
+ *   paragraph AT THE SAME F (ascending s / q from +0.0, one rounded add a term, a vertex row longer than HG_TABLE_SEQ_MAX in
+ *   the plain call's P pieces and LDS tree), dst_scale applied last, a row with no entry exactly +0.0 whatever its scale.  An
+ *   entry of idx outside 0 .. n - 1 (of pos_v outside 0 .. rows k - 1) adds nothing and nothing is read through it.  The
+ *   transposed gather takes the vertex of a position from its destination row: (ptr_v, pos_v) must be hg_table_transpose's
+ *   of idx, which is passed for the contract and not read.
+ *   Who evaluates alpha does not change it: where 16-byte lanes share a head (Ch % 4 == 0, Ch >= 16) a wave forms the
+ *   coefficients of its rows' next entries once, in LDS, and the lanes of a head read them from there; elsewhere, and in
+ *   the long rows, a lane forms its own (csrc/hg_table_attention.hip).
+ * Refusals launch nothing, set hg_last_error.  Stats: the several-heads softmax entries' refusals in their order, a null
+ *   seg_max or seg_inv and "both scores NULL" among the null pointers.  Gathers: the heads gathers' refusals in their order --
+ *   HG_ERR_INVALID for a null idx (ptr_v, pos_v, idx), a null src or dst, rows, n or F < 1, k outside 1 .. 64, rows * k >=
+ *   2^31, heads < 1, F % heads != 0; HG_ERR_UNSUPPORTED for a pointer that is not 4-byte aligned -- and then HG_ERR_INVALID for
+ *   a null seg_max or seg_inv, for node_score and edge_score both NULL, and for a group other than the two.
+ * Detect these entries by their exported symbols (HG_AGGR_VERSION does not change). */
+HG_API int hg_table_attention_stats_heads_f32(const int32_t *idx, int32_t rows, int32_t k, int32_t n, int32_t heads,
+                                              int32_t group, const float *node_score, const float *edge_score, float slope,
+                                              const int32_t *ptr_v, const int32_t *pos_v, float *seg_max, float *seg_inv,
+                                              hg_stream_t stream);
+HG_API int hg_table_attention_gather_heads_f32(const int32_t *idx, int32_t rows, int32_t k, int32_t n, int32_t F, int32_t heads,
+                                               int32_t group, const float *src, const float *node_score,
+                                               const float *edge_score, float slope, const float *seg_max,
+                                               const float *seg_inv, const float *src_scale, const float *dst_scale,
+                                               float *dst, hg_stream_t stream);
+HG_API int hg_table_attention_gather_t_heads_f32(const int32_t *ptr_v, const int32_t *pos_v, const int32_t *idx, int32_t rows,
+                                                 int32_t k, int32_t n, int32_t F, int32_t heads, int32_t group,
+                                                 const float *src, const float *node_score, const float *edge_score,
+                                                 float slope, const float *seg_max, const float *seg_inv,
+                                                 const float *src_scale, const float *dst_scale, float *dst,
+                                                 hg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
