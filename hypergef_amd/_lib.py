@@ -65,6 +65,7 @@ SYMBOLS = (
     "hg_table_gather_heads_f32", "hg_table_gather_t_heads_f32", "hg_table_dot_heads_f32",
     "hg_table_softmax_dropout_heads_f32", "hg_table_softmax_dropout_bwd_heads_f32",
     "hg_table_attention_stats_heads_f32", "hg_table_attention_gather_heads_f32", "hg_table_attention_gather_t_heads_f32",
+    "hg_table_dot_attention_f32", "hg_table_dot_attention_bwd_f32", "hg_table_dot_attention_gather_t_f32",
 )
 HG_TABLE_HYPEREDGE = 0
 HG_TABLE_VERTEX = 1
@@ -412,6 +413,14 @@ def lib():
         L.hg_table_attention_gather_t_heads_f32.restype = ctypes.c_int
         L.hg_table_attention_gather_t_heads_f32.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, f32, vp, vp, vp,
                                                             vp, vp, vp]
+    if hasattr(L, "hg_table_dot_attention_f32"):  # likewise: dot-product attention over the table, one walk a row
+        f32 = ctypes.c_float
+        L.hg_table_dot_attention_f32.restype = ctypes.c_int
+        L.hg_table_dot_attention_f32.argtypes = [vp, i32, i32, i32, i32, i32, vp, vp, f32, f32, vp, vp, vp, vp]
+        L.hg_table_dot_attention_bwd_f32.restype = ctypes.c_int
+        L.hg_table_dot_attention_bwd_f32.argtypes = [vp, i32, i32, i32, i32, i32, vp, vp, f32, f32, vp, vp, vp, vp, vp, vp, vp]
+        L.hg_table_dot_attention_gather_t_f32.restype = ctypes.c_int
+        L.hg_table_dot_attention_gather_t_f32.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp]
     L.hg_aggr_push_groups_f32.restype = ctypes.c_int
     L.hg_aggr_push_groups_f32.argtypes = [i32, i32, i32, i64, vp, vp, vp, vp, vp, vp,
                                           vp, vp, vp, vp, vp, vp]

@@ -19,6 +19,8 @@ single-head call's bits.  `knn_softmax(dropout=p)` drops coefficients inside the
 (hg_table_softmax_dropout_*_heads_f32): a Philox mask that is never stored.
 `knn_attention_aggr` (`ops.knn_attention_aggr`; hg_table_attention_*) is `knn_aggr` on `knn_softmax`'s alpha in one call, bit
 for bit, without alpha: two statistics per segment and head, and every coefficient formed inside the gather that uses it.
+`knn_dot_attention_aggr` (`ops.knn_dot_attention_aggr`; hg_table_dot_attention_*) is dot-product attention under the hyperedge
+group: logits <query[i], X[j]>, the row softmax and hop 0 in one walk per (row, head), every member row loaded once.
 """
 import ctypes
 import numbers
@@ -1400,6 +1402,174 @@ def knn_attention_aggr(idx, X, node_score=None, edge_score=None, group="hyperedg
     return _KnnAttentionAggr.apply(X, node_score, edge_score, idx, ptr_v, pos_v, degE, degV, group, float(negative_slope), H)
 
 
+DOT_ATTENTION_CH_MAX = 256  # include/hg_aggr.h: one lane group holds a head's columns
+
+
+def _dot_attention_entry(name):
+    """An hg_table_dot_attention_* entry of the library; a build without it is an error, never another path."""
+    L = _lib.lib()
+    if not hasattr(L, name):
+        raise RuntimeError("this build of libhgaggr has no %s (dot-product attention over a neighbour table)" % name)
+    return getattr(L, name)
+
+
+def table_dot_attention(idx, n, src, query, scale, slope, dst_scale=None, heads=1, want_alpha=True):
+    """(dst [rows, F], alpha [rows, k, heads] or None) of hg_table_dot_attention_f32: logits scale <query[i], src[idx[i, s]]> per
+    head, leaky relu, softmax over the table row and the weighted sum of the same rows, one launch.  No checks, no gradient."""
+    rows, k = idx.shape
+    F = src.shape[1]
+    dst = torch.empty((rows, F), dtype=torch.float32, device=idx.device)
+    alpha = torch.empty((rows, k, heads), dtype=torch.float32, device=idx.device) if want_alpha else None
+    with torch.cuda.device(idx.device):
+        _lib.check(_dot_attention_entry("hg_table_dot_attention_f32")(
+            _ptr(idx), rows, k, n, F, heads, _ptr(query), _ptr(src), scale, slope, _ptr(dst_scale), _ptr(dst), _ptr(alpha),
+            _stream_handle(idx.device)))
+    return dst, alpha
+
+
+def table_dot_attention_bwd(idx, n, src, query, scale, slope, alpha, ddst, dalpha_ext=None, dst_scale=None, heads=1):
+    """(dquery [rows, F], ds [rows, k, heads]) of hg_table_dot_attention_bwd_f32 for the forward's alpha, the gradient ddst of
+    its dst and the gradient dalpha_ext that reaches alpha from elsewhere (None: none).  No checks, no gradient."""
+    rows, k = idx.shape
+    F = src.shape[1]
+    dquery = torch.empty((rows, F), dtype=torch.float32, device=idx.device)
+    ds = torch.empty((rows, k, heads), dtype=torch.float32, device=idx.device)
+    with torch.cuda.device(idx.device):
+        _lib.check(_dot_attention_entry("hg_table_dot_attention_bwd_f32")(
+            _ptr(idx), rows, k, n, F, heads, _ptr(query), _ptr(src), scale, slope, _ptr(dst_scale), _ptr(alpha), _ptr(ddst),
+            _ptr(dalpha_ext), _ptr(dquery), _ptr(ds), _stream_handle(idx.device)))
+    return dquery, ds
+
+
+def table_dot_attention_gather_t(ptr_v, pos_v, k, src, w, src_scale=None, dst_scale=None, heads=1, src2=None, w2=None):
+    """dst [n, F] of hg_table_dot_attention_gather_t_f32: dst[v, head h] = dst_scale[v] sum_q ((src[i] src_scale[i]) w[p, h] +
+    src2[i] w2[p, h]), p = pos_v[q], i = p // k, one lane group per (vertex, head) summing in ascending q whatever the row's
+    length -- so a head's bits do not depend on F or heads.  src, src2 [rows, F]; w, w2 [rows * k, heads].  No checks, no gradient."""
+    rows, F = src.shape
+    n = ptr_v.shape[0] - 1
+    dst = torch.empty((n, F), dtype=torch.float32, device=src.device)
+    with torch.cuda.device(src.device):
+        _lib.check(_dot_attention_entry("hg_table_dot_attention_gather_t_f32")(
+            _ptr(ptr_v), _ptr(pos_v), rows, k, n, F, heads, _ptr(src), _ptr(w), _ptr(src_scale), _ptr(src2), _ptr(w2),
+            _ptr(dst_scale), _ptr(dst), _stream_handle(src.device)))
+    return dst
+
+
+class _KnnDotAttentionAggr(torch.autograd.Function):
+    """Y = degV . H_alpha (degE . (H_alpha^T X)) with alpha the row softmax of scale <query[i], X[j]> per head.  Forward: the
+    fused kernel (E and alpha in one launch) and hop 1 per (vertex, head), hg_table_dot_attention_gather_t_f32.  Backward: dE
+    and hop 1's dalpha from the existing gather and dot, the fused backward kernel (dquery and ds), and dX = the value path +
+    the key path, one launch of the hop-1 kernel with two sources.  Saves X, query, the table, its transpose, the scales, alpha [rows, k, H] and E [rows, F] -- nothing of
+    rows * k * F elements."""
+
+    @staticmethod
+    def forward(ctx, X, query, idx, ptr_v, pos_v, degE, degV, scale, slope, heads):
+        ctx.scale, ctx.slope, ctx.heads = scale, slope, heads
+        E, alpha = table_dot_attention(idx, X.shape[0], X, query, scale, slope, degE, heads)
+        Y = table_dot_attention_gather_t(ptr_v, pos_v, idx.shape[1], E, alpha, None, degV, heads)
+        ctx.save_for_backward(X, query, idx, ptr_v, pos_v, degE, degV, alpha, E)
+        ctx.mark_non_differentiable(alpha)
+        return Y, alpha
+
+    @staticmethod
+    def backward(ctx, dY, _):
+        X, query, idx, ptr_v, pos_v, degE, degV, alpha, E = ctx.saved_tensors
+        dY = dY.contiguous()
+        k, H = idx.shape[1], ctx.heads
+        need_x, need_q = ctx.needs_input_grad[:2]
+        dE = table_gather(idx, dY, alpha, degV, None, heads=H)
+        dalpha_ext = table_dot(idx, dY, E, degV, heads=H)
+        dquery, ds = table_dot_attention_bwd(idx, X.shape[0], X, query, ctx.scale, ctx.slope, alpha, dE, dalpha_ext, degE, H)
+        dX = None
+        if need_x:
+            dX = table_dot_attention_gather_t(ptr_v, pos_v, k, dE, alpha, degE, None, H, query, ds)
+        return (dX, dquery if need_q else None, *(None,) * 8)
+
+
+def knn_dot_attention_aggr(idx, X, query, negative_slope=1.0, scale=None, degE=None, degV=None, transpose=None, heads=1,
+                           return_alpha=False):
+    """Dot-product attention's aggregation over a neighbour table, hyperedge group: with j = idx[i, s], Ch = F / heads,
+        t[i, s, h] = scale <query[i, head h], X[j, head h]>,   a = t if t > 0 else negative_slope t,
+        alpha[i, :, h] = softmax of a over row i's candidates (0 <= j < n; no candidate: +0.0),
+        E[i, head h] = degE[i] sum_s alpha[i, s, h] X[j, head h],   Y[v, head h] = degV[v] sum_{p: idx[p] = v} alpha[p, h] E[p // k, head h]
+    -- HypergraphAttnConv(score='dot', group='hyperedge')'s formula on the table, query the hyperedges' keys.  idx [rows, k]
+    int32; X [n, F] and query [rows, F] float32; scale: a number (default Ch ** -0.5); negative_slope = 1.0 is the plain softmax
+    of the logits; degE [rows] or [rows, 1], degV [n] or [n, 1] or None; transpose: ops.knn_transpose(idx, n) to reuse.  Returns
+    Y [n, F], and with return_alpha=True (Y, alpha) with alpha [rows, k] or [rows, k, heads], detached.
+    Forward: one launch of hg_table_dot_attention_f32 (csrc/hg_table_dot_attention.hip) -- a lane group per (row, head) forms
+    the logits, an online softmax and the weighted sum in one walk over the row, every member row of X loaded once -- and hop 1,
+    hg_table_dot_attention_gather_t_f32: a lane group per (vertex, head), ascending whatever the row's length, so head h of Y
+    (and of alpha) is the single-head call on head h's columns, bit for bit.  Gradients are exact for X (through both hops and
+    through the logits) and query: the existing gather and dot give hop 1's share, hg_table_dot_attention_bwd_f32 dquery and the
+    logits' gradient, one two-source launch of the hop-1 kernel dX.  Saved for the backward: alpha and E, nothing of rows * k * F elements.  degE and degV get no
+    gradient.  Deterministic: every sum's order is include/hg_aggr.h's, two calls give the same bits.  Nothing waits, nothing is
+    read back, nothing is allocated outside torch.
+    Hub-heavy tables: hop 1 and the dX launch give a vertex to one lane group, which walks the vertex's entries serially (that is
+    what makes a head's bits independent of F and heads).  A vertex named by hundreds of rows is the launch's tail -- measured at
+    k = 10, in-degrees of 184-305 make the call 1.1-1.4x slower than the composed path at N = 50000 -- and a table with in-degrees
+    in the thousands was not measured: ops.knn_softmax(entry_score=) and ops.knn_aggr spread such a row over a workgroup (profiles/r29_table_dot_attention.md).
+    X, query and the gradient of Y must share their 16-byte alignment for the forward and backward to pick the same lane width c
+    (torch's allocations do).
+    Only the hyperedge group exists (the vertex group has no row-local softmax: compose ops.knn_softmax(entry_score=) and
+    ops.knn_aggr).  float32 only, no dropout; Ch <= 256.
+    Refusals, in this order and before a device is touched: TypeError for an idx (ptr_v, pos_v) that is not int32, for an X,
+    query, degE or degV that is not float32 and for a scale that is neither a number nor a tensor; ValueError for heads, for the
+    shapes and k, for F no multiple of heads, for Ch > 256, for a query that is not [rows, F]; RuntimeError for a scale, degE or
+    degV that requires a gradient, and for CPU tensors.  A build of the library without the entries raises RuntimeError."""
+    _table_shape(idx)
+    _check_dtype(X, "X", torch.float32, " (knn_dot_attention_aggr has no bfloat16, float16 or float64 form)")
+    _check_dtype(query, "query", torch.float32)
+    scales = (("degE", degE), ("degV", degV))
+    for name, t in scales:
+        if t is not None:
+            _check_dtype(t, name, torch.float32)
+    if scale is not None and not isinstance(scale, torch.Tensor) and (isinstance(scale, bool) or not isinstance(scale, numbers.Real)):
+        raise TypeError("scale must be None or a number, got %s" % (type(scale),))
+    _check_transpose_types(transpose)
+    H = _heads_value(heads)
+    rows, k = _table_shape_values(idx)
+    if X.dim() != 2 or X.shape[0] < 1 or X.shape[1] < 1:
+        raise ValueError("X must be [n >= 1, F >= 1], got %s" % (tuple(X.shape),))
+    n, F = X.shape
+    if F % H:
+        raise ValueError("X has F = %d columns, no multiple of heads = %d" % (F, H))
+    if F // H > DOT_ATTENTION_CH_MAX:
+        raise ValueError("F / heads = %d columns a head, above %d (hg_table_dot_attention_f32 holds a head in one lane group)"
+                         % (F // H, DOT_ATTENTION_CH_MAX))
+    if tuple(query.shape) != (rows, F):
+        raise ValueError("query must be [rows, F] = [%d, %d], got %s" % (rows, F, tuple(query.shape)))
+    for name, t, count in (("degE", degE, rows), ("degV", degV, n)):
+        if t is not None and tuple(t.shape) not in ((count,), (count, 1)):
+            raise ValueError("%s must be [%d] or [%d, 1], got %s" % (name, count, count, tuple(t.shape)))
+    if isinstance(scale, torch.Tensor) and scale.numel() != 1:
+        raise ValueError("scale must be one number, got a tensor of %s" % (tuple(scale.shape),))
+    _check_transpose_shapes(transpose, n, rows * k)
+    if isinstance(scale, torch.Tensor) and (scale.requires_grad or scale.is_cuda):
+        raise RuntimeError("scale gets no gradient from knn_dot_attention_aggr and is a host number: pass float(scale)")
+    if torch.is_grad_enabled():
+        for name, t in scales:
+            if t is not None and t.requires_grad:
+                raise RuntimeError("%s gets no gradient from knn_dot_attention_aggr: pass %s.detach()" % (name, name))
+    _check_table_index(idx, "idx")
+    _check_feat(X, "X", device=idx.device)
+    _check_feat(query, "query", device=idx.device)
+    for name, t in scales:
+        if t is not None:
+            _check_feat(t, name, device=idx.device)
+    _dot_attention_entry("hg_table_dot_attention_bwd_f32")
+    if transpose is None:
+        transpose = knn_transpose(idx, n)
+    ptr_v, pos_v = transpose
+    _check_table_index(ptr_v, "ptr_v")
+    _check_table_index(pos_v, "pos_v")
+    degE, degV = (None if t is None else t.detach() for _, t in scales)
+    scale = float(F // H) ** -0.5 if scale is None else float(scale)
+    Y, alpha = _KnnDotAttentionAggr.apply(X, query, idx, ptr_v, pos_v, degE, degV, scale, float(negative_slope), H)
+    if return_alpha:
+        return Y, (alpha if H > 1 else alpha.view(rows, k))
+    return Y
+
+
 class KnnHypergraph:
     """The hypergraph "each vertex and its k - 1 nearest neighbours" as a device-only object: what HyperGraph.from_knn builds,
     without the read-back, the host transpose and the plan.  Nothing here reads a tensor back; with segments=None nothing
@@ -1422,6 +1592,8 @@ class KnnHypergraph:
       attention_aggregate(Z, node_score, edge_score, group="hyperedge", negative_slope=0.2, heads=1): ops.knn_attention_aggr
         with the stored table, transpose and degrees -- aggregate(Z, weight=attention(..), heads=heads), bit for bit, with no
         [N, k, heads] array in the forward or kept for the backward.
+      dot_attention_aggregate(Z, query, negative_slope=1.0, heads=1): ops.knn_dot_attention_aggr with the stored table,
+        transpose and degrees -- dot-product attention of every hyperedge's query row [N, F] to its members' rows of Z.
     form: ops.knn's -- "dot" and "dot_split" give the same idx and dist through a matrix-unit prefilter, and their own mean.  Under "dot" X
     may be bfloat16: the table, dist, mean, transpose and degrees are int32 / float32 as always, and aggregate / weights take
     bfloat16 Z / X where `options` (or the caller's) has Options.incidence_bf16 = 'rows' -- ops.knn_aggr's and ops.knn_dist's
@@ -1472,6 +1644,10 @@ class KnnHypergraph:
     def attention_aggregate(self, Z, node_score=None, edge_score=None, group="hyperedge", negative_slope=0.2, heads=1):
         return knn_attention_aggr(self.idx, Z, node_score, edge_score, group, negative_slope, self.degE, self.degV,
                                   transpose=(self.ptr_v, self.pos_v), heads=heads)
+
+    def dot_attention_aggregate(self, Z, query, negative_slope=1.0, heads=1):
+        return knn_dot_attention_aggr(self.idx, Z, query, negative_slope, None, self.degE, self.degV,
+                                      transpose=(self.ptr_v, self.pos_v), heads=heads)
 
 
 def table_seq_max():

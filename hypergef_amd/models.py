@@ -200,12 +200,39 @@ class DynamicHypergraphConv(nn.Module):
     (hg_table_attention_*), so alpha [N, k, H] is neither written in the forward nor kept for the backward.  The same
     parameters, the same state_dict, and the same output and gradients, bit for bit; still nothing waits and the layer is
     still recorded into a hipGraph.  Attention dropout is the unfused path's (ValueError here).  False (the default) is the
-    layer above, untouched."""
+    layer above, untouched.
+    score = 'dot' (needs attention='hyperedge', device_graph=True, dropout = 0.0 and fused_attention=False):
+    HypergraphAttnConv(score='dot', group='hyperedge') without bias on a hypergraph rebuilt every forward -- no a_v / a_e but a
+    second bias-free linear lin_k (in_channels -> H * out_channels), and
+        Z = lin(X),   Ke = ops.knn_gather(idx, lin_k(X), 'hyperedge', 'mean'),
+        Y = hyperg.dot_attention_aggregate(Z, Ke, negative_slope, heads)            (ops.knn_dot_attention_aggr),
+    logit[(e, u), h] = <Z[u, head h], Ke[e, head h]> * out_channels ** -0.5, softmax of its leaky relu over each hyperedge,
+    formed with hop 0 in one launch (hg_table_dot_attention_f32).  Parameters: lin.weight and lin_k.weight.  With segments=None
+    or set_rows the layer still waits nowhere and is recorded into a hipGraph.  float32 only.  attention='vertex' raises
+    ValueError: the operator serves the hyperedge group alone.  score = 'additive' (the default) is the layer above: same
+    bits, same state_dict."""
 
     def __init__(self, in_channels, out_channels, k, probabilistic=False, segments=None, m_prob=1.0, options=None,
                  device_graph=False, knn_form="difference", learn_distances=False, first_aggr="sum", second_aggr="sum",
-                 attention=None, negative_slope=0.2, heads=1, concat=True, set_rows=None, dropout=0.0, fused_attention=False):
+                 attention=None, negative_slope=0.2, heads=1, concat=True, set_rows=None, dropout=0.0, fused_attention=False,
+                 score="additive"):
         super().__init__()
+        if score not in ("additive", "dot"):
+            raise ValueError("score must be 'additive' or 'dot', got %r" % (score,))
+        self.score = score
+        if score == "dot":
+            if attention == "vertex":
+                raise ValueError("score='dot' needs attention='hyperedge': ops.knn_dot_attention_aggr serves the hyperedge group "
+                                 "alone (the vertex group has no row-local softmax)")
+            if attention != "hyperedge":
+                raise ValueError("score='dot' needs attention='hyperedge', got %r" % (attention,))
+            if not device_graph:
+                raise ValueError("score='dot' needs device_graph=True (ops.knn_dot_attention_aggr runs over the device table; on "
+                                 "a planned hypergraph use HypergraphAttnConv(score='dot'))")
+            if ops._dropout_p(dropout) > 0.0:
+                raise ValueError("score='dot' has no attention dropout: dropout=%r needs score='additive'" % (dropout,))
+            if fused_attention:
+                raise ValueError("score='dot' needs fused_attention=False (that flag fuses the additive scores' coefficients)")
         self.dropout = ops._dropout_p(dropout)
         if self.dropout > 0.0 and attention is None:
             raise ValueError("dropout=%r needs attention='hyperedge' or 'vertex' (it drops attention coefficients)" % (dropout,))
@@ -254,6 +281,9 @@ class DynamicHypergraphConv(nn.Module):
                                  "and %r" % (attention, first_aggr, second_aggr))
             if probabilistic:
                 raise ValueError("attention=%r needs probabilistic=False (the coefficients are the table's weights)" % (attention,))
+            if score == "dot":
+                self.lin_k = ops.Linear(in_channels, heads * out_channels, bias=False, options=options)
+                return
             bound = math.sqrt(6.0 / (out_channels + 1))
             self.a_v = nn.Parameter(torch.empty(heads * out_channels).uniform_(-bound, bound))
             self.a_e = nn.Parameter(torch.empty(heads * out_channels).uniform_(-bound, bound))
@@ -265,6 +295,11 @@ class DynamicHypergraphConv(nn.Module):
         hyperg = self.hyperg = KnnHypergraph.build(X, self.k, segments=self.segments, form=self.knn_form, set_rows=self.set_rows)
         Z = self.lin(X)
         transpose = (hyperg.ptr_v, hyperg.pos_v)
+        if self.score == "dot":
+            H, C = self.heads, self.out_channels
+            Ke = knn_gather(hyperg.idx, self.lin_k(X), "hyperedge", "mean", transpose=transpose)
+            Y = hyperg.dot_attention_aggregate(Z, Ke, self.negative_slope, heads=H)
+            return Y if self.concat or H == 1 else Y.view(Y.shape[0], H, C).mean(1)
         if self.heads > 1:
             H, C = self.heads, self.out_channels
             Zh = Z.view(Z.shape[0], H, C)

@@ -1359,6 +1359,76 @@ HG_API int hg_table_attention_gather_t_heads_f32(const int32_t *ptr_v, const int
                                                  const float *src_scale, const float *dst_scale, float *dst,
                                                  hg_stream_t stream);
 
+/* Dot-product attention over a neighbour table, hyperedge group (csrc/hg_table_dot_attention.hip): logits, softmax and hop 0
+ * of the aggregation in one launch, a member row of src loaded once.  With j = idx[i, s], head h the columns h Ch .. (h + 1) Ch -
+ * 1, Ch = F / heads, and the candidates of row i the entries with 0 <= j < n:
+ *     t[i, s, h]     = scale * <query[i, head h], src[j, head h]>
+ *     a              = t > 0 ? t : slope * t                       (slope = 1: the plain softmax of the logits)
+ *     alpha[i, :, h] = softmax of a over the row's candidates      (no candidate: +0.0; a row with none: all +0.0)
+ *     dst[i, head h] = dst_scale[i] * sum_s alpha[i, s, h] * src[j, head h]
+ * idx [rows, k], query and dst [rows, F], src [n, F], dst_scale [rows] or NULL (no multiplication), alpha [rows, k, heads] or
+ * NULL (not written).  Only the hyperedge group exists: the segment is the table row.  One launch on `stream`; no workspace, no
+ * atomics, no LDS, nothing allocated or waited for; both entries can be recorded into a hipGraph.  float32 only.
+ * UNITS: one (row, head) is owned by Gp lanes, Gp = the power of two at or above min(ceil(Ch / c), 64); c = 4 (lane g owns the
+ *   columns 4 g .. 4 g + 3 of the head) where Ch % 4 == 0 and query, src and dst (backward: query, src, ddst, dquery) are 16-byte
+ *   aligned, else c = 1 (lane g owns the columns g, g + Gp, g + 2 Gp, g + 3 Gp below Ch).  Ch <= 256 either way; a wider head
+ *   is HG_ERR_UNSUPPORTED.
+ * ATTENTION ORDER (forward): per entry, lane g runs p = fma(query[i, x], src[j, x], p) over its columns x ascending from +0.0;
+ *   p[g] = p[g] + p[g xor o] for o = Gp / 2, Gp / 4 .. 1, every lane at once; t = scale * p[0], a = t > 0 ? t : slope * t (two
+ *   roundings).  The candidates are then folded in ascending s: the first sets m = a, l = 1, acc = src[j]; every later one
+ *   m' = max(m, a), corr = __expf(m - m'), e = __expf(a - m'), l = l * corr + e, acc[x] = acc[x] * corr + e * src[j, x]
+ *   (each product and each add rounded, no fma), m = m'.  dst[i, x] = dst_scale[i] * (acc[x] * (1 / l)); a row with no
+ *   candidate stores +0.0 whatever its scale.  alpha[i, s, h] = __expf(a - m) * (1 / l) with the final m and l.
+ * ATTENTION ORDER (backward, hg_table_dot_attention_bwd_f32): g[x] = dst_scale[i] * ddst[i, x]; per entry pg = the chain and
+ *   butterfly above on (g, src[j]) and, where slope != 1, t on (query[i], src[j]) as in the forward; dalpha = pg +
+ *   dalpha_ext[i, s, h] (dalpha_ext NULL: no addition); D = sum over the candidates, ascending s from +0.0, of alpha * dalpha
+ *   (product rounded, one rounded add);
+ *     ds[i, s, h] = ((alpha * (dalpha - D)) * (t > 0 ? 1 : slope)) * scale            (+0.0 for an entry that is no candidate)
+ *     dquery[i, x] = sum over the candidates, ascending s from +0.0, of ds[i, s, h] * src[j, x]
+ *   Two walks over the row (D first); both form dalpha by the same operations, so by the same bits.  With alpha and dst of the
+ *   forward, ddst the gradient of dst and dalpha_ext the gradient that reaches alpha from elsewhere (hop 1), ds is the
+ *   gradient of the product <query[i, head h], src[j, head h]> (the scale is folded in), so src's gradient is
+ *   hg_table_dot_attention_gather_t_f32(src = ddst, w = alpha, src_scale = dst_scale, src2 = query, w2 = ds): the value path
+ *   and the key path.
+ * So two calls give the same bits; the bits of a row depend on the row's entries, the rows they name, query[i], the scales,
+ * F, heads and the alignment alone -- not on rows or on where the row stands; and head h of an H-head call equals the
+ * single-head call on contiguous copies of head h's columns, bit for bit, at equal c.
+ * Refusals launch nothing, set hg_last_error, in this order: HG_ERR_INVALID for a null idx, then a null query, src or dst
+ *   (backward: query, src, alpha, ddst, dquery or ds), for rows, n or F < 1, k outside 1 .. 64, rows * k >= 2^31, heads < 1,
+ *   F % heads != 0; HG_ERR_UNSUPPORTED for Ch > 256 and for a pointer that is not 4-byte aligned.
+ * Not covered: the vertex group, a value array distinct from src, dropout, bfloat16, Ch > 256.
+ * Detect these entries by their exported symbols (HG_AGGR_VERSION does not change). */
+HG_API int hg_table_dot_attention_f32(const int32_t *idx, int32_t rows, int32_t k, int32_t n, int32_t F, int32_t heads,
+                                      const float *query, const float *src, float scale, float slope,
+                                      const float *dst_scale /* may be NULL */, float *dst, float *alpha /* may be NULL */,
+                                      hg_stream_t stream);
+HG_API int hg_table_dot_attention_bwd_f32(const int32_t *idx, int32_t rows, int32_t k, int32_t n, int32_t F, int32_t heads,
+                                          const float *query, const float *src, float scale, float slope,
+                                          const float *dst_scale /* may be NULL */, const float *alpha, const float *ddst,
+                                          const float *dalpha_ext /* may be NULL */, float *dquery, float *ds,
+                                          hg_stream_t stream);
+/* hg_table_dot_attention_gather_t_f32: hop 1 of the same operator and the two gathers of its dX, one launch.  For the transpose
+ * (ptr_v [n + 1], pos_v [rows k]) of the table, p = pos_v[q], i = p / k:
+ *     dst[v, head h] = dst_scale[v] * sum_q ((src[i, head h] * src_scale[i]) * w[p, h] + src2[i, head h] * w2[p, h])
+ * q = ptr_v[v] .. ptr_v[v + 1] - 1; src, src2 [rows, F], w, w2 [rows k, heads], dst [n, F]; src_scale [rows] and dst_scale [n]
+ * may be NULL (no multiplication); src2 and w2 are both NULL (no second term) or both given.  A position outside 0 .. rows k - 1
+ * adds nothing; a vertex with no entry is +0.0 whatever its scale.
+ * HOP 1 ORDER: the UNITS paragraph with (vertex, head) for (row, head).  A unit sums its vertex row in ascending q from +0.0,
+ *   WHATEVER ITS LENGTH -- no pieces, no tree, no HG_TABLE_SEQ_MAX: acc = acc + (src * src_scale) * w (each product rounded, one
+ *   rounded add), then acc = acc + src2 * w2 likewise, entry by entry; dst_scale last.  So the bits of dst[v, head h] depend on
+ *   the vertex row, the rows and weights it names and the scales alone, not on F, heads or n: head h of an H-head call is the
+ *   single-head call on contiguous copies of head h's columns (w[:, h]), bit for bit, at equal c -- which
+ *   hg_table_gather_t_heads_f32, whose long rows are cut by the call's F, does not give.  A hub vertex is one lane group's
+ *   serial walk: this entry serves the attention operator's contract, not the fastest sum of a long row.
+ * Refusals launch nothing, in this order: HG_ERR_INVALID for a null ptr_v or pos_v, a null src, w or dst, src2 without w2 or
+ *   w2 without src2, then the sizes, heads and F % heads as above; HG_ERR_UNSUPPORTED for Ch > 256 and for a pointer that is not
+ *   4-byte aligned. */
+HG_API int hg_table_dot_attention_gather_t_f32(const int32_t *ptr_v, const int32_t *pos_v, int32_t rows, int32_t k, int32_t n,
+                                               int32_t F, int32_t heads, const float *src, const float *w,
+                                               const float *src_scale /* may be NULL */, const float *src2 /* may be NULL */,
+                                               const float *w2 /* may be NULL */, const float *dst_scale /* may be NULL */,
+                                               float *dst, hg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
